@@ -5,7 +5,7 @@ Workload (BASELINE.json metric "Msamples/sec at 1920x1080x1024spp", config C4): 
 documented 871 400-triangle stand-in for the missing dragon.obj.scene, 1920x1080, 1024 spp, max depth 16, black
 environment (intensity 0), light from the 'areaLight' quad.  One "step" = one complete frame.
 
-  python bench.py [--gpus N --steps K --warmup W]           # N = 1
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]           # N = 1
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 N > 1: one process per GPU; every rank holds a scene replica and renders the pixel tiles it owns (16x16 tiles dealt
@@ -16,9 +16,14 @@ the barrier, the max over ranks and the per-rank timing table - so the only RCCL
 loads (PT_RCCL_PATH overrides which).  Total work is fixed => "strong".
 
 Timed span of a step: pt_render = kernels + reduce + D2H of the complete float3 frame into pinned host memory on
-rank 0.  After the timed loop every rank checks that no watchdog fired and rank 0 checks the frame against the checksum of the
-parity-tested image (tests/golden/c4_frame_crc.json; `--write-golden` regenerates it, tests/test_gpu_parity.py pins the same
-render against the oracle).  Prints one JSON line on rank 0.
+rank 0.  After the timed loop every rank checks that no watchdog fired.  Prints one JSON line on rank 0.
+
+A plain run does only what the headline needs: set up, warm up, time K steps, print.  `--dump-outputs DIR` then writes the frame of
+the last timed step (what a caller of pt_render receives) as DIR/frame.npy, float32 H x W x 3; the inputs are fixed, so two builds
+can be compared output for output.  `--full` adds everything else, as before: the counted renders and the `roofline` block
+(SURVEY 8(d) algorithmic bytes, the committed PMC summary), the check of the frame against the checksum of the parity-tested image
+(tests/golden/c4_frame_crc.json; `--write-golden` regenerates it, tests/test_gpu_parity.py pins the same render against the oracle)
+and, on one GPU, the CPU baseline (`--no-cpu-baseline` leaves it out).
 """
 import argparse
 import json
@@ -46,35 +51,11 @@ def build_workload():
     from owl_path_tracer_amd.pyhost import procedural, scene_io
 
     _, mats = scene_io.parse_scene(os.path.join(ROOT, "assets", "dragon.json"))
-    meshes = _cached("dragon_standin", procedural.dragon_standin)
+    # generated on every run (deterministic, well under a second): no cache outside the repository that could outlive a change
+    # of the generator
+    meshes = procedural.dragon_standin()
     ents = scene_io.build_entities(meshes, mats)
     return scene_io, mats, ents
-
-
-def _cached(name, make):
-    """The stand-in takes ~17 s to generate in numpy; profiling runs start bench.py eight times on one box: keep the arrays in /tmp
-    (deterministic generator; nothing is read from the repository or the network)."""
-    path = "/tmp/ptamd_bench_%s_%d.npz" % (name, os.getuid())
-    try:
-        if os.path.exists(path):
-            z = np.load(path, allow_pickle=False)
-            return [(str(n), dict(vertices=z["v%d" % i], normals=z["n%d" % i], texcoords=z["t%d" % i], indices=z["i%d" % i])) for i, n in enumerate(z["names"])]
-    except Exception:  # unreadable cache (another user's file, a stale format): generate
-        pass
-    ms = make()
-    tmp = "%s.%d.tmp.npz" % (path, os.getpid())  # the N ranks of one node write side by side: a name of its own each, then an atomic rename
-    try:
-        d = {"names": np.array([n for n, _ in ms])}
-        for i, (_, m) in enumerate(ms):
-            d["v%d" % i], d["n%d" % i], d["t%d" % i], d["i%d" % i] = m["vertices"], m["normals"], m["texcoords"], m["indices"]
-        np.savez(tmp, **d)
-        os.replace(tmp, path)
-    except Exception:
-        try:
-            os.remove(tmp)
-        except OSError:
-            pass
-    return ms
 
 
 def algorithmic_bytes(st, n_pixels_out, textured_scatters=0):
@@ -165,9 +146,13 @@ def main():
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--spp-per-launch", type=int, default=0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
     ap.add_argument("--write-golden", action="store_true", help="store the checksum of this run's frame as the expected one (after the parity tests passed)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the frame of the last timed step as DIR/frame.npy (float32, H x W x 3)")
+    ap.add_argument("--full", action="store_true", help="also the counted renders and roofline, the golden-checksum check and the CPU baseline")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
 
     import torch
     import torch.distributed as dist
@@ -218,19 +203,20 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # instrumented passes (untimed): work counters for the algorithmic-bytes figure - of this build's walk (records as fetched: a
-    # quad node = two 64-byte units, an oct node of the sparse-wave group walk = four) and of the plain binary walk of the same tree
-    # (one 64-byte node per visit, leaves of <= 4 triangles: SURVEY 8(d)'s unit, independent of how this build packs its records)
-    ctx.set_option("count", 1)
-    step()
-    cst = ctx.stats()
-    for k, v in (("quad", 0), ("groups", 0)):
-        ctx.set_option(k, v)
-    step()
-    cst_bin = ctx.stats()
-    for k, v in (("quad", 1), ("groups", 1)):
-        ctx.set_option(k, v)
-    ctx.set_option("count", 0)
+    if args.full:
+        # instrumented passes (untimed): work counters for the algorithmic-bytes figure - of this build's walk (records as fetched: a
+        # quad node = two 64-byte units, an oct node of the sparse-wave group walk = four) and of the plain binary walk of the same tree
+        # (one 64-byte node per visit, leaves of <= 4 triangles: SURVEY 8(d)'s unit, independent of how this build packs its records)
+        ctx.set_option("count", 1)
+        step()
+        cst = ctx.stats()
+        for k, v in (("quad", 0), ("groups", 0)):
+            ctx.set_option(k, v)
+        step()
+        cst_bin = ctx.stats()
+        for k, v in (("quad", 1), ("groups", 1)):
+            ctx.set_option(k, v)
+        ctx.set_option("count", 0)
     own_pixels = int(B.shard_pixels(W, H, D.TILE, rank, world).size)
 
     for _ in range(args.warmup):
@@ -253,7 +239,9 @@ def main():
     med_ms = float(np.median(step_ms))
     # what each rank spent where (medians over the timed steps): explains a scaling curve without another run
     mine = {"rank": rank, "pixels": own_pixels, "kernel_ms": round(float(np.median(kernel_ms)), 3), "reduce_ms": round(float(np.median(reduce_ms)), 3),
-            "d2h_ms": round(float(np.median(d2h_ms)), 3), "step_ms": round(med_ms, 3), "rays": int(cst["rays"])}
+            "d2h_ms": round(float(np.median(d2h_ms)), 3), "step_ms": round(med_ms, 3)}
+    if args.full:
+        mine["rays"] = int(cst["rays"])
     per_rank = [mine]
     if world > 1:
         t = torch.tensor([elapsed, med_ms], dtype=torch.float64)  # CPU tensor: gloo
@@ -263,8 +251,12 @@ def main():
         dist.all_gather_object(per_rank, mine)
     st = ctx.stats()
 
-    crc = frame_crc(frame.rgb) if rank == 0 else None
-    if rank == 0:
+    if rank == 0 and args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "frame.npy"), np.array(frame.rgb, np.float32))  # a copy: the pinned buffer is freed below
+
+    if rank == 0 and (args.write_golden or args.full):
+        crc = frame_crc(frame.rgb)
         if args.write_golden:
             with open(GOLDEN_CRC, "w") as f:
                 json.dump({"workload": "C4 stand-in 1920x1080x1024spp depth 16 (bench.py)", "crc32_float3_frame": crc, "provenance": "bench.py --write-golden (re-run the opt-in whole-frame oracle comparison to tie it to the oracle again)",
@@ -277,23 +269,7 @@ def main():
             frame_check = "crc32 %08x == tests/golden/c4_frame_crc.json" % crc
 
     if rank == 0:
-        launches = max(1, st["launches"])
-        k_ms = float(np.median(kernel_ms))  # per frame on this rank
-        p_ms = float(np.median(prepass_ms))  # of which: cost pre-pass launch (PREPASS_SPP samples per pixel) + queue sort
-        alg_frame = algorithmic_bytes(cst, own_pixels)  # this rank's frame, both launches
-        # The dominant kernel launch is the main one (launch 2 of 2 per frame): samples PREPASS_SPP.. of every pixel.  Counted work
-        # is per frame; per-sample work does not depend on the sample index, so the main launch carries (SPP - PREPASS_SPP) / SPP.
-        pre_spp = int(st.get("prepass_spp", 0)) or PREPASS_SPP
-        main_share = (SPP - pre_spp) / SPP if launches > 1 else 1.0
-        alg_bytes = alg_frame * main_share
-        main_ms = k_ms - p_ms
-        achieved = alg_bytes / (main_ms * 1e-3) / 1e9
-        alg_bin = algorithmic_bytes(cst_bin, own_pixels) * main_share  # binary-visit equivalents of the same rays
-        achieved_bin = alg_bin / (main_ms * 1e-3) / 1e9
         samples = W * H * SPP * args.steps
-        pmc = measured_pmc(world)
-        pmc_traffic = int(pmc["traffic_bytes_per_launch"]) if pmc else None
-        pmc_binding = pmc.get("binding") if pmc else None
         out = {
             "metric": "Msamples/sec at 1920x1080x1024spp",
             "value": round(samples / elapsed / 1e6, 2),
@@ -304,7 +280,6 @@ def main():
             "ms_per_step": round(elapsed / args.steps * 1e3, 3),
             "ms_per_step_median": round(med_ms, 3),
             "timed_span": "pt_render: kernels + RCCL reduce (N > 1) + D2H of the float3 frame into pinned host memory on rank 0",
-            "frame_check": frame_check,
             "higher_is_better": True,
             "scaling": "strong",
             "vs_baseline": None,
@@ -315,33 +290,51 @@ def main():
                        "tiles": "%dx%d round-robin over %d rank(s), one RCCL reduce of the float3 framebuffer inside the library (pt_comm_init_rank)" % (D.TILE, D.TILE, world),
                        "kernel": "wavefront-scheduled megakernel; per frame: cost pre-pass launch (%d spp) + queue sort + one persistent main launch" % (int(st.get("prepass_spp", 0)) or PREPASS_SPP), "triangles": int(st["n_triangles"]), "bvh_nodes": int(st["bvh_nodes"]),
                        "bvh_depth": int(st["bvh_depth"])},
+        }
+        if args.full:
+            out["frame_check"] = frame_check
+            launches = max(1, st["launches"])
+            k_ms = float(np.median(kernel_ms))  # per frame on this rank
+            p_ms = float(np.median(prepass_ms))  # of which: cost pre-pass launch (PREPASS_SPP samples per pixel) + queue sort
+            alg_frame = algorithmic_bytes(cst, own_pixels)  # this rank's frame, both launches
+            # The dominant kernel launch is the main one (launch 2 of 2 per frame): samples PREPASS_SPP.. of every pixel.  Counted work
+            # is per frame; per-sample work does not depend on the sample index, so the main launch carries (SPP - PREPASS_SPP) / SPP.
+            pre_spp = int(st.get("prepass_spp", 0)) or PREPASS_SPP
+            main_share = (SPP - pre_spp) / SPP if launches > 1 else 1.0
+            alg_bytes = alg_frame * main_share
+            main_ms = k_ms - p_ms
+            achieved = alg_bytes / (main_ms * 1e-3) / 1e9
+            alg_bin = algorithmic_bytes(cst_bin, own_pixels) * main_share  # binary-visit equivalents of the same rays
+            achieved_bin = alg_bin / (main_ms * 1e-3) / 1e9
+            pmc = measured_pmc(world)
+            pmc_traffic = int(pmc["traffic_bytes_per_launch"]) if pmc else None
+            pmc_binding = pmc.get("binding") if pmc else None
             # `achieved` = algorithmic bytes in ITS unit - 64 B per BVH2 node visit (the rays of this frame counted as a plain
             # binary walk of the same tree by the instrumented instance), 36 B per triangle test, 152 B per scatter, 12 B per pixel - over
             # the duration of the main launch.  These bytes are mostly served by the caches: `traffic` / `hbm_measured_*` is what the PMC
             # counters saw beyond L2, and `binding` what the same profile says the kernel actually waits for.
-            "roofline": {"bound": "hbm", "achieved": round(achieved_bin, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved_bin / HBM_PEAK_GBS, 4),
-                         "traffic": pmc_traffic,
-                         "hbm_measured_gbs": round(pmc_traffic / (main_ms * 1e-3) / 1e9, 1) if pmc_traffic else None,
-                         "hbm_measured_frac": round(pmc_traffic / (main_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if pmc_traffic else None,
-                         "binding": pmc_binding,
-                         "accounting": "achieved = SURVEY 8(d) algorithmic bytes (64 B per BVH2 node visit of the same rays on the same tree, counted by the "
-                                       "instrumented one-level walk; 36 B per triangle test; 152 B per scatter; 12 B per pixel) / duration of the main launch; "
-                                       "*_as_fetched = bytes of the records this build requests (quad node 2 x 64 B, oct node 4 x 64 B per visit): not an HBM figure "
-                                       "(can exceed the peak: the working set is cache resident); traffic = FETCH_SIZE + WRITE_SIZE of the main launch (rocprofv3 "
-                                       "PMC, separate passes, %s); hbm_measured_frac = traffic / main-launch time / peak"
-                                       % (pmc["file"] if pmc else "no committed PMC summary matches this kernel build"),
-                         "achieved_as_fetched": round(achieved, 1), "frac_as_fetched": round(achieved / HBM_PEAK_GBS, 4),
-                         "algorithmic_bytes_per_launch": int(alg_bin), "algorithmic_bytes_per_launch_as_fetched": int(alg_bytes),
-                         "counts_per_frame_rank0_binary_walk": {k: int(cst_bin[k]) for k in ("rays", "nodes", "tris", "scatters")},
-                         "kernel": "pt_render_wave_kernel<false>, main launch", "kernel_ms_per_launch": round(main_ms, 3), "launches_per_step": launches,
-                         "prepass_and_sort_ms": round(p_ms, 3), "kernel_ms_per_frame": round(k_ms, 3),
-                         "counts_per_frame_rank0": {k: int(cst[k]) for k in ("samples", "rays", "nodes", "tris", "scatters", "env_misses")},
-                         "vgprs": st["vgprs"], "lds_bytes": st["lds_bytes"], "grid": st["grid"], "block": st["block"]},
-        }
+            out["roofline"] = {"bound": "hbm", "achieved": round(achieved_bin, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved_bin / HBM_PEAK_GBS, 4),
+                               "traffic": pmc_traffic,
+                               "hbm_measured_gbs": round(pmc_traffic / (main_ms * 1e-3) / 1e9, 1) if pmc_traffic else None,
+                               "hbm_measured_frac": round(pmc_traffic / (main_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if pmc_traffic else None,
+                               "binding": pmc_binding,
+                               "accounting": "achieved = SURVEY 8(d) algorithmic bytes (64 B per BVH2 node visit of the same rays on the same tree, counted by the "
+                                             "instrumented one-level walk; 36 B per triangle test; 152 B per scatter; 12 B per pixel) / duration of the main launch; "
+                                             "*_as_fetched = bytes of the records this build requests (quad node 2 x 64 B, oct node 4 x 64 B per visit): not an HBM figure "
+                                             "(can exceed the peak: the working set is cache resident); traffic = FETCH_SIZE + WRITE_SIZE of the main launch (rocprofv3 "
+                                             "PMC, separate passes, %s); hbm_measured_frac = traffic / main-launch time / peak"
+                                             % (pmc["file"] if pmc else "no committed PMC summary matches this kernel build"),
+                               "achieved_as_fetched": round(achieved, 1), "frac_as_fetched": round(achieved / HBM_PEAK_GBS, 4),
+                               "algorithmic_bytes_per_launch": int(alg_bin), "algorithmic_bytes_per_launch_as_fetched": int(alg_bytes),
+                               "counts_per_frame_rank0_binary_walk": {k: int(cst_bin[k]) for k in ("rays", "nodes", "tris", "scatters")},
+                               "kernel": "pt_render_wave_kernel<false>, main launch", "kernel_ms_per_launch": round(main_ms, 3), "launches_per_step": launches,
+                               "prepass_and_sort_ms": round(p_ms, 3), "kernel_ms_per_frame": round(k_ms, 3),
+                               "counts_per_frame_rank0": {k: int(cst[k]) for k in ("samples", "rays", "nodes", "tris", "scatters", "env_misses")},
+                               "vgprs": st["vgprs"], "lds_bytes": st["lds_bytes"], "grid": st["grid"], "block": st["block"]}
         out["per_rank"] = per_rank
         if rehearsal_dev is not None:
             out["rehearsal"] = True
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(scene_io, mats, ents, cam.as_array())
         print(json.dumps(out), flush=True)
 

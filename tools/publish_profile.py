@@ -9,7 +9,7 @@ shutil.copy(os.path.join(src, "kernel_stats.csv"), os.path.join(dst, name + "_ke
 with open(os.path.join(src, "bench.log")) as f:
     lines = [l for l in f if l.startswith("{")]
 with open(os.path.join(dst, name + "_bench.log"), "w") as f:
-    f.write("# rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 3 --warmup 1   (the JSON line bench.py printed under the profiler)\n")
+    f.write("# rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps 3 --warmup 1   (the JSON line bench.py printed under the profiler)\n")
     f.write(lines[-1])
 bench = json.loads(lines[-1])
 # per-launch durations of the render kernel from the kernel trace of the same run
@@ -24,7 +24,7 @@ with open(os.path.join(dst, name + "_kernel_trace.txt"), "w") as f:
     for k, ms in rows:
         f.write("%s %.3f\n" % (k, ms))
 pmc = json.load(open(os.path.join(src, "pmc_summary.json")))
-pmc["command"] = "rocprofv3 --kernel-trace --pmc <one group per run> -- python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline (tools/profile_round.sh)"
+pmc["command"] = "rocprofv3 --kernel-trace --pmc <one group per run> -- python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline (tools/profile_round.sh)"
 json.dump(pmc, open(os.path.join(dst, name + "_pmc.json"), "w"), indent=1)
 d = pmc["derived"]
 sys.path.insert(0, root)
