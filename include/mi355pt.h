@@ -101,7 +101,7 @@ typedef struct pt_stats {
     int32_t whole_pixels;   /* other pixels of that launch that kept their path slot for all samples (whole-pixel schedule: every pixel had a slot from the start); 0: ring schedule */
     int32_t prepass_spp;    /* samples per pixel of the cost pre-pass launch of the last render (0: the render did not sort) */
     /* counted renders, hit-shading passes by sampled lobe (disney.cuh:9-13: 0 diffuse, 1 clearcoat, 2 metallic, 3 glass; 4 = emitter hit,
-     * 5 = NaN retry): [0..5] items, [7] passes that shaded one lobe bin alone (option "lobe_bins"), [8..13] passes in which at least one
+     * 5 = NaN retry): [0..5] items, [7] always 0 (it counted the passes of an experiment that is gone), [8..13] passes in which at least one
      * item took that branch, [14] passes that ran two or more BSDF bodies, [15] passes whose items all took the same branch */
     uint64_t lobes[16];
     /* counted renders, traversal (lane-steps): [0] quad-node steps that enter no child, [1] of those: the node lies beyond the best hit
@@ -207,9 +207,7 @@ int pt_group_render(pt_group* g, const pt_camera* cam, int32_t width, int32_t he
  *   level and running pixels up to which a wave counts as sparse);  "tune0" (8: a shading pass with idle lanes also takes the entries of the other
  *   queue when that holds at least this many; > 64 = never; off by itself when an environment map is bound);
  *   "quad" 1 (default: two binary levels per 128-byte record) | 0;  "box_exact" -1 (default: slab distances by one fma per plane, the
- *   subtracting form when the camera is more than 42 scene extents from the origin) | 0 | 1;  "lobe_bins" 1 | -1: lobe-coherent hit passes (a hit pass shades the hits of ONE predicted
- *   lobe at a time; -1: only when the materials can sample two or more lobes) - exists in `make lobebins` builds only (validated bit-exact, costs
- *   what it saves: profiles/r04_notes.md); the product build returns PT_E_INVALID; "tune4" (24: hits of one lobe that make a pass of their own);  "fallback" 1: use the wavefront kernel's 168-VGPR instance (what
+ *   subtracting form when the camera is more than 42 scene extents from the origin) | 0 | 1;  "fallback" 1: use the wavefront kernel's 168-VGPR instance (what
  *   the library does by itself when the 128-VGPR instance of a build needs scratch). */
 int pt_set_option(pt_ctx* ctx, const char* key, int64_t value);
 int pt_get_stats(pt_ctx* ctx, pt_stats* out);

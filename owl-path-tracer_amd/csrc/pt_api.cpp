@@ -108,43 +108,9 @@ int upload_env(pt_ctx* c)
     return PT_OK;
 }
 
-// Lobe thresholds of one material for the lobe bins of the hit pass (pt_kernel.hip, LOBE-COHERENT HIT PASSES): the cumulative
-// selection probabilities of sample_disney in ITS order (disney.cuh:15-29,44-63: metallic, clearcoat, diffuse; glass is what is left)
-// in units of 1/512 of the draw, 10 bits each; bit 30: emitter (device.cu:157-161 ends the path before any lobe runs), bit 31: the
-// material has a glass lobe (force_btdf, disney.cuh:39).  A prediction aid only - the shader decides from the exact values.
-uint32_t pt_lobe_code(const float* m)
-{
-    const float metallic = m[4], clearcoat = m[11], transmission = m[14], emission = m[16];
-    const float wd = (1.0f - transmission) * (1.0f - metallic), wm = metallic, wc = 0.25f * clearcoat, wg = (1.0f - metallic) * transmission;
-    const float sum = wm + wg + wd + wc;
-    auto q = [&](float x) {
-        const float v = sum > 0.0f ? x / sum * 512.0f + 0.5f : 0.0f;
-        return (uint32_t)(v != v || v < 0.0f ? 0.0f : (v > 512.0f ? 512.0f : v));
-    };
-    const uint32_t t0 = q(wm), t1 = std::max(t0, q(wm + wc)), t2 = std::max(t1, q(wm + wc + wd));
-    return t0 | (t1 << 10) | (t2 << 20) | (emission > 0.0f ? 0x40000000u : 0u) | (wg > 0.0f ? 0x80000000u : 0u);
-}
-
 int upload_materials(pt_ctx* c)
 {
-    // the lobe-code table (index = material + 1; 0 = material_data{} defaults, device.cu:150-154) and whether the scene can sample
-    // more than one lobe at all (one lobe: the bins would only cost)
-    c->lobe_mask = 0;
-    std::memset(c->lobe_codes, 0, sizeof(c->lobe_codes));
-    const bool fits = c->n_materials + 1 <= PT_LOBE_TABLE;
-    static const float def_mat[PT_MAT_FLOATS] = {0.8f, 0.8f, 0.8f, 0.0f, 0.0f, 0.5f, 1.0f, 0.5f, 0.0f, 0.0f, 1.0f, 0.0f, 0.03f, 1.45f, 0.0f, 0.0f, 0.0f};
-    for (int i = 0; fits && i <= c->n_materials; ++i) {
-        const uint32_t code = pt_lobe_code(i == 0 ? def_mat : &c->materials[(size_t)(i - 1) * PT_MAT_STRIDE]);
-        c->lobe_codes[i] = code;
-        if (i == 0 && !c->uses_default_material) continue;
-        if (code & 0x40000000u) continue; // emitter: no lobe
-        const uint32_t t0 = code & 0x3ffu, t1 = (code >> 10) & 0x3ffu, t2 = (code >> 20) & 0x3ffu;
-        c->lobe_mask |= (t0 > 0 ? 4u : 0u) | (t1 > t0 ? 2u : 0u) | (t2 > t1 ? 1u : 0u) | (t2 < 512u ? 8u : 0u);
-    }
-    if (!fits) c->lobe_mask = 0;
     if (c->host_only) return PT_OK;
-    int rc = upload(c, c->d_lobe, c->lobe_codes, sizeof(c->lobe_codes));
-    if (rc) return rc;
     return upload(c, c->d_materials, c->materials.data(), c->materials.size() * sizeof(float));
 }
 
@@ -221,12 +187,6 @@ void fill_params(pt_ctx* c, PtKernelParams& P)
     P.n_materials = c->n_materials;
     P.stack_entries = c->bvh.depth < 1 ? 1 : c->bvh.depth;
     for (int i = 0; i < 8; ++i) P.tune[i] = c->tune[i];
-    P.lobe_codes = (const uint32_t*)c->d_lobe.p;
-    P.hit_slot_mask = c->tri_packed ? 0x00ffffffu : 0xffffffffu;
-    // lobe bins (wavefront kernel; off by default - measured: they cost what they save, profiles/r04_notes.md): 1 = whenever the scene
-    // allows, -1 = when its materials can sample two or more different lobes
-    const int n_lobes = __builtin_popcount(c->lobe_mask);
-    P.lobe_bins = (c->kernel == 2 && c->tri_packed && c->lobe_mask != 0 && (c->lobe_bins > 0 || (c->lobe_bins < 0 && n_lobes >= 2))) ? 1 : 0;
 }
 
 } // namespace
@@ -298,7 +258,7 @@ void pt_destroy(pt_ctx* c)
         (void)hipStreamSynchronize(c->stream);
         (void)pt_comm_destroy(c);
         DevBuf* bufs[] = {&c->d_nodes8, &c->d_nodes4, &c->d_nodes, &c->d_tris, &c->d_shade, &c->d_materials, &c->d_texdesc, &c->d_env, &c->d_pixels, &c->d_heads,
-                          &c->d_rng, &c->d_accum, &c->d_out, &c->d_out8, &c->d_counters, &c->d_dbg_in, &c->d_dbg_out, &c->d_slots, &c->d_laps, &c->d_ring, &c->d_params, &c->d_cost, &c->d_sorted, &c->d_sort_scratch, &c->d_dbg_start, &c->d_bucket, &c->d_tiers, &c->d_lobe};
+                          &c->d_rng, &c->d_accum, &c->d_out, &c->d_out8, &c->d_counters, &c->d_dbg_in, &c->d_dbg_out, &c->d_slots, &c->d_laps, &c->d_ring, &c->d_params, &c->d_cost, &c->d_sorted, &c->d_sort_scratch, &c->d_dbg_start, &c->d_bucket, &c->d_tiers};
         for (DevBuf* b : bufs) release(*b);
         for (void* p : c->d_textures) (void)hipFree(p);
         if (c->ev0) (void)hipEventDestroy(c->ev0);
@@ -342,10 +302,6 @@ int pt_set_option(pt_ctx* c, const char* key, int64_t value)
     else if (k == "ns_express") c->ns_express = (int)(value < 1 ? 1 : (value > 64 ? 64 : value));
     else if (k == "groups") c->groups = (int)(value < 0 ? 0 : (value > 2 ? 2 : value)); // group walk: 0 never, 1 sparse waves (default), 2 always
     else if (k == "ploc_radius") c->ploc_radius = (int)(value < 1 ? 1 : (value > 64 ? 64 : value)); // bvh_builder 2: neighbours searched on either side
-    else if (k == "lobe_bins") {
-        if (value && !pt_kernel_lobe_bins()) return fail(c, PT_E_INVALID, "option 'lobe_bins': this build has no lobe bins (make -C owl-path-tracer_amd/csrc lobebins)");
-        c->lobe_bins = (int)(value < 0 ? -1 : (value > 1 ? 1 : value));
-    } // hit passes by predicted lobe: 0 never (default), 1 whenever possible, -1 when the scene has two or more lobes
     else if (k == "box_exact") c->box_exact = (int)(value < 0 ? -1 : (value > 0 ? 1 : 0)); // slab test form: -1 automatic (fma unless the camera is far outside the scene), 0 fma, 1 subtracting
     else if (k == "quad") c->quad = value != 0; // wavefront kernel: quad nodes (two binary levels per fetch), next pt_render
     else if (k == "node_pairs") c->node_pairs = value != 0;
@@ -397,10 +353,8 @@ int pt_upload_scene(pt_ctx* c, const pt_mesh* meshes, int32_t n_meshes, const fl
     if (material_texture)
         for (int i = 0; i < n_materials; ++i) c->material_texture[i] = material_texture[i];
     size_t g = 0;
-    c->uses_default_material = false;
     for (int m = 0; m < n_meshes; ++m) {
         const pt_mesh& ms = meshes[m];
-        if (ms.material_index < 0 && ms.n_triangles > 0) c->uses_default_material = true;
         if (ms.n_triangles > 0 && (!ms.vertices || !ms.indices)) return fail(c, PT_E_INVALID, "mesh %d: null vertices/indices", m);
         if (ms.material_index >= n_materials) return fail(c, PT_E_INVALID, "mesh %d: material index %d out of range", m, ms.material_index);
         if (ms.texture_index >= n_textures) return fail(c, PT_E_INVALID, "mesh %d: texture index %d out of range", m, ms.texture_index);
@@ -585,13 +539,7 @@ int upload_scene_to_device(pt_ctx* c)
     if ((rc = upload(c, c->d_nodes, c->bvh.nodes.data(), c->bvh.nodes.size() * sizeof(PtNode)))) return rc;
     if ((rc = upload(c, c->d_nodes4, c->nodes4.data(), c->nodes4.size() * sizeof(PtNode4)))) return rc;
     if ((rc = upload(c, c->d_nodes8, c->nodes8.data(), c->nodes8.size() * sizeof(PtNode8)))) return rc;
-    {   // the device copy of the triangle records carries the material with the id (PtTri::id): below 2^23 triangle slots a hit's
-        // triangle slot leaves room for it in the word the kernel keeps per hit, and id << 8 stays a positive int (same tie-break order)
-        // (packed on the device after the copy: pt_pack_tri_ids_kernel)
-        c->tri_packed = pt_kernel_lobe_bins() && c->bvh.tris.size() < ((size_t)1 << 23); // (only builds with the lobe bins use it)
-        if ((rc = upload(c, c->d_tris, c->bvh.tris.data(), c->bvh.tris.size() * sizeof(PtTri)))) return rc;
-        if (c->tri_packed) HIP_TRY(c, pt_launch_pack_tri_ids((PtTri*)c->d_tris.p, (long long)c->bvh.tris.size(), c->stream));
-    }
+    if ((rc = upload(c, c->d_tris, c->bvh.tris.data(), c->bvh.tris.size() * sizeof(PtTri)))) return rc;
     if ((rc = upload(c, c->d_shade, c->shade.data(), c->shade.size() * sizeof(PtShade)))) return rc;
     for (void* p : c->d_textures) (void)hipFree(p);
     c->d_textures.clear();
@@ -629,7 +577,6 @@ int clone_scene(pt_ctx* dst, const pt_ctx* src)
     dst->materials = src->materials;
     dst->n_materials = src->n_materials;
     dst->material_texture = src->material_texture;
-    dst->uses_default_material = src->uses_default_material;
     dst->textures = src->textures;
     dst->env = src->env;
     dst->env_map = src->env_map;
@@ -690,6 +637,352 @@ int64_t pt_shard_pixels(int32_t width, int32_t height, int32_t tile, int32_t ran
     return shard_pixels(width, height, tile, rank, world_size, ids, cap);
 }
 
+} // extern "C"
+
+namespace {
+
+#ifndef PT_DEFAULT_NS
+#define PT_DEFAULT_NS 96 // path slots per wave of the wavefront kernel: 16 waves/CU up to 104; 64..255 swept on C4 (profiles/r01_summary.md), 88..104 within 1 %
+#endif
+static_assert(PT_DEFAULT_NS >= 16 && PT_DEFAULT_NS <= 252, "PT_DEFAULT_NS: 16..252 path slots per wave");
+
+// Chunk schedule of one wavefront launch over `total` samples per pixel: n_full chunks of `chunk` samples, then the rest in
+// halving chunks (rem/2, rem/4, ... >= tail_min).  A frame ends when its slowest in-flight work item ends, so the
+// last items must be short (profiles/r01_summary.md, "wind-down").
+struct Schedule { int chunk = 0, n_full = 0, n_chunks = 1, tail_len[PT_MAX_TAIL_CHUNKS] = {}; };
+
+Schedule make_schedule(int total, int chunk, int rem_min, int tail_min)
+{
+    Schedule sc;
+    sc.chunk = std::max(1, std::min(chunk, total));
+    sc.n_full = total / sc.chunk;
+    int rem = total - sc.n_full * sc.chunk;
+    if (tail_min > 0 && sc.n_full > 0 && rem < rem_min) { --sc.n_full; rem += sc.chunk; }
+    int n_tail = 0;
+    while (rem > 0) {
+        int len = rem;
+        if (tail_min > 0 && rem > tail_min && n_tail < PT_MAX_TAIL_CHUNKS - 1) len = std::max(tail_min, (rem + 1) / 2);
+        sc.tail_len[n_tail++] = len;
+        rem -= len;
+    }
+    sc.n_chunks = sc.n_full + n_tail;
+    return sc;
+}
+
+// The scene (fill_params) and the tree walks of the wavefront kernel for a frame from `cam`.
+void walk_params(pt_ctx* c, const pt_camera* cam, PtKernelParams& P)
+{
+    fill_params(c, P);
+    {   // the fma form of the slab test (pt_kernel.hip, node4_step) displaces a plane by |o| 2^-24; the boxes are padded by 1e-5 x the scene
+        // extent (bvh.pad): exact form when the camera is so far from the origin that this would eat a quarter of the padding
+        const float reach = c->bvh.pad * 4194304.0f; // pad x 2^22 = 42 scene extents
+        float far_o = 0.0f;
+        for (int a = 0; a < 3; ++a) far_o = std::max(far_o, std::fabs(cam->origin[a]));
+        P.box_exact = (c->box_exact > 0 || (c->box_exact < 0 && !(far_o <= reach))) ? 1 : 0;
+    }
+    if (c->kernel == 2 && c->quad && !c->nodes4.empty()) { // the wavefront kernel walks the quad nodes: own root and stack bound
+        P.nodes4 = (const PtNode4*)c->d_nodes4.p;
+        P.root = c->root4;
+        P.stack_entries = 3 * c->depth4 + 1;
+    }
+    if (c->kernel == 2 && c->groups && !c->nodes8.empty()) { // group walk of sparse waves (oct nodes)
+        P.nodes8 = (const PtNode8*)c->d_nodes8.p;
+        P.root8 = c->root8;
+        P.groups = c->groups;
+    }
+}
+
+// What one frame launches, decided before any buffer is sized (plan_frame).
+// kernel 1 (lane-per-pixel): optional spp chunks = separate launches.
+// Wavefront kernel, schedule 1 (default): a short cost pre-pass (pre samples of every pixel, rays counted), a counting sort of the
+// pixel queue by that cost, then ONE persistent launch over the cost-ordered queue whose first chunk is sticky_pct % of the remaining
+// samples (a slot keeps its pixel, no hand-offs, expensive pixels start first) and whose last samples go round in halving chunks
+// through the per-chunk rings, so that the frame ends on ~n_pixels short work items.
+// schedule 0 (or spp_per_launch, which the resumability tests use): one launch, chunk_spp chunks + halving tail.
+// All schedules give the same image bit for bit (a pixel's stream does not depend on who renders it, or when).
+struct FramePlan {
+    int variant = 0, use_count = 0; // instance of the render kernel (pt_launch_render) and whether it is the instrumented one
+    PtGeometry geo{};               // its launch geometry
+    int bpc = 0, grid = 0;          // workgroups per CU, of the (main) launch
+    int ring_grid = 0;              // with a tier plan: the workgroups of the ring schedule (the plan's fallback; the pre-pass launches these)
+    bool sorted = false;            // cost pre-pass, queue sort, main launch
+    bool tiers = false;             // ... whose main launch has a whole-pixel tier plan prepared (pt_plan_tiers_kernel)
+    int pre = 0;                    // samples of the cost pre-pass
+    int n_launch = 1, S = 0;        // launches; samples per launch (kernel 1)
+    Schedule sc;                    // chunk schedule of the (main) wavefront launch
+    int tail_min = 16;              // smallest chunk of its halving tail
+    uint32_t n_express = 0;         // express pixels (pt_kernel.hip, take_ticket), their waves and pixels per express wave
+    int express_waves = 0, ns_express = 0;
+};
+
+// Samples, chunks and express pixels of a wavefront frame whose launch geometry plan_frame has fixed.
+int plan_chunks(pt_ctx* c, bool group_walk, int max_samples, FramePlan& f)
+{
+    f.tail_min = c->chunk_tail_min >= 0 ? c->chunk_tail_min : 16; // (automatic: set per schedule below)
+    f.S = max_samples;
+    f.n_launch = f.sorted ? 2 : 1;
+    const int ns = f.geo.ns;
+    if (f.sorted) {
+        const int rest = max_samples - f.pre;
+        // Share of a pixel's remaining samples that its first slot renders in one go.  With many more pixels than slots the
+        // frame is throughput-bound and hand-offs are pure overhead: 80 %; with fewer pixels per slot 50-65 % (a launch whose
+        // pixels all have a slot and whose costs have a tail runs the tier schedule instead).
+        int sticky = c->sticky_pct;
+        if (sticky < 1) {
+            const double ratio = (double)c->n_pixels / ((double)c->num_cus * (double)f.bpc * (double)ns);
+            sticky = (int)std::min(80.0, 50.0 + 6.0 * ratio); // (rounds 1-2, queue ordered by rays: 10-75, rising with the ratio; re-swept with the
+                                                             // queue ordered by time: C4 80, 1/2 shard and C3 65, 1/4 shard 50-65, C2 60 - r3_ab57/58.log)
+        }
+        // With the queue ordered by the TIME of a pixel's samples the hand-offs of the tail buy little and every lap is a barrier of
+        // sorts: the last quarter goes in two chunks, not five (C4 528 -> 500 ms, C3 161 -> 153; smallest tail chunk 16 / 32 / 64 / 128
+        // of 1016 samples: 528 / 515 / 505 / 498 ms; profiles/r03_logs/r3_ab54.log).
+        if (c->chunk_tail_min < 0) f.tail_min = std::max(16, rest / 8);
+        const int big = std::max(1, (int)((int64_t)rest * sticky / 100));
+        f.sc = make_schedule(rest, big, rest - big, f.tail_min);
+    } else {
+        const int chunk = std::min(c->spp_per_launch > 0 ? c->spp_per_launch : c->chunk_spp, std::min(max_samples, 65535));
+        f.sc = make_schedule(max_samples, chunk, 1, f.tail_min);
+    }
+    const int n_chunks = f.sc.n_chunks;
+    if ((uint64_t)c->n_pixels * (uint64_t)n_chunks >= 0xfff00000ull) return fail(c, PT_E_LIMIT, "too many (pixel, chunk) tickets");
+    if (n_chunks > 255 || c->n_pixels >= (1u << 24)) return fail(c, PT_E_LIMIT, "the wavefront kernel needs n_chunks <= 255 and < 2^24 pixels per rank (raise chunk_spp)");
+    // Express pixels (pt_kernel.hip, take_ticket): the most expensive entries of the cost-ordered queue get waves of their own when the
+    // frame is bound by its longest sample chains, i.e. when (nearly) every pixel is in flight from the start - few pixels per path slot
+    // (a shard of a multi-GPU frame, a small image).  A throughput-bound frame (many pixels per slot) has none: sparse waves would only
+    // take wave slots from it.  Options "express_permille" (-1 = automatic: 10 per mille up to 1.5 pixels per slot, 0 from 4),
+    // "ns_express" (8 pixels per express wave), at most an eighth of the waves.
+    if (f.sorted && group_walk && n_chunks <= 254 && (uint64_t)c->n_pixels * (uint64_t)n_chunks < 0xE0000000ull) {
+        int& rgrid = f.tiers ? f.ring_grid : f.grid; // the workgroups of the ring schedule (with a tier plan the launch has all resident ones)
+        const double ratio = (double)c->n_pixels / ((double)rgrid * (double)ns);
+        double permille = c->express_permille >= 0 ? (double)c->express_permille : (ratio <= 1.5 ? 10.0 : (ratio >= 4.0 ? 0.0 : 10.0 * (4.0 - ratio) / 2.5));
+        const int nse = std::max(1, std::min(c->ns_express, ns));
+        uint64_t want = (uint64_t)((double)c->n_pixels * permille / 1000.0);
+        const int capacity = c->num_cus * f.bpc;
+        // at most an eighth of the ring schedule's waves, or what the bulk leaves free.  (Round 4 tried up to 60 % of the waves for 1-15 % of the
+        // pixels at 8-48 per wave, also with the grid oversubscribed by the express waves: world 2 351 -> 400-470 ms, world 4 269 -> 300-370,
+        // profiles/r04_notes.md 5.)
+        const int cap_waves = std::max(rgrid / 8, std::min(capacity / 2, capacity - rgrid));
+        want = std::min<uint64_t>(want, (uint64_t)cap_waves * (uint64_t)nse);
+        if (want > 0 && want < c->n_pixels) {
+            f.n_express = (uint32_t)want;
+            f.express_waves = (int)((want + (uint64_t)nse - 1) / (uint64_t)nse);
+            f.ns_express = nse;
+            // wave slots the bulk does not fill (a shard, a small image) hold the express waves on top of the bulk's
+            rgrid = std::min(capacity, (int)(((long)c->n_pixels - (long)f.n_express + ns - 1) / ns) + f.express_waves);
+        }
+    }
+    return PT_OK;
+}
+
+// The launch plan of a frame from the context's options, the pixel queue, the device and the tree bounds in P.  Its only device
+// interaction is the geometry query of the kernel instance; every PT_E_LIMIT refusal of a render happens here.
+int plan_frame(pt_ctx* c, const PtKernelParams& P, int max_samples, FramePlan& f)
+{
+    // variant of the launch: the wavefront kernel's product instance (2) unless it needs scratch in this build - then its fallback
+    // instance with the larger register budget (3): slower (12 instead of 16 waves per CU), the same arithmetic
+    // (the one-level walk over PtNode[] - option quad = 0, or a tree too deep for the quad walk's stack bound - is compiled into the
+    // instrumented instance only: the product instance is kept small for the instruction cache)
+    f.use_count = (c->count || (c->kernel == 2 && !P.nodes4)) ? 1 : 0;
+    f.variant = c->kernel == 2 && c->fallback && !f.use_count ? 3 : c->kernel;
+    // The wavefront kernel keeps `ns` pixels in flight per wave; shrink ns when the image is too small to give every resident wave a
+    // full set (e.g. 512x512 over 4096 waves), otherwise use the default.
+    const int group_entries = P.nodes8 ? 7 * c->depth8 + 1 : 0;
+    int want_ns = c->slots_per_wave > 0 ? c->slots_per_wave : PT_DEFAULT_NS;
+    const PtGeometry& g = f.geo;
+    auto geometry = [&] { return pt_kernel_geometry(f.variant, f.use_count, P.stack_entries, group_entries, want_ns, P.box_exact, &f.geo); };
+    hipError_t ge = geometry();
+    if (ge == hipErrorInvalidConfiguration && f.variant == 2 && !f.use_count) {
+        f.variant = 3;
+        ge = geometry();
+    }
+    if (ge == hipErrorInvalidConfiguration)
+        return fail(c, PT_E_LIMIT, f.use_count ? "the instrumented instance of the render kernel needs scratch in this build; such builds rendered wrong pixels and are refused (pt_kernel.hip; tests/test_abi_host.py reads hipcc's resource report)"
+                                               : "this build of the render kernel spills registers to scratch even in its fallback instance; such builds rendered wrong pixels and are refused (pt_kernel.hip)");
+    HIP_TRY(c, ge);
+    if (c->kernel == 2 && c->slots_per_wave == 0 && g.max_blocks_per_cu > 0) {
+        // small images: fewer slots per wave so that at least 8 waves per CU have pixels (never below 64)
+        const long fit = (long)c->n_pixels / ((long)c->num_cus * 8);
+        if (fit < want_ns) {
+            want_ns = (int)std::max(64L, fit);
+            HIP_TRY(c, geometry());
+        }
+    }
+    if (g.max_blocks_per_cu < 1) return fail(c, PT_E_LIMIT, "render kernel does not fit a CU (LDS %zu bytes, BVH depth %d)", g.lds_bytes, c->bvh.depth);
+    f.bpc = c->blocks_per_cu > 0 ? std::min(c->blocks_per_cu, g.max_blocks_per_cu) : g.max_blocks_per_cu;
+    const long capacity = (long)c->num_cus * f.bpc;
+    const int per_wg = c->kernel == 1 ? g.block : g.ns; // never more path slots than pixels: a pixel's chunks are sequential
+    f.grid = (int)std::max(1L, std::min(((long)c->n_pixels + per_wg - 1) / per_wg, capacity));
+    f.pre = c->prepass_spp > 0 ? c->prepass_spp : 8; // samples of the cost pre-pass
+    f.sorted = c->kernel == 2 && c->schedule == 1 && c->spp_per_launch == 0 && max_samples >= 4 * f.pre && max_samples <= 65535;
+    // Whole-pixel schedule (pt_kernel.hip, TIERS): when every pixel can have a path slot from the start, the main launch hands out
+    // pixels instead of (pixel, chunk) tickets, and every wave serves one cost class with as few pixels as that class needs - the plan
+    // is made on the device from the histogram of the counting sort (pt_plan_tiers_kernel).  Option "whole": -1 automatic, 0 never.
+    if (f.sorted && P.nodes8 && c->whole != 0 && c->slots_per_wave == 0) {
+        for (int nsd = 96; nsd <= 104 && !f.tiers; nsd += 8) { // 16 waves per CU up to 104 slots
+            if (c->whole < 1 && (long)c->n_pixels + (long)PT_MAX_TIERS * nsd > capacity * nsd) continue; // (one partly filled wave per class)
+            want_ns = nsd;
+            HIP_TRY(c, geometry());
+            if (g.max_blocks_per_cu >= f.bpc && g.ns == nsd) {
+                f.tiers = true;
+                f.ring_grid = (int)std::max(1L, std::min(((long)c->n_pixels + g.ns - 1) / g.ns, capacity)); // what the ring schedule would launch
+                f.grid = (int)capacity;
+            }
+        }
+        if (!f.tiers) {
+            want_ns = PT_DEFAULT_NS;
+            HIP_TRY(c, geometry());
+        }
+    }
+    // the tier plan lives on the cost estimate: twice the samples (1/8 shard of C4 218 -> 201 ms; a throughput-bound frame gains nothing)
+    if (f.tiers && c->prepass_spp == 0 && max_samples >= 4 * 16) f.pre = 16;
+    if (c->kernel == 1) {
+        f.S = std::min(c->spp_per_launch > 0 ? std::min(c->spp_per_launch, max_samples) : max_samples, 65535);
+        f.n_launch = (max_samples + f.S - 1) / f.S;
+        return PT_OK;
+    }
+    return plan_chunks(c, P.nodes8 != nullptr, max_samples, f);
+}
+
+// Every device buffer of a frame sized from its plan, and every clear it needs: all of it is enqueued before the frame's first event.
+int frame_buffers(pt_ctx* c, const FramePlan& f, int W, int H, void* d_out_rgb, void* d_out_rgba8, hipStream_t stream)
+{
+    int rc;
+    const int n_chunks = f.sc.n_chunks;
+    if (f.geo.state_words && (rc = ensure(c, c->d_slots, f.geo.state_words * 4 * (size_t)f.grid))) return rc;
+    if (f.sorted) {
+        if ((rc = ensure(c, c->d_cost, (size_t)W * H))) return rc; // cost image; zero where this rank owns nothing
+        if ((rc = ensure(c, c->d_bucket, (size_t)c->n_pixels))) return rc;
+        HIP_TRY(c, hipMemsetAsync(c->d_cost.p, 0, (size_t)W * H, stream));
+        if ((rc = ensure(c, c->d_sorted, (size_t)c->n_pixels * 4))) return rc;
+        if ((rc = ensure(c, c->d_sort_scratch, pt_sort_scratch_bytes(c->n_pixels)))) return rc;
+    }
+    if (c->kernel == 2) {
+        // one ring of ready pixels per chunk index: ring c holds, in completion order of chunk c - 1, the pixels whose chunk c
+        // may start.  d_laps = watchdog flag + one fill counter per ring.
+        // Layout (never a plain store in a cache line that also holds device-scope atomics): [0] watchdog flag | +256 B: ring fill
+        // counters (n_chunks + 1, + the pre-pass's spare) | 256-B aligned: diagnostics timelines of the two launches.
+        c->lap_ticks_ofs = ((256 + (size_t)(n_chunks + 3) * 4 + 255) / 256) * 256;
+        const size_t laps_bytes = c->lap_ticks_ofs + ((size_t)PT_LAP_REGION(n_chunks) + (size_t)PT_LAP_REGION(1)) * 8;
+        if ((rc = ensure(c, c->d_laps, laps_bytes))) return rc;
+        if ((rc = ensure(c, c->d_ring, (size_t)c->n_pixels * 4 * (size_t)n_chunks))) return rc;
+        HIP_TRY(c, hipMemsetAsync(c->d_laps.p, 0, laps_bytes, stream));
+        if (n_chunks > 1) HIP_TRY(c, hipMemsetAsync(c->d_ring.p, 0, (size_t)c->n_pixels * 4 * (size_t)n_chunks, stream));
+        if ((rc = ensure(c, c->d_params, sizeof(PtKernelParams) * (size_t)f.n_launch))) return rc;
+    }
+    c->last_chunks = n_chunks;
+    if ((rc = ensure(c, c->d_heads, (size_t)f.n_launch * PT_HEADS_WORDS * 4))) return rc; // per launch: the ticket counter, the express counter 256 bytes on, the tier counters
+    HIP_TRY(c, hipMemsetAsync(c->d_heads.p, 0, (size_t)f.n_launch * PT_HEADS_WORDS * 4, stream));
+    if (f.tiers && (rc = ensure(c, c->d_tiers, (1 + PT_MAX_TIERS * PT_TIER_WORDS) * 4))) return rc;
+    HIP_TRY(c, hipMemsetAsync(d_out_rgb, 0, (size_t)W * H * 3 * sizeof(float), stream));
+    if (d_out_rgba8) HIP_TRY(c, hipMemsetAsync(d_out_rgba8, 0, (size_t)W * H * 4, stream));
+    if (f.n_launch > 1 || n_chunks > 1) {
+        if ((rc = ensure(c, c->d_rng, (size_t)W * H * 4))) return rc;
+        if ((rc = ensure(c, c->d_accum, (size_t)W * H * 12))) return rc;
+    }
+    if (f.use_count) {
+        if ((rc = ensure(c, c->d_counters, sizeof(PtCounters)))) return rc;
+        HIP_TRY(c, hipMemsetAsync(c->d_counters.p, 0, sizeof(PtCounters), stream));
+    }
+    if (c->latency && f.sorted) {
+        if ((rc = ensure(c, c->d_dbg_start, (size_t)W * H * 8))) return rc; // + rays per pixel (instrumented instance)
+        HIP_TRY(c, hipMemsetAsync(c->d_dbg_start.p, 0, (size_t)W * H * 8, stream));
+    }
+    return PT_OK;
+}
+
+// The parameters every launch of the frame shares (P holds the scene and the tree walk already: fill_params, pt_render_device).
+void frame_params(pt_ctx* c, const FramePlan& f, const pt_camera* cam, int W, int H, int max_samples, int max_depth, void* d_out_rgb, void* d_out_rgba8,
+                  PtKernelParams& P)
+{
+    P.lds_levels = f.geo.lds_levels;
+    P.ns = f.geo.ns;
+    P.slot_state = f.geo.state_words ? (uint32_t*)c->d_slots.p : nullptr;
+    std::memcpy(P.cam, cam, sizeof(float) * 12);
+    P.pixel_ids = (const uint32_t*)c->d_pixels.p;
+    P.n_pixels = c->n_pixels;
+    P.rng_state = (uint32_t*)c->d_rng.p;
+    P.accum = (float*)c->d_accum.p;
+    P.out_rgb = (float*)d_out_rgb;
+    P.out_rgba8 = (uint32_t*)d_out_rgba8;
+    P.counters = f.use_count ? (PtCounters*)c->d_counters.p : nullptr;
+    P.width = W;
+    P.height = H;
+    P.max_samples = max_samples;
+    P.max_depth = max_depth;
+    P.ring = (uint32_t*)c->d_ring.p;
+    P.ring_tail = c->d_laps.p ? (uint32_t*)c->d_laps.p + 64 : nullptr;
+    P.error_flag = (uint32_t*)c->d_laps.p;
+    P.lap_ticks = (unsigned long long*)((char*)c->d_laps.p + c->lap_ticks_ofs);
+    P.timeline = c->timeline;
+    if (c->latency && f.sorted) P.dbg_cost = (uint8_t*)c->d_cost.p;
+    P.census_mode = c->census_mode;
+    P.chunk_spp = f.sc.chunk;
+    P.n_chunks = f.sc.n_chunks;
+    P.n_full = f.sc.n_full;
+    for (int i = 0; i < PT_MAX_TAIL_CHUNKS; ++i) P.tail_len[i] = f.sc.tail_len[i];
+    P.n_tickets = c->n_pixels * (uint32_t)f.sc.n_chunks;
+    P.ns_express = f.ns_express;
+}
+
+// What launch l of the frame changes in P: its samples, and with a cost pre-pass (sorted) launch 0 is that pre-pass over the queue in
+// shard order, one chunk per pixel, and launch 1 everything else over the cost-ordered queue, expensive pixels first.
+void launch_params(pt_ctx* c, const FramePlan& f, int l, int max_samples, PtKernelParams& P)
+{
+    P.queue_head = (uint32_t*)c->d_heads.p + PT_HEADS_WORDS * l;
+    if (!f.sorted) {
+        P.sample_begin = l * f.S;
+        P.sample_count = std::min(f.S, max_samples - l * f.S);
+        return;
+    }
+    const bool pre = l == 0;
+    const int n_chunks = f.sc.n_chunks;
+    P.sample_begin = pre ? 0 : f.pre;
+    P.sample_count = pre ? f.pre : max_samples - f.pre;
+    P.pixel_ids = pre ? (const uint32_t*)c->d_pixels.p : (const uint32_t*)c->d_sorted.p;
+    P.cost_out = pre ? (uint8_t*)c->d_cost.p : nullptr;
+    P.dbg_start = (!pre && c->latency) ? (uint32_t*)c->d_dbg_start.p : nullptr;
+    P.lap_ticks = (unsigned long long*)((char*)c->d_laps.p + c->lap_ticks_ofs) + (pre ? PT_LAP_REGION(n_chunks) : 0); // the pre-pass's block follows the main launch's
+    P.ring_tail = (uint32_t*)c->d_laps.p + 64 + (pre ? n_chunks : 0); // the pre-pass only uses its [1]: the spare counter
+    P.chunk_spp = pre ? P.sample_count : f.sc.chunk;
+    P.n_chunks = pre ? 1 : n_chunks;
+    P.n_full = pre ? 1 : f.sc.n_full;
+    P.n_tickets = pre ? c->n_pixels : (c->n_pixels - f.n_express) * (uint32_t)n_chunks;
+    P.n_express = pre ? 0 : f.n_express;
+    P.express_waves = pre ? 0 : f.express_waves;
+    // the tier plan decides on the device: pixels by cost class (then none of the above is used), or the ring schedule as prepared
+    P.tiers = (!pre && f.tiers) ? (const uint32_t*)c->d_tiers.p : nullptr;
+    if (!pre && f.tiers) P.ring_grid = f.ring_grid;
+}
+
+// End of a frame, after its last launch (f == nullptr: a rank that owns no pixel and launched nothing): what pt_synchronize, pt_get_stats
+// and the diagnostics readers look at.  The kernel's own figures (registers, block, LDS) stay those of the last frame that ran one.
+int finish_frame(pt_ctx* c, hipStream_t stream, int W, int H, const FramePlan* f, int stack_entries)
+{
+    HIP_TRY(c, hipEventRecord(c->ev1, stream));
+    c->ev_pending = true;
+    c->flag_pending = f != nullptr;
+    c->last_stream = stream;
+    c->last_launches = f ? f->n_launch : 0;
+    c->last_sorted = f && f->sorted;
+    c->last_w = W;
+    c->last_h = H;
+    c->stats.express_pixels = f ? (int32_t)f->n_express : 0;
+    c->stats.whole_pixels = f && f->tiers ? (int32_t)c->n_pixels : 0;
+    c->stats.prepass_spp = f && f->sorted ? f->pre : 0;
+    c->stats.grid = f ? f->grid : 0;
+    if (!f) return PT_OK;
+    c->stats.vgprs = f->geo.vgprs;
+    c->stats.kernel_variant = f->variant;
+    c->stats.lds_bytes = (int)f->geo.lds_bytes;
+    c->stats.block = f->geo.block;
+    c->stats.stack_entries = stack_entries;
+    return PT_OK;
+}
+
+} // namespace
+
+extern "C" {
+
 int pt_render_device(pt_ctx* c, const pt_camera* cam, int32_t W, int32_t H, int32_t max_samples, int32_t max_depth, void* d_out_rgb,
                      void* d_out_rgba8, void* stream_v)
 {
@@ -709,337 +1002,35 @@ int pt_render_device(pt_ctx* c, const pt_camera* cam, int32_t W, int32_t H, int3
         HIP_TRY(c, hipEventRecord(c->ev0, stream));
         HIP_TRY(c, hipMemsetAsync(d_out_rgb, 0, (size_t)W * H * 3 * sizeof(float), stream));
         if (d_out_rgba8) HIP_TRY(c, hipMemsetAsync(d_out_rgba8, 0, (size_t)W * H * 4, stream));
-        HIP_TRY(c, hipEventRecord(c->ev1, stream));
-        c->ev_pending = true;
-        c->flag_pending = false;
-        c->last_stream = stream;
-        c->last_launches = 0;
-        c->last_sorted = false;
-        c->last_w = W;
-        c->last_h = H;
-        c->stats.express_pixels = 0;
-        c->stats.whole_pixels = 0;
-        c->stats.prepass_spp = 0;
-        c->stats.grid = 0;
+        if ((rc = finish_frame(c, stream, W, H, nullptr, 0))) return rc;
         if (c->count && c->d_counters.p) HIP_TRY(c, hipMemsetAsync(c->d_counters.p, 0, sizeof(PtCounters), stream));
         return PT_OK;
     }
 
-    // kernel 1 (lane-per-pixel): optional spp chunks = separate launches.  kernel 2 (wavefront): ONE persistent launch that
-    // walks (pixel, chunk) tickets; spp_per_launch, if set, becomes its chunk size so that the resumability tests cover it.
     PtKernelParams P;
-    fill_params(c, P);
-    {   // the fma form of the slab test (pt_kernel.hip, node4_step) displaces a plane by |o| 2^-24; the boxes are padded by 1e-5 x the scene
-        // extent (bvh.pad): exact form when the camera is so far from the origin that this would eat a quarter of the padding
-        const float reach = c->bvh.pad * 4194304.0f; // pad x 2^22 = 42 scene extents
-        float far_o = 0.0f;
-        for (int a = 0; a < 3; ++a) far_o = std::max(far_o, std::fabs(cam->origin[a]));
-        P.box_exact = (c->box_exact > 0 || (c->box_exact < 0 && !(far_o <= reach))) ? 1 : 0;
-    }
-    if (c->kernel == 2 && c->quad && !c->nodes4.empty()) { // the wavefront kernel walks the quad nodes: own root and stack bound
-        P.nodes4 = (const PtNode4*)c->d_nodes4.p;
-        P.root = c->root4;
-        P.stack_entries = 3 * c->depth4 + 1;
-    }
-    if (c->kernel == 2 && c->groups && !c->nodes8.empty()) { // group walk of sparse waves (oct nodes)
-        P.nodes8 = (const PtNode8*)c->d_nodes8.p;
-        P.root8 = c->root8;
-        P.groups = c->groups;
-    }
-
-    // Launch geometry.  The wavefront kernel keeps `ns` pixels in flight per wave; shrink ns when the image is too small to give
-    // every resident wave a full set (e.g. 512x512 over 4096 waves), otherwise use the default.
-    const int group_entries = P.nodes8 ? 7 * c->depth8 + 1 : 0;
-    size_t lds = 0, state_words = 0;
-    int vg = 0, sg = 0, slds = 0, occ = 0, block = 0, ns = 0;
-    static const int default_ns = [] { const char* e = getenv("PT_DEFAULT_NS"); const int v = e ? atoi(e) : 0; return v >= 16 && v <= 252 ? v : 96; }(); // (A/B builds of tools/)
-    int want_ns = c->slots_per_wave > 0 ? c->slots_per_wave : default_ns; // 16 waves/CU up to 104; 64..255 swept on C4 (profiles/r01_summary.md), 88..104 within 1 %
-    // variant of the launch: the wavefront kernel's product instance (2) unless it needs scratch in this build - then its fallback
-    // instance with the larger register budget (3): slower (12 instead of 16 waves per CU), the same arithmetic
-    // (the one-level walk over PtNode[] - option quad = 0, or a tree too deep for the quad walk's stack bound - is compiled into the
-    // instrumented instance only: the product instance is kept small for the instruction cache)
-    const int use_count = (c->count || (c->kernel == 2 && !P.nodes4)) ? 1 : 0;
-    int variant = c->kernel == 2 && c->fallback && !use_count ? 3 : c->kernel;
-    {
-        hipError_t ge = pt_kernel_geometry(variant, use_count, P.stack_entries, group_entries, want_ns, P.lobe_bins, P.box_exact, &block, &lds, &ns, &state_words, &vg, &occ, &P.lds_levels);
-        if (ge == hipErrorInvalidConfiguration && variant == 2 && !use_count) {
-            variant = 3;
-            ge = pt_kernel_geometry(variant, use_count, P.stack_entries, group_entries, want_ns, P.lobe_bins, P.box_exact, &block, &lds, &ns, &state_words, &vg, &occ, &P.lds_levels);
-        }
-        if (ge == hipErrorInvalidConfiguration)
-            return fail(c, PT_E_LIMIT, use_count ? "the instrumented instance of the render kernel needs scratch in this build; such builds rendered wrong pixels and are refused (pt_kernel.hip; tests/test_abi_host.py reads hipcc's resource report)"
-                                                 : "this build of the render kernel spills registers to scratch even in its fallback instance; such builds rendered wrong pixels and are refused (pt_kernel.hip)");
-        HIP_TRY(c, ge);
-    }
-    if (c->kernel == 2 && c->slots_per_wave == 0 && occ > 0) {
-        // small images: fewer slots per wave so that at least 8 waves per CU have pixels (never below 64)
-        long fit = (long)c->n_pixels / ((long)c->num_cus * 8);
-        if (fit < want_ns) {
-            want_ns = (int)std::max(64L, fit);
-            HIP_TRY(c, pt_kernel_geometry(variant, use_count, P.stack_entries, group_entries, want_ns, P.lobe_bins, P.box_exact, &block, &lds, &ns, &state_words, &vg, &occ, &P.lds_levels));
-        }
-    }
-    if (occ < 1) return fail(c, PT_E_LIMIT, "render kernel does not fit a CU (LDS %zu bytes, BVH depth %d)", lds, c->bvh.depth);
-    int bpc = c->blocks_per_cu > 0 ? std::min(c->blocks_per_cu, occ) : occ;
-    long want = ((long)c->n_pixels + ns - 1) / ns; // never more path slots than pixels: a pixel's chunks are sequential
-    if (c->kernel == 1) want = ((long)c->n_pixels + block - 1) / block;
-    int grid = (int)std::max(1L, std::min(want, (long)c->num_cus * bpc));
-    int pre = c->prepass_spp > 0 ? c->prepass_spp : 8; // samples of the cost pre-pass
-    const bool sorted = c->kernel == 2 && c->schedule == 1 && c->spp_per_launch == 0 && max_samples >= 4 * pre && max_samples <= 65535;
-    // Whole-pixel schedule (pt_kernel.hip, TIERS): when every pixel can have a path slot from the start, the main launch hands out
-    // pixels instead of (pixel, chunk) tickets, and every wave serves one cost class with as few pixels as that class needs - the plan
-    // is made on the device from the histogram of the counting sort (pt_plan_tiers_kernel).  Option "whole": -1 automatic, 0 never.
-    bool tiers = false;
-    int ring_grid = 0;
-    if (sorted && P.nodes8 && c->whole != 0 && c->slots_per_wave == 0 && occ > 0) {
-        const long capacity = (long)c->num_cus * bpc;
-        for (int nsd = 96; nsd <= 104 && !tiers; nsd += 8) { // 16 waves per CU up to 104 slots
-            if (c->whole < 1 && (long)c->n_pixels + (long)PT_MAX_TIERS * nsd > capacity * nsd) continue; // (one partly filled wave per class)
-            want_ns = nsd;
-            HIP_TRY(c, pt_kernel_geometry(variant, use_count, P.stack_entries, group_entries, want_ns, P.lobe_bins, P.box_exact, &block, &lds, &ns, &state_words, &vg, &occ, &P.lds_levels));
-            if (occ >= bpc && ns == nsd) {
-                tiers = true;
-                ring_grid = (int)std::max(1L, std::min(((long)c->n_pixels + ns - 1) / ns, capacity)); // what the ring schedule would launch
-                grid = (int)capacity;
-            }
-        }
-        if (!tiers) {
-            want_ns = default_ns;
-            HIP_TRY(c, pt_kernel_geometry(variant, use_count, P.stack_entries, group_entries, want_ns, P.lobe_bins, P.box_exact, &block, &lds, &ns, &state_words, &vg, &occ, &P.lds_levels));
-        }
-    }
-    // the tier plan lives on the cost estimate: twice the samples (1/8 shard of C4 218 -> 201 ms; a throughput-bound frame gains nothing)
-    if (tiers && c->prepass_spp == 0 && max_samples >= 4 * 16) pre = 16;
-    uint32_t n_express = 0;
-    int express_waves = 0;
-    if (state_words) {
-        if ((rc = ensure(c, c->d_slots, state_words * 4 * (size_t)grid))) return rc;
-        P.slot_state = (uint32_t*)c->d_slots.p;
-    }
-    P.ns = ns;
-
-    // Chunk schedule of one wavefront launch over `total` samples per pixel: n_full chunks of `chunk` samples, then the rest in
-    // halving chunks (rem/2, rem/4, ... >= chunk_tail_min).  A frame ends when its slowest in-flight work item ends, so the
-    // last items must be short (profiles/r01_summary.md, "wind-down").
-    struct Schedule { int chunk = 0, n_full = 0, n_chunks = 1, tail_len[PT_MAX_TAIL_CHUNKS] = {}; };
-    int tail_min = c->chunk_tail_min >= 0 ? c->chunk_tail_min : 16; // smallest chunk of the halving tail (automatic: set per schedule below)
-    auto make_schedule = [&](int total, int chunk, int rem_min) {
-        Schedule sc;
-        sc.chunk = std::max(1, std::min(chunk, total));
-        sc.n_full = total / sc.chunk;
-        int rem = total - sc.n_full * sc.chunk;
-        if (tail_min > 0 && sc.n_full > 0 && rem < rem_min) { --sc.n_full; rem += sc.chunk; }
-        int n_tail = 0;
-        while (rem > 0) {
-            int len = rem;
-            if (tail_min > 0 && rem > tail_min && n_tail < PT_MAX_TAIL_CHUNKS - 1) len = std::max(tail_min, (rem + 1) / 2);
-            sc.tail_len[n_tail++] = len;
-            rem -= len;
-        }
-        sc.n_chunks = sc.n_full + n_tail;
-        return sc;
-    };
-    // kernel 1 (lane-per-pixel): optional spp chunks = separate launches.
-    // Wavefront kernel, schedule 1 (default): a short cost pre-pass (prepass_spp samples of every pixel, rays counted), a
-    // counting sort of the pixel queue by that cost, then ONE persistent launch over the cost-ordered queue whose first chunk
-    // is sticky_pct % of the remaining samples (a slot keeps its pixel, no hand-offs, expensive pixels start first) and whose
-    // last samples go round in halving chunks through the per-chunk rings, so that the frame ends on ~n_pixels short work items.
-    // schedule 0 (or spp_per_launch, which the resumability tests use): one launch, chunk_spp chunks + halving tail.
-    // All schedules give the same image bit for bit (a pixel's stream does not depend on who renders it, or when).
-    int S, n_launch;
-    Schedule main_sc;
-    if (c->kernel == 1) {
-        S = c->spp_per_launch > 0 ? std::min(c->spp_per_launch, max_samples) : max_samples;
-        S = std::min(S, 65535);
-        n_launch = (max_samples + S - 1) / S;
-    } else {
-        S = max_samples;
-        n_launch = sorted ? 2 : 1;
-        if (sorted) {
-            const int rest = max_samples - pre;
-            // Share of a pixel's remaining samples that its first slot renders in one go.  With many more pixels than slots the
-            // frame is throughput-bound and hand-offs are pure overhead: 80 %; with fewer pixels per slot 50-65 % (a launch whose
-            // pixels all have a slot and whose costs have a tail runs the tier schedule instead).
-            int sticky = c->sticky_pct;
-            if (sticky < 1) {
-                const double ratio = (double)c->n_pixels / ((double)c->num_cus * (double)bpc * (double)ns);
-                sticky = (int)std::min(80.0, 50.0 + 6.0 * ratio); // (rounds 1-2, queue ordered by rays: 10-75, rising with the ratio; re-swept with the
-                                                                 // queue ordered by time: C4 80, 1/2 shard and C3 65, 1/4 shard 50-65, C2 60 - r3_ab57/58.log)
-            }
-            // With the queue ordered by the TIME of a pixel's samples the hand-offs of the tail buy little and every lap is a barrier of
-            // sorts: the last quarter goes in two chunks, not five (C4 528 -> 500 ms, C3 161 -> 153; smallest tail chunk 16 / 32 / 64 / 128
-            // of 1016 samples: 528 / 515 / 505 / 498 ms; profiles/r03_logs/r3_ab54.log).
-            if (c->chunk_tail_min < 0) tail_min = std::max(16, rest / 8);
-            const int big = std::max(1, (int)((int64_t)rest * sticky / 100));
-            main_sc = make_schedule(rest, big, rest - big);
-            if ((rc = ensure(c, c->d_cost, (size_t)W * H))) return rc; // cost image; zero where this rank owns nothing
-            if ((rc = ensure(c, c->d_bucket, (size_t)c->n_pixels))) return rc;
-            HIP_TRY(c, hipMemsetAsync(c->d_cost.p, 0, (size_t)W * H, stream));
-            if ((rc = ensure(c, c->d_sorted, (size_t)c->n_pixels * 4))) return rc;
-            if ((rc = ensure(c, c->d_sort_scratch, pt_sort_scratch_bytes(c->n_pixels)))) return rc;
-        } else {
-            const int chunk = std::min(c->spp_per_launch > 0 ? c->spp_per_launch : c->chunk_spp, std::min(max_samples, 65535));
-            main_sc = make_schedule(max_samples, chunk, 1);
-        }
-        const int n_chunks = main_sc.n_chunks;
-        if ((uint64_t)c->n_pixels * (uint64_t)n_chunks >= 0xfff00000ull) return fail(c, PT_E_LIMIT, "too many (pixel, chunk) tickets");
-        if (n_chunks > 255 || c->n_pixels >= (1u << 24)) return fail(c, PT_E_LIMIT, "the wavefront kernel needs n_chunks <= 255 and < 2^24 pixels per rank (raise chunk_spp)");
-        // one ring of ready pixels per chunk index: ring c holds, in completion order of chunk c - 1, the pixels whose chunk c
-        // may start.  d_laps = watchdog flag + one fill counter per ring.
-        // Layout (never a plain store in a cache line that also holds device-scope atomics): [0] watchdog flag | +256 B: ring fill
-        // counters (n_chunks + 1, + the pre-pass's spare) | 256-B aligned: diagnostics timelines of the two launches.
-        c->lap_ticks_ofs = ((256 + (size_t)(n_chunks + 3) * 4 + 255) / 256) * 256;
-        const size_t laps_bytes = c->lap_ticks_ofs + ((size_t)PT_LAP_REGION(n_chunks) + (size_t)PT_LAP_REGION(1)) * 8;
-        if ((rc = ensure(c, c->d_laps, laps_bytes))) return rc;
-        if ((rc = ensure(c, c->d_ring, (size_t)c->n_pixels * 4 * (size_t)n_chunks))) return rc;
-        HIP_TRY(c, hipMemsetAsync(c->d_laps.p, 0, laps_bytes, stream));
-        if (n_chunks > 1) HIP_TRY(c, hipMemsetAsync(c->d_ring.p, 0, (size_t)c->n_pixels * 4 * (size_t)n_chunks, stream));
-    }
-    const int n_chunks = main_sc.n_chunks;
-    if ((rc = ensure(c, c->d_heads, (size_t)n_launch * PT_HEADS_WORDS * 4))) return rc; // per launch: the ticket counter, the express counter 256 bytes on, the tier counters
-    HIP_TRY(c, hipMemsetAsync(c->d_heads.p, 0, (size_t)n_launch * PT_HEADS_WORDS * 4, stream));
-    if (tiers && (rc = ensure(c, c->d_tiers, (1 + PT_MAX_TIERS * PT_TIER_WORDS) * 4))) return rc;
-    HIP_TRY(c, hipMemsetAsync(d_out_rgb, 0, (size_t)W * H * 3 * sizeof(float), stream));
-    if (d_out_rgba8) HIP_TRY(c, hipMemsetAsync(d_out_rgba8, 0, (size_t)W * H * 4, stream));
-    if (n_launch > 1 || n_chunks > 1) {
-        if ((rc = ensure(c, c->d_rng, (size_t)W * H * 4))) return rc;
-        if ((rc = ensure(c, c->d_accum, (size_t)W * H * 12))) return rc;
-    }
-    if (use_count) {
-        if ((rc = ensure(c, c->d_counters, sizeof(PtCounters)))) return rc;
-        HIP_TRY(c, hipMemsetAsync(c->d_counters.p, 0, sizeof(PtCounters), stream));
-    }
-
-    std::memcpy(P.cam, cam, sizeof(float) * 12);
-    P.pixel_ids = (const uint32_t*)c->d_pixels.p;
-    P.n_pixels = c->n_pixels;
-    P.rng_state = (uint32_t*)c->d_rng.p;
-    P.accum = (float*)c->d_accum.p;
-    P.out_rgb = (float*)d_out_rgb;
-    P.out_rgba8 = (uint32_t*)d_out_rgba8;
-    P.counters = use_count ? (PtCounters*)c->d_counters.p : nullptr;
-    P.width = W;
-    P.height = H;
-    P.max_samples = max_samples;
-    P.max_depth = max_depth;
-    P.ring = (uint32_t*)c->d_ring.p;
-    P.ring_tail = c->d_laps.p ? (uint32_t*)c->d_laps.p + 64 : nullptr;
-    P.error_flag = (uint32_t*)c->d_laps.p;
-    P.lap_ticks = (unsigned long long*)((char*)c->d_laps.p + c->lap_ticks_ofs);
-    c->last_chunks = n_chunks;
-    P.cost_out = nullptr;
-    P.timeline = c->timeline;
-    P.dbg_start = nullptr;
-    P.dbg_cost = nullptr;
-    if (c->latency && sorted) {
-        if ((rc = ensure(c, c->d_dbg_start, (size_t)W * H * 8))) return rc; // + rays per pixel (instrumented instance)
-        HIP_TRY(c, hipMemsetAsync(c->d_dbg_start.p, 0, (size_t)W * H * 8, stream));
-        P.dbg_cost = (uint8_t*)c->d_cost.p;
-    }
-    P.census_mode = c->census_mode;
-    P.chunk_spp = main_sc.chunk;
-    P.n_chunks = n_chunks;
-    P.n_tickets = c->n_pixels * (uint32_t)n_chunks;
-    // Express pixels (pt_kernel.hip, take_ticket): the most expensive entries of the cost-ordered queue get waves of their own when the
-    // frame is bound by its longest sample chains, i.e. when (nearly) every pixel is in flight from the start - few pixels per path slot
-    // (a shard of a multi-GPU frame, a small image).  A throughput-bound frame (many pixels per slot) has none: sparse waves would only
-    // take wave slots from it.  Options "express_permille" (-1 = automatic: 10 per mille up to 1.5 pixels per slot, 0 from 4),
-    // "ns_express" (8 pixels per express wave), at most an eighth of the waves.
-    if (sorted && P.nodes8 && n_chunks <= 254 && (uint64_t)c->n_pixels * (uint64_t)n_chunks < 0xE0000000ull) {
-        int& rgrid = tiers ? ring_grid : grid; // the workgroups of the ring schedule (with a tier plan the launch has all resident ones)
-        const double ratio = (double)c->n_pixels / ((double)rgrid * (double)ns);
-        double permille = c->express_permille >= 0 ? (double)c->express_permille : (ratio <= 1.5 ? 10.0 : (ratio >= 4.0 ? 0.0 : 10.0 * (4.0 - ratio) / 2.5));
-        const int nse = std::max(1, std::min(c->ns_express, ns));
-        uint64_t want = (uint64_t)((double)c->n_pixels * permille / 1000.0);
-        const int capacity = c->num_cus * bpc;
-        // at most an eighth of the ring schedule's waves, or what the bulk leaves free.  (Round 4 tried up to 60 % of the waves for 1-15 % of the
-        // pixels at 8-48 per wave, also with the grid oversubscribed by the express waves: world 2 351 -> 400-470 ms, world 4 269 -> 300-370,
-        // profiles/r04_notes.md 5.)
-        const int cap_waves = std::max(rgrid / 8, std::min(capacity / 2, capacity - rgrid));
-        want = std::min<uint64_t>(want, (uint64_t)cap_waves * (uint64_t)nse);
-        if (want > 0 && want < c->n_pixels) {
-            n_express = (uint32_t)want;
-            express_waves = (int)((want + (uint64_t)nse - 1) / (uint64_t)nse);
-            P.ns_express = nse;
-            // wave slots the bulk does not fill (a shard, a small image) hold the express waves on top of the bulk's
-            rgrid = std::min(capacity, (int)(((long)c->n_pixels - (long)n_express + ns - 1) / ns) + express_waves);
-            if (state_words) {
-                if ((rc = ensure(c, c->d_slots, state_words * 4 * (size_t)grid))) return rc;
-                P.slot_state = (uint32_t*)c->d_slots.p;
-            }
-        }
-    }
-    P.n_full = main_sc.n_full;
-    for (int i = 0; i < PT_MAX_TAIL_CHUNKS; ++i) P.tail_len[i] = main_sc.tail_len[i];
+    walk_params(c, cam, P);
+    FramePlan f;
+    if ((rc = plan_frame(c, P, max_samples, f))) return rc;
+    if ((rc = frame_buffers(c, f, W, H, d_out_rgb, d_out_rgba8, stream))) return rc;
+    frame_params(c, f, cam, W, H, max_samples, max_depth, d_out_rgb, d_out_rgba8, P);
 
     HIP_TRY(c, hipEventRecord(c->ev0, stream));
-    if (c->kernel == 2 && (rc = ensure(c, c->d_params, sizeof(PtKernelParams) * (size_t)n_launch))) return rc;
-    for (int l = 0; l < n_launch; ++l) {
-        P.queue_head = (uint32_t*)c->d_heads.p + PT_HEADS_WORDS * l;
-        P.sample_begin = l * S;
-        P.sample_count = std::min(S, max_samples - l * S);
-        if (sorted) { // launch 0: cost pre-pass in queue order; launch 1: everything else, expensive pixels first
-            P.sample_begin = l == 0 ? 0 : pre;
-            P.sample_count = l == 0 ? pre : max_samples - pre;
-            P.pixel_ids = l == 0 ? (const uint32_t*)c->d_pixels.p : (const uint32_t*)c->d_sorted.p;
-            P.cost_out = l == 0 ? (uint8_t*)c->d_cost.p : nullptr;
-            P.dbg_start = (l == 1 && c->latency) ? (uint32_t*)c->d_dbg_start.p : nullptr;
-            P.lap_ticks = (unsigned long long*)((char*)c->d_laps.p + c->lap_ticks_ofs) + (l == 0 ? PT_LAP_REGION(n_chunks) : 0); // the pre-pass's block follows the main launch's
-            P.ring_tail = (uint32_t*)c->d_laps.p + 64 + (l == 0 ? n_chunks : 0); // the pre-pass only uses its [1]: the spare counter
-            if (l == 0) { // one chunk per pixel
-                P.chunk_spp = P.sample_count;
-                P.n_chunks = 1;
-                P.n_full = 1;
-                P.n_tickets = c->n_pixels;
-                P.n_express = 0;
-                P.express_waves = 0;
-                P.tiers = nullptr;
-            } else {
-                P.chunk_spp = main_sc.chunk;
-                P.n_chunks = n_chunks;
-                P.n_full = main_sc.n_full;
-                P.n_express = n_express;
-                P.express_waves = express_waves;
-                P.n_tickets = (c->n_pixels - n_express) * (uint32_t)n_chunks;
-                if (tiers) { // the plan decides on the device: pixels by cost class (then none of the above is used), or the ring schedule as prepared
-                    P.tiers = (const uint32_t*)c->d_tiers.p;
-                    P.ring_grid = ring_grid;
-                }
-            }
-            if (l == 1) {
-                HIP_TRY(c, pt_launch_sort_pixels((const uint8_t*)c->d_cost.p, W, H, c->cost_radius, (const uint32_t*)c->d_pixels.p, (uint32_t*)c->d_sorted.p,
-                                                 c->n_pixels, (uint32_t)pre, (uint32_t*)c->d_sort_scratch.p, (uint8_t*)c->d_bucket.p, stream));
-                if (tiers) HIP_TRY(c, pt_launch_plan_tiers((const uint32_t*)c->d_sort_scratch.p, c->n_pixels, grid, ns, c->whole > 0, (uint32_t*)c->d_tiers.p, stream));
-                HIP_TRY(c, hipEventRecord(c->evm, stream));
-            }
+    for (int l = 0; l < f.n_launch; ++l) {
+        launch_params(c, f, l, max_samples, P);
+        if (f.sorted && l == 1) { // the queue in cost order (and the tier plan) from the pre-pass's cost image
+            HIP_TRY(c, pt_launch_sort_pixels((const uint8_t*)c->d_cost.p, W, H, c->cost_radius, (const uint32_t*)c->d_pixels.p, (uint32_t*)c->d_sorted.p,
+                                             c->n_pixels, (uint32_t)f.pre, (uint32_t*)c->d_sort_scratch.p, (uint8_t*)c->d_bucket.p, stream));
+            if (f.tiers) HIP_TRY(c, pt_launch_plan_tiers((const uint32_t*)c->d_sort_scratch.p, c->n_pixels, f.grid, f.geo.ns, c->whole > 0, (uint32_t*)c->d_tiers.p, stream));
+            HIP_TRY(c, hipEventRecord(c->evm, stream));
         }
         const PtKernelParams* dP = (const PtKernelParams*)c->d_params.p + l; // one block per launch: launch l+1's copy never races launch l
         if (c->kernel == 2) HIP_TRY(c, pt_launch_store_params(&P, (PtKernelParams*)dP, stream)); // by value: P is reused for the next launch
         // (with a tier plan prepared only the main launch has every resident workgroup; the pre-pass measures the pixels' costs in waves
         // as dense as the ring schedule's - C2 74.3 -> 71 ms, 1/8 shard 198 -> 194)
-        HIP_TRY(c, pt_launch_render(&P, dP, variant, (tiers && sorted && l == 0) ? ring_grid : grid, lds, stream, use_count));
+        HIP_TRY(c, pt_launch_render(&P, dP, f.variant, (f.tiers && l == 0) ? f.ring_grid : f.grid, f.geo.lds_bytes, stream, f.use_count));
     }
-    HIP_TRY(c, hipEventRecord(c->ev1, stream));
-    c->ev_pending = true;
-    c->flag_pending = true;
-    c->last_stream = stream;
-    c->last_launches = n_launch;
-    c->last_sorted = sorted;
-    c->last_w = W;
-    c->last_h = H;
-    c->stats.vgprs = vg;
-    c->stats.kernel_variant = variant;
-    c->stats.express_pixels = n_express;
-    c->stats.whole_pixels = tiers ? (int32_t)c->n_pixels : 0;
-    c->stats.prepass_spp = sorted ? pre : 0;
-    c->stats.sgprs = sg;
-    c->stats.lds_bytes = (int)lds + slds;
-    c->stats.block = block;
-    c->stats.grid = grid;
-    c->stats.stack_entries = P.stack_entries;
-    return PT_OK;
+    return finish_frame(c, stream, W, H, &f, P.stack_entries);
 }
-
 
 int pt_synchronize(pt_ctx* c)
 {

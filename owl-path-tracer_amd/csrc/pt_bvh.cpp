@@ -754,10 +754,7 @@ void pt_bvh_collapse4(const PtBvh& b, std::vector<PtNode4>* out, int32_t* root4,
     *root4 = b.root;
     *depth4 = 0;
     if (b.root < 0) return; // empty scene or a leaf as root: no quad nodes
-    {
-        const char* e = getenv("PT_COLLAPSE4_BY_AREA"); // A/B switch (tools/): 0 = the fixed two-level collapse of rounds 2-3
-        if (e ? e[0] != '0' : PT_COLLAPSE4_BY_AREA) { collapse4_by_area(b, out, root4, depth4); return; }
-    }
+    if (PT_COLLAPSE4_BY_AREA) { collapse4_by_area(b, out, root4, depth4); return; } // (A/B: make variant FLAGS=-DPT_COLLAPSE4_BY_AREA=1)
     struct Item { int32_t node2; int32_t idx4; int depth; };
     std::vector<Item> todo;
     out->emplace_back();

@@ -57,17 +57,13 @@
 #ifndef PT_QUAD_REPS
 #define PT_QUAD_REPS 1 // quad-node steps per burst (a quad step is two binary levels and up to three pushes)
 #endif
-#ifndef PT_WITH_LOBE_BINS
-#define PT_WITH_LOBE_BINS 0 // lobe-coherent hit passes (option "lobe_bins"): validated bit-exact, but they cost what they save, and their 2 KB of code cost
-                            // the product instance 1 % even when switched off (profiles/r04_notes.md) - `make lobebins` builds the library with them
-#endif
 #ifndef PT_TOPUP_MIN
 #define PT_TOPUP_MIN 8 // a shading pass with idle lanes also takes entries of the other queue when that holds at least this many (option "tune0"; > 64 = never):
                        // fewer, fuller passes - C4 497-500 -> 491-492 ms, C2 72.6-73.2 -> 70.8 (profiles/r04_notes.md); not with an environment map, whose
                        // miss shader (atan2, asin, a texel) is too long to run for a few topped-up lanes (C5: 3 194 -> 3 219)
 #endif
-#ifndef PT_PURE_MIN
-#define PT_PURE_MIN 24     // lanes the fullest lobe bin must fill for a hit pass over that bin alone (option "tune4")
+#ifndef PT_ALLOW_SCRATCH
+#define PT_ALLOW_SCRATCH 0 // 1: launch instances that spill to scratch (pt_kernel_geometry; only for investigating the spills)
 #endif
 #ifndef PT_RETIRE_MIN
 #define PT_RETIRE_MIN 16   // finished lanes that trigger a retire/refill pass (8..24 swept: +-1 %)
@@ -372,11 +368,11 @@ static inline int pt_wave_lds_stack(int stack_entries, int group_entries)
     const int a = stack_entries < PT_LDS_STACK ? stack_entries : PT_LDS_STACK, b = (group_entries + 7) / 8;
     return a > b ? a : b;
 }
-// bins: the four lobe bins of the hit pass (ns bytes each) + the lobe-code table (LOBE-COHERENT HIT PASSES)
-static inline size_t pt_wave_lds_bytes(int stack_entries, int group_entries, int ns, int bins)
+// LDS of a wave: its stack levels, the ray and state fields of its slots, and the three byte queues (rays, hits, misses), 16-byte aligned
+static inline size_t pt_wave_lds_bytes(int stack_entries, int group_entries, int ns)
 {
     return ((size_t)pt_wave_lds_stack(stack_entries, group_entries) * PT_WAVE + (size_t)(L_NFIELDS + S_NFIELDS) * ns) * 4 +
-           (((size_t)(bins ? 7 : 3) * ns + (bins ? PT_LOBE_TABLE * 4 : 0) + 15) & ~(size_t)15);
+           (((size_t)3 * ns + 15) & ~(size_t)15);
 }
 static_assert(PT_GROUP_STACK <= 8 * PT_LDS_STACK, "a group's stack is eight columns of the LDS stack area");
 static inline size_t pt_wave_state_words(int stack_entries)
@@ -391,10 +387,6 @@ struct WaveCtx {
     uint32_t* lray;   // LDS
     uint32_t* lstate; // LDS
     uint8_t *rayq, *hitq, *missq;
-    uint8_t* binq;          // lobe bins of the hit pass: binq[b * ns + i], b = predicted lobe (LOBE-COHERENT HIT PASSES, below)
-    const uint32_t* ltab;   // LDS copy of the per-material lobe codes (PT_LOBE_TABLE words)
-    uint32_t bin_head, bin_count; // ring heads / fills of the four bins, one byte each (ns <= 255)
-    int binned;             // items in the bins (hit_count counts the unclassified ones in hitq)
     int ns;
     int ray_head, ray_count, hit_head, hit_count, miss_head, miss_count, n_dead;
     bool miss_blocked; // the last miss pass only polled tickets whose predecessor chunk is still running
@@ -437,7 +429,7 @@ enum { PICK_NONE = 0, PICK_HIT = 1, PICK_MISS = 2 };
 __device__ __forceinline__ int pick_pass(const WaveCtx& w, bool starving)
 {
     const bool miss_ok = !w.miss_blocked;
-    const int hits = w.hit_count + w.binned; // hits waiting for shading: not yet classified + in the lobe bins
+    const int hits = w.hit_count; // hits waiting for shading
     if (hits >= w.full_batch) return PICK_HIT;
     if (miss_ok && w.miss_count >= w.full_batch) return PICK_MISS;
     if (w.ray_count < w.ray_low) {
@@ -471,91 +463,22 @@ __device__ __forceinline__ void shade_pass(const PtKernelParams& P, WaveCtx& w, 
     int n, n1 = 0, n2 = 0; // items of the pass: n1 from the queue it was called for, n2 topped up from the other one
     bool lane_miss = IS_MISS;
     int ps_slot = 0;
-    if (PT_WITH_LOBE_BINS && !IS_MISS && P.lobe_bins) {
-        // ---- LOBE-COHERENT HIT PASSES (round 4) ----------------------------------------------------------------------------------
-        // sample_disney picks ONE of four lobe bodies per hit from one draw against thresholds that depend on the material only
-        // (disney.cuh:31-63), and the bodies are long (GGX sampling + three Smith terms; GTR1 with pow / log; rough glass), so a hit
-        // pass over a mixed batch runs all of them back to back, each with the few lanes that chose it (C2: two bodies per pass at
-        // ~19 of 64 lanes each).  Here a hit is first CLASSIFIED - the material index travels with the hit (packed with the triangle
-        // id: tri_eval, retire), its lobe thresholds come from a 32-word LDS table, and the draw the shader will make next is peeked
-        // from the slot's RNG state without advancing it - and appended to the bin of its predicted lobe; the pass then shades ONE
-        // bin when that bin alone fills enough lanes (>= pure_min), else everything that is queued, bin by bin.  The shader itself is
-        // untouched and still decides everything from its own draw: a wrong prediction (9-bit thresholds; force_btdf, which needs
-        // the shading normal) costs divergence, never a different result, and a slot still has one item in flight, so the
-        // per-pixel RNG order (device.cu:226-243) is what it was.
-        uint32_t bh = w.bin_head, bc = w.bin_count;
-        while (w.hit_count > 0) { // classify the new arrivals (at most ns: two rounds)
-            const int nc = w.hit_count < PT_WAVE ? w.hit_count : PT_WAVE;
-            int lobe = -1, cslot = 0;
-            if (lane < nc) {
-                cslot = (int)w.hitq[w.wrap(w.hit_head + lane)];
-                const uint32_t code = w.ltab[LF(L_AZ, cslot) >> 24]; // material + 1 (0: material_data{} defaults), <= PT_LOBE_TABLE - 1
-                const uint32_t q9 = (16807u * GF(S_RNG, cslot) + 1013904223u) >> 23; // top 9 bits of the next draw (random.hpp:61-69)
-                const int prev = (int)((GF(S_PACK, cslot) >> 22) & 7u) - 1;
-                lobe = q9 < (code & 0x3ffu) ? kLobeMetallic : (q9 < ((code >> 10) & 0x3ffu) ? kLobeClearcoat : (q9 < ((code >> 20) & 0x3ffu) ? kLobeDiffuse : kLobeGlass));
-                if ((code & 0x80000000u) && prev == kLobeGlass) lobe = kLobeGlass; // inside a glass object: force_btdf (disney.cuh:39)
-                if (code & 0x40000000u) lobe = kLobeDiffuse;                       // emitter: no body runs at all - with the cheapest bin
-            }
-#pragma unroll
-            for (int b = 0; b < 4; ++b) {
-                const unsigned long long mb = __ballot(lobe == b);
-                const int cnt_b = (int)((bc >> (8 * b)) & 0xffu), head_b = (int)((bh >> (8 * b)) & 0xffu);
-                if (lobe == b) w.binq[b * ns + w.wrap(w.wrap(head_b + cnt_b) + rank_in(mb))] = (uint8_t)cslot;
-                bc += (uint32_t)popc64(mb) << (8 * b);
-            }
-            w.hit_head = w.wrap(w.hit_head + nc);
-            w.hit_count -= nc;
-            w.binned += nc;
-        }
-        // the fullest bin alone if it fills pure_min lanes, else all bins in turn
-        const int c0 = (int)(bc & 0xffu), c1 = (int)((bc >> 8) & 0xffu), c2 = (int)((bc >> 16) & 0xffu), c3 = (int)(bc >> 24);
-        int best = 0, cbest = c0;
-        if (c1 > cbest) { best = 1; cbest = c1; }
-        if (c2 > cbest) { best = 2; cbest = c2; }
-        if (c3 > cbest) { best = 3; cbest = c3; }
-        const int pure_min = P.tune[4] > 0 ? P.tune[4] : PT_PURE_MIN;
-        const bool pure = cbest >= pure_min && cbest >= w.min_batch;
-        int t0 = c0, t1 = c1, t2 = c2, t3 = c3; // items taken from each bin
-        if (pure) {
-            t0 = best == 0 ? (c0 < PT_WAVE ? c0 : PT_WAVE) : 0; t1 = best == 1 ? (c1 < PT_WAVE ? c1 : PT_WAVE) : 0;
-            t2 = best == 2 ? (c2 < PT_WAVE ? c2 : PT_WAVE) : 0; t3 = best == 3 ? (c3 < PT_WAVE ? c3 : PT_WAVE) : 0;
-        } else {
-            int room = PT_WAVE;
-            t0 = t0 < room ? t0 : room; room -= t0;
-            t1 = t1 < room ? t1 : room; room -= t1;
-            t2 = t2 < room ? t2 : room; room -= t2;
-            t3 = t3 < room ? t3 : room;
-        }
-        n = n1 = t0 + t1 + t2 + t3;
-        if (lane < n) {
-            const int b = lane < t0 ? 0 : (lane < t0 + t1 ? 1 : (lane < t0 + t1 + t2 ? 2 : 3));
-            const int i = lane - (b > 0 ? t0 : 0) - (b > 1 ? t1 : 0) - (b > 2 ? t2 : 0);
-            ps_slot = (int)w.binq[b * ns + w.wrap((int)((bh >> (8 * b)) & 0xffu) + i)];
-        }
-        const uint32_t h0 = (uint32_t)w.wrap((int)(bh & 0xffu) + t0), h1 = (uint32_t)w.wrap((int)((bh >> 8) & 0xffu) + t1),
-                       h2 = (uint32_t)w.wrap((int)((bh >> 16) & 0xffu) + t2), h3 = (uint32_t)w.wrap((int)(bh >> 24) + t3);
-        w.bin_head = h0 | (h1 << 8) | (h2 << 16) | (h3 << 24);
-        w.bin_count = bc - ((uint32_t)t0 | ((uint32_t)t1 << 8) | ((uint32_t)t2 << 16) | ((uint32_t)t3 << 24));
-        w.binned -= n;
-        if (COUNT) cn.lobe[7] += pure;
-    } else {
-        // the queue the pass was called for, topped up from the other one when that holds at least topup_min entries: the second half of
-        // a pass (sample accumulation, next camera ray / work item, state write-back) is the same for both kinds and costs as much
-        // as the hit shader itself, so lanes a half-empty batch leaves idle may as well serve the other queue (option "tune0")
-        uint8_t* q = IS_MISS ? w.missq : w.hitq;
-        uint8_t* q2 = IS_MISS ? w.hitq : w.missq;
-        const int q_head = IS_MISS ? w.miss_head : w.hit_head, q2_head = IS_MISS ? w.hit_head : w.miss_head;
-        const int q_count = IS_MISS ? w.miss_count : w.hit_count, q2_count = IS_MISS ? w.hit_count : w.miss_count;
-        n1 = q_count < PT_WAVE ? q_count : PT_WAVE;
-        const int topup_min = w.topup_min;
-        if (topup_min > 0 && topup_min <= PT_WAVE && q2_count >= topup_min && (IS_MISS || !w.miss_blocked)) n2 = q2_count < PT_WAVE - n1 ? q2_count : PT_WAVE - n1;
-        n = n1 + n2;
-        if (lane < n1) ps_slot = (int)q[w.wrap(q_head + lane)];
-        else if (lane < n) { ps_slot = (int)q2[w.wrap(q2_head + lane - n1)]; lane_miss = !IS_MISS; }
-        const int hit_taken = IS_MISS ? n2 : n1, miss_taken = IS_MISS ? n1 : n2;
-        w.hit_head = w.wrap(w.hit_head + hit_taken); w.hit_count -= hit_taken;
-        w.miss_head = w.wrap(w.miss_head + miss_taken); w.miss_count -= miss_taken;
-    }
+    // the queue the pass was called for, topped up from the other one when that holds at least topup_min entries: the second half of
+    // a pass (sample accumulation, next camera ray / work item, state write-back) is the same for both kinds and costs as much
+    // as the hit shader itself, so lanes a half-empty batch leaves idle may as well serve the other queue (option "tune0")
+    uint8_t* q = IS_MISS ? w.missq : w.hitq;
+    uint8_t* q2 = IS_MISS ? w.hitq : w.missq;
+    const int q_head = IS_MISS ? w.miss_head : w.hit_head, q2_head = IS_MISS ? w.hit_head : w.miss_head;
+    const int q_count = IS_MISS ? w.miss_count : w.hit_count, q2_count = IS_MISS ? w.hit_count : w.miss_count;
+    n1 = q_count < PT_WAVE ? q_count : PT_WAVE;
+    const int topup_min = w.topup_min;
+    if (topup_min > 0 && topup_min <= PT_WAVE && q2_count >= topup_min && (IS_MISS || !w.miss_blocked)) n2 = q2_count < PT_WAVE - n1 ? q2_count : PT_WAVE - n1;
+    n = n1 + n2;
+    if (lane < n1) ps_slot = (int)q[w.wrap(q_head + lane)];
+    else if (lane < n) { ps_slot = (int)q2[w.wrap(q2_head + lane - n1)]; lane_miss = !IS_MISS; }
+    const int hit_taken = IS_MISS ? n2 : n1, miss_taken = IS_MISS ? n1 : n2;
+    w.hit_head = w.wrap(w.hit_head + hit_taken); w.hit_count -= hit_taken;
+    w.miss_head = w.wrap(w.miss_head + miss_taken); w.miss_count -= miss_taken;
     const bool mine = lane < n;
     if (COUNT) { // (all four with constant indices and selected values: a dynamic index sends the counter block to scratch)
         const uint32_t m1 = IS_MISS ? 1u : 0u, nm = (uint32_t)(IS_MISS ? n1 : n2);
@@ -591,7 +514,7 @@ __device__ __forceinline__ void shade_pass(const PtKernelParams& P, WaveCtx& w, 
             if (COUNT) ++cn.rays;
             if (P.dbg_start && !P.cost_out) atomicAdd(P.dbg_start + (size_t)P.width * (size_t)P.height + (uint32_t)px + (uint32_t)P.width * (uint32_t)py, 1u); // diagnostics: rays per pixel
             v3 radiance;
-            const int tslot = lane_miss ? -1 : (int)(LF(L_AZ, ps_slot) & (PT_WITH_LOBE_BINS ? P.hit_slot_mask : 0xffffffffu)); // (the hit's material rides in the top byte: retire)
+            const int tslot = lane_miss ? -1 : (int)LF(L_AZ, ps_slot);
             const uint32_t scat0 = cn.scat;
             int r = shade_hit<COUNT>(P, P.materials, tslot, LFF(L_AX, ps_slot), LFF(L_AY, ps_slot), ps, radiance, cn);
             if (COUNT && !lane_miss) branch = r == SR_RETRY ? 5 : (cn.scat != scat0 ? ps.lobe : 4);
@@ -794,7 +717,7 @@ __device__ __forceinline__ int traverse_groups(const PtKernelParams& P, WaveCtx&
             if (fin_hit) {
                 LF(L_AX, pslot) = __float_as_uint(h.u);
                 LF(L_AY, pslot) = __float_as_uint(h.v);
-                LF(L_AZ, pslot) = (uint32_t)h.slot | (PT_WITH_LOBE_BINS ? (uint32_t)h.id << 24 & ~P.hit_slot_mask : 0u); // + material code of the hit (PtTri::id, packed)
+                LF(L_AZ, pslot) = (uint32_t)h.slot;
                 w.hitq[w.wrap(w.wrap(w.hit_head + w.hit_count) + rank_in(m_fh))] = (uint8_t)pslot;
             }
             if (fin_miss) w.missq[w.wrap(w.wrap(w.miss_head + w.miss_count) + rank_in(m_fm))] = (uint8_t)pslot;
@@ -972,12 +895,6 @@ __global__ void __launch_bounds__(PT_WAVE, WAVES) pt_render_wave_kernel(const Pt
     w.rayq = reinterpret_cast<uint8_t*>(lstate + S_NFIELDS * ns);
     w.hitq = w.rayq + ns;
     w.missq = w.hitq + ns;
-    w.binq = w.missq + ns;
-    uint32_t* ltab = reinterpret_cast<uint32_t*>(w.binq + ((PT_WITH_LOBE_BINS && P.lobe_bins) ? 4 * ns : 0)); // (4-byte aligned: ns is a multiple of 4 when the bins exist)
-    w.ltab = ltab;
-    if (PT_WITH_LOBE_BINS && P.lobe_bins && lane < PT_LOBE_TABLE) ltab[lane] = gp(P.lobe_codes)[lane];
-    w.bin_head = w.bin_count = 0u;
-    w.binned = 0;
     const PtNode* __restrict__ nodes = P.nodes;
     const PtNode4* __restrict__ nodes4 = P.nodes4;
     const bool quad = !COUNT || nodes4 != nullptr; // the product instances walk quad nodes only (pt_api.cpp launches the instrumented one otherwise): a compile-time fact there
@@ -1133,7 +1050,7 @@ __global__ void __launch_bounds__(PT_WAVE, WAVES) pt_render_wave_kernel(const Pt
                     if (fin_hit) {
                         LF(L_AX, pslot) = __float_as_uint(h.u);
                         LF(L_AY, pslot) = __float_as_uint(h.v);
-                        LF(L_AZ, pslot) = (uint32_t)h.slot | (PT_WITH_LOBE_BINS ? (uint32_t)h.id << 24 & ~P.hit_slot_mask : 0u); // + material code of the hit (PtTri::id, packed)
+                        LF(L_AZ, pslot) = (uint32_t)h.slot;
                         w.hitq[w.wrap(w.wrap(w.hit_head + w.hit_count) + rank_in(m_fh))] = (uint8_t)pslot;
                     }
                     if (fin_miss) w.missq[w.wrap(w.wrap(w.miss_head + w.miss_count) + rank_in(m_fm))] = (uint8_t)pslot;
@@ -1293,37 +1210,25 @@ extern "C" hipError_t pt_launch_render(const PtKernelParams* p, const PtKernelPa
 // Launch geometry of a render variant (1: lane per pixel, 2: wavefront kernel, 3: the wavefront kernel's 168-VGPR fallback
 // instance): block size, dynamic LDS bytes, pixels a block keeps in flight (ns is chosen here for the wavefront kernel), per-block
 // global state words, registers, occupancy.  hipErrorInvalidConfiguration: the instance needs scratch (see below).
-extern "C" hipError_t pt_kernel_geometry(int variant, int count, int stack_entries, int group_entries, int want_ns, int bins, int exact, int* block, size_t* lds_bytes, int* ns,
-                                         size_t* state_words_per_block, int* vgprs, int* max_blocks_per_cu, int* lds_levels)
+extern "C" hipError_t pt_kernel_geometry(int variant, int count, int stack_entries, int group_entries, int want_ns, int exact, PtGeometry* g)
 {
-    if (variant == 1) { // pt_kernel_aux.hip
-        *lds_levels = stack_entries;
-        *state_words_per_block = 0;
-        return pt_lane_kernel_geometry(count, stack_entries, block, lds_bytes, ns, vgprs, max_blocks_per_cu);
-    }
+    if (variant == 1) return pt_lane_kernel_geometry(count, stack_entries, g); // pt_kernel_aux.hip
     const void* fn = count ? (const void*)pt_render_wave_kernel<true, PT_COUNT_WAVES_PER_EU, false>
                      : variant == 3 ? (exact ? (const void*)pt_render_wave_kernel<false, PT_FALLBACK_WAVES, true> : (const void*)pt_render_wave_kernel<false, PT_FALLBACK_WAVES, false>)
                                     : (exact ? (const void*)pt_render_wave_kernel<false, PT_WAVES_PER_EU, true> : (const void*)pt_render_wave_kernel<false, PT_WAVES_PER_EU, false>);
-    int n = want_ns < 16 ? 16 : (want_ns > 255 ? 255 : want_ns);
-    if (bins) n = (n + 3) & ~3; // the lobe-code table follows the byte queues: keep it word aligned
-    if (n > 252) n = 252;
-    *block = PT_WAVE;
-    *ns = n;
-    *lds_bytes = pt_wave_lds_bytes(stack_entries, group_entries, n, bins);
-    *lds_levels = pt_wave_lds_stack(stack_entries, group_entries);
-    *state_words_per_block = pt_wave_state_words(stack_entries);
+    const int n = want_ns < 16 ? 16 : (want_ns > 252 ? 252 : want_ns);
+    g->block = PT_WAVE;
+    g->ns = n;
+    g->lds_bytes = pt_wave_lds_bytes(stack_entries, group_entries, n);
+    g->lds_levels = pt_wave_lds_stack(stack_entries, group_entries);
+    g->state_words = pt_wave_state_words(stack_entries);
     hipFuncAttributes fa;
     hipError_t e = hipFuncGetAttributes(&fa, fn);
     if (e != hipSuccess) return e;
-    // register spills: see pt_render_wave_kernel.  PT_ALLOW_SCRATCH=1 in the environment lifts the refusal for the experiment that
-    // investigates it (profiles/r02_spill_investigation.md); never set it in production
-    if (fa.localSizeBytes != 0 && !(getenv("PT_ALLOW_SCRATCH") && getenv("PT_ALLOW_SCRATCH")[0] == '1')) return hipErrorInvalidConfiguration;
-    *vgprs = fa.numRegs;
-    int nb = 0;
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, *block, *lds_bytes);
-    *max_blocks_per_cu = nb;
-    return e;
+    // register spills: see pt_render_wave_kernel.  A build with -DPT_ALLOW_SCRATCH=1 (make variant) lifts the refusal for the experiment
+    // that investigates it (profiles/r02_spill_investigation.md); never in production
+    if (fa.localSizeBytes != 0 && !PT_ALLOW_SCRATCH) return hipErrorInvalidConfiguration;
+    g->vgprs = fa.numRegs;
+    g->max_blocks_per_cu = 0;
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(&g->max_blocks_per_cu, fn, g->block, g->lds_bytes);
 }
-
-// does this build contain the lobe bins of the hit pass (option "lobe_bins")?
-extern "C" int pt_kernel_lobe_bins(void) { return PT_WITH_LOBE_BINS; }

@@ -153,7 +153,7 @@ __global__ void __launch_bounds__(PT_BLOCK) pt_debug_kernel(const PtKernelParams
         Hit h;
         Counters cn;
         closest_hit<false>(P, stack, V(x[0], x[1], x[2]), V(x[3], x[4], x[5]), h, cn);
-        y[0] = h.slot >= 0 ? 1.0f : 0.0f; y[1] = h.t; y[2] = h.u; y[3] = h.v; y[4] = __int_as_float(h.slot >= 0 ? (P.hit_slot_mask != 0xffffffffu ? h.id >> 8 : h.id) : -1);
+        y[0] = h.slot >= 0 ? 1.0f : 0.0f; y[1] = h.t; y[2] = h.u; y[3] = h.v; y[4] = __int_as_float(h.slot >= 0 ? h.id : -1);
         break;
     }
     case PT_OP_FRAME: {
@@ -193,20 +193,20 @@ extern "C" hipError_t pt_launch_render_lane(const PtKernelParams* p, int grid, s
     return hipGetLastError();
 }
 
-extern "C" hipError_t pt_lane_kernel_geometry(int count, int stack_entries, int* block, size_t* lds_bytes, int* ns, int* vgprs, int* max_blocks_per_cu)
+extern "C" hipError_t pt_lane_kernel_geometry(int count, int stack_entries, PtGeometry* g)
 {
     const void* fn = count ? (const void*)pt_render_kernel<true> : (const void*)pt_render_kernel<false>;
-    *block = PT_BLOCK;
-    *lds_bytes = (size_t)stack_entries * PT_BLOCK * 4;
-    *ns = PT_BLOCK;
+    g->block = PT_BLOCK;
+    g->ns = PT_BLOCK;
+    g->lds_bytes = (size_t)stack_entries * PT_BLOCK * 4;
+    g->lds_levels = stack_entries;
+    g->state_words = 0;
     hipFuncAttributes fa;
     hipError_t e = hipFuncGetAttributes(&fa, fn);
     if (e != hipSuccess) return e;
-    *vgprs = fa.numRegs;
-    int nb = 0;
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, *block, *lds_bytes);
-    *max_blocks_per_cu = nb;
-    return e;
+    g->vgprs = fa.numRegs;
+    g->max_blocks_per_cu = 0;
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(&g->max_blocks_per_cu, fn, g->block, g->lds_bytes);
 }
 
 extern "C" int pt_debug_block(void) { return PT_BLOCK; }

@@ -200,7 +200,7 @@ def _case(gpu, orc, scene_io, seed, large=False, path=None):
 
 def _context():
     gpu = B.Context(0)
-    for kv in os.environ.get("PT_FUZZ_OPTIONS", "").split():  # e.g. PT_LIB_PATH=.../libmi355pt_lobebins.so PT_FUZZ_OPTIONS="lobe_bins=1": a side build through the same cases
+    for kv in os.environ.get("PT_FUZZ_OPTIONS", "").split():  # e.g. PT_FUZZ_OPTIONS="fallback=1", or a side build (PT_LIB_PATH=...) through the same cases
         k, v = kv.split("=")
         gpu.set_option(k, int(v))
     return gpu
