@@ -2,7 +2,7 @@
 
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg import this module.
 The product (owl-path-tracer_amd) never does.  See oracle/pt_oracle.h for the parity note
-(PARITY UNPINNED: the reference ships no fixtures for this path and cannot be built here).
+(the reference's furnace images, and its own device code compiled for the CPU: oracle/reference.py).
 """
 import ctypes as C
 import os
