@@ -18,7 +18,7 @@
 
 // Slivers are never hit (part of the closest-hit definition; the oracle applies the same rule in its own words): a triangle
 // whose height over its longest edge is below 1e-5 of that edge - |e1 x e2|^2 <= 1e-10 * max|e|^4, in double - is collapsed to its first
-// vertex for the BVH and the triangle test (det = 0: the Moeller-Trumbore test rejects it for every ray).  Why: for such a needle the
+// vertex (the first finite one) for the BVH and the triangle test (det = 0: the Moeller-Trumbore test rejects it for every ray).  Why: for such a needle the
 // test's u, v, t are rounding noise and it reports "hits" far outside the triangle's bounding box, which a BVH walk does or does not see
 // depending on the order in which it visits the leaves (found by tests/test_gpu_fuzz.py, seed 794689: the oracle's walk and this library's
 // disagreed on one ray of 1.7e4 random scenes).  A height of < 100 ulp of the coordinates carries no geometry anyway.
@@ -32,7 +32,12 @@ static inline void pt_collapse_sliver(float* p)
     const double l1 = e1[0] * e1[0] + e1[1] * e1[1] + e1[2] * e1[2], l2 = e2[0] * e2[0] + e2[1] * e2[1] + e2[2] * e2[2], l3 = e3[0] * e3[0] + e3[1] * e3[1] + e3[2] * e3[2];
     const double L2 = l1 > l2 ? (l1 > l3 ? l1 : l3) : (l2 > l3 ? l2 : l3);
     if (!(n2 > 1e-10 * L2 * L2)) { // also NaN / infinite vertices
-        for (int k = 3; k < 9; ++k) p[k] = p[k % 3];
+        // to the first corner with finite coordinates (the origin if there is none): the leaf boxes stay finite with lo <= hi, which the
+        // octant-ordered slab test of the quad-node step needs (pt_kernel.hip, node4_step).  The point is never hit wherever it lies.
+        int f = 0;
+        while (f < 3 && !(std::isfinite(p[3 * f]) && std::isfinite(p[3 * f + 1]) && std::isfinite(p[3 * f + 2]))) ++f;
+        const float q[3] = {f < 3 ? p[3 * f] : 0.0f, f < 3 ? p[3 * f + 1] : 0.0f, f < 3 ? p[3 * f + 2] : 0.0f};
+        for (int k = 0; k < 9; ++k) p[k] = q[k % 3];
     }
 }
 #define PT_AUTO_PLOC_TRIS 64000000 // builder 3: the device PLOC builder beyond this many triangles (see pt_upload_scene)
@@ -784,6 +789,9 @@ int plan_frame(pt_ctx* c, const PtKernelParams& P, int max_samples, FramePlan& f
     // instrumented instance only: the product instance is kept small for the instruction cache)
     f.use_count = (c->count || (c->kernel == 2 && !P.nodes4)) ? 1 : 0;
     f.variant = c->kernel == 2 && c->fallback && !f.use_count ? 3 : c->kernel;
+    // the wavefront kernel's quad-node and leaf steps address their records with 32-bit byte offsets from the buffer base (node4_step, leaf_test)
+    if (c->kernel == 2 && (c->bvh.tris.size() * sizeof(PtTri) > 0xffffffffull || c->nodes4.size() * sizeof(PtNode4) > 0xffffffffull))
+        return fail(c, PT_E_LIMIT, "the wavefront kernel needs triangle records and quad nodes below 4 GiB each (%zu triangle slots, %zu quad nodes)", c->bvh.tris.size(), c->nodes4.size());
     // The wavefront kernel keeps `ns` pixels in flight per wave; shrink ns when the image is too small to give every resident wave a
     // full set (e.g. 512x512 over 4096 waves), otherwise use the default.
     const int group_entries = P.nodes8 ? 7 * c->depth8 + 1 : 0;
@@ -1164,15 +1172,22 @@ int pt_debug_quad_info(pt_ctx* c, int64_t out[8])
     for (const PtNode4& q : c->nodes4) {
         for (int k = 0; k < 4; ++k) {
             const int32_t r = q.child[k];
-            if (r >= 0) ++internal;
-            else if (r == -1) {
+            if (r == -1) {
                 ++empty;
                 for (int a = 0; a < 3; ++a)
                     if (!(q.lo[a][k] == INFINITY && q.hi[a][k] == INFINITY)) return fail(c, PT_E_LIMIT, "quad node: empty slot with a finite box");
-            } else {
+                continue;
+            }
+            if (r >= 0) ++internal;
+            else {
                 ++leaf_slots;
                 tris += (int64_t)(~(uint32_t)r & 7u);
             }
+            // the octant-ordered slab test (node4_step) takes the lo row as the entry plane for inv > 0 and the hi row for inv < 0: exact
+            // only for finite lo <= hi
+            for (int a = 0; a < 3; ++a)
+                if (!(std::isfinite(q.lo[a][k]) && std::isfinite(q.hi[a][k]) && q.lo[a][k] <= q.hi[a][k]))
+                    return fail(c, PT_E_LIMIT, "quad node: slot %d has a box that is not finite with lo <= hi on axis %d", k, a);
         }
     }
     for (const PtNode& nd : c->bvh.nodes) {

@@ -75,16 +75,27 @@ namespace {
 // Quad-node step (PtNode4, pt_types.h): the four grandchild boxes of a binary node in one 128-byte record - one cache line and
 // one memory round trip per TWO levels of the binary tree.  Slab test as in node_step, two packed pairs; the lane continues with
 // the nearest hit child and pushes the other hit children (in slot order; any visiting order gives the same closest hit).
-// The lane reads its own record with 7 x global_load_dwordx4 = 7 vL1D accesses per lane and step.  (Two validated experiments that did not
-// pay - whole-line cooperative fetches through an LDS staging area, 64-byte records with 8-bit planes - live in variants/.)
+// The lane reads its own record with 7 x global_load_dwordx4 = 7 vL1D accesses per lane and step, at 32-bit offsets from the wave-uniform
+// base (the host keeps the quad nodes below 4 GiB: pt_api.cpp).  (Two validated experiments that did not pay - whole-line cooperative
+// fetches through an LDS staging area, 64-byte records with 8-bit planes - live in variants/.)
 template <int STRIDE, int LDS_ENTRIES, bool CENSUS = false>
 __device__ __forceinline__ void node4_step(const PtNode4* __restrict__ nodes4, uint32_t* stack, uint32_t PT_AS1* ovf, v3 o, v3 inv, float tbest, int& cur, int& sp,
                                            const bool exact, uint32_t* n_nohit = nullptr, uint32_t* n_beyond = nullptr)
 {
     bool crossed = false; // CENSUS: the ray crosses some slot's box when the bound of the best hit is ignored
-    const size_t nb = (size_t)(uint32_t)cur * sizeof(PtNode4);
-    const f32x4 lx = ldg4(nodes4, nb), ly = ldg4(nodes4, nb + 16), lz = ldg4(nodes4, nb + 32);
-    const f32x4 hx = ldg4(nodes4, nb + 48), hy = ldg4(nodes4, nb + 64), hz = ldg4(nodes4, nb + 80), cf = ldg4(nodes4, nb + 96);
+    // Octant order: on each axis the ray enters a slab through the plane row that faces it - lo for inv > 0, hi for inv < 0 - and leaves
+    // through the other one, so the step fetches the rows as (entry, exit) pairs and needs no per-axis min / max.  Both slab forms below are
+    // monotone in the plane for a fixed inv (correctly rounded operations of a monotone function), so for lo <= hi the entry distance IS
+    // the minimum of the two and the exit distance the maximum, bit for bit; every non-empty slot has finite lo <= hi (the host and device
+    // builders pad finite boxes; pt_debug_quad_info checks it) and an empty slot {+inf, +inf} still misses (entry +inf or exit -inf).
+    // The sign bit picks the row: ray_inv never returns 0, NaN or an infinity, and d = -0 gives -PT_INV_MAX, whose sign matches.
+    const uint32_t ex = (uint32_t)(__float_as_int(inv.x) >> 31) & 48u; // 0 or 48: byte offset of the entry row from the lo row
+    const uint32_t ey = (uint32_t)(__float_as_int(inv.y) >> 31) & 48u;
+    const uint32_t ez = (uint32_t)(__float_as_int(inv.z) >> 31) & 48u;
+    const uint32_t rec = (uint32_t)cur * (uint32_t)sizeof(PtNode4);
+    const f32x4 nx4 = ldg4u(nodes4, rec + ex, 0), ny4 = ldg4u(nodes4, rec + ey, 16), nz4 = ldg4u(nodes4, rec + ez, 32);
+    const f32x4 fx4 = ldg4u(nodes4, rec + (ex ^ 48u), 0), fy4 = ldg4u(nodes4, rec + (ey ^ 48u), 16), fz4 = ldg4u(nodes4, rec + (ez ^ 48u), 32);
+    const f32x4 cf = ldg4u(nodes4, rec, 96);
     // Slab distances (round 4): fma(plane, 1/d, -(o/d)) - one packed fma per pair of planes instead of a subtraction and a multiplication
     // (24 of the step's ~150 VALU operations; C4 492 -> 484-486 ms, C3 149 -> 146).  Against (plane - o) * (1/d) the distance is off by
     // |o/d| 2^-24, i.e. the plane seems displaced by |o| 2^-24 in space: rays start on surfaces or at the camera, the boxes are padded by
@@ -97,60 +108,52 @@ __device__ __forceinline__ void node4_step(const PtNode4* __restrict__ nodes4, u
     const float nx = -(o.x * inv.x), ny = -(o.y * inv.y), nz = -(o.z * inv.z);
     const f32x2 nox = {nx, nx}, noy = {ny, ny}, noz = {nz, nz};
     const f32x2 pad = {1.0000004f, 1.0000004f};
-    float tn[4];
-    bool hit[4];
+    // Keys of the nearest-child choice: the entry distance's bits for a hit slot (a positive float: the bits order as unsigned integers),
+    // all ones for a miss - integer min / max and compares instead of selects of booleans.
+    const uint32_t kMiss = 0xffffffffu;
+    uint32_t key[4];
 #pragma unroll
     for (int p = 0; p < 2; ++p) { // slots {0, 1} and {2, 3}
-        const f32x2 lox = p ? (f32x2){lx.z, lx.w} : (f32x2){lx.x, lx.y}, loy = p ? (f32x2){ly.z, ly.w} : (f32x2){ly.x, ly.y};
-        const f32x2 loz = p ? (f32x2){lz.z, lz.w} : (f32x2){lz.x, lz.y}, hix = p ? (f32x2){hx.z, hx.w} : (f32x2){hx.x, hx.y};
-        const f32x2 hiy = p ? (f32x2){hy.z, hy.w} : (f32x2){hy.x, hy.y}, hiz = p ? (f32x2){hz.z, hz.w} : (f32x2){hz.x, hz.y};
-        f32x2 t0x, t1x, t0y, t1y, t0z, t1z;
+        const f32x2 enx = p ? (f32x2){nx4.z, nx4.w} : (f32x2){nx4.x, nx4.y}, eny = p ? (f32x2){ny4.z, ny4.w} : (f32x2){ny4.x, ny4.y};
+        const f32x2 enz = p ? (f32x2){nz4.z, nz4.w} : (f32x2){nz4.x, nz4.y}, exx = p ? (f32x2){fx4.z, fx4.w} : (f32x2){fx4.x, fx4.y};
+        const f32x2 exy = p ? (f32x2){fy4.z, fy4.w} : (f32x2){fy4.x, fy4.y}, exz = p ? (f32x2){fz4.z, fz4.w} : (f32x2){fz4.x, fz4.y};
+        f32x2 tnx, tfx, tny, tfy, tnz, tfz;
         if (exact) { // a compile-time constant in the product instances (see pt_render_wave_kernel: EXACT)
-            t0x = (lox - ox) * ix; t1x = (hix - ox) * ix;
-            t0y = (loy - oy) * iy; t1y = (hiy - oy) * iy;
-            t0z = (loz - oz) * iz; t1z = (hiz - oz) * iz;
+            tnx = (enx - ox) * ix; tfx = (exx - ox) * ix;
+            tny = (eny - oy) * iy; tfy = (exy - oy) * iy;
+            tnz = (enz - oz) * iz; tfz = (exz - oz) * iz;
         } else {
-            t0x = __builtin_elementwise_fma(lox, ix, nox); t1x = __builtin_elementwise_fma(hix, ix, nox);
-            t0y = __builtin_elementwise_fma(loy, iy, noy); t1y = __builtin_elementwise_fma(hiy, iy, noy);
-            t0z = __builtin_elementwise_fma(loz, iz, noz); t1z = __builtin_elementwise_fma(hiz, iz, noz);
+            tnx = __builtin_elementwise_fma(enx, ix, nox); tfx = __builtin_elementwise_fma(exx, ix, nox);
+            tny = __builtin_elementwise_fma(eny, iy, noy); tfy = __builtin_elementwise_fma(exy, iy, noy);
+            tnz = __builtin_elementwise_fma(enz, iz, noz); tfz = __builtin_elementwise_fma(exz, iz, noz);
         }
-        const float ta = fmax_hw(fmax_hw(fmin_hw(t0x.x, t1x.x), fmin_hw(t0y.x, t1y.x)), fmax_hw(fmin_hw(t0z.x, t1z.x), kTMin));
-        const float tb = fmax_hw(fmax_hw(fmin_hw(t0x.y, t1x.y), fmin_hw(t0y.y, t1y.y)), fmax_hw(fmin_hw(t0z.y, t1z.y), kTMin));
-        f32x2 tf = {fmin_hw(fmin_hw(fmax_hw(t0x.x, t1x.x), fmax_hw(t0y.x, t1y.x)), fmin_hw(fmax_hw(t0z.x, t1z.x), tbest)),
-                    fmin_hw(fmin_hw(fmax_hw(t0x.y, t1x.y), fmax_hw(t0y.y, t1y.y)), fmin_hw(fmax_hw(t0z.y, t1z.y), tbest))};
+        const float ta = fmax_hw(fmax_hw(tnx.x, tny.x), fmax_hw(tnz.x, kTMin));
+        const float tb = fmax_hw(fmax_hw(tnx.y, tny.y), fmax_hw(tnz.y, kTMin));
+        f32x2 tf = {fmin_hw(fmin_hw(tfx.x, tfy.x), fmin_hw(tfz.x, tbest)), fmin_hw(fmin_hw(tfx.y, tfy.y), fmin_hw(tfz.y, tbest))};
         tf = tf * pad;
-        tn[2 * p] = ta; tn[2 * p + 1] = tb;
-        hit[2 * p] = ta <= tf.x; hit[2 * p + 1] = tb <= tf.y;
+        key[2 * p] = ta <= tf.x ? __float_as_uint(ta) : kMiss;
+        key[2 * p + 1] = tb <= tf.y ? __float_as_uint(tb) : kMiss;
         if (CENSUS) { // instrumented instance: would the slot be hit without the bound of the best hit so far?
-            const float fa = fmin_hw(fmin_hw(fmax_hw(t0x.x, t1x.x), fmax_hw(t0y.x, t1y.x)), fmax_hw(t0z.x, t1z.x)) * 1.0000004f;
-            const float fb = fmin_hw(fmin_hw(fmax_hw(t0x.y, t1x.y), fmax_hw(t0y.y, t1y.y)), fmax_hw(t0z.y, t1z.y)) * 1.0000004f;
+            const float fa = fmin_hw(fmin_hw(tfx.x, tfy.x), tfz.x) * 1.0000004f;
+            const float fb = fmin_hw(fmin_hw(tfx.y, tfy.y), tfz.y) * 1.0000004f;
             crossed = crossed || ta <= fa || tb <= fb;
         }
     }
     const int r0 = __float_as_int(cf.x), r1 = __float_as_int(cf.y), r2 = __float_as_int(cf.z), r3 = __float_as_int(cf.w);
-    const float far_key = kTMax * 2.0f; // beyond every valid entry distance
-    const float k0 = hit[0] ? tn[0] : far_key, k1 = hit[1] ? tn[1] : far_key, k2 = hit[2] ? tn[2] : far_key, k3 = hit[3] ? tn[3] : far_key;
-    const bool b01 = k1 < k0, b23 = k3 < k2;
-    const float m01 = b01 ? k1 : k0, m23 = b23 ? k3 : k2;
-    const int r01 = b01 ? r1 : r0, r23 = b23 ? r3 : r2;
+    const bool b01 = key[1] < key[0], b23 = key[3] < key[2]; // the pair's second slot is the nearer one
+    const uint32_t m01 = b01 ? key[1] : key[0], M01 = b01 ? key[0] : key[1], m23 = b23 ? key[3] : key[2], M23 = b23 ? key[2] : key[3];
+    const int n01 = b01 ? r1 : r0, f01 = b01 ? r0 : r1, n23 = b23 ? r3 : r2, f23 = b23 ? r2 : r3; // nearer / farther child of each pair
     const bool in_b = m23 < m01; // the nearest hit is in slot pair {2, 3}
-    const int nearc = in_b ? r23 : r01;
-    const bool any = hit[0] || hit[1] || hit[2] || hit[3];
+    const int nearc = in_b ? n23 : n01;
+    const bool any = (in_b ? m23 : m01) != kMiss;
     if (CENSUS) { // steps that enter nothing, and of those the ones where the ray does cross a box: the node lies beyond the best hit
         *n_nohit += any ? 0u : 1u;
         *n_beyond += (!any && crossed) ? 1u : 0u;
     }
-    // push order: the two slots of the OTHER pair first, the nearest's sibling last (popped first): siblings share a parent box, so
-    // the sibling is usually the next nearest.  Three pushes at most.
-    // (of the other pair, the farther slot first)
-    const bool swap_o = in_b ? b01 : b23; // the other pair's second slot is the nearer one: push it second
-    const int oa = in_b ? r0 : r2, ob = in_b ? r1 : r3;
-    const bool ha = in_b ? hit[0] : hit[2], hb = in_b ? hit[1] : hit[3];
-    const int x1 = swap_o ? oa : ob, x2 = swap_o ? ob : oa;
-    const bool h1 = swap_o ? ha : hb, h2 = swap_o ? hb : ha;
-    const bool first_of_pair = in_b ? !b23 : !b01; // the nearest is the first slot of its pair
-    const int x3 = in_b ? (first_of_pair ? r3 : r2) : (first_of_pair ? r1 : r0);
-    const bool h3 = in_b ? (first_of_pair ? hit[3] : hit[2]) : (first_of_pair ? hit[1] : hit[0]);
+    // push order: the two slots of the OTHER pair first, the farther one first, then the nearest's sibling (popped first): siblings share a
+    // parent box, so the sibling is usually the next nearest.  Three pushes at most; a pushed key is a hit.
+    const int x1 = in_b ? f01 : f23, x2 = in_b ? n01 : n23, x3 = in_b ? f23 : f01;
+    const bool h1 = (in_b ? M01 : M23) != kMiss, h2 = (in_b ? m01 : m23) != kMiss, h3 = (in_b ? M23 : M01) != kMiss;
     // (strictly by entry distance - the partner inserted where its distance puts it - costs 12 more instructions per step and saves
     // 0.1 % of the triangle tests: C4 497 -> 515 ms, C5 3 211 -> 3 353, profiles/r04_notes.md)
     if (LDS_ENTRIES == 0x7fffffff) {

@@ -40,6 +40,11 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 template <class T>
 __device__ __forceinline__ T PT_AS1* gp(T* p) { return (T PT_AS1*)p; }
 __device__ __forceinline__ f32x4 ldg4(const void* base, size_t byte_off) { return *(const f32x4 PT_AS1*)((const char PT_AS1*)base + byte_off); }
+// the same at a 32-bit per-lane offset from a wave-uniform base (the buffer is < 4 GiB): global_load_dwordx4 v, v_off, s[base] offset:imm,
+// no 64-bit address arithmetic per lane; imm is added outside the 32-bit sum so that it folds into the instruction
+__device__ __forceinline__ f32x4 ldg4u(const void* base, uint32_t byte_off, int imm) { return *(const f32x4 PT_AS1*)((const char PT_AS1*)base + (size_t)byte_off + imm); }
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ f32x2 ldg2u(const void* base, uint32_t byte_off, int imm) { return *(const f32x2 PT_AS1*)((const char PT_AS1*)base + (size_t)byte_off + imm); }
 __device__ __forceinline__ float fmin_hw(float a, float b) { return __builtin_fminf(a, b); }
 __device__ __forceinline__ float fmax_hw(float a, float b) { return __builtin_fmaxf(a, b); }
 
@@ -127,7 +132,40 @@ __device__ __forceinline__ void tri_test(const PtTri* __restrict__ tris, int slo
     const f32x4 a = ldg4(tris, tb), b = ldg4(tris, tb + 16), c = ldg4(tris, tb + 32);
     tri_eval(a, b, c, slot, o, d, h);
 }
+// tri_eval's acceptance of one triangle, with u + v already formed
+__device__ __forceinline__ void tri_take(float t, float u, float v, float uv, int id, int slot, Hit& h)
+{
+    if (u >= 0.0f && v >= 0.0f && uv <= 1.0f && t > kTMin && (t < h.t || (t == h.t && id < h.id))) {
+        h.t = t; h.u = u; h.v = v; h.id = id; h.slot = slot;
+    }
+}
+__device__ __forceinline__ f32x2 fma2(f32x2 a, f32x2 b, f32x2 c) { return __builtin_elementwise_fma(a, b, c); }
+// Two triangles at once, {first, second} in the two halves of packed-f32 registers (v_pk_mul / v_pk_add / v_pk_fma_f32): each half does
+// exactly tri_eval's operations in tri_eval's order - dot and cross as in pt_device.h, an fma only where they have one, the correctly
+// rounded 1/det per triangle - so t, u and v are tri_eval's bit for bit.  The hits are merged in (t, id) order, first then second (take1:
+// the second is a triangle of the leaf).
+__device__ __forceinline__ void tri_eval2(const f32x4 a0, const f32x4 b0, const f32x2 c0, const f32x4 a1, const f32x4 b1, const f32x2 c1, int slot0, bool take1,
+                                          const f32x2 ox, const f32x2 oy, const f32x2 oz, const f32x2 dx, const f32x2 dy, const f32x2 dz, Hit& h)
+{
+    const f32x2 p0x = {a0.x, a1.x}, p0y = {a0.y, a1.y}, p0z = {a0.z, a1.z};
+    const f32x2 p1x = {a0.w, a1.w}, p1y = {b0.x, b1.x}, p1z = {b0.y, b1.y};
+    const f32x2 p2x = {b0.z, b1.z}, p2y = {b0.w, b1.w}, p2z = {c0.x, c1.x};
+    const f32x2 e1x = p1x - p0x, e1y = p1y - p0y, e1z = p1z - p0z;
+    const f32x2 e2x = p2x - p0x, e2y = p2y - p0y, e2z = p2z - p0z;
+    const f32x2 pvx = fma2(dy, e2z, -(dz * e2y)), pvy = fma2(dz, e2x, -(dx * e2z)), pvz = fma2(dx, e2y, -(dy * e2x)); // cross(d, e2)
+    const f32x2 det = fma2(e1z, pvz, fma2(e1y, pvy, e1x * pvx));                                                      // dot(e1, pv)
+    const f32x2 inv = {1.0f / det.x, 1.0f / det.y};
+    const f32x2 tvx = ox - p0x, tvy = oy - p0y, tvz = oz - p0z;
+    const f32x2 u = fma2(tvz, pvz, fma2(tvy, pvy, tvx * pvx)) * inv;                                                   // dot(tv, pv) * inv
+    const f32x2 qvx = fma2(tvy, e1z, -(tvz * e1y)), qvy = fma2(tvz, e1x, -(tvx * e1z)), qvz = fma2(tvx, e1y, -(tvy * e1x)); // cross(tv, e1)
+    const f32x2 v = fma2(dz, qvz, fma2(dy, qvy, dx * qvx)) * inv;                                                      // dot(d, qv) * inv
+    const f32x2 t = fma2(e2z, qvz, fma2(e2y, qvy, e2x * qvx)) * inv;                                                   // dot(e2, qv) * inv
+    const f32x2 uv = u + v;
+    tri_take(t.x, u.x, v.x, uv.x, __float_as_int(c0.y), slot0, h);
+    if (take1) tri_take(t.y, u.y, v.y, uv.y, __float_as_int(c1.y), slot0 + 1, h);
+}
 // All triangles of one leaf: the records of the first PT_LEAF_PREFETCH triangles are requested together, the tests follow.
+// The wavefront kernel's leaf step; tris is below 4 GiB there (pt_api.cpp, plan_frame): 32-bit offsets from the wave-uniform base.
 #ifndef PT_LEAF_PREFETCH
 #define PT_LEAF_PREFETCH 4
 #endif
@@ -136,20 +174,21 @@ __device__ __forceinline__ void leaf_test(const PtTri* __restrict__ tris, int fi
 #if PT_LEAF_PREFETCH == 0
     for (int k = 0; k < count; ++k) tri_test(tris, first + k, o, d, h);
 #else
-    f32x4 ra[PT_LEAF_PREFETCH], rb[PT_LEAF_PREFETCH], rc[PT_LEAF_PREFETCH];
+    static_assert(PT_LEAF_PREFETCH == 4, "the leaf step tests the triangles of a leaf in two pairs");
+    f32x4 ra[4], rb[4];
+    f32x2 rc[4]; // {p2.z, id}: the material index and the pad word are not needed here
     // unconditional loads (lanes with fewer triangles re-read their last one): one basic block, so all requests are in flight
     // before the first wait; with a per-triangle predicate the compiler waits inside each predicated block
 #pragma unroll
-    for (int k = 0; k < PT_LEAF_PREFETCH; ++k) {
+    for (int k = 0; k < 4; ++k) {
         const int kk = k < count ? k : count - 1;
-        const size_t tb = (size_t)(uint32_t)(first + kk) * sizeof(PtTri);
-        ra[k] = ldg4(tris, tb); rb[k] = ldg4(tris, tb + 16); rc[k] = ldg4(tris, tb + 32);
+        const uint32_t tb = (uint32_t)(first + kk) * (uint32_t)sizeof(PtTri);
+        ra[k] = ldg4u(tris, tb, 0); rb[k] = ldg4u(tris, tb, 16); rc[k] = ldg2u(tris, tb, 32);
     }
-#pragma unroll
-    for (int k = 0; k < PT_LEAF_PREFETCH; ++k) {
-        if (k < count) tri_eval(ra[k], rb[k], rc[k], first + k, o, d, h);
-    }
-    for (int k = PT_LEAF_PREFETCH; k < count; ++k) tri_test(tris, first + k, o, d, h); // leaf_size > PT_LEAF_PREFETCH only
+    const f32x2 ox = {o.x, o.x}, oy = {o.y, o.y}, oz = {o.z, o.z}, dx = {d.x, d.x}, dy = {d.y, d.y}, dz = {d.z, d.z};
+    tri_eval2(ra[0], rb[0], rc[0], ra[1], rb[1], rc[1], first, count > 1, ox, oy, oz, dx, dy, dz, h);
+    if (count > 2) tri_eval2(ra[2], rb[2], rc[2], ra[3], rb[3], rc[3], first + 2, count > 3, ox, oy, oz, dx, dy, dz, h);
+    for (int k = 4; k < count; ++k) tri_test(tris, first + k, o, d, h); // leaf_size > 4 only
 #endif
 }
 
@@ -169,8 +208,6 @@ __device__ __forceinline__ uint32_t stack_pop(uint32_t* stack, uint32_t PT_AS1* 
     if (LDS_ENTRIES == 0x7fffffff || sp < LDS_ENTRIES) return stack[sp * STRIDE];
     return ovf[(sp - LDS_ENTRIES) * STRIDE];
 }
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 template <int STRIDE, int LDS_ENTRIES>
 __device__ __forceinline__ void node_step(const PtNode* __restrict__ nodes, uint32_t* stack, uint32_t PT_AS1* ovf, v3 o, v3 inv, float tbest, int& cur,
