@@ -217,13 +217,36 @@ int pt_get_stats(pt_ctx* ctx, pt_stats* out);
 void pt_to_camera_data(const float look_from[3], const float look_at[3], const float look_up[3], float vertical_fov_deg,
                        int32_t width, int32_t height, pt_camera* out);
 
-/* ---- validation hooks (used by tests/ only; never on the render path) ---- */
+/* ---- validation hooks (used by tests/ only; never on the render path) ----
+ * Closest hit = minimum over all triangles of the Moeller-Trumbore t (ties: lower global triangle id), slivers never hit.  Every walk
+ * (lane per pixel, quad, group, host) computes exactly that, whatever the hierarchy, for ray origins whose largest |coordinate| is
+ * within 10 x max(scene extent, largest |coordinate| of the scene) and rays that do not lie in a non-axis-aligned triangle's plane up
+ * to rounding, nor graze one at its edge at less than 1e-2 rad.  Farther out the triangle test places hits outside the padded boxes (1 of 300 000 rays from 41 extents, 7e-4 of the
+ * rays from 3 000: brute force and any hierarchy, the oracle's too, then disagree); DESIGN.md 2.1. */
 /* Closest hit through the PRODUCT BVH walked on the host: validates the host builder without a GPU. */
 int pt_debug_closest_hit_host(pt_ctx* ctx, const float org[3], const float dir[3], float tmin, float tmax,
                               float* t, float* u, float* v, int32_t* prim);
-/* Batched device-side evaluation of the kernel's building blocks on the GPU (op codes in pt_kernel.hip):
- * lets the parity tests compare them bit-for-bit with the oracle.  in/out are host arrays. */
+/* The same for n rays at once (rays: o[3], d[3] each; out: hit, t, u, v, id bits - 5 floats each), on all host threads.  Returns n. */
+int64_t pt_debug_closest_hit_host_n(pt_ctx* ctx, const float* rays, int64_t n, float tmin, float tmax, float* out);
+/* Batched device-side evaluation of the kernel's building blocks on the GPU (op codes in pt_kernel_aux.hip):
+ * lets the parity tests compare them bit-for-bit with the oracle.  in/out are host arrays.
+ * Ops 30..35 are RAY PROBES: in = o[3], d[3] per ray, out = {hit, t, u, v, id bits, aux} (6 floats), through the device functions of
+ * the render kernel itself (not copies of them):
+ *   30 / 31  quad walk, whole stack in LDS: ray_inv -> node4_step<.., all in LDS> -> leaf_test; slab form fma (30) / subtracting (31);
+ *   32 / 33  quad walk with the short LDS stack and the HBM overflow column (node4_step<.., PT_LDS_STACK>); fma / subtracting;
+ *            aux of 30..33 = deepest stack level the ray's walk reached (entries; > PT_LDS_STACK = 12: pushes went to HBM);
+ *   34 / 35  group walk: traverse_groups over the oct nodes, eight lanes per ray, 100 rays per wave in 24 path slots, shading batches of
+ *            8 so that groups are parked and resumed; fma / subtracting; t is not carried by that walk (0); aux = group phases of the ray's
+ *            wave that had ended with parked groups when the ray was written out.
+ * A scene whose quad / oct nodes do not exist (tree too deep) is an error, not another walk.  The caller's rays must be finite. */
 int pt_debug_eval(pt_ctx* ctx, int32_t op, const float* in, int32_t in_stride, float* out, int32_t out_stride, int64_t n);
+
+/* Read-back of the hierarchy a context holds after pt_upload_scene (host copies; works on a host-only context and after a device
+ * build): raw records as csrc/pt_types.h lays them out.  out NULL: returns the bytes needed; else copies and returns the bytes
+ * written (cap too small: PT_E_INVALID).  PT_TREE_INFO: int64[8] = {root, root4, root8, depth, depth4, depth8, pad (float bits in
+ * the low word), largest leaf}; roots are node indices or leaf codes; the quad / oct arrays are empty when the tree is too deep for them. */
+enum { PT_TREE_BINARY = 0, PT_TREE_QUAD = 1, PT_TREE_OCT = 2, PT_TREE_TRIS = 3, PT_TREE_INFO = 4 };
+int64_t pt_debug_export_tree(pt_ctx* ctx, int32_t which, void* out, int64_t cap);
 
 /* What pt_group_upload_scene does for devices 1..n-1: the scene `src` holds (BVH built once) copied into `dst` and uploaded to
  * dst's GPU.  Exposed so that a one-GPU box can test it with two contexts on the same device. */

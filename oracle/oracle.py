@@ -90,6 +90,7 @@ def lib():
     L.orc_scene_bvh_depth.argtypes = [C.c_void_p]
     L.orc_to_camera_data.argtypes = [fp, fp, fp, C.c_float, C.c_int, C.c_int, C.POINTER(Camera)]
     L.orc_intersect.argtypes = [C.c_void_p, fp, fp, C.c_float, C.c_float, C.c_int, fp, fp, fp, C.POINTER(C.c_int32)]
+    L.orc_intersect_n.argtypes = [C.c_void_p, fp, C.c_int64, C.c_float, C.c_float, C.c_int, C.c_int, fp]
     L.orc_render.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(Env), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                              C.POINTER(C.c_uint32), C.c_int64, fp, C.POINTER(C.c_uint32), C.POINTER(Counters)]
     L.orc_trace_pixel.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(Env), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
@@ -356,6 +357,17 @@ class Scene:
         p = C.c_int32()
         ok = lib().orc_intersect(self.h, _vec3(org), _vec3(direction), tmin, tmax, int(use_bvh), C.byref(t), C.byref(u), C.byref(v), C.byref(p))
         return bool(ok), float(t.value), float(u.value), float(v.value), int(p.value)
+
+    def intersect_n(self, rays, tmin=1e-3, tmax=1e10, use_bvh=True, threads=None):
+        """Closest hits of n rays (n x 6: origin, direction): (hit bool, t, u, v float32, prim int32; -1 on a miss)."""
+        r = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
+        out = np.zeros((r.shape[0], 5), np.float32)
+        if threads is None:
+            threads = min(16, os.cpu_count() or 1)
+        rc = lib().orc_intersect_n(self.h, r.ctypes.data_as(C.POINTER(C.c_float)), r.shape[0], tmin, tmax, int(use_bvh), int(threads),
+                                   out.ctypes.data_as(C.POINTER(C.c_float)))
+        assert rc == 0
+        return out[:, 0] != 0, out[:, 1].copy(), out[:, 2].copy(), out[:, 3].copy(), out[:, 4].copy().view(np.int32)
 
     def render(self, cam, env, W, H, spp, max_depth, use_bvh=True, threads=None, pixel_list=None, want_rgba8=False, want_counters=False,
                out=None):

@@ -1146,6 +1146,47 @@ int orc_intersect(const orc_scene* s, const float org[3], const float dir[3], fl
     return ok;
 }
 
+/* n rays at once (rays: o[3], d[3] each; out: hit, t, u, v, prim bits - 5 floats each), shared out over n_threads threads */
+typedef struct isect_job {
+    const orc_scene* s;
+    const float* rays;
+    float* out;
+    int64_t n, next;
+    float tmin, tmax;
+    int use_bvh;
+} isect_job;
+
+static void* isect_worker(void* arg)
+{
+    isect_job* j = (isect_job*)arg;
+    const int64_t chunk = 64;
+    for (;;) {
+        int64_t begin = __atomic_fetch_add(&j->next, chunk, __ATOMIC_RELAXED);
+        if (begin >= j->n) break;
+        int64_t end = begin + chunk < j->n ? begin + chunk : j->n;
+        for (int64_t i = begin; i < end; ++i) {
+            float* y = j->out + 5 * i;
+            int32_t prim = -1;
+            y[0] = (float)orc_intersect(j->s, j->rays + 6 * i, j->rays + 6 * i + 3, j->tmin, j->tmax, j->use_bvh, y + 1, y + 2, y + 3, &prim);
+            memcpy(y + 4, &prim, 4);
+        }
+    }
+    return NULL;
+}
+
+int orc_intersect_n(const orc_scene* s, const float* rays, int64_t n, float tmin, float tmax, int use_bvh, int n_threads, float* out)
+{
+    if (!s || !rays || !out || n < 0) return -1;
+    isect_job j = {s, rays, out, n, 0, tmin, tmax, use_bvh};
+    if (n_threads < 1) n_threads = 1;
+    if (n_threads > 256) n_threads = 256;
+    pthread_t th[256];
+    for (int i = 1; i < n_threads; ++i) pthread_create(&th[i], NULL, isect_worker, &j);
+    isect_worker(&j);
+    for (int i = 1; i < n_threads; ++i) pthread_join(th[i], NULL);
+    return 0;
+}
+
 /* ------------------------------------------------------------------------------------------ */
 /* trace_path  device.cu:113-218                                                              */
 /* ------------------------------------------------------------------------------------------ */

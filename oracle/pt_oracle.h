@@ -86,6 +86,9 @@ void orc_to_camera_data(const float look_from[3], const float look_at[3], const 
 int orc_intersect(const orc_scene* s, const float org[3], const float dir[3], float tmin, float tmax,
                   int use_bvh, float* t, float* u, float* v, int32_t* prim);
 
+/* The same for n rays (rays: o[3], d[3] each; out: hit, t, u, v, prim bits - 5 floats each; prim -1 on a miss) on n_threads threads. */
+int orc_intersect_n(const orc_scene* s, const float* rays, int64_t n, float tmin, float tmax, int use_bvh, int n_threads, float* out);
+
 /*
  * Render (ray_gen, device.cu:220-254).  out_rgb: W*H*3 floats, already row-flipped like the
  * reference framebuffer (index x + W*(H-1-y)); out_rgba8 optional (owl::make_rgba).

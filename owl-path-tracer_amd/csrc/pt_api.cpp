@@ -697,6 +697,57 @@ void walk_params(pt_ctx* c, const pt_camera* cam, PtKernelParams& P)
     }
 }
 
+// The ray probes of pt_debug_eval (ops >= PT_PROBE_FIRST, pt_launch.h): rays already uploaded to d_dbg_in, d_dbg_out sized and cleared; P
+// holds the scene (fill_params).  The probes walk the quad / oct nodes with the device functions of the render kernel (pt_kernel.hip); a
+// scene without those nodes is an error, never another walk.
+int probe_eval(pt_ctx* c, PtKernelParams& P, int op, int in_stride, float* out, int out_stride, int64_t n)
+{
+    if (op > PT_PROBE_LAST) return fail(c, PT_E_INVALID, "pt_debug_eval: unknown op %d", op);
+    if (!c->have_scene) return fail(c, PT_E_NO_SCENE, "pt_debug_eval: ray probe before pt_upload_scene");
+    if (in_stride < 6 || out_stride < PT_PROBE_OUT) return fail(c, PT_E_INVALID, "ray probe: 6 floats in, %d out per ray", PT_PROBE_OUT);
+    const bool group = op >= PT_PROBE_GROUP;
+    P.box_exact = (op - PT_PROBE_FIRST) & 1;
+    int grid = 0;
+    size_t lds = 0, scratch_words = 0;
+    if (!group) {
+        if (c->nodes4.empty() && c->root4 >= 0) return fail(c, PT_E_LIMIT, "ray probe: the scene has no quad nodes (tree too deep for the quad walk)");
+        P.nodes4 = (const PtNode4*)c->d_nodes4.p;
+        P.root = c->root4;
+        P.stack_entries = 3 * c->depth4 + 1;
+        const bool overflow = op >= PT_PROBE_QUAD_OVF;
+        const int levels = P.stack_entries + 3; // the LDS-only step stores three entries above the top whether or not it pushes them
+        grid = (int)std::min<int64_t>((n + 63) / 64, 2048);
+        P.lds_levels = overflow ? std::min(levels, pt_probe_lds_stack()) : levels;
+        lds = (size_t)P.lds_levels * 64 * 4;
+        scratch_words = overflow ? (size_t)std::max(0, levels - P.lds_levels) * 64 * (size_t)grid : 0;
+    } else {
+        if (c->nodes8.empty() && c->root8 >= 0) return fail(c, PT_E_LIMIT, "ray probe: the scene has no oct nodes (tree too deep for the group walk)");
+        P.nodes8 = (const PtNode8*)c->d_nodes8.p;
+        P.root8 = c->root8;
+        P.groups = 2;
+        P.ns = PT_PROBE_GROUP_SLOTS;
+        P.lds_levels = std::max(1, (7 * c->depth8 + 1 + 7) / 8);
+        grid = (int)((n + PT_PROBE_GROUP_RAYS - 1) / PT_PROBE_GROUP_RAYS);
+        lds = pt_probe_group_lds_bytes(P.lds_levels, P.ns);
+        scratch_words = pt_probe_group_state_words() * (size_t)grid;
+    }
+    DevBuf d_scratch; // overflow columns / park areas, then the watchdog flag
+    int rc = ensure(c, d_scratch, (scratch_words + 64) * 4);
+    if (rc) return rc;
+    uint32_t* flag = (uint32_t*)d_scratch.p + scratch_words;
+    P.error_flag = flag;
+    uint32_t fired = 0;
+    hipError_t e = hipMemsetAsync(flag, 0, 4, c->stream);
+    if (e == hipSuccess) e = pt_launch_probe(&P, op, (const float*)c->d_dbg_in.p, in_stride, (float*)c->d_dbg_out.p, out_stride, (long long)n, grid, lds, (uint32_t*)d_scratch.p, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(out, c->d_dbg_out.p, (size_t)n * out_stride * 4, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(&fired, flag, 4, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    release(d_scratch);
+    if (e != hipSuccess) return fail(c, PT_E_HIP, "ray probe %d failed: %s", op, hipGetErrorString(e));
+    if (fired) return fail(c, PT_E_HIP, "ray probe %d: a walk ran out of its step or stack bound; the results are incomplete", op);
+    return PT_OK;
+}
+
 // What one frame launches, decided before any buffer is sized (plan_frame).
 // kernel 1 (lane-per-pixel): optional spp chunks = separate launches.
 // Wavefront kernel, schedule 1 (default): a short cost pre-pass (pre samples of every pixel, rays counted), a counting sort of the
@@ -1157,6 +1208,46 @@ int pt_debug_closest_hit_host(pt_ctx* c, const float org[3], const float dir[3],
     return pt_bvh_closest_hit_host(c->bvh, org, dir, tmin, tmax, t, u, v, prim) ? 1 : 0;
 }
 
+int64_t pt_debug_closest_hit_host_n(pt_ctx* c, const float* rays, int64_t n, float tmin, float tmax, float* out)
+{
+    if (!c || !rays || !out || n < 0) return PT_E_INVALID;
+    if (!c->have_scene) return PT_E_NO_SCENE;
+    pt_parallel_ranges((size_t)n, [&](size_t lo, size_t hi) {
+        for (size_t i = lo; i < hi; ++i) {
+            float t = 0.0f, u = 0.0f, v = 0.0f;
+            int32_t prim = -1;
+            const bool hit = pt_bvh_closest_hit_host(c->bvh, rays + 6 * i, rays + 6 * i + 3, tmin, tmax, &t, &u, &v, &prim);
+            float* y = out + 5 * i;
+            y[0] = hit ? 1.0f : 0.0f; y[1] = t; y[2] = u; y[3] = v;
+            const int32_t id = hit ? prim : -1;
+            std::memcpy(y + 4, &id, 4);
+        }
+    });
+    return n;
+}
+
+int64_t pt_debug_export_tree(pt_ctx* c, int32_t which, void* out, int64_t cap)
+{
+    if (!c || cap < 0) return PT_E_INVALID;
+    if (!c->have_scene) return fail(c, PT_E_NO_SCENE, "pt_debug_export_tree before pt_upload_scene");
+    int64_t info[8] = {c->bvh.root, c->root4, c->root8, c->bvh.depth, c->depth4, c->depth8, 0, c->bvh.max_leaf};
+    std::memcpy(&info[6], &c->bvh.pad, sizeof(float));
+    const void* src = nullptr;
+    size_t bytes = 0;
+    switch (which) {
+    case PT_TREE_BINARY: src = c->bvh.nodes.data(); bytes = c->bvh.nodes.size() * sizeof(PtNode); break;
+    case PT_TREE_QUAD: src = c->nodes4.data(); bytes = c->nodes4.size() * sizeof(PtNode4); break;
+    case PT_TREE_OCT: src = c->nodes8.data(); bytes = c->nodes8.size() * sizeof(PtNode8); break;
+    case PT_TREE_TRIS: src = c->bvh.tris.data(); bytes = c->bvh.tris.size() * sizeof(PtTri); break;
+    case PT_TREE_INFO: src = info; bytes = sizeof(info); break;
+    default: return fail(c, PT_E_INVALID, "pt_debug_export_tree: unknown array %d", which);
+    }
+    if (!out) return (int64_t)bytes; // size query
+    if ((size_t)cap < bytes) return fail(c, PT_E_INVALID, "pt_debug_export_tree: %zu bytes needed, %lld given", bytes, (long long)cap);
+    if (bytes) std::memcpy(out, src, bytes);
+    return (int64_t)bytes;
+}
+
 int pt_debug_clone_scene(pt_ctx* dst, const pt_ctx* src)
 {
     if (!dst || !src || dst == src) return PT_E_INVALID;
@@ -1325,6 +1416,7 @@ int pt_debug_eval(pt_ctx* c, int32_t op, const float* in, int32_t in_stride, flo
     HIP_TRY(c, hipMemsetAsync(c->d_dbg_out.p, 0, (size_t)n * out_stride * 4, c->stream));
     PtKernelParams P;
     fill_params(c, P);
+    if (op >= PT_PROBE_FIRST) return probe_eval(c, P, op, in_stride, out, out_stride, n);
     if (!c->have_scene) { P.root = -1; P.stack_entries = 1; }
     size_t lds = (size_t)P.stack_entries * pt_debug_block() * 4;
     HIP_TRY(c, pt_launch_debug(&P, op, (const float*)c->d_dbg_in.p, in_stride, (float*)c->d_dbg_out.p, out_stride, (long long)n, lds, c->stream));

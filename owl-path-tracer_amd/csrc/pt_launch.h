@@ -19,7 +19,20 @@ struct PtGeometry {
     int max_blocks_per_cu;  // occupancy at lds_bytes
 };
 
+// Ray probes of pt_debug_eval (pt_kernel.hip, "ray probes"): op = PT_PROBE_QUAD / PT_PROBE_QUAD_OVF / PT_PROBE_GROUP + slab form (0: fma, 1: subtracting).
+// in: o[3], d[3] per ray; out: PT_PROBE_OUT floats per ray (layout in include/mi355pt.h).
+enum { PT_PROBE_FIRST = 30, PT_PROBE_QUAD = 30, PT_PROBE_QUAD_OVF = 32, PT_PROBE_GROUP = 34, PT_PROBE_LAST = 35 };
+#define PT_PROBE_OUT 6
+#define PT_PROBE_GROUP_SLOTS 24 // path slots of a wave of the group probe: three rays per group, so groups park and resume
+#define PT_PROBE_GROUP_RAYS 100 // rays per wave of the group probe: neither a multiple of 8 nor of 64
+
 extern "C" {
+// scratch: quad probe with overflow: the waves' HBM stack columns; group probe: the waves' park areas (pt_probe_group_state_words each)
+hipError_t pt_launch_probe(const PtKernelParams* p, int op, const float* in, int in_stride, float* out, int out_stride, long long n, int grid, size_t lds_bytes,
+                           uint32_t* scratch, hipStream_t stream);
+int pt_probe_lds_stack(void);                                // PT_LDS_STACK of this build
+size_t pt_probe_group_lds_bytes(int lds_levels, int ns);
+size_t pt_probe_group_state_words(void);
 hipError_t pt_launch_render(const PtKernelParams* p, const PtKernelParams* d_params, int variant, int grid, size_t lds_bytes, hipStream_t stream, int count);
 hipError_t pt_launch_debug(const PtKernelParams* p, int op, const float* in, int in_stride, float* out, int out_stride, long long n, size_t lds_bytes,
                            hipStream_t stream);

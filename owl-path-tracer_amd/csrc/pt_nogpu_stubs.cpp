@@ -15,6 +15,10 @@ hipError_t pt_launch_plan_tiers(const uint32_t*, uint32_t, int, int, int, uint32
 hipError_t pt_launch_sort_pixels(const uint8_t*, int, int, int, const uint32_t*, uint32_t*, uint32_t, uint32_t, uint32_t*, uint8_t*, hipStream_t) { return hipErrorNotSupported; }
 hipError_t pt_kernel_geometry(int, int, int, int, int, int, PtGeometry*) { return hipErrorNotSupported; }
 int pt_debug_block(void) { return 256; }
+hipError_t pt_launch_probe(const PtKernelParams*, int, const float*, int, float*, int, long long, int, size_t, uint32_t*, hipStream_t) { return hipErrorNotSupported; }
+int pt_probe_lds_stack(void) { return 12; }
+size_t pt_probe_group_lds_bytes(int, int) { return 16; }
+size_t pt_probe_group_state_words(void) { return 16; }
 size_t pt_lbvh_workspace_bytes(int) { return 16; }
 hipError_t pt_lbvh_build_device(const float*, int, int, void*, size_t, PtNode*, uint32_t*, int32_t*, int32_t*, int32_t*, int32_t*, float*, hipStream_t) { return hipErrorNotSupported; }
 size_t pt_ploc_workspace_bytes(int) { return 16; }

@@ -14,7 +14,19 @@ HEADER_PATH = os.path.join(os.path.dirname(_PKG), "include", "mi355pt.h")
 
 PT_MAT_FLOATS = 17
 OPS = {"sin": 0, "cos": 1, "tan": 2, "atan": 3, "atan2": 4, "asin": 5, "log": 6, "exp": 7, "pow": 8, "sqrt": 9, "div": 10,
-       "sample_disney": 20, "closest_hit": 21, "frame": 22, "rng": 23}
+       "sample_disney": 20, "closest_hit": 21, "frame": 22, "rng": 23,
+       # ray probes through the render kernel's own walks (include/mi355pt.h): quad walk with the whole stack in LDS / with the HBM overflow
+       # column, group walk; "_exact" = the subtracting slab form.  6 floats out: hit, t, u, v, id bits, aux
+       "quad": 30, "quad_exact": 31, "quad_ovf": 32, "quad_ovf_exact": 33, "group": 34, "group_exact": 35}
+PROBE_OPS = ("quad", "quad_exact", "quad_ovf", "quad_ovf_exact", "group", "group_exact")
+PT_LDS_STACK = 12  # csrc/pt_kernel.hip: stack levels of the quad walk kept in LDS
+
+# csrc/pt_types.h, for Context.export_trees
+NODE_DTYPE = np.dtype([("lo", "<f4", (3, 2)), ("hi", "<f4", (3, 2)), ("left", "<i4"), ("right", "<i4"), ("pad", "<u4", (2,))])
+NODE4_DTYPE = np.dtype([("lo", "<f4", (3, 4)), ("hi", "<f4", (3, 4)), ("child", "<i4", (4,)), ("pad", "<u4", (4,))])
+NODE8_DTYPE = np.dtype([("c", [("lo", "<f4", (3,)), ("hi", "<f4", (3,)), ("ref", "<i4"), ("pad", "<u4")], (8,))])
+TRI_DTYPE = np.dtype([("p0", "<f4", (3,)), ("p1", "<f4", (3,)), ("p2", "<f4", (3,)), ("id", "<i4"), ("material", "<i4"), ("pad", "<u4")])
+assert (NODE_DTYPE.itemsize, NODE4_DTYPE.itemsize, NODE8_DTYPE.itemsize, TRI_DTYPE.itemsize) == (64, 128, 256, 48)
 
 
 class PtError(RuntimeError):
@@ -64,7 +76,7 @@ class Stats(C.Structure):
 
 EXPORTS = ["pt_create", "pt_destroy", "pt_last_error", "pt_abi_version", "pt_upload_scene", "pt_set_materials", "pt_set_environment",
            "pt_set_pixel_shard", "pt_shard_pixels", "pt_render", "pt_render_device", "pt_synchronize", "pt_set_option", "pt_get_stats",
-           "pt_to_camera_data", "pt_debug_closest_hit_host", "pt_debug_eval", "pt_debug_read_queue", "pt_debug_read_laps", "pt_debug_read_finish", "pt_debug_read_tiers", "pt_debug_plan_tiers",
+           "pt_to_camera_data", "pt_debug_closest_hit_host", "pt_debug_closest_hit_host_n", "pt_debug_export_tree", "pt_debug_eval", "pt_debug_read_queue", "pt_debug_read_laps", "pt_debug_read_finish", "pt_debug_read_tiers", "pt_debug_plan_tiers",
            "pt_comm_get_unique_id", "pt_comm_init_rank", "pt_comm_destroy", "pt_reduce_framebuffer", "pt_host_alloc", "pt_host_free",
            "pt_group_create", "pt_group_destroy", "pt_group_size", "pt_group_ctx", "pt_group_last_error", "pt_group_upload_scene",
            "pt_group_set_materials", "pt_group_set_option", "pt_group_render", "pt_debug_quad_info", "pt_debug_oct_info", "pt_debug_clone_scene"]
@@ -103,6 +115,10 @@ def lib():
     L.pt_to_camera_data.restype = None
     L.pt_to_camera_data.argtypes = [fp, fp, fp, C.c_float, C.c_int32, C.c_int32, C.POINTER(Camera)]
     L.pt_debug_closest_hit_host.argtypes = [C.c_void_p, fp, fp, C.c_float, C.c_float, fp, fp, fp, C.POINTER(C.c_int32)]
+    L.pt_debug_closest_hit_host_n.argtypes = [C.c_void_p, fp, C.c_int64, C.c_float, C.c_float, fp]
+    L.pt_debug_closest_hit_host_n.restype = C.c_int64
+    L.pt_debug_export_tree.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64]
+    L.pt_debug_export_tree.restype = C.c_int64
     L.pt_debug_eval.argtypes = [C.c_void_p, C.c_int32, fp, C.c_int32, fp, C.c_int32, C.c_int64]
     L.pt_debug_read_queue.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), C.c_int64]
     L.pt_debug_read_queue.restype = C.c_int64
@@ -337,6 +353,34 @@ class Context:
         rc = self._check(lib().pt_debug_closest_hit_host(self._h, _vec3(org), _vec3(direction), tmin, tmax, C.byref(t), C.byref(u), C.byref(v),
                                                          C.byref(p)), "pt_debug_closest_hit_host")
         return bool(rc), float(t.value), float(u.value), float(v.value), int(p.value)
+
+    def closest_hit_host_n(self, rays, tmin=1e-3, tmax=1e10):
+        """closest_hit_host for n rays (n x 6: origin, direction): (hit bool, t, u, v float32, id int32; -1 on a miss)."""
+        r = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
+        out = np.zeros((r.shape[0], 5), np.float32)
+        n = lib().pt_debug_closest_hit_host_n(self._h, r.ctypes.data_as(C.POINTER(C.c_float)), r.shape[0], tmin, tmax, out.ctypes.data_as(C.POINTER(C.c_float)))
+        if n < 0:
+            self._check(int(n), "pt_debug_closest_hit_host_n")
+        return out[:, 0] != 0, out[:, 1].copy(), out[:, 2].copy(), out[:, 3].copy(), out[:, 4].copy().view(np.int32)
+
+    def _export(self, which, dtype):
+        n = lib().pt_debug_export_tree(self._h, which, None, 0)
+        if n < 0:
+            self._check(int(n), "pt_debug_export_tree")
+        a = np.zeros(int(n) // dtype.itemsize, dtype)
+        if n:
+            self._check(int(lib().pt_debug_export_tree(self._h, which, a.ctypes.data_as(C.c_void_p), a.nbytes)), "pt_debug_export_tree")
+        return a
+
+    def export_trees(self):
+        """The hierarchy the context holds (pt_debug_export_tree): structured arrays `nodes`, `nodes4`, `nodes8`, `tris` (csrc/pt_types.h)
+        and root, root4, root8, depth, depth4, depth8, pad (float32), max_leaf."""
+        info = self._export(4, np.dtype("<i8"))
+        d = dict(zip(("root", "root4", "root8", "depth", "depth4", "depth8"), (int(x) for x in info[:6])))
+        d["pad"] = np.array([int(info[6]) & 0xffffffff], np.uint32).view(np.float32)[0]
+        d["max_leaf"] = int(info[7])
+        d["nodes"], d["nodes4"], d["nodes8"], d["tris"] = (self._export(k, t) for k, t in enumerate((NODE_DTYPE, NODE4_DTYPE, NODE8_DTYPE, TRI_DTYPE)))
+        return d
 
     def clone_scene_from(self, other):
         self._check(lib().pt_debug_clone_scene(self._h, other._h), "pt_debug_clone_scene")

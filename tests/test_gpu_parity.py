@@ -1315,6 +1315,13 @@ def test_device_lbvh_builder(gpu, orc, cornell, scene_io, procedural, builder):
             d = rng.normal(size=(n, 3)).astype(np.float32)
             d /= np.linalg.norm(d, axis=1, keepdims=True).astype(np.float32)
             got = ctx.debug_eval("closest_hit", np.concatenate([o, d], 1), 5)
+            # the walks the product frame runs (quad walk with both stack instances, group walk; both slab forms), every ray: hit, u, v, id
+            # - and t where the walk carries it - as the lane-per-pixel walk has them (tests/test_gpu_ray_probes.py holds them to brute force)
+            for op in B.PROBE_OPS:
+                pr = ctx.debug_eval(op, np.concatenate([o, d], 1), 6)
+                cols = [0, 2, 3, 4] if op.startswith("group") else [0, 1, 2, 3, 4]
+                hitm = got[:, 0] != 0
+                assert np.array_equal(pr[:, 0], got[:, 0]) and np.array_equal(pr[hitm][:, cols].view(np.uint32), got[hitm][:, cols].view(np.uint32)), (op, leaf)
             for i in range(0, n, 97):
                 hit, t, u, v, prim = S.intersect(o[i], d[i], use_bvh=False)
                 assert bool(got[i, 0]) == hit
