@@ -173,8 +173,11 @@ int pt_reduce_framebuffer(pt_ctx* ctx, void* d_rgb, void* d_rgba8, int64_t n_pix
 void* pt_host_alloc(size_t bytes);
 void pt_host_free(void* p);
 
-/* (b) One process, N GPUs (`pt_main --gpus N`): N contexts + ncclCommInitAll; scene calls fan out to every device (full
- *     replica each), pt_group_render = shards + one reduce + read-back from device 0.  devices NULL = 0..n-1. */
+/* (b) One process, N GPUs (`pt_main --gpus N` / `pt_main --devices a,b,c`): N contexts + ncclCommInitAll; scene calls fan out to
+ *     every device (full replica each), pt_group_render = shards + one reduce + read-back from devices[0].  devices NULL = 0..n-1;
+ *     otherwise any n device numbers in any order (n <= 64).  A device named twice is refused by the real RCCL (ncclCommInitAll fails,
+ *     pt_group_create returns NULL); the stub collective of the test suite (tests/stub/fake_rccl.cpp) accepts it, which is how the
+ *     tests run N contexts on one card.  After pt_group_render returned PT_E_HIP from the reduce, destroy the group. */
 typedef struct pt_group pt_group;
 pt_group* pt_group_create(const int32_t* devices, int32_t n);   /* NULL on failure; pt_last_error(NULL) has the reason */
 void pt_group_destroy(pt_group* g);

@@ -208,6 +208,7 @@ void pt_group_destroy(pt_group* g)
     for (size_t i = 0; i < g->ctx.size(); ++i) {
         pt_ctx* c = g->ctx[i];
         (void)hipSetDevice(c->device);
+        (void)hipStreamSynchronize(c->stream); // a failed pt_group_render may have left this rank's launches in flight on d_rgb
         (void)pt_comm_destroy(c);
         if (i < g->d_rgb.size() && g->d_rgb[i]) (void)hipFree(g->d_rgb[i]);
         if (i < g->d_rgba8.size() && g->d_rgba8[i]) (void)hipFree(g->d_rgba8[i]);

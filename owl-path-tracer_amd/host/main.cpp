@@ -5,8 +5,9 @@
 //
 // Optional flags (defaults reproduce the reference, which has no CLI): --assets DIR, --out DIR, --settings FILE, --device N
 // (-1: load + build only, no render), --gpus N (devices --device .. --device + N - 1 of this node, default 0..N-1: pixel tiles sharded over them, one RCCL reduce of the
-// float3 framebuffer onto device 0 - pt_group_* in mi355pt.h; the image is bit-identical to --gpus 1), --dump-scene FILE (binary
-// dump of the ingested scene for the loader tests).
+// float3 framebuffer onto device 0 - pt_group_* in mi355pt.h; the image is bit-identical to --gpus 1), --devices a,b,c (the same
+// group path on exactly these devices, the reduce onto the first; with --gpus the counts must agree, with --device it is an error;
+// a device named twice is refused by the real RCCL), --dump-scene FILE (binary dump of the ingested scene for the loader tests).
 #include <sys/stat.h>
 #include <unistd.h>
 
@@ -52,6 +53,23 @@ void dump_scene(const std::string& path, const host::Scene& s)
     std::fclose(f);
 }
 
+// --devices a,b,c: non-negative integers, at least one
+std::vector<int32_t> parse_devices(const std::string& list)
+{
+    std::vector<int32_t> devs;
+    size_t p = 0;
+    for (;;) {
+        const size_t q = list.find(',', p);
+        const std::string tok = list.substr(p, q == std::string::npos ? std::string::npos : q - p);
+        if (tok.empty() || tok.size() > 6 || tok.find_first_not_of("0123456789") != std::string::npos)
+            throw std::runtime_error("--devices needs a comma-separated list of non-negative device numbers, got '" + list + "'");
+        devs.push_back((int32_t)std::atoi(tok.c_str()));
+        if (q == std::string::npos) break;
+        p = q + 1;
+    }
+    return devs;
+}
+
 std::string fmt1(float v)
 {
     char b[64];
@@ -85,6 +103,10 @@ void render_frame(App& a, const std::string& values)
     else check(a, pt_render(a.ctx, &a.cam, W, H, a.settings.max_samples, a.settings.max_path_depth, rgb.data(), rgba.data()), "pt_render");
     pt_stats st;
     pt_get_stats(a.ctx, &st);
+    for (int32_t i = 1; i < pt_group_size(a.group); ++i) { // the frame takes as long as its slowest rank
+        pt_stats si;
+        if (pt_get_stats(pt_group_ctx(a.group, i), &si) == PT_OK && si.kernel_ms > st.kernel_ms) st.kernel_ms = si.kernel_ms;
+    }
     std::string name = a.settings.scene + "_" + a.settings.test.name + "_" + a.settings.test.attribute_name + "(" + values + ").png";
     std::string path = a.out_dir + "/" + name;
     imgio::write_png_rgba8(path, W, H, rgba.data());
@@ -141,13 +163,16 @@ int main(int argc, char** argv)
         std::string settings_path, dump;
         a.out_dir = cwd;
         int device = 0, gpus = 0; // gpus 0: flag not given, single context as in the reference
+        bool have_device = false, have_devices = false;
+        std::vector<int32_t> devs; // --devices
         for (int i = 1; i < argc; ++i) {
             std::string k = argv[i];
             auto next = [&]() { if (i + 1 >= argc) throw std::runtime_error("missing value for " + k); return std::string(argv[++i]); };
             if (k == "--assets") assets = next();
             else if (k == "--out") a.out_dir = next();
             else if (k == "--settings") settings_path = next();
-            else if (k == "--device") device = std::atoi(next().c_str());
+            else if (k == "--device") { device = std::atoi(next().c_str()); have_device = true; }
+            else if (k == "--devices") { devs = parse_devices(next()); have_devices = true; }
             else if (k == "--gpus") gpus = std::atoi(next().c_str());
             else if (k == "--dump-scene") dump = next();
             else if (k == "--convert-png" || k == "--convert-hdr") { // codec self-test hooks: decode with our reader, re-encode with our writer
@@ -157,6 +182,13 @@ int main(int argc, char** argv)
                 return 0;
             }
             else throw std::runtime_error("unknown option " + k);
+        }
+        if (gpus < 0) throw std::runtime_error("--gpus needs a positive count");
+        if (have_devices) {
+            if (have_device) throw std::runtime_error("--devices and --device exclude each other (--devices lists every device)");
+            if (gpus > 0 && gpus != (int)devs.size())
+                throw std::runtime_error("--devices names " + std::to_string(devs.size()) + " device(s) but --gpus says " + std::to_string(gpus));
+            gpus = (int)devs.size();
         }
         if (settings_path.empty()) settings_path = assets + "/settings.json"; // application.cpp:145
 
@@ -220,11 +252,10 @@ int main(int argc, char** argv)
         env.intensity = a.settings.environment_intensity;
         env.map = {env_img.width, env_img.height, env_img.rgba.empty() ? nullptr : env_img.rgba.data()};
 
-        if (gpus < 0) throw std::runtime_error("--gpus needs a positive count");
         if (meshes.empty()) throw std::runtime_error("no geometries"); // application.cpp:133
         if (gpus >= 1 && device >= 0) { // devices device..device+gpus-1: a scene replica on each, the library's communicator across them
-            std::vector<int32_t> devs((size_t)gpus);
-            for (int i = 0; i < gpus; ++i) devs[(size_t)i] = device + i;
+            if (!have_devices)
+                for (int i = 0; i < gpus; ++i) devs.push_back(device + i);
             a.group = pt_group_create(devs.data(), gpus);
             if (!a.group) throw std::runtime_error(std::string("pt_group_create: ") + pt_last_error(nullptr));
             a.ctx = pt_group_ctx(a.group, 0);

@@ -244,6 +244,37 @@ def plan_tiers(bucket_pixels, capacity, ns=96, force=False):
     return [dict(zip(("q0", "pixels", "per_wave", "wave0", "waves", "cost_class"), (int(x) for x in t[1 + 8 * i:7 + 8 * i]))) for i in range(int(t[0]))]
 
 
+def _marshal_scene(entities, materials, textures=None, mesh_textures=None, env=None):
+    """The argument list of pt_upload_scene / pt_group_upload_scene after the handle, and the arrays it points into (keep them
+    alive until the call returned).  entities: list of (mesh dict, material index); materials: (n,17) float32; textures: list of
+    (H,W) uint32 arrays; mesh_textures: per-entity texture index (or None)."""
+    textures = textures or []
+    keep = []
+    arr = (Mesh * max(1, len(entities)))()
+    for i, (m, mat_id) in enumerate(entities):
+        v = np.ascontiguousarray(m["vertices"], np.float32)
+        n = np.ascontiguousarray(m["normals"], np.float32)
+        tc = np.ascontiguousarray(m["texcoords"], np.float32)
+        idx = np.ascontiguousarray(m["indices"], np.int32)
+        keep += [v, n, tc, idx]
+        e = arr[i]
+        e.vertices = v.ctypes.data_as(C.POINTER(C.c_float))
+        e.normals = n.ctypes.data_as(C.POINTER(C.c_float)) if n.size else None
+        e.texcoords = tc.ctypes.data_as(C.POINTER(C.c_float)) if tc.size else None
+        e.indices = idx.ctypes.data_as(C.POINTER(C.c_int32))
+        e.n_vertices, e.n_normals, e.n_texcoords, e.n_triangles = v.shape[0], n.shape[0], tc.shape[0], idx.shape[0]
+        e.material_index = int(mat_id)
+        e.texture_index = int(mesh_textures[i]) if mesh_textures is not None else -1
+    mats = np.ascontiguousarray(np.asarray(materials, np.float32).reshape(-1, PT_MAT_FLOATS))
+    tarr = (Texture * max(1, len(textures)))()
+    for i, t in enumerate(textures):
+        tarr[i], k = _texture(t)
+        keep.append(k)
+    keep += [arr, mats, tarr, env]
+    envp = C.byref(env) if env is not None else None
+    return (arr, len(entities), mats.ctypes.data_as(C.POINTER(C.c_float)), mats.shape[0], tarr, len(textures), None, envp), keep
+
+
 class Context:
     """Thin object wrapper; device=-1 gives a host-only validation context (no render possible)."""
 
@@ -254,9 +285,19 @@ class Context:
             raise PtError("pt_create failed: " + lib().pt_last_error(None).decode())
         self.device = device
 
+    @classmethod
+    def _view(cls, handle):
+        """A Context over a handle somebody else owns (Group.ctx): close() forgets the handle, nothing is destroyed."""
+        self = cls.__new__(cls)
+        self._h = handle
+        self._owned = False
+        self.device = None
+        return self
+
     def close(self):
         if getattr(self, "_h", None):
-            lib().pt_destroy(self._h)
+            if getattr(self, "_owned", True):
+                lib().pt_destroy(self._h)
             self._h = None
 
     def __del__(self):
@@ -276,31 +317,9 @@ class Context:
     def upload_scene(self, entities, materials, textures=None, mesh_textures=None, env=None):
         """entities: list of (mesh dict, material index); materials: (n,17) float32;
         textures: list of (H,W) uint32 arrays; mesh_textures: per-entity texture index (or None)."""
-        textures = textures or []
-        keep = []
-        arr = (Mesh * max(1, len(entities)))()
-        for i, (m, mat_id) in enumerate(entities):
-            v = np.ascontiguousarray(m["vertices"], np.float32)
-            n = np.ascontiguousarray(m["normals"], np.float32)
-            tc = np.ascontiguousarray(m["texcoords"], np.float32)
-            idx = np.ascontiguousarray(m["indices"], np.int32)
-            keep += [v, n, tc, idx]
-            e = arr[i]
-            e.vertices = v.ctypes.data_as(C.POINTER(C.c_float))
-            e.normals = n.ctypes.data_as(C.POINTER(C.c_float)) if n.size else None
-            e.texcoords = tc.ctypes.data_as(C.POINTER(C.c_float)) if tc.size else None
-            e.indices = idx.ctypes.data_as(C.POINTER(C.c_int32))
-            e.n_vertices, e.n_normals, e.n_texcoords, e.n_triangles = v.shape[0], n.shape[0], tc.shape[0], idx.shape[0]
-            e.material_index = int(mat_id)
-            e.texture_index = int(mesh_textures[i]) if mesh_textures is not None else -1
-        mats = np.ascontiguousarray(np.asarray(materials, np.float32).reshape(-1, PT_MAT_FLOATS))
-        tarr = (Texture * max(1, len(textures)))()
-        for i, t in enumerate(textures):
-            tarr[i], k = _texture(t)
-            keep.append(k)
-        envp = C.byref(env) if env is not None else None
-        self._check(lib().pt_upload_scene(self._h, arr, len(entities), mats.ctypes.data_as(C.POINTER(C.c_float)), mats.shape[0], tarr,
-                                          len(textures), None, envp), "pt_upload_scene")
+        args, keep = _marshal_scene(entities, materials, textures, mesh_textures, env)
+        self._check(lib().pt_upload_scene(self._h, *args), "pt_upload_scene")
+        del keep
 
     def set_materials(self, materials):
         mats = np.ascontiguousarray(np.asarray(materials, np.float32).reshape(-1, PT_MAT_FLOATS))
@@ -443,3 +462,66 @@ class Context:
         self._check(lib().pt_debug_eval(self._h, OPS[op] if isinstance(op, str) else op, x.ctypes.data_as(C.POINTER(C.c_float)), x.shape[1],
                                         out.ctypes.data_as(C.POINTER(C.c_float)), out_stride, x.shape[0]), "pt_debug_eval")
         return out
+
+
+class Group:
+    """One process, N contexts behind one communicator (pt_group_* in include/mi355pt.h): pixel tiles over `devices`, one reduce onto
+    devices[0].  The real RCCL refuses a device that appears twice; the stub collective of tests/stub/fake_rccl.cpp accepts it."""
+
+    def __init__(self, devices):
+        devices = [int(d) for d in devices]
+        arr = (C.c_int32 * max(1, len(devices)))(*devices)
+        self._g = lib().pt_group_create(arr, len(devices))
+        if not self._g:
+            raise PtError("pt_group_create failed: " + lib().pt_last_error(None).decode())
+        self.devices = devices
+
+    def close(self):
+        if getattr(self, "_g", None):
+            lib().pt_group_destroy(self._g)
+            self._g = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def last_error(self):
+        return lib().pt_group_last_error(self._g).decode()
+
+    def _check(self, rc, what):
+        if rc < 0:
+            raise PtError("%s failed (%d): %s" % (what, rc, self.last_error()))
+        return rc
+
+    @property
+    def size(self):
+        return int(lib().pt_group_size(self._g))
+
+    def ctx(self, i):
+        """Rank i's context as a non-owning Context (stats, quad_info, oct_info, ...); valid until the group is closed."""
+        h = lib().pt_group_ctx(self._g, int(i))
+        if not h:
+            raise PtError("pt_group_ctx: no rank %d in a group of %d" % (i, self.size))
+        return Context._view(h)
+
+    def upload_scene(self, entities, materials, textures=None, mesh_textures=None, env=None):
+        """Arguments as Context.upload_scene: the tree is built once, on rank 0's context, and cloned to the others."""
+        args, keep = _marshal_scene(entities, materials, textures, mesh_textures, env)
+        self._check(lib().pt_group_upload_scene(self._g, *args), "pt_group_upload_scene")
+        del keep
+
+    def set_materials(self, materials):
+        mats = np.ascontiguousarray(np.asarray(materials, np.float32).reshape(-1, PT_MAT_FLOATS))
+        self._check(lib().pt_group_set_materials(self._g, mats.ctypes.data_as(C.POINTER(C.c_float)), mats.shape[0]), "pt_group_set_materials")
+
+    def set_option(self, key, value):
+        self._check(lib().pt_group_set_option(self._g, key.encode(), int(value)), "pt_group_set_option")
+
+    def render(self, cam, W, H, spp, max_depth, want_rgba8=False):
+        rgb = np.empty((H, W, 3), np.float32)
+        rgba = np.empty((H, W), np.uint32) if want_rgba8 else None
+        self._check(lib().pt_group_render(self._g, C.byref(cam), W, H, spp, max_depth, rgb.ctypes.data_as(C.POINTER(C.c_float)),
+                                          rgba.ctypes.data_as(C.POINTER(C.c_uint32)) if rgba is not None else None), "pt_group_render")
+        return rgb, rgba

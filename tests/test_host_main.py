@@ -6,17 +6,19 @@ import os
 import shutil
 import struct
 import subprocess
+import sys
 
 import numpy as np
 import pytest
 
-from conftest import ASSETS, ROOT
+import rccl_stub
+from conftest import ASSETS, GOLDEN, ROOT
 
 PT_MAIN = os.path.join(ROOT, "owl-path-tracer_amd", "pt_main")
 
 
-def _run(args, cwd=None):
-    out = subprocess.run([PT_MAIN] + args, cwd=cwd, capture_output=True, text=True, timeout=600)
+def _run(args, cwd=None, env=None):
+    out = subprocess.run([PT_MAIN] + args, cwd=cwd, capture_output=True, text=True, timeout=600, env=env)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     return out
 
@@ -233,12 +235,9 @@ def _device_count():
     return torch.cuda.device_count()
 
 
-@pytest.mark.gpu
-def test_pt_main_environment_hdr_and_texture_end_to_end(tmp_path, orc, scene_io):
-    """SURVEY 8(f2): assets/environment.hdr (RLE RGBE) and a PNG texture through the real entry point on the GPU -
-    application.cpp:160 -> image_buffer.cpp:36-58 (stb tone map + vertical flip) -> device.cu:23-39 (miss shader lookup), and
-    application.cpp:225-246 -> device.cu:75-94 (texture).  The oracle gets the environment map as the product's own decoder
-    produces it (the decoder itself is checked against the stb formula in test_png_and_hdr_codecs)."""
+def _hdr_and_texture_assets(tmp_path, scene_io):
+    """A copy of assets/ with the cube's texture PNG, an environment.hdr (RLE RGBE) and settings that use both: (dir, texture, map
+    width, map height)."""
     from PIL import Image
 
     a = tmp_path / "assets"
@@ -261,6 +260,18 @@ def test_pt_main_environment_hdr_and_texture_end_to_end(tmp_path, orc, scene_io)
     s = json.load(open(os.path.join(ASSETS, "configs", "c1_cube.json")))
     s.update(buffer_size=[160, 96], max_samples=32, max_path_depth=6, environment_use=True, environment_auto=False, environment_intensity=1.0)
     (a / "settings.json").write_text(json.dumps(s))
+    return a, tex, EW, EH
+
+
+@pytest.mark.gpu
+def test_pt_main_environment_hdr_and_texture_end_to_end(tmp_path, orc, scene_io):
+    """SURVEY 8(f2): assets/environment.hdr (RLE RGBE) and a PNG texture through the real entry point on the GPU -
+    application.cpp:160 -> image_buffer.cpp:36-58 (stb tone map + vertical flip) -> device.cu:23-39 (miss shader lookup), and
+    application.cpp:225-246 -> device.cu:75-94 (texture).  The oracle gets the environment map as the product's own decoder
+    produces it (the decoder itself is checked against the stb formula in test_png_and_hdr_codecs)."""
+    from PIL import Image
+
+    a, tex, EW, EH = _hdr_and_texture_assets(tmp_path, scene_io)
     out = _run(["--assets", str(a), "--out", str(tmp_path)])
     png = tmp_path / "cube_bench_roughness(0.2).png"
     assert png.exists(), out.stderr
@@ -297,3 +308,94 @@ def test_pt_main_gpus_flag_is_bit_identical(tmp_path):
         os.makedirs(d)
         _run(["--assets", str(a), "--out", str(d), "--gpus", str(n)])
         assert open(d / name, "rb").read() == want, "--gpus %d differs from the single-context image" % n
+
+
+def _sweep_assets(tmp_path):
+    """C2 as a three-frame material sweep (the sphere's metallic 0, 0.5, 1 through pt_set_materials / pt_group_set_materials) at
+    200x120, 48 spp: (assets dir, PNG names)."""
+    a = tmp_path / "assets"
+    shutil.copytree(ASSETS, a)
+    s = json.load(open(os.path.join(ASSETS, "configs", "c2_cornell-box.json")))
+    s.update(buffer_size=[200, 120], max_samples=48)
+    s["test"] = dict(name="sweep", material_name="sphere", attribute_name="metallic", material_type=2, values=[0.0, 1.0], step_size=0.5)
+    (a / "settings.json").write_text(json.dumps(s))
+    return a, ["cornell-box_sweep_metallic(%.1f).png" % v for v in (0.0, 0.5, 1.0)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("workload", ["sweep", "hdr_and_texture"])
+def test_pt_main_devices_under_stub_collective(tmp_path, scene_io, workload):
+    """`pt_main --devices 0,0` / `0,0,0` (and `--gpus 2 --devices 0,0`): the group path with 2 and 3 contexts on one card, the stub
+    collective of tests/stub/fake_rccl.cpp standing in for RCCL (it is not RCCL; the real library refuses a device named twice).
+    Every PNG must be byte-identical to the single-context run's: a three-frame material sweep on the cornell box (every frame after
+    a pt_group_set_materials), and the textured cube under environment.hdr (texture + environment map through clone_scene)."""
+    if workload == "sweep":
+        a, names = _sweep_assets(tmp_path)
+    else:
+        a, names = _hdr_and_texture_assets(tmp_path, scene_io)[0], ["cube_bench_roughness(0.2).png"]
+    ref_dir = tmp_path / "ref"
+    os.makedirs(ref_dir)
+    _run(["--assets", str(a), "--out", str(ref_dir)])
+    want = [open(ref_dir / n, "rb").read() for n in names]
+    assert len(set(want)) == len(want), "the frames of the sweep must differ, or the material swap is not under test"
+    env = rccl_stub.stub_env()
+    for i, flags in enumerate((["--devices", "0,0"], ["--devices", "0,0,0"], ["--gpus", "2", "--devices", "0,0"])):
+        d = tmp_path / ("g%d" % i)
+        os.makedirs(d)
+        _run(["--assets", str(a), "--out", str(d)] + flags, env=env)
+        for n, w in zip(names, want):
+            assert open(d / n, "rb").read() == w, "%s: %s differs from the single-context image" % (" ".join(flags), n)
+
+
+@pytest.mark.parametrize("flags,word", [(["--devices", "0,x"], "--devices"), (["--devices", ""], "--devices"), (["--devices", "0,,1"], "--devices"),
+                                        (["--devices", "-1"], "--devices"), (["--devices", "0,0", "--gpus", "3"], "--gpus"),
+                                        (["--devices", "0", "--device", "1"], "--device"), (["--device", "-1", "--devices", "0"], "--device"),
+                                        (["--devices"], "--devices")])
+def test_pt_main_devices_flag_errors(flags, word):
+    """A device list that is empty or holds anything but non-negative integers, a count that disagrees with --gpus, and --devices next
+    to --device: exit status 1 and a message that names the option (no GPU needed: refused before anything is opened)."""
+    out = subprocess.run([PT_MAIN, "--assets", ASSETS, "--settings", os.path.join(ASSETS, "configs", "c1_cube.json")] + flags, capture_output=True, text=True, timeout=120)
+    assert out.returncode == 1, out.stderr[-2000:]
+    assert out.stderr.startswith("error: ") and word in out.stderr and "--devices" in out.stderr, out.stderr[-2000:]
+
+
+BENCH_REHEARSAL_LIMIT = 20  # seconds: three times the 6.5 s measured, see test_bench_two_rank_rehearsal
+
+
+@pytest.mark.gpu
+def test_bench_two_rank_rehearsal(tmp_path):
+    """bench.py's N = 2 leg as the script itself offers it for a one-GPU box (PT_BENCH_DEVICE + PT_RCCL_PATH, bench.py main()): both
+    ranks on device 0 under torch.distributed.run, the stub collective instead of RCCL.  Checked: what the script promises for such
+    a run - one JSON line marked "rehearsal", n_gpus 2, a per-rank table whose pixel counts are the two shards - and that the frame it
+    dumps has the golden checksum, which test_c4_golden_crc_is_the_oracles ties to the oracle.  No timing number of this run means
+    anything (two ranks on one card through files) and none is asserted.  BENCH_REHEARSAL_LIMIT only guards against a hang: the
+    command took 5.8 and 6.5 s of wall time as the first thing run on an MI355X box (5.3 to 5.7 s inside the suite; everything it runs -
+    bench.py, the process-per-rank driver, the stub's file mode - is as in the parent commit), and the limit is three times the longest."""
+    import importlib.util
+    import zlib
+
+    try:
+        if importlib.util.find_spec("torch.distributed.run") is None:
+            raise ImportError
+    except ImportError:
+        pytest.skip("torch.distributed.run cannot be imported")
+    from owl_path_tracer_amd.pyhost import binding as B
+
+    dump = tmp_path / "dump"
+    env = rccl_stub.stub_env(PT_BENCH_DEVICE="0")
+    rc, so, se = rccl_stub.run_child([sys.executable, "-m", "torch.distributed.run", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "bench.py", "--gpus", "2",
+                                      "--steps", "1", "--warmup", "0", "--dump-outputs", str(dump)], env, BENCH_REHEARSAL_LIMIT, cwd=ROOT)
+    assert rc == 0, so[-2000:] + se[-4000:]
+    lines = [json.loads(l) for l in so.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, so[-4000:]
+    out = lines[0]
+    assert out.get("rehearsal") is True and out["n_gpus"] == 2
+    W, H = 1920, 1080
+    rows = sorted(out["per_rank"], key=lambda r: r["rank"])
+    assert [r["rank"] for r in rows] == [0, 1]
+    assert [r["pixels"] for r in rows] == [len(B.shard_pixels(W, H, 16, r, 2)) for r in range(2)]
+    assert sum(r["pixels"] for r in rows) == W * H
+    frame = np.load(dump / "frame.npy")
+    assert frame.shape == (H, W, 3) and frame.dtype == np.float32
+    crc = zlib.crc32(np.ascontiguousarray(frame, np.float32).tobytes()) & 0xFFFFFFFF  # bench.py: frame_crc
+    assert crc == json.load(open(os.path.join(GOLDEN, "c4_frame_crc.json")))["crc32_float3_frame"]

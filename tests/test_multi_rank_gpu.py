@@ -10,6 +10,7 @@ import time
 import numpy as np
 import pytest
 
+import rccl_stub
 from conftest import ROOT
 
 pytestmark = pytest.mark.gpu
@@ -92,17 +93,9 @@ def test_library_reduce_across_processes(tmp_path, world):
 @pytest.mark.parametrize("world", [2, 3, 4])  # (4 ranks + this process = 5 of the 6 processes the pool allows on the card)
 def test_library_reduce_with_stub_collective(tmp_path, world):
     """The library's N-rank plumbing with N > 1 PROCESSES on ONE GPU: every rank opens device 0 and PT_RCCL_PATH points at
-    tests/stub/fake_rccl.cpp (built here), whose ncclReduce is a blocking sum through files.  That is NOT RCCL and proves nothing
+    tests/stub/fake_rccl.cpp (built by tests/rccl_stub.py), whose ncclReduce is a blocking sum through files.  That is NOT RCCL and proves nothing
     about RCCL - what it exercises is our side, which had never run with more than one rank (round-3 advisor finding): the unique id
     through a file, pt_comm_init_rank per process and the pixel shard it sets, ONE reduce per frame and rank although only the root
     passes buffers, the root's RGBA8 pack of the reduced frame, a second frame on the same communicator, teardown.  The frame on
     rank 0 must be the single-GPU frame bit for bit (world 3 leaves ranks with different tile counts)."""
-    import shutil
-
-    gxx = shutil.which("g++")
-    if not gxx or not os.path.exists("/opt/rocm/include/rccl/rccl.h"):
-        pytest.skip("g++ or the RCCL header is missing")
-    stub = str(tmp_path / "libfake_rccl.so")
-    subprocess.check_call([gxx, "-O1", "-std=c++17", "-fPIC", "-shared", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-o", stub,
-                           os.path.join(ROOT, "tests", "stub", "fake_rccl.cpp"), "-L/opt/rocm/lib", "-lamdhip64", "-Wl,-rpath,/opt/rocm/lib"])
-    _run_ranks(tmp_path, world, dict(os.environ, PT_RCCL_PATH=stub), same_device=True)
+    _run_ranks(tmp_path, world, rccl_stub.stub_env(), same_device=True)
