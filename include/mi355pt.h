@@ -151,6 +151,37 @@ int pt_render_device(pt_ctx* ctx, const pt_camera* cam, int32_t width, int32_t h
  * it (the image is then incomplete); pt_get_stats reports the same. */
 int pt_synchronize(pt_ctx* ctx);
 
+/* ---- batch render: K frames of the uploaded scene in one launch sequence (no reference counterpart: the reference's test_loop,
+ * host/main.cpp, renders its material sweep one owlLaunch2D per value) ----
+ * Every frame has its own camera and its own material table; size, samples, depth and environment are shared.  Frame f is stored at
+ * out + f * W*H*3 (out_rgba8 + f * W*H) in the framebuffer order of pt_render, and is bit for bit what pt_set_materials(frame f's table)
+ * + pt_render(frame f's camera) gives: the frames are stacked into one virtual image of W x (K*H) whose pixels - own RNG stream each,
+ * seeded by the position inside the frame - share one pixel queue, one cost pre-pass, one sort and one main launch.
+ *   n_materials must equal the scene's; a row's texture slot stays the one pt_upload_scene derived; the context's own table
+ *   (pt_set_materials) is neither used (unless materials == NULL) nor changed.
+ *   Any n_frames >= 1: a batch that exceeds what one launch sequence can hold (K*H <= 65535 rows, K*W*H < 2^24 pixels, option
+ *   "batch_frames") is cut into several by the library (pt_debug_plan_batch shows how); a single frame beyond them is PT_E_LIMIT.
+ *   The pixel shard applies per frame (a rank owns the same tiles in every frame); with a communicator pt_render_batch issues ONE
+ *   reduce per launch sequence over all of its frames and rank 0 receives them.
+ *   Refused with PT_E_INVALID and a message, never rendered frame by frame: option "kernel" = 1, "latency", "timeline".
+ *   pt_get_stats afterwards covers the whole batch: kernel_ms from the first launch to the last kernel end, launches = render-kernel
+ *   launches of all launch sequences, counted renders sum over the frames; prepass_ms is the first launch sequence's, the geometry
+ *   fields the last one's.  The readers below (pt_debug_read_queue / _tiers / _laps) then describe the LAST launch sequence, pixel ids
+ *   being those of its virtual image: x + W * (f*H + y), f counted from the sequence's first frame. */
+typedef struct pt_frame {
+    pt_camera camera;
+    const float* materials; /* n_materials * PT_MAT_FLOATS of this frame; NULL = the context's current table */
+} pt_frame;
+int pt_render_batch(pt_ctx* ctx, const pt_frame* frames, int32_t n_frames, int32_t n_materials, int32_t width, int32_t height,
+                    int32_t max_samples, int32_t max_path_depth, float* out_rgb, uint32_t* out_rgba8);
+/* The same, asynchronous on `stream` (NULL = the context's), frames left in HBM (n_frames * W*H*3 floats; d_out_rgba8 optional); no reduce. */
+int pt_render_batch_device(pt_ctx* ctx, const pt_frame* frames, int32_t n_frames, int32_t n_materials, int32_t width, int32_t height,
+                           int32_t max_samples, int32_t max_path_depth, void* d_out_rgb, void* d_out_rgba8, void* stream);
+/* Host only, no GPU needed: how a batch of n_frames is cut into launch sequences.  out[i] = frames of sequence i (at most cap are
+ * written); max_frames = option "batch_frames" (0: what the limits allow).  Returns the number of sequences, PT_E_LIMIT if one frame
+ * is already too large, PT_E_INVALID for bad arguments. */
+int64_t pt_debug_plan_batch(int32_t width, int32_t height, int32_t n_frames, int32_t max_frames, int32_t* out, int64_t cap);
+
 /* ---- N GPUs: pixel tiles sharded over ranks + ONE RCCL sum-reduce of the float3 framebuffer onto rank 0 (pt_comm.cpp) ----
  * No reference counterpart (the reference is single-GPU: create_context(nullptr, 1), application.cpp:62); for N > 1 these
  * replace the render + read-back of application.cpp:363-369.  Every pixel has exactly one non-zero contributor, so the
@@ -211,7 +242,8 @@ int pt_group_render(pt_group* g, const pt_camera* cam, int32_t width, int32_t he
  *   queue when that holds at least this many; > 64 = never; off by itself when an environment map is bound);
  *   "quad" 1 (default: two binary levels per 128-byte record) | 0;  "box_exact" -1 (default: slab distances by one fma per plane, the
  *   subtracting form when the camera is more than 42 scene extents from the origin) | 0 | 1;  "fallback" 1: use the wavefront kernel's 168-VGPR instance (what
- *   the library does by itself when the 128-VGPR instance of a build needs scratch). */
+ *   the library does by itself when the 128-VGPR instance of a build needs scratch);
+ *   "batch_frames" 0 (default: as many as the limits allow) | n: most frames per launch sequence of pt_render_batch. */
 int pt_set_option(pt_ctx* ctx, const char* key, int64_t value);
 int pt_get_stats(pt_ctx* ctx, pt_stats* out);
 

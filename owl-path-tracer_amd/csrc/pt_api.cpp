@@ -156,18 +156,23 @@ int64_t shard_pixels(int W, int H, int tile, int rank, int world, uint32_t* ids,
     return n;
 }
 
-int ensure_queue(pt_ctx* c, int W, int H)
+// frames > 1 (pt_render_batch): the queue of the virtual image of W x (frames * H) - the shard of ONE frame, repeated per frame with the
+// ids moved down by the frames above it (id = x + W * (f * H + y)): a rank owns the same tiles in every frame.
+int ensure_queue(pt_ctx* c, int W, int H, int frames = 1)
 {
-    if (c->queue_valid && c->q_w == W && c->q_h == H && c->q_rank == c->rank && c->q_world == c->world && c->q_tile == c->tile) return PT_OK;
-    int64_t n = shard_pixels(W, H, c->tile, c->rank, c->world, nullptr, 0);
-    if (n < 0) return fail(c, PT_E_INVALID, "invalid pixel shard (%d of %d)", c->rank, c->world);
+    if (c->queue_valid && c->q_w == W && c->q_h == H && c->q_frames == frames && c->q_rank == c->rank && c->q_world == c->world && c->q_tile == c->tile) return PT_OK;
+    const int64_t n1 = shard_pixels(W, H, c->tile, c->rank, c->world, nullptr, 0);
+    if (n1 < 0) return fail(c, PT_E_INVALID, "invalid pixel shard (%d of %d)", c->rank, c->world);
+    const int64_t n = n1 * frames;
     std::vector<uint32_t> ids((size_t)n);
-    shard_pixels(W, H, c->tile, c->rank, c->world, ids.data(), n);
+    shard_pixels(W, H, c->tile, c->rank, c->world, ids.data(), n1);
+    for (int f = 1; f < frames; ++f)
+        for (int64_t i = 0; i < n1; ++i) ids[(size_t)(f * n1 + i)] = ids[(size_t)i] + (uint32_t)f * (uint32_t)W * (uint32_t)H;
     int rc = upload(c, c->d_pixels, ids.data(), ids.size() * 4);
     if (rc) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream)); // ids is a local
     c->n_pixels = (uint32_t)n;
-    c->q_w = W; c->q_h = H; c->q_rank = c->rank; c->q_world = c->world; c->q_tile = c->tile;
+    c->q_w = W; c->q_h = H; c->q_frames = frames; c->q_rank = c->rank; c->q_world = c->world; c->q_tile = c->tile;
     c->queue_valid = true;
     return PT_OK;
 }
@@ -203,6 +208,11 @@ int check_watchdog(pt_ctx* c)
     if (c->kernel != 2 || !c->d_laps.p || !c->flag_pending) return PT_OK;
     uint32_t wd = 0;
     HIP_TRY(c, hipMemcpy(&wd, c->d_laps.p, 4, hipMemcpyDeviceToHost));
+    if (c->last_seqs > 1 && c->d_seq_flags.p) { // a batch: the flags of its earlier launch sequences (the next sequence clears d_laps)
+        std::vector<uint32_t> fl((size_t)c->last_seqs - 1);
+        HIP_TRY(c, hipMemcpy(fl.data(), c->d_seq_flags.p, fl.size() * 4, hipMemcpyDeviceToHost));
+        for (uint32_t v : fl) wd |= v;
+    }
     c->flag_pending = false;
     c->watchdog_fired = wd != 0;
     if (wd) return fail(c, PT_E_HIP, "render kernel watchdog fired (scheduler made no progress); the image is incomplete");
@@ -263,7 +273,7 @@ void pt_destroy(pt_ctx* c)
         (void)hipStreamSynchronize(c->stream);
         (void)pt_comm_destroy(c);
         DevBuf* bufs[] = {&c->d_nodes8, &c->d_nodes4, &c->d_nodes, &c->d_tris, &c->d_shade, &c->d_materials, &c->d_texdesc, &c->d_env, &c->d_pixels, &c->d_heads,
-                          &c->d_rng, &c->d_accum, &c->d_out, &c->d_out8, &c->d_counters, &c->d_dbg_in, &c->d_dbg_out, &c->d_slots, &c->d_laps, &c->d_ring, &c->d_params, &c->d_cost, &c->d_sorted, &c->d_sort_scratch, &c->d_dbg_start, &c->d_bucket, &c->d_tiers};
+                          &c->d_rng, &c->d_accum, &c->d_out, &c->d_out8, &c->d_counters, &c->d_dbg_in, &c->d_dbg_out, &c->d_slots, &c->d_laps, &c->d_ring, &c->d_params, &c->d_cost, &c->d_sorted, &c->d_sort_scratch, &c->d_dbg_start, &c->d_bucket, &c->d_tiers, &c->d_batch_mats, &c->d_batch_cams, &c->d_seq_flags};
         for (DevBuf* b : bufs) release(*b);
         for (void* p : c->d_textures) (void)hipFree(p);
         if (c->ev0) (void)hipEventDestroy(c->ev0);
@@ -308,6 +318,7 @@ int pt_set_option(pt_ctx* c, const char* key, int64_t value)
     else if (k == "groups") c->groups = (int)(value < 0 ? 0 : (value > 2 ? 2 : value)); // group walk: 0 never, 1 sparse waves (default), 2 always
     else if (k == "ploc_radius") c->ploc_radius = (int)(value < 1 ? 1 : (value > 64 ? 64 : value)); // bvh_builder 2: neighbours searched on either side
     else if (k == "box_exact") c->box_exact = (int)(value < 0 ? -1 : (value > 0 ? 1 : 0)); // slab test form: -1 automatic (fma unless the camera is far outside the scene), 0 fma, 1 subtracting
+    else if (k == "batch_frames") c->batch_frames = (int)(value < 0 ? 0 : (value > 0x7fffffff ? 0x7fffffff : value)); // pt_render_batch: most frames per launch sequence (0: what the limits allow)
     else if (k == "quad") c->quad = value != 0; // wavefront kernel: quad nodes (two binary levels per fetch), next pt_render
     else if (k == "node_pairs") c->node_pairs = value != 0;
     else if (k == "leaf_align") c->leaf_align = (int)(value < 1 ? 1 : (value > 8 ? 8 : value));
@@ -758,6 +769,7 @@ int probe_eval(pt_ctx* c, PtKernelParams& P, int op, int in_stride, float* out, 
 // All schedules give the same image bit for bit (a pixel's stream does not depend on who renders it, or when).
 struct FramePlan {
     int variant = 0, use_count = 0; // instance of the render kernel (pt_launch_render) and whether it is the instrumented one
+    bool batch = false;             // the batch instances (pt_launch_render_batch): set by the caller before plan_frame
     PtGeometry geo{};               // its launch geometry
     int bpc = 0, grid = 0;          // workgroups per CU, of the (main) launch
     int ring_grid = 0;              // with a tier plan: the workgroups of the ring schedule (the plan's fallback; the pre-pass launches these)
@@ -848,7 +860,10 @@ int plan_frame(pt_ctx* c, const PtKernelParams& P, int max_samples, FramePlan& f
     const int group_entries = P.nodes8 ? 7 * c->depth8 + 1 : 0;
     int want_ns = c->slots_per_wave > 0 ? c->slots_per_wave : PT_DEFAULT_NS;
     const PtGeometry& g = f.geo;
-    auto geometry = [&] { return pt_kernel_geometry(f.variant, f.use_count, P.stack_entries, group_entries, want_ns, P.box_exact, &f.geo); };
+    auto geometry = [&] {
+        return f.batch ? pt_batch_kernel_geometry(f.variant, f.use_count, P.stack_entries, group_entries, want_ns, P.box_exact, &f.geo)
+                       : pt_kernel_geometry(f.variant, f.use_count, P.stack_entries, group_entries, want_ns, P.box_exact, &f.geo);
+    };
     hipError_t ge = geometry();
     if (ge == hipErrorInvalidConfiguration && f.variant == 2 && !f.use_count) {
         f.variant = 3;
@@ -903,7 +918,9 @@ int plan_frame(pt_ctx* c, const PtKernelParams& P, int max_samples, FramePlan& f
 }
 
 // Every device buffer of a frame sized from its plan, and every clear it needs: all of it is enqueued before the frame's first event.
-int frame_buffers(pt_ctx* c, const FramePlan& f, int W, int H, void* d_out_rgb, void* d_out_rgba8, hipStream_t stream)
+// (H: rows of the launch's image - of the virtual image of a batch's launch sequence; first = false: a later launch sequence of a batch,
+// whose work counters go on counting)
+int frame_buffers(pt_ctx* c, const FramePlan& f, int W, int H, void* d_out_rgb, void* d_out_rgba8, hipStream_t stream, bool first = true)
 {
     int rc;
     const int n_chunks = f.sc.n_chunks;
@@ -940,7 +957,7 @@ int frame_buffers(pt_ctx* c, const FramePlan& f, int W, int H, void* d_out_rgb, 
     }
     if (f.use_count) {
         if ((rc = ensure(c, c->d_counters, sizeof(PtCounters)))) return rc;
-        HIP_TRY(c, hipMemsetAsync(c->d_counters.p, 0, sizeof(PtCounters), stream));
+        if (first) HIP_TRY(c, hipMemsetAsync(c->d_counters.p, 0, sizeof(PtCounters), stream));
     }
     if (c->latency && f.sorted) {
         if ((rc = ensure(c, c->d_dbg_start, (size_t)W * H * 8))) return rc; // + rays per pixel (instrumented instance)
@@ -1038,6 +1055,153 @@ int finish_frame(pt_ctx* c, hipStream_t stream, int W, int H, const FramePlan* f
     return PT_OK;
 }
 
+// The launches of a planned frame (H: rows of the launch's image, see frame_buffers).  mark_prepass: record evm after the queue sort
+// (a batch does so in its first launch sequence only: pt_stats.prepass_ms).
+int run_launches(pt_ctx* c, const FramePlan& f, PtKernelParams& P, int W, int H, int max_samples, hipStream_t stream, bool mark_prepass)
+{
+    for (int l = 0; l < f.n_launch; ++l) {
+        launch_params(c, f, l, max_samples, P);
+        if (f.sorted && l == 1) { // the queue in cost order (and the tier plan) from the pre-pass's cost image
+            HIP_TRY(c, pt_launch_sort_pixels((const uint8_t*)c->d_cost.p, W, H, c->cost_radius, (const uint32_t*)c->d_pixels.p, (uint32_t*)c->d_sorted.p,
+                                             c->n_pixels, (uint32_t)f.pre, (uint32_t*)c->d_sort_scratch.p, (uint8_t*)c->d_bucket.p, stream));
+            if (f.tiers) HIP_TRY(c, pt_launch_plan_tiers((const uint32_t*)c->d_sort_scratch.p, c->n_pixels, f.grid, f.geo.ns, c->whole > 0, (uint32_t*)c->d_tiers.p, stream));
+            if (mark_prepass) HIP_TRY(c, hipEventRecord(c->evm, stream));
+        }
+        const PtKernelParams* dP = (const PtKernelParams*)c->d_params.p + l; // one block per launch: launch l+1's copy never races launch l
+        if (c->kernel == 2) HIP_TRY(c, pt_launch_store_params(&P, (PtKernelParams*)dP, stream)); // by value: P is reused for the next launch
+        // (with a tier plan prepared only the main launch has every resident workgroup; the pre-pass measures the pixels' costs in waves
+        // as dense as the ring schedule's - C2 74.3 -> 71 ms, 1/8 shard 198 -> 194)
+        const int grid = (f.tiers && l == 0) ? f.ring_grid : f.grid;
+        HIP_TRY(c, f.batch ? pt_launch_render_batch(&P, dP, f.variant, grid, f.geo.lds_bytes, stream, f.use_count)
+                           : pt_launch_render(&P, dP, f.variant, grid, f.geo.lds_bytes, stream, f.use_count));
+    }
+    return PT_OK;
+}
+
+// ---- batches (pt_render_batch) ------------------------------------------------------------------------------------------
+// K frames of the uploaded scene are stacked into a virtual image of W x (K * H) and rendered by ONE launch sequence over the queue of
+// that image (pt_kernel_batch.hip).  What bounds K, from the code that sets each limit:
+//   * a path slot holds its pixel as x | y << 16 (pt_kernel.hip, S_PIX) and pt_render_device accepts heights up to 65535: K * H <= 65535;
+//   * plan_chunks refuses n_pixels >= 2^24 (the express ticket space): K * W * H < 2^24, taken for the whole frame whatever the rank's
+//     shard, so that every rank of a communicator cuts a batch alike (one reduce per launch sequence on each).  With n_chunks <= 255
+//     this also keeps the (pixel, chunk) tickets below plan_chunks' bound (2^24 * 255 < 0xfff00000);
+//   * option "batch_frames" (> 0).
+int64_t batch_max_frames(int W, int H, int max_frames)
+{
+    if (W <= 0 || H <= 0 || W > 65535 || H > 65535) return 0;
+    int64_t k = 65535 / H;
+    k = std::min<int64_t>(k, ((int64_t)(1 << 24) - 1) / ((int64_t)W * H));
+    if (max_frames > 0) k = std::min<int64_t>(k, max_frames);
+    return k;
+}
+
+struct BatchArgs {
+    const pt_frame* frames;
+    int n_frames, W, H, max_samples, max_depth;
+};
+
+// One launch sequence: frames [f0, f0 + K) of the batch into d_out_rgb / d_out_rgba8 (already offset to frame f0).
+int batch_sequence(pt_ctx* c, const BatchArgs& a, int f0, int K, int seq, void* d_out_rgb, void* d_out_rgba8, hipStream_t stream, int* launches)
+{
+    const int W = a.W, H = a.H, Hv = K * a.H;
+    int rc = ensure_queue(c, W, H, K);
+    if (rc) return rc;
+    if (c->n_pixels == 0) { // a rank without a tile: zeros, no kernel (see pt_render_device)
+        HIP_TRY(c, hipMemsetAsync(d_out_rgb, 0, (size_t)W * Hv * 3 * sizeof(float), stream));
+        if (d_out_rgba8) HIP_TRY(c, hipMemsetAsync(d_out_rgba8, 0, (size_t)W * Hv * 4, stream));
+        if (c->count && c->d_counters.p && seq == 0) HIP_TRY(c, hipMemsetAsync(c->d_counters.p, 0, sizeof(PtCounters), stream));
+        return finish_frame(c, stream, W, Hv, nullptr, 0);
+    }
+    PtKernelParams P;
+    walk_params(c, &a.frames[f0].camera, P);
+    // one slab form per launch sequence: the subtracting one if ANY of its cameras is beyond the switch of walk_params (boxes only
+    // have to be conservative, so no image changes)
+    for (int f = 1; f < K && !P.box_exact; ++f) {
+        PtKernelParams Q;
+        walk_params(c, &a.frames[f0 + f].camera, Q);
+        P.box_exact = Q.box_exact;
+    }
+    FramePlan f;
+    f.batch = true;
+    if ((rc = plan_frame(c, P, a.max_samples, f))) return rc;
+    if ((rc = frame_buffers(c, f, W, Hv, d_out_rgb, d_out_rgba8, stream, seq == 0))) return rc;
+    frame_params(c, f, &a.frames[f0].camera, W, H, a.max_samples, a.max_depth, d_out_rgb, d_out_rgba8, P);
+    P.batch_frames = K;
+    P.batch_cams = (const float*)c->d_batch_cams.p + (size_t)12 * f0;
+    P.materials = (const float*)c->d_batch_mats.p + (size_t)f0 * c->n_materials * PT_MAT_STRIDE;
+    if ((rc = run_launches(c, f, P, W, Hv, a.max_samples, stream, seq == 0))) return rc;
+    *launches += f.n_launch;
+    return finish_frame(c, stream, W, Hv, &f, P.stack_entries);
+}
+
+// The whole batch on `stream`; with reduce = true (pt_render_batch) one pt_reduce_framebuffer per launch sequence over all of its frames.
+int batch_device(pt_ctx* c, const pt_frame* frames, int32_t n_frames, int32_t n_materials, int32_t W, int32_t H, int32_t max_samples, int32_t max_depth,
+                 void* d_out_rgb, void* d_out_rgba8, void* d_reduce_rgba8, hipStream_t stream, bool reduce)
+{
+    if (n_frames < 1 || !frames) return fail(c, PT_E_INVALID, "pt_render_batch: a batch needs at least one frame (n_frames %d%s)", n_frames, frames ? "" : ", frames NULL");
+    if (!c->have_scene) return fail(c, PT_E_NO_SCENE, "no geometries (pt_upload_scene not called)");
+    if (n_materials != c->n_materials) return fail(c, PT_E_INVALID, "pt_render_batch: %d materials per frame, the scene has %d", n_materials, c->n_materials);
+    if (W <= 0 || H <= 0 || W > 65535 || H > 65535 || max_samples <= 0 || max_depth < 0 || max_depth > 63 || (int64_t)W * H > (int64_t)0x7fffffff)
+        return fail(c, PT_E_INVALID, "bad render size %dx%d spp %d depth %d (depth must be 0..63)", W, H, max_samples, max_depth);
+    // what only exists for one frame at a time is refused by name, never rendered by a loop of single frames
+    if (c->kernel != 2) return fail(c, PT_E_INVALID, "pt_render_batch: the lane-per-pixel kernel (option kernel = 1) has no batch form");
+    if (c->latency) return fail(c, PT_E_INVALID, "pt_render_batch: the per-pixel latency diagnostics (option latency) are per frame; switch them off for a batch");
+    if (c->timeline) return fail(c, PT_E_INVALID, "pt_render_batch: the chunk timeline (option timeline) is per frame; switch it off for a batch");
+    if (c->host_only) return fail(c, PT_E_NO_DEVICE, "host-only context: the HIP render path is required and there is no CPU fallback");
+    const int64_t kmax = batch_max_frames(W, H, c->batch_frames);
+    if (kmax < 1) return fail(c, PT_E_LIMIT, "pt_render_batch: one %dx%d frame already exceeds a launch sequence (< 2^24 pixels)", W, H);
+    HIP_TRY(c, hipSetDevice(c->device));
+    // every frame's camera and material table (the 17 floats of the caller + the context's texture slot per row) in HBM, once per batch
+    const size_t row = (size_t)c->n_materials * PT_MAT_STRIDE;
+    c->batch_cams_h.resize((size_t)n_frames * 12);
+    c->batch_mats_h.assign((size_t)n_frames * row, 0.0f);
+    for (int f = 0; f < n_frames; ++f) {
+        std::memcpy(&c->batch_cams_h[(size_t)f * 12], &frames[f].camera, 48);
+        float* dst = c->batch_mats_h.data() + (size_t)f * row;
+        if (!frames[f].materials) { // the context's current table
+            if (row) std::memcpy(dst, c->materials.data(), row * sizeof(float));
+            continue;
+        }
+        for (int i = 0; i < c->n_materials; ++i) {
+            std::memcpy(dst + (size_t)i * PT_MAT_STRIDE, frames[f].materials + (size_t)i * PT_MAT_FLOATS, PT_MAT_FLOATS * sizeof(float));
+            const int32_t slot = i < (int)c->material_texture.size() ? c->material_texture[i] : -1;
+            std::memcpy(dst + (size_t)i * PT_MAT_STRIDE + 17, &slot, 4);
+        }
+    }
+    int rc;
+    if ((rc = ensure(c, c->d_batch_cams, c->batch_cams_h.size() * 4)) || (rc = ensure(c, c->d_batch_mats, c->batch_mats_h.size() * 4))) return rc;
+    const int n_seq = (int)((n_frames + kmax - 1) / kmax);
+    if ((rc = ensure(c, c->d_seq_flags, (size_t)n_seq * 4))) return rc;
+    HIP_TRY(c, hipMemcpyAsync(c->d_batch_cams.p, c->batch_cams_h.data(), c->batch_cams_h.size() * 4, hipMemcpyHostToDevice, stream));
+    if (row) HIP_TRY(c, hipMemcpyAsync(c->d_batch_mats.p, c->batch_mats_h.data(), c->batch_mats_h.size() * 4, hipMemcpyHostToDevice, stream));
+    HIP_TRY(c, hipStreamSynchronize(stream)); // (as pt_set_materials: the staging vectors are the context's and may be refilled by the next call)
+    const BatchArgs a{frames, n_frames, W, H, max_samples, max_depth};
+    const size_t npx = (size_t)W * H;
+    int launches = 0;
+    bool launched = false; // some launch sequence ran kernels (a rank without a tile runs none)
+    c->last_seqs = 0;
+    HIP_TRY(c, hipEventRecord(c->ev0, stream));
+    for (int s = 0, f0 = 0; f0 < n_frames; ++s) {
+        const int K = (int)std::min<int64_t>(kmax, n_frames - f0);
+        float* o = (float*)d_out_rgb + (size_t)f0 * npx * 3;
+        uint32_t* o8 = d_out_rgba8 ? (uint32_t*)d_out_rgba8 + (size_t)f0 * npx : nullptr;
+        if ((rc = batch_sequence(c, a, f0, K, s, o, o8, stream, &launches))) return rc;
+        // the sequence's watchdog flag, kept for check_watchdog: the next sequence clears the block it lives in
+        if (f0 + K < n_frames && c->d_laps.p && c->flag_pending) HIP_TRY(c, hipMemcpyAsync((uint32_t*)c->d_seq_flags.p + s, c->d_laps.p, 4, hipMemcpyDeviceToDevice, stream));
+        else if (f0 + K < n_frames) HIP_TRY(c, hipMemsetAsync((uint32_t*)c->d_seq_flags.p + s, 0, 4, stream));
+        if (reduce && c->comm) {
+            uint32_t* r8 = d_reduce_rgba8 ? (uint32_t*)d_reduce_rgba8 + (size_t)f0 * npx : nullptr;
+            if ((rc = pt_reduce_framebuffer(c, o, r8, (int64_t)K * (int64_t)npx, stream))) return rc;
+        }
+        launched = launched || c->flag_pending;
+        c->last_seqs = s + 1;
+        f0 += K;
+    }
+    c->flag_pending = launched;
+    c->last_launches = launches; // render-kernel launches of all launch sequences (pt_stats.launches)
+    return PT_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -1074,20 +1238,8 @@ int pt_render_device(pt_ctx* c, const pt_camera* cam, int32_t W, int32_t H, int3
     frame_params(c, f, cam, W, H, max_samples, max_depth, d_out_rgb, d_out_rgba8, P);
 
     HIP_TRY(c, hipEventRecord(c->ev0, stream));
-    for (int l = 0; l < f.n_launch; ++l) {
-        launch_params(c, f, l, max_samples, P);
-        if (f.sorted && l == 1) { // the queue in cost order (and the tier plan) from the pre-pass's cost image
-            HIP_TRY(c, pt_launch_sort_pixels((const uint8_t*)c->d_cost.p, W, H, c->cost_radius, (const uint32_t*)c->d_pixels.p, (uint32_t*)c->d_sorted.p,
-                                             c->n_pixels, (uint32_t)f.pre, (uint32_t*)c->d_sort_scratch.p, (uint8_t*)c->d_bucket.p, stream));
-            if (f.tiers) HIP_TRY(c, pt_launch_plan_tiers((const uint32_t*)c->d_sort_scratch.p, c->n_pixels, f.grid, f.geo.ns, c->whole > 0, (uint32_t*)c->d_tiers.p, stream));
-            HIP_TRY(c, hipEventRecord(c->evm, stream));
-        }
-        const PtKernelParams* dP = (const PtKernelParams*)c->d_params.p + l; // one block per launch: launch l+1's copy never races launch l
-        if (c->kernel == 2) HIP_TRY(c, pt_launch_store_params(&P, (PtKernelParams*)dP, stream)); // by value: P is reused for the next launch
-        // (with a tier plan prepared only the main launch has every resident workgroup; the pre-pass measures the pixels' costs in waves
-        // as dense as the ring schedule's - C2 74.3 -> 71 ms, 1/8 shard 198 -> 194)
-        HIP_TRY(c, pt_launch_render(&P, dP, f.variant, (f.tiers && l == 0) ? f.ring_grid : f.grid, f.geo.lds_bytes, stream, f.use_count));
-    }
+    if ((rc = run_launches(c, f, P, W, H, max_samples, stream, true))) return rc;
+    c->last_seqs = 1;
     return finish_frame(c, stream, W, H, &f, P.stack_entries);
 }
 
@@ -1134,6 +1286,59 @@ int pt_render(pt_ctx* c, const pt_camera* cam, int32_t W, int32_t H, int32_t max
         c->stats.d2h_ms = ms;
     }
     return check_watchdog(c);
+}
+
+int pt_render_batch_device(pt_ctx* c, const pt_frame* frames, int32_t n_frames, int32_t n_materials, int32_t W, int32_t H, int32_t max_samples, int32_t max_depth,
+                           void* d_out_rgb, void* d_out_rgba8, void* stream_v)
+{
+    if (!c || !d_out_rgb) return PT_E_INVALID;
+    return batch_device(c, frames, n_frames, n_materials, W, H, max_samples, max_depth, d_out_rgb, d_out_rgba8, nullptr, stream_v ? (hipStream_t)stream_v : c->stream, false);
+}
+
+int pt_render_batch(pt_ctx* c, const pt_frame* frames, int32_t n_frames, int32_t n_materials, int32_t W, int32_t H, int32_t max_samples, int32_t max_depth,
+                    float* out_rgb, uint32_t* out_rgba8)
+{
+    // with a communicator attached only rank 0 receives the frames (as pt_render)
+    const bool root = !c || !c->comm || c->comm_rank == 0;
+    if (!c || (root && !out_rgb)) return PT_E_INVALID;
+    int rc;
+    const bool sized = n_frames >= 1 && W > 0 && H > 0 && !c->host_only; // (everything else is refused by batch_device, with its message)
+    const size_t npx = sized ? (size_t)n_frames * (size_t)W * (size_t)H : 0;
+    if (sized) {
+        HIP_TRY(c, hipSetDevice(c->device));
+        if ((rc = ensure(c, c->d_out, npx * 12))) return rc;
+        if (out_rgba8 && (rc = ensure(c, c->d_out8, npx * 4))) return rc;
+    }
+    // with a communicator the RGBA8 frames are made from the reduced float frames on the root, one reduce per launch sequence
+    rc = batch_device(c, frames, n_frames, n_materials, W, H, max_samples, max_depth, c->d_out.p, (out_rgba8 && !c->comm) ? c->d_out8.p : nullptr,
+                      (root && out_rgba8 && c->comm) ? c->d_out8.p : nullptr, c->stream, true);
+    if (rc) return rc;
+    HIP_TRY(c, hipEventRecord(c->evr, c->stream));
+    if (root) {
+        HIP_TRY(c, hipMemcpyAsync(out_rgb, c->d_out.p, npx * 12, hipMemcpyDeviceToHost, c->stream));
+        if (out_rgba8) HIP_TRY(c, hipMemcpyAsync(out_rgba8, c->d_out8.p, npx * 4, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY(c, hipEventRecord(c->evd, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    {
+        float ms = 0.0f;
+        HIP_TRY(c, hipEventElapsedTime(&ms, c->ev1, c->evr)); // (the last launch sequence's reduce; the earlier ones lie inside kernel_ms)
+        c->stats.reduce_ms = ms;
+        HIP_TRY(c, hipEventElapsedTime(&ms, c->evr, c->evd));
+        c->stats.d2h_ms = ms;
+    }
+    return check_watchdog(c);
+}
+
+int64_t pt_debug_plan_batch(int32_t W, int32_t H, int32_t n_frames, int32_t max_frames, int32_t* out, int64_t cap)
+{
+    if (n_frames < 1 || max_frames < 0 || W <= 0 || H <= 0 || W > 65535 || H > 65535 || cap < 0) return PT_E_INVALID;
+    const int64_t kmax = batch_max_frames(W, H, max_frames);
+    if (kmax < 1) return PT_E_LIMIT;
+    int64_t n = 0;
+    for (int64_t f0 = 0; f0 < n_frames; f0 += kmax, ++n)
+        if (out && n < cap) out[n] = (int32_t)std::min<int64_t>(kmax, n_frames - f0);
+    return n;
 }
 
 int pt_get_stats(pt_ctx* c, pt_stats* out)

@@ -49,17 +49,17 @@ struct pt_ctx {
     bool have_scene = false;
 
     // device
-    DevBuf d_nodes8, d_nodes4, d_nodes, d_tris, d_shade, d_materials, d_texdesc, d_env, d_pixels, d_heads, d_rng, d_accum, d_out, d_out8, d_counters, d_dbg_in, d_dbg_out, d_slots, d_laps, d_ring, d_params, d_cost, d_sorted, d_sort_scratch, d_dbg_start, d_bucket, d_tiers;
+    DevBuf d_nodes8, d_nodes4, d_nodes, d_tris, d_shade, d_materials, d_texdesc, d_env, d_pixels, d_heads, d_rng, d_accum, d_out, d_out8, d_counters, d_dbg_in, d_dbg_out, d_slots, d_laps, d_ring, d_params, d_cost, d_sorted, d_sort_scratch, d_dbg_start, d_bucket, d_tiers, d_batch_mats, d_batch_cams, d_seq_flags; // d_batch_*: per-frame tables of pt_render_batch; d_seq_flags: watchdog flags of its earlier launch sequences
     std::vector<void*> d_textures;
 
     // pixel queue
-    int q_w = 0, q_h = 0, q_rank = 0, q_world = 1, q_tile = 16;
+    int q_w = 0, q_h = 0, q_frames = 1, q_rank = 0, q_world = 1, q_tile = 16;
     int rank = 0, world = 1, tile = 16;
     uint32_t n_pixels = 0;
     bool queue_valid = false;
 
     // options
-    int spp_per_launch = 0, count = 0, blocks_per_cu = 0, leaf_size = 4, max_bvh_depth = 48, kernel = 2, slots_per_wave = 0, chunk_spp = 64, chunk_tail_min = -1, schedule = 1, prepass_spp = 0, census_mode = 0, sticky_pct = -1, latency = 0, cost_radius = 2, timeline = 0, node_pairs = 0, leaf_align = 1, bvh_builder = 3, quad = 1, groups = 1, wide_leaves = 1, fallback = 0, ploc_radius = 16, express_permille = -1, ns_express = 8, whole = -1, box_exact = -1;
+    int spp_per_launch = 0, count = 0, blocks_per_cu = 0, leaf_size = 4, max_bvh_depth = 48, kernel = 2, slots_per_wave = 0, chunk_spp = 64, chunk_tail_min = -1, schedule = 1, prepass_spp = 0, census_mode = 0, sticky_pct = -1, latency = 0, cost_radius = 2, timeline = 0, node_pairs = 0, leaf_align = 1, bvh_builder = 3, quad = 1, groups = 1, wide_leaves = 1, fallback = 0, ploc_radius = 16, express_permille = -1, ns_express = 8, whole = -1, box_exact = -1, batch_frames = 0;
     int tune[8] = {};
 
     void* comm = nullptr;   // ncclComm_t once pt_comm_init_rank / pt_group_create attached one (pt_comm.cpp)
@@ -71,6 +71,8 @@ struct pt_ctx {
     int last_w = 0, last_h = 0;
     size_t lap_ticks_ofs = 0;
     int last_chunks = 0;
+    int last_seqs = 1;                 // launch sequences of the last render (pt_render_batch may need several)
+    std::vector<float> batch_cams_h, batch_mats_h; // pt_render_batch: staging of the per-frame tables
 };
 
 namespace pti {

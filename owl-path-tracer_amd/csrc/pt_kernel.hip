@@ -27,9 +27,23 @@
 // The traversal stack is stack[level][lane] in LDS: bank = lane % 32 whatever the level, so the stack itself is conflict-free (the LDS
 // bank conflicts rocprof reports - a third of the LDS cycles, at ~6 % LDS utilisation - come from the slot-indexed state arrays,
 // lray / lstate[field * ns + slot], where lanes hold arbitrary slots).
+//
+// BATCH BUILD.  pt_kernel_batch.hip includes this file with PT_BATCH = 1: the same scheduler and device functions as instances of
+// pt_render_batch_kernel, which render K frames of one scene stacked into a virtual image of width x (K * height) - own camera and
+// material table per frame (pt_render_batch).  Everything that only looks at the queue works on the virtual image unchanged; the
+// places that must know the frame are the PT_BATCH blocks below (frame_of).  With PT_BATCH = 0 the preprocessor removes all of it:
+// the single-frame instances carry no batch code ("Batches").
 #include "pt_launch.h"
 #include "pt_tiers.h"
 #include "pt_trace.h"
+#ifndef PT_BATCH
+#define PT_BATCH 0
+#endif
+#if PT_BATCH
+#define PT_RENDER_KERNEL pt_render_batch_kernel
+#else
+#define PT_RENDER_KERNEL pt_render_wave_kernel
+#endif
 #ifndef PT_WAVES_PER_EU
 #define PT_WAVES_PER_EU 4
 #endif
@@ -209,6 +223,15 @@ __device__ __forceinline__ uint32_t ld_agent(const uint32_t* p) { return __hip_a
 __device__ __forceinline__ void st_agent(uint32_t* p, uint32_t v) { __hip_atomic_store(gp(p), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ uint32_t take_agent(uint32_t* p) { return __hip_atomic_fetch_add(gp(p), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
+#if PT_BATCH
+// Row py of the virtual image -> frame and row inside the frame (P.height is the height of ONE frame).
+__device__ __forceinline__ void frame_of(const PtKernelParams& P, int py, int& frame, int& fy)
+{
+    frame = (int)((uint32_t)py / (uint32_t)P.height);
+    fy = py - frame * P.height;
+}
+#endif
+
 #define PT_NO_TICKET 0xfffffffeu // take_ticket: the queue is exhausted
 struct WaveTier {      // where this wave's pixels come from (wave-uniform)
     uint32_t* counter; // tier schedule: the ticket counter of the wave's tier, else null
@@ -273,7 +296,11 @@ __device__ __forceinline__ bool start_chunk(const PtKernelParams& P, uint32_t ti
     py = (int)(pid / (uint32_t)P.width);
     if (c == 0 && P.dbg_start) gp(P.dbg_start)[pid] = (uint32_t)wall_clock64();
     if ((c == 0 || c == PT_WHOLE) && P.sample_begin == 0) {
+#if PT_BATCH
+        rng = rng_init((uint32_t)px, (uint32_t)py % (uint32_t)P.height); // the pixel's row inside its frame
+#else
         rng = rng_init((uint32_t)px, (uint32_t)py); // device.cu:226
+#endif
         color = vs(0.0f);
     } else {
         rng = ld_agent(P.rng_state + pid);
@@ -310,7 +337,13 @@ __device__ __forceinline__ void finish_chunk(const PtKernelParams& P, uint32_t c
     }
     if (last_chunk && P.sample_begin + P.sample_count >= P.max_samples) {
         v3 out = color * (1.0f / (float)P.max_samples);                          // device.cu:247
+#if PT_BATCH
+        int frame, fy; // frame f is stored at f * W * H, rows flipped inside the frame
+        frame_of(P, py, frame, fy);
+        size_t ofs = (size_t)frame * ((size_t)P.width * (size_t)P.height) + (size_t)px + (size_t)P.width * (size_t)(P.height - 1 - fy);
+#else
         size_t ofs = (size_t)px + (size_t)P.width * (size_t)(P.height - 1 - py); // device.cu:251
+#endif
         float PT_AS1* orgb = gp(P.out_rgb);
         orgb[3 * ofs] = out.x;
         orgb[3 * ofs + 1] = out.y;
@@ -519,7 +552,13 @@ __device__ __forceinline__ void shade_pass(const PtKernelParams& P, WaveCtx& w, 
             v3 radiance;
             const int tslot = lane_miss ? -1 : (int)LF(L_AZ, ps_slot);
             const uint32_t scat0 = cn.scat;
+#if PT_BATCH
+            int frame, fy; // the material table of the pixel's frame
+            frame_of(P, py, frame, fy);
+            int r = shade_hit<COUNT>(P, P.materials + (size_t)frame * (size_t)(P.n_materials * PT_MAT_STRIDE), tslot, LFF(L_AX, ps_slot), LFF(L_AY, ps_slot), ps, radiance, cn);
+#else
             int r = shade_hit<COUNT>(P, P.materials, tslot, LFF(L_AX, ps_slot), LFF(L_AY, ps_slot), ps, radiance, cn);
+#endif
             if (COUNT && !lane_miss) branch = r == SR_RETRY ? 5 : (cn.scat != scat0 ? ps.lobe : 4);
             if (r == SR_RETRY) {
                 to_hit = true; // same hit, fresh draws (device.cu:196-201); L_A* still hold the hit
@@ -557,7 +596,13 @@ __device__ __forceinline__ void shade_pass(const PtKernelParams& P, WaveCtx& w, 
                 }
             }
             if (have_pixel) {
+#if PT_BATCH
+                int frame, fy; // the camera of the pixel's frame: a per-lane gather from the table in HBM
+                frame_of(P, py, frame, fy);
+                gen_camera_ray_from(P, gp(P.batch_cams) + 12 * frame, px, fy, ps);
+#else
                 gen_camera_ray(P, px, py, ps);
+#endif
                 to_ray = true;
             }
         }
@@ -873,7 +918,7 @@ __device__ __forceinline__ int traverse_groups(const PtKernelParams& P, WaveCtx&
 //   EXACT: the slab tests use the subtracting form (camera far outside the scene: node4_step) - instances of their own, so that the product
 //   instances carry one form only; the instrumented instance switches at run time (P.box_exact).
 template <bool COUNT, int WAVES, bool EXACT>
-__global__ void __launch_bounds__(PT_WAVE, WAVES) pt_render_wave_kernel(const PtKernelParams* __restrict__ Pp)
+__global__ void __launch_bounds__(PT_WAVE, WAVES) PT_RENDER_KERNEL(const PtKernelParams* __restrict__ Pp)
 {
     // The parameter block lives in HBM and is read with scalar loads where it is used.  Passed by value it arrives as
     // s_load_dwordx16 tuples that stay live for the whole kernel; the register allocator then spilled them to VGPR lanes
@@ -1197,28 +1242,43 @@ __global__ void __launch_bounds__(PT_WAVE, WAVES) pt_render_wave_kernel(const Pt
 // ---- launchers (called from pt_api.cpp) --------------------------------------------------------------------
 
 // d_params: device copy of *p (wavefront kernel reads its parameters from HBM; the caller keeps it stream-ordered)
+// (the batch build defines the same two functions for its own instances: pt_launch_render_batch / pt_batch_kernel_geometry, variants 2 and 3 only)
+#if PT_BATCH
+extern "C" hipError_t pt_launch_render_batch(const PtKernelParams* p, const PtKernelParams* d_params, int variant, int grid, size_t lds_bytes,
+                                             hipStream_t stream, int count)
+{
+    if (variant != 2 && variant != 3) return hipErrorInvalidValue; // the lane-per-pixel kernel has no batch form
+    if (p->batch_frames < 1 || p->batch_cams == nullptr) return hipErrorInvalidValue;
+#else
 extern "C" hipError_t pt_launch_render(const PtKernelParams* p, const PtKernelParams* d_params, int variant, int grid, size_t lds_bytes,
                                        hipStream_t stream, int count)
 {
     if (variant == 1) return pt_launch_render_lane(p, grid, lds_bytes, stream, count); // pt_kernel_aux.hip
+#endif
     const bool exact = p->box_exact != 0;
-    if (count) hipLaunchKernelGGL((pt_render_wave_kernel<true, PT_COUNT_WAVES_PER_EU, false>), dim3(grid), dim3(PT_WAVE), lds_bytes, stream, d_params);
-    else if (variant == 3 && exact) hipLaunchKernelGGL((pt_render_wave_kernel<false, PT_FALLBACK_WAVES, true>), dim3(grid), dim3(PT_WAVE), lds_bytes, stream, d_params);
-    else if (variant == 3) hipLaunchKernelGGL((pt_render_wave_kernel<false, PT_FALLBACK_WAVES, false>), dim3(grid), dim3(PT_WAVE), lds_bytes, stream, d_params);
-    else if (exact) hipLaunchKernelGGL((pt_render_wave_kernel<false, PT_WAVES_PER_EU, true>), dim3(grid), dim3(PT_WAVE), lds_bytes, stream, d_params);
-    else hipLaunchKernelGGL((pt_render_wave_kernel<false, PT_WAVES_PER_EU, false>), dim3(grid), dim3(PT_WAVE), lds_bytes, stream, d_params);
+    if (count) hipLaunchKernelGGL((PT_RENDER_KERNEL<true, PT_COUNT_WAVES_PER_EU, false>), dim3(grid), dim3(PT_WAVE), lds_bytes, stream, d_params);
+    else if (variant == 3 && exact) hipLaunchKernelGGL((PT_RENDER_KERNEL<false, PT_FALLBACK_WAVES, true>), dim3(grid), dim3(PT_WAVE), lds_bytes, stream, d_params);
+    else if (variant == 3) hipLaunchKernelGGL((PT_RENDER_KERNEL<false, PT_FALLBACK_WAVES, false>), dim3(grid), dim3(PT_WAVE), lds_bytes, stream, d_params);
+    else if (exact) hipLaunchKernelGGL((PT_RENDER_KERNEL<false, PT_WAVES_PER_EU, true>), dim3(grid), dim3(PT_WAVE), lds_bytes, stream, d_params);
+    else hipLaunchKernelGGL((PT_RENDER_KERNEL<false, PT_WAVES_PER_EU, false>), dim3(grid), dim3(PT_WAVE), lds_bytes, stream, d_params);
     return hipGetLastError();
 }
 
 // Launch geometry of a render variant (1: lane per pixel, 2: wavefront kernel, 3: the wavefront kernel's 168-VGPR fallback
 // instance): block size, dynamic LDS bytes, pixels a block keeps in flight (ns is chosen here for the wavefront kernel), per-block
 // global state words, registers, occupancy.  hipErrorInvalidConfiguration: the instance needs scratch (see below).
+#if PT_BATCH
+extern "C" hipError_t pt_batch_kernel_geometry(int variant, int count, int stack_entries, int group_entries, int want_ns, int exact, PtGeometry* g)
+{
+    if (variant != 2 && variant != 3) return hipErrorInvalidValue;
+#else
 extern "C" hipError_t pt_kernel_geometry(int variant, int count, int stack_entries, int group_entries, int want_ns, int exact, PtGeometry* g)
 {
     if (variant == 1) return pt_lane_kernel_geometry(count, stack_entries, g); // pt_kernel_aux.hip
-    const void* fn = count ? (const void*)pt_render_wave_kernel<true, PT_COUNT_WAVES_PER_EU, false>
-                     : variant == 3 ? (exact ? (const void*)pt_render_wave_kernel<false, PT_FALLBACK_WAVES, true> : (const void*)pt_render_wave_kernel<false, PT_FALLBACK_WAVES, false>)
-                                    : (exact ? (const void*)pt_render_wave_kernel<false, PT_WAVES_PER_EU, true> : (const void*)pt_render_wave_kernel<false, PT_WAVES_PER_EU, false>);
+#endif
+    const void* fn = count ? (const void*)PT_RENDER_KERNEL<true, PT_COUNT_WAVES_PER_EU, false>
+                     : variant == 3 ? (exact ? (const void*)PT_RENDER_KERNEL<false, PT_FALLBACK_WAVES, true> : (const void*)PT_RENDER_KERNEL<false, PT_FALLBACK_WAVES, false>)
+                                    : (exact ? (const void*)PT_RENDER_KERNEL<false, PT_WAVES_PER_EU, true> : (const void*)PT_RENDER_KERNEL<false, PT_WAVES_PER_EU, false>);
     const int n = want_ns < 16 ? 16 : (want_ns > 252 ? 252 : want_ns);
     g->block = PT_WAVE;
     g->ns = n;
@@ -1236,6 +1296,7 @@ extern "C" hipError_t pt_kernel_geometry(int variant, int count, int stack_entri
     return hipOccupancyMaxActiveBlocksPerMultiprocessor(&g->max_blocks_per_cu, fn, g->block, g->lds_bytes);
 }
 
+#if !PT_BATCH // (the probes belong to the single-frame build)
 // =====================================================================================================================
 // Ray probes (tests only: pt_debug_eval ops PT_PROBE_*, pt_launch.h; tests/test_gpu_ray_probes.py)
 // =====================================================================================================================
@@ -1405,3 +1466,4 @@ extern "C" hipError_t pt_launch_probe(const PtKernelParams* p, int op, const flo
     }
     return hipGetLastError();
 }
+#endif // !PT_BATCH

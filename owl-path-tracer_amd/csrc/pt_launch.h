@@ -41,6 +41,9 @@ hipError_t pt_launch_plan_tiers(const uint32_t* scratch, uint32_t n, int capacit
 hipError_t pt_launch_sort_pixels(const uint8_t* cost_img, int W, int H, int radius, const uint32_t* in, uint32_t* out, uint32_t n, uint32_t c0, uint32_t* scratch,
                                  uint8_t* bucket, hipStream_t stream);
 hipError_t pt_kernel_geometry(int variant, int count, int stack_entries, int group_entries, int want_ns, int exact, PtGeometry* g);
+// pt_kernel_batch.hip: the batch instances of the wavefront kernel (variants 2 and 3 and the instrumented instance; PtKernelParams::batch_*)
+hipError_t pt_launch_render_batch(const PtKernelParams* p, const PtKernelParams* d_params, int variant, int grid, size_t lds_bytes, hipStream_t stream, int count);
+hipError_t pt_batch_kernel_geometry(int variant, int count, int stack_entries, int group_entries, int want_ns, int exact, PtGeometry* g);
 int pt_debug_block(void);
 // pt_kernel_aux.hip: the lane-per-pixel variant (pt_launch_render / pt_kernel_geometry forward variant 1 to these)
 hipError_t pt_launch_render_lane(const PtKernelParams* p, int grid, size_t lds_bytes, hipStream_t stream, int count);

@@ -14,6 +14,8 @@ size_t pt_sort_scratch_bytes(uint32_t) { return 16; }
 hipError_t pt_launch_plan_tiers(const uint32_t*, uint32_t, int, int, int, uint32_t*, hipStream_t) { return hipErrorNotSupported; }
 hipError_t pt_launch_sort_pixels(const uint8_t*, int, int, int, const uint32_t*, uint32_t*, uint32_t, uint32_t, uint32_t*, uint8_t*, hipStream_t) { return hipErrorNotSupported; }
 hipError_t pt_kernel_geometry(int, int, int, int, int, int, PtGeometry*) { return hipErrorNotSupported; }
+hipError_t pt_launch_render_batch(const PtKernelParams*, const PtKernelParams*, int, int, size_t, hipStream_t, int) { return hipErrorNotSupported; }
+hipError_t pt_batch_kernel_geometry(int, int, int, int, int, int, PtGeometry*) { return hipErrorNotSupported; }
 int pt_debug_block(void) { return 256; }
 hipError_t pt_launch_probe(const PtKernelParams*, int, const float*, int, float*, int, long long, int, size_t, uint32_t*, hipStream_t) { return hipErrorNotSupported; }
 int pt_probe_lds_stack(void) { return 12; }

@@ -396,6 +396,26 @@ __device__ __forceinline__ void gen_camera_ray(const PtKernelParams& P, int px, 
     ps.retries = 0;
 }
 
+// The same ray from a camera record in HBM (12 floats: origin, llc, horizontal, vertical) and the row py INSIDE the pixel's frame: the
+// batch instances (pt_kernel_batch.hip), where every lane may render a pixel of another frame.  Operation for operation gen_camera_ray.
+__device__ __forceinline__ void gen_camera_ray_from(const PtKernelParams& P, const float PT_AS1* cam, int px, int py, PathState& ps)
+{
+    float rx = rng_next(ps.rng);
+    float ry = rng_next(ps.rng);
+    float su = ((float)px + rx) / (float)P.width;
+    float sv = ((float)py + ry) / (float)P.height;
+    const v3 cam_origin = V(cam[0], cam[1], cam[2]);
+    const v3 cam_llc = V(cam[3], cam[4], cam[5]);
+    const v3 cam_hor = V(cam[6], cam[7], cam[8]);
+    const v3 cam_ver = V(cam[9], cam[10], cam[11]);
+    ps.org = cam_origin;
+    ps.dir = normalize(((cam_llc + cam_hor * su) + cam_ver * sv) - cam_origin);
+    ps.throughput = vs(1.0f);
+    ps.depth = 0;
+    ps.lobe = kLobeNone;
+    ps.retries = 0;
+}
+
 template <bool COUNT>
 __device__ __forceinline__ void flush_counters(const PtKernelParams& P, const Counters& cn)
 {

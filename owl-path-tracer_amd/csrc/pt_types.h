@@ -157,4 +157,9 @@ struct PtKernelParams {
     int32_t groups;            // group walk: 0 = never, 1 = when a wave has few rays to trace (sparse wave), 2 = always (tests)
     int32_t tune[8];           // scheduler knobs (pt_set_option "tune0".."tune7"; 0 = built-in default), see pt_kernel.hip
     int32_t box_exact;         // wavefront kernel: 1 = slab distances as (plane - o) * (1 / d) instead of the fma form (camera farther than 40 scene extents from the origin)
+    // Batch render (pt_render_batch; read by the instances of pt_kernel_batch.hip only, appended so that no earlier offset moves): the launch covers
+    // batch_frames frames stacked into a virtual image of width x (batch_frames * height); height stays the height of ONE frame, pixel ids, the cost
+    // image, rng_state and accum are those of the virtual image, materials holds one table per frame (n_materials * PT_MAT_STRIDE floats each)
+    int32_t batch_frames;
+    const float* batch_cams;   // camera of frame f: 12 floats at batch_cams + 12 * f
 };

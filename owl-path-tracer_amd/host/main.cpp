@@ -7,7 +7,9 @@
 // (-1: load + build only, no render), --gpus N (devices --device .. --device + N - 1 of this node, default 0..N-1: pixel tiles sharded over them, one RCCL reduce of the
 // float3 framebuffer onto device 0 - pt_group_* in mi355pt.h; the image is bit-identical to --gpus 1), --devices a,b,c (the same
 // group path on exactly these devices, the reduce onto the first; with --gpus the counts must agree, with --device it is an error;
-// a device named twice is refused by the real RCCL), --dump-scene FILE (binary dump of the ingested scene for the loader tests).
+// a device named twice is refused by the real RCCL), --dump-scene FILE (binary dump of the ingested scene for the loader tests),
+// --batch K (K >= 1: test_loop collects K sweep steps and renders them with ONE pt_render_batch - one launch sequence for K frames -
+// instead of K x pt_set_materials + pt_render; the PNGs are byte for byte the same; not together with --gpus / --devices).
 #include <sys/stat.h>
 #include <unistd.h>
 
@@ -85,6 +87,7 @@ struct App {
     pt_group* group = nullptr; // --gpus N: N contexts + the library's RCCL communicator
     pt_camera cam{};
     std::string out_dir;
+    int batch = 0; // --batch K: sweep steps per pt_render_batch (0: one pt_render per step)
 };
 
 void check(App& a, int rc, const char* what)
@@ -114,6 +117,33 @@ void render_frame(App& a, const std::string& values)
     std::fprintf(stderr, "  %.1f ms kernel, %.1f Msamples/s\n", st.kernel_ms, (double)W * H * a.settings.max_samples / (st.kernel_ms * 1e3));
 }
 
+// --batch: the collected sweep steps (material table and value string each) as one pt_render_batch; one PNG per step as render_frame writes it
+void render_batch(App& a, const std::vector<std::vector<float>>& tables, const std::vector<std::string>& values)
+{
+    std::fprintf(stderr, "TRACING (batch of %zu)\n", tables.size());
+    const int W = a.settings.buffer_size[0], H = a.settings.buffer_size[1];
+    const size_t K = tables.size(), npx = (size_t)W * H;
+    std::vector<pt_frame> frames(K);
+    for (size_t f = 0; f < K; ++f) {
+        frames[f].camera = a.cam;
+        frames[f].materials = tables[f].data();
+    }
+    std::vector<float> rgb(K * npx * 3);
+    std::vector<uint32_t> rgba(K * npx);
+    check(a, pt_render_batch(a.ctx, frames.data(), (int32_t)K, (int32_t)a.scene.materials.size(), W, H, a.settings.max_samples, a.settings.max_path_depth, rgb.data(),
+                             rgba.data()), "pt_render_batch");
+    pt_stats st;
+    pt_get_stats(a.ctx, &st);
+    for (size_t f = 0; f < K; ++f) {
+        std::string name = a.settings.scene + "_" + a.settings.test.name + "_" + a.settings.test.attribute_name + "(" + values[f] + ").png";
+        std::string path = a.out_dir + "/" + name;
+        imgio::write_png_rgba8(path, W, H, rgba.data() + f * npx);
+        std::printf("Image written to %s\n", path.c_str());
+    }
+    std::fprintf(stderr, "  %.1f ms kernel for %zu frames (%d launches), %.1f Msamples/s\n", st.kernel_ms, K, st.launches,
+                 (double)K * W * H * a.settings.max_samples / (st.kernel_ms * 1e3));
+}
+
 float* find_material(App& a)
 { // get_material, application.cpp:307-317 (the reference dereferences end() when the name is unknown; we report it)
     for (size_t i = 0; i < a.scene.materials.size(); ++i)
@@ -131,6 +161,8 @@ void test_loop(App& a)
     if (vec ? t.vec_values.size() < 2 : t.flt_values.size() < 2) throw std::runtime_error("test.values needs two entries");
     float* mat = find_material(a);
     const int attr = host::attribute_index(t.attribute_name);
+    std::vector<std::vector<float>> tables; // --batch: the steps collected so far
+    std::vector<std::string> names;
     for (int i = 0; i <= 100; i += vstep) {
         const float c = i / 100.0f;
         std::string values;
@@ -144,6 +176,16 @@ void test_loop(App& a)
             float v = t.flt_values[0] + (t.flt_values[1] - t.flt_values[0]) * c;
             if (attr >= 0) mat[attr] = v;
             values = fmt1(v);
+        }
+        if (a.batch > 0) { // the step's table goes into the batch; the context's own table is not touched
+            tables.push_back(a.materials);
+            names.push_back(values);
+            if ((int)tables.size() == a.batch || i + vstep > 100) {
+                render_batch(a, tables, names);
+                tables.clear();
+                names.clear();
+            }
+            continue;
         }
         if (a.group) check(a, pt_group_set_materials(a.group, a.materials.data(), (int32_t)a.scene.materials.size()), "pt_group_set_materials");
         else check(a, pt_set_materials(a.ctx, a.materials.data(), (int32_t)a.scene.materials.size()), "pt_set_materials"); // reset_field
@@ -163,7 +205,7 @@ int main(int argc, char** argv)
         std::string settings_path, dump;
         a.out_dir = cwd;
         int device = 0, gpus = 0; // gpus 0: flag not given, single context as in the reference
-        bool have_device = false, have_devices = false;
+        bool have_device = false, have_devices = false, have_batch = false;
         std::vector<int32_t> devs; // --devices
         for (int i = 1; i < argc; ++i) {
             std::string k = argv[i];
@@ -175,6 +217,7 @@ int main(int argc, char** argv)
             else if (k == "--devices") { devs = parse_devices(next()); have_devices = true; }
             else if (k == "--gpus") gpus = std::atoi(next().c_str());
             else if (k == "--dump-scene") dump = next();
+            else if (k == "--batch") { a.batch = std::atoi(next().c_str()); have_batch = true; }
             else if (k == "--convert-png" || k == "--convert-hdr") { // codec self-test hooks: decode with our reader, re-encode with our writer
                 std::string in = next(), out = next();
                 imgio::Image img = k == "--convert-png" ? imgio::load_png_rgba8(in) : imgio::load_hdr_as_ldr_rgba8(in);
@@ -184,6 +227,8 @@ int main(int argc, char** argv)
             else throw std::runtime_error("unknown option " + k);
         }
         if (gpus < 0) throw std::runtime_error("--gpus needs a positive count");
+        if (have_batch && a.batch < 1) throw std::runtime_error("--batch needs a positive number of frames per batch");
+        if (have_batch && (gpus > 0 || have_devices)) throw std::runtime_error("--batch cannot be combined with --gpus / --devices yet (pt_group_* has no batch call)");
         if (have_devices) {
             if (have_device) throw std::runtime_error("--devices and --device exclude each other (--devices lists every device)");
             if (gpus > 0 && gpus != (int)devs.size())

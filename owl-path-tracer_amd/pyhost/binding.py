@@ -58,6 +58,11 @@ class Camera(C.Structure):
         return np.array(list(self.origin) + list(self.llc) + list(self.horizontal) + list(self.vertical), np.float32)
 
 
+class Frame(C.Structure):
+    """pt_frame: one frame of a batch - its camera and its material table (NULL: the context's current one)."""
+    _fields_ = [("camera", Camera), ("materials", C.POINTER(C.c_float))]
+
+
 class Stats(C.Structure):
     _fields_ = [("kernel_ms", C.c_double), ("launches", C.c_int32), ("vgprs", C.c_int32), ("sgprs", C.c_int32), ("lds_bytes", C.c_int32),
                 ("block", C.c_int32), ("grid", C.c_int32), ("stack_entries", C.c_int32),
@@ -79,7 +84,8 @@ EXPORTS = ["pt_create", "pt_destroy", "pt_last_error", "pt_abi_version", "pt_upl
            "pt_to_camera_data", "pt_debug_closest_hit_host", "pt_debug_closest_hit_host_n", "pt_debug_export_tree", "pt_debug_eval", "pt_debug_read_queue", "pt_debug_read_laps", "pt_debug_read_finish", "pt_debug_read_tiers", "pt_debug_plan_tiers",
            "pt_comm_get_unique_id", "pt_comm_init_rank", "pt_comm_destroy", "pt_reduce_framebuffer", "pt_host_alloc", "pt_host_free",
            "pt_group_create", "pt_group_destroy", "pt_group_size", "pt_group_ctx", "pt_group_last_error", "pt_group_upload_scene",
-           "pt_group_set_materials", "pt_group_set_option", "pt_group_render", "pt_debug_quad_info", "pt_debug_oct_info", "pt_debug_clone_scene"]
+           "pt_group_set_materials", "pt_group_set_option", "pt_group_render", "pt_debug_quad_info", "pt_debug_oct_info", "pt_debug_clone_scene",
+           "pt_render_batch", "pt_render_batch_device", "pt_debug_plan_batch"]
 PT_COMM_ID_BYTES = 128
 
 _lib = None
@@ -156,6 +162,10 @@ def lib():
     L.pt_debug_oct_info.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
     L.pt_debug_clone_scene.argtypes = [C.c_void_p, C.c_void_p]
     L.pt_group_render.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_int32, C.c_int32, C.c_int32, C.c_int32, fp, C.POINTER(C.c_uint32)]
+    L.pt_render_batch.argtypes = [C.c_void_p, C.POINTER(Frame), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, fp, C.POINTER(C.c_uint32)]
+    L.pt_render_batch_device.argtypes = [C.c_void_p, C.POINTER(Frame), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.pt_debug_plan_batch.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int64]
+    L.pt_debug_plan_batch.restype = C.c_int64
     _lib = L
     return L
 
@@ -242,6 +252,33 @@ def plan_tiers(bucket_pixels, capacity, ns=96, force=False):
     if n < 0:
         raise RuntimeError("pt_debug_plan_tiers: %d" % n)
     return [dict(zip(("q0", "pixels", "per_wave", "wave0", "waves", "cost_class"), (int(x) for x in t[1 + 8 * i:7 + 8 * i]))) for i in range(int(t[0]))]
+
+
+def plan_batch(W, H, n_frames, max_frames=0):
+    """How pt_render_batch cuts n_frames frames of W x H into launch sequences (host only): frames per sequence.  max_frames = option
+    "batch_frames".  Raises PtError when one frame is already beyond a launch sequence, or for bad arguments."""
+    n = lib().pt_debug_plan_batch(int(W), int(H), int(n_frames), int(max_frames), None, 0)
+    if n < 0:
+        raise PtError("pt_debug_plan_batch failed (%d): %s" % (n, "one frame exceeds a launch sequence" if n == -5 else "invalid arguments"))
+    out = (C.c_int32 * int(n))()
+    lib().pt_debug_plan_batch(int(W), int(H), int(n_frames), int(max_frames), out, int(n))
+    return [int(x) for x in out]
+
+
+def _marshal_frames(frames):
+    """frames: list of (Camera, materials or None), materials (n, 17) float32.  Returns (Frame array, materials per frame, keep-alive)."""
+    arr = (Frame * max(1, len(frames)))()
+    keep, n_mat = [], 0
+    for i, (cam, mats) in enumerate(frames):
+        C.memmove(C.byref(arr[i].camera), C.byref(cam), C.sizeof(Camera))
+        if mats is None:
+            arr[i].materials = None
+        else:
+            m = np.ascontiguousarray(np.asarray(mats, np.float32).reshape(-1, PT_MAT_FLOATS))
+            keep.append(m)
+            n_mat = m.shape[0]
+            arr[i].materials = m.ctypes.data_as(C.POINTER(C.c_float))
+    return arr, n_mat, keep
 
 
 def _marshal_scene(entities, materials, textures=None, mesh_textures=None, env=None):
@@ -337,6 +374,31 @@ class Context:
         self._check(lib().pt_render(self._h, C.byref(cam), W, H, spp, max_depth, rgb.ctypes.data_as(C.POINTER(C.c_float)),
                                     rgba.ctypes.data_as(C.POINTER(C.c_uint32)) if rgba is not None else None), "pt_render")
         return rgb, rgba
+
+    def render_batch(self, frames, W, H, spp, max_depth, want_rgba8=False, n_materials=None, receive=True):
+        """pt_render_batch: frames = list of (Camera, materials or None - the context's table).  Returns (K, H, W, 3) float32 and, with
+        want_rgba8, (K, H, W) uint32: frame k is what set_materials(frames[k][1]) + render(frames[k][0]) returns.  n_materials: only
+        needed when every frame passes None; receive = False: a non-root rank of a communicator (returns None, None)."""
+        arr, n_mat, keep = _marshal_frames(frames)
+        if n_materials is not None:
+            n_mat = int(n_materials)
+        K = len(frames)
+        rgb = np.empty((K, H, W, 3), np.float32) if receive else None
+        rgba = np.empty((K, H, W), np.uint32) if (want_rgba8 and receive) else None
+        self._check(lib().pt_render_batch(self._h, arr if K else None, K, n_mat, W, H, spp, max_depth,
+                                          rgb.ctypes.data_as(C.POINTER(C.c_float)) if rgb is not None else None,
+                                          rgba.ctypes.data_as(C.POINTER(C.c_uint32)) if rgba is not None else None), "pt_render_batch")
+        del keep
+        return rgb, rgba
+
+    def render_batch_device(self, frames, W, H, spp, max_depth, d_out_rgb, d_out_rgba8=None, stream=None, n_materials=None):
+        arr, n_mat, keep = _marshal_frames(frames)
+        if n_materials is not None:
+            n_mat = int(n_materials)
+        self._check(lib().pt_render_batch_device(self._h, arr if frames else None, len(frames), n_mat, W, H, spp, max_depth, C.c_void_p(d_out_rgb),
+                                                 C.c_void_p(d_out_rgba8) if d_out_rgba8 else None, C.c_void_p(stream) if stream else None),
+                    "pt_render_batch_device")
+        del keep
 
     def render_into(self, cam, W, H, spp, max_depth, rgb, rgba8=None):
         """pt_render into caller-owned arrays (e.g. a PinnedFrame); rgb may be None on the non-root ranks of a communicator."""

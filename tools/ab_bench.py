@@ -1,5 +1,9 @@
 #!/usr/bin/env python3
-"""A/B timing of libmi355pt.so variants on one GPU: PT_LIB_PATH=<.so> python tools/ab_bench.py [c4|c2] [reps] [opt=val ...]"""
+"""A/B timing of libmi355pt.so variants on one GPU: PT_LIB_PATH=<.so> python tools/ab_bench.py [c4|c2] [reps] [opt=val ...]
+
+batch=K (c2 / c3 / c4, with shard_rank= / shard_world= if wanted): K frames of a material sweep as ONE pt_render_batch (B) against the same
+K frames as K x (pt_set_materials + pt_render) (A), alternating in this process after one warm-up of each: kernel ms from pt_stats, wall
+ms around the calls including the read-back; the frames are compared bit for bit.  census=1 adds a counted batch (scheduler census)."""
 import os, sys, json, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -9,7 +13,7 @@ ptamd.load()
 from owl_path_tracer_amd.pyhost import binding as B, scene_io, procedural
 
 PRE_UPLOAD = ("leaf_size", "max_bvh_depth", "node_pairs", "leaf_align", "bvh_builder", "ploc_radius", "wide_leaves")  # builder / layout options: before upload_scene
-NOT_OPTIONS = ("finish", "tiers", "spp", "census", "shard_rank", "shard_world", "shard_tile", "detail_u", "detail_v", "chain", "sweep", "frame_out")
+NOT_OPTIONS = ("finish", "tiers", "spp", "census", "shard_rank", "shard_world", "shard_tile", "detail_u", "detail_v", "chain", "sweep", "frame_out", "batch")
 
 # C3 material sweep ("for BSDF coverage add a material sweep over metallic/clearcoat/transmission/sheen"; the reference's
 # driver is test_loop / modify_sbt, application.hpp:89-108, application.cpp:329-360): the attribute is set on the two objects of the
@@ -48,6 +52,76 @@ def cached_meshes(name, make):
     except OSError:
         pass
     return ms
+
+
+def batch_ab(ctx, which, mats, cam, W, H, spp, reps, opts):
+    """batch=K: see the module docstring.  C3: the first K rows of SWEEP; C2 / C4: one material's metallic at K values."""
+    K = int(opts["batch"])
+    base = np.stack([m for _, m, _ in mats]).astype(np.float32)
+    names = [n for n, _, _ in mats]
+    tables = []
+    if which == "c3":
+        if K > len(SWEEP):
+            raise SystemExit("c3 batch=K: K <= %d (the SWEEP table)" % len(SWEEP))
+        for label, edits in SWEEP[:K]:
+            mm = base.copy()
+            for i, n in enumerate(names):
+                if n != "ground":
+                    for k, v in edits.items():
+                        mm[i, k] = v
+            tables.append(mm)
+    else:
+        who = names.index("sphere") if "sphere" in names else 0
+        for j in range(K):
+            mm = base.copy()
+            mm[who, 4] = j / max(1, K - 1)  # metallic
+            tables.append(mm)
+    frames = [(cam, t) for t in tables]
+
+    def run_a():
+        t0 = time.perf_counter()
+        k_ms, out = 0.0, []
+        for c, t in frames:
+            ctx.set_materials(t)
+            rgb, _ = ctx.render(c, W, H, spp, 16)
+            k_ms += ctx.stats()["kernel_ms"]
+            out.append(rgb)
+        return k_ms, (time.perf_counter() - t0) * 1e3, out
+
+    def run_b():
+        t0 = time.perf_counter()
+        rgb, _ = ctx.render_batch(frames, W, H, spp, 16)
+        wall = (time.perf_counter() - t0) * 1e3
+        return ctx.stats()["kernel_ms"], wall, rgb
+
+    _, _, fa = run_a()  # warm-up of each, and the parity check
+    _, _, fb = run_b()
+    same = all(np.array_equal(fa[f].view(np.uint32), fb[f].view(np.uint32)) for f in range(K))
+    a_k, a_w, b_k, b_w = [], [], [], []
+    for _ in range(reps):
+        k, w, _ = run_a(); a_k.append(k); a_w.append(w)
+        k, w, _ = run_b(); b_k.append(k); b_w.append(w)
+    st = ctx.stats()
+    ctx.set_materials(base)
+    owned = B.shard_pixels(W, H, int(opts.get("shard_tile", 16)), int(opts["shard_rank"]), int(opts.get("shard_world", 8))).size if "shard_rank" in opts else W * H
+    slots = 256 * 16 * 96  # nominal: 256 CUs x 16 one-wave workgroups x 96 path slots
+    med = lambda x: float(np.median(x))
+    out = {"lib": os.path.basename(B.LIB_PATH), "scene": which, "opts": opts, "K": K, "frames_identical": bool(same), "reps": reps,
+           "A_loop_kernel_ms": [round(x, 2) for x in a_k], "B_batch_kernel_ms": [round(x, 2) for x in b_k], "A_loop_wall_ms": [round(x, 2) for x in a_w], "B_batch_wall_ms": [round(x, 2) for x in b_w],
+           "A_ms_per_frame": round(med(a_k) / K, 2), "B_ms_per_frame": round(med(b_k) / K, 2), "A_wall_ms_per_frame": round(med(a_w) / K, 2), "B_wall_ms_per_frame": round(med(b_w) / K, 2),
+           "A_spread_ms_per_frame": round((max(a_k) - min(a_k)) / K, 2), "A_minus_B_ms_per_frame": round((med(a_k) - med(b_k)) / K, 2),
+           "pixels_per_slot_A": round(owned / slots, 3), "pixels_per_slot_B": round(K * owned / slots, 3), "B_launches": st["launches"], "B_vgprs": st["vgprs"], "B_variant": st["kernel_variant"],
+           "B_whole_pixels": st["whole_pixels"], "B_express_pixels": st["express_pixels"]}
+    if opts.get("census"):
+        ctx.set_option("count", 1)
+        ctx.render_batch(frames, W, H, spp, 16)
+        cs = ctx.stats()
+        ctx.set_option("count", 0)
+        sc = cs["sched"]
+        out["B_census"] = {"lane_utilisation": round(sc[15] / max(1, sc[12]) / 64.0, 3), "idle_lanes/iter": round(sc[13] / max(1, sc[12]), 2), "hit_items/pass": round(sc[7] / max(1, sc[6]), 2),
+                           "miss_items/pass": round(sc[9] / max(1, sc[8]), 2), "winddown_ray_share": round(sc[17] / max(1, cs["rays"]), 4), "rays": cs["rays"], "samples": cs["samples"],
+                           "group_ray_share": round(cs["groups"][5] / max(1, cs["rays"]), 4), "counted_kernel_ms": round(cs["kernel_ms"], 2)}
+    print(json.dumps(out))
 
 
 def main():
@@ -96,6 +170,10 @@ def main():
     for k, v in opts.items():
         if k not in PRE_UPLOAD and k not in NOT_OPTIONS:
             ctx.set_option(k, int(v))
+    if opts.get("batch"):
+        if which not in ("c2", "c3", "c4"):
+            raise SystemExit("batch=K: c2, c3 or c4")
+        return batch_ab(ctx, which, mats, cam, W, H, spp, reps, opts)
     if opts.get("sweep"):  # c3 sweep=1: one timed frame (+ one counted frame) per material variant
         base = np.stack([m for _, m, _ in mats]).astype(np.float32)
         names = [n for n, _, _ in mats]
