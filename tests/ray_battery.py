@@ -8,7 +8,8 @@ slab form is claimed.  Every ray is finite and its direction has unit length to 
 here can make a walk spin.
 
 Also: the hierarchy read-back turned into parent maps (`TreePaths`), the structure checks both files run on it, and a float32 numpy
-emulation of the product's slab tests (`slab_margin`).
+emulation of the product's slab tests (`slab_margin`); closed meshes with rays from inside and the battery as the exact-geometry
+referee takes it (tests/exact_hit.py, tests/test_exact_hit.py, tests/test_gpu_exact_hit.py).
 """
 import os
 
@@ -529,3 +530,113 @@ def slab_margin(lo, hi, o, inv, tbest, exact, octant):
         ok = tn <= tfp
         margin = (tfp.astype(np.float64) - tn.astype(np.float64)) / np.spacing(np.abs(tf)).astype(np.float64)
     return ok, margin
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# closed meshes with shared float32 vertices, rays from strictly inside: exact geometry says every such ray hits
+# ---------------------------------------------------------------------------------------------------------------------
+def icosphere(sub):
+    """Unit icosphere, (20 x 4^sub, 3, 3) float32; neighbours share bit-identical float32 vertices."""
+    p = (1 + 5 ** 0.5) / 2
+    V = [(-1, p, 0), (1, p, 0), (-1, -p, 0), (1, -p, 0), (0, -1, p), (0, 1, p), (0, -1, -p), (0, 1, -p), (p, 0, -1), (p, 0, 1), (-p, 0, -1), (-p, 0, 1)]
+    F = [(0, 11, 5), (0, 5, 1), (0, 1, 7), (0, 7, 10), (0, 10, 11), (1, 5, 9), (5, 11, 4), (11, 10, 2), (10, 7, 6), (7, 1, 8),
+         (3, 9, 4), (3, 4, 2), (3, 2, 6), (3, 6, 8), (3, 8, 9), (4, 9, 5), (2, 4, 11), (6, 2, 10), (8, 6, 7), (9, 8, 1)]
+    V = [np.array(v, float) / np.linalg.norm(v) for v in V]
+    for _ in range(sub):
+        cache, F2 = {}, []
+
+        def mid(a, b):
+            k = (min(a, b), max(a, b))
+            if k not in cache:
+                m = V[a] + V[b]
+                V.append(m / np.linalg.norm(m))
+                cache[k] = len(V) - 1
+            return cache[k]
+
+        for a, b, c in F:
+            ab, bc, ca = mid(a, b), mid(b, c), mid(c, a)
+            F2 += [(a, ab, ca), (b, bc, ab), (c, ca, bc), (ab, bc, ca)]
+        F = F2
+    return np.array(V, np.float32)[np.array(F)]
+
+
+CLOSED_RADIUS = 1.7
+CLOSED_OFFSET = 13.6  # 4 extents of the icosphere
+
+
+def closed_mesh_names():
+    return ["box", "ico320", "ico1280", "ico1280_offset"]
+
+
+def make_closed_mesh(name):
+    """((n, 3, 3) float32 triangles, centre, half-width of the cube of origins strictly inside)."""
+    if name == "box":
+        lo, hi = np.float32([-1.25, -0.5, -2.0]), np.float32([0.75, 1.5, 1.0])
+        c = np.array([[lo[0] if (i & 1) == 0 else hi[0], lo[1] if (i & 2) == 0 else hi[1], lo[2] if (i & 4) == 0 else hi[2]] for i in range(8)], np.float32)
+        quads = [(0, 1, 3, 2), (4, 6, 7, 5), (0, 4, 5, 1), (2, 3, 7, 6), (0, 2, 6, 4), (1, 5, 7, 3)]
+        F = [f for a, b, cc, d in quads for f in ((a, b, cc), (a, cc, d))]
+        return c[np.array(F)], 0.5 * (lo.astype(np.float64) + hi), 0.6
+    sub, off = {"ico320": (2, 0.0), "ico1280": (3, 0.0), "ico1280_offset": (3, CLOSED_OFFSET)}[name]
+    tris = (icosphere(sub) * np.float32(CLOSED_RADIUS) + np.float32(off)).astype(np.float32)
+    return tris, np.full(3, float(np.float32(off))), 0.6
+
+
+CLOSED_SETS = ("random", "edges_and_vertices")
+
+
+def closed_mesh_rays(tris, centre, half, rng, n):
+    """{set name: (n, 6) float32 rays} from origins strictly inside: random directions; aimed at points on shared edges, a quarter of
+    them at vertices."""
+    o = (centre + rng.uniform(-half, half, (n, 3))).astype(np.float32)
+    out = {"random": np.concatenate([o, _rand_dirs(rng, n)], 1)}
+    k, e = rng.integers(0, tris.shape[0], n), rng.integers(0, 3, n)
+    a, b = tris[k, e].astype(np.float64), tris[k, (e + 1) % 3].astype(np.float64)
+    s = rng.random((n, 1))
+    s[: n // 4] = 0.0
+    o = (centre + rng.uniform(-half, half, (n, 3))).astype(np.float32)
+    out["edges_and_vertices"] = np.concatenate([o, _unit32(a + (b - a) * s - o)], 1)
+    return {k: np.ascontiguousarray(v, np.float32) for k, v in out.items()}
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# how many rays per class the exact referee (tests/exact_hit.py) takes on a scene: it visits every (ray, triangle) pair in numpy
+# ---------------------------------------------------------------------------------------------------------------------
+REFEREE_PAIRS = int(os.environ.get("PT_REFEREE_PAIRS", "12000000"))
+REFEREE_MIN_RAYS = 120
+
+
+def referee_rays_per_class(n_tris, n_per_class):
+    """PT_PROBE_RAYS per class where the scene is small, fewer on large ones (a battery has ~10.5 n rays), never below 120: with
+    120 every class and every far-origin distance is still drawn."""
+    return int(min(n_per_class, max(REFEREE_MIN_RAYS, REFEREE_PAIRS // (11 * max(1, n_tris)))))
+
+
+_referee_cache = {}
+
+
+def referee_battery(orc, name, n_per_class):
+    """Scene, the battery's rays (same seed and planes as the other two files; fewer per class on large scenes) and the referee's
+    tables for them, once per scene and process: dict(tris, rays, cls, tables, n, seconds)."""
+    import time
+
+    import exact_hit
+    from owl_path_tracer_amd.pyhost import binding as B
+
+    key = (name, n_per_class)
+    if key not in _referee_cache:
+        tris = make_scene(name)
+        n = referee_rays_per_class(tris.shape[0], n_per_class)
+        S = oracle_scene(orc, tris)
+        host = B.Context(-1)
+        host.set_option("leaf_size", 4)
+        host.set_option("wide_leaves", 1)
+        upload(host, tris)
+        t4 = trees_of(host.export_trees())[1]
+        host.close()
+        used = t4.ref != -1
+        planes = np.stack([t4.lo[used], t4.hi[used]], 1) if t4.n_nodes else None
+        rays, cls = make_rays(tris, np.random.default_rng(4242), n, planes=planes, hit_fn=lambda r: S.intersect_n(r, use_bvh=True)[:2])
+        t0 = time.time()
+        tables = exact_hit.Tables(tris, rays)
+        _referee_cache[key] = dict(tris=tris, rays=rays, cls=cls, tables=tables, n=n, S=S, seconds=time.time() - t0)
+    return _referee_cache[key]

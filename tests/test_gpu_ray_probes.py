@@ -16,6 +16,7 @@ Default size: 2 000 rays per class, ~21 000 rays per scene, ten scenes, 63 launc
 16 host threads (tests/test_gpu_fuzz.py: ~15 s).  PT_PROBE_RAYS=N for a larger sweep, PT_WRITE_PROFILES=1 records counts and times in
 profiles/r06_ray_probes.json: run once with 10 000 (1.03 M rays, 13.5 s) - no mismatch inside the domain in any of the 54 (op,
 builder, leaf size) combinations per scene, none at 10-42 extents, 31 (quad) / 18 (group) of 252 000 beyond 42 extents.
+Every counted mismatch outside the domain must lie between two admissible hits: both answers satisfy R1 and R2 of tests/exact_hit.py.
 """
 import json
 import os
@@ -24,6 +25,7 @@ import time
 import numpy as np
 import pytest
 
+import exact_hit
 import ray_battery as rb
 from owl_path_tracer_amd.pyhost import binding as B
 
@@ -73,6 +75,7 @@ def test_probes_against_brute_force(orc, name):
     host.close()
     t_gpu = 0.0
     max_sp, parks = 0, 0
+    referee = exact_hit.OnDemand(tris, rays)  # for the counted mismatches: they may differ, but only between two admissible hits
     for builder in BUILDERS:
         for leaf in LEAVES:
             ctx = B.Context(0)
@@ -96,6 +99,11 @@ def test_probes_against_brute_force(orc, name):
                 for k, m in ((0, mid), (2, far), (4, copl)):  # [mismatches, rays] at 10-42 extents, beyond 42, classes 8 / 9
                     rec[k] += int((b & m).sum())
                     rec[k + 1] += int(m.sum())
+                out_idx = np.nonzero(b & ~held)[0]
+                for who, ans in ((op, exact_hit.answer_of_probe(out)), ("brute force", truth)):
+                    wrong = referee.inadmissible(out_idx, ans, with_t=not group or who != op)
+                    assert wrong.size == 0, "%s and brute force differ outside the domain (%s, builder %d leaf %d) and %s's answer breaks R1 or R2 of tests/exact_hit.py on %d rays; first: class %d %r" % (
+                        op, name, builder, leaf, who, wrong.size, cls[wrong[0]], rays[wrong[0]].tolist())
                 bh = b & held
                 print("%s builder %d leaf %d %-14s mismatches %d of %d held; 10-42 extents %d of %d; beyond %d of %d" % (name, builder, leaf, op, bh.sum(), held.sum(), (b & mid).sum(), mid.sum(), (b & far).sum(), far.sum()))
                 assert not bh.any(), "%s, builder %d leaf %d: %d of %d rays differ from brute force; first: class %d %r got %r want %r" % (

@@ -16,6 +16,7 @@ Three layers, on the scenes and the ray battery of tests/ray_battery.py (shared 
 
 PT_WRITE_PROFILES=1 writes the measured margins and counts to profiles/r06_slab_margins.json (run once; the file is committed).
 ~50 s on 8 threads (2 000 rays per class and scene, ~21 000 rays per scene; PT_PROBE_RAYS=N for more).
+Every counted mismatch outside the domain must lie between two admissible hits: both answers satisfy R1 and R2 of tests/exact_hit.py.
 """
 import json
 import os
@@ -24,6 +25,7 @@ import time
 import numpy as np
 import pytest
 
+import exact_hit
 import ray_battery as rb
 from owl_path_tracer_amd.pyhost import binding as B
 
@@ -107,6 +109,7 @@ def test_closest_hit_definition(orc, name):
     held, mid, far = rb.bands(rays, rb.scene_measure(b["tris"]), cls)
     copl = np.isin(cls, rb.OUTSIDE)
     assert held.sum() > 0.8 * held.size
+    referee = exact_hit.OnDemand(b["tris"], rays)  # for the counted mismatches: they may differ, but only between two admissible hits
     for leaf in (1, 4, 7):
         S = b["S"] if leaf == 4 else rb.oracle_scene(orc, b["tris"], leaf_size=leaf)
         ctx = _host_ctx(b["tris"], leaf, 1)
@@ -117,6 +120,10 @@ def test_closest_hit_definition(orc, name):
             for k, band in ((0, mid), (2, far), (4, copl)):
                 rec[k] += int((m & band).sum())
                 rec[k + 1] += int(band.sum())
+            for whose, ans in ((who, got), ("brute force", truth)):
+                wrong = referee.inadmissible(np.nonzero(m & ~held)[0], ans)
+                assert wrong.size == 0, "%s (leaf %d) and brute force differ outside the domain and %s's answer breaks R1 or R2 of tests/exact_hit.py on %d rays; first: class %d %r" % (
+                    who, leaf, whose, wrong.size, cls[wrong[0]], rays[wrong[0]].tolist())
             bad = np.nonzero(m & held)[0]
             assert bad.size == 0, "%s (leaf %d) differs from brute force on %d rays; first: class %d %r" % (who, leaf, bad.size, cls[bad[0]], rays[bad[0]].tolist())
         ctx.close()
