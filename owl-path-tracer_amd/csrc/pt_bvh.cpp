@@ -141,7 +141,7 @@ int build_threads()
 
 } // namespace
 
-// fn(begin, end) over [0, n) in one contiguous share per thread (pt_api.cpp: flattening and re-ordering of the per-triangle records)
+// fn(begin, end) over [0, n) in one contiguous share per thread (pt_scene.cpp: flattening and re-ordering of the per-triangle records)
 void pt_parallel_ranges(size_t n, const std::function<void(size_t, size_t)>& fn)
 {
     const int T = n >= 65536 ? build_threads() : 1;
@@ -963,7 +963,7 @@ void pt_bvh_build(const float* positions, int32_t n_tris, int leaf_size, int max
             PtTri& tr = out->tris[i];
             std::memcpy(tr.p0, positions + (size_t)id * 9, 36);
             tr.id = id;
-            tr.material = -1; // filled in by the caller that owns the shading records (pt_api.cpp)
+            tr.material = -1; // filled in by the caller that owns the shading records (pt_scene.cpp)
             tr.pad = 0;
         }
     });

@@ -88,8 +88,7 @@ int need_rccl(pt_ctx* c)
 
 struct pt_group {
     std::vector<pt_ctx*> ctx;
-    std::vector<void*> d_rgb, d_rgba8; // per device: W*H*3 floats / W*H uint32
-    size_t cap_px = 0;
+    size_t cap_px = 0;                 // pixels the per-device framebuffers (each context's d_out / d_out8) and the staging hold
     float* pinned_rgb = nullptr;       // staging for the root's D2H (pinned: the reference's framebuffer is pinned host memory, owl.hpp:108-111)
     uint32_t* pinned_rgba8 = nullptr;
     std::string err;
@@ -197,26 +196,16 @@ pt_group* pt_group_create(const int32_t* devices, int32_t n)
         }
     }
     for (int i = 0; i < n; ++i) (void)pt_set_pixel_shard(g->ctx[(size_t)i], i, n, 16);
-    g->d_rgb.assign((size_t)n, nullptr);
-    g->d_rgba8.assign((size_t)n, nullptr);
     return g;
 }
 
 void pt_group_destroy(pt_group* g)
 {
     if (!g) return;
-    for (size_t i = 0; i < g->ctx.size(); ++i) {
-        pt_ctx* c = g->ctx[i];
-        (void)hipSetDevice(c->device);
-        (void)hipStreamSynchronize(c->stream); // a failed pt_group_render may have left this rank's launches in flight on d_rgb
-        (void)pt_comm_destroy(c);
-        if (i < g->d_rgb.size() && g->d_rgb[i]) (void)hipFree(g->d_rgb[i]);
-        if (i < g->d_rgba8.size() && g->d_rgba8[i]) (void)hipFree(g->d_rgba8[i]);
-        pt_destroy(c);
-    }
+    for (pt_ctx* c : g->ctx) pt_destroy(c); // drains the device first (a failed pt_group_render may have left this rank's launches in flight on d_out), frees its framebuffers with it current
     pt_host_free(g->pinned_rgb);
     pt_host_free(g->pinned_rgba8);
-    delete g;
+    delete g; // frees the per-device framebuffers (DevBuf)
 }
 
 int32_t pt_group_size(const pt_group* g) { return g ? (int32_t)g->ctx.size() : 0; }
@@ -266,14 +255,12 @@ int pt_group_render(pt_group* g, const pt_camera* cam, int32_t W, int32_t H, int
     const size_t npx = (size_t)W * (size_t)H;
     const int n = (int)g->ctx.size();
     auto bad = [&](pt_ctx* c, int rc) { g->err = pt_last_error(c); return rc; };
+    auto make_current = [](pt_ctx* c) { return hipSetDevice(c->device) == hipSuccess ? PT_OK : pti::fail(c, PT_E_HIP, "hipSetDevice(%d) failed", c->device); };
     if (npx > g->cap_px) { // per-device framebuffers + pinned staging on the host
         for (int i = 0; i < n; ++i) {
             pt_ctx* c = g->ctx[(size_t)i];
-            if (hipSetDevice(c->device) != hipSuccess) return bad(c, pti::fail(c, PT_E_HIP, "hipSetDevice(%d) failed", c->device));
-            if (g->d_rgb[(size_t)i]) (void)hipFree(g->d_rgb[(size_t)i]);
-            if (g->d_rgba8[(size_t)i]) (void)hipFree(g->d_rgba8[(size_t)i]);
-            g->d_rgb[(size_t)i] = g->d_rgba8[(size_t)i] = nullptr;
-            if (hipMalloc(&g->d_rgb[(size_t)i], npx * 12) != hipSuccess || hipMalloc(&g->d_rgba8[(size_t)i], npx * 4) != hipSuccess)
+            if (int rc = make_current(c)) return bad(c, rc);
+            if (pti::ensure(c, c->d_out, npx * 12) || pti::ensure(c, c->d_out8, npx * 4))
                 return bad(c, pti::fail(c, PT_E_HIP, "framebuffer allocation on device %d failed", c->device));
         }
         pt_host_free(g->pinned_rgb);
@@ -297,7 +284,7 @@ int pt_group_render(pt_group* g, const pt_camera* cam, int32_t W, int32_t H, int
     // the reduced float frame ...
     for (int i = 0; i < n; ++i) {
         pt_ctx* c = g->ctx[(size_t)i];
-        int rc = pt_render_device(c, cam, W, H, max_samples, max_depth, g->d_rgb[(size_t)i], (out_rgba8 && n == 1) ? g->d_rgba8[(size_t)i] : nullptr, nullptr);
+        int rc = pt_render_device(c, cam, W, H, max_samples, max_depth, c->d_out.p, (out_rgba8 && n == 1) ? c->d_out8.p : nullptr, nullptr);
         if (rc) return fail_all(c, rc);
     }
     // ... then ONE reduce onto device 0 (grouped: one host thread drives all ranks of the communicator)
@@ -308,7 +295,7 @@ int pt_group_render(pt_group* g, const pt_camera* cam, int32_t W, int32_t H, int
         pt_ctx* bad_ctx = nullptr;
         for (int i = 0; i < n && r == ncclSuccess; ++i) {
             pt_ctx* c = g->ctx[(size_t)i];
-            r = g_rccl.Reduce(g->d_rgb[(size_t)i], g->d_rgb[(size_t)i], npx * 3, ncclFloat32, ncclSum, 0, (ncclComm_t)c->comm, c->stream);
+            r = g_rccl.Reduce(c->d_out.p, c->d_out.p, npx * 3, ncclFloat32, ncclSum, 0, (ncclComm_t)c->comm, c->stream);
             if (r != ncclSuccess) bad_ctx = c;
         }
         // the group is closed even after a failed call (an open group would swallow every later call of this thread); a reduce that
@@ -322,11 +309,11 @@ int pt_group_render(pt_group* g, const pt_camera* cam, int32_t W, int32_t H, int
         }
         if (re != ncclSuccess) return fail_all(c0, pti::fail(c0, PT_E_HIP, "ncclGroupEnd failed: %s", g_rccl.GetErrorString(re)));
     }
-    if (hipSetDevice(c0->device) != hipSuccess) return fail_all(c0, pti::fail(c0, PT_E_HIP, "hipSetDevice(%d) failed", c0->device));
-    if (out_rgba8 && n > 1 && pt_launch_pack_rgba8((const float*)g->d_rgb[0], (uint32_t*)g->d_rgba8[0], (long long)npx, c0->stream) != hipSuccess)
+    if (int rc = make_current(c0)) return fail_all(c0, rc);
+    if (out_rgba8 && n > 1 && pt_launch_pack_rgba8((const float*)c0->d_out.p, (uint32_t*)c0->d_out8.p, (long long)npx, c0->stream) != hipSuccess)
         return fail_all(c0, pti::fail(c0, PT_E_HIP, "RGBA8 pack launch failed"));
-    if (hipMemcpyAsync(g->pinned_rgb, g->d_rgb[0], npx * 12, hipMemcpyDeviceToHost, c0->stream) != hipSuccess ||
-        (out_rgba8 && hipMemcpyAsync(g->pinned_rgba8, g->d_rgba8[0], npx * 4, hipMemcpyDeviceToHost, c0->stream) != hipSuccess))
+    if (hipMemcpyAsync(g->pinned_rgb, c0->d_out.p, npx * 12, hipMemcpyDeviceToHost, c0->stream) != hipSuccess ||
+        (out_rgba8 && hipMemcpyAsync(g->pinned_rgba8, c0->d_out8.p, npx * 4, hipMemcpyDeviceToHost, c0->stream) != hipSuccess))
         return fail_all(c0, pti::fail(c0, PT_E_HIP, "framebuffer read-back failed"));
     {
         int first_rc = PT_OK;

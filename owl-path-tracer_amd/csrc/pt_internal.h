@@ -1,5 +1,6 @@
-// pt_internal.h -- private to the library: the context behind the opaque pt_ctx of include/mi355pt.h, shared by pt_api.cpp
-// (scene, render) and pt_comm.cpp (RCCL reduce, multi-GPU group).
+// pt_internal.h -- private to the library: the context behind the opaque pt_ctx of include/mi355pt.h and the helpers its host sources
+// share: pt_api.cpp (context, options, stats), pt_scene.cpp (scene upload and clone), pt_render.cpp (frames and batches), pt_debug.cpp
+// (probes and readers) and pt_comm.cpp (RCCL reduce, multi-GPU group).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -10,9 +11,15 @@
 #include "pt_bvh.h"
 #include "pt_types.h"
 
+// A device allocation and its owner: freed with the object that holds it (a context, a group, a local of one call).  A buffer that was
+// never allocated frees nothing, so a host-only context (device < 0) never calls into HIP.  Movable, not copyable (the move constructor
+// leaves no implicit copy).
 struct DevBuf {
     void* p = nullptr;
     size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    ~DevBuf() { if (p) (void)hipFree(p); }
 };
 
 struct HostTexture {
@@ -20,18 +27,9 @@ struct HostTexture {
     std::vector<uint32_t> px;
 };
 
-struct pt_ctx {
-    int device = -1;
-    bool host_only = false;
-    int num_cus = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr, evm = nullptr, evr = nullptr, evd = nullptr; // evm: after the cost pre-pass and the queue sort; evr / evd: after the reduce / the read-back of pt_render
-    bool ev_pending = false;
-    bool flag_pending = false, watchdog_fired = false; // the watchdog flag of the last render has not been looked at yet / was set
-    hipStream_t last_stream = nullptr;                  // stream of the last pt_render_device (may be the caller's)
-    std::string err;
-
-    // host copies
+// The host copies of an uploaded scene: everything a replica of a multi-GPU group takes over from device 0 (pti::clone_scene is one
+// assignment of this), and the four figures of pt_stats that describe it.
+struct HostScene {
     PtBvh bvh;
     std::vector<PtNode4> nodes4; // two-level collapse of bvh.nodes for the wavefront kernel (pt_bvh_collapse4)
     int32_t root4 = -1;
@@ -46,41 +44,83 @@ struct pt_ctx {
     std::vector<HostTexture> textures;
     pt_env env{};
     HostTexture env_map;
+    uint64_t bvh_nodes = 0, bvh_depth = 0, n_triangles = 0; // pt_stats
+    double bvh_build_ms = 0.0;
+};
+
+// pt_set_option: every option with its default.
+struct PtOptions {
+    int spp_per_launch = 0, count = 0, blocks_per_cu = 0, leaf_size = 4, max_bvh_depth = 48, kernel = 2, slots_per_wave = 0, chunk_spp = 64, chunk_tail_min = -1, schedule = 1, prepass_spp = 0, census_mode = 0, sticky_pct = -1, latency = 0, cost_radius = 2, timeline = 0, node_pairs = 0, leaf_align = 1, bvh_builder = 3, quad = 1, groups = 1, wide_leaves = 1, fallback = 0, ploc_radius = 16, express_permille = -1, ns_express = 8, whole = -1, box_exact = -1, batch_frames = 0;
+    int tune[8] = {};
+};
+
+// What the pixel queue in d_pixels was made for (ensure_queue).
+struct QueueKey {
+    int w = 0, h = 0, frames = 1, rank = 0, world = 1, tile = 16;
+    bool operator==(const QueueKey& o) const { return w == o.w && h == o.h && frames == o.frames && rank == o.rank && world == o.world && tile == o.tile; }
+};
+
+// What a finished frame - or launch sequence of a batch - leaves behind for pt_synchronize, pt_get_stats, the watchdog check and the
+// diagnostics readers.  Written by finish_frame (pt_render.cpp) alone; the readers only take the two pending marks down.
+struct LastFrame {
+    bool ev_pending = false;    // ev0 .. ev1 have not been turned into pt_stats.kernel_ms yet
+    bool flag_pending = false, watchdog_fired = false; // the watchdog flag of the last render has not been looked at yet / was set
+    hipStream_t stream = nullptr; // stream of the last pt_render_device (may be the caller's)
+    int launches = 0;           // render-kernel launches, of all launch sequences of a batch (pt_stats.launches)
+    bool sorted = false;
+    int w = 0, h = 0;
+    int chunks = 0;             // of the last frame that ran a kernel, with the offset of its timelines in d_laps
+    size_t lap_ticks_ofs = 0;
+    int seqs = 1;               // launch sequences of the last render (pt_render_batch may need several)
+};
+
+struct pt_ctx {
+    int device = -1;
+    bool host_only = false;
+    int num_cus = 0;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr, evm = nullptr, evr = nullptr, evd = nullptr; // evm: after the cost pre-pass and the queue sort; evr / evd: after the reduce / the read-back of pt_render
+    std::string err;
+
+    HostScene scene;
     bool have_scene = false;
 
     // device
     DevBuf d_nodes8, d_nodes4, d_nodes, d_tris, d_shade, d_materials, d_texdesc, d_env, d_pixels, d_heads, d_rng, d_accum, d_out, d_out8, d_counters, d_dbg_in, d_dbg_out, d_slots, d_laps, d_ring, d_params, d_cost, d_sorted, d_sort_scratch, d_dbg_start, d_bucket, d_tiers, d_batch_mats, d_batch_cams, d_seq_flags; // d_batch_*: per-frame tables of pt_render_batch; d_seq_flags: watchdog flags of its earlier launch sequences
-    std::vector<void*> d_textures;
+    std::vector<DevBuf> d_textures;
 
     // pixel queue
-    int q_w = 0, q_h = 0, q_frames = 1, q_rank = 0, q_world = 1, q_tile = 16;
+    QueueKey queue;
+    bool queue_valid = false;
     int rank = 0, world = 1, tile = 16;
     uint32_t n_pixels = 0;
-    bool queue_valid = false;
 
-    // options
-    int spp_per_launch = 0, count = 0, blocks_per_cu = 0, leaf_size = 4, max_bvh_depth = 48, kernel = 2, slots_per_wave = 0, chunk_spp = 64, chunk_tail_min = -1, schedule = 1, prepass_spp = 0, census_mode = 0, sticky_pct = -1, latency = 0, cost_radius = 2, timeline = 0, node_pairs = 0, leaf_align = 1, bvh_builder = 3, quad = 1, groups = 1, wide_leaves = 1, fallback = 0, ploc_radius = 16, express_permille = -1, ns_express = 8, whole = -1, box_exact = -1, batch_frames = 0;
-    int tune[8] = {};
+    PtOptions opt;
 
     void* comm = nullptr;   // ncclComm_t once pt_comm_init_rank / pt_group_create attached one (pt_comm.cpp)
     int comm_rank = 0, comm_world = 1;
 
-    pt_stats stats{};
-    int last_launches = 0;
-    bool last_sorted = false;
-    int last_w = 0, last_h = 0;
-    size_t lap_ticks_ofs = 0;
-    int last_chunks = 0;
-    int last_seqs = 1;                 // launch sequences of the last render (pt_render_batch may need several)
+    pt_stats stats{}; // (its scene figures are kept in `scene`: pt_get_stats)
+    LastFrame last;
     std::vector<float> batch_cams_h, batch_mats_h; // pt_render_batch: staging of the per-frame tables
 };
 
+// Helpers that more than one host source uses.  The library is built with default visibility, so the five that existed before the host
+// layer was split stay among its exported names as they were; the ones the split added are PT_LOCAL and add nothing to that list.
+#define PT_LOCAL __attribute__((visibility("hidden")))
 namespace pti {
+// pt_api.cpp
 int fail(pt_ctx* c, int code, const char* fmt, ...);
 int ensure(pt_ctx* c, DevBuf& b, size_t bytes);
-int check_watchdog(pt_ctx* c);
+PT_LOCAL int upload(pt_ctx* c, DevBuf& b, const void* src, size_t bytes);
+PT_LOCAL int need_device(pt_ctx* c);
+// pt_scene.cpp
 int upload_scene_to_device(pt_ctx* c);
 int clone_scene(pt_ctx* dst, const pt_ctx* src);
+PT_LOCAL void material_row(const pt_ctx* c, float* dst, const float* src, int i);
+// pt_render.cpp
+int check_watchdog(pt_ctx* c);
+PT_LOCAL void fill_params(pt_ctx* c, PtKernelParams& P);
 } // namespace pti
 
 #define HIP_TRY(c, call)                                                                                   \

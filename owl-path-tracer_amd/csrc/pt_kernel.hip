@@ -19,7 +19,7 @@
 //    Lanes are workers, not pixel owners: a ray's lane is unrelated to the lane that shades its hit.  The per-pixel
 //    sample order -- hence the reference's per-pixel RNG stream (device.cu:226-243) -- is preserved because a slot
 //    has at most one ray in flight.  Work items are (pixel, sample chunk) tickets; the host orders the pixel queue by a
-//    cost pre-pass (pt_api.cpp, "schedule").
+//    cost pre-pass (pt_render.cpp, "schedule").
 //
 //  (The simple persistent lane-per-pixel form, option kernel=1, and the validation kernel live in pt_kernel_aux.hip; the queue sort,
 //  the tier plan and the small helper kernels in pt_schedule.hip; the device code all of them share in pt_trace.h.)
@@ -90,7 +90,7 @@ namespace {
 // one memory round trip per TWO levels of the binary tree.  Slab test as in node_step, two packed pairs; the lane continues with
 // the nearest hit child and pushes the other hit children (in slot order; any visiting order gives the same closest hit).
 // The lane reads its own record with 7 x global_load_dwordx4 = 7 vL1D accesses per lane and step, at 32-bit offsets from the wave-uniform
-// base (the host keeps the quad nodes below 4 GiB: pt_api.cpp).  (Two validated experiments that did not pay - whole-line cooperative
+// base (the host keeps the quad nodes below 4 GiB: pt_render.cpp).  (Two validated experiments that did not pay - whole-line cooperative
 // fetches through an LDS staging area, 64-byte records with 8-bit planes - live in variants/.)
 template <int STRIDE, int LDS_ENTRIES, bool CENSUS = false>
 __device__ __forceinline__ void node4_step(const PtNode4* __restrict__ nodes4, uint32_t* stack, uint32_t PT_AS1* ovf, v3 o, v3 inv, float tbest, int& cur, int& sp,
@@ -114,7 +114,7 @@ __device__ __forceinline__ void node4_step(const PtNode4* __restrict__ nodes4, u
     // (24 of the step's ~150 VALU operations; C4 492 -> 484-486 ms, C3 149 -> 146).  Against (plane - o) * (1/d) the distance is off by
     // |o/d| 2^-24, i.e. the plane seems displaced by |o| 2^-24 in space: rays start on surfaces or at the camera, the boxes are padded by
     // 1e-5 x the scene extent, and the host launches the instances with the subtracting form (`exact`) for a camera farther than 42
-    // extents from the origin (pt_api.cpp) - the test stays conservative with respect to every hit the triangle test can report, and
+    // extents from the origin (pt_render.cpp) - the test stays conservative with respect to every hit the triangle test can report, and
     // the triangle test decides the image.  The reciprocals are finite (ray_inv clamps them: a direction component of exactly 0 would
     // otherwise give -inf or NaN here depending on the signs of plane and origin, and cull boxes the ray runs through).
     // (Both forms behind a run-time switch in ONE instance cost 4 %: C4 486 -> 508 ms, profiles/r04_notes.md.)
@@ -217,7 +217,7 @@ __device__ __forceinline__ void node4_step(const PtNode4* __restrict__ nodes4, u
 // An agent-scope acquire per poll would also be correct but is 2-3x slower per hop and, with hundreds of pollers, costs the
 // whole chip bandwidth (same section, "Invalid forms"); a release would write back the XCD's L2.  Counters that are updated with
 // device-scope atomics (ticket heads, ring fills, the diagnostics accumulators) sit on cache lines that nothing stores to
-// plainly (pt_api.cpp lays them out in 256-byte blocks; PT_LAP_DIAG_OFS) - a plain store into such a line made publications
+// plainly (pt_render.cpp lays them out in 256-byte blocks; PT_LAP_DIAG_OFS) - a plain store into such a line made publications
 // disappear in round 1.  No spinning: a slot whose cell is not published yet keeps its ticket and polls again in a later pass.
 __device__ __forceinline__ uint32_t ld_agent(const uint32_t* p) { return __hip_atomic_load(gp(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void st_agent(uint32_t* p, uint32_t v) { __hip_atomic_store(gp(p), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -682,7 +682,7 @@ __device__ __forceinline__ void shade_pass(const PtKernelParams& P, WaveCtx& w, 
 // The closest hit does not depend on the visiting order (tri_eval's tie-break on the triangle id, conservative boxes), so the
 // image is bit-identical to the per-lane walk's - the parity suite runs with the group walk forced on as well (option groups = 2).
 // A group's stack is eight adjacent columns of the per-lane LDS stack area: entry e at stack[(e >> 3) * 64 + 8 * group + (e & 7)]
-// (capacity 8 * levels; the host enables the group walk only if 7 * depth8 + 1 entries fit, pt_api.cpp).
+// (capacity 8 * levels; the host enables the group walk only if 7 * depth8 + 1 entries fit, pt_render.cpp).
 #ifndef PT_GROUP_ORDERED
 #define PT_GROUP_ORDERED 1 // the hit children that are not entered go on the group's stack farthest first (0: in lane order)
 #endif
@@ -945,7 +945,7 @@ __global__ void __launch_bounds__(PT_WAVE, WAVES) PT_RENDER_KERNEL(const PtKerne
     w.missq = w.hitq + ns;
     const PtNode* __restrict__ nodes = P.nodes;
     const PtNode4* __restrict__ nodes4 = P.nodes4;
-    const bool quad = !COUNT || nodes4 != nullptr; // the product instances walk quad nodes only (pt_api.cpp launches the instrumented one otherwise): a compile-time fact there
+    const bool quad = !COUNT || nodes4 != nullptr; // the product instances walk quad nodes only (pt_render.cpp launches the instrumented one otherwise): a compile-time fact there
     const bool box_exact = EXACT || (COUNT && P.box_exact != 0); // node4_step / group walk: the subtracting slab form (camera far outside the scene)
     const PtTri* __restrict__ tris = P.tris;
 
@@ -1239,7 +1239,7 @@ __global__ void __launch_bounds__(PT_WAVE, WAVES) PT_RENDER_KERNEL(const PtKerne
     flush_counters<COUNT>(P, cn);
 }
 
-// ---- launchers (called from pt_api.cpp) --------------------------------------------------------------------
+// ---- launchers (called from pt_render.cpp) --------------------------------------------------------------------
 
 // d_params: device copy of *p (wavefront kernel reads its parameters from HBM; the caller keeps it stream-ordered)
 // (the batch build defines the same two functions for its own instances: pt_launch_render_batch / pt_batch_kernel_geometry, variants 2 and 3 only)

@@ -1,5 +1,5 @@
 // Tier plan of the whole-pixel schedule (pt_kernel.hip, TIERS): host + device code, so that the CPU tests can exercise exactly what the
-// one-thread kernel pt_plan_tiers_kernel runs after the counting sort (pt_debug_plan_tiers in pt_api.cpp).
+// one-thread kernel pt_plan_tiers_kernel runs after the counting sort (pt_debug_plan_tiers in pt_debug.cpp).
 #pragma once
 #include <cmath>
 #include <cstdint>

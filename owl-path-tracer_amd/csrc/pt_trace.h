@@ -165,7 +165,7 @@ __device__ __forceinline__ void tri_eval2(const f32x4 a0, const f32x4 b0, const 
     if (take1) tri_take(t.y, u.y, v.y, uv.y, __float_as_int(c1.y), slot0 + 1, h);
 }
 // All triangles of one leaf: the records of the first PT_LEAF_PREFETCH triangles are requested together, the tests follow.
-// The wavefront kernel's leaf step; tris is below 4 GiB there (pt_api.cpp, plan_frame): 32-bit offsets from the wave-uniform base.
+// The wavefront kernel's leaf step; tris is below 4 GiB there (pt_render.cpp, plan_frame): 32-bit offsets from the wave-uniform base.
 #ifndef PT_LEAF_PREFETCH
 #define PT_LEAF_PREFETCH 4
 #endif

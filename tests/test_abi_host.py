@@ -61,6 +61,42 @@ def test_upload_validation(cube):
         B.Context(-1).set_materials(mats)
 
 
+def test_clone_gives_a_host_only_context_the_same_scene(cornell):
+    """pti::clone_scene (the replicas of a multi-GPU group) without a GPU: everything the host-side hooks show of the scene is equal after
+    the clone - the five arrays of pt_debug_export_tree, the quad and oct figures, the scene figures of pt_stats and the closest hits of
+    seeded rays - and both contexts still take a material table of the scene's size (and refuse another)."""
+    mats = [m for _, m, _ in cornell["materials"]]
+    src, dst = B.Context(-1), B.Context(-1)
+    with pytest.raises(B.PtError, match="source context has no scene"):
+        dst.clone_scene_from(src)
+    src.set_option("leaf_size", 2)  # not the default: the clone takes the tree over, it does not rebuild it with its own options
+    src.upload_scene(cornell["entities"], mats)
+    dst.clone_scene_from(src)
+    a, b = src.export_trees(), dst.export_trees()
+    assert a.keys() == b.keys() and len(a["nodes"]) > 1000 and len(a["nodes4"]) > 0 and len(a["nodes8"]) > 0
+    for k in a:
+        if isinstance(a[k], np.ndarray):
+            assert a[k].dtype == b[k].dtype and a[k].tobytes() == b[k].tobytes(), k
+        else:
+            assert np.array(a[k]).tobytes() == np.array(b[k]).tobytes(), k
+    assert src.quad_info() == dst.quad_info() and src.oct_info() == dst.oct_info()
+    sa, sb = src.stats(), dst.stats()
+    for k in ("n_triangles", "bvh_nodes", "bvh_depth", "bvh_build_ms"):
+        assert sa[k] == sb[k], k
+    assert sa["n_triangles"] == 17974 and sa["bvh_nodes"] > 0 and sa["bvh_depth"] > 0
+    rng = np.random.default_rng(2024)
+    rays = np.concatenate([rng.uniform(-1.5, 1.5, (400, 3)) + [0, 1, 0], rng.normal(size=(400, 3))], axis=1).astype(np.float32)
+    ha, hb = src.closest_hit_host_n(rays), dst.closest_hit_host_n(rays)
+    assert ha[0].sum() > 100
+    for x, y in zip(ha, hb):
+        assert x.tobytes() == y.tobytes()
+    for ctx in (src, dst):
+        ctx.set_materials(mats)
+        with pytest.raises(B.PtError, match="material count changed"):
+            ctx.set_materials(mats + mats[:1])
+        ctx.close()
+
+
 def test_camera_matches_oracle_bitwise(orc):
     for args in (([3, 1, 0], [0, 1, 0], [0, 1, 0], 50, 512, 512), ([4, 2.5, 0], [0, .75, 0], [0, 1, 0], 50, 1920, 1080),
                  ([2, 1, 2], [0, 0, 0], [0, 1, 0], 50, 256, 256), ([0, 2, 5], [0, .5, 0], [0, 1, 0], 45, 1080, 1440)):

@@ -16,7 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "owl-path-tracer_amd", "csrc")
 NEW = ("pt_render_batch", "pt_render_batch_device", "pt_debug_plan_batch")
 
-# The limits of one launch sequence, from the code that sets them (csrc/pt_api.cpp, batch_max_frames): a path slot packs its pixel as
+# The limits of one launch sequence, from the code that sets them (csrc/pt_render.cpp, batch_max_frames): a path slot packs its pixel as
 # x | y << 16 and pt_render_device accepts heights up to 65535, so the virtual image has at most 65535 rows; plan_chunks refuses
 # n_pixels >= 2^24.
 MAX_ROWS = 65535

@@ -597,7 +597,7 @@ def test_empty_rank_and_world8_sum(gpu, cornell):
 
 def test_slab_test_forms_and_far_camera(gpu, orc, cornell):
     """The quad step computes slab distances as fma(plane, 1/d, -(o/d)) (round 4) and the host switches to (plane - o) * (1/d) for a camera
-    far outside the scene (pt_api.cpp, box_exact): both forms must give the oracle's image - boxes are conservative either way - and so
+    far outside the scene (pt_render.cpp, box_exact): both forms must give the oracle's image - boxes are conservative either way - and so
     must a camera 3 000 units away (300 scene extents), where the fma form's error would exceed the boxes' padding."""
     _upload(gpu, cornell, env=B.make_env(color=(1, 1, 1), intensity=0.0))
     S = orc.Scene(cornell["flat"])

@@ -209,7 +209,7 @@ def test_closest_hit_does_not_depend_on_the_hierarchy(orc, scene_io):
     """The closest hit is DEFINED as the minimum over all triangles of the Moeller-Trumbore t (ties: lower id), so that every hierarchy -
     the oracle's, the product's three builders, quad and oct nodes - must find the same one.  That only holds if no triangle reports hits
     outside its (padded) bounding box: slivers, whose test results are rounding noise, are collapsed at scene build (pt_oracle.c
-    orc_scene_create, csrc/pt_api.cpp pt_collapse_sliver).  Property test on the oracle alone: BVH walk == brute force over random
+    orc_scene_create, csrc/pt_scene.cpp pt_collapse_sliver).  Property test on the oracle alone: BVH walk == brute force over random
     scenes with needles, coincident and degenerate triangles (the generator of tests/test_gpu_fuzz.py)."""
     import test_gpu_fuzz as F
 
