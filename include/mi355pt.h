@@ -105,7 +105,8 @@ typedef struct pt_stats {
      * item took that branch, [14] passes that ran two or more BSDF bodies, [15] passes whose items all took the same branch */
     uint64_t lobes[16];
     /* counted renders, traversal (lane-steps): [0] quad-node steps that enter no child, [1] of those: the node lies beyond the best hit
-     * found so far, [2] unused, [3] leaf steps that do not improve the hit */
+     * found so far, [2] option "watertight" = 1: (ray, triangle) pairs whose edge functions were recomputed from float64 products (else 0),
+     * [3] leaf steps that do not improve the hit */
     uint64_t trav[4];
 } pt_stats;
 
@@ -222,7 +223,7 @@ int pt_group_set_option(pt_group* g, const char* key, int64_t value);
 int pt_group_render(pt_group* g, const pt_camera* cam, int32_t width, int32_t height, int32_t max_samples, int32_t max_path_depth,
                     float* out_rgb, uint32_t* out_rgba8);
 
-/* Tuning / test options (all have working defaults; none changes an image):
+/* Tuning / test options (all have working defaults; none changes an image, except "watertight"):
  *   "kernel" 2 (default, wavefront-scheduled) | 1 (lane per pixel);  "count" 0/1: instrumented kernel that fills pt_stats;
  *   "leaf_size", "max_bvh_depth": BVH builder, next pt_upload_scene;  "bvh_builder" 3 (default: by triangle count - 0 up to 64 M
  *   triangles, 2 beyond) | 0 (binned SAH on all host threads: the tree that walks fastest, 0.9 M triangles in 58-83 ms) | 1 (linear BVH built on
@@ -243,7 +244,17 @@ int pt_group_render(pt_group* g, const pt_camera* cam, int32_t width, int32_t he
  *   "quad" 1 (default: two binary levels per 128-byte record) | 0;  "box_exact" -1 (default: slab distances by one fma per plane, the
  *   subtracting form when the camera is more than 42 scene extents from the origin) | 0 | 1;  "fallback" 1: use the wavefront kernel's 168-VGPR instance (what
  *   the library does by itself when the 128-VGPR instance of a build needs scratch);
- *   "batch_frames" 0 (default: as many as the limits allow) | n: most frames per launch sequence of pt_render_batch. */
+ *   "batch_frames" 0 (default: as many as the limits allow) | n: most frames per launch sequence of pt_render_batch;
+ *   "watertight" 0 (default: Moeller-Trumbore, bit for bit the images of every earlier version) | 1: every triangle test of the wavefront
+ *   render path (pt_render, pt_render_device, the communicator path, pt_group_render), of the ray probes 30..35 and of
+ *   pt_debug_closest_hit_host / _n is the watertight test of Woop, Benthin and Wald in the float32 sequence of DESIGN.md 2.1: no ray
+ *   passes between two triangles that share an edge or a vertex (OptiX, which the reference traces with, lets none through either).
+ *   THE ONE OPTION THAT CHANGES AN IMAGE: t, u, v of a hit come from another operation sequence, and rays that Moeller-Trumbore lets
+ *   through a seam (10-16 % of the rays aimed at shared edges or vertices, ~1e-6 of random ones) now hit.  Everything else of the
+ *   closest-hit definition stays: two-sided, t > 1e-3, minimum t, ties to the lower triangle id, slivers collapsed at upload (so a
+ *   needle inside a closed mesh still opens a gap of under 1e-5 of its edge).  Switchable between renders of one context, no new
+ *   pt_upload_scene.  With "watertight" = 1 these are refused with PT_E_INVALID and a message, never rendered with the other test:
+ *   option "kernel" = 1 (either order of the two pt_set_option calls), pt_debug_eval's closest-hit op 21, pt_render_batch(_device). */
 int pt_set_option(pt_ctx* ctx, const char* key, int64_t value);
 int pt_get_stats(pt_ctx* ctx, pt_stats* out);
 
@@ -253,7 +264,8 @@ void pt_to_camera_data(const float look_from[3], const float look_at[3], const f
                        int32_t width, int32_t height, pt_camera* out);
 
 /* ---- validation hooks (used by tests/ only; never on the render path) ----
- * Closest hit = minimum over all triangles of the Moeller-Trumbore t (ties: lower global triangle id), slivers never hit.  Every walk
+ * Closest hit = minimum over all triangles of the Moeller-Trumbore t (option "watertight" = 1: of the watertight test's t, for the host
+ * walk and the ray probes 30..35; op 21 is refused then) (ties: lower global triangle id), slivers never hit.  Every walk
  * (lane per pixel, quad, group, host) computes exactly that, whatever the hierarchy, for ray origins whose largest |coordinate| is
  * within 10 x max(scene extent, largest |coordinate| of the scene) and rays that do not lie in a non-axis-aligned triangle's plane up
  * to rounding, nor graze one at its edge at less than 1e-2 rad.  Farther out the triangle test places hits outside the padded boxes (1 of 300 000 rays from 41 extents, 7e-4 of the

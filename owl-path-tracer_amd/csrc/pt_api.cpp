@@ -142,12 +142,18 @@ int pt_set_option(pt_ctx* c, const char* key, int64_t value)
     else if (k == "ploc_radius") c->opt.ploc_radius = (int)(value < 1 ? 1 : (value > 64 ? 64 : value)); // bvh_builder 2: neighbours searched on either side
     else if (k == "box_exact") c->opt.box_exact = (int)(value < 0 ? -1 : (value > 0 ? 1 : 0)); // slab test form: -1 automatic (fma unless the camera is far outside the scene), 0 fma, 1 subtracting
     else if (k == "batch_frames") c->opt.batch_frames = (int)(value < 0 ? 0 : (value > 0x7fffffff ? 0x7fffffff : value)); // pt_render_batch: most frames per launch sequence (0: what the limits allow)
+    else if (k == "watertight") { // the triangle test of every walk of the wavefront render path, the ray probes and the host walk: 0 Moeller-Trumbore, 1 watertight
+        if (value != 0 && value != 1) return fail(c, PT_E_INVALID, "watertight must be 0 (Moeller-Trumbore, default) or 1 (watertight edge functions)");
+        if (value == 1 && c->opt.kernel != 2) return fail(c, PT_E_INVALID, "watertight = 1: the lane-per-pixel kernel (option kernel = 1) has no watertight form; set kernel = 2 first");
+        c->opt.watertight = (int)value;
+    }
     else if (k == "quad") c->opt.quad = value != 0; // wavefront kernel: quad nodes (two binary levels per fetch), next pt_render
     else if (k == "node_pairs") c->opt.node_pairs = value != 0;
     else if (k == "leaf_align") c->opt.leaf_align = (int)(value < 1 ? 1 : (value > 8 ? 8 : value));
     else if (k.size() == 5 && k.compare(0, 4, "tune") == 0 && k[4] >= '0' && k[4] <= '7') c->opt.tune[k[4] - '0'] = (int)value;
     else if (k == "kernel") {
         if (value != 1 && value != 2) return fail(c, PT_E_INVALID, "kernel must be 1 (lane-per-pixel) or 2 (wavefront-scheduled)");
+        if (value == 1 && c->opt.watertight) return fail(c, PT_E_INVALID, "kernel = 1: the lane-per-pixel kernel has no watertight form (option watertight = 1); set watertight = 0 first");
         c->opt.kernel = (int)value;
     }
     else return fail(c, PT_E_INVALID, "unknown option '%s'", key);

@@ -1062,10 +1062,54 @@ inline bool hbox(const float* mn, const float* mx, hv3 o, hv3 inv, float tmin, f
 }
 } // namespace
 
+// The watertight triangle test (Woop, Benthin, Wald) in the float32 sequence DESIGN.md 2.1 fixes, written out as the definition has it -
+// axes as indices - where the device code (pt_trace.h, "WATERTIGHT BUILD") selects: the two must agree bit for bit.  Nothing may fuse: this file is compiled with -ffp-contract=off like the rest of the library.
+namespace {
+struct HostWtRay { int kx, ky, kz; float sx, sy, sz; };
+inline HostWtRay host_wt_ray(const float d[3])
+{
+    HostWtRay r;
+    const float ax = std::fabs(d[0]), ay = std::fabs(d[1]), az = std::fabs(d[2]);
+    r.kz = (ax >= ay && ax >= az) ? 0 : (ay >= az ? 1 : 2); // the largest |d|, the first on a tie
+    r.kx = (r.kz + 1) % 3;
+    r.ky = (r.kx + 1) % 3;
+    if (d[r.kz] < 0.0f) std::swap(r.kx, r.ky);
+    r.sx = d[r.kx] / d[r.kz];
+    r.sy = d[r.ky] / d[r.kz];
+    r.sz = 1.0f / d[r.kz];
+    return r;
+}
+inline float host_wt_edge64(float a, float b, float c, float d) { return (float)((double)a * (double)b - (double)c * (double)d); }
+// false: rejected before t is looked at
+inline bool host_wt_tri(const PtTri& tr, const float o[3], const HostWtRay& r, float* t, float* u, float* v)
+{
+    const float A[3] = {tr.p0[0] - o[0], tr.p0[1] - o[1], tr.p0[2] - o[2]};
+    const float B[3] = {tr.p1[0] - o[0], tr.p1[1] - o[1], tr.p1[2] - o[2]};
+    const float C[3] = {tr.p2[0] - o[0], tr.p2[1] - o[1], tr.p2[2] - o[2]};
+    const float Ax = A[r.kx] - r.sx * A[r.kz], Ay = A[r.ky] - r.sy * A[r.kz];
+    const float Bx = B[r.kx] - r.sx * B[r.kz], By = B[r.ky] - r.sy * B[r.kz];
+    const float Cx = C[r.kx] - r.sx * C[r.kz], Cy = C[r.ky] - r.sy * C[r.kz];
+    float U = Cx * By - Cy * Bx, V = Ax * Cy - Ay * Cx, W = Bx * Ay - By * Ax;
+    if (U == 0.0f || V == 0.0f || W == 0.0f) { // exact products, one rounding of the difference to float64, one to float32
+        U = host_wt_edge64(Cx, By, Cy, Bx);
+        V = host_wt_edge64(Ax, Cy, Ay, Cx);
+        W = host_wt_edge64(Bx, Ay, By, Ax);
+    }
+    if ((U < 0.0f || V < 0.0f || W < 0.0f) && (U > 0.0f || V > 0.0f || W > 0.0f)) return false;
+    const float det = (U + V) + W;
+    if (det == 0.0f) return false;
+    const float T = (U * (r.sz * A[r.kz]) + V * (r.sz * B[r.kz])) + W * (r.sz * C[r.kz]);
+    const float inv = 1.0f / det;
+    *t = T * inv; *u = V * inv; *v = W * inv;
+    return true;
+}
+} // namespace
+
 bool pt_bvh_closest_hit_host(const PtBvh& bvh, const float org[3], const float dir[3], float tmin, float tmax, float* t_out, float* u_out,
-                             float* v_out, int32_t* prim)
+                             float* v_out, int32_t* prim, bool watertight)
 {
     hv3 o{org[0], org[1], org[2]}, d{dir[0], dir[1], dir[2]};
+    const HostWtRay wr = watertight ? host_wt_ray(dir) : HostWtRay{};
     hv3 inv{1.0f / d.x, 1.0f / d.y, 1.0f / d.z};
     float bt = tmax, bu = 0.0f, bv = 0.0f;
     int32_t bid = 0x7fffffff;
@@ -1092,6 +1136,13 @@ bool pt_bvh_closest_hit_host(const PtBvh& bvh, const float org[3], const float d
             int first = (int)(code >> 3), count = (int)(code & 7u);
             for (int i = 0; i < count; ++i) {
                 const PtTri& tr = bvh.tris[first + i];
+                if (watertight) {
+                    float t, u, v;
+                    if (host_wt_tri(tr, org, wr, &t, &u, &v) && t > tmin && (t < bt || (t == bt && tr.id < bid))) {
+                        bt = t; bu = u; bv = v; bid = tr.id;
+                    }
+                    continue;
+                }
                 hv3 p0{tr.p0[0], tr.p0[1], tr.p0[2]}, p1{tr.p1[0], tr.p1[1], tr.p1[2]}, p2{tr.p2[0], tr.p2[1], tr.p2[2]};
                 hv3 e1 = hsub(p1, p0), e2 = hsub(p2, p0);
                 hv3 pv = hcross(d, e2);

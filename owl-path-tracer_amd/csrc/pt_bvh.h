@@ -36,8 +36,9 @@ void pt_parallel_ranges(size_t n, const std::function<void(size_t, size_t)>& fn)
 void pt_bvh_quad_cost(const std::vector<PtNode4>& nodes4, int32_t root4, double* node_visits, double* leaf_visits);
 
 // Host mirror of the kernel's traversal over the product BVH (validation only, never on the render path).
+// watertight: the triangle test of option "watertight" = 1 (csrc/pt_trace.h, "WATERTIGHT BUILD") instead of Moeller-Trumbore
 bool pt_bvh_closest_hit_host(const PtBvh& bvh, const float org[3], const float dir[3], float tmin, float tmax, float* t, float* u,
-                             float* v, int32_t* prim);
+                             float* v, int32_t* prim, bool watertight = false);
 
 // Three-level collapse into oct nodes (PtNode8, pt_types.h): starting from the two children of a binary node, the internal slot with
 // the largest surface area is replaced by its two children until eight slots are used (or none is internal).  root8 = 0 when the

@@ -53,7 +53,8 @@ int probe_eval(pt_ctx* c, PtKernelParams& P, int op, int in_stride, float* out, 
     P.error_flag = flag;
     uint32_t fired = 0;
     hipError_t e = hipMemsetAsync(flag, 0, 4, c->stream);
-    if (e == hipSuccess) e = pt_launch_probe(&P, op, (const float*)c->d_dbg_in.p, in_stride, (float*)c->d_dbg_out.p, out_stride, (long long)n, grid, lds, (uint32_t*)d_scratch.p, c->stream);
+    // option "watertight": the same probe kernels around the watertight instances of leaf_test / traverse_groups (pt_kernel_wt.hip)
+    if (e == hipSuccess) e = (c->opt.watertight ? pt_launch_probe_wt : pt_launch_probe)(&P, op, (const float*)c->d_dbg_in.p, in_stride, (float*)c->d_dbg_out.p, out_stride, (long long)n, grid, lds, (uint32_t*)d_scratch.p, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(out, c->d_dbg_out.p, (size_t)n * out_stride * 4, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(&fired, flag, 4, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
@@ -156,6 +157,8 @@ int pt_debug_eval(pt_ctx* c, int32_t op, const float* in, int32_t in_stride, flo
     PtKernelParams P;
     fill_params(c, P);
     if (op >= PT_PROBE_FIRST) return probe_eval(c, P, op, in_stride, out, out_stride, n);
+    if (op == PT_DEBUG_OP_CLOSEST_HIT && c->opt.watertight)
+        return fail(c, PT_E_INVALID, "pt_debug_eval: the validation kernel's closest-hit op (21) has no watertight form (option watertight = 1); use the ray probes 30..35");
     if (!c->have_scene) { P.root = -1; P.stack_entries = 1; }
     size_t lds = (size_t)P.stack_entries * pt_debug_block() * 4;
     HIP_TRY(c, pt_launch_debug(&P, op, (const float*)c->d_dbg_in.p, in_stride, (float*)c->d_dbg_out.p, out_stride, (long long)n, lds, c->stream));

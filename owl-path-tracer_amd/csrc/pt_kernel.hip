@@ -39,7 +39,24 @@
 #ifndef PT_BATCH
 #define PT_BATCH 0
 #endif
+#ifndef PT_WATERTIGHT
+#define PT_WATERTIGHT 0
+#endif
+#if PT_WATERTIGHT
 #if PT_BATCH
+#error "the watertight build has no batch instances"
+#endif
+// every global name of this file gets a twin of its own in the watertight build (kernels are templates or strong symbols)
+#define PT_RENDER_KERNEL pt_render_wt_kernel
+#define pt_launch_render pt_launch_render_wt
+#define pt_kernel_geometry pt_wt_kernel_geometry
+#define pt_probe_quad_kernel pt_probe_quad_wt_kernel
+#define pt_probe_group_kernel pt_probe_group_wt_kernel
+#define pt_launch_probe pt_launch_probe_wt
+#define pt_probe_lds_stack pt_probe_lds_stack_wt
+#define pt_probe_group_lds_bytes pt_probe_group_lds_bytes_wt
+#define pt_probe_group_state_words pt_probe_group_state_words_wt
+#elif PT_BATCH
 #define PT_RENDER_KERNEL pt_render_batch_kernel
 #else
 #define PT_RENDER_KERNEL pt_render_wave_kernel
@@ -853,7 +870,14 @@ __device__ __forceinline__ int traverse_groups(const PtKernelParams& P, WaveCtx&
         if (m_leafg != 0ull) {
             // -- leaf groups: lane k tests triangle k; (t, id)-lexicographic minimum over the group, payload (u, v, slot)
             Hit hc = h;
+#if PT_WATERTIGHT
+            if (tri_on) {
+                const WtRay wr = wt_ray(d);
+                tri_eval_wt(ta, tb4, tc, first + sub, o, PT_WT_PASS(wr), hc, COUNT ? &cn.wt64 : nullptr);
+            }
+#else
             if (tri_on) tri_eval(ta, tb4, tc, first + sub, o, d, hc);
+#endif
             PT_HIT_STAGE(dpp_xor1)
             PT_HIT_STAGE(dpp_xor2)
             PT_HIT_STAGE(dpp_mir8)
@@ -1194,7 +1218,11 @@ __global__ void __launch_bounds__(PT_WAVE, WAVES) PT_RENDER_KERNEL(const PtKerne
                         const int firstt = (int)(code >> 3), count = (int)(code & 7u);
                         if (COUNT) cn.tris += (uint32_t)count;
                         const float t_before = h.t;
+#if PT_WATERTIGHT
+                        leaf_test(tris, firstt, count, o, d, h, COUNT ? &cn.wt64 : nullptr);
+#else
                         leaf_test(tris, firstt, count, o, d, h);
+#endif
                         if (COUNT) cn.leaf_noimp += h.t == t_before ? 1u : 0u;
                         if (cur < PT_DONE) { // the lane was blocked on a second leaf: it becomes the pending one
                             pend = cur;
@@ -1253,7 +1281,11 @@ extern "C" hipError_t pt_launch_render_batch(const PtKernelParams* p, const PtKe
 extern "C" hipError_t pt_launch_render(const PtKernelParams* p, const PtKernelParams* d_params, int variant, int grid, size_t lds_bytes,
                                        hipStream_t stream, int count)
 {
+#if PT_WATERTIGHT
+    if (variant != 2 && variant != 3) return hipErrorInvalidValue; // the lane-per-pixel kernel has no watertight form
+#else
     if (variant == 1) return pt_launch_render_lane(p, grid, lds_bytes, stream, count); // pt_kernel_aux.hip
+#endif
 #endif
     const bool exact = p->box_exact != 0;
     if (count) hipLaunchKernelGGL((PT_RENDER_KERNEL<true, PT_COUNT_WAVES_PER_EU, false>), dim3(grid), dim3(PT_WAVE), lds_bytes, stream, d_params);
@@ -1274,7 +1306,11 @@ extern "C" hipError_t pt_batch_kernel_geometry(int variant, int count, int stack
 #else
 extern "C" hipError_t pt_kernel_geometry(int variant, int count, int stack_entries, int group_entries, int want_ns, int exact, PtGeometry* g)
 {
+#if PT_WATERTIGHT
+    if (variant != 2 && variant != 3) return hipErrorInvalidValue;
+#else
     if (variant == 1) return pt_lane_kernel_geometry(count, stack_entries, g); // pt_kernel_aux.hip
+#endif
 #endif
     const void* fn = count ? (const void*)PT_RENDER_KERNEL<true, PT_COUNT_WAVES_PER_EU, false>
                      : variant == 3 ? (exact ? (const void*)PT_RENDER_KERNEL<false, PT_FALLBACK_WAVES, true> : (const void*)PT_RENDER_KERNEL<false, PT_FALLBACK_WAVES, false>)

@@ -115,6 +115,7 @@ enum {
     PT_OP_FRAME = 22,         // in: n[3], w[3] (6) -> out: t[3], b[3], local[3], world(local)[3] (12)
     PT_OP_RNG = 23            // in: seed_u bits, seed_v bits (2) -> out: state0 bits, f0, f1, f2, state3 bits (5)
 };
+static_assert(PT_OP_CLOSEST_HIT == PT_DEBUG_OP_CLOSEST_HIT, "pt_debug_eval refuses this op by number when option watertight is set (pt_debug.cpp)");
 
 __global__ void __launch_bounds__(PT_BLOCK) pt_debug_kernel(const PtKernelParams P, int op, const float* __restrict__ in, int in_stride,
                                                            float* __restrict__ out, int out_stride, long long n)

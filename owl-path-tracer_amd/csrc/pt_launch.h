@@ -23,6 +23,7 @@ struct PtGeometry {
 // in: o[3], d[3] per ray; out: PT_PROBE_OUT floats per ray (layout in include/mi355pt.h).
 enum { PT_PROBE_FIRST = 30, PT_PROBE_QUAD = 30, PT_PROBE_QUAD_OVF = 32, PT_PROBE_GROUP = 34, PT_PROBE_LAST = 35 };
 #define PT_PROBE_OUT 6
+#define PT_DEBUG_OP_CLOSEST_HIT 21 // the validation kernel's closest-hit op (PT_OP_CLOSEST_HIT, pt_kernel_aux.hip): Moeller-Trumbore only
 #define PT_PROBE_GROUP_SLOTS 24 // path slots of a wave of the group probe: three rays per group, so groups park and resume
 #define PT_PROBE_GROUP_RAYS 100 // rays per wave of the group probe: neither a multiple of 8 nor of 64
 
@@ -44,6 +45,11 @@ hipError_t pt_kernel_geometry(int variant, int count, int stack_entries, int gro
 // pt_kernel_batch.hip: the batch instances of the wavefront kernel (variants 2 and 3 and the instrumented instance; PtKernelParams::batch_*)
 hipError_t pt_launch_render_batch(const PtKernelParams* p, const PtKernelParams* d_params, int variant, int grid, size_t lds_bytes, hipStream_t stream, int count);
 hipError_t pt_batch_kernel_geometry(int variant, int count, int stack_entries, int group_entries, int want_ns, int exact, PtGeometry* g);
+// pt_kernel_wt.hip: the watertight instances of the wavefront kernel (variants 2 and 3 and the instrumented instance) and of the ray probes
+hipError_t pt_launch_render_wt(const PtKernelParams* p, const PtKernelParams* d_params, int variant, int grid, size_t lds_bytes, hipStream_t stream, int count);
+hipError_t pt_wt_kernel_geometry(int variant, int count, int stack_entries, int group_entries, int want_ns, int exact, PtGeometry* g);
+hipError_t pt_launch_probe_wt(const PtKernelParams* p, int op, const float* in, int in_stride, float* out, int out_stride, long long n, int grid, size_t lds_bytes,
+                              uint32_t* scratch, hipStream_t stream);
 int pt_debug_block(void);
 // pt_kernel_aux.hip: the lane-per-pixel variant (pt_launch_render / pt_kernel_geometry forward variant 1 to these)
 hipError_t pt_launch_render_lane(const PtKernelParams* p, int grid, size_t lds_bytes, hipStream_t stream, int count);

@@ -140,6 +140,7 @@ void walk_params(pt_ctx* c, const pt_camera* cam, PtKernelParams& P)
 struct FramePlan {
     int variant = 0, use_count = 0; // instance of the render kernel (pt_launch_render) and whether it is the instrumented one
     bool batch = false;             // the batch instances (pt_launch_render_batch): set by the caller before plan_frame
+    bool wt = false;                // the watertight instances (pt_launch_render_wt): option "watertight", set by plan_frame
     PtGeometry geo{};               // its launch geometry
     int bpc = 0, grid = 0;          // workgroups per CU, of the (main) launch
     int ring_grid = 0;              // with a tier plan: the workgroups of the ring schedule (the plan's fallback; the pre-pass launches these)
@@ -224,6 +225,11 @@ int plan_frame(pt_ctx* c, const PtKernelParams& P, int max_samples, FramePlan& f
     // instance with the larger register budget (3): slower (12 instead of 16 waves per CU), the same arithmetic
     // (the one-level walk over PtNode[] - option quad = 0, or a tree too deep for the quad walk's stack bound - is compiled into the
     // instrumented instance only: the product instance is kept small for the instruction cache)
+    // option "watertight": the same three instances from pt_kernel_wt.hip, chosen and refused by the same rules (a 128-VGPR watertight
+    // instance that needs scratch falls back to the 168-VGPR one, a fallback that needs it too is PT_E_LIMIT below)
+    f.wt = c->opt.watertight != 0;
+    if (f.wt && c->opt.kernel != 2) return fail(c, PT_E_INVALID, "watertight = 1: the lane-per-pixel kernel (option kernel = 1) has no watertight form");
+    if (f.wt && f.batch) return fail(c, PT_E_INVALID, "pt_render_batch: batches have no watertight instances (option watertight = 1); render the frames one by one or set watertight = 0");
     f.use_count = (c->opt.count || (c->opt.kernel == 2 && !P.nodes4)) ? 1 : 0;
     f.variant = c->opt.kernel == 2 && c->opt.fallback && !f.use_count ? 3 : c->opt.kernel;
     // the wavefront kernel's quad-node and leaf steps address their records with 32-bit byte offsets from the buffer base (node4_step, leaf_test)
@@ -236,6 +242,7 @@ int plan_frame(pt_ctx* c, const PtKernelParams& P, int max_samples, FramePlan& f
     const PtGeometry& g = f.geo;
     auto geometry = [&] {
         return f.batch ? pt_batch_kernel_geometry(f.variant, f.use_count, P.stack_entries, group_entries, want_ns, P.box_exact, &f.geo)
+               : f.wt  ? pt_wt_kernel_geometry(f.variant, f.use_count, P.stack_entries, group_entries, want_ns, P.box_exact, &f.geo)
                        : pt_kernel_geometry(f.variant, f.use_count, P.stack_entries, group_entries, want_ns, P.box_exact, &f.geo);
     };
     hipError_t ge = geometry();
@@ -475,6 +482,7 @@ int run_launches(pt_ctx* c, const FramePlan& f, PtKernelParams& P, int W, int H,
         // as dense as the ring schedule's - C2 74.3 -> 71 ms, 1/8 shard 198 -> 194)
         const int grid = (f.tiers && l == 0) ? f.ring_grid : f.grid;
         HIP_TRY(c, f.batch ? pt_launch_render_batch(&P, dP, f.variant, grid, f.geo.lds_bytes, stream, f.use_count)
+                   : f.wt  ? pt_launch_render_wt(&P, dP, f.variant, grid, f.geo.lds_bytes, stream, f.use_count)
                            : pt_launch_render(&P, dP, f.variant, grid, f.geo.lds_bytes, stream, f.use_count));
     }
     return PT_OK;
@@ -539,6 +547,7 @@ int batch_device(pt_ctx* c, const pt_frame* frames, int32_t n_frames, int32_t n_
     if (rc) return rc;
     // what only exists for one frame at a time is refused by name, never rendered by a loop of single frames
     if (c->opt.kernel != 2) return fail(c, PT_E_INVALID, "pt_render_batch: the lane-per-pixel kernel (option kernel = 1) has no batch form");
+    if (c->opt.watertight) return fail(c, PT_E_INVALID, "pt_render_batch: batches have no watertight instances (option watertight = 1); render the frames one by one or set watertight = 0");
     if (c->opt.latency) return fail(c, PT_E_INVALID, "pt_render_batch: the per-pixel latency diagnostics (option latency) are per frame; switch them off for a batch");
     if (c->opt.timeline) return fail(c, PT_E_INVALID, "pt_render_batch: the chunk timeline (option timeline) is per frame; switch it off for a batch");
     if ((rc = need_device(c))) return rc;

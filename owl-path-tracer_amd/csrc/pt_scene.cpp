@@ -405,18 +405,19 @@ int pt_set_environment(pt_ctx* c, const pt_env* env)
 int pt_debug_closest_hit_host(pt_ctx* c, const float org[3], const float dir[3], float tmin, float tmax, float* t, float* u, float* v, int32_t* prim)
 {
     if (!c || !c->have_scene) return PT_E_NO_SCENE;
-    return pt_bvh_closest_hit_host(c->scene.bvh, org, dir, tmin, tmax, t, u, v, prim) ? 1 : 0;
+    return pt_bvh_closest_hit_host(c->scene.bvh, org, dir, tmin, tmax, t, u, v, prim, c->opt.watertight != 0) ? 1 : 0;
 }
 
 int64_t pt_debug_closest_hit_host_n(pt_ctx* c, const float* rays, int64_t n, float tmin, float tmax, float* out)
 {
     if (!c || !rays || !out || n < 0) return PT_E_INVALID;
     if (!c->have_scene) return PT_E_NO_SCENE;
+    const bool wt = c->opt.watertight != 0; // the walk follows the option as the render does
     pt_parallel_ranges((size_t)n, [&](size_t lo, size_t hi) {
         for (size_t i = lo; i < hi; ++i) {
             float t = 0.0f, u = 0.0f, v = 0.0f;
             int32_t prim = -1;
-            const bool hit = pt_bvh_closest_hit_host(c->scene.bvh, rays + 6 * i, rays + 6 * i + 3, tmin, tmax, &t, &u, &v, &prim);
+            const bool hit = pt_bvh_closest_hit_host(c->scene.bvh, rays + 6 * i, rays + 6 * i + 3, tmin, tmax, &t, &u, &v, &prim, wt);
             float* y = out + 5 * i;
             y[0] = hit ? 1.0f : 0.0f; y[1] = t; y[2] = u; y[3] = v;
             const int32_t id = hit ? prim : -1;

@@ -16,6 +16,10 @@ using namespace ptd;
 
 namespace {
 
+#ifndef PT_WATERTIGHT
+#define PT_WATERTIGHT 0 // 1: pt_kernel_wt.hip, the watertight triangle test (below, "WATERTIGHT BUILD")
+#endif
+
 struct Hit {
     float t, u, v;
     int slot; // leaf-order index of the triangle
@@ -31,6 +35,9 @@ struct Counters {
     unsigned long long grp_cyc = 0;
     uint32_t lobe[16] = {};  // wave-uniform census of the hit passes by sampled lobe (PtCounters::lobes)
     uint32_t cull_nohit = 0, cull_beyond = 0, leaf_noimp = 0; // per lane: quad steps that enter no child; of those: node beyond the best hit; leaf steps that do not improve the hit
+#if PT_WATERTIGHT
+    uint32_t wt64 = 0; // per lane: (ray, triangle) pairs whose edge functions were recomputed from float64 products (pt_stats.trav[2])
+#endif
 };
 
 // Pointers read out of the parameter block are generic; every buffer is hipMalloc memory, so all accesses below go through
@@ -164,11 +171,151 @@ __device__ __forceinline__ void tri_eval2(const f32x4 a0, const f32x4 b0, const 
     tri_take(t.x, u.x, v.x, uv.x, __float_as_int(c0.y), slot0, h);
     if (take1) tri_take(t.y, u.y, v.y, uv.y, __float_as_int(c1.y), slot0 + 1, h);
 }
+#if PT_WATERTIGHT
+// WATERTIGHT BUILD (pt_kernel_wt.hip includes pt_kernel.hip with PT_WATERTIGHT = 1; option "watertight").  The triangle test of Woop,
+// Benthin and Wald ("Watertight Ray/Triangle Intersection", JCGT 2013) in the fixed float32 sequence of DESIGN.md 2.1: the ray's dominant
+// axis becomes z, the vertices are sheared into the ray's frame and the three 2-D edge functions U, V, W decide the hit.  An edge
+// function is a difference of two products of the SAME four float32 values for the two triangles that share the edge, with the roles
+// exchanged: as long as nothing is fused, the two are exact negatives of each other, so a ray can never be outside both.  Hence: no fma
+// anywhere in here (plain * and -, and the translation unit is compiled with -ffp-contract=off; the pragma below keeps that true under
+// any flags), and where an edge function is exactly 0 all three are recomputed with float64 products (exact for float32 factors) and a
+// float64 difference, rounded to float32, which keeps the sign of the exact value.
+// kz = index of the largest |d| component (first wins), kx = (kz + 1) % 3, ky = (kx + 1) % 3, kx and ky exchanged for d[kz] < 0 (the
+// definition keeps the winding; with a two-sided test the exchange only shows in the signs of zeros - u = +0 or -0 on an edge - and
+// the bits are part of the contract: pt_bvh.cpp and tests/watertight_ref.py index, this code selects, and the tests compare bit for bit).
+// The axes are chosen with compare-and-select, never by indexing a register array: each of the three picks is "first flag ? x :
+// (second flag ? y : z)" with six per-ray flags, two v_cndmask per component whatever the permutation.
+struct WtRay {
+    bool x0, x1, y0, y1, z0, z1; // kx == 0, kx == 1, ky == 0, ky == 1, kz == 0, kz == 1
+    float sx, sy, sz;            // d[kx] / d[kz], d[ky] / d[kz], 1 / d[kz]: correctly rounded divisions
+};
+// (handed on as scalars: the struct as a reference parameter stayed in memory across the leaf loop - 16 bytes of scratch per lane)
+#define PT_WT_PASS(r) (r).x0, (r).x1, (r).y0, (r).y1, (r).z0, (r).z1, (r).sx, (r).sy, (r).sz
+#define PT_WT_PARAMS const bool rx0, const bool rx1, const bool ry0, const bool ry1, const bool rz0, const bool rz1, const float rsx, const float rsy, const float rsz
+#define PT_WT_FROM_PARAMS {rx0, rx1, ry0, ry1, rz0, rz1, rsx, rsy, rsz}
+__device__ __forceinline__ float wt_pick(const bool f0, const bool f1, float x, float y, float z) { return f0 ? x : (f1 ? y : z); }
+__device__ __forceinline__ f32x2 wt_pick(const bool f0, const bool f1, f32x2 x, f32x2 y, f32x2 z) { return f0 ? x : (f1 ? y : z); }
+__device__ __forceinline__ WtRay wt_ray(v3 dir)
+{
+    const float dx = dir.x, dy = dir.y, dz0 = dir.z;
+    const float ax = __builtin_fabsf(dx), ay = __builtin_fabsf(dy), az = __builtin_fabsf(dz0);
+    WtRay r;
+    r.z0 = ax >= ay && ax >= az;
+    r.z1 = !r.z0 && ay >= az;
+    const bool z2 = !r.z0 && !r.z1;
+    const float dz = wt_pick(r.z0, r.z1, dx, dy, dz0);
+    const bool sw = dz < 0.0f;
+    r.x0 = sw ? r.z1 : z2;   // kx: kz + 1, or kz + 2 after the exchange
+    r.x1 = sw ? z2 : r.z0;
+    r.y0 = sw ? z2 : r.z1;   // ky: kz + 2, or kz + 1
+    r.y1 = sw ? r.z0 : z2;
+    r.sx = wt_pick(r.x0, r.x1, dx, dy, dz0) / dz;
+    r.sy = wt_pick(r.y0, r.y1, dx, dy, dz0) / dz;
+    r.sz = 1.0f / dz;
+    return r;
+}
+// one edge function from float64 products: the products are exact, the difference is rounded to float64 and then to float32
+__device__ __forceinline__ float wt_edge64(float a, float b, float c, float d)
+{
+#pragma clang fp contract(off)
+    return (float)((double)a * (double)b - (double)c * (double)d);
+}
+// acceptance: the edge functions do not disagree in sign, det != 0, then tri_take's rule for t and the tie-break (u, v are not tested
+// again: V / det may round to 1 + 2^-23 on an edge, and rejecting that would open the seam the test exists to close)
+__device__ __forceinline__ void wt_take(float U, float V, float W, float det, float t, float u, float v, int id, int slot, Hit& h)
+{
+    const bool neg = U < 0.0f || V < 0.0f || W < 0.0f, pos = U > 0.0f || V > 0.0f || W > 0.0f;
+    if (!(neg && pos) && det != 0.0f && t > kTMin && (t < h.t || (t == h.t && id < h.id))) {
+        h.t = t; h.u = u; h.v = v; h.id = id; h.slot = slot;
+    }
+}
+// One triangle (the group walk's lane-per-triangle leaf, triangles beyond the fourth of a leaf).  n64: instrumented instance, counts the
+// pairs that took the float64 branch.
+__device__ __forceinline__ void tri_eval_wt(const f32x4 a, const f32x4 b, const f32x4 c, int slot, v3 o, PT_WT_PARAMS, Hit& h, uint32_t* n64 = nullptr)
+{
+#pragma clang fp contract(off)
+    const WtRay r = PT_WT_FROM_PARAMS;
+    const float a0 = a.x - o.x, a1 = a.y - o.y, a2 = a.z - o.z; // A = p0 - o
+    const float b0 = a.w - o.x, b1 = b.x - o.y, b2 = b.y - o.z; // B = p1 - o
+    const float c0 = b.z - o.x, c1 = b.w - o.y, c2 = c.x - o.z; // C = p2 - o
+    const float Az = wt_pick(r.z0, r.z1, a0, a1, a2), Bz = wt_pick(r.z0, r.z1, b0, b1, b2), Cz = wt_pick(r.z0, r.z1, c0, c1, c2);
+    const float Ax = wt_pick(r.x0, r.x1, a0, a1, a2) - r.sx * Az, Ay = wt_pick(r.y0, r.y1, a0, a1, a2) - r.sy * Az;
+    const float Bx = wt_pick(r.x0, r.x1, b0, b1, b2) - r.sx * Bz, By = wt_pick(r.y0, r.y1, b0, b1, b2) - r.sy * Bz;
+    const float Cx = wt_pick(r.x0, r.x1, c0, c1, c2) - r.sx * Cz, Cy = wt_pick(r.y0, r.y1, c0, c1, c2) - r.sy * Cz;
+    float U = Cx * By - Cy * Bx, V = Ax * Cy - Ay * Cx, W = Bx * Ay - By * Ax;
+    const bool zero = U == 0.0f || V == 0.0f || W == 0.0f;
+    if (__ballot(zero) != 0ull) { // wave-uniform: rare for ordinary rays, the rule for rays aimed at a vertex or an edge
+        const float U64 = wt_edge64(Cx, By, Cy, Bx), V64 = wt_edge64(Ax, Cy, Ay, Cx), W64 = wt_edge64(Bx, Ay, By, Ax);
+        U = zero ? U64 : U; V = zero ? V64 : V; W = zero ? W64 : W;
+        if (n64) *n64 += zero ? 1u : 0u;
+    }
+    const float det = (U + V) + W;
+    const float T = (U * (r.sz * Az) + V * (r.sz * Bz)) + W * (r.sz * Cz);
+    const float inv = 1.0f / det;
+    wt_take(U, V, W, det, T * inv, V * inv, W * inv, __float_as_int(c.y), slot, h);
+}
+// Two triangles at once in packed-f32 registers, as tri_eval2: each half does exactly tri_eval_wt's operations in its order
+// (v_pk_mul_f32 / v_pk_add_f32 round like their scalar forms), the reciprocal of det per triangle.
+__device__ __forceinline__ void tri_eval_wt2(const f32x4 a0, const f32x4 b0, const f32x2 c0, const f32x4 a1, const f32x4 b1, const f32x2 c1, int slot0, bool take1, const f32x2 ox,
+                                             const f32x2 oy, const f32x2 oz, PT_WT_PARAMS, Hit& h, uint32_t* n64 = nullptr)
+{
+#pragma clang fp contract(off)
+    const WtRay r = PT_WT_FROM_PARAMS;
+    const f32x2 A0 = (f32x2){a0.x, a1.x} - ox, A1 = (f32x2){a0.y, a1.y} - oy, A2 = (f32x2){a0.z, a1.z} - oz;
+    const f32x2 B0 = (f32x2){a0.w, a1.w} - ox, B1 = (f32x2){b0.x, b1.x} - oy, B2 = (f32x2){b0.y, b1.y} - oz;
+    const f32x2 C0 = (f32x2){b0.z, b1.z} - ox, C1 = (f32x2){b0.w, b1.w} - oy, C2 = (f32x2){c0.x, c1.x} - oz;
+    const f32x2 sx = {r.sx, r.sx}, sy = {r.sy, r.sy}, sz = {r.sz, r.sz};
+    const f32x2 Az = wt_pick(r.z0, r.z1, A0, A1, A2), Bz = wt_pick(r.z0, r.z1, B0, B1, B2), Cz = wt_pick(r.z0, r.z1, C0, C1, C2);
+    const f32x2 Ax = wt_pick(r.x0, r.x1, A0, A1, A2) - sx * Az, Ay = wt_pick(r.y0, r.y1, A0, A1, A2) - sy * Az;
+    const f32x2 Bx = wt_pick(r.x0, r.x1, B0, B1, B2) - sx * Bz, By = wt_pick(r.y0, r.y1, B0, B1, B2) - sy * Bz;
+    const f32x2 Cx = wt_pick(r.x0, r.x1, C0, C1, C2) - sx * Cz, Cy = wt_pick(r.y0, r.y1, C0, C1, C2) - sy * Cz;
+    f32x2 U = Cx * By - Cy * Bx, V = Ax * Cy - Ay * Cx, W = Bx * Ay - By * Ax;
+    const bool zero0 = U.x == 0.0f || V.x == 0.0f || W.x == 0.0f, zero1 = U.y == 0.0f || V.y == 0.0f || W.y == 0.0f;
+    if (__ballot(zero0 || zero1) != 0ull) {
+        const f32x2 U64 = {wt_edge64(Cx.x, By.x, Cy.x, Bx.x), wt_edge64(Cx.y, By.y, Cy.y, Bx.y)};
+        const f32x2 V64 = {wt_edge64(Ax.x, Cy.x, Ay.x, Cx.x), wt_edge64(Ax.y, Cy.y, Ay.y, Cx.y)};
+        const f32x2 W64 = {wt_edge64(Bx.x, Ay.x, By.x, Ax.x), wt_edge64(Bx.y, Ay.y, By.y, Ax.y)};
+        U.x = zero0 ? U64.x : U.x; V.x = zero0 ? V64.x : V.x; W.x = zero0 ? W64.x : W.x;
+        U.y = zero1 ? U64.y : U.y; V.y = zero1 ? V64.y : V.y; W.y = zero1 ? W64.y : W.y;
+        if (n64) *n64 += (zero0 ? 1u : 0u) + ((zero1 && take1) ? 1u : 0u);
+    }
+    const f32x2 det = (U + V) + W;
+    const f32x2 T = (U * (sz * Az) + V * (sz * Bz)) + W * (sz * Cz);
+    const f32x2 inv = {1.0f / det.x, 1.0f / det.y};
+    const f32x2 t = T * inv, u = V * inv, v = W * inv;
+    wt_take(U.x, V.x, W.x, det.x, t.x, u.x, v.x, __float_as_int(c0.y), slot0, h);
+    if (take1) wt_take(U.y, V.y, W.y, det.y, t.y, u.y, v.y, __float_as_int(c1.y), slot0 + 1, h);
+}
+#endif // PT_WATERTIGHT
 // All triangles of one leaf: the records of the first PT_LEAF_PREFETCH triangles are requested together, the tests follow.
 // The wavefront kernel's leaf step; tris is below 4 GiB there (pt_render.cpp, plan_frame): 32-bit offsets from the wave-uniform base.
 #ifndef PT_LEAF_PREFETCH
 #define PT_LEAF_PREFETCH 4
 #endif
+#if PT_WATERTIGHT
+// The watertight leaf step: the same loads and the same pairing; the ray's axes and shear are formed here, once per leaf step, from d
+// alone (carrying them with the ray would cost five registers in the walk and a wider park area; the arithmetic gives the same bits).
+__device__ __forceinline__ void leaf_test(const PtTri* __restrict__ tris, int first, int count, v3 o, v3 d, Hit& h, uint32_t* n64 = nullptr)
+{
+    static_assert(PT_LEAF_PREFETCH == 4, "the leaf step tests the triangles of a leaf in two pairs");
+    f32x4 ra[4], rb[4];
+    f32x2 rc[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int kk = k < count ? k : count - 1;
+        const uint32_t tb = (uint32_t)(first + kk) * (uint32_t)sizeof(PtTri);
+        ra[k] = ldg4u(tris, tb, 0); rb[k] = ldg4u(tris, tb, 16); rc[k] = ldg2u(tris, tb, 32);
+    }
+    const WtRay r = wt_ray(d);
+    const f32x2 ox = {o.x, o.x}, oy = {o.y, o.y}, oz = {o.z, o.z};
+    tri_eval_wt2(ra[0], rb[0], rc[0], ra[1], rb[1], rc[1], first, count > 1, ox, oy, oz, PT_WT_PASS(r), h, n64);
+    if (count > 2) tri_eval_wt2(ra[2], rb[2], rc[2], ra[3], rb[3], rc[3], first + 2, count > 3, ox, oy, oz, PT_WT_PASS(r), h, n64);
+    for (int k = 4; k < count; ++k) { // leaf_size > 4 only
+        const size_t tb = (size_t)(uint32_t)(first + k) * sizeof(PtTri);
+        tri_eval_wt(ldg4(tris, tb), ldg4(tris, tb + 16), ldg4(tris, tb + 32), first + k, o, PT_WT_PASS(r), h, n64);
+    }
+}
+#else
 __device__ __forceinline__ void leaf_test(const PtTri* __restrict__ tris, int first, int count, v3 o, v3 d, Hit& h)
 {
 #if PT_LEAF_PREFETCH == 0
@@ -191,6 +338,7 @@ __device__ __forceinline__ void leaf_test(const PtTri* __restrict__ tris, int fi
     for (int k = 4; k < count; ++k) tri_test(tris, first + k, o, d, h); // leaf_size > 4 only
 #endif
 }
+#endif // PT_WATERTIGHT
 
 // One BVH-node step for a lane: test both children, descend into the nearer hit child, push the other.
 // Stack entry i lives in LDS (stack[i * STRIDE]) for i < LDS_ENTRIES, else in the lane's HBM overflow column
@@ -450,6 +598,13 @@ __device__ __forceinline__ void flush_counters(const PtKernelParams& P, const Co
         for (int off = 32; off > 0; off >>= 1) { x0 += __shfl_down(x0, off, 64); x1 += __shfl_down(x1, off, 64); x3 += __shfl_down(x3, off, 64); }
         if ((threadIdx.x & 63) == 0) { atomicAdd(&P.counters->trav[0], x0); atomicAdd(&P.counters->trav[1], x1); atomicAdd(&P.counters->trav[3], x3); }
     }
+#if PT_WATERTIGHT
+    {
+        unsigned long long x2 = cn.wt64;
+        for (int off = 32; off > 0; off >>= 1) x2 += __shfl_down(x2, off, 64);
+        if ((threadIdx.x & 63) == 0) atomicAdd(&P.counters->trav[2], x2);
+    }
+#endif
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         unsigned long long x = cn.depth[k];

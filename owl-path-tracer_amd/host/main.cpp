@@ -9,7 +9,8 @@
 // group path on exactly these devices, the reduce onto the first; with --gpus the counts must agree, with --device it is an error;
 // a device named twice is refused by the real RCCL), --dump-scene FILE (binary dump of the ingested scene for the loader tests),
 // --batch K (K >= 1: test_loop collects K sweep steps and renders them with ONE pt_render_batch - one launch sequence for K frames -
-// instead of K x pt_set_materials + pt_render; the PNGs are byte for byte the same; not together with --gpus / --devices).
+// instead of K x pt_set_materials + pt_render; the PNGs are byte for byte the same; not together with --gpus / --devices),
+// --watertight (option "watertight" = 1 on every context: the watertight triangle test, mi355pt.h; not together with --batch).
 #include <sys/stat.h>
 #include <unistd.h>
 
@@ -205,7 +206,7 @@ int main(int argc, char** argv)
         std::string settings_path, dump;
         a.out_dir = cwd;
         int device = 0, gpus = 0; // gpus 0: flag not given, single context as in the reference
-        bool have_device = false, have_devices = false, have_batch = false;
+        bool have_device = false, have_devices = false, have_batch = false, watertight = false;
         std::vector<int32_t> devs; // --devices
         for (int i = 1; i < argc; ++i) {
             std::string k = argv[i];
@@ -218,6 +219,7 @@ int main(int argc, char** argv)
             else if (k == "--gpus") gpus = std::atoi(next().c_str());
             else if (k == "--dump-scene") dump = next();
             else if (k == "--batch") { a.batch = std::atoi(next().c_str()); have_batch = true; }
+            else if (k == "--watertight") watertight = true;
             else if (k == "--convert-png" || k == "--convert-hdr") { // codec self-test hooks: decode with our reader, re-encode with our writer
                 std::string in = next(), out = next();
                 imgio::Image img = k == "--convert-png" ? imgio::load_png_rgba8(in) : imgio::load_hdr_as_ldr_rgba8(in);
@@ -235,6 +237,7 @@ int main(int argc, char** argv)
                 throw std::runtime_error("--devices names " + std::to_string(devs.size()) + " device(s) but --gpus says " + std::to_string(gpus));
             gpus = (int)devs.size();
         }
+        if (have_batch && watertight) throw std::runtime_error("--batch cannot be combined with --watertight (pt_render_batch has no watertight instances)");
         if (settings_path.empty()) settings_path = assets + "/settings.json"; // application.cpp:145
 
         std::fprintf(stderr, "Parsing settings\n");
@@ -312,6 +315,10 @@ int main(int argc, char** argv)
             if (!a.ctx) throw std::runtime_error(std::string("pt_create: ") + pt_last_error(nullptr));
             check(a, pt_upload_scene(a.ctx, meshes.data(), (int32_t)meshes.size(), a.materials.data(), (int32_t)a.scene.materials.size(),
                                      textures.data(), (int32_t)textures.size(), nullptr, &env), "pt_upload_scene");
+        }
+        if (watertight) {
+            if (a.group) check(a, pt_group_set_option(a.group, "watertight", 1), "pt_group_set_option");
+            else check(a, pt_set_option(a.ctx, "watertight", 1), "pt_set_option");
         }
         pt_to_camera_data(a.scene.camera.look_from, a.scene.camera.look_at, a.scene.camera.look_up, a.scene.camera.vertical_fov,
                           a.settings.buffer_size[0], a.settings.buffer_size[1], &a.cam); // parse_camera -> to_camera_data

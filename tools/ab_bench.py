@@ -3,7 +3,11 @@
 
 batch=K (c2 / c3 / c4, with shard_rank= / shard_world= if wanted): K frames of a material sweep as ONE pt_render_batch (B) against the same
 K frames as K x (pt_set_materials + pt_render) (A), alternating in this process after one warm-up of each: kernel ms from pt_stats, wall
-ms around the calls including the read-back; the frames are compared bit for bit.  census=1 adds a counted batch (scheduler census)."""
+ms around the calls including the read-back; the frames are compared bit for bit.  census=1 adds a counted batch (scheduler census).
+
+toggle=KEY (any scene): option KEY = 0 (A) against KEY = 1 (B) on ONE context and upload, alternating in this process after one warm-up
+of each: kernel ms with spread, the instance that ran (variant, VGPRs) and a counted frame per side (rays, triangle tests, pt_stats.trav).
+toggle=watertight is how profiles/r09_watertight.json was measured."""
 import os, sys, json, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -13,7 +17,7 @@ ptamd.load()
 from owl_path_tracer_amd.pyhost import binding as B, scene_io, procedural
 
 PRE_UPLOAD = ("leaf_size", "max_bvh_depth", "node_pairs", "leaf_align", "bvh_builder", "ploc_radius", "wide_leaves")  # builder / layout options: before upload_scene
-NOT_OPTIONS = ("finish", "tiers", "spp", "census", "shard_rank", "shard_world", "shard_tile", "detail_u", "detail_v", "chain", "sweep", "frame_out", "batch")
+NOT_OPTIONS = ("finish", "tiers", "spp", "census", "shard_rank", "shard_world", "shard_tile", "detail_u", "detail_v", "chain", "sweep", "frame_out", "batch", "toggle")
 
 # C3 material sweep ("for BSDF coverage add a material sweep over metallic/clearcoat/transmission/sheen"; the reference's
 # driver is test_loop / modify_sbt, application.hpp:89-108, application.cpp:329-360): the attribute is set on the two objects of the
@@ -124,6 +128,36 @@ def batch_ab(ctx, which, mats, cam, W, H, spp, reps, opts):
     print(json.dumps(out))
 
 
+def toggle_ab(ctx, which, key, cam, W, H, spp, reps, opts):
+    """toggle=KEY: see the module docstring."""
+    import zlib
+
+    sides = {}
+    for v in (0, 1):  # warm-up of each side, its frame and its counted frame
+        ctx.set_option(key, v)
+        rgb, _ = ctx.render(cam, W, H, spp, 16)
+        st = ctx.stats()
+        ctx.set_option("count", 1)
+        ctx.render(cam, W, H, spp, 16)
+        cs = ctx.stats()
+        ctx.set_option("count", 0)
+        sides[v] = {"variant": st["kernel_variant"], "vgprs": st["vgprs"], "vgprs_instrumented": cs["vgprs"], "launches": st["launches"], "kernel_ms": [],
+                    "frame_crc32": "%08x" % (zlib.crc32(np.ascontiguousarray(rgb, np.float32).tobytes()) & 0xFFFFFFFF), "finite": bool(np.isfinite(rgb).all()),
+                    "mean": float(rgb.mean(dtype=np.float64)), "rays": cs["rays"], "tris": cs["tris"], "nodes": cs["nodes"], "samples": cs["samples"], "trav": cs["trav"]}
+    for _ in range(reps):
+        for v in (0, 1):
+            ctx.set_option(key, v)
+            ctx.render(cam, W, H, spp, 16)
+            sides[v]["kernel_ms"].append(round(ctx.stats()["kernel_ms"], 2))
+    ctx.set_option(key, 0)
+    for v in (0, 1):
+        k = sides[v]["kernel_ms"]
+        sides[v].update(kernel_ms_min=min(k), kernel_ms_med=round(float(np.median(k)), 2), kernel_ms_max=max(k))
+    a, b = sides[0], sides[1]
+    print(json.dumps({"lib": os.path.basename(B.LIB_PATH), "scene": which, "toggle": key, "opts": opts, "size": [W, H, spp], "reps": reps, "A_%s_0" % key: a, "B_%s_1" % key: b,
+                      "B_over_A_med": round(b["kernel_ms_med"] / a["kernel_ms_med"], 4), "B_over_A_min": round(b["kernel_ms_min"] / a["kernel_ms_min"], 4)}))
+
+
 def main():
     which = sys.argv[1] if len(sys.argv) > 1 else "c4"
     reps = int(sys.argv[2]) if len(sys.argv) > 2 else 3
@@ -174,6 +208,8 @@ def main():
         if which not in ("c2", "c3", "c4"):
             raise SystemExit("batch=K: c2, c3 or c4")
         return batch_ab(ctx, which, mats, cam, W, H, spp, reps, opts)
+    if opts.get("toggle"):
+        return toggle_ab(ctx, which, opts["toggle"], cam, W, H, spp, reps, opts)
     if opts.get("sweep"):  # c3 sweep=1: one timed frame (+ one counted frame) per material variant
         base = np.stack([m for _, m, _ in mats]).astype(np.float32)
         names = [n for n, _, _ in mats]
