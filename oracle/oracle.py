@@ -86,6 +86,7 @@ def lib():
     L.orc_scene_create.argtypes = [C.POINTER(SceneDesc), C.c_int]
     L.orc_scene_destroy.argtypes = [C.c_void_p]
     L.orc_scene_set_materials.argtypes = [C.c_void_p, fp, C.c_int]
+    L.orc_scene_set_watertight.argtypes = [C.c_void_p, C.c_int]
     L.orc_scene_bvh_nodes.argtypes = [C.c_void_p]
     L.orc_scene_bvh_depth.argtypes = [C.c_void_p]
     L.orc_to_camera_data.argtypes = [fp, fp, fp, C.c_float, C.c_int, C.c_int, C.POINTER(Camera)]
@@ -299,7 +300,7 @@ def make_env(use_map=False, use_auto=False, color=(0, 0, 0), intensity=0.0, env_
 class Scene:
     """Oracle scene built from a flattened triangle soup (see pyhost.scene_io.flatten_scene)."""
 
-    def __init__(self, flat, leaf_size=4):
+    def __init__(self, flat, leaf_size=4, watertight=False):
         self._keep = []
         d = SceneDesc()
         n = int(flat["positions"].shape[0])
@@ -329,6 +330,9 @@ class Scene:
         self._keep += [mi, ti, mats, arr]
         self.n_tris = n
         self.h = lib().orc_scene_create(C.byref(d), leaf_size)
+        self.watertight = False
+        if watertight:
+            self.set_watertight(True)
 
     def __del__(self):
         try:
@@ -337,6 +341,11 @@ class Scene:
                 self.h = None
         except Exception:
             pass
+
+    def set_watertight(self, on):
+        """The triangle test of every later closest hit and render of this scene: False = Moeller-Trumbore, True = option "watertight" = 1."""
+        lib().orc_scene_set_watertight(self.h, int(bool(on)))
+        self.watertight = bool(on)
 
     def set_materials(self, mats):
         m, mp = _f(np.asarray(mats, np.float32).reshape(-1))

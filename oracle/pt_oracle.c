@@ -852,6 +852,7 @@ struct orc_scene {
     int depth;
     int32_t root; /* root child ref (leaf if tiny) */
     float rmin[3], rmax[3];
+    int watertight; /* 0: Moeller-Trumbore (the default); 1: the watertight test of DESIGN.md 2.1 (orc_scene_set_watertight) */
 };
 
 typedef struct build_ctx {
@@ -1056,14 +1057,66 @@ void orc_scene_set_materials(orc_scene* s, const float* materials, int n_materia
     s->n_materials = n_materials;
     s->materials = (float*)xmemdup(materials, (size_t)n_materials * ORC_MAT_FLOATS * 4);
 }
+void orc_scene_set_watertight(orc_scene* s, int on) { s->watertight = on != 0; }
 int orc_scene_bvh_nodes(const orc_scene* s) { return s->n_nodes; }
 int orc_scene_bvh_depth(const orc_scene* s) { return s->depth; }
 
 typedef struct hit { float t, u, v; int32_t prim; } hit;
 
-/* Moeller-Trumbore, two-sided, tmin < t < tmax; ties in t resolved towards the lower global id */
-static inline void tri_test(const float* p, int32_t id, v3 o, v3 d, float tmin, hit* h)
+/* The watertight test (Woop, Benthin, Wald, JCGT 2013) in the operation sequence DESIGN.md 2.1 fixes, written from that text: all
+   float32, nothing fused (the build has -ffp-contract=off and no fmaf is spelled here), the axes chosen by index. */
+typedef struct wt_ray { int kx, ky, kz; float Sx, Sy, Sz, ox, oy, oz; } wt_ray; /* per ray: the axes, the shear, the origin in those axes */
+
+static inline wt_ray wt_ray_of(v3 o, v3 d)
 {
+    const float dir[3] = {d.x, d.y, d.z}, org[3] = {o.x, o.y, o.z};
+    wt_ray r;
+    r.kz = 0; /* the largest |component|, the first one on a tie */
+    if (dm_abs(dir[1]) > dm_abs(dir[r.kz])) r.kz = 1;
+    if (dm_abs(dir[2]) > dm_abs(dir[r.kz])) r.kz = 2;
+    r.kx = (r.kz + 1) % 3;
+    r.ky = (r.kx + 1) % 3;
+    if (dir[r.kz] < 0.0f) { int k = r.kx; r.kx = r.ky; r.ky = k; }
+    r.Sx = dir[r.kx] / dir[r.kz];
+    r.Sy = dir[r.ky] / dir[r.kz];
+    r.Sz = 1.0f / dir[r.kz];
+    r.ox = org[r.kx]; r.oy = org[r.ky]; r.oz = org[r.kz];
+    return r;
+}
+
+static inline float wt_edge64(float a, float b, float c, float d) { return (float)((double)a * (double)b - (double)c * (double)d); }
+
+static inline void tri_test_watertight(const float* p, int32_t id, const wt_ray* r, float tmin, hit* h)
+{
+    const int kx = r->kx, ky = r->ky, kz = r->kz;
+    const float ox = r->ox, oy = r->oy, oz = r->oz;
+    float x[3], y[3], z[3]; /* A, B, C = p0, p1, p2 relative to the origin, sheared along the ray */
+    z[0] = p[kz] - oz;     x[0] = (p[kx] - ox) - r->Sx * z[0];     y[0] = (p[ky] - oy) - r->Sy * z[0];
+    z[1] = p[3 + kz] - oz; x[1] = (p[3 + kx] - ox) - r->Sx * z[1]; y[1] = (p[3 + ky] - oy) - r->Sy * z[1];
+    z[2] = p[6 + kz] - oz; x[2] = (p[6 + kx] - ox) - r->Sx * z[2]; y[2] = (p[6 + ky] - oy) - r->Sy * z[2];
+    float U = x[2] * y[1] - y[2] * x[1];
+    float Vv = x[0] * y[2] - y[0] * x[2];
+    float W = x[1] * y[0] - y[1] * x[0];
+    if ((U == 0.0f) | (Vv == 0.0f) | (W == 0.0f)) { /* on an edge or a vertex up to rounding: all three again, exact products */
+        U = wt_edge64(x[2], y[1], y[2], x[1]);
+        Vv = wt_edge64(x[0], y[2], y[0], x[2]);
+        W = wt_edge64(x[1], y[0], y[1], x[0]);
+    }
+    if (((U < 0.0f) | (Vv < 0.0f) | (W < 0.0f)) & ((U > 0.0f) | (Vv > 0.0f) | (W > 0.0f))) return; /* one negative and another positive */
+    float det = (U + Vv) + W;
+    if (det == 0.0f) return;
+    float T = (U * (r->Sz * z[0]) + Vv * (r->Sz * z[1])) + W * (r->Sz * z[2]);
+    float inv = 1.0f / det;
+    float t = T * inv, u = Vv * inv, v = W * inv; /* u: weight of p1, v: weight of p2; neither is tested again */
+    if (t > tmin && (t < h->t || (t == h->t && id < h->prim))) {
+        h->t = t; h->u = u; h->v = v; h->prim = id;
+    }
+}
+
+/* Moeller-Trumbore, two-sided, tmin < t < tmax; ties in t resolved towards the lower global id */
+static inline void tri_test(const float* p, int32_t id, v3 o, v3 d, float tmin, hit* h, const wt_ray* wt)
+{
+    if (wt) { tri_test_watertight(p, id, wt, tmin, h); return; } /* the scene's switch is at 1 */
     v3 p0 = ld3(p), p1 = ld3(p + 3), p2 = ld3(p + 6);
     v3 e1 = vsub(p1, p0), e2 = vsub(p2, p0);
     v3 pv = vcross(d, e2);
@@ -1095,6 +1148,9 @@ static int intersect_bvh(const orc_scene* s, v3 o, v3 d, float tmin, float tmax,
     h->t = tmax; h->prim = 0x7fffffff; h->u = h->v = 0.0f;
     if (s->n_tris == 0) return 0;
     v3 inv = V(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
+    wt_ray wr;
+    const wt_ray* wt = NULL;
+    if (s->watertight) { wr = wt_ray_of(o, d); wt = &wr; }
     int32_t stack[128];
     int sp = 0;
     int32_t cur = s->root;
@@ -1118,7 +1174,7 @@ static int intersect_bvh(const orc_scene* s, v3 o, v3 d, float tmin, float tmax,
             int first = (int)(code >> 3), count = (int)(code & 7u);
             for (int i = 0; i < count; ++i) {
                 if (cnt) cnt->tris++;
-                tri_test(s->pos + (size_t)(first + i) * 9, s->ids[first + i], o, d, tmin, h);
+                tri_test(s->pos + (size_t)(first + i) * 9, s->ids[first + i], o, d, tmin, h, wt);
             }
         }
         if (sp == 0) break;
@@ -1130,9 +1186,12 @@ static int intersect_bvh(const orc_scene* s, v3 o, v3 d, float tmin, float tmax,
 static int intersect_brute(const orc_scene* s, v3 o, v3 d, float tmin, float tmax, hit* h, orc_counters* cnt)
 {
     h->t = tmax; h->prim = 0x7fffffff; h->u = h->v = 0.0f;
+    wt_ray wr;
+    const wt_ray* wt = NULL;
+    if (s->watertight) { wr = wt_ray_of(o, d); wt = &wr; }
     for (int i = 0; i < s->n_tris; ++i) {
         if (cnt) cnt->tris++;
-        tri_test(s->gpos + (size_t)i * 9, i, o, d, tmin, h);
+        tri_test(s->gpos + (size_t)i * 9, i, o, d, tmin, h, wt);
     }
     return h->prim != 0x7fffffff;
 }

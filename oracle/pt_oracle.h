@@ -75,6 +75,10 @@ typedef struct orc_scene orc_scene;
 orc_scene* orc_scene_create(const orc_scene_desc* d, int leaf_size);
 void orc_scene_destroy(orc_scene* s);
 void orc_scene_set_materials(orc_scene* s, const float* materials, int n_materials);
+/* Which triangle test every closest hit of this scene uses from now on (orc_intersect*, orc_render, orc_trace_*): 0, the default, is
+   Moeller-Trumbore; 1 is the watertight test of option "watertight" = 1 in the operation sequence of DESIGN.md 2.1.  The sliver rule,
+   tmin, the tie-break and the boxes are the same for both. */
+void orc_scene_set_watertight(orc_scene* s, int on);
 int orc_scene_bvh_nodes(const orc_scene* s);
 int orc_scene_bvh_depth(const orc_scene* s);
 

@@ -6,6 +6,10 @@ triangle soup (with coincident, degenerate, axis-aligned and huge triangles mixe
 extremes 0 / 1 over-represented), an environment mode, a camera (every fourth one axis-parallel from an off-origin point), an image size
 that is not a multiple of anything, spp, depth and one of the library's render paths.  40 cases by default (~15 s); PT_FUZZ_CASES=N for
 more, PT_FUZZ_SEED to move the sequence.  A failure prints the seed of the case, which reproduces it alone.
+
+The same cases a second time with option "watertight" = 1 against the oracle's watertight twin (Scene(..., watertight=True)): the drawn
+path plus the option, the default path where the drawn one is the lane-per-pixel kernel, which refuses the option.  That the oracle's
+watertight frame of every default case does not depend on its hierarchy is tests/test_oracle_watertight.py's business (no GPU).
 """
 import os
 
@@ -28,7 +32,7 @@ PATHS = [(), (("groups", 2),), (("groups", 0),), (("kernel", 1),), (("whole", 1)
          (("shard", 0),), (("shard", 1),), (("shard", 2),)]
 DEFAULTS = {"groups": 1, "kernel": 2, "whole": -1, "express_permille": -1, "schedule": 1, "chunk_spp": 64, "fallback": 0, "box_exact": -1, "count": 0, "quad": 1,
             "slots_per_wave": 0, "blocks_per_cu": 0, "prepass_spp": 0, "cost_radius": 2, "spp_per_launch": 0, "chunk_tail_min": -1, "sticky_pct": -1, "ns_express": 8,
-            "tune0": 0, "adaptive": 1}
+            "tune0": 0, "adaptive": 1, "watertight": 0}
 
 
 def _bits(a):
@@ -152,7 +156,14 @@ def draw_case(seed, large=False):
                 camera=(frm, at, up, fov), path=path, shard=shard)
 
 
-def _case(gpu, orc, scene_io, seed, large=False, path=None):
+def watertight_path(path):
+    """The path of a case with option "watertight" = 1: option "kernel" = 1 has no watertight form and refuses it, the default path stands in."""
+    if any(k == "kernel" and v == 1 for k, v in path):
+        path = ()
+    return tuple(path) + (("watertight", 1),)
+
+
+def _case(gpu, orc, scene_io, seed, large=False, path=None, watertight=0):
     c = draw_case(seed, large)
     ents, mats, W, H, spp, depth, mode, env = c["ents"], c["mats"], c["W"], c["H"], c["spp"], c["depth"], c["mode"], c["env"]
     texs, mesh_tex, tex_by_mat, shard = c["texs"], c["mesh_tex"], c["tex_by_mat"], c["shard"]
@@ -161,6 +172,8 @@ def _case(gpu, orc, scene_io, seed, large=False, path=None):
         path = c["path"]
     else:
         shard = None  # (tools/fuzz_diag.py: the same case through a path of the caller's choice)
+    if watertight:
+        path = watertight_path(path)
     cam = B.to_camera_data(frm, at, up, fov, W, H)
     ocam = orc.to_camera_data(tuple(frm), tuple(at), tuple(up), fov, W, H)
     pre = {"bvh": ("bvh_builder", 3), "leaf": ("leaf_size", 4), "wide": ("wide_leaves", 0)}
@@ -182,7 +195,7 @@ def _case(gpu, orc, scene_io, seed, large=False, path=None):
                 gpu.set_option(*pre[k])
             elif k != "shard":
                 gpu.set_option(k, DEFAULTS[k])
-    S = orc.Scene(scene_io.flatten_scene(ents, [("m%d" % i, m, "") for i, m in enumerate(mats)], tex_by_mat))
+    S = orc.Scene(scene_io.flatten_scene(ents, [("m%d" % i, m, "") for i, m in enumerate(mats)], tex_by_mat), watertight=bool(watertight))
     want, want8, _ = S.render(ocam, orc.make_env(**env), W, H, spp, depth, want_rgba8=True)
     if shard:
         own = np.zeros(W * H, bool)
@@ -206,17 +219,35 @@ def _context():
     return gpu
 
 
-def test_random_scenes_bitwise(orc, scene_io):
+def _random_scenes(orc, scene_io, watertight):
     gpu = _context()
     only = os.environ.get("PT_FUZZ_ONLY")
     seeds = [int(only)] if only else [SEED0 + i for i in range(N_CASES)]
     for n, seed in enumerate(seeds):
-        _case(gpu, orc, scene_io, seed)
+        _case(gpu, orc, scene_io, seed, watertight=watertight)
         if (n + 1) % 100 == 0:
-            print("fuzz: %d cases bit-identical" % (n + 1), flush=True)
+            print("fuzz%s: %d cases bit-identical" % (", watertight" if watertight else "", n + 1), flush=True)
+    gpu.close()
+    return len(seeds)
+
+
+def test_random_scenes_bitwise(orc, scene_io):
+    _random_scenes(orc, scene_io, 0)
+
+
+def test_random_scenes_bitwise_watertight(orc, scene_io):
+    """The same seeds, the same generator, every case compared: t, u, v of the watertight leaf step reach normals, texels and the next
+    ray's origin, and the frame is the watertight oracle's bit for bit."""
+    n = _random_scenes(orc, scene_io, 1)
+    print("fuzz, watertight: %d cases compared, none left out" % n)
+    if os.environ.get("PT_WRITE_PROFILES") == "1":  # (how many of these frames differ from the switch-0 frame: section "oracle" of the same file)
+        from test_watertight_host import write_profile
+
+        write_profile("gpu_fuzz", dict(seed0=SEED0, cases_compared_bit_for_bit=n, cases_left_out=0, large_frames_compared=N_LARGE_WATERTIGHT))
 
 
 N_LARGE = int(os.environ.get("PT_FUZZ_LARGE", "8"))
+N_LARGE_WATERTIGHT = 4
 
 
 def test_random_large_frames_bitwise(orc, scene_io):
@@ -228,3 +259,11 @@ def test_random_large_frames_bitwise(orc, scene_io):
         _case(gpu, orc, scene_io, SEED0 + 5_000_000 + n, large=True)
         if (n + 1) % 25 == 0:
             print("fuzz (large frames): %d cases bit-identical" % (n + 1), flush=True)
+
+
+def test_random_large_frames_bitwise_watertight(orc, scene_io):
+    """Four of the large frames with option "watertight" = 1 against the watertight oracle."""
+    gpu = _context()
+    for n in range(N_LARGE_WATERTIGHT):
+        _case(gpu, orc, scene_io, SEED0 + 5_000_000 + n, large=True, watertight=1)
+    gpu.close()

@@ -1,5 +1,7 @@
 """The watertight triangle test of option "watertight" = 1, restated in float32 numpy as brute force over all triangles: the bit-level
-reference of tests/test_watertight_host.py and tests/test_gpu_watertight.py.  No GPU, no product code.
+reference of tests/test_watertight_host.py (the library's host walk), tests/test_gpu_watertight.py (the device's ray probes) and
+tests/test_oracle_watertight.py (the oracle's watertight twin, which in turn is the reference of the watertight FRAMES: numpy brute
+force does not render).  No GPU, no product code, no oracle code.
 
 The test of Woop, Benthin and Wald ("Watertight Ray/Triangle Intersection", JCGT 2013) in the operation sequence DESIGN.md 2.1 fixes.
 numpy's float32 `*`, `-`, `+`, `/` are correctly rounded and never fused, so every intermediate here is what an IEEE implementation

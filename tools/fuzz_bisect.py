@@ -1,4 +1,6 @@
-"""Find the first sample of a differing pixel of a fuzz case where product and oracle part ways."""
+"""Find the first sample of a differing pixel of a fuzz case where product and oracle part ways: `python tools/fuzz_bisect.py <seed> [large]
+[watertight]`.  With `watertight` both sides use the watertight triangle test, and the per-bounce replay goes through probe op "quad"
+(the validation kernel's closest-hit op has no watertight form)."""
 import os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -11,7 +13,8 @@ from owl_path_tracer_amd.pyhost import scene_io, binding as B
 import test_gpu_fuzz as F
 
 seed = int(sys.argv[1])
-c = F.draw_case(seed, len(sys.argv) > 2)
+wt = "watertight" in sys.argv[2:]
+c = F.draw_case(seed, any(a != "watertight" for a in sys.argv[2:]))
 ents, mats, W, H, spp, depth, mode, env = c["ents"], c["mats"], c["W"], c["H"], c["spp"], c["depth"], c["mode"], c["env"]
 texs, mesh_tex, tex_by_mat = c["texs"], c["mesh_tex"], c["tex_by_mat"]
 frm, at, up, fov = c["camera"]
@@ -22,7 +25,8 @@ cam = B.to_camera_data(frm, at, up, fov, W, H)
 ocam = orc.to_camera_data(tuple(frm), tuple(at), tuple(up), fov, W, H)
 gpu = B.Context(0)
 gpu.upload_scene(ents, mats, textures=texs, mesh_textures=mesh_tex, env=B.make_env(**env))
-S = orc.Scene(scene_io.flatten_scene(ents, [("m%d" % i, m, "") for i, m in enumerate(mats)], tex_by_mat))
+S = orc.Scene(scene_io.flatten_scene(ents, [("m%d" % i, m, "") for i, m in enumerate(mats)], tex_by_mat), watertight=wt)
+gpu.set_option("watertight", int(wt))
 oenv = orc.make_env(**env)
 got, _ = gpu.render(cam, W, H, spp, depth)
 want, _, _ = S.render(ocam, oenv, W, H, spp, depth)
@@ -59,7 +63,7 @@ for (y, x) in bad[:1]:
     log = S.trace_sample(ocam, oenv, W, H, int(x), int(py), first - 1, depth)
     print("oracle log of sample %d: %d bounces" % (first - 1, len(log)))
     rays = log[:, 0:6].copy()
-    hits = gpu.debug_eval("closest_hit", rays, 5)
+    hits = gpu.debug_eval("quad", rays, 6)[:, :5] if wt else gpu.debug_eval("closest_hit", rays, 5)
     rows = []
     for r in log:
         mi = int(r[11:12].view(np.int32)[0])
