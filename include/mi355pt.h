@@ -131,6 +131,20 @@ int pt_upload_scene(pt_ctx* ctx, const pt_mesh* meshes, int32_t n_meshes, const 
 int pt_set_materials(pt_ctx* ctx, const float* materials, int32_t n_materials);
 int pt_set_environment(pt_ctx* ctx, const pt_env* env);
 
+/* ---- moving geometry: new vertices for the uploaded scene, the hierarchies refitted on the device, nothing rebuilt (no reference
+ * counterpart: the reference rebuilds its acceleration structure, application.cpp:131-140) ----
+ * Needs a scene uploaded with option "dynamic" = 1.  Reads ONLY these fields of each mesh: vertices (NULL = this mesh is unchanged),
+ * normals (NULL = keep the normals the library holds), n_vertices and n_normals; n_meshes and these counts must equal the upload's,
+ * everything else in pt_mesh is ignored (indices may be NULL).  Blocking; waits for the frames in flight.  Every argument is checked
+ * before anything is touched: a refused call (PT_E_NO_SCENE: no scene; PT_E_INVALID: scene not uploaded with "dynamic" = 1, a count
+ * that differs, a NULL array with a non-zero count) leaves the scene exactly as it was.
+ * The topology of the three hierarchies stays; triangle records, sliver collapse, padding and every box become bit for bit what a fresh
+ * pt_upload_scene of the moved meshes would store for that topology, so - the closest hit being independent of the hierarchy - every
+ * frame, probe and counter after the call equals the one after a fresh upload.  What does not follow the geometry is the QUALITY of the
+ * tree: it was built for the uploaded positions and walks slower the further the scene deforms (DESIGN.md 4 "Refit" has figures); the
+ * remedy is a fresh pt_upload_scene. */
+int pt_update_vertices(pt_ctx* ctx, const pt_mesh* meshes, int32_t n_meshes);
+
 /* ---- pixel ownership (multi-GPU sharding; no reference counterpart: the reference is single-GPU) ----
  * Default: this context renders every pixel.  Launch-index pixel id = x + W*y (ray_gen's pixelId). */
 int pt_set_pixel_shard(pt_ctx* ctx, int32_t rank, int32_t world_size, int32_t tile);
@@ -220,6 +234,7 @@ int pt_group_upload_scene(pt_group* g, const pt_mesh* meshes, int32_t n_meshes, 
                           const pt_texture* textures, int32_t n_textures, const int32_t* material_texture, const pt_env* env);
 int pt_group_set_materials(pt_group* g, const float* materials, int32_t n_materials);
 int pt_group_set_option(pt_group* g, const char* key, int64_t value);
+int pt_group_update_vertices(pt_group* g, const pt_mesh* meshes, int32_t n_meshes); /* every device refits its own replica */
 int pt_group_render(pt_group* g, const pt_camera* cam, int32_t width, int32_t height, int32_t max_samples, int32_t max_path_depth,
                     float* out_rgb, uint32_t* out_rgba8);
 
@@ -254,7 +269,10 @@ int pt_group_render(pt_group* g, const pt_camera* cam, int32_t width, int32_t he
  *   closest-hit definition stays: two-sided, t > 1e-3, minimum t, ties to the lower triangle id, slivers collapsed at upload (so a
  *   needle inside a closed mesh still opens a gap of under 1e-5 of its edge).  Switchable between renders of one context, no new
  *   pt_upload_scene.  With "watertight" = 1 these are refused with PT_E_INVALID and a message, never rendered with the other test:
- *   option "kernel" = 1 (either order of the two pt_set_option calls), pt_debug_eval's closest-hit op 21, pt_render_batch(_device). */
+ *   option "kernel" = 1 (either order of the two pt_set_option calls), pt_debug_eval's closest-hit op 21, pt_render_batch(_device).
+ *   "dynamic" 0 (default: pt_upload_scene keeps and allocates exactly what it always did) | 1: the NEXT pt_upload_scene also keeps, on
+ *   the host and in HBM, what pt_update_vertices needs - the meshes' vertex and normal arrays, three vertex indices per triangle slot,
+ *   the binary nodes sorted by height, and for every quad / oct slot the binary box it is a copy of. */
 int pt_set_option(pt_ctx* ctx, const char* key, int64_t value);
 int pt_get_stats(pt_ctx* ctx, pt_stats* out);
 
@@ -291,9 +309,18 @@ int pt_debug_eval(pt_ctx* ctx, int32_t op, const float* in, int32_t in_stride, f
 /* Read-back of the hierarchy a context holds after pt_upload_scene (host copies; works on a host-only context and after a device
  * build): raw records as csrc/pt_types.h lays them out.  out NULL: returns the bytes needed; else copies and returns the bytes
  * written (cap too small: PT_E_INVALID).  PT_TREE_INFO: int64[8] = {root, root4, root8, depth, depth4, depth8, pad (float bits in
- * the low word), largest leaf}; roots are node indices or leaf codes; the quad / oct arrays are empty when the tree is too deep for them. */
-enum { PT_TREE_BINARY = 0, PT_TREE_QUAD = 1, PT_TREE_OCT = 2, PT_TREE_TRIS = 3, PT_TREE_INFO = 4 };
+ * the low word), largest leaf}; roots are node indices or leaf codes; the quad / oct arrays are empty when the tree is too deep for them.
+ * which | PT_TREE_DEVICE: the named array read back from HBM (a hipMemcpy) instead of the host copy - what the kernels of
+ * pt_update_vertices wrote; PT_E_INVALID on a host-only context; PT_TREE_INFO is the host's either way.  After pt_update_vertices on a
+ * device context the host copies are refitted by the first call that reads them (this one without the flag, pt_debug_closest_hit_host /
+ * _n, pt_debug_quad_info / _oct_info, pt_debug_clone_scene): the render path never pays for a host refit. */
+enum { PT_TREE_BINARY = 0, PT_TREE_QUAD = 1, PT_TREE_OCT = 2, PT_TREE_TRIS = 3, PT_TREE_INFO = 4, PT_TREE_DEVICE = 16 };
 int64_t pt_debug_export_tree(pt_ctx* ctx, int32_t which, void* out, int64_t cap);
+
+/* The last pt_update_vertices of this context: out = {device milliseconds from the first kernel to the last (HIP events; 0 on a host-only
+ * context), bytes copied host to device, triangles the sliver rule collapsed to points, the padding of the boxes, height levels of the
+ * binary tree (= refit launches), 0, 0, 0}; all 0 before the first update. */
+int pt_debug_update_info(pt_ctx* ctx, double out[8]);
 
 /* What pt_group_upload_scene does for devices 1..n-1: the scene `src` holds (BVH built once) copied into `dst` and uploaded to
  * dst's GPU.  Exposed so that a one-GPU box can test it with two contexts on the same device. */

@@ -102,7 +102,7 @@ void pt_destroy(pt_ctx* c)
         (void)hipSetDevice(c->device);
         (void)hipStreamSynchronize(c->stream);
         (void)pt_comm_destroy(c);
-        for (hipEvent_t e : {c->ev0, c->ev1, c->evm, c->evr, c->evd})
+        for (hipEvent_t e : {c->ev0, c->ev1, c->evm, c->evr, c->evd, c->evu0, c->evu1})
             if (e) (void)hipEventDestroy(e);
         if (c->stream) (void)hipStreamDestroy(c->stream);
     }
@@ -146,6 +146,10 @@ int pt_set_option(pt_ctx* c, const char* key, int64_t value)
         if (value != 0 && value != 1) return fail(c, PT_E_INVALID, "watertight must be 0 (Moeller-Trumbore, default) or 1 (watertight edge functions)");
         if (value == 1 && c->opt.kernel != 2) return fail(c, PT_E_INVALID, "watertight = 1: the lane-per-pixel kernel (option kernel = 1) has no watertight form; set kernel = 2 first");
         c->opt.watertight = (int)value;
+    }
+    else if (k == "dynamic") { // next pt_upload_scene: 1 = keep what pt_update_vertices needs (vertex arrays, indices, refit schedule), on the host and in HBM
+        if (value != 0 && value != 1) return fail(c, PT_E_INVALID, "dynamic must be 0 (default) or 1 (the next pt_upload_scene keeps what pt_update_vertices needs)");
+        c->opt.dynamic = (int)value;
     }
     else if (k == "quad") c->opt.quad = value != 0; // wavefront kernel: quad nodes (two binary levels per fetch), next pt_render
     else if (k == "node_pairs") c->opt.node_pairs = value != 0;

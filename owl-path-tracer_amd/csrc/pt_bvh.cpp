@@ -656,9 +656,9 @@ static void layout_align_leaves(PtBvh* b, int align)
 // replaced by its two children until four slots are used (as pt_bvh_collapse8 does for eight).  Against the fixed two-level collapse
 // below: no slot stays empty next to a leaf child while another slot could still be opened, and a large child is opened in preference
 // to a small one - fewer quad nodes on a ray's way (expected visits = sum over quad nodes of area(slot box) / area(root)).
-static void collapse4_by_area(const PtBvh& b, std::vector<PtNode4>* out, int32_t* root4, int* depth4)
+static void collapse4_by_area(const PtBvh& b, std::vector<PtNode4>* out, int32_t* root4, int* depth4, std::vector<int32_t>* src)
 {
-    struct Slot { float lo[3], hi[3]; int32_t ref; };
+    struct Slot { float lo[3], hi[3]; int32_t ref; int32_t src; };
     auto area = [](const Slot& s) {
         const float dx = s.hi[0] - s.lo[0], dy = s.hi[1] - s.lo[1], dz = s.hi[2] - s.lo[2];
         return dx * dy + dy * dz + dz * dx;
@@ -667,6 +667,7 @@ static void collapse4_by_area(const PtBvh& b, std::vector<PtNode4>* out, int32_t
         Slot s;
         for (int a = 0; a < 3; ++a) { s.lo[a] = nd.lo[a][side]; s.hi[a] = nd.hi[a][side]; }
         s.ref = side ? nd.right : nd.left;
+        s.src = (int32_t)(&nd - b.nodes.data()) * 2 + side;
         return s;
     };
     struct Item { int32_t node2; int32_t idx4; int depth; };
@@ -705,8 +706,10 @@ static void collapse4_by_area(const PtBvh& b, std::vector<PtNode4>* out, int32_t
         for (int a = 0; a < 3; ++a)
             for (int k = 0; k < 4; ++k) q.lo[a][k] = q.hi[a][k] = INFINITY; // never hit (empty slot)
         for (int k = 0; k < 4; ++k) { q.child[k] = -1; q.pad[k] = 0; }
+        if (src) src->resize(out->size() * 4, -1);
         for (int k = 0; k < n; ++k) {
             for (int a = 0; a < 3; ++a) { q.lo[a][k] = slots[k].lo[a]; q.hi[a][k] = slots[k].hi[a]; }
+            if (src) (*src)[(size_t)it.idx4 * 4 + (size_t)k] = slots[k].src;
             if (slots[k].ref >= 0) {
                 const int32_t idx = (int32_t)out->size();
                 out->emplace_back();
@@ -748,13 +751,18 @@ void pt_bvh_quad_cost(const std::vector<PtNode4>& nodes4, int32_t root4, double*
 #ifndef PT_COLLAPSE4_BY_AREA
 #define PT_COLLAPSE4_BY_AREA 0 // measured (profiles/r04_notes.md): 2-10 % fewer quad steps, no time gained (C5 +1.5 %): off
 #endif
-void pt_bvh_collapse4(const PtBvh& b, std::vector<PtNode4>* out, int32_t* root4, int* depth4)
+void pt_bvh_collapse4(const PtBvh& b, std::vector<PtNode4>* out, int32_t* root4, int* depth4, std::vector<int32_t>* src)
 {
     out->clear();
+    if (src) src->clear();
     *root4 = b.root;
     *depth4 = 0;
     if (b.root < 0) return; // empty scene or a leaf as root: no quad nodes
-    if (PT_COLLAPSE4_BY_AREA) { collapse4_by_area(b, out, root4, depth4); return; } // (A/B: make variant FLAGS=-DPT_COLLAPSE4_BY_AREA=1)
+    if (PT_COLLAPSE4_BY_AREA) { // (A/B: make variant FLAGS=-DPT_COLLAPSE4_BY_AREA=1)
+        collapse4_by_area(b, out, root4, depth4, src);
+        if (src) src->resize(out->size() * 4, -1);
+        return;
+    }
     struct Item { int32_t node2; int32_t idx4; int depth; };
     std::vector<Item> todo;
     out->emplace_back();
@@ -769,6 +777,7 @@ void pt_bvh_collapse4(const PtBvh& b, std::vector<PtNode4>* out, int32_t* root4,
         for (int a = 0; a < 3; ++a)
             for (int k = 0; k < 4; ++k) q.lo[a][k] = q.hi[a][k] = INFINITY; // never hit (empty slot)
         for (int k = 0; k < 4; ++k) { q.child[k] = -1; q.pad[k] = 0; }
+        int32_t from[4] = {-1, -1, -1, -1}; // the binary (node, side) a slot's box is a copy of: 2 * node + side
         for (int side = 0; side < 2; ++side) {
             const int32_t c = side ? nd.right : nd.left;
             if (c >= 0) { // internal child: its two children take the slots of this side
@@ -777,6 +786,7 @@ void pt_bvh_collapse4(const PtBvh& b, std::vector<PtNode4>* out, int32_t* root4,
                     const int slot = side * 2 + s2;
                     const int32_t gc = s2 ? cn.right : cn.left;
                     for (int a = 0; a < 3; ++a) { q.lo[a][slot] = cn.lo[a][s2]; q.hi[a][slot] = cn.hi[a][s2]; }
+                    from[slot] = c * 2 + s2;
                     if (gc >= 0) {
                         const int32_t idx = (int32_t)out->size();
                         out->emplace_back();
@@ -789,20 +799,26 @@ void pt_bvh_collapse4(const PtBvh& b, std::vector<PtNode4>* out, int32_t* root4,
             } else if (c < -1) { // leaf child: keeps its own box
                 const int slot = side * 2;
                 for (int a = 0; a < 3; ++a) { q.lo[a][slot] = nd.lo[a][side]; q.hi[a][slot] = nd.hi[a][side]; }
+                from[slot] = it.node2 * 2 + side;
                 q.child[slot] = c;
             }
         }
         (*out)[(size_t)it.idx4] = q;
+        if (src) {
+            src->resize(out->size() * 4, -1);
+            for (int k = 0; k < 4; ++k) (*src)[(size_t)it.idx4 * 4 + (size_t)k] = from[k];
+        }
     }
 }
 
-void pt_bvh_collapse8(const PtBvh& b, int wide_leaves, std::vector<PtNode8>* out, int32_t* root8, int* depth8)
+void pt_bvh_collapse8(const PtBvh& b, int wide_leaves, std::vector<PtNode8>* out, int32_t* root8, int* depth8, std::vector<int32_t>* src)
 {
     out->clear();
+    if (src) src->clear();
     *root8 = b.root;
     *depth8 = 0;
     if (b.root < 0) return; // empty scene or a leaf as root: no oct nodes
-    struct Slot { float lo[3], hi[3]; int32_t ref; };
+    struct Slot { float lo[3], hi[3]; int32_t ref; int32_t src; };
     auto area = [](const Slot& s) {
         const float dx = s.hi[0] - s.lo[0], dy = s.hi[1] - s.lo[1], dz = s.hi[2] - s.lo[2];
         return dx * dy + dy * dz + dz * dx;
@@ -844,6 +860,7 @@ void pt_bvh_collapse8(const PtBvh& b, int wide_leaves, std::vector<PtNode8>* out
         Slot s;
         for (int a = 0; a < 3; ++a) { s.lo[a] = nd.lo[a][side]; s.hi[a] = nd.hi[a][side]; }
         s.ref = side ? nd.right : nd.left;
+        s.src = (int32_t)(&nd - b.nodes.data()) * 2 + side; // (a wide leaf keeps the box of the subtree it replaces: this slot's as well)
         if (wide_leaves && s.ref >= 0 && sub[(size_t)s.ref].count) s.ref = (int32_t)~((sub[(size_t)s.ref].first << 3) | sub[(size_t)s.ref].count);
         return s;
     };
@@ -882,8 +899,10 @@ void pt_bvh_collapse8(const PtBvh& b, int wide_leaves, std::vector<PtNode8>* out
             q.c[k].ref = -1;
             q.c[k].pad = 0;
         }
+        if (src) src->resize(out->size() * 8, -1);
         for (int k = 0; k < n; ++k) {
             for (int a = 0; a < 3; ++a) { q.c[k].lo[a] = slots[k].lo[a]; q.c[k].hi[a] = slots[k].hi[a]; }
+            if (src) (*src)[(size_t)it.idx8 * 8 + (size_t)k] = slots[k].src;
             if (slots[k].ref >= 0) {
                 const int32_t idx = (int32_t)out->size();
                 out->emplace_back();
@@ -895,6 +914,7 @@ void pt_bvh_collapse8(const PtBvh& b, int wide_leaves, std::vector<PtNode8>* out
         }
         (*out)[(size_t)it.idx8] = q;
     }
+    if (src) src->resize(out->size() * 8, -1);
 }
 
 void pt_bvh_layout(PtBvh* b, int sibling_pairs, int leaf_align)
@@ -1038,6 +1058,118 @@ bool pt_bvh_from_hierarchy(const float* positions, int32_t n_tris, const int32_t
     };
     out->root = emit(emit, root, 1);
     return !too_deep && (int32_t)out->tris.size() == n_tris;
+}
+
+// ---- refit (option "dynamic", pt_update_vertices): new boxes for an unchanged topology --------------------------------------------
+// Every stored box is the exact float32 min / max of the vertices below it, then one float32 -/+ pad (Builder::store); min / max are
+// exact and rounding is monotone, so min(a - pad, b - pad) == min(a, b) - pad bit for bit: a parent's box for an internal child is the
+// plain union of that child's two stored, already padded boxes, and a bottom-up pass gives the boxes the builder would have stored for
+// this topology and these vertices.  The device does the same four steps (pt_refit.hip); this is its host twin.
+
+// Height of every binary node (1 = both children are leaves; 0 = not reachable from the root: the holes of the sibling-pair layout) and
+// the reachable nodes sorted by height: level l = level_nodes[level_ofs[l] .. level_ofs[l + 1]) holds the nodes of height l + 1, whose
+// internal children all lie in lower levels.
+void pt_bvh_refit_schedule(const PtBvh& b, PtRefit* r)
+{
+    r->height.assign(b.nodes.size(), 0);
+    r->level_nodes.clear();
+    r->level_ofs.assign(1, 0);
+    if (b.root < 0) return;
+    std::vector<int32_t> order; // parents before children
+    order.reserve(b.nodes.size());
+    std::vector<int32_t> st{b.root};
+    while (!st.empty()) {
+        const int32_t i = st.back();
+        st.pop_back();
+        order.push_back(i);
+        if (b.nodes[(size_t)i].left >= 0) st.push_back(b.nodes[(size_t)i].left);
+        if (b.nodes[(size_t)i].right >= 0) st.push_back(b.nodes[(size_t)i].right);
+    }
+    int levels = 0;
+    for (size_t k = order.size(); k-- > 0;) {
+        const PtNode& nd = b.nodes[(size_t)order[k]];
+        const int hl = nd.left >= 0 ? r->height[(size_t)nd.left] : 0, hr = nd.right >= 0 ? r->height[(size_t)nd.right] : 0;
+        const int h = 1 + std::max(hl, hr);
+        r->height[(size_t)order[k]] = h;
+        levels = std::max(levels, h);
+    }
+    r->level_ofs.assign((size_t)levels + 1, 0);
+    for (int32_t i : order) r->level_ofs[(size_t)r->height[(size_t)i]]++; // nodes of height h counted at [h], h >= 1
+    for (int l = 0; l < levels; ++l) r->level_ofs[(size_t)l + 1] += r->level_ofs[(size_t)l];
+    std::vector<int32_t> fill(r->level_ofs.begin(), r->level_ofs.end() - 1);
+    r->level_nodes.resize(order.size());
+    for (int32_t i : order) r->level_nodes[(size_t)fill[(size_t)r->height[(size_t)i] - 1]++] = i;
+}
+
+namespace {
+inline float rmin(float a, float b) { return b < a ? b : a; } // (the vertices are finite after the sliver rule: no NaN to order)
+inline float rmax(float a, float b) { return b > a ? b : a; }
+} // namespace
+
+void pt_bvh_refit(PtBvh* b, const PtRefit& r, std::vector<PtNode4>* nodes4, std::vector<PtNode8>* nodes8)
+{
+    // extent over the (collapsed) triangles, not over the vertex array: an unreferenced vertex does not move the pad; as pt_bvh_build
+    float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (const PtTri& t : b->tris) {
+        if (t.id == 0x7fffffff) continue;
+        for (int a = 0; a < 3; ++a) {
+            mn[a] = rmin(mn[a], rmin(t.p0[a], rmin(t.p1[a], t.p2[a])));
+            mx[a] = rmax(mx[a], rmax(t.p0[a], rmax(t.p1[a], t.p2[a])));
+        }
+    }
+    float ext = 0.0f;
+    if (mn[0] <= mx[0])
+        for (int a = 0; a < 3; ++a) {
+            ext = std::max(ext, mx[a] - mn[a]);
+            ext = std::max(ext, std::max(std::fabs(mn[a]), std::fabs(mx[a])));
+        }
+    const float pad = ext * 1e-5f;
+    b->pad = pad;
+    const size_t levels = r.level_ofs.empty() ? 0 : r.level_ofs.size() - 1;
+    for (size_t l = 0; l < levels; ++l) {
+        const int32_t* list = r.level_nodes.data() + r.level_ofs[l];
+        pt_parallel_ranges((size_t)(r.level_ofs[l + 1] - r.level_ofs[l]), [&](size_t lo, size_t hi) {
+            for (size_t k = lo; k < hi; ++k) {
+                PtNode& nd = b->nodes[(size_t)list[k]];
+                for (int side = 0; side < 2; ++side) {
+                    const int32_t c = side ? nd.right : nd.left;
+                    if (c >= 0) { // internal child: the union of its two stored boxes, no further pad
+                        const PtNode& cn = b->nodes[(size_t)c];
+                        for (int a = 0; a < 3; ++a) { nd.lo[a][side] = rmin(cn.lo[a][0], cn.lo[a][1]); nd.hi[a][side] = rmax(cn.hi[a][0], cn.hi[a][1]); }
+                    } else if (c < -1) { // leaf child: the bounds of its triangles, -/+ pad
+                        const uint32_t code = ~(uint32_t)c, first = code >> 3, count = code & 7u;
+                        float lmn[3] = {INFINITY, INFINITY, INFINITY}, lmx[3] = {-INFINITY, -INFINITY, -INFINITY};
+                        for (uint32_t i = first; i < first + count; ++i) {
+                            const PtTri& t = b->tris[i];
+                            if (t.id == 0x7fffffff) continue;
+                            for (int a = 0; a < 3; ++a) {
+                                lmn[a] = rmin(lmn[a], rmin(t.p0[a], rmin(t.p1[a], t.p2[a])));
+                                lmx[a] = rmax(lmx[a], rmax(t.p0[a], rmax(t.p1[a], t.p2[a])));
+                            }
+                        }
+                        for (int a = 0; a < 3; ++a) { nd.lo[a][side] = lmn[a] - pad; nd.hi[a][side] = lmx[a] + pad; }
+                    }
+                }
+            }
+        });
+    }
+    // quad and oct slots copy the box of their binary (node, side); empty slots keep {+inf, +inf}
+    if (nodes4)
+        for (size_t s = 0; s < r.src4.size() && s < nodes4->size() * 4; ++s) {
+            const int32_t from = r.src4[s];
+            if (from < 0) continue;
+            const PtNode& nd = b->nodes[(size_t)(from >> 1)];
+            PtNode4& q = (*nodes4)[s >> 2];
+            for (int a = 0; a < 3; ++a) { q.lo[a][s & 3] = nd.lo[a][from & 1]; q.hi[a][s & 3] = nd.hi[a][from & 1]; }
+        }
+    if (nodes8)
+        for (size_t s = 0; s < r.src8.size() && s < nodes8->size() * 8; ++s) {
+            const int32_t from = r.src8[s];
+            if (from < 0) continue;
+            const PtNode& nd = b->nodes[(size_t)(from >> 1)];
+            PtNode8::Child& ch = (*nodes8)[s >> 3].c[s & 7];
+            for (int a = 0; a < 3; ++a) { ch.lo[a] = nd.lo[a][from & 1]; ch.hi[a] = nd.hi[a][from & 1]; }
+        }
 }
 
 // ---- host mirror of the kernel traversal (validation of the builder; same arithmetic as pt_kernel.hip) ----

@@ -242,6 +242,13 @@ int pt_group_set_materials(pt_group* g, const float* materials, int32_t n_materi
     return PT_OK;
 }
 
+int pt_group_update_vertices(pt_group* g, const pt_mesh* meshes, int32_t n_meshes)
+{
+    if (!g) return PT_E_INVALID;
+    GROUP_EACH(g, pt_update_vertices(c_, meshes, n_meshes)); // every device refits its own replica: nothing is rebuilt or cloned
+    return PT_OK;
+}
+
 int pt_group_set_option(pt_group* g, const char* key, int64_t value)
 {
     if (!g) return PT_E_INVALID;

@@ -27,6 +27,18 @@ struct HostTexture {
     std::vector<uint32_t> px;
 };
 
+// What an upload with option "dynamic" = 1 keeps beside the scene so that pt_update_vertices can move its vertices (pt_scene.cpp).
+struct DynScene {
+    bool enabled = false;
+    std::vector<float> verts, normals;                   // the meshes' arrays, concatenated; mesh m starts at vbase[m] / nbase[m] (elements of 3 floats)
+    std::vector<int32_t> vbase, nbase, n_verts, n_normals; // per mesh, counts as pt_upload_scene was given them
+    PtRefit refit;
+    // a device context refits in HBM only: the host copies (triangle records, three hierarchies, and the shading normals when
+    // stale_normals) are brought up to date by the first call that reads them (pti::sync_host_scene)
+    bool host_stale = false, stale_normals = false;
+    double info[8] = {};                                 // pt_debug_update_info
+};
+
 // The host copies of an uploaded scene: everything a replica of a multi-GPU group takes over from device 0 (pti::clone_scene is one
 // assignment of this), and the four figures of pt_stats that describe it.
 struct HostScene {
@@ -46,11 +58,12 @@ struct HostScene {
     HostTexture env_map;
     uint64_t bvh_nodes = 0, bvh_depth = 0, n_triangles = 0; // pt_stats
     double bvh_build_ms = 0.0;
+    DynScene dyn;
 };
 
 // pt_set_option: every option with its default.
 struct PtOptions {
-    int spp_per_launch = 0, count = 0, blocks_per_cu = 0, leaf_size = 4, max_bvh_depth = 48, kernel = 2, slots_per_wave = 0, chunk_spp = 64, chunk_tail_min = -1, schedule = 1, prepass_spp = 0, census_mode = 0, sticky_pct = -1, latency = 0, cost_radius = 2, timeline = 0, node_pairs = 0, leaf_align = 1, bvh_builder = 3, quad = 1, groups = 1, wide_leaves = 1, fallback = 0, ploc_radius = 16, express_permille = -1, ns_express = 8, whole = -1, box_exact = -1, batch_frames = 0, watertight = 0;
+    int spp_per_launch = 0, count = 0, blocks_per_cu = 0, leaf_size = 4, max_bvh_depth = 48, kernel = 2, slots_per_wave = 0, chunk_spp = 64, chunk_tail_min = -1, schedule = 1, prepass_spp = 0, census_mode = 0, sticky_pct = -1, latency = 0, cost_radius = 2, timeline = 0, node_pairs = 0, leaf_align = 1, bvh_builder = 3, quad = 1, groups = 1, wide_leaves = 1, fallback = 0, ploc_radius = 16, express_permille = -1, ns_express = 8, whole = -1, box_exact = -1, batch_frames = 0, watertight = 0, dynamic = 0;
     int tune[8] = {};
 };
 
@@ -79,6 +92,7 @@ struct pt_ctx {
     bool host_only = false;
     int num_cus = 0;
     hipStream_t stream = nullptr;
+    hipEvent_t evu0 = nullptr, evu1 = nullptr; // around the kernels of the last pt_update_vertices (created by the first one)
     hipEvent_t ev0 = nullptr, ev1 = nullptr, evm = nullptr, evr = nullptr, evd = nullptr; // evm: after the cost pre-pass and the queue sort; evr / evd: after the reduce / the read-back of pt_render
     std::string err;
 
@@ -87,6 +101,7 @@ struct pt_ctx {
 
     // device
     DevBuf d_nodes8, d_nodes4, d_nodes, d_tris, d_shade, d_materials, d_texdesc, d_env, d_pixels, d_heads, d_rng, d_accum, d_out, d_out8, d_counters, d_dbg_in, d_dbg_out, d_slots, d_laps, d_ring, d_params, d_cost, d_sorted, d_sort_scratch, d_dbg_start, d_bucket, d_tiers, d_batch_mats, d_batch_cams, d_seq_flags; // d_batch_*: per-frame tables of pt_render_batch; d_seq_flags: watchdog flags of its earlier launch sequences
+    DevBuf d_verts, d_vnormals, d_tri_vi, d_level_nodes, d_src4, d_src8, d_refit_ws; // option "dynamic": what the refit kernels read (pt_refit.hip)
     std::vector<DevBuf> d_textures;
 
     // pixel queue
@@ -117,6 +132,7 @@ PT_LOCAL int need_device(pt_ctx* c);
 // pt_scene.cpp
 int upload_scene_to_device(pt_ctx* c);
 int clone_scene(pt_ctx* dst, const pt_ctx* src);
+PT_LOCAL void sync_host_scene(pt_ctx* c); // after a pt_update_vertices on the device: the host copies refitted, if they are stale
 PT_LOCAL void material_row(const pt_ctx* c, float* dst, const float* src, int i);
 // pt_render.cpp
 int check_watchdog(pt_ctx* c);

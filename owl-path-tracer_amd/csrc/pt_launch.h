@@ -27,7 +27,29 @@ enum { PT_PROBE_FIRST = 30, PT_PROBE_QUAD = 30, PT_PROBE_QUAD_OVF = 32, PT_PROBE
 #define PT_PROBE_GROUP_SLOTS 24 // path slots of a wave of the group probe: three rays per group, so groups park and resume
 #define PT_PROBE_GROUP_RAYS 100 // rays per wave of the group probe: neither a multiple of 8 nor of 64
 
+// pt_refit.hip: the device side of pt_update_vertices.  Device pointers except level_ofs (host: n_levels + 1 offsets into level_nodes).
+#define PT_REFIT_PARTIALS 1024 // blocks of the first stage of the extent reduction, at most
+struct PtRefitArgs {
+    PtNode* nodes;
+    PtNode4* nodes4;
+    PtNode8* nodes8;
+    PtTri* tris;
+    PtShade* shade;
+    const float* verts;           // the concatenated vertex arrays of the meshes
+    const float* normals;         // the concatenated normal arrays; null: the shading records keep their normals
+    const int32_t* tri_vi;        // 4 per leaf-order slot (PtRefit::tri_vi, pt_bvh.h)
+    const int32_t* level_nodes;   // binary nodes sorted by height
+    const int32_t* src4;          // per quad slot: 2 * node + side of the binary box it copies, -1 empty
+    const int32_t* src8;          // per oct slot
+    float* ws;                    // pt_refit_workspace_bytes(): [0] = pad, [1] = collapsed slivers (uint32) once the launches have run
+    const int32_t* level_ofs;
+    int32_t n_slots, n_levels, n_slots4, n_slots8;
+};
+
 extern "C" {
+size_t pt_refit_workspace_bytes(void);
+// gather, extent, one refit launch per level, propagate - all on `stream`, `first` recorded before the first kernel, `last` after the last
+hipError_t pt_launch_refit(const PtRefitArgs* a, hipEvent_t first, hipEvent_t last, hipStream_t stream);
 // scratch: quad probe with overflow: the waves' HBM stack columns; group probe: the waves' park areas (pt_probe_group_state_words each)
 hipError_t pt_launch_probe(const PtKernelParams* p, int op, const float* in, int in_stride, float* out, int out_stride, long long n, int grid, size_t lds_bytes,
                            uint32_t* scratch, hipStream_t stream);

@@ -238,13 +238,15 @@ void layout_and_collapse(pt_ctx* c)
     HostScene& s = c->scene;
     pt_bvh_layout(&s.bvh, c->opt.node_pairs, c->opt.leaf_align);
     s.bvh_nodes = s.bvh.nodes.size();
+    std::vector<int32_t>* src4 = s.dyn.enabled ? &s.dyn.refit.src4 : nullptr; // option "dynamic": which binary box every slot copies
+    std::vector<int32_t>* src8 = s.dyn.enabled ? &s.dyn.refit.src8 : nullptr;
     { // the two collapses only read the binary tree: side by side
-        std::thread oct([&] { pt_bvh_collapse8(s.bvh, c->opt.wide_leaves, &s.nodes8, &s.root8, &s.depth8); });
-        pt_bvh_collapse4(s.bvh, &s.nodes4, &s.root4, &s.depth4);
+        std::thread oct([&] { pt_bvh_collapse8(s.bvh, c->opt.wide_leaves, &s.nodes8, &s.root8, &s.depth8, src8); });
+        pt_bvh_collapse4(s.bvh, &s.nodes4, &s.root4, &s.depth4, src4);
         oct.join();
     }
-    if (3 * s.depth4 + 1 > PT_MAX_STACK) s.nodes4.clear(); // the quad walk could need more stack than the kernel has: binary walk instead
-    if (7 * s.depth8 + 1 > PT_GROUP_STACK) s.nodes8.clear(); // a group's stack (eight LDS stack columns) could overflow: no group walk
+    if (3 * s.depth4 + 1 > PT_MAX_STACK) { s.nodes4.clear(); s.dyn.refit.src4.clear(); } // the quad walk could need more stack than the kernel has: binary walk instead
+    if (7 * s.depth8 + 1 > PT_GROUP_STACK) { s.nodes8.clear(); s.dyn.refit.src8.clear(); } // a group's stack (eight LDS stack columns) could overflow: no group walk
 }
 
 // shading records in leaf order (padding slots included), gathered from the caller's arrays: the three vertex normals and
@@ -277,6 +279,74 @@ void shading_records(pt_ctx* c, const pt_mesh* meshes, const std::vector<size_t>
     });
 }
 
+// Option "dynamic" = 1: what pt_update_vertices needs beside the scene - the meshes' vertex and normal arrays, concatenated, with
+// per-mesh bases; per leaf-order slot its three vertex indices with the base folded in; the refit schedule of the binary tree.  (The
+// collapses have already noted which binary box every quad / oct slot copies: layout_and_collapse.)
+int retain_dynamic(pt_ctx* c, const pt_mesh* meshes, int32_t n_meshes, const std::vector<size_t>& mesh_first)
+{
+    HostScene& s = c->scene;
+    DynScene& d = s.dyn;
+    if (!d.enabled) return PT_OK;
+    size_t nv = 0, nn = 0;
+    for (int m = 0; m < n_meshes; ++m) {
+        d.vbase.push_back((int32_t)nv);
+        d.nbase.push_back((int32_t)nn);
+        d.n_verts.push_back(meshes[m].n_vertices);
+        d.n_normals.push_back(meshes[m].n_normals);
+        nv += (size_t)std::max(0, meshes[m].n_vertices);
+        nn += (size_t)std::max(0, meshes[m].n_normals);
+        if (nv > 0x7fffffffull || nn > 0x7fffffffull) return fail(c, PT_E_LIMIT, "option \"dynamic\": more than 2^31 vertices or normals");
+    }
+    d.verts.assign(nv * 3, 0.0f);
+    d.normals.assign(nn * 3, 0.0f);
+    for (int m = 0; m < n_meshes; ++m) {
+        if (meshes[m].vertices && meshes[m].n_vertices > 0) std::memcpy(&d.verts[(size_t)d.vbase[(size_t)m] * 3], meshes[m].vertices, (size_t)meshes[m].n_vertices * 12);
+        if (meshes[m].normals && meshes[m].n_normals > 0) std::memcpy(&d.normals[(size_t)d.nbase[(size_t)m] * 3], meshes[m].normals, (size_t)meshes[m].n_normals * 12);
+    }
+    const size_t n_slots = s.bvh.tris.size();
+    d.refit.tri_vi.assign(n_slots * 4, -1);
+    pt_parallel_ranges(n_slots, [&](size_t lo, size_t hi) {
+        for (size_t i = lo; i < hi; ++i) {
+            const int32_t id = s.bvh.tris[i].id;
+            if (id == 0x7fffffff) continue;
+            const int m = (int)(std::upper_bound(mesh_first.begin(), mesh_first.end(), (size_t)id) - mesh_first.begin()) - 1;
+            const size_t t = (size_t)id - mesh_first[(size_t)m];
+            for (int k = 0; k < 3; ++k) d.refit.tri_vi[i * 4 + (size_t)k] = d.vbase[(size_t)m] + meshes[m].indices[t * 3 + (size_t)k]; // validated by flatten_meshes
+            d.refit.tri_vi[i * 4 + 3] = d.nbase[(size_t)m] - d.vbase[(size_t)m];
+        }
+    });
+    pt_bvh_refit_schedule(s.bvh, &d.refit);
+    return PT_OK;
+}
+
+// Step 1 of an update on the host copies: every live slot's vertices through the retained indices, the sliver rule, p0..p2 of its
+// PtTri - and n0..n2 of its PtShade with `normals`.  Returns the number of triangles that are points afterwards (collapsed slivers).
+size_t gather_host(pt_ctx* c, bool normals)
+{
+    HostScene& s = c->scene;
+    const DynScene& d = s.dyn;
+    std::atomic<size_t> points{0};
+    pt_parallel_ranges(s.bvh.tris.size(), [&](size_t lo, size_t hi) {
+        size_t n_points = 0;
+        for (size_t i = lo; i < hi; ++i) {
+            PtTri& tr = s.bvh.tris[i];
+            if (tr.id == 0x7fffffff) continue;
+            const int32_t* vi = &d.refit.tri_vi[i * 4];
+            float p[9];
+            for (int k = 0; k < 3; ++k) std::memcpy(p + 3 * k, &d.verts[(size_t)vi[k] * 3], 12);
+            pt_collapse_sliver(p);
+            std::memcpy(tr.p0, p, 36);
+            n_points += (p[0] == p[3] && p[0] == p[6] && p[1] == p[4] && p[1] == p[7] && p[2] == p[5] && p[2] == p[8]) ? 1 : 0;
+            if (normals) {
+                PtShade& sh = s.shade[i];
+                for (int k = 0; k < 3; ++k) std::memcpy(k == 0 ? sh.n0 : (k == 1 ? sh.n1 : sh.n2), &d.normals[(size_t)((long long)vi[k] + vi[3]) * 3], 12);
+            }
+        }
+        points += n_points;
+    });
+    return points.load();
+}
+
 // Host copies of the textures, the material table and the environment.
 void copy_tables(pt_ctx* c, const float* materials, int32_t n_materials, const pt_texture* textures, int32_t n_textures, const pt_env* env)
 {
@@ -298,6 +368,8 @@ extern "C" int pt_upload_scene(pt_ctx* c, const pt_mesh* meshes, int32_t n_meshe
     // from here on the context has NO scene until the upload has succeeded (a failure half way must not leave the previous scene's flag
     // over new host arrays)
     c->have_scene = false;
+    c->scene.dyn = DynScene{};
+    c->scene.dyn.enabled = c->opt.dynamic != 0;
     if (!c->host_only) HIP_TRY(c, hipSetDevice(c->device));
     // PT_UPLOAD_TRACE=1: phase times of this call on stderr
     const bool trace = getenv("PT_UPLOAD_TRACE") && getenv("PT_UPLOAD_TRACE")[0] == '1';
@@ -326,6 +398,7 @@ extern "C" int pt_upload_scene(pt_ctx* c, const pt_mesh* meshes, int32_t n_meshe
     phase("quad + oct nodes");
     shading_records(c, meshes, mesh_first);
     phase("shading records");
+    if ((rc = retain_dynamic(c, meshes, n_meshes, mesh_first))) return rc;
     copy_tables(c, materials, n_materials, textures, n_textures, env);
     if (!c->host_only && (rc = upload_scene_to_device(c))) return rc;
     phase("textures, upload to HBM");
@@ -354,6 +427,15 @@ int upload_scene_to_device(pt_ctx* c)
     if ((rc = upload(c, c->d_nodes8, c->scene.nodes8.data(), c->scene.nodes8.size() * sizeof(PtNode8)))) return rc;
     if ((rc = upload(c, c->d_tris, c->scene.bvh.tris.data(), c->scene.bvh.tris.size() * sizeof(PtTri)))) return rc;
     if ((rc = upload(c, c->d_shade, c->scene.shade.data(), c->scene.shade.size() * sizeof(PtShade)))) return rc;
+    if (const DynScene& d = c->scene.dyn; d.enabled) { // what the refit kernels read (pt_refit.hip)
+        if ((rc = upload(c, c->d_verts, d.verts.data(), d.verts.size() * sizeof(float)))) return rc;
+        if ((rc = upload(c, c->d_vnormals, d.normals.data(), d.normals.size() * sizeof(float)))) return rc;
+        if ((rc = upload(c, c->d_tri_vi, d.refit.tri_vi.data(), d.refit.tri_vi.size() * 4))) return rc;
+        if ((rc = upload(c, c->d_level_nodes, d.refit.level_nodes.data(), d.refit.level_nodes.size() * 4))) return rc;
+        if ((rc = upload(c, c->d_src4, d.refit.src4.data(), d.refit.src4.size() * 4))) return rc;
+        if ((rc = upload(c, c->d_src8, d.refit.src8.data(), d.refit.src8.size() * 4))) return rc;
+        if ((rc = ensure(c, c->d_refit_ws, pt_refit_workspace_bytes()))) return rc;
+    }
     c->d_textures.clear();
     std::vector<PtTexDesc> descs((size_t)n_textures);
     for (int i = 0; i < n_textures; ++i) {
@@ -375,6 +457,7 @@ int upload_scene_to_device(pt_ctx* c)
 int clone_scene(pt_ctx* dst, const pt_ctx* src)
 {
     if (!src->have_scene) return fail(dst, PT_E_NO_SCENE, "clone_scene: the source context has no scene");
+    sync_host_scene(const_cast<pt_ctx*>(src)); // (the host copies are a cache of what the source's device holds after an update)
     dst->scene = src->scene;
     dst->have_scene = true;
     dst->queue_valid = false;
@@ -382,9 +465,107 @@ int clone_scene(pt_ctx* dst, const pt_ctx* src)
     return upload_scene_to_device(dst);
 }
 
+// After pt_update_vertices on a device context only HBM holds the moved scene: the host twin of the refit runs when somebody reads the
+// host copies (the product path never does).
+void sync_host_scene(pt_ctx* c)
+{
+    DynScene& d = c->scene.dyn;
+    if (!d.enabled || !d.host_stale) return;
+    (void)gather_host(c, d.stale_normals);
+    pt_bvh_refit(&c->scene.bvh, d.refit, &c->scene.nodes4, &c->scene.nodes8);
+    d.host_stale = d.stale_normals = false;
+}
+
 } // namespace pti
 
 extern "C" {
+
+int pt_update_vertices(pt_ctx* c, const pt_mesh* meshes, int32_t n_meshes)
+{
+    if (!c) return PT_E_INVALID;
+    if (!c->have_scene) return fail(c, PT_E_NO_SCENE, "pt_update_vertices before pt_upload_scene");
+    HostScene& s = c->scene;
+    DynScene& d = s.dyn;
+    // everything is checked before anything is touched
+    if (!d.enabled) return fail(c, PT_E_INVALID, "pt_update_vertices: the scene was not uploaded with option \"dynamic\" = 1");
+    if (n_meshes != (int32_t)d.vbase.size()) return fail(c, PT_E_INVALID, "pt_update_vertices: %d meshes, the scene was uploaded with %zu", n_meshes, d.vbase.size());
+    if (n_meshes > 0 && !meshes) return fail(c, PT_E_INVALID, "pt_update_vertices: null mesh array with non-zero count");
+    for (int m = 0; m < n_meshes; ++m)
+        if (meshes[m].n_vertices != d.n_verts[(size_t)m] || meshes[m].n_normals != d.n_normals[(size_t)m])
+            return fail(c, PT_E_INVALID, "pt_update_vertices: mesh %d has %d vertices / %d normals, the scene was uploaded with %d / %d", m, meshes[m].n_vertices,
+                        meshes[m].n_normals, d.n_verts[(size_t)m], d.n_normals[(size_t)m]);
+    if (!c->host_only) { // after the frames in flight, as upload_between_frames
+        HIP_TRY(c, hipSetDevice(c->device));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        if (!c->evu0) HIP_TRY(c, hipEventCreate(&c->evu0));
+        if (!c->evu1) HIP_TRY(c, hipEventCreate(&c->evu1));
+    }
+    // the host keeps the new arrays (the caller owns its input); the device gets the ranges that changed
+    bool any_normals = false;
+    double h2d = 0.0;
+    for (int m = 0; m < n_meshes; ++m) {
+        const pt_mesh& ms = meshes[m];
+        if (ms.vertices && ms.n_vertices > 0) {
+            float* dst = &d.verts[(size_t)d.vbase[(size_t)m] * 3];
+            const size_t bytes = (size_t)ms.n_vertices * 12;
+            std::memcpy(dst, ms.vertices, bytes);
+            if (!c->host_only) {
+                HIP_TRY(c, hipMemcpyAsync((char*)c->d_verts.p + (size_t)d.vbase[(size_t)m] * 12, dst, bytes, hipMemcpyHostToDevice, c->stream));
+                h2d += (double)bytes;
+            }
+        }
+        if (ms.normals && ms.n_normals > 0) {
+            float* dst = &d.normals[(size_t)d.nbase[(size_t)m] * 3];
+            const size_t bytes = (size_t)ms.n_normals * 12;
+            std::memcpy(dst, ms.normals, bytes);
+            any_normals = true;
+            if (!c->host_only) {
+                HIP_TRY(c, hipMemcpyAsync((char*)c->d_vnormals.p + (size_t)d.nbase[(size_t)m] * 12, dst, bytes, hipMemcpyHostToDevice, c->stream));
+                h2d += (double)bytes;
+            }
+        }
+    }
+    const int levels = d.refit.level_ofs.empty() ? 0 : (int)d.refit.level_ofs.size() - 1;
+    double ms_dev = 0.0, slivers = 0.0;
+    if (c->host_only) { // the host twin is the update
+        slivers = (double)gather_host(c, any_normals);
+        pt_bvh_refit(&s.bvh, d.refit, &s.nodes4, &s.nodes8);
+    } else {
+        PtRefitArgs a{};
+        a.nodes = (PtNode*)c->d_nodes.p; a.nodes4 = (PtNode4*)c->d_nodes4.p; a.nodes8 = (PtNode8*)c->d_nodes8.p;
+        a.tris = (PtTri*)c->d_tris.p; a.shade = (PtShade*)c->d_shade.p;
+        a.verts = (const float*)c->d_verts.p; a.normals = any_normals ? (const float*)c->d_vnormals.p : nullptr;
+        a.tri_vi = (const int32_t*)c->d_tri_vi.p; a.level_nodes = (const int32_t*)c->d_level_nodes.p;
+        a.src4 = (const int32_t*)c->d_src4.p; a.src8 = (const int32_t*)c->d_src8.p;
+        a.ws = (float*)c->d_refit_ws.p;
+        a.level_ofs = d.refit.level_ofs.data();
+        a.n_slots = (int32_t)s.bvh.tris.size(); a.n_levels = levels;
+        a.n_slots4 = (int32_t)std::min(s.nodes4.size() * 4, d.refit.src4.size()); a.n_slots8 = (int32_t)std::min(s.nodes8.size() * 8, d.refit.src8.size());
+        hipError_t e = pt_launch_refit(&a, c->evu0, c->evu1, c->stream);
+        if (e != hipSuccess) return fail(c, PT_E_HIP, "pt_update_vertices: refit launch failed: %s", hipGetErrorString(e));
+        uint32_t down[2] = {0, 0}; // pad (float bits), collapsed slivers
+        if (a.n_slots > 0) HIP_TRY(c, hipMemcpyAsync(down, c->d_refit_ws.p, sizeof(down), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        float ms = 0.0f;
+        HIP_TRY(c, hipEventElapsedTime(&ms, c->evu0, c->evu1));
+        ms_dev = ms;
+        std::memcpy(&s.bvh.pad, &down[0], 4); // walk_params and the automatic box_exact decision read the host's pad
+        slivers = (double)down[1];
+        d.host_stale = true;
+        d.stale_normals = d.stale_normals || any_normals;
+    }
+    c->queue_valid = false; // whatever is cached per geometry
+    const double info[8] = {ms_dev, h2d, slivers, (double)s.bvh.pad, (double)levels, 0.0, 0.0, 0.0};
+    std::memcpy(d.info, info, sizeof(info));
+    return PT_OK;
+}
+
+int pt_debug_update_info(pt_ctx* c, double out[8])
+{
+    if (!c || !out) return PT_E_INVALID;
+    std::memcpy(out, c->scene.dyn.info, sizeof(c->scene.dyn.info));
+    return PT_OK;
+}
 
 int pt_set_materials(pt_ctx* c, const float* materials, int32_t n_materials)
 {
@@ -405,6 +586,7 @@ int pt_set_environment(pt_ctx* c, const pt_env* env)
 int pt_debug_closest_hit_host(pt_ctx* c, const float org[3], const float dir[3], float tmin, float tmax, float* t, float* u, float* v, int32_t* prim)
 {
     if (!c || !c->have_scene) return PT_E_NO_SCENE;
+    sync_host_scene(c);
     return pt_bvh_closest_hit_host(c->scene.bvh, org, dir, tmin, tmax, t, u, v, prim, c->opt.watertight != 0) ? 1 : 0;
 }
 
@@ -412,6 +594,7 @@ int64_t pt_debug_closest_hit_host_n(pt_ctx* c, const float* rays, int64_t n, flo
 {
     if (!c || !rays || !out || n < 0) return PT_E_INVALID;
     if (!c->have_scene) return PT_E_NO_SCENE;
+    sync_host_scene(c);
     const bool wt = c->opt.watertight != 0; // the walk follows the option as the render does
     pt_parallel_ranges((size_t)n, [&](size_t lo, size_t hi) {
         for (size_t i = lo; i < hi; ++i) {
@@ -431,21 +614,30 @@ int64_t pt_debug_export_tree(pt_ctx* c, int32_t which, void* out, int64_t cap)
 {
     if (!c || cap < 0) return PT_E_INVALID;
     if (!c->have_scene) return fail(c, PT_E_NO_SCENE, "pt_debug_export_tree before pt_upload_scene");
+    const bool from_device = (which & PT_TREE_DEVICE) != 0; // the named array as HBM holds it (what the refit kernels wrote)
+    which &= ~PT_TREE_DEVICE;
+    if (from_device && c->host_only) return fail(c, PT_E_INVALID, "pt_debug_export_tree: PT_TREE_DEVICE on a host-only context");
+    if (!from_device) sync_host_scene(c);
     int64_t info[8] = {c->scene.bvh.root, c->scene.root4, c->scene.root8, c->scene.bvh.depth, c->scene.depth4, c->scene.depth8, 0, c->scene.bvh.max_leaf};
     std::memcpy(&info[6], &c->scene.bvh.pad, sizeof(float));
     const void* src = nullptr;
     size_t bytes = 0;
+    const void* d_src = nullptr; // (the sizes are the host arrays': an update changes no count)
     switch (which) {
-    case PT_TREE_BINARY: src = c->scene.bvh.nodes.data(); bytes = c->scene.bvh.nodes.size() * sizeof(PtNode); break;
-    case PT_TREE_QUAD: src = c->scene.nodes4.data(); bytes = c->scene.nodes4.size() * sizeof(PtNode4); break;
-    case PT_TREE_OCT: src = c->scene.nodes8.data(); bytes = c->scene.nodes8.size() * sizeof(PtNode8); break;
-    case PT_TREE_TRIS: src = c->scene.bvh.tris.data(); bytes = c->scene.bvh.tris.size() * sizeof(PtTri); break;
+    case PT_TREE_BINARY: src = c->scene.bvh.nodes.data(); bytes = c->scene.bvh.nodes.size() * sizeof(PtNode); d_src = c->d_nodes.p; break;
+    case PT_TREE_QUAD: src = c->scene.nodes4.data(); bytes = c->scene.nodes4.size() * sizeof(PtNode4); d_src = c->d_nodes4.p; break;
+    case PT_TREE_OCT: src = c->scene.nodes8.data(); bytes = c->scene.nodes8.size() * sizeof(PtNode8); d_src = c->d_nodes8.p; break;
+    case PT_TREE_TRIS: src = c->scene.bvh.tris.data(); bytes = c->scene.bvh.tris.size() * sizeof(PtTri); d_src = c->d_tris.p; break;
     case PT_TREE_INFO: src = info; bytes = sizeof(info); break;
     default: return fail(c, PT_E_INVALID, "pt_debug_export_tree: unknown array %d", which);
     }
     if (!out) return (int64_t)bytes; // size query
     if ((size_t)cap < bytes) return fail(c, PT_E_INVALID, "pt_debug_export_tree: %zu bytes needed, %lld given", bytes, (long long)cap);
-    if (bytes) std::memcpy(out, src, bytes);
+    if (bytes && from_device && which != PT_TREE_INFO) {
+        HIP_TRY(c, hipSetDevice(c->device));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        HIP_TRY(c, hipMemcpy(out, d_src, bytes, hipMemcpyDeviceToHost));
+    } else if (bytes) std::memcpy(out, src, bytes);
     return (int64_t)bytes;
 }
 
@@ -459,6 +651,7 @@ int pt_debug_quad_info(pt_ctx* c, int64_t out[8])
 {
     if (!c || !out) return PT_E_INVALID;
     if (!c->have_scene) return fail(c, PT_E_NO_SCENE, "pt_debug_quad_info before pt_upload_scene");
+    sync_host_scene(c);
     // {quad nodes, depth, leaf slots, triangles in leaf slots, empty slots, internal slots, binary nodes, binary leaf references}
     int64_t leaf_slots = 0, tris = 0, empty = 0, internal = 0, bin_leaves = 0;
     for (const PtNode4& q : c->scene.nodes4) {
@@ -495,6 +688,7 @@ int pt_debug_oct_info(pt_ctx* c, int64_t out[8])
 {
     if (!c || !out) return PT_E_INVALID;
     if (!c->have_scene) return fail(c, PT_E_NO_SCENE, "pt_debug_oct_info before pt_upload_scene");
+    sync_host_scene(c);
     // {oct nodes, depth, leaf slots, triangles in leaf slots, empty slots, internal slots, largest leaf, triangle slots of the scene}
     int64_t leaf_slots = 0, tris = 0, empty = 0, internal = 0, max_leaf = 0;
     std::vector<uint8_t> seen(c->scene.bvh.tris.size(), 0);

@@ -85,7 +85,8 @@ EXPORTS = ["pt_create", "pt_destroy", "pt_last_error", "pt_abi_version", "pt_upl
            "pt_comm_get_unique_id", "pt_comm_init_rank", "pt_comm_destroy", "pt_reduce_framebuffer", "pt_host_alloc", "pt_host_free",
            "pt_group_create", "pt_group_destroy", "pt_group_size", "pt_group_ctx", "pt_group_last_error", "pt_group_upload_scene",
            "pt_group_set_materials", "pt_group_set_option", "pt_group_render", "pt_debug_quad_info", "pt_debug_oct_info", "pt_debug_clone_scene",
-           "pt_render_batch", "pt_render_batch_device", "pt_debug_plan_batch"]
+           "pt_render_batch", "pt_render_batch_device", "pt_debug_plan_batch", "pt_update_vertices", "pt_group_update_vertices", "pt_debug_update_info"]
+PT_TREE_DEVICE = 16  # pt_debug_export_tree: ORed into `which`, the array as HBM holds it
 PT_COMM_ID_BYTES = 128
 
 _lib = None
@@ -166,6 +167,9 @@ def lib():
     L.pt_render_batch_device.argtypes = [C.c_void_p, C.POINTER(Frame), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     L.pt_debug_plan_batch.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int64]
     L.pt_debug_plan_batch.restype = C.c_int64
+    L.pt_update_vertices.argtypes = [C.c_void_p, C.POINTER(Mesh), C.c_int32]
+    L.pt_group_update_vertices.argtypes = [C.c_void_p, C.POINTER(Mesh), C.c_int32]
+    L.pt_debug_update_info.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
     _lib = L
     return L
 
@@ -312,6 +316,35 @@ def _marshal_scene(entities, materials, textures=None, mesh_textures=None, env=N
     return (arr, len(entities), mats.ctypes.data_as(C.POINTER(C.c_float)), mats.shape[0], tarr, len(textures), None, envp), keep
 
 
+def _mesh_counts(entities):
+    return [(int(np.asarray(m["vertices"]).reshape(-1, 3).shape[0]), int(np.asarray(m["normals"]).reshape(-1, 3).shape[0])) for m, _ in entities]
+
+
+def _marshal_update(meshes, counts):
+    """The pt_mesh array of pt_update_vertices.  meshes: one entry per uploaded mesh - None (unchanged) or a dict with "vertices" and /
+    or "normals" (a missing or None array is passed as NULL: vertices = the mesh is unchanged, normals = keep the retained ones); the keys
+    "n_vertices" / "n_normals" override a count.  counts: (n_vertices, n_normals) per mesh as uploaded, for the arrays that are not passed."""
+    keep = []
+    arr = (Mesh * max(1, len(meshes)))()
+    for i, m in enumerate(meshes):
+        m = m or {}
+        e = arr[i]
+        nv, nn = counts[i] if counts is not None and i < len(counts) else (0, 0)
+        v, n = m.get("vertices"), m.get("normals")
+        if v is not None:
+            v = np.ascontiguousarray(v, np.float32).reshape(-1, 3)
+            keep.append(v)
+            e.vertices = v.ctypes.data_as(C.POINTER(C.c_float))
+            nv = v.shape[0]
+        if n is not None:
+            n = np.ascontiguousarray(n, np.float32).reshape(-1, 3)
+            keep.append(n)
+            e.normals = n.ctypes.data_as(C.POINTER(C.c_float))
+            nn = n.shape[0]
+        e.n_vertices, e.n_normals = int(m.get("n_vertices", nv)), int(m.get("n_normals", nn))
+    return arr, keep
+
+
 class Context:
     """Thin object wrapper; device=-1 gives a host-only validation context (no render possible)."""
 
@@ -356,7 +389,21 @@ class Context:
         textures: list of (H,W) uint32 arrays; mesh_textures: per-entity texture index (or None)."""
         args, keep = _marshal_scene(entities, materials, textures, mesh_textures, env)
         self._check(lib().pt_upload_scene(self._h, *args), "pt_upload_scene")
+        self._counts = _mesh_counts(entities)
         del keep
+
+    def update_vertices(self, meshes, counts=None):
+        """pt_update_vertices (scene uploaded with option "dynamic" = 1): meshes as _marshal_update takes them, e.g. the mesh dicts of
+        upload_scene with moved "vertices".  counts: only for a context that did not upload the scene itself."""
+        arr, keep = _marshal_update(meshes, counts if counts is not None else getattr(self, "_counts", None))
+        self._check(lib().pt_update_vertices(self._h, arr if len(meshes) else None, len(meshes)), "pt_update_vertices")
+        del keep
+
+    def update_info(self):
+        """pt_debug_update_info: the last update_vertices of this context."""
+        a = (C.c_double * 8)()
+        self._check(lib().pt_debug_update_info(self._h, a), "pt_debug_update_info")
+        return dict(device_ms=float(a[0]), h2d_bytes=int(a[1]), slivers=int(a[2]), pad=np.float32(a[3]), levels=int(a[4]))
 
     def set_materials(self, materials):
         mats = np.ascontiguousarray(np.asarray(materials, np.float32).reshape(-1, PT_MAT_FLOATS))
@@ -453,14 +500,15 @@ class Context:
             self._check(int(lib().pt_debug_export_tree(self._h, which, a.ctypes.data_as(C.c_void_p), a.nbytes)), "pt_debug_export_tree")
         return a
 
-    def export_trees(self):
+    def export_trees(self, device=False):
         """The hierarchy the context holds (pt_debug_export_tree): structured arrays `nodes`, `nodes4`, `nodes8`, `tris` (csrc/pt_types.h)
-        and root, root4, root8, depth, depth4, depth8, pad (float32), max_leaf."""
+        and root, root4, root8, depth, depth4, depth8, pad (float32), max_leaf.  device = True: the four arrays as HBM holds them
+        (PT_TREE_DEVICE), not the host copies."""
         info = self._export(4, np.dtype("<i8"))
         d = dict(zip(("root", "root4", "root8", "depth", "depth4", "depth8"), (int(x) for x in info[:6])))
         d["pad"] = np.array([int(info[6]) & 0xffffffff], np.uint32).view(np.float32)[0]
         d["max_leaf"] = int(info[7])
-        d["nodes"], d["nodes4"], d["nodes8"], d["tris"] = (self._export(k, t) for k, t in enumerate((NODE_DTYPE, NODE4_DTYPE, NODE8_DTYPE, TRI_DTYPE)))
+        d["nodes"], d["nodes4"], d["nodes8"], d["tris"] = (self._export(k | (PT_TREE_DEVICE if device else 0), t) for k, t in enumerate((NODE_DTYPE, NODE4_DTYPE, NODE8_DTYPE, TRI_DTYPE)))
         return d
 
     def clone_scene_from(self, other):
@@ -572,6 +620,13 @@ class Group:
         """Arguments as Context.upload_scene: the tree is built once, on rank 0's context, and cloned to the others."""
         args, keep = _marshal_scene(entities, materials, textures, mesh_textures, env)
         self._check(lib().pt_group_upload_scene(self._g, *args), "pt_group_upload_scene")
+        self._counts = _mesh_counts(entities)
+        del keep
+
+    def update_vertices(self, meshes, counts=None):
+        """pt_group_update_vertices: arguments as Context.update_vertices; every device refits its own replica."""
+        arr, keep = _marshal_update(meshes, counts if counts is not None else getattr(self, "_counts", None))
+        self._check(lib().pt_group_update_vertices(self._g, arr if len(meshes) else None, len(meshes)), "pt_group_update_vertices")
         del keep
 
     def set_materials(self, materials):
