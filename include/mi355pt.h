@@ -197,6 +197,39 @@ int pt_render_batch_device(pt_ctx* ctx, const pt_frame* frames, int32_t n_frames
  * is already too large, PT_E_INVALID for bad arguments. */
 int64_t pt_debug_plan_batch(int32_t width, int32_t height, int32_t n_frames, int32_t max_frames, int32_t* out, int64_t cap);
 
+/* ---- guide pass: first-hit albedo, shading normal, depth and coverage (no reference counterpart; the guides a denoiser behind the
+ * library wants for its low-sample frames, and a coverage channel for compositing) ----
+ * A pass of its own beside the render: one launch of a guide kernel that walks camera rays to their closest hit and stops there.
+ * DEFINITION, for pixel (px, py) of a W x H frame and n_samples >= 1 (the kernel, the CPU twin pt_debug_aov_host and the numpy
+ * restatement tests/aov_ref.py implement exactly this):
+ *   rng = rng_init(px, py); for k = 0 .. n_samples-1: rx = rng_next, then ry = rng_next, and the ray is gen_camera_ray's, operation
+ *   for operation: su = (px + rx) / W, sv = (py + ry) / H, dir = normalize(((llc + horizontal*su) + vertical*sv) - origin), from origin.
+ *   Nothing else draws from the stream: SAMPLE 0 IS THE BEAUTY FRAME'S FIRST CAMERA RAY OF THAT PIXEL; THE LATER SAMPLES ARE THE GUIDE
+ *   PASS'S OWN JITTER (the beauty frame's stream goes on into its bounces, so its second camera ray is another one).
+ *   Closest hit as everywhere in this library: t > 1e-3, minimum t, ties to the lower triangle id, slivers never hit; option
+ *   "watertight" selects the triangle test.  Each sample contributes 8 floats:
+ *     miss: albedo = what the miss shader returns (environment map texel, or the automatic gradient, or the environment colour, times
+ *           the environment intensity); alpha, normal and depth 0;
+ *     hit:  alpha 1; depth = the hit's t; normal = the interpolated shading normal exactly as the hit shader forms it (the fma chain
+ *           over the three vertex normals, then normalize) - NOT flipped towards the viewer, computed for emitters too, (0,0,0) if a
+ *           component is not finite; albedo = (emission, emission, emission) if the material's emission > 0, else its base colour
+ *           after the hit shader's texture lookup (material defaults for material_index < 0).
+ *   The contributions are summed in float32 in sample order from 0, and the stored value is sum * (1.0f / (float)n_samples).
+ * LAYOUT: 8 consecutive floats per pixel, {albedo r, g, b, alpha, normal x, y, z, depth}, at pixel offset x + W*(H-1-y) like out_rgb;
+ * pixels the context does not own (pt_set_pixel_shard) are all 0.
+ * LIMITS: first hit only - no follow-through on glass or mirrors (a window shows the window); no batch form (one frame per call).
+ * pt_render_aov: blocking.  Honours the pixel shard, the current material table and environment, "watertight", "box_exact", "quad", and
+ * a scene moved by pt_update_vertices.  With a communicator: ONE sum-reduce of the W*H*8 floats onto rank 0 (one non-zero contributor
+ * per pixel: bit-identical to the one-GPU buffers); the other ranks may pass NULL.  pt_get_stats afterwards: kernel_ms and launches (1)
+ * are the guide launch's, and so are vgprs, lds_bytes, block, grid, stack_entries.  The pass keeps no state: a pt_render after it is bit
+ * for bit the pt_render before it.  Sizes as pt_render (PT_E_INVALID beyond 65535 x 65535 or for n_samples < 1); PT_E_NO_SCENE
+ * without a scene; every argument is checked before anything is touched.  Without quad nodes (option "quad" = 0, or a tree too deep for
+ * them) the pass runs the binary walk, which has no watertight test: together with "watertight" = 1 that is refused with PT_E_INVALID. */
+int pt_render_aov(pt_ctx* ctx, const pt_camera* cam, int32_t width, int32_t height, int32_t n_samples, float* out_aov);
+/* The same, asynchronous on `stream` (NULL = the context's), no reduce, the W*H*8 floats left in HBM at d_out_aov (16-byte aligned);
+ * conventions of pt_render_device.  pt_synchronize waits for it and returns PT_E_HIP if a walk ran out of its step or stack bound. */
+int pt_render_aov_device(pt_ctx* ctx, const pt_camera* cam, int32_t width, int32_t height, int32_t n_samples, void* d_out_aov, void* stream);
+
 /* ---- N GPUs: pixel tiles sharded over ranks + ONE RCCL sum-reduce of the float3 framebuffer onto rank 0 (pt_comm.cpp) ----
  * No reference counterpart (the reference is single-GPU: create_context(nullptr, 1), application.cpp:62); for N > 1 these
  * replace the render + read-back of application.cpp:363-369.  Every pixel has exactly one non-zero contributor, so the
@@ -237,6 +270,8 @@ int pt_group_set_option(pt_group* g, const char* key, int64_t value);
 int pt_group_update_vertices(pt_group* g, const pt_mesh* meshes, int32_t n_meshes); /* every device refits its own replica */
 int pt_group_render(pt_group* g, const pt_camera* cam, int32_t width, int32_t height, int32_t max_samples, int32_t max_path_depth,
                     float* out_rgb, uint32_t* out_rgba8);
+/* pt_render_aov over the group: every device's own tiles, one reduce of the W*H*8 floats onto devices[0], read-back from there */
+int pt_group_render_aov(pt_group* g, const pt_camera* cam, int32_t width, int32_t height, int32_t n_samples, float* out_aov);
 
 /* Tuning / test options (all have working defaults; none changes an image, except "watertight"):
  *   "kernel" 2 (default, wavefront-scheduled) | 1 (lane per pixel);  "count" 0/1: instrumented kernel that fills pt_stats;
@@ -293,6 +328,12 @@ int pt_debug_closest_hit_host(pt_ctx* ctx, const float org[3], const float dir[3
                               float* t, float* u, float* v, int32_t* prim);
 /* The same for n rays at once (rays: o[3], d[3] each; out: hit, t, u, v, id bits - 5 floats each), on all host threads.  Returns n. */
 int64_t pt_debug_closest_hit_host_n(pt_ctx* ctx, const float* rays, int64_t n, float tmin, float tmax, float* out);
+/* The CPU twin of the guide pass (pt_render_aov): its definition run by the host walk of pt_debug_closest_hit_host_n over the host
+ * copies of the scene, on all host threads; works on a host-only context (device = -1), follows "watertight", the current materials and
+ * environment, and pt_update_vertices.  pixel_ids: launch-index ids x + W*y (any, whatever the pixel shard); out: 8 floats per listed
+ * pixel, in list order.  Returns n_pixels; PT_E_NO_SCENE / PT_E_INVALID as pt_render_aov, and PT_E_INVALID for an id outside the frame. */
+int64_t pt_debug_aov_host(pt_ctx* ctx, const pt_camera* cam, int32_t width, int32_t height, int32_t n_samples, const uint32_t* pixel_ids,
+                          int64_t n_pixels, float* out);
 /* Batched device-side evaluation of the kernel's building blocks on the GPU (op codes in pt_kernel_aux.hip):
  * lets the parity tests compare them bit-for-bit with the oracle.  in/out are host arrays.
  * Ops 30..35 are RAY PROBES: in = o[3], d[3] per ray, out = {hit, t, u, v, id bits, aux} (6 floats), through the device functions of

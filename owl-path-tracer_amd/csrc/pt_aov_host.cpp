@@ -1,0 +1,139 @@
+// pt_aov_host.cpp -- pt_debug_aov_host: the CPU twin of the guide pass (pt_render_aov; kernel: pt_kernel.hip "guide pass").
+// The twin runs the definition of include/mi355pt.h with the host walk of pt_debug_closest_hit_host_n over the host copies of the
+// scene, and with the arithmetic of pt_device.h itself: the header is included here with PTD = static inline, so rng_init, rng_next,
+// normalize, lerp3, uv_on_sphere (the polynomial atan2 / asin), tex_nearest and the material row are the functions the kernel
+// compiles, run by the CPU under the same contract (binary32, -ffp-contract=off, fma only where spelled, correctly rounded division
+// and sqrt).  What is restated here is what the kernel takes from pt_trace.h, which is device code throughout: the camera ray
+// (gen_camera_ray), interp3 and the miss branch / attribute fetch of shade_hit - each a few lines, cited below.
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+#include <vector>
+
+// the four bit casts pt_device.h uses are device functions of the HIP headers: host forms under the same names
+static inline uint32_t pt_host_float_as_uint(float x) { uint32_t u; std::memcpy(&u, &x, 4); return u; }
+static inline float pt_host_uint_as_float(uint32_t u) { float x; std::memcpy(&x, &u, 4); return x; }
+#define __float_as_uint pt_host_float_as_uint
+#define __uint_as_float pt_host_uint_as_float
+#define PTD static inline
+#include "pt_device.h"
+#undef __float_as_uint
+#undef __uint_as_float
+
+#include "pt_internal.h"
+
+using namespace pti;
+using namespace ptd;
+
+namespace {
+
+v3 interp3(float bw, float bx, float by, v3 a, v3 b, v3 c) // pt_trace.h
+{
+    return V(fma_(by, c.x, fma_(bx, b.x, bw * a.x)), fma_(by, c.y, fma_(bx, b.y, bw * a.y)), fma_(by, c.z, fma_(bx, b.z, bw * a.z)));
+}
+bool finite_(float x) { return !(isinf_(x) || isnan_(x)); }
+
+struct AovScene {
+    const HostScene* s;
+    std::vector<int32_t> slot_of; // global triangle id -> leaf-order slot (the host walk reports the id, the records are in leaf order)
+    pt_camera cam;
+    int W, H, n;
+    bool wt;
+};
+
+// One pixel: include/mi355pt.h, "guide pass"; the kernel's loop body (pt_aov_kernel) line for line.
+void aov_pixel(const AovScene& A, int px, int py, float* y)
+{
+    const HostScene& S = *A.s;
+    uint32_t rng = rng_init((uint32_t)px, (uint32_t)py);
+    v3 s_alb = vs(0.0f), s_nrm = vs(0.0f);
+    float s_alpha = 0.0f, s_depth = 0.0f;
+    const v3 origin = V(A.cam.origin[0], A.cam.origin[1], A.cam.origin[2]), llc = V(A.cam.llc[0], A.cam.llc[1], A.cam.llc[2]);
+    const v3 hor = V(A.cam.horizontal[0], A.cam.horizontal[1], A.cam.horizontal[2]), ver = V(A.cam.vertical[0], A.cam.vertical[1], A.cam.vertical[2]);
+    for (int k = 0; k < A.n; ++k) {
+        const float rx = rng_next(rng); // gen_camera_ray (pt_trace.h)
+        const float ry = rng_next(rng);
+        const float su = ((float)px + rx) / (float)A.W;
+        const float sv = ((float)py + ry) / (float)A.H;
+        const v3 dir = normalize(((llc + hor * su) + ver * sv) - origin);
+        const float o[3] = {origin.x, origin.y, origin.z}, d[3] = {dir.x, dir.y, dir.z};
+        float t = 0.0f, hu = 0.0f, hv = 0.0f;
+        int32_t prim = -1;
+        const bool hit = pt_bvh_closest_hit_host(S.bvh, o, d, kTMin, kTMax, &t, &hu, &hv, &prim, A.wt);
+        v3 alb, nrm = vs(0.0f);
+        float alpha = 0.0f, depth = 0.0f;
+        if (!hit) { // shade_hit's miss branch
+            v3 radiance = vs(0.0f);
+            if (S.env.use_map && S.env_map.w > 0) {
+                float tu, tv;
+                uv_on_sphere(dir, tu, tv);
+                radiance = radiance + tex_nearest(S.env_map.px.data(), S.env_map.w, S.env_map.h, tu, tv);
+            } else if (S.env.use_auto) {
+                radiance = radiance + lerp3(vs(1.0f), V(0.5f, 0.7f, 1.0f), 0.5f * (dir.y + 1.0f));
+            } else {
+                radiance = radiance + V(S.env.color[0], S.env.color[1], S.env.color[2]);
+            }
+            alb = radiance * S.env.intensity;
+        } else { // shade_hit's attribute fetch
+            const size_t slot = (size_t)A.slot_of[(size_t)prim];
+            const PtShade& sh = S.shade[slot];
+            const int mi = S.bvh.tris[slot].material;
+            Material mat = material_default();
+            int32_t tex_slot = -1;
+            if (mi >= 0) {
+                const float* mp = &S.materials[(size_t)mi * PT_MAT_STRIDE];
+                mat = material_load(mp);
+                std::memcpy(&tex_slot, mp + 17, 4);
+            }
+            const float bx = hu, by = hv;
+            const float bw = 1.0f - bx - by;
+            const v3 v_n = normalize(interp3(bw, bx, by, V(sh.n0[0], sh.n0[1], sh.n0[2]), V(sh.n1[0], sh.n1[1], sh.n1[2]), V(sh.n2[0], sh.n2[1], sh.n2[2])));
+            if (finite_(v_n.x) && finite_(v_n.y) && finite_(v_n.z)) nrm = v_n;
+            if (mat.emission > 0.0f) {
+                alb = vs(mat.emission);
+            } else {
+                if (tex_slot >= 0) {
+                    const float tu = fma_(by, sh.tc[4], fma_(bx, sh.tc[2], bw * sh.tc[0]));
+                    const float tv = fma_(by, sh.tc[5], fma_(bx, sh.tc[3], bw * sh.tc[1]));
+                    const HostTexture& tx = S.textures[(size_t)tex_slot];
+                    mat.base_color = tex_nearest(tx.px.data(), tx.w, tx.h, tu, tv);
+                }
+                alb = mat.base_color;
+            }
+            alpha = 1.0f;
+            depth = t;
+        }
+        s_alb = s_alb + alb; s_alpha = s_alpha + alpha;
+        s_nrm = s_nrm + nrm; s_depth = s_depth + depth;
+    }
+    const float inv_n = 1.0f / (float)A.n;
+    y[0] = s_alb.x * inv_n; y[1] = s_alb.y * inv_n; y[2] = s_alb.z * inv_n; y[3] = s_alpha * inv_n;
+    y[4] = s_nrm.x * inv_n; y[5] = s_nrm.y * inv_n; y[6] = s_nrm.z * inv_n; y[7] = s_depth * inv_n;
+}
+
+} // namespace
+
+extern "C" int64_t pt_debug_aov_host(pt_ctx* c, const pt_camera* cam, int32_t W, int32_t H, int32_t n_samples, const uint32_t* pixel_ids, int64_t n_pixels, float* out)
+{
+    if (!c || !cam || !out || n_pixels < 0 || (n_pixels > 0 && !pixel_ids)) return PT_E_INVALID;
+    if (!c->have_scene) return fail(c, PT_E_NO_SCENE, "no geometries (pt_upload_scene not called)");
+    if (W <= 0 || H <= 0 || W > 65535 || H > 65535 || n_samples <= 0 || (int64_t)W * H > (int64_t)0x7fffffff)
+        return fail(c, PT_E_INVALID, "bad guide pass size %dx%d, %d samples", W, H, n_samples);
+    for (int64_t i = 0; i < n_pixels; ++i)
+        if (pixel_ids[i] >= (uint32_t)W * (uint32_t)H) return fail(c, PT_E_INVALID, "pt_debug_aov_host: pixel id %u outside the %dx%d frame", pixel_ids[i], W, H);
+    sync_host_scene(c);
+    AovScene A;
+    A.s = &c->scene;
+    A.cam = *cam;
+    A.W = W; A.H = H; A.n = n_samples;
+    A.wt = c->opt.watertight != 0; // the walk follows the option as the render does
+    A.slot_of.assign((size_t)c->scene.n_triangles, -1);
+    for (size_t s = 0; s < c->scene.bvh.tris.size(); ++s) {
+        const int32_t id = c->scene.bvh.tris[s].id;
+        if (id >= 0 && (size_t)id < A.slot_of.size()) A.slot_of[(size_t)id] = (int32_t)s; // (padding slots carry id 0x7fffffff)
+    }
+    pt_parallel_ranges((size_t)n_pixels, [&](size_t lo, size_t hi) {
+        for (size_t i = lo; i < hi; ++i) aov_pixel(A, (int)(pixel_ids[i] % (uint32_t)W), (int)(pixel_ids[i] / (uint32_t)W), out + 8 * i);
+    });
+    return n_pixels;
+}

@@ -17,6 +17,8 @@
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
+#include <string>
+#include <vector>
 
 #include "pt_internal.h"
 #include "pt_launch.h"
@@ -86,9 +88,19 @@ int need_rccl(pt_ctx* c)
 
 } // namespace
 
+namespace pti {
+int reduce_sum(pt_ctx* c, void* d_buf, size_t n_floats, hipStream_t stream)
+{
+    if (!c->comm) return PT_OK;
+    RCCL_TRY(c, g_rccl.Reduce(d_buf, d_buf, n_floats, ncclFloat32, ncclSum, 0, (ncclComm_t)c->comm, stream));
+    return PT_OK;
+}
+} // namespace pti
+
 struct pt_group {
     std::vector<pt_ctx*> ctx;
     size_t cap_px = 0;                 // pixels the per-device framebuffers (each context's d_out / d_out8) and the staging hold
+    std::vector<float> aov;            // staging of pt_group_render_aov (pageable: the guide buffers are read back once per frame)
     float* pinned_rgb = nullptr;       // staging for the root's D2H (pinned: the reference's framebuffer is pinned host memory, owl.hpp:108-111)
     uint32_t* pinned_rgba8 = nullptr;
     std::string err;
@@ -333,6 +345,62 @@ int pt_group_render(pt_group* g, const pt_camera* cam, int32_t W, int32_t H, int
     }
     std::memcpy(out_rgb, g->pinned_rgb, npx * 12);
     if (out_rgba8) std::memcpy(out_rgba8, g->pinned_rgba8, npx * 4);
+    return PT_OK;
+}
+
+// The guide pass over the group: every device runs the guide kernel over its own tiles, ONE grouped reduce of the W*H*8 floats onto
+// device 0, read-back from there.
+int pt_group_render_aov(pt_group* g, const pt_camera* cam, int32_t W, int32_t H, int32_t n_samples, float* out_aov)
+{
+    if (!g || !cam || !out_aov || W <= 0 || H <= 0) return PT_E_INVALID;
+    const int n = (int)g->ctx.size();
+    const size_t n_floats = (size_t)W * (size_t)H * 8;
+    auto fail_all = [&](pt_ctx* c, int rc) { // as pt_group_render: remember the reason, drain every device, return
+        g->err = pt_last_error(c);
+        for (pt_ctx* o : g->ctx) {
+            (void)hipSetDevice(o->device);
+            (void)hipStreamSynchronize(o->stream);
+        }
+        return rc;
+    };
+    for (int i = 0; i < n; ++i) {
+        pt_ctx* c = g->ctx[(size_t)i];
+        if (hipSetDevice(c->device) != hipSuccess) return fail_all(c, pti::fail(c, PT_E_HIP, "hipSetDevice(%d) failed", c->device));
+        if (W > 65535 || H > 65535) return fail_all(c, pti::fail(c, PT_E_INVALID, "bad render size %dx%d", W, H));
+        int rc = pti::ensure(c, c->d_aov, n_floats * 4);
+        if (!rc) rc = pt_render_aov_device(c, cam, W, H, n_samples, c->d_aov.p, nullptr);
+        if (rc) return fail_all(c, rc);
+    }
+    pt_ctx* c0 = g->ctx[0];
+    if (n > 1) {
+        ncclResult_t r = g_rccl.GroupStart();
+        if (r != ncclSuccess) return fail_all(c0, pti::fail(c0, PT_E_HIP, "ncclGroupStart failed: %s", g_rccl.GetErrorString(r)));
+        pt_ctx* bad_ctx = nullptr;
+        for (int i = 0; i < n && r == ncclSuccess; ++i) {
+            pt_ctx* c = g->ctx[(size_t)i];
+            r = g_rccl.Reduce(c->d_aov.p, c->d_aov.p, n_floats, ncclFloat32, ncclSum, 0, (ncclComm_t)c->comm, c->stream);
+            if (r != ncclSuccess) bad_ctx = c;
+        }
+        const ncclResult_t re = g_rccl.GroupEnd(); // closed even after a failed call (see pt_group_render)
+        if (r != ncclSuccess) {
+            g->err = std::string("ncclReduce failed on device ") + std::to_string(bad_ctx->device) + ": " + g_rccl.GetErrorString(r) + " (destroy the group)";
+            (void)pti::fail(bad_ctx, PT_E_HIP, "%s", g->err.c_str());
+            return PT_E_HIP;
+        }
+        if (re != ncclSuccess) return fail_all(c0, pti::fail(c0, PT_E_HIP, "ncclGroupEnd failed: %s", g_rccl.GetErrorString(re)));
+    }
+    if (hipSetDevice(c0->device) != hipSuccess) return fail_all(c0, pti::fail(c0, PT_E_HIP, "hipSetDevice(%d) failed", c0->device));
+    g->aov.resize(n_floats);
+    if (hipMemcpyAsync(g->aov.data(), c0->d_aov.p, n_floats * 4, hipMemcpyDeviceToHost, c0->stream) != hipSuccess)
+        return fail_all(c0, pti::fail(c0, PT_E_HIP, "guide buffer read-back failed"));
+    int first_rc = PT_OK;
+    pt_ctx* first_bad = nullptr;
+    for (int i = 0; i < n; ++i) { // drains EVERY device's stream and reads its bound flag
+        const int rc = pt_synchronize(g->ctx[(size_t)i]);
+        if (rc && !first_rc) { first_rc = rc; first_bad = g->ctx[(size_t)i]; }
+    }
+    if (first_rc) { g->err = pt_last_error(first_bad); return first_rc; }
+    std::memcpy(out_aov, g->aov.data(), n_floats * 4);
     return PT_OK;
 }
 

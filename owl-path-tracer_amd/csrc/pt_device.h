@@ -12,7 +12,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#ifndef PTD // (pt_aov_host.cpp defines it empty-handed - static inline - and so runs these very functions on the CPU: the guide pass's twin)
 #define PTD __device__ __forceinline__
+#endif
 
 namespace ptd {
 

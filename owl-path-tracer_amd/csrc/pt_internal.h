@@ -85,6 +85,7 @@ struct LastFrame {
     int chunks = 0;             // of the last frame that ran a kernel, with the offset of its timelines in d_laps
     size_t lap_ticks_ofs = 0;
     int seqs = 1;               // launch sequences of the last render (pt_render_batch may need several)
+    bool aov_flag_pending = false; // the last call was a guide pass (pt_render_aov*) that ran a kernel: its bound flag in d_aov_ws has not been looked at yet
 };
 
 struct pt_ctx {
@@ -102,6 +103,7 @@ struct pt_ctx {
     // device
     DevBuf d_nodes8, d_nodes4, d_nodes, d_tris, d_shade, d_materials, d_texdesc, d_env, d_pixels, d_heads, d_rng, d_accum, d_out, d_out8, d_counters, d_dbg_in, d_dbg_out, d_slots, d_laps, d_ring, d_params, d_cost, d_sorted, d_sort_scratch, d_dbg_start, d_bucket, d_tiers, d_batch_mats, d_batch_cams, d_seq_flags; // d_batch_*: per-frame tables of pt_render_batch; d_seq_flags: watchdog flags of its earlier launch sequences
     DevBuf d_verts, d_vnormals, d_tri_vi, d_level_nodes, d_src4, d_src8, d_refit_ws; // option "dynamic": what the refit kernels read (pt_refit.hip)
+    DevBuf d_aov, d_aov_ws; // guide pass: the frame of pt_render_aov / pt_group_render_aov; bound flag (64 words) + the waves' stack overflow columns
     std::vector<DevBuf> d_textures;
 
     // pixel queue
@@ -137,6 +139,8 @@ PT_LOCAL void material_row(const pt_ctx* c, float* dst, const float* src, int i)
 // pt_render.cpp
 int check_watchdog(pt_ctx* c);
 PT_LOCAL void fill_params(pt_ctx* c, PtKernelParams& P);
+// pt_comm.cpp
+PT_LOCAL int reduce_sum(pt_ctx* c, void* d_buf, size_t n_floats, hipStream_t stream); // in-place sum-reduce onto rank 0; nothing without a communicator
 } // namespace pti
 
 #define HIP_TRY(c, call)                                                                                   \

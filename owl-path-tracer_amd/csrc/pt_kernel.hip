@@ -42,6 +42,12 @@
 #ifndef PT_WATERTIGHT
 #define PT_WATERTIGHT 0
 #endif
+#ifndef PT_AOV
+#define PT_AOV 0 // 1: pt_kernel_aov.hip / pt_kernel_aov_wt.hip - the device functions of this file around the guide kernels alone ("guide pass", at the end)
+#endif
+#if PT_AOV && PT_BATCH
+#error "the guide pass has no batch form"
+#endif
 #if PT_WATERTIGHT
 #if PT_BATCH
 #error "the watertight build has no batch instances"
@@ -56,6 +62,9 @@
 #define pt_probe_lds_stack pt_probe_lds_stack_wt
 #define pt_probe_group_lds_bytes pt_probe_group_lds_bytes_wt
 #define pt_probe_group_state_words pt_probe_group_state_words_wt
+#define pt_aov_kernel pt_aov_wt_kernel
+#define pt_launch_aov pt_launch_aov_wt
+#define pt_aov_geometry pt_aov_geometry_wt
 #elif PT_BATCH
 #define PT_RENDER_KERNEL pt_render_batch_kernel
 #else
@@ -1269,6 +1278,7 @@ __global__ void __launch_bounds__(PT_WAVE, WAVES) PT_RENDER_KERNEL(const PtKerne
 
 // ---- launchers (called from pt_render.cpp) --------------------------------------------------------------------
 
+#if !PT_AOV // (the guide builds take the device functions above and instantiate none of the render kernels)
 // d_params: device copy of *p (wavefront kernel reads its parameters from HBM; the caller keeps it stream-ordered)
 // (the batch build defines the same two functions for its own instances: pt_launch_render_batch / pt_batch_kernel_geometry, variants 2 and 3 only)
 #if PT_BATCH
@@ -1332,7 +1342,9 @@ extern "C" hipError_t pt_kernel_geometry(int variant, int count, int stack_entri
     return hipOccupancyMaxActiveBlocksPerMultiprocessor(&g->max_blocks_per_cu, fn, g->block, g->lds_bytes);
 }
 
-#if !PT_BATCH // (the probes belong to the single-frame build)
+#endif // !PT_AOV
+
+#if !PT_BATCH && !PT_AOV // (the probes belong to the single-frame build)
 // =====================================================================================================================
 // Ray probes (tests only: pt_debug_eval ops PT_PROBE_*, pt_launch.h; tests/test_gpu_ray_probes.py)
 // =====================================================================================================================
@@ -1502,4 +1514,179 @@ extern "C" hipError_t pt_launch_probe(const PtKernelParams* p, int op, const flo
     }
     return hipGetLastError();
 }
-#endif // !PT_BATCH
+#endif // !PT_BATCH && !PT_AOV
+
+#if PT_AOV
+// =====================================================================================================================
+// Guide pass (pt_render_aov, include/mi355pt.h): first-hit albedo, shading normal, depth and coverage
+// =====================================================================================================================
+// Built as translation units of their own - pt_kernel_aov.hip and, with PT_WATERTIGHT = 1, pt_kernel_aov_wt.hip include this file with
+// PT_AOV = 1 - so that the translation units of the render instances hold the kernels they always held (tests/test_watertight_host.py
+// counts them) and `make asm`, `asm-batch`, `asm-wt` print what they printed.
+// A pass of its own beside the render kernel (whose instances sit at their register budgets: no room for seven more accumulators per
+// slot): one pixel per lane, one wave per workgroup, n_samples camera rays per pixel, each walked to its closest hit and no further.
+// Like the probes above the kernel owns no traversal or shading arithmetic: the ray is gen_camera_ray's, the walk is ray_inv -> node4_step<PT_WAVE,
+// PT_LDS_STACK> (short LDS stack, deeper levels in the wave's HBM columns) -> leaf_test with the probe's loop around them, and what a
+// sample contributes comes from the records, the material row and the texture that shade_hit reads, through the same functions.
+// The lanes of a wave take an 8 x 8 block of pixels (four per 16-pixel shard tile; pt_shard_pixels deals tiles whose side is a multiple
+// of 8, so a block has one owner and a wave that does not own its block has nothing to do): the primary rays of a wave stay together
+// through the upper node steps.  BINARY (no quad nodes: option quad = 0 or a tree too deep for them): closest_hit of pt_trace.h, whole
+// stack in LDS, Moeller-Trumbore only - the watertight build has no such instance.
+#ifndef PT_AOV_WAVES_PER_EU
+#define PT_AOV_WAVES_PER_EU 4 // 128 VGPRs, 16 waves per CU at 3 KB of LDS each
+#endif
+namespace {
+__device__ __forceinline__ bool finite_(float x) { return !(isinf_(x) || isnan_(x)); }
+// What one sample contributes: tslot < 0 = miss.  The miss branch and the attribute fetch are shade_hit's, expression for expression.
+__device__ __forceinline__ void aov_sample(const PtKernelParams& P, int tslot, float hu, float hv, float ht, v3 dir, v3& albedo, float& alpha, v3& normal, float& depth)
+{
+    if (tslot < 0) {
+        v3 radiance = vs(0.0f);
+        if (P.env_use_map && P.env_map.width > 0) {
+            float tu, tv;
+            uv_on_sphere(dir, tu, tv);
+            radiance = radiance + tex_nearest(gp(P.env_map.texels), P.env_map.width, P.env_map.height, tu, tv);
+        } else if (P.env_use_auto) {
+            radiance = radiance + lerp3(vs(1.0f), V(0.5f, 0.7f, 1.0f), 0.5f * (dir.y + 1.0f));
+        } else {
+            radiance = radiance + V(P.env_color[0], P.env_color[1], P.env_color[2]);
+        }
+        albedo = radiance * P.env_intensity;
+        alpha = 0.0f; normal = vs(0.0f); depth = 0.0f;
+        return;
+    }
+    const f32x4 c = ldg4(P.tris, (size_t)(uint32_t)tslot * sizeof(PtTri) + 32); // {p2.z, id, material, pad}
+    const size_t sb = (size_t)(uint32_t)tslot * sizeof(PtShade);
+    const f32x4 s0 = ldg4(P.shade, sb), s1 = ldg4(P.shade, sb + 16), s2 = ldg4(P.shade, sb + 32), s3 = ldg4(P.shade, sb + 48);
+    const int mi = __float_as_int(c.z);
+    Material mat = material_default();
+    int tex_slot = -1;
+    if (mi >= 0) {
+        const float PT_AS1* mp = gp(P.materials) + mi * PT_MAT_STRIDE;
+        mat = material_load(mp);
+        tex_slot = __float_as_int(mp[17]);
+    }
+    const float bx = hu, by = hv;
+    const float bw = 1.0f - bx - by;
+    const v3 v_n = normalize(interp3(bw, bx, by, V(s0.x, s0.y, s0.z), V(s0.w, s1.x, s1.y), V(s1.z, s1.w, s2.x)));
+    normal = (finite_(v_n.x) && finite_(v_n.y) && finite_(v_n.z)) ? v_n : vs(0.0f); // not flipped towards the viewer; emitters have one too
+    if (mat.emission > 0.0f) {
+        albedo = vs(mat.emission);
+    } else {
+        if (tex_slot >= 0) {
+            const float tu = fma_(by, s3.z, fma_(bx, s3.x, bw * s2.z));
+            const float tv = fma_(by, s3.w, fma_(bx, s3.y, bw * s2.w));
+            const PtTexDesc PT_AS1* tdp = gp(P.textures) + tex_slot;
+            mat.base_color = tex_nearest(gp(tdp->texels), tdp->width, tdp->height, tu, tv);
+        }
+        albedo = mat.base_color;
+    }
+    alpha = 1.0f;
+    depth = ht;
+}
+} // namespace
+
+template <bool BINARY, bool EXACT>
+__global__ void __launch_bounds__(PT_WAVE, PT_AOV_WAVES_PER_EU) pt_aov_kernel(const PtKernelParams P, const PtAovArgs A)
+{
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    const int lane = threadIdx.x;
+    uint32_t* stack = lds + lane; // stack[level * 64 + lane]
+    const int ovf_levels = A.cap > PT_LDS_STACK ? A.cap - PT_LDS_STACK : 0;
+    uint32_t PT_AS1* ovf = gp(A.ovf) + (size_t)blockIdx.x * ((size_t)ovf_levels * PT_WAVE) + lane;
+    const PtNode4* __restrict__ nodes4 = P.nodes4;
+    const PtTri* __restrict__ tris = P.tris;
+    const int nbx = (P.width + 7) >> 3, nby = (P.height + 7) >> 3;
+    const float inv_n = 1.0f / (float)A.n_samples;
+    for (int b = blockIdx.x; b < nbx * nby; b += gridDim.x) {
+        const int bx = b % nbx, by = b / nbx;
+        if (((bx * 8) / A.tile + (by * 8) / A.tile) % A.world != A.rank) continue; // another rank's tile (wave-uniform)
+        const int px = bx * 8 + (lane & 7), py = by * 8 + (lane >> 3);
+        if (px >= P.width || py >= P.height) continue; // the block sticks out of the frame
+        PathState ps;
+        ps.rng = rng_init((uint32_t)px, (uint32_t)py); // the beauty frame's stream: sample 0 is its first camera ray of this pixel
+        v3 s_alb = vs(0.0f), s_nrm = vs(0.0f);
+        float s_alpha = 0.0f, s_depth = 0.0f;
+        for (int k = 0; k < A.n_samples; ++k) {
+            gen_camera_ray(P, px, py, ps); // two draws; nothing else of this pass draws from the stream
+            const v3 o = ps.org, d = ps.dir;
+            Hit h;
+            h.t = kTMax; h.u = 0.0f; h.v = 0.0f; h.id = 0x7fffffff; h.slot = -1;
+#if !PT_WATERTIGHT
+            if (BINARY) {
+                Counters cn;
+                closest_hit<false, PT_WAVE>(P, stack, o, d, h, cn);
+            } else
+#endif
+            {
+                const v3 inv = ray_inv(d);
+                int cur = P.root, sp = 0, steps = 0;
+                while (cur != PT_DONE) {
+                    // bounded as the probe's walk: a ray needs a few thousand steps, the stack bound comes from the host (3 * depth4 + 1, + 3)
+                    if (++steps > (1 << 20) || sp + 3 > A.cap) {
+                        gp(P.error_flag)[0] = 1u;
+                        break;
+                    }
+                    if (cur >= 0) {
+                        node4_step<PT_WAVE, PT_LDS_STACK>(nodes4, stack, ovf, o, inv, h.t, cur, sp, EXACT);
+                    } else {
+                        const uint32_t code = ~(uint32_t)cur;
+                        leaf_test(tris, (int)(code >> 3), (int)(code & 7u), o, d, h);
+                        if (sp > 0) {
+                            --sp;
+                            cur = (int)stack_pop<PT_WAVE, PT_LDS_STACK>(stack, ovf, sp);
+                        } else {
+                            cur = PT_DONE;
+                        }
+                    }
+                }
+            }
+            v3 alb, nrm;
+            float alpha, depth;
+            aov_sample(P, h.slot, h.u, h.v, h.t, d, alb, alpha, nrm, depth);
+            s_alb = s_alb + alb; s_alpha = s_alpha + alpha; // float32, in sample order
+            s_nrm = s_nrm + nrm; s_depth = s_depth + depth;
+        }
+        const size_t ofs = (size_t)px + (size_t)P.width * (size_t)(P.height - 1 - py); // as out_rgb
+        f32x4 PT_AS1* y = (f32x4 PT_AS1*)(gp(A.out) + 8 * ofs);                        // two 16-byte stores
+        y[0] = (f32x4){s_alb.x * inv_n, s_alb.y * inv_n, s_alb.z * inv_n, s_alpha * inv_n};
+        y[1] = (f32x4){s_nrm.x * inv_n, s_nrm.y * inv_n, s_nrm.z * inv_n, s_depth * inv_n};
+    }
+}
+
+extern "C" hipError_t pt_aov_geometry(int binary, int exact, int stack_entries, PtGeometry* g)
+{
+#if PT_WATERTIGHT
+    if (binary) return hipErrorInvalidValue; // the binary walk has no watertight test
+    const void* fn = exact ? (const void*)pt_aov_kernel<false, true> : (const void*)pt_aov_kernel<false, false>;
+#else
+    const void* fn = binary ? (const void*)pt_aov_kernel<true, false> : (exact ? (const void*)pt_aov_kernel<false, true> : (const void*)pt_aov_kernel<false, false>);
+#endif
+    g->block = PT_WAVE;
+    g->ns = PT_WAVE;
+    g->lds_levels = binary ? stack_entries : PT_LDS_STACK;
+    g->lds_bytes = (size_t)g->lds_levels * PT_WAVE * 4;
+    g->state_words = 0;
+    hipFuncAttributes fa;
+    hipError_t e = hipFuncGetAttributes(&fa, fn);
+    if (e != hipSuccess) return e;
+    if (fa.localSizeBytes != 0) return hipErrorInvalidConfiguration; // as the render instances: a build that spills is refused
+    g->vgprs = fa.numRegs;
+    g->max_blocks_per_cu = 0;
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(&g->max_blocks_per_cu, fn, g->block, g->lds_bytes);
+}
+
+extern "C" hipError_t pt_launch_aov(const PtKernelParams* p, const PtAovArgs* a, int binary, int grid, size_t lds_bytes, hipStream_t stream)
+{
+    if (grid < 1) grid = 1;
+#if PT_WATERTIGHT
+    if (binary) return hipErrorInvalidValue;
+#else
+    if (binary) hipLaunchKernelGGL((pt_aov_kernel<true, false>), dim3(grid), dim3(PT_WAVE), lds_bytes, stream, *p, *a);
+    else
+#endif
+    if (p->box_exact) hipLaunchKernelGGL((pt_aov_kernel<false, true>), dim3(grid), dim3(PT_WAVE), lds_bytes, stream, *p, *a);
+    else hipLaunchKernelGGL((pt_aov_kernel<false, false>), dim3(grid), dim3(PT_WAVE), lds_bytes, stream, *p, *a);
+    return hipGetLastError();
+}
+#endif // PT_AOV

@@ -46,7 +46,24 @@ struct PtRefitArgs {
     int32_t n_slots, n_levels, n_slots4, n_slots8;
 };
 
+// Guide pass (pt_render_aov; pt_kernel.hip "guide pass"): what the guide kernels take beside the scene and the camera in PtKernelParams.
+struct PtAovArgs {
+    float* out;        // W*H*8 floats, cleared by the caller: {albedo r, g, b, alpha, normal x, y, z, depth} per pixel, framebuffer order
+    uint32_t* ovf;     // quad walk: the waves' HBM stack columns, (cap - PT_LDS_STACK) * 64 words per workgroup (none when cap <= PT_LDS_STACK)
+    int32_t n_samples;
+    int32_t cap;       // quad walk: stack levels a lane may use (stack bound + the three pushes of a step)
+    int32_t rank, world, tile; // pixel shard (pt_shard_pixels: tile a multiple of 8, tile (tx, ty) belongs to rank (tx + ty) % world)
+    int32_t pad;
+};
+
 extern "C" {
+// pt_kernel.hip / pt_kernel_wt.hip: the guide kernels.  binary = 1: the one-level walk over PtNode[] (closest_hit of pt_trace.h; Moeller-
+// Trumbore only: the watertight build has no such instance and answers hipErrorInvalidValue).  Geometry: block, lds_bytes, lds_levels and
+// vgprs of the instance; hipErrorInvalidConfiguration if it needs scratch.
+hipError_t pt_launch_aov(const PtKernelParams* p, const PtAovArgs* a, int binary, int grid, size_t lds_bytes, hipStream_t stream);
+hipError_t pt_aov_geometry(int binary, int exact, int stack_entries, PtGeometry* g);
+hipError_t pt_launch_aov_wt(const PtKernelParams* p, const PtAovArgs* a, int binary, int grid, size_t lds_bytes, hipStream_t stream);
+hipError_t pt_aov_geometry_wt(int binary, int exact, int stack_entries, PtGeometry* g);
 size_t pt_refit_workspace_bytes(void);
 // gather, extent, one refit launch per level, propagate - all on `stream`, `first` recorded before the first kernel, `last` after the last
 hipError_t pt_launch_refit(const PtRefitArgs* a, hipEvent_t first, hipEvent_t last, hipStream_t stream);

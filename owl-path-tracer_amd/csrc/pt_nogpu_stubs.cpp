@@ -20,6 +20,10 @@ hipError_t pt_launch_render_wt(const PtKernelParams*, const PtKernelParams*, int
 hipError_t pt_wt_kernel_geometry(int, int, int, int, int, int, PtGeometry*) { return hipErrorNotSupported; }
 hipError_t pt_launch_probe_wt(const PtKernelParams*, int, const float*, int, float*, int, long long, int, size_t, uint32_t*, hipStream_t) { return hipErrorNotSupported; }
 int pt_debug_block(void) { return 256; }
+hipError_t pt_launch_aov(const PtKernelParams*, const PtAovArgs*, int, int, size_t, hipStream_t) { return hipErrorNotSupported; }
+hipError_t pt_aov_geometry(int, int, int, PtGeometry*) { return hipErrorNotSupported; }
+hipError_t pt_launch_aov_wt(const PtKernelParams*, const PtAovArgs*, int, int, size_t, hipStream_t) { return hipErrorNotSupported; }
+hipError_t pt_aov_geometry_wt(int, int, int, PtGeometry*) { return hipErrorNotSupported; }
 hipError_t pt_launch_probe(const PtKernelParams*, int, const float*, int, float*, int, long long, int, size_t, uint32_t*, hipStream_t) { return hipErrorNotSupported; }
 int pt_probe_lds_stack(void) { return 12; }
 size_t pt_probe_group_lds_bytes(int, int) { return 16; }

@@ -38,6 +38,12 @@ void fill_params(pt_ctx* c, PtKernelParams& P)
 // After the render stream has drained: did a wave's watchdog fire (pt_kernel.hip, PT_WATCHDOG_ROUNDS)?  The image is then incomplete.
 int check_watchdog(pt_ctx* c)
 {
+    if (c->last.aov_flag_pending && c->d_aov_ws.p) { // the last call was a guide pass: its walks' step and stack bound (pt_kernel.hip, pt_aov_kernel)
+        uint32_t fired = 0;
+        HIP_TRY(c, hipMemcpy(&fired, c->d_aov_ws.p, 4, hipMemcpyDeviceToHost));
+        c->last.aov_flag_pending = false;
+        if (fired) return fail(c, PT_E_HIP, "guide pass: a walk ran out of its step or stack bound; the buffers are incomplete");
+    }
     if (c->opt.kernel != 2 || !c->d_laps.p || !c->last.flag_pending) return PT_OK;
     uint32_t wd = 0;
     HIP_TRY(c, hipMemcpy(&wd, c->d_laps.p, 4, hipMemcpyDeviceToHost));
@@ -425,6 +431,7 @@ int finish_frame(pt_ctx* c, hipStream_t stream, int W, int H, const FramePlan* f
     L.w = W;
     L.h = H;
     L.seqs = first ? 1 : L.seqs + 1;
+    L.aov_flag_pending = false;
     c->stats.express_pixels = f ? (int32_t)f->n_express : 0;
     c->stats.whole_pixels = f && f->tiers ? (int32_t)c->n_pixels : 0;
     c->stats.prepass_spp = f && f->sorted ? f->pre : 0;
@@ -614,9 +621,118 @@ int read_back(pt_ctx* c, bool root, float* out_rgb, uint32_t* out_rgba8, size_t 
     return check_watchdog(c);
 }
 
+// ---- guide pass (pt_render_aov) --------------------------------------------------------------------------------------------
+// One launch of the guide kernel over the frame's 8 x 8 pixel blocks; the kernel itself skips the blocks of other ranks' tiles, so the
+// pass needs no pixel queue and none of the render's buffers: it leaves the state of the render path (queue, d_laps, slots) alone.
+#define PT_AOV_FLAG_WORDS 64 // d_aov_ws: the bound flag on a line of its own, then the overflow columns
+int aov_device(pt_ctx* c, const pt_camera* cam, int W, int H, int n_samples, void* d_out, hipStream_t stream)
+{
+    // refusals first: nothing is enqueued or allocated before them
+    const bool quad = c->opt.quad && !c->scene.nodes4.empty();
+    const bool wt = c->opt.watertight != 0;
+    if (!quad && wt)
+        return fail(c, PT_E_INVALID, "pt_render_aov: without quad nodes (option quad = 0, or a tree too deep for them) the guide pass runs the binary walk, which has no watertight test (option watertight = 1)");
+    if (quad && (c->scene.bvh.tris.size() * sizeof(PtTri) > 0xffffffffull || c->scene.nodes4.size() * sizeof(PtNode4) > 0xffffffffull))
+        return fail(c, PT_E_LIMIT, "the guide kernel needs triangle records and quad nodes below 4 GiB each (%zu triangle slots, %zu quad nodes)", c->scene.bvh.tris.size(), c->scene.nodes4.size());
+    PtKernelParams P;
+    walk_params(c, cam, P); // the scene, the slab form ("box_exact" as the render)
+    P.nodes8 = nullptr;
+    P.groups = 0;
+    if (quad) {
+        P.nodes4 = (const PtNode4*)c->d_nodes4.p;
+        P.root = c->scene.root4;
+        P.stack_entries = 3 * c->scene.depth4 + 1;
+    } else {
+        P.nodes4 = nullptr;
+        P.root = c->scene.bvh.root;
+        P.stack_entries = c->scene.bvh.depth < 1 ? 1 : c->scene.bvh.depth;
+    }
+    PtGeometry g{};
+    const hipError_t ge = (wt ? pt_aov_geometry_wt : pt_aov_geometry)(quad ? 0 : 1, P.box_exact, P.stack_entries, &g);
+    if (ge == hipErrorInvalidConfiguration) return fail(c, PT_E_LIMIT, "this build of the guide kernel spills registers to scratch; such builds are refused (pt_kernel.hip)");
+    HIP_TRY(c, ge);
+    if (g.max_blocks_per_cu < 1) return fail(c, PT_E_LIMIT, "guide kernel does not fit a CU (LDS %zu bytes, BVH depth %d)", g.lds_bytes, c->scene.bvh.depth);
+    int tile = c->tile < 8 ? 8 : c->tile; // as pt_shard_pixels rounds it
+    tile = (tile + 7) & ~7;
+    if (pt_shard_pixels(W, H, tile, c->rank, c->world, nullptr, 0) < 0) return fail(c, PT_E_INVALID, "invalid pixel shard (%d of %d)", c->rank, c->world);
+    const long n_blocks = (long)((W + 7) / 8) * (long)((H + 7) / 8);
+    const int grid = (int)std::max(1L, std::min(n_blocks, (long)c->num_cus * 32)); // a few rounds of resident waves: the blocks differ in cost
+    PtAovArgs A{};
+    A.cap = quad ? P.stack_entries + 3 : 0;
+    const size_t ovf_words = quad ? (size_t)std::max(0, A.cap - g.lds_levels) * 64 * (size_t)grid : 0;
+    int rc;
+    if ((rc = ensure(c, c->d_aov_ws, (PT_AOV_FLAG_WORDS + ovf_words) * 4))) return rc;
+    HIP_TRY(c, hipMemsetAsync(c->d_aov_ws.p, 0, PT_AOV_FLAG_WORDS * 4, stream));
+    HIP_TRY(c, hipMemsetAsync(d_out, 0, (size_t)W * H * 8 * sizeof(float), stream)); // pixels of other ranks stay 0
+    P.error_flag = (uint32_t*)c->d_aov_ws.p;
+    P.lds_levels = g.lds_levels;
+    std::memcpy(P.cam, cam, sizeof(float) * 12);
+    P.width = W;
+    P.height = H;
+    A.out = (float*)d_out;
+    A.ovf = (uint32_t*)c->d_aov_ws.p + PT_AOV_FLAG_WORDS;
+    A.n_samples = n_samples;
+    A.rank = c->rank; A.world = c->world; A.tile = tile;
+    HIP_TRY(c, hipEventRecord(c->ev0, stream));
+    HIP_TRY(c, (wt ? pt_launch_aov_wt : pt_launch_aov)(&P, &A, quad ? 0 : 1, grid, g.lds_bytes, stream));
+    // what pt_synchronize and pt_get_stats look at: kernel_ms / launches of this launch (finish_frame is the render's)
+    HIP_TRY(c, hipEventRecord(c->ev1, stream));
+    LastFrame& L = c->last;
+    L.ev_pending = true;
+    L.flag_pending = false;
+    L.aov_flag_pending = true;
+    L.stream = stream;
+    L.launches = 1;
+    L.sorted = false;
+    L.w = W;
+    L.h = H;
+    L.seqs = 1;
+    c->stats.express_pixels = c->stats.whole_pixels = c->stats.prepass_spp = 0;
+    c->stats.grid = grid;
+    c->stats.vgprs = g.vgprs;
+    c->stats.lds_bytes = (int)g.lds_bytes;
+    c->stats.block = g.block;
+    c->stats.stack_entries = P.stack_entries;
+    return PT_OK;
+}
+
 } // namespace
 
 extern "C" {
+
+int pt_render_aov_device(pt_ctx* c, const pt_camera* cam, int32_t W, int32_t H, int32_t n_samples, void* d_out_aov, void* stream_v)
+{
+    if (!c || !cam || !d_out_aov) return PT_E_INVALID;
+    int rc;
+    if ((rc = need_device(c)) || (rc = check_render_args(c, W, H, n_samples, 0))) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    return aov_device(c, cam, W, H, n_samples, d_out_aov, stream_v ? (hipStream_t)stream_v : c->stream);
+}
+
+int pt_render_aov(pt_ctx* c, const pt_camera* cam, int32_t W, int32_t H, int32_t n_samples, float* out_aov)
+{
+    // with a communicator attached only rank 0 receives the buffers (as pt_render)
+    const bool root = !c || !c->comm || c->comm_rank == 0;
+    if (!c || !cam || (root && !out_aov)) return PT_E_INVALID;
+    int rc;
+    if ((rc = need_device(c)) || (rc = check_render_args(c, W, H, n_samples, 0))) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t n_floats = (size_t)W * H * 8;
+    if ((rc = ensure(c, c->d_aov, n_floats * 4))) return rc;
+    if ((rc = aov_device(c, cam, W, H, n_samples, c->d_aov.p, c->stream))) return rc;
+    // N ranks: ONE sum-reduce of the W*H*8 floats onto rank 0; one non-zero contributor per pixel, so the sum is exact
+    if (c->comm && (rc = reduce_sum(c, c->d_aov.p, n_floats, c->stream))) return rc;
+    HIP_TRY(c, hipEventRecord(c->evr, c->stream));
+    if (root) HIP_TRY(c, hipMemcpyAsync(out_aov, c->d_aov.p, n_floats * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipEventRecord(c->evd, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    float ms = 0.0f;
+    HIP_TRY(c, hipEventElapsedTime(&ms, c->ev1, c->evr));
+    c->stats.reduce_ms = ms;
+    HIP_TRY(c, hipEventElapsedTime(&ms, c->evr, c->evd));
+    c->stats.d2h_ms = ms;
+    return check_watchdog(c);
+}
 
 int pt_render_device(pt_ctx* c, const pt_camera* cam, int32_t W, int32_t H, int32_t max_samples, int32_t max_depth, void* d_out_rgb,
                      void* d_out_rgba8, void* stream_v)

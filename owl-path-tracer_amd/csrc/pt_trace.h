@@ -397,7 +397,8 @@ __device__ __forceinline__ void node_step(const PtNode* __restrict__ nodes, uint
     }
 }
 
-template <bool COUNT>
+// STRIDE: words between two levels of a lane's stack = threads of the workgroup (the guide kernel of pt_kernel.hip runs it with one wave)
+template <bool COUNT, int STRIDE = PT_BLOCK>
 __device__ __forceinline__ void closest_hit(const PtKernelParams& P, uint32_t* stack, v3 o, v3 d, Hit& h, Counters& cn)
 {
     h.t = kTMax; h.u = 0.0f; h.v = 0.0f; h.id = 0x7fffffff; h.slot = -1;
@@ -409,7 +410,7 @@ __device__ __forceinline__ void closest_hit(const PtKernelParams& P, uint32_t* s
     for (;;) {
         while (cur >= 0) { // internal nodes: runs until every lane of the wave is at a leaf or finished
             if (COUNT) ++cn.nodes;
-            node_step<PT_BLOCK, 0x7fffffff>(nodes, stack, nullptr, o, inv, h.t, cur, sp);
+            node_step<STRIDE, 0x7fffffff>(nodes, stack, nullptr, o, inv, h.t, cur, sp);
         }
         if (cur == PT_DONE) break;
         uint32_t code = ~(uint32_t)cur;
@@ -420,7 +421,7 @@ __device__ __forceinline__ void closest_hit(const PtKernelParams& P, uint32_t* s
         }
         if (sp == 0) break;
         --sp;
-        cur = (int)stack[sp * PT_BLOCK];
+        cur = (int)stack[sp * STRIDE];
     }
 }
 

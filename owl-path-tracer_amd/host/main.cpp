@@ -11,6 +11,9 @@
 // --batch K (K >= 1: test_loop collects K sweep steps and renders them with ONE pt_render_batch - one launch sequence for K frames -
 // instead of K x pt_set_materials + pt_render; the PNGs are byte for byte the same; not together with --gpus / --devices),
 // --watertight (option "watertight" = 1 on every context: the watertight triangle test, mi355pt.h; not together with --batch).
+// --aov N (N >= 1: after every frame the guide pass with N samples per pixel - pt_render_aov / pt_group_render_aov, mi355pt.h - and three
+// more files next to <name>.png: <name>_albedo.png = make_rgba of the albedo, <name>_normal.png = make_rgba of 0.5 * n + 0.5,
+// <name>_depth.png = grey, depth / the frame's largest depth; works with --gpus / --devices and --watertight, not with --batch).
 #include <sys/stat.h>
 #include <unistd.h>
 
@@ -89,11 +92,48 @@ struct App {
     pt_camera cam{};
     std::string out_dir;
     int batch = 0; // --batch K: sweep steps per pt_render_batch (0: one pt_render per step)
+    int aov = 0;   // --aov N: samples per pixel of the guide pass after every frame (0: none)
 };
 
 void check(App& a, int rc, const char* what)
 {
     if (rc < 0) throw std::runtime_error(std::string(what) + ": " + (a.group ? pt_group_last_error(a.group) : pt_last_error(a.ctx)));
+}
+
+// owl::make_rgba as csrc/pt_device.h has it: min(255, max(0, int(f * 256))) per channel, alpha 255
+uint32_t make_8bit(float f)
+{
+    const float s = f * 256.0f;
+    int v = (s != s) ? 0 : (s >= 2147483520.0f ? 2147483647 : (s <= -2147483520.0f ? -2147483647 : (int)s));
+    v = v < 0 ? 0 : v;
+    return (uint32_t)(v > 255 ? 255 : v);
+}
+uint32_t make_rgba(float r, float g, float b) { return make_8bit(r) | (make_8bit(g) << 8) | (make_8bit(b) << 16) | (0xffu << 24); }
+
+// --aov: the guide buffers of the frame just rendered, as three PNGs next to it (base = the frame's path without ".png")
+void write_guides(App& a, const std::string& base)
+{
+    const int W = a.settings.buffer_size[0], H = a.settings.buffer_size[1];
+    const size_t npx = (size_t)W * H;
+    std::vector<float> g(npx * 8);
+    if (a.group) check(a, pt_group_render_aov(a.group, &a.cam, W, H, a.aov, g.data()), "pt_group_render_aov");
+    else check(a, pt_render_aov(a.ctx, &a.cam, W, H, a.aov, g.data()), "pt_render_aov");
+    float far = 0.0f;
+    for (size_t i = 0; i < npx; ++i) far = g[8 * i + 7] > far ? g[8 * i + 7] : far;
+    std::vector<uint32_t> albedo(npx), normal(npx), depth(npx);
+    for (size_t i = 0; i < npx; ++i) {
+        const float* p = &g[8 * i];
+        albedo[i] = make_rgba(p[0], p[1], p[2]);
+        normal[i] = make_rgba(0.5f * p[4] + 0.5f, 0.5f * p[5] + 0.5f, 0.5f * p[6] + 0.5f);
+        const float d = far > 0.0f ? p[7] / far : 0.0f;
+        depth[i] = make_rgba(d, d, d);
+    }
+    const char* names[3] = {"_albedo.png", "_normal.png", "_depth.png"};
+    const std::vector<uint32_t>* img[3] = {&albedo, &normal, &depth};
+    for (int k = 0; k < 3; ++k) {
+        imgio::write_png_rgba8(base + names[k], W, H, img[k]->data());
+        std::printf("Image written to %s\n", (base + names[k]).c_str());
+    }
 }
 
 // render_frame, application.cpp:363-371
@@ -116,6 +156,7 @@ void render_frame(App& a, const std::string& values)
     imgio::write_png_rgba8(path, W, H, rgba.data());
     std::printf("Image written to %s\n", path.c_str());
     std::fprintf(stderr, "  %.1f ms kernel, %.1f Msamples/s\n", st.kernel_ms, (double)W * H * a.settings.max_samples / (st.kernel_ms * 1e3));
+    if (a.aov > 0) write_guides(a, path.substr(0, path.size() - 4));
 }
 
 // --batch: the collected sweep steps (material table and value string each) as one pt_render_batch; one PNG per step as render_frame writes it
@@ -206,7 +247,7 @@ int main(int argc, char** argv)
         std::string settings_path, dump;
         a.out_dir = cwd;
         int device = 0, gpus = 0; // gpus 0: flag not given, single context as in the reference
-        bool have_device = false, have_devices = false, have_batch = false, watertight = false;
+        bool have_device = false, have_devices = false, have_batch = false, have_aov = false, watertight = false;
         std::vector<int32_t> devs; // --devices
         for (int i = 1; i < argc; ++i) {
             std::string k = argv[i];
@@ -219,6 +260,7 @@ int main(int argc, char** argv)
             else if (k == "--gpus") gpus = std::atoi(next().c_str());
             else if (k == "--dump-scene") dump = next();
             else if (k == "--batch") { a.batch = std::atoi(next().c_str()); have_batch = true; }
+            else if (k == "--aov") { a.aov = std::atoi(next().c_str()); have_aov = true; }
             else if (k == "--watertight") watertight = true;
             else if (k == "--convert-png" || k == "--convert-hdr") { // codec self-test hooks: decode with our reader, re-encode with our writer
                 std::string in = next(), out = next();
@@ -237,6 +279,8 @@ int main(int argc, char** argv)
                 throw std::runtime_error("--devices names " + std::to_string(devs.size()) + " device(s) but --gpus says " + std::to_string(gpus));
             gpus = (int)devs.size();
         }
+        if (have_aov && a.aov < 1) throw std::runtime_error("--aov needs a positive number of samples per pixel");
+        if (have_aov && have_batch) throw std::runtime_error("--aov cannot be combined with --batch (the guide pass has no batch form)");
         if (have_batch && watertight) throw std::runtime_error("--batch cannot be combined with --watertight (pt_render_batch has no watertight instances)");
         if (settings_path.empty()) settings_path = assets + "/settings.json"; // application.cpp:145
 

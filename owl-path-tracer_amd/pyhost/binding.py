@@ -85,7 +85,8 @@ EXPORTS = ["pt_create", "pt_destroy", "pt_last_error", "pt_abi_version", "pt_upl
            "pt_comm_get_unique_id", "pt_comm_init_rank", "pt_comm_destroy", "pt_reduce_framebuffer", "pt_host_alloc", "pt_host_free",
            "pt_group_create", "pt_group_destroy", "pt_group_size", "pt_group_ctx", "pt_group_last_error", "pt_group_upload_scene",
            "pt_group_set_materials", "pt_group_set_option", "pt_group_render", "pt_debug_quad_info", "pt_debug_oct_info", "pt_debug_clone_scene",
-           "pt_render_batch", "pt_render_batch_device", "pt_debug_plan_batch", "pt_update_vertices", "pt_group_update_vertices", "pt_debug_update_info"]
+           "pt_render_batch", "pt_render_batch_device", "pt_debug_plan_batch", "pt_update_vertices", "pt_group_update_vertices", "pt_debug_update_info",
+           "pt_render_aov", "pt_render_aov_device", "pt_group_render_aov", "pt_debug_aov_host"]
 PT_TREE_DEVICE = 16  # pt_debug_export_tree: ORed into `which`, the array as HBM holds it
 PT_COMM_ID_BYTES = 128
 
@@ -170,6 +171,11 @@ def lib():
     L.pt_update_vertices.argtypes = [C.c_void_p, C.POINTER(Mesh), C.c_int32]
     L.pt_group_update_vertices.argtypes = [C.c_void_p, C.POINTER(Mesh), C.c_int32]
     L.pt_debug_update_info.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+    L.pt_render_aov.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_int32, C.c_int32, C.c_int32, fp]
+    L.pt_render_aov_device.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+    L.pt_group_render_aov.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_int32, C.c_int32, C.c_int32, fp]
+    L.pt_debug_aov_host.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_uint32), C.c_int64, fp]
+    L.pt_debug_aov_host.restype = C.c_int64
     _lib = L
     return L
 
@@ -452,6 +458,29 @@ class Context:
         self._check(lib().pt_render(self._h, C.byref(cam), W, H, spp, max_depth, rgb.ctypes.data_as(C.POINTER(C.c_float)) if rgb is not None else None,
                                     rgba8.ctypes.data_as(C.POINTER(C.c_uint32)) if rgba8 is not None else None), "pt_render")
 
+    def render_aov(self, cam, W, H, n_samples, receive=True):
+        """pt_render_aov: the guide buffers of the frame, (H, W, 8) float32 = albedo r g b, alpha, normal x y z, depth per pixel (first hit
+        only; include/mi355pt.h "guide pass").  receive = False: a non-root rank of a communicator (returns None)."""
+        out = np.empty((H, W, 8), np.float32) if receive else None
+        self._check(lib().pt_render_aov(self._h, C.byref(cam), W, H, n_samples, out.ctypes.data_as(C.POINTER(C.c_float)) if receive else None), "pt_render_aov")
+        return out
+
+    def render_aov_device(self, cam, W, H, n_samples, d_out_aov, stream=None):
+        """pt_render_aov_device: asynchronous, W*H*8 floats left in HBM at the device pointer d_out_aov; synchronize() waits for it."""
+        self._check(lib().pt_render_aov_device(self._h, C.byref(cam), W, H, n_samples, C.c_void_p(d_out_aov), C.c_void_p(stream) if stream else None),
+                    "pt_render_aov_device")
+
+    def aov_host(self, cam, W, H, n_samples, pixel_ids=None):
+        """pt_debug_aov_host, the CPU twin of render_aov (works on a host-only context): (n, 8) float32 for the listed launch-index pixel ids
+        x + W*y; pixel_ids None: every pixel, returned as (H, W, 8) in the framebuffer order of render_aov (row 0 = the top row, y = H-1)."""
+        whole = pixel_ids is None
+        ids = np.arange(W * H, dtype=np.uint32) if whole else np.ascontiguousarray(pixel_ids, np.uint32).reshape(-1)
+        out = np.zeros((ids.size, 8), np.float32)
+        n = lib().pt_debug_aov_host(self._h, C.byref(cam), W, H, n_samples, ids.ctypes.data_as(C.POINTER(C.c_uint32)), ids.size, out.ctypes.data_as(C.POINTER(C.c_float)))
+        if n < 0:
+            self._check(int(n), "pt_debug_aov_host")
+        return out.reshape(H, W, 8)[::-1].copy() if whole else out
+
     def comm_init_rank(self, unique_id, rank, world):
         buf = (C.c_uint8 * PT_COMM_ID_BYTES).from_buffer_copy(unique_id)
         self._check(lib().pt_comm_init_rank(self._h, buf, rank, world), "pt_comm_init_rank")
@@ -642,3 +671,9 @@ class Group:
         self._check(lib().pt_group_render(self._g, C.byref(cam), W, H, spp, max_depth, rgb.ctypes.data_as(C.POINTER(C.c_float)),
                                           rgba.ctypes.data_as(C.POINTER(C.c_uint32)) if rgba is not None else None), "pt_group_render")
         return rgb, rgba
+
+    def render_aov(self, cam, W, H, n_samples):
+        """pt_group_render_aov: the guide buffers (H, W, 8) of the frame, every device's own tiles reduced onto devices[0]."""
+        out = np.empty((H, W, 8), np.float32)
+        self._check(lib().pt_group_render_aov(self._g, C.byref(cam), W, H, n_samples, out.ctypes.data_as(C.POINTER(C.c_float))), "pt_group_render_aov")
+        return out
