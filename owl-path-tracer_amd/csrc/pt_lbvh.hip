@@ -450,7 +450,9 @@ extern "C" size_t pt_ploc_workspace_bytes(int n)
 }
 
 // d_pos: n * 9 floats.  Host outputs (capacity 2n - 1 each unless stated): h_child (both -1 for node i < n: triangle h_order[i]), h_box (6 floats per
-// node), h_count (triangles below), h_order (n), *h_root, *h_rounds.
+// node), h_count (triangles below), h_order (n), *h_root, *h_rounds.  *h_root = -1 with hipSuccess: more than PT_PLOC_MAX_ROUNDS rounds
+// would be needed; the other outputs are then not written.
+#define PT_PLOC_MAX_ROUNDS 4096
 extern "C" hipError_t pt_ploc_build_device(const float* d_pos, int n, int radius, void* d_workspace, size_t workspace_bytes, int* h_child, float* h_box, int* h_count,
                                            uint32_t* h_order, int32_t* h_root, int32_t* h_rounds, hipStream_t stream)
 {
@@ -499,7 +501,14 @@ extern "C" hipError_t pt_ploc_build_device(const float* d_pos, int n, int radius
         (void)hipMemcpyAsync(&last_valid, valid + (m - 1), 4, hipMemcpyDeviceToHost, stream);
         if ((e = hipStreamSynchronize(stream)) != hipSuccess) return e;
         const int m_new = (int)(last_off + last_valid);
-        if (m_new >= m || m_new < 1 || ++rounds > 4096) return hipErrorUnknown; // the smallest union is always a mutual pair: every round merges
+        if (m_new >= m || m_new < 1) return hipErrorUnknown; // the smallest union is always a mutual pair: every round merges
+        // round budget: on a strip of equal-width triangles a single pair is mutual per round (n / 2 rounds, each four launches and a
+        // synchronise).  Out of budget is not an error: no hierarchy (*h_root = -1) and the caller's host builder takes over.
+        if (++rounds >= PT_PLOC_MAX_ROUNDS && m_new > 1) {
+            *h_root = -1;
+            *h_rounds = rounds;
+            return hipSuccess;
+        }
         m = m_new;
         int* t = cid; cid = cid_next; cid_next = t;
     }

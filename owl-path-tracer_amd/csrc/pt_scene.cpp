@@ -154,7 +154,7 @@ int flatten_meshes(pt_ctx* c, const pt_mesh* meshes, int32_t n_meshes, int32_t n
 }
 
 // device PLOC (pt_lbvh.hip): the hierarchy comes down, the host lays it out (pt_bvh_from_hierarchy).  built = false: deeper than the
-// stack allows.
+// stack allows, or the device ran out of its round budget (root < 0) - build_bvh then builds on the host.
 int build_ploc(pt_ctx* c, const std::vector<float>& pos, int n, bool& built)
 {
     std::vector<int32_t> h_child(2 * (size_t)n * 2), h_count(2 * (size_t)n);
@@ -169,6 +169,7 @@ int build_ploc(pt_ctx* c, const std::vector<float>& pos, int n, bool& built)
                                             &rounds, c->stream);
         if (e != hipSuccess) return fail(c, PT_E_HIP, "device PLOC build failed: %s", hipGetErrorString(e));
     }
+    if (root < 0) return PT_OK; // out of rounds: nothing came down and scene.bvh has not been touched
     built = pt_bvh_from_hierarchy(pos.data(), n, h_child.data(), h_box.data(), h_count.data(), h_order.data(), root, c->opt.leaf_size, c->opt.max_bvh_depth, &c->scene.bvh);
     return PT_OK;
 }
@@ -228,6 +229,8 @@ int build_bvh(pt_ctx* c, const std::vector<float>& pos, size_t n_tris)
         if (rc) return rc;
     }
     // the host builder: the default, and - because it caps the depth - what takes over from a device builder instead of failing the upload
+    // (a tree deeper than max_bvh_depth, PLOC out of rounds).  pt_bvh_build resets every field of scene.bvh first: nothing of the nodes
+    // build_lbvh read back or of the partial layout of pt_bvh_from_hierarchy survives, and upload_scene_to_device rewrites d_nodes.
     if (!built) pt_bvh_build(pos.data(), (int32_t)n_tris, c->opt.leaf_size, c->opt.max_bvh_depth, &c->scene.bvh);
     return PT_OK;
 }
