@@ -135,9 +135,9 @@ int pt_set_environment(pt_ctx* ctx, const pt_env* env);
  * counterpart: the reference rebuilds its acceleration structure, application.cpp:131-140) ----
  * Needs a scene uploaded with option "dynamic" = 1.  Reads ONLY these fields of each mesh: vertices (NULL = this mesh is unchanged),
  * normals (NULL = keep the normals the library holds), n_vertices and n_normals; n_meshes and these counts must equal the upload's,
- * everything else in pt_mesh is ignored (indices may be NULL).  Blocking; waits for the frames in flight.  Every argument is checked
- * before anything is touched: a refused call (PT_E_NO_SCENE: no scene; PT_E_INVALID: scene not uploaded with "dynamic" = 1, a count
- * that differs, a NULL array with a non-zero count) leaves the scene exactly as it was.
+ * everything else in pt_mesh is ignored (indices may be NULL).  Blocking; waits for the frames in flight, on a caller's stream too
+ * (pt_render_device).  Every argument is checked before anything is touched: a refused call (PT_E_NO_SCENE: no scene; PT_E_INVALID:
+ * scene not uploaded with "dynamic" = 1, a count that differs, a NULL array with a non-zero count) leaves the scene exactly as it was.
  * The topology of the three hierarchies stays; triangle records, sliver collapse, padding and every box become bit for bit what a fresh
  * pt_upload_scene of the moved meshes would store for that topology, so - the closest hit being independent of the hierarchy - every
  * frame, probe and counter after the call equals the one after a fresh upload.  What does not follow the geometry is the QUALITY of the
@@ -159,11 +159,38 @@ int64_t pt_shard_pixels(int32_t width, int32_t height, int32_t tile, int32_t ran
 int pt_render(pt_ctx* ctx, const pt_camera* cam, int32_t width, int32_t height, int32_t max_samples, int32_t max_path_depth,
               float* out_rgb, uint32_t* out_rgba8);
 /* Same render, asynchronous on `stream` (a hipStream_t; NULL = the context's own stream), result left
- * in HBM at d_out_rgb (device pointer, W*H*3 floats) for the caller's RCCL reduce.  d_out_rgba8 optional. */
+ * in HBM at d_out_rgb (device pointer, W*H*3 floats) for the caller's RCCL reduce.  d_out_rgba8 optional.
+ *
+ * STREAMS AND WHAT MAY BE CALLED WHILE A FRAME IS IN FLIGHT.  A context has ONE frame's worth of work buffers (pixel queue, rings,
+ * cost image, sort, tier plan, kernel parameters, RNG and accumulation state, counters), one copy of the scene in HBM and one set of
+ * timing events.  The context's own stream is non-blocking: HIP orders nothing between it and a caller's stream.  THE LIBRARY does:
+ * every call that touches what a frame in flight uses is ordered after the context's LAST ASYNCHRONOUS CALL, whichever stream that
+ * call was given.  So any call of this header may follow a pt_*_device call at once, with no pt_synchronize between them.
+ *   - The asynchronous calls (pt_render_device, pt_render_batch_device, pt_render_aov_device, pt_reduce_framebuffer) wait ON THE
+ *     DEVICE: the stream they are given waits for an event recorded at the end of the previous asynchronous call - only if that call
+ *     used another stream; on the same stream the stream's own order suffices and nothing is added.  The host returns at once, with
+ *     two exceptions that existed before: a frame of another size, shard or batch length rewrites the pixel queue and a frame that
+ *     needs larger work buffers reallocates them - both first wait on the host for the frame in flight; and pt_render_batch_device
+ *     returns when its per-frame tables have reached HBM, i.e. after whatever precedes it on `stream`.
+ *   - The blocking renders (pt_render, pt_render_batch, pt_render_aov) run on the context's stream behind the same device-side wait
+ *     and return with the context idle.  After a blocking call, or on the context's own stream, they add no wait at all.
+ *   - The calls that change or read what a frame uses WAIT ON THE HOST for the last asynchronous call's stream (if it is not the
+ *     context's) and then for the context's: pt_set_materials, pt_set_environment, pt_update_vertices, pt_upload_scene,
+ *     pt_set_pixel_shard when it changes the shard of a queue in use, pt_comm_destroy, pt_destroy, pt_debug_eval and the pt_debug_*
+ *     readers of device state - and pt_synchronize, which is that wait plus the watchdog check.  A frame enqueued before such a call
+ *     renders the state before it, a frame enqueued after it the state after it.
+ *   - pt_get_stats waits for the end of the last frame's kernels (an event), not for the stream.
+ * WHAT STAYS THE CALLER'S BUSINESS: the output buffers - the library does not know who reads d_out_rgb, so a second frame into the
+ * same buffer, or a read of it, is ordered by the caller (same stream, an event of its own, or pt_synchronize); the stream - it must
+ * live until a pt_synchronize (or another of the host-waiting calls above) that follows the last call on it has returned; after
+ * that the library does not look at it again.  One thread at a time per context, as everywhere in this header. */
 int pt_render_device(pt_ctx* ctx, const pt_camera* cam, int32_t width, int32_t height, int32_t max_samples, int32_t max_path_depth,
                      void* d_out_rgb, void* d_out_rgba8, void* stream);
-/* Waits for the last pt_render_device (its stream and the context's) and returns PT_E_HIP if a wave's watchdog fired during
- * it (the image is then incomplete); pt_get_stats reports the same. */
+/* Waits on the host for the context's last asynchronous call - pt_render_device, pt_render_batch_device, pt_render_aov_device or
+ * pt_reduce_framebuffer, on the stream it was given - and for the context's own stream.  Every earlier asynchronous call of the context
+ * is complete then as well, whatever stream it used: each was ordered before the next (see pt_render_device).  Returns PT_E_HIP if a
+ * wave's watchdog fired during the last frame (the image is then incomplete); pt_get_stats reports the same.  PT_OK at once on an idle
+ * or host-only context.  A caller's stream may be destroyed once this has returned. */
 int pt_synchronize(pt_ctx* ctx);
 
 /* ---- batch render: K frames of the uploaded scene in one launch sequence (no reference counterpart: the reference's test_loop,

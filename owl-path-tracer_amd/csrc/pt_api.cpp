@@ -28,7 +28,11 @@ int ensure(pt_ctx* c, DevBuf& b, size_t bytes)
 {
     if (bytes == 0) bytes = 16;
     if (b.cap >= bytes) return PT_OK;
-    if (b.p) HIP_TRY(c, hipFree(b.p));
+    if (b.p) { // a buffer grows: nothing in flight may still use the old one (a frame on a caller's stream included)
+        int rc = wait_idle(c);
+        if (rc) return rc;
+        HIP_TRY(c, hipFree(b.p));
+    }
     b.p = nullptr;
     b.cap = 0;
     HIP_TRY(c, hipMalloc(&b.p, bytes));
@@ -41,6 +45,29 @@ int upload(pt_ctx* c, DevBuf& b, const void* src, size_t bytes)
     int rc = ensure(c, b, bytes);
     if (rc) return rc;
     if (bytes) HIP_TRY(c, hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, c->stream));
+    return PT_OK;
+}
+
+int order_after_last(pt_ctx* c, hipStream_t stream)
+{
+    if (c->last.stream && c->last.stream != stream) HIP_TRY(c, hipStreamWaitEvent(stream, c->evo, 0));
+    return PT_OK;
+}
+
+int mark_last(pt_ctx* c, hipStream_t stream)
+{
+    HIP_TRY(c, hipEventRecord(c->evo, stream));
+    c->last.stream = stream;
+    return PT_OK;
+}
+
+int wait_idle(pt_ctx* c)
+{
+    if (c->host_only) return PT_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (c->last.stream && c->last.stream != c->stream) HIP_TRY(c, hipStreamSynchronize(c->last.stream)); // an asynchronous call on a caller's stream
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->last.stream = nullptr; // (the caller's stream is not looked at again: it may be destroyed from here on)
     return PT_OK;
 }
 
@@ -88,7 +115,7 @@ pt_ctx* pt_create(const pt_config* cfg)
     c->num_cus = prop.multiProcessorCount;
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess || hipEventCreate(&c->ev0) != hipSuccess ||
         hipEventCreate(&c->ev1) != hipSuccess || hipEventCreate(&c->evm) != hipSuccess || hipEventCreate(&c->evr) != hipSuccess ||
-        hipEventCreate(&c->evd) != hipSuccess) {
+        hipEventCreate(&c->evd) != hipSuccess || hipEventCreateWithFlags(&c->evo, hipEventDisableTiming) != hipSuccess) {
         fail(nullptr, PT_E_HIP, "stream/event creation failed");
         return refuse();
     }
@@ -99,10 +126,9 @@ void pt_destroy(pt_ctx* c)
 {
     if (!c) return;
     if (!c->host_only) {
-        (void)hipSetDevice(c->device);
-        (void)hipStreamSynchronize(c->stream);
+        (void)wait_idle(c);
         (void)pt_comm_destroy(c);
-        for (hipEvent_t e : {c->ev0, c->ev1, c->evm, c->evr, c->evd, c->evu0, c->evu1})
+        for (hipEvent_t e : {c->ev0, c->ev1, c->evm, c->evr, c->evd, c->evo, c->evu0, c->evu1})
             if (e) (void)hipEventDestroy(e);
         if (c->stream) (void)hipStreamDestroy(c->stream);
     }
@@ -205,6 +231,11 @@ int pt_set_pixel_shard(pt_ctx* c, int32_t rank, int32_t world_size, int32_t tile
 {
     if (!c) return PT_E_INVALID;
     if (world_size < 1 || rank < 0 || rank >= world_size || tile < 1) return fail(c, PT_E_INVALID, "bad shard %d/%d tile %d", rank, world_size, tile);
+    if (!c->host_only && c->queue_valid && (rank != c->rank || world_size != c->world || tile != c->tile)) { // the pixel queue is another one from here on
+        int rc = wait_idle(c);
+        if (rc) return rc;
+        c->queue_valid = false;
+    }
     c->rank = rank;
     c->world = world_size;
     c->tile = tile;

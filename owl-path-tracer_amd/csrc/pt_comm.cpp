@@ -95,6 +95,18 @@ int reduce_sum(pt_ctx* c, void* d_buf, size_t n_floats, hipStream_t stream)
     RCCL_TRY(c, g_rccl.Reduce(d_buf, d_buf, n_floats, ncclFloat32, ncclSum, 0, (ncclComm_t)c->comm, stream));
     return PT_OK;
 }
+
+int reduce_framebuffer(pt_ctx* c, void* d_rgb, void* d_rgba8, int64_t n_pixels, hipStream_t stream)
+{
+    if (!c->comm) return PT_OK;
+    // ONE collective, in place on every rank; only the root's buffer holds the sum afterwards.  The RGBA8 image is not reduced: every
+    // pixel has exactly one non-zero contributor, so the root quantises the reduced float frame and gets bit for bit what the owning
+    // rank would have stored - and the number of collectives a rank enqueues never depends on the buffers its caller happened to pass
+    // (round 2 reduced d_rgba8 only where it was non-null: a root with an RGBA8 buffer and peers without one deadlocked).
+    RCCL_TRY(c, g_rccl.Reduce(d_rgb, d_rgb, (size_t)n_pixels * 3, ncclFloat32, ncclSum, 0, (ncclComm_t)c->comm, stream));
+    if (d_rgba8 && c->comm_rank == 0) HIP_TRY(c, pt_launch_pack_rgba8((const float*)d_rgb, (uint32_t*)d_rgba8, (long long)n_pixels, stream));
+    return PT_OK;
+}
 } // namespace pti
 
 struct pt_group {
@@ -141,8 +153,7 @@ int pt_comm_destroy(pt_ctx* c)
 {
     if (!c) return PT_E_INVALID;
     if (c->comm) {
-        (void)hipSetDevice(c->device);
-        (void)hipStreamSynchronize(c->stream);
+        (void)pti::wait_idle(c);
         (void)g_rccl.CommDestroy((ncclComm_t)c->comm);
         c->comm = nullptr;
     }
@@ -157,13 +168,13 @@ int pt_reduce_framebuffer(pt_ctx* c, void* d_rgb, void* d_rgba8, int64_t n_pixel
     if (!c->comm) return PT_OK; // a single rank owns every pixel: nothing to add
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t stream = stream_v ? (hipStream_t)stream_v : c->stream;
-    // ONE collective, in place on every rank; only the root's buffer holds the sum afterwards.  The RGBA8 image is not reduced: every
-    // pixel has exactly one non-zero contributor, so the root quantises the reduced float frame and gets bit for bit what the owning
-    // rank would have stored - and the number of collectives a rank enqueues never depends on the buffers its caller happened to pass
-    // (round 2 reduced d_rgba8 only where it was non-null: a root with an RGBA8 buffer and peers without one deadlocked).
-    RCCL_TRY(c, g_rccl.Reduce(d_rgb, d_rgb, (size_t)n_pixels * 3, ncclFloat32, ncclSum, 0, (ncclComm_t)c->comm, stream));
-    if (d_rgba8 && c->comm_rank == 0) HIP_TRY(c, pt_launch_pack_rgba8((const float*)d_rgb, (uint32_t*)d_rgba8, (long long)n_pixels, stream));
-    return PT_OK;
+    // an asynchronous call of its own: after the context's last one (the frame it reduces, if that went to another stream), and the
+    // last one from here on
+    int rc = pti::order_after_last(c, stream);
+    if (rc) return rc;
+    rc = pti::reduce_framebuffer(c, d_rgb, d_rgba8, n_pixels, stream);
+    const int rm = pti::mark_last(c, stream);
+    return rc ? rc : rm;
 }
 
 void* pt_host_alloc(size_t bytes)

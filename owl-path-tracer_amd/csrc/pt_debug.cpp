@@ -63,13 +63,9 @@ int probe_eval(pt_ctx* c, PtKernelParams& P, int op, int in_stride, float* out, 
     return PT_OK;
 }
 
-// Before a reader of device-side diagnostics copies anything: the context's GPU current and its render stream drained.
-int drain(pt_ctx* c)
-{
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return PT_OK;
-}
+// Before a reader of device-side diagnostics copies anything: the context's GPU current and the last frame complete, on whichever
+// stream it was enqueued.
+int drain(pt_ctx* c) { return wait_idle(c); }
 
 } // namespace
 
@@ -149,8 +145,8 @@ int pt_debug_eval(pt_ctx* c, int32_t op, const float* in, int32_t in_stride, flo
     if (!c || !in || !out || n < 0 || in_stride < 1 || out_stride < 1) return PT_E_INVALID;
     if (c->host_only) return fail(c, PT_E_NO_DEVICE, "host-only context: pt_debug_eval needs the GPU");
     if (n == 0) return PT_OK;
-    HIP_TRY(c, hipSetDevice(c->device));
     int rc;
+    if ((rc = wait_idle(c))) return rc; // the probes run on the context's stream: after a frame in flight on a caller's
     if ((rc = upload(c, c->d_dbg_in, in, (size_t)n * in_stride * 4))) return rc;
     if ((rc = ensure(c, c->d_dbg_out, (size_t)n * out_stride * 4))) return rc;
     HIP_TRY(c, hipMemsetAsync(c->d_dbg_out.p, 0, (size_t)n * out_stride * 4, c->stream));

@@ -74,11 +74,13 @@ struct QueueKey {
 };
 
 // What a finished frame - or launch sequence of a batch - leaves behind for pt_synchronize, pt_get_stats, the watchdog check and the
-// diagnostics readers.  Written by finish_frame (pt_render.cpp) alone; the readers only take the two pending marks down.
+// diagnostics readers.  Written by finish_frame (pt_render.cpp) alone; the readers only take the two pending marks down, and `stream`
+// belongs to the ordering helpers below (order_after_last, mark_last, wait_idle).
 struct LastFrame {
     bool ev_pending = false;    // ev0 .. ev1 have not been turned into pt_stats.kernel_ms yet
     bool flag_pending = false, watchdog_fired = false; // the watchdog flag of the last render has not been looked at yet / was set
-    hipStream_t stream = nullptr; // stream of the last pt_render_device (may be the caller's)
+    hipStream_t stream = nullptr; // stream of the context's last asynchronous call (may be the caller's), with evo recorded at its end;
+                                  // nullptr once the host has waited for it (pti::wait_idle, the end of a blocking render)
     int launches = 0;           // render-kernel launches, of all launch sequences of a batch (pt_stats.launches)
     bool sorted = false;
     int w = 0, h = 0;
@@ -95,6 +97,7 @@ struct pt_ctx {
     hipStream_t stream = nullptr;
     hipEvent_t evu0 = nullptr, evu1 = nullptr; // around the kernels of the last pt_update_vertices (created by the first one)
     hipEvent_t ev0 = nullptr, ev1 = nullptr, evm = nullptr, evr = nullptr, evd = nullptr; // evm: after the cost pre-pass and the queue sort; evr / evd: after the reduce / the read-back of pt_render
+    hipEvent_t evo = nullptr; // the ordering event: end of the last asynchronous call, on last.stream (no timing; never one of the events above)
     std::string err;
 
     HostScene scene;
@@ -131,6 +134,11 @@ int fail(pt_ctx* c, int code, const char* fmt, ...);
 int ensure(pt_ctx* c, DevBuf& b, size_t bytes);
 PT_LOCAL int upload(pt_ctx* c, DevBuf& b, const void* src, size_t bytes);
 PT_LOCAL int need_device(pt_ctx* c);
+// A context has ONE frame's worth of work buffers, so every call that touches them is ordered after the context's last asynchronous
+// call, whichever stream that call used (include/mi355pt.h, pt_render_device):
+PT_LOCAL int order_after_last(pt_ctx* c, hipStream_t stream); // before a call enqueues on `stream`: a device-side wait, and only when the last call used another stream
+PT_LOCAL int mark_last(pt_ctx* c, hipStream_t stream);        // after an asynchronous call has enqueued its last on `stream`
+PT_LOCAL int wait_idle(pt_ctx* c);                            // the blocking calls: the host waits for last.stream (if it is not the context's), then for the context's
 // pt_scene.cpp
 int upload_scene_to_device(pt_ctx* c);
 int clone_scene(pt_ctx* dst, const pt_ctx* src);
@@ -140,6 +148,7 @@ PT_LOCAL void material_row(const pt_ctx* c, float* dst, const float* src, int i)
 int check_watchdog(pt_ctx* c);
 PT_LOCAL void fill_params(pt_ctx* c, PtKernelParams& P);
 // pt_comm.cpp
+PT_LOCAL int reduce_framebuffer(pt_ctx* c, void* d_rgb, void* d_rgba8, int64_t n_pixels, hipStream_t stream); // pt_reduce_framebuffer inside a call that is ordered already
 PT_LOCAL int reduce_sum(pt_ctx* c, void* d_buf, size_t n_floats, hipStream_t stream); // in-place sum-reduce onto rank 0; nothing without a communicator
 } // namespace pti
 

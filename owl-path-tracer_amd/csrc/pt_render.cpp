@@ -64,19 +64,22 @@ namespace {
 
 // frames > 1 (pt_render_batch): the queue of the virtual image of W x (frames * H) - the shard of ONE frame, repeated per frame with the
 // ids moved down by the frames above it (id = x + W * (f * H + y)): a rank owns the same tiles in every frame.
-int ensure_queue(pt_ctx* c, int W, int H, int frames = 1)
+// stream: the one the call enqueues on - an earlier launch sequence of the same batch may still read the queue there.
+int ensure_queue(pt_ctx* c, int W, int H, int frames, hipStream_t stream)
 {
     const QueueKey key{W, H, frames, c->rank, c->world, c->tile};
     if (c->queue_valid && c->queue == key) return PT_OK;
     const int64_t n1 = pt_shard_pixels(W, H, c->tile, c->rank, c->world, nullptr, 0);
     if (n1 < 0) return fail(c, PT_E_INVALID, "invalid pixel shard (%d of %d)", c->rank, c->world);
     const int64_t n = n1 * frames;
+    int rc = wait_idle(c); // d_pixels is rewritten in place: after the frame in flight, whichever stream it is on ...
+    if (rc) return rc;
+    if (stream != c->stream) HIP_TRY(c, hipStreamSynchronize(stream)); // ... and after what this call itself has enqueued so far
     std::vector<uint32_t> ids((size_t)n);
     pt_shard_pixels(W, H, c->tile, c->rank, c->world, ids.data(), n1);
     for (int f = 1; f < frames; ++f)
         for (int64_t i = 0; i < n1; ++i) ids[(size_t)(f * n1 + i)] = ids[(size_t)i] + (uint32_t)f * (uint32_t)W * (uint32_t)H;
-    int rc = upload(c, c->d_pixels, ids.data(), ids.size() * 4);
-    if (rc) return rc;
+    if ((rc = upload(c, c->d_pixels, ids.data(), ids.size() * 4))) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream)); // ids is a local
     c->n_pixels = (uint32_t)n;
     c->queue = key;
@@ -425,7 +428,6 @@ int finish_frame(pt_ctx* c, hipStream_t stream, int W, int H, const FramePlan* f
     LastFrame& L = c->last;
     L.ev_pending = true;
     L.flag_pending = (!first && L.flag_pending) || f != nullptr;
-    L.stream = stream;
     L.launches = (first ? 0 : L.launches) + (f ? f->n_launch : 0);
     L.sorted = f && f->sorted;
     L.w = W;
@@ -521,7 +523,7 @@ struct BatchArgs {
 int batch_sequence(pt_ctx* c, const BatchArgs& a, int f0, int K, bool first, void* d_out_rgb, void* d_out_rgba8, hipStream_t stream)
 {
     const int W = a.W, H = a.H, Hv = K * a.H;
-    int rc = ensure_queue(c, W, H, K);
+    int rc = ensure_queue(c, W, H, K, stream);
     if (rc) return rc;
     if (c->n_pixels == 0) return empty_frame(c, stream, W, Hv, d_out_rgb, d_out_rgba8, first);
     PtKernelParams P;
@@ -593,7 +595,7 @@ int batch_device(pt_ctx* c, const pt_frame* frames, int32_t n_frames, int32_t n_
         else if (f0 + K < n_frames) HIP_TRY(c, hipMemsetAsync((uint32_t*)c->d_seq_flags.p + s, 0, 4, stream));
         if (reduce && c->comm) {
             uint32_t* r8 = d_reduce_rgba8 ? (uint32_t*)d_reduce_rgba8 + (size_t)f0 * npx : nullptr;
-            if ((rc = pt_reduce_framebuffer(c, o, r8, (int64_t)K * (int64_t)npx, stream))) return rc;
+            if ((rc = reduce_framebuffer(c, o, r8, (int64_t)K * (int64_t)npx, stream))) return rc;
         }
         f0 += K;
     }
@@ -613,6 +615,7 @@ int read_back(pt_ctx* c, bool root, float* out_rgb, uint32_t* out_rgba8, size_t 
     }
     HIP_TRY(c, hipEventRecord(c->evd, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->last.stream = nullptr; // drained: the blocking call was ordered after the last asynchronous one (order_after_last)
     float ms = 0.0f;
     HIP_TRY(c, hipEventElapsedTime(&ms, c->ev1, c->evr));
     c->stats.reduce_ms = ms;
@@ -681,7 +684,6 @@ int aov_device(pt_ctx* c, const pt_camera* cam, int W, int H, int n_samples, voi
     L.ev_pending = true;
     L.flag_pending = false;
     L.aov_flag_pending = true;
-    L.stream = stream;
     L.launches = 1;
     L.sorted = false;
     L.w = W;
@@ -696,53 +698,11 @@ int aov_device(pt_ctx* c, const pt_camera* cam, int W, int H, int n_samples, voi
     return PT_OK;
 }
 
-} // namespace
-
-extern "C" {
-
-int pt_render_aov_device(pt_ctx* c, const pt_camera* cam, int32_t W, int32_t H, int32_t n_samples, void* d_out_aov, void* stream_v)
+// One frame on `stream`, which the caller has ordered after the context's last asynchronous call (order_after_last).
+int render_device(pt_ctx* c, const pt_camera* cam, int W, int H, int max_samples, int max_depth, void* d_out_rgb, void* d_out_rgba8, hipStream_t stream)
 {
-    if (!c || !cam || !d_out_aov) return PT_E_INVALID;
     int rc;
-    if ((rc = need_device(c)) || (rc = check_render_args(c, W, H, n_samples, 0))) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    return aov_device(c, cam, W, H, n_samples, d_out_aov, stream_v ? (hipStream_t)stream_v : c->stream);
-}
-
-int pt_render_aov(pt_ctx* c, const pt_camera* cam, int32_t W, int32_t H, int32_t n_samples, float* out_aov)
-{
-    // with a communicator attached only rank 0 receives the buffers (as pt_render)
-    const bool root = !c || !c->comm || c->comm_rank == 0;
-    if (!c || !cam || (root && !out_aov)) return PT_E_INVALID;
-    int rc;
-    if ((rc = need_device(c)) || (rc = check_render_args(c, W, H, n_samples, 0))) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    const size_t n_floats = (size_t)W * H * 8;
-    if ((rc = ensure(c, c->d_aov, n_floats * 4))) return rc;
-    if ((rc = aov_device(c, cam, W, H, n_samples, c->d_aov.p, c->stream))) return rc;
-    // N ranks: ONE sum-reduce of the W*H*8 floats onto rank 0; one non-zero contributor per pixel, so the sum is exact
-    if (c->comm && (rc = reduce_sum(c, c->d_aov.p, n_floats, c->stream))) return rc;
-    HIP_TRY(c, hipEventRecord(c->evr, c->stream));
-    if (root) HIP_TRY(c, hipMemcpyAsync(out_aov, c->d_aov.p, n_floats * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipEventRecord(c->evd, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    float ms = 0.0f;
-    HIP_TRY(c, hipEventElapsedTime(&ms, c->ev1, c->evr));
-    c->stats.reduce_ms = ms;
-    HIP_TRY(c, hipEventElapsedTime(&ms, c->evr, c->evd));
-    c->stats.d2h_ms = ms;
-    return check_watchdog(c);
-}
-
-int pt_render_device(pt_ctx* c, const pt_camera* cam, int32_t W, int32_t H, int32_t max_samples, int32_t max_depth, void* d_out_rgb,
-                     void* d_out_rgba8, void* stream_v)
-{
-    if (!c || !cam || !d_out_rgb) return PT_E_INVALID;
-    int rc;
-    if ((rc = need_device(c)) || (rc = check_render_args(c, W, H, max_samples, max_depth))) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t stream = stream_v ? (hipStream_t)stream_v : c->stream;
-    if ((rc = ensure_queue(c, W, H))) return rc;
+    if ((rc = ensure_queue(c, W, H, 1, stream))) return rc;
     if (c->n_pixels == 0) {
         HIP_TRY(c, hipEventRecord(c->ev0, stream));
         return empty_frame(c, stream, W, H, d_out_rgb, d_out_rgba8);
@@ -760,13 +720,88 @@ int pt_render_device(pt_ctx* c, const pt_camera* cam, int32_t W, int32_t H, int3
     return finish_frame(c, stream, W, H, &f, P.stack_entries);
 }
 
+// An asynchronous entry point around `enqueue`: ordered after the context's last asynchronous call on the device, and itself the last
+// one from here on - also when it failed half-way, for what it did enqueue.
+template <class F> int async_call(pt_ctx* c, hipStream_t stream, F enqueue)
+{
+    int rc = order_after_last(c, stream);
+    if (rc) return rc;
+    rc = enqueue();
+    const int rm = mark_last(c, stream);
+    return rc ? rc : rm;
+}
+
+// A blocking render around `run`, which enqueues on the context's stream and drains it: ordered after the last asynchronous call like
+// any other (nothing is added on an idle context or behind a call on the context's own stream).  If it fails, what it did enqueue
+// may still be pending on the context's stream, which is then the last one for the next call to wait for.
+template <class F> int blocking_call(pt_ctx* c, F run)
+{
+    int rc = order_after_last(c, c->stream);
+    if (rc) return rc;
+    if ((rc = run())) (void)mark_last(c, c->stream);
+    return rc;
+}
+
+} // namespace
+
+extern "C" {
+
+int pt_render_aov_device(pt_ctx* c, const pt_camera* cam, int32_t W, int32_t H, int32_t n_samples, void* d_out_aov, void* stream_v)
+{
+    if (!c || !cam || !d_out_aov) return PT_E_INVALID;
+    int rc;
+    if ((rc = need_device(c)) || (rc = check_render_args(c, W, H, n_samples, 0))) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t stream = stream_v ? (hipStream_t)stream_v : c->stream;
+    return async_call(c, stream, [&] { return aov_device(c, cam, W, H, n_samples, d_out_aov, stream); });
+}
+
+int pt_render_aov(pt_ctx* c, const pt_camera* cam, int32_t W, int32_t H, int32_t n_samples, float* out_aov)
+{
+    // with a communicator attached only rank 0 receives the buffers (as pt_render)
+    const bool root = !c || !c->comm || c->comm_rank == 0;
+    if (!c || !cam || (root && !out_aov)) return PT_E_INVALID;
+    int rc;
+    if ((rc = need_device(c)) || (rc = check_render_args(c, W, H, n_samples, 0))) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t n_floats = (size_t)W * H * 8;
+    return blocking_call(c, [&]() -> int {
+        int rc;
+        if ((rc = ensure(c, c->d_aov, n_floats * 4))) return rc;
+        if ((rc = aov_device(c, cam, W, H, n_samples, c->d_aov.p, c->stream))) return rc;
+        // N ranks: ONE sum-reduce of the W*H*8 floats onto rank 0; one non-zero contributor per pixel, so the sum is exact
+        if (c->comm && (rc = reduce_sum(c, c->d_aov.p, n_floats, c->stream))) return rc;
+        HIP_TRY(c, hipEventRecord(c->evr, c->stream));
+        if (root) HIP_TRY(c, hipMemcpyAsync(out_aov, c->d_aov.p, n_floats * 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipEventRecord(c->evd, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        c->last.stream = nullptr; // drained (as read_back)
+        float ms = 0.0f;
+        HIP_TRY(c, hipEventElapsedTime(&ms, c->ev1, c->evr));
+        c->stats.reduce_ms = ms;
+        HIP_TRY(c, hipEventElapsedTime(&ms, c->evr, c->evd));
+        c->stats.d2h_ms = ms;
+        return check_watchdog(c);
+    });
+}
+
+int pt_render_device(pt_ctx* c, const pt_camera* cam, int32_t W, int32_t H, int32_t max_samples, int32_t max_depth, void* d_out_rgb,
+                     void* d_out_rgba8, void* stream_v)
+{
+    if (!c || !cam || !d_out_rgb) return PT_E_INVALID;
+    int rc;
+    if ((rc = need_device(c)) || (rc = check_render_args(c, W, H, max_samples, max_depth))) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t stream = stream_v ? (hipStream_t)stream_v : c->stream;
+    return async_call(c, stream, [&] { return render_device(c, cam, W, H, max_samples, max_depth, d_out_rgb, d_out_rgba8, stream); });
+}
+
 int pt_synchronize(pt_ctx* c)
 {
     if (!c) return PT_E_INVALID;
     if (c->host_only) return PT_OK;
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (c->last.stream && c->last.stream != c->stream) HIP_TRY(c, hipStreamSynchronize(c->last.stream)); // pt_render_device on a caller's stream
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    int rc = wait_idle(c);
+    if (rc) return rc;
     return check_watchdog(c);
 }
 
@@ -778,24 +813,31 @@ int pt_render(pt_ctx* c, const pt_camera* cam, int32_t W, int32_t H, int32_t max
     int rc = need_device(c);
     if (rc) return rc;
     if (W <= 0 || H <= 0) return fail(c, PT_E_INVALID, "bad render size %dx%d", W, H);
+    if ((rc = check_render_args(c, W, H, max_samples, max_depth))) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
-    size_t npx = (size_t)W * H;
-    if ((rc = ensure(c, c->d_out, npx * 12))) return rc;
-    if (out_rgba8 && (rc = ensure(c, c->d_out8, npx * 4))) return rc;
-    // with a communicator the RGBA8 image is made from the reduced float frame on the root (pt_reduce_framebuffer): every rank
-    // enqueues the same single collective whatever buffers its caller passed
-    rc = pt_render_device(c, cam, W, H, max_samples, max_depth, c->d_out.p, (out_rgba8 && !c->comm) ? c->d_out8.p : nullptr, nullptr);
-    if (rc) return rc;
-    // N ranks: the one collective of the path - RCCL sum-reduce of the float3 framebuffer onto rank 0 (pt_comm.cpp)
-    if (c->comm && (rc = pt_reduce_framebuffer(c, c->d_out.p, (root && out_rgba8) ? c->d_out8.p : nullptr, (int64_t)npx, nullptr))) return rc;
-    return read_back(c, root, out_rgb, out_rgba8, npx);
+    const size_t npx = (size_t)W * H;
+    return blocking_call(c, [&]() -> int {
+        int rc;
+        if ((rc = ensure(c, c->d_out, npx * 12))) return rc;
+        if (out_rgba8 && (rc = ensure(c, c->d_out8, npx * 4))) return rc;
+        // with a communicator the RGBA8 image is made from the reduced float frame on the root (pt_reduce_framebuffer): every rank
+        // enqueues the same single collective whatever buffers its caller passed
+        rc = render_device(c, cam, W, H, max_samples, max_depth, c->d_out.p, (out_rgba8 && !c->comm) ? c->d_out8.p : nullptr, c->stream);
+        if (rc) return rc;
+        // N ranks: the one collective of the path - RCCL sum-reduce of the float3 framebuffer onto rank 0 (pt_comm.cpp)
+        if (c->comm && (rc = reduce_framebuffer(c, c->d_out.p, (root && out_rgba8) ? c->d_out8.p : nullptr, (int64_t)npx, c->stream))) return rc;
+        return read_back(c, root, out_rgb, out_rgba8, npx);
+    });
 }
 
 int pt_render_batch_device(pt_ctx* c, const pt_frame* frames, int32_t n_frames, int32_t n_materials, int32_t W, int32_t H, int32_t max_samples, int32_t max_depth,
                            void* d_out_rgb, void* d_out_rgba8, void* stream_v)
 {
     if (!c || !d_out_rgb) return PT_E_INVALID;
-    return batch_device(c, frames, n_frames, n_materials, W, H, max_samples, max_depth, d_out_rgb, d_out_rgba8, nullptr, stream_v ? (hipStream_t)stream_v : c->stream, false);
+    if (c->host_only) return batch_device(c, frames, n_frames, n_materials, W, H, max_samples, max_depth, d_out_rgb, d_out_rgba8, nullptr, nullptr, false); // (refused there, with its message)
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t stream = stream_v ? (hipStream_t)stream_v : c->stream;
+    return async_call(c, stream, [&] { return batch_device(c, frames, n_frames, n_materials, W, H, max_samples, max_depth, d_out_rgb, d_out_rgba8, nullptr, stream, false); });
 }
 
 int pt_render_batch(pt_ctx* c, const pt_frame* frames, int32_t n_frames, int32_t n_materials, int32_t W, int32_t H, int32_t max_samples, int32_t max_depth,
@@ -804,19 +846,21 @@ int pt_render_batch(pt_ctx* c, const pt_frame* frames, int32_t n_frames, int32_t
     // with a communicator attached only rank 0 receives the frames (as pt_render)
     const bool root = !c || !c->comm || c->comm_rank == 0;
     if (!c || (root && !out_rgb)) return PT_E_INVALID;
-    int rc;
-    const bool sized = n_frames >= 1 && W > 0 && H > 0 && !c->host_only; // (everything else is refused by batch_device, with its message)
-    const size_t npx = sized ? (size_t)n_frames * (size_t)W * (size_t)H : 0;
-    if (sized) {
-        HIP_TRY(c, hipSetDevice(c->device));
+    // with a communicator the RGBA8 frames are made from the reduced float frames on the root, one reduce per launch sequence
+    auto batch = [&] {
+        return batch_device(c, frames, n_frames, n_materials, W, H, max_samples, max_depth, c->d_out.p, (out_rgba8 && !c->comm) ? c->d_out8.p : nullptr,
+                            (root && out_rgba8 && c->comm) ? c->d_out8.p : nullptr, c->stream, true);
+    };
+    if (n_frames < 1 || W <= 0 || H <= 0 || c->host_only) return batch(); // refused there, with its message, before anything is enqueued
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t npx = (size_t)n_frames * (size_t)W * (size_t)H;
+    return blocking_call(c, [&]() -> int {
+        int rc;
         if ((rc = ensure(c, c->d_out, npx * 12))) return rc;
         if (out_rgba8 && (rc = ensure(c, c->d_out8, npx * 4))) return rc;
-    }
-    // with a communicator the RGBA8 frames are made from the reduced float frames on the root, one reduce per launch sequence
-    rc = batch_device(c, frames, n_frames, n_materials, W, H, max_samples, max_depth, c->d_out.p, (out_rgba8 && !c->comm) ? c->d_out8.p : nullptr,
-                      (root && out_rgba8 && c->comm) ? c->d_out8.p : nullptr, c->stream, true);
-    if (rc) return rc;
-    return read_back(c, root, out_rgb, out_rgba8, npx);
+        if ((rc = batch())) return rc;
+        return read_back(c, root, out_rgb, out_rgba8, npx);
+    });
 }
 
 int64_t pt_debug_plan_batch(int32_t W, int32_t H, int32_t n_frames, int32_t max_frames, int32_t* out, int64_t cap)

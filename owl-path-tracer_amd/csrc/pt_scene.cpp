@@ -64,14 +64,14 @@ int upload_materials(pt_ctx* c)
     return upload(c, c->d_materials, c->scene.materials.data(), c->scene.materials.size() * sizeof(float));
 }
 
-// A table of the uploaded scene replaced on the device: after the frames in flight, and complete when the call returns.
+// A table of the uploaded scene replaced on the device: after the frames in flight (on a caller's stream too: wait_idle), and complete
+// when the call returns.
 int upload_between_frames(pt_ctx* c, int (*up)(pt_ctx*))
 {
     if (c->host_only) return PT_OK;
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    int rc = up(c);
+    int rc = wait_idle(c);
     if (rc) return rc;
+    if ((rc = up(c))) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return PT_OK;
 }
@@ -373,7 +373,9 @@ extern "C" int pt_upload_scene(pt_ctx* c, const pt_mesh* meshes, int32_t n_meshe
     c->have_scene = false;
     c->scene.dyn = DynScene{};
     c->scene.dyn.enabled = c->opt.dynamic != 0;
-    if (!c->host_only) HIP_TRY(c, hipSetDevice(c->device));
+    // every device buffer of the scene is reused in place where its capacity suffices (ensure), and a device builder writes d_nodes
+    // directly: after the frames in flight
+    if (!c->host_only && (rc = wait_idle(c))) return rc;
     // PT_UPLOAD_TRACE=1: phase times of this call on stderr
     const bool trace = getenv("PT_UPLOAD_TRACE") && getenv("PT_UPLOAD_TRACE")[0] == '1';
     auto t_phase = std::chrono::steady_clock::now();
@@ -498,8 +500,7 @@ int pt_update_vertices(pt_ctx* c, const pt_mesh* meshes, int32_t n_meshes)
             return fail(c, PT_E_INVALID, "pt_update_vertices: mesh %d has %d vertices / %d normals, the scene was uploaded with %d / %d", m, meshes[m].n_vertices,
                         meshes[m].n_normals, d.n_verts[(size_t)m], d.n_normals[(size_t)m]);
     if (!c->host_only) { // after the frames in flight, as upload_between_frames
-        HIP_TRY(c, hipSetDevice(c->device));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        if (int rc = wait_idle(c)) return rc;
         if (!c->evu0) HIP_TRY(c, hipEventCreate(&c->evu0));
         if (!c->evu1) HIP_TRY(c, hipEventCreate(&c->evu1));
     }
@@ -637,8 +638,7 @@ int64_t pt_debug_export_tree(pt_ctx* c, int32_t which, void* out, int64_t cap)
     if (!out) return (int64_t)bytes; // size query
     if ((size_t)cap < bytes) return fail(c, PT_E_INVALID, "pt_debug_export_tree: %zu bytes needed, %lld given", bytes, (long long)cap);
     if (bytes && from_device && which != PT_TREE_INFO) {
-        HIP_TRY(c, hipSetDevice(c->device));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        if (int rc = wait_idle(c)) return rc;
         HIP_TRY(c, hipMemcpy(out, d_src, bytes, hipMemcpyDeviceToHost));
     } else if (bytes) std::memcpy(out, src, bytes);
     return (int64_t)bytes;

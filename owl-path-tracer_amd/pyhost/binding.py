@@ -445,6 +445,8 @@ class Context:
         return rgb, rgba
 
     def render_batch_device(self, frames, W, H, spp, max_depth, d_out_rgb, d_out_rgba8=None, stream=None, n_materials=None):
+        """pt_render_batch_device: asynchronous, the frames left in HBM at the device pointers (integers).  stream: a hipStream_t as an
+        integer, None = the context's own stream; ordering and lifetime as render_device."""
         arr, n_mat, keep = _marshal_frames(frames)
         if n_materials is not None:
             n_mat = int(n_materials)
@@ -466,7 +468,8 @@ class Context:
         return out
 
     def render_aov_device(self, cam, W, H, n_samples, d_out_aov, stream=None):
-        """pt_render_aov_device: asynchronous, W*H*8 floats left in HBM at the device pointer d_out_aov; synchronize() waits for it."""
+        """pt_render_aov_device: asynchronous, W*H*8 floats left in HBM at the device pointer d_out_aov; synchronize() waits for it.
+        stream: a hipStream_t as an integer, None = the context's own stream; ordering and lifetime as render_device."""
         self._check(lib().pt_render_aov_device(self._h, C.byref(cam), W, H, n_samples, C.c_void_p(d_out_aov), C.c_void_p(stream) if stream else None),
                     "pt_render_aov_device")
 
@@ -489,10 +492,15 @@ class Context:
         self._check(lib().pt_comm_destroy(self._h), "pt_comm_destroy")
 
     def reduce_framebuffer(self, d_rgb, d_rgba8, n_pixels, stream=None):
+        """pt_reduce_framebuffer; stream as render_device."""
         self._check(lib().pt_reduce_framebuffer(self._h, C.c_void_p(d_rgb), C.c_void_p(d_rgba8) if d_rgba8 else None, n_pixels,
                                                 C.c_void_p(stream) if stream else None), "pt_reduce_framebuffer")
 
     def render_device(self, cam, W, H, spp, max_depth, d_out_rgb, d_out_rgba8=None, stream=None):
+        """pt_render_device: asynchronous, the frame left in HBM at the device pointers (integers).  stream: a hipStream_t as an integer
+        (the value of the handle, e.g. ctypes.c_void_p.value or torch.cuda.Stream.cuda_stream), None = the context's own stream.  The
+        library orders the call after the context's last asynchronous one, whichever stream that used (include/mi355pt.h); the stream
+        must live until a synchronize() after the last call on it has returned."""
         self._check(lib().pt_render_device(self._h, C.byref(cam), W, H, spp, max_depth, C.c_void_p(d_out_rgb),
                                            C.c_void_p(d_out_rgba8) if d_out_rgba8 else None, C.c_void_p(stream) if stream else None),
                     "pt_render_device")

@@ -48,6 +48,34 @@ def test_host_only_context_has_no_render_fallback(cube):
         ctx.debug_eval("sin", np.zeros(4, np.float32), 1)
 
 
+def test_asynchronous_entry_points_on_a_host_only_context(cube):
+    """PT_E_NO_DEVICE from pt_render_device and pt_render_batch_device, with the context's stream (NULL) and with a caller's stream alike
+    (the handle is never looked at), before and after the refusal pt_synchronize has nothing to wait for, and the blocking calls that
+    wait for a frame in flight on a device context (pt_set_materials, pt_set_pixel_shard, pt_upload_scene again) wait for nothing here."""
+    PT_OK, PT_E_NO_DEVICE = 0, -2
+    L = B.lib()
+    mats = [m for _, m, _ in cube["materials"]]
+    ctx = B.Context(-1)
+    try:
+        assert L.pt_synchronize(ctx._h) == PT_OK
+        ctx.upload_scene(cube["entities"], mats, textures=[np.zeros((2, 2), np.uint32)], mesh_textures=[0])
+        cam = B.to_camera_data([2, 1, 2], [0, 0, 0], [0, 1, 0], 50, 8, 8)
+        arr, n_mat, keep = B._marshal_frames([(cam, None), (cam, np.stack(mats))])
+        for stream in (None, C.c_void_p(0x1000)):
+            assert L.pt_render_device(ctx._h, C.byref(cam), 8, 8, 1, 4, C.c_void_p(16), None, stream) == PT_E_NO_DEVICE
+            assert "no CPU fallback" in L.pt_last_error(ctx._h).decode()
+            assert L.pt_render_batch_device(ctx._h, arr, 2, n_mat, 8, 8, 1, 4, C.c_void_p(16), None, stream) == PT_E_NO_DEVICE
+            assert L.pt_render_aov_device(ctx._h, C.byref(cam), 8, 8, 1, C.c_void_p(16), stream) == PT_E_NO_DEVICE
+            assert L.pt_synchronize(ctx._h) == PT_OK
+        ctx.set_materials(mats)
+        ctx.set_pixel_shard(1, 2, 16)
+        ctx.set_pixel_shard(0, 1, 16)
+        ctx.upload_scene(cube["entities"], mats, textures=[np.zeros((2, 2), np.uint32)], mesh_textures=[0])
+        assert L.pt_synchronize(ctx._h) == PT_OK
+    finally:
+        ctx.close()
+
+
 def test_upload_validation(cube):
     ctx = B.Context(-1)
     ents = cube["entities"]
