@@ -1,0 +1,102 @@
+"""Random call sequences on one context against the oracle, call by call (generator, model and runner: tests/seq_common.py).
+
+One test per seed: a fresh context lives through an upload with option "dynamic" = 1 and a drawn builder and leaf size, then 8 to 12
+calls - update_vertices, new tables, environments, shards, the watertight switch, scheduler knobs, a second upload; single frames,
+batches and guide passes, blocking and asynchronous on the context's stream or on one of two caller streams; refused calls - and every
+frame and guide buffer is the oracle's for the state the model says the context is in, bit for bit.  An asynchronous call is followed
+by the next call at once; one pt_synchronize after the last step precedes the read-back.  After every update the arrays in HBM are held
+to the box definition, on whatever tree builder 0, 1 or 2 made.  tests/test_sequences_host.py asserts what the default seeds contain
+and that their changes show.
+
+12 seeds by default; PT_SEQ_CASES=N for more, PT_SEQ_ONLY=seed for one (tools/seq_replay.py prints and replays a seed).  One more
+test runs two of the sequences over pt_group_* (two contexts on one card, the stub collective, a child process) with option
+"watertight" = 1 and compares the group's frames and guide buffers with a single context's, which run() holds to the oracle.
+PT_WRITE_PROFILES=1 records the call lists, the builder and the seconds per seed in profiles/r14_sequences.json.
+"""
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import pytest
+
+import async_common as A
+import rccl_stub
+import seq_common as SC
+from owl_path_tracer_amd.pyhost import binding as B
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ONLY = os.environ.get("PT_SEQ_ONLY")
+SEEDS = [int(ONLY)] if ONLY else SC.default_seeds(int(os.environ.get("PT_SEQ_CASES", str(SC.N_DEFAULT))))
+_report = {}
+
+
+@pytest.fixture(scope="module")
+def model(orc):
+    m = SC.Model(orc)
+    yield m
+    if os.environ.get("PT_WRITE_PROFILES") == "1" and _report:
+        path = os.path.join(ROOT, "profiles", "r14_sequences.json")
+        with open(path, "w") as f:
+            json.dump(dict(seed0=SC.SEED0, sequences=_report), f, indent=1, sort_keys=True)
+
+
+@pytest.mark.parametrize("seed", SEEDS)
+def test_sequence(model, seed):
+    seq = SC.draw_sequence(seed)
+    ctx = B.Context(0)
+    t0, o0 = time.time(), model.seconds
+    try:
+        SC.run(ctx, seq, model, A=A)
+    finally:
+        try:
+            ctx.close()
+        finally:
+            A.destroy_streams()
+    _report[str(seed)] = dict(calls=["upload: " + SC.describe(seq["upload"])] + [SC.describe(s) for s in seq["steps"]], builder=seq["upload"]["builder"],
+                              seconds_library=round(SC.run.seconds, 3), seconds_oracle=round(model.seconds - o0, 3), seconds_test=round(time.time() - t0, 3))
+    if os.environ.get("PT_WRITE_PROFILES") == "1":  # (the visible share costs the oracle one more frame per change: only for the record)
+        shown, hidden, frames, flat = SC.visibility(seq, model)
+        _report[str(seed)].update(changes=sum(shown.values()) + len(hidden), visible_changes=sum(shown.values()), observing_steps=frames, flat_frames=len(flat))
+    print("seed %d: %d steps, %.2f s in the library, %.2f s in the oracle" % (seed, len(seq["steps"]), SC.run.seconds, model.seconds - o0))
+
+
+def _group_seeds():
+    """The first two default seeds whose group projection shows a frame AND a guide buffer after an update_vertices."""
+    out = []
+    for seed in SC.default_seeds():
+        ops = [s["op"] for s in SC.group_projection(SC.draw_sequence(seed))["steps"]]
+        if "update_vertices" in ops:
+            rest = ops[ops.index("update_vertices"):]
+            if "render" in rest and "render_aov" in rest:
+                out.append(seed)
+    return out[:2]
+
+
+def test_sequences_over_a_group(model, tmp_path):
+    seeds = _group_seeds()
+    assert len(seeds) == 2, seeds
+    out = str(tmp_path / "got")
+    rc, so, se = rccl_stub.run_child([sys.executable, os.path.join(ROOT, "tests", "seq_group_child.py"), out, "0,0"] + [str(s) for s in seeds], rccl_stub.stub_env(), 300)
+    assert rc == 0, "child exited with %s\n%s\n%s" % (rc, so[-2000:], se[-4000:])
+    done = json.load(open(os.path.join(out, "done.json")))
+    for seed in seeds:
+        seq = SC.group_projection(SC.draw_sequence(seed))
+        ctx = B.Context(0)
+        try:
+            single = SC.run(ctx, seq, model, A=A)  # the single context, held to the watertight oracle on the way
+        finally:
+            ctx.close()
+        assert done[str(seed)]["size"] == 2 and done[str(seed)]["steps"] == [g[0] for g in single]
+        kinds = set()
+        for i, f, f8 in single:
+            what = "group of 2, sequence seed=%d, step %d (%s)" % (seed, i, SC.describe(seq["steps"][i]))
+            bad = SC.same(np.load(os.path.join(out, "%d_%d_rgb.npy" % (seed, i))), f)
+            assert not bad.any(), "%s: %d of %d floats differ from the single context's" % (what, bad.sum(), bad.size)
+            if f8 is not None:
+                np.testing.assert_array_equal(np.load(os.path.join(out, "%d_%d_rgba8.npy" % (seed, i))), f8, err_msg=what)
+            kinds.add(seq["steps"][i]["op"])
+        assert kinds == {"render", "render_aov"}
