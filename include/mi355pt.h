@@ -166,13 +166,14 @@ int pt_render(pt_ctx* ctx, const pt_camera* cam, int32_t width, int32_t height, 
  * timing events.  The context's own stream is non-blocking: HIP orders nothing between it and a caller's stream.  THE LIBRARY does:
  * every call that touches what a frame in flight uses is ordered after the context's LAST ASYNCHRONOUS CALL, whichever stream that
  * call was given.  So any call of this header may follow a pt_*_device call at once, with no pt_synchronize between them.
- *   - The asynchronous calls (pt_render_device, pt_render_batch_device, pt_render_aov_device, pt_reduce_framebuffer) wait ON THE
+ *   - The asynchronous calls (pt_render_device, pt_render_batch_device, pt_render_aov_device, pt_denoise_device, pt_reduce_framebuffer) wait ON THE
  *     DEVICE: the stream they are given waits for an event recorded at the end of the previous asynchronous call - only if that call
  *     used another stream; on the same stream the stream's own order suffices and nothing is added.  The host returns at once, with
  *     two exceptions that existed before: a frame of another size, shard or batch length rewrites the pixel queue and a frame that
- *     needs larger work buffers reallocates them - both first wait on the host for the frame in flight; and pt_render_batch_device
+ *     needs larger work buffers reallocates them (pt_denoise_device: its filter records, when the frame is larger than any it filtered
+ *     before) - both first wait on the host for the frame in flight; and pt_render_batch_device
  *     returns when its per-frame tables have reached HBM, i.e. after whatever precedes it on `stream`.
- *   - The blocking renders (pt_render, pt_render_batch, pt_render_aov) run on the context's stream behind the same device-side wait
+ *   - The blocking renders (pt_render, pt_render_batch, pt_render_aov) and pt_denoise run on the context's stream behind the same device-side wait
  *     and return with the context idle.  After a blocking call, or on the context's own stream, they add no wait at all.
  *   - The calls that change or read what a frame uses WAIT ON THE HOST for the last asynchronous call's stream (if it is not the
  *     context's) and then for the context's: pt_set_materials, pt_set_environment, pt_update_vertices, pt_upload_scene,
@@ -186,8 +187,8 @@ int pt_render(pt_ctx* ctx, const pt_camera* cam, int32_t width, int32_t height, 
  * that the library does not look at it again.  One thread at a time per context, as everywhere in this header. */
 int pt_render_device(pt_ctx* ctx, const pt_camera* cam, int32_t width, int32_t height, int32_t max_samples, int32_t max_path_depth,
                      void* d_out_rgb, void* d_out_rgba8, void* stream);
-/* Waits on the host for the context's last asynchronous call - pt_render_device, pt_render_batch_device, pt_render_aov_device or
- * pt_reduce_framebuffer, on the stream it was given - and for the context's own stream.  Every earlier asynchronous call of the context
+/* Waits on the host for the context's last asynchronous call - pt_render_device, pt_render_batch_device, pt_render_aov_device,
+ * pt_denoise_device or pt_reduce_framebuffer, on the stream it was given - and for the context's own stream.  Every earlier asynchronous call of the context
  * is complete then as well, whatever stream it used: each was ordered before the next (see pt_render_device).  Returns PT_E_HIP if a
  * wave's watchdog fired during the last frame (the image is then incomplete); pt_get_stats reports the same.  PT_OK at once on an idle
  * or host-only context.  A caller's stream may be destroyed once this has returned. */
@@ -224,8 +225,8 @@ int pt_render_batch_device(pt_ctx* ctx, const pt_frame* frames, int32_t n_frames
  * is already too large, PT_E_INVALID for bad arguments. */
 int64_t pt_debug_plan_batch(int32_t width, int32_t height, int32_t n_frames, int32_t max_frames, int32_t* out, int64_t cap);
 
-/* ---- guide pass: first-hit albedo, shading normal, depth and coverage (no reference counterpart; the guides a denoiser behind the
- * library wants for its low-sample frames, and a coverage channel for compositing) ----
+/* ---- guide pass: first-hit albedo, shading normal, depth and coverage (no reference counterpart; the guides pt_denoise below - or a denoiser behind
+ * the library - wants for its low-sample frames, and a coverage channel for compositing) ----
  * A pass of its own beside the render: one launch of a guide kernel that walks camera rays to their closest hit and stops there.
  * DEFINITION, for pixel (px, py) of a W x H frame and n_samples >= 1 (the kernel, the CPU twin pt_debug_aov_host and the numpy
  * restatement tests/aov_ref.py implement exactly this):
@@ -256,6 +257,58 @@ int pt_render_aov(pt_ctx* ctx, const pt_camera* cam, int32_t width, int32_t heig
 /* The same, asynchronous on `stream` (NULL = the context's), no reduce, the W*H*8 floats left in HBM at d_out_aov (16-byte aligned);
  * conventions of pt_render_device.  pt_synchronize waits for it and returns PT_E_HIP if a walk ran out of its step or stack bound. */
 int pt_render_aov_device(pt_ctx* ctx, const pt_camera* cam, int32_t width, int32_t height, int32_t n_samples, void* d_out_aov, void* stream);
+
+/* ---- denoiser: guide-driven a-trous filter for low-sample frames (no reference counterpart; the reference binds no denoiser) ----
+ * An edge-avoiding a-trous wavelet filter (Dammertz, Sewtz, Hanika, Lensch 2010): L iterations of a 5 x 5 B3-spline kernel whose tap
+ * distance doubles each iteration, every tap weighted by how far it differs from the centre pixel in colour, shading normal, relative
+ * depth and albedo; optionally on colour / albedo (PT_DENOISE_DEMODULATE).  It consumes a frame of pt_render and the guide buffers of
+ * pt_render_aov, needs the WHOLE frame and no scene: with N GPUs call it on rank 0 (or pt_group_ctx(g, 0)) after the reduce.  It issues
+ * no collective and has no group or batch form.
+ * BUFFERS: rgb and out_rgb are W*H*3 floats, aov the W*H*8 floats of pt_render_aov, all in the framebuffer order those calls produce
+ * (the kernel is symmetric, so the filter works in framebuffer rows and columns as they lie in memory: row = index / W, x = index % W).
+ * out_rgb may equal rgb (d_out_rgb may equal d_rgb): the filter works on buffers of its own.  out_rgba8 is optional.
+ * DEFINITION (the kernels of csrc/pt_denoise.hip, the CPU twin pt_debug_denoise_host and the numpy restatement tests/denoise_ref.py
+ * implement exactly this).  Arithmetic: the contract of csrc/pt_device.h - float32, no contraction, fma_ only where written, correctly
+ * rounded "/", dot(a, b) = fma_(a.z, b.z, fma_(a.y, b.y, a.x * b.x)), and its exp_, max_, make_rgba.
+ *   Per pixel p, from aov: a = floats 0..2 (albedo), n = floats 4..6 (normal), z = float 7 (depth).
+ *   Prepare:  rgb_k that is not finite is taken as 0;  d_k = max_(a_k, 1e-3f) with the flag, else 1;  c0_k = rgb_k / d_k with the flag,
+ *             else rgb_k itself;  kz_p = 1.0f / (sd * sd) with sd = sigma_depth * max_(z_p, 1e-6f).
+ *   Host constants, once, in float32 and in this order:  kn = 1.0f / (sigma_normal * sigma_normal);  ka likewise from sigma_albedo;  per
+ *             iteration i: sc = sigma_color * 2^-i (exact), kc_i = 1.0f / (sc * sc).
+ *   Iteration i = 0 .. L-1, s = 1 << i:  sum = (0, 0, 0), wsum = 0, then for dy = -2..2 (outer loop) and dx = -2..2 (inner loop):
+ *             q = (x + dx*s, row + dy*s); a tap outside the frame is skipped (no clamp, no mirror);
+ *             h = k[|dx|] * k[|dy|] with k = {3/8, 1/4, 1/16} (the products are exact);
+ *             centre tap: w = h, nothing else computed;
+ *             any other tap:  ec = dot(c_i(q) - c_i(p), same);  en = dot(n(q) - n(p), same);  dz = z(q) - z(p), ez = dz * dz;
+ *                             ea = dot(a(q) - a(p), same);  e = fma_(ea, ka, fma_(ez, kz_p, fma_(en, kn, ec * kc_i)));
+ *                             w = h * exp_(-e);  if !(w > 0) the tap is skipped (NaN and non-finite guides included);
+ *             sum_k = fma_(w, c_i(q)_k, sum_k), wsum = wsum + w.
+ *             After the 25 taps: c_{i+1}(p)_k = sum_k / wsum (wsum >= 9/64 always: the centre tap).
+ *   Finish:   out_k = c_L_k * d_k with the flag, else c_L_k;  out_rgba8 = make_rgba(out).
+ * LIMITS: relative depth under-filters surfaces seen at grazing angles; the guides are first-hit, so glass and mirrors are filtered by
+ * their own surface, not by what shows in them; the colour sigma halves each iteration, as in the paper.
+ * REFUSED with PT_E_INVALID and a message, before anything is touched: a NULL pointer (p and out_rgba8 excepted), W or H outside
+ * 1..65535 or W*H >= 2^31, iterations outside 1..8, a flag bit other than PT_DENOISE_DEMODULATE, a sigma that is not > 0 (NaN included;
+ * +infinity is allowed and switches the term off).  A host-only context answers pt_denoise and pt_denoise_device with PT_E_NO_DEVICE.
+ * pt_denoise: blocking (H2D of both inputs, the filter, D2H; the context is idle on return).  pt_denoise_device: asynchronous on `stream`
+ * (NULL = the context's), device pointers, d_aov 16-byte aligned; conventions of pt_render_device - ordered after the context's last
+ * asynchronous call and itself the last one afterwards; pt_synchronize waits for it.  pt_get_stats afterwards: kernel_ms from the first
+ * to the last filter kernel, launches = the filter's (L + 2), block, grid, vgprs, lds_bytes those of the iteration kernel.  The filter
+ * keeps no render state: a pt_render after it is bit for bit the pt_render before it. */
+#define PT_DENOISE_DEMODULATE 1
+typedef struct pt_denoise_params {
+    int32_t iterations;   /* L, 1..8: steps 1, 2, 4, ... 2^(L-1) */
+    int32_t flags;        /* bit 0 (PT_DENOISE_DEMODULATE): filter colour / albedo, multiply back at the end; other bits must be 0 */
+    float sigma_color, sigma_normal, sigma_depth, sigma_albedo; /* each > 0; +infinity switches the term off */
+} pt_denoise_params;
+void pt_denoise_default_params(pt_denoise_params* p);   /* 5, 0, 4.0f, 0.25f, 0.1f, 0.2f */
+int pt_denoise(pt_ctx* ctx, const float* rgb, const float* aov, int32_t width, int32_t height, const pt_denoise_params* p /* NULL = defaults */,
+               float* out_rgb, uint32_t* out_rgba8 /* optional */);
+int pt_denoise_device(pt_ctx* ctx, const void* d_rgb, const void* d_aov, int32_t width, int32_t height, const pt_denoise_params* p,
+                      void* d_out_rgb, void* d_out_rgba8, void* stream);
+/* The CPU twin of the filter: the definition above on all host threads; works on a host-only context; returns width * height. */
+int64_t pt_debug_denoise_host(pt_ctx* ctx, const float* rgb, const float* aov, int32_t width, int32_t height, const pt_denoise_params* p,
+                              float* out_rgb, uint32_t* out_rgba8);
 
 /* ---- N GPUs: pixel tiles sharded over ranks + ONE RCCL sum-reduce of the float3 framebuffer onto rank 0 (pt_comm.cpp) ----
  * No reference counterpart (the reference is single-GPU: create_context(nullptr, 1), application.cpp:62); for N > 1 these

@@ -107,6 +107,7 @@ struct pt_ctx {
     DevBuf d_nodes8, d_nodes4, d_nodes, d_tris, d_shade, d_materials, d_texdesc, d_env, d_pixels, d_heads, d_rng, d_accum, d_out, d_out8, d_counters, d_dbg_in, d_dbg_out, d_slots, d_laps, d_ring, d_params, d_cost, d_sorted, d_sort_scratch, d_dbg_start, d_bucket, d_tiers, d_batch_mats, d_batch_cams, d_seq_flags; // d_batch_*: per-frame tables of pt_render_batch; d_seq_flags: watchdog flags of its earlier launch sequences
     DevBuf d_verts, d_vnormals, d_tri_vi, d_level_nodes, d_src4, d_src8, d_refit_ws; // option "dynamic": what the refit kernels read (pt_refit.hip)
     DevBuf d_aov, d_aov_ws; // guide pass: the frame of pt_render_aov / pt_group_render_aov; bound flag (64 words) + the waves' stack overflow columns
+    DevBuf d_dn_ws, d_dn_rgb, d_dn_aov, d_dn_out8; // denoiser: the filter's records (pt_denoise_workspace_bytes); pt_denoise's staging of rgb (in and out), guides and RGBA8
     std::vector<DevBuf> d_textures;
 
     // pixel queue
@@ -147,6 +148,9 @@ PT_LOCAL void material_row(const pt_ctx* c, float* dst, const float* src, int i)
 // pt_render.cpp
 int check_watchdog(pt_ctx* c);
 PT_LOCAL void fill_params(pt_ctx* c, PtKernelParams& P);
+// pt_denoise_host.cpp
+PT_LOCAL int check_denoise_args(pt_ctx* c, const char* who, int W, int H, const pt_denoise_params* p, pt_denoise_params* eff); // the refusals of pt_denoise* and the twin; *eff = the parameters in effect
+PT_LOCAL void denoise_constants(const pt_denoise_params& p, float* kn, float* ka, float kc[8]); // the definition's host constants
 // pt_comm.cpp
 PT_LOCAL int reduce_framebuffer(pt_ctx* c, void* d_rgb, void* d_rgba8, int64_t n_pixels, hipStream_t stream); // pt_reduce_framebuffer inside a call that is ordered already
 PT_LOCAL int reduce_sum(pt_ctx* c, void* d_buf, size_t n_floats, hipStream_t stream); // in-place sum-reduce onto rank 0; nothing without a communicator

@@ -56,7 +56,28 @@ struct PtAovArgs {
     int32_t pad;
 };
 
+// Denoiser (pt_denoise; pt_denoise.hip): what its three kernels take.  The host fills everything but the record pointers, which
+// pt_launch_denoise carves out of ws; the constants are include/mi355pt.h's "host constants" (pti::denoise_constants).
+struct PtDenoiseArgs {
+    const float* rgb;       // W*H*3 floats, framebuffer order (may equal out_rgb)
+    const float* aov;       // W*H*8 floats of the guide pass, 16-byte aligned
+    float* out_rgb;         // W*H*3 floats
+    uint32_t* out_rgba8;    // W*H, or null
+    void* ws;               // pt_denoise_workspace_bytes(W, H), 16-byte aligned
+    float4* col[2];         // colour r g b + kz, ping-pong
+    float4* nz;             // normal x y z + depth
+    float4* alb;            // albedo r g b
+    int32_t width, height, iterations, flags;
+    float sigma_depth, kn, ka, pad;
+    float kc[8];            // per iteration
+};
+
 extern "C" {
+// pt_denoise.hip: prepare + `iterations` iteration launches + finish on `stream`; the geometry is the iteration kernel's (grid = its
+// workgroups for a W x H frame), hipErrorInvalidConfiguration if one of the three kernels needs scratch
+size_t pt_denoise_workspace_bytes(int W, int H);
+hipError_t pt_denoise_geometry(int W, int H, PtGeometry* g, int* grid);
+hipError_t pt_launch_denoise(const PtDenoiseArgs* a, hipStream_t stream);
 // pt_kernel.hip / pt_kernel_wt.hip: the guide kernels.  binary = 1: the one-level walk over PtNode[] (closest_hit of pt_trace.h; Moeller-
 // Trumbore only: the watertight build has no such instance and answers hipErrorInvalidValue).  Geometry: block, lds_bytes, lds_levels and
 // vgprs of the instance; hipErrorInvalidConfiguration if it needs scratch.

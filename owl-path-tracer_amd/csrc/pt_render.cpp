@@ -1,5 +1,6 @@
 // pt_render.cpp -- a frame, from the pixel queue to the read-back: the plan of its launches, its buffers and parameters, the launches,
-// batches of frames (pt_render_batch), pt_render / pt_render_device, pt_synchronize and the watchdog check.
+// batches of frames (pt_render_batch), the guide pass and the denoiser (pt_render_aov, pt_denoise), pt_render / pt_render_device,
+// pt_synchronize and the watchdog check.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -698,6 +699,52 @@ int aov_device(pt_ctx* c, const pt_camera* cam, int W, int H, int n_samples, voi
     return PT_OK;
 }
 
+// ---- denoiser (pt_denoise) -------------------------------------------------------------------------------------------------
+// The filter of pt_denoise.hip over device buffers: prepare, L iteration launches, finish.  It reads no scene and touches none of the
+// render's buffers or state (queue, d_laps, slots): its records live in d_dn_ws.  prm: checked by the caller (check_denoise_args).
+int denoise_device(pt_ctx* c, const void* d_rgb, const void* d_aov, int W, int H, const pt_denoise_params& prm, void* d_out_rgb, void* d_out_rgba8, hipStream_t stream)
+{
+    PtGeometry g{};
+    int grid = 0;
+    const hipError_t ge = pt_denoise_geometry(W, H, &g, &grid);
+    if (ge == hipErrorInvalidConfiguration) return fail(c, PT_E_LIMIT, "this build of the denoise kernels spills registers to scratch; such builds are refused (pt_denoise.hip)");
+    HIP_TRY(c, ge);
+    int rc;
+    if ((rc = ensure(c, c->d_dn_ws, pt_denoise_workspace_bytes(W, H)))) return rc; // (growing it first waits on the host for what is in flight)
+    PtDenoiseArgs A{};
+    A.rgb = (const float*)d_rgb;
+    A.aov = (const float*)d_aov;
+    A.out_rgb = (float*)d_out_rgb;
+    A.out_rgba8 = (uint32_t*)d_out_rgba8;
+    A.ws = c->d_dn_ws.p;
+    A.width = W;
+    A.height = H;
+    A.iterations = prm.iterations;
+    A.flags = prm.flags;
+    A.sigma_depth = prm.sigma_depth;
+    denoise_constants(prm, &A.kn, &A.ka, A.kc);
+    HIP_TRY(c, hipEventRecord(c->ev0, stream));
+    HIP_TRY(c, pt_launch_denoise(&A, stream));
+    // what pt_synchronize and pt_get_stats look at: kernel_ms from the first to the last filter kernel (as aov_device)
+    HIP_TRY(c, hipEventRecord(c->ev1, stream));
+    LastFrame& L = c->last;
+    L.ev_pending = true;
+    L.flag_pending = false;
+    L.aov_flag_pending = false;
+    L.launches = prm.iterations + 2;
+    L.sorted = false;
+    L.w = W;
+    L.h = H;
+    L.seqs = 1;
+    c->stats.express_pixels = c->stats.whole_pixels = c->stats.prepass_spp = 0;
+    c->stats.grid = grid;
+    c->stats.vgprs = g.vgprs;
+    c->stats.lds_bytes = (int)g.lds_bytes;
+    c->stats.block = g.block;
+    c->stats.stack_entries = 0;
+    return PT_OK;
+}
+
 // One frame on `stream`, which the caller has ordered after the context's last asynchronous call (order_after_last).
 int render_device(pt_ctx* c, const pt_camera* cam, int W, int H, int max_samples, int max_depth, void* d_out_rgb, void* d_out_rgba8, hipStream_t stream)
 {
@@ -773,6 +820,49 @@ int pt_render_aov(pt_ctx* c, const pt_camera* cam, int32_t W, int32_t H, int32_t
         if (c->comm && (rc = reduce_sum(c, c->d_aov.p, n_floats, c->stream))) return rc;
         HIP_TRY(c, hipEventRecord(c->evr, c->stream));
         if (root) HIP_TRY(c, hipMemcpyAsync(out_aov, c->d_aov.p, n_floats * 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipEventRecord(c->evd, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        c->last.stream = nullptr; // drained (as read_back)
+        float ms = 0.0f;
+        HIP_TRY(c, hipEventElapsedTime(&ms, c->ev1, c->evr));
+        c->stats.reduce_ms = ms;
+        HIP_TRY(c, hipEventElapsedTime(&ms, c->evr, c->evd));
+        c->stats.d2h_ms = ms;
+        return check_watchdog(c);
+    });
+}
+
+int pt_denoise_device(pt_ctx* c, const void* d_rgb, const void* d_aov, int32_t W, int32_t H, const pt_denoise_params* p, void* d_out_rgb, void* d_out_rgba8, void* stream_v)
+{
+    if (!c) return PT_E_INVALID;
+    if (!d_rgb || !d_aov || !d_out_rgb) return fail(c, PT_E_INVALID, "pt_denoise_device: NULL %s", !d_rgb ? "d_rgb" : (!d_aov ? "d_aov" : "d_out_rgb"));
+    int rc;
+    pt_denoise_params prm;
+    if ((rc = need_device(c)) || (rc = check_denoise_args(c, "pt_denoise_device", W, H, p, &prm))) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t stream = stream_v ? (hipStream_t)stream_v : c->stream;
+    return async_call(c, stream, [&] { return denoise_device(c, d_rgb, d_aov, W, H, prm, d_out_rgb, d_out_rgba8, stream); });
+}
+
+int pt_denoise(pt_ctx* c, const float* rgb, const float* aov, int32_t W, int32_t H, const pt_denoise_params* p, float* out_rgb, uint32_t* out_rgba8)
+{
+    if (!c) return PT_E_INVALID;
+    if (!rgb || !aov || !out_rgb) return fail(c, PT_E_INVALID, "pt_denoise: NULL %s", !rgb ? "rgb" : (!aov ? "aov" : "out_rgb"));
+    int rc;
+    pt_denoise_params prm;
+    if ((rc = need_device(c)) || (rc = check_denoise_args(c, "pt_denoise", W, H, p, &prm))) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t npx = (size_t)W * H;
+    return blocking_call(c, [&]() -> int {
+        int rc;
+        if ((rc = ensure(c, c->d_dn_rgb, npx * 12)) || (rc = ensure(c, c->d_dn_aov, npx * 32))) return rc;
+        if (out_rgba8 && (rc = ensure(c, c->d_dn_out8, npx * 4))) return rc;
+        HIP_TRY(c, hipMemcpyAsync(c->d_dn_rgb.p, rgb, npx * 12, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(c->d_dn_aov.p, aov, npx * 32, hipMemcpyHostToDevice, c->stream));
+        if ((rc = denoise_device(c, c->d_dn_rgb.p, c->d_dn_aov.p, W, H, prm, c->d_dn_rgb.p, out_rgba8 ? c->d_dn_out8.p : nullptr, c->stream))) return rc; // in place on the staging copy
+        HIP_TRY(c, hipEventRecord(c->evr, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(out_rgb, c->d_dn_rgb.p, npx * 12, hipMemcpyDeviceToHost, c->stream));
+        if (out_rgba8) HIP_TRY(c, hipMemcpyAsync(out_rgba8, c->d_dn_out8.p, npx * 4, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(c, hipEventRecord(c->evd, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         c->last.stream = nullptr; // drained (as read_back)

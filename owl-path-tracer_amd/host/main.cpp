@@ -14,6 +14,9 @@
 // --aov N (N >= 1: after every frame the guide pass with N samples per pixel - pt_render_aov / pt_group_render_aov, mi355pt.h - and three
 // more files next to <name>.png: <name>_albedo.png = make_rgba of the albedo, <name>_normal.png = make_rgba of 0.5 * n + 0.5,
 // <name>_depth.png = grey, depth / the frame's largest depth; works with --gpus / --devices and --watertight, not with --batch).
+// --denoise (needs --aov N, so not with --batch either: after every frame and its guides pt_denoise with the default parameters - mi355pt.h,
+// "denoiser" - and one more file, <name>_denoised.png = the filter's RGBA8 image; with --gpus / --devices the filter runs on the first
+// device's context, which holds the reduced frame).
 #include <sys/stat.h>
 #include <unistd.h>
 
@@ -93,6 +96,7 @@ struct App {
     std::string out_dir;
     int batch = 0; // --batch K: sweep steps per pt_render_batch (0: one pt_render per step)
     int aov = 0;   // --aov N: samples per pixel of the guide pass after every frame (0: none)
+    bool denoise = false; // --denoise: pt_denoise of every frame with its guides
 };
 
 void check(App& a, int rc, const char* what)
@@ -110,8 +114,9 @@ uint32_t make_8bit(float f)
 }
 uint32_t make_rgba(float r, float g, float b) { return make_8bit(r) | (make_8bit(g) << 8) | (make_8bit(b) << 16) | (0xffu << 24); }
 
-// --aov: the guide buffers of the frame just rendered, as three PNGs next to it (base = the frame's path without ".png")
-void write_guides(App& a, const std::string& base)
+// --aov: the guide buffers of the frame just rendered, as three PNGs next to it (base = the frame's path without ".png");
+// --denoise: the frame (rgb) filtered with them, as a fourth
+void write_guides(App& a, const std::string& base, const std::vector<float>& rgb)
 {
     const int W = a.settings.buffer_size[0], H = a.settings.buffer_size[1];
     const size_t npx = (size_t)W * H;
@@ -134,6 +139,12 @@ void write_guides(App& a, const std::string& base)
         imgio::write_png_rgba8(base + names[k], W, H, img[k]->data());
         std::printf("Image written to %s\n", (base + names[k]).c_str());
     }
+    if (!a.denoise) return;
+    std::vector<float> out(npx * 3);
+    std::vector<uint32_t> out8(npx);
+    if (pt_denoise(a.ctx, rgb.data(), g.data(), W, H, nullptr, out.data(), out8.data()) < 0) throw std::runtime_error(std::string("pt_denoise: ") + pt_last_error(a.ctx));
+    imgio::write_png_rgba8(base + "_denoised.png", W, H, out8.data());
+    std::printf("Image written to %s\n", (base + "_denoised.png").c_str());
 }
 
 // render_frame, application.cpp:363-371
@@ -156,7 +167,7 @@ void render_frame(App& a, const std::string& values)
     imgio::write_png_rgba8(path, W, H, rgba.data());
     std::printf("Image written to %s\n", path.c_str());
     std::fprintf(stderr, "  %.1f ms kernel, %.1f Msamples/s\n", st.kernel_ms, (double)W * H * a.settings.max_samples / (st.kernel_ms * 1e3));
-    if (a.aov > 0) write_guides(a, path.substr(0, path.size() - 4));
+    if (a.aov > 0) write_guides(a, path.substr(0, path.size() - 4), rgb);
 }
 
 // --batch: the collected sweep steps (material table and value string each) as one pt_render_batch; one PNG per step as render_frame writes it
@@ -262,6 +273,7 @@ int main(int argc, char** argv)
             else if (k == "--batch") { a.batch = std::atoi(next().c_str()); have_batch = true; }
             else if (k == "--aov") { a.aov = std::atoi(next().c_str()); have_aov = true; }
             else if (k == "--watertight") watertight = true;
+            else if (k == "--denoise") a.denoise = true;
             else if (k == "--convert-png" || k == "--convert-hdr") { // codec self-test hooks: decode with our reader, re-encode with our writer
                 std::string in = next(), out = next();
                 imgio::Image img = k == "--convert-png" ? imgio::load_png_rgba8(in) : imgio::load_hdr_as_ldr_rgba8(in);
@@ -279,6 +291,8 @@ int main(int argc, char** argv)
                 throw std::runtime_error("--devices names " + std::to_string(devs.size()) + " device(s) but --gpus says " + std::to_string(gpus));
             gpus = (int)devs.size();
         }
+        if (a.denoise && have_batch) throw std::runtime_error("--denoise cannot be combined with --batch (it needs the guides of --aov, which has no batch form)");
+        if (a.denoise && !have_aov) throw std::runtime_error("--denoise needs --aov N (the filter is driven by the guide buffers)");
         if (have_aov && a.aov < 1) throw std::runtime_error("--aov needs a positive number of samples per pixel");
         if (have_aov && have_batch) throw std::runtime_error("--aov cannot be combined with --batch (the guide pass has no batch form)");
         if (have_batch && watertight) throw std::runtime_error("--batch cannot be combined with --watertight (pt_render_batch has no watertight instances)");

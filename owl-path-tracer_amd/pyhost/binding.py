@@ -63,6 +63,12 @@ class Frame(C.Structure):
     _fields_ = [("camera", Camera), ("materials", C.POINTER(C.c_float))]
 
 
+class DenoiseParams(C.Structure):
+    """pt_denoise_params: iterations L (1..8), flags (PT_DENOISE_DEMODULATE), the four sigmas (> 0; +inf switches a term off)."""
+    _fields_ = [("iterations", C.c_int32), ("flags", C.c_int32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float),
+                ("sigma_albedo", C.c_float)]
+
+
 class Stats(C.Structure):
     _fields_ = [("kernel_ms", C.c_double), ("launches", C.c_int32), ("vgprs", C.c_int32), ("sgprs", C.c_int32), ("lds_bytes", C.c_int32),
                 ("block", C.c_int32), ("grid", C.c_int32), ("stack_entries", C.c_int32),
@@ -86,7 +92,9 @@ EXPORTS = ["pt_create", "pt_destroy", "pt_last_error", "pt_abi_version", "pt_upl
            "pt_group_create", "pt_group_destroy", "pt_group_size", "pt_group_ctx", "pt_group_last_error", "pt_group_upload_scene",
            "pt_group_set_materials", "pt_group_set_option", "pt_group_render", "pt_debug_quad_info", "pt_debug_oct_info", "pt_debug_clone_scene",
            "pt_render_batch", "pt_render_batch_device", "pt_debug_plan_batch", "pt_update_vertices", "pt_group_update_vertices", "pt_debug_update_info",
-           "pt_render_aov", "pt_render_aov_device", "pt_group_render_aov", "pt_debug_aov_host"]
+           "pt_render_aov", "pt_render_aov_device", "pt_group_render_aov", "pt_debug_aov_host",
+           "pt_denoise_default_params", "pt_denoise", "pt_denoise_device", "pt_debug_denoise_host"]
+PT_DENOISE_DEMODULATE = 1
 PT_TREE_DEVICE = 16  # pt_debug_export_tree: ORed into `which`, the array as HBM holds it
 PT_COMM_ID_BYTES = 128
 
@@ -176,6 +184,12 @@ def lib():
     L.pt_group_render_aov.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_int32, C.c_int32, C.c_int32, fp]
     L.pt_debug_aov_host.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_uint32), C.c_int64, fp]
     L.pt_debug_aov_host.restype = C.c_int64
+    L.pt_denoise_default_params.restype = None
+    L.pt_denoise_default_params.argtypes = [C.POINTER(DenoiseParams)]
+    L.pt_denoise.argtypes = [C.c_void_p, fp, fp, C.c_int32, C.c_int32, C.POINTER(DenoiseParams), fp, C.POINTER(C.c_uint32)]
+    L.pt_denoise_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(DenoiseParams), C.c_void_p, C.c_void_p, C.c_void_p]
+    L.pt_debug_denoise_host.argtypes = [C.c_void_p, fp, fp, C.c_int32, C.c_int32, C.POINTER(DenoiseParams), fp, C.POINTER(C.c_uint32)]
+    L.pt_debug_denoise_host.restype = C.c_int64
     _lib = L
     return L
 
@@ -251,6 +265,17 @@ def make_env(use_map=False, use_auto=False, color=(0, 0, 0), intensity=0.0, env_
     e.intensity = float(intensity)
     e.map, e._keep = _texture(env_map)
     return e
+
+
+def denoise_default_params(**changes):
+    """pt_denoise_default_params (5 iterations, no flag, sigmas 4, 0.25, 0.1, 0.2), with the given fields changed."""
+    p = DenoiseParams()
+    lib().pt_denoise_default_params(C.byref(p))
+    for k, v in changes.items():
+        if k not in dict(DenoiseParams._fields_):
+            raise KeyError(k)
+        setattr(p, k, v)
+    return p
 
 
 def plan_tiers(bucket_pixels, capacity, ns=96, force=False):
@@ -483,6 +508,35 @@ class Context:
         if n < 0:
             self._check(int(n), "pt_debug_aov_host")
         return out.reshape(H, W, 8)[::-1].copy() if whole else out
+
+    def _denoise(self, fn, what, rgb, aov, params, want_rgba8, in_place):
+        aov = np.ascontiguousarray(aov, np.float32)
+        H, W = aov.shape[0], aov.shape[1]
+        src = rgb if in_place else np.ascontiguousarray(rgb, np.float32)
+        assert src.dtype == np.float32 and src.flags["C_CONTIGUOUS"] and src.shape == (H, W, 3) and aov.shape == (H, W, 8)
+        out = src if in_place else np.empty((H, W, 3), np.float32)
+        rgba = np.empty((H, W), np.uint32) if want_rgba8 else None
+        fp = C.POINTER(C.c_float)
+        rc = fn(self._h, src.ctypes.data_as(fp), aov.ctypes.data_as(fp), W, H, C.byref(params) if params is not None else None, out.ctypes.data_as(fp),
+                rgba.ctypes.data_as(C.POINTER(C.c_uint32)) if rgba is not None else None)
+        if rc < 0:
+            self._check(int(rc), what)
+        return out, rgba
+
+    def denoise(self, rgb, aov, params=None, want_rgba8=False, in_place=False):
+        """pt_denoise: rgb (H, W, 3) as render returns it and aov (H, W, 8) as render_aov returns it -> the filtered frame (and its RGBA8
+        image).  params: a DenoiseParams (None: the defaults).  in_place: the result overwrites rgb (a contiguous float32 array)."""
+        return self._denoise(lib().pt_denoise, "pt_denoise", rgb, aov, params, want_rgba8, in_place)
+
+    def denoise_host(self, rgb, aov, params=None, want_rgba8=False, in_place=False):
+        """pt_debug_denoise_host, the CPU twin of denoise (works on a host-only context)."""
+        return self._denoise(lib().pt_debug_denoise_host, "pt_debug_denoise_host", rgb, aov, params, want_rgba8, in_place)
+
+    def denoise_device(self, d_rgb, d_aov, W, H, d_out_rgb, params=None, d_out_rgba8=None, stream=None):
+        """pt_denoise_device: asynchronous, device pointers (integers; d_out_rgb may equal d_rgb); synchronize() waits for it.  stream: a
+        hipStream_t as an integer, None = the context's own stream; ordering and lifetime as render_device."""
+        self._check(lib().pt_denoise_device(self._h, C.c_void_p(d_rgb), C.c_void_p(d_aov), W, H, C.byref(params) if params is not None else None, C.c_void_p(d_out_rgb),
+                                            C.c_void_p(d_out_rgba8) if d_out_rgba8 else None, C.c_void_p(stream) if stream else None), "pt_denoise_device")
 
     def comm_init_rank(self, unique_id, rank, world):
         buf = (C.c_uint8 * PT_COMM_ID_BYTES).from_buffer_copy(unique_id)

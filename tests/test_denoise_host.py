@@ -1,0 +1,232 @@
+"""The denoiser (pt_denoise: guide-driven a-trous filter) without a GPU.
+
+* The four exports exist, the ABI version is still 5, the default parameters are the header's.
+* The CPU twin pt_debug_denoise_host == the numpy restatement tests/denoise_ref.py bit for bit on every case of denoise_common.py
+  (colours with NaN, +-Inf, negatives, zeros; albedos with zeros; a +Inf depth and NaN normals; frames smaller than the kernel, frames
+  the taps leave, widths across 64 and 128; both flag values; every sigma at +infinity), out_rgba8 included, and in place.
+* Every refusal by code and message, nothing written; pt_denoise / pt_denoise_device on a host-only context: PT_E_NO_DEVICE.
+* `make asm-denoise`: no kernel needs scratch.  `pt_main --denoise` without --aov, or with --batch, is refused.
+* Three properties that a mistake shared by kernel, twin and restatement would break:
+  (a) a constant colour over random guides comes back within a relative 51 L 2^-24: per iteration at most 25 fma and 25 additions that
+      form the two sums, and one division (every weight is positive, so the quotient of the exact sums IS the constant);
+  (b) without the flag every output component lies inside the range of that component over the (sanitised) input, widened by the
+      same bound relative to the range's largest magnitude (a weighted mean with positive weights);
+  (c) two half-planes with perpendicular normals and different constant colours at the default sigmas: en = 2, kn = 16, so a tap
+      across the edge weighs at most e^-32 = 1.3e-14 of its spline weight and each side keeps its colour within 1e-6 relative.
+* Quality against the oracle's own high-sample frame: Cornell 64 x 48, 8 spp against 2048 spp, guides from pt_debug_aov_host at n = 1,
+  default parameters: relRMSE of the denoised frame <= 0.5 x that of the noisy one.  (A numpy draft of the definition gave 0.262 against
+  1.183 without the flag and 0.367 with it.)"""
+import ctypes as C
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+import aov_common as AC
+import denoise_common as DC
+import denoise_ref
+from owl_path_tracer_amd.pyhost import binding as B
+
+ROOT = AC.ROOT
+F32 = np.float32
+INF = float("inf")
+PT_E_INVALID, PT_E_NO_DEVICE = -1, -2
+
+
+@pytest.fixture(scope="module")
+def host():
+    ctx = B.Context(-1)
+    yield ctx
+    ctx.close()
+
+
+def test_exports_abi_and_defaults():
+    L = B.lib()
+    header = open(B.HEADER_PATH).read()
+    for name in ("pt_denoise_default_params", "pt_denoise", "pt_denoise_device", "pt_debug_denoise_host"):
+        assert hasattr(L, name), name
+        assert name in B.EXPORTS
+        assert re.search(r"\b%s\(" % name, header), name
+    assert L.pt_abi_version() == 5
+    p = B.denoise_default_params()
+    assert (p.iterations, p.flags) == (5, 0)
+    assert [F32(x) for x in (p.sigma_color, p.sigma_normal, p.sigma_depth, p.sigma_albedo)] == [F32(4.0), F32(0.25), F32(0.1), F32(0.2)]
+    assert C.sizeof(B.DenoiseParams) == 24
+    assert "pt_denoise_device" in re.search(r"The asynchronous calls \(([^)]*)\)", header).group(1)
+
+
+@pytest.mark.parametrize("cid", DC.IDS)
+def test_host_twin_equals_the_restatement(orc, host, cid):
+    rgb, aov = DC.inputs(cid)
+    want, want8 = DC.reference(cid)
+    assert np.isfinite(want).all()
+    p = DC.params(B, cid)
+    got, got8 = host.denoise_host(rgb, aov, p, want_rgba8=True)
+    DC.assert_same(got, want, "%s: host twin vs denoise_ref" % cid)
+    assert (got8 == want8).all(), cid
+    buf = np.array(rgb, F32)  # in place: out_rgb = rgb
+    same, _ = host.denoise_host(buf, aov, p, in_place=True)
+    assert same is buf
+    DC.assert_same(buf, want, "%s: in place" % cid)
+    if rgb.size > 3 and p.iterations > 1:
+        assert (DC.bits(want) != DC.bits(np.where(np.isfinite(rgb), rgb, 0))).any(), "the filter must change the frame"
+
+
+def test_default_parameters_are_what_null_means(host):
+    rgb, aov = DC.frame(21, 13, 5)
+    a, a8 = host.denoise_host(rgb, aov, None, want_rgba8=True)
+    b, b8 = host.denoise_host(rgb, aov, B.denoise_default_params(), want_rgba8=True)
+    DC.assert_same(a, b, "NULL parameters")
+    assert (a8 == b8).all()
+
+
+def test_refusals(host):
+    L = B.lib()
+    W, H = 8, 6
+    rgb = np.full((H, W, 3), 0.5, F32)
+    aov = np.full((H, W, 8), 0.5, F32)
+    out = np.full((H, W, 3), 7.0, F32)
+    out8 = np.full((H, W), 7, np.uint32)
+    fp = C.POINTER(C.c_float)
+    r, g, o, o8 = rgb.ctypes.data_as(fp), aov.ctypes.data_as(fp), out.ctypes.data_as(fp), out8.ctypes.data_as(C.POINTER(C.c_uint32))
+    P = lambda **kw: C.byref(B.denoise_default_params(**kw))
+    h = host._h
+
+    def refused(args, word):
+        assert L.pt_debug_denoise_host(*args) == PT_E_INVALID, word
+        assert word in L.pt_last_error(h).decode(), (word, L.pt_last_error(h).decode())
+
+    assert L.pt_debug_denoise_host(None, r, g, W, H, None, o, o8) == PT_E_INVALID
+    refused((h, None, g, W, H, None, o, o8), "NULL rgb")
+    refused((h, r, None, W, H, None, o, o8), "NULL aov")
+    refused((h, r, g, W, H, None, None, o8), "NULL out_rgb")
+    for w, hh in ((0, H), (W, 0), (-1, H), (W, -3), (65536, 1), (1, 65536), (65535, 65535)):
+        refused((h, r, g, w, hh, None, o, o8), "bad frame size %dx%d" % (w, hh))
+    for it in (0, 9, -1):
+        refused((h, r, g, W, H, P(iterations=it), o, o8), "iterations %d outside 1..8" % it)
+    for fl in (2, 3, 0x100, -2):
+        refused((h, r, g, W, H, P(flags=fl), o, o8), "unknown flag bits")
+    for name in ("sigma_color", "sigma_normal", "sigma_depth", "sigma_albedo"):
+        for v in (0.0, -1.0, float("nan"), -INF):
+            refused((h, r, g, W, H, P(**{name: v}), o, o8), name)
+    assert (out == 7.0).all() and (out8 == 7).all(), "a refused call wrote to the output"
+    # no CPU fallback behind the device entry points, with or without valid arguments
+    assert L.pt_denoise(h, r, g, W, H, None, o, o8) == PT_E_NO_DEVICE
+    assert L.pt_denoise_device(h, C.c_void_p(16), C.c_void_p(16), W, H, None, C.c_void_p(16), None, None) == PT_E_NO_DEVICE
+    assert L.pt_denoise(h, None, g, W, H, None, o, o8) == PT_E_INVALID and "NULL rgb" in L.pt_last_error(h).decode()
+    assert L.pt_denoise_device(h, C.c_void_p(16), None, W, H, None, C.c_void_p(16), None, None) == PT_E_INVALID
+    assert L.pt_denoise(None, r, g, W, H, None, o, o8) == PT_E_INVALID
+    assert (out == 7.0).all() and (out8 == 7).all()
+    assert L.pt_debug_denoise_host(h, r, g, W, H, P(sigma_depth=INF, iterations=8, flags=1), o, None) == W * H  # all of these are allowed
+    assert np.isfinite(out).all() and (out != 7.0).all()
+
+
+def test_denoise_kernels_need_no_scratch():
+    """From the Makefile's own target (the flags that ship): the three kernels report ScratchSize 0."""
+    if not (shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc")):
+        pytest.skip("hipcc not available")
+    csrc = os.path.join(ROOT, "owl-path-tracer_amd", "csrc")
+    env = {k: v for k, v in os.environ.items() if k not in ("CXXFLAGS", "MAKEFLAGS")}
+    r = subprocess.run(["make", "-s", "-C", csrc, "asm-denoise"], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, (r.stdout + r.stderr)[-2000:]
+    blocks = re.findall(r"Function Name: (\S+).*?VGPRs: (\d+).*?ScratchSize \[bytes/lane\]: (\d+)", r.stdout + r.stderr, flags=re.S)
+    names = [b[0] for b in blocks]
+    assert len(blocks) == 3 and all("pt_denoise_" in nm for nm in names), names
+    for stage in ("prepare", "iter", "finish"):
+        assert sum(("pt_denoise_%s_kernel" % stage) in nm for nm in names) == 1, names
+    assert all(int(sz) == 0 for _, _, sz in blocks), blocks
+
+
+def test_pt_main_refuses_denoise_without_guides_or_with_a_batch():
+    pt_main = os.path.join(ROOT, "owl-path-tracer_amd", "pt_main")
+    for extra, word in ((["--denoise"], "--aov"), (["--aov", "1", "--denoise", "--batch", "2"], "--batch")):
+        r = subprocess.run([pt_main, "--device", "-1", "--assets", os.path.join(ROOT, "assets")] + extra, capture_output=True, text=True, timeout=120)
+        assert r.returncode == 1 and "--denoise" in r.stderr and word in r.stderr, r.stderr[-1000:]
+
+
+def _bound(L):
+    return 51.0 * L * 2.0 ** -24
+
+
+@pytest.mark.parametrize("L", [1, 5, 8])
+def test_constant_colour_stays_constant(host, L):
+    rng = np.random.default_rng(40 + L)
+    W, H = 41, 27
+    aov = DC.guides(rng, W, H)
+    col = np.array([0.7, 3.25, 1e-3], F32)
+    rgb = np.broadcast_to(col, (H, W, 3)).copy()
+    for impl in (lambda: host.denoise_host(rgb, aov, B.denoise_default_params(iterations=L))[0], lambda: denoise_ref.denoise(rgb, aov, iterations=L)[0]):
+        out = impl().astype(np.float64)
+        rel = np.abs(out - col.astype(np.float64)) / col.astype(np.float64)
+        print("L = %d: largest relative deviation %.3g (bound %.3g)" % (L, rel.max(), _bound(L)))
+        assert rel.max() <= _bound(L)
+
+
+@pytest.mark.parametrize("cid", [c for c in DC.IDS if "_f0" in c])
+def test_output_stays_inside_the_input_range(host, cid):
+    rgb, aov = DC.inputs(cid)
+    p = DC.params(B, cid)
+    out, _ = host.denoise_host(rgb, aov, p)
+    clean = np.where(np.isfinite(rgb), rgb, F32(0.0)).astype(np.float64)
+    for k in range(3):
+        lo, hi = clean[..., k].min(), clean[..., k].max()
+        slack = _bound(p.iterations) * max(abs(lo), abs(hi))
+        assert lo - slack <= out[..., k].min() and out[..., k].max() <= hi + slack, (cid, k, lo, hi, out[..., k].min(), out[..., k].max())
+
+
+def test_an_edge_in_the_normals_is_kept(host):
+    W, H = 48, 20
+    rgb = np.zeros((H, W, 3), F32)
+    aov = np.zeros((H, W, 8), F32)
+    left = np.arange(W) < 21
+    a, b = np.array([0.9, 0.2, 0.4], F32), np.array([0.1, 0.6, 2.0], F32)
+    rgb[:, left], rgb[:, ~left] = a, b
+    aov[..., 0:3] = 0.5
+    aov[..., 3] = 1.0
+    aov[:, left, 4:7], aov[:, ~left, 4:7] = (1.0, 0.0, 0.0), (0.0, 0.0, 1.0)
+    aov[..., 7] = 2.0
+    for flags in (0, 1):
+        for out in (host.denoise_host(rgb, aov, B.denoise_default_params(flags=flags))[0], denoise_ref.denoise(rgb, aov, flags=flags)[0]):
+            for side, colour in ((left, a), (~left, b)):
+                rel = np.abs(out[:, side].astype(np.float64) - colour) / colour
+                assert rel.max() <= 1e-6, (flags, rel.max())
+
+
+def rel_rmse(x, ref):
+    x, ref = x.astype(np.float64), ref.astype(np.float64)
+    return float(np.sqrt(np.mean((x - ref) ** 2 / (ref ** 2 + 1e-2))))
+
+
+@pytest.mark.parametrize("flags", [0, 1])
+def test_quality_against_the_high_sample_frame(orc, host, flags):
+    W, H = 64, 48
+    noisy, ref, aov = _cornell_frames(orc, W, H)
+    out, _ = host.denoise_host(noisy, aov, B.denoise_default_params(flags=flags))
+    before, after = rel_rmse(noisy, ref), rel_rmse(out, ref)
+    print("flags = %d: relRMSE noisy %.3f -> denoised %.3f" % (flags, before, after))
+    assert after <= 0.5 * before, (before, after)
+
+
+_frames = {}
+
+
+def _cornell_frames(orc, W, H):
+    """(8 spp frame, 2048 spp frame, guides at n = 1) of aov_common's Cornell, depth 8, computed once."""
+    if (W, H) not in _frames:
+        sc = AC.scene("cornell")
+        S = orc.Scene(sc["flat"])
+        cam = AC.camera(sc, W, H, orc.to_camera_data)
+        env = orc.make_env(**sc["env"])
+        noisy, _, _ = S.render(cam, env, W, H, 8, 8)
+        ref, _, _ = S.render(cam, env, W, H, 2048, 8)
+        ctx = B.Context(-1)
+        try:
+            AC.upload(ctx, sc, B)
+            aov = ctx.aov_host(AC.camera(sc, W, H, B.to_camera_data), W, H, 1)
+        finally:
+            ctx.close()
+        _frames[(W, H)] = (noisy, ref, aov)
+    return _frames[(W, H)]
