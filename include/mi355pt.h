@@ -166,14 +166,14 @@ int pt_render(pt_ctx* ctx, const pt_camera* cam, int32_t width, int32_t height, 
  * timing events.  The context's own stream is non-blocking: HIP orders nothing between it and a caller's stream.  THE LIBRARY does:
  * every call that touches what a frame in flight uses is ordered after the context's LAST ASYNCHRONOUS CALL, whichever stream that
  * call was given.  So any call of this header may follow a pt_*_device call at once, with no pt_synchronize between them.
- *   - The asynchronous calls (pt_render_device, pt_render_batch_device, pt_render_aov_device, pt_denoise_device, pt_reduce_framebuffer) wait ON THE
+ *   - The asynchronous calls (pt_render_device, pt_render_batch_device, pt_render_aov_device, pt_render_aov_follow_device, pt_denoise_device, pt_reduce_framebuffer) wait ON THE
  *     DEVICE: the stream they are given waits for an event recorded at the end of the previous asynchronous call - only if that call
  *     used another stream; on the same stream the stream's own order suffices and nothing is added.  The host returns at once, with
  *     two exceptions that existed before: a frame of another size, shard or batch length rewrites the pixel queue and a frame that
  *     needs larger work buffers reallocates them (pt_denoise_device: its filter records, when the frame is larger than any it filtered
  *     before) - both first wait on the host for the frame in flight; and pt_render_batch_device
  *     returns when its per-frame tables have reached HBM, i.e. after whatever precedes it on `stream`.
- *   - The blocking renders (pt_render, pt_render_batch, pt_render_aov) and pt_denoise run on the context's stream behind the same device-side wait
+ *   - The blocking renders (pt_render, pt_render_batch, pt_render_aov, pt_render_aov_follow) and pt_denoise run on the context's stream behind the same device-side wait
  *     and return with the context idle.  After a blocking call, or on the context's own stream, they add no wait at all.
  *   - The calls that change or read what a frame uses WAIT ON THE HOST for the last asynchronous call's stream (if it is not the
  *     context's) and then for the context's: pt_set_materials, pt_set_environment, pt_update_vertices, pt_upload_scene,
@@ -188,7 +188,7 @@ int pt_render(pt_ctx* ctx, const pt_camera* cam, int32_t width, int32_t height, 
 int pt_render_device(pt_ctx* ctx, const pt_camera* cam, int32_t width, int32_t height, int32_t max_samples, int32_t max_path_depth,
                      void* d_out_rgb, void* d_out_rgba8, void* stream);
 /* Waits on the host for the context's last asynchronous call - pt_render_device, pt_render_batch_device, pt_render_aov_device,
- * pt_denoise_device or pt_reduce_framebuffer, on the stream it was given - and for the context's own stream.  Every earlier asynchronous call of the context
+ * pt_render_aov_follow_device, pt_denoise_device or pt_reduce_framebuffer, on the stream it was given - and for the context's own stream.  Every earlier asynchronous call of the context
  * is complete then as well, whatever stream it used: each was ordered before the next (see pt_render_device).  Returns PT_E_HIP if a
  * wave's watchdog fired during the last frame (the image is then incomplete); pt_get_stats reports the same.  PT_OK at once on an idle
  * or host-only context.  A caller's stream may be destroyed once this has returned. */
@@ -245,7 +245,8 @@ int64_t pt_debug_plan_batch(int32_t width, int32_t height, int32_t n_frames, int
  *   The contributions are summed in float32 in sample order from 0, and the stored value is sum * (1.0f / (float)n_samples).
  * LAYOUT: 8 consecutive floats per pixel, {albedo r, g, b, alpha, normal x, y, z, depth}, at pixel offset x + W*(H-1-y) like out_rgb;
  * pixels the context does not own (pt_set_pixel_shard) are all 0.
- * LIMITS: first hit only - no follow-through on glass or mirrors (a window shows the window); no batch form (one frame per call).
+ * LIMITS: first hit only - a window shows the window, a mirror the mirror; pt_render_aov_follow below lets the guide ray pass such
+ * surfaces.  No batch form (one frame per call).
  * pt_render_aov: blocking.  Honours the pixel shard, the current material table and environment, "watertight", "box_exact", "quad", and
  * a scene moved by pt_update_vertices.  With a communicator: ONE sum-reduce of the W*H*8 floats onto rank 0 (one non-zero contributor
  * per pixel: bit-identical to the one-GPU buffers); the other ranks may pass NULL.  pt_get_stats afterwards: kernel_ms and launches (1)
@@ -257,6 +258,54 @@ int pt_render_aov(pt_ctx* ctx, const pt_camera* cam, int32_t width, int32_t heig
 /* The same, asynchronous on `stream` (NULL = the context's), no reduce, the W*H*8 floats left in HBM at d_out_aov (16-byte aligned);
  * conventions of pt_render_device.  pt_synchronize waits for it and returns PT_E_HIP if a walk ran out of its step or stack bound. */
 int pt_render_aov_device(pt_ctx* ctx, const pt_camera* cam, int32_t width, int32_t height, int32_t n_samples, void* d_out_aov, void* stream);
+
+/* ---- guide pass, follow mode: the guide ray passes mirrors and glass to the surface seen in them or through them ----
+ * The guide pass above with a loop around its walk; kernels of their own (csrc/pt_kernel_aov_follow.hip), the CPU twin
+ * pt_debug_aov_follow_host and the numpy restatement tests/aov_follow_ref.py implement exactly this.
+ * DEFINITION, per sample.  The camera ray, the RNG draws and the closest-hit rule are exactly those of pt_render_aov; the follow loop
+ * draws nothing from the stream.  Arithmetic: the contract of csrc/pt_device.h, and its reflect, refract, dot, normalize, sqrt_; interp3
+ * of csrc/pt_trace.h.
+ *   tint = (1,1,1); dist = 0; o = camera origin; d = camera ray direction
+ *   for step = 0, 1, ...:
+ *     closest hit of (o, d) under the library's rule (t > 1e-3, minimum t, lower id, slivers never; "watertight" selects the test)
+ *     step 0 decides alpha: 1 on a hit, 0 on a miss                    (coverage stays first-hit: it is for compositing)
+ *     miss:  albedo = tint * (what the miss shader returns for d); normal = 0; depth = dist; stop
+ *     dist = dist + t                                                   (float32, in step order)
+ *     material row, texture slot, bw = 1 - u - v, bx = u, by = v, v_n = normalize(interp3 of the vertex normals), base colour after the
+ *       texture lookup: the expressions of pt_render_aov's hit, i.e. of the hit shader, unchanged
+ *     kind = NONE if emission > 0, or step == max_follow, or a component of v_n is not finite; else classify(material)
+ *     kind NONE:  albedo = tint * (emission > 0 ? (e,e,e) : base colour); normal = v_n if finite else 0; depth = dist; stop
+ *     wo = -d;  v_p = interp3(bw, bx, by, p0, p1, p2)                   (the hit shader's hit point, no normal offset)
+ *     MIRROR: wi = reflect(wo, v_n);                       tint' = tint * base colour
+ *     GLASS:  c = dot(wo, v_n);  c > 0 ? (n' = v_n, eta = 1.0f / ior) : (n' = -v_n, eta = ior)
+ *             refract(wo, n', eta, wi) succeeds:           tint' = tint * (sqrt_(base.x), sqrt_(base.y), sqrt_(base.z))
+ *             else (total internal reflection):            wi = reflect(wo, v_n); tint' = tint * base colour
+ *     d' = normalize(wi); a component of d' not finite: this surface is kind NONE after all (its albedo under the tint that reached it), stop
+ *     o = v_p; d = d'; tint = tint'
+ *   classify: with the lobe weights of the BSDF sampler, mw = metallic, gw = (1 - metallic) * specular_transmission,
+ *     dw = (1 - specular_transmission) * (1 - metallic), cw = 0.25f * clearcoat:
+ *     MIRROR if mw > gw && mw > dw && mw > cw && roughness <= roughness_max;
+ *     else GLASS if gw > mw && gw > dw && gw > cw && specular_transmission_roughness <= roughness_max;  else NONE (NaN fields land here).
+ *   Accumulation, the 1.0f / n_samples scale, the 8-float layout, the framebuffer order and the pixel shard are those of pt_render_aov.
+ * CONSEQUENCES: max_follow = 0 is bit for bit pt_render_aov (1.0f * x and 0 + t are exact); for any max_follow a sample whose first hit
+ * is not followed contributes exactly what it contributes to pt_render_aov.
+ * LIMITS: the normal of a followed sample is the last surface's normal in world space, not mirrored into the virtual image; depth is
+ * the path length; at glass only the transmitted ray is followed, except on total internal reflection - the Fresnel reflection on a
+ * window is not guided; the tint ignores Fresnel and the specular tint; no batch form.
+ * pt_render_aov_follow (blocking) and pt_render_aov_follow_device (asynchronous; joins the asynchronous calls of the streams contract at
+ * pt_render_device: ordered after the context's last asynchronous call and itself the last one afterwards) behave like pt_render_aov and
+ * pt_render_aov_device in everything those list: arguments checked before anything is touched, PT_E_NO_SCENE, PT_E_INVALID - also for
+ * max_follow outside 0..8, roughness_max outside [0, 1] or NaN, reserved != 0 -, the refusal of "watertight" = 1 on the binary walk, one
+ * sum-reduce with a communicator, the pt_get_stats fields, no render state kept. */
+typedef struct pt_aov_params {
+    int32_t n_samples;    /* >= 1 */
+    int32_t max_follow;   /* 0..8 specular surfaces a guide ray may pass; 0 = first hit */
+    float roughness_max;  /* 0..1: a surface rougher than this is not followed */
+    int32_t reserved;     /* must be 0 */
+} pt_aov_params;
+void pt_aov_default_params(pt_aov_params* p);   /* 1, 4, 0.3f, 0 */
+int pt_render_aov_follow(pt_ctx* ctx, const pt_camera* cam, int32_t width, int32_t height, const pt_aov_params* p /* NULL = defaults */, float* out_aov);
+int pt_render_aov_follow_device(pt_ctx* ctx, const pt_camera* cam, int32_t width, int32_t height, const pt_aov_params* p, void* d_out_aov, void* stream);
 
 /* ---- denoiser: guide-driven a-trous filter for low-sample frames (no reference counterpart; the reference binds no denoiser) ----
  * An edge-avoiding a-trous wavelet filter (Dammertz, Sewtz, Hanika, Lensch 2010): L iterations of a 5 x 5 B3-spline kernel whose tap
@@ -285,8 +334,8 @@ int pt_render_aov_device(pt_ctx* ctx, const pt_camera* cam, int32_t width, int32
  *             sum_k = fma_(w, c_i(q)_k, sum_k), wsum = wsum + w.
  *             After the 25 taps: c_{i+1}(p)_k = sum_k / wsum (wsum >= 9/64 always: the centre tap).
  *   Finish:   out_k = c_L_k * d_k with the flag, else c_L_k;  out_rgba8 = make_rgba(out).
- * LIMITS: relative depth under-filters surfaces seen at grazing angles; the guides are first-hit, so glass and mirrors are filtered by
- * their own surface, not by what shows in them; the colour sigma halves each iteration, as in the paper.
+ * LIMITS: relative depth under-filters surfaces seen at grazing angles; with the guides of pt_render_aov glass and mirrors are filtered by
+ * their own surface, not by what shows in them (pt_render_aov_follow supplies guides that follow them); the colour sigma halves each iteration, as in the paper.
  * REFUSED with PT_E_INVALID and a message, before anything is touched: a NULL pointer (p and out_rgba8 excepted), W or H outside
  * 1..65535 or W*H >= 2^31, iterations outside 1..8, a flag bit other than PT_DENOISE_DEMODULATE, a sigma that is not > 0 (NaN included;
  * +infinity is allowed and switches the term off).  A host-only context answers pt_denoise and pt_denoise_device with PT_E_NO_DEVICE.
@@ -352,6 +401,8 @@ int pt_group_render(pt_group* g, const pt_camera* cam, int32_t width, int32_t he
                     float* out_rgb, uint32_t* out_rgba8);
 /* pt_render_aov over the group: every device's own tiles, one reduce of the W*H*8 floats onto devices[0], read-back from there */
 int pt_group_render_aov(pt_group* g, const pt_camera* cam, int32_t width, int32_t height, int32_t n_samples, float* out_aov);
+/* pt_render_aov_follow over the group, the same way */
+int pt_group_render_aov_follow(pt_group* g, const pt_camera* cam, int32_t width, int32_t height, const pt_aov_params* p /* NULL = defaults */, float* out_aov);
 
 /* Tuning / test options (all have working defaults; none changes an image, except "watertight"):
  *   "kernel" 2 (default, wavefront-scheduled) | 1 (lane per pixel);  "count" 0/1: instrumented kernel that fills pt_stats;
@@ -415,6 +466,9 @@ int64_t pt_debug_closest_hit_host_n(pt_ctx* ctx, const float* rays, int64_t n, f
  * pixel, in list order.  Returns n_pixels; PT_E_NO_SCENE / PT_E_INVALID as pt_render_aov, and PT_E_INVALID for an id outside the frame. */
 int64_t pt_debug_aov_host(pt_ctx* ctx, const pt_camera* cam, int32_t width, int32_t height, int32_t n_samples, const uint32_t* pixel_ids,
                           int64_t n_pixels, float* out);
+/* The CPU twin of the follow mode (pt_render_aov_follow), the same way; p NULL = the defaults; PT_E_INVALID also for what that call refuses in p. */
+int64_t pt_debug_aov_follow_host(pt_ctx* ctx, const pt_camera* cam, int32_t width, int32_t height, const pt_aov_params* p, const uint32_t* pixel_ids,
+                                 int64_t n_pixels, float* out);
 /* Batched device-side evaluation of the kernel's building blocks on the GPU (op codes in pt_kernel_aux.hip):
  * lets the parity tests compare them bit-for-bit with the oracle.  in/out are host arrays.
  * Ops 30..35 are RAY PROBES: in = o[3], d[3] per ray, out = {hit, t, u, v, id bits, aux} (6 floats), through the device functions of

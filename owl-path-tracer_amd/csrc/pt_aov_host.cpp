@@ -1,4 +1,5 @@
-// pt_aov_host.cpp -- pt_debug_aov_host: the CPU twin of the guide pass (pt_render_aov; kernel: pt_kernel.hip "guide pass").
+// pt_aov_host.cpp -- pt_debug_aov_host: the CPU twin of the guide pass (pt_render_aov; kernel: pt_kernel.hip "guide pass"), and
+// pt_debug_aov_follow_host, the twin of its follow mode (pt_render_aov_follow; "guide pass, follow mode"), with that mode's parameter checks.
 // The twin runs the definition of include/mi355pt.h with the host walk of pt_debug_closest_hit_host_n over the host copies of the
 // scene, and with the arithmetic of pt_device.h itself: the header is included here with PTD = static inline, so rng_init, rng_next,
 // normalize, lerp3, uv_on_sphere (the polynomial atan2 / asin), tex_nearest and the material row are the functions the kernel
@@ -111,16 +112,166 @@ void aov_pixel(const AovScene& A, int px, int py, float* y)
     y[4] = s_nrm.x * inv_n; y[5] = s_nrm.y * inv_n; y[6] = s_nrm.z * inv_n; y[7] = s_depth * inv_n;
 }
 
+// Follow mode, one pixel: include/mi355pt.h, "guide pass, follow mode"; the loop of pt_aov_follow_kernel and aov_follow_surface line for line.
+enum { AOV_NONE = 0, AOV_MIRROR = 1, AOV_GLASS = 2 };
+int aov_classify(const Material& m, float roughness_max) // sample_disney's lobe weights
+{
+    const float dw = (1.0f - m.specular_transmission) * (1.0f - m.metallic);
+    const float mw = m.metallic;
+    const float cw = 0.25f * m.clearcoat;
+    const float gw = (1.0f - m.metallic) * m.specular_transmission;
+    if (mw > gw && mw > dw && mw > cw && m.roughness <= roughness_max) return AOV_MIRROR;
+    if (gw > mw && gw > dw && gw > cw && m.specular_transmission_roughness <= roughness_max) return AOV_GLASS;
+    return AOV_NONE;
+}
+
+void aov_follow_pixel(const AovScene& A, const pt_aov_params& prm, int px, int py, float* y)
+{
+    const HostScene& S = *A.s;
+    uint32_t rng = rng_init((uint32_t)px, (uint32_t)py);
+    v3 s_alb = vs(0.0f), s_nrm = vs(0.0f);
+    float s_alpha = 0.0f, s_depth = 0.0f;
+    const v3 origin = V(A.cam.origin[0], A.cam.origin[1], A.cam.origin[2]), llc = V(A.cam.llc[0], A.cam.llc[1], A.cam.llc[2]);
+    const v3 hor = V(A.cam.horizontal[0], A.cam.horizontal[1], A.cam.horizontal[2]), ver = V(A.cam.vertical[0], A.cam.vertical[1], A.cam.vertical[2]);
+    for (int k = 0; k < A.n; ++k) {
+        const float rx = rng_next(rng); // gen_camera_ray (pt_trace.h)
+        const float ry = rng_next(rng);
+        const float su = ((float)px + rx) / (float)A.W;
+        const float sv = ((float)py + ry) / (float)A.H;
+        v3 o = origin, d = normalize(((llc + hor * su) + ver * sv) - origin);
+        v3 tint = vs(1.0f), alb = vs(0.0f), nrm = vs(0.0f);
+        float dist = 0.0f, alpha = 0.0f, depth = 0.0f;
+        for (int step = 0;; ++step) {
+            const float of[3] = {o.x, o.y, o.z}, df[3] = {d.x, d.y, d.z};
+            float t = 0.0f, hu = 0.0f, hv = 0.0f;
+            int32_t prim = -1;
+            const bool hit = pt_bvh_closest_hit_host(S.bvh, of, df, kTMin, kTMax, &t, &hu, &hv, &prim, A.wt);
+            if (step == 0) alpha = hit ? 1.0f : 0.0f; // coverage stays first-hit
+            if (!hit) { // shade_hit's miss branch
+                v3 radiance = vs(0.0f);
+                if (S.env.use_map && S.env_map.w > 0) {
+                    float tu, tv;
+                    uv_on_sphere(d, tu, tv);
+                    radiance = radiance + tex_nearest(S.env_map.px.data(), S.env_map.w, S.env_map.h, tu, tv);
+                } else if (S.env.use_auto) {
+                    radiance = radiance + lerp3(vs(1.0f), V(0.5f, 0.7f, 1.0f), 0.5f * (d.y + 1.0f));
+                } else {
+                    radiance = radiance + V(S.env.color[0], S.env.color[1], S.env.color[2]);
+                }
+                alb = tint * (radiance * S.env.intensity);
+                nrm = vs(0.0f);
+                depth = dist;
+                break;
+            }
+            dist = dist + t;
+            const size_t slot = (size_t)A.slot_of[(size_t)prim];
+            const PtShade& sh = S.shade[slot];
+            const PtTri& tr = S.bvh.tris[slot];
+            const int mi = tr.material;
+            Material mat = material_default();
+            int32_t tex_slot = -1;
+            if (mi >= 0) {
+                const float* mp = &S.materials[(size_t)mi * PT_MAT_STRIDE];
+                mat = material_load(mp);
+                std::memcpy(&tex_slot, mp + 17, 4);
+            }
+            const float bx = hu, by = hv;
+            const float bw = 1.0f - bx - by;
+            const v3 v_n = normalize(interp3(bw, bx, by, V(sh.n0[0], sh.n0[1], sh.n0[2]), V(sh.n1[0], sh.n1[1], sh.n1[2]), V(sh.n2[0], sh.n2[1], sh.n2[2])));
+            const bool n_ok = finite_(v_n.x) && finite_(v_n.y) && finite_(v_n.z);
+            const bool emits = mat.emission > 0.0f;
+            if (!emits && tex_slot >= 0) {
+                const float tu = fma_(by, sh.tc[4], fma_(bx, sh.tc[2], bw * sh.tc[0]));
+                const float tv = fma_(by, sh.tc[5], fma_(bx, sh.tc[3], bw * sh.tc[1]));
+                const HostTexture& tx = S.textures[(size_t)tex_slot];
+                mat.base_color = tex_nearest(tx.px.data(), tx.w, tx.h, tu, tv);
+            }
+            const int kind = (emits || step == prm.max_follow || !n_ok) ? (int)AOV_NONE : aov_classify(mat, prm.roughness_max);
+            if (kind != AOV_NONE) {
+                const v3 wo = -d;
+                v3 wi = vs(0.0f), t2 = tint * mat.base_color;
+                bool through = false;
+                if (kind == AOV_GLASS) {
+                    const float ct = dot(wo, v_n);
+                    through = ct > 0.0f ? refract(wo, v_n, 1.0f / mat.ior, wi) : refract(wo, -v_n, mat.ior, wi);
+                }
+                if (through) t2 = tint * V(sqrt_(mat.base_color.x), sqrt_(mat.base_color.y), sqrt_(mat.base_color.z));
+                else wi = reflect(wo, v_n); // a mirror, or total internal reflection
+                const v3 dn = normalize(wi);
+                if (finite_(dn.x) && finite_(dn.y) && finite_(dn.z)) {
+                    o = interp3(bw, bx, by, V(tr.p0[0], tr.p0[1], tr.p0[2]), V(tr.p1[0], tr.p1[1], tr.p1[2]), V(tr.p2[0], tr.p2[1], tr.p2[2])); // shade_hit's v_p
+                    d = dn;
+                    tint = t2;
+                    continue;
+                }
+            }
+            alb = tint * (emits ? vs(mat.emission) : mat.base_color);
+            nrm = n_ok ? v_n : vs(0.0f);
+            depth = dist;
+            break;
+        }
+        s_alb = s_alb + alb; s_alpha = s_alpha + alpha;
+        s_nrm = s_nrm + nrm; s_depth = s_depth + depth;
+    }
+    const float inv_n = 1.0f / (float)A.n;
+    y[0] = s_alb.x * inv_n; y[1] = s_alb.y * inv_n; y[2] = s_alb.z * inv_n; y[3] = s_alpha * inv_n;
+    y[4] = s_nrm.x * inv_n; y[5] = s_nrm.y * inv_n; y[6] = s_nrm.z * inv_n; y[7] = s_depth * inv_n;
+}
+
+// What both twins take: the argument checks of pt_debug_aov_host, the scene's host copies, the slot table
+int64_t aov_host(pt_ctx* c, const pt_camera* cam, int32_t W, int32_t H, int32_t n_samples, const uint32_t* pixel_ids, int64_t n_pixels, float* out, const pt_aov_params* follow,
+                 const char* who);
+
 } // namespace
+
+namespace pti {
+// What pt_render_aov_follow, its device form and the twin refuse alike, before anything is touched; *eff = the parameters in effect.
+int check_aov_params(pt_ctx* c, const pt_aov_params* p, const char* who, pt_aov_params* eff)
+{
+    if (p) *eff = *p;
+    else pt_aov_default_params(eff);
+    if (eff->n_samples < 1) return fail(c, PT_E_INVALID, "%s: n_samples %d must be >= 1", who, eff->n_samples);
+    if (eff->max_follow < 0 || eff->max_follow > 8) return fail(c, PT_E_INVALID, "%s: max_follow %d outside 0..8", who, eff->max_follow);
+    if (!(eff->roughness_max >= 0.0f && eff->roughness_max <= 1.0f)) return fail(c, PT_E_INVALID, "%s: roughness_max %g outside 0..1", who, (double)eff->roughness_max);
+    if (eff->reserved != 0) return fail(c, PT_E_INVALID, "%s: reserved must be 0 (got %d)", who, eff->reserved);
+    return PT_OK;
+}
+} // namespace pti
+
+extern "C" void pt_aov_default_params(pt_aov_params* p)
+{
+    if (!p) return;
+    p->n_samples = 1;
+    p->max_follow = 4;
+    p->roughness_max = 0.3f;
+    p->reserved = 0;
+}
+
+extern "C" int64_t pt_debug_aov_follow_host(pt_ctx* c, const pt_camera* cam, int32_t W, int32_t H, const pt_aov_params* p, const uint32_t* pixel_ids, int64_t n_pixels, float* out)
+{
+    if (!c || !cam || !out || n_pixels < 0 || (n_pixels > 0 && !pixel_ids)) return PT_E_INVALID;
+    if (!c->have_scene) return fail(c, PT_E_NO_SCENE, "no geometries (pt_upload_scene not called)");
+    pt_aov_params prm;
+    const int rc = check_aov_params(c, p, "pt_debug_aov_follow_host", &prm);
+    if (rc) return rc;
+    return aov_host(c, cam, W, H, prm.n_samples, pixel_ids, n_pixels, out, &prm, "pt_debug_aov_follow_host");
+}
 
 extern "C" int64_t pt_debug_aov_host(pt_ctx* c, const pt_camera* cam, int32_t W, int32_t H, int32_t n_samples, const uint32_t* pixel_ids, int64_t n_pixels, float* out)
 {
     if (!c || !cam || !out || n_pixels < 0 || (n_pixels > 0 && !pixel_ids)) return PT_E_INVALID;
     if (!c->have_scene) return fail(c, PT_E_NO_SCENE, "no geometries (pt_upload_scene not called)");
+    return aov_host(c, cam, W, H, n_samples, pixel_ids, n_pixels, out, nullptr, "pt_debug_aov_host");
+}
+
+namespace {
+int64_t aov_host(pt_ctx* c, const pt_camera* cam, int32_t W, int32_t H, int32_t n_samples, const uint32_t* pixel_ids, int64_t n_pixels, float* out, const pt_aov_params* follow,
+                 const char* who)
+{
     if (W <= 0 || H <= 0 || W > 65535 || H > 65535 || n_samples <= 0 || (int64_t)W * H > (int64_t)0x7fffffff)
         return fail(c, PT_E_INVALID, "bad guide pass size %dx%d, %d samples", W, H, n_samples);
     for (int64_t i = 0; i < n_pixels; ++i)
-        if (pixel_ids[i] >= (uint32_t)W * (uint32_t)H) return fail(c, PT_E_INVALID, "pt_debug_aov_host: pixel id %u outside the %dx%d frame", pixel_ids[i], W, H);
+        if (pixel_ids[i] >= (uint32_t)W * (uint32_t)H) return fail(c, PT_E_INVALID, "%s: pixel id %u outside the %dx%d frame", who, pixel_ids[i], W, H);
     sync_host_scene(c);
     AovScene A;
     A.s = &c->scene;
@@ -133,7 +284,12 @@ extern "C" int64_t pt_debug_aov_host(pt_ctx* c, const pt_camera* cam, int32_t W,
         if (id >= 0 && (size_t)id < A.slot_of.size()) A.slot_of[(size_t)id] = (int32_t)s; // (padding slots carry id 0x7fffffff)
     }
     pt_parallel_ranges((size_t)n_pixels, [&](size_t lo, size_t hi) {
-        for (size_t i = lo; i < hi; ++i) aov_pixel(A, (int)(pixel_ids[i] % (uint32_t)W), (int)(pixel_ids[i] / (uint32_t)W), out + 8 * i);
+        for (size_t i = lo; i < hi; ++i) {
+            const int px = (int)(pixel_ids[i] % (uint32_t)W), py = (int)(pixel_ids[i] / (uint32_t)W);
+            if (follow) aov_follow_pixel(A, *follow, px, py, out + 8 * i);
+            else aov_pixel(A, px, py, out + 8 * i);
+        }
     });
     return n_pixels;
 }
+} // namespace

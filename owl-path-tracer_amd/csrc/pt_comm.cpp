@@ -361,7 +361,23 @@ int pt_group_render(pt_group* g, const pt_camera* cam, int32_t W, int32_t H, int
 
 // The guide pass over the group: every device runs the guide kernel over its own tiles, ONE grouped reduce of the W*H*8 floats onto
 // device 0, read-back from there.
+static int group_render_aov(pt_group* g, const pt_camera* cam, int32_t W, int32_t H, int32_t n_samples, const pt_aov_params* follow, float* out_aov);
+
 int pt_group_render_aov(pt_group* g, const pt_camera* cam, int32_t W, int32_t H, int32_t n_samples, float* out_aov)
+{
+    return group_render_aov(g, cam, W, H, n_samples, nullptr, out_aov);
+}
+
+int pt_group_render_aov_follow(pt_group* g, const pt_camera* cam, int32_t W, int32_t H, const pt_aov_params* p, float* out_aov)
+{
+    pt_aov_params prm;
+    if (p) prm = *p;
+    else pt_aov_default_params(&prm);
+    return group_render_aov(g, cam, W, H, prm.n_samples, &prm, out_aov); // every device's pt_render_aov_follow_device checks prm
+}
+
+// follow == null: pt_render_aov_device on every device, else pt_render_aov_follow_device
+static int group_render_aov(pt_group* g, const pt_camera* cam, int32_t W, int32_t H, int32_t n_samples, const pt_aov_params* follow, float* out_aov)
 {
     if (!g || !cam || !out_aov || W <= 0 || H <= 0) return PT_E_INVALID;
     const int n = (int)g->ctx.size();
@@ -379,7 +395,7 @@ int pt_group_render_aov(pt_group* g, const pt_camera* cam, int32_t W, int32_t H,
         if (hipSetDevice(c->device) != hipSuccess) return fail_all(c, pti::fail(c, PT_E_HIP, "hipSetDevice(%d) failed", c->device));
         if (W > 65535 || H > 65535) return fail_all(c, pti::fail(c, PT_E_INVALID, "bad render size %dx%d", W, H));
         int rc = pti::ensure(c, c->d_aov, n_floats * 4);
-        if (!rc) rc = pt_render_aov_device(c, cam, W, H, n_samples, c->d_aov.p, nullptr);
+        if (!rc) rc = follow ? pt_render_aov_follow_device(c, cam, W, H, follow, c->d_aov.p, nullptr) : pt_render_aov_device(c, cam, W, H, n_samples, c->d_aov.p, nullptr);
         if (rc) return fail_all(c, rc);
     }
     pt_ctx* c0 = g->ctx[0];

@@ -151,6 +151,8 @@ PT_LOCAL void fill_params(pt_ctx* c, PtKernelParams& P);
 // pt_denoise_host.cpp
 PT_LOCAL int check_denoise_args(pt_ctx* c, const char* who, int W, int H, const pt_denoise_params* p, pt_denoise_params* eff); // the refusals of pt_denoise* and the twin; *eff = the parameters in effect
 PT_LOCAL void denoise_constants(const pt_denoise_params& p, float* kn, float* ka, float kc[8]); // the definition's host constants
+// pt_aov_host.cpp
+PT_LOCAL int check_aov_params(pt_ctx* c, const pt_aov_params* p, const char* who, pt_aov_params* eff); // the refusals of pt_render_aov_follow* and the twin; *eff = the parameters in effect
 // pt_comm.cpp
 PT_LOCAL int reduce_framebuffer(pt_ctx* c, void* d_rgb, void* d_rgba8, int64_t n_pixels, hipStream_t stream); // pt_reduce_framebuffer inside a call that is ordered already
 PT_LOCAL int reduce_sum(pt_ctx* c, void* d_buf, size_t n_floats, hipStream_t stream); // in-place sum-reduce onto rank 0; nothing without a communicator

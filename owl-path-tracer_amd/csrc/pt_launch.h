@@ -55,6 +55,14 @@ struct PtAovArgs {
     int32_t rank, world, tile; // pixel shard (pt_shard_pixels: tile a multiple of 8, tile (tx, ty) belongs to rank (tx + ty) % world)
     int32_t pad;
 };
+// Follow mode of the guide pass (pt_render_aov_follow; pt_kernel.hip "guide pass, follow mode"): the first-hit pass's arguments and pt_aov_params
+struct PtAovFollowArgs {
+    PtAovArgs a;
+    int32_t max_follow;  // 0..8 specular surfaces a guide ray may pass
+    float roughness_max; // a surface rougher than this is not followed
+    float inv_n;         // 1.0f / (float)n_samples, formed on the host (IEEE division, the first-hit kernel's value): a wave-uniform float costs a VGPR
+    int32_t pad;
+};
 
 // Denoiser (pt_denoise; pt_denoise.hip): what its three kernels take.  The host fills everything but the record pointers, which
 // pt_launch_denoise carves out of ws; the constants are include/mi355pt.h's "host constants" (pti::denoise_constants).
@@ -85,6 +93,11 @@ hipError_t pt_launch_aov(const PtKernelParams* p, const PtAovArgs* a, int binary
 hipError_t pt_aov_geometry(int binary, int exact, int stack_entries, PtGeometry* g);
 hipError_t pt_launch_aov_wt(const PtKernelParams* p, const PtAovArgs* a, int binary, int grid, size_t lds_bytes, hipStream_t stream);
 hipError_t pt_aov_geometry_wt(int binary, int exact, int stack_entries, PtGeometry* g);
+// pt_kernel_aov_follow.hip / pt_kernel_aov_follow_wt.hip: the follow kernels, same conventions; lds_bytes covers the stack and the state a lane parks behind it
+hipError_t pt_launch_aov_follow(const PtKernelParams* p, const PtAovFollowArgs* a, int binary, int grid, size_t lds_bytes, hipStream_t stream);
+hipError_t pt_aov_follow_geometry(int binary, int exact, int stack_entries, PtGeometry* g);
+hipError_t pt_launch_aov_follow_wt(const PtKernelParams* p, const PtAovFollowArgs* a, int binary, int grid, size_t lds_bytes, hipStream_t stream);
+hipError_t pt_aov_follow_geometry_wt(int binary, int exact, int stack_entries, PtGeometry* g);
 size_t pt_refit_workspace_bytes(void);
 // gather, extent, one refit launch per level, propagate - all on `stream`, `first` recorded before the first kernel, `last` after the last
 hipError_t pt_launch_refit(const PtRefitArgs* a, hipEvent_t first, hipEvent_t last, hipStream_t stream);

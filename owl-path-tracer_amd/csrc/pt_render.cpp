@@ -628,14 +628,15 @@ int read_back(pt_ctx* c, bool root, float* out_rgb, uint32_t* out_rgba8, size_t 
 // ---- guide pass (pt_render_aov) --------------------------------------------------------------------------------------------
 // One launch of the guide kernel over the frame's 8 x 8 pixel blocks; the kernel itself skips the blocks of other ranks' tiles, so the
 // pass needs no pixel queue and none of the render's buffers: it leaves the state of the render path (queue, d_laps, slots) alone.
+// follow != null: the follow kernels (pt_render_aov_follow; prm checked by the caller, check_aov_params) - same refusals, buffers and stats.
 #define PT_AOV_FLAG_WORDS 64 // d_aov_ws: the bound flag on a line of its own, then the overflow columns
-int aov_device(pt_ctx* c, const pt_camera* cam, int W, int H, int n_samples, void* d_out, hipStream_t stream)
+int aov_device(pt_ctx* c, const pt_camera* cam, int W, int H, int n_samples, void* d_out, hipStream_t stream, const pt_aov_params* follow = nullptr)
 {
     // refusals first: nothing is enqueued or allocated before them
     const bool quad = c->opt.quad && !c->scene.nodes4.empty();
     const bool wt = c->opt.watertight != 0;
     if (!quad && wt)
-        return fail(c, PT_E_INVALID, "pt_render_aov: without quad nodes (option quad = 0, or a tree too deep for them) the guide pass runs the binary walk, which has no watertight test (option watertight = 1)");
+        return fail(c, PT_E_INVALID, "%s: without quad nodes (option quad = 0, or a tree too deep for them) the guide pass runs the binary walk, which has no watertight test (option watertight = 1)", follow ? "pt_render_aov_follow" : "pt_render_aov");
     if (quad && (c->scene.bvh.tris.size() * sizeof(PtTri) > 0xffffffffull || c->scene.nodes4.size() * sizeof(PtNode4) > 0xffffffffull))
         return fail(c, PT_E_LIMIT, "the guide kernel needs triangle records and quad nodes below 4 GiB each (%zu triangle slots, %zu quad nodes)", c->scene.bvh.tris.size(), c->scene.nodes4.size());
     PtKernelParams P;
@@ -652,7 +653,8 @@ int aov_device(pt_ctx* c, const pt_camera* cam, int W, int H, int n_samples, voi
         P.stack_entries = c->scene.bvh.depth < 1 ? 1 : c->scene.bvh.depth;
     }
     PtGeometry g{};
-    const hipError_t ge = (wt ? pt_aov_geometry_wt : pt_aov_geometry)(quad ? 0 : 1, P.box_exact, P.stack_entries, &g);
+    const hipError_t ge = follow ? (wt ? pt_aov_follow_geometry_wt : pt_aov_follow_geometry)(quad ? 0 : 1, P.box_exact, P.stack_entries, &g)
+                                 : (wt ? pt_aov_geometry_wt : pt_aov_geometry)(quad ? 0 : 1, P.box_exact, P.stack_entries, &g);
     if (ge == hipErrorInvalidConfiguration) return fail(c, PT_E_LIMIT, "this build of the guide kernel spills registers to scratch; such builds are refused (pt_kernel.hip)");
     HIP_TRY(c, ge);
     if (g.max_blocks_per_cu < 1) return fail(c, PT_E_LIMIT, "guide kernel does not fit a CU (LDS %zu bytes, BVH depth %d)", g.lds_bytes, c->scene.bvh.depth);
@@ -678,7 +680,16 @@ int aov_device(pt_ctx* c, const pt_camera* cam, int W, int H, int n_samples, voi
     A.n_samples = n_samples;
     A.rank = c->rank; A.world = c->world; A.tile = tile;
     HIP_TRY(c, hipEventRecord(c->ev0, stream));
-    HIP_TRY(c, (wt ? pt_launch_aov_wt : pt_launch_aov)(&P, &A, quad ? 0 : 1, grid, g.lds_bytes, stream));
+    if (follow) {
+        PtAovFollowArgs F{};
+        F.a = A;
+        F.max_follow = follow->max_follow;
+        F.roughness_max = follow->roughness_max;
+        F.inv_n = 1.0f / (float)n_samples;
+        HIP_TRY(c, (wt ? pt_launch_aov_follow_wt : pt_launch_aov_follow)(&P, &F, quad ? 0 : 1, grid, g.lds_bytes, stream));
+    } else {
+        HIP_TRY(c, (wt ? pt_launch_aov_wt : pt_launch_aov)(&P, &A, quad ? 0 : 1, grid, g.lds_bytes, stream));
+    }
     // what pt_synchronize and pt_get_stats look at: kernel_ms / launches of this launch (finish_frame is the render's)
     HIP_TRY(c, hipEventRecord(c->ev1, stream));
     LastFrame& L = c->last;
@@ -793,15 +804,33 @@ template <class F> int blocking_call(pt_ctx* c, F run)
 
 extern "C" {
 
+// The two forms of the guide pass behind their entry points: follow == null is pt_render_aov*, else pt_render_aov_follow* with checked parameters
+static int render_aov_device(pt_ctx* c, const pt_camera* cam, int32_t W, int32_t H, int32_t n_samples, void* d_out_aov, void* stream_v, const pt_aov_params* follow)
+{
+    hipStream_t stream = stream_v ? (hipStream_t)stream_v : c->stream;
+    return async_call(c, stream, [&] { return aov_device(c, cam, W, H, n_samples, d_out_aov, stream, follow); });
+}
+
 int pt_render_aov_device(pt_ctx* c, const pt_camera* cam, int32_t W, int32_t H, int32_t n_samples, void* d_out_aov, void* stream_v)
 {
     if (!c || !cam || !d_out_aov) return PT_E_INVALID;
     int rc;
     if ((rc = need_device(c)) || (rc = check_render_args(c, W, H, n_samples, 0))) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t stream = stream_v ? (hipStream_t)stream_v : c->stream;
-    return async_call(c, stream, [&] { return aov_device(c, cam, W, H, n_samples, d_out_aov, stream); });
+    return render_aov_device(c, cam, W, H, n_samples, d_out_aov, stream_v, nullptr);
 }
+
+int pt_render_aov_follow_device(pt_ctx* c, const pt_camera* cam, int32_t W, int32_t H, const pt_aov_params* p, void* d_out_aov, void* stream_v)
+{
+    if (!c || !cam || !d_out_aov) return PT_E_INVALID;
+    pt_aov_params prm;
+    int rc;
+    if ((rc = need_device(c)) || (rc = check_aov_params(c, p, "pt_render_aov_follow_device", &prm)) || (rc = check_render_args(c, W, H, prm.n_samples, 0))) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    return render_aov_device(c, cam, W, H, prm.n_samples, d_out_aov, stream_v, &prm);
+}
+
+static int render_aov(pt_ctx* c, const pt_camera* cam, int32_t W, int32_t H, int32_t n_samples, float* out_aov, const pt_aov_params* follow);
 
 int pt_render_aov(pt_ctx* c, const pt_camera* cam, int32_t W, int32_t H, int32_t n_samples, float* out_aov)
 {
@@ -811,11 +840,28 @@ int pt_render_aov(pt_ctx* c, const pt_camera* cam, int32_t W, int32_t H, int32_t
     int rc;
     if ((rc = need_device(c)) || (rc = check_render_args(c, W, H, n_samples, 0))) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
+    return render_aov(c, cam, W, H, n_samples, out_aov, nullptr);
+}
+
+int pt_render_aov_follow(pt_ctx* c, const pt_camera* cam, int32_t W, int32_t H, const pt_aov_params* p, float* out_aov)
+{
+    const bool root = !c || !c->comm || c->comm_rank == 0;
+    if (!c || !cam || (root && !out_aov)) return PT_E_INVALID;
+    pt_aov_params prm;
+    int rc;
+    if ((rc = need_device(c)) || (rc = check_aov_params(c, p, "pt_render_aov_follow", &prm)) || (rc = check_render_args(c, W, H, prm.n_samples, 0))) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    return render_aov(c, cam, W, H, prm.n_samples, out_aov, &prm);
+}
+
+static int render_aov(pt_ctx* c, const pt_camera* cam, int32_t W, int32_t H, int32_t n_samples, float* out_aov, const pt_aov_params* follow)
+{
+    const bool root = !c->comm || c->comm_rank == 0;
     const size_t n_floats = (size_t)W * H * 8;
     return blocking_call(c, [&]() -> int {
         int rc;
         if ((rc = ensure(c, c->d_aov, n_floats * 4))) return rc;
-        if ((rc = aov_device(c, cam, W, H, n_samples, c->d_aov.p, c->stream))) return rc;
+        if ((rc = aov_device(c, cam, W, H, n_samples, c->d_aov.p, c->stream, follow))) return rc;
         // N ranks: ONE sum-reduce of the W*H*8 floats onto rank 0; one non-zero contributor per pixel, so the sum is exact
         if (c->comm && (rc = reduce_sum(c, c->d_aov.p, n_floats, c->stream))) return rc;
         HIP_TRY(c, hipEventRecord(c->evr, c->stream));

@@ -14,6 +14,8 @@
 // --aov N (N >= 1: after every frame the guide pass with N samples per pixel - pt_render_aov / pt_group_render_aov, mi355pt.h - and three
 // more files next to <name>.png: <name>_albedo.png = make_rgba of the albedo, <name>_normal.png = make_rgba of 0.5 * n + 0.5,
 // <name>_depth.png = grey, depth / the frame's largest depth; works with --gpus / --devices and --watertight, not with --batch).
+// --follow K [--follow-roughness R] (needs --aov N: the guide pass in follow mode - pt_render_aov_follow / pt_group_render_aov_follow with
+// max_follow = K in 0..8 and roughness_max = R in 0..1, default 0.3 - the same three files, and what --denoise consumes).
 // --denoise (needs --aov N, so not with --batch either: after every frame and its guides pt_denoise with the default parameters - mi355pt.h,
 // "denoiser" - and one more file, <name>_denoised.png = the filter's RGBA8 image; with --gpus / --devices the filter runs on the first
 // device's context, which holds the reduced frame).
@@ -96,6 +98,8 @@ struct App {
     std::string out_dir;
     int batch = 0; // --batch K: sweep steps per pt_render_batch (0: one pt_render per step)
     int aov = 0;   // --aov N: samples per pixel of the guide pass after every frame (0: none)
+    int follow = -1;               // --follow K: the guide pass in follow mode, max_follow = K (-1: first hit, pt_render_aov)
+    float follow_roughness = -1.0f; // --follow-roughness R: roughness_max (< 0: the default of pt_aov_default_params)
     bool denoise = false; // --denoise: pt_denoise of every frame with its guides
 };
 
@@ -121,7 +125,15 @@ void write_guides(App& a, const std::string& base, const std::vector<float>& rgb
     const int W = a.settings.buffer_size[0], H = a.settings.buffer_size[1];
     const size_t npx = (size_t)W * H;
     std::vector<float> g(npx * 8);
-    if (a.group) check(a, pt_group_render_aov(a.group, &a.cam, W, H, a.aov, g.data()), "pt_group_render_aov");
+    if (a.follow >= 0) {
+        pt_aov_params prm;
+        pt_aov_default_params(&prm);
+        prm.n_samples = a.aov;
+        prm.max_follow = a.follow;
+        if (a.follow_roughness >= 0.0f) prm.roughness_max = a.follow_roughness;
+        if (a.group) check(a, pt_group_render_aov_follow(a.group, &a.cam, W, H, &prm, g.data()), "pt_group_render_aov_follow");
+        else check(a, pt_render_aov_follow(a.ctx, &a.cam, W, H, &prm, g.data()), "pt_render_aov_follow");
+    } else if (a.group) check(a, pt_group_render_aov(a.group, &a.cam, W, H, a.aov, g.data()), "pt_group_render_aov");
     else check(a, pt_render_aov(a.ctx, &a.cam, W, H, a.aov, g.data()), "pt_render_aov");
     float far = 0.0f;
     for (size_t i = 0; i < npx; ++i) far = g[8 * i + 7] > far ? g[8 * i + 7] : far;
@@ -258,7 +270,7 @@ int main(int argc, char** argv)
         std::string settings_path, dump;
         a.out_dir = cwd;
         int device = 0, gpus = 0; // gpus 0: flag not given, single context as in the reference
-        bool have_device = false, have_devices = false, have_batch = false, have_aov = false, watertight = false;
+        bool have_device = false, have_devices = false, have_batch = false, have_aov = false, have_follow = false, have_follow_roughness = false, watertight = false;
         std::vector<int32_t> devs; // --devices
         for (int i = 1; i < argc; ++i) {
             std::string k = argv[i];
@@ -272,6 +284,8 @@ int main(int argc, char** argv)
             else if (k == "--dump-scene") dump = next();
             else if (k == "--batch") { a.batch = std::atoi(next().c_str()); have_batch = true; }
             else if (k == "--aov") { a.aov = std::atoi(next().c_str()); have_aov = true; }
+            else if (k == "--follow") { a.follow = std::atoi(next().c_str()); have_follow = true; }
+            else if (k == "--follow-roughness") { a.follow_roughness = (float)std::atof(next().c_str()); have_follow_roughness = true; }
             else if (k == "--watertight") watertight = true;
             else if (k == "--denoise") a.denoise = true;
             else if (k == "--convert-png" || k == "--convert-hdr") { // codec self-test hooks: decode with our reader, re-encode with our writer
@@ -293,6 +307,10 @@ int main(int argc, char** argv)
         }
         if (a.denoise && have_batch) throw std::runtime_error("--denoise cannot be combined with --batch (it needs the guides of --aov, which has no batch form)");
         if (a.denoise && !have_aov) throw std::runtime_error("--denoise needs --aov N (the filter is driven by the guide buffers)");
+        if (have_follow && !have_aov) throw std::runtime_error("--follow needs --aov N (it is a mode of the guide pass)");
+        if (have_follow && (a.follow < 0 || a.follow > 8)) throw std::runtime_error("--follow needs a number of surfaces 0..8");
+        if (have_follow_roughness && !have_follow) throw std::runtime_error("--follow-roughness needs --follow K");
+        if (have_follow_roughness && !(a.follow_roughness >= 0.0f && a.follow_roughness <= 1.0f)) throw std::runtime_error("--follow-roughness needs a value 0..1");
         if (have_aov && a.aov < 1) throw std::runtime_error("--aov needs a positive number of samples per pixel");
         if (have_aov && have_batch) throw std::runtime_error("--aov cannot be combined with --batch (the guide pass has no batch form)");
         if (have_batch && watertight) throw std::runtime_error("--batch cannot be combined with --watertight (pt_render_batch has no watertight instances)");

@@ -69,6 +69,11 @@ class DenoiseParams(C.Structure):
                 ("sigma_albedo", C.c_float)]
 
 
+class AovParams(C.Structure):
+    """pt_aov_params: n_samples (>= 1), max_follow (0..8 specular surfaces a guide ray may pass), roughness_max (0..1), reserved (0)."""
+    _fields_ = [("n_samples", C.c_int32), ("max_follow", C.c_int32), ("roughness_max", C.c_float), ("reserved", C.c_int32)]
+
+
 class Stats(C.Structure):
     _fields_ = [("kernel_ms", C.c_double), ("launches", C.c_int32), ("vgprs", C.c_int32), ("sgprs", C.c_int32), ("lds_bytes", C.c_int32),
                 ("block", C.c_int32), ("grid", C.c_int32), ("stack_entries", C.c_int32),
@@ -93,7 +98,8 @@ EXPORTS = ["pt_create", "pt_destroy", "pt_last_error", "pt_abi_version", "pt_upl
            "pt_group_set_materials", "pt_group_set_option", "pt_group_render", "pt_debug_quad_info", "pt_debug_oct_info", "pt_debug_clone_scene",
            "pt_render_batch", "pt_render_batch_device", "pt_debug_plan_batch", "pt_update_vertices", "pt_group_update_vertices", "pt_debug_update_info",
            "pt_render_aov", "pt_render_aov_device", "pt_group_render_aov", "pt_debug_aov_host",
-           "pt_denoise_default_params", "pt_denoise", "pt_denoise_device", "pt_debug_denoise_host"]
+           "pt_denoise_default_params", "pt_denoise", "pt_denoise_device", "pt_debug_denoise_host",
+           "pt_aov_default_params", "pt_render_aov_follow", "pt_render_aov_follow_device", "pt_group_render_aov_follow", "pt_debug_aov_follow_host"]
 PT_DENOISE_DEMODULATE = 1
 PT_TREE_DEVICE = 16  # pt_debug_export_tree: ORed into `which`, the array as HBM holds it
 PT_COMM_ID_BYTES = 128
@@ -184,6 +190,13 @@ def lib():
     L.pt_group_render_aov.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_int32, C.c_int32, C.c_int32, fp]
     L.pt_debug_aov_host.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_uint32), C.c_int64, fp]
     L.pt_debug_aov_host.restype = C.c_int64
+    L.pt_aov_default_params.restype = None
+    L.pt_aov_default_params.argtypes = [C.POINTER(AovParams)]
+    L.pt_render_aov_follow.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_int32, C.c_int32, C.POINTER(AovParams), fp]
+    L.pt_render_aov_follow_device.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_int32, C.c_int32, C.POINTER(AovParams), C.c_void_p, C.c_void_p]
+    L.pt_group_render_aov_follow.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_int32, C.c_int32, C.POINTER(AovParams), fp]
+    L.pt_debug_aov_follow_host.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_int32, C.c_int32, C.POINTER(AovParams), C.POINTER(C.c_uint32), C.c_int64, fp]
+    L.pt_debug_aov_follow_host.restype = C.c_int64
     L.pt_denoise_default_params.restype = None
     L.pt_denoise_default_params.argtypes = [C.POINTER(DenoiseParams)]
     L.pt_denoise.argtypes = [C.c_void_p, fp, fp, C.c_int32, C.c_int32, C.POINTER(DenoiseParams), fp, C.POINTER(C.c_uint32)]
@@ -273,6 +286,17 @@ def denoise_default_params(**changes):
     lib().pt_denoise_default_params(C.byref(p))
     for k, v in changes.items():
         if k not in dict(DenoiseParams._fields_):
+            raise KeyError(k)
+        setattr(p, k, v)
+    return p
+
+
+def aov_default_params(**changes):
+    """pt_aov_default_params (1 sample, max_follow 4, roughness_max 0.3), with the given fields changed."""
+    p = AovParams()
+    lib().pt_aov_default_params(C.byref(p))
+    for k, v in changes.items():
+        if k not in dict(AovParams._fields_):
             raise KeyError(k)
         setattr(p, k, v)
     return p
@@ -509,6 +533,30 @@ class Context:
             self._check(int(n), "pt_debug_aov_host")
         return out.reshape(H, W, 8)[::-1].copy() if whole else out
 
+    def render_aov_follow(self, cam, W, H, params=None, receive=True):
+        """pt_render_aov_follow: the guide buffers (H, W, 8) with the guide ray following mirrors and glass (include/mi355pt.h "guide pass,
+        follow mode"); params: AovParams (aov_default_params), None = the defaults.  receive = False: a non-root rank of a communicator."""
+        out = np.empty((H, W, 8), np.float32) if receive else None
+        self._check(lib().pt_render_aov_follow(self._h, C.byref(cam), W, H, C.byref(params) if params is not None else None,
+                                               out.ctypes.data_as(C.POINTER(C.c_float)) if receive else None), "pt_render_aov_follow")
+        return out
+
+    def render_aov_follow_device(self, cam, W, H, d_out_aov, params=None, stream=None):
+        """pt_render_aov_follow_device: asynchronous, W*H*8 floats left in HBM at d_out_aov; conventions of render_aov_device."""
+        self._check(lib().pt_render_aov_follow_device(self._h, C.byref(cam), W, H, C.byref(params) if params is not None else None, C.c_void_p(d_out_aov),
+                                                      C.c_void_p(stream) if stream else None), "pt_render_aov_follow_device")
+
+    def aov_follow_host(self, cam, W, H, params=None, pixel_ids=None):
+        """pt_debug_aov_follow_host, the CPU twin of render_aov_follow (works on a host-only context); pixel_ids and result as aov_host."""
+        whole = pixel_ids is None
+        ids = np.arange(W * H, dtype=np.uint32) if whole else np.ascontiguousarray(pixel_ids, np.uint32).reshape(-1)
+        out = np.zeros((ids.size, 8), np.float32)
+        n = lib().pt_debug_aov_follow_host(self._h, C.byref(cam), W, H, C.byref(params) if params is not None else None, ids.ctypes.data_as(C.POINTER(C.c_uint32)), ids.size,
+                                           out.ctypes.data_as(C.POINTER(C.c_float)))
+        if n < 0:
+            self._check(int(n), "pt_debug_aov_follow_host")
+        return out.reshape(H, W, 8)[::-1].copy() if whole else out
+
     def _denoise(self, fn, what, rgb, aov, params, want_rgba8, in_place):
         aov = np.ascontiguousarray(aov, np.float32)
         H, W = aov.shape[0], aov.shape[1]
@@ -738,4 +786,11 @@ class Group:
         """pt_group_render_aov: the guide buffers (H, W, 8) of the frame, every device's own tiles reduced onto devices[0]."""
         out = np.empty((H, W, 8), np.float32)
         self._check(lib().pt_group_render_aov(self._g, C.byref(cam), W, H, n_samples, out.ctypes.data_as(C.POINTER(C.c_float))), "pt_group_render_aov")
+        return out
+
+    def render_aov_follow(self, cam, W, H, params=None):
+        """pt_group_render_aov_follow: the follow-mode guide buffers (H, W, 8), reduced onto devices[0]."""
+        out = np.empty((H, W, 8), np.float32)
+        self._check(lib().pt_group_render_aov_follow(self._g, C.byref(cam), W, H, C.byref(params) if params is not None else None, out.ctypes.data_as(C.POINTER(C.c_float))),
+                    "pt_group_render_aov_follow")
         return out

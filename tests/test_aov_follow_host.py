@@ -1,0 +1,335 @@
+"""The follow mode of the guide pass (pt_render_aov_follow: the guide ray passes mirrors and glass) without a GPU.
+
+* The five exports exist, the ABI version is still 5, the default parameters are the header's; argument errors on a host-only context.
+* The scenes hold what they are for, asserted from the oracle's hits: mirror_wall shows the wall directly, in the mirror and through the
+  pane, a reflected miss and a primary miss; tir has samples that reflect internally and samples that leave.  On every ray of every
+  case, follow rays included, the oracle's walk and its brute force agree (the closest-hit domain of DESIGN.md 2.1) - no ray is left out.
+* pt_debug_aov_follow_host == tests/aov_follow_ref.py, all 8 channels of every pixel, over the cases of aov_follow_common.py (four
+  scenes x two sizes x n = 1, 3 x max_follow 0, 1, 2, 4 x roughness_max 0.3, 0.2) with watertight 0 and 1.
+* max_follow = 0 equals pt_debug_aov_host; at n = 1 the pixels whose first hit classifies NONE equal pt_debug_aov_host and every other
+  pixel differs somewhere.
+* The header's wording by value on mirror_wall: alpha 1 in the mirror; a mirror pixel's albedo is tint x checker texel, so both texel
+  colours occur where pt_debug_aov_host gives one value; depth is the sum of the segment lengths; a reflected miss has normal 0, alpha 1,
+  depth > 0.  pt_set_materials turning the mirror diffuse changes exactly the pixels whose first hit was the mirror.
+* A moved scene (pt_update_vertices on a host-only context) is followed like a fresh upload.
+* `make asm-aov-follow`: exactly the five follow kernels, no scratch, at most 128 VGPRs; `make asm-aov` still reports its five.
+* What the feature buys: mirror_wall 64 x 48, the oracle's 8 spp frame filtered by pt_debug_denoise_host (defaults +
+  PT_DENOISE_DEMODULATE) with first-hit guides and with follow guides (twins, n = 4), relRMSE against 1024 spp over the pixels whose
+  first hit is the mirror or the pane: follow < first-hit.  (When the test was written: 773 pixels, 0.190 noisy, 0.552 with first-hit
+  guides, 0.160 with follow guides; the test prints its own figures.)"""
+import ctypes as C
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+import aov_follow_common as FC
+import aov_follow_ref as FR
+import refit_common as RC
+from owl_path_tracer_amd.pyhost import binding as B, scene_io
+
+ROOT = FC.ROOT
+F32 = np.float32
+PT_E_INVALID, PT_E_NO_DEVICE, PT_E_NO_SCENE = -1, -2, -4
+NAMES = ("pt_aov_default_params", "pt_render_aov_follow", "pt_render_aov_follow_device", "pt_group_render_aov_follow", "pt_debug_aov_follow_host")
+
+
+def test_exports_abi_and_defaults():
+    L = B.lib()
+    header = open(B.HEADER_PATH).read()
+    for name in NAMES:
+        assert hasattr(L, name), name
+        assert name in B.EXPORTS
+        assert re.search(r"\b%s\(" % name, header), name
+    assert L.pt_abi_version() == 5
+    p = B.aov_default_params()
+    assert (p.n_samples, p.max_follow, p.reserved) == (1, 4, 0) and F32(p.roughness_max) == F32(0.3)
+    assert C.sizeof(B.AovParams) == 16
+    assert "pt_render_aov_follow_device" in re.search(r"The asynchronous calls \(([^)]*)\)", header).group(1)
+    with pytest.raises(KeyError):
+        B.aov_default_params(no_such_field=1)
+
+
+def test_argument_errors_on_a_host_only_context():
+    L = B.lib()
+    sc = FC.scene("mirror_wall")
+    cam = FC.camera(sc, 8, 8, B.to_camera_data)
+    ids = np.arange(64, dtype=np.uint32)
+    out = np.full((64, 8), 7.0, F32)
+    idp, outp = ids.ctypes.data_as(C.POINTER(C.c_uint32)), out.ctypes.data_as(C.POINTER(C.c_float))
+    ok = B.aov_default_params()
+    ctx = B.Context(-1)
+    try:
+        assert L.pt_debug_aov_follow_host(ctx._h, C.byref(cam), 8, 8, C.byref(ok), idp, 64, outp) == PT_E_NO_SCENE
+        assert L.pt_render_aov_follow(ctx._h, C.byref(cam), 8, 8, C.byref(ok), outp) == PT_E_NO_DEVICE  # no CPU fallback of the render entry point
+        FC.upload(ctx, sc, B)
+        assert L.pt_render_aov_follow(ctx._h, C.byref(cam), 8, 8, None, outp) == PT_E_NO_DEVICE
+        assert L.pt_render_aov_follow_device(ctx._h, C.byref(cam), 8, 8, C.byref(ok), C.c_void_p(16), None) == PT_E_NO_DEVICE
+        assert L.pt_group_render_aov_follow(None, C.byref(cam), 8, 8, C.byref(ok), outp) == PT_E_INVALID
+        assert L.pt_render_aov_follow(None, C.byref(cam), 8, 8, C.byref(ok), outp) == PT_E_INVALID
+        assert L.pt_render_aov_follow(ctx._h, None, 8, 8, C.byref(ok), outp) == PT_E_INVALID
+        assert L.pt_render_aov_follow(ctx._h, C.byref(cam), 8, 8, C.byref(ok), None) == PT_E_INVALID
+        assert L.pt_render_aov_follow_device(ctx._h, C.byref(cam), 8, 8, C.byref(ok), None, None) == PT_E_INVALID
+        for args in [(None, C.byref(cam), 8, 8, C.byref(ok), idp, 64, outp), (ctx._h, None, 8, 8, C.byref(ok), idp, 64, outp), (ctx._h, C.byref(cam), 8, 8, C.byref(ok), idp, 64, None),
+                     (ctx._h, C.byref(cam), 8, 8, C.byref(ok), None, 64, outp), (ctx._h, C.byref(cam), 8, 8, C.byref(ok), idp, -1, outp),
+                     (ctx._h, C.byref(cam), 0, 8, C.byref(ok), idp, 64, outp), (ctx._h, C.byref(cam), 8, -1, C.byref(ok), idp, 64, outp),
+                     (ctx._h, C.byref(cam), 65536, 8, C.byref(ok), idp, 64, outp), (ctx._h, C.byref(cam), 8, 7, C.byref(ok), idp, 64, outp)]:  # 8 x 7: ids 56..63 lie outside
+            assert L.pt_debug_aov_follow_host(*args) == PT_E_INVALID, args[2:4]
+        for bad in (dict(n_samples=0), dict(n_samples=-2), dict(max_follow=-1), dict(max_follow=9), dict(roughness_max=-0.01), dict(roughness_max=1.01),
+                    dict(roughness_max=float("nan")), dict(roughness_max=float("inf")), dict(reserved=1), dict(reserved=-1)):
+            p = B.aov_default_params(**bad)
+            assert L.pt_debug_aov_follow_host(ctx._h, C.byref(cam), 8, 8, C.byref(p), idp, 64, outp) == PT_E_INVALID, bad
+        assert (out == 7.0).all(), "a refused call wrote to the output"
+        assert L.pt_debug_aov_follow_host(ctx._h, C.byref(cam), 8, 8, C.byref(ok), idp, 0, outp) == 0
+        for good in (dict(max_follow=0), dict(max_follow=8), dict(roughness_max=0.0), dict(roughness_max=1.0)):
+            assert L.pt_debug_aov_follow_host(ctx._h, C.byref(cam), 8, 8, C.byref(B.aov_default_params(**good)), idp, 64, outp) == 64, good
+        assert L.pt_debug_aov_follow_host(ctx._h, C.byref(cam), 8, 8, None, idp, 64, outp) == 64  # NULL = the defaults
+        assert np.isfinite(out).all() and (out != 7.0).any()
+        FC.assert_same(out, ctx.aov_follow_host(cam, 8, 8, ok, pixel_ids=ids), "NULL parameters are the defaults")
+    finally:
+        ctx.close()
+
+
+def _same_bytes(a, b):
+    return (np.ascontiguousarray(a).view(np.uint8) == np.ascontiguousarray(b).view(np.uint8)).all()
+
+
+@pytest.mark.parametrize("wt", [0, 1])
+@pytest.mark.parametrize("name,W,H,n", FC.FRAMES)
+def test_host_twin_equals_the_restatement_inside_the_domain(orc, name, W, H, n, wt):
+    sc = FC.scene(name)
+    S = orc.Scene(sc["flat"], watertight=bool(wt))
+    cam = FC.camera(sc, W, H, B.to_camera_data)
+    ctx = B.Context(-1)
+    try:
+        FC.upload(ctx, sc, B)
+        ctx.set_option("watertight", wt)
+        first = ctx.aov_host(cam, W, H, n)
+        for k, r in FC.MODES:
+            what = "%s %dx%d n=%d max_follow=%d roughness_max=%g wt=%d" % (name, W, H, n, k, r, wt)
+            want, log = FC.reference(orc, name, W, H, n, k, r, wt, want_log=True)
+            assert np.isfinite(want).all()
+            # the domain: the oracle's walk and its brute force agree on every ray of the case, follow rays included
+            for step, e in enumerate(log["log"]):
+                walk = S.intersect_n(e["rays"], use_bvh=True)
+                brute = S.intersect_n(e["rays"], use_bvh=False)
+                for a, b in zip(walk, brute):
+                    assert _same_bytes(a, b), (what, step)
+                assert _same_bytes(brute[0], e["hit"]) and _same_bytes(brute[1], e["t"]) and _same_bytes(brute[4], e["prim"])
+            assert len(log["log"]) <= k + 1
+            got = ctx.aov_follow_host(cam, W, H, FC.params(B, n, k, r))
+            FC.assert_same(got, want, what + ": host twin vs aov_follow_ref")
+            if k == 0:
+                FC.assert_same(got, first, what + ": max_follow = 0 vs pt_debug_aov_host")
+            else:
+                assert (FC.bits(got) != FC.bits(first)).any(), what + ": the case must follow something"
+        ids = np.array([W * H - 1, 0, W + 1, 0], np.uint32)  # list order, any ids, repeats
+        k, r = FC.MODES[-2]
+        part = ctx.aov_follow_host(cam, W, H, FC.params(B, n, k, r), pixel_ids=ids)
+        FC.assert_same(part, FC.reference(orc, name, W, H, n, k, r, wt)[::-1].reshape(-1, 8)[ids], "listed pixels")
+    finally:
+        ctx.close()
+
+
+def test_the_ico_metal_is_followed_at_0_3_and_not_at_0_2(orc):
+    name, W, H = "ico_colour", 24, 16
+    _, a = FC.reference(orc, name, W, H, 1, 4, 0.3, 0, want_log=True)
+    _, b = FC.reference(orc, name, W, H, 1, 4, 0.2, 0, want_log=True)
+    assert (a["log"][0]["kind"] == FR.MIRROR).sum() > 10 and (a["log"][0]["kind"] == FR.GLASS).sum() > 10
+    assert (b["log"][0]["kind"] == FR.MIRROR).sum() == 0 and (b["log"][0]["kind"] == FR.GLASS).sum() == (a["log"][0]["kind"] == FR.GLASS).sum()
+
+
+@pytest.mark.parametrize("name", ["mirror_wall", "tir", "ico_map"])
+def test_unfollowed_pixels_equal_the_first_hit_pass(orc, name):
+    """At n = 1 a pixel is its one sample: first hit NONE (or a miss) -> bit for bit pt_debug_aov_host; followed -> differs somewhere."""
+    W, H, k, r = 37, 23, 4, 0.3
+    sc = FC.scene(name)
+    _, log = FC.reference(orc, name, W, H, 1, k, r, 0, want_log=True)
+    followed = log["log"][0]["went_on"].reshape(H, W)[::-1]
+    assert followed.any() and (name == "tir" or not followed.all())
+    ctx = B.Context(-1)
+    try:
+        FC.upload(ctx, sc, B)
+        cam = FC.camera(sc, W, H, B.to_camera_data)
+        first, fol = ctx.aov_host(cam, W, H, 1), ctx.aov_follow_host(cam, W, H, FC.params(B, 1, k, r))
+    finally:
+        ctx.close()
+    FC.assert_same(fol[~followed], first[~followed], "pixels whose first hit is not followed")
+    assert (FC.bits(fol[followed]) != FC.bits(first[followed])).any(-1).all(), "every followed pixel differs somewhere"
+
+
+def _census(sc, log):
+    """Per sample of a logged frame: material of the first hit (-2 on a miss), and for followed samples the material where they ended
+    (-2: they left the scene)."""
+    mi = np.asarray(sc["flat"]["material_index"])
+    n = log["log"][0]["idx"].size
+    first = np.where(log["log"][0]["hit"], mi[np.maximum(log["log"][0]["prim"], 0)], -2)
+    last = first.copy()
+    steps = np.zeros(n, int)
+    for s, e in enumerate(log["log"][1:], 1):
+        last[e["idx"]] = np.where(e["hit"], mi[np.maximum(e["prim"], 0)], -2)
+        steps[e["idx"]] = s
+    return first, last, steps
+
+
+def test_mirror_wall_holds_what_it_is_for(orc):
+    sc = FC.scene("mirror_wall")
+    for W, H in ((24, 16), (37, 23)):
+        for wt in (0, 1):
+            _, log = FC.reference(orc, "mirror_wall", W, H, 1, 4, 0.3, wt, want_log=True)
+            first, last, steps = _census(sc, log)
+            assert (first == FC.M_WALL).sum() >= 20, "the wall seen directly"
+            assert ((first == FC.M_MIRROR) & (last == FC.M_WALL)).sum() >= 10, "the wall seen in the mirror"
+            assert ((first == FC.M_GLASS) & (last == FC.M_WALL) & (steps == 2)).sum() >= 10, "the wall seen through both faces of the pane"
+            assert ((first == FC.M_MIRROR) & (last == -2)).sum() >= 3, "a reflected miss"
+            assert (first == -2).sum() >= 20, "a primary miss"
+
+
+def test_tir_reflects_and_leaves(orc):
+    for W, H in ((24, 16), (37, 23)):
+        for wt in (0, 1):
+            _, log = FC.reference(orc, "tir", W, H, 1, 4, 0.3, wt, want_log=True)
+            e0 = log["log"][0]
+            assert e0["hit"].all() and (e0["kind"] == FR.GLASS).all(), "the camera is inside the glass"
+            assert e0["tir"].sum() >= 10, "samples that take the reflection branch"
+            assert (e0["went_on"] & ~e0["tir"]).sum() >= 10, "samples that leave"
+
+
+def test_values_say_what_the_header_says(orc):
+    name, W, H, k, r = "mirror_wall", 37, 23, 4, 0.3
+    sc = FC.scene(name)
+    want, log = FC.reference(orc, name, W, H, 1, k, r, 0, want_log=True)
+    first, last, steps = _census(sc, log)
+    fb = lambda m: m.reshape(H, W)[::-1]
+    ctx = B.Context(-1)
+    try:
+        FC.upload(ctx, sc, B)
+        cam = FC.camera(sc, W, H, B.to_camera_data)
+        fol, hit1 = ctx.aov_follow_host(cam, W, H, FC.params(B, 1, k, r)), ctx.aov_host(cam, W, H, 1)
+        mats = np.stack(sc["mats"]).astype(F32).copy()
+        mats[FC.M_MIRROR, 4] = 0.0  # metallic: the mirror becomes diffuse
+        ctx.set_materials(mats)
+        diffuse = ctx.aov_follow_host(cam, W, H, FC.params(B, 1, k, r))
+    finally:
+        ctx.close()
+    in_mirror = fb((first == FC.M_MIRROR) & (last == FC.M_WALL) & (steps == 1))
+    assert in_mirror.sum() >= 20
+    assert (fol[fb(first == FC.M_MIRROR)][:, 3] == 1).all(), "alpha is 1 in the mirror"
+    # albedo = tint x checker texel: both texel colours occur, each exactly mirror colour x texel (float32 product, 1 x colour exact)
+    tint = F32(FC.MIRROR_COLOUR)
+    tex = scene_io.checker_texture()
+    texels = []
+    for px in (int(tex[0, 0]), int(tex[0, 8])):
+        texels.append(np.array([orc.dm("div", F32((px >> s) & 255), F32(255.0))[0] for s in (0, 8, 16)], F32))
+    assert (texels[0] != texels[1]).any()
+    alb = fol[in_mirror][:, :3]
+    is0, is1 = (alb == tint * texels[0]).all(1), (alb == tint * texels[1]).all(1)
+    assert (is0 | is1).all() and is0.any() and is1.any(), "the mirror shows the checker under its tint"
+    assert (hit1[in_mirror][:, :3] == tint).all(), "the first-hit pass gives the mirror's own colour there"
+    # depth is the path length: the float32 sum of the logged segments, in step order
+    dist = np.zeros(W * H, F32)
+    for e in log["log"]:
+        dist[e["idx"][e["hit"]]] = dist[e["idx"][e["hit"]]] + e["t"][e["hit"]]
+    FC.assert_same(fol[..., 7], fb(dist), "depth")
+    assert (fol[in_mirror][:, 7] > hit1[in_mirror][:, 7]).all()
+    gone = fb((first == FC.M_MIRROR) & (last == -2))
+    assert gone.any() and (fol[gone][:, 4:7] == 0).all() and (fol[gone][:, 3] == 1).all() and (fol[gone][:, 7] > 0).all(), "a reflected miss"
+    changed = (FC.bits(fol) != FC.bits(diffuse)).any(-1)
+    assert (changed == fb(first == FC.M_MIRROR)).all(), "turning the mirror diffuse changes exactly the pixels that were followed at it"
+
+
+def test_host_only_context_after_update_vertices():
+    scene = RC.make_scene("cornell")
+    W, H = 24, 16
+    cam = B.to_camera_data([3.0, 1.0, 0.0], [0.0, 1.0, 0.0], [0, 1, 0], 50.0, W, H)
+    env = B.make_env(color=(0.5, 0.25, 1.0), intensity=1.0)
+    mats = [m.copy() for _, m, _ in RC.cornell_materials()]
+    for m in mats[1:3]:  # two of the materials become mirrors: the moved scene is followed
+        m[4], m[7] = 1.0, 0.0
+    prm = FC.params(B, 2, 4, 0.3)
+    dyn = B.Context(-1)
+    try:
+        dyn.set_option("dynamic", 1)
+        RC.upload(dyn, scene, materials=mats, env=env)
+        before = dyn.aov_follow_host(cam, W, H, prm)
+        assert (FC.bits(before) != FC.bits(dyn.aov_host(cam, W, H, 2))).any(), "the frame must hold followed pixels"
+        for k, with_normals in ((1, False), (2, True)):
+            meshes = RC.moved(scene, k, with_normals=with_normals)
+            dyn.update_vertices(meshes)
+            fresh = B.Context(-1)
+            try:
+                RC.upload(fresh, scene, meshes, materials=mats, env=env)
+                want = fresh.aov_follow_host(cam, W, H, prm)
+            finally:
+                fresh.close()
+            got = dyn.aov_follow_host(cam, W, H, prm)
+            FC.assert_same(got, want, "cornell, update %d" % k)
+            assert (FC.bits(got) != FC.bits(before)).any(), "the movement must show in the buffers"
+    finally:
+        dyn.close()
+
+
+def _asm_report(target):
+    if not (shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc")):
+        pytest.skip("hipcc not available")
+    csrc = os.path.join(ROOT, "owl-path-tracer_amd", "csrc")
+    env = {k: v for k, v in os.environ.items() if k not in ("CXXFLAGS", "MAKEFLAGS")}
+    r = subprocess.run(["make", "-s", "-C", csrc, target], env=env, capture_output=True, text=True, timeout=1500)
+    assert r.returncode == 0, (r.stdout + r.stderr)[-2000:]
+    return re.findall(r"Function Name: (\S+).*?VGPRs: (\d+).*?ScratchSize \[bytes/lane\]: (\d+)", r.stdout + r.stderr, flags=re.S)
+
+
+def test_follow_kernels_need_no_scratch_and_fit_128_vgprs():
+    """From the Makefile's own target (the flags that ship): the five follow kernels and no other, ScratchSize 0, at most 128 VGPRs - the
+    four waves per SIMD the kernel is launched with."""
+    blocks = _asm_report("asm-aov-follow")
+    names = [b[0] for b in blocks]
+    assert all("pt_aov_follow_" in nm for nm in names), names  # told from pt_aov_kernel / pt_aov_wt_kernel by name
+    assert len(blocks) == 5 and len(set(names)) == 5, names  # binary walk + two slab forms of the quad walk; the watertight build: the two quad forms
+    assert sum("pt_aov_follow_wt_kernel" in nm for nm in names) == 2 and sum("pt_aov_follow_kernel" in nm for nm in names) == 3, names
+    assert all(int(sz) == 0 for _, _, sz in blocks), blocks
+    assert all(int(v) <= 128 for _, v, _ in blocks), blocks
+
+
+def test_first_hit_translation_units_keep_their_five_kernels():
+    blocks = _asm_report("asm-aov")
+    names = [b[0] for b in blocks]
+    assert len(blocks) == 5 and len(set(names)) == 5 and not any("follow" in nm for nm in names), names
+    assert sum("pt_aov_wt_kernel" in nm for nm in names) == 2 and sum("pt_aov_kernel" in nm for nm in names) == 3, names
+
+
+def rel_rmse(x, ref):
+    x, ref = x.astype(np.float64), ref.astype(np.float64)
+    return float(np.sqrt(np.mean((x - ref) ** 2 / (ref ** 2 + 1e-2))))
+
+
+def test_what_the_feature_buys(orc):
+    """The yardstick is the parent's own behaviour: the same filter on the same frame with first-hit guides."""
+    name, W, H = "mirror_wall", 64, 48
+    sc = FC.scene(name)
+    S = orc.Scene(sc["flat"])
+    ocam = FC.camera(sc, W, H, orc.to_camera_data)
+    env = orc.make_env(**sc["env"])
+    noisy, _, _ = S.render(ocam, env, W, H, 8, 8)
+    ref, _, _ = S.render(ocam, env, W, H, 1024, 8)
+    # the pixels whose first hit is the mirror or the pane: sample 0's hit, from the oracle
+    _, log = FC.reference(orc, name, W, H, 1, 0, 0.3, 0, want_log=True)
+    first, _, _ = _census(sc, log)
+    mask = ((first == FC.M_MIRROR) | (first == FC.M_GLASS)).reshape(H, W)[::-1]
+    assert mask.sum() > 300
+    ctx = B.Context(-1)
+    try:
+        FC.upload(ctx, sc, B)
+        cam = FC.camera(sc, W, H, B.to_camera_data)
+        prm = B.denoise_default_params(flags=B.PT_DENOISE_DEMODULATE)
+        with_first, _ = ctx.denoise_host(noisy, ctx.aov_host(cam, W, H, 4), prm)
+        with_follow, _ = ctx.denoise_host(noisy, ctx.aov_follow_host(cam, W, H, B.aov_default_params(n_samples=4)), prm)
+    finally:
+        ctx.close()
+    e_noisy, e_first, e_follow = rel_rmse(noisy[mask], ref[mask]), rel_rmse(with_first[mask], ref[mask]), rel_rmse(with_follow[mask], ref[mask])
+    print("mirror_wall %dx%d, %d pixels behind the mirror or the pane: relRMSE noisy %.3f, filtered with first-hit guides %.3f, with follow guides %.3f"
+          % (W, H, int(mask.sum()), e_noisy, e_first, e_follow))
+    assert e_follow < e_first, (e_first, e_follow)
