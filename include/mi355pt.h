@@ -166,14 +166,15 @@ int pt_render(pt_ctx* ctx, const pt_camera* cam, int32_t width, int32_t height, 
  * timing events.  The context's own stream is non-blocking: HIP orders nothing between it and a caller's stream.  THE LIBRARY does:
  * every call that touches what a frame in flight uses is ordered after the context's LAST ASYNCHRONOUS CALL, whichever stream that
  * call was given.  So any call of this header may follow a pt_*_device call at once, with no pt_synchronize between them.
- *   - The asynchronous calls (pt_render_device, pt_render_batch_device, pt_render_aov_device, pt_render_aov_follow_device, pt_denoise_device, pt_reduce_framebuffer) wait ON THE
+ *   - The asynchronous calls (pt_render_device, pt_render_batch_device, pt_render_aov_device, pt_render_aov_follow_device, pt_render_aov_batch_device, pt_denoise_device,
+ *     pt_denoise_batch_device, pt_reduce_framebuffer) wait ON THE
  *     DEVICE: the stream they are given waits for an event recorded at the end of the previous asynchronous call - only if that call
  *     used another stream; on the same stream the stream's own order suffices and nothing is added.  The host returns at once, with
  *     two exceptions that existed before: a frame of another size, shard or batch length rewrites the pixel queue and a frame that
  *     needs larger work buffers reallocates them (pt_denoise_device: its filter records, when the frame is larger than any it filtered
- *     before) - both first wait on the host for the frame in flight; and pt_render_batch_device
- *     returns when its per-frame tables have reached HBM, i.e. after whatever precedes it on `stream`.
- *   - The blocking renders (pt_render, pt_render_batch, pt_render_aov, pt_render_aov_follow) and pt_denoise run on the context's stream behind the same device-side wait
+ *     before) - both first wait on the host for the frame in flight; and pt_render_batch_device and pt_render_aov_batch_device
+ *     return when their per-frame tables have reached HBM, i.e. after whatever precedes them on `stream`.
+ *   - The blocking renders (pt_render, pt_render_batch, pt_render_aov, pt_render_aov_follow, pt_render_aov_batch), pt_denoise and pt_denoise_batch run on the context's stream behind the same device-side wait
  *     and return with the context idle.  After a blocking call, or on the context's own stream, they add no wait at all.
  *   - The calls that change or read what a frame uses WAIT ON THE HOST for the last asynchronous call's stream (if it is not the
  *     context's) and then for the context's: pt_set_materials, pt_set_environment, pt_update_vertices, pt_upload_scene,
@@ -188,7 +189,7 @@ int pt_render(pt_ctx* ctx, const pt_camera* cam, int32_t width, int32_t height, 
 int pt_render_device(pt_ctx* ctx, const pt_camera* cam, int32_t width, int32_t height, int32_t max_samples, int32_t max_path_depth,
                      void* d_out_rgb, void* d_out_rgba8, void* stream);
 /* Waits on the host for the context's last asynchronous call - pt_render_device, pt_render_batch_device, pt_render_aov_device,
- * pt_render_aov_follow_device, pt_denoise_device or pt_reduce_framebuffer, on the stream it was given - and for the context's own stream.  Every earlier asynchronous call of the context
+ * pt_render_aov_follow_device, pt_render_aov_batch_device, pt_denoise_device, pt_denoise_batch_device or pt_reduce_framebuffer, on the stream it was given - and for the context's own stream.  Every earlier asynchronous call of the context
  * is complete then as well, whatever stream it used: each was ordered before the next (see pt_render_device).  Returns PT_E_HIP if a
  * wave's watchdog fired during the last frame (the image is then incomplete); pt_get_stats reports the same.  PT_OK at once on an idle
  * or host-only context.  A caller's stream may be destroyed once this has returned. */
@@ -246,7 +247,7 @@ int64_t pt_debug_plan_batch(int32_t width, int32_t height, int32_t n_frames, int
  * LAYOUT: 8 consecutive floats per pixel, {albedo r, g, b, alpha, normal x, y, z, depth}, at pixel offset x + W*(H-1-y) like out_rgb;
  * pixels the context does not own (pt_set_pixel_shard) are all 0.
  * LIMITS: first hit only - a window shows the window, a mirror the mirror; pt_render_aov_follow below lets the guide ray pass such
- * surfaces.  No batch form (one frame per call).
+ * surfaces.  Batch form: pt_render_aov_batch below with max_follow = 0.
  * pt_render_aov: blocking.  Honours the pixel shard, the current material table and environment, "watertight", "box_exact", "quad", and
  * a scene moved by pt_update_vertices.  With a communicator: ONE sum-reduce of the W*H*8 floats onto rank 0 (one non-zero contributor
  * per pixel: bit-identical to the one-GPU buffers); the other ranks may pass NULL.  pt_get_stats afterwards: kernel_ms and launches (1)
@@ -291,7 +292,7 @@ int pt_render_aov_device(pt_ctx* ctx, const pt_camera* cam, int32_t width, int32
  * is not followed contributes exactly what it contributes to pt_render_aov.
  * LIMITS: the normal of a followed sample is the last surface's normal in world space, not mirrored into the virtual image; depth is
  * the path length; at glass only the transmitted ray is followed, except on total internal reflection - the Fresnel reflection on a
- * window is not guided; the tint ignores Fresnel and the specular tint; no batch form.
+ * window is not guided; the tint ignores Fresnel and the specular tint.  Batch form: pt_render_aov_batch below.
  * pt_render_aov_follow (blocking) and pt_render_aov_follow_device (asynchronous; joins the asynchronous calls of the streams contract at
  * pt_render_device: ordered after the context's last asynchronous call and itself the last one afterwards) behave like pt_render_aov and
  * pt_render_aov_device in everything those list: arguments checked before anything is touched, PT_E_NO_SCENE, PT_E_INVALID - also for
@@ -306,13 +307,34 @@ typedef struct pt_aov_params {
 void pt_aov_default_params(pt_aov_params* p);   /* 1, 4, 0.3f, 0 */
 int pt_render_aov_follow(pt_ctx* ctx, const pt_camera* cam, int32_t width, int32_t height, const pt_aov_params* p /* NULL = defaults */, float* out_aov);
 int pt_render_aov_follow_device(pt_ctx* ctx, const pt_camera* cam, int32_t width, int32_t height, const pt_aov_params* p, void* d_out_aov, void* stream);
+/* The guide buffers of a batch: the frames of pt_render_batch (own camera and material table each) through the follow kernels, ONE
+ * launch per launch sequence (batch instances: csrc/pt_kernel_aov_follow_batch.hip).  DEFINED BY THE SINGLE-FRAME CALL: frame f is stored
+ * at out_aov + f * W*H*8 and is bit for bit what pt_set_materials(frame f's table) + pt_render_aov_follow(frame f's camera, p) stores
+ * for that frame alone; a materials == NULL frame uses the context's current table.  max_follow = 0 therefore gives the first-hit guides
+ * of pt_render_aov (CONSEQUENCES above).  Frames and tables as pt_render_batch: n_materials must equal the scene's; a row's texture slot
+ * stays the one the upload derived; the context's own table is neither used (unless a frame's is NULL) nor changed; the pixel shard
+ * applies per frame and pixels not owned are +0.  The batch is cut into launch sequences exactly as pt_render_batch cuts it
+ * (pt_debug_plan_batch, option "batch_frames"; a single frame beyond a sequence is PT_E_LIMIT) and the result does not depend on the cut.
+ * REFUSED before anything is touched or enqueued, with a message that names the call: everything pt_render_aov_follow refuses,
+ * n_frames < 1 or frames == NULL, a wrong n_materials, and option "watertight" = 1 (batches have no watertight instances).  On a
+ * host-only context valid arguments give PT_E_NO_DEVICE, invalid ones PT_E_INVALID.
+ * pt_render_aov_batch: blocking, like pt_render_aov_follow; with a communicator ONE sum-reduce per launch sequence over all of its frames
+ * onto rank 0 (the other ranks may pass NULL).  pt_render_aov_batch_device: asynchronous on `stream` (NULL = the context's), no reduce,
+ * n_frames * W*H*8 floats left in HBM at d_out_aov (16-byte aligned); joins the asynchronous calls of the streams contract at
+ * pt_render_device and, like pt_render_batch_device, returns when its per-frame tables have reached HBM.  pt_get_stats afterwards:
+ * kernel_ms from the first to the last kernel of the call, launches = launch sequences, the geometry fields of the guide kernel (grid: the
+ * longest sequence's).  No render state is kept: a pt_render after it is bit for bit the pt_render before it. */
+int pt_render_aov_batch(pt_ctx* ctx, const pt_frame* frames, int32_t n_frames, int32_t n_materials, int32_t width, int32_t height,
+                        const pt_aov_params* p /* NULL = defaults */, float* out_aov);
+int pt_render_aov_batch_device(pt_ctx* ctx, const pt_frame* frames, int32_t n_frames, int32_t n_materials, int32_t width, int32_t height,
+                               const pt_aov_params* p, void* d_out_aov, void* stream);
 
 /* ---- denoiser: guide-driven a-trous filter for low-sample frames (no reference counterpart; the reference binds no denoiser) ----
  * An edge-avoiding a-trous wavelet filter (Dammertz, Sewtz, Hanika, Lensch 2010): L iterations of a 5 x 5 B3-spline kernel whose tap
  * distance doubles each iteration, every tap weighted by how far it differs from the centre pixel in colour, shading normal, relative
  * depth and albedo; optionally on colour / albedo (PT_DENOISE_DEMODULATE).  It consumes a frame of pt_render and the guide buffers of
  * pt_render_aov, needs the WHOLE frame and no scene: with N GPUs call it on rank 0 (or pt_group_ctx(g, 0)) after the reduce.  It issues
- * no collective and has no group or batch form.
+ * no collective and has no group form; pt_denoise_batch below filters the frames of a batch.
  * BUFFERS: rgb and out_rgb are W*H*3 floats, aov the W*H*8 floats of pt_render_aov, all in the framebuffer order those calls produce
  * (the kernel is symmetric, so the filter works in framebuffer rows and columns as they lie in memory: row = index / W, x = index % W).
  * out_rgb may equal rgb (d_out_rgb may equal d_rgb): the filter works on buffers of its own.  out_rgba8 is optional.
@@ -355,6 +377,21 @@ int pt_denoise(pt_ctx* ctx, const float* rgb, const float* aov, int32_t width, i
                float* out_rgb, uint32_t* out_rgba8 /* optional */);
 int pt_denoise_device(pt_ctx* ctx, const void* d_rgb, const void* d_aov, int32_t width, int32_t height, const pt_denoise_params* p,
                       void* d_out_rgb, void* d_out_rgba8, void* stream);
+/* The filter over the frames of a batch (csrc/pt_denoise_batch.hip): n_frames frames of one size, W*H*3 floats apart in rgb and out_rgb,
+ * W*H*8 in aov, W*H in out_rgba8 - the layouts pt_render_batch and pt_render_aov_batch produce - with shared parameters.  DEFINED BY THE
+ * SINGLE-FRAME CALL: frame f is bit for bit pt_denoise of frame f of rgb and frame f of aov; no tap ever reads another frame.  out_rgb may
+ * equal rgb (d_out_rgb may equal d_rgb); out_rgba8 is optional; no scene is needed.  The batch is cut into launch sequences as
+ * pt_render_batch cuts it (pt_debug_plan_batch, option "batch_frames"; a single frame beyond a sequence is PT_E_LIMIT): a sequence is
+ * L + 2 launches over one set of filter records for its frames (64 bytes per pixel of the sequence), and the result does not depend on
+ * the cut.  REFUSED before anything is touched, with a message that names the call: everything pt_denoise refuses, and n_frames < 1; on a
+ * host-only context valid arguments give PT_E_NO_DEVICE, invalid ones PT_E_INVALID.  pt_denoise_batch is blocking like pt_denoise,
+ * pt_denoise_batch_device asynchronous like pt_denoise_device (same streams contract).  pt_get_stats afterwards: kernel_ms from the first
+ * to the last kernel of the call, launches = sequences * (L + 2), block, grid (the longest sequence's), vgprs, lds_bytes those of the
+ * iteration kernel.  No render state is kept. */
+int pt_denoise_batch(pt_ctx* ctx, const float* rgb, const float* aov, int32_t n_frames, int32_t width, int32_t height,
+                     const pt_denoise_params* p /* NULL = defaults */, float* out_rgb, uint32_t* out_rgba8 /* optional */);
+int pt_denoise_batch_device(pt_ctx* ctx, const void* d_rgb, const void* d_aov, int32_t n_frames, int32_t width, int32_t height,
+                            const pt_denoise_params* p, void* d_out_rgb, void* d_out_rgba8, void* stream);
 /* The CPU twin of the filter: the definition above on all host threads; works on a host-only context; returns width * height. */
 int64_t pt_debug_denoise_host(pt_ctx* ctx, const float* rgb, const float* aov, int32_t width, int32_t height, const pt_denoise_params* p,
                               float* out_rgb, uint32_t* out_rgba8);

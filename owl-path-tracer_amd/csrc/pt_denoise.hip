@@ -12,6 +12,11 @@
 //   finish     colour record -> out_rgb (and out_rgba8), multiplied back by the albedo divisor with PT_DENOISE_DEMODULATE.
 // The caller's rgb / out_rgb are 12 bytes per pixel with no alignment promise, so those two streams are dword accesses; every record of
 // the work buffer and the guide input are 16-byte accesses.
+//
+// BATCH BUILD.  pt_denoise_batch.hip includes this file with PT_DENOISE_BATCH = 1: the same three kernels as pt_denoise_batch_{prepare,
+// iter,finish}_kernel over K frames of one size (pt_denoise_batch), the frame in blockIdx.z.  A kernel first moves every record and
+// caller pointer to its frame's own base (dn_frame); the pixel, the taps and their bounds test are then the single frame's, so no tap
+// reads another frame.  With PT_DENOISE_BATCH = 0 the preprocessor removes all of it.
 #include <hip/hip_runtime.h>
 
 #include "../../include/mi355pt.h"
@@ -19,6 +24,18 @@
 #include "pt_launch.h"
 
 using namespace ptd;
+
+#ifndef PT_DENOISE_BATCH
+#define PT_DENOISE_BATCH 0
+#endif
+#if PT_DENOISE_BATCH
+#define pt_denoise_prepare_kernel pt_denoise_batch_prepare_kernel
+#define pt_denoise_iter_kernel pt_denoise_batch_iter_kernel
+#define pt_denoise_finish_kernel pt_denoise_batch_finish_kernel
+#define pt_denoise_workspace_bytes pt_denoise_batch_workspace_bytes
+#define pt_denoise_geometry pt_denoise_batch_geometry
+#define pt_launch_denoise pt_launch_denoise_batch
+#endif
 
 namespace {
 
@@ -31,6 +48,24 @@ __device__ __forceinline__ bool dn_pixel(const PtDenoiseArgs& A, int& x, int& ro
     return x < A.width && row < A.height;
 }
 
+#if PT_DENOISE_BATCH
+// Everything a kernel indexes by pixel, moved to frame blockIdx.z: the four record arrays are K frames long each, the caller's buffers
+// are K frames back to back.  Returns the pixels a frame is apart (for the iteration kernel's src / dst).
+__device__ __forceinline__ size_t dn_frame(PtDenoiseArgs& A)
+{
+    const size_t f = (size_t)blockIdx.z * ((size_t)A.width * (size_t)A.height);
+    A.rgb += 3 * f;
+    A.aov += 8 * f;
+    A.out_rgb += 3 * f;
+    if (A.out_rgba8) A.out_rgba8 += f;
+    A.col[0] += f;
+    A.col[1] += f;
+    A.nz += f;
+    A.alb += f;
+    return f;
+}
+#endif
+
 __device__ __forceinline__ float dn_finite_or_0(float v) { return (isinf_(v) || isnan_(v)) ? 0.0f : v; }
 __device__ __forceinline__ float dn_div(float a) { return max_(a, 1e-3f); } // d_k of PT_DENOISE_DEMODULATE
 
@@ -38,6 +73,9 @@ __global__ __launch_bounds__(DN_TILE_W * DN_TILE_H) void pt_denoise_prepare_kern
 {
     int x, row;
     if (!dn_pixel(A, x, row)) return;
+#if PT_DENOISE_BATCH
+    dn_frame(A);
+#endif
     const size_t i = (size_t)row * (size_t)A.width + (size_t)x;
     const float4* g = (const float4*)A.aov + 2 * i;
     const float4 g0 = g[0], g1 = g[1]; // albedo r g b, alpha | normal x y z, depth
@@ -55,6 +93,11 @@ __global__ __launch_bounds__(DN_TILE_W * DN_TILE_H) void pt_denoise_iter_kernel(
 {
     int x, row;
     if (!dn_pixel(A, x, row)) return;
+#if PT_DENOISE_BATCH
+    const size_t frame_ofs = dn_frame(A);
+    src += frame_ofs;
+    dst += frame_ofs;
+#endif
     const int W = A.width, H = A.height;
     const float4* __restrict__ nzb = A.nz;
     const float4* __restrict__ alb = A.alb;
@@ -103,6 +146,9 @@ __global__ __launch_bounds__(DN_TILE_W * DN_TILE_H) void pt_denoise_finish_kerne
 {
     int x, row;
     if (!dn_pixel(A, x, row)) return;
+#if PT_DENOISE_BATCH
+    src += dn_frame(A);
+#endif
     const size_t i = (size_t)row * (size_t)A.width + (size_t)x;
     const float4 c = src[i];
     v3 o = V(c.x, c.y, c.z);
@@ -117,11 +163,19 @@ __global__ __launch_bounds__(DN_TILE_W * DN_TILE_H) void pt_denoise_finish_kerne
 
 } // namespace
 
+#if PT_DENOISE_BATCH
+extern "C" size_t pt_denoise_workspace_bytes(int W, int H, int K) { return (size_t)K * (size_t)W * (size_t)H * 64; } // four 16-byte records per pixel of K frames
+#else
 extern "C" size_t pt_denoise_workspace_bytes(int W, int H) { return (size_t)W * (size_t)H * 64; } // four 16-byte records per pixel
+#endif
 
 // Geometry of the iteration kernel for a W x H frame (block, grid = workgroups, vgprs, lds_bytes = 0); hipErrorInvalidConfiguration if
 // one of the three kernels needs scratch in this build.
+#if PT_DENOISE_BATCH
+extern "C" hipError_t pt_denoise_geometry(int W, int H, int K, PtGeometry* g, int* grid) // (K frames: grid = the workgroups of all of them)
+#else
 extern "C" hipError_t pt_denoise_geometry(int W, int H, PtGeometry* g, int* grid)
+#endif
 {
     const void* fns[3] = {(const void*)pt_denoise_iter_kernel, (const void*)pt_denoise_prepare_kernel, (const void*)pt_denoise_finish_kernel};
     hipFuncAttributes fa;
@@ -138,20 +192,36 @@ extern "C" hipError_t pt_denoise_geometry(int W, int H, PtGeometry* g, int* grid
     g->vgprs = fa.numRegs; // (the loop ends on the iteration kernel)
     g->max_blocks_per_cu = 0;
     *grid = ((W + DN_TILE_W - 1) / DN_TILE_W) * ((H + DN_TILE_H - 1) / DN_TILE_H);
+#if PT_DENOISE_BATCH
+    *grid *= K;
+#endif
     return hipOccupancyMaxActiveBlocksPerMultiprocessor(&g->max_blocks_per_cu, fns[0], g->block, 0);
 }
 
 // prepare, a->iterations iteration launches, finish - all on `stream`.  a->ws: pt_denoise_workspace_bytes(), 16-byte aligned.
+#if PT_DENOISE_BATCH
+// (K frames, 1 <= K <= 65535: a->rgb, aov, out_rgb, out_rgba8 are those of the first; a->ws: pt_denoise_batch_workspace_bytes(W, H, K))
+extern "C" hipError_t pt_launch_denoise(const PtDenoiseArgs* a, int K, hipStream_t stream)
+{
+    if (K < 1 || K > 65535) return hipErrorInvalidValue;
+    PtDenoiseArgs A = *a;
+    const size_t npx = (size_t)K * (size_t)A.width * (size_t)A.height;
+#else
 extern "C" hipError_t pt_launch_denoise(const PtDenoiseArgs* a, hipStream_t stream)
 {
     PtDenoiseArgs A = *a;
     const size_t npx = (size_t)A.width * (size_t)A.height;
+#endif
     float4* ws = (float4*)A.ws;
     A.col[0] = ws;
     A.col[1] = ws + npx;
     A.nz = ws + 2 * npx;
     A.alb = ws + 3 * npx;
+#if PT_DENOISE_BATCH
+    const dim3 block(DN_TILE_W, DN_TILE_H), grid((A.width + DN_TILE_W - 1) / DN_TILE_W, (A.height + DN_TILE_H - 1) / DN_TILE_H, K);
+#else
     const dim3 block(DN_TILE_W, DN_TILE_H), grid((A.width + DN_TILE_W - 1) / DN_TILE_W, (A.height + DN_TILE_H - 1) / DN_TILE_H);
+#endif
     hipLaunchKernelGGL(pt_denoise_prepare_kernel, grid, block, 0, stream, A);
     for (int i = 0; i < A.iterations; ++i)
         hipLaunchKernelGGL(pt_denoise_iter_kernel, grid, block, 0, stream, A, (const float4*)A.col[i & 1], A.col[(i + 1) & 1], 1 << i, A.kc[i]);

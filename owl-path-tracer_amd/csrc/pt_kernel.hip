@@ -44,10 +44,11 @@
 #endif
 #ifndef PT_AOV
 #define PT_AOV 0 // 1: pt_kernel_aov.hip / pt_kernel_aov_wt.hip - the device functions of this file around the guide kernels alone ("guide pass", at the end)
-                 // 2: pt_kernel_aov_follow.hip / pt_kernel_aov_follow_wt.hip - the same around the follow kernels ("guide pass, follow mode")
+                 // 2: pt_kernel_aov_follow.hip / pt_kernel_aov_follow_wt.hip - the same around the follow kernels ("guide pass, follow mode");
+                 //    with PT_BATCH = 1 (pt_kernel_aov_follow_batch.hip) around their batch instances (pt_render_aov_batch)
 #endif
-#if PT_AOV && PT_BATCH
-#error "the guide pass has no batch form"
+#if PT_AOV == 1 && PT_BATCH
+#error "the first-hit guide pass has no batch form (pt_render_aov_batch runs the follow kernels; max_follow = 0 gives the first-hit guides)"
 #endif
 #if PT_WATERTIGHT
 #if PT_BATCH
@@ -71,6 +72,9 @@
 #define pt_aov_follow_geometry pt_aov_follow_geometry_wt
 #elif PT_BATCH
 #define PT_RENDER_KERNEL pt_render_batch_kernel
+#define pt_aov_follow_kernel pt_aov_follow_batch_kernel
+#define pt_launch_aov_follow pt_launch_aov_follow_batch
+#define pt_aov_follow_geometry pt_aov_follow_batch_geometry
 #else
 #define PT_RENDER_KERNEL pt_render_wave_kernel
 #endif
@@ -1710,6 +1714,10 @@ extern "C" hipError_t pt_launch_aov(const PtKernelParams* p, const PtAovArgs* a,
 // only between samples, and the lane's place in its 8 x 8 block: 15 words per lane, 3.75 KB per wave (16 waves per CU: 108 KB of 160 KB together with the stacks).  The accesses
 // are volatile: the compiler must not promote the parked words back into registers across the walk (it did, and spilled them to scratch).
 // No scratch, 128 VGPRs at the most (`make asm-aov-follow`).
+// BATCH BUILD (pt_kernel_aov_follow_batch.hip: PT_AOV = 2 and PT_BATCH = 1; pt_render_aov_batch).  The same kernel as pt_aov_follow_batch_kernel
+// over the 8 x 8 blocks of K frames, frame by frame: a wave's block lies in one frame, so the frame's camera (P.batch_cams) and material
+// table (P.materials + frame * n_materials * PT_MAT_STRIDE) are wave-uniform - scalar loads, no per-lane gather as in the render batch -
+// and frame f is stored W * H pixels behind frame f - 1.  With PT_BATCH = 0 the preprocessor removes all of it (`make asm-aov-follow-batch`).
 #define PT_AS3 __attribute__((address_space(3)))
 #define PT_AOV_PARK 15 // LDS words per lane behind the stack: 8 sums, tint r g b, path length, RNG state, px | py << 16, the lane's place in its block
 enum { AOV_NONE = 0, AOV_MIRROR = 1, AOV_GLASS = 2 };
@@ -1728,8 +1736,14 @@ __device__ __forceinline__ int aov_classify(const Material& m, float roughness_m
 
 // One surface of a guide ray (o, d) whose walk ended in h.  Returns true if the ray goes on: o, d, tint updated, dist advanced.  Otherwise
 // the sample's contribution is complete: albedo, normal, depth set.  The miss branch is aov_sample's; the fetches are its expressions.
+#if PT_BATCH
+// (batch instances: mats = the material table of the block's frame, wave-uniform; everything else as below)
+__device__ __forceinline__ bool aov_follow_surface(const PtKernelParams& P, const float* mats, const PtAovFollowArgs& F, const Hit& h, int step, v3& o, v3& d, v3& tint,
+                                                   float& dist, v3& albedo, v3& normal, float& depth)
+#else
 __device__ __forceinline__ bool aov_follow_surface(const PtKernelParams& P, const PtAovFollowArgs& F, const Hit& h, int step, v3& o, v3& d, v3& tint, float& dist,
                                                    v3& albedo, v3& normal, float& depth)
+#endif
 {
     if (h.slot < 0) { // aov_sample's miss branch, expression for expression
         v3 radiance = vs(0.0f);
@@ -1760,7 +1774,11 @@ __device__ __forceinline__ bool aov_follow_surface(const PtKernelParams& P, cons
     Material mat = material_default();
     int tex_slot = -1;
     if (mi >= 0) {
+#if PT_BATCH
+        const float PT_AS1* mp = gp(mats) + mi * PT_MAT_STRIDE;
+#else
         const float PT_AS1* mp = gp(P.materials) + mi * PT_MAT_STRIDE;
+#endif
         mat = material_load(mp);
         tex_slot = __float_as_int(mp[17]);
     }
@@ -1818,8 +1836,17 @@ __global__ void __launch_bounds__(PT_WAVE, PT_AOV_WAVES_PER_EU) pt_aov_follow_ke
     const PtTri* __restrict__ tris = P.tris;
     const int nbx = (P.width + 7) >> 3, nby = (P.height + 7) >> 3;
     parku[14 * PT_WAVE] = (uint32_t)(lane & 7) | ((uint32_t)(lane >> 3) << 16);
+#if PT_BATCH
+    // K * nbx * nby blocks, frame by frame: a block belongs to ONE frame whatever the height, so the frame, its camera and its material
+    // table are wave-uniform.  bf: the block inside its frame - shard, pixels and RNG stream are the single frame's.
+    const int nb = nbx * nby;
+    for (int bb = blockIdx.x; bb < P.batch_frames * nb; bb += gridDim.x) {
+        const int frame = bb / nb, b = bb - frame * nb;
+        const int bx = b % nbx, by = b / nbx;
+#else
     for (int b = blockIdx.x; b < nbx * nby; b += gridDim.x) {
         const int bx = b % nbx, by = b / nbx;
+#endif
         if (((bx * 8) / A.tile + (by * 8) / A.tile) % A.world != A.rank) continue; // another rank's tile (wave-uniform)
         const uint32_t in_block = parku[14 * PT_WAVE];
         const int px = bx * 8 + (int)(in_block & 0xffffu), py = by * 8 + (int)(in_block >> 16);
@@ -1832,7 +1859,11 @@ __global__ void __launch_bounds__(PT_WAVE, PT_AOV_WAVES_PER_EU) pt_aov_follow_ke
             PathState ps;
             ps.rng = parku[12 * PT_WAVE];
             const uint32_t pxy = parku[13 * PT_WAVE];
+#if PT_BATCH
+            gen_camera_ray_from(P, gp(P.batch_cams) + 12 * frame, (int)(pxy & 0xffffu), (int)(pxy >> 16), ps);
+#else
             gen_camera_ray(P, (int)(pxy & 0xffffu), (int)(pxy >> 16), ps); // two draws; the follow loop draws nothing
+#endif
             parku[12 * PT_WAVE] = ps.rng;
             v3 o = ps.org, d = ps.dir;
             park[8 * PT_WAVE] = 1.0f; park[9 * PT_WAVE] = 1.0f; park[10 * PT_WAVE] = 1.0f; park[11 * PT_WAVE] = 0.0f;
@@ -1873,7 +1904,11 @@ __global__ void __launch_bounds__(PT_WAVE, PT_AOV_WAVES_PER_EU) pt_aov_follow_ke
                 if (step == 0 && h.slot >= 0) park[3 * PT_WAVE] = park[3 * PT_WAVE] + 1.0f; // coverage stays first-hit
                 v3 tint = V(park[8 * PT_WAVE], park[9 * PT_WAVE], park[10 * PT_WAVE]);
                 float dist = park[11 * PT_WAVE];
+#if PT_BATCH
+                if (!aov_follow_surface(P, P.materials + (size_t)frame * (size_t)(P.n_materials * PT_MAT_STRIDE), F, h, step, o, d, tint, dist, alb, nrm, depth)) break;
+#else
                 if (!aov_follow_surface(P, F, h, step, o, d, tint, dist, alb, nrm, depth)) break;
+#endif
                 park[8 * PT_WAVE] = tint.x; park[9 * PT_WAVE] = tint.y; park[10 * PT_WAVE] = tint.z; park[11 * PT_WAVE] = dist;
             }
             // float32, in sample order
@@ -1882,7 +1917,11 @@ __global__ void __launch_bounds__(PT_WAVE, PT_AOV_WAVES_PER_EU) pt_aov_follow_ke
             park[7 * PT_WAVE] = park[7 * PT_WAVE] + depth;
         }
         const uint32_t pxy = parku[13 * PT_WAVE];
+#if PT_BATCH
+        const size_t ofs = (size_t)frame * ((size_t)P.width * (size_t)P.height) + (size_t)(pxy & 0xffffu) + (size_t)P.width * (size_t)(P.height - 1 - (int)(pxy >> 16));
+#else
         const size_t ofs = (size_t)(pxy & 0xffffu) + (size_t)P.width * (size_t)(P.height - 1 - (int)(pxy >> 16)); // as out_rgb
+#endif
         f32x4 PT_AS1* y = (f32x4 PT_AS1*)(gp(A.out) + 8 * ofs);                        // two 16-byte stores
         y[0] = (f32x4){park[0 * PT_WAVE] * F.inv_n, park[1 * PT_WAVE] * F.inv_n, park[2 * PT_WAVE] * F.inv_n, park[3 * PT_WAVE] * F.inv_n};
         y[1] = (f32x4){park[4 * PT_WAVE] * F.inv_n, park[5 * PT_WAVE] * F.inv_n, park[6 * PT_WAVE] * F.inv_n, park[7 * PT_WAVE] * F.inv_n};
@@ -1915,6 +1954,9 @@ extern "C" hipError_t pt_aov_follow_geometry(int binary, int exact, int stack_en
 extern "C" hipError_t pt_launch_aov_follow(const PtKernelParams* p, const PtAovFollowArgs* a, int binary, int grid, size_t lds_bytes, hipStream_t stream)
 {
     if (grid < 1) grid = 1;
+#if PT_BATCH
+    if (p->batch_frames < 1 || p->batch_cams == nullptr) return hipErrorInvalidValue; // (pt_launch_aov_follow_batch: frames, cameras and tables as pt_launch_render_batch)
+#endif
 #if PT_WATERTIGHT
     if (binary) return hipErrorInvalidValue;
 #else

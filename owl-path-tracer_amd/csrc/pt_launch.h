@@ -86,6 +86,11 @@ extern "C" {
 size_t pt_denoise_workspace_bytes(int W, int H);
 hipError_t pt_denoise_geometry(int W, int H, PtGeometry* g, int* grid);
 hipError_t pt_launch_denoise(const PtDenoiseArgs* a, hipStream_t stream);
+// pt_denoise_batch.hip: the same over K frames of one size, back to back in every caller buffer (the pointers of *a are the first frame's),
+// frame in blockIdx.z: 1 <= K <= 65535; workspace and grid cover all K frames
+size_t pt_denoise_batch_workspace_bytes(int W, int H, int K);
+hipError_t pt_denoise_batch_geometry(int W, int H, int K, PtGeometry* g, int* grid);
+hipError_t pt_launch_denoise_batch(const PtDenoiseArgs* a, int K, hipStream_t stream);
 // pt_kernel.hip / pt_kernel_wt.hip: the guide kernels.  binary = 1: the one-level walk over PtNode[] (closest_hit of pt_trace.h; Moeller-
 // Trumbore only: the watertight build has no such instance and answers hipErrorInvalidValue).  Geometry: block, lds_bytes, lds_levels and
 // vgprs of the instance; hipErrorInvalidConfiguration if it needs scratch.
@@ -98,6 +103,10 @@ hipError_t pt_launch_aov_follow(const PtKernelParams* p, const PtAovFollowArgs* 
 hipError_t pt_aov_follow_geometry(int binary, int exact, int stack_entries, PtGeometry* g);
 hipError_t pt_launch_aov_follow_wt(const PtKernelParams* p, const PtAovFollowArgs* a, int binary, int grid, size_t lds_bytes, hipStream_t stream);
 hipError_t pt_aov_follow_geometry_wt(int binary, int exact, int stack_entries, PtGeometry* g);
+// pt_kernel_aov_follow_batch.hip: the batch instances of the follow kernels over the blocks of p->batch_frames frames (p->batch_cams, p->materials =
+// the first frame's table, a->out = the first frame's buffers; PtKernelParams::batch_*), same conventions
+hipError_t pt_launch_aov_follow_batch(const PtKernelParams* p, const PtAovFollowArgs* a, int binary, int grid, size_t lds_bytes, hipStream_t stream);
+hipError_t pt_aov_follow_batch_geometry(int binary, int exact, int stack_entries, PtGeometry* g);
 size_t pt_refit_workspace_bytes(void);
 // gather, extent, one refit launch per level, propagate - all on `stream`, `first` recorded before the first kernel, `last` after the last
 hipError_t pt_launch_refit(const PtRefitArgs* a, hipEvent_t first, hipEvent_t last, hipStream_t stream);

@@ -28,9 +28,14 @@ hipError_t pt_launch_aov_follow(const PtKernelParams*, const PtAovFollowArgs*, i
 hipError_t pt_aov_follow_geometry(int, int, int, PtGeometry*) { return hipErrorNotSupported; }
 hipError_t pt_launch_aov_follow_wt(const PtKernelParams*, const PtAovFollowArgs*, int, int, size_t, hipStream_t) { return hipErrorNotSupported; }
 hipError_t pt_aov_follow_geometry_wt(int, int, int, PtGeometry*) { return hipErrorNotSupported; }
+hipError_t pt_launch_aov_follow_batch(const PtKernelParams*, const PtAovFollowArgs*, int, int, size_t, hipStream_t) { return hipErrorNotSupported; }
+hipError_t pt_aov_follow_batch_geometry(int, int, int, PtGeometry*) { return hipErrorNotSupported; }
 size_t pt_denoise_workspace_bytes(int, int) { return 16; }
 hipError_t pt_denoise_geometry(int, int, PtGeometry*, int*) { return hipErrorNotSupported; }
 hipError_t pt_launch_denoise(const PtDenoiseArgs*, hipStream_t) { return hipErrorNotSupported; }
+size_t pt_denoise_batch_workspace_bytes(int, int, int) { return 16; }
+hipError_t pt_denoise_batch_geometry(int, int, int, PtGeometry*, int*) { return hipErrorNotSupported; }
+hipError_t pt_launch_denoise_batch(const PtDenoiseArgs*, int, hipStream_t) { return hipErrorNotSupported; }
 hipError_t pt_launch_probe(const PtKernelParams*, int, const float*, int, float*, int, long long, int, size_t, uint32_t*, hipStream_t) { return hipErrorNotSupported; }
 int pt_probe_lds_stack(void) { return 12; }
 size_t pt_probe_group_lds_bytes(int, int) { return 16; }

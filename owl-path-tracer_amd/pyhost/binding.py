@@ -99,7 +99,8 @@ EXPORTS = ["pt_create", "pt_destroy", "pt_last_error", "pt_abi_version", "pt_upl
            "pt_render_batch", "pt_render_batch_device", "pt_debug_plan_batch", "pt_update_vertices", "pt_group_update_vertices", "pt_debug_update_info",
            "pt_render_aov", "pt_render_aov_device", "pt_group_render_aov", "pt_debug_aov_host",
            "pt_denoise_default_params", "pt_denoise", "pt_denoise_device", "pt_debug_denoise_host",
-           "pt_aov_default_params", "pt_render_aov_follow", "pt_render_aov_follow_device", "pt_group_render_aov_follow", "pt_debug_aov_follow_host"]
+           "pt_aov_default_params", "pt_render_aov_follow", "pt_render_aov_follow_device", "pt_group_render_aov_follow", "pt_debug_aov_follow_host",
+           "pt_render_aov_batch", "pt_render_aov_batch_device", "pt_denoise_batch", "pt_denoise_batch_device"]
 PT_DENOISE_DEMODULATE = 1
 PT_TREE_DEVICE = 16  # pt_debug_export_tree: ORed into `which`, the array as HBM holds it
 PT_COMM_ID_BYTES = 128
@@ -203,6 +204,10 @@ def lib():
     L.pt_denoise_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(DenoiseParams), C.c_void_p, C.c_void_p, C.c_void_p]
     L.pt_debug_denoise_host.argtypes = [C.c_void_p, fp, fp, C.c_int32, C.c_int32, C.POINTER(DenoiseParams), fp, C.POINTER(C.c_uint32)]
     L.pt_debug_denoise_host.restype = C.c_int64
+    L.pt_render_aov_batch.argtypes = [C.c_void_p, C.POINTER(Frame), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(AovParams), fp]
+    L.pt_render_aov_batch_device.argtypes = [C.c_void_p, C.POINTER(Frame), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(AovParams), C.c_void_p, C.c_void_p]
+    L.pt_denoise_batch.argtypes = [C.c_void_p, fp, fp, C.c_int32, C.c_int32, C.c_int32, C.POINTER(DenoiseParams), fp, C.POINTER(C.c_uint32)]
+    L.pt_denoise_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(DenoiseParams), C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = L
     return L
 
@@ -546,6 +551,29 @@ class Context:
         self._check(lib().pt_render_aov_follow_device(self._h, C.byref(cam), W, H, C.byref(params) if params is not None else None, C.c_void_p(d_out_aov),
                                                       C.c_void_p(stream) if stream else None), "pt_render_aov_follow_device")
 
+    def render_aov_batch(self, frames, W, H, params=None, n_materials=None, receive=True):
+        """pt_render_aov_batch: frames as render_batch.  Returns (K, H, W, 8) float32: frame k is what set_materials(frames[k][1]) +
+        render_aov_follow(frames[k][0], params) returns.  n_materials: only needed when every frame passes None; receive = False: a
+        non-root rank of a communicator (returns None)."""
+        arr, n_mat, keep = _marshal_frames(frames)
+        if n_materials is not None:
+            n_mat = int(n_materials)
+        K = len(frames)
+        out = np.empty((K, H, W, 8), np.float32) if receive else None
+        self._check(lib().pt_render_aov_batch(self._h, arr if K else None, K, n_mat, W, H, C.byref(params) if params is not None else None,
+                                              out.ctypes.data_as(C.POINTER(C.c_float)) if receive else None), "pt_render_aov_batch")
+        del keep
+        return out
+
+    def render_aov_batch_device(self, frames, W, H, d_out_aov, params=None, stream=None, n_materials=None):
+        """pt_render_aov_batch_device: asynchronous, K * W*H*8 floats left in HBM at d_out_aov; conventions of render_batch_device."""
+        arr, n_mat, keep = _marshal_frames(frames)
+        if n_materials is not None:
+            n_mat = int(n_materials)
+        self._check(lib().pt_render_aov_batch_device(self._h, arr if frames else None, len(frames), n_mat, W, H, C.byref(params) if params is not None else None,
+                                                     C.c_void_p(d_out_aov), C.c_void_p(stream) if stream else None), "pt_render_aov_batch_device")
+        del keep
+
     def aov_follow_host(self, cam, W, H, params=None, pixel_ids=None):
         """pt_debug_aov_follow_host, the CPU twin of render_aov_follow (works on a host-only context); pixel_ids and result as aov_host."""
         whole = pixel_ids is None
@@ -579,6 +607,27 @@ class Context:
     def denoise_host(self, rgb, aov, params=None, want_rgba8=False, in_place=False):
         """pt_debug_denoise_host, the CPU twin of denoise (works on a host-only context)."""
         return self._denoise(lib().pt_debug_denoise_host, "pt_debug_denoise_host", rgb, aov, params, want_rgba8, in_place)
+
+    def denoise_batch(self, rgb, aov, params=None, want_rgba8=False, in_place=False):
+        """pt_denoise_batch: rgb (K, H, W, 3) as render_batch returns it and aov (K, H, W, 8) as render_aov_batch returns it -> the K filtered
+        frames (and their RGBA8 images); frame k is what denoise(rgb[k], aov[k], params) returns.  in_place: the result overwrites rgb."""
+        aov = np.ascontiguousarray(aov, np.float32)
+        K, H, W = aov.shape[0], aov.shape[1], aov.shape[2]
+        src = rgb if in_place else np.ascontiguousarray(rgb, np.float32)
+        assert src.dtype == np.float32 and src.flags["C_CONTIGUOUS"] and src.shape == (K, H, W, 3) and aov.shape == (K, H, W, 8)
+        out = src if in_place else np.empty((K, H, W, 3), np.float32)
+        rgba = np.empty((K, H, W), np.uint32) if want_rgba8 else None
+        fp = C.POINTER(C.c_float)
+        self._check(lib().pt_denoise_batch(self._h, src.ctypes.data_as(fp), aov.ctypes.data_as(fp), K, W, H, C.byref(params) if params is not None else None,
+                                           out.ctypes.data_as(fp), rgba.ctypes.data_as(C.POINTER(C.c_uint32)) if rgba is not None else None), "pt_denoise_batch")
+        return out, rgba
+
+    def denoise_batch_device(self, d_rgb, d_aov, K, W, H, d_out_rgb, params=None, d_out_rgba8=None, stream=None):
+        """pt_denoise_batch_device: asynchronous, device pointers to K frames back to back (d_out_rgb may equal d_rgb); conventions of
+        denoise_device."""
+        self._check(lib().pt_denoise_batch_device(self._h, C.c_void_p(d_rgb), C.c_void_p(d_aov), K, W, H, C.byref(params) if params is not None else None,
+                                                  C.c_void_p(d_out_rgb), C.c_void_p(d_out_rgba8) if d_out_rgba8 else None, C.c_void_p(stream) if stream else None),
+                    "pt_denoise_batch_device")
 
     def denoise_device(self, d_rgb, d_aov, W, H, d_out_rgb, params=None, d_out_rgba8=None, stream=None):
         """pt_denoise_device: asynchronous, device pointers (integers; d_out_rgb may equal d_rgb); synchronize() waits for it.  stream: a
