@@ -5,7 +5,7 @@
 // normalize, lerp3, uv_on_sphere (the polynomial atan2 / asin), tex_nearest and the material row are the functions the kernel
 // compiles, run by the CPU under the same contract (binary32, -ffp-contract=off, fma only where spelled, correctly rounded division
 // and sqrt).  What is restated here is what the kernel takes from pt_trace.h, which is device code throughout: the camera ray
-// (gen_camera_ray), interp3 and the miss branch / attribute fetch of shade_hit - each a few lines, cited below.
+// (gen_camera_ray), interp3 and the miss branch / attribute fetch of shade_hit - each a few lines, once for both twin pixels, cited below.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -37,10 +37,75 @@ bool finite_(float x) { return !(isinf_(x) || isnan_(x)); }
 struct AovScene {
     const HostScene* s;
     std::vector<int32_t> slot_of; // global triangle id -> leaf-order slot (the host walk reports the id, the records are in leaf order)
-    pt_camera cam;
+    v3 origin, llc, hor, ver;     // the camera
     int W, H, n;
     bool wt;
 };
+
+// What the two kernels take from pt_trace.h, for both twin pixels.  gen_camera_ray: the direction of the pixel's next sample.
+v3 camera_dir(const AovScene& A, int px, int py, uint32_t& rng)
+{
+    const float rx = rng_next(rng);
+    const float ry = rng_next(rng);
+    const float su = ((float)px + rx) / (float)A.W;
+    const float sv = ((float)py + ry) / (float)A.H;
+    return normalize(((A.llc + A.hor * su) + A.ver * sv) - A.origin);
+}
+
+// shade_hit's miss branch: what a ray along dir sees of the environment
+v3 miss_radiance(const HostScene& S, v3 dir)
+{
+    v3 radiance = vs(0.0f);
+    if (S.env.use_map && S.env_map.w > 0) {
+        float tu, tv;
+        uv_on_sphere(dir, tu, tv);
+        radiance = radiance + tex_nearest(S.env_map.px.data(), S.env_map.w, S.env_map.h, tu, tv);
+    } else if (S.env.use_auto) {
+        radiance = radiance + lerp3(vs(1.0f), V(0.5f, 0.7f, 1.0f), 0.5f * (dir.y + 1.0f));
+    } else {
+        radiance = radiance + V(S.env.color[0], S.env.color[1], S.env.color[2]);
+    }
+    return radiance * S.env.intensity;
+}
+
+// shade_hit's attribute fetch at the hit (prim, hu, hv): the material row with its texture looked up (unless the surface emits), the
+// interpolated normal and whether it is finite
+struct AovHit {
+    const PtTri* tr;
+    Material mat;
+    float bw, bx, by;
+    v3 v_n;
+    bool n_ok, emits;
+};
+AovHit fetch_hit(const AovScene& A, int32_t prim, float hu, float hv)
+{
+    const HostScene& S = *A.s;
+    const size_t slot = (size_t)A.slot_of[(size_t)prim];
+    const PtShade& sh = S.shade[slot];
+    AovHit h;
+    h.tr = &S.bvh.tris[slot];
+    const int mi = h.tr->material;
+    h.mat = material_default();
+    int32_t tex_slot = -1;
+    if (mi >= 0) {
+        const float* mp = &S.materials[(size_t)mi * PT_MAT_STRIDE];
+        h.mat = material_load(mp);
+        std::memcpy(&tex_slot, mp + 17, 4);
+    }
+    const float bx = hu, by = hv;
+    const float bw = 1.0f - bx - by;
+    h.bw = bw; h.bx = bx; h.by = by;
+    h.v_n = normalize(interp3(bw, bx, by, V(sh.n0[0], sh.n0[1], sh.n0[2]), V(sh.n1[0], sh.n1[1], sh.n1[2]), V(sh.n2[0], sh.n2[1], sh.n2[2])));
+    h.n_ok = finite_(h.v_n.x) && finite_(h.v_n.y) && finite_(h.v_n.z);
+    h.emits = h.mat.emission > 0.0f;
+    if (!h.emits && tex_slot >= 0) {
+        const float tu = fma_(by, sh.tc[4], fma_(bx, sh.tc[2], bw * sh.tc[0]));
+        const float tv = fma_(by, sh.tc[5], fma_(bx, sh.tc[3], bw * sh.tc[1]));
+        const HostTexture& tx = S.textures[(size_t)tex_slot];
+        h.mat.base_color = tex_nearest(tx.px.data(), tx.w, tx.h, tu, tv);
+    }
+    return h;
+}
 
 // One pixel: include/mi355pt.h, "guide pass"; the kernel's loop body (pt_aov_kernel) line for line.
 void aov_pixel(const AovScene& A, int px, int py, float* y)
@@ -49,58 +114,20 @@ void aov_pixel(const AovScene& A, int px, int py, float* y)
     uint32_t rng = rng_init((uint32_t)px, (uint32_t)py);
     v3 s_alb = vs(0.0f), s_nrm = vs(0.0f);
     float s_alpha = 0.0f, s_depth = 0.0f;
-    const v3 origin = V(A.cam.origin[0], A.cam.origin[1], A.cam.origin[2]), llc = V(A.cam.llc[0], A.cam.llc[1], A.cam.llc[2]);
-    const v3 hor = V(A.cam.horizontal[0], A.cam.horizontal[1], A.cam.horizontal[2]), ver = V(A.cam.vertical[0], A.cam.vertical[1], A.cam.vertical[2]);
     for (int k = 0; k < A.n; ++k) {
-        const float rx = rng_next(rng); // gen_camera_ray (pt_trace.h)
-        const float ry = rng_next(rng);
-        const float su = ((float)px + rx) / (float)A.W;
-        const float sv = ((float)py + ry) / (float)A.H;
-        const v3 dir = normalize(((llc + hor * su) + ver * sv) - origin);
-        const float o[3] = {origin.x, origin.y, origin.z}, d[3] = {dir.x, dir.y, dir.z};
+        const v3 dir = camera_dir(A, px, py, rng);
+        const float o[3] = {A.origin.x, A.origin.y, A.origin.z}, d[3] = {dir.x, dir.y, dir.z};
         float t = 0.0f, hu = 0.0f, hv = 0.0f;
         int32_t prim = -1;
         const bool hit = pt_bvh_closest_hit_host(S.bvh, o, d, kTMin, kTMax, &t, &hu, &hv, &prim, A.wt);
         v3 alb, nrm = vs(0.0f);
         float alpha = 0.0f, depth = 0.0f;
-        if (!hit) { // shade_hit's miss branch
-            v3 radiance = vs(0.0f);
-            if (S.env.use_map && S.env_map.w > 0) {
-                float tu, tv;
-                uv_on_sphere(dir, tu, tv);
-                radiance = radiance + tex_nearest(S.env_map.px.data(), S.env_map.w, S.env_map.h, tu, tv);
-            } else if (S.env.use_auto) {
-                radiance = radiance + lerp3(vs(1.0f), V(0.5f, 0.7f, 1.0f), 0.5f * (dir.y + 1.0f));
-            } else {
-                radiance = radiance + V(S.env.color[0], S.env.color[1], S.env.color[2]);
-            }
-            alb = radiance * S.env.intensity;
-        } else { // shade_hit's attribute fetch
-            const size_t slot = (size_t)A.slot_of[(size_t)prim];
-            const PtShade& sh = S.shade[slot];
-            const int mi = S.bvh.tris[slot].material;
-            Material mat = material_default();
-            int32_t tex_slot = -1;
-            if (mi >= 0) {
-                const float* mp = &S.materials[(size_t)mi * PT_MAT_STRIDE];
-                mat = material_load(mp);
-                std::memcpy(&tex_slot, mp + 17, 4);
-            }
-            const float bx = hu, by = hv;
-            const float bw = 1.0f - bx - by;
-            const v3 v_n = normalize(interp3(bw, bx, by, V(sh.n0[0], sh.n0[1], sh.n0[2]), V(sh.n1[0], sh.n1[1], sh.n1[2]), V(sh.n2[0], sh.n2[1], sh.n2[2])));
-            if (finite_(v_n.x) && finite_(v_n.y) && finite_(v_n.z)) nrm = v_n;
-            if (mat.emission > 0.0f) {
-                alb = vs(mat.emission);
-            } else {
-                if (tex_slot >= 0) {
-                    const float tu = fma_(by, sh.tc[4], fma_(bx, sh.tc[2], bw * sh.tc[0]));
-                    const float tv = fma_(by, sh.tc[5], fma_(bx, sh.tc[3], bw * sh.tc[1]));
-                    const HostTexture& tx = S.textures[(size_t)tex_slot];
-                    mat.base_color = tex_nearest(tx.px.data(), tx.w, tx.h, tu, tv);
-                }
-                alb = mat.base_color;
-            }
+        if (!hit) {
+            alb = miss_radiance(S, dir);
+        } else {
+            const AovHit h = fetch_hit(A, prim, hu, hv);
+            if (h.n_ok) nrm = h.v_n;
+            alb = h.emits ? vs(h.mat.emission) : h.mat.base_color;
             alpha = 1.0f;
             depth = t;
         }
@@ -131,14 +158,8 @@ void aov_follow_pixel(const AovScene& A, const pt_aov_params& prm, int px, int p
     uint32_t rng = rng_init((uint32_t)px, (uint32_t)py);
     v3 s_alb = vs(0.0f), s_nrm = vs(0.0f);
     float s_alpha = 0.0f, s_depth = 0.0f;
-    const v3 origin = V(A.cam.origin[0], A.cam.origin[1], A.cam.origin[2]), llc = V(A.cam.llc[0], A.cam.llc[1], A.cam.llc[2]);
-    const v3 hor = V(A.cam.horizontal[0], A.cam.horizontal[1], A.cam.horizontal[2]), ver = V(A.cam.vertical[0], A.cam.vertical[1], A.cam.vertical[2]);
     for (int k = 0; k < A.n; ++k) {
-        const float rx = rng_next(rng); // gen_camera_ray (pt_trace.h)
-        const float ry = rng_next(rng);
-        const float su = ((float)px + rx) / (float)A.W;
-        const float sv = ((float)py + ry) / (float)A.H;
-        v3 o = origin, d = normalize(((llc + hor * su) + ver * sv) - origin);
+        v3 o = A.origin, d = camera_dir(A, px, py, rng);
         v3 tint = vs(1.0f), alb = vs(0.0f), nrm = vs(0.0f);
         float dist = 0.0f, alpha = 0.0f, depth = 0.0f;
         for (int step = 0;; ++step) {
@@ -147,46 +168,17 @@ void aov_follow_pixel(const AovScene& A, const pt_aov_params& prm, int px, int p
             int32_t prim = -1;
             const bool hit = pt_bvh_closest_hit_host(S.bvh, of, df, kTMin, kTMax, &t, &hu, &hv, &prim, A.wt);
             if (step == 0) alpha = hit ? 1.0f : 0.0f; // coverage stays first-hit
-            if (!hit) { // shade_hit's miss branch
-                v3 radiance = vs(0.0f);
-                if (S.env.use_map && S.env_map.w > 0) {
-                    float tu, tv;
-                    uv_on_sphere(d, tu, tv);
-                    radiance = radiance + tex_nearest(S.env_map.px.data(), S.env_map.w, S.env_map.h, tu, tv);
-                } else if (S.env.use_auto) {
-                    radiance = radiance + lerp3(vs(1.0f), V(0.5f, 0.7f, 1.0f), 0.5f * (d.y + 1.0f));
-                } else {
-                    radiance = radiance + V(S.env.color[0], S.env.color[1], S.env.color[2]);
-                }
-                alb = tint * (radiance * S.env.intensity);
+            if (!hit) {
+                alb = tint * miss_radiance(S, d);
                 nrm = vs(0.0f);
                 depth = dist;
                 break;
             }
             dist = dist + t;
-            const size_t slot = (size_t)A.slot_of[(size_t)prim];
-            const PtShade& sh = S.shade[slot];
-            const PtTri& tr = S.bvh.tris[slot];
-            const int mi = tr.material;
-            Material mat = material_default();
-            int32_t tex_slot = -1;
-            if (mi >= 0) {
-                const float* mp = &S.materials[(size_t)mi * PT_MAT_STRIDE];
-                mat = material_load(mp);
-                std::memcpy(&tex_slot, mp + 17, 4);
-            }
-            const float bx = hu, by = hv;
-            const float bw = 1.0f - bx - by;
-            const v3 v_n = normalize(interp3(bw, bx, by, V(sh.n0[0], sh.n0[1], sh.n0[2]), V(sh.n1[0], sh.n1[1], sh.n1[2]), V(sh.n2[0], sh.n2[1], sh.n2[2])));
-            const bool n_ok = finite_(v_n.x) && finite_(v_n.y) && finite_(v_n.z);
-            const bool emits = mat.emission > 0.0f;
-            if (!emits && tex_slot >= 0) {
-                const float tu = fma_(by, sh.tc[4], fma_(bx, sh.tc[2], bw * sh.tc[0]));
-                const float tv = fma_(by, sh.tc[5], fma_(bx, sh.tc[3], bw * sh.tc[1]));
-                const HostTexture& tx = S.textures[(size_t)tex_slot];
-                mat.base_color = tex_nearest(tx.px.data(), tx.w, tx.h, tu, tv);
-            }
-            const int kind = (emits || step == prm.max_follow || !n_ok) ? (int)AOV_NONE : aov_classify(mat, prm.roughness_max);
+            const AovHit h = fetch_hit(A, prim, hu, hv);
+            const Material& mat = h.mat;
+            const v3 v_n = h.v_n;
+            const int kind = (h.emits || step == prm.max_follow || !h.n_ok) ? (int)AOV_NONE : aov_classify(mat, prm.roughness_max);
             if (kind != AOV_NONE) {
                 const v3 wo = -d;
                 v3 wi = vs(0.0f), t2 = tint * mat.base_color;
@@ -199,14 +191,15 @@ void aov_follow_pixel(const AovScene& A, const pt_aov_params& prm, int px, int p
                 else wi = reflect(wo, v_n); // a mirror, or total internal reflection
                 const v3 dn = normalize(wi);
                 if (finite_(dn.x) && finite_(dn.y) && finite_(dn.z)) {
-                    o = interp3(bw, bx, by, V(tr.p0[0], tr.p0[1], tr.p0[2]), V(tr.p1[0], tr.p1[1], tr.p1[2]), V(tr.p2[0], tr.p2[1], tr.p2[2])); // shade_hit's v_p
+                    const PtTri& tr = *h.tr;
+                    o = interp3(h.bw, h.bx, h.by, V(tr.p0[0], tr.p0[1], tr.p0[2]), V(tr.p1[0], tr.p1[1], tr.p1[2]), V(tr.p2[0], tr.p2[1], tr.p2[2])); // shade_hit's v_p
                     d = dn;
                     tint = t2;
                     continue;
                 }
             }
-            alb = tint * (emits ? vs(mat.emission) : mat.base_color);
-            nrm = n_ok ? v_n : vs(0.0f);
+            alb = tint * (h.emits ? vs(mat.emission) : mat.base_color);
+            nrm = h.n_ok ? v_n : vs(0.0f);
             depth = dist;
             break;
         }
@@ -275,7 +268,8 @@ int64_t aov_host(pt_ctx* c, const pt_camera* cam, int32_t W, int32_t H, int32_t 
     sync_host_scene(c);
     AovScene A;
     A.s = &c->scene;
-    A.cam = *cam;
+    A.origin = V(cam->origin[0], cam->origin[1], cam->origin[2]); A.llc = V(cam->llc[0], cam->llc[1], cam->llc[2]);
+    A.hor = V(cam->horizontal[0], cam->horizontal[1], cam->horizontal[2]); A.ver = V(cam->vertical[0], cam->vertical[1], cam->vertical[2]);
     A.W = W; A.H = H; A.n = n_samples;
     A.wt = c->opt.watertight != 0; // the walk follows the option as the render does
     A.slot_of.assign((size_t)c->scene.n_triangles, -1);

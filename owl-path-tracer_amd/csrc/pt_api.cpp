@@ -1,5 +1,5 @@
 // pt_api.cpp -- the C-ABI declared in include/mi355pt.h (host side, HIP runtime): context lifetime, options, statistics, errors, pixel
-// shards and the camera; with pt_scene.cpp (scene), pt_render.cpp (frames), pt_debug.cpp (probes, readers) and pt_comm.cpp (N GPUs).
+// shards and the camera; with pt_scene.cpp (scene), pt_render.cpp (frames), pt_guides.cpp (guide pass, denoiser), pt_debug.cpp (probes, readers) and pt_comm.cpp (N GPUs).
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>

@@ -1,9 +1,10 @@
 // pt_internal.h -- private to the library: the context behind the opaque pt_ctx of include/mi355pt.h and the helpers its host sources
-// share: pt_api.cpp (context, options, stats), pt_scene.cpp (scene upload and clone), pt_render.cpp (frames and batches), pt_debug.cpp
-// (probes and readers) and pt_comm.cpp (RCCL reduce, multi-GPU group).
+// share: pt_api.cpp (context, options, stats), pt_scene.cpp (scene upload and clone), pt_render.cpp (frames and batches), pt_guides.cpp
+// (guide pass and denoiser), pt_debug.cpp (probes and readers) and pt_comm.cpp (RCCL reduce, multi-GPU group).
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -74,7 +75,7 @@ struct QueueKey {
 };
 
 // What a finished frame - or launch sequence of a batch - leaves behind for pt_synchronize, pt_get_stats, the watchdog check and the
-// diagnostics readers.  Written by finish_frame (pt_render.cpp) alone; the readers only take the two pending marks down, and `stream`
+// diagnostics readers.  Written by finish_frame (pt_render.cpp) and note_pass (pt_guides.cpp) alone; the readers only take the two pending marks down, and `stream`
 // belongs to the ordering helpers below (order_after_last, mark_last, wait_idle).
 struct LastFrame {
     bool ev_pending = false;    // ev0 .. ev1 have not been turned into pt_stats.kernel_ms yet
@@ -148,6 +149,12 @@ PT_LOCAL void material_row(const pt_ctx* c, float* dst, const float* src, int i)
 // pt_render.cpp
 int check_watchdog(pt_ctx* c);
 PT_LOCAL void fill_params(pt_ctx* c, PtKernelParams& P);
+PT_LOCAL void walk_params(pt_ctx* c, const pt_camera* cam, PtKernelParams& P);
+PT_LOCAL int check_render_args(pt_ctx* c, int W, int H, int max_samples, int max_depth, const int32_t* n_materials = nullptr);
+PT_LOCAL int64_t batch_max_frames(int W, int H, int max_frames);
+PT_LOCAL int stage_batch_tables(pt_ctx* c, const pt_frame* frames, int n_frames, hipStream_t stream);
+struct D2H { void* dst; const void* src; size_t bytes; }; // a copy to a host buffer of the caller; dst null: none
+PT_LOCAL int drain(pt_ctx* c, std::initializer_list<D2H> copies);
 // pt_denoise_host.cpp
 PT_LOCAL int check_denoise_args(pt_ctx* c, const char* who, int W, int H, const pt_denoise_params* p, pt_denoise_params* eff); // the refusals of pt_denoise* and the twin; *eff = the parameters in effect
 PT_LOCAL void denoise_constants(const pt_denoise_params& p, float* kn, float* ka, float kc[8]); // the definition's host constants
@@ -156,6 +163,28 @@ PT_LOCAL int check_aov_params(pt_ctx* c, const pt_aov_params* p, const char* who
 // pt_comm.cpp
 PT_LOCAL int reduce_framebuffer(pt_ctx* c, void* d_rgb, void* d_rgba8, int64_t n_pixels, hipStream_t stream); // pt_reduce_framebuffer inside a call that is ordered already
 PT_LOCAL int reduce_sum(pt_ctx* c, void* d_buf, size_t n_floats, hipStream_t stream); // in-place sum-reduce onto rank 0; nothing without a communicator
+
+// An asynchronous entry point around `enqueue`: ordered after the context's last asynchronous call on the device, and itself the last
+// one from here on - also when it failed half-way, for what it did enqueue.
+template <class F> int async_call(pt_ctx* c, hipStream_t stream, F enqueue)
+{
+    int rc = order_after_last(c, stream);
+    if (rc) return rc;
+    rc = enqueue();
+    const int rm = mark_last(c, stream);
+    return rc ? rc : rm;
+}
+
+// A blocking render around `run`, which enqueues on the context's stream and drains it: ordered after the last asynchronous call like
+// any other (nothing is added on an idle context or behind a call on the context's own stream).  If it fails, what it did enqueue
+// may still be pending on the context's stream, which is then the last one for the next call to wait for.
+template <class F> int blocking_call(pt_ctx* c, F run)
+{
+    int rc = order_after_last(c, c->stream);
+    if (rc) return rc;
+    if ((rc = run())) (void)mark_last(c, c->stream);
+    return rc;
+}
 } // namespace pti
 
 #define HIP_TRY(c, call)                                                                                   \

@@ -1,5 +1,5 @@
 // pt_launch.h -- prototypes of the kernel launchers (defined in pt_kernel.hip / pt_lbvh.hip, stubbed in pt_nogpu_stubs.cpp for the
-// host-side sanitizer build) as pt_scene.cpp / pt_render.cpp / pt_debug.cpp / pt_comm.cpp call them.  ONE declaration for definition, stub and caller: the functions
+// host-side sanitizer build) as pt_scene.cpp / pt_render.cpp / pt_guides.cpp / pt_debug.cpp / pt_comm.cpp call them.  ONE declaration for definition, stub and caller: the functions
 // have C linkage, so a mismatched parameter list would link and then misbehave (round-3 advisor finding).
 #pragma once
 #include <hip/hip_runtime.h>

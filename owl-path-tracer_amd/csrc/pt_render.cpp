@@ -1,6 +1,6 @@
 // pt_render.cpp -- a frame, from the pixel queue to the read-back: the plan of its launches, its buffers and parameters, the launches,
-// batches of frames (pt_render_batch), the guide pass and the denoiser with their batch forms (pt_render_aov*, pt_denoise*), pt_render / pt_render_device,
-// pt_synchronize and the watchdog check.
+// batches of frames (pt_render_batch), pt_render / pt_render_device, pt_synchronize, the watchdog check and the drain that ends every
+// blocking call (the guide pass and the denoiser are pt_guides.cpp).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -59,6 +59,104 @@ int check_watchdog(pt_ctx* c)
     return PT_OK;
 }
 
+// The scene (fill_params) and the tree walks of the wavefront kernel for a frame from `cam`.
+void walk_params(pt_ctx* c, const pt_camera* cam, PtKernelParams& P)
+{
+    fill_params(c, P);
+    {   // the fma form of the slab test (pt_kernel.hip, node4_step) displaces a plane by |o| 2^-24; the boxes are padded by 1e-5 x the scene
+        // extent (bvh.pad): exact form when the camera is so far from the origin that this would eat a quarter of the padding
+        const float reach = c->scene.bvh.pad * 4194304.0f; // pad x 2^22 = 42 scene extents
+        float far_o = 0.0f;
+        for (int a = 0; a < 3; ++a) far_o = std::max(far_o, std::fabs(cam->origin[a]));
+        P.box_exact = (c->opt.box_exact > 0 || (c->opt.box_exact < 0 && !(far_o <= reach))) ? 1 : 0;
+    }
+    if (c->opt.kernel == 2 && c->opt.quad && !c->scene.nodes4.empty()) { // the wavefront kernel walks the quad nodes: own root and stack bound
+        P.nodes4 = (const PtNode4*)c->d_nodes4.p;
+        P.root = c->scene.root4;
+        P.stack_entries = 3 * c->scene.depth4 + 1;
+    }
+    if (c->opt.kernel == 2 && c->opt.groups && !c->scene.nodes8.empty()) { // group walk of sparse waves (oct nodes)
+        P.nodes8 = (const PtNode8*)c->d_nodes8.p;
+        P.root8 = c->scene.root8;
+        P.groups = c->opt.groups;
+    }
+}
+
+// What pt_render_device and a batch refuse alike, before anything is enqueued.  n_materials: rows of a batch's per-frame tables, compared
+// with the scene's between the two (nullptr: a single frame brings no table).
+int check_render_args(pt_ctx* c, int W, int H, int max_samples, int max_depth, const int32_t* n_materials)
+{
+    if (!c->have_scene) return fail(c, PT_E_NO_SCENE, "no geometries (pt_upload_scene not called)");
+    if (n_materials && *n_materials != c->scene.n_materials) return fail(c, PT_E_INVALID, "pt_render_batch: %d materials per frame, the scene has %d", *n_materials, c->scene.n_materials);
+    if (W <= 0 || H <= 0 || W > 65535 || H > 65535 || max_samples <= 0 || max_depth < 0 || max_depth > 63 || (int64_t)W * H > (int64_t)0x7fffffff)
+        return fail(c, PT_E_INVALID, "bad render size %dx%d spp %d depth %d (depth must be 0..63)", W, H, max_samples, max_depth);
+    return PT_OK;
+}
+
+// ---- batches (pt_render_batch) ------------------------------------------------------------------------------------------
+// K frames of the uploaded scene are stacked into a virtual image of W x (K * H) and rendered by ONE launch sequence over the queue of
+// that image (pt_kernel_batch.hip).  What bounds K, from the code that sets each limit:
+//   * a path slot holds its pixel as x | y << 16 (pt_kernel.hip, S_PIX) and pt_render_device accepts heights up to 65535: K * H <= 65535;
+//   * plan_chunks refuses n_pixels >= 2^24 (the express ticket space): K * W * H < 2^24, taken for the whole frame whatever the rank's
+//     shard, so that every rank of a communicator cuts a batch alike (one reduce per launch sequence on each).  With n_chunks <= 255
+//     this also keeps the (pixel, chunk) tickets below plan_chunks' bound (2^24 * 255 < 0xfff00000);
+//   * option "batch_frames" (> 0).
+int64_t batch_max_frames(int W, int H, int max_frames)
+{
+    if (W <= 0 || H <= 0 || W > 65535 || H > 65535) return 0;
+    int64_t k = 65535 / H;
+    k = std::min<int64_t>(k, ((int64_t)(1 << 24) - 1) / ((int64_t)W * H));
+    if (max_frames > 0) k = std::min<int64_t>(k, max_frames);
+    return k;
+}
+
+// Every frame's camera and material table (the 17 floats of the caller + the context's texture slot per row) in HBM, once per batch:
+// d_batch_cams / d_batch_mats, which pt_render_batch and pt_render_aov_batch share.  The copies go on `stream`, which the caller has
+// ordered after the context's last asynchronous call (async_call / blocking_call) - an earlier batch may still read the tables there -
+// and the call waits for them on the host.
+int stage_batch_tables(pt_ctx* c, const pt_frame* frames, int n_frames, hipStream_t stream)
+{
+    int rc;
+    const size_t row = (size_t)c->scene.n_materials * PT_MAT_STRIDE;
+    c->batch_cams_h.resize((size_t)n_frames * 12);
+    c->batch_mats_h.assign((size_t)n_frames * row, 0.0f);
+    for (int f = 0; f < n_frames; ++f) {
+        std::memcpy(&c->batch_cams_h[(size_t)f * 12], &frames[f].camera, 48);
+        float* dst = c->batch_mats_h.data() + (size_t)f * row;
+        if (!frames[f].materials) { // the context's current table
+            if (row) std::memcpy(dst, c->scene.materials.data(), row * sizeof(float));
+            continue;
+        }
+        for (int i = 0; i < c->scene.n_materials; ++i) material_row(c, dst + (size_t)i * PT_MAT_STRIDE, frames[f].materials + (size_t)i * PT_MAT_FLOATS, i);
+    }
+    if ((rc = ensure(c, c->d_batch_cams, c->batch_cams_h.size() * 4)) || (rc = ensure(c, c->d_batch_mats, c->batch_mats_h.size() * 4))) return rc;
+    HIP_TRY(c, hipMemcpyAsync(c->d_batch_cams.p, c->batch_cams_h.data(), c->batch_cams_h.size() * 4, hipMemcpyHostToDevice, stream));
+    if (row) HIP_TRY(c, hipMemcpyAsync(c->d_batch_mats.p, c->batch_mats_h.data(), c->batch_mats_h.size() * 4, hipMemcpyHostToDevice, stream));
+    HIP_TRY(c, hipStreamSynchronize(stream)); // (as pt_set_materials: the staging vectors are the context's and may be refilled by the next call)
+    return PT_OK;
+}
+
+// The end of every blocking call, after its kernels and its reduce are enqueued on the context's stream: the copies to the caller's host
+// buffers between evr and evd (one with dst null is a buffer this caller does not receive: not the root, no RGBA8 asked for), the drain,
+// the two times of pt_stats and the watchdog.
+int drain(pt_ctx* c, std::initializer_list<D2H> copies)
+{
+    // kernels end (ev1) .. here: this rank's share of the reduce, incl. waiting for the slowest rank (of a batch: the last launch
+    // sequence's reduce; the earlier ones lie inside kernel_ms)
+    HIP_TRY(c, hipEventRecord(c->evr, c->stream));
+    for (const D2H& d : copies)
+        if (d.dst) HIP_TRY(c, hipMemcpyAsync(d.dst, d.src, d.bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipEventRecord(c->evd, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->last.stream = nullptr; // drained: the blocking call was ordered after the last asynchronous one (order_after_last)
+    float ms = 0.0f;
+    HIP_TRY(c, hipEventElapsedTime(&ms, c->ev1, c->evr));
+    c->stats.reduce_ms = ms;
+    HIP_TRY(c, hipEventElapsedTime(&ms, c->evr, c->evd));
+    c->stats.d2h_ms = ms;
+    return check_watchdog(c);
+}
+
 } // namespace pti
 
 namespace {
@@ -114,29 +212,6 @@ Schedule make_schedule(int total, int chunk, int rem_min, int tail_min)
     }
     sc.n_chunks = sc.n_full + n_tail;
     return sc;
-}
-
-// The scene (fill_params) and the tree walks of the wavefront kernel for a frame from `cam`.
-void walk_params(pt_ctx* c, const pt_camera* cam, PtKernelParams& P)
-{
-    fill_params(c, P);
-    {   // the fma form of the slab test (pt_kernel.hip, node4_step) displaces a plane by |o| 2^-24; the boxes are padded by 1e-5 x the scene
-        // extent (bvh.pad): exact form when the camera is so far from the origin that this would eat a quarter of the padding
-        const float reach = c->scene.bvh.pad * 4194304.0f; // pad x 2^22 = 42 scene extents
-        float far_o = 0.0f;
-        for (int a = 0; a < 3; ++a) far_o = std::max(far_o, std::fabs(cam->origin[a]));
-        P.box_exact = (c->opt.box_exact > 0 || (c->opt.box_exact < 0 && !(far_o <= reach))) ? 1 : 0;
-    }
-    if (c->opt.kernel == 2 && c->opt.quad && !c->scene.nodes4.empty()) { // the wavefront kernel walks the quad nodes: own root and stack bound
-        P.nodes4 = (const PtNode4*)c->d_nodes4.p;
-        P.root = c->scene.root4;
-        P.stack_entries = 3 * c->scene.depth4 + 1;
-    }
-    if (c->opt.kernel == 2 && c->opt.groups && !c->scene.nodes8.empty()) { // group walk of sparse waves (oct nodes)
-        P.nodes8 = (const PtNode8*)c->d_nodes8.p;
-        P.root8 = c->scene.root8;
-        P.groups = c->opt.groups;
-    }
 }
 
 // What one frame launches, decided before any buffer is sized (plan_frame).
@@ -463,17 +538,6 @@ int empty_frame(pt_ctx* c, hipStream_t stream, int W, int H, void* d_out_rgb, vo
     return finish_frame(c, stream, W, H, nullptr, 0, first);
 }
 
-// What pt_render_device and a batch refuse alike, before anything is enqueued.  n_materials: rows of a batch's per-frame tables, compared
-// with the scene's between the two (nullptr: a single frame brings no table).
-int check_render_args(pt_ctx* c, int W, int H, int max_samples, int max_depth, const int32_t* n_materials = nullptr)
-{
-    if (!c->have_scene) return fail(c, PT_E_NO_SCENE, "no geometries (pt_upload_scene not called)");
-    if (n_materials && *n_materials != c->scene.n_materials) return fail(c, PT_E_INVALID, "pt_render_batch: %d materials per frame, the scene has %d", *n_materials, c->scene.n_materials);
-    if (W <= 0 || H <= 0 || W > 65535 || H > 65535 || max_samples <= 0 || max_depth < 0 || max_depth > 63 || (int64_t)W * H > (int64_t)0x7fffffff)
-        return fail(c, PT_E_INVALID, "bad render size %dx%d spp %d depth %d (depth must be 0..63)", W, H, max_samples, max_depth);
-    return PT_OK;
-}
-
 // The launches of a planned frame (H: rows of the launch's image, see frame_buffers).  mark_prepass: record evm after the queue sort
 // (a batch does so in its first launch sequence only: pt_stats.prepass_ms).
 int run_launches(pt_ctx* c, const FramePlan& f, PtKernelParams& P, int W, int H, int max_samples, hipStream_t stream, bool mark_prepass)
@@ -496,23 +560,6 @@ int run_launches(pt_ctx* c, const FramePlan& f, PtKernelParams& P, int W, int H,
                            : pt_launch_render(&P, dP, f.variant, grid, f.geo.lds_bytes, stream, f.use_count));
     }
     return PT_OK;
-}
-
-// ---- batches (pt_render_batch) ------------------------------------------------------------------------------------------
-// K frames of the uploaded scene are stacked into a virtual image of W x (K * H) and rendered by ONE launch sequence over the queue of
-// that image (pt_kernel_batch.hip).  What bounds K, from the code that sets each limit:
-//   * a path slot holds its pixel as x | y << 16 (pt_kernel.hip, S_PIX) and pt_render_device accepts heights up to 65535: K * H <= 65535;
-//   * plan_chunks refuses n_pixels >= 2^24 (the express ticket space): K * W * H < 2^24, taken for the whole frame whatever the rank's
-//     shard, so that every rank of a communicator cuts a batch alike (one reduce per launch sequence on each).  With n_chunks <= 255
-//     this also keeps the (pixel, chunk) tickets below plan_chunks' bound (2^24 * 255 < 0xfff00000);
-//   * option "batch_frames" (> 0).
-int64_t batch_max_frames(int W, int H, int max_frames)
-{
-    if (W <= 0 || H <= 0 || W > 65535 || H > 65535) return 0;
-    int64_t k = 65535 / H;
-    k = std::min<int64_t>(k, ((int64_t)(1 << 24) - 1) / ((int64_t)W * H));
-    if (max_frames > 0) k = std::min<int64_t>(k, max_frames);
-    return k;
 }
 
 struct BatchArgs {
@@ -546,32 +593,6 @@ int batch_sequence(pt_ctx* c, const BatchArgs& a, int f0, int K, bool first, voi
     P.materials = (const float*)c->d_batch_mats.p + (size_t)f0 * c->scene.n_materials * PT_MAT_STRIDE;
     if ((rc = run_launches(c, f, P, W, Hv, a.max_samples, stream, first))) return rc;
     return finish_frame(c, stream, W, Hv, &f, P.stack_entries, first);
-}
-
-// Every frame's camera and material table (the 17 floats of the caller + the context's texture slot per row) in HBM, once per batch:
-// d_batch_cams / d_batch_mats, which pt_render_batch and pt_render_aov_batch share.  The copies go on `stream`, which the caller has
-// ordered after the context's last asynchronous call (async_call / blocking_call) - an earlier batch may still read the tables there -
-// and the call waits for them on the host.
-int stage_batch_tables(pt_ctx* c, const pt_frame* frames, int n_frames, hipStream_t stream)
-{
-    int rc;
-    const size_t row = (size_t)c->scene.n_materials * PT_MAT_STRIDE;
-    c->batch_cams_h.resize((size_t)n_frames * 12);
-    c->batch_mats_h.assign((size_t)n_frames * row, 0.0f);
-    for (int f = 0; f < n_frames; ++f) {
-        std::memcpy(&c->batch_cams_h[(size_t)f * 12], &frames[f].camera, 48);
-        float* dst = c->batch_mats_h.data() + (size_t)f * row;
-        if (!frames[f].materials) { // the context's current table
-            if (row) std::memcpy(dst, c->scene.materials.data(), row * sizeof(float));
-            continue;
-        }
-        for (int i = 0; i < c->scene.n_materials; ++i) material_row(c, dst + (size_t)i * PT_MAT_STRIDE, frames[f].materials + (size_t)i * PT_MAT_FLOATS, i);
-    }
-    if ((rc = ensure(c, c->d_batch_cams, c->batch_cams_h.size() * 4)) || (rc = ensure(c, c->d_batch_mats, c->batch_mats_h.size() * 4))) return rc;
-    HIP_TRY(c, hipMemcpyAsync(c->d_batch_cams.p, c->batch_cams_h.data(), c->batch_cams_h.size() * 4, hipMemcpyHostToDevice, stream));
-    if (row) HIP_TRY(c, hipMemcpyAsync(c->d_batch_mats.p, c->batch_mats_h.data(), c->batch_mats_h.size() * 4, hipMemcpyHostToDevice, stream));
-    HIP_TRY(c, hipStreamSynchronize(stream)); // (as pt_set_materials: the staging vectors are the context's and may be refilled by the next call)
-    return PT_OK;
 }
 
 // The whole batch on `stream`; with reduce = true (pt_render_batch) one pt_reduce_framebuffer per launch sequence over all of its frames.
@@ -613,326 +634,10 @@ int batch_device(pt_ctx* c, const pt_frame* frames, int32_t n_frames, int32_t n_
     return PT_OK;
 }
 
-// The end of pt_render and pt_render_batch, after the frames and their reduce are enqueued: npx pixels from d_out / d_out8 to the
-// root's host buffers, the drain, the two times of pt_stats and the watchdog.
+// The end of pt_render and pt_render_batch: npx pixels from d_out / d_out8 to the root's host buffers.
 int read_back(pt_ctx* c, bool root, float* out_rgb, uint32_t* out_rgba8, size_t npx)
 {
-    // kernels end (ev1) .. here: this rank's share of the reduce, incl. waiting for the slowest rank (of a batch: the last launch
-    // sequence's reduce; the earlier ones lie inside kernel_ms)
-    HIP_TRY(c, hipEventRecord(c->evr, c->stream));
-    if (root) {
-        HIP_TRY(c, hipMemcpyAsync(out_rgb, c->d_out.p, npx * 12, hipMemcpyDeviceToHost, c->stream));
-        if (out_rgba8) HIP_TRY(c, hipMemcpyAsync(out_rgba8, c->d_out8.p, npx * 4, hipMemcpyDeviceToHost, c->stream));
-    }
-    HIP_TRY(c, hipEventRecord(c->evd, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    c->last.stream = nullptr; // drained: the blocking call was ordered after the last asynchronous one (order_after_last)
-    float ms = 0.0f;
-    HIP_TRY(c, hipEventElapsedTime(&ms, c->ev1, c->evr));
-    c->stats.reduce_ms = ms;
-    HIP_TRY(c, hipEventElapsedTime(&ms, c->evr, c->evd));
-    c->stats.d2h_ms = ms;
-    return check_watchdog(c);
-}
-
-// ---- guide pass (pt_render_aov) --------------------------------------------------------------------------------------------
-// One launch of the guide kernel over the frame's 8 x 8 pixel blocks; the kernel itself skips the blocks of other ranks' tiles, so the
-// pass needs no pixel queue and none of the render's buffers: it leaves the state of the render path (queue, d_laps, slots) alone.
-// follow != null: the follow kernels (pt_render_aov_follow; prm checked by the caller, check_aov_params) - same refusals, buffers and stats.
-#define PT_AOV_FLAG_WORDS 64 // d_aov_ws: the bound flag on a line of its own, then the overflow columns
-int aov_device(pt_ctx* c, const pt_camera* cam, int W, int H, int n_samples, void* d_out, hipStream_t stream, const pt_aov_params* follow = nullptr)
-{
-    // refusals first: nothing is enqueued or allocated before them
-    const bool quad = c->opt.quad && !c->scene.nodes4.empty();
-    const bool wt = c->opt.watertight != 0;
-    if (!quad && wt)
-        return fail(c, PT_E_INVALID, "%s: without quad nodes (option quad = 0, or a tree too deep for them) the guide pass runs the binary walk, which has no watertight test (option watertight = 1)", follow ? "pt_render_aov_follow" : "pt_render_aov");
-    if (quad && (c->scene.bvh.tris.size() * sizeof(PtTri) > 0xffffffffull || c->scene.nodes4.size() * sizeof(PtNode4) > 0xffffffffull))
-        return fail(c, PT_E_LIMIT, "the guide kernel needs triangle records and quad nodes below 4 GiB each (%zu triangle slots, %zu quad nodes)", c->scene.bvh.tris.size(), c->scene.nodes4.size());
-    PtKernelParams P;
-    walk_params(c, cam, P); // the scene, the slab form ("box_exact" as the render)
-    P.nodes8 = nullptr;
-    P.groups = 0;
-    if (quad) {
-        P.nodes4 = (const PtNode4*)c->d_nodes4.p;
-        P.root = c->scene.root4;
-        P.stack_entries = 3 * c->scene.depth4 + 1;
-    } else {
-        P.nodes4 = nullptr;
-        P.root = c->scene.bvh.root;
-        P.stack_entries = c->scene.bvh.depth < 1 ? 1 : c->scene.bvh.depth;
-    }
-    PtGeometry g{};
-    const hipError_t ge = follow ? (wt ? pt_aov_follow_geometry_wt : pt_aov_follow_geometry)(quad ? 0 : 1, P.box_exact, P.stack_entries, &g)
-                                 : (wt ? pt_aov_geometry_wt : pt_aov_geometry)(quad ? 0 : 1, P.box_exact, P.stack_entries, &g);
-    if (ge == hipErrorInvalidConfiguration) return fail(c, PT_E_LIMIT, "this build of the guide kernel spills registers to scratch; such builds are refused (pt_kernel.hip)");
-    HIP_TRY(c, ge);
-    if (g.max_blocks_per_cu < 1) return fail(c, PT_E_LIMIT, "guide kernel does not fit a CU (LDS %zu bytes, BVH depth %d)", g.lds_bytes, c->scene.bvh.depth);
-    int tile = c->tile < 8 ? 8 : c->tile; // as pt_shard_pixels rounds it
-    tile = (tile + 7) & ~7;
-    if (pt_shard_pixels(W, H, tile, c->rank, c->world, nullptr, 0) < 0) return fail(c, PT_E_INVALID, "invalid pixel shard (%d of %d)", c->rank, c->world);
-    const long n_blocks = (long)((W + 7) / 8) * (long)((H + 7) / 8);
-    const int grid = (int)std::max(1L, std::min(n_blocks, (long)c->num_cus * 32)); // a few rounds of resident waves: the blocks differ in cost
-    PtAovArgs A{};
-    A.cap = quad ? P.stack_entries + 3 : 0;
-    const size_t ovf_words = quad ? (size_t)std::max(0, A.cap - g.lds_levels) * 64 * (size_t)grid : 0;
-    int rc;
-    if ((rc = ensure(c, c->d_aov_ws, (PT_AOV_FLAG_WORDS + ovf_words) * 4))) return rc;
-    HIP_TRY(c, hipMemsetAsync(c->d_aov_ws.p, 0, PT_AOV_FLAG_WORDS * 4, stream));
-    HIP_TRY(c, hipMemsetAsync(d_out, 0, (size_t)W * H * 8 * sizeof(float), stream)); // pixels of other ranks stay 0
-    P.error_flag = (uint32_t*)c->d_aov_ws.p;
-    P.lds_levels = g.lds_levels;
-    std::memcpy(P.cam, cam, sizeof(float) * 12);
-    P.width = W;
-    P.height = H;
-    A.out = (float*)d_out;
-    A.ovf = (uint32_t*)c->d_aov_ws.p + PT_AOV_FLAG_WORDS;
-    A.n_samples = n_samples;
-    A.rank = c->rank; A.world = c->world; A.tile = tile;
-    HIP_TRY(c, hipEventRecord(c->ev0, stream));
-    if (follow) {
-        PtAovFollowArgs F{};
-        F.a = A;
-        F.max_follow = follow->max_follow;
-        F.roughness_max = follow->roughness_max;
-        F.inv_n = 1.0f / (float)n_samples;
-        HIP_TRY(c, (wt ? pt_launch_aov_follow_wt : pt_launch_aov_follow)(&P, &F, quad ? 0 : 1, grid, g.lds_bytes, stream));
-    } else {
-        HIP_TRY(c, (wt ? pt_launch_aov_wt : pt_launch_aov)(&P, &A, quad ? 0 : 1, grid, g.lds_bytes, stream));
-    }
-    // what pt_synchronize and pt_get_stats look at: kernel_ms / launches of this launch (finish_frame is the render's)
-    HIP_TRY(c, hipEventRecord(c->ev1, stream));
-    LastFrame& L = c->last;
-    L.ev_pending = true;
-    L.flag_pending = false;
-    L.aov_flag_pending = true;
-    L.launches = 1;
-    L.sorted = false;
-    L.w = W;
-    L.h = H;
-    L.seqs = 1;
-    c->stats.express_pixels = c->stats.whole_pixels = c->stats.prepass_spp = 0;
-    c->stats.grid = grid;
-    c->stats.vgprs = g.vgprs;
-    c->stats.lds_bytes = (int)g.lds_bytes;
-    c->stats.block = g.block;
-    c->stats.stack_entries = P.stack_entries;
-    return PT_OK;
-}
-
-// ---- guide batch (pt_render_aov_batch) ---------------------------------------------------------------------------------------
-// What the guide batch refuses before anything is touched or enqueued, a host-only context last (who: the entry point; *eff = the
-// parameters in effect).  The tables are staged, the batch is cut and the instances are chosen in aov_batch_device.
-int check_aov_batch_args(pt_ctx* c, const char* who, const pt_frame* frames, int n_frames, int n_materials, int W, int H, const pt_aov_params* p, pt_aov_params* eff)
-{
-    if (n_frames < 1 || !frames) return fail(c, PT_E_INVALID, "%s: a batch needs at least one frame (n_frames %d%s)", who, n_frames, frames ? "" : ", frames NULL");
-    int rc;
-    if ((rc = check_aov_params(c, p, who, eff))) return rc;
-    if (!c->have_scene) return fail(c, PT_E_NO_SCENE, "%s: no geometries (pt_upload_scene not called)", who);
-    if (n_materials != c->scene.n_materials) return fail(c, PT_E_INVALID, "%s: %d materials per frame, the scene has %d", who, n_materials, c->scene.n_materials);
-    if (W <= 0 || H <= 0 || W > 65535 || H > 65535 || (int64_t)W * H > (int64_t)0x7fffffff) return fail(c, PT_E_INVALID, "%s: bad guide pass size %dx%d", who, W, H);
-    if (c->opt.watertight) return fail(c, PT_E_INVALID, "%s: batches have no watertight instances (option watertight = 1); render the guides frame by frame or set watertight = 0", who);
-    int tile = c->tile < 8 ? 8 : c->tile; // as pt_shard_pixels rounds it
-    tile = (tile + 7) & ~7;
-    if (pt_shard_pixels(W, H, tile, c->rank, c->world, nullptr, 0) < 0) return fail(c, PT_E_INVALID, "%s: invalid pixel shard (%d of %d)", who, c->rank, c->world);
-    return need_device(c);
-}
-
-// The guide buffers of frames [0, n_frames) into d_out (W*H*8 floats per frame, back to back): one launch of the batch instances of the
-// follow kernels (pt_kernel_aov_follow_batch.hip) per launch sequence, the batch cut as pt_render_batch cuts it (batch_max_frames).  The
-// blocks of a sequence are those of its frames one after the other; everything per frame - shard, pixel blocks, RNG stream, walk - is
-// aov_device's.  reduce = true (pt_render_aov_batch): ONE sum-reduce per launch sequence over all of its frames.  prm: checked by the caller.
-int aov_batch_device(pt_ctx* c, const pt_frame* frames, int n_frames, int W, int H, const pt_aov_params& prm, void* d_out, hipStream_t stream, bool reduce)
-{
-    const bool quad = c->opt.quad && !c->scene.nodes4.empty();
-    if (quad && (c->scene.bvh.tris.size() * sizeof(PtTri) > 0xffffffffull || c->scene.nodes4.size() * sizeof(PtNode4) > 0xffffffffull))
-        return fail(c, PT_E_LIMIT, "the guide kernel needs triangle records and quad nodes below 4 GiB each (%zu triangle slots, %zu quad nodes)", c->scene.bvh.tris.size(), c->scene.nodes4.size());
-    const int64_t kmax = batch_max_frames(W, H, c->opt.batch_frames);
-    if (kmax < 1) return fail(c, PT_E_LIMIT, "pt_render_aov_batch: one %dx%d frame already exceeds a launch sequence (< 2^24 pixels)", W, H);
-    PtKernelParams P;
-    walk_params(c, &frames[0].camera, P); // the scene; the slab form is chosen per launch sequence below
-    P.nodes8 = nullptr;
-    P.groups = 0;
-    if (quad) {
-        P.nodes4 = (const PtNode4*)c->d_nodes4.p;
-        P.root = c->scene.root4;
-        P.stack_entries = 3 * c->scene.depth4 + 1;
-    } else {
-        P.nodes4 = nullptr;
-        P.root = c->scene.bvh.root;
-        P.stack_entries = c->scene.bvh.depth < 1 ? 1 : c->scene.bvh.depth;
-    }
-    // both slab forms may run in one batch: neither may spill, and they share the launch geometry (block, LDS)
-    PtGeometry g{}, gx{};
-    hipError_t ge = pt_aov_follow_batch_geometry(quad ? 0 : 1, 0, P.stack_entries, &g);
-    if (ge == hipSuccess && quad) ge = pt_aov_follow_batch_geometry(0, 1, P.stack_entries, &gx);
-    if (ge == hipErrorInvalidConfiguration) return fail(c, PT_E_LIMIT, "this build of the batch guide kernel spills registers to scratch; such builds are refused (pt_kernel.hip)");
-    HIP_TRY(c, ge);
-    if (g.max_blocks_per_cu < 1) return fail(c, PT_E_LIMIT, "guide kernel does not fit a CU (LDS %zu bytes, BVH depth %d)", g.lds_bytes, c->scene.bvh.depth);
-    int tile = c->tile < 8 ? 8 : c->tile; // as pt_shard_pixels rounds it
-    tile = (tile + 7) & ~7;
-    const long n_blocks = (long)((W + 7) / 8) * (long)((H + 7) / 8); // of one frame
-    auto grid_of = [&](int K) { return (int)std::max(1L, std::min((long)K * n_blocks, (long)c->num_cus * 32)); }; // as aov_device: a few rounds of resident waves
-    PtAovFollowArgs F{};
-    PtAovArgs& A = F.a;
-    A.cap = quad ? P.stack_entries + 3 : 0;
-    const int k_first = (int)std::min<int64_t>(kmax, n_frames); // the longest sequence has the most workgroups
-    const size_t ovf_words = quad ? (size_t)std::max(0, A.cap - g.lds_levels) * 64 * (size_t)grid_of(k_first) : 0;
-    int rc;
-    if ((rc = ensure(c, c->d_aov_ws, (PT_AOV_FLAG_WORDS + ovf_words) * 4))) return rc;
-    if ((rc = stage_batch_tables(c, frames, n_frames, stream))) return rc;
-    const size_t npx = (size_t)W * H;
-    HIP_TRY(c, hipMemsetAsync(c->d_aov_ws.p, 0, PT_AOV_FLAG_WORDS * 4, stream)); // one bound flag for every sequence
-    HIP_TRY(c, hipMemsetAsync(d_out, 0, (size_t)n_frames * npx * 8 * sizeof(float), stream)); // pixels of other ranks stay 0
-    P.error_flag = (uint32_t*)c->d_aov_ws.p;
-    P.lds_levels = g.lds_levels;
-    std::memcpy(P.cam, &frames[0].camera, sizeof(float) * 12); // (not read: every frame's camera comes from batch_cams)
-    P.width = W;
-    P.height = H;
-    A.ovf = (uint32_t*)c->d_aov_ws.p + PT_AOV_FLAG_WORDS;
-    A.n_samples = prm.n_samples;
-    A.rank = c->rank; A.world = c->world; A.tile = tile;
-    F.max_follow = prm.max_follow;
-    F.roughness_max = prm.roughness_max;
-    F.inv_n = 1.0f / (float)prm.n_samples;
-    HIP_TRY(c, hipEventRecord(c->ev0, stream));
-    int n_seq = 0, vgprs = g.vgprs;
-    for (int f0 = 0; f0 < n_frames; ++n_seq) {
-        const int K = (int)std::min<int64_t>(kmax, n_frames - f0);
-        // one slab form per launch sequence: the subtracting one if ANY of its cameras is beyond the switch of walk_params (batch_sequence)
-        P.box_exact = 0;
-        for (int f = 0; f < K && !P.box_exact; ++f) {
-            PtKernelParams Q;
-            walk_params(c, &frames[f0 + f].camera, Q);
-            P.box_exact = Q.box_exact;
-        }
-        P.batch_frames = K;
-        P.batch_cams = (const float*)c->d_batch_cams.p + (size_t)12 * f0;
-        P.materials = (const float*)c->d_batch_mats.p + (size_t)f0 * c->scene.n_materials * PT_MAT_STRIDE;
-        A.out = (float*)d_out + (size_t)f0 * npx * 8;
-        HIP_TRY(c, pt_launch_aov_follow_batch(&P, &F, quad ? 0 : 1, grid_of(K), g.lds_bytes, stream));
-        if (quad && P.box_exact) vgprs = gx.vgprs;
-        HIP_TRY(c, hipEventRecord(c->ev1, stream)); // (after the last kernel: the earlier sequences' reduces lie inside kernel_ms, as pt_render_batch's)
-        if (reduce && c->comm && (rc = reduce_sum(c, A.out, (size_t)K * npx * 8, stream))) return rc;
-        f0 += K;
-    }
-    // what pt_synchronize and pt_get_stats look at (as aov_device): launches = launch sequences, the geometry of the guide kernel
-    LastFrame& L = c->last;
-    L.ev_pending = true;
-    L.flag_pending = false;
-    L.aov_flag_pending = true;
-    L.launches = n_seq;
-    L.sorted = false;
-    L.w = W;
-    L.h = H;
-    L.seqs = 1; // (d_seq_flags is the render batch's)
-    c->stats.express_pixels = c->stats.whole_pixels = c->stats.prepass_spp = 0;
-    c->stats.grid = grid_of(k_first);
-    c->stats.vgprs = vgprs;
-    c->stats.lds_bytes = (int)g.lds_bytes;
-    c->stats.block = g.block;
-    c->stats.stack_entries = P.stack_entries;
-    return PT_OK;
-}
-
-// ---- denoiser (pt_denoise) -------------------------------------------------------------------------------------------------
-// The filter of pt_denoise.hip over device buffers: prepare, L iteration launches, finish.  It reads no scene and touches none of the
-// render's buffers or state (queue, d_laps, slots): its records live in d_dn_ws.  prm: checked by the caller (check_denoise_args).
-int denoise_device(pt_ctx* c, const void* d_rgb, const void* d_aov, int W, int H, const pt_denoise_params& prm, void* d_out_rgb, void* d_out_rgba8, hipStream_t stream)
-{
-    PtGeometry g{};
-    int grid = 0;
-    const hipError_t ge = pt_denoise_geometry(W, H, &g, &grid);
-    if (ge == hipErrorInvalidConfiguration) return fail(c, PT_E_LIMIT, "this build of the denoise kernels spills registers to scratch; such builds are refused (pt_denoise.hip)");
-    HIP_TRY(c, ge);
-    int rc;
-    if ((rc = ensure(c, c->d_dn_ws, pt_denoise_workspace_bytes(W, H)))) return rc; // (growing it first waits on the host for what is in flight)
-    PtDenoiseArgs A{};
-    A.rgb = (const float*)d_rgb;
-    A.aov = (const float*)d_aov;
-    A.out_rgb = (float*)d_out_rgb;
-    A.out_rgba8 = (uint32_t*)d_out_rgba8;
-    A.ws = c->d_dn_ws.p;
-    A.width = W;
-    A.height = H;
-    A.iterations = prm.iterations;
-    A.flags = prm.flags;
-    A.sigma_depth = prm.sigma_depth;
-    denoise_constants(prm, &A.kn, &A.ka, A.kc);
-    HIP_TRY(c, hipEventRecord(c->ev0, stream));
-    HIP_TRY(c, pt_launch_denoise(&A, stream));
-    // what pt_synchronize and pt_get_stats look at: kernel_ms from the first to the last filter kernel (as aov_device)
-    HIP_TRY(c, hipEventRecord(c->ev1, stream));
-    LastFrame& L = c->last;
-    L.ev_pending = true;
-    L.flag_pending = false;
-    L.aov_flag_pending = false;
-    L.launches = prm.iterations + 2;
-    L.sorted = false;
-    L.w = W;
-    L.h = H;
-    L.seqs = 1;
-    c->stats.express_pixels = c->stats.whole_pixels = c->stats.prepass_spp = 0;
-    c->stats.grid = grid;
-    c->stats.vgprs = g.vgprs;
-    c->stats.lds_bytes = (int)g.lds_bytes;
-    c->stats.block = g.block;
-    c->stats.stack_entries = 0;
-    return PT_OK;
-}
-
-// pt_denoise_batch over device buffers: n_frames frames of W x H, back to back in every buffer, cut into launch sequences as pt_render_batch
-// cuts a batch (batch_max_frames); a sequence is prepare, L iteration launches and finish of pt_denoise_batch.hip over ONE workspace for
-// its frames, the next sequence reuses it in stream order.  prm: checked by the caller.
-int denoise_batch_device(pt_ctx* c, const void* d_rgb, const void* d_aov, int n_frames, int W, int H, const pt_denoise_params& prm, void* d_out_rgb, void* d_out_rgba8, hipStream_t stream)
-{
-    const int64_t kmax = batch_max_frames(W, H, c->opt.batch_frames);
-    if (kmax < 1) return fail(c, PT_E_LIMIT, "pt_denoise_batch: one %dx%d frame already exceeds a launch sequence (< 2^24 pixels)", W, H);
-    const int k_first = (int)std::min<int64_t>(kmax, n_frames);
-    PtGeometry g{};
-    int grid = 0;
-    const hipError_t ge = pt_denoise_batch_geometry(W, H, k_first, &g, &grid);
-    if (ge == hipErrorInvalidConfiguration) return fail(c, PT_E_LIMIT, "this build of the batch denoise kernels spills registers to scratch; such builds are refused (pt_denoise.hip)");
-    HIP_TRY(c, ge);
-    int rc;
-    if ((rc = ensure(c, c->d_dn_ws, pt_denoise_batch_workspace_bytes(W, H, k_first)))) return rc; // (growing it first waits on the host for what is in flight)
-    PtDenoiseArgs A{};
-    A.ws = c->d_dn_ws.p;
-    A.width = W;
-    A.height = H;
-    A.iterations = prm.iterations;
-    A.flags = prm.flags;
-    A.sigma_depth = prm.sigma_depth;
-    denoise_constants(prm, &A.kn, &A.ka, A.kc);
-    const size_t npx = (size_t)W * H;
-    HIP_TRY(c, hipEventRecord(c->ev0, stream));
-    int n_seq = 0;
-    for (int f0 = 0; f0 < n_frames; ++n_seq) {
-        const int K = (int)std::min<int64_t>(kmax, n_frames - f0);
-        A.rgb = (const float*)d_rgb + (size_t)f0 * npx * 3;
-        A.aov = (const float*)d_aov + (size_t)f0 * npx * 8;
-        A.out_rgb = (float*)d_out_rgb + (size_t)f0 * npx * 3;
-        A.out_rgba8 = d_out_rgba8 ? (uint32_t*)d_out_rgba8 + (size_t)f0 * npx : nullptr;
-        HIP_TRY(c, pt_launch_denoise_batch(&A, K, stream));
-        f0 += K;
-    }
-    HIP_TRY(c, hipEventRecord(c->ev1, stream));
-    LastFrame& L = c->last;
-    L.ev_pending = true;
-    L.flag_pending = false;
-    L.aov_flag_pending = false;
-    L.launches = n_seq * (prm.iterations + 2);
-    L.sorted = false;
-    L.w = W;
-    L.h = H;
-    L.seqs = 1;
-    c->stats.express_pixels = c->stats.whole_pixels = c->stats.prepass_spp = 0;
-    c->stats.grid = grid;
-    c->stats.vgprs = g.vgprs;
-    c->stats.lds_bytes = (int)g.lds_bytes;
-    c->stats.block = g.block;
-    c->stats.stack_entries = 0;
-    return PT_OK;
+    return drain(c, {{root ? out_rgb : nullptr, c->d_out.p, npx * 12}, {root ? out_rgba8 : nullptr, c->d_out8.p, npx * 4}});
 }
 
 // One frame on `stream`, which the caller has ordered after the context's last asynchronous call (order_after_last).
@@ -957,244 +662,9 @@ int render_device(pt_ctx* c, const pt_camera* cam, int W, int H, int max_samples
     return finish_frame(c, stream, W, H, &f, P.stack_entries);
 }
 
-// An asynchronous entry point around `enqueue`: ordered after the context's last asynchronous call on the device, and itself the last
-// one from here on - also when it failed half-way, for what it did enqueue.
-template <class F> int async_call(pt_ctx* c, hipStream_t stream, F enqueue)
-{
-    int rc = order_after_last(c, stream);
-    if (rc) return rc;
-    rc = enqueue();
-    const int rm = mark_last(c, stream);
-    return rc ? rc : rm;
-}
-
-// A blocking render around `run`, which enqueues on the context's stream and drains it: ordered after the last asynchronous call like
-// any other (nothing is added on an idle context or behind a call on the context's own stream).  If it fails, what it did enqueue
-// may still be pending on the context's stream, which is then the last one for the next call to wait for.
-template <class F> int blocking_call(pt_ctx* c, F run)
-{
-    int rc = order_after_last(c, c->stream);
-    if (rc) return rc;
-    if ((rc = run())) (void)mark_last(c, c->stream);
-    return rc;
-}
-
 } // namespace
 
 extern "C" {
-
-// The two forms of the guide pass behind their entry points: follow == null is pt_render_aov*, else pt_render_aov_follow* with checked parameters
-static int render_aov_device(pt_ctx* c, const pt_camera* cam, int32_t W, int32_t H, int32_t n_samples, void* d_out_aov, void* stream_v, const pt_aov_params* follow)
-{
-    hipStream_t stream = stream_v ? (hipStream_t)stream_v : c->stream;
-    return async_call(c, stream, [&] { return aov_device(c, cam, W, H, n_samples, d_out_aov, stream, follow); });
-}
-
-int pt_render_aov_device(pt_ctx* c, const pt_camera* cam, int32_t W, int32_t H, int32_t n_samples, void* d_out_aov, void* stream_v)
-{
-    if (!c || !cam || !d_out_aov) return PT_E_INVALID;
-    int rc;
-    if ((rc = need_device(c)) || (rc = check_render_args(c, W, H, n_samples, 0))) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    return render_aov_device(c, cam, W, H, n_samples, d_out_aov, stream_v, nullptr);
-}
-
-int pt_render_aov_follow_device(pt_ctx* c, const pt_camera* cam, int32_t W, int32_t H, const pt_aov_params* p, void* d_out_aov, void* stream_v)
-{
-    if (!c || !cam || !d_out_aov) return PT_E_INVALID;
-    pt_aov_params prm;
-    int rc;
-    if ((rc = need_device(c)) || (rc = check_aov_params(c, p, "pt_render_aov_follow_device", &prm)) || (rc = check_render_args(c, W, H, prm.n_samples, 0))) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    return render_aov_device(c, cam, W, H, prm.n_samples, d_out_aov, stream_v, &prm);
-}
-
-static int render_aov(pt_ctx* c, const pt_camera* cam, int32_t W, int32_t H, int32_t n_samples, float* out_aov, const pt_aov_params* follow);
-
-int pt_render_aov(pt_ctx* c, const pt_camera* cam, int32_t W, int32_t H, int32_t n_samples, float* out_aov)
-{
-    // with a communicator attached only rank 0 receives the buffers (as pt_render)
-    const bool root = !c || !c->comm || c->comm_rank == 0;
-    if (!c || !cam || (root && !out_aov)) return PT_E_INVALID;
-    int rc;
-    if ((rc = need_device(c)) || (rc = check_render_args(c, W, H, n_samples, 0))) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    return render_aov(c, cam, W, H, n_samples, out_aov, nullptr);
-}
-
-int pt_render_aov_follow(pt_ctx* c, const pt_camera* cam, int32_t W, int32_t H, const pt_aov_params* p, float* out_aov)
-{
-    const bool root = !c || !c->comm || c->comm_rank == 0;
-    if (!c || !cam || (root && !out_aov)) return PT_E_INVALID;
-    pt_aov_params prm;
-    int rc;
-    if ((rc = need_device(c)) || (rc = check_aov_params(c, p, "pt_render_aov_follow", &prm)) || (rc = check_render_args(c, W, H, prm.n_samples, 0))) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    return render_aov(c, cam, W, H, prm.n_samples, out_aov, &prm);
-}
-
-static int render_aov(pt_ctx* c, const pt_camera* cam, int32_t W, int32_t H, int32_t n_samples, float* out_aov, const pt_aov_params* follow)
-{
-    const bool root = !c->comm || c->comm_rank == 0;
-    const size_t n_floats = (size_t)W * H * 8;
-    return blocking_call(c, [&]() -> int {
-        int rc;
-        if ((rc = ensure(c, c->d_aov, n_floats * 4))) return rc;
-        if ((rc = aov_device(c, cam, W, H, n_samples, c->d_aov.p, c->stream, follow))) return rc;
-        // N ranks: ONE sum-reduce of the W*H*8 floats onto rank 0; one non-zero contributor per pixel, so the sum is exact
-        if (c->comm && (rc = reduce_sum(c, c->d_aov.p, n_floats, c->stream))) return rc;
-        HIP_TRY(c, hipEventRecord(c->evr, c->stream));
-        if (root) HIP_TRY(c, hipMemcpyAsync(out_aov, c->d_aov.p, n_floats * 4, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipEventRecord(c->evd, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        c->last.stream = nullptr; // drained (as read_back)
-        float ms = 0.0f;
-        HIP_TRY(c, hipEventElapsedTime(&ms, c->ev1, c->evr));
-        c->stats.reduce_ms = ms;
-        HIP_TRY(c, hipEventElapsedTime(&ms, c->evr, c->evd));
-        c->stats.d2h_ms = ms;
-        return check_watchdog(c);
-    });
-}
-
-int pt_denoise_device(pt_ctx* c, const void* d_rgb, const void* d_aov, int32_t W, int32_t H, const pt_denoise_params* p, void* d_out_rgb, void* d_out_rgba8, void* stream_v)
-{
-    if (!c) return PT_E_INVALID;
-    if (!d_rgb || !d_aov || !d_out_rgb) return fail(c, PT_E_INVALID, "pt_denoise_device: NULL %s", !d_rgb ? "d_rgb" : (!d_aov ? "d_aov" : "d_out_rgb"));
-    int rc;
-    pt_denoise_params prm;
-    if ((rc = need_device(c)) || (rc = check_denoise_args(c, "pt_denoise_device", W, H, p, &prm))) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t stream = stream_v ? (hipStream_t)stream_v : c->stream;
-    return async_call(c, stream, [&] { return denoise_device(c, d_rgb, d_aov, W, H, prm, d_out_rgb, d_out_rgba8, stream); });
-}
-
-int pt_denoise(pt_ctx* c, const float* rgb, const float* aov, int32_t W, int32_t H, const pt_denoise_params* p, float* out_rgb, uint32_t* out_rgba8)
-{
-    if (!c) return PT_E_INVALID;
-    if (!rgb || !aov || !out_rgb) return fail(c, PT_E_INVALID, "pt_denoise: NULL %s", !rgb ? "rgb" : (!aov ? "aov" : "out_rgb"));
-    int rc;
-    pt_denoise_params prm;
-    if ((rc = need_device(c)) || (rc = check_denoise_args(c, "pt_denoise", W, H, p, &prm))) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    const size_t npx = (size_t)W * H;
-    return blocking_call(c, [&]() -> int {
-        int rc;
-        if ((rc = ensure(c, c->d_dn_rgb, npx * 12)) || (rc = ensure(c, c->d_dn_aov, npx * 32))) return rc;
-        if (out_rgba8 && (rc = ensure(c, c->d_dn_out8, npx * 4))) return rc;
-        HIP_TRY(c, hipMemcpyAsync(c->d_dn_rgb.p, rgb, npx * 12, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(c->d_dn_aov.p, aov, npx * 32, hipMemcpyHostToDevice, c->stream));
-        if ((rc = denoise_device(c, c->d_dn_rgb.p, c->d_dn_aov.p, W, H, prm, c->d_dn_rgb.p, out_rgba8 ? c->d_dn_out8.p : nullptr, c->stream))) return rc; // in place on the staging copy
-        HIP_TRY(c, hipEventRecord(c->evr, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(out_rgb, c->d_dn_rgb.p, npx * 12, hipMemcpyDeviceToHost, c->stream));
-        if (out_rgba8) HIP_TRY(c, hipMemcpyAsync(out_rgba8, c->d_dn_out8.p, npx * 4, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipEventRecord(c->evd, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        c->last.stream = nullptr; // drained (as read_back)
-        float ms = 0.0f;
-        HIP_TRY(c, hipEventElapsedTime(&ms, c->ev1, c->evr));
-        c->stats.reduce_ms = ms;
-        HIP_TRY(c, hipEventElapsedTime(&ms, c->evr, c->evd));
-        c->stats.d2h_ms = ms;
-        return check_watchdog(c);
-    });
-}
-
-int pt_render_aov_batch_device(pt_ctx* c, const pt_frame* frames, int32_t n_frames, int32_t n_materials, int32_t W, int32_t H, const pt_aov_params* p, void* d_out_aov,
-                               void* stream_v)
-{
-    if (!c) return PT_E_INVALID;
-    if (!d_out_aov) return fail(c, PT_E_INVALID, "pt_render_aov_batch_device: NULL d_out_aov");
-    pt_aov_params prm;
-    int rc;
-    if ((rc = check_aov_batch_args(c, "pt_render_aov_batch_device", frames, n_frames, n_materials, W, H, p, &prm))) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t stream = stream_v ? (hipStream_t)stream_v : c->stream;
-    return async_call(c, stream, [&] { return aov_batch_device(c, frames, n_frames, W, H, prm, d_out_aov, stream, false); });
-}
-
-int pt_render_aov_batch(pt_ctx* c, const pt_frame* frames, int32_t n_frames, int32_t n_materials, int32_t W, int32_t H, const pt_aov_params* p, float* out_aov)
-{
-    if (!c) return PT_E_INVALID;
-    // with a communicator attached only rank 0 receives the buffers (as pt_render_aov)
-    const bool root = !c->comm || c->comm_rank == 0;
-    if (root && !out_aov) return fail(c, PT_E_INVALID, "pt_render_aov_batch: NULL out_aov");
-    pt_aov_params prm;
-    int rc;
-    if ((rc = check_aov_batch_args(c, "pt_render_aov_batch", frames, n_frames, n_materials, W, H, p, &prm))) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    const size_t n_floats = (size_t)n_frames * (size_t)W * (size_t)H * 8;
-    return blocking_call(c, [&]() -> int {
-        int rc;
-        if ((rc = ensure(c, c->d_aov, n_floats * 4))) return rc;
-        // N ranks: one sum-reduce per launch sequence onto rank 0 (aov_batch_device); one non-zero contributor per pixel, so the sum is exact
-        if ((rc = aov_batch_device(c, frames, n_frames, W, H, prm, c->d_aov.p, c->stream, true))) return rc;
-        HIP_TRY(c, hipEventRecord(c->evr, c->stream));
-        if (root) HIP_TRY(c, hipMemcpyAsync(out_aov, c->d_aov.p, n_floats * 4, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipEventRecord(c->evd, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        c->last.stream = nullptr; // drained (as read_back)
-        float ms = 0.0f;
-        HIP_TRY(c, hipEventElapsedTime(&ms, c->ev1, c->evr));
-        c->stats.reduce_ms = ms;
-        HIP_TRY(c, hipEventElapsedTime(&ms, c->evr, c->evd));
-        c->stats.d2h_ms = ms;
-        return check_watchdog(c);
-    });
-}
-
-// What the two forms of the denoise batch refuse alike before anything is touched, a host-only context last.
-static int check_denoise_batch_args(pt_ctx* c, const char* who, int32_t n_frames, int32_t W, int32_t H, const pt_denoise_params* p, pt_denoise_params* eff)
-{
-    if (n_frames < 1) return fail(c, PT_E_INVALID, "%s: a batch needs at least one frame (n_frames %d)", who, n_frames);
-    int rc;
-    if ((rc = check_denoise_args(c, who, W, H, p, eff))) return rc;
-    return need_device(c);
-}
-
-int pt_denoise_batch_device(pt_ctx* c, const void* d_rgb, const void* d_aov, int32_t n_frames, int32_t W, int32_t H, const pt_denoise_params* p, void* d_out_rgb,
-                            void* d_out_rgba8, void* stream_v)
-{
-    if (!c) return PT_E_INVALID;
-    if (!d_rgb || !d_aov || !d_out_rgb) return fail(c, PT_E_INVALID, "pt_denoise_batch_device: NULL %s", !d_rgb ? "d_rgb" : (!d_aov ? "d_aov" : "d_out_rgb"));
-    int rc;
-    pt_denoise_params prm;
-    if ((rc = check_denoise_batch_args(c, "pt_denoise_batch_device", n_frames, W, H, p, &prm))) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t stream = stream_v ? (hipStream_t)stream_v : c->stream;
-    return async_call(c, stream, [&] { return denoise_batch_device(c, d_rgb, d_aov, n_frames, W, H, prm, d_out_rgb, d_out_rgba8, stream); });
-}
-
-int pt_denoise_batch(pt_ctx* c, const float* rgb, const float* aov, int32_t n_frames, int32_t W, int32_t H, const pt_denoise_params* p, float* out_rgb, uint32_t* out_rgba8)
-{
-    if (!c) return PT_E_INVALID;
-    if (!rgb || !aov || !out_rgb) return fail(c, PT_E_INVALID, "pt_denoise_batch: NULL %s", !rgb ? "rgb" : (!aov ? "aov" : "out_rgb"));
-    int rc;
-    pt_denoise_params prm;
-    if ((rc = check_denoise_batch_args(c, "pt_denoise_batch", n_frames, W, H, p, &prm))) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    const size_t npx = (size_t)n_frames * (size_t)W * (size_t)H;
-    return blocking_call(c, [&]() -> int {
-        int rc;
-        if ((rc = ensure(c, c->d_dn_rgb, npx * 12)) || (rc = ensure(c, c->d_dn_aov, npx * 32))) return rc;
-        if (out_rgba8 && (rc = ensure(c, c->d_dn_out8, npx * 4))) return rc;
-        HIP_TRY(c, hipMemcpyAsync(c->d_dn_rgb.p, rgb, npx * 12, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(c->d_dn_aov.p, aov, npx * 32, hipMemcpyHostToDevice, c->stream));
-        if ((rc = denoise_batch_device(c, c->d_dn_rgb.p, c->d_dn_aov.p, n_frames, W, H, prm, c->d_dn_rgb.p, out_rgba8 ? c->d_dn_out8.p : nullptr, c->stream))) return rc; // in place on the staging copy
-        HIP_TRY(c, hipEventRecord(c->evr, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(out_rgb, c->d_dn_rgb.p, npx * 12, hipMemcpyDeviceToHost, c->stream));
-        if (out_rgba8) HIP_TRY(c, hipMemcpyAsync(out_rgba8, c->d_dn_out8.p, npx * 4, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipEventRecord(c->evd, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        c->last.stream = nullptr; // drained (as read_back)
-        float ms = 0.0f;
-        HIP_TRY(c, hipEventElapsedTime(&ms, c->ev1, c->evr));
-        c->stats.reduce_ms = ms;
-        HIP_TRY(c, hipEventElapsedTime(&ms, c->evr, c->evd));
-        c->stats.d2h_ms = ms;
-        return check_watchdog(c);
-    });
-}
 
 int pt_render_device(pt_ctx* c, const pt_camera* cam, int32_t W, int32_t H, int32_t max_samples, int32_t max_depth, void* d_out_rgb,
                      void* d_out_rgba8, void* stream_v)
