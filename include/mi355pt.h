@@ -148,8 +148,11 @@ int pt_update_vertices(pt_ctx* ctx, const pt_mesh* meshes, int32_t n_meshes);
 /* ---- pixel ownership (multi-GPU sharding; no reference counterpart: the reference is single-GPU) ----
  * Default: this context renders every pixel.  Launch-index pixel id = x + W*y (ray_gen's pixelId). */
 int pt_set_pixel_shard(pt_ctx* ctx, int32_t rank, int32_t world_size, int32_t tile);
-/* Host-only helper (no GPU needed): ids owned by `rank` when tile x tile pixel tiles are dealt
- * round-robin in row-major tile order.  Returns the count (writes at most cap ids); <0 on error. */
+/* Host-only helper (no GPU needed): ids owned by `rank` when tile x tile pixel tiles are dealt along the
+ * anti-diagonals: tile (tx, ty), counted from pixel (0, 0), belongs to rank (tx + ty) % world_size.  `tile` is
+ * first rounded up to a multiple of 8, at least 8 (so tiles 1, 4 and 8 deal alike, and 9 deals as 16): the
+ * kernels work in 8 x 8 pixel blocks and a block has one owner.  Returns the count (writes at most cap ids,
+ * tile by tile, inside a tile in 8 x 8 blocks); <0 on error. */
 int64_t pt_shard_pixels(int32_t width, int32_t height, int32_t tile, int32_t rank, int32_t world_size, uint32_t* ids, int64_t cap);
 
 /* ---- render (replaces owlLaunch2D + framebuffer read-back: application.cpp:363-369) ----

@@ -67,7 +67,10 @@ struct AovJob {
 int aov_device(pt_ctx* c, const AovJob& j)
 {
     // refusals first: nothing is enqueued or allocated before them
-    const bool batch = j.frames != nullptr, quad = c->opt.quad && !c->scene.nodes4.empty(), wt = c->opt.watertight != 0;
+    // quad: the quad instances walk the scene - its quad nodes, or a root that is itself a leaf (a scene of a few triangles has no nodes at
+    // all: root4 is the leaf reference, the walk is one leaf step and touches no node).  Only a tree too deep for quad nodes (nodes4
+    // cleared, root4 >= 0) and option quad = 0 leave the binary walk.
+    const bool batch = j.frames != nullptr, quad = c->opt.quad && (!c->scene.nodes4.empty() || c->scene.root4 < 0), wt = c->opt.watertight != 0;
     const int W = j.W, H = j.H, n_frames = batch ? j.n_frames : 1, binary = quad ? 0 : 1;
     hipStream_t stream = j.stream;
     if (!quad && wt)

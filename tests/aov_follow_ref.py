@@ -5,7 +5,8 @@ aov_ref.miss_albedo) - float32 numpy arithmetic, one IEEE operation per numpy op
 imports the library under test.
 
 All samples of a frame advance together, one surface per round; a sample that has stopped keeps its contribution.  samples() also returns
-the log the tests read: every ray walked, the triangle it hit, the kind the surface classified as, the segment lengths."""
+the log the tests read: every ray walked, the triangle it hit, the kind the surface classified as, the segment lengths, and why a sample
+stopped where it stopped."""
 import numpy as np
 
 import aov_ref
@@ -13,6 +14,8 @@ import oracle as orc
 from aov_ref import F32, dot3, fma32, interp3, normalize3
 
 NONE, MIRROR, GLASS = 0, 1, 2
+# log field "stop", per hit: why the sample ended on this surface (the first reason of the definition's order that applies); WENT_ON: it did not
+WENT_ON, STOP_EMITTER, STOP_CAP, STOP_BAD_NORMAL, STOP_CLASSIFIED_NONE, STOP_NON_FINITE_DIRECTION = 0, 1, 2, 3, 4, 5
 # material row (orc.MAT_FLOATS floats): base colour 0..2, metallic 4, roughness 7, clearcoat 11, ior 13, specular_transmission 14,
 # specular_transmission_roughness 15, emission 16
 METALLIC, ROUGHNESS, CLEARCOAT, IOR, SPEC_TRANS, SPEC_TRANS_ROUGHNESS, EMISSION = 4, 7, 11, 13, 14, 15, 16
@@ -53,7 +56,8 @@ def refract(w, n, eta):
 
 def samples(S, flat, env, cam, W, H, n_samples, max_follow, roughness_max, pixel_ids, materials=None):
     """dict(contrib (n_pixels, n_samples, 8), log): log[step] = dict(idx: flat sample indices walked in this round, rays (k, 6), hit, t, prim,
-    kind (of the hit surfaces; -1 on a miss), went_on, tir)."""
+    kind (of the hit surfaces; -1 on a miss), went_on, tir, stop (a STOP_* reason or WENT_ON; -1 on a miss), mat (the material index of the hit
+    triangle, < 0: the defaults; -2 on a miss), tex (the base colour came from a texture lookup), n_ok (the shading normal is finite))."""
     rays0 = aov_ref.camera_rays(cam, W, H, n_samples, pixel_ids)
     shape = rays0.shape[:2]
     n = shape[0] * shape[1]
@@ -71,7 +75,8 @@ def samples(S, flat, env, cam, W, H, n_samples, max_follow, roughness_max, pixel
         rays = np.concatenate([o[active], d[active]], 1).astype(F32)
         hit, t, u, v, prim = S.intersect_n(rays, use_bvh=False)
         entry = dict(idx=active.copy(), rays=rays, hit=hit.copy(), t=t.copy(), prim=prim.copy(), kind=np.full(active.size, -1), went_on=np.zeros(active.size, bool),
-                     tir=np.zeros(active.size, bool))
+                     tir=np.zeros(active.size, bool), stop=np.full(active.size, -1), mat=np.full(active.size, -2), tex=np.zeros(active.size, bool),
+                     n_ok=np.zeros(active.size, bool))
         log.append(entry)
         if step == 0:
             out[active, 3] = np.where(hit, F32(1.0), F32(0.0))  # coverage stays first-hit
@@ -143,6 +148,11 @@ def samples(S, flat, env, cam, W, H, n_samples, max_follow, roughness_max, pixel
         entry["kind"][hi] = kind
         entry["went_on"][hi] = go
         entry["tir"][hi] = (kind == GLASS) & ~through & go
+        entry["stop"][hi] = np.where(go, WENT_ON, np.where(emits, STOP_EMITTER, np.where(step == max_follow, STOP_CAP, np.where(~n_ok, STOP_BAD_NORMAL, np.where(
+            kind == NONE, STOP_CLASSIFIED_NONE, STOP_NON_FINITE_DIRECTION)))))
+        entry["mat"][hi] = mi
+        entry["tex"][hi] = look
+        entry["n_ok"][hi] = n_ok
         active = a[go]
         step += 1
     return dict(contrib=out.reshape(shape + (8,)), log=log, shape=shape)
