@@ -38,14 +38,13 @@ def fma32(a, b, c):
         toward = np.where(d > 0, F32(np.inf), F32(-np.inf)).astype(F32)
         nb = np.nextafter(r, toward)
         tie = (d != 0) & np.isfinite(s) & (2.0 * d == (nb.astype(np.float64) - r.astype(np.float64)))
-    if tie.any():
-        r = r.copy()
-        for i in zip(*np.nonzero(tie)):
-            exact = Fraction(float(a[i])) * Fraction(float(b[i])) + Fraction(float(c[i]))
-            mid = (Fraction(float(r[i])) + Fraction(float(nb[i]))) / 2
-            if exact != mid:  # not a true tie: the side of the midpoint decides (a true tie: numpy's ties-to-even of s already stands)
-                lo, hi = sorted((float(r[i]), float(nb[i])))
-                r[i] = F32(lo if exact < mid else hi)
+        if tie.any():
+            # s is then the midpoint of r and nb, so the exact sum lies on the side of s that the float64 addition's own error points
+            # to: e of Knuth's TwoSum, p + c = s + e exactly (p, c, s finite).  e == 0 is a true tie: numpy's ties-to-even of s stands.
+            t = s - p
+            e = (p - (s - t)) + (c.astype(np.float64) - t)
+            lo, hi = np.minimum(r, nb), np.maximum(r, nb)
+            r = np.where(tie & (e < 0), lo, np.where(tie & (e > 0), hi, r)).astype(F32)
     return r
 
 

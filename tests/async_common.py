@@ -80,6 +80,12 @@ def synchronize(s):
     _ok(hip().hipStreamSynchronize(s), "hipStreamSynchronize")
 
 
+def to_device(ptr, a):
+    """A blocking copy of a host array to a device pointer (an integer)."""
+    a = np.ascontiguousarray(a)
+    _ok(hip().hipMemcpy(C.c_void_p(ptr), a.ctypes.data_as(C.c_void_p), a.nbytes, H2D), "hipMemcpy")
+
+
 class DeviceFrame:
     """Caller-owned output buffers of `frames` frames of W x H: .rgb (frames * H * W * floats float32) and .rgba8 (frames * H * W
     uint32), device pointers as integers, every byte 0xA5 until a call writes it.  read() copies both back (after a synchronize: a

@@ -35,12 +35,28 @@ that this first read refits, and both are held to the box definition of refit_co
 meshes), whichever builder made the tree.  On a mismatch -
 never after an error return - a fresh context uploads the model's state and makes the same call once: the message says whether that
 one agrees with the oracle (stale state from the sequence) or not (a single-call bug), and gives seed, step and the call list.
+
+THE SECOND FAMILY.  draw_guide_sequence(seed) (seeds from GSEED0) draws 8 to 14 steps around the eight entry points of csrc/pt_guides.cpp -
+pt_render_aov_follow, pt_render_aov_batch, pt_denoise, pt_denoise_batch and their _device forms - from the same _Gen and its change
+blocks; its docstring lists the blocks.  The room always has its sphere, glass or metal in three scenes out of four, with roughnesses on
+both sides of the drawn roughness_max.  The model of a follow pass is tests/aov_follow_ref.py with the state's table, environment and
+triangle test, of a guide batch the loop of it with each frame's table, of a filter tests/denoise_ref.py of the MODEL's frame and guide
+buffers (Model.inputs): nothing the library returned reaches it.  The runner gives a blocking filter those inputs; an asynchronous one
+of a chain reads the caller buffers that the two asynchronous calls before it fill - three streams, no synchronize, the library's
+ordering after the context's last asynchronous call is what makes that legal - and any other one reads the model's inputs, copied to HBM
+before the first step.  A filter in place leaves its result in the frame it read, which is then checked through the result only.  A
+buffer no call was to write (the RGBA8 image beside guide buffers or beside a filter without one, everything handed to a refused call)
+must still hold its fill pattern at the end.  After every blocking call of the family pt_get_stats' launches are the header's: 1, L + 2,
+the launch sequences of pt_debug_plan_batch under the current "batch_frames", and sequences * (L + 2).
 """
+import ctypes as C
 import time
 
 import numpy as np
 
+import aov_follow_ref
 import aov_ref
+import denoise_ref
 import ray_battery as rb
 import refit_common as RC
 from owl_path_tracer_amd.pyhost import binding as B, scene_io
@@ -54,9 +70,29 @@ SAMPLE_BUDGET = 200_000  # oracle samples per call (about a quarter of a second 
 SMALL, LARGE = ((9, 17), (6, 11)), ((56, 73), (40, 57))
 RENDER_OPS = ("render", "render_device", "render_batch", "render_batch_device")
 AOV_OPS = ("render_aov", "render_aov_device")
-OBSERVING = RENDER_OPS + AOV_OPS
-ASYNC_OPS = ("render_device", "render_batch_device", "render_aov_device")
+FOLLOW_OPS = ("render_aov_follow", "render_aov_follow_device")
+AOV_BATCH_OPS = ("render_aov_batch", "render_aov_batch_device")
+DENOISE_OPS = ("denoise", "denoise_device")
+DENOISE_BATCH_OPS = ("denoise_batch", "denoise_batch_device")
+FILTER_OPS = DENOISE_OPS + DENOISE_BATCH_OPS
+GUIDE_OPS = FOLLOW_OPS + AOV_BATCH_OPS + FILTER_OPS  # the eight entry points of the second family (draw_guide_sequence)
+OBSERVING = RENDER_OPS + AOV_OPS + GUIDE_OPS
+ASYNC_OPS = ("render_device", "render_batch_device", "render_aov_device") + GUIDE_OPS[1::2]
+BLOCKING_OF = {"render_device": "render", "render_batch_device": "render_batch", "render_aov_device": "render_aov", **{d: b for b, d in zip(GUIDE_OPS[0::2], GUIDE_OPS[1::2])}}
 REFUSED = ("batch_watertight", "update_count", "kernel_watertight", "aov_zero_samples")
+# the second family
+GSEED0 = 20270102
+GUIDE_BUDGET = 2_500   # guide samples per call of the numpy restatement (every round of it is a brute-force walk): n steps down until the call fits
+GUIDE_SAMPLE_BUDGET = 50_000   # oracle samples per call in this family (SAMPLE_BUDGET's kind): its frames are the low-sample ones a filter is for
+FILTER_BUDGET = 4_100  # pixels x iterations per call of the numpy filter (25 taps of a dozen float32-exact fma each): L steps down until the call fits
+MAX_FOLLOW = (0, 1, 4, 8)
+ROUGHNESS_MAX = (0.0, 0.3, 1.0)
+GLASS_ROUGHNESS = (0.0, 0.05, 0.5)   # specular_transmission_roughness of a glass row
+METAL_ROUGHNESS = (0.0, 0.25, 0.6)   # roughness of a metal row: both sets lie on both sides of roughness_max = 0.3
+GUIDE_REFUSED = ("aov_batch_watertight", "follow_max_follow", "aov_batch_materials", "denoise_iterations", "denoise_nan_sigma", "denoise_batch_no_frames")
+GUIDE_LOOKS_AT = ("update_vertices", "set_materials", "set_environment", "set_pixel_shard", "watertight")  # "<kind>!": that change, looked at by a guide pass
+BETWEEN = ("render_aov_follow", "render_aov_batch", "denoise", "denoise_batch")
+SIGMAS = dict(sigma_color=(1.0, 4.0, 16.0), sigma_normal=(0.1, 0.25, 1.0), sigma_depth=(0.05, 0.1, 0.5), sigma_albedo=(0.1, 0.2, 1.0))
 CHANGES = ("update_vertices", "set_materials", "set_environment", "set_pixel_shard", "watertight", "upload")  # the kinds whose effect must show
 # scheduler knobs of the fuzz (tests/test_gpu_fuzz.py PATHS): none may change an image, so the model ignores them
 KNOB_KEYS = {"groups", "whole", "express_permille", "schedule", "chunk_spp", "fallback", "slots_per_wave", "blocks_per_cu", "prepass_spp", "cost_radius", "spp_per_launch",
@@ -126,10 +162,21 @@ def _draw_env(rng, mode=None):
     return dict(use_map=True, intensity=float(rng.uniform(0.3, 2.0)), env_map=_rgba8(rng, int(rng.integers(2, 17)), int(rng.integers(2, 33))))
 
 
-def _draw_upload(rng):
+def _specular(rng, colour):
+    """The sphere's material in the second family: glass or metal in three draws out of four, with a roughness on either side of roughness_max."""
+    kind = int(rng.integers(0, 8))
+    if kind < 3:
+        return scene_io.material(base_color=colour, specular_transmission=1.0, ior=1.5, roughness=0.05, specular_transmission_roughness=float(rng.choice(GLASS_ROUGHNESS)))
+    if kind < 6:
+        return scene_io.material(base_color=colour, metallic=1.0, roughness=float(rng.choice(METAL_ROUGHNESS)))
+    return scene_io.material(base_color=colour) if kind == 6 else scene_io.material(base_color=colour, clearcoat=1.0, clearcoat_gloss=0.8)
+
+
+def _draw_upload(rng, guide=False):
+    """guide: the room of the second family - the sphere is always there, and its material is _specular's."""
     scale = float(10.0 ** rng.uniform(-1.0, 1.5))
     offset = rng.uniform(-1.0, 1.0, 3) * scale * (0.0 if rng.random() < 0.3 else float(rng.uniform(0.0, 3.0)))
-    n_mesh = int(rng.integers(2, 5))
+    n_mesh = int(rng.integers(3, 5)) if guide else int(rng.integers(2, 5))
     n = int(rng.integers(3, 5)) if n_mesh == 2 else int(rng.integers(2, 4))  # 5 * 2 * n^2 wall triangles
     ents = [(_mesh(*_room(n), scale, offset), 0)]
     mats = [scene_io.material(base_color=tuple(rng.uniform(0.3, 0.9, 3)), roughness=float(rng.uniform(0.2, 1.0)))]
@@ -138,9 +185,9 @@ def _draw_upload(rng):
         radius = float(rng.uniform(0.35, 0.55))
         v, nr, tc = _sphere(sub, radius, (rng.uniform(-0.3, 0.3), -0.95 + radius, rng.uniform(-0.3, 0.3)))
         ents.append((_mesh(v, nr, tc, np.arange(v.shape[0]), scale, offset), 1))
-        kind = int(rng.integers(0, 4))
+        kind = 0 if guide else int(rng.integers(0, 4))
         colour = tuple(rng.uniform(0.2, 1.0, 3))
-        mats.append([scene_io.material(base_color=colour, specular_transmission=1.0, ior=1.5, roughness=0.05), scene_io.material(base_color=colour, metallic=1.0, roughness=0.25),
+        mats.append(_specular(rng, colour) if guide else [scene_io.material(base_color=colour, specular_transmission=1.0, ior=1.5, roughness=0.05), scene_io.material(base_color=colour, metallic=1.0, roughness=0.25),
                      scene_io.material(base_color=colour), scene_io.material(base_color=colour, clearcoat=1.0, clearcoat_gloss=0.8)][kind])
     if n_mesh >= 4:
         v, nr, tc = _sphere(0, 0.15, (rng.uniform(-0.4, 0.4), 0.7, rng.uniform(-0.4, 0.4)))
@@ -166,8 +213,9 @@ def _draw_camera(rng, st):
     return [float(x) for x in frm], [float(x) for x in at], up, float(rng.uniform(35.0, 75.0))
 
 
-def _draw_mats(rng, mats):
-    """Another table: the walls' base colour always changes, the other rows half of the time."""
+def _draw_mats(rng, mats, guide=False):
+    """Another table: the walls' base colour always changes, the other rows half of the time.  guide: a glass or metal row also gets another
+    of its roughnesses, which moves it across roughness_max and back."""
     m = np.array(mats, F32)
     m[0, 0:3] = (m[0, [1, 2, 0]] * F32(0.5) + rng.uniform(0.05, 0.45, 3).astype(F32))
     for r in range(1, m.shape[0]):
@@ -177,6 +225,10 @@ def _draw_mats(rng, mats):
             else:
                 m[r, 0:3] = rng.uniform(0.1, 1.0, 3).astype(F32)
                 m[r, 7] = F32(rng.uniform(0.05, 1.0))
+        if guide and m[r, 4] == 1:
+            m[r, 7] = F32(rng.choice(METAL_ROUGHNESS))
+        if guide and m[r, 14] == 1:
+            m[r, 15] = F32(rng.choice(GLASS_ROUGHNESS))
     return m
 
 
@@ -192,7 +244,7 @@ def apply(st, step):
     if op == "upload":
         _geo[0] += 1
         return dict(scene=(step["ents"], step["n_mat"], step["shift"]), meshes=[m for m, _ in step["ents"]], mats=step["mats"], env=step["env"], texs=step["texs"],
-                    mesh_tex=step["mesh_tex"], tex_by_mat=step["tex_by_mat"], shard=st["shard"] if st else None, wt=st["wt"] if st else 0, geo=_geo[0],
+                    mesh_tex=step["mesh_tex"], tex_by_mat=step["tex_by_mat"], shard=st["shard"] if st else None, wt=st["wt"] if st else 0, batch_frames=st.get("batch_frames", 0) if st else 0, geo=_geo[0],
                     scale=step["scale"], centre=step["centre"], builder=step["builder"], leaf=step["leaf"])
     if op == "update_vertices":
         mv = RC.moved(st["scene"], step["k"], with_normals=step["with_normals"])
@@ -212,6 +264,8 @@ def apply(st, step):
         return dict(st, shard=step["shard"])
     if op == "set_option" and step["key"] == "watertight":
         return dict(st, wt=int(step["value"]))
+    if op == "set_option" and step["key"] == "batch_frames":  # (no image depends on it: only the launches that pt_get_stats counts)
+        return dict(st, batch_frames=int(step["value"]))
     return st
 
 
@@ -247,7 +301,12 @@ class Model:
     def __init__(self, orc):
         self.orc = orc
         self._S = {}
+        self._want = {}  # one sequence's outputs by (state, call): a filter asks for its render and guides again, and so does a repeated render
         self.seconds = 0.0
+
+    def forget(self):
+        """Before another sequence: the outputs kept for the last one go."""
+        self._want.clear()
 
     def flat(self, st):
         return self.scene(st)[1]
@@ -275,19 +334,74 @@ class Model:
         """(floats, RGBA8 or None) of an observing step in state st."""
         t0 = time.time()
         try:
-            op, W, H = step["op"], step["W"], step["H"]
-            if op in ("render", "render_device"):
-                return self._frame(st, step["cam"], st["mats"], W, H, step["spp"], step["depth"])
-            if op in ("render_batch", "render_batch_device"):
-                fr = [self._frame(st, cam, st["mats"] if mats is None else mats, W, H, step["spp"], step["depth"]) for cam, mats in step["frames"]]
-                return np.stack([f[0] for f in fr]), np.stack([f[1] for f in fr])
-            assert op in AOV_OPS, op
-            S, flat = self.scene(st)
-            cam = step["cam"]
-            a = aov_ref.aov(S, flat, st["env"], self.orc.to_camera_data(tuple(cam[0]), tuple(cam[1]), tuple(cam[2]), cam[3], W, H).as_array(), W, H, step["n"], materials=st["mats"])
-            return np.where(own_mask(st, W, H)[..., None], a, F32(0.0)), None
+            return self._expected(st, step)
         finally:
             self.seconds += time.time() - t0
+
+    def inputs(self, st, step):
+        """(rgb, guide buffers) of a filter step: the model's own outputs of the two calls the step names (step["src"])."""
+        t0 = time.time()
+        try:
+            return self._expected(st, step["src"]["render"])[0], self._expected(st, step["src"]["guides"])[0]
+        finally:
+            self.seconds += time.time() - t0
+
+    def _expected(self, st, step):
+        key = (_state_key(st), _call_key(step))
+        if key not in self._want:  # (run() and visibility() start with an empty cache: it holds one sequence's outputs)
+            self._want[key] = self._compute(st, step)
+            for a in self._want[key]:
+                if a is not None:
+                    a.flags.writeable = False  # shared among the steps that ask for it
+        return self._want[key]
+
+    def _follow(self, st, cam, mats, W, H, step):
+        S, flat = self.scene(st)
+        a = aov_follow_ref.aov(S, flat, st["env"], self.orc.to_camera_data(tuple(cam[0]), tuple(cam[1]), tuple(cam[2]), cam[3], W, H).as_array(), W, H, step["n"],
+                               step["max_follow"], step["roughness_max"], materials=np.asarray(mats, F32))
+        return np.where(own_mask(st, W, H)[..., None], a, F32(0.0))
+
+    def _compute(self, st, step):
+        op, W, H = step["op"], step["W"], step["H"]
+        if op in ("render", "render_device"):
+            return self._frame(st, step["cam"], st["mats"], W, H, step["spp"], step["depth"])
+        if op in ("render_batch", "render_batch_device"):
+            fr = [self._frame(st, cam, st["mats"] if mats is None else mats, W, H, step["spp"], step["depth"]) for cam, mats in step["frames"]]
+            return np.stack([f[0] for f in fr]), np.stack([f[1] for f in fr])
+        if op in FOLLOW_OPS:
+            return self._follow(st, step["cam"], st["mats"], W, H, step), None
+        if op in AOV_BATCH_OPS:  # the loop of the single-frame restatement with each frame's table
+            return np.stack([self._follow(st, cam, st["mats"] if mats is None else mats, W, H, step) for cam, mats in step["frames"]]), None
+        if op in FILTER_OPS:
+            rgb, aov = self._expected(st, step["src"]["render"])[0], self._expected(st, step["src"]["guides"])[0]
+            if op in DENOISE_OPS:
+                out, out8 = denoise_ref.denoise(rgb, aov, **step["params"])
+            else:
+                fr = [denoise_ref.denoise(rgb[f], aov[f], **step["params"]) for f in range(rgb.shape[0])]
+                out, out8 = np.stack([f[0] for f in fr]), np.stack([f[1] for f in fr])
+            return out, (out8 if step["want_rgba8"] else None)
+        assert op in AOV_OPS, op
+        S, flat = self.scene(st)
+        cam = step["cam"]
+        a = aov_ref.aov(S, flat, st["env"], self.orc.to_camera_data(tuple(cam[0]), tuple(cam[1]), tuple(cam[2]), cam[3], W, H).as_array(), W, H, step["n"], materials=st["mats"])
+        return np.where(own_mask(st, W, H)[..., None], a, F32(0.0)), None
+
+
+def _state_key(st):
+    env = st["env"]
+    return (st["geo"], st["wt"], tuple(st["shard"] or ()), np.asarray(st["mats"], F32).tobytes(),
+            tuple(sorted((k, v.tobytes() if isinstance(v, np.ndarray) else v) for k, v in env.items())))
+
+
+def _call_key(step):
+    """What of a step the model's output depends on (not the form of the call, its stream or its buffers)."""
+    op = BLOCKING_OF.get(step["op"], step["op"])
+    key = (op, step["W"], step["H"], repr(step.get("cam")), step.get("spp"), step.get("depth"), step.get("n"), step.get("max_follow"), step.get("roughness_max"))
+    if "frames" in step:
+        key += tuple((repr(cam), None if mats is None else np.asarray(mats, F32).tobytes()) for cam, mats in step["frames"])
+    if op in ("denoise", "denoise_batch"):
+        key += (repr(sorted(step["params"].items())), step["want_rgba8"], _call_key(step["src"]["render"]), _call_key(step["src"]["guides"]))
+    return key
 
 
 def states_of(seq):
@@ -346,16 +460,17 @@ class _Gen:
         self.steps.append(step)
         self.st = apply(self.st, step)
 
-    def size(self):
+    def size(self, counter="sizes"):
         rng = self.rng
-        (w0, w1), (h0, h1) = (SMALL, LARGE, SMALL)[self.sizes] if self.sizes < 3 else ((8, 73), (6, 57))
-        self.sizes += 1
+        k = getattr(self, counter)
+        (w0, w1), (h0, h1) = (SMALL, LARGE, SMALL)[k] if k < 3 else ((8, 73), (6, 57))
+        setattr(self, counter, k + 1)
         return int(rng.integers(w0, w1)), int(rng.integers(h0, h1))
 
-    def spp(self, W, H, K=1):
+    def spp(self, W, H, K=1, budget=SAMPLE_BUDGET):
         """Depth 1 shows the environment and the emitters only: it is drawn for one frame in ten."""
         i = int(self.rng.integers(0, len(SPP)))
-        while i > 0 and W * H * K * SPP[i] > SAMPLE_BUDGET:
+        while i > 0 and W * H * K * SPP[i] > budget:
             i -= 1
         return SPP[i], int(self.rng.choice(DEPTHS, p=(0.1, 0.4, 0.5)))
 
@@ -426,6 +541,12 @@ class _Gen:
                 step.update(cam=_draw_camera(rng, self.st), W=16, H=12)
             self.add(step)
             return self.render()
+        if self.change(b):
+            self.render()
+
+    def change(self, b):
+        """One change block's change; returns whether an observation is still due (the watertight switch brings its own)."""
+        rng, st = self.rng, self.st
         if b == "update_vertices":
             self.k = self.k % 6 + 1 + int(rng.integers(0, 2))
             null = int(rng.integers(0, len(st["meshes"]))) if rng.random() < 0.4 else None
@@ -442,7 +563,8 @@ class _Gen:
             shard = (int(rng.integers(0, 2)), world, int(rng.choice([1, 8, 16])))
             self.add(dict(op="set_pixel_shard", shard=None if st["shard"] else shard))
         elif b == "watertight":
-            return self.set_wt(1 - st["wt"])
+            self.set_wt(1 - st["wt"])
+            return False
         elif b == "box_exact":
             self.add(dict(op="set_option", key="box_exact", value=int(rng.choice([0, 1]))))
         elif b == "knob":
@@ -452,7 +574,277 @@ class _Gen:
             self.add(_draw_upload(rng))
         else:
             raise KeyError(b)
-        self.render()
+        return True
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the second family: follow guides, batch guides and the denoiser
+# ---------------------------------------------------------------------------------------------------------------------
+def default_guide_seeds(n=N_DEFAULT):
+    return [GSEED0 + i for i in range(n)]
+
+
+def draw_guide_sequence(seed, host_only=False):
+    """8 to 14 steps around pt_render_aov_follow, pt_render_aov_batch, pt_denoise and pt_denoise_batch (blocking and _device forms) on the
+    room of _draw_upload(guide=True).  A change (_Gen.change) or a refused call is looked at by the NEXT step, which is an observation of this
+    family (_GuideGen.render) or the first step of one of these blocks, each step with a form and a stream of its own draw unless said otherwise:
+        denoise_chain  [render, render_aov_follow of the same view, denoise of the two]: all blocking, or all asynchronous with nothing
+                       between the calls - the filter reads the two caller buffers the steps before it fill
+        batch_chain    [render_batch, render_aov_batch, denoise_batch] over the same frames, the same way
+        between        [render, X, the same render again], X = BETWEEN[seed % 4]
+        table_kept     [render_aov_batch with tables of its own, render_aov_follow with the context's table]
+        refused        [one of GUIDE_REFUSED (seed % 6)]
+        batch_frames   [option "batch_frames" = 1 or 2 (0 if it is set), a batch_chain or a guide batch]: the cut must not show
+        filter         [denoise or denoise_batch] of a frame and guides that no call of the sequence made (the model's own)
+    A block that needs watertight = 0 puts [set_option watertight 0, follow pass] in front.  The first three FILTERED sizes of a sequence are
+    small, large, small (frames x W x H grows and shrinks by more than 4 x): the filter's records are reallocated when they grow.  Blocks
+    are generated in a drawn order while they fit (their cost in the state they meet is known); room stays for the refused call and a
+    denoise_chain, which every sequence has."""
+    rng = np.random.default_rng(seed)
+    up = _draw_upload(rng, guide=True)
+    n = max(int(rng.integers(8, 15)), int(rng.integers(8, 15)))  # (the long blocks need room: mostly 11 and more)
+    G = _GuideGen(rng, seed, up)
+    # what a sequence is for goes by its seed, so that any twelve seeds in a row have all of it; the rest is drawn
+    third = (seed // 4) % 3
+    mandatory = ["refused", "denoise_chain"] + [["between"], ["batch_chain"], ["table_kept", "batch_frames"]][third] + (["filter", "filter"] if seed % 2 == 0 else []) + (["upload"] if seed % 4 == 1 else []) + [GUIDE_LOOKS_AT[seed % 5] + "!"]
+    # THE SCHEDULE.  `order` lists block names; a name is generated when its turn comes if it still fits into the n steps.  G.cost(b) is what
+    # b takes in the state it would meet (exact: a pending change costs one observation more, a batch behind watertight = 1 the switch
+    # back).  `mandatory` are this seed's blocks: they are shuffled to the front with three others and fit before anything optional does.
+    special = ["table_kept", "batch_frames", "denoise_chain", "batch_chain", "filter"]
+    other = ["update_vertices", "set_materials", "set_environment", "set_pixel_shard", "watertight", "box_exact", "knob", "observe", "update_vertices", "set_environment", "set_pixel_shard"]
+    special = [special[int(i)] for i in rng.permutation(len(special))]
+    other = [other[int(i)] for i in rng.permutation(len(other))]
+    head = mandatory + other[:3]
+    order = [head[int(i)] for i in rng.permutation(len(head))] + other[3:5] + special[:1] + other[5:] + special[1:]
+    left = list(mandatory)  # mandatory blocks whose turn has not come: an optional block must leave room for them
+    # the two blocks EVERY sequence has are placed whatever came before, so their worst cases (a pending change to look at first, the
+    # switch to watertight = 1 in front of the refused batch) are kept free from the start: 8 steps at most, and n >= 8
+    hard = {"refused": 3 + 2 * (GUIDE_REFUSED[seed % 6] == "aov_batch_watertight"), "denoise_chain": 3}  # in every sequence: their worst cases stay free (8 steps at most)
+    for b in order:
+        due = b in left
+        if due:
+            left.remove(b)
+        room = n - len(G.steps) - sum(hard[m] for m in left if m in hard)
+        if due:  # this seed's own block: in if it fits beside the two reservations
+            if b in hard or G.cost(b) <= room:
+                G.block(b)
+        # an optional block: beside the reservations, room must stay for the seed's blocks still to come, at their present cost - and a
+        # switch to watertight = 1 makes each batch block among them dearer by the switch back (3 steps, once)
+        elif G.cost(b) + sum(G.cost(m) for m in left if m not in hard) + (3 if b == "watertight" and not G.st["wt"] and {"batch_chain", "table_kept", "batch_frames"} & set(left) else 0) <= room:
+            G.block(b)
+    if G.pending:
+        G.render()
+    while len(G.steps) < n:  # fill up: the bounds above are worst cases
+        if n - len(G.steps) >= 2 and rng.random() < 0.6:
+            G.block(CHANGES[int(rng.integers(0, 4))])
+        else:
+            G.block("observe")
+    assert 8 <= len(G.steps) <= 14 and not G.pending, len(G.steps)
+    return dict(seed=seed, family="guide", host_only=bool(host_only), upload=up, steps=G.steps)
+
+
+class _GuideGen(_Gen):
+    def __init__(self, rng, seed, up):
+        _Gen.__init__(self, rng, seed, up)
+        self.filtered = 0  # filter sizes drawn so far: small, large, small, then anything
+        self.bf = 0
+        self.pending = False  # a change or a refused call that no step has looked at yet
+        self.guide_only = False
+
+    def add(self, step):
+        _Gen.add(self, step)
+        self.pending = step["op"] not in OBSERVING
+
+    def cost(self, b):
+        """The steps block b takes in the present state, the observation a change still needs included."""
+        pend, wt = int(self.pending), self.st["wt"]
+        wt0 = (2 + pend) if wt else 0  # [what is pending is looked at], the switch, its follow pass
+        if b in ("denoise_chain", "filter", "observe"):
+            return {"denoise_chain": 3, "filter": 1, "observe": 1}[b]
+        if b in ("batch_chain", "table_kept"):
+            return wt0 + {"batch_chain": 3, "table_kept": 2}[b]
+        if b == "batch_frames":  # a change itself: what is pending is looked at first
+            return 4 + (wt0 if wt else pend)
+        if b == "between":
+            return 3 + (wt0 if BETWEEN[self.seed % 4] == "render_aov_batch" else 0)
+        if b == "refused":
+            return 2 + pend + (2 if (GUIDE_REFUSED[self.seed % 6] == "aov_batch_watertight" and not wt) else 0)
+        return 2 + pend  # a change and what looks at it
+
+    def set_wt(self, v):
+        if self.pending:
+            self.follow()
+        _Gen.set_wt(self, v)
+
+    def form(self):
+        """(asynchronous, stream)"""
+        dev = bool(self.rng.random() < 0.5)
+        return dev, (self.stream() if dev else None)
+
+    def any_size(self):
+        return int(self.rng.integers(8, 73)), int(self.rng.integers(6, 57))
+
+    def spp(self, W, H, K=1, filtered=False):
+        """A frame that is filtered has bounces: at depth 1 it shows the environment and the emitters only, and a filter leaves a flat frame as it is."""
+        spp, depth = _Gen.spp(self, W, H, K, GUIDE_SAMPLE_BUDGET)
+        return spp, (int(self.rng.choice(DEPTHS[1:])) if (filtered and depth == 1) else depth)
+
+    def follow_params(self, W, H, K=1):
+        rng = self.rng
+        n = int(rng.integers(1, 4))
+        while n > 1 and W * H * K * n > GUIDE_BUDGET:
+            n -= 1
+        return dict(n=n, max_follow=int(rng.choice(MAX_FOLLOW)), roughness_max=float(rng.choice(ROUGHNESS_MAX)))
+
+    def filter_params(self, pixels):
+        rng = self.rng
+        L = int(rng.integers(1, 6))
+        while L > 1 and pixels * L > FILTER_BUDGET:
+            L -= 1
+        p = dict(iterations=L, flags=int(rng.integers(0, 2)))
+        for k, v in SIGMAS.items():
+            p[k] = float(rng.choice(v))
+        if rng.random() < 0.3:
+            p[list(SIGMAS)[int(rng.integers(0, 4))]] = float("inf")
+        return p
+
+    def frames(self, K):
+        rng = self.rng
+        null = int(rng.integers(0, K))
+        return [(_draw_camera(rng, self.st), None if f == null else _draw_mats(rng, self.st["mats"], guide=True)) for f in range(K)]
+
+    # ---- single steps
+    def frame(self, W, H, dev=None, stream=None, filtered=False):
+        spp, depth = self.spp(W, H, filtered=filtered)
+        if dev is None:
+            dev, stream = self.form()
+        self.add(dict(op="render_device" if dev else "render", cam=_draw_camera(self.rng, self.st), W=W, H=H, spp=spp, depth=depth, stream=stream))
+
+    def follow(self, cam=None, size=None, form=None):
+        W, H = size or self.any_size()
+        dev, stream = form or self.form()
+        self.add(dict(op=FOLLOW_OPS[dev], cam=cam or _draw_camera(self.rng, self.st), W=W, H=H, stream=stream, **self.follow_params(W, H)))
+
+    aov = follow  # what _Gen.set_wt looks at the switch with: the depth channel is the path length, the sum of the hits' t
+
+    def aov_batch(self, frames=None, size=None, form=None):
+        if self.st["wt"]:
+            self.set_wt(0)
+        W, H = size or self.any_size()
+        frames = frames or self.frames(int(self.rng.integers(2, 4)))
+        dev, stream = form or self.form()
+        self.add(dict(op=AOV_BATCH_OPS[dev], frames=frames, W=W, H=H, stream=stream, **self.follow_params(W, H, len(frames))))
+
+    def filter(self, src=None, chain=False, form=None, batch=None):
+        """A filter step.  src: (render step, guide step), the two steps before it (chain) - else a frame and guides of its own draw."""
+        rng = self.rng
+        if src is None:
+            batch = bool(rng.random() < 0.4) if batch is None else batch
+            W, H = self.size("filtered")
+            if batch:
+                frames = self.frames(int(rng.integers(2, 4)))
+                spp, depth = self.spp(W, H, len(frames), filtered=True)
+                src = (dict(op="render_batch", frames=frames, W=W, H=H, spp=spp, depth=depth, stream=None), dict(op="render_aov_batch", frames=frames, W=W, H=H, stream=None, **self.follow_params(W, H, len(frames))))
+            else:
+                cam = _draw_camera(rng, self.st)
+                spp, depth = self.spp(W, H, filtered=True)
+                src = (dict(op="render", cam=cam, W=W, H=H, spp=spp, depth=depth, stream=None), dict(op="render_aov_follow", cam=cam, W=W, H=H, stream=None, **self.follow_params(W, H)))
+        batch = "frames" in src[0]
+        dev, stream = form or self.form()
+        self.add(dict(op=(DENOISE_BATCH_OPS if batch else DENOISE_OPS)[dev], W=src[0]["W"], H=src[0]["H"], K=len(src[0]["frames"]) if batch else 1, params=self.filter_params(src[0]["W"] * src[0]["H"] * (len(src[0]["frames"]) if batch else 1)),
+                      in_place=bool(rng.random() < 0.5), want_rgba8=bool(rng.random() < 0.5), stream=stream, chain=chain, src=dict(render=src[0], guides=src[1])))
+
+    def render(self, allow_batch=True, allow_aov=True):
+        """One observing step of this family, which is what _Gen's change blocks look at their change with."""
+        r = self.rng.random() * (0.8 if self.guide_only else 1.0)
+        if r < 0.5 or not allow_aov:
+            return self.follow() if allow_aov else self.frame(*self.any_size())
+        if r < 0.8:
+            return self.aov_batch() if (allow_batch and self.st["wt"] == 0) else self.follow()
+        if r < 0.93:
+            return self.frame(*self.any_size())
+        return self.filter()
+
+    # ---- blocks
+    def chain(self, batch, K=None):
+        """[render, guides, filter]: all blocking, or all asynchronous - each on a stream of its own draw, nothing in between."""
+        rng = self.rng
+        if batch and self.st["wt"]:
+            self.set_wt(0)
+        dev = bool(rng.random() < 0.5)
+        form = lambda: (dev, self.stream() if dev else None)
+        W, H = self.size("filtered")
+        if batch:
+            frames = self.frames(K or int(rng.integers(2, 4)))
+            spp, depth = self.spp(W, H, len(frames), filtered=True)
+            d, stream = form()
+            self.add(dict(op="render_batch_device" if d else "render_batch", frames=frames, W=W, H=H, spp=spp, depth=depth, stream=stream))
+            first = self.steps[-1]
+            self.aov_batch(frames, (W, H), form())
+        else:
+            self.frame(W, H, *form(), filtered=True)
+            first = self.steps[-1]
+            self.follow(first["cam"], (W, H), form())
+        self.filter((first, self.steps[-1]), chain=True, form=form())
+
+    def block(self, b):
+        rng, st = self.rng, self.st
+        if b.endswith("!"):
+            self.guide_only = True
+            self.block(b[:-1])
+            self.guide_only = False
+            return
+        if b == "observe":
+            return self.render()
+        if b == "filter":
+            return self.filter()
+        if b == "denoise_chain":
+            return self.chain(False)
+        if b == "batch_chain":
+            return self.chain(True)
+        if b == "between":
+            x = BETWEEN[self.seed % 4]
+            if x == "render_aov_batch" and st["wt"]:
+                self.set_wt(0)
+            self.frame(*self.any_size())
+            first = self.steps[-1]
+            if x == "render_aov_follow":
+                self.follow(first["cam"], (first["W"], first["H"]))
+            elif x == "render_aov_batch":
+                self.aov_batch()
+            else:
+                self.filter(batch=(x == "denoise_batch"))
+            return self.add(dict(first))
+        if b == "table_kept":
+            self.aov_batch()
+            return self.follow()
+        if st["wt"] and b == "batch_frames":
+            self.set_wt(0)
+        elif self.pending and b != "watertight":
+            self.render()  # one change at a time
+        if b == "batch_frames":
+            self.bf = 0 if self.bf else (1 if rng.random() < 0.7 else 2)
+            self.add(dict(op="set_option", key="batch_frames", value=self.bf))
+            return self.chain(True, 3 if self.bf == 1 else None) if rng.random() < 0.8 else self.aov_batch()  # (one frame per launch sequence: three of them)
+        if b == "refused":
+            what = GUIDE_REFUSED[self.seed % 6]
+            if what == "aov_batch_watertight" and not st["wt"]:
+                self.set_wt(1)
+            dev, stream = self.form()
+            step = dict(op="refused", what=what, dev=dev, stream=stream, W=16, H=12)
+            if what in ("aov_batch_watertight", "aov_batch_materials"):
+                step.update(frames=self.frames(2))
+            elif what == "follow_max_follow":
+                step.update(cam=_draw_camera(rng, self.st))
+            return self.add(step)
+        if b == "upload":
+            self.k = 0
+            self.add(_draw_upload(rng, guide=True))
+        elif b == "set_materials":
+            self.add(dict(op="set_materials", mats=_draw_mats(rng, st["mats"], guide=True)))
+        elif not self.change(b):
+            return
+        self.render()  # a change is looked at right away, mostly by a guide pass
 
 
 def kind_of(step):
@@ -480,19 +872,30 @@ def describe(step):
     if op == "knob":
         return "set_option " + " ".join("%s=%d" % kv for kv in step["options"])
     if op == "refused":
-        return "refused: " + step["what"]
+        return "refused: " + step["what"] + ("" if "dev" not in step else " (blocking)" if not step["dev"] else " (_device on %s)" % _stream_name(step["stream"]))
     if op in OBSERVING:
         s = "%s %dx%d" % (op, step["W"], step["H"])
         if op in AOV_OPS:
             s += " n=%d" % step["n"]
+        elif op in FOLLOW_OPS + AOV_BATCH_OPS:
+            s += " n=%d max_follow=%d roughness_max=%g" % (step["n"], step["max_follow"], step["roughness_max"])
+        elif op in FILTER_OPS:
+            p = step["params"]
+            s += "%s L=%d flags=%d sigmas %g %g %g %g%s%s of %s" % (" %d frames" % step["K"] if op in DENOISE_BATCH_OPS else "", p["iterations"], p["flags"], p["sigma_color"], p["sigma_normal"],
+                                                                p["sigma_depth"], p["sigma_albedo"], ", in place" if step["in_place"] else "", ", RGBA8" if step["want_rgba8"] else "",
+                                                                "the two steps before" if step["chain"] else "[%s] and [%s]" % (describe(step["src"]["render"]), describe(step["src"]["guides"])))
         else:
             s += " %d spp depth %d" % (step["spp"], step["depth"])
         if "frames" in step:
             s += " %d frames (table of frame %d NULL)" % (len(step["frames"]), [m is None for _, m in step["frames"]].index(True))
         if op in ASYNC_OPS:
-            s += " on %s" % ("the context's stream" if step["stream"] is None else "caller stream %d" % step["stream"])
+            s += " on %s" % _stream_name(step["stream"])
         return s
     return op
+
+
+def _stream_name(stream):
+    return "the context's stream" if stream is None else "caller stream %d" % stream
 
 
 def call_list(seq, upto=None):
@@ -538,11 +941,79 @@ def coverage(seqs):
     return cov
 
 
+def guide_coverage(seqs):
+    """What sequences of the second family contain between them; tests/test_sequences_host.py asserts the issue's conditions on it."""
+    cov = dict(ops={o: 0 for o in GUIDE_OPS}, streams={o: set() for o in GUIDE_OPS[1::2]}, async_chains_mixed=0, async_batch_chains=0, in_place={(b, v): 0 for b in (False, True) for v in (False, True)},
+               filters=[], growth_and_shrink=0, max_follow=set(), roughness_max=set(), refused=set(), table_kept=0, between=set(), bf1_before_k3_chain=0, followed={k: 0 for k in CHANGES}, upload_mid=0,
+               glass_or_metal=0, inf_sigma=0, iterations=set(), demodulate=set(), null_table=0)
+    for seq in seqs:
+        steps, bf, px, grow, shrink, nf = seq["steps"], 0, None, 0, 0, 0
+        m = seq["upload"]["mats"][1]
+        cov["glass_or_metal"] += bool(m[4] == 1 or m[14] == 1)
+        for i, s in enumerate(steps):
+            op = s["op"]
+            nxt = steps[i + 1] if i + 1 < len(steps) else None
+            if op in GUIDE_OPS:
+                cov["ops"][op] += 1
+                if op in ASYNC_OPS:
+                    cov["streams"][op].add(s["stream"])
+            if op in FOLLOW_OPS + AOV_BATCH_OPS:
+                cov["max_follow"].add(s["max_follow"])
+                cov["roughness_max"].add(s["roughness_max"])
+            if op in AOV_BATCH_OPS:
+                cov["null_table"] += sum(mats is None for _, mats in s["frames"]) == 1
+                cov["table_kept"] += bool(nxt and nxt["op"] in FOLLOW_OPS and any(mats is not None for _, mats in s["frames"]))
+            if op == "set_option" and s["key"] == "batch_frames":
+                bf = s["value"]
+            if op == "upload":
+                cov["upload_mid"] += 1
+            if op == "refused":
+                cov["refused"].add(s["what"])
+            if op in GUIDE_OPS and 0 < i and nxt and steps[i - 1]["op"] in ("render", "render_device") and nxt == steps[i - 1] and not s.get("chain"):
+                cov["between"].add(BLOCKING_OF.get(op, op))
+            if op in FILTER_OPS:
+                batch = op in DENOISE_BATCH_OPS
+                cov["in_place"][(batch, s["in_place"])] += 1
+                cov["inf_sigma"] += any(np.isinf(v) for v in s["params"].values())
+                cov["iterations"].add(s["params"]["iterations"])
+                cov["demodulate"].add(s["params"]["flags"])
+                now = s["K"] * s["W"] * s["H"]
+                if px is not None:
+                    grow += now >= 4 * px
+                    shrink += 4 * now <= px
+                px, nf = now, nf + 1
+                if s["chain"] and op in ASYNC_OPS:
+                    assert steps[i - 1]["op"] in ASYNC_OPS and steps[i - 2]["op"] in ASYNC_OPS
+                    if batch:
+                        cov["async_batch_chains"] += 1
+                    else:
+                        cov["async_chains_mixed"] += len({steps[j]["stream"] for j in (i - 2, i - 1, i)}) > 1
+                if s["chain"] and batch and s["K"] == 3 and bf == 1:
+                    cov["bf1_before_k3_chain"] += 1
+            kind = kind_of(s)
+            if kind is not None and nxt and nxt["op"] in FOLLOW_OPS + AOV_BATCH_OPS:
+                cov["followed"][kind] += 1
+        cov["filters"].append((seq["seed"], nf, grow, shrink))
+        cov["growth_and_shrink"] += grow >= 1 and shrink >= 1
+    return cov
+
+
 def visibility(seq, model):
     """With the oracle alone: (shown, hidden, frames, flat).  A change is VISIBLE if the oracle's output of the next observing step differs
     from what that step shows in the state before the change (the generator puts nothing but a refused call between the two).  shown:
     visible changes per kind of CHANGES; hidden: [(step, kind)]; frames: observing steps; flat: those whose output is one constant pixel."""
+    return _visibility(seq, model)[:4]
+
+
+def guide_visibility(seq, model):
+    """visibility() and, for the second family: follow = (observations of the follow kernels, those whose expected buffer differs from the
+    same call with max_follow = 0); filters = [(step, share of the owned pixels in which the filter's output differs from its input)]."""
+    return _visibility(seq, model)
+
+
+def _visibility(seq, model):
     steps, states = seq["steps"], states_of(seq)
+    model.forget()
     want = {}
 
     def expected(j):
@@ -550,13 +1021,20 @@ def visibility(seq, model):
             want[j] = model.expected(states[j], steps[j])
         return want[j]
 
-    shown, hidden, frames, flat = {k: 0 for k in CHANGES}, [], 0, []
+    shown, hidden, frames, flat, follow, filters = {k: 0 for k in CHANGES}, [], 0, [], [0, 0], []
     for i, s in enumerate(steps):
         if s["op"] in OBSERVING:
             frames += 1
             a = expected(i)[0]
             if (a == a.reshape(-1, a.shape[-1])[0]).all():
                 flat.append(i)
+        if s["op"] in FOLLOW_OPS + AOV_BATCH_OPS:
+            follow[0] += 1
+            follow[1] += bool(same(expected(i)[0], model.expected(states[i], dict(s, max_follow=0))[0]).any())
+        if s["op"] in FILTER_OPS:
+            own = np.stack([own_mask(states[i], s["W"], s["H"])] * s["K"]).reshape(expected(i)[0].shape[:-1])
+            diff = same(expected(i)[0], model.inputs(states[i], s)[0]).any(-1)
+            filters.append((i, float((diff & own).sum()) / max(1, int(own.sum()))))
         kind = kind_of(s)
         if kind is None:
             continue
@@ -568,7 +1046,7 @@ def visibility(seq, model):
             shown[kind] += 1
         else:
             hidden.append((i, kind))
-    return shown, hidden, frames, flat
+    return shown, hidden, frames, flat, tuple(follow), filters
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -617,8 +1095,64 @@ def expect_refusal(fn, what):
     raise AssertionError("%s: the call was accepted" % what)
 
 
-def refused_call(ctx, st, step, host_only=False):
+def _follow_params(step, **changes):
+    return B.aov_default_params(**dict(dict(n_samples=step.get("n", 1), max_follow=step.get("max_follow", 4), roughness_max=step.get("roughness_max", 0.3)), **changes))
+
+
+def _filter_params(step, **changes):
+    return B.denoise_default_params(**dict(step["params"], **changes))
+
+
+def _refused_into(ctx, what, call, shape):
+    """A blocking guide call that must be refused, through its C entry point with an output array of the caller's: PT_E_INVALID, and the
+    array as it was."""
+    out = np.full(shape, 0.25, F32)
+    rc = int(call(out.ctypes.data_as(C.POINTER(C.c_float))))
+    assert rc == -1, "%s: the call returned %d, not PT_E_INVALID (%s)" % (what, rc, B.lib().pt_last_error(ctx._h).decode())
+    assert (out == F32(0.25)).all(), "%s: the refused call wrote to its output" % what
+
+
+def guide_refused_call(ctx, st, step, host_only=False, frame=None, stream=None):
+    """The refused calls of the second family: PT_E_INVALID, on a host-only context too (through the twin where the call has one; the batch
+    forms check their arguments before they ask for the device).  frame: the caller buffers of the _device form (a DeviceFrame the
+    runner reads back at the end: not a byte of it may change); the blocking filters get an in_place frame that must stay as it is."""
+    what, W, H = step["what"], step["W"], step["H"]
+    dev = step["dev"] and not host_only
+    n_mat = st["mats"].shape[0]
+    if what in ("aov_batch_watertight", "aov_batch_materials"):
+        frames = [(_bcam(cam, W, H), mats) for cam, mats in step["frames"]]
+        n_mat += what == "aov_batch_materials"
+        if dev:
+            return expect_refusal(lambda: ctx.render_aov_batch_device(frames, W, H, frame.rgb, None, stream=stream, n_materials=n_mat), what)
+        arr, _, keep = B._marshal_frames(frames)
+        return _refused_into(ctx, what, lambda out: B.lib().pt_render_aov_batch(ctx._h, arr, len(frames), n_mat, W, H, None, out), (len(frames), H, W, 8))
+    if what == "follow_max_follow":
+        cam, p = _bcam(step["cam"], W, H), B.aov_default_params(max_follow=9)
+        if dev:
+            return expect_refusal(lambda: ctx.render_aov_follow_device(cam, W, H, frame.rgb, p, stream=stream), what)
+        if host_only:
+            ids = np.arange(W * H, dtype=np.uint32)
+            return _refused_into(ctx, what, lambda out: B.lib().pt_debug_aov_follow_host(ctx._h, C.byref(cam), W, H, C.byref(p), ids.ctypes.data_as(C.POINTER(C.c_uint32)), ids.size, out), (H, W, 8))
+        return _refused_into(ctx, what, lambda out: B.lib().pt_render_aov_follow(ctx._h, C.byref(cam), W, H, C.byref(p), out), (H, W, 8))
+    rgb, aov = np.full((2, H, W, 3), 0.25, F32), np.zeros((2, H, W, 8), F32)
+    if what == "denoise_batch_no_frames":
+        if dev:
+            return expect_refusal(lambda: ctx.denoise_batch_device(frame.rgb, frame.rgb, 0, W, H, frame.rgb, None, d_out_rgba8=frame.rgba8, stream=stream), what)
+        expect_refusal(lambda: ctx.denoise_batch(rgb[:0], aov[:0], None, want_rgba8=True, in_place=True), what)
+    else:
+        p = B.denoise_default_params(iterations=0) if what == "denoise_iterations" else B.denoise_default_params(sigma_normal=float("nan"))
+        if dev:
+            return expect_refusal(lambda: ctx.denoise_device(frame.rgb, frame.rgb, W, H, frame.rgb, p, d_out_rgba8=frame.rgba8, stream=stream), what)
+        expect_refusal(lambda: (ctx.denoise_host if host_only else ctx.denoise)(rgb[0], aov[0], p, want_rgba8=True, in_place=True), what)
+        if host_only:  # the batch form: its arguments first, the device last
+            expect_refusal(lambda: ctx.denoise_batch(rgb, aov, p, in_place=True), what)
+    assert (rgb == F32(0.25)).all(), "%s: the refused call wrote to its frame" % what
+
+
+def refused_call(ctx, st, step, host_only=False, frame=None, stream=None):
     what = step["what"]
+    if what in GUIDE_REFUSED:
+        return guide_refused_call(ctx, st, step, host_only, frame, stream)
     if what == "batch_watertight":
         frames = [(_bcam(cam, step["W"], step["H"]), mats) for cam, mats in step["frames"]]
         return expect_refusal(lambda: ctx.render_batch(frames, step["W"], step["H"], step["spp"], step["depth"], n_materials=st["mats"].shape[0]), what)
@@ -636,8 +1170,10 @@ def refused_call(ctx, st, step, host_only=False):
     return expect_refusal(lambda: ctx.render_aov(cam, step["W"], step["H"], 0), what)
 
 
-def observe(ctx, step, n_mat, bufs=None, A=None):
-    """The observing call.  Blocking: returns (floats, RGBA8 or None).  Asynchronous: enqueues into bufs (a DeviceFrame) and returns None."""
+def observe(ctx, step, n_mat, bufs=None, A=None, inputs=None, filter_on=None):
+    """The observing call.  Blocking: returns (floats, RGBA8 or None).  Asynchronous: enqueues into bufs (a DeviceFrame) and returns None.
+    A filter step - blocking: inputs = (rgb, guide buffers), host arrays that stay as they are; asynchronous: bufs = (d_rgb, d_aov, the
+    DeviceFrame of the result).  filter_on: the context that filters (pt_denoise has no group form), default ctx."""
     op, W, H = step["op"], step["W"], step["H"]
     stream = A.stream(step["stream"]) if (A is not None and step.get("stream") is not None) else None
     if op == "render":
@@ -651,26 +1187,60 @@ def observe(ctx, step, n_mat, bufs=None, A=None):
         return ctx.render_batch_device(frames, W, H, step["spp"], step["depth"], bufs.rgb, bufs.rgba8, stream=stream, n_materials=n_mat)
     if op == "render_aov":
         return ctx.render_aov(_bcam(step["cam"], W, H), W, H, step["n"]), None
+    if op == "render_aov_follow":
+        return ctx.render_aov_follow(_bcam(step["cam"], W, H), W, H, _follow_params(step)), None
+    if op == "render_aov_follow_device":
+        return ctx.render_aov_follow_device(_bcam(step["cam"], W, H), W, H, bufs.rgb, _follow_params(step), stream=stream)
+    if op in AOV_BATCH_OPS:
+        frames = [(_bcam(cam, W, H), mats) for cam, mats in step["frames"]]
+        if op == "render_aov_batch":
+            return ctx.render_aov_batch(frames, W, H, _follow_params(step), n_materials=n_mat), None
+        return ctx.render_aov_batch_device(frames, W, H, bufs.rgb, _follow_params(step), stream=stream, n_materials=n_mat)
+    if op in ("denoise", "denoise_batch"):
+        rgb = np.array(inputs[0], F32) if step["in_place"] else inputs[0]  # (the model's frame is shared: in place works on a copy)
+        out, out8 = getattr(filter_on or ctx, op)(rgb, inputs[1], _filter_params(step), want_rgba8=step["want_rgba8"], in_place=step["in_place"])
+        assert not step["in_place"] or out is rgb
+        return out, out8
+    if op in ("denoise_device", "denoise_batch_device"):
+        d_rgb, d_aov, out = bufs
+        if op == "denoise_device":
+            return ctx.denoise_device(d_rgb, d_aov, W, H, out.rgb, _filter_params(step), d_out_rgba8=out.rgba8 if step["want_rgba8"] else None, stream=stream)
+        return ctx.denoise_batch_device(d_rgb, d_aov, step["K"], W, H, out.rgb, _filter_params(step), d_out_rgba8=out.rgba8 if step["want_rgba8"] else None, stream=stream)
     assert op == "render_aov_device", op
     return ctx.render_aov_device(_bcam(step["cam"], W, H), W, H, step["n"], bufs.rgb, stream=stream)
 
 
 def _device_frame(A, step):
-    if step["op"] == "render_aov_device":
-        return A.DeviceFrame(step["W"], step["H"], floats=8)
-    return A.DeviceFrame(step["W"], step["H"], frames=len(step.get("frames", [0])))
+    """The caller buffers a _device step writes (a refused one: must leave alone)."""
+    if step["op"] == "refused":
+        return A.DeviceFrame(step["W"], step["H"], frames=2, floats=8)
+    if step["op"] in ("render_aov_device", "render_aov_follow_device", "render_aov_batch_device"):
+        return A.DeviceFrame(step["W"], step["H"], frames=len(step.get("frames", [0])), floats=8)
+    return A.DeviceFrame(step["W"], step["H"], frames=step["K"] if step["op"] in FILTER_OPS else len(step.get("frames", [0])))
 
 
-def fresh_agrees(st, step, want):
-    """One more comparison after a mismatch: a fresh context, the model's state, the same call (blocking form of it)."""
+def expected_launches(st, step):
+    """stats()["launches"] after a blocking call of the second family (include/mi355pt.h): the cut is pt_debug_plan_batch's."""
+    op = step["op"]
+    if op == "render_aov_follow":
+        return 1
+    if op == "denoise":
+        return step["params"]["iterations"] + 2
+    seqs = len(B.plan_batch(step["W"], step["H"], step["K"] if op == "denoise_batch" else len(step["frames"]), st.get("batch_frames", 0)))
+    return seqs if op == "render_aov_batch" else seqs * (step["params"]["iterations"] + 2)
+
+
+def fresh_agrees(st, step, want, inputs=None):
+    """One more comparison after a mismatch: a fresh context, the model's state, the same call (blocking form of it; a filter gets the
+    model's inputs)."""
     ctx = B.Context(0)
     try:
         ctx.set_option("watertight", st["wt"])
         upload(ctx, st)
         if st["shard"]:
             ctx.set_pixel_shard(*st["shard"])
-        blocking = dict(step, op={"render_device": "render", "render_batch_device": "render_batch", "render_aov_device": "render_aov"}.get(step["op"], step["op"]))
-        got = observe(ctx, blocking, st["mats"].shape[0])
+        blocking = dict(step, op=BLOCKING_OF.get(step["op"], step["op"]))
+        got = observe(ctx, blocking, st["mats"].shape[0], inputs=inputs)
         return not same(got[0], want[0]).any() and (want[1] is None or not same(got[1], want[1]).any())
     finally:
         ctx.close()
@@ -683,10 +1253,12 @@ def run(ctx, seq, model, upto=None, A=None, diagnose=True, log=None):
     synchronize)."""
     steps = seq["steps"][:upto]
     host = seq["host_only"]
+    model.forget()
     assert host == (A is None)
-    where = lambda i: "sequence seed=%d, step %d (%s)" % (seq["seed"], i, describe(steps[i]))
-    bufs, pending, got_all = {}, [], []
+    where = lambda i: "%ssequence seed=%d, step %d (%s)" % (seq.get("family", "") and seq["family"] + " ", seq["seed"], i, describe(steps[i]))
+    bufs, pending, got_all, outs = {}, [], [], {}
     t_gpu = 0.0
+    poison = np.uint32(0xA5A5A5A5)
 
     def check(i, st, got, want):
         bad = same(got[0], want[0])
@@ -695,7 +1267,7 @@ def run(ctx, seq, model, upto=None, A=None, diagnose=True, log=None):
             return
         verdict = ""
         if diagnose and not host:
-            ok = fresh_agrees(st, steps[i], want)
+            ok = fresh_agrees(st, steps[i], want, model.inputs(st, steps[i]) if steps[i]["op"] in FILTER_OPS else None)
             verdict = ("; a FRESH context in the model's state agrees with the oracle: STALE STATE from the sequence" if ok else
                        "; a fresh context in the model's state differs from the oracle as well: a SINGLE-CALL bug")
         first = tuple(np.argwhere(bad)[0]) if bad.any() else None
@@ -704,29 +1276,34 @@ def run(ctx, seq, model, upto=None, A=None, diagnose=True, log=None):
             "" if first is None else "; first at %s: got %r, want %r" % (first, got[0][first], want[0][first]), verdict, call_list(seq, i + 1)))
 
     try:
+        states = states_of(dict(seq, steps=steps))
         if not host:  # every caller buffer before anything is enqueued: an allocation or its fill may wait for the device
             for i, s in enumerate(steps):
-                if s["op"] in ASYNC_OPS:
+                if (s["op"] in ASYNC_OPS and not (s["op"] in FILTER_OPS and s["in_place"])) or (s["op"] == "refused" and s.get("dev")):  # (in place: the frame it reads)
                     bufs[i] = _device_frame(A, s)
-        st = apply(None, seq["upload"])
+                if s["op"] in ASYNC_OPS and s["op"] in FILTER_OPS and not s["chain"]:  # a filter of the model's own frame and guides: in HBM before the first step
+                    rgb, aov = model.inputs(states[i], s)
+                    bufs[i, "rgb"], bufs[i, "aov"] = A.DeviceFrame(s["W"], s["H"], frames=s["K"]), A.DeviceFrame(s["W"], s["H"], frames=s["K"], floats=8)
+                    A.to_device(bufs[i, "rgb"].rgb, rgb)
+                    A.to_device(bufs[i, "aov"].rgb, aov)
+        st = states[0]
         t0 = time.time()
         upload(ctx, st, seq["upload"])
         t_gpu += time.time() - t0
         if host:
             _host_handover(ctx, st, seq["upload"])
         for i, s in enumerate(steps):
-            op = s["op"]
+            op, st = s["op"], states[i]
             if log:
                 log("%3d %s" % (i, describe(s)))
             t0 = time.time()
+            new = states[i + 1]
             if op == "upload":
-                new = apply(st, s)
                 upload(ctx, new, s)
                 if host:
                     _host_handover(ctx, new, s)
             elif op == "update_vertices":
                 ctx.update_vertices(update_args(st, s))
-                new = apply(st, s)
                 exs = [("host", ctx.export_trees())] if host else [("HBM", ctx.export_trees(device=True)), ("lazily refitted host", ctx.export_trees())]
                 t_gpu += time.time() - t0
                 V = collapsed_of(new)
@@ -745,33 +1322,56 @@ def run(ctx, seq, model, upto=None, A=None, diagnose=True, log=None):
                 for k, v in s["options"]:
                     ctx.set_option(k, v)
             elif op == "refused":
-                refused_call(ctx, st, s, host)
+                refused_call(ctx, st, s, host, bufs.get(i), A.stream(s["stream"]) if (not host and s.get("stream") is not None) else None)
             elif host:
                 t_gpu += time.time() - t0
                 observe_host(ctx, st, s, model, where(i))
                 t0 = time.time()
             elif op in ASYNC_OPS:
-                observe(ctx, s, st["mats"].shape[0], bufs[i], A)
+                b = bufs.get(i)
+                if op in FILTER_OPS:  # from the buffers the two calls before it fill (a chain), or from the model's; in place: into the frame's own
+                    src = (bufs[i - 2], bufs[i - 1]) if s["chain"] else (bufs[i, "rgb"], bufs[i, "aov"])
+                    if s["in_place"]:
+                        outs[i] = i - 2 if s["chain"] else (i, "rgb")
+                    b = (src[0].rgb, src[1].rgb, bufs[outs.get(i, i)])
+                observe(ctx, s, st["mats"].shape[0], b, A)
                 pending.append((i, st))
             else:
-                got = observe(ctx, s, st["mats"].shape[0])
+                inputs = None
+                if op in FILTER_OPS:
+                    t_gpu += time.time() - t0
+                    inputs = model.inputs(st, s)
+                    t0 = time.time()
+                got = observe(ctx, s, st["mats"].shape[0], inputs=inputs)
+                launches = ctx.stats()["launches"] if op in GUIDE_OPS else None
                 t_gpu += time.time() - t0
                 got_all.append((i,) + tuple(got))
                 check(i, st, got, model.expected(st, s))
+                assert launches is None or launches == expected_launches(st, s), "%s: pt_get_stats counts %d launches, the header says %d" % (where(i), launches, expected_launches(st, s))
                 t0 = time.time()
             t_gpu += time.time() - t0
-            st = apply(st, s)
         if pending:
             t0 = time.time()
             ctx.synchronize()  # the one wait of the sequence: everything before it was ordered by the library
             t_gpu += time.time() - t0
+            overwritten = {o: i for i, o in outs.items()}  # a frame that a filter after it worked on in place: seen through the filter's result only
+            raw = {i: bufs[outs.get(i, i)].read() for i, _ in pending}
             for i, sti in pending:
-                rgb, rgba8 = bufs[i].read()
-                got = (rgb, None) if steps[i]["op"] == "render_aov_device" else (rgb, rgba8)
-                got_all.append((i,) + got)
-            for i, sti in pending:
-                got = [g for g in got_all if g[0] == i][0][1:]
-                check(i, sti, got, model.expected(sti, steps[i]))
+                s, (rgb, rgba8) = steps[i], raw[i]
+                want = model.expected(sti, s)
+                got_all.append((i, rgb, rgba8 if want[1] is not None else None))
+                if i in overwritten:  # its RGBA8 image is the render's own unless the filter wrote one
+                    if not steps[overwritten[i]]["want_rgba8"]:
+                        bad8 = same(rgba8, want[1])
+                        assert not bad8.any(), "%s: %d of %d RGBA8 pixels differ from the oracle\ncalls:\n%s" % (where(i), bad8.sum(), bad8.size, call_list(seq, i + 1))
+                    continue
+                if want[1] is None and not (s.get("chain") and i in outs):  # nobody was to write the RGBA8 buffer of this step
+                    assert (rgba8 == poison).all(), "%s: the call wrote to a buffer that is not its own (the RGBA8 image beside its result)" % where(i)
+                check(i, sti, (rgb, rgba8 if want[1] is not None else None), want)
+            for i, s in enumerate(steps):
+                if s["op"] == "refused" and i in bufs:
+                    rgb, rgba8 = bufs[i].read()
+                    assert (rgb.view(np.uint32) == poison).all() and (rgba8 == poison).all(), "%s: the refused call wrote to the caller's buffers" % where(i)
     finally:
         if not host:
             try:
@@ -803,6 +1403,10 @@ def observe_host(ctx, st, step, model, what):
     tests/aov_ref.py, closest hits of 200 battery rays inside the domain against the oracle's brute force, the boxes against their
     definition."""
     W, H = step["W"], step["H"]
+    if step["op"] in GUIDE_OPS:
+        observe_guides_host(ctx, st, step, model, what)
+        if step["op"] not in FOLLOW_OPS:
+            return
     cams = [c for c, _ in step["frames"]] if "frames" in step else [step["cam"]]
     n = step.get("n", 1 + step.get("spp", 1) % 2)
     S, flat = model.scene(st)
@@ -827,13 +1431,56 @@ def observe_host(ctx, st, step, model, what):
     RC.assert_boxes(ctx.export_trees(), collapsed_of(st), what + ": host arrays against the box definition")
 
 
+def expect_no_device(fn, what):
+    """fn must raise PtError with PT_E_NO_DEVICE: a valid call of a device entry point on a host-only context."""
+    try:
+        fn()
+    except B.PtError as e:
+        assert "(-2)" in str(e), "%s: a host-only context answers a valid call with another code than PT_E_NO_DEVICE: %s" % (what, e)
+        return
+    raise AssertionError("%s: a host-only context accepted the call" % what)
+
+
+def observe_guides_host(ctx, st, step, model, what):
+    """The second family on a host-only context: a follow pass through pt_debug_aov_follow_host against tests/aov_follow_ref.py; a guide batch
+    is answered with PT_E_NO_DEVICE, and the twin shows its frame with the context's table; a filter through pt_debug_denoise_host on the
+    model's inputs against tests/denoise_ref.py, frame by frame, the batch form answered with PT_E_NO_DEVICE."""
+    op, W, H = step["op"], step["W"], step["H"]
+    whole = dict(st, shard=None)  # (the twin knows no shard)
+    if op in FOLLOW_OPS + AOV_BATCH_OPS:
+        cam = step["cam"] if op in FOLLOW_OPS else [c for c, mats in step["frames"] if mats is None][0]
+        if op in AOV_BATCH_OPS:
+            frames = [(_bcam(c, W, H), mats) for c, mats in step["frames"]]
+            expect_no_device(lambda: ctx.render_aov_batch(frames, W, H, _follow_params(step), n_materials=st["mats"].shape[0]), what)
+        got = ctx.aov_follow_host(_bcam(cam, W, H), W, H, _follow_params(step))
+        want, _ = model.expected(whole, dict(step, op="render_aov_follow", cam=cam))
+        bad = same(got, want)
+        assert not bad.any(), "%s: pt_debug_aov_follow_host, %d of %d floats differ from aov_follow_ref; first at %s" % (what, bad.sum(), bad.size, tuple(np.argwhere(bad)[0]))
+        return
+    rgb, aov = model.inputs(whole, step)
+    want, want8 = model.expected(whole, step)
+    if op in DENOISE_BATCH_OPS:
+        expect_no_device(lambda: ctx.denoise_batch(rgb, aov, _filter_params(step)), what)
+    else:
+        expect_no_device(lambda: ctx.denoise(rgb, aov, _filter_params(step)), what)
+        rgb, aov, want, want8 = rgb[None], aov[None], want[None], None if want8 is None else want8[None]
+    for f in range(rgb.shape[0]):
+        src = np.array(rgb[f], F32) if step["in_place"] else rgb[f]
+        got, got8 = ctx.denoise_host(src, aov[f], _filter_params(step), want_rgba8=step["want_rgba8"], in_place=step["in_place"])
+        bad = same(got, want[f])
+        assert not bad.any(), "%s: pt_debug_denoise_host, frame %d: %d of %d floats differ from denoise_ref; first at %s" % (what, f, bad.sum(), bad.size, tuple(np.argwhere(bad)[0]))
+        assert want8 is None or (got8 == want8[f]).all(), "%s: pt_debug_denoise_host, frame %d: the RGBA8 image differs from denoise_ref's" % (what, f)
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # the group path: what pt_group_* can express of a sequence
 # ---------------------------------------------------------------------------------------------------------------------
 def group_projection(seq):
     """The sequence as a pt_group can run it, with option "watertight" = 1 throughout: uploads, update_vertices, set_materials, box_exact
-    and the scheduler knobs stay; every single frame becomes a blocking render, every guide pass a blocking one; batches (refused with
-    watertight = 1), shards (the group's own business), set_environment (no group call), refusals and the watertight switches go."""
+    and the scheduler knobs stay; every single frame becomes a blocking render, every guide pass (first hit or follow mode) a blocking one,
+    and a denoise_chain becomes the group's render, the group's follow pass and pt_denoise of the two on rank 0's context; batches (refused
+    with watertight = 1), the other filters, shards (the group's own business), set_environment (no group call), refusals, "batch_frames" and
+    the watertight switches go."""
     steps = [dict(op="set_option", key="watertight", value=1)]
     for s in seq["steps"]:
         op = s["op"]
@@ -843,7 +1490,13 @@ def group_projection(seq):
             steps.append(dict(s, op="render", stream=None))
         elif op in AOV_OPS:
             steps.append(dict(s, op="render_aov", stream=None))
-    return dict(seed=seq["seed"], host_only=False, upload=seq["upload"], steps=steps)
+        elif op in FOLLOW_OPS:
+            steps.append(dict(s, op="render_aov_follow", stream=None))
+        elif op in DENOISE_OPS and s["chain"]:  # behind the group's frame and guides: pt_denoise on rank 0's context, as the header prescribes for N GPUs
+            render, guides = steps[-2], steps[-1]
+            assert render["op"] == "render" and guides["op"] == "render_aov_follow"
+            steps.append(dict(s, op="denoise", stream=None, src=dict(render=render, guides=guides)))
+    return dict(seed=seq["seed"], family=seq.get("family", ""), host_only=False, upload=seq["upload"], steps=steps)
 
 
 def run_plain(target, seq):
@@ -864,8 +1517,10 @@ def run_plain(target, seq):
         elif op == "knob":
             for k, v in s["options"]:
                 target.set_option(k, v)
+        elif op == "denoise":  # of the two observations before it, on rank 0's context where target is a group
+            out.append((i,) + tuple(observe(target, s, st["mats"].shape[0], inputs=(out[-2][1], out[-1][1]), filter_on=target.ctx(0) if hasattr(target, "ctx") else None)))
         else:
-            assert op in ("render", "render_aov"), op
+            assert op in ("render", "render_aov", "render_aov_follow"), op
             out.append((i,) + tuple(observe(target, s, st["mats"].shape[0])))
         st = apply(st, s)
     return out

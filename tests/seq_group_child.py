@@ -1,7 +1,8 @@
 """The child of tests/test_gpu_sequences.py::test_sequences_over_a_group: `python tests/seq_group_child.py OUT_DIR DEVICES SEED...`.  A
 pt_group over DEVICES (pt_comm.cpp resolves PT_RCCL_PATH once per process, hence the child) runs the group projection of every
-sequence (tests/seq_common.py: option "watertight" = 1, uploads, updates, tables, single frames, guide passes) and leaves every
-observation in OUT_DIR as seed_step_rgb.npy / seed_step_rgba8.npy, then done.json."""
+sequence (tests/seq_common.py: option "watertight" = 1, uploads, updates, tables, single frames, guide passes; a seed from
+seq_common.GSEED0 on is one of the second family: follow passes, and pt_denoise on rank 0's context of the group's frame and guides) and
+leaves every observation in OUT_DIR as seed_step_rgb.npy / seed_step_rgba8.npy, then done.json."""
 import json
 import os
 import sys
@@ -26,7 +27,7 @@ def main(out_dir, devices, seeds):
     for seed in seeds:
         g = B.Group([int(d) for d in devices.split(",")])
         try:
-            obs = SC.run_plain(g, SC.group_projection(SC.draw_sequence(seed)))
+            obs = SC.run_plain(g, SC.group_projection(SC.draw_guide_sequence(seed) if seed >= SC.GSEED0 else SC.draw_sequence(seed)))
             size = g.size
         finally:
             g.close()

@@ -1,4 +1,5 @@
-"""Print a seed's call sequence (tests/seq_common.py), and run it: `python tools/seq_replay.py <seed> [--run [K]] [--host]`.
+"""Print a seed's call sequence (tests/seq_common.py), and run it: `python tools/seq_replay.py <seed> [--run [K]] [--host]`.  A seed from
+seq_common.GSEED0 on is one of the second family (follow guides, batch guides, the denoiser).
 
 Without --run: the upload and the steps in words (no GPU needed).  --run: the first K steps (all without K) on a fresh context with the
 runner of tests/test_gpu_sequences.py, every observation compared with the oracle, each step printed as it starts; a difference ends
@@ -19,8 +20,8 @@ from owl_path_tracer_amd.pyhost import binding as B
 args = sys.argv[1:]
 seed = int(args[0])
 host = "--host" in args
-seq = SC.draw_sequence(seed, host_only=host)
-print("sequence seed=%d: %d steps" % (seed, len(seq["steps"])))
+seq = (SC.draw_guide_sequence if seed >= SC.GSEED0 else SC.draw_sequence)(seed, host_only=host)
+print("%ssequence seed=%d: %d steps" % ("guide " if seed >= SC.GSEED0 else "", seed, len(seq["steps"])))
 print(SC.call_list(seq))
 if "--run" in args:
     k = args.index("--run")
