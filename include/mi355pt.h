@@ -170,18 +170,19 @@ int pt_render(pt_ctx* ctx, const pt_camera* cam, int32_t width, int32_t height, 
  * every call that touches what a frame in flight uses is ordered after the context's LAST ASYNCHRONOUS CALL, whichever stream that
  * call was given.  So any call of this header may follow a pt_*_device call at once, with no pt_synchronize between them.
  *   - The asynchronous calls (pt_render_device, pt_render_batch_device, pt_render_aov_device, pt_render_aov_follow_device, pt_render_aov_batch_device, pt_denoise_device,
- *     pt_denoise_batch_device, pt_reduce_framebuffer) wait ON THE
+ *     pt_denoise_batch_device, pt_accum_add_device, pt_reduce_framebuffer) wait ON THE
  *     DEVICE: the stream they are given waits for an event recorded at the end of the previous asynchronous call - only if that call
  *     used another stream; on the same stream the stream's own order suffices and nothing is added.  The host returns at once, with
  *     two exceptions that existed before: a frame of another size, shard or batch length rewrites the pixel queue and a frame that
  *     needs larger work buffers reallocates them (pt_denoise_device: its filter records, when the frame is larger than any it filtered
- *     before) - both first wait on the host for the frame in flight; and pt_render_batch_device and pt_render_aov_batch_device
- *     return when their per-frame tables have reached HBM, i.e. after whatever precedes them on `stream`.
- *   - The blocking renders (pt_render, pt_render_batch, pt_render_aov, pt_render_aov_follow, pt_render_aov_batch), pt_denoise and pt_denoise_batch run on the context's stream behind the same device-side wait
+ *     before) - both first wait on the host for the frame in flight; pt_render_batch_device and pt_render_aov_batch_device
+ *     return when their per-frame tables have reached HBM, i.e. after whatever precedes them on `stream`; and a pt_accum_add_device that
+ *     selects its pixels returns when the count of its active set has reached the host (see there).
+ *   - The blocking renders (pt_render, pt_render_batch, pt_render_aov, pt_render_aov_follow, pt_render_aov_batch, pt_accum_add), pt_denoise and pt_denoise_batch run on the context's stream behind the same device-side wait
  *     and return with the context idle.  After a blocking call, or on the context's own stream, they add no wait at all.
  *   - The calls that change or read what a frame uses WAIT ON THE HOST for the last asynchronous call's stream (if it is not the
  *     context's) and then for the context's: pt_set_materials, pt_set_environment, pt_update_vertices, pt_upload_scene,
- *     pt_set_pixel_shard when it changes the shard of a queue in use, pt_comm_destroy, pt_destroy, pt_debug_eval and the pt_debug_*
+ *     pt_set_pixel_shard when it changes the shard of a queue in use, pt_accum_begin, pt_accum_read, pt_accum_end, pt_comm_destroy, pt_destroy, pt_debug_eval and the pt_debug_*
  *     readers of device state - and pt_synchronize, which is that wait plus the watchdog check.  A frame enqueued before such a call
  *     renders the state before it, a frame enqueued after it the state after it.
  *   - pt_get_stats waits for the end of the last frame's kernels (an event), not for the stream.
@@ -192,7 +193,7 @@ int pt_render(pt_ctx* ctx, const pt_camera* cam, int32_t width, int32_t height, 
 int pt_render_device(pt_ctx* ctx, const pt_camera* cam, int32_t width, int32_t height, int32_t max_samples, int32_t max_path_depth,
                      void* d_out_rgb, void* d_out_rgba8, void* stream);
 /* Waits on the host for the context's last asynchronous call - pt_render_device, pt_render_batch_device, pt_render_aov_device,
- * pt_render_aov_follow_device, pt_render_aov_batch_device, pt_denoise_device, pt_denoise_batch_device or pt_reduce_framebuffer, on the stream it was given - and for the context's own stream.  Every earlier asynchronous call of the context
+ * pt_render_aov_follow_device, pt_render_aov_batch_device, pt_denoise_device, pt_denoise_batch_device, pt_accum_add_device or pt_reduce_framebuffer, on the stream it was given - and for the context's own stream.  Every earlier asynchronous call of the context
  * is complete then as well, whatever stream it used: each was ordered before the next (see pt_render_device).  Returns PT_E_HIP if a
  * wave's watchdog fired during the last frame (the image is then incomplete); pt_get_stats reports the same.  PT_OK at once on an idle
  * or host-only context.  A caller's stream may be destroyed once this has returned. */
@@ -398,6 +399,84 @@ int pt_denoise_batch_device(pt_ctx* ctx, const void* d_rgb, const void* d_aov, i
 /* The CPU twin of the filter: the definition above on all host threads; works on a host-only context; returns width * height. */
 int64_t pt_debug_denoise_host(pt_ctx* ctx, const float* rgb, const float* aov, int32_t width, int32_t height, const pt_denoise_params* p,
                               float* out_rgb, uint32_t* out_rgba8);
+
+/* ---- progressive accumulation: a frame that grows by "adds", with a per-pixel noise estimate and adaptive adds (no reference
+ * counterpart: the reference restarts every frame at sample 0) ----
+ * A context holds at most ONE accumulation.  It owns its device buffers (62 bytes per pixel of the frame beside the 16 of the image); no other
+ * call of this header reads or writes them.  pt_accum_begin fixes camera, size, depth and the pixel shard as they are at that moment;
+ * every pt_accum_add gives the pixels of its ACTIVE SET n_samples more samples of their own RNG streams and returns the image so far.
+ * STATE per pixel: rng and sum[3] - the render kernel's own rng_state / accum at the launch id x + W*y - and seen[3], half[3], n, n_half,
+ * passes, noise.  pt_accum_begin sets noise = +inf and everything else 0.
+ * AN ADD: (1) select the active set; (2) run the render path (the wavefront kernel, its schedules, option "watertight") over exactly
+ * those pixels for n_samples more samples of each pixel's stream - a pixel's first add starts from the seed of pt_render, later ones from
+ * the stored state; the render kernel writes no framebuffer; (3) resolve.
+ * DEFINITION (the kernels of csrc/pt_accum.hip, the CPU twins pt_debug_accum_resolve_host / pt_debug_accum_select_host - one source,
+ * csrc/pt_accum_math.h - and the numpy restatement tests/accum_ref.py implement exactly this).  Arithmetic: the contract of
+ * csrc/pt_device.h - float32, no contraction, correctly rounded "/", its sqrt_, max_, make_rgba; |v| clears the sign bit.
+ *   Resolve, for every owned pixel:
+ *     if the pixel was active in this add:  if passes is odd: half_k = half_k + (sum_k - seen_k), n_half += n_samples;
+ *                                           then seen = sum, n += n_samples, passes += 1.
+ *     n >= 1:  out_k = sum_k * (1.0f / (float)n) - pt_render's own expression with max_samples = n - and rgba8 = make_rgba(out);
+ *     n == 0:  out = +0, rgba8 = 0.
+ *     noise = +inf while n_half == 0; else a_k = half_k * (1.0f / (float)n_half), b_k = (sum_k - half_k) * (1.0f / (float)(n - n_half)),
+ *             d = (|a_0 - b_0| + |a_1 - b_1|) + |a_2 - b_2|,  l = max_((out_0 + out_1) + out_2, 1e-2f),  noise = d / sqrt_(l).
+ *     This is the half-buffer error estimate of production adaptive samplers: two disjoint sample sets of the same pixel (the samples
+ *     of the pixel's even and of its odd passes), normalised by brightness.
+ *   Pixels the context does not own are +0 in every output.
+ *   Select, for the next add: an owned pixel is active iff (max_pixel_samples == 0 || n < max_pixel_samples) and
+ *     (noise_threshold == 0 || !(noise <= noise_threshold)).  NaN and +inf are active, so every pixel takes part in a frame's first two
+ *     adds whatever the threshold.  The order of the compacted id list is not part of the contract; the image does not depend on it.  An
+ *     empty active set is not an error: no render kernel is launched, resolve still rewrites the outputs, active_pixels = 0.
+ * CONSEQUENCES.  A pixel with n samples is bit for bit that pixel of pt_render at max_samples = n (same camera, size, depth, scene
+ * state, "watertight"), however the n were split into adds: uniform adds totalling N give the whole frame of pt_render(N), rgba8
+ * included.  Samples see the materials, environment and vertices current at their add.  Changing the pixel shard or uploading a new
+ * scene after pt_accum_begin makes the next add PT_E_INVALID until a new begin.
+ * LAYOUTS: out_rgb (W*H*3 floats), out_rgba8, out_noise and out_samples (W*H each) are in framebuffer order x + W*(H-1-y), like out_rgb
+ * of pt_render.
+ * ORDERING: pt_accum_add_device joins the asynchronous calls of the streams contract at pt_render_device: ordered after the context's
+ * last asynchronous call and itself the last one afterwards.  pt_accum_add is a blocking render (context's stream, idle on return);
+ * pt_accum_begin, pt_accum_read, pt_accum_end and pt_debug_accum_state wait on the host like pt_set_materials.  A uniform add without a
+ * cap returns at once on the host (the exceptions of pt_render_device apply: a work buffer that has to grow).  An add that SELECTS
+ * (threshold > 0 or a cap) waits on the host for the 4-byte count of its active set - i.e. for everything before it on its stream -
+ * because the launch cannot be planned without it.  Any other call of the header may come between two adds (a pt_render of another size,
+ * guide passes, the denoiser, batches): it leaves the accumulation untouched and is itself unchanged by it.
+ * COMMUNICATOR: not built yet - pt_accum_begin, pt_accum_add and pt_accum_add_device on a context with a communicator are PT_E_INVALID
+ * by name (an accumulation begun before the communicator was attached can still be read and ended).  There is no pt_group_*
+ * form.  A pixel shard set with pt_set_pixel_shard works: noise and sample maps are per shard.
+ * REFUSED with PT_E_INVALID and a message that names the call, before anything is touched: n_samples outside 1..65535, a negative cap,
+ * a threshold that is negative or NaN, reserved != 0; options "kernel" = 1, "latency", "timeline"; add / read / info without a begin;
+ * sizes pt_render refuses; a pixel's n about to pass 2^31 - 65536 (judged by the sum of the adds' n_samples).  PT_E_NO_SCENE without a
+ * scene.  On a host-only context valid arguments give PT_E_NO_DEVICE at pt_accum_begin, so no accumulation exists there.
+ * pt_get_stats after an add: kernel_ms from the first launch - of an add that selects, the select kernel's, so the wait for the count lies
+ * inside - to the end of resolve, launches = the render-kernel launches (0 for an empty active set), the geometry fields the render
+ * kernel's (after an empty active set: those of the last frame that ran one). */
+typedef struct pt_accum_params {
+    int32_t n_samples;          /* 1..65535: samples this add gives every ACTIVE pixel */
+    int32_t max_pixel_samples;  /* 0 = no cap; else a pixel with n >= this is never active again (n may overshoot by < n_samples) */
+    float   noise_threshold;    /* 0 = uniform add (every owned pixel under the cap); > 0 = only pixels with !(noise <= threshold) */
+    int32_t reserved;           /* must be 0 */
+} pt_accum_params;
+void pt_accum_default_params(pt_accum_params* p);            /* 16, 0, 0.0f, 0 */
+typedef struct pt_accum_info {
+    int32_t  width, height, max_path_depth, adds;            /* adds so far */
+    int64_t  owned_pixels, active_pixels;                    /* active: of the last add */
+    uint64_t samples_total;                                  /* sum over the adds of active_pixels * n_samples */
+} pt_accum_info;
+int pt_accum_begin(pt_ctx* ctx, const pt_camera* cam, int32_t width, int32_t height, int32_t max_path_depth); /* replaces an accumulation the context has */
+int pt_accum_add(pt_ctx* ctx, const pt_accum_params* p /* NULL = defaults */, float* out_rgb /* may be NULL */, uint32_t* out_rgba8 /* may be NULL */);
+int pt_accum_add_device(pt_ctx* ctx, const pt_accum_params* p, void* d_out_rgb /* may be NULL */, void* d_out_rgba8 /* may be NULL */, void* stream);
+int pt_accum_read(pt_ctx* ctx, float* out_rgb, uint32_t* out_rgba8, float* out_noise, uint32_t* out_samples); /* any pointer may be NULL */
+int pt_accum_info_get(pt_ctx* ctx, pt_accum_info* out);
+int pt_accum_end(pt_ctx* ctx);                               /* frees the buffers; PT_OK when there is none */
+/* Validation hooks.  The two twins work on a host-only context and on flat arrays of n_pixels pixels (no row order is implied).
+ * resolve: sum[3n], seen[3n], half[3n], n, n_half, passes, active and owned flags (bytes, 0 / not 0), n_samples 1..65535 -> seen, half, n,
+ * n_half, passes updated in place, out_rgb[3n], out_rgba8[n], noise[n]; returns n_pixels.  select: -> active flags (0 / 1); returns the
+ * number of active pixels; refuses the parameters an add refuses.  state: the raw state of the context's accumulation in framebuffer
+ * order (sum and half W*H*3 floats, the others W*H; any pointer may be NULL), +0 outside the shard; waits on the host. */
+int64_t pt_debug_accum_resolve_host(pt_ctx* ctx, int64_t n_pixels, const float* sum, float* seen, float* half, uint32_t* n, uint32_t* n_half, uint32_t* passes,
+                                    const uint8_t* active, const uint8_t* owned, int32_t n_samples, float* out_rgb, uint32_t* out_rgba8, float* noise);
+int64_t pt_debug_accum_select_host(pt_ctx* ctx, const float* noise, const uint32_t* n, const uint8_t* owned, int64_t n_pixels, const pt_accum_params* p, uint8_t* active);
+int pt_debug_accum_state(pt_ctx* ctx, float* sum, float* half, uint32_t* n, uint32_t* n_half, uint32_t* passes);
 
 /* ---- N GPUs: pixel tiles sharded over ranks + ONE RCCL sum-reduce of the float3 framebuffer onto rank 0 (pt_comm.cpp) ----
  * No reference counterpart (the reference is single-GPU: create_context(nullptr, 1), application.cpp:62); for N > 1 these

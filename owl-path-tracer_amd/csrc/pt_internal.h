@@ -1,10 +1,12 @@
 // pt_internal.h -- private to the library: the context behind the opaque pt_ctx of include/mi355pt.h and the helpers its host sources
 // share: pt_api.cpp (context, options, stats), pt_scene.cpp (scene upload and clone), pt_render.cpp (frames and batches), pt_guides.cpp
-// (guide pass and denoiser), pt_debug.cpp (probes and readers) and pt_comm.cpp (RCCL reduce, multi-GPU group).
+// (guide pass and denoiser), pt_accum_host.cpp (progressive accumulation), pt_debug.cpp (probes and readers) and pt_comm.cpp (RCCL reduce, multi-GPU group).
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <functional>
 #include <initializer_list>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -91,6 +93,26 @@ struct LastFrame {
     bool aov_flag_pending = false; // the last call was a guide pass (pt_render_aov*) that ran a kernel: its bound flag in d_aov_ws has not been looked at yet
 };
 
+// The context's progressive accumulation (pt_accum_*; pt_accum_host.cpp): the frame that grows by adds, and the owner of its state across
+// calls.  No other call of the header reads or writes these buffers.  Everything per pixel is indexed by the launch id x + W * y except
+// out / out8 (framebuffer order).
+struct Accum {
+    pt_camera cam{};
+    int w = 0, h = 0, depth = 0;
+    int rank = 0, world = 1, tile = 16; // the pixel shard as pt_accum_begin found it
+    uint64_t scene_epoch = 0;           // ... and the upload it found (pt_ctx::scene_epoch)
+    uint32_t n_owned = 0;
+    int adds = 0;
+    int64_t active_pixels = 0;          // of the last add
+    uint64_t samples_total = 0;
+    uint64_t n_upper = 0;               // no pixel has more samples than this: the sum of the adds' n_samples
+    DevBuf rng, sum;                    // the render kernel's rng_state / accum
+    DevBuf seen, half, n, n_half, passes, noise, owned, active;
+    DevBuf queue;                       // the shard's pixel queue (n_owned ids), kept: other calls rewrite the context's d_pixels
+    DevBuf count;                       // select's counter, 256 bytes of its own
+    DevBuf out, out8;                   // resolve's image
+};
+
 struct pt_ctx {
     int device = -1;
     bool host_only = false;
@@ -103,6 +125,7 @@ struct pt_ctx {
 
     HostScene scene;
     bool have_scene = false;
+    uint64_t scene_epoch = 0; // counts pt_upload_scene / clone_scene: what was begun on an earlier scene notices (pt_accum_add)
 
     // device
     DevBuf d_nodes8, d_nodes4, d_nodes, d_tris, d_shade, d_materials, d_texdesc, d_env, d_pixels, d_heads, d_rng, d_accum, d_out, d_out8, d_counters, d_dbg_in, d_dbg_out, d_slots, d_laps, d_ring, d_params, d_cost, d_sorted, d_sort_scratch, d_dbg_start, d_bucket, d_tiers, d_batch_mats, d_batch_cams, d_seq_flags; // d_batch_*: per-frame tables of pt_render_batch; d_seq_flags: watchdog flags of its earlier launch sequences
@@ -125,6 +148,7 @@ struct pt_ctx {
     pt_stats stats{}; // (its scene figures are kept in `scene`: pt_get_stats)
     LastFrame last;
     std::vector<float> batch_cams_h, batch_mats_h; // pt_render_batch: staging of the per-frame tables
+    std::unique_ptr<Accum> acc; // pt_accum_begin .. pt_accum_end
 };
 
 // Helpers that more than one host source uses.  The library is built with default visibility, so the five that existed before the host
@@ -155,6 +179,11 @@ PT_LOCAL int64_t batch_max_frames(int W, int H, int max_frames);
 PT_LOCAL int stage_batch_tables(pt_ctx* c, const pt_frame* frames, int n_frames, hipStream_t stream);
 struct D2H { void* dst; const void* src; size_t bytes; }; // a copy to a host buffer of the caller; dst null: none
 PT_LOCAL int drain(pt_ctx* c, std::initializer_list<D2H> copies);
+// One add of the progressive accumulation over the pixel queue as it stands (d_pixels, n_pixels; none: no kernel runs): the frame path
+// with the pixels' state in d_rng / d_sum and no framebuffer.  `resolve` enqueues what follows the launches and lies inside kernel_ms, which
+// starts at ev0: recorded here before the first launch, or by the caller before its select launch (ev0_recorded).
+PT_LOCAL int accum_frame(pt_ctx* c, const pt_camera* cam, int W, int H, int n_samples, int max_depth, bool first_add, uint32_t* d_rng, float* d_sum, hipStream_t stream,
+                         bool ev0_recorded, const std::function<int()>& resolve);
 // pt_denoise_host.cpp
 PT_LOCAL int check_denoise_args(pt_ctx* c, const char* who, int W, int H, const pt_denoise_params* p, pt_denoise_params* eff); // the refusals of pt_denoise* and the twin; *eff = the parameters in effect
 PT_LOCAL void denoise_constants(const pt_denoise_params& p, float* kn, float* ka, float kc[8]); // the definition's host constants

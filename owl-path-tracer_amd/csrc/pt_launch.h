@@ -80,7 +80,40 @@ struct PtDenoiseArgs {
     float kc[8];            // per iteration
 };
 
+// Progressive accumulation (pt_accum_*; pt_accum.hip): what its two kernels take.  Every per-pixel array is indexed by the launch id
+// x + W * y (the render kernel's index into rng_state / accum) except the two images, which are in framebuffer order.
+struct PtAccumArgs {
+    const float* sum;        // W*H*3: the render kernel's accum
+    float* seen;             // W*H*3: sum as of the pixel's last resolve
+    float* half;             // W*H*3: the samples of every second pass
+    uint32_t* n;             // samples, samples in half, passes
+    uint32_t* n_half;
+    uint32_t* passes;
+    float* noise;            // W*H
+    const uint8_t* owned;    // 1: a pixel of this context's shard
+    const uint8_t* active;   // 1: took part in this add (select's flags); not read with all_active
+    float* out_rgb;          // W*H*3
+    uint32_t* out_rgba8;     // W*H
+    uint32_t n_frame;        // W*H
+    int32_t width, height, n_samples, all_active;
+};
+struct PtAccumSelectArgs {
+    const uint32_t* queue;   // the shard's pixel queue
+    const float* noise;
+    const uint32_t* n;
+    uint8_t* active;         // by id, written for every queue entry
+    uint32_t* ids_out;       // n_queue entries: the active ids, compacted
+    uint32_t* count;         // their number; 0 on entry, alone on its cache line
+    uint32_t n_queue, cap;   // cap = max_pixel_samples (0: none)
+    float threshold;         // noise_threshold (0: none)
+    int32_t pad;
+};
+
 extern "C" {
+// pt_accum.hip: geometry of the resolve kernel (block, vgprs); hipErrorInvalidConfiguration if one of the two kernels needs scratch
+hipError_t pt_accum_geometry(PtGeometry* g);
+hipError_t pt_launch_accum_resolve(const PtAccumArgs* a, hipStream_t stream);
+hipError_t pt_launch_accum_select(const PtAccumSelectArgs* a, hipStream_t stream);
 // pt_denoise.hip: prepare + `iterations` iteration launches + finish on `stream`; the geometry is the iteration kernel's (grid = its
 // workgroups for a W x H frame), hipErrorInvalidConfiguration if one of the three kernels needs scratch
 size_t pt_denoise_workspace_bytes(int W, int H);

@@ -238,6 +238,7 @@ struct FramePlan {
     size_t lap_ticks_ofs = 0;       // where the timelines start in d_laps (plan_chunks)
     uint32_t n_express = 0;         // express pixels (pt_kernel.hip, take_ticket), their waves and pixels per express wave
     int express_waves = 0, ns_express = 0;
+    int sample_base = 0;            // an add of the progressive accumulation that continues its pixels (accum_frame): every launch has sample_begin != 0
 };
 
 // Samples, chunks and express pixels of a wavefront frame whose launch geometry plan_frame has fixed.
@@ -411,7 +412,7 @@ int frame_buffers(pt_ctx* c, const FramePlan& f, int W, int H, void* d_out_rgb, 
     if ((rc = ensure(c, c->d_heads, (size_t)f.n_launch * PT_HEADS_WORDS * 4))) return rc; // per launch: the ticket counter, the express counter 256 bytes on, the tier counters
     HIP_TRY(c, hipMemsetAsync(c->d_heads.p, 0, (size_t)f.n_launch * PT_HEADS_WORDS * 4, stream));
     if (f.tiers && (rc = ensure(c, c->d_tiers, (1 + PT_MAX_TIERS * PT_TIER_WORDS) * 4))) return rc;
-    HIP_TRY(c, hipMemsetAsync(d_out_rgb, 0, (size_t)W * H * 3 * sizeof(float), stream));
+    if (d_out_rgb) HIP_TRY(c, hipMemsetAsync(d_out_rgb, 0, (size_t)W * H * 3 * sizeof(float), stream)); // (null: accum_frame, whose launches write no framebuffer)
     if (d_out_rgba8) HIP_TRY(c, hipMemsetAsync(d_out_rgba8, 0, (size_t)W * H * 4, stream));
     if (f.n_launch > 1 || n_chunks > 1) {
         if ((rc = ensure(c, c->d_rng, (size_t)W * H * 4))) return rc;
@@ -468,13 +469,13 @@ void launch_params(pt_ctx* c, const FramePlan& f, int l, int max_samples, PtKern
 {
     P.queue_head = (uint32_t*)c->d_heads.p + PT_HEADS_WORDS * l;
     if (!f.sorted) {
-        P.sample_begin = l * f.S;
+        P.sample_begin = f.sample_base + l * f.S;
         P.sample_count = std::min(f.S, max_samples - l * f.S);
         return;
     }
     const bool pre = l == 0;
     const int n_chunks = f.sc.n_chunks;
-    P.sample_begin = pre ? 0 : f.pre;
+    P.sample_begin = f.sample_base + (pre ? 0 : f.pre);
     P.sample_count = pre ? f.pre : max_samples - f.pre;
     P.pixel_ids = pre ? (const uint32_t*)c->d_pixels.p : (const uint32_t*)c->d_sorted.p;
     P.cost_out = pre ? (uint8_t*)c->d_cost.p : nullptr;
@@ -663,6 +664,40 @@ int render_device(pt_ctx* c, const pt_camera* cam, int W, int H, int max_samples
 }
 
 } // namespace
+
+namespace pti {
+
+// An add of the progressive accumulation (pt_accum_host.cpp) is the frame path above with four differences: the pixel queue is the one
+// the add has put into d_pixels / n_pixels (its active set); rng_state / accum are the accumulation's own; a continuing add starts every
+// launch at sample_begin != 0, so start_chunk loads the pixel's state instead of seeding it (pt_kernel.hip: the only two uses of
+// sample_begin are that test and the one below); and max_samples is a value no launch reaches (sample_begin + sample_count <= 2 * 65536),
+// so finish_chunk always stores the state and never writes a framebuffer.  n_samples < 4 * prepass_spp takes the unsorted schedule,
+// larger adds the pre-pass, the sort and - on small active sets - tiers and express pixels, exactly as plan_frame decides for a shard.
+int accum_frame(pt_ctx* c, const pt_camera* cam, int W, int H, int n_samples, int max_depth, bool first_add, uint32_t* d_rng, float* d_sum, hipStream_t stream,
+                bool ev0_recorded, const std::function<int()>& resolve)
+{
+    int rc;
+    if (c->n_pixels == 0) { // an empty active set: resolve alone
+        if (!ev0_recorded) HIP_TRY(c, hipEventRecord(c->ev0, stream));
+        if ((rc = resolve())) return rc;
+        return finish_frame(c, stream, W, H, nullptr, 0);
+    }
+    PtKernelParams P;
+    walk_params(c, cam, P);
+    FramePlan f;
+    f.sample_base = first_add ? 0 : 65536;
+    if ((rc = plan_frame(c, P, n_samples, f))) return rc;
+    if ((rc = frame_buffers(c, f, W, H, nullptr, nullptr, stream))) return rc;
+    frame_params(c, f, cam, W, H, 0x7fffffff, max_depth, nullptr, nullptr, P);
+    P.rng_state = d_rng;
+    P.accum = d_sum;
+    if (!ev0_recorded) HIP_TRY(c, hipEventRecord(c->ev0, stream));
+    if ((rc = run_launches(c, f, P, W, H, n_samples, stream, true))) return rc;
+    if ((rc = resolve())) return rc;
+    return finish_frame(c, stream, W, H, &f, P.stack_entries);
+}
+
+} // namespace pti
 
 extern "C" {
 

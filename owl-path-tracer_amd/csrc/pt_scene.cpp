@@ -371,6 +371,7 @@ extern "C" int pt_upload_scene(pt_ctx* c, const pt_mesh* meshes, int32_t n_meshe
     // from here on the context has NO scene until the upload has succeeded (a failure half way must not leave the previous scene's flag
     // over new host arrays)
     c->have_scene = false;
+    ++c->scene_epoch;
     c->scene.dyn = DynScene{};
     c->scene.dyn.enabled = c->opt.dynamic != 0;
     // every device buffer of the scene is reused in place where its capacity suffices (ensure), and a device builder writes d_nodes
@@ -465,6 +466,7 @@ int clone_scene(pt_ctx* dst, const pt_ctx* src)
     sync_host_scene(const_cast<pt_ctx*>(src)); // (the host copies are a cache of what the source's device holds after an update)
     dst->scene = src->scene;
     dst->have_scene = true;
+    ++dst->scene_epoch;
     dst->queue_valid = false;
     if (dst->host_only) return PT_OK;
     return upload_scene_to_device(dst);

@@ -19,6 +19,9 @@
 // --denoise (needs --aov N, so not with --batch either: after every frame and its guides pt_denoise with the default parameters - mi355pt.h,
 // "denoiser" - and one more file, <name>_denoised.png = the filter's RGBA8 image; with --gpus / --devices the filter runs on the first
 // device's context, which holds the reduced frame).
+// --adds K (1 <= K <= max_samples: every frame is a progressive accumulation - pt_accum_begin, K uniform pt_accum_add of max_samples / K
+// samples, the remainder with the last, pt_accum_end; mi355pt.h, "progressive accumulation" - and the files are byte for byte those
+// without the flag; works with --watertight, --aov and --denoise, not with --gpus / --devices or --batch).
 #include <sys/stat.h>
 #include <unistd.h>
 
@@ -101,6 +104,7 @@ struct App {
     int follow = -1;               // --follow K: the guide pass in follow mode, max_follow = K (-1: first hit, pt_render_aov)
     float follow_roughness = -1.0f; // --follow-roughness R: roughness_max (< 0: the default of pt_aov_default_params)
     bool denoise = false; // --denoise: pt_denoise of every frame with its guides
+    int adds = 0;  // --adds K: every frame in K uniform adds of a progressive accumulation (0: one pt_render)
 };
 
 void check(App& a, int rc, const char* what)
@@ -166,10 +170,25 @@ void render_frame(App& a, const std::string& values)
     const int W = a.settings.buffer_size[0], H = a.settings.buffer_size[1];
     std::vector<float> rgb((size_t)W * H * 3);
     std::vector<uint32_t> rgba((size_t)W * H);
-    if (a.group) check(a, pt_group_render(a.group, &a.cam, W, H, a.settings.max_samples, a.settings.max_path_depth, rgb.data(), rgba.data()), "pt_group_render");
+    double adds_ms = 0.0;
+    if (a.adds > 0) { // the frame grows by a.adds uniform adds; only the last add's image is kept
+        check(a, pt_accum_begin(a.ctx, &a.cam, W, H, a.settings.max_path_depth), "pt_accum_begin");
+        pt_accum_params prm;
+        pt_accum_default_params(&prm);
+        const int each = a.settings.max_samples / a.adds;
+        for (int k = 0; k < a.adds; ++k) {
+            const bool last = k + 1 == a.adds;
+            prm.n_samples = last ? a.settings.max_samples - each * (a.adds - 1) : each;
+            check(a, pt_accum_add(a.ctx, &prm, last ? rgb.data() : nullptr, last ? rgba.data() : nullptr), "pt_accum_add");
+            pt_stats sk;
+            if (pt_get_stats(a.ctx, &sk) == PT_OK) adds_ms += sk.kernel_ms;
+        }
+        check(a, pt_accum_end(a.ctx), "pt_accum_end");
+    } else if (a.group) check(a, pt_group_render(a.group, &a.cam, W, H, a.settings.max_samples, a.settings.max_path_depth, rgb.data(), rgba.data()), "pt_group_render");
     else check(a, pt_render(a.ctx, &a.cam, W, H, a.settings.max_samples, a.settings.max_path_depth, rgb.data(), rgba.data()), "pt_render");
     pt_stats st;
     pt_get_stats(a.ctx, &st);
+    if (a.adds > 0) st.kernel_ms = adds_ms; // the kernels of all adds
     for (int32_t i = 1; i < pt_group_size(a.group); ++i) { // the frame takes as long as its slowest rank
         pt_stats si;
         if (pt_get_stats(pt_group_ctx(a.group, i), &si) == PT_OK && si.kernel_ms > st.kernel_ms) st.kernel_ms = si.kernel_ms;
@@ -270,7 +289,7 @@ int main(int argc, char** argv)
         std::string settings_path, dump;
         a.out_dir = cwd;
         int device = 0, gpus = 0; // gpus 0: flag not given, single context as in the reference
-        bool have_device = false, have_devices = false, have_batch = false, have_aov = false, have_follow = false, have_follow_roughness = false, watertight = false;
+        bool have_device = false, have_devices = false, have_batch = false, have_adds = false, have_aov = false, have_follow = false, have_follow_roughness = false, watertight = false;
         std::vector<int32_t> devs; // --devices
         for (int i = 1; i < argc; ++i) {
             std::string k = argv[i];
@@ -288,6 +307,7 @@ int main(int argc, char** argv)
             else if (k == "--follow-roughness") { a.follow_roughness = (float)std::atof(next().c_str()); have_follow_roughness = true; }
             else if (k == "--watertight") watertight = true;
             else if (k == "--denoise") a.denoise = true;
+            else if (k == "--adds") { a.adds = std::atoi(next().c_str()); have_adds = true; }
             else if (k == "--convert-png" || k == "--convert-hdr") { // codec self-test hooks: decode with our reader, re-encode with our writer
                 std::string in = next(), out = next();
                 imgio::Image img = k == "--convert-png" ? imgio::load_png_rgba8(in) : imgio::load_hdr_as_ldr_rgba8(in);
@@ -297,6 +317,9 @@ int main(int argc, char** argv)
             else throw std::runtime_error("unknown option " + k);
         }
         if (gpus < 0) throw std::runtime_error("--gpus needs a positive count");
+        if (have_adds && a.adds < 1) throw std::runtime_error("--adds needs a positive number of adds per frame");
+        if (have_adds && (gpus > 0 || have_devices)) throw std::runtime_error("--adds cannot be combined with --gpus / --devices (pt_accum_* has no group form)");
+        if (have_adds && have_batch) throw std::runtime_error("--adds cannot be combined with --batch (there are no batches of accumulations)");
         if (have_batch && a.batch < 1) throw std::runtime_error("--batch needs a positive number of frames per batch");
         if (have_batch && (gpus > 0 || have_devices)) throw std::runtime_error("--batch cannot be combined with --gpus / --devices yet (pt_group_* has no batch call)");
         if (have_devices) {
@@ -318,6 +341,8 @@ int main(int argc, char** argv)
 
         std::fprintf(stderr, "Parsing settings\n");
         a.settings = host::parse_settings(settings_path);
+        if (have_adds && a.adds > a.settings.max_samples)
+            throw std::runtime_error("--adds " + std::to_string(a.adds) + " exceeds max_samples = " + std::to_string(a.settings.max_samples) + " (every add needs at least one sample)");
         std::fprintf(stderr, "Parsing camera\nParsing materials\n");
         a.scene = host::load_scene(assets, a.settings.scene);
         for (auto const& m : a.scene.materials) std::fprintf(stderr, " - %s\n", m.name.c_str());

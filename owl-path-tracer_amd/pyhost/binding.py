@@ -74,6 +74,17 @@ class AovParams(C.Structure):
     _fields_ = [("n_samples", C.c_int32), ("max_follow", C.c_int32), ("roughness_max", C.c_float), ("reserved", C.c_int32)]
 
 
+class AccumParams(C.Structure):
+    """pt_accum_params: n_samples (1..65535) for every active pixel, max_pixel_samples (0: no cap), noise_threshold (0: uniform add), reserved (0)."""
+    _fields_ = [("n_samples", C.c_int32), ("max_pixel_samples", C.c_int32), ("noise_threshold", C.c_float), ("reserved", C.c_int32)]
+
+
+class AccumInfo(C.Structure):
+    """pt_accum_info."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("max_path_depth", C.c_int32), ("adds", C.c_int32), ("owned_pixels", C.c_int64),
+                ("active_pixels", C.c_int64), ("samples_total", C.c_uint64)]
+
+
 class Stats(C.Structure):
     _fields_ = [("kernel_ms", C.c_double), ("launches", C.c_int32), ("vgprs", C.c_int32), ("sgprs", C.c_int32), ("lds_bytes", C.c_int32),
                 ("block", C.c_int32), ("grid", C.c_int32), ("stack_entries", C.c_int32),
@@ -100,7 +111,9 @@ EXPORTS = ["pt_create", "pt_destroy", "pt_last_error", "pt_abi_version", "pt_upl
            "pt_render_aov", "pt_render_aov_device", "pt_group_render_aov", "pt_debug_aov_host",
            "pt_denoise_default_params", "pt_denoise", "pt_denoise_device", "pt_debug_denoise_host",
            "pt_aov_default_params", "pt_render_aov_follow", "pt_render_aov_follow_device", "pt_group_render_aov_follow", "pt_debug_aov_follow_host",
-           "pt_render_aov_batch", "pt_render_aov_batch_device", "pt_denoise_batch", "pt_denoise_batch_device"]
+           "pt_render_aov_batch", "pt_render_aov_batch_device", "pt_denoise_batch", "pt_denoise_batch_device",
+           "pt_accum_default_params", "pt_accum_begin", "pt_accum_add", "pt_accum_add_device", "pt_accum_read", "pt_accum_info_get", "pt_accum_end",
+           "pt_debug_accum_resolve_host", "pt_debug_accum_select_host", "pt_debug_accum_state"]
 PT_DENOISE_DEMODULATE = 1
 PT_TREE_DEVICE = 16  # pt_debug_export_tree: ORed into `which`, the array as HBM holds it
 PT_COMM_ID_BYTES = 128
@@ -208,6 +221,20 @@ def lib():
     L.pt_render_aov_batch_device.argtypes = [C.c_void_p, C.POINTER(Frame), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(AovParams), C.c_void_p, C.c_void_p]
     L.pt_denoise_batch.argtypes = [C.c_void_p, fp, fp, C.c_int32, C.c_int32, C.c_int32, C.POINTER(DenoiseParams), fp, C.POINTER(C.c_uint32)]
     L.pt_denoise_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(DenoiseParams), C.c_void_p, C.c_void_p, C.c_void_p]
+    u32p = C.POINTER(C.c_uint32)
+    L.pt_accum_default_params.restype = None
+    L.pt_accum_default_params.argtypes = [C.POINTER(AccumParams)]
+    L.pt_accum_begin.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_int32, C.c_int32, C.c_int32]
+    L.pt_accum_add.argtypes = [C.c_void_p, C.POINTER(AccumParams), fp, u32p]
+    L.pt_accum_add_device.argtypes = [C.c_void_p, C.POINTER(AccumParams), C.c_void_p, C.c_void_p, C.c_void_p]
+    L.pt_accum_read.argtypes = [C.c_void_p, fp, u32p, fp, u32p]
+    L.pt_accum_info_get.argtypes = [C.c_void_p, C.POINTER(AccumInfo)]
+    L.pt_accum_end.argtypes = [C.c_void_p]
+    L.pt_debug_accum_resolve_host.argtypes = [C.c_void_p, C.c_int64, fp, fp, fp, u32p, u32p, u32p, u8p, u8p, C.c_int32, fp, u32p, fp]
+    L.pt_debug_accum_resolve_host.restype = C.c_int64
+    L.pt_debug_accum_select_host.argtypes = [C.c_void_p, fp, u32p, u8p, C.c_int64, C.POINTER(AccumParams), u8p]
+    L.pt_debug_accum_select_host.restype = C.c_int64
+    L.pt_debug_accum_state.argtypes = [C.c_void_p, fp, fp, u32p, u32p, u32p]
     _lib = L
     return L
 
@@ -302,6 +329,17 @@ def aov_default_params(**changes):
     lib().pt_aov_default_params(C.byref(p))
     for k, v in changes.items():
         if k not in dict(AovParams._fields_):
+            raise KeyError(k)
+        setattr(p, k, v)
+    return p
+
+
+def accum_default_params(**changes):
+    """pt_accum_default_params (16 samples, no cap, threshold 0 = uniform), with the given fields changed."""
+    p = AccumParams()
+    lib().pt_accum_default_params(C.byref(p))
+    for k, v in changes.items():
+        if k not in dict(AccumParams._fields_):
             raise KeyError(k)
         setattr(p, k, v)
     return p
@@ -634,6 +672,79 @@ class Context:
         hipStream_t as an integer, None = the context's own stream; ordering and lifetime as render_device."""
         self._check(lib().pt_denoise_device(self._h, C.c_void_p(d_rgb), C.c_void_p(d_aov), W, H, C.byref(params) if params is not None else None, C.c_void_p(d_out_rgb),
                                             C.c_void_p(d_out_rgba8) if d_out_rgba8 else None, C.c_void_p(stream) if stream else None), "pt_denoise_device")
+
+    # ---- progressive accumulation (pt_accum_*) ----
+    def accum_begin(self, cam, W, H, max_depth):
+        """pt_accum_begin: a frame that grows by accum_add; fixes camera, size, depth and the pixel shard."""
+        self._check(lib().pt_accum_begin(self._h, C.byref(cam), W, H, max_depth), "pt_accum_begin")
+        self._accum_shape = (H, W)
+
+    def accum_add(self, params=None, want_rgb=True, want_rgba8=False):
+        """pt_accum_add: params an AccumParams (None: the defaults) -> (rgb (H, W, 3) or None, rgba8 (H, W) or None) of the frame so far."""
+        H, W = self._accum_shape
+        rgb = np.empty((H, W, 3), np.float32) if want_rgb else None
+        rgba = np.empty((H, W), np.uint32) if want_rgba8 else None
+        self._check(lib().pt_accum_add(self._h, C.byref(params) if params is not None else None, rgb.ctypes.data_as(C.POINTER(C.c_float)) if want_rgb else None,
+                                       rgba.ctypes.data_as(C.POINTER(C.c_uint32)) if want_rgba8 else None), "pt_accum_add")
+        return rgb, rgba
+
+    def accum_add_device(self, params=None, d_out_rgb=None, d_out_rgba8=None, stream=None):
+        """pt_accum_add_device: asynchronous, the frame so far left in HBM at the device pointers (integers, each may be None); stream and
+        ordering as render_device.  An add that selects its pixels waits on the host for the size of its active set."""
+        self._check(lib().pt_accum_add_device(self._h, C.byref(params) if params is not None else None, C.c_void_p(d_out_rgb) if d_out_rgb else None,
+                                              C.c_void_p(d_out_rgba8) if d_out_rgba8 else None, C.c_void_p(stream) if stream else None), "pt_accum_add_device")
+
+    def accum_read(self):
+        """pt_accum_read -> dict(rgb (H, W, 3), rgba8, noise, samples (H, W each)) in framebuffer order."""
+        H, W = self._accum_shape
+        out = dict(rgb=np.empty((H, W, 3), np.float32), rgba8=np.empty((H, W), np.uint32), noise=np.empty((H, W), np.float32), samples=np.empty((H, W), np.uint32))
+        fp, up = C.POINTER(C.c_float), C.POINTER(C.c_uint32)
+        self._check(lib().pt_accum_read(self._h, out["rgb"].ctypes.data_as(fp), out["rgba8"].ctypes.data_as(up), out["noise"].ctypes.data_as(fp),
+                                        out["samples"].ctypes.data_as(up)), "pt_accum_read")
+        return out
+
+    def accum_info(self):
+        i = AccumInfo()
+        self._check(lib().pt_accum_info_get(self._h, C.byref(i)), "pt_accum_info_get")
+        return {k: getattr(i, k) for k, _ in AccumInfo._fields_}
+
+    def accum_end(self):
+        self._check(lib().pt_accum_end(self._h), "pt_accum_end")
+
+    def accum_state(self):
+        """pt_debug_accum_state -> dict(sum, half (H, W, 3), n, n_half, passes (H, W)): the raw state in framebuffer order."""
+        H, W = self._accum_shape
+        out = dict(sum=np.empty((H, W, 3), np.float32), half=np.empty((H, W, 3), np.float32), n=np.empty((H, W), np.uint32), n_half=np.empty((H, W), np.uint32),
+                   passes=np.empty((H, W), np.uint32))
+        fp, up = C.POINTER(C.c_float), C.POINTER(C.c_uint32)
+        self._check(lib().pt_debug_accum_state(self._h, out["sum"].ctypes.data_as(fp), out["half"].ctypes.data_as(fp), out["n"].ctypes.data_as(up),
+                                               out["n_half"].ctypes.data_as(up), out["passes"].ctypes.data_as(up)), "pt_debug_accum_state")
+        return out
+
+    def accum_resolve_host(self, sum_, seen, half, n, n_half, passes, active, owned, n_samples):
+        """pt_debug_accum_resolve_host on flat arrays (sum, seen, half: (N, 3) float32; n, n_half, passes: (N,) uint32; active, owned: (N,)
+        uint8).  The inputs are not changed -> dict(seen, half, n, n_half, passes, rgb, rgba8, noise)."""
+        fp, up, bp = C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.POINTER(C.c_uint8)
+        s = np.ascontiguousarray(sum_, np.float32)
+        N = s.shape[0]
+        o = dict(seen=np.array(seen, np.float32), half=np.array(half, np.float32), n=np.array(n, np.uint32), n_half=np.array(n_half, np.uint32),
+                 passes=np.array(passes, np.uint32), rgb=np.empty((N, 3), np.float32), rgba8=np.empty(N, np.uint32), noise=np.empty(N, np.float32))
+        a, w = np.ascontiguousarray(active, np.uint8), np.ascontiguousarray(owned, np.uint8)
+        rc = lib().pt_debug_accum_resolve_host(self._h, N, s.ctypes.data_as(fp), o["seen"].ctypes.data_as(fp), o["half"].ctypes.data_as(fp), o["n"].ctypes.data_as(up),
+                                               o["n_half"].ctypes.data_as(up), o["passes"].ctypes.data_as(up), a.ctypes.data_as(bp), w.ctypes.data_as(bp), int(n_samples),
+                                               o["rgb"].ctypes.data_as(fp), o["rgba8"].ctypes.data_as(up), o["noise"].ctypes.data_as(fp))
+        self._check(int(rc), "pt_debug_accum_resolve_host")
+        return o
+
+    def accum_select_host(self, noise, n, owned, params=None):
+        """pt_debug_accum_select_host -> (active flags (N,) uint8, their count)."""
+        fp, up, bp = C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.POINTER(C.c_uint8)
+        z, m, w = np.ascontiguousarray(noise, np.float32).ravel(), np.ascontiguousarray(n, np.uint32).ravel(), np.ascontiguousarray(owned, np.uint8).ravel()
+        act = np.empty(z.size, np.uint8)
+        rc = lib().pt_debug_accum_select_host(self._h, z.ctypes.data_as(fp), m.ctypes.data_as(up), w.ctypes.data_as(bp), z.size, C.byref(params) if params is not None else None,
+                                              act.ctypes.data_as(bp))
+        self._check(int(rc), "pt_debug_accum_select_host")
+        return act, int(rc)
 
     def comm_init_rank(self, unique_id, rank, world):
         buf = (C.c_uint8 * PT_COMM_ID_BYTES).from_buffer_copy(unique_id)
