@@ -170,7 +170,7 @@ int pt_render(pt_ctx* ctx, const pt_camera* cam, int32_t width, int32_t height, 
  * every call that touches what a frame in flight uses is ordered after the context's LAST ASYNCHRONOUS CALL, whichever stream that
  * call was given.  So any call of this header may follow a pt_*_device call at once, with no pt_synchronize between them.
  *   - The asynchronous calls (pt_render_device, pt_render_batch_device, pt_render_aov_device, pt_render_aov_follow_device, pt_render_aov_batch_device, pt_denoise_device,
- *     pt_denoise_batch_device, pt_accum_add_device, pt_reduce_framebuffer) wait ON THE
+ *     pt_denoise_batch_device, pt_denoise_var_device, pt_accum_add_device, pt_accum_denoise_device, pt_reduce_framebuffer) wait ON THE
  *     DEVICE: the stream they are given waits for an event recorded at the end of the previous asynchronous call - only if that call
  *     used another stream; on the same stream the stream's own order suffices and nothing is added.  The host returns at once, with
  *     two exceptions that existed before: a frame of another size, shard or batch length rewrites the pixel queue and a frame that
@@ -178,11 +178,11 @@ int pt_render(pt_ctx* ctx, const pt_camera* cam, int32_t width, int32_t height, 
  *     before) - both first wait on the host for the frame in flight; pt_render_batch_device and pt_render_aov_batch_device
  *     return when their per-frame tables have reached HBM, i.e. after whatever precedes them on `stream`; and a pt_accum_add_device that
  *     selects its pixels returns when the count of its active set has reached the host (see there).
- *   - The blocking renders (pt_render, pt_render_batch, pt_render_aov, pt_render_aov_follow, pt_render_aov_batch, pt_accum_add), pt_denoise and pt_denoise_batch run on the context's stream behind the same device-side wait
+ *   - The blocking renders (pt_render, pt_render_batch, pt_render_aov, pt_render_aov_follow, pt_render_aov_batch, pt_accum_add), pt_denoise, pt_denoise_batch, pt_denoise_var and pt_accum_denoise run on the context's stream behind the same device-side wait
  *     and return with the context idle.  After a blocking call, or on the context's own stream, they add no wait at all.
  *   - The calls that change or read what a frame uses WAIT ON THE HOST for the last asynchronous call's stream (if it is not the
  *     context's) and then for the context's: pt_set_materials, pt_set_environment, pt_update_vertices, pt_upload_scene,
- *     pt_set_pixel_shard when it changes the shard of a queue in use, pt_accum_begin, pt_accum_read, pt_accum_end, pt_comm_destroy, pt_destroy, pt_debug_eval and the pt_debug_*
+ *     pt_set_pixel_shard when it changes the shard of a queue in use, pt_accum_begin, pt_accum_read, pt_accum_variance, pt_accum_end, pt_comm_destroy, pt_destroy, pt_debug_eval and the pt_debug_*
  *     readers of device state - and pt_synchronize, which is that wait plus the watchdog check.  A frame enqueued before such a call
  *     renders the state before it, a frame enqueued after it the state after it.
  *   - pt_get_stats waits for the end of the last frame's kernels (an event), not for the stream.
@@ -193,7 +193,7 @@ int pt_render(pt_ctx* ctx, const pt_camera* cam, int32_t width, int32_t height, 
 int pt_render_device(pt_ctx* ctx, const pt_camera* cam, int32_t width, int32_t height, int32_t max_samples, int32_t max_path_depth,
                      void* d_out_rgb, void* d_out_rgba8, void* stream);
 /* Waits on the host for the context's last asynchronous call - pt_render_device, pt_render_batch_device, pt_render_aov_device,
- * pt_render_aov_follow_device, pt_render_aov_batch_device, pt_denoise_device, pt_denoise_batch_device, pt_accum_add_device or pt_reduce_framebuffer, on the stream it was given - and for the context's own stream.  Every earlier asynchronous call of the context
+ * pt_render_aov_follow_device, pt_render_aov_batch_device, pt_denoise_device, pt_denoise_batch_device, pt_denoise_var_device, pt_accum_add_device, pt_accum_denoise_device or pt_reduce_framebuffer, on the stream it was given - and for the context's own stream.  Every earlier asynchronous call of the context
  * is complete then as well, whatever stream it used: each was ordered before the next (see pt_render_device).  Returns PT_E_HIP if a
  * wave's watchdog fired during the last frame (the image is then incomplete); pt_get_stats reports the same.  PT_OK at once on an idle
  * or host-only context.  A caller's stream may be destroyed once this has returned. */
@@ -403,7 +403,7 @@ int64_t pt_debug_denoise_host(pt_ctx* ctx, const float* rgb, const float* aov, i
 /* ---- progressive accumulation: a frame that grows by "adds", with a per-pixel noise estimate and adaptive adds (no reference
  * counterpart: the reference restarts every frame at sample 0) ----
  * A context holds at most ONE accumulation.  It owns its device buffers (62 bytes per pixel of the frame beside the 16 of the image); no other
- * call of this header reads or writes them.  pt_accum_begin fixes camera, size, depth and the pixel shard as they are at that moment;
+ * call of this header writes them (pt_accum_variance and pt_accum_denoise, further down, read them).  pt_accum_begin fixes camera, size, depth and the pixel shard as they are at that moment;
  * every pt_accum_add gives the pixels of its ACTIVE SET n_samples more samples of their own RNG streams and returns the image so far.
  * STATE per pixel: rng and sum[3] - the render kernel's own rng_state / accum at the launch id x + W*y - and seen[3], half[3], n, n_half,
  * passes, noise.  pt_accum_begin sets noise = +inf and everything else 0.
@@ -477,6 +477,69 @@ int64_t pt_debug_accum_resolve_host(pt_ctx* ctx, int64_t n_pixels, const float* 
                                     const uint8_t* active, const uint8_t* owned, int32_t n_samples, float* out_rgb, uint32_t* out_rgba8, float* noise);
 int64_t pt_debug_accum_select_host(pt_ctx* ctx, const float* noise, const uint32_t* n, const uint8_t* owned, int64_t n_pixels, const pt_accum_params* p, uint8_t* active);
 int pt_debug_accum_state(pt_ctx* ctx, float* sum, float* half, uint32_t* n, uint32_t* n_half, uint32_t* passes);
+
+/* ---- variance-guided denoise of a growing frame (no reference counterpart) ----
+ * pt_denoise's colour sigma is a constant in absolute units, right for one noise level only: as an accumulation gathers samples the
+ * filtered frame stops improving.  This filter is the spatial stage of SVGF (Schied et al. 2017): the same a-trous kernel, but the
+ * colour distance is measured in units of the pixel's own estimated VARIANCE, and that variance is filtered along with the colour, so
+ * the filter narrows by itself as the frame converges.  The accumulation already stores what the estimate needs (half, n_half).  For a
+ * first preview of a few samples pt_denoise stays the better call: one difference of two halves is a noisy variance estimate.
+ * No batch form and no group form: like pt_denoise it needs the whole frame (with N GPUs: on rank 0 after the reduce).
+ *
+ * 1. VARIANCE OF AN ACCUMULATION'S PIXELS (csrc/pt_accum_math.h accum_variance_pixel, ONE copy for the kernel and its CPU twin), with
+ *    VMAX = 1e30f, per owned pixel from sum, half, n, n_half:
+ *      n_half == 0:  var_k = VMAX, k = 0..2 (unknown).
+ *      otherwise:    ia = 1.0f / (float)n_half, ib = 1.0f / (float)(n - n_half) (resolve's own expressions);
+ *                    fh = (float)n_half / (float)n, r = fh * (1.0f - fh);
+ *                    a_k = half_k * ia, b_k = (sum_k - half_k) * ib, e_k = a_k - b_k;  var_k = r * (e_k * e_k);
+ *                    if !(var_k <= VMAX) var_k = VMAX (NaN and +inf included).
+ *      colour:       n >= 1: sum_k * (1.0f / (float)n) (resolve's expression), else +0.
+ *    Pixels that are not owned are +0 in both outputs.  Why r: E[(a - b)^2] = s^2 (1/n_half + 1/(n - n_half)), and the variance of the
+ *    pixel's mean is s^2 / n.
+ *    pt_accum_variance writes the W*H*3 floats of the map in framebuffer order; it waits on the host like pt_accum_read.
+ *    pt_debug_accum_variance_host: the twin on flat arrays of n_pixels pixels, like the other accumulation twins; returns n_pixels.
+ * 2. THE FILTER.  pt_denoise_var(rgb, var, aov): var is W*H*3 floats laid out like rgb, the per-channel variance of the pixel value;
+ *    every other buffer, the order and out_rgb == rgb are as for pt_denoise.  It reuses pt_denoise_params; HERE sigma_color COUNTS
+ *    STANDARD DEVIATIONS (default 3).  DEFINITION: that of pt_denoise, same arithmetic contract, fma_ only where written, except:
+ *      Prepare:  rgb, d_k, c0 and kz as in pt_denoise;  v_k = var_k without the flag, v_k = var_k / (d_k * d_k) with it;
+ *                v = (v_0 + v_1) + v_2,  v0(p) = (v >= 0.0f && v <= VMAX) ? v : VMAX.
+ *      Host constants:  kn, ka as before;  s2 = sigma_color * sigma_color.  No per-iteration halving: the filtered variance narrows
+ *                the colour term by itself.
+ *      Iteration i, s = 1 << i, at pixel p:
+ *        (1) the variance around p, over the 3 x 3 DIRECT neighbours (distance 1, not s):  gs = 0, gw = 0;  for dy = -1..1 (outer), dx =
+ *            -1..1 (inner), taps outside the frame skipped:  g = m[|dx|] * m[|dy|] with m = {1/2, 1/4};  gs = fma_(g, v_i(q), gs),
+ *            gw = gw + g;  vb = gs / gw.
+ *        (2) kc_p = 0 if s2 is +infinity (no colour term), else kc_p = 1.0f / fma_(s2, vb, 1e-10f).
+ *        (3) the 25 taps of pt_denoise in its order with kc_p in the place of kc_i; every tap that is taken also does
+ *            vs = fma_(w * w, v_i(q), vs) (centre tap: w = h).  c_{i+1} = sum / wsum,  v_{i+1} = min_(vs / (wsum * wsum), VMAX).
+ *      Finish:   that of pt_denoise.
+ *    CONSEQUENCES: a pixel whose variance is unknown is filtered by its guides alone; a variance map of 0 leaves every pixel that
+ *    differs from its neighbours as it is.
+ *    REFUSED: everything pt_denoise refuses, and NULL var; on a host-only context valid arguments give PT_E_NO_DEVICE, invalid ones
+ *    PT_E_INVALID.  pt_denoise_var is blocking like pt_denoise; pt_denoise_var_device is asynchronous like pt_denoise_device (d_aov
+ *    16-byte aligned) and joins the asynchronous calls of the streams contract.  pt_get_stats afterwards: kernel_ms from the first to the
+ *    last kernel, launches = L + 2, block, grid, vgprs, lds_bytes those of the iteration kernel.
+ *    pt_debug_denoise_var_host: the CPU twin, works on a host-only context; out_var (optional, W*H floats) receives v_L; returns W*H.
+ * 3. ON THE ACCUMULATION, WITHOUT A HOST ROUND TRIP.  pt_accum_denoise / pt_accum_denoise_device run the variance kernel over the
+ *    accumulation's state and then the filter on resolve's image; W and H are the accumulation's.  They read the state and change none of
+ *    it: the next add, pt_accum_read and a pt_render afterwards are bit for bit what they are without the call, and the result is bit for
+ *    bit pt_denoise_var(pt_accum_read's rgb, pt_accum_variance's map, aov).  The blocking form behaves like pt_denoise; the device form is
+ *    asynchronous and ordered like pt_accum_add_device.  REFUSED by name before anything is touched: no accumulation; a pixel shard that
+ *    does not own the whole frame (the filter needs every pixel); a communicator (as pt_accum_add); NULL aov or out_rgb; the parameter
+ *    refusals of pt_denoise.  pt_get_stats afterwards: as pt_denoise_var with launches = L + 3.
+ * The four kernels are csrc/pt_denoise_var.hip; the numpy restatement is tests/denoise_var_ref.py. */
+void pt_denoise_var_default_params(pt_denoise_params* p);   /* 5, 0, 3.0f, 0.25f, 0.1f, 0.2f */
+int pt_denoise_var(pt_ctx* ctx, const float* rgb, const float* var, const float* aov, int32_t width, int32_t height,
+                   const pt_denoise_params* p /* NULL = defaults */, float* out_rgb, uint32_t* out_rgba8 /* optional */);
+int pt_denoise_var_device(pt_ctx* ctx, const void* d_rgb, const void* d_var, const void* d_aov, int32_t width, int32_t height, const pt_denoise_params* p,
+                          void* d_out_rgb, void* d_out_rgba8, void* stream);
+int64_t pt_debug_denoise_var_host(pt_ctx* ctx, const float* rgb, const float* var, const float* aov, int32_t width, int32_t height, const pt_denoise_params* p,
+                                  float* out_rgb, uint32_t* out_rgba8, float* out_var /* optional: v_L, W*H floats */);
+int pt_accum_variance(pt_ctx* ctx, float* out_var);
+int64_t pt_debug_accum_variance_host(pt_ctx* ctx, int64_t n_pixels, const float* sum, const float* half, const uint32_t* n, const uint32_t* n_half,
+                                     const uint8_t* owned, float* out_rgb, float* out_var);
+int pt_accum_denoise(pt_ctx* ctx, const float* aov, const pt_denoise_params* p /* NULL = defaults */, float* out_rgb, uint32_t* out_rgba8 /* optional */);
+int pt_accum_denoise_device(pt_ctx* ctx, const void* d_aov, const pt_denoise_params* p, void* d_out_rgb, void* d_out_rgba8 /* optional */, void* stream);
 
 /* ---- N GPUs: pixel tiles sharded over ranks + ONE RCCL sum-reduce of the float3 framebuffer onto rank 0 (pt_comm.cpp) ----
  * No reference counterpart (the reference is single-GPU: create_context(nullptr, 1), application.cpp:62); for N > 1 these

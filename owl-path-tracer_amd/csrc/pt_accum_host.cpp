@@ -24,6 +24,22 @@ static inline float pt_host_uint_as_float(uint32_t u) { float x; std::memcpy(&x,
 using namespace pti;
 using namespace ptd;
 
+namespace pti {
+
+int need_accum(pt_ctx* c, const char* who)
+{
+    if (!c->acc) return fail(c, PT_E_INVALID, "%s: the context has no accumulation (pt_accum_begin not called)", who);
+    return PT_OK;
+}
+
+int refuse_comm(pt_ctx* c, const char* who)
+{
+    if (c->comm) return fail(c, PT_E_INVALID, "%s: a context with a communicator has no accumulation yet (render the ranks' shards with pt_set_pixel_shard and reduce them yourself)", who);
+    return PT_OK;
+}
+
+} // namespace pti
+
 namespace {
 
 constexpr int64_t kMaxPixelSamples = 2147483648ll - 65536; // a pixel's n stays below this: n and n + n_samples are exact in int32 everywhere
@@ -47,18 +63,6 @@ int check_accum_context(pt_ctx* c, const char* who)
     if (c->opt.latency) return fail(c, PT_E_INVALID, "%s: the per-pixel latency diagnostics (option latency) are per frame; switch them off for an accumulation", who);
     if (c->opt.timeline) return fail(c, PT_E_INVALID, "%s: the chunk timeline (option timeline) is per frame; switch it off for an accumulation", who);
     if (!c->have_scene) return fail(c, PT_E_NO_SCENE, "%s: no geometries (pt_upload_scene not called)", who);
-    return PT_OK;
-}
-
-int need_accum(pt_ctx* c, const char* who)
-{
-    if (!c->acc) return fail(c, PT_E_INVALID, "%s: the context has no accumulation (pt_accum_begin not called)", who);
-    return PT_OK;
-}
-
-int refuse_comm(pt_ctx* c, const char* who)
-{
-    if (c->comm) return fail(c, PT_E_INVALID, "%s: a context with a communicator has no accumulation yet (render the ranks' shards with pt_set_pixel_shard and reduce them yourself)", who);
     return PT_OK;
 }
 
@@ -351,6 +355,23 @@ int64_t pt_debug_accum_resolve_host(pt_ctx* c, int64_t n_pixels, const float* su
         passes[i] = s.passes;
         out_rgba8[i] = o.rgba8;
         noise[i] = o.noise;
+    }
+    return n_pixels;
+}
+
+int64_t pt_debug_accum_variance_host(pt_ctx* c, int64_t n_pixels, const float* sum, const float* half, const uint32_t* n, const uint32_t* n_half, const uint8_t* owned,
+                                     float* out_rgb, float* out_var)
+{
+    if (!c) return PT_E_INVALID;
+    const char* who = "pt_debug_accum_variance_host";
+    if (!sum || !half || !n || !n_half || !owned || !out_rgb || !out_var) return fail(c, PT_E_INVALID, "%s: NULL array", who);
+    if (n_pixels < 0 || n_pixels > 0x7fffffff) return fail(c, PT_E_INVALID, "%s: n_pixels %lld outside 0..2^31-1", who, (long long)n_pixels);
+    for (int64_t i = 0; i < n_pixels; ++i) {
+        if (!owned[i]) {
+            for (int k = 0; k < 3; ++k) out_rgb[3 * i + k] = out_var[3 * i + k] = 0.0f;
+            continue;
+        }
+        accum_variance_pixel(sum + 3 * i, half + 3 * i, n[i], n_half[i], out_rgb + 3 * i, out_var + 3 * i);
     }
     return n_pixels;
 }

@@ -57,4 +57,29 @@ PTD bool accum_select_pixel(float noise, uint32_t n, uint32_t cap, float thresho
     return (cap == 0u || n < cap) && (threshold == 0.0f || !(noise <= threshold));
 }
 
+// Variance of an owned pixel's value from the two disjoint halves of its samples (include/mi355pt.h, "variance-guided denoise"): ONE
+// copy for pt_accum_variance_kernel (pt_denoise_var.hip) and pt_debug_accum_variance_host.  E[(a - b)^2] = s^2 (1 / n_half + 1 / (n -
+// n_half)) and the variance of the pixel's mean is s^2 / n, hence r.  kVarMax stands for "unknown"; ia, ib and the colour are resolve's
+// own expressions.
+constexpr float kVarMax = 1e30f;
+PTD void accum_variance_pixel(const float sum[3], const float half[3], uint32_t n, uint32_t n_half, float rgb[3], float var[3])
+{
+    rgb[0] = rgb[1] = rgb[2] = 0.0f;
+    if (n >= 1u) {
+        const float inv = 1.0f / (float)n;
+        for (int k = 0; k < 3; ++k) rgb[k] = sum[k] * inv;
+    }
+    if (n_half == 0u) {
+        var[0] = var[1] = var[2] = kVarMax;
+        return;
+    }
+    const float ia = 1.0f / (float)n_half, ib = 1.0f / (float)(n - n_half);
+    const float fh = (float)n_half / (float)n, r = fh * (1.0f - fh);
+    for (int k = 0; k < 3; ++k) {
+        const float a = half[k] * ia, b = (sum[k] - half[k]) * ib, e = a - b;
+        const float v = r * (e * e);
+        var[k] = (v <= kVarMax) ? v : kVarMax; // NaN and +inf included
+    }
+}
+
 } // namespace ptd

@@ -1,6 +1,7 @@
 // pt_guides.cpp -- what goes with a frame: the guide pass (pt_render_aov*: first hit or follow mode, one frame or the frames of a batch)
-// and the denoiser (pt_denoise*, one frame or a batch), each ONE device path behind its asynchronous and blocking entry points.
-// Neither reads the render's pixel queue or touches its buffers and state (d_laps, slots): their own are d_aov_ws and d_dn_ws.
+// the denoiser (pt_denoise*, one frame or a batch) and the variance-guided denoiser (pt_denoise_var*, and pt_accum_denoise* /
+// pt_accum_variance on the context's accumulation), each ONE device path behind its asynchronous and blocking entry points.
+// None reads the render's pixel queue or touches its buffers and state (d_laps, slots): their own are d_aov_ws, d_dn_ws and d_dn_var.
 #include <algorithm>
 #include <cstring>
 
@@ -276,6 +277,112 @@ int denoise_blocking(pt_ctx* c, const DenoiseJob& j, const float* rgb, const flo
     });
 }
 
+// ---- variance-guided denoiser (pt_denoise_var*, pt_accum_denoise*, pt_accum_variance) ------------------------------------------
+// The variance kernel over the accumulation's state, into d_out_var (W*H*3 floats, framebuffer order).  It reads the state and writes none.
+int accum_variance_launch(pt_ctx* c, void* d_out_var, hipStream_t stream)
+{
+    const Accum& a = *c->acc;
+    PtAccumVarArgs V{};
+    V.sum = (const float*)a.sum.p;
+    V.half = (const float*)a.half.p;
+    V.n = (const uint32_t*)a.n.p;
+    V.n_half = (const uint32_t*)a.n_half.p;
+    V.owned = (const uint8_t*)a.owned.p;
+    V.out_var = (float*)d_out_var;
+    V.n_frame = (uint32_t)a.w * (uint32_t)a.h;
+    V.width = a.w;
+    V.height = a.h;
+    HIP_TRY(c, pt_launch_accum_variance(&V, stream));
+    return PT_OK;
+}
+
+// The filter over device buffers, ONE path: prepare, L iteration launches, finish on the kernels of pt_denoise_var.hip, its records in
+// d_dn_ws like pt_denoise's.  accum: the frame is the context's accumulation - the variance kernel first (its map in d_dn_var), the colour
+// resolve's own image; d_rgb and d_var are not looked at.
+struct DenoiseVarJob {
+    bool accum;
+    int W, H;
+    pt_denoise_params prm; // checked by the caller (check_denoise_args)
+};
+
+int denoise_var_device(pt_ctx* c, const DenoiseVarJob& j, const void* d_rgb, const void* d_var, const void* d_aov, void* d_out_rgb, void* d_out_rgba8, hipStream_t stream)
+{
+    const int W = j.W, H = j.H;
+    PtGeometry g{};
+    int grid = 0;
+    const hipError_t ge = pt_denoise_var_geometry(W, H, &g, &grid);
+    if (ge == hipErrorInvalidConfiguration) return fail(c, PT_E_LIMIT, "this build of the variance-guided denoise kernels spills registers to scratch; such builds are refused (pt_denoise_var.hip)");
+    HIP_TRY(c, ge);
+    const size_t npx = (size_t)W * H;
+    int rc;
+    if ((rc = ensure(c, c->d_dn_ws, pt_denoise_var_workspace_bytes(W, H)))) return rc; // (growing it first waits on the host for what is in flight)
+    if (j.accum && (rc = ensure(c, c->d_dn_var, npx * 12))) return rc;
+    PtDenoiseVarArgs A{};
+    A.rgb = (const float*)(j.accum ? c->acc->out.p : d_rgb);
+    A.var = (const float*)(j.accum ? c->d_dn_var.p : d_var);
+    A.aov = (const float*)d_aov;
+    A.out_rgb = (float*)d_out_rgb;
+    A.out_rgba8 = (uint32_t*)d_out_rgba8;
+    A.ws = c->d_dn_ws.p;
+    A.width = W;
+    A.height = H;
+    A.iterations = j.prm.iterations;
+    A.flags = j.prm.flags;
+    A.sigma_depth = j.prm.sigma_depth;
+    float kc_unused[8];
+    denoise_constants(j.prm, &A.kn, &A.ka, kc_unused);
+    A.s2 = j.prm.sigma_color * j.prm.sigma_color;
+    HIP_TRY(c, hipEventRecord(c->ev0, stream));
+    if (j.accum && (rc = accum_variance_launch(c, c->d_dn_var.p, stream))) return rc;
+    HIP_TRY(c, pt_launch_denoise_var(&A, stream));
+    HIP_TRY(c, hipEventRecord(c->ev1, stream)); // kernel_ms: from the first to the last kernel
+    note_pass(c, W, H, j.prm.iterations + 2 + (j.accum ? 1 : 0), grid, g, 0, false);
+    return PT_OK;
+}
+
+int denoise_var_async(pt_ctx* c, const DenoiseVarJob& j, const void* d_rgb, const void* d_var, const void* d_aov, void* d_out_rgb, void* d_out_rgba8, void* stream_v)
+{
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t stream = stream_v ? (hipStream_t)stream_v : c->stream;
+    return async_call(c, stream, [&] { return denoise_var_device(c, j, d_rgb, d_var, d_aov, d_out_rgb, d_out_rgba8, stream); });
+}
+
+// Host buffers: staged in d_dn_rgb / d_dn_var / d_dn_aov, filtered into d_dn_rgb, and back.  accum: only the guides are staged.
+int denoise_var_blocking(pt_ctx* c, const DenoiseVarJob& j, const float* rgb, const float* var, const float* aov, float* out_rgb, uint32_t* out_rgba8)
+{
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t npx = (size_t)j.W * (size_t)j.H;
+    return blocking_call(c, [&]() -> int {
+        int rc;
+        if ((rc = ensure(c, c->d_dn_rgb, npx * 12)) || (rc = ensure(c, c->d_dn_aov, npx * 32)) || (rc = ensure(c, c->d_dn_var, npx * 12))) return rc;
+        if (out_rgba8 && (rc = ensure(c, c->d_dn_out8, npx * 4))) return rc;
+        if (!j.accum) {
+            HIP_TRY(c, hipMemcpyAsync(c->d_dn_rgb.p, rgb, npx * 12, hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(c, hipMemcpyAsync(c->d_dn_var.p, var, npx * 12, hipMemcpyHostToDevice, c->stream));
+        }
+        HIP_TRY(c, hipMemcpyAsync(c->d_dn_aov.p, aov, npx * 32, hipMemcpyHostToDevice, c->stream));
+        if ((rc = denoise_var_device(c, j, c->d_dn_rgb.p, c->d_dn_var.p, c->d_dn_aov.p, c->d_dn_rgb.p, out_rgba8 ? c->d_dn_out8.p : nullptr, c->stream))) return rc;
+        return drain(c, {{out_rgb, c->d_dn_rgb.p, npx * 12}, {out_rgba8, c->d_dn_out8.p, npx * 4}});
+    });
+}
+
+// What the two forms of pt_accum_denoise refuse alike before anything is touched, a host-only context last; j->W, H = the accumulation's.
+int check_accum_denoise_args(pt_ctx* c, const char* who, const void* aov, const pt_denoise_params* p, const void* out_rgb, DenoiseVarJob* j)
+{
+    int rc;
+    if ((rc = need_accum(c, who))) return rc;
+    const Accum& a = *c->acc;
+    if ((uint64_t)a.n_owned != (uint64_t)a.w * (uint64_t)a.h)
+        return fail(c, PT_E_INVALID, "%s: the accumulation's pixel shard (%d of %d) owns %u of the frame's %lld pixels; the filter needs every pixel", who, a.rank, a.world, a.n_owned, (long long)a.w * a.h);
+    if ((rc = refuse_comm(c, who))) return rc;
+    if (!aov || !out_rgb) return fail(c, PT_E_INVALID, "%s: NULL %s", who, !aov ? "aov" : "out_rgb");
+    j->accum = true;
+    j->W = a.w;
+    j->H = a.h;
+    if ((rc = check_denoise_args(c, who, a.w, a.h, p, &j->prm, pt_denoise_var_default_params))) return rc;
+    return need_device(c);
+}
+
 // What the two forms of the denoise batch refuse alike before anything is touched, a host-only context last.
 int check_denoise_batch_args(pt_ctx* c, const char* who, int32_t n_frames, int32_t W, int32_t H, const pt_denoise_params* p, pt_denoise_params* eff)
 {
@@ -366,6 +473,65 @@ int pt_denoise(pt_ctx* c, const float* rgb, const float* aov, int32_t W, int32_t
     DenoiseJob j{false, 1, W, H};
     if ((rc = need_device(c)) || (rc = check_denoise_args(c, "pt_denoise", W, H, p, &j.prm))) return rc;
     return denoise_blocking(c, j, rgb, aov, out_rgb, out_rgba8);
+}
+
+int pt_denoise_var_device(pt_ctx* c, const void* d_rgb, const void* d_var, const void* d_aov, int32_t W, int32_t H, const pt_denoise_params* p, void* d_out_rgb, void* d_out_rgba8,
+                          void* stream_v)
+{
+    if (!c) return PT_E_INVALID;
+    if (!d_rgb || !d_var || !d_aov || !d_out_rgb) return fail(c, PT_E_INVALID, "pt_denoise_var_device: NULL %s", !d_rgb ? "d_rgb" : (!d_var ? "d_var" : (!d_aov ? "d_aov" : "d_out_rgb")));
+    int rc;
+    DenoiseVarJob j{false, W, H};
+    if ((rc = check_denoise_args(c, "pt_denoise_var_device", W, H, p, &j.prm, pt_denoise_var_default_params)) || (rc = need_device(c))) return rc;
+    return denoise_var_async(c, j, d_rgb, d_var, d_aov, d_out_rgb, d_out_rgba8, stream_v);
+}
+
+int pt_denoise_var(pt_ctx* c, const float* rgb, const float* var, const float* aov, int32_t W, int32_t H, const pt_denoise_params* p, float* out_rgb, uint32_t* out_rgba8)
+{
+    if (!c) return PT_E_INVALID;
+    if (!rgb || !var || !aov || !out_rgb) return fail(c, PT_E_INVALID, "pt_denoise_var: NULL %s", !rgb ? "rgb" : (!var ? "var" : (!aov ? "aov" : "out_rgb")));
+    int rc;
+    DenoiseVarJob j{false, W, H};
+    if ((rc = check_denoise_args(c, "pt_denoise_var", W, H, p, &j.prm, pt_denoise_var_default_params)) || (rc = need_device(c))) return rc;
+    return denoise_var_blocking(c, j, rgb, var, aov, out_rgb, out_rgba8);
+}
+
+int pt_accum_denoise_device(pt_ctx* c, const void* d_aov, const pt_denoise_params* p, void* d_out_rgb, void* d_out_rgba8, void* stream_v)
+{
+    if (!c) return PT_E_INVALID;
+    int rc;
+    DenoiseVarJob j{};
+    if ((rc = check_accum_denoise_args(c, "pt_accum_denoise_device", d_aov, p, d_out_rgb, &j))) return rc;
+    return denoise_var_async(c, j, nullptr, nullptr, d_aov, d_out_rgb, d_out_rgba8, stream_v);
+}
+
+int pt_accum_denoise(pt_ctx* c, const float* aov, const pt_denoise_params* p, float* out_rgb, uint32_t* out_rgba8)
+{
+    if (!c) return PT_E_INVALID;
+    int rc;
+    DenoiseVarJob j{};
+    if ((rc = check_accum_denoise_args(c, "pt_accum_denoise", aov, p, out_rgb, &j))) return rc;
+    return denoise_var_blocking(c, j, nullptr, nullptr, aov, out_rgb, out_rgba8);
+}
+
+int pt_accum_variance(pt_ctx* c, float* out_var)
+{
+    if (!c) return PT_E_INVALID;
+    int rc;
+    if ((rc = need_accum(c, "pt_accum_variance"))) return rc;
+    if (!out_var) return fail(c, PT_E_INVALID, "pt_accum_variance: NULL out_var");
+    if ((rc = need_device(c)) || (rc = wait_idle(c))) return rc;
+    const Accum& a = *c->acc;
+    const size_t npx = (size_t)a.w * a.h;
+    PtGeometry g{};
+    int grid = 0;
+    const hipError_t ge = pt_denoise_var_geometry(a.w, a.h, &g, &grid);
+    if (ge == hipErrorInvalidConfiguration) return fail(c, PT_E_LIMIT, "this build of the variance-guided denoise kernels spills registers to scratch; such builds are refused (pt_denoise_var.hip)");
+    HIP_TRY(c, ge);
+    if ((rc = ensure(c, c->d_dn_var, npx * 12)) || (rc = accum_variance_launch(c, c->d_dn_var.p, c->stream))) return rc;
+    HIP_TRY(c, hipMemcpyAsync(out_var, c->d_dn_var.p, npx * 12, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return check_watchdog(c);
 }
 
 int pt_denoise_batch_device(pt_ctx* c, const void* d_rgb, const void* d_aov, int32_t n_frames, int32_t W, int32_t H, const pt_denoise_params* p, void* d_out_rgb,

@@ -94,7 +94,7 @@ struct LastFrame {
 };
 
 // The context's progressive accumulation (pt_accum_*; pt_accum_host.cpp): the frame that grows by adds, and the owner of its state across
-// calls.  No other call of the header reads or writes these buffers.  Everything per pixel is indexed by the launch id x + W * y except
+// calls.  No other call of the header writes these buffers; pt_accum_variance and pt_accum_denoise (pt_guides.cpp) read them.  Everything per pixel is indexed by the launch id x + W * y except
 // out / out8 (framebuffer order).
 struct Accum {
     pt_camera cam{};
@@ -132,6 +132,7 @@ struct pt_ctx {
     DevBuf d_verts, d_vnormals, d_tri_vi, d_level_nodes, d_src4, d_src8, d_refit_ws; // option "dynamic": what the refit kernels read (pt_refit.hip)
     DevBuf d_aov, d_aov_ws; // guide pass: the frame of pt_render_aov / pt_group_render_aov; bound flag (64 words) + the waves' stack overflow columns
     DevBuf d_dn_ws, d_dn_rgb, d_dn_aov, d_dn_out8; // denoiser: the filter's records (pt_denoise_workspace_bytes); pt_denoise's staging of rgb (in and out), guides and RGBA8
+    DevBuf d_dn_var; // pt_denoise_var's staging of the variance map; pt_accum_variance's / pt_accum_denoise's map of the accumulation
     std::vector<DevBuf> d_textures;
 
     // pixel queue
@@ -185,8 +186,12 @@ PT_LOCAL int drain(pt_ctx* c, std::initializer_list<D2H> copies);
 PT_LOCAL int accum_frame(pt_ctx* c, const pt_camera* cam, int W, int H, int n_samples, int max_depth, bool first_add, uint32_t* d_rng, float* d_sum, hipStream_t stream,
                          bool ev0_recorded, const std::function<int()>& resolve);
 // pt_denoise_host.cpp
-PT_LOCAL int check_denoise_args(pt_ctx* c, const char* who, int W, int H, const pt_denoise_params* p, pt_denoise_params* eff); // the refusals of pt_denoise* and the twin; *eff = the parameters in effect
+PT_LOCAL int check_denoise_args(pt_ctx* c, const char* who, int W, int H, const pt_denoise_params* p, pt_denoise_params* eff,
+                                void (*defaults)(pt_denoise_params*) = pt_denoise_default_params); // the refusals of pt_denoise*, pt_denoise_var* and the twins; *eff = the parameters in effect (p null: defaults)
 PT_LOCAL void denoise_constants(const pt_denoise_params& p, float* kn, float* ka, float kc[8]); // the definition's host constants
+// pt_accum_host.cpp
+PT_LOCAL int need_accum(pt_ctx* c, const char* who);  // PT_E_INVALID by name without an accumulation
+PT_LOCAL int refuse_comm(pt_ctx* c, const char* who); // PT_E_INVALID by name with a communicator
 // pt_aov_host.cpp
 PT_LOCAL int check_aov_params(pt_ctx* c, const pt_aov_params* p, const char* who, pt_aov_params* eff); // the refusals of pt_render_aov_follow* and the twin; *eff = the parameters in effect
 // pt_comm.cpp

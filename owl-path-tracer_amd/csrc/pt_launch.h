@@ -80,6 +80,33 @@ struct PtDenoiseArgs {
     float kc[8];            // per iteration
 };
 
+// Variance-guided denoiser (pt_denoise_var, pt_accum_denoise; pt_denoise_var.hip): what its prepare, iteration and finish kernels take.
+// As PtDenoiseArgs; the colour record carries the summed variance v instead of kz, which moves to the albedo record.
+struct PtDenoiseVarArgs {
+    const float* rgb;       // W*H*3 floats, framebuffer order (may equal out_rgb)
+    const float* var;       // W*H*3 floats: per-channel variance of rgb
+    const float* aov;       // W*H*8 floats of the guide pass, 16-byte aligned
+    float* out_rgb;         // W*H*3 floats
+    uint32_t* out_rgba8;    // W*H, or null
+    void* ws;               // pt_denoise_var_workspace_bytes(W, H), 16-byte aligned
+    float4* col[2];         // colour r g b + v, ping-pong
+    float4* nz;             // normal x y z + depth
+    float4* alb;            // albedo r g b + kz
+    int32_t width, height, iterations, flags;
+    float sigma_depth, kn, ka, s2; // s2 = sigma_color^2 (+infinity: no colour term)
+};
+// ... and its variance kernel over an accumulation's state (arrays by launch id x + W * y, as PtAccumArgs): out_var in framebuffer order.
+struct PtAccumVarArgs {
+    const float* sum;
+    const float* half;
+    const uint32_t* n;
+    const uint32_t* n_half;
+    const uint8_t* owned;
+    float* out_var;          // W*H*3
+    uint32_t n_frame;        // W*H
+    int32_t width, height, pad;
+};
+
 // Progressive accumulation (pt_accum_*; pt_accum.hip): what its two kernels take.  Every per-pixel array is indexed by the launch id
 // x + W * y (the render kernel's index into rng_state / accum) except the two images, which are in framebuffer order.
 struct PtAccumArgs {
@@ -119,7 +146,13 @@ hipError_t pt_launch_accum_select(const PtAccumSelectArgs* a, hipStream_t stream
 size_t pt_denoise_workspace_bytes(int W, int H);
 hipError_t pt_denoise_geometry(int W, int H, PtGeometry* g, int* grid);
 hipError_t pt_launch_denoise(const PtDenoiseArgs* a, hipStream_t stream);
-// pt_denoise_batch.hip: the same over K frames of one size, back to back in every caller buffer (the pointers of *a are the first frame's),
+// pt_denoise_var.hip: the variance-guided filter, same conventions (prepare + `iterations` launches + finish); the geometry is the
+// iteration kernel's, hipErrorInvalidConfiguration if one of the FOUR kernels (the variance kernel included) needs scratch
+size_t pt_denoise_var_workspace_bytes(int W, int H);
+hipError_t pt_denoise_var_geometry(int W, int H, PtGeometry* g, int* grid);
+hipError_t pt_launch_denoise_var(const PtDenoiseVarArgs* a, hipStream_t stream);
+hipError_t pt_launch_accum_variance(const PtAccumVarArgs* a, hipStream_t stream);
+// pt_denoise_batch.hip: the kernels of pt_denoise.hip over K frames of one size, back to back in every caller buffer (the pointers of *a are the first frame's),
 // frame in blockIdx.z: 1 <= K <= 65535; workspace and grid cover all K frames
 size_t pt_denoise_batch_workspace_bytes(int W, int H, int K);
 hipError_t pt_denoise_batch_geometry(int W, int H, int K, PtGeometry* g, int* grid);

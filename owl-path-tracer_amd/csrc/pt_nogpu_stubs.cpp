@@ -36,6 +36,10 @@ hipError_t pt_launch_denoise(const PtDenoiseArgs*, hipStream_t) { return hipErro
 size_t pt_denoise_batch_workspace_bytes(int, int, int) { return 16; }
 hipError_t pt_denoise_batch_geometry(int, int, int, PtGeometry*, int*) { return hipErrorNotSupported; }
 hipError_t pt_launch_denoise_batch(const PtDenoiseArgs*, int, hipStream_t) { return hipErrorNotSupported; }
+size_t pt_denoise_var_workspace_bytes(int, int) { return 16; }
+hipError_t pt_denoise_var_geometry(int, int, PtGeometry*, int*) { return hipErrorNotSupported; }
+hipError_t pt_launch_denoise_var(const PtDenoiseVarArgs*, hipStream_t) { return hipErrorNotSupported; }
+hipError_t pt_launch_accum_variance(const PtAccumVarArgs*, hipStream_t) { return hipErrorNotSupported; }
 hipError_t pt_accum_geometry(PtGeometry*) { return hipErrorNotSupported; }
 hipError_t pt_launch_accum_resolve(const PtAccumArgs*, hipStream_t) { return hipErrorNotSupported; }
 hipError_t pt_launch_accum_select(const PtAccumSelectArgs*, hipStream_t) { return hipErrorNotSupported; }

@@ -22,6 +22,8 @@
 // --adds K (1 <= K <= max_samples: every frame is a progressive accumulation - pt_accum_begin, K uniform pt_accum_add of max_samples / K
 // samples, the remainder with the last, pt_accum_end; mi355pt.h, "progressive accumulation" - and the files are byte for byte those
 // without the flag; works with --watertight, --aov and --denoise, not with --gpus / --devices or --batch).
+// --denoise-variance (needs --adds K with K >= 2 and --aov N, not with --denoise: after every frame and its guides pt_accum_denoise with the
+// default parameters - mi355pt.h, "variance-guided denoise" - on the frame's accumulation; <name>_denoised.png = its RGBA8 image).
 #include <sys/stat.h>
 #include <unistd.h>
 
@@ -105,6 +107,7 @@ struct App {
     float follow_roughness = -1.0f; // --follow-roughness R: roughness_max (< 0: the default of pt_aov_default_params)
     bool denoise = false; // --denoise: pt_denoise of every frame with its guides
     int adds = 0;  // --adds K: every frame in K uniform adds of a progressive accumulation (0: one pt_render)
+    bool denoise_variance = false; // --denoise-variance: pt_accum_denoise of every frame's accumulation with its guides
 };
 
 void check(App& a, int rc, const char* what)
@@ -155,10 +158,12 @@ void write_guides(App& a, const std::string& base, const std::vector<float>& rgb
         imgio::write_png_rgba8(base + names[k], W, H, img[k]->data());
         std::printf("Image written to %s\n", (base + names[k]).c_str());
     }
-    if (!a.denoise) return;
+    if (!a.denoise && !a.denoise_variance) return;
     std::vector<float> out(npx * 3);
     std::vector<uint32_t> out8(npx);
-    if (pt_denoise(a.ctx, rgb.data(), g.data(), W, H, nullptr, out.data(), out8.data()) < 0) throw std::runtime_error(std::string("pt_denoise: ") + pt_last_error(a.ctx));
+    if (a.denoise_variance) { // the frame's accumulation is still open (render_frame): filtered where it lies, with its own variance estimate
+        if (pt_accum_denoise(a.ctx, g.data(), nullptr, out.data(), out8.data()) < 0) throw std::runtime_error(std::string("pt_accum_denoise: ") + pt_last_error(a.ctx));
+    } else if (pt_denoise(a.ctx, rgb.data(), g.data(), W, H, nullptr, out.data(), out8.data()) < 0) throw std::runtime_error(std::string("pt_denoise: ") + pt_last_error(a.ctx));
     imgio::write_png_rgba8(base + "_denoised.png", W, H, out8.data());
     std::printf("Image written to %s\n", (base + "_denoised.png").c_str());
 }
@@ -183,7 +188,7 @@ void render_frame(App& a, const std::string& values)
             pt_stats sk;
             if (pt_get_stats(a.ctx, &sk) == PT_OK) adds_ms += sk.kernel_ms;
         }
-        check(a, pt_accum_end(a.ctx), "pt_accum_end");
+        // (the accumulation stays open for --denoise-variance: ended below, after the guides)
     } else if (a.group) check(a, pt_group_render(a.group, &a.cam, W, H, a.settings.max_samples, a.settings.max_path_depth, rgb.data(), rgba.data()), "pt_group_render");
     else check(a, pt_render(a.ctx, &a.cam, W, H, a.settings.max_samples, a.settings.max_path_depth, rgb.data(), rgba.data()), "pt_render");
     pt_stats st;
@@ -199,6 +204,7 @@ void render_frame(App& a, const std::string& values)
     std::printf("Image written to %s\n", path.c_str());
     std::fprintf(stderr, "  %.1f ms kernel, %.1f Msamples/s\n", st.kernel_ms, (double)W * H * a.settings.max_samples / (st.kernel_ms * 1e3));
     if (a.aov > 0) write_guides(a, path.substr(0, path.size() - 4), rgb);
+    if (a.adds > 0) check(a, pt_accum_end(a.ctx), "pt_accum_end");
 }
 
 // --batch: the collected sweep steps (material table and value string each) as one pt_render_batch; one PNG per step as render_frame writes it
@@ -307,6 +313,7 @@ int main(int argc, char** argv)
             else if (k == "--follow-roughness") { a.follow_roughness = (float)std::atof(next().c_str()); have_follow_roughness = true; }
             else if (k == "--watertight") watertight = true;
             else if (k == "--denoise") a.denoise = true;
+            else if (k == "--denoise-variance") a.denoise_variance = true;
             else if (k == "--adds") { a.adds = std::atoi(next().c_str()); have_adds = true; }
             else if (k == "--convert-png" || k == "--convert-hdr") { // codec self-test hooks: decode with our reader, re-encode with our writer
                 std::string in = next(), out = next();
@@ -330,6 +337,10 @@ int main(int argc, char** argv)
         }
         if (a.denoise && have_batch) throw std::runtime_error("--denoise cannot be combined with --batch (it needs the guides of --aov, which has no batch form)");
         if (a.denoise && !have_aov) throw std::runtime_error("--denoise needs --aov N (the filter is driven by the guide buffers)");
+        if (a.denoise_variance && a.denoise) throw std::runtime_error("--denoise-variance cannot be combined with --denoise (both write <name>_denoised.png)");
+        if (a.denoise_variance && (!have_adds || a.adds < 2))
+            throw std::runtime_error("--denoise-variance needs --adds K with K >= 2 (the variance estimate comes from the two halves of an accumulation's samples)");
+        if (a.denoise_variance && !have_aov) throw std::runtime_error("--denoise-variance needs --aov N (the filter is driven by the guide buffers)");
         if (have_follow && !have_aov) throw std::runtime_error("--follow needs --aov N (it is a mode of the guide pass)");
         if (have_follow && (a.follow < 0 || a.follow > 8)) throw std::runtime_error("--follow needs a number of surfaces 0..8");
         if (have_follow_roughness && !have_follow) throw std::runtime_error("--follow-roughness needs --follow K");

@@ -113,7 +113,9 @@ EXPORTS = ["pt_create", "pt_destroy", "pt_last_error", "pt_abi_version", "pt_upl
            "pt_aov_default_params", "pt_render_aov_follow", "pt_render_aov_follow_device", "pt_group_render_aov_follow", "pt_debug_aov_follow_host",
            "pt_render_aov_batch", "pt_render_aov_batch_device", "pt_denoise_batch", "pt_denoise_batch_device",
            "pt_accum_default_params", "pt_accum_begin", "pt_accum_add", "pt_accum_add_device", "pt_accum_read", "pt_accum_info_get", "pt_accum_end",
-           "pt_debug_accum_resolve_host", "pt_debug_accum_select_host", "pt_debug_accum_state"]
+           "pt_debug_accum_resolve_host", "pt_debug_accum_select_host", "pt_debug_accum_state",
+           "pt_denoise_var_default_params", "pt_denoise_var", "pt_denoise_var_device", "pt_debug_denoise_var_host",
+           "pt_accum_variance", "pt_debug_accum_variance_host", "pt_accum_denoise", "pt_accum_denoise_device"]
 PT_DENOISE_DEMODULATE = 1
 PT_TREE_DEVICE = 16  # pt_debug_export_tree: ORed into `which`, the array as HBM holds it
 PT_COMM_ID_BYTES = 128
@@ -235,6 +237,17 @@ def lib():
     L.pt_debug_accum_select_host.argtypes = [C.c_void_p, fp, u32p, u8p, C.c_int64, C.POINTER(AccumParams), u8p]
     L.pt_debug_accum_select_host.restype = C.c_int64
     L.pt_debug_accum_state.argtypes = [C.c_void_p, fp, fp, u32p, u32p, u32p]
+    L.pt_denoise_var_default_params.restype = None
+    L.pt_denoise_var_default_params.argtypes = [C.POINTER(DenoiseParams)]
+    L.pt_denoise_var.argtypes = [C.c_void_p, fp, fp, fp, C.c_int32, C.c_int32, C.POINTER(DenoiseParams), fp, u32p]
+    L.pt_denoise_var_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(DenoiseParams), C.c_void_p, C.c_void_p, C.c_void_p]
+    L.pt_debug_denoise_var_host.argtypes = [C.c_void_p, fp, fp, fp, C.c_int32, C.c_int32, C.POINTER(DenoiseParams), fp, u32p, fp]
+    L.pt_debug_denoise_var_host.restype = C.c_int64
+    L.pt_accum_variance.argtypes = [C.c_void_p, fp]
+    L.pt_debug_accum_variance_host.argtypes = [C.c_void_p, C.c_int64, fp, fp, u32p, u32p, u8p, fp, fp]
+    L.pt_debug_accum_variance_host.restype = C.c_int64
+    L.pt_accum_denoise.argtypes = [C.c_void_p, fp, C.POINTER(DenoiseParams), fp, u32p]
+    L.pt_accum_denoise_device.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(DenoiseParams), C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = L
     return L
 
@@ -316,6 +329,17 @@ def denoise_default_params(**changes):
     """pt_denoise_default_params (5 iterations, no flag, sigmas 4, 0.25, 0.1, 0.2), with the given fields changed."""
     p = DenoiseParams()
     lib().pt_denoise_default_params(C.byref(p))
+    for k, v in changes.items():
+        if k not in dict(DenoiseParams._fields_):
+            raise KeyError(k)
+        setattr(p, k, v)
+    return p
+
+
+def denoise_var_default_params(**changes):
+    """pt_denoise_var_default_params (as denoise_default_params, sigma_color 3 - standard deviations), with the given fields changed."""
+    p = DenoiseParams()
+    lib().pt_denoise_var_default_params(C.byref(p))
     for k, v in changes.items():
         if k not in dict(DenoiseParams._fields_):
             raise KeyError(k)
@@ -745,6 +769,80 @@ class Context:
                                               act.ctypes.data_as(bp))
         self._check(int(rc), "pt_debug_accum_select_host")
         return act, int(rc)
+
+    # ---- variance-guided denoise (pt_denoise_var*, pt_accum_variance, pt_accum_denoise*) ----
+    def _denoise_var(self, fn, what, rgb, var, aov, params, want_rgba8, in_place, want_var=None):
+        aov = np.ascontiguousarray(aov, np.float32)
+        var = np.ascontiguousarray(var, np.float32)
+        H, W = aov.shape[0], aov.shape[1]
+        src = rgb if in_place else np.ascontiguousarray(rgb, np.float32)
+        assert src.dtype == np.float32 and src.flags["C_CONTIGUOUS"] and src.shape == (H, W, 3) and var.shape == (H, W, 3) and aov.shape == (H, W, 8)
+        out = src if in_place else np.empty((H, W, 3), np.float32)
+        rgba = np.empty((H, W), np.uint32) if want_rgba8 else None
+        fp = C.POINTER(C.c_float)
+        args = [self._h, src.ctypes.data_as(fp), var.ctypes.data_as(fp), aov.ctypes.data_as(fp), W, H, C.byref(params) if params is not None else None, out.ctypes.data_as(fp),
+                rgba.ctypes.data_as(C.POINTER(C.c_uint32)) if rgba is not None else None]
+        vout = None
+        if want_var is not None:
+            vout = np.empty((H, W), np.float32) if want_var else None
+            args.append(vout.ctypes.data_as(fp) if vout is not None else None)
+        rc = fn(*args)
+        if rc < 0:
+            self._check(int(rc), what)
+        return (out, rgba) if want_var is None else (out, rgba, vout)
+
+    def denoise_var(self, rgb, var, aov, params=None, want_rgba8=False, in_place=False):
+        """pt_denoise_var: rgb and its per-channel variance map var (H, W, 3 each), aov (H, W, 8) -> the filtered frame (and its RGBA8 image).
+        params: a DenoiseParams whose sigma_color counts standard deviations (None: denoise_var_default_params)."""
+        return self._denoise_var(lib().pt_denoise_var, "pt_denoise_var", rgb, var, aov, params, want_rgba8, in_place)
+
+    def denoise_var_host(self, rgb, var, aov, params=None, want_rgba8=False, in_place=False, want_var=False):
+        """pt_debug_denoise_var_host, the CPU twin of denoise_var (works on a host-only context) -> (out, rgba8 or None, v_L (H, W) or None)."""
+        return self._denoise_var(lib().pt_debug_denoise_var_host, "pt_debug_denoise_var_host", rgb, var, aov, params, want_rgba8, in_place, want_var=bool(want_var))
+
+    def denoise_var_device(self, d_rgb, d_var, d_aov, W, H, d_out_rgb, params=None, d_out_rgba8=None, stream=None):
+        """pt_denoise_var_device: asynchronous, device pointers (integers; d_out_rgb may equal d_rgb); conventions of denoise_device."""
+        self._check(lib().pt_denoise_var_device(self._h, C.c_void_p(d_rgb), C.c_void_p(d_var), C.c_void_p(d_aov), W, H, C.byref(params) if params is not None else None,
+                                                C.c_void_p(d_out_rgb), C.c_void_p(d_out_rgba8) if d_out_rgba8 else None, C.c_void_p(stream) if stream else None),
+                    "pt_denoise_var_device")
+
+    def accum_variance(self):
+        """pt_accum_variance -> (H, W, 3) float32: the per-channel variance of the accumulation's pixel values, framebuffer order."""
+        H, W = self._accum_shape
+        out = np.empty((H, W, 3), np.float32)
+        self._check(lib().pt_accum_variance(self._h, out.ctypes.data_as(C.POINTER(C.c_float))), "pt_accum_variance")
+        return out
+
+    def accum_variance_host(self, sum_, half, n, n_half, owned):
+        """pt_debug_accum_variance_host on flat arrays (sum, half: (N, 3) float32; n, n_half: (N,) uint32; owned: (N,) uint8) -> (rgb, var), (N, 3) each."""
+        fp, up, bp = C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.POINTER(C.c_uint8)
+        s, h = np.ascontiguousarray(sum_, np.float32).reshape(-1, 3), np.ascontiguousarray(half, np.float32).reshape(-1, 3)
+        m, mh, w = np.ascontiguousarray(n, np.uint32).ravel(), np.ascontiguousarray(n_half, np.uint32).ravel(), np.ascontiguousarray(owned, np.uint8).ravel()
+        N = s.shape[0]
+        assert h.shape[0] == N and m.size == N and mh.size == N and w.size == N
+        rgb, var = np.empty((N, 3), np.float32), np.empty((N, 3), np.float32)
+        rc = lib().pt_debug_accum_variance_host(self._h, N, s.ctypes.data_as(fp), h.ctypes.data_as(fp), m.ctypes.data_as(up), mh.ctypes.data_as(up), w.ctypes.data_as(bp),
+                                                rgb.ctypes.data_as(fp), var.ctypes.data_as(fp))
+        self._check(int(rc), "pt_debug_accum_variance_host")
+        return rgb, var
+
+    def accum_denoise(self, aov, params=None, want_rgba8=False):
+        """pt_accum_denoise: the variance-guided filter on the accumulation as it stands, aov (H, W, 8) -> (rgb (H, W, 3), rgba8 or None).  It
+        changes nothing of the accumulation."""
+        H, W = self._accum_shape
+        aov = np.ascontiguousarray(aov, np.float32)
+        assert aov.shape == (H, W, 8)
+        out = np.empty((H, W, 3), np.float32)
+        rgba = np.empty((H, W), np.uint32) if want_rgba8 else None
+        fp = C.POINTER(C.c_float)
+        self._check(lib().pt_accum_denoise(self._h, aov.ctypes.data_as(fp), C.byref(params) if params is not None else None, out.ctypes.data_as(fp),
+                                           rgba.ctypes.data_as(C.POINTER(C.c_uint32)) if rgba is not None else None), "pt_accum_denoise")
+        return out, rgba
+
+    def accum_denoise_device(self, d_aov, d_out_rgb, params=None, d_out_rgba8=None, stream=None):
+        """pt_accum_denoise_device: asynchronous, device pointers (integers); stream and ordering as accum_add_device."""
+        self._check(lib().pt_accum_denoise_device(self._h, C.c_void_p(d_aov), C.byref(params) if params is not None else None, C.c_void_p(d_out_rgb),
+                                                  C.c_void_p(d_out_rgba8) if d_out_rgba8 else None, C.c_void_p(stream) if stream else None), "pt_accum_denoise_device")
 
     def comm_init_rank(self, unique_id, rank, world):
         buf = (C.c_uint8 * PT_COMM_ID_BYTES).from_buffer_copy(unique_id)
