@@ -170,7 +170,7 @@ int pt_render(pt_ctx* ctx, const pt_camera* cam, int32_t width, int32_t height, 
  * every call that touches what a frame in flight uses is ordered after the context's LAST ASYNCHRONOUS CALL, whichever stream that
  * call was given.  So any call of this header may follow a pt_*_device call at once, with no pt_synchronize between them.
  *   - The asynchronous calls (pt_render_device, pt_render_batch_device, pt_render_aov_device, pt_render_aov_follow_device, pt_render_aov_batch_device, pt_denoise_device,
- *     pt_denoise_batch_device, pt_denoise_var_device, pt_accum_add_device, pt_accum_denoise_device, pt_reduce_framebuffer) wait ON THE
+ *     pt_denoise_batch_device, pt_denoise_var_device, pt_accum_add_device, pt_accum_denoise_device, pt_accum_reproject_device, pt_reduce_framebuffer) wait ON THE
  *     DEVICE: the stream they are given waits for an event recorded at the end of the previous asynchronous call - only if that call
  *     used another stream; on the same stream the stream's own order suffices and nothing is added.  The host returns at once, with
  *     two exceptions that existed before: a frame of another size, shard or batch length rewrites the pixel queue and a frame that
@@ -178,7 +178,7 @@ int pt_render(pt_ctx* ctx, const pt_camera* cam, int32_t width, int32_t height, 
  *     before) - both first wait on the host for the frame in flight; pt_render_batch_device and pt_render_aov_batch_device
  *     return when their per-frame tables have reached HBM, i.e. after whatever precedes them on `stream`; and a pt_accum_add_device that
  *     selects its pixels returns when the count of its active set has reached the host (see there).
- *   - The blocking renders (pt_render, pt_render_batch, pt_render_aov, pt_render_aov_follow, pt_render_aov_batch, pt_accum_add), pt_denoise, pt_denoise_batch, pt_denoise_var and pt_accum_denoise run on the context's stream behind the same device-side wait
+ *   - The blocking renders (pt_render, pt_render_batch, pt_render_aov, pt_render_aov_follow, pt_render_aov_batch, pt_accum_add), pt_denoise, pt_denoise_batch, pt_denoise_var, pt_accum_denoise and pt_accum_reproject run on the context's stream behind the same device-side wait
  *     and return with the context idle.  After a blocking call, or on the context's own stream, they add no wait at all.
  *   - The calls that change or read what a frame uses WAIT ON THE HOST for the last asynchronous call's stream (if it is not the
  *     context's) and then for the context's: pt_set_materials, pt_set_environment, pt_update_vertices, pt_upload_scene,
@@ -193,7 +193,7 @@ int pt_render(pt_ctx* ctx, const pt_camera* cam, int32_t width, int32_t height, 
 int pt_render_device(pt_ctx* ctx, const pt_camera* cam, int32_t width, int32_t height, int32_t max_samples, int32_t max_path_depth,
                      void* d_out_rgb, void* d_out_rgba8, void* stream);
 /* Waits on the host for the context's last asynchronous call - pt_render_device, pt_render_batch_device, pt_render_aov_device,
- * pt_render_aov_follow_device, pt_render_aov_batch_device, pt_denoise_device, pt_denoise_batch_device, pt_denoise_var_device, pt_accum_add_device, pt_accum_denoise_device or pt_reduce_framebuffer, on the stream it was given - and for the context's own stream.  Every earlier asynchronous call of the context
+ * pt_render_aov_follow_device, pt_render_aov_batch_device, pt_denoise_device, pt_denoise_batch_device, pt_denoise_var_device, pt_accum_add_device, pt_accum_denoise_device, pt_accum_reproject_device or pt_reduce_framebuffer, on the stream it was given - and for the context's own stream.  Every earlier asynchronous call of the context
  * is complete then as well, whatever stream it used: each was ordered before the next (see pt_render_device).  Returns PT_E_HIP if a
  * wave's watchdog fired during the last frame (the image is then incomplete); pt_get_stats reports the same.  PT_OK at once on an idle
  * or host-only context.  A caller's stream may be destroyed once this has returned. */
@@ -403,7 +403,7 @@ int64_t pt_debug_denoise_host(pt_ctx* ctx, const float* rgb, const float* aov, i
 /* ---- progressive accumulation: a frame that grows by "adds", with a per-pixel noise estimate and adaptive adds (no reference
  * counterpart: the reference restarts every frame at sample 0) ----
  * A context holds at most ONE accumulation.  It owns its device buffers (62 bytes per pixel of the frame beside the 16 of the image); no other
- * call of this header writes them (pt_accum_variance and pt_accum_denoise, further down, read them).  pt_accum_begin fixes camera, size, depth and the pixel shard as they are at that moment;
+ * call of this header writes them (pt_accum_variance and pt_accum_denoise, further down, read them; pt_accum_reproject, further down still, moves them to a new camera).  pt_accum_begin fixes camera, size, depth and the pixel shard as they are at that moment;
  * every pt_accum_add gives the pixels of its ACTIVE SET n_samples more samples of their own RNG streams and returns the image so far.
  * STATE per pixel: rng and sum[3] - the render kernel's own rng_state / accum at the launch id x + W*y - and seen[3], half[3], n, n_half,
  * passes, noise.  pt_accum_begin sets noise = +inf and everything else 0.
@@ -540,6 +540,79 @@ int64_t pt_debug_accum_variance_host(pt_ctx* ctx, int64_t n_pixels, const float*
                                      const uint8_t* owned, float* out_rgb, float* out_var);
 int pt_accum_denoise(pt_ctx* ctx, const float* aov, const pt_denoise_params* p /* NULL = defaults */, float* out_rgb, uint32_t* out_rgba8 /* optional */);
 int pt_accum_denoise_device(pt_ctx* ctx, const void* d_aov, const pt_denoise_params* p, void* d_out_rgb, void* d_out_rgba8 /* optional */, void* stream);
+
+/* ---- reprojection: move an accumulation to a new camera (no reference counterpart) ----
+ * When the camera moves, a new pt_accum_begin throws every sample away.  pt_accum_reproject keeps them: the accumulation's own state
+ * follows the surfaces to the new camera, every pixel keeps its RNG stream, and pixels that come into view (or fail a consistency test)
+ * restart with n = 0 and noise = +inf, which is what an add's select already takes for "needs samples".  pt_accum_read,
+ * pt_accum_variance, pt_accum_denoise and the next pt_accum_add work on the result unchanged; the render kernel is not involved.
+ * aov_prev holds the guides (W*H*8 floats, as pt_render_aov produces them) under the accumulation's CURRENT camera, aov_cur the guides
+ * under new_cam; W and H are the accumulation's; the device pointers are 16-byte aligned; the two may be the same buffer.
+ * DEFINITION (the kernel of csrc/pt_accum_reproject.hip and the CPU twin pt_debug_accum_reproject_host - one source,
+ * csrc/pt_accum_math.h accum_reproject_source / accum_reproject_history - and the numpy restatement tests/accum_reproject_ref.py
+ * implement exactly this).  Arithmetic is the contract of csrc/pt_device.h: its dot, cross, normalize, sqrt_, abs_, isinf_, unfused
+ * + - *, correctly rounded /.
+ *   Host constants, computed once per call, in this order, from the OLD camera (o', llc', h', v'):
+ *     a = llc' - o',  N = cross(h', v'),  inn = 1.0f / dot(N, N),  na = dot(N, a).
+ *   Per owned pixel (px, py) of the new frame, with g its record of aov_cur at framebuffer index px + W*(H-1-py):
+ *   1. Camera ray through the pixel centre.  su = ((float)px + 0.5f) / (float)W, sv likewise with H;
+ *      dc = normalize(((llc + horizontal*su) + vertical*sv) - origin), which are gen_camera_ray's operations on the new camera.
+ *   2. Surface or sky.  The pixel is a surface if g.alpha >= 0.5f && g.depth > 0.0f && !isinf_(g.depth), else sky (a point at infinity).
+ *      Surface: P = origin + dc * g.depth, r = P - o', ze = sqrt_(dot(r, r)).   Sky: r = dc.
+ *   3. Projection into the old camera.  dn = dot(N, r), lam = na / dn.  No history unless lam > 0.0f && !isinf_(lam).
+ *      w = r * lam - a;  su' = dot(cross(w, v'), N) * inn,  sv' = dot(cross(h', w), N) * inn;  fx = su' * (float)W, fy = sv' * (float)H.
+ *      No history unless fx >= 0 && fx < W && fy >= 0 && fy < H (NaN fails).  qx = (int)fx, qy = (int)fy.
+ *      The SOURCE is the one old pixel that contains the point: one tap, no interpolation, so n, n_half and passes stay integers.
+ *   4. No history if the source is not owned by the context.
+ *   5. Consistency, with s the record of aov_prev at qx + W*(H-1-qy), classified as in step 2.  Every comparison must be TRUE, so NaN
+ *      guides fail:  same class;  surface: abs_(s.depth - ze) <= depth_tol * ze and dot(g.normal, s.normal) >= normal_min;
+ *      both classes: da = s.albedo - g.albedo, dot(da, da) <= albedo_tol * albedo_tol.
+ *   6. History.  Copy sum, half, n, n_half, passes of launch id qx + W*qy.  Then, if max_history != 0 && n > max_history:
+ *        f = (float)max_history / (float)n,  sum_k = sum_k * f;
+ *        nh = (uint32_t)((uint64_t)n_half * max_history / n);
+ *        half_k = nh ? half_k * ((float)nh / (float)n_half) : +0;
+ *        n_half = nh,  n = max_history.
+ *      No history: all of these are +0 / 0.
+ *   7. Resolve.  seen = sum.  Then accum_resolve_pixel(state, active = false, ...) of pt_accum_math.h gives out_rgb, out_rgba8 and
+ *      noise: resolve's own expressions, one copy.
+ *   Pixels that are not owned stay +0 everywhere.  rng is not read and not written: every pixel goes on with its own stream.
+ * After the call the accumulation's camera is new_cam: pt_accum_read, pt_accum_variance, pt_accum_denoise and the next pt_accum_add see
+ * the moved state.  A pixel without history has n = 0 and noise = +inf, so it is active in any selecting add.  adds, samples_total,
+ * owned_pixels and the bound on a pixel's n (the sum of the adds' n_samples) are unchanged.
+ * CONSEQUENCES AND LIMITS.
+ *   - After a reproject, "a pixel with n samples is bit for bit pt_render at n" no longer holds for this accumulation.  It holds again
+ *     after pt_accum_begin.
+ *   - Static scenes only: samples taken before pt_update_vertices, pt_set_materials or pt_set_environment are carried along.  The albedo
+ *     test catches part of a material change, nothing more.
+ *   - One tap misplaces history by up to half a pixel per call.  max_history bounds how long that is kept.
+ *   - View-dependent shading (mirrors, glass) is reprojected by its surface, not by what shows in it.
+ *   - Before the first add (adds == 0) the call only changes the camera.
+ *   - A second set of state buffers (36 bytes per pixel) is allocated at the first reproject and swapped with the first set by the call.
+ * The three default tolerances are starting values chosen from the filter's sigmas, not measured optima.
+ * ORDERING: pt_accum_reproject_device joins the asynchronous calls of the streams contract at pt_render_device and the list at
+ * pt_synchronize.  The blocking form belongs with pt_accum_denoise: context's stream, idle on return; it uploads both guides.  The
+ * host-side pointer swap and camera change happen at enqueue, which is safe because every later call is ordered after it.
+ * REFUSED with PT_E_INVALID by name, before anything is touched: no accumulation; a communicator (as pt_accum_add); a shard changed or
+ * a scene uploaded since begin (as pt_accum_add); NULL camera or guides; reserved != 0; max_history of 1 or negative; a tolerance that is
+ * negative or NaN; normal_min that is NaN or > 1.  A host-only context - which can hold no accumulation - judges the arguments alone and
+ * answers PT_E_NO_DEVICE to valid ones.  The twin works there: old_cam is the camera the state was gathered under, owned the shard's
+ * flags (W*H bytes, framebuffer order; NULL = all); sum, half, n, n_half, passes are updated in place, in framebuffer order as
+ * pt_debug_accum_state gives them; it refuses what the call refuses of its arguments, NULL arrays and sizes pt_render refuses; returns W*H.
+ * pt_get_stats afterwards: kernel_ms of the one kernel, launches = 1, block, grid, vgprs, lds_bytes the reproject kernel's. */
+typedef struct pt_reproject_params {
+    int32_t max_history;  /* 0 = no cap; else >= 2: a pixel that arrives with n > max_history is scaled down to it */
+    int32_t reserved;     /* must be 0 */
+    float depth_tol;      /* >= 0: |z_source - z_expected| <= depth_tol * z_expected;  +inf = test off */
+    float normal_min;     /* -1..1 or -inf: dot(n_cur, n_source) >= normal_min;          -inf = test off */
+    float albedo_tol;     /* >= 0: |a_source - a_cur|^2 <= albedo_tol^2;                 +inf = test off */
+} pt_reproject_params;
+void pt_accum_reproject_default_params(pt_reproject_params* p);   /* 0, 0, 0.05f, 0.9f, 0.1f */
+int pt_accum_reproject(pt_ctx* ctx, const pt_camera* new_cam, const float* aov_prev, const float* aov_cur, const pt_reproject_params* p /* NULL = defaults */);
+int pt_accum_reproject_device(pt_ctx* ctx, const pt_camera* new_cam, const void* d_aov_prev, const void* d_aov_cur, const pt_reproject_params* p, void* stream);
+int64_t pt_debug_accum_reproject_host(pt_ctx* ctx, const pt_camera* old_cam, const pt_camera* new_cam, int32_t width, int32_t height,
+                                      const float* aov_prev, const float* aov_cur, const uint8_t* owned /* W*H, framebuffer order; NULL = all */, const pt_reproject_params* p,
+                                      float* sum, float* half, uint32_t* n, uint32_t* n_half, uint32_t* passes, /* in/out, framebuffer order, as pt_debug_accum_state gives them */
+                                      float* out_rgb, uint32_t* out_rgba8, float* out_noise);                   /* framebuffer order; returns W*H */
 
 /* ---- N GPUs: pixel tiles sharded over ranks + ONE RCCL sum-reduce of the float3 framebuffer onto rank 0 (pt_comm.cpp) ----
  * No reference counterpart (the reference is single-GPU: create_context(nullptr, 1), application.cpp:62); for N > 1 these

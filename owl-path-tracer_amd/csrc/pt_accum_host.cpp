@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <algorithm>
 #include <cstring>
 #include <limits>
 #include <vector>
@@ -145,15 +146,23 @@ int add_device(pt_ctx* c, const pt_accum_params& prm, void* d_out_rgb, void* d_o
     return PT_OK;
 }
 
+// The accumulation still stands on the shard and the scene pt_accum_begin found.
+int check_accum_unchanged(pt_ctx* c, const char* who)
+{
+    const Accum& a = *c->acc;
+    if (a.rank != c->rank || a.world != c->world || a.tile != c->tile)
+        return fail(c, PT_E_INVALID, "%s: the pixel shard changed after pt_accum_begin (%d of %d tile %d, now %d of %d tile %d); begin again", who, a.rank, a.world, a.tile, c->rank, c->world, c->tile);
+    if (a.scene_epoch != c->scene_epoch) return fail(c, PT_E_INVALID, "%s: a new scene was uploaded after pt_accum_begin; begin again", who);
+    return PT_OK;
+}
+
 // Everything an add refuses before it touches anything, in the order of the header; *eff = the parameters in effect.
 int check_add(pt_ctx* c, const char* who, const pt_accum_params* p, pt_accum_params* eff)
 {
     int rc;
     if ((rc = check_accum_params(c, who, p, eff)) || (rc = check_accum_context(c, who)) || (rc = need_accum(c, who)) || (rc = refuse_comm(c, who))) return rc;
+    if ((rc = check_accum_unchanged(c, who))) return rc;
     const Accum& a = *c->acc;
-    if (a.rank != c->rank || a.world != c->world || a.tile != c->tile)
-        return fail(c, PT_E_INVALID, "%s: the pixel shard changed after pt_accum_begin (%d of %d tile %d, now %d of %d tile %d); begin again", who, a.rank, a.world, a.tile, c->rank, c->world, c->tile);
-    if (a.scene_epoch != c->scene_epoch) return fail(c, PT_E_INVALID, "%s: a new scene was uploaded after pt_accum_begin; begin again", who);
     if ((int64_t)a.n_upper + eff->n_samples > kMaxPixelSamples)
         return fail(c, PT_E_INVALID, "%s: a pixel would pass %lld samples (%llu so far + %d)", who, (long long)kMaxPixelSamples, (unsigned long long)a.n_upper, eff->n_samples);
     return PT_OK;
@@ -177,6 +186,125 @@ int read_flipped(pt_ctx* c, void* dst, const DevBuf& b, int W, int H, size_t ele
         for (size_t i = 0; i < npx; ++i)
             if (!owned_or_null[i]) std::memset(tmp.data() + i * elem, 0, elem);
     flip_rows(dst, tmp.data(), W, H, elem);
+    return PT_OK;
+}
+
+// ---- reprojection (pt_accum_reproject*; include/mi355pt.h, "reprojection") -------------------------------------------------------
+// What the two calls and the twin refuse alike in the parameters; *eff = the parameters in effect.
+int check_reproject_params(pt_ctx* c, const char* who, const pt_reproject_params* p, pt_reproject_params* eff)
+{
+    if (p) *eff = *p;
+    else pt_accum_reproject_default_params(eff);
+    if (eff->reserved != 0) return fail(c, PT_E_INVALID, "%s: reserved must be 0 (is %d)", who, eff->reserved);
+    if (eff->max_history < 0 || eff->max_history == 1) return fail(c, PT_E_INVALID, "%s: max_history %d must be 0 (no cap) or >= 2", who, eff->max_history);
+    if (!(eff->depth_tol >= 0.0f)) return fail(c, PT_E_INVALID, "%s: depth_tol %g must be >= 0 (+inf = test off)", who, (double)eff->depth_tol);
+    if (!(eff->albedo_tol >= 0.0f)) return fail(c, PT_E_INVALID, "%s: albedo_tol %g must be >= 0 (+inf = test off)", who, (double)eff->albedo_tol);
+    if (!(eff->normal_min <= 1.0f)) return fail(c, PT_E_INVALID, "%s: normal_min %g must be <= 1 (-inf = test off)", who, (double)eff->normal_min);
+    return PT_OK;
+}
+
+// What pt_accum_reproject and pt_accum_reproject_device refuse before anything is touched, in the order of the header.  A host-only
+// context can hold no accumulation: there the arguments alone are judged, and valid ones meet PT_E_NO_DEVICE.
+int check_reproject(pt_ctx* c, const char* who, const pt_camera* new_cam, const void* aov_prev, const void* aov_cur, const pt_reproject_params* p, pt_reproject_params* eff)
+{
+    int rc;
+    if (!c->host_only && ((rc = need_accum(c, who)) || (rc = refuse_comm(c, who)) || (rc = check_accum_unchanged(c, who)))) return rc;
+    if (!new_cam || !aov_prev || !aov_cur) return fail(c, PT_E_INVALID, "%s: NULL %s", who, !new_cam ? "new_cam" : (!aov_prev ? "aov_prev" : "aov_cur"));
+    if ((rc = check_reproject_params(c, who, p, eff))) return rc;
+    return need_device(c);
+}
+
+// The header's host constants, in its order, from the OLD camera; everything else of *R copied.
+void reproject_constants(const pt_camera& old_cam, const pt_camera& new_cam, int W, int H, const pt_reproject_params& prm, PtAccumReproject* R)
+{
+    const v3 oo = V(old_cam.origin[0], old_cam.origin[1], old_cam.origin[2]), llc = V(old_cam.llc[0], old_cam.llc[1], old_cam.llc[2]);
+    const v3 ho = V(old_cam.horizontal[0], old_cam.horizontal[1], old_cam.horizontal[2]), vo = V(old_cam.vertical[0], old_cam.vertical[1], old_cam.vertical[2]);
+    const v3 a = llc - oo;
+    const v3 N = cross(ho, vo);
+    const float inn = 1.0f / dot(N, N);
+    const float na = dot(N, a);
+    for (int k = 0; k < 3; ++k) {
+        R->o[k] = new_cam.origin[k];
+        R->llc[k] = new_cam.llc[k];
+        R->hor[k] = new_cam.horizontal[k];
+        R->ver[k] = new_cam.vertical[k];
+        R->oo[k] = old_cam.origin[k];
+        R->ho[k] = old_cam.horizontal[k];
+        R->vo[k] = old_cam.vertical[k];
+    }
+    R->a[0] = a.x; R->a[1] = a.y; R->a[2] = a.z;
+    R->N[0] = N.x; R->N[1] = N.y; R->N[2] = N.z;
+    R->inn = inn;
+    R->na = na;
+    R->depth_tol = prm.depth_tol;
+    R->normal_min = prm.normal_min;
+    R->albedo_tol = prm.albedo_tol;
+    R->width = W;
+    R->height = H;
+    R->max_history = prm.max_history;
+}
+
+void swap_bufs(DevBuf& x, DevBuf& y)
+{
+    std::swap(x.p, y.p);
+    std::swap(x.cap, y.cap);
+}
+
+// The reproject on `stream`, which the caller has ordered after the context's last asynchronous call: the second set of state buffers
+// on its first use, the one kernel from the first set into the second, then - on the host, at enqueue: every later call is ordered after
+// this one - the two sets swapped and the camera changed.
+int reproject_device(pt_ctx* c, const pt_camera& new_cam, const pt_reproject_params& prm, const void* d_aov_prev, const void* d_aov_cur, hipStream_t stream)
+{
+    Accum& a = *c->acc;
+    if (a.adds == 0) { // nothing to move yet: the first add starts every pixel from its seed under the new camera
+        a.cam = new_cam;
+        return PT_OK;
+    }
+    PtGeometry g{};
+    int grid = 0;
+    const hipError_t ge = pt_accum_reproject_geometry(a.w, a.h, &g, &grid);
+    if (ge == hipErrorInvalidConfiguration) return fail(c, PT_E_LIMIT, "this build of the reproject kernel spills registers to scratch; such builds are refused (pt_accum_reproject.hip)");
+    HIP_TRY(c, ge);
+    const size_t npx = (size_t)a.w * a.h;
+    int rc;
+    if (!a.have_set2) {
+        struct Z { DevBuf* b; size_t bytes; };
+        for (const Z& z : {Z{&a.sum2, npx * 12}, Z{&a.half2, npx * 12}, Z{&a.n2, npx * 4}, Z{&a.n_half2, npx * 4}, Z{&a.passes2, npx * 4}}) {
+            if ((rc = ensure(c, *z.b, z.bytes))) return rc;
+            HIP_TRY(c, hipMemsetAsync(z.b->p, 0, z.bytes, stream)); // pixels outside the shard stay +0 in both sets: the kernel writes none of them
+        }
+        a.have_set2 = true;
+    }
+    PtAccumReprojectArgs A{};
+    reproject_constants(a.cam, new_cam, a.w, a.h, prm, &A.R);
+    A.aov_prev = (const float*)d_aov_prev;
+    A.aov_cur = (const float*)d_aov_cur;
+    A.owned = (const uint8_t*)a.owned.p;
+    A.sum_in = (const float*)a.sum.p;
+    A.half_in = (const float*)a.half.p;
+    A.n_in = (const uint32_t*)a.n.p;
+    A.n_half_in = (const uint32_t*)a.n_half.p;
+    A.passes_in = (const uint32_t*)a.passes.p;
+    A.sum_out = (float*)a.sum2.p;
+    A.half_out = (float*)a.half2.p;
+    A.n_out = (uint32_t*)a.n2.p;
+    A.n_half_out = (uint32_t*)a.n_half2.p;
+    A.passes_out = (uint32_t*)a.passes2.p;
+    A.seen = (float*)a.seen.p;
+    A.noise = (float*)a.noise.p;
+    A.out_rgb = (float*)a.out.p;
+    A.out_rgba8 = (uint32_t*)a.out8.p;
+    A.n_frame = (uint32_t)npx;
+    HIP_TRY(c, hipEventRecord(c->ev0, stream));
+    HIP_TRY(c, pt_launch_accum_reproject(&A, stream));
+    HIP_TRY(c, hipEventRecord(c->ev1, stream));
+    note_pass(c, a.w, a.h, 1, grid, g, 0, false);
+    swap_bufs(a.sum, a.sum2);
+    swap_bufs(a.half, a.half2);
+    swap_bufs(a.n, a.n2);
+    swap_bufs(a.n_half, a.n_half2);
+    swap_bufs(a.passes, a.passes2);
+    a.cam = new_cam;
     return PT_OK;
 }
 
@@ -391,6 +519,118 @@ int64_t pt_debug_accum_select_host(pt_ctx* c, const float* noise, const uint32_t
         count += active[i];
     }
     return count;
+}
+
+void pt_accum_reproject_default_params(pt_reproject_params* p)
+{
+    if (!p) return;
+    p->max_history = 0;
+    p->reserved = 0;
+    p->depth_tol = 0.05f;
+    p->normal_min = 0.9f;
+    p->albedo_tol = 0.1f;
+}
+
+int pt_accum_reproject_device(pt_ctx* c, const pt_camera* new_cam, const void* d_aov_prev, const void* d_aov_cur, const pt_reproject_params* p, void* stream_v)
+{
+    if (!c) return PT_E_INVALID;
+    pt_reproject_params prm;
+    int rc;
+    if ((rc = check_reproject(c, "pt_accum_reproject_device", new_cam, d_aov_prev, d_aov_cur, p, &prm))) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t stream = stream_v ? (hipStream_t)stream_v : c->stream;
+    return async_call(c, stream, [&] { return reproject_device(c, *new_cam, prm, d_aov_prev, d_aov_cur, stream); });
+}
+
+int pt_accum_reproject(pt_ctx* c, const pt_camera* new_cam, const float* aov_prev, const float* aov_cur, const pt_reproject_params* p)
+{
+    if (!c) return PT_E_INVALID;
+    pt_reproject_params prm;
+    int rc;
+    if ((rc = check_reproject(c, "pt_accum_reproject", new_cam, aov_prev, aov_cur, p, &prm))) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (c->acc->adds == 0) { // only the camera changes (reproject_device): no guides to stage, no kernel to wait for
+        if ((rc = wait_idle(c))) return rc;
+        return reproject_device(c, *new_cam, prm, aov_prev, aov_cur, c->stream);
+    }
+    const size_t bytes = (size_t)c->acc->w * c->acc->h * 32;
+    return blocking_call(c, [&]() -> int {
+        int rc;
+        // both guides staged in d_dn_aov (the denoiser's staging of guides), the new camera's first; one copy when they are one buffer
+        if ((rc = ensure(c, c->d_dn_aov, 2 * bytes))) return rc;
+        char* d_cur = (char*)c->d_dn_aov.p;
+        char* d_prev = aov_prev == aov_cur ? d_cur : d_cur + bytes;
+        HIP_TRY(c, hipMemcpyAsync(d_cur, aov_cur, bytes, hipMemcpyHostToDevice, c->stream));
+        if (d_prev != d_cur) HIP_TRY(c, hipMemcpyAsync(d_prev, aov_prev, bytes, hipMemcpyHostToDevice, c->stream));
+        if ((rc = reproject_device(c, *new_cam, prm, d_prev, d_cur, c->stream))) return rc;
+        return drain(c, {});
+    });
+}
+
+int64_t pt_debug_accum_reproject_host(pt_ctx* c, const pt_camera* old_cam, const pt_camera* new_cam, int32_t W, int32_t H, const float* aov_prev, const float* aov_cur,
+                                      const uint8_t* owned, const pt_reproject_params* p, float* sum, float* half, uint32_t* n, uint32_t* n_half, uint32_t* passes,
+                                      float* out_rgb, uint32_t* out_rgba8, float* out_noise)
+{
+    if (!c) return PT_E_INVALID;
+    const char* who = "pt_debug_accum_reproject_host";
+    if (!old_cam || !new_cam || !aov_prev || !aov_cur) return fail(c, PT_E_INVALID, "%s: NULL %s", who, !old_cam ? "old_cam" : (!new_cam ? "new_cam" : (!aov_prev ? "aov_prev" : "aov_cur")));
+    if (!sum || !half || !n || !n_half || !passes || !out_rgb || !out_rgba8 || !out_noise) return fail(c, PT_E_INVALID, "%s: NULL array", who);
+    if (W <= 0 || H <= 0 || W > 65535 || H > 65535 || (int64_t)W * H > (int64_t)0x7fffffff) return fail(c, PT_E_INVALID, "%s: bad frame size %dx%d", who, W, H);
+    pt_reproject_params prm;
+    int rc = check_reproject_params(c, who, p, &prm);
+    if (rc) return rc;
+    PtAccumReproject R;
+    reproject_constants(*old_cam, *new_cam, W, H, prm, &R);
+    // the state by launch id, as the kernel has it: the shared code indexes both alike
+    const size_t npx = (size_t)W * H;
+    std::vector<uint8_t> own(npx, 1);
+    std::vector<float> sum_in(npx * 3), half_in(npx * 3);
+    std::vector<uint32_t> n_in(npx), n_half_in(npx), passes_in(npx);
+    if (owned) flip_rows(own.data(), owned, W, H, 1);
+    flip_rows(sum_in.data(), sum, W, H, 12);
+    flip_rows(half_in.data(), half, W, H, 12);
+    flip_rows(n_in.data(), n, W, H, 4);
+    flip_rows(n_half_in.data(), n_half, W, H, 4);
+    flip_rows(passes_in.data(), passes, W, H, 4);
+    pt_parallel_ranges((size_t)H, [&](size_t lo, size_t hi) {
+        for (size_t y = lo; y < hi; ++y)
+            for (int x = 0; x < W; ++x) {
+                const size_t id = (size_t)x + (size_t)W * y, ofs = (size_t)x + (size_t)W * ((size_t)H - 1 - y);
+                AccumPixel s;
+                for (int k = 0; k < 3; ++k) s.sum[k] = s.seen[k] = s.half[k] = 0.0f;
+                s.n = s.n_half = s.passes = 0u;
+                AccumResolved o;
+                o.rgb[0] = o.rgb[1] = o.rgb[2] = 0.0f;
+                o.rgba8 = 0u;
+                o.noise = 0.0f;
+                if (own[id]) {
+                    uint32_t q = 0;
+                    if (accum_reproject_source(R, x, (int)y, aov_prev, aov_cur, own.data(), &q)) {
+                        for (int k = 0; k < 3; ++k) {
+                            s.sum[k] = sum_in[3 * (size_t)q + k];
+                            s.half[k] = half_in[3 * (size_t)q + k];
+                        }
+                        s.n = n_in[q];
+                        s.n_half = n_half_in[q];
+                        s.passes = passes_in[q];
+                        accum_reproject_history(s, (uint32_t)prm.max_history);
+                    }
+                    for (int k = 0; k < 3; ++k) s.seen[k] = s.sum[k];
+                    accum_resolve_pixel(s, false, 0u, o);
+                }
+                for (int k = 0; k < 3; ++k) {
+                    sum[3 * ofs + k] = s.sum[k];
+                    half[3 * ofs + k] = s.half[k];
+                    out_rgb[3 * ofs + k] = o.rgb[k];
+                }
+                n[ofs] = s.n;
+                n_half[ofs] = s.n_half;
+                passes[ofs] = s.passes;
+                out_rgba8[ofs] = o.rgba8;
+                out_noise[ofs] = o.noise;
+            }
+    });
+    return (int64_t)npx;
 }
 
 } // extern "C"

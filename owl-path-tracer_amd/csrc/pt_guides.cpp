@@ -10,11 +10,9 @@
 
 using namespace pti;
 
-namespace {
+namespace pti {
 
-// End of an auxiliary pass, after its ev1: the one place beside finish_frame (pt_render.cpp) that writes what pt_synchronize and
-// pt_get_stats look at.  kernel_ms is ev0 .. ev1; g: the geometry of the pass's kernel; aov_flag: a guide pass, whose bound flag in
-// d_aov_ws check_watchdog has to look at.
+// (pt_internal.h; pt_accum_host.cpp ends its reproject pass with it as well)
 void note_pass(pt_ctx* c, int W, int H, int launches, int grid, const PtGeometry& g, int stack_entries, bool aov_flag)
 {
     LastFrame& L = c->last;
@@ -33,6 +31,10 @@ void note_pass(pt_ctx* c, int W, int H, int launches, int grid, const PtGeometry
     c->stats.block = g.block;
     c->stats.stack_entries = stack_entries;
 }
+
+} // namespace pti
+
+namespace {
 
 // ---- guide pass (pt_render_aov*) -------------------------------------------------------------------------------------------
 // The instances of the guide kernel (pt_launch.h), by [follow mode][watertight][batch].  The first-hit kernel takes the PtAovArgs a

@@ -1,6 +1,6 @@
 // pt_internal.h -- private to the library: the context behind the opaque pt_ctx of include/mi355pt.h and the helpers its host sources
 // share: pt_api.cpp (context, options, stats), pt_scene.cpp (scene upload and clone), pt_render.cpp (frames and batches), pt_guides.cpp
-// (guide pass and denoiser), pt_accum_host.cpp (progressive accumulation), pt_debug.cpp (probes and readers) and pt_comm.cpp (RCCL reduce, multi-GPU group).
+// (guide pass and denoiser), pt_accum_host.cpp (progressive accumulation and its reprojection), pt_debug.cpp (probes and readers) and pt_comm.cpp (RCCL reduce, multi-GPU group).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -12,6 +12,7 @@
 
 #include "../../include/mi355pt.h"
 #include "pt_bvh.h"
+#include "pt_launch.h"
 #include "pt_types.h"
 
 // A device allocation and its owner: freed with the object that holds it (a context, a group, a local of one call).  A buffer that was
@@ -111,6 +112,10 @@ struct Accum {
     DevBuf queue;                       // the shard's pixel queue (n_owned ids), kept: other calls rewrite the context's d_pixels
     DevBuf count;                       // select's counter, 256 bytes of its own
     DevBuf out, out8;                   // resolve's image
+    // pt_accum_reproject: the second set of sum / half / n / n_half / passes (36 bytes per pixel), allocated and cleared by the first
+    // reproject; the kernel gathers from the first set into this one and the call swaps the two (swap_sets)
+    DevBuf sum2, half2, n2, n_half2, passes2;
+    bool have_set2 = false;
 };
 
 struct pt_ctx {
@@ -189,6 +194,11 @@ PT_LOCAL int accum_frame(pt_ctx* c, const pt_camera* cam, int W, int H, int n_sa
 PT_LOCAL int check_denoise_args(pt_ctx* c, const char* who, int W, int H, const pt_denoise_params* p, pt_denoise_params* eff,
                                 void (*defaults)(pt_denoise_params*) = pt_denoise_default_params); // the refusals of pt_denoise*, pt_denoise_var* and the twins; *eff = the parameters in effect (p null: defaults)
 PT_LOCAL void denoise_constants(const pt_denoise_params& p, float* kn, float* ka, float kc[8]); // the definition's host constants
+// pt_guides.cpp
+// End of an auxiliary pass, after its ev1: the one place beside finish_frame (pt_render.cpp) that writes what pt_synchronize and
+// pt_get_stats look at.  kernel_ms is ev0 .. ev1; g: the geometry of the pass's kernel; aov_flag: a guide pass, whose bound flag in
+// d_aov_ws check_watchdog has to look at.
+PT_LOCAL void note_pass(pt_ctx* c, int W, int H, int launches, int grid, const PtGeometry& g, int stack_entries, bool aov_flag);
 // pt_accum_host.cpp
 PT_LOCAL int need_accum(pt_ctx* c, const char* who);  // PT_E_INVALID by name without an accumulation
 PT_LOCAL int refuse_comm(pt_ctx* c, const char* who); // PT_E_INVALID by name with a communicator

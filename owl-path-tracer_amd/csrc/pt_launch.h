@@ -136,7 +136,45 @@ struct PtAccumSelectArgs {
     int32_t pad;
 };
 
+// Reprojection of the accumulation (pt_accum_reproject; pt_accum_reproject.hip): the kernel gathers the state of every owned pixel's source
+// from one set of buffers into the other and resolves it.  Arrays by launch id except the guides and the two images (framebuffer order).
+// What the per-pixel definition (pt_accum_math.h, accum_reproject_source / accum_reproject_history) takes beside the pixel: the new
+// camera, the old one with the header's host constants, the parameters.
+struct PtAccumReproject {
+    float o[3], llc[3], hor[3], ver[3];    // new camera
+    float oo[3], a[3], ho[3], vo[3], N[3]; // old camera: origin, a = llc' - o', h', v', N = cross(h', v')
+    float inn, na;                         // 1 / dot(N, N), dot(N, a)
+    float depth_tol, normal_min, albedo_tol;
+    int32_t width, height, max_history;
+};
+struct PtAccumReprojectArgs {
+    PtAccumReproject R;
+    const float* aov_prev;   // W*H*8 floats each, 16-byte aligned; may be the same buffer
+    const float* aov_cur;
+    const uint8_t* owned;
+    const float* sum_in;     // the state before the call: read at the source
+    const float* half_in;
+    const uint32_t* n_in;
+    const uint32_t* n_half_in;
+    const uint32_t* passes_in;
+    float* sum_out;          // the state after it: written at the pixel; none of these is one of the inputs
+    float* half_out;
+    uint32_t* n_out;
+    uint32_t* n_half_out;
+    uint32_t* passes_out;
+    float* seen;             // = sum_out; the kernel does not read it
+    float* noise;
+    float* out_rgb;
+    uint32_t* out_rgba8;
+    uint32_t n_frame;        // W*H
+    int32_t pad;
+};
+
 extern "C" {
+// pt_accum_reproject.hip: geometry of the reproject kernel (block, vgprs; *grid = its workgroups for a W x H frame);
+// hipErrorInvalidConfiguration if it needs scratch
+hipError_t pt_accum_reproject_geometry(int W, int H, PtGeometry* g, int* grid);
+hipError_t pt_launch_accum_reproject(const PtAccumReprojectArgs* a, hipStream_t stream);
 // pt_accum.hip: geometry of the resolve kernel (block, vgprs); hipErrorInvalidConfiguration if one of the two kernels needs scratch
 hipError_t pt_accum_geometry(PtGeometry* g);
 hipError_t pt_launch_accum_resolve(const PtAccumArgs* a, hipStream_t stream);

@@ -43,6 +43,8 @@ hipError_t pt_launch_accum_variance(const PtAccumVarArgs*, hipStream_t) { return
 hipError_t pt_accum_geometry(PtGeometry*) { return hipErrorNotSupported; }
 hipError_t pt_launch_accum_resolve(const PtAccumArgs*, hipStream_t) { return hipErrorNotSupported; }
 hipError_t pt_launch_accum_select(const PtAccumSelectArgs*, hipStream_t) { return hipErrorNotSupported; }
+hipError_t pt_accum_reproject_geometry(int, int, PtGeometry*, int*) { return hipErrorNotSupported; }
+hipError_t pt_launch_accum_reproject(const PtAccumReprojectArgs*, hipStream_t) { return hipErrorNotSupported; }
 hipError_t pt_launch_probe(const PtKernelParams*, int, const float*, int, float*, int, long long, int, size_t, uint32_t*, hipStream_t) { return hipErrorNotSupported; }
 int pt_probe_lds_stack(void) { return 12; }
 size_t pt_probe_group_lds_bytes(int, int) { return 16; }

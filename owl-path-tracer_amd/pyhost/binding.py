@@ -79,6 +79,14 @@ class AccumParams(C.Structure):
     _fields_ = [("n_samples", C.c_int32), ("max_pixel_samples", C.c_int32), ("noise_threshold", C.c_float), ("reserved", C.c_int32)]
 
 
+class ReprojectParams(C.Structure):
+    """pt_reproject_params: max_history (0: no cap, else >= 2), reserved (0), depth_tol (>= 0), normal_min (<= 1), albedo_tol (>= 0); +inf / -inf switch a test off."""
+    _fields_ = [("max_history", C.c_int32), ("reserved", C.c_int32), ("depth_tol", C.c_float), ("normal_min", C.c_float), ("albedo_tol", C.c_float)]
+
+
+pt_reproject_params = ReprojectParams
+
+
 class AccumInfo(C.Structure):
     """pt_accum_info."""
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("max_path_depth", C.c_int32), ("adds", C.c_int32), ("owned_pixels", C.c_int64),
@@ -115,7 +123,8 @@ EXPORTS = ["pt_create", "pt_destroy", "pt_last_error", "pt_abi_version", "pt_upl
            "pt_accum_default_params", "pt_accum_begin", "pt_accum_add", "pt_accum_add_device", "pt_accum_read", "pt_accum_info_get", "pt_accum_end",
            "pt_debug_accum_resolve_host", "pt_debug_accum_select_host", "pt_debug_accum_state",
            "pt_denoise_var_default_params", "pt_denoise_var", "pt_denoise_var_device", "pt_debug_denoise_var_host",
-           "pt_accum_variance", "pt_debug_accum_variance_host", "pt_accum_denoise", "pt_accum_denoise_device"]
+           "pt_accum_variance", "pt_debug_accum_variance_host", "pt_accum_denoise", "pt_accum_denoise_device",
+           "pt_accum_reproject_default_params", "pt_accum_reproject", "pt_accum_reproject_device", "pt_debug_accum_reproject_host"]
 PT_DENOISE_DEMODULATE = 1
 PT_TREE_DEVICE = 16  # pt_debug_export_tree: ORed into `which`, the array as HBM holds it
 PT_COMM_ID_BYTES = 128
@@ -248,6 +257,13 @@ def lib():
     L.pt_debug_accum_variance_host.restype = C.c_int64
     L.pt_accum_denoise.argtypes = [C.c_void_p, fp, C.POINTER(DenoiseParams), fp, u32p]
     L.pt_accum_denoise_device.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(DenoiseParams), C.c_void_p, C.c_void_p, C.c_void_p]
+    L.pt_accum_reproject_default_params.restype = None
+    L.pt_accum_reproject_default_params.argtypes = [C.POINTER(ReprojectParams)]
+    L.pt_accum_reproject.argtypes = [C.c_void_p, C.POINTER(Camera), fp, fp, C.POINTER(ReprojectParams)]
+    L.pt_accum_reproject_device.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_void_p, C.c_void_p, C.POINTER(ReprojectParams), C.c_void_p]
+    L.pt_debug_accum_reproject_host.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(Camera), C.c_int32, C.c_int32, fp, fp, u8p, C.POINTER(ReprojectParams),
+                                                fp, fp, u32p, u32p, u32p, fp, u32p, fp]
+    L.pt_debug_accum_reproject_host.restype = C.c_int64
     _lib = L
     return L
 
@@ -364,6 +380,17 @@ def accum_default_params(**changes):
     lib().pt_accum_default_params(C.byref(p))
     for k, v in changes.items():
         if k not in dict(AccumParams._fields_):
+            raise KeyError(k)
+        setattr(p, k, v)
+    return p
+
+
+def reproject_default_params(**changes):
+    """pt_accum_reproject_default_params (no cap, depth_tol 0.05, normal_min 0.9, albedo_tol 0.1), with the given fields changed."""
+    p = ReprojectParams()
+    lib().pt_accum_reproject_default_params(C.byref(p))
+    for k, v in changes.items():
+        if k not in dict(ReprojectParams._fields_):
             raise KeyError(k)
         setattr(p, k, v)
     return p
@@ -843,6 +870,44 @@ class Context:
         """pt_accum_denoise_device: asynchronous, device pointers (integers); stream and ordering as accum_add_device."""
         self._check(lib().pt_accum_denoise_device(self._h, C.c_void_p(d_aov), C.byref(params) if params is not None else None, C.c_void_p(d_out_rgb),
                                                   C.c_void_p(d_out_rgba8) if d_out_rgba8 else None, C.c_void_p(stream) if stream else None), "pt_accum_denoise_device")
+
+    # ---- reprojection (pt_accum_reproject*) ----
+    def accum_reproject(self, new_cam, aov_prev, aov_cur, params=None):
+        """pt_accum_reproject: the accumulation follows the surfaces to new_cam.  aov_prev / aov_cur: the guides (H, W, 8) under the
+        accumulation's camera and under new_cam (may be the same array); params a ReprojectParams (None: the defaults)."""
+        H, W = self._accum_shape
+        prev = np.ascontiguousarray(aov_prev, np.float32)
+        cur = prev if aov_cur is aov_prev else np.ascontiguousarray(aov_cur, np.float32)
+        assert prev.shape == (H, W, 8) and cur.shape == (H, W, 8)
+        fp = C.POINTER(C.c_float)
+        self._check(lib().pt_accum_reproject(self._h, C.byref(new_cam), prev.ctypes.data_as(fp), cur.ctypes.data_as(fp), C.byref(params) if params is not None else None),
+                    "pt_accum_reproject")
+
+    def accum_reproject_device(self, new_cam, d_aov_prev, d_aov_cur, params=None, stream=None):
+        """pt_accum_reproject_device: asynchronous, device pointers (integers, 16-byte aligned); stream and ordering as accum_add_device."""
+        self._check(lib().pt_accum_reproject_device(self._h, C.byref(new_cam), C.c_void_p(d_aov_prev), C.c_void_p(d_aov_cur), C.byref(params) if params is not None else None,
+                                                    C.c_void_p(stream) if stream else None), "pt_accum_reproject_device")
+
+    def accum_reproject_host(self, old_cam, new_cam, aov_prev, aov_cur, state, owned=None, params=None):
+        """pt_debug_accum_reproject_host, the CPU twin (works on a host-only context).  state: dict(sum, half (H, W, 3), n, n_half, passes
+        (H, W)) in framebuffer order as accum_state gives it; owned (H, W) flags or None.  The inputs are not changed -> dict(sum, half, n,
+        n_half, passes, rgb, rgba8, noise)."""
+        prev, cur = np.ascontiguousarray(aov_prev, np.float32), np.ascontiguousarray(aov_cur, np.float32)
+        H, W = prev.shape[0], prev.shape[1]
+        assert prev.shape == (H, W, 8) and cur.shape == (H, W, 8)
+        o = dict(sum=np.array(state["sum"], np.float32), half=np.array(state["half"], np.float32), n=np.array(state["n"], np.uint32),
+                 n_half=np.array(state["n_half"], np.uint32), passes=np.array(state["passes"], np.uint32), rgb=np.empty((H, W, 3), np.float32),
+                 rgba8=np.empty((H, W), np.uint32), noise=np.empty((H, W), np.float32))
+        assert o["sum"].shape == (H, W, 3) and o["half"].shape == (H, W, 3) and all(o[k].shape == (H, W) for k in ("n", "n_half", "passes"))
+        own = None if owned is None else np.ascontiguousarray(owned, np.uint8)
+        assert own is None or own.shape == (H, W)
+        fp, up, bp = C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.POINTER(C.c_uint8)
+        rc = lib().pt_debug_accum_reproject_host(self._h, C.byref(old_cam), C.byref(new_cam), W, H, prev.ctypes.data_as(fp), cur.ctypes.data_as(fp),
+                                                 own.ctypes.data_as(bp) if own is not None else None, C.byref(params) if params is not None else None,
+                                                 o["sum"].ctypes.data_as(fp), o["half"].ctypes.data_as(fp), o["n"].ctypes.data_as(up), o["n_half"].ctypes.data_as(up),
+                                                 o["passes"].ctypes.data_as(up), o["rgb"].ctypes.data_as(fp), o["rgba8"].ctypes.data_as(up), o["noise"].ctypes.data_as(fp))
+        self._check(int(rc), "pt_debug_accum_reproject_host")
+        return o
 
     def comm_init_rank(self, unique_id, rank, world):
         buf = (C.c_uint8 * PT_COMM_ID_BYTES).from_buffer_copy(unique_id)
