@@ -170,7 +170,7 @@ int pt_render(pt_ctx* ctx, const pt_camera* cam, int32_t width, int32_t height, 
  * every call that touches what a frame in flight uses is ordered after the context's LAST ASYNCHRONOUS CALL, whichever stream that
  * call was given.  So any call of this header may follow a pt_*_device call at once, with no pt_synchronize between them.
  *   - The asynchronous calls (pt_render_device, pt_render_batch_device, pt_render_aov_device, pt_render_aov_follow_device, pt_render_aov_batch_device, pt_denoise_device,
- *     pt_denoise_batch_device, pt_denoise_var_device, pt_accum_add_device, pt_accum_denoise_device, pt_accum_reproject_device, pt_reduce_framebuffer) wait ON THE
+ *     pt_denoise_batch_device, pt_denoise_var_device, pt_accum_add_device, pt_accum_denoise_device, pt_accum_reproject_device, pt_upsample_device, pt_reduce_framebuffer) wait ON THE
  *     DEVICE: the stream they are given waits for an event recorded at the end of the previous asynchronous call - only if that call
  *     used another stream; on the same stream the stream's own order suffices and nothing is added.  The host returns at once, with
  *     two exceptions that existed before: a frame of another size, shard or batch length rewrites the pixel queue and a frame that
@@ -178,7 +178,7 @@ int pt_render(pt_ctx* ctx, const pt_camera* cam, int32_t width, int32_t height, 
  *     before) - both first wait on the host for the frame in flight; pt_render_batch_device and pt_render_aov_batch_device
  *     return when their per-frame tables have reached HBM, i.e. after whatever precedes them on `stream`; and a pt_accum_add_device that
  *     selects its pixels returns when the count of its active set has reached the host (see there).
- *   - The blocking renders (pt_render, pt_render_batch, pt_render_aov, pt_render_aov_follow, pt_render_aov_batch, pt_accum_add), pt_denoise, pt_denoise_batch, pt_denoise_var, pt_accum_denoise and pt_accum_reproject run on the context's stream behind the same device-side wait
+ *   - The blocking renders (pt_render, pt_render_batch, pt_render_aov, pt_render_aov_follow, pt_render_aov_batch, pt_accum_add), pt_denoise, pt_denoise_batch, pt_denoise_var, pt_accum_denoise, pt_accum_reproject and pt_upsample run on the context's stream behind the same device-side wait
  *     and return with the context idle.  After a blocking call, or on the context's own stream, they add no wait at all.
  *   - The calls that change or read what a frame uses WAIT ON THE HOST for the last asynchronous call's stream (if it is not the
  *     context's) and then for the context's: pt_set_materials, pt_set_environment, pt_update_vertices, pt_upload_scene,
@@ -193,7 +193,7 @@ int pt_render(pt_ctx* ctx, const pt_camera* cam, int32_t width, int32_t height, 
 int pt_render_device(pt_ctx* ctx, const pt_camera* cam, int32_t width, int32_t height, int32_t max_samples, int32_t max_path_depth,
                      void* d_out_rgb, void* d_out_rgba8, void* stream);
 /* Waits on the host for the context's last asynchronous call - pt_render_device, pt_render_batch_device, pt_render_aov_device,
- * pt_render_aov_follow_device, pt_render_aov_batch_device, pt_denoise_device, pt_denoise_batch_device, pt_denoise_var_device, pt_accum_add_device, pt_accum_denoise_device, pt_accum_reproject_device or pt_reduce_framebuffer, on the stream it was given - and for the context's own stream.  Every earlier asynchronous call of the context
+ * pt_render_aov_follow_device, pt_render_aov_batch_device, pt_denoise_device, pt_denoise_batch_device, pt_denoise_var_device, pt_accum_add_device, pt_accum_denoise_device, pt_accum_reproject_device, pt_upsample_device or pt_reduce_framebuffer, on the stream it was given - and for the context's own stream.  Every earlier asynchronous call of the context
  * is complete then as well, whatever stream it used: each was ordered before the next (see pt_render_device).  Returns PT_E_HIP if a
  * wave's watchdog fired during the last frame (the image is then incomplete); pt_get_stats reports the same.  PT_OK at once on an idle
  * or host-only context.  A caller's stream may be destroyed once this has returned. */
@@ -613,6 +613,70 @@ int64_t pt_debug_accum_reproject_host(pt_ctx* ctx, const pt_camera* old_cam, con
                                       const float* aov_prev, const float* aov_cur, const uint8_t* owned /* W*H, framebuffer order; NULL = all */, const pt_reproject_params* p,
                                       float* sum, float* half, uint32_t* n, uint32_t* n_half, uint32_t* passes, /* in/out, framebuffer order, as pt_debug_accum_state gives them */
                                       float* out_rgb, uint32_t* out_rgba8, float* out_noise);                   /* framebuffer order; returns W*H */
+
+/* ---- upsampling: lift a low-resolution frame to full resolution with full-resolution guides (no reference counterpart) ----
+ * The render is the one cost of a frame that grows with the pixel count; the guide pass is cheap at any size and pt_camera is
+ * resolution-independent (su = (px + rx) / W: ONE camera struct serves both sizes).  Irradiance is smooth where albedo and geometry
+ * are not, so a frame rendered (and filtered) at w x h is lifted to W x H by joint bilateral upsampling (Kopf, Cohen, Lischinski,
+ * Uyttendaele 2007): a tent filter over taps x taps low-resolution pixels, every tap weighted by how far its low-resolution guides
+ * differ from the high-resolution pixel's in shading normal, relative depth and albedo; optionally on colour / albedo
+ * (PT_UPSAMPLE_DEMODULATE).  It needs no scene and keeps no render state; it needs WHOLE frames: with N GPUs call it on rank 0 after
+ * the reduce.  No batch form, no group form, no collective.
+ * BUFFERS: rgb_lo is w*h*3 floats, aov_lo w*h*8 floats, aov_hi W*H*8 floats, out_rgb W*H*3 floats, all in the framebuffer order that
+ * pt_render and pt_render_aov produce; like pt_denoise the filter works in rows as they lie in memory (row = index / width; the mapping
+ * below is symmetric under the row flip).  Device guide pointers are 16-byte aligned.  Outputs must not overlap inputs.  out_rgba8 is
+ * optional.
+ * DEFINITION (the kernels of csrc/pt_upsample.hip, the CPU twin pt_debug_upsample_host and the numpy restatement tests/upsample_ref.py
+ * implement exactly this).  Arithmetic: the contract of csrc/pt_device.h - float32, no contraction, fma_ only where written, correctly
+ * rounded "/", its dot, exp_, max_, abs_, make_rgba; floorf is exact.
+ *   Host constants, once, in this order:  rx = (float)w / (float)W, ry = (float)h / (float)H;  kn = 1.0f / (sigma_normal * sigma_normal),
+ *             ka likewise from sigma_albedo;  R = taps / 2, ir = 1.0f / (float)R.
+ *   Prepare, per low pixel q, from aov_lo: a = floats 0..2, n = floats 4..6, z = float 7.  An rgb_k that is not finite is taken as 0;
+ *             c(q)_k = rgb_k / max_(a_k, 1e-3f) with the flag, else rgb_k.
+ *   Per high pixel p = (x, row), with a_p, n_p, z_p from its aov_hi record:
+ *     1. sd = sigma_depth * max_(z_p, 1e-6f), kz = 1.0f / (sd * sd).
+ *     2. fx = ((float)x + 0.5f) * rx - 0.5f, x0 = (int)floorf(fx), tx = fx - (float)x0.  The same gives fy, y0, ty from row and ry.
+ *     3. sum = psum = (0, 0, 0), wsum = pw = 0.
+ *     4. For j = 1-R .. R (outer) and i = 1-R .. R (inner), q = (x0 + i, y0 + j):
+ *          a tap outside the low frame is skipped (no clamp, no mirror);
+ *          bx = 1.0f - abs_((float)i - tx) * ir, by likewise from j and ty, and the tap is skipped unless bx > 0 && by > 0;
+ *          b = bx * by;  psum_k = fma_(b, c(q)_k, psum_k);  pw = pw + b;
+ *          en = dot(n(q) - n_p, same);  dz = z(q) - z_p, ez = dz * dz;  ea = dot(a(q) - a_p, same);
+ *          e = fma_(ea, ka, fma_(ez, kz, en * kn));  wt = b * exp_(-e);
+ *          if !(wt > 0) the tap adds nothing more (NaN and non-finite guides included);
+ *          sum_k = fma_(wt, c(q)_k, sum_k);  wsum = wsum + wt.
+ *     5. v = (wsum >= 1e-4f * pw) ? sum / wsum : psum / pw.  When no low-resolution neighbour matches, the pixel is a feature thinner
+ *        than a low pixel and gets the plain tent filter.  pw > 0 always, because the tap at x0 or at x0 + 1 lies in the frame with
+ *        positive bx (and likewise in y).
+ *     6. out_k = v_k * max_(a_p_k, 1e-3f) with the flag, else v_k;  out_rgba8 = make_rgba(out).
+ * CONSEQUENCES: every sigma at +infinity, flag 0, taps 2 and finite guides give bilinear interpolation.  Equal sizes, identical finite
+ * guides, flag 0 and taps 2 give the sanitised input bit for bit: there is then one tap with b = 1, and exp_(-0.0f) is exactly 1.0f by
+ * the code of pt_device.h (a -0.0f comes back as +0.0f: fma_(1, c, +0); with taps 4 the tent has radius 2 and reaches the neighbours).
+ * LIMITS: first-hit guides blur what shows in mirrors and glass; pt_render_aov_follow guides at both sizes help.  Shadow and
+ * indirect-light edges have no guide: they are interpolated at low-resolution sharpness.
+ * REFUSED with PT_E_INVALID, by name, before anything is touched: a NULL pointer (p and out_rgba8 excepted); w, h, W or H outside
+ * 1..65535, or W*H >= 2^31; w > W or h > H; taps not 2 or 4; an unknown flag bit; a sigma that is not > 0 (NaN included; +infinity is
+ * allowed and switches the term off); reserved != 0.  A host-only context answers valid arguments with PT_E_NO_DEVICE and invalid ones
+ * with PT_E_INVALID; the twin works there.
+ * ORDERING: pt_upsample_device joins the asynchronous calls of the streams contract at pt_render_device and the list at pt_synchronize
+ * (its records, 48 bytes per low pixel, live in a work buffer of the context that grows like pt_denoise_device's).  pt_upsample is
+ * blocking like pt_denoise: it stages its three inputs and reads back.  pt_get_stats afterwards: kernel_ms from the first to the last
+ * kernel, launches = 2, block, grid, vgprs, lds_bytes those of the upsample kernel. */
+#define PT_UPSAMPLE_DEMODULATE 1
+typedef struct pt_upsample_params {
+    int32_t taps;       /* 2 or 4: the low-resolution window is taps x taps */
+    int32_t flags;      /* bit 0 PT_UPSAMPLE_DEMODULATE; other bits must be 0 */
+    float sigma_normal, sigma_depth, sigma_albedo;   /* each > 0; +infinity switches the term off */
+    int32_t reserved;   /* must be 0 */
+} pt_upsample_params;                                 /* 24 bytes */
+void pt_upsample_default_params(pt_upsample_params* p);   /* 4, PT_UPSAMPLE_DEMODULATE, 0.25f, 0.1f, 0.2f, 0 */
+int pt_upsample(pt_ctx* ctx, const float* rgb_lo, const float* aov_lo, int32_t w, int32_t h, const float* aov_hi, int32_t W, int32_t H,
+                const pt_upsample_params* p /* NULL = defaults */, float* out_rgb, uint32_t* out_rgba8 /* optional */);
+int pt_upsample_device(pt_ctx* ctx, const void* d_rgb_lo, const void* d_aov_lo, int32_t w, int32_t h, const void* d_aov_hi, int32_t W, int32_t H,
+                       const pt_upsample_params* p, void* d_out_rgb, void* d_out_rgba8, void* stream);
+/* The CPU twin: the definition above on all host threads; works on a host-only context; returns W * H. */
+int64_t pt_debug_upsample_host(pt_ctx* ctx, const float* rgb_lo, const float* aov_lo, int32_t w, int32_t h, const float* aov_hi, int32_t W, int32_t H,
+                               const pt_upsample_params* p, float* out_rgb, uint32_t* out_rgba8);
 
 /* ---- N GPUs: pixel tiles sharded over ranks + ONE RCCL sum-reduce of the float3 framebuffer onto rank 0 (pt_comm.cpp) ----
  * No reference counterpart (the reference is single-GPU: create_context(nullptr, 1), application.cpp:62); for N > 1 these

@@ -1,7 +1,8 @@
 // pt_guides.cpp -- what goes with a frame: the guide pass (pt_render_aov*: first hit or follow mode, one frame or the frames of a batch)
 // the denoiser (pt_denoise*, one frame or a batch) and the variance-guided denoiser (pt_denoise_var*, and pt_accum_denoise* /
-// pt_accum_variance on the context's accumulation), each ONE device path behind its asynchronous and blocking entry points.
-// None reads the render's pixel queue or touches its buffers and state (d_laps, slots): their own are d_aov_ws, d_dn_ws and d_dn_var.
+// pt_accum_variance on the context's accumulation) and the upsampling (pt_upsample*), each ONE device path behind its asynchronous and
+// blocking entry points.
+// None reads the render's pixel queue or touches its buffers and state (d_laps, slots): their own are d_aov_ws, d_dn_ws, d_dn_var and d_up_ws.
 #include <algorithm>
 #include <cstring>
 
@@ -279,6 +280,67 @@ int denoise_blocking(pt_ctx* c, const DenoiseJob& j, const float* rgb, const flo
     });
 }
 
+// ---- upsampling (pt_upsample*) -----------------------------------------------------------------------------------------------
+// A w x h frame and its guides to W x H under the high guides, over device buffers: prepare over the low frame, the upsample kernel over
+// the high one (pt_upsample.hip).  It reads no scene; its records live in d_up_ws.
+struct UpsampleJob {
+    int w, h, W, H;
+    pt_upsample_params prm; // checked by the caller (check_upsample_args)
+};
+
+int upsample_device(pt_ctx* c, const UpsampleJob& j, const void* d_rgb_lo, const void* d_aov_lo, const void* d_aov_hi, void* d_out_rgb, void* d_out_rgba8, hipStream_t stream)
+{
+    PtGeometry g{};
+    int grid = 0;
+    const hipError_t ge = pt_upsample_geometry(j.W, j.H, &g, &grid);
+    if (ge == hipErrorInvalidConfiguration) return fail(c, PT_E_LIMIT, "this build of the upsample kernels spills registers to scratch; such builds are refused (pt_upsample.hip)");
+    HIP_TRY(c, ge);
+    int rc;
+    if ((rc = ensure(c, c->d_up_ws, pt_upsample_workspace_bytes(j.w, j.h)))) return rc; // (growing it first waits on the host for what is in flight)
+    PtUpsampleArgs A{};
+    A.rgb_lo = (const float*)d_rgb_lo;
+    A.aov_lo = (const float*)d_aov_lo;
+    A.aov_hi = (const float*)d_aov_hi;
+    A.out_rgb = (float*)d_out_rgb;
+    A.out_rgba8 = (uint32_t*)d_out_rgba8;
+    A.ws = c->d_up_ws.p;
+    A.w = j.w; A.h = j.h; A.W = j.W; A.H = j.H;
+    A.taps = j.prm.taps;
+    A.flags = j.prm.flags;
+    A.sigma_depth = j.prm.sigma_depth;
+    upsample_constants(j.prm, j.w, j.h, j.W, j.H, &A.rx, &A.ry, &A.kn, &A.ka, &A.ir);
+    HIP_TRY(c, hipEventRecord(c->ev0, stream));
+    HIP_TRY(c, pt_launch_upsample(&A, stream));
+    HIP_TRY(c, hipEventRecord(c->ev1, stream)); // kernel_ms: from the first to the last kernel
+    note_pass(c, j.W, j.H, 2, grid, g, 0, false);
+    return PT_OK;
+}
+
+int upsample_async(pt_ctx* c, const UpsampleJob& j, const void* d_rgb_lo, const void* d_aov_lo, const void* d_aov_hi, void* d_out_rgb, void* d_out_rgba8, void* stream_v)
+{
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t stream = stream_v ? (hipStream_t)stream_v : c->stream;
+    return async_call(c, stream, [&] { return upsample_device(c, j, d_rgb_lo, d_aov_lo, d_aov_hi, d_out_rgb, d_out_rgba8, stream); });
+}
+
+// Host buffers: the low frame and its guides staged in d_up_rgb / d_up_aov, the high guides in d_dn_aov, the result in d_dn_rgb (and
+// d_dn_out8), and back.
+int upsample_blocking(pt_ctx* c, const UpsampleJob& j, const float* rgb_lo, const float* aov_lo, const float* aov_hi, float* out_rgb, uint32_t* out_rgba8)
+{
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t n_lo = (size_t)j.w * (size_t)j.h, n_hi = (size_t)j.W * (size_t)j.H;
+    return blocking_call(c, [&]() -> int {
+        int rc;
+        if ((rc = ensure(c, c->d_up_rgb, n_lo * 12)) || (rc = ensure(c, c->d_up_aov, n_lo * 32)) || (rc = ensure(c, c->d_dn_aov, n_hi * 32)) || (rc = ensure(c, c->d_dn_rgb, n_hi * 12))) return rc;
+        if (out_rgba8 && (rc = ensure(c, c->d_dn_out8, n_hi * 4))) return rc;
+        HIP_TRY(c, hipMemcpyAsync(c->d_up_rgb.p, rgb_lo, n_lo * 12, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(c->d_up_aov.p, aov_lo, n_lo * 32, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(c->d_dn_aov.p, aov_hi, n_hi * 32, hipMemcpyHostToDevice, c->stream));
+        if ((rc = upsample_device(c, j, c->d_up_rgb.p, c->d_up_aov.p, c->d_dn_aov.p, c->d_dn_rgb.p, out_rgba8 ? c->d_dn_out8.p : nullptr, c->stream))) return rc;
+        return drain(c, {{out_rgb, c->d_dn_rgb.p, n_hi * 12}, {out_rgba8, c->d_dn_out8.p, n_hi * 4}});
+    });
+}
+
 // ---- variance-guided denoiser (pt_denoise_var*, pt_accum_denoise*, pt_accum_variance) ------------------------------------------
 // The variance kernel over the accumulation's state, into d_out_var (W*H*3 floats, framebuffer order).  It reads the state and writes none.
 int accum_variance_launch(pt_ctx* c, void* d_out_var, hipStream_t stream)
@@ -475,6 +537,29 @@ int pt_denoise(pt_ctx* c, const float* rgb, const float* aov, int32_t W, int32_t
     DenoiseJob j{false, 1, W, H};
     if ((rc = need_device(c)) || (rc = check_denoise_args(c, "pt_denoise", W, H, p, &j.prm))) return rc;
     return denoise_blocking(c, j, rgb, aov, out_rgb, out_rgba8);
+}
+
+int pt_upsample_device(pt_ctx* c, const void* d_rgb_lo, const void* d_aov_lo, int32_t w, int32_t h, const void* d_aov_hi, int32_t W, int32_t H, const pt_upsample_params* p,
+                       void* d_out_rgb, void* d_out_rgba8, void* stream_v)
+{
+    if (!c) return PT_E_INVALID;
+    if (!d_rgb_lo || !d_aov_lo || !d_aov_hi || !d_out_rgb)
+        return fail(c, PT_E_INVALID, "pt_upsample_device: NULL %s", !d_rgb_lo ? "d_rgb_lo" : (!d_aov_lo ? "d_aov_lo" : (!d_aov_hi ? "d_aov_hi" : "d_out_rgb")));
+    int rc;
+    UpsampleJob j{w, h, W, H};
+    if ((rc = check_upsample_args(c, "pt_upsample_device", w, h, W, H, p, &j.prm)) || (rc = need_device(c))) return rc;
+    return upsample_async(c, j, d_rgb_lo, d_aov_lo, d_aov_hi, d_out_rgb, d_out_rgba8, stream_v);
+}
+
+int pt_upsample(pt_ctx* c, const float* rgb_lo, const float* aov_lo, int32_t w, int32_t h, const float* aov_hi, int32_t W, int32_t H, const pt_upsample_params* p, float* out_rgb,
+                uint32_t* out_rgba8)
+{
+    if (!c) return PT_E_INVALID;
+    if (!rgb_lo || !aov_lo || !aov_hi || !out_rgb) return fail(c, PT_E_INVALID, "pt_upsample: NULL %s", !rgb_lo ? "rgb_lo" : (!aov_lo ? "aov_lo" : (!aov_hi ? "aov_hi" : "out_rgb")));
+    int rc;
+    UpsampleJob j{w, h, W, H};
+    if ((rc = check_upsample_args(c, "pt_upsample", w, h, W, H, p, &j.prm)) || (rc = need_device(c))) return rc;
+    return upsample_blocking(c, j, rgb_lo, aov_lo, aov_hi, out_rgb, out_rgba8);
 }
 
 int pt_denoise_var_device(pt_ctx* c, const void* d_rgb, const void* d_var, const void* d_aov, int32_t W, int32_t H, const pt_denoise_params* p, void* d_out_rgb, void* d_out_rgba8,

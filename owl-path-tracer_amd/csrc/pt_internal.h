@@ -138,6 +138,7 @@ struct pt_ctx {
     DevBuf d_aov, d_aov_ws; // guide pass: the frame of pt_render_aov / pt_group_render_aov; bound flag (64 words) + the waves' stack overflow columns
     DevBuf d_dn_ws, d_dn_rgb, d_dn_aov, d_dn_out8; // denoiser: the filter's records (pt_denoise_workspace_bytes); pt_denoise's staging of rgb (in and out), guides and RGBA8
     DevBuf d_dn_var; // pt_denoise_var's staging of the variance map; pt_accum_variance's / pt_accum_denoise's map of the accumulation
+    DevBuf d_up_ws, d_up_rgb, d_up_aov; // upsampling: the low frame's records (pt_upsample_workspace_bytes); pt_upsample's staging of the low frame and its guides (the high guides and both outputs stage in d_dn_aov, d_dn_rgb, d_dn_out8)
     std::vector<DevBuf> d_textures;
 
     // pixel queue
@@ -194,6 +195,9 @@ PT_LOCAL int accum_frame(pt_ctx* c, const pt_camera* cam, int W, int H, int n_sa
 PT_LOCAL int check_denoise_args(pt_ctx* c, const char* who, int W, int H, const pt_denoise_params* p, pt_denoise_params* eff,
                                 void (*defaults)(pt_denoise_params*) = pt_denoise_default_params); // the refusals of pt_denoise*, pt_denoise_var* and the twins; *eff = the parameters in effect (p null: defaults)
 PT_LOCAL void denoise_constants(const pt_denoise_params& p, float* kn, float* ka, float kc[8]); // the definition's host constants
+// pt_upsample_host.cpp
+PT_LOCAL int check_upsample_args(pt_ctx* c, const char* who, int w, int h, int W, int H, const pt_upsample_params* p, pt_upsample_params* eff); // the refusals of pt_upsample* and the twin; *eff = the parameters in effect (p null: defaults)
+PT_LOCAL void upsample_constants(const pt_upsample_params& p, int w, int h, int W, int H, float* rx, float* ry, float* kn, float* ka, float* ir); // the definition's host constants
 // pt_guides.cpp
 // End of an auxiliary pass, after its ev1: the one place beside finish_frame (pt_render.cpp) that writes what pt_synchronize and
 // pt_get_stats look at.  kernel_ms is ev0 .. ev1; g: the geometry of the pass's kernel; aov_flag: a guide pass, whose bound flag in

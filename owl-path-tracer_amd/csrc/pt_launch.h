@@ -170,7 +170,29 @@ struct PtAccumReprojectArgs {
     int32_t pad;
 };
 
+// Upsampling (pt_upsample; pt_upsample.hip): what its two kernels take.  The host fills everything but the record pointers, which
+// pt_launch_upsample carves out of ws; the constants are include/mi355pt.h's "host constants" (pti::upsample_constants).
+struct PtUpsampleArgs {
+    const float* rgb_lo;    // w*h*3 floats, framebuffer order
+    const float* aov_lo;    // w*h*8 floats of the guide pass at the low size, 16-byte aligned
+    const float* aov_hi;    // W*H*8 floats of the guide pass at the high size, 16-byte aligned
+    float* out_rgb;         // W*H*3 floats
+    uint32_t* out_rgba8;    // W*H, or null
+    void* ws;               // pt_upsample_workspace_bytes(w, h), 16-byte aligned
+    float4* col;            // low records: colour r g b (divided by the albedo divisor with the flag)
+    float4* nz;             // normal x y z + depth
+    float4* alb;            // albedo r g b
+    int32_t w, h, W, H;
+    int32_t taps, flags;
+    float sigma_depth, rx, ry, kn, ka, ir;
+};
+
 extern "C" {
+// pt_upsample.hip: prepare (over the low frame) + upsample (over the high frame) on `stream`; the geometry is the upsample kernel's
+// (grid = its workgroups for a W x H frame), hipErrorInvalidConfiguration if one of the two kernels needs scratch
+size_t pt_upsample_workspace_bytes(int w, int h);
+hipError_t pt_upsample_geometry(int W, int H, PtGeometry* g, int* grid);
+hipError_t pt_launch_upsample(const PtUpsampleArgs* a, hipStream_t stream);
 // pt_accum_reproject.hip: geometry of the reproject kernel (block, vgprs; *grid = its workgroups for a W x H frame);
 // hipErrorInvalidConfiguration if it needs scratch
 hipError_t pt_accum_reproject_geometry(int W, int H, PtGeometry* g, int* grid);

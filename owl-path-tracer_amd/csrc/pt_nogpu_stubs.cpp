@@ -45,6 +45,9 @@ hipError_t pt_launch_accum_resolve(const PtAccumArgs*, hipStream_t) { return hip
 hipError_t pt_launch_accum_select(const PtAccumSelectArgs*, hipStream_t) { return hipErrorNotSupported; }
 hipError_t pt_accum_reproject_geometry(int, int, PtGeometry*, int*) { return hipErrorNotSupported; }
 hipError_t pt_launch_accum_reproject(const PtAccumReprojectArgs*, hipStream_t) { return hipErrorNotSupported; }
+size_t pt_upsample_workspace_bytes(int, int) { return 16; }
+hipError_t pt_upsample_geometry(int, int, PtGeometry*, int*) { return hipErrorNotSupported; }
+hipError_t pt_launch_upsample(const PtUpsampleArgs*, hipStream_t) { return hipErrorNotSupported; }
 hipError_t pt_launch_probe(const PtKernelParams*, int, const float*, int, float*, int, long long, int, size_t, uint32_t*, hipStream_t) { return hipErrorNotSupported; }
 int pt_probe_lds_stack(void) { return 12; }
 size_t pt_probe_group_lds_bytes(int, int) { return 16; }

@@ -24,6 +24,9 @@
 // without the flag; works with --watertight, --aov and --denoise, not with --gpus / --devices or --batch).
 // --denoise-variance (needs --adds K with K >= 2 and --aov N, not with --denoise: after every frame and its guides pt_accum_denoise with the
 // default parameters - mi355pt.h, "variance-guided denoise" - on the frame's accumulation; <name>_denoised.png = its RGBA8 image).
+// --upsample K (K in 2..8; needs --aov N, not with --batch, --adds, --denoise-variance or --gpus / --devices: every frame is rendered at
+// ceil(W / K) x ceil(H / K), the guide pass runs at both sizes, --denoise filters the low frame, and pt_upsample with the default
+// parameters - mi355pt.h, "upsampling" - lifts it to W x H; <name>.png is that image and the only file of the frame).
 #include <sys/stat.h>
 #include <unistd.h>
 
@@ -108,6 +111,7 @@ struct App {
     bool denoise = false; // --denoise: pt_denoise of every frame with its guides
     int adds = 0;  // --adds K: every frame in K uniform adds of a progressive accumulation (0: one pt_render)
     bool denoise_variance = false; // --denoise-variance: pt_accum_denoise of every frame's accumulation with its guides
+    int upsample = 0; // --upsample K: render at 1/K of the size in each direction, pt_upsample to the full size (0: render at full size)
 };
 
 void check(App& a, int rc, const char* what)
@@ -125,13 +129,10 @@ uint32_t make_8bit(float f)
 }
 uint32_t make_rgba(float r, float g, float b) { return make_8bit(r) | (make_8bit(g) << 8) | (make_8bit(b) << 16) | (0xffu << 24); }
 
-// --aov: the guide buffers of the frame just rendered, as three PNGs next to it (base = the frame's path without ".png");
-// --denoise: the frame (rgb) filtered with them, as a fourth
-void write_guides(App& a, const std::string& base, const std::vector<float>& rgb)
+// the guide pass of --aov (first hit, or --follow) at W x H into g
+void render_guides(App& a, int W, int H, std::vector<float>& g)
 {
-    const int W = a.settings.buffer_size[0], H = a.settings.buffer_size[1];
-    const size_t npx = (size_t)W * H;
-    std::vector<float> g(npx * 8);
+    g.resize((size_t)W * H * 8);
     if (a.follow >= 0) {
         pt_aov_params prm;
         pt_aov_default_params(&prm);
@@ -142,6 +143,16 @@ void write_guides(App& a, const std::string& base, const std::vector<float>& rgb
         else check(a, pt_render_aov_follow(a.ctx, &a.cam, W, H, &prm, g.data()), "pt_render_aov_follow");
     } else if (a.group) check(a, pt_group_render_aov(a.group, &a.cam, W, H, a.aov, g.data()), "pt_group_render_aov");
     else check(a, pt_render_aov(a.ctx, &a.cam, W, H, a.aov, g.data()), "pt_render_aov");
+}
+
+// --aov: the guide buffers of the frame just rendered, as three PNGs next to it (base = the frame's path without ".png");
+// --denoise: the frame (rgb) filtered with them, as a fourth
+void write_guides(App& a, const std::string& base, const std::vector<float>& rgb)
+{
+    const int W = a.settings.buffer_size[0], H = a.settings.buffer_size[1];
+    const size_t npx = (size_t)W * H;
+    std::vector<float> g;
+    render_guides(a, W, H, g);
     float far = 0.0f;
     for (size_t i = 0; i < npx; ++i) far = g[8 * i + 7] > far ? g[8 * i + 7] : far;
     std::vector<uint32_t> albedo(npx), normal(npx), depth(npx);
@@ -168,9 +179,34 @@ void write_guides(App& a, const std::string& base, const std::vector<float>& rgb
     std::printf("Image written to %s\n", (base + "_denoised.png").c_str());
 }
 
+// --upsample K: the frame at ceil(W / K) x ceil(H / K) under the SAME camera (pt_camera is resolution-independent), guides at both sizes,
+// --denoise at the low size, pt_upsample to W x H
+void render_frame_upsampled(App& a, const std::string& values)
+{
+    std::fprintf(stderr, "TRACING\n");
+    const int W = a.settings.buffer_size[0], H = a.settings.buffer_size[1];
+    const int w = (W + a.upsample - 1) / a.upsample, h = (H + a.upsample - 1) / a.upsample;
+    std::vector<float> lo((size_t)w * h * 3), g_lo, g_hi, out((size_t)W * H * 3);
+    std::vector<uint32_t> rgba((size_t)W * H);
+    check(a, pt_render(a.ctx, &a.cam, w, h, a.settings.max_samples, a.settings.max_path_depth, lo.data(), nullptr), "pt_render");
+    pt_stats st;
+    pt_get_stats(a.ctx, &st);
+    render_guides(a, w, h, g_lo);
+    if (a.denoise) check(a, pt_denoise(a.ctx, lo.data(), g_lo.data(), w, h, nullptr, lo.data(), nullptr), "pt_denoise");
+    render_guides(a, W, H, g_hi);
+    check(a, pt_upsample(a.ctx, lo.data(), g_lo.data(), w, h, g_hi.data(), W, H, nullptr, out.data(), rgba.data()), "pt_upsample");
+    pt_stats su;
+    pt_get_stats(a.ctx, &su);
+    std::string path = a.out_dir + "/" + a.settings.scene + "_" + a.settings.test.name + "_" + a.settings.test.attribute_name + "(" + values + ").png";
+    imgio::write_png_rgba8(path, W, H, rgba.data());
+    std::printf("Image written to %s\n", path.c_str());
+    std::fprintf(stderr, "  %.1f ms render kernel at %dx%d, %.3f ms upsample to %dx%d\n", st.kernel_ms, w, h, su.kernel_ms, W, H);
+}
+
 // render_frame, application.cpp:363-371
 void render_frame(App& a, const std::string& values)
 {
+    if (a.upsample > 0) return render_frame_upsampled(a, values);
     std::fprintf(stderr, "TRACING\n");
     const int W = a.settings.buffer_size[0], H = a.settings.buffer_size[1];
     std::vector<float> rgb((size_t)W * H * 3);
@@ -295,6 +331,7 @@ int main(int argc, char** argv)
         std::string settings_path, dump;
         a.out_dir = cwd;
         int device = 0, gpus = 0; // gpus 0: flag not given, single context as in the reference
+        bool have_upsample = false;
         bool have_device = false, have_devices = false, have_batch = false, have_adds = false, have_aov = false, have_follow = false, have_follow_roughness = false, watertight = false;
         std::vector<int32_t> devs; // --devices
         for (int i = 1; i < argc; ++i) {
@@ -315,6 +352,7 @@ int main(int argc, char** argv)
             else if (k == "--denoise") a.denoise = true;
             else if (k == "--denoise-variance") a.denoise_variance = true;
             else if (k == "--adds") { a.adds = std::atoi(next().c_str()); have_adds = true; }
+            else if (k == "--upsample") { a.upsample = std::atoi(next().c_str()); have_upsample = true; }
             else if (k == "--convert-png" || k == "--convert-hdr") { // codec self-test hooks: decode with our reader, re-encode with our writer
                 std::string in = next(), out = next();
                 imgio::Image img = k == "--convert-png" ? imgio::load_png_rgba8(in) : imgio::load_hdr_as_ldr_rgba8(in);
@@ -341,6 +379,11 @@ int main(int argc, char** argv)
         if (a.denoise_variance && (!have_adds || a.adds < 2))
             throw std::runtime_error("--denoise-variance needs --adds K with K >= 2 (the variance estimate comes from the two halves of an accumulation's samples)");
         if (a.denoise_variance && !have_aov) throw std::runtime_error("--denoise-variance needs --aov N (the filter is driven by the guide buffers)");
+        if (have_upsample && have_batch) throw std::runtime_error("--upsample cannot be combined with --batch (pt_upsample has no batch form)");
+        if (have_upsample && !have_aov) throw std::runtime_error("--upsample needs --aov N (the upsampling is driven by the guide buffers at both sizes)");
+        if (have_upsample && (a.upsample < 2 || a.upsample > 8)) throw std::runtime_error("--upsample needs a factor 2..8");
+        if (have_upsample && (have_adds || a.denoise_variance)) throw std::runtime_error("--upsample cannot be combined with --adds / --denoise-variance (it renders the low frame with one pt_render)");
+        if (have_upsample && (gpus > 0 || have_devices)) throw std::runtime_error("--upsample cannot be combined with --gpus / --devices (pt_upsample has no group form)");
         if (have_follow && !have_aov) throw std::runtime_error("--follow needs --aov N (it is a mode of the guide pass)");
         if (have_follow && (a.follow < 0 || a.follow > 8)) throw std::runtime_error("--follow needs a number of surfaces 0..8");
         if (have_follow_roughness && !have_follow) throw std::runtime_error("--follow-roughness needs --follow K");

@@ -87,6 +87,12 @@ class ReprojectParams(C.Structure):
 pt_reproject_params = ReprojectParams
 
 
+class UpsampleParams(C.Structure):
+    """pt_upsample_params: taps (2 or 4), flags (PT_UPSAMPLE_DEMODULATE), three sigmas (> 0; +inf switches a term off), reserved (0)."""
+    _fields_ = [("taps", C.c_int32), ("flags", C.c_int32), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float), ("sigma_albedo", C.c_float),
+                ("reserved", C.c_int32)]
+
+
 class AccumInfo(C.Structure):
     """pt_accum_info."""
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("max_path_depth", C.c_int32), ("adds", C.c_int32), ("owned_pixels", C.c_int64),
@@ -124,8 +130,10 @@ EXPORTS = ["pt_create", "pt_destroy", "pt_last_error", "pt_abi_version", "pt_upl
            "pt_debug_accum_resolve_host", "pt_debug_accum_select_host", "pt_debug_accum_state",
            "pt_denoise_var_default_params", "pt_denoise_var", "pt_denoise_var_device", "pt_debug_denoise_var_host",
            "pt_accum_variance", "pt_debug_accum_variance_host", "pt_accum_denoise", "pt_accum_denoise_device",
-           "pt_accum_reproject_default_params", "pt_accum_reproject", "pt_accum_reproject_device", "pt_debug_accum_reproject_host"]
+           "pt_accum_reproject_default_params", "pt_accum_reproject", "pt_accum_reproject_device", "pt_debug_accum_reproject_host",
+           "pt_upsample_default_params", "pt_upsample", "pt_upsample_device", "pt_debug_upsample_host"]
 PT_DENOISE_DEMODULATE = 1
+PT_UPSAMPLE_DEMODULATE = 1
 PT_TREE_DEVICE = 16  # pt_debug_export_tree: ORed into `which`, the array as HBM holds it
 PT_COMM_ID_BYTES = 128
 
@@ -264,6 +272,13 @@ def lib():
     L.pt_debug_accum_reproject_host.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(Camera), C.c_int32, C.c_int32, fp, fp, u8p, C.POINTER(ReprojectParams),
                                                 fp, fp, u32p, u32p, u32p, fp, u32p, fp]
     L.pt_debug_accum_reproject_host.restype = C.c_int64
+    L.pt_upsample_default_params.restype = None
+    L.pt_upsample_default_params.argtypes = [C.POINTER(UpsampleParams)]
+    L.pt_upsample.argtypes = [C.c_void_p, fp, fp, C.c_int32, C.c_int32, fp, C.c_int32, C.c_int32, C.POINTER(UpsampleParams), fp, u32p]
+    L.pt_upsample_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(UpsampleParams), C.c_void_p, C.c_void_p,
+                                     C.c_void_p]
+    L.pt_debug_upsample_host.argtypes = [C.c_void_p, fp, fp, C.c_int32, C.c_int32, fp, C.c_int32, C.c_int32, C.POINTER(UpsampleParams), fp, u32p]
+    L.pt_debug_upsample_host.restype = C.c_int64
     _lib = L
     return L
 
@@ -358,6 +373,17 @@ def denoise_var_default_params(**changes):
     lib().pt_denoise_var_default_params(C.byref(p))
     for k, v in changes.items():
         if k not in dict(DenoiseParams._fields_):
+            raise KeyError(k)
+        setattr(p, k, v)
+    return p
+
+
+def upsample_default_params(**changes):
+    """pt_upsample_default_params (taps 4, PT_UPSAMPLE_DEMODULATE, sigmas 0.25, 0.1, 0.2), with the given fields changed."""
+    p = UpsampleParams()
+    lib().pt_upsample_default_params(C.byref(p))
+    for k, v in changes.items():
+        if k not in dict(UpsampleParams._fields_):
             raise KeyError(k)
         setattr(p, k, v)
     return p
@@ -723,6 +749,39 @@ class Context:
         hipStream_t as an integer, None = the context's own stream; ordering and lifetime as render_device."""
         self._check(lib().pt_denoise_device(self._h, C.c_void_p(d_rgb), C.c_void_p(d_aov), W, H, C.byref(params) if params is not None else None, C.c_void_p(d_out_rgb),
                                             C.c_void_p(d_out_rgba8) if d_out_rgba8 else None, C.c_void_p(stream) if stream else None), "pt_denoise_device")
+
+    # ---- upsampling (pt_upsample*) ----
+    def _upsample(self, fn, what, rgb_lo, aov_lo, aov_hi, params, want_rgba8):
+        aov_lo = np.ascontiguousarray(aov_lo, np.float32)
+        aov_hi = np.ascontiguousarray(aov_hi, np.float32)
+        rgb_lo = np.ascontiguousarray(rgb_lo, np.float32)
+        h, w = aov_lo.shape[0], aov_lo.shape[1]
+        H, W = aov_hi.shape[0], aov_hi.shape[1]
+        assert rgb_lo.shape == (h, w, 3) and aov_lo.shape == (h, w, 8) and aov_hi.shape == (H, W, 8)
+        out = np.empty((H, W, 3), np.float32)
+        rgba = np.empty((H, W), np.uint32) if want_rgba8 else None
+        fp = C.POINTER(C.c_float)
+        rc = fn(self._h, rgb_lo.ctypes.data_as(fp), aov_lo.ctypes.data_as(fp), w, h, aov_hi.ctypes.data_as(fp), W, H, C.byref(params) if params is not None else None,
+                out.ctypes.data_as(fp), rgba.ctypes.data_as(C.POINTER(C.c_uint32)) if rgba is not None else None)
+        if rc < 0:
+            self._check(int(rc), what)
+        return out, rgba
+
+    def upsample(self, rgb_lo, aov_lo, aov_hi, params=None, want_rgba8=False):
+        """pt_upsample: rgb_lo (h, w, 3) and aov_lo (h, w, 8) as render / render_aov return them at the low size, aov_hi (H, W, 8) at the
+        full size -> the (H, W, 3) frame (and its RGBA8 image).  params: an UpsampleParams (None: the defaults)."""
+        return self._upsample(lib().pt_upsample, "pt_upsample", rgb_lo, aov_lo, aov_hi, params, want_rgba8)
+
+    def upsample_host(self, rgb_lo, aov_lo, aov_hi, params=None, want_rgba8=False):
+        """pt_debug_upsample_host, the CPU twin of upsample (works on a host-only context)."""
+        return self._upsample(lib().pt_debug_upsample_host, "pt_debug_upsample_host", rgb_lo, aov_lo, aov_hi, params, want_rgba8)
+
+    def upsample_device(self, d_rgb_lo, d_aov_lo, w, h, d_aov_hi, W, H, d_out_rgb, params=None, d_out_rgba8=None, stream=None):
+        """pt_upsample_device: asynchronous, device pointers (integers; the outputs must not overlap the inputs); synchronize() waits for
+        it.  stream: a hipStream_t as an integer, None = the context's own stream; ordering and lifetime as render_device."""
+        self._check(lib().pt_upsample_device(self._h, C.c_void_p(d_rgb_lo), C.c_void_p(d_aov_lo), w, h, C.c_void_p(d_aov_hi), W, H,
+                                             C.byref(params) if params is not None else None, C.c_void_p(d_out_rgb), C.c_void_p(d_out_rgba8) if d_out_rgba8 else None,
+                                             C.c_void_p(stream) if stream else None), "pt_upsample_device")
 
     # ---- progressive accumulation (pt_accum_*) ----
     def accum_begin(self, cam, W, H, max_depth):
