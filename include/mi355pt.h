@@ -430,7 +430,9 @@ int64_t pt_debug_denoise_host(pt_ctx* ctx, const float* rgb, const float* aov, i
  * CONSEQUENCES.  A pixel with n samples is bit for bit that pixel of pt_render at max_samples = n (same camera, size, depth, scene
  * state, "watertight"), however the n were split into adds: uniform adds totalling N give the whole frame of pt_render(N), rgba8
  * included.  Samples see the materials, environment and vertices current at their add.  Changing the pixel shard or uploading a new
- * scene after pt_accum_begin makes the next add PT_E_INVALID until a new begin.
+ * scene after pt_accum_begin makes the next add PT_E_INVALID until a new begin.  The accumulation itself stays as it was and stays
+ * readable: pt_accum_read, pt_accum_info_get, pt_debug_accum_state, pt_accum_variance, pt_accum_denoise (which judges the shard the
+ * accumulation was begun with) and pt_accum_end go on working on it; with the shard it was begun with set again, adds go on too.
  * LAYOUTS: out_rgb (W*H*3 floats), out_rgba8, out_noise and out_samples (W*H each) are in framebuffer order x + W*(H-1-y), like out_rgb
  * of pt_render.
  * ORDERING: pt_accum_add_device joins the asynchronous calls of the streams contract at pt_render_device: ordered after the context's

@@ -94,6 +94,8 @@ def lib():
     L.orc_intersect_n.argtypes = [C.c_void_p, fp, C.c_int64, C.c_float, C.c_float, C.c_int, C.c_int, fp]
     L.orc_render.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(Env), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                              C.POINTER(C.c_uint32), C.c_int64, fp, C.POINTER(C.c_uint32), C.POINTER(Counters)]
+    L.orc_accumulate.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(Env), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                 C.POINTER(C.c_uint32), C.c_int64, C.c_int, C.POINTER(C.c_uint32), fp, C.POINTER(Counters)]
     L.orc_trace_pixel.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(Env), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                   C.c_int, fp, C.POINTER(C.c_uint32)]
     L.orc_rng_init.restype = C.c_uint32
@@ -399,6 +401,30 @@ class Scene:
         if rc != 0:
             raise RuntimeError("orc_render failed: %d" % rc)
         return rgb, rgba, (cnt.as_dict() if cnt is not None else None)
+
+    def accumulate(self, cam, env, W, H, n_samples, max_depth, rng, sum, pixel_list=None, first=False, threads=None, use_bvh=True):
+        """n_samples more samples for the launch ids x + W*y of pixel_list (None: every pixel), continuing from rng[id] (uint32, W*H) and
+        sum[3*id..] (float32, W*H*3), both in launch order and updated IN PLACE - or from the seed and 0 when `first` is set.  The scene's
+        present materials and triangle test apply.  Pixels not listed keep their rng and sum.  Returns (rng, sum)."""
+        for a, dt, size in ((rng, np.uint32, W * H), (sum, np.float32, W * H * 3)):
+            if not (isinstance(a, np.ndarray) and a.dtype == dt and a.flags.c_contiguous and a.flags.writeable and a.size == size):
+                raise ValueError("accumulate: rng / sum must be writeable contiguous uint32 (W*H) / float32 (W*H*3) arrays")
+        if threads is None:
+            threads = os.cpu_count() or 1
+        pl, npx = None, 0
+        if pixel_list is not None:
+            pl = np.ascontiguousarray(pixel_list, np.uint32).reshape(-1)
+            npx = pl.size
+            if np.unique(pl).size != npx:
+                raise ValueError("accumulate: pixel_list names a pixel twice")
+            if npx == 0:
+                return rng, sum
+        rc = lib().orc_accumulate(self.h, C.byref(cam), C.byref(env), W, H, int(n_samples), int(max_depth), int(use_bvh), int(threads),
+                                  pl.ctypes.data_as(C.POINTER(C.c_uint32)) if pl is not None else None, npx, int(bool(first)),
+                                  rng.ctypes.data_as(C.POINTER(C.c_uint32)), sum.ctypes.data_as(C.POINTER(C.c_float)), None)
+        if rc != 0:
+            raise RuntimeError("orc_accumulate failed: %d" % rc)
+        return rng, sum
 
     def trace_sample(self, cam, env, W, H, px, py, sample, max_depth, use_bvh=True, max_rows=256):
         """Per-bounce log of one sample of one pixel: (rows, 32) float32, layout in pt_oracle.c (ORC_LOG_FLOATS)."""

@@ -1381,14 +1381,15 @@ static v3 trace_path(const render_ctx* rc, v3 org, v3 dir, uint32_t* rng, orc_co
     return vmul(radiance, throughput); /* device.cu:217 */
 }
 
-/* one pixel of ray_gen, device.cu:220-254 */
-static v3 render_pixel(const render_ctx* rc, const orc_camera* cam, int W, int H, int px, int py, int max_samples, orc_counters* cnt,
-                       float* per_sample_rgb, uint32_t* per_sample_state)
+/* `n` more iterations of ray_gen's sample loop (device.cu:232-245) for one pixel, continuing from *rng and *color: THE one copy of the
+   loop.  per_sample_*: optional, n entries. */
+static void accumulate_pixel(const render_ctx* rc, const orc_camera* cam, int W, int H, int px, int py, int n, uint32_t* rng_io, v3* color_io,
+                             orc_counters* cnt, float* per_sample_rgb, uint32_t* per_sample_state)
 {
-    uint32_t rng = orc_rng_init((uint32_t)px, (uint32_t)py);
-    v3 color = vs(0.0f);
+    uint32_t rng = *rng_io;
+    v3 color = *color_io;
     v3 origin = ld3(cam->origin), llc = ld3(cam->llc), hor = ld3(cam->horizontal), ver = ld3(cam->vertical);
-    for (int s = 0; s < max_samples; ++s) {
+    for (int s = 0; s < n; ++s) {
         float rx = rng_next(&rng);
         float ry = rng_next(&rng);
         float su = ((float)px + rx) / (float)W;
@@ -1402,6 +1403,17 @@ static v3 render_pixel(const render_ctx* rc, const orc_camera* cam, int W, int H
         if (per_sample_rgb) st3(per_sample_rgb + (size_t)s * 3, r);
         if (per_sample_state) per_sample_state[s] = rng;
     }
+    *rng_io = rng;
+    *color_io = color;
+}
+
+/* one pixel of ray_gen, device.cu:220-254: accumulate from the seed, then scale */
+static v3 render_pixel(const render_ctx* rc, const orc_camera* cam, int W, int H, int px, int py, int max_samples, orc_counters* cnt,
+                       float* per_sample_rgb, uint32_t* per_sample_state)
+{
+    uint32_t rng = orc_rng_init((uint32_t)px, (uint32_t)py);
+    v3 color = vs(0.0f);
+    accumulate_pixel(rc, cam, W, H, px, py, max_samples, &rng, &color, cnt, per_sample_rgb, per_sample_state);
     color = vscale(color, 1.0f / (float)max_samples); /* device.cu:247 */
     return color;
 }
@@ -1414,6 +1426,9 @@ typedef struct job {
     int64_t n_pixels;
     float* out_rgb;
     uint32_t* out_rgba8;
+    uint32_t* acc_rng; /* orc_accumulate: the per-pixel state, by launch id; out_rgb / out_rgba8 are NULL then */
+    float* acc_sum;
+    int acc_first;
     int64_t next;
     pthread_mutex_t mu;
     orc_counters total;
@@ -1433,6 +1448,14 @@ static void* worker(void* arg)
         for (int64_t i = begin; i < end; ++i) {
             uint32_t id = j->pixel_list ? j->pixel_list[i] : (uint32_t)i;
             int px = (int)(id % (uint32_t)j->W), py = (int)(id / (uint32_t)j->W);
+            if (j->acc_rng) {
+                uint32_t rng = j->acc_first ? orc_rng_init((uint32_t)px, (uint32_t)py) : j->acc_rng[id];
+                v3 c = j->acc_first ? vs(0.0f) : ld3(j->acc_sum + (size_t)id * 3);
+                accumulate_pixel(&j->rc, j->cam, j->W, j->H, px, py, j->max_samples, &rng, &c, j->want_counters ? &local : NULL, NULL, NULL);
+                j->acc_rng[id] = rng;
+                st3(j->acc_sum + (size_t)id * 3, c);
+                continue;
+            }
             v3 c = render_pixel(&j->rc, j->cam, j->W, j->H, px, py, j->max_samples, j->want_counters ? &local : NULL, NULL, NULL);
             size_t ofs = (size_t)px + (size_t)j->W * (size_t)(j->H - 1 - py); /* device.cu:251 */
             if (j->out_rgb) st3(j->out_rgb + ofs * 3, c);
@@ -1449,6 +1472,20 @@ static void* worker(void* arg)
     return NULL;
 }
 
+static void run_job(job* j, int n_threads, orc_counters* counters)
+{
+    j->want_counters = counters != NULL;
+    pthread_mutex_init(&j->mu, NULL);
+    if (n_threads < 1) n_threads = 1;
+    if (n_threads > 256) n_threads = 256;
+    pthread_t th[256];
+    for (int i = 1; i < n_threads; ++i) pthread_create(&th[i], NULL, worker, j);
+    worker(j);
+    for (int i = 1; i < n_threads; ++i) pthread_join(th[i], NULL);
+    pthread_mutex_destroy(&j->mu);
+    if (counters) *counters = j->total;
+}
+
 int orc_render(const orc_scene* s, const orc_camera* cam, const orc_env* env, int W, int H, int max_samples, int max_depth, int use_bvh,
                int n_threads, const uint32_t* pixel_list, int64_t n_pixels, float* out_rgb, uint32_t* out_rgba8, orc_counters* counters)
 {
@@ -1460,16 +1497,25 @@ int orc_render(const orc_scene* s, const orc_camera* cam, const orc_env* env, in
     j.pixel_list = pixel_list;
     j.n_pixels = pixel_list ? n_pixels : (int64_t)W * H;
     j.out_rgb = out_rgb; j.out_rgba8 = out_rgba8;
-    j.want_counters = counters != NULL;
-    pthread_mutex_init(&j.mu, NULL);
-    if (n_threads < 1) n_threads = 1;
-    if (n_threads > 256) n_threads = 256;
-    pthread_t th[256];
-    for (int i = 1; i < n_threads; ++i) pthread_create(&th[i], NULL, worker, &j);
-    worker(&j);
-    for (int i = 1; i < n_threads; ++i) pthread_join(th[i], NULL);
-    pthread_mutex_destroy(&j.mu);
-    if (counters) *counters = j.total;
+    run_job(&j, n_threads, counters);
+    return 0;
+}
+
+int orc_accumulate(const orc_scene* s, const orc_camera* cam, const orc_env* env, int W, int H, int n_samples, int max_depth, int use_bvh,
+                   int n_threads, const uint32_t* pixel_list, int64_t n_pixels, int first, uint32_t* rng, float* sum, orc_counters* counters)
+{
+    if (!s || !cam || !env || !rng || !sum || W <= 0 || H <= 0 || n_samples <= 0 || (pixel_list && n_pixels < 0)) return -1;
+    if (pixel_list) /* ids are unique (two workers may not own one pixel) and inside the frame; uniqueness is the caller's */
+        for (int64_t i = 0; i < n_pixels; ++i)
+            if (pixel_list[i] >= (uint32_t)((int64_t)W * H)) return -1;
+    job j;
+    memset(&j, 0, sizeof(j));
+    j.rc.s = s; j.rc.env = env; j.rc.max_depth = max_depth; j.rc.use_bvh = use_bvh;
+    j.cam = cam; j.W = W; j.H = H; j.max_samples = n_samples;
+    j.pixel_list = pixel_list;
+    j.n_pixels = pixel_list ? n_pixels : (int64_t)W * H;
+    j.acc_rng = rng; j.acc_sum = sum; j.acc_first = first != 0;
+    run_job(&j, n_threads, counters);
     return 0;
 }
 

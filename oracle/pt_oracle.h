@@ -97,13 +97,24 @@ int orc_intersect_n(const orc_scene* s, const float* rays, int64_t n, float tmin
  * Render (ray_gen, device.cu:220-254).  out_rgb: W*H*3 floats, already row-flipped like the
  * reference framebuffer (index x + W*(H-1-y)); out_rgba8 optional (owl::make_rgba).
  * pixel_list (optional): launch-index pixels id = x + W*y to render; others are left untouched.
- * spp_begin/spp_count allow resuming: rng_state/accum (W*H u32 / W*H*3 float, launch-index order)
- * carry the per-pixel stream between chunks when non-NULL.
+ * A pixel is "accumulate n samples from the seed, then scale by 1.0f / n": the sample loop has one copy, orc_accumulate's.
  */
 int orc_render(const orc_scene* s, const orc_camera* cam, const orc_env* env, int W, int H,
                int max_samples, int max_depth, int use_bvh, int n_threads,
                const uint32_t* pixel_list, int64_t n_pixels,
                float* out_rgb, uint32_t* out_rgba8, orc_counters* counters);
+
+/*
+ * Continue pixels: for every listed launch id x + W*y (all W*H when pixel_list is NULL; ids are distinct) n_samples more iterations of
+ * ray_gen's sample loop, from rng[id] and sum[3*id ..] - or from orc_rng_init(x, y) and 0 when `first` is set - under the scene's
+ * present materials and triangle test.  rng (W*H u32) and sum (W*H*3 floats), both in launch order, are updated in place; pixels that
+ * are not listed keep theirs.  No division, no framebuffer: sum * (1.0f / N) after N samples in all is orc_render's pixel at N.
+ * Threaded like orc_render.  Returns -1 for NULL arrays, sizes or counts <= 0, or an id outside the frame.
+ */
+int orc_accumulate(const orc_scene* s, const orc_camera* cam, const orc_env* env, int W, int H,
+                   int n_samples, int max_depth, int use_bvh, int n_threads,
+                   const uint32_t* pixel_list, int64_t n_pixels, int first,
+                   uint32_t* rng, float* sum, orc_counters* counters);
 
 /* Per-pixel trace for debugging parity: per-sample radiance (max_samples*3) and rng state after each sample. */
 int orc_trace_pixel(const orc_scene* s, const orc_camera* cam, const orc_env* env, int W, int H, int px, int py,

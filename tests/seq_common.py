@@ -48,6 +48,17 @@ before the first step.  A filter in place leaves its result in the frame it read
 buffer no call was to write (the RGBA8 image beside guide buffers or beside a filter without one, everything handed to a refused call)
 must still hold its fill pattern at the end.  After every blocking call of the family pt_get_stats' launches are the header's: 1, L + 2,
 the launch sequences of pt_debug_plan_batch under the current "batch_frames", and sequences * (L + 2).
+
+THE THIRD FAMILY.  draw_accum_sequence(seed) (seeds from ASEED0) draws 10 to 16 steps around the fifteen entry points of the progressive
+accumulation - pt_accum_begin / add / read / variance / denoise / reproject / end, pt_denoise_var, pt_upsample and their _device forms - in
+the middle of a context's life: three accumulations (small, large, small), adds after a scene change or a scheduler knob, selecting adds,
+reprojects with guides of the step before, [add, guides, accum_denoise, upsample] blocking or asynchronous on one stream, calls of the
+other two families in between, refused calls; its docstring lists the blocks.  The accumulation is stateful, so its model is not a
+function of (state, step): tests/accum_seq_common.py keeps it (AccumModel: the oracle continues every active pixel from its stored stream -
+oracle.Scene.accumulate - in the state current at that add; accum_ref, accum_reproject_ref, denoise_var_ref, upsample_ref do the rest),
+and run() hands the family's steps to its SeqRunner: blocking steps are compared at once with pt_debug_accum_state, pt_accum_read and
+pt_accum_info_get, asynchronous ones after the one pt_synchronize together with the final state; on a host-only context every step of the
+model is held through the library's CPU twins instead.
 """
 import ctypes as C
 import time
@@ -94,6 +105,22 @@ GUIDE_LOOKS_AT = ("update_vertices", "set_materials", "set_environment", "set_pi
 BETWEEN = ("render_aov_follow", "render_aov_batch", "denoise", "denoise_batch")
 SIGMAS = dict(sigma_color=(1.0, 4.0, 16.0), sigma_normal=(0.1, 0.25, 1.0), sigma_depth=(0.05, 0.1, 0.5), sigma_albedo=(0.1, 0.2, 1.0))
 CHANGES = ("update_vertices", "set_materials", "set_environment", "set_pixel_shard", "watertight", "upload")  # the kinds whose effect must show
+# the third family
+ASEED0 = 20271020
+ACCUM_OPS = ("accum_begin", "accum_add", "accum_add_device", "accum_read", "accum_variance", "accum_denoise", "accum_denoise_device", "accum_reproject", "accum_reproject_device",
+             "accum_end", "denoise_var", "denoise_var_device", "upsample", "upsample_device")
+ACCUM_ASYNC = ("accum_add_device", "accum_denoise_device", "accum_reproject_device", "denoise_var_device", "upsample_device")
+BLOCKING_OF_ACCUM = {d: d[:-7] for d in ACCUM_ASYNC}
+ACCUM_SPP = (1, 5, 8, 16, 40, 64)
+# oracle samples per add (GUIDE_SAMPLE_BUDGET's figure).  MEASURED with it: 0.15 to 0.5 s per default seed for the whole host-only test on the CPU
+# (tests/test_sequences_host.py), of which 0.03 to 0.3 s are the oracle's and the restatements'; 0.06 to 0.19 s of oracle per seed in the GPU test
+# (profiles/r20_accum_sequences.json), against 0.055 to 0.184 s for the second family's seeds in profiles/r18_guide_sequences.json
+ACCUM_BUDGET = 50_000
+ACCUM_SMALL, ACCUM_LARGE = ((9, 17), (6, 11)), ((32, 41), (24, 31))  # 54..160 and 768..1200 pixels: a growth and a shrink of 4.8 x at least
+ACCUM_CHANGES = ("watertight", "update_vertices", "set_materials", "set_environment")
+ACCUM_REFUSED = ("accum_bad_params", "accum_after_shard", "accum_after_upload", "accum_no_accum")
+ACCUM_TAILS = (("read",), ("denoise_var", "end"), ("upsample", "variance"), (), ("variance",), ("other", "denoise_var_device"), ("end",), (), ("read",), ("denoise_var", "other"),
+               ("denoise_var_device", "variance"), ())
 # scheduler knobs of the fuzz (tests/test_gpu_fuzz.py PATHS): none may change an image, so the model ignores them
 KNOB_KEYS = {"groups", "whole", "express_permille", "schedule", "chunk_spp", "fallback", "slots_per_wave", "blocks_per_cu", "prepass_spp", "cost_radius", "spp_per_launch",
              "chunk_tail_min", "sticky_pct", "ns_express", "tune0", "adaptive"}
@@ -847,6 +874,207 @@ class _GuideGen(_Gen):
         self.render()  # a change is looked at right away, mostly by a guide pass
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# the third family: one accumulation in the middle of a context's life
+# ---------------------------------------------------------------------------------------------------------------------
+def default_accum_seeds(n=N_DEFAULT):
+    return [ASEED0 + i for i in range(n)]
+
+
+def draw_accum_sequence(seed, host_only=False):
+    """10 to 16 steps around pt_accum_begin / add / read / variance / denoise / reproject / end, pt_denoise_var and pt_upsample (blocking and
+    _device forms), on the room of _draw_upload(guide=True).  Every sequence has three accumulations - small, large, small: a growth and a
+    shrink of more than 4 x in pixels - and what else it is for goes by j = seed - ASEED0, so that any twelve seeds in a row have all of it:
+        [begin small, add]
+        [change, add]                  change = ACCUM_CHANGES[j % 4]: watertight (the switch brings its follow pass), update_vertices,
+                                       set_materials, set_environment; samples see the state current at their add
+        [begin large over the live accumulation, add] and a second add where a selecting add follows
+        j % 4:  [knob, selecting add, accum_denoise] | [guides(new camera), reproject, add] |
+                [add, guides, accum_denoise, upsample], all blocking or all asynchronous on ONE of the three streams |
+                [guides, reproject with a cap, guides, reproject back without, selecting add]
+        [set_pixel_shard or (odd j) upload, refused add, begin small, add]; for j % 12 in (4, 11) [refused add (bad parameters), add, begin
+        small over the live accumulation, add] instead
+        ACCUM_TAILS[j % 12]: read, variance, denoise_var, upsample, [end, refused read], [a call of another family and size, add].
+    A selecting add takes the median of the model's finite positive noise as its threshold (the model computes it when its turn comes: the
+    call list says "median"; 1.0 where no pixel has finite noise).  Add sizes come from ACCUM_SPP, stepped down until the add fits ACCUM_BUDGET."""
+    rng = np.random.default_rng(seed)
+    up = _draw_upload(rng, guide=True)
+    G = _AccumGen(rng, seed, up)
+    j = seed - ASEED0
+    G.begin(small=True)
+    G.accum_add()
+    G.change_add(ACCUM_CHANGES[j % 4])
+    G.begin(small=False)
+    G.accum_add()
+    if j % 4 == 0:
+        G.accum_add()
+        G.add(dict(op="knob", options=G.knobs[int(rng.integers(0, len(G.knobs)))]))
+        G.accum_add(select=True)
+        G.accum_denoise(dev=bool(j % 8))
+    elif j % 4 == 1:
+        G.reproject(cap=0, dev=bool((j // 4) % 2))
+        G.accum_add()
+    elif j % 4 == 2:
+        G.chain(dev=(j % 8 == 2))
+    else:
+        G.accum_add()
+        G.reproject(cap=16, dev=False)
+        G.reproject(cap=0, dev=True, back=True)
+        G.accum_add(select=True)
+    if j % 12 in (4, 11):
+        G.refused("accum_bad_params")
+        G.accum_add()
+    elif j % 2:
+        G.k = 0
+        G.add(_draw_upload(rng, guide=True))
+        G.refused("accum_after_upload")
+    else:
+        G.add(dict(op="set_pixel_shard", shard=(int(rng.integers(0, 2)), int(rng.integers(2, 4)), int(rng.choice([1, 8, 16])))))
+        G.refused("accum_after_shard")
+    G.begin(small=True)
+    G.accum_add()
+    for t in ACCUM_TAILS[j % 12]:
+        if t in ("read", "variance"):
+            G.add(dict(op="accum_" + t))
+        elif t.startswith("denoise_var"):
+            G.denoise_var(dev=t.endswith("_device"))
+        elif t.startswith("upsample"):
+            G.upsample(dev=t.endswith("_device"), stream=G.stream() if t.endswith("_device") else None)
+        elif t == "end":
+            G.add(dict(op="accum_end"))
+            G.live = None
+            G.refused("accum_no_accum")
+        else:
+            assert t == "other", t
+            G.other()
+            G.accum_add()
+    assert 10 <= len(G.steps) <= 16, len(G.steps)
+    return dict(seed=seed, family="accum", host_only=bool(host_only), upload=up, steps=G.steps)
+
+
+class _AccumGen(_GuideGen):
+    def __init__(self, rng, seed, up):
+        _GuideGen.__init__(self, rng, seed, up)
+        self.live = None  # dict(view, W, H, adds) of the accumulation the context holds
+
+    def add(self, step):
+        _Gen.add(self, step)  # (nothing is ever pending here: _GuideGen.set_wt puts no extra pass in front of the switch)
+
+    def begin(self, small):
+        rng = self.rng
+        (w0, w1), (h0, h1) = ACCUM_SMALL if small else ACCUM_LARGE
+        W, H = int(rng.integers(w0, w1)), int(rng.integers(h0, h1))
+        view = _draw_camera(rng, self.st)
+        self.add(dict(op="accum_begin", cam=view, W=W, H=H, depth=int(rng.choice(DEPTHS[1:])), over_live=self.live is not None))
+        self.live = dict(view=view, W=W, H=H, adds=0)
+
+    def accum_add(self, select=False, form=None):
+        rng, a = self.rng, self.live
+        i = int(rng.integers(0, len(ACCUM_SPP)))
+        while i > 0 and a["W"] * a["H"] * ACCUM_SPP[i] > ACCUM_BUDGET:
+            i -= 1
+        dev, stream = form or self.form()
+        cap = int(rng.choice([0, 0, 0, 100]))
+        self.add(dict(op="accum_add_device" if dev else "accum_add", n=ACCUM_SPP[i], cap=cap, select=bool(select), W=a["W"], H=a["H"], stream=stream,
+                      want=bool(rng.random() < 0.7) if dev else True))
+        a["adds"] += 1
+
+    def change_add(self, kind):
+        if kind == "set_materials":
+            self.add(dict(op="set_materials", mats=_draw_mats(self.rng, self.st["mats"], guide=True)))
+        else:
+            self.change(kind)  # (the watertight switch brings its follow pass)
+        self.accum_add()
+
+    def other(self):
+        """A call of the first or the second family at a size of its own between two adds."""
+        if self.rng.random() < 0.5:
+            self.frame(*self.any_size())
+        else:
+            self.follow()
+
+    def refused(self, what):
+        dev, stream = self.form()
+        self.add(dict(op="refused", what=what, dev=dev, stream=stream, W=16, H=12))
+
+    def _aov(self, view):
+        a = self.live
+        return dict(op="render_aov", cam=view, W=a["W"], H=a["H"], n=1, stream=None)
+
+    def _follow(self, view, W, H):
+        return dict(op="render_aov_follow", cam=view, W=W, H=H, stream=None, **self.follow_params(W, H))
+
+    def reproject(self, cap, dev, back=False):
+        """[guides under the new camera, reproject]: the call gets the buffer the guide pass filled (its host copy in the blocking form) and
+        the model's guides under the old camera."""
+        rng, a = self.rng, self.live
+        old = a["view"]
+        a.setdefault("first_view", old)
+        new = a["first_view"] if back else _orbit(old, float(rng.choice([-25.0, -15.0, 15.0, 25.0])))
+        stream = self.stream() if dev else None
+        self.add(dict(self._aov(new), op="render_aov_device" if dev else "render_aov", stream=stream))
+        self.add(dict(op="accum_reproject_device" if dev else "accum_reproject", cam=new, W=a["W"], H=a["H"], cap=cap, stream=stream, prev=self._aov(old), cur=self.steps[-1]))
+        a["view"] = new
+
+    def accum_denoise(self, dev, guides=None, chain=False, stream=None):
+        a = self.live
+        stream = stream if chain else (self.stream() if dev else None)
+        self.add(dict(op="accum_denoise_device" if dev else "accum_denoise", W=a["W"], H=a["H"], params=self.filter_params(a["W"] * a["H"]), want_rgba8=bool(self.rng.random() < 0.5),
+                      stream=stream, chain=bool(chain), guides=guides or self._follow(a["view"], a["W"], a["H"])))
+
+    def chain(self, dev):
+        """[add, follow guides, accum_denoise, upsample to 2 x]: all blocking, or all asynchronous on one stream with nothing in between - the
+        filter reads the caller buffer the guide pass fills, the upsampling the filter's frame and the same guides."""
+        a = self.live
+        stream = self.stream() if dev else None
+        self.accum_add(form=(dev, stream))
+        self.add(dict(self._follow(a["view"], a["W"], a["H"]), op=FOLLOW_OPS[dev], stream=stream))
+        g = self.steps[-1]
+        self.accum_denoise(dev, guides=g, chain=True, stream=stream)
+        self.upsample(dev=dev, stream=stream, chain=True)
+
+    def upsample_params(self):
+        rng = self.rng
+        return dict(taps=int(rng.choice([2, 4])), flags=int(rng.integers(0, 2)), sigma_normal=float(rng.choice(SIGMAS["sigma_normal"])), sigma_depth=float(rng.choice(SIGMAS["sigma_depth"])),
+                    sigma_albedo=float(rng.choice(SIGMAS["sigma_albedo"])))
+
+    def upsample(self, dev=None, stream=None, chain=False):
+        """chain: the low frame is the accumulation's filtered frame of the step before, its guides those of the step before that; else a frame and
+        guides of the model's own at a small size.  The full size is 2 x the low one."""
+        rng = self.rng
+        if dev is None:
+            dev, stream = self.form()
+        if chain:
+            a = self.live
+            w, h, view = a["W"], a["H"], a["view"]
+            lo = (None, self.steps[-2])
+        else:
+            (w0, w1), (h0, h1) = ACCUM_SMALL
+            w, h, view = int(rng.integers(w0, w1)), int(rng.integers(h0, h1)), _draw_camera(rng, self.st)
+            spp, depth = self.spp(w, h, filtered=True)
+            lo = (dict(op="render", cam=view, W=w, H=h, spp=spp, depth=depth, stream=None), self._follow(view, w, h))
+        self.add(dict(op="upsample_device" if dev else "upsample", w=w, h=h, W=2 * w, H=2 * h, params=self.upsample_params(), want_rgba8=bool(rng.random() < 0.5), stream=stream,
+                      chain=bool(chain), src=dict(render=lo[0], guides=lo[1], guides_hi=dict(lo[1], op="render_aov_follow", W=2 * w, H=2 * h, stream=None))))
+
+    def denoise_var(self, dev):
+        """pt_denoise_var of a frame, a variance map and guides that no call of the sequence made (the model's own)."""
+        rng = self.rng
+        stream = self.stream() if dev else None
+        (w0, w1), (h0, h1) = ACCUM_SMALL if rng.random() < 0.5 else ACCUM_LARGE
+        W, H, view = int(rng.integers(w0, w1)), int(rng.integers(h0, h1)), _draw_camera(rng, self.st)
+        spp, depth = self.spp(W, H, filtered=True)
+        self.add(dict(op="denoise_var_device" if dev else "denoise_var", W=W, H=H, params=self.filter_params(W * H), want_rgba8=bool(rng.random() < 0.5), stream=stream, var_seed=int(rng.integers(0, 1 << 30)),
+                      src=dict(render=dict(op="render", cam=view, W=W, H=H, spp=spp, depth=depth, stream=None), guides=self._follow(view, W, H))))
+
+
+def _orbit(view, deg):
+    """The view after an orbit of `deg` degrees about the vertical through look_at."""
+    frm, at, up, fov = view
+    c, s = np.cos(np.radians(deg)), np.sin(np.radians(deg))
+    x, y, z = (np.asarray(frm, np.float64) - np.asarray(at, np.float64))
+    return [float(at[0] + c * x + s * z), float(at[1] + y), float(at[2] - s * x + c * z)], [float(v) for v in at], list(up), fov
+
+
 def kind_of(step):
     """The kind of change a step is, one of CHANGES, or None."""
     if step["op"] in ("update_vertices", "set_materials", "set_environment", "set_pixel_shard", "upload"):
@@ -871,6 +1099,25 @@ def describe(step):
         return "set_option %s=%d" % (step["key"], step["value"])
     if op == "knob":
         return "set_option " + " ".join("%s=%d" % kv for kv in step["options"])
+    if op in ACCUM_OPS:
+        s = op
+        if op == "accum_begin":
+            s += " %dx%d depth %d%s" % (step["W"], step["H"], step["depth"], " over a live accumulation" if step["over_live"] else "")
+        elif op in ("accum_add", "accum_add_device"):
+            s += " %d samples%s%s%s" % (step["n"], ", cap %d" % step["cap"] if step["cap"] else "", ", threshold = the median noise" if step["select"] else "", "" if step["want"] else ", no frame")
+        elif op in ("accum_reproject", "accum_reproject_device"):
+            s += " max_history %d, guides of the step before" % step["cap"]
+        elif op in ("accum_denoise", "accum_denoise_device", "denoise_var", "denoise_var_device"):
+            p = step["params"]
+            s += " %dx%d L=%d flags=%d sigmas %g %g %g %g%s, guides %s" % (step["W"], step["H"], p["iterations"], p["flags"], p["sigma_color"], p["sigma_normal"], p["sigma_depth"], p["sigma_albedo"],
+                                                                        ", RGBA8" if step["want_rgba8"] else "", "of the step before" if step.get("chain") else "[%s]" % describe(step.get("guides") or step["src"]["guides"]))
+        elif op in ("upsample", "upsample_device"):
+            p = step["params"]
+            s += " %dx%d -> %dx%d taps=%d flags=%d sigmas %g %g %g%s of %s" % (step["w"], step["h"], step["W"], step["H"], p["taps"], p["flags"], p["sigma_normal"], p["sigma_depth"], p["sigma_albedo"],
+                                                                            ", RGBA8" if step["want_rgba8"] else "", "the two steps before" if step["chain"] else "[%s]" % describe(step["src"]["render"]))
+        if op in ACCUM_ASYNC:
+            s += " on %s" % _stream_name(step["stream"])
+        return s
     if op == "refused":
         return "refused: " + step["what"] + ("" if "dev" not in step else " (blocking)" if not step["dev"] else " (_device on %s)" % _stream_name(step["stream"]))
     if op in OBSERVING:
@@ -1259,6 +1506,7 @@ def run(ctx, seq, model, upto=None, A=None, diagnose=True, log=None):
     bufs, pending, got_all, outs = {}, [], [], {}
     t_gpu = 0.0
     poison = np.uint32(0xA5A5A5A5)
+    acc = None
 
     def check(i, st, got, want):
         bad = same(got[0], want[0])
@@ -1279,13 +1527,19 @@ def run(ctx, seq, model, upto=None, A=None, diagnose=True, log=None):
         states = states_of(dict(seq, steps=steps))
         if not host:  # every caller buffer before anything is enqueued: an allocation or its fill may wait for the device
             for i, s in enumerate(steps):
-                if (s["op"] in ASYNC_OPS and not (s["op"] in FILTER_OPS and s["in_place"])) or (s["op"] == "refused" and s.get("dev")):  # (in place: the frame it reads)
+                if (s["op"] in ASYNC_OPS and not (s["op"] in FILTER_OPS and s["in_place"])) or (s["op"] == "refused" and s.get("dev") and s["what"] not in ACCUM_REFUSED):  # (in place: the frame it reads)
                     bufs[i] = _device_frame(A, s)
                 if s["op"] in ASYNC_OPS and s["op"] in FILTER_OPS and not s["chain"]:  # a filter of the model's own frame and guides: in HBM before the first step
                     rgb, aov = model.inputs(states[i], s)
                     bufs[i, "rgb"], bufs[i, "aov"] = A.DeviceFrame(s["W"], s["H"], frames=s["K"]), A.DeviceFrame(s["W"], s["H"], frames=s["K"], floats=8)
                     A.to_device(bufs[i, "rgb"].rgb, rgb)
                     A.to_device(bufs[i, "aov"].rgb, aov)
+        if seq.get("family") == "accum":  # the third family's steps: tests/accum_seq_common.py (imported here: it builds on this module)
+            import accum_seq_common
+
+            acc = accum_seq_common.SeqRunner(ctx, model, A, host, seq, steps, states, bufs, where)
+            if not host:
+                acc.prepare()
         st = states[0]
         t0 = time.time()
         upload(ctx, st, seq["upload"])
@@ -1321,6 +1575,10 @@ def run(ctx, seq, model, upto=None, A=None, diagnose=True, log=None):
             elif op == "knob":
                 for k, v in s["options"]:
                     ctx.set_option(k, v)
+            elif op in ACCUM_OPS or (op == "refused" and s["what"] in ACCUM_REFUSED):
+                t_gpu += time.time() - t0
+                acc.step(i)
+                t0 = time.time()
             elif op == "refused":
                 refused_call(ctx, st, s, host, bufs.get(i), A.stream(s["stream"]) if (not host and s.get("stream") is not None) else None)
             elif host:
@@ -1350,7 +1608,7 @@ def run(ctx, seq, model, upto=None, A=None, diagnose=True, log=None):
                 assert launches is None or launches == expected_launches(st, s), "%s: pt_get_stats counts %d launches, the header says %d" % (where(i), launches, expected_launches(st, s))
                 t0 = time.time()
             t_gpu += time.time() - t0
-        if pending:
+        if pending or (acc is not None and acc.pending):
             t0 = time.time()
             ctx.synchronize()  # the one wait of the sequence: everything before it was ordered by the library
             t_gpu += time.time() - t0
@@ -1372,13 +1630,16 @@ def run(ctx, seq, model, upto=None, A=None, diagnose=True, log=None):
                 if s["op"] == "refused" and i in bufs:
                     rgb, rgba8 = bufs[i].read()
                     assert (rgb.view(np.uint32) == poison).all() and (rgba8 == poison).all(), "%s: the refused call wrote to the caller's buffers" % where(i)
+        if acc is not None:
+            acc.finish()
+            t_gpu += acc.seconds
     finally:
         if not host:
             try:
-                if pending:
+                if pending or (acc is not None and acc.pending):
                     ctx.synchronize()
             finally:
-                for f in bufs.values():
+                for f in list(bufs.values()) + (acc.frames() if acc is not None else []):
                     f.free()
                 A.destroy_streams()
     run.seconds = t_gpu

@@ -14,7 +14,13 @@ filter chained over caller buffers on three streams with nothing in between, the
 tables in front of the context's, the batch cut changed, refused calls that must leave the caller's buffers alone - against
 tests/aov_follow_ref.py and tests/denoise_ref.py on the oracle's frames, bit for bit, and pt_get_stats' launches after every blocking call.
 
-12 seeds by default per family; PT_SEQ_CASES=N for more, PT_SEQ_ONLY=seed for one of either family (tools/seq_replay.py prints and replays
+test_accum_sequence is the third family (seq_common.draw_accum_sequence, 10 to 16 calls; model: tests/accum_seq_common.py): three
+accumulations of growing and shrinking size in the middle of a context's life - adds after scene changes and scheduler knobs, selecting
+adds, reprojects, the filter and the upsampling chained on one stream, pt_denoise_var and pt_upsample of the model's own inputs, calls of the
+other families in between, refused calls - every blocking step compared at once with state, read-back and info, the asynchronous ones and
+the final state after the one pt_synchronize.  PT_WRITE_PROFILES=1 records its call lists and seconds in profiles/r20_accum_sequences.json.
+
+12 seeds by default per family; PT_SEQ_CASES=N for more, PT_SEQ_ONLY=seed for one of any family (tools/seq_replay.py prints and replays
 a seed).  One more test runs sequences over pt_group_* (two contexts on one card, the stub collective, a child process) with option
 "watertight" = 1 and compares the group's frames and guide buffers with a single context's, which run() holds to the oracle: two of the
 first family, and one of the second, whose follow passes are the group's and whose filter runs on rank 0's context.
@@ -43,8 +49,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ONLY = os.environ.get("PT_SEQ_ONLY")
 N_CASES = int(os.environ.get("PT_SEQ_CASES", str(SC.N_DEFAULT)))
 SEEDS = [s for s in [int(ONLY)] if s < SC.GSEED0] if ONLY else SC.default_seeds(N_CASES)
-GUIDE_SEEDS = [s for s in [int(ONLY)] if s >= SC.GSEED0] if ONLY else SC.default_guide_seeds(N_CASES)
-_report, _guide_report = {}, {}
+GUIDE_SEEDS = [s for s in [int(ONLY)] if SC.GSEED0 <= s < SC.ASEED0] if ONLY else SC.default_guide_seeds(N_CASES)
+ACCUM_SEEDS = [s for s in [int(ONLY)] if s >= SC.ASEED0] if ONLY else SC.default_accum_seeds(N_CASES)
+_report, _guide_report, _accum_report = {}, {}, {}
 
 
 @pytest.fixture(scope="module")
@@ -60,6 +67,11 @@ def model(orc):
         with open(os.path.join(ROOT, "profiles", "r18_guide_sequences.json"), "w") as f:
             json.dump(dict(seed0=SC.GSEED0, sequences=_guide_report, first_family_seconds_of_this_run=first, slowest_first_family_test=max([v["seconds_test"] for v in first.values()] or [0]),
                            slowest_guide_test=max(v["seconds_test"] for v in _guide_report.values())), f, indent=1, sort_keys=True)
+
+
+    if os.environ.get("PT_WRITE_PROFILES") == "1" and _accum_report:
+        with open(os.path.join(ROOT, "profiles", "r20_accum_sequences.json"), "w") as f:
+            json.dump(dict(seed0=SC.ASEED0, accum_budget=SC.ACCUM_BUDGET, sequences=_accum_report, slowest_accum_test=max(v["seconds_test"] for v in _accum_report.values())), f, indent=1, sort_keys=True)
 
 
 def _only_with(seeds):
@@ -102,6 +114,26 @@ def test_guide_sequence(model, seed):
     _guide_report[str(seed)] = dict(calls=["upload: " + SC.describe(seq["upload"])] + [SC.describe(s) for s in seq["steps"]], builder=seq["upload"]["builder"],
                                     seconds_library=round(SC.run.seconds, 3), seconds_oracle=round(model.seconds - o0, 3), seconds_test=round(time.time() - t0, 3))
     print("guide seed %d: %d steps, %.2f s in the library, %.2f s in the oracle" % (seed, len(seq["steps"]), SC.run.seconds, model.seconds - o0))
+
+
+@_only_with(ACCUM_SEEDS)
+def test_accum_sequence(model, seed):
+    import accum_seq_common as AQ
+
+    seq = SC.draw_accum_sequence(seed)
+    ctx = B.Context(0)
+    t0, o0 = time.time(), model.seconds + AQ.oracle_seconds[0]
+    try:
+        SC.run(ctx, seq, model, A=A)
+    finally:
+        try:
+            ctx.close()
+        finally:
+            A.destroy_streams()
+    oracle = model.seconds + AQ.oracle_seconds[0] - o0
+    _accum_report[str(seed)] = dict(calls=["upload: " + SC.describe(seq["upload"])] + [SC.describe(s) for s in seq["steps"]], builder=seq["upload"]["builder"],
+                                    seconds_library=round(SC.run.seconds, 3), seconds_oracle=round(oracle, 3), seconds_test=round(time.time() - t0, 3))
+    print("accum seed %d: %d steps, %.2f s in the library, %.2f s in the oracle" % (seed, len(seq["steps"]), SC.run.seconds, oracle))
 
 
 def _group_seeds():

@@ -20,6 +20,14 @@
    tests/denoise_ref.py, refused calls through the twins, PT_E_NO_DEVICE for valid calls of the batch forms and PT_E_INVALID for invalid
    ones; what its twelve default seeds contain; and that their changes show, the follow kernels have something to follow and the
    filters change their frames.
+6. the third family (seq_common.draw_accum_sequence: one accumulation in the middle of a context's life; model and runner part in
+   tests/accum_seq_common.py): on a host-only context every step of the model is held through the library's CPU twins applied to the
+   model's arrays before the step; what its twelve default seeds contain (every entry point twice, all three streams, every kind of change
+   followed by an add, a selecting add after a knob, reprojects with and without a cap and two in one accumulation, a blocking and an
+   all-asynchronous chain, both sides of the sort threshold, every refusal, a begin over a live accumulation, growth and shrink); with the
+   oracle alone, that at least 9 in 10 changes alter the sums of the next add, every kind at least twice, and that at most 1 in 10
+   reprojects keeps all or none of its pixels; and the pinned call lists of the second and third family
+   (tests/golden/guide_sequence_call_lists.json, accum_sequence_call_lists.json).
 """
 import json
 import os
@@ -27,6 +35,7 @@ import os
 import numpy as np
 import pytest
 
+import accum_seq_common as AQ
 import seq_common as SC
 from owl_path_tracer_amd.pyhost import binding as B
 
@@ -160,3 +169,77 @@ def test_guide_changes_are_visible_and_the_guides_have_something_to_follow(model
     assert 3 * follow[1] >= follow[0], follow
     assert all(share >= 0.5 for _, _, share in filters), [f for f in filters if f[2] < 0.5]
     assert 10 * len(flat) <= frames, flat
+
+
+# ---- the third family: one accumulation in the middle of a context's life (seq_common.draw_accum_sequence, tests/accum_seq_common.py) ----
+ACCUM_SEEDS = SC.default_accum_seeds()
+
+
+def _pinned(name):
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", name)) as f:
+        return json.load(f)
+
+
+@pytest.mark.parametrize("seed", ACCUM_SEEDS)
+def test_accum_sequence_on_a_host_only_context(model, seed):
+    """Every step of the model is held through the library's CPU twins applied to the model's arrays before the step (select, resolve,
+    reproject, variance, denoise_var, upsample); valid pt_accum_begin and pt_accum_reproject calls answer PT_E_NO_DEVICE, and - no
+    accumulation can exist there - an add answers PT_E_INVALID, as the header says of an add without a begin."""
+    seq = SC.draw_accum_sequence(seed, host_only=True)
+    assert [SC.describe(s) for s in seq["steps"]] == [SC.describe(s) for s in SC.draw_accum_sequence(seed)["steps"]], "host_only does not change a draw"
+    ctx = B.Context(-1)
+    try:
+        SC.run(ctx, seq, model)
+    finally:
+        ctx.close()
+
+
+def test_the_default_accum_sequences_cover_what_they_are_for():
+    seqs = [SC.draw_accum_sequence(s) for s in ACCUM_SEEDS]
+    assert len(seqs) == 12 and not set(ACCUM_SEEDS) & (set(SEEDS) | set(GUIDE_SEEDS))
+    for seq in seqs:
+        assert 10 <= len(seq["steps"]) <= 16, seq["seed"]
+        for s in seq["steps"]:
+            if s["op"] == "accum_begin":
+                assert 9 <= s["W"] <= 40 and 6 <= s["H"] <= 30, SC.describe(s)
+            if s["op"] in ("accum_add", "accum_add_device"):
+                assert s["n"] in SC.ACCUM_SPP and s["W"] * s["H"] * s["n"] <= max(SC.ACCUM_BUDGET, s["W"] * s["H"]), SC.describe(s)
+    c = AQ.coverage(seqs)
+    print(c)
+    assert all(v >= 2 for v in c["ops"].values()), c["ops"]
+    assert c["streams"] == {None, 0, 1}
+    assert all(v >= 2 for v in c["change_then_add"].values()), c["change_then_add"]
+    assert c["knob_then_selecting_add"] >= 2 and c["selecting"] >= 4
+    assert 0 in c["caps"] and any(cap >= 2 for cap in c["caps"])
+    assert c["reprojects_in_one"] >= 2
+    assert c["async_chains"] >= 1 and c["blocking_chains"] >= 1
+    assert {5, 8, 16} & c["add_sizes"] and {40, 64} <= c["add_sizes"], "both sides of the sort threshold (4 x prepass_spp = 32 or 64)"
+    assert c["refused"] == set(SC.ACCUM_REFUSED)
+    assert c["begin_over_live"] >= len(seqs)
+    assert c["growth_and_shrink"] == len(seqs), "every sequence has a growth and a shrink of 4 x in the accumulation's pixels"
+    assert c["between"] >= 2, "calls of the other families between two adds"
+
+
+def test_accum_changes_are_visible_and_reprojects_keep_a_part(model):
+    shown, hidden, shares = {k: 0 for k in SC.ACCUM_CHANGES}, [], []
+    for seed in ACCUM_SEEDS:
+        sh, hi, sr = AQ.visibility(SC.draw_accum_sequence(seed), model)
+        for k, v in sh.items():
+            shown[k] += v
+        hidden += [(seed,) + h for h in hi]
+        shares += [(seed,) + s for s in sr]
+    n = sum(shown.values()) + len(hidden)
+    print("visible changes: %d of %d %r; hidden: %r; history kept by the reprojects: %r" % (sum(shown.values()), n, shown, hidden, [(s, i, round(v, 3)) for s, i, v in shares]))
+    assert 10 * sum(shown.values()) >= 9 * n, hidden
+    assert all(v >= 2 for v in shown.values()), shown
+    trivial = [s for s in shares if s[2] in (0.0, 1.0)]
+    assert len(shares) >= 6 and 10 * len(trivial) <= len(shares), trivial
+
+
+def test_the_accum_and_guide_draws_are_the_pinned_ones():
+    for name, seed0, seeds, draw in (("accum_sequence_call_lists.json", SC.ASEED0, ACCUM_SEEDS, SC.draw_accum_sequence), ("guide_sequence_call_lists.json", SC.GSEED0, GUIDE_SEEDS, SC.draw_guide_sequence)):
+        pinned = _pinned(name)
+        assert pinned["seed0"] == seed0 and sorted(pinned["call_lists"]) == sorted(str(s) for s in seeds)
+        for seed in seeds:
+            seq = draw(seed)
+            assert ["upload: " + SC.describe(seq["upload"])] + [SC.describe(s) for s in seq["steps"]] == pinned["call_lists"][str(seed)], (name, seed)

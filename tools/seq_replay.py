@@ -1,5 +1,6 @@
 """Print a seed's call sequence (tests/seq_common.py), and run it: `python tools/seq_replay.py <seed> [--run [K]] [--host]`.  A seed from
-seq_common.GSEED0 on is one of the second family (follow guides, batch guides, the denoiser).
+seq_common.GSEED0 on is one of the second family (follow guides, batch guides, the denoiser), a seed from seq_common.ASEED0 on one of the
+third (an accumulation in the middle of a context's life; model: tests/accum_seq_common.py).
 
 Without --run: the upload and the steps in words (no GPU needed).  --run: the first K steps (all without K) on a fresh context with the
 runner of tests/test_gpu_sequences.py, every observation compared with the oracle, each step printed as it starts; a difference ends
@@ -20,8 +21,9 @@ from owl_path_tracer_amd.pyhost import binding as B
 args = sys.argv[1:]
 seed = int(args[0])
 host = "--host" in args
-seq = (SC.draw_guide_sequence if seed >= SC.GSEED0 else SC.draw_sequence)(seed, host_only=host)
-print("%ssequence seed=%d: %d steps" % ("guide " if seed >= SC.GSEED0 else "", seed, len(seq["steps"])))
+family = "accum " if seed >= SC.ASEED0 else "guide " if seed >= SC.GSEED0 else ""
+seq = {"accum ": SC.draw_accum_sequence, "guide ": SC.draw_guide_sequence, "": SC.draw_sequence}[family](seed, host_only=host)
+print("%ssequence seed=%d: %d steps" % (family, seed, len(seq["steps"])))
 print(SC.call_list(seq))
 if "--run" in args:
     k = args.index("--run")
