@@ -170,7 +170,7 @@ int pt_render(pt_ctx* ctx, const pt_camera* cam, int32_t width, int32_t height, 
  * every call that touches what a frame in flight uses is ordered after the context's LAST ASYNCHRONOUS CALL, whichever stream that
  * call was given.  So any call of this header may follow a pt_*_device call at once, with no pt_synchronize between them.
  *   - The asynchronous calls (pt_render_device, pt_render_batch_device, pt_render_aov_device, pt_render_aov_follow_device, pt_render_aov_batch_device, pt_denoise_device,
- *     pt_denoise_batch_device, pt_denoise_var_device, pt_accum_add_device, pt_accum_denoise_device, pt_accum_reproject_device, pt_upsample_device, pt_reduce_framebuffer) wait ON THE
+ *     pt_denoise_batch_device, pt_denoise_var_device, pt_accum_add_device, pt_accum_denoise_device, pt_accum_reproject_device, pt_upsample_device, pt_trace_closest_device, pt_trace_occluded_device, pt_reduce_framebuffer) wait ON THE
  *     DEVICE: the stream they are given waits for an event recorded at the end of the previous asynchronous call - only if that call
  *     used another stream; on the same stream the stream's own order suffices and nothing is added.  The host returns at once, with
  *     two exceptions that existed before: a frame of another size, shard or batch length rewrites the pixel queue and a frame that
@@ -178,7 +178,7 @@ int pt_render(pt_ctx* ctx, const pt_camera* cam, int32_t width, int32_t height, 
  *     before) - both first wait on the host for the frame in flight; pt_render_batch_device and pt_render_aov_batch_device
  *     return when their per-frame tables have reached HBM, i.e. after whatever precedes them on `stream`; and a pt_accum_add_device that
  *     selects its pixels returns when the count of its active set has reached the host (see there).
- *   - The blocking renders (pt_render, pt_render_batch, pt_render_aov, pt_render_aov_follow, pt_render_aov_batch, pt_accum_add), pt_denoise, pt_denoise_batch, pt_denoise_var, pt_accum_denoise, pt_accum_reproject and pt_upsample run on the context's stream behind the same device-side wait
+ *   - The blocking renders (pt_render, pt_render_batch, pt_render_aov, pt_render_aov_follow, pt_render_aov_batch, pt_accum_add), pt_denoise, pt_denoise_batch, pt_denoise_var, pt_accum_denoise, pt_accum_reproject, pt_upsample, pt_trace_closest and pt_trace_occluded run on the context's stream behind the same device-side wait
  *     and return with the context idle.  After a blocking call, or on the context's own stream, they add no wait at all.
  *   - The calls that change or read what a frame uses WAIT ON THE HOST for the last asynchronous call's stream (if it is not the
  *     context's) and then for the context's: pt_set_materials, pt_set_environment, pt_update_vertices, pt_upload_scene,
@@ -193,7 +193,7 @@ int pt_render(pt_ctx* ctx, const pt_camera* cam, int32_t width, int32_t height, 
 int pt_render_device(pt_ctx* ctx, const pt_camera* cam, int32_t width, int32_t height, int32_t max_samples, int32_t max_path_depth,
                      void* d_out_rgb, void* d_out_rgba8, void* stream);
 /* Waits on the host for the context's last asynchronous call - pt_render_device, pt_render_batch_device, pt_render_aov_device,
- * pt_render_aov_follow_device, pt_render_aov_batch_device, pt_denoise_device, pt_denoise_batch_device, pt_denoise_var_device, pt_accum_add_device, pt_accum_denoise_device, pt_accum_reproject_device, pt_upsample_device or pt_reduce_framebuffer, on the stream it was given - and for the context's own stream.  Every earlier asynchronous call of the context
+ * pt_render_aov_follow_device, pt_render_aov_batch_device, pt_denoise_device, pt_denoise_batch_device, pt_denoise_var_device, pt_accum_add_device, pt_accum_denoise_device, pt_accum_reproject_device, pt_upsample_device, pt_trace_closest_device, pt_trace_occluded_device or pt_reduce_framebuffer, on the stream it was given - and for the context's own stream.  Every earlier asynchronous call of the context
  * is complete then as well, whatever stream it used: each was ordered before the next (see pt_render_device).  Returns PT_E_HIP if a
  * wave's watchdog fired during the last frame (the image is then incomplete); pt_get_stats reports the same.  PT_OK at once on an idle
  * or host-only context.  A caller's stream may be destroyed once this has returned. */
@@ -680,6 +680,52 @@ int pt_upsample_device(pt_ctx* ctx, const void* d_rgb_lo, const void* d_aov_lo, 
 int64_t pt_debug_upsample_host(pt_ctx* ctx, const float* rgb_lo, const float* aov_lo, int32_t w, int32_t h, const float* aov_hi, int32_t W, int32_t H,
                                const pt_upsample_params* p, float* out_rgb, uint32_t* out_rgba8);
 
+/* ---- ray queries: closest hit and occlusion for the CALLER'S rays (no reference counterpart: the reference traces only the rays its
+ * own ray_gen makes, and shoots no shadow rays) ----
+ * pt_trace_closest answers "what does this ray hit", pt_trace_occluded "does this ray hit anything before tmax" - picking, line of
+ * sight, ambient-occlusion and visibility guides, light baking, motion vectors.  Kernels of their own (csrc/pt_kernel_rays.hip,
+ * csrc/pt_kernel_rays_wt.hip) around the device functions of the render kernel; the CPU twin is pt_debug_trace_rays_host.
+ * DEFINITION, per ray (a pt_ray: 32 bytes; the kernel reads it as two 16-byte loads).
+ *   thi = tmax < 1e10f ? tmax : 1e10f: NaN and +infinity give the library's own bound.  The lower bound is the library's fixed 1e-3, as
+ *   everywhere.  Float 7 of the record (`unused`) is NOT READ: it leaves room for a per-ray lower bound later.  dir need not be
+ *   normalised, and t is in units of |dir|.  org and dir must be finite and dir non-zero (the domain of the probes below); the hit
+ *   domain is the one stated at "validation hooks": origins within 10 extents, no coplanar or grazing rays.
+ *   CLOSEST: over all triangles the active test accepts with 1e-3 < t <= thi, the one with minimum t, ties to the lower global
+ *   triangle id, slivers never; the active test is Moeller-Trumbore, or the watertight test under option "watertight" = 1.  This is
+ *   exactly pt_debug_closest_hit_host(org, dir, 1e-3, thi): that walk starts at t = thi, id = 0x7fffffff, so a hit at exactly thi is
+ *   taken.  out = {t, u, v, prim}, prim the global triangle id (entity order, then face order; pt_prim_to_mesh inverts it); a miss is
+ *   {+0, +0, +0, -1}.
+ *   OCCLUDED: out = 1 iff the closest set above is not empty, else 0 - a property of the scene, not of the walk, which stops at the first
+ *   triangle it accepts.
+ * The calls honour "watertight", "box_exact" (1: the subtracting slab form; 0 and the default -1: the fma form - there is no camera to
+ * measure, and the hit domain keeps origins within 10 extents, inside that form's reach of 42) and a scene moved by pt_update_vertices.
+ * They ignore the pixel shard, materials and environment.  With a communicator they issue no collective: every context traces its own
+ * rays.  They need quad nodes: a scene loaded with option "quad" = 0, or one whose tree is too deep for them, is refused with
+ * PT_E_INVALID by name.  They keep no render state: a pt_render after them is bit for bit the one before.  n == 0 is PT_OK with no launch.
+ * REFUSED with PT_E_INVALID, by name, before anything is touched: NULL rays or out with n > 0; n < 0 or n >= 2^31; a d_rays that is
+ * not 16-byte aligned (nor a d_out of pt_trace_closest_device: a hit is one 16-byte store).  PT_E_NO_SCENE without a scene.  On a
+ * host-only context valid arguments give PT_E_NO_DEVICE and invalid ones PT_E_INVALID; the twin works there.
+ * ORDERING: the _device forms (device pointers, `stream` NULL = the context's) join the asynchronous calls of the streams contract at
+ * pt_render_device and the list at pt_synchronize.  The blocking forms stage the rays, run on the context's stream behind the same
+ * device-side wait, and read back; the context is idle on return.
+ * THE WALK: a wave owns a contiguous range of rays (a multiple of 64: the caller's coherence stays inside a wave) and refills its idle
+ * lanes from it when no more than "rays_refill" lanes are still walking (pt_set_option); every walk is bounded like the probes', and
+ * pt_synchronize returns PT_E_HIP if one ran out of its step or stack bound (that ray is reported as a miss), as for the guide pass.
+ * pt_get_stats afterwards: kernel_ms and launches (1) are the ray launch's, and so are block, grid, vgprs, lds_bytes, stack_entries.
+ * NOT BUILT: no pt_main flag, no pt_group_* form, no batch form. */
+typedef struct pt_ray     { float org[3]; float tmax; float dir[3]; float unused; } pt_ray;     /* 32 bytes */
+typedef struct pt_ray_hit { float t, u, v; int32_t prim; } pt_ray_hit;                          /* 16 bytes */
+int pt_trace_closest        (pt_ctx* ctx, const pt_ray* rays, int64_t n, pt_ray_hit* out);
+int pt_trace_closest_device (pt_ctx* ctx, const void* d_rays, int64_t n, void* d_out /* n pt_ray_hit */, void* stream);
+int pt_trace_occluded       (pt_ctx* ctx, const pt_ray* rays, int64_t n, uint8_t* out);
+int pt_trace_occluded_device(pt_ctx* ctx, const void* d_rays, int64_t n, void* d_out /* n bytes */, void* stream);
+/* The CPU twin: the definition above run by the host walk of pt_debug_closest_hit_host_n on all host threads; works on a host-only
+ * context, follows "watertight" and pt_update_vertices.  occluded = 0: out is n pt_ray_hit; else n bytes.  Returns n. */
+int64_t pt_debug_trace_rays_host(pt_ctx* ctx, const pt_ray* rays, int64_t n, int32_t occluded, void* out);
+/* Host only: the mesh (entity of the upload) and the triangle inside it of a global triangle id, through the prefix sums of n_triangles
+ * of the upload.  PT_E_INVALID outside 0 .. n_triangles-1, PT_E_NO_SCENE without a scene. */
+int pt_prim_to_mesh(pt_ctx* ctx, int32_t prim, int32_t* mesh, int32_t* triangle);
+
 /* ---- N GPUs: pixel tiles sharded over ranks + ONE RCCL sum-reduce of the float3 framebuffer onto rank 0 (pt_comm.cpp) ----
  * No reference counterpart (the reference is single-GPU: create_context(nullptr, 1), application.cpp:62); for N > 1 these
  * replace the render + read-back of application.cpp:363-369.  Every pixel has exactly one non-zero contributor, so the
@@ -760,7 +806,12 @@ int pt_group_render_aov_follow(pt_group* g, const pt_camera* cam, int32_t width,
  *   option "kernel" = 1 (either order of the two pt_set_option calls), pt_debug_eval's closest-hit op 21, pt_render_batch(_device).
  *   "dynamic" 0 (default: pt_upload_scene keeps and allocates exactly what it always did) | 1: the NEXT pt_upload_scene also keeps, on
  *   the host and in HBM, what pt_update_vertices needs - the meshes' vertex and normal arrays, three vertex indices per triangle slot,
- *   the binary nodes sorted by height, and for every quad / oct slot the binary box it is a copy of. */
+ *   the binary nodes sorted by height, and for every quad / oct slot the binary box it is a copy of.
+ *   "rays_refill" 0..63 (default 32, a starting value nobody had measured when it was chosen; README "Ray queries" has the figures): a wave
+ *   of pt_trace_closest / pt_trace_occluded gives its idle lanes new rays of its range when at most this many lanes are still walking -
+ *   0: a new batch only when the whole wave is done, 63: whenever a lane is idle.  Like the others it changes no result.
+ *   "rays_grid" 0 (default: as many waves as the occupancy query says are resident, or one per 64 rays if that is fewer) | n: at most n
+ *   waves, each with a longer range - the tests use it to give a wave many 64-ray blocks to refill from; it changes no result. */
 int pt_set_option(pt_ctx* ctx, const char* key, int64_t value);
 int pt_get_stats(pt_ctx* ctx, pt_stats* out);
 

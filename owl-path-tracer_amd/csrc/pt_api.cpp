@@ -177,6 +177,11 @@ int pt_set_option(pt_ctx* c, const char* key, int64_t value)
         if (value != 0 && value != 1) return fail(c, PT_E_INVALID, "dynamic must be 0 (default) or 1 (the next pt_upload_scene keeps what pt_update_vertices needs)");
         c->opt.dynamic = (int)value;
     }
+    else if (k == "rays_refill") { // pt_trace_closest / pt_trace_occluded: idle lanes of a wave take new rays when at most this many lanes are still walking
+        if (value < 0 || value > 63) return fail(c, PT_E_INVALID, "rays_refill must be 0 (a new batch only when the whole wave is done) .. 63 (whenever a lane is idle); default 32");
+        c->opt.rays_refill = (int)value;
+    }
+    else if (k == "rays_grid") c->opt.rays_grid = (int)(value < 0 ? 0 : (value > 0x7fffffff ? 0x7fffffff : value)); // pt_trace_*: most workgroups of the ray launch (0: what the occupancy query says is resident)
     else if (k == "quad") c->opt.quad = value != 0; // wavefront kernel: quad nodes (two binary levels per fetch), next pt_render
     else if (k == "node_pairs") c->opt.node_pairs = value != 0;
     else if (k == "leaf_align") c->opt.leaf_align = (int)(value < 1 ? 1 : (value > 8 ? 8 : value));

@@ -1,6 +1,6 @@
 // pt_internal.h -- private to the library: the context behind the opaque pt_ctx of include/mi355pt.h and the helpers its host sources
 // share: pt_api.cpp (context, options, stats), pt_scene.cpp (scene upload and clone), pt_render.cpp (frames and batches), pt_guides.cpp
-// (guide pass and denoiser), pt_accum_host.cpp (progressive accumulation and its reprojection), pt_debug.cpp (probes and readers) and pt_comm.cpp (RCCL reduce, multi-GPU group).
+// (guide pass and denoiser), pt_accum_host.cpp (progressive accumulation and its reprojection), pt_rays_host.cpp (ray queries), pt_debug.cpp (probes and readers) and pt_comm.cpp (RCCL reduce, multi-GPU group).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -61,13 +61,14 @@ struct HostScene {
     pt_env env{};
     HostTexture env_map;
     uint64_t bvh_nodes = 0, bvh_depth = 0, n_triangles = 0; // pt_stats
+    std::vector<uint64_t> mesh_first; // global id of every mesh's first triangle, then n_triangles: the prefix sums pt_prim_to_mesh inverts
     double bvh_build_ms = 0.0;
     DynScene dyn;
 };
 
 // pt_set_option: every option with its default.
 struct PtOptions {
-    int spp_per_launch = 0, count = 0, blocks_per_cu = 0, leaf_size = 4, max_bvh_depth = 48, kernel = 2, slots_per_wave = 0, chunk_spp = 64, chunk_tail_min = -1, schedule = 1, prepass_spp = 0, census_mode = 0, sticky_pct = -1, latency = 0, cost_radius = 2, timeline = 0, node_pairs = 0, leaf_align = 1, bvh_builder = 3, quad = 1, groups = 1, wide_leaves = 1, fallback = 0, ploc_radius = 16, express_permille = -1, ns_express = 8, whole = -1, box_exact = -1, batch_frames = 0, watertight = 0, dynamic = 0;
+    int spp_per_launch = 0, count = 0, blocks_per_cu = 0, leaf_size = 4, max_bvh_depth = 48, kernel = 2, slots_per_wave = 0, chunk_spp = 64, chunk_tail_min = -1, schedule = 1, prepass_spp = 0, census_mode = 0, sticky_pct = -1, latency = 0, cost_radius = 2, timeline = 0, node_pairs = 0, leaf_align = 1, bvh_builder = 3, quad = 1, groups = 1, wide_leaves = 1, fallback = 0, ploc_radius = 16, express_permille = -1, ns_express = 8, whole = -1, box_exact = -1, batch_frames = 0, watertight = 0, dynamic = 0, rays_refill = 32, rays_grid = 0;
     int tune[8] = {};
 };
 
@@ -138,6 +139,7 @@ struct pt_ctx {
     DevBuf d_aov, d_aov_ws; // guide pass: the frame of pt_render_aov / pt_group_render_aov; bound flag (64 words) + the waves' stack overflow columns
     DevBuf d_dn_ws, d_dn_rgb, d_dn_aov, d_dn_out8; // denoiser: the filter's records (pt_denoise_workspace_bytes); pt_denoise's staging of rgb (in and out), guides and RGBA8
     DevBuf d_dn_var; // pt_denoise_var's staging of the variance map; pt_accum_variance's / pt_accum_denoise's map of the accumulation
+    DevBuf d_rays_in, d_rays_out; // ray queries: the blocking forms' staging of the rays and of the results (pt_rays_host.cpp; the overflow columns and the bound flag are the guide pass's d_aov_ws)
     DevBuf d_up_ws, d_up_rgb, d_up_aov; // upsampling: the low frame's records (pt_upsample_workspace_bytes); pt_upsample's staging of the low frame and its guides (the high guides and both outputs stage in d_dn_aov, d_dn_rgb, d_dn_out8)
     std::vector<DevBuf> d_textures;
 

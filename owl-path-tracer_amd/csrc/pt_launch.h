@@ -64,6 +64,17 @@ struct PtAovFollowArgs {
     int32_t pad;
 };
 
+// Ray queries (pt_trace_closest, pt_trace_occluded; pt_kernel.hip "ray queries"): what the ray kernels take beside the scene in PtKernelParams.
+struct PtRaysArgs {
+    const void* rays;  // n pt_ray records (include/mi355pt.h: org, tmax, dir, one float that is not read), 16-byte aligned
+    void* out;         // closest: n pt_ray_hit {t, u, v, prim}, 16-byte aligned; occluded: n bytes
+    uint32_t* ovf;     // the waves' HBM stack columns, (cap - PT_LDS_STACK) * 64 words per workgroup (none when cap <= PT_LDS_STACK)
+    int32_t n;         // rays (< 2^31)
+    int32_t per_wave;  // rays of a workgroup's range, a multiple of 64: workgroup b owns [b * per_wave, min(n, (b + 1) * per_wave))
+    int32_t cap;       // stack levels a lane may use (stack bound + the three pushes of a step)
+    int32_t refill;    // option "rays_refill", 0..63: idle lanes take new rays when at most this many lanes are still walking
+};
+
 // Denoiser (pt_denoise; pt_denoise.hip): what its three kernels take.  The host fills everything but the record pointers, which
 // pt_launch_denoise carves out of ws; the constants are include/mi355pt.h's "host constants" (pti::denoise_constants).
 struct PtDenoiseArgs {
@@ -224,6 +235,12 @@ hipError_t pt_launch_aov(const PtKernelParams* p, const PtAovArgs* a, int binary
 hipError_t pt_aov_geometry(int binary, int exact, int stack_entries, PtGeometry* g);
 hipError_t pt_launch_aov_wt(const PtKernelParams* p, const PtAovArgs* a, int binary, int grid, size_t lds_bytes, hipStream_t stream);
 hipError_t pt_aov_geometry_wt(int binary, int exact, int stack_entries, PtGeometry* g);
+// pt_kernel_rays.hip / pt_kernel_rays_wt.hip: the ray kernels (quad walk only; slab form by p->box_exact).  Geometry: block, lds_bytes,
+// lds_levels, vgprs and max_blocks_per_cu of the instance; hipErrorInvalidConfiguration if it needs scratch.
+hipError_t pt_launch_rays(const PtKernelParams* p, const PtRaysArgs* a, int occluded, int grid, size_t lds_bytes, hipStream_t stream);
+hipError_t pt_rays_geometry(int occluded, int exact, PtGeometry* g);
+hipError_t pt_launch_rays_wt(const PtKernelParams* p, const PtRaysArgs* a, int occluded, int grid, size_t lds_bytes, hipStream_t stream);
+hipError_t pt_rays_geometry_wt(int occluded, int exact, PtGeometry* g);
 // pt_kernel_aov_follow.hip / pt_kernel_aov_follow_wt.hip: the follow kernels, same conventions; lds_bytes covers the stack and the state a lane parks behind it
 hipError_t pt_launch_aov_follow(const PtKernelParams* p, const PtAovFollowArgs* a, int binary, int grid, size_t lds_bytes, hipStream_t stream);
 hipError_t pt_aov_follow_geometry(int binary, int exact, int stack_entries, PtGeometry* g);

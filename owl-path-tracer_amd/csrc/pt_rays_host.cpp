@@ -1,0 +1,161 @@
+// pt_rays_host.cpp -- ray queries on the caller's rays (pt_trace_closest*, pt_trace_occluded*): ONE device path behind the asynchronous
+// and blocking entry points, the CPU twin pt_debug_trace_rays_host and pt_prim_to_mesh.
+// The pass reads the scene and nothing of a frame: no pixel queue, no shard, no materials, no environment, no collective.  Its own
+// buffers are d_rays_in / d_rays_out (the blocking forms' staging); the waves' stack overflow columns and the bound flag are the guide
+// pass's d_aov_ws, laid out as there (pt_guides.cpp) - the two passes are ordered like any two calls of a context, and check_watchdog
+// looks at one flag.
+#include <algorithm>
+#include <cstring>
+
+#include "pt_internal.h"
+#include "pt_launch.h"
+
+using namespace pti;
+
+namespace {
+
+#define PT_RAYS_FLAG_WORDS 64 // d_aov_ws: the bound flag on a line of its own, then the overflow columns (PT_AOV_FLAG_WORDS of pt_guides.cpp)
+constexpr float kRayTMin = 1e-3f, kRayTMax = 1e10f; // kTMin, kTMax of pt_device.h
+
+static_assert(sizeof(pt_ray) == 32 && sizeof(pt_ray_hit) == 16, "the ray kernels read a ray as two 16-byte loads and store a hit as one");
+
+const struct RaysInstance {
+    hipError_t (*geometry)(int occluded, int exact, PtGeometry* g);
+    hipError_t (*launch)(const PtKernelParams* p, const PtRaysArgs* a, int occluded, int grid, size_t lds_bytes, hipStream_t stream);
+} kRaysInstance[2] = {{pt_rays_geometry, pt_launch_rays}, {pt_rays_geometry_wt, pt_launch_rays_wt}}; // by [watertight]
+
+// What every form refuses before anything is touched, a host-only context last (who: the entry point).
+int check_rays_args(pt_ctx* c, const char* who, const void* rays, int64_t n, const void* out, bool device, bool closest)
+{
+    if (n < 0 || n >= ((int64_t)1 << 31)) return fail(c, PT_E_INVALID, "%s: n = %lld rays (0 .. 2^31 - 1)", who, (long long)n);
+    if (n > 0 && (!rays || !out)) return fail(c, PT_E_INVALID, "%s: NULL %s", who, !rays ? (device ? "d_rays" : "rays") : (device ? "d_out" : "out"));
+    if (device && n > 0 && ((uintptr_t)rays & 15u)) return fail(c, PT_E_INVALID, "%s: d_rays is not 16-byte aligned (a ray is two 16-byte loads)", who);
+    if (device && closest && n > 0 && ((uintptr_t)out & 15u)) return fail(c, PT_E_INVALID, "%s: d_out is not 16-byte aligned (a hit is one 16-byte store)", who);
+    if (!c->have_scene) return fail(c, PT_E_NO_SCENE, "%s: no geometries (pt_upload_scene not called)", who);
+    // the ray kernels walk the quad nodes - or a root that is itself a leaf (a scene of a few triangles has no nodes at all) - and nothing else
+    if (!c->opt.quad || (c->scene.nodes4.empty() && c->scene.root4 >= 0))
+        return fail(c, PT_E_INVALID, "%s: the ray queries need quad nodes (%s)", who, !c->opt.quad ? "option quad = 0" : "the tree is too deep for them");
+    return need_device(c);
+}
+
+// One launch of the ray kernel over n >= 1 rays in HBM.  A wave owns a contiguous range of whole 64-ray blocks; the grid is what the
+// occupancy query says is resident, or fewer when there are fewer blocks.
+int rays_device(pt_ctx* c, bool occluded, const void* d_rays, int64_t n, void* d_out, hipStream_t stream)
+{
+    const bool wt = c->opt.watertight != 0;
+    if (c->scene.bvh.tris.size() * sizeof(PtTri) > 0xffffffffull || c->scene.nodes4.size() * sizeof(PtNode4) > 0xffffffffull)
+        return fail(c, PT_E_LIMIT, "the ray kernel needs triangle records and quad nodes below 4 GiB each (%zu triangle slots, %zu quad nodes)", c->scene.bvh.tris.size(), c->scene.nodes4.size());
+    PtKernelParams P;
+    fill_params(c, P); // the scene; no camera, so no distance to judge the slab form by: the subtracting form only on request
+    P.box_exact = c->opt.box_exact > 0 ? 1 : 0;
+    P.nodes4 = (const PtNode4*)c->d_nodes4.p;
+    P.root = c->scene.root4;
+    P.stack_entries = 3 * c->scene.depth4 + 1;
+    const RaysInstance& inst = kRaysInstance[wt];
+    PtGeometry g{};
+    const hipError_t ge = inst.geometry(occluded, P.box_exact, &g);
+    if (ge == hipErrorInvalidConfiguration) return fail(c, PT_E_LIMIT, "this build of the ray kernel spills registers to scratch; such builds are refused (pt_kernel.hip)");
+    HIP_TRY(c, ge);
+    if (g.max_blocks_per_cu < 1) return fail(c, PT_E_LIMIT, "ray kernel does not fit a CU (LDS %zu bytes)", g.lds_bytes);
+    const int64_t n_blocks = (n + 63) / 64;
+    int64_t resident = (int64_t)c->num_cus * g.max_blocks_per_cu;
+    if (c->opt.rays_grid > 0) resident = std::min<int64_t>(resident, c->opt.rays_grid); // option "rays_grid": fewer, longer ranges (tests, tuning)
+    const int64_t blocks_per_wave = (n_blocks + resident - 1) / resident;
+    const int grid = (int)((n_blocks + blocks_per_wave - 1) / blocks_per_wave);
+    if (blocks_per_wave * 64 > 0x7fffffc0ll) return fail(c, PT_E_LIMIT, "ray kernel: %lld rays per wave", (long long)blocks_per_wave * 64);
+    PtRaysArgs A{};
+    A.cap = P.stack_entries + 3;
+    const size_t ovf_words = (size_t)std::max(0, A.cap - g.lds_levels) * 64 * (size_t)grid;
+    int rc;
+    if ((rc = ensure(c, c->d_aov_ws, (PT_RAYS_FLAG_WORDS + ovf_words) * 4))) return rc; // (growing it first waits on the host for what is in flight)
+    HIP_TRY(c, hipMemsetAsync(c->d_aov_ws.p, 0, PT_RAYS_FLAG_WORDS * 4, stream));
+    P.error_flag = (uint32_t*)c->d_aov_ws.p;
+    P.lds_levels = g.lds_levels;
+    A.rays = d_rays;
+    A.out = d_out;
+    A.ovf = (uint32_t*)c->d_aov_ws.p + PT_RAYS_FLAG_WORDS;
+    A.n = (int32_t)n;
+    A.per_wave = (int32_t)(blocks_per_wave * 64);
+    A.refill = c->opt.rays_refill;
+    HIP_TRY(c, hipEventRecord(c->ev0, stream));
+    HIP_TRY(c, inst.launch(&P, &A, occluded, grid, g.lds_bytes, stream));
+    HIP_TRY(c, hipEventRecord(c->ev1, stream));
+    note_pass(c, (int)std::min<int64_t>(n, 0x7fffffff), 1, 1, grid, g, P.stack_entries, true);
+    return PT_OK;
+}
+
+int rays_async(pt_ctx* c, const char* who, bool occluded, const void* d_rays, int64_t n, void* d_out, void* stream_v)
+{
+    if (!c) return PT_E_INVALID;
+    int rc;
+    if ((rc = check_rays_args(c, who, d_rays, n, d_out, true, !occluded))) return rc;
+    if (n == 0) return PT_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t stream = stream_v ? (hipStream_t)stream_v : c->stream;
+    return async_call(c, stream, [&] { return rays_device(c, occluded, d_rays, n, d_out, stream); });
+}
+
+// Host buffers: the rays staged in d_rays_in, the results in d_rays_out, and back.
+int rays_blocking(pt_ctx* c, const char* who, bool occluded, const pt_ray* rays, int64_t n, void* out)
+{
+    if (!c) return PT_E_INVALID;
+    int rc;
+    if ((rc = check_rays_args(c, who, rays, n, out, false, !occluded))) return rc;
+    if (n == 0) return PT_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t out_bytes = (size_t)n * (occluded ? 1 : sizeof(pt_ray_hit));
+    return blocking_call(c, [&]() -> int {
+        int rc2;
+        if ((rc2 = ensure(c, c->d_rays_in, (size_t)n * sizeof(pt_ray))) || (rc2 = ensure(c, c->d_rays_out, out_bytes))) return rc2;
+        HIP_TRY(c, hipMemcpyAsync(c->d_rays_in.p, rays, (size_t)n * sizeof(pt_ray), hipMemcpyHostToDevice, c->stream));
+        if ((rc2 = rays_device(c, occluded, c->d_rays_in.p, n, c->d_rays_out.p, c->stream))) return rc2;
+        return drain(c, {{out, c->d_rays_out.p, out_bytes}});
+    });
+}
+
+} // namespace
+
+extern "C" {
+
+int pt_trace_closest(pt_ctx* c, const pt_ray* rays, int64_t n, pt_ray_hit* out) { return rays_blocking(c, "pt_trace_closest", false, rays, n, out); }
+int pt_trace_occluded(pt_ctx* c, const pt_ray* rays, int64_t n, uint8_t* out) { return rays_blocking(c, "pt_trace_occluded", true, rays, n, out); }
+int pt_trace_closest_device(pt_ctx* c, const void* d_rays, int64_t n, void* d_out, void* stream) { return rays_async(c, "pt_trace_closest_device", false, d_rays, n, d_out, stream); }
+int pt_trace_occluded_device(pt_ctx* c, const void* d_rays, int64_t n, void* d_out, void* stream) { return rays_async(c, "pt_trace_occluded_device", true, d_rays, n, d_out, stream); }
+
+int64_t pt_debug_trace_rays_host(pt_ctx* c, const pt_ray* rays, int64_t n, int32_t occluded, void* out)
+{
+    if (!c) return PT_E_INVALID;
+    if (n < 0 || n >= ((int64_t)1 << 31)) return fail(c, PT_E_INVALID, "pt_debug_trace_rays_host: n = %lld rays (0 .. 2^31 - 1)", (long long)n);
+    if (n > 0 && (!rays || !out)) return fail(c, PT_E_INVALID, "pt_debug_trace_rays_host: NULL %s", !rays ? "rays" : "out");
+    if (!c->have_scene) return fail(c, PT_E_NO_SCENE, "pt_debug_trace_rays_host: no geometries (pt_upload_scene not called)");
+    sync_host_scene(c);
+    const bool wt = c->opt.watertight != 0;
+    pt_parallel_ranges((size_t)n, [&](size_t lo, size_t hi) {
+        for (size_t i = lo; i < hi; ++i) {
+            const pt_ray& r = rays[i];
+            const float thi = r.tmax < kRayTMax ? r.tmax : kRayTMax; // NaN and +inf: the library's own bound
+            float t = 0.0f, u = 0.0f, v = 0.0f;
+            int32_t prim = -1;
+            const bool hit = pt_bvh_closest_hit_host(c->scene.bvh, r.org, r.dir, kRayTMin, thi, &t, &u, &v, &prim, wt);
+            if (occluded) ((uint8_t*)out)[i] = hit ? 1 : 0;
+            else ((pt_ray_hit*)out)[i] = hit ? pt_ray_hit{t, u, v, prim} : pt_ray_hit{0.0f, 0.0f, 0.0f, -1};
+        }
+    });
+    return n;
+}
+
+int pt_prim_to_mesh(pt_ctx* c, int32_t prim, int32_t* mesh, int32_t* triangle)
+{
+    if (!c) return PT_E_INVALID;
+    if (!c->have_scene) return fail(c, PT_E_NO_SCENE, "pt_prim_to_mesh: no geometries (pt_upload_scene not called)");
+    const std::vector<uint64_t>& first = c->scene.mesh_first; // n_meshes + 1 prefix sums
+    if (prim < 0 || first.size() < 2 || (uint64_t)prim >= first.back())
+        return fail(c, PT_E_INVALID, "pt_prim_to_mesh: triangle id %d outside 0 .. %lld", prim, first.empty() ? -1ll : (long long)first.back() - 1);
+    // the last mesh that starts at or before prim (meshes without triangles share their successor's start and are never the answer)
+    const size_t m = (size_t)(std::upper_bound(first.begin(), first.end() - 1, (uint64_t)prim) - first.begin()) - 1;
+    if (mesh) *mesh = (int32_t)m;
+    if (triangle) *triangle = (int32_t)((uint64_t)prim - first[m]);
+    return PT_OK;
+}
+
+} // extern "C"

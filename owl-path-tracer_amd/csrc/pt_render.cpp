@@ -39,11 +39,11 @@ void fill_params(pt_ctx* c, PtKernelParams& P)
 // After the render stream has drained: did a wave's watchdog fire (pt_kernel.hip, PT_WATCHDOG_ROUNDS)?  The image is then incomplete.
 int check_watchdog(pt_ctx* c)
 {
-    if (c->last.aov_flag_pending && c->d_aov_ws.p) { // the last call was a guide pass: its walks' step and stack bound (pt_kernel.hip, pt_aov_kernel)
+    if (c->last.aov_flag_pending && c->d_aov_ws.p) { // the last call was a guide pass or a ray query: its walks' step and stack bound (pt_kernel.hip, pt_aov_kernel / pt_rays_kernel)
         uint32_t fired = 0;
         HIP_TRY(c, hipMemcpy(&fired, c->d_aov_ws.p, 4, hipMemcpyDeviceToHost));
         c->last.aov_flag_pending = false;
-        if (fired) return fail(c, PT_E_HIP, "guide pass: a walk ran out of its step or stack bound; the buffers are incomplete");
+        if (fired) return fail(c, PT_E_HIP, "guide pass or ray query: a walk ran out of its step or stack bound; the buffers are incomplete");
     }
     if (c->opt.kernel != 2 || !c->d_laps.p || !c->last.flag_pending) return PT_OK;
     uint32_t wd = 0;

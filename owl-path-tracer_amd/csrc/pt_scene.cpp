@@ -398,6 +398,7 @@ extern "C" int pt_upload_scene(pt_ctx* c, const pt_mesh* meshes, int32_t n_meshe
     c->scene.bvh_nodes = c->scene.bvh.nodes.size();
     c->scene.bvh_depth = (uint64_t)c->scene.bvh.depth;
     c->scene.n_triangles = n_tris;
+    c->scene.mesh_first.assign(mesh_first.begin(), mesh_first.end()); // pt_prim_to_mesh
     if (c->scene.bvh.depth > PT_MAX_STACK) return fail(c, PT_E_LIMIT, "BVH depth %d exceeds %d", c->scene.bvh.depth, PT_MAX_STACK);
     phase("BVH build");
     layout_and_collapse(c);

@@ -131,7 +131,12 @@ EXPORTS = ["pt_create", "pt_destroy", "pt_last_error", "pt_abi_version", "pt_upl
            "pt_denoise_var_default_params", "pt_denoise_var", "pt_denoise_var_device", "pt_debug_denoise_var_host",
            "pt_accum_variance", "pt_debug_accum_variance_host", "pt_accum_denoise", "pt_accum_denoise_device",
            "pt_accum_reproject_default_params", "pt_accum_reproject", "pt_accum_reproject_device", "pt_debug_accum_reproject_host",
-           "pt_upsample_default_params", "pt_upsample", "pt_upsample_device", "pt_debug_upsample_host"]
+           "pt_upsample_default_params", "pt_upsample", "pt_upsample_device", "pt_debug_upsample_host",
+           "pt_trace_closest", "pt_trace_closest_device", "pt_trace_occluded", "pt_trace_occluded_device", "pt_debug_trace_rays_host", "pt_prim_to_mesh"]
+# pt_ray / pt_ray_hit (include/mi355pt.h "ray queries"): 32 and 16 bytes
+RAY_DTYPE = np.dtype([("org", "<f4", (3,)), ("tmax", "<f4"), ("dir", "<f4", (3,)), ("unused", "<f4")])
+HIT_DTYPE = np.dtype([("t", "<f4"), ("u", "<f4"), ("v", "<f4"), ("prim", "<i4")])
+assert RAY_DTYPE.itemsize == 32 and HIT_DTYPE.itemsize == 16
 PT_DENOISE_DEMODULATE = 1
 PT_UPSAMPLE_DEMODULATE = 1
 PT_TREE_DEVICE = 16  # pt_debug_export_tree: ORed into `which`, the array as HBM holds it
@@ -279,6 +284,13 @@ def lib():
                                      C.c_void_p]
     L.pt_debug_upsample_host.argtypes = [C.c_void_p, fp, fp, C.c_int32, C.c_int32, fp, C.c_int32, C.c_int32, C.POINTER(UpsampleParams), fp, u32p]
     L.pt_debug_upsample_host.restype = C.c_int64
+    L.pt_trace_closest.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    L.pt_trace_closest_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    L.pt_trace_occluded.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    L.pt_trace_occluded_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    L.pt_debug_trace_rays_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
+    L.pt_debug_trace_rays_host.restype = C.c_int64
+    L.pt_prim_to_mesh.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     _lib = L
     return L
 
@@ -354,6 +366,23 @@ def make_env(use_map=False, use_auto=False, color=(0, 0, 0), intensity=0.0, env_
     e.intensity = float(intensity)
     e.map, e._keep = _texture(env_map)
     return e
+
+
+def make_rays(rays, tmax=np.inf):
+    """(n, 6) float32 origins and directions -> n pt_ray records (RAY_DTYPE) with the given bound(s): a scalar or n values.  The
+    float that the library does not read is set to NaN."""
+    r = np.asarray(rays, np.float32).reshape(-1, 6)
+    out = np.zeros(r.shape[0], RAY_DTYPE)
+    out["org"], out["dir"] = r[:, :3], r[:, 3:]
+    out["tmax"] = np.asarray(tmax, np.float32)
+    out["unused"] = np.float32(np.nan)
+    return out
+
+
+def _rays(rays):
+    """pt_ray records as a contiguous RAY_DTYPE array (an (n, 6) float array gets tmax = +inf)."""
+    a = np.asarray(rays)
+    return np.ascontiguousarray(a) if a.dtype == RAY_DTYPE else make_rays(a)
 
 
 def denoise_default_params(**changes):
@@ -967,6 +996,41 @@ class Context:
                                                  o["passes"].ctypes.data_as(up), o["rgb"].ctypes.data_as(fp), o["rgba8"].ctypes.data_as(up), o["noise"].ctypes.data_as(fp))
         self._check(int(rc), "pt_debug_accum_reproject_host")
         return o
+
+    def _trace(self, fn, what, rays, occluded, extra=()):
+        r = _rays(rays)
+        out = np.empty(r.shape[0], np.uint8 if occluded else HIT_DTYPE)
+        rc = fn(self._h, r.ctypes.data_as(C.c_void_p), r.shape[0], *extra, out.ctypes.data_as(C.c_void_p))
+        self._check(int(rc), what)
+        return out
+
+    def trace_closest(self, rays):
+        """pt_trace_closest: the closest hit of every ray (RAY_DTYPE records, or (n, 6) origins and directions with tmax = +inf) as a
+        HIT_DTYPE array {t, u, v, prim}; a miss is {0, 0, 0, -1} (include/mi355pt.h "ray queries")."""
+        return self._trace(lib().pt_trace_closest, "pt_trace_closest", rays, False)
+
+    def trace_occluded(self, rays):
+        """pt_trace_occluded: one byte per ray, 1 = some triangle is hit within the ray's bound."""
+        return self._trace(lib().pt_trace_occluded, "pt_trace_occluded", rays, True)
+
+    def trace_rays_host(self, rays, occluded=False):
+        """pt_debug_trace_rays_host, the CPU twin of trace_closest / trace_occluded (works on a host-only context)."""
+        return self._trace(lib().pt_debug_trace_rays_host, "pt_debug_trace_rays_host", rays, occluded, (int(bool(occluded)),))
+
+    def trace_closest_device(self, d_rays, n, d_out, stream=None):
+        """pt_trace_closest_device: asynchronous, n pt_ray records at the device pointer d_rays (16-byte aligned), n pt_ray_hit left at
+        d_out; synchronize() waits for it.  stream: a hipStream_t as an integer, None = the context's own; ordering as render_device."""
+        self._check(lib().pt_trace_closest_device(self._h, C.c_void_p(d_rays), int(n), C.c_void_p(d_out), C.c_void_p(stream) if stream else None), "pt_trace_closest_device")
+
+    def trace_occluded_device(self, d_rays, n, d_out, stream=None):
+        """pt_trace_occluded_device: the same for the occlusion flags, n bytes left at d_out."""
+        self._check(lib().pt_trace_occluded_device(self._h, C.c_void_p(d_rays), int(n), C.c_void_p(d_out), C.c_void_p(stream) if stream else None), "pt_trace_occluded_device")
+
+    def prim_to_mesh(self, prim):
+        """pt_prim_to_mesh: (entity of the upload, triangle inside it) of a global triangle id."""
+        m, t = C.c_int32(-1), C.c_int32(-1)
+        self._check(lib().pt_prim_to_mesh(self._h, int(prim), C.byref(m), C.byref(t)), "pt_prim_to_mesh")
+        return int(m.value), int(t.value)
 
     def comm_init_rank(self, unique_id, rank, world):
         buf = (C.c_uint8 * PT_COMM_ID_BYTES).from_buffer_copy(unique_id)
