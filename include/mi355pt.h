@@ -170,7 +170,7 @@ int pt_render(pt_ctx* ctx, const pt_camera* cam, int32_t width, int32_t height, 
  * every call that touches what a frame in flight uses is ordered after the context's LAST ASYNCHRONOUS CALL, whichever stream that
  * call was given.  So any call of this header may follow a pt_*_device call at once, with no pt_synchronize between them.
  *   - The asynchronous calls (pt_render_device, pt_render_batch_device, pt_render_aov_device, pt_render_aov_follow_device, pt_render_aov_batch_device, pt_denoise_device,
- *     pt_denoise_batch_device, pt_denoise_var_device, pt_accum_add_device, pt_accum_denoise_device, pt_accum_reproject_device, pt_upsample_device, pt_trace_closest_device, pt_trace_occluded_device, pt_reduce_framebuffer) wait ON THE
+ *     pt_denoise_batch_device, pt_denoise_var_device, pt_accum_add_device, pt_accum_denoise_device, pt_accum_reproject_device, pt_upsample_device, pt_trace_closest_device, pt_trace_occluded_device, pt_render_rays_device, pt_reduce_framebuffer) wait ON THE
  *     DEVICE: the stream they are given waits for an event recorded at the end of the previous asynchronous call - only if that call
  *     used another stream; on the same stream the stream's own order suffices and nothing is added.  The host returns at once, with
  *     two exceptions that existed before: a frame of another size, shard or batch length rewrites the pixel queue and a frame that
@@ -178,7 +178,7 @@ int pt_render(pt_ctx* ctx, const pt_camera* cam, int32_t width, int32_t height, 
  *     before) - both first wait on the host for the frame in flight; pt_render_batch_device and pt_render_aov_batch_device
  *     return when their per-frame tables have reached HBM, i.e. after whatever precedes them on `stream`; and a pt_accum_add_device that
  *     selects its pixels returns when the count of its active set has reached the host (see there).
- *   - The blocking renders (pt_render, pt_render_batch, pt_render_aov, pt_render_aov_follow, pt_render_aov_batch, pt_accum_add), pt_denoise, pt_denoise_batch, pt_denoise_var, pt_accum_denoise, pt_accum_reproject, pt_upsample, pt_trace_closest and pt_trace_occluded run on the context's stream behind the same device-side wait
+ *   - The blocking renders (pt_render, pt_render_batch, pt_render_aov, pt_render_aov_follow, pt_render_aov_batch, pt_accum_add), pt_denoise, pt_denoise_batch, pt_denoise_var, pt_accum_denoise, pt_accum_reproject, pt_upsample, pt_trace_closest, pt_trace_occluded and pt_render_rays run on the context's stream behind the same device-side wait
  *     and return with the context idle.  After a blocking call, or on the context's own stream, they add no wait at all.
  *   - The calls that change or read what a frame uses WAIT ON THE HOST for the last asynchronous call's stream (if it is not the
  *     context's) and then for the context's: pt_set_materials, pt_set_environment, pt_update_vertices, pt_upload_scene,
@@ -193,7 +193,7 @@ int pt_render(pt_ctx* ctx, const pt_camera* cam, int32_t width, int32_t height, 
 int pt_render_device(pt_ctx* ctx, const pt_camera* cam, int32_t width, int32_t height, int32_t max_samples, int32_t max_path_depth,
                      void* d_out_rgb, void* d_out_rgba8, void* stream);
 /* Waits on the host for the context's last asynchronous call - pt_render_device, pt_render_batch_device, pt_render_aov_device,
- * pt_render_aov_follow_device, pt_render_aov_batch_device, pt_denoise_device, pt_denoise_batch_device, pt_denoise_var_device, pt_accum_add_device, pt_accum_denoise_device, pt_accum_reproject_device, pt_upsample_device, pt_trace_closest_device, pt_trace_occluded_device or pt_reduce_framebuffer, on the stream it was given - and for the context's own stream.  Every earlier asynchronous call of the context
+ * pt_render_aov_follow_device, pt_render_aov_batch_device, pt_denoise_device, pt_denoise_batch_device, pt_denoise_var_device, pt_accum_add_device, pt_accum_denoise_device, pt_accum_reproject_device, pt_upsample_device, pt_trace_closest_device, pt_trace_occluded_device, pt_render_rays_device or pt_reduce_framebuffer, on the stream it was given - and for the context's own stream.  Every earlier asynchronous call of the context
  * is complete then as well, whatever stream it used: each was ordered before the next (see pt_render_device).  Returns PT_E_HIP if a
  * wave's watchdog fired during the last frame (the image is then incomplete); pt_get_stats reports the same.  PT_OK at once on an idle
  * or host-only context.  A caller's stream may be destroyed once this has returned. */
@@ -725,6 +725,53 @@ int64_t pt_debug_trace_rays_host(pt_ctx* ctx, const pt_ray* rays, int64_t n, int
 /* Host only: the mesh (entity of the upload) and the triangle inside it of a global triangle id, through the prefix sums of n_triangles
  * of the upload.  PT_E_INVALID outside 0 .. n_triangles-1, PT_E_NO_SCENE without a scene. */
 int pt_prim_to_mesh(pt_ctx* ctx, int32_t prim, int32_t* mesh, int32_t* triangle);
+
+/* ---- ray images: path-traced radiance along the CALLER'S rays (no reference counterpart: the reference starts every path at its one
+ * pinhole camera, device.cu:231-241) ----
+ * pt_render_rays is pt_render with the camera replaced by a ray image: one pt_ray_gen record per pixel - an equirectangular or fisheye
+ * panorama, a cube-map light probe, an irradiance or lightmap bake from surface points, a lens model with an aperture.  Everything
+ * behind the camera ray is the render kernel itself: the instances of csrc/pt_kernel_rayimage.hip are csrc/pt_kernel.hip compiled with
+ * another ray generator (gen_ray_from, csrc/pt_trace.h).
+ * DEFINITION.  `rays` is a ray image of width x height records (a pt_ray_gen: 64 bytes; the kernel reads it as four 16-byte loads, once
+ * per sample); the record of pixel (x, y) is at launch index x + W*y.  Pixel (x, y) is pt_render's pixel in everything except the camera
+ * ray: the stream rng_init(x, y), rx = rng_next then ry = rng_next per sample, trace_path with its bounce loop, Russian roulette and NaN
+ * retries, the sum over max_samples, out = sum * (1 / max_samples) and make_rgba, stored at x + W*(H-1-y).  The camera ray of a sample
+ * starts at org and has the direction
+ *     dir_s = normalize((dir + du * rx) + dv * ry)
+ * in the arithmetic contract of csrc/pt_device.h: float32, no contraction, v3 * scalar per component, the same normalize
+ * (v * (1 / sqrt(dot(v, v)))).  Both draws are made even when du = dv = 0, so the stream is pt_render's.  The four reserved floats are
+ * NOT READ.  Two consequences:
+ *   - with du = dv = 0 the pixel is bit for bit pixel (x, y) of pt_render at the same W, H, max_samples and depth with the camera
+ *     {origin = org, llc = L, horizontal = 0, vertical = 0}, whenever fl(L - org) == dir;
+ *   - at W = H = 1 with org = 0 the pixel is bit for bit pt_render's with the camera {0, dir, du, dv}: su = (0 + rx) / 1 = rx, and
+ *     x - 0 = x.
+ * The call honours the material table, the environment, pt_update_vertices, the schedules and their knobs, "count" and a pixel shard set
+ * with pt_set_pixel_shard (pixels not owned are +0); the pt_get_stats fields are those of a pt_render.  "box_exact": 1 the subtracting
+ * slab form, 0 the fma form; the default -1 judges the blocking form's table as walk_params judges a camera (the largest |org| component
+ * against 42 scene extents) and gives the device form, whose records the host cannot see, the subtracting form - the image is the same
+ * under both.  It keeps no state: a pt_render after it is bit for bit the one before it, and an accumulation on the context is untouched.
+ * REFUSED with PT_E_INVALID, by name, before anything is touched: NULL rays / d_rays or out_rgb / d_out_rgb; the sizes and depths pt_render
+ * refuses; a d_rays that is not 16-byte aligned; in the blocking form (the host reads the table) a record whose org, dir, du or dv is not
+ * finite or whose dir is 0; option "watertight" = 1 (there are no watertight instances, as with batches), "kernel" = 1, "latency",
+ * "timeline"; a context with a communicator.  PT_E_NO_SCENE without a scene.  On a host-only context valid arguments give PT_E_NO_DEVICE
+ * and invalid ones PT_E_INVALID.  The device form cannot check the records: a record that the blocking form would refuse gives an
+ * undefined pixel, inside the walk's usual bounds (steps, stack, watchdog).
+ * ORDERING: pt_render_rays_device joins the asynchronous calls of the streams contract at pt_render_device and the list at
+ * pt_synchronize; d_rays stays the caller's buffer and must stay valid and unchanged until the work has completed on `stream`.  The
+ * blocking form stages the table in a buffer of the context's, runs on the context's stream behind the same device-side wait, and reads
+ * back; the context is idle on return.
+ * NOT BUILT: no pt_main flag, no pt_group_* form, no batch form, no watertight instances, no communicator, no accumulation over a ray
+ * image, no guide pass for ray images (a denoised panorama needs one). */
+typedef struct pt_ray_gen {      /* 64 bytes, read as four 16-byte loads */
+    float org[3]; float reserved0;   /* reserved floats are NOT READ */
+    float dir[3]; float reserved1;
+    float du[3];  float reserved2;   /* jitter: dir + du*rx + dv*ry, rx, ry in [0,1) */
+    float dv[3];  float reserved3;
+} pt_ray_gen;
+int pt_render_rays(pt_ctx* ctx, const pt_ray_gen* rays, int32_t width, int32_t height, int32_t max_samples, int32_t max_path_depth,
+                   float* out_rgb, uint32_t* out_rgba8);
+int pt_render_rays_device(pt_ctx* ctx, const void* d_rays, int32_t width, int32_t height, int32_t max_samples, int32_t max_path_depth,
+                          void* d_out_rgb, void* d_out_rgba8, void* stream);
 
 /* ---- N GPUs: pixel tiles sharded over ranks + ONE RCCL sum-reduce of the float3 framebuffer onto rank 0 (pt_comm.cpp) ----
  * No reference counterpart (the reference is single-GPU: create_context(nullptr, 1), application.cpp:62); for N > 1 these

@@ -140,6 +140,7 @@ struct pt_ctx {
     DevBuf d_dn_ws, d_dn_rgb, d_dn_aov, d_dn_out8; // denoiser: the filter's records (pt_denoise_workspace_bytes); pt_denoise's staging of rgb (in and out), guides and RGBA8
     DevBuf d_dn_var; // pt_denoise_var's staging of the variance map; pt_accum_variance's / pt_accum_denoise's map of the accumulation
     DevBuf d_rays_in, d_rays_out; // ray queries: the blocking forms' staging of the rays and of the results (pt_rays_host.cpp; the overflow columns and the bound flag are the guide pass's d_aov_ws)
+    DevBuf d_ray_image; // ray images: the blocking form's staging of the caller's table (pt_render_rays, pt_render.cpp)
     DevBuf d_up_ws, d_up_rgb, d_up_aov; // upsampling: the low frame's records (pt_upsample_workspace_bytes); pt_upsample's staging of the low frame and its guides (the high guides and both outputs stage in d_dn_aov, d_dn_rgb, d_dn_out8)
     std::vector<DevBuf> d_textures;
 

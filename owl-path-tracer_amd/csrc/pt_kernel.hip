@@ -33,6 +33,13 @@
 // material table per frame (pt_render_batch).  Everything that only looks at the queue works on the virtual image unchanged; the
 // places that must know the frame are the PT_BATCH blocks below (frame_of).  With PT_BATCH = 0 the preprocessor removes all of it:
 // the single-frame instances carry no batch code ("Batches").
+//
+// RAY IMAGE BUILD.  pt_kernel_rayimage.hip includes this file with PT_RAYGEN = 1: the same scheduler and device functions as instances of
+// pt_render_rayimage_kernel, whose pixels start their paths on the caller's rays (pt_render_rays): the one place of a path that knows
+// there is a camera is the ray generator, so the one PT_RAYGEN block below replaces gen_camera_ray by a gather of the pixel's 64-byte record
+// from the table in HBM (gen_ray_from, pt_trace.h; the table pointer travels in P.batch_cams, which nothing else reads when batch_frames == 0).
+// The record is gathered per sample, not kept: the 4-wave instance has no 16 registers to spare, and a pixel's chunks may run on different
+// waves.  With PT_RAYGEN = 0 the preprocessor removes all of it ("Ray images").
 #include "pt_launch.h"
 #include "pt_tiers.h"
 #include "pt_trace.h"
@@ -53,6 +60,12 @@
 #endif
 #if PT_AOV == 1 && PT_BATCH
 #error "the first-hit guide pass has no batch form (pt_render_aov_batch runs the follow kernels; max_follow = 0 gives the first-hit guides)"
+#endif
+#ifndef PT_RAYGEN
+#define PT_RAYGEN 0 // 1: pt_kernel_rayimage.hip - the wavefront kernel with the camera replaced by a per-pixel ray record (pt_render_rays, "RAY IMAGE BUILD" above)
+#endif
+#if PT_RAYGEN && (PT_BATCH || PT_WATERTIGHT || PT_AOV)
+#error "the ray-image build has no batch, watertight or guide instances"
 #endif
 #if PT_WATERTIGHT
 #if PT_BATCH
@@ -77,6 +90,10 @@
 #define pt_rays_kernel pt_rays_wt_kernel
 #define pt_launch_rays pt_launch_rays_wt
 #define pt_rays_geometry pt_rays_geometry_wt
+#elif PT_RAYGEN
+#define PT_RENDER_KERNEL pt_render_rayimage_kernel
+#define pt_launch_render pt_launch_render_rayimage
+#define pt_kernel_geometry pt_rayimage_kernel_geometry
 #elif PT_BATCH
 #define PT_RENDER_KERNEL pt_render_batch_kernel
 #define pt_aov_follow_kernel pt_aov_follow_batch_kernel
@@ -641,6 +658,8 @@ __device__ __forceinline__ void shade_pass(const PtKernelParams& P, WaveCtx& w, 
                 int frame, fy; // the camera of the pixel's frame: a per-lane gather from the table in HBM
                 frame_of(P, py, frame, fy);
                 gen_camera_ray_from(P, gp(P.batch_cams) + 12 * frame, px, fy, ps);
+#elif PT_RAYGEN
+                gen_ray_from(P, gp(P.batch_cams), px, py, ps); // the pixel's own ray record: a per-lane gather from the table in HBM
 #else
                 gen_camera_ray(P, px, py, ps);
 #endif
@@ -1308,6 +1327,9 @@ extern "C" hipError_t pt_launch_render(const PtKernelParams* p, const PtKernelPa
 {
 #if PT_WATERTIGHT
     if (variant != 2 && variant != 3) return hipErrorInvalidValue; // the lane-per-pixel kernel has no watertight form
+#elif PT_RAYGEN
+    if (variant != 2 && variant != 3) return hipErrorInvalidValue; // the lane-per-pixel kernel has no ray-image form
+    if (p->batch_cams == nullptr || p->batch_frames != 0) return hipErrorInvalidValue; // (the ray table, in the batch cameras' place)
 #else
     if (variant == 1) return pt_launch_render_lane(p, grid, lds_bytes, stream, count); // pt_kernel_aux.hip
 #endif
@@ -1331,7 +1353,7 @@ extern "C" hipError_t pt_batch_kernel_geometry(int variant, int count, int stack
 #else
 extern "C" hipError_t pt_kernel_geometry(int variant, int count, int stack_entries, int group_entries, int want_ns, int exact, PtGeometry* g)
 {
-#if PT_WATERTIGHT
+#if PT_WATERTIGHT || PT_RAYGEN
     if (variant != 2 && variant != 3) return hipErrorInvalidValue;
 #else
     if (variant == 1) return pt_lane_kernel_geometry(count, stack_entries, g); // pt_kernel_aux.hip
@@ -1359,7 +1381,7 @@ extern "C" hipError_t pt_kernel_geometry(int variant, int count, int stack_entri
 
 #endif // !PT_AOV
 
-#if !PT_BATCH && !PT_AOV // (the probes belong to the single-frame build)
+#if !PT_BATCH && !PT_AOV && !PT_RAYGEN // (the probes belong to the single-frame build)
 // =====================================================================================================================
 // Ray probes (tests only: pt_debug_eval ops PT_PROBE_*, pt_launch.h; tests/test_gpu_ray_probes.py)
 // =====================================================================================================================
@@ -1529,7 +1551,7 @@ extern "C" hipError_t pt_launch_probe(const PtKernelParams* p, int op, const flo
     }
     return hipGetLastError();
 }
-#endif // !PT_BATCH && !PT_AOV
+#endif // !PT_BATCH && !PT_AOV && !PT_RAYGEN
 
 #if PT_AOV == 1 || PT_AOV == 2
 // =====================================================================================================================

@@ -270,6 +270,10 @@ hipError_t pt_kernel_geometry(int variant, int count, int stack_entries, int gro
 // pt_kernel_batch.hip: the batch instances of the wavefront kernel (variants 2 and 3 and the instrumented instance; PtKernelParams::batch_*)
 hipError_t pt_launch_render_batch(const PtKernelParams* p, const PtKernelParams* d_params, int variant, int grid, size_t lds_bytes, hipStream_t stream, int count);
 hipError_t pt_batch_kernel_geometry(int variant, int count, int stack_entries, int group_entries, int want_ns, int exact, PtGeometry* g);
+// pt_kernel_rayimage.hip: the ray-image instances of the wavefront kernel (variants 2 and 3 and the instrumented instance; the table of W * H
+// pt_ray_gen records, 16-byte aligned, in PtKernelParams::batch_cams with batch_frames = 0)
+hipError_t pt_launch_render_rayimage(const PtKernelParams* p, const PtKernelParams* d_params, int variant, int grid, size_t lds_bytes, hipStream_t stream, int count);
+hipError_t pt_rayimage_kernel_geometry(int variant, int count, int stack_entries, int group_entries, int want_ns, int exact, PtGeometry* g);
 // pt_kernel_wt.hip: the watertight instances of the wavefront kernel (variants 2 and 3 and the instrumented instance) and of the ray probes
 hipError_t pt_launch_render_wt(const PtKernelParams* p, const PtKernelParams* d_params, int variant, int grid, size_t lds_bytes, hipStream_t stream, int count);
 hipError_t pt_wt_kernel_geometry(int variant, int count, int stack_entries, int group_entries, int want_ns, int exact, PtGeometry* g);

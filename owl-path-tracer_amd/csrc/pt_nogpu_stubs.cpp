@@ -16,6 +16,8 @@ hipError_t pt_launch_sort_pixels(const uint8_t*, int, int, int, const uint32_t*,
 hipError_t pt_kernel_geometry(int, int, int, int, int, int, PtGeometry*) { return hipErrorNotSupported; }
 hipError_t pt_launch_render_batch(const PtKernelParams*, const PtKernelParams*, int, int, size_t, hipStream_t, int) { return hipErrorNotSupported; }
 hipError_t pt_batch_kernel_geometry(int, int, int, int, int, int, PtGeometry*) { return hipErrorNotSupported; }
+hipError_t pt_launch_render_rayimage(const PtKernelParams*, const PtKernelParams*, int, int, size_t, hipStream_t, int) { return hipErrorNotSupported; }
+hipError_t pt_rayimage_kernel_geometry(int, int, int, int, int, int, PtGeometry*) { return hipErrorNotSupported; }
 hipError_t pt_launch_render_wt(const PtKernelParams*, const PtKernelParams*, int, int, size_t, hipStream_t, int) { return hipErrorNotSupported; }
 hipError_t pt_wt_kernel_geometry(int, int, int, int, int, int, PtGeometry*) { return hipErrorNotSupported; }
 hipError_t pt_launch_probe_wt(const PtKernelParams*, int, const float*, int, float*, int, long long, int, size_t, uint32_t*, hipStream_t) { return hipErrorNotSupported; }

@@ -1,5 +1,5 @@
 // pt_render.cpp -- a frame, from the pixel queue to the read-back: the plan of its launches, its buffers and parameters, the launches,
-// batches of frames (pt_render_batch), pt_render / pt_render_device, pt_synchronize, the watchdog check and the drain that ends every
+// batches of frames (pt_render_batch), ray images (pt_render_rays), pt_render / pt_render_device, pt_synchronize, the watchdog check and the drain that ends every
 // blocking call (the guide pass and the denoiser are pt_guides.cpp).
 #include <algorithm>
 #include <cmath>
@@ -226,6 +226,7 @@ struct FramePlan {
     int variant = 0, use_count = 0; // instance of the render kernel (pt_launch_render) and whether it is the instrumented one
     bool batch = false;             // the batch instances (pt_launch_render_batch): set by the caller before plan_frame
     bool wt = false;                // the watertight instances (pt_launch_render_wt): option "watertight", set by plan_frame
+    bool rays = false;              // the ray-image instances (pt_launch_render_rayimage): set by the caller before plan_frame (rays_image_device)
     PtGeometry geo{};               // its launch geometry
     int bpc = 0, grid = 0;          // workgroups per CU, of the (main) launch
     int ring_grid = 0;              // with a tier plan: the workgroups of the ring schedule (the plan's fallback; the pre-pass launches these)
@@ -315,6 +316,7 @@ int plan_frame(pt_ctx* c, const PtKernelParams& P, int max_samples, FramePlan& f
     // instance that needs scratch falls back to the 168-VGPR one, a fallback that needs it too is PT_E_LIMIT below)
     f.wt = c->opt.watertight != 0;
     if (f.wt && c->opt.kernel != 2) return fail(c, PT_E_INVALID, "watertight = 1: the lane-per-pixel kernel (option kernel = 1) has no watertight form");
+    if (f.wt && f.rays) return fail(c, PT_E_INVALID, "pt_render_rays: ray images have no watertight instances (option watertight = 1); set watertight = 0");
     if (f.wt && f.batch) return fail(c, PT_E_INVALID, "pt_render_batch: batches have no watertight instances (option watertight = 1); render the frames one by one or set watertight = 0");
     f.use_count = (c->opt.count || (c->opt.kernel == 2 && !P.nodes4)) ? 1 : 0;
     f.variant = c->opt.kernel == 2 && c->opt.fallback && !f.use_count ? 3 : c->opt.kernel;
@@ -328,6 +330,7 @@ int plan_frame(pt_ctx* c, const PtKernelParams& P, int max_samples, FramePlan& f
     const PtGeometry& g = f.geo;
     auto geometry = [&] {
         return f.batch ? pt_batch_kernel_geometry(f.variant, f.use_count, P.stack_entries, group_entries, want_ns, P.box_exact, &f.geo)
+               : f.rays ? pt_rayimage_kernel_geometry(f.variant, f.use_count, P.stack_entries, group_entries, want_ns, P.box_exact, &f.geo)
                : f.wt  ? pt_wt_kernel_geometry(f.variant, f.use_count, P.stack_entries, group_entries, want_ns, P.box_exact, &f.geo)
                        : pt_kernel_geometry(f.variant, f.use_count, P.stack_entries, group_entries, want_ns, P.box_exact, &f.geo);
     };
@@ -557,6 +560,7 @@ int run_launches(pt_ctx* c, const FramePlan& f, PtKernelParams& P, int W, int H,
         // as dense as the ring schedule's - C2 74.3 -> 71 ms, 1/8 shard 198 -> 194)
         const int grid = (f.tiers && l == 0) ? f.ring_grid : f.grid;
         HIP_TRY(c, f.batch ? pt_launch_render_batch(&P, dP, f.variant, grid, f.geo.lds_bytes, stream, f.use_count)
+                   : f.rays ? pt_launch_render_rayimage(&P, dP, f.variant, grid, f.geo.lds_bytes, stream, f.use_count)
                    : f.wt  ? pt_launch_render_wt(&P, dP, f.variant, grid, f.geo.lds_bytes, stream, f.use_count)
                            : pt_launch_render(&P, dP, f.variant, grid, f.geo.lds_bytes, stream, f.use_count));
     }
@@ -663,6 +667,67 @@ int render_device(pt_ctx* c, const pt_camera* cam, int W, int H, int max_samples
     return finish_frame(c, stream, W, H, &f, P.stack_entries);
 }
 
+// ---- ray images (pt_render_rays) ----------------------------------------------------------------------------------------
+// What both forms refuse before anything is touched, a host-only context last (who: the entry point; device: rays is a device pointer,
+// whose records the host cannot look at).
+int check_ray_image_args(pt_ctx* c, const char* who, const void* rays, int W, int H, int max_samples, int max_depth, const void* out_rgb, bool device)
+{
+    if (!rays || !out_rgb) return fail(c, PT_E_INVALID, "%s: NULL %s", who, !rays ? (device ? "d_rays" : "rays") : (device ? "d_out_rgb" : "out_rgb"));
+    if (device && ((uintptr_t)rays & 15u)) return fail(c, PT_E_INVALID, "%s: d_rays is not 16-byte aligned (a record is four 16-byte loads)", who);
+    int rc = check_render_args(c, W, H, max_samples, max_depth);
+    if (rc) return rc;
+    // what only exists for a camera's frame is refused by name, never rendered some other way
+    if (c->opt.kernel != 2) return fail(c, PT_E_INVALID, "%s: the lane-per-pixel kernel (option kernel = 1) has no ray-image form", who);
+    if (c->opt.watertight) return fail(c, PT_E_INVALID, "%s: ray images have no watertight instances (option watertight = 1); set watertight = 0", who);
+    if (c->opt.latency) return fail(c, PT_E_INVALID, "%s: the per-pixel latency diagnostics (option latency) belong to pt_render; switch them off for a ray image", who);
+    if (c->opt.timeline) return fail(c, PT_E_INVALID, "%s: the chunk timeline (option timeline) belongs to pt_render; switch it off for a ray image", who);
+    if (c->comm) return fail(c, PT_E_INVALID, "%s: a context with a communicator renders no ray images yet (render the ranks' shards with pt_set_pixel_shard and reduce them yourself)", who);
+    if (!device) { // the records themselves: finite, and a direction to normalize
+        const pt_ray_gen* r = (const pt_ray_gen*)rays;
+        const int64_t n = (int64_t)W * H;
+        for (int64_t i = 0; i < n; ++i) {
+            const float* v[4] = {r[i].org, r[i].dir, r[i].du, r[i].dv};
+            static const char* const name[4] = {"org", "dir", "du", "dv"};
+            for (int k = 0; k < 4; ++k)
+                if (!std::isfinite(v[k][0]) || !std::isfinite(v[k][1]) || !std::isfinite(v[k][2]))
+                    return fail(c, PT_E_INVALID, "%s: record %lld (pixel %lld, %lld): %s is not finite", who, (long long)i, (long long)(i % W), (long long)(i / W), name[k]);
+            if (r[i].dir[0] == 0.0f && r[i].dir[1] == 0.0f && r[i].dir[2] == 0.0f)
+                return fail(c, PT_E_INVALID, "%s: record %lld (pixel %lld, %lld): dir is 0", who, (long long)i, (long long)(i % W), (long long)(i / W));
+        }
+    }
+    return need_device(c);
+}
+
+// One frame over the ray image at d_rays on `stream`, which the caller has ordered after the context's last asynchronous call: render_device
+// with the ray-image instances (FramePlan::rays) and the table in the batch cameras' place.  far_o: the largest |org| component of the
+// table, which decides the slab form as the camera's origin does in walk_params (+infinity: unknown, the subtracting form unless
+// option "box_exact" = 0 asks for the other).
+int rays_image_device(pt_ctx* c, const void* d_rays, float far_o, int W, int H, int max_samples, int max_depth, void* d_out_rgb, void* d_out_rgba8, hipStream_t stream)
+{
+    int rc;
+    if ((rc = ensure_queue(c, W, H, 1, stream))) return rc;
+    if (c->n_pixels == 0) {
+        HIP_TRY(c, hipEventRecord(c->ev0, stream));
+        return empty_frame(c, stream, W, H, d_out_rgb, d_out_rgba8);
+    }
+
+    pt_camera cam{}; // no camera: walk_params reads the origin alone, the kernel nothing of P.cam
+    cam.origin[0] = far_o;
+    PtKernelParams P;
+    walk_params(c, &cam, P);
+    FramePlan f;
+    f.rays = true;
+    if ((rc = plan_frame(c, P, max_samples, f))) return rc;
+    if ((rc = frame_buffers(c, f, W, H, d_out_rgb, d_out_rgba8, stream))) return rc;
+    cam.origin[0] = 0.0f;
+    frame_params(c, f, &cam, W, H, max_samples, max_depth, d_out_rgb, d_out_rgba8, P);
+    P.batch_cams = (const float*)d_rays; // (batch_frames stays 0: pt_launch_render_rayimage checks both)
+
+    HIP_TRY(c, hipEventRecord(c->ev0, stream));
+    if ((rc = run_launches(c, f, P, W, H, max_samples, stream, true))) return rc;
+    return finish_frame(c, stream, W, H, &f, P.stack_entries);
+}
+
 } // namespace
 
 namespace pti {
@@ -743,6 +808,38 @@ int pt_render(pt_ctx* c, const pt_camera* cam, int32_t W, int32_t H, int32_t max
         // N ranks: the one collective of the path - RCCL sum-reduce of the float3 framebuffer onto rank 0 (pt_comm.cpp)
         if (c->comm && (rc = reduce_framebuffer(c, c->d_out.p, (root && out_rgba8) ? c->d_out8.p : nullptr, (int64_t)npx, c->stream))) return rc;
         return read_back(c, root, out_rgb, out_rgba8, npx);
+    });
+}
+
+int pt_render_rays_device(pt_ctx* c, const void* d_rays, int32_t W, int32_t H, int32_t max_samples, int32_t max_depth, void* d_out_rgb, void* d_out_rgba8,
+                          void* stream_v)
+{
+    if (!c) return PT_E_INVALID;
+    int rc;
+    if ((rc = check_ray_image_args(c, "pt_render_rays_device", d_rays, W, H, max_samples, max_depth, d_out_rgb, true))) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t stream = stream_v ? (hipStream_t)stream_v : c->stream;
+    // the records are the caller's and unknown here: the slab form that holds at any distance, unless the option chooses
+    return async_call(c, stream, [&] { return rays_image_device(c, d_rays, INFINITY, W, H, max_samples, max_depth, d_out_rgb, d_out_rgba8, stream); });
+}
+
+int pt_render_rays(pt_ctx* c, const pt_ray_gen* rays, int32_t W, int32_t H, int32_t max_samples, int32_t max_depth, float* out_rgb, uint32_t* out_rgba8)
+{
+    if (!c) return PT_E_INVALID;
+    int rc;
+    if ((rc = check_ray_image_args(c, "pt_render_rays", rays, W, H, max_samples, max_depth, out_rgb, false))) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t npx = (size_t)W * H;
+    float far_o = 0.0f;
+    for (size_t i = 0; i < npx; ++i)
+        for (int a = 0; a < 3; ++a) far_o = std::max(far_o, std::fabs(rays[i].org[a]));
+    return blocking_call(c, [&]() -> int {
+        int rc;
+        if ((rc = ensure(c, c->d_out, npx * 12)) || (rc = ensure(c, c->d_ray_image, npx * sizeof(pt_ray_gen)))) return rc;
+        if (out_rgba8 && (rc = ensure(c, c->d_out8, npx * 4))) return rc;
+        HIP_TRY(c, hipMemcpyAsync(c->d_ray_image.p, rays, npx * sizeof(pt_ray_gen), hipMemcpyHostToDevice, c->stream));
+        if ((rc = rays_image_device(c, c->d_ray_image.p, far_o, W, H, max_samples, max_depth, c->d_out.p, out_rgba8 ? c->d_out8.p : nullptr, c->stream))) return rc;
+        return read_back(c, true, out_rgb, out_rgba8, npx);
     });
 }
 

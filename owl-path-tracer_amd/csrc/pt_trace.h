@@ -565,6 +565,27 @@ __device__ __forceinline__ void gen_camera_ray_from(const PtKernelParams& P, con
     ps.retries = 0;
 }
 
+// The ray of the next sample of pixel (px, py) from the caller's ray image (pt_render_rays; include/mi355pt.h, pt_ray_gen): the record of
+// the pixel at table + 16 * (px + W * py) floats as four 16-byte loads {org, -}, {dir, -}, {du, -}, {dv, -} (the fourth floats are loaded
+// and not used), dir_s = normalize((dir + du * rx) + dv * ry).  The same two draws in the same order and the same resets as gen_camera_ray:
+// only the ray itself differs.  The ray-image instances (pt_kernel_rayimage.hip) call it once per sample: the record is not kept.
+__device__ __forceinline__ void gen_ray_from(const PtKernelParams& P, const float PT_AS1* table, int px, int py, PathState& ps)
+{
+    float rx = rng_next(ps.rng);
+    float ry = rng_next(ps.rng);
+    const size_t rb = ((size_t)(uint32_t)px + (size_t)(uint32_t)P.width * (size_t)(uint32_t)py) * 64; // < 2^31 pixels: below 2^37 bytes
+    const f32x4 r0 = *(const f32x4 PT_AS1*)((const char PT_AS1*)table + rb);
+    const f32x4 r1 = *(const f32x4 PT_AS1*)((const char PT_AS1*)table + rb + 16);
+    const f32x4 r2 = *(const f32x4 PT_AS1*)((const char PT_AS1*)table + rb + 32);
+    const f32x4 r3 = *(const f32x4 PT_AS1*)((const char PT_AS1*)table + rb + 48);
+    ps.org = V(r0.x, r0.y, r0.z);
+    ps.dir = normalize((V(r1.x, r1.y, r1.z) + V(r2.x, r2.y, r2.z) * rx) + V(r3.x, r3.y, r3.z) * ry);
+    ps.throughput = vs(1.0f);
+    ps.depth = 0;
+    ps.lobe = kLobeNone;
+    ps.retries = 0;
+}
+
 template <bool COUNT>
 __device__ __forceinline__ void flush_counters(const PtKernelParams& P, const Counters& cn)
 {

@@ -162,4 +162,6 @@ struct PtKernelParams {
     // image, rng_state and accum are those of the virtual image, materials holds one table per frame (n_materials * PT_MAT_STRIDE floats each)
     int32_t batch_frames;
     const float* batch_cams;   // camera of frame f: 12 floats at batch_cams + 12 * f
+                               // (ray images, pt_render_rays: batch_frames = 0 and this is the table of W * H pt_ray_gen records, read by the
+                               // instances of pt_kernel_rayimage.hip only - no batch form exists, so the two uses never meet)
 };

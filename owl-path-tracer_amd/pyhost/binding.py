@@ -132,11 +132,16 @@ EXPORTS = ["pt_create", "pt_destroy", "pt_last_error", "pt_abi_version", "pt_upl
            "pt_accum_variance", "pt_debug_accum_variance_host", "pt_accum_denoise", "pt_accum_denoise_device",
            "pt_accum_reproject_default_params", "pt_accum_reproject", "pt_accum_reproject_device", "pt_debug_accum_reproject_host",
            "pt_upsample_default_params", "pt_upsample", "pt_upsample_device", "pt_debug_upsample_host",
-           "pt_trace_closest", "pt_trace_closest_device", "pt_trace_occluded", "pt_trace_occluded_device", "pt_debug_trace_rays_host", "pt_prim_to_mesh"]
+           "pt_trace_closest", "pt_trace_closest_device", "pt_trace_occluded", "pt_trace_occluded_device", "pt_debug_trace_rays_host", "pt_prim_to_mesh",
+           "pt_render_rays", "pt_render_rays_device"]
 # pt_ray / pt_ray_hit (include/mi355pt.h "ray queries"): 32 and 16 bytes
 RAY_DTYPE = np.dtype([("org", "<f4", (3,)), ("tmax", "<f4"), ("dir", "<f4", (3,)), ("unused", "<f4")])
 HIT_DTYPE = np.dtype([("t", "<f4"), ("u", "<f4"), ("v", "<f4"), ("prim", "<i4")])
 assert RAY_DTYPE.itemsize == 32 and HIT_DTYPE.itemsize == 16
+# pt_ray_gen (include/mi355pt.h "ray images"): 64 bytes; pyhost/ray_image.py builds tables of these
+RAY_GEN_DTYPE = np.dtype([("org", "<f4", (3,)), ("reserved0", "<f4"), ("dir", "<f4", (3,)), ("reserved1", "<f4"),
+                          ("du", "<f4", (3,)), ("reserved2", "<f4"), ("dv", "<f4", (3,)), ("reserved3", "<f4")])
+assert RAY_GEN_DTYPE.itemsize == 64
 PT_DENOISE_DEMODULATE = 1
 PT_UPSAMPLE_DEMODULATE = 1
 PT_TREE_DEVICE = 16  # pt_debug_export_tree: ORed into `which`, the array as HBM holds it
@@ -291,6 +296,8 @@ def lib():
     L.pt_debug_trace_rays_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
     L.pt_debug_trace_rays_host.restype = C.c_int64
     L.pt_prim_to_mesh.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    L.pt_render_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, fp, C.POINTER(C.c_uint32)]
+    L.pt_render_rays_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = L
     return L
 
@@ -1052,6 +1059,26 @@ class Context:
         self._check(lib().pt_render_device(self._h, C.byref(cam), W, H, spp, max_depth, C.c_void_p(d_out_rgb),
                                            C.c_void_p(d_out_rgba8) if d_out_rgba8 else None, C.c_void_p(stream) if stream else None),
                     "pt_render_device")
+
+    def render_rays(self, rays, W, H, spp, max_depth, want_rgba8=False):
+        """pt_render_rays: path-traced radiance along a ray image - W * H RAY_GEN_DTYPE records, the record of pixel (x, y) at x + W * y
+        (pyhost/ray_image.py builds them).  Returns what render() returns: (H, W, 3) float32 in framebuffer order (row H - 1 - y) and,
+        with want_rgba8, (H, W) uint32."""
+        r = np.ascontiguousarray(rays, RAY_GEN_DTYPE).reshape(-1)
+        if r.shape[0] != W * H:
+            raise PtError("render_rays: %d records for a %dx%d ray image" % (r.shape[0], W, H))
+        rgb = np.empty((H, W, 3), np.float32)
+        rgba = np.empty((H, W), np.uint32) if want_rgba8 else None
+        self._check(lib().pt_render_rays(self._h, r.ctypes.data_as(C.c_void_p), W, H, spp, max_depth, rgb.ctypes.data_as(C.POINTER(C.c_float)),
+                                         rgba.ctypes.data_as(C.POINTER(C.c_uint32)) if rgba is not None else None), "pt_render_rays")
+        return rgb, rgba
+
+    def render_rays_device(self, d_rays, W, H, spp, max_depth, d_out_rgb, d_out_rgba8=None, stream=None):
+        """pt_render_rays_device: asynchronous, W * H pt_ray_gen records at the device pointer d_rays (16-byte aligned; the caller's, valid and
+        unchanged until the work has completed), the frame left in HBM as render_device leaves it.  stream and ordering as render_device."""
+        self._check(lib().pt_render_rays_device(self._h, C.c_void_p(d_rays), W, H, spp, max_depth, C.c_void_p(d_out_rgb),
+                                                C.c_void_p(d_out_rgba8) if d_out_rgba8 else None, C.c_void_p(stream) if stream else None),
+                    "pt_render_rays_device")
 
     def synchronize(self):
         self._check(lib().pt_synchronize(self._h), "pt_synchronize")
