@@ -21,8 +21,15 @@
 //    has at most one ray in flight.  Work items are (pixel, sample chunk) tickets; the host orders the pixel queue by a
 //    cost pre-pass (pt_render.cpp, "schedule").
 //
-//  (The simple persistent lane-per-pixel form, option kernel=1, and the validation kernel live in pt_kernel_aux.hip; the queue sort,
-//  the tier plan and the small helper kernels in pt_schedule.hip; the device code all of them share in pt_trace.h.)
+// FILE MAP.  This file is the wavefront render kernel and nothing else: tickets, WaveCtx, shade_pass, traverse_groups, the kernel, its
+// launcher and its geometry function.  It is the translation unit of the single-frame build; pt_kernel_batch.hip, pt_kernel_wt.hip and
+// pt_kernel_rayimage.hip include it under a mode (PT_BATCH, PT_WATERTIGHT, PT_RAYGEN: the same kernel).  Every other kernel family has a
+// header of its own around the device code all of them share (pt_trace.h: slab and triangle tests, node_step, node4_step, shade_hit,
+// camera rays) and includes neither this file nor another family:
+//   pt_probes.h        the ray probes (tests only), included at the end of this file by the single-frame and the watertight build
+//   pt_aov.h           what the guide kernels share; pt_aov_first.h / pt_aov_follow.h: the first-hit and the follow kernels (pt_kernel_aov*.hip)
+//   pt_rays_kernels.h  the ray queries (pt_kernel_rays.hip, pt_kernel_rays_wt.hip)
+//   pt_kernel_aux.hip  the lane-per-pixel form (option kernel=1) and the validation kernel; pt_schedule.hip: queue sort, tier plan, helpers
 //
 // The traversal stack is stack[level][lane] in LDS: bank = lane % 32 whatever the level, so the stack itself is conflict-free (the LDS
 // bank conflicts rocprof reports - a third of the LDS cycles, at ~6 % LDS utilisation - come from the slot-indexed state arrays,
@@ -44,63 +51,30 @@
 #include "pt_tiers.h"
 #include "pt_trace.h"
 #ifndef PT_BATCH
-#define PT_BATCH 0
-#endif
-#ifndef PT_WATERTIGHT
-#define PT_WATERTIGHT 0
-#endif
-#ifndef PT_AOV
-#define PT_AOV 0 // 1: pt_kernel_aov.hip / pt_kernel_aov_wt.hip - the device functions of this file around the guide kernels alone ("guide pass", at the end)
-                 // 2: pt_kernel_aov_follow.hip / pt_kernel_aov_follow_wt.hip - the same around the follow kernels ("guide pass, follow mode");
-                 //    with PT_BATCH = 1 (pt_kernel_aov_follow_batch.hip) around their batch instances (pt_render_aov_batch)
-                 // 3: pt_kernel_rays.hip / pt_kernel_rays_wt.hip - the same around the ray kernels of pt_trace_closest / pt_trace_occluded ("ray queries")
-#endif
-#if PT_AOV == 3 && PT_BATCH
-#error "the ray queries have no batch form"
-#endif
-#if PT_AOV == 1 && PT_BATCH
-#error "the first-hit guide pass has no batch form (pt_render_aov_batch runs the follow kernels; max_follow = 0 gives the first-hit guides)"
+#define PT_BATCH 0 // (PT_WATERTIGHT: pt_trace.h)
 #endif
 #ifndef PT_RAYGEN
 #define PT_RAYGEN 0 // 1: pt_kernel_rayimage.hip - the wavefront kernel with the camera replaced by a per-pixel ray record (pt_render_rays, "RAY IMAGE BUILD" above)
 #endif
-#if PT_RAYGEN && (PT_BATCH || PT_WATERTIGHT || PT_AOV)
-#error "the ray-image build has no batch, watertight or guide instances"
+#if PT_BATCH + PT_WATERTIGHT + PT_RAYGEN > 1
+#error "the batch, watertight and ray-image builds do not combine"
 #endif
+// The kernel, its launcher and its geometry function under the unit's mode: the names pt_launch.h declares and pt_render.cpp calls
+// (the kernels are templates; the batch build spells its two functions out where they are defined)
 #if PT_WATERTIGHT
-#if PT_BATCH
-#error "the watertight build has no batch instances"
-#endif
-// every global name of this file gets a twin of its own in the watertight build (kernels are templates or strong symbols)
 #define PT_RENDER_KERNEL pt_render_wt_kernel
-#define pt_launch_render pt_launch_render_wt
-#define pt_kernel_geometry pt_wt_kernel_geometry
-#define pt_probe_quad_kernel pt_probe_quad_wt_kernel
-#define pt_probe_group_kernel pt_probe_group_wt_kernel
-#define pt_launch_probe pt_launch_probe_wt
-#define pt_probe_lds_stack pt_probe_lds_stack_wt
-#define pt_probe_group_lds_bytes pt_probe_group_lds_bytes_wt
-#define pt_probe_group_state_words pt_probe_group_state_words_wt
-#define pt_aov_kernel pt_aov_wt_kernel
-#define pt_launch_aov pt_launch_aov_wt
-#define pt_aov_geometry pt_aov_geometry_wt
-#define pt_aov_follow_kernel pt_aov_follow_wt_kernel
-#define pt_launch_aov_follow pt_launch_aov_follow_wt
-#define pt_aov_follow_geometry pt_aov_follow_geometry_wt
-#define pt_rays_kernel pt_rays_wt_kernel
-#define pt_launch_rays pt_launch_rays_wt
-#define pt_rays_geometry pt_rays_geometry_wt
+#define PT_RENDER_LAUNCH pt_launch_render_wt
+#define PT_RENDER_GEOMETRY pt_wt_kernel_geometry
 #elif PT_RAYGEN
 #define PT_RENDER_KERNEL pt_render_rayimage_kernel
-#define pt_launch_render pt_launch_render_rayimage
-#define pt_kernel_geometry pt_rayimage_kernel_geometry
+#define PT_RENDER_LAUNCH pt_launch_render_rayimage
+#define PT_RENDER_GEOMETRY pt_rayimage_kernel_geometry
 #elif PT_BATCH
 #define PT_RENDER_KERNEL pt_render_batch_kernel
-#define pt_aov_follow_kernel pt_aov_follow_batch_kernel
-#define pt_launch_aov_follow pt_launch_aov_follow_batch
-#define pt_aov_follow_geometry pt_aov_follow_batch_geometry
 #else
 #define PT_RENDER_KERNEL pt_render_wave_kernel
+#define PT_RENDER_LAUNCH pt_launch_render
+#define PT_RENDER_GEOMETRY pt_kernel_geometry
 #endif
 #ifndef PT_WAVES_PER_EU
 #define PT_WAVES_PER_EU 4
@@ -141,113 +115,7 @@
 #define PT_RETIRE_MIN 16   // finished lanes that trigger a retire/refill pass (8..24 swept: +-1 %)
 #endif
 
-
 namespace {
-
-// Quad-node step (PtNode4, pt_types.h): the four grandchild boxes of a binary node in one 128-byte record - one cache line and
-// one memory round trip per TWO levels of the binary tree.  Slab test as in node_step, two packed pairs; the lane continues with
-// the nearest hit child and pushes the other hit children (in slot order; any visiting order gives the same closest hit).
-// The lane reads its own record with 7 x global_load_dwordx4 = 7 vL1D accesses per lane and step, at 32-bit offsets from the wave-uniform
-// base (the host keeps the quad nodes below 4 GiB: pt_render.cpp).  (Two validated experiments that did not pay - whole-line cooperative
-// fetches through an LDS staging area, 64-byte records with 8-bit planes - live in variants/.)
-template <int STRIDE, int LDS_ENTRIES, bool CENSUS = false>
-__device__ __forceinline__ void node4_step(const PtNode4* __restrict__ nodes4, uint32_t* stack, uint32_t PT_AS1* ovf, v3 o, v3 inv, float tbest, int& cur, int& sp,
-                                           const bool exact, uint32_t* n_nohit = nullptr, uint32_t* n_beyond = nullptr)
-{
-    bool crossed = false; // CENSUS: the ray crosses some slot's box when the bound of the best hit is ignored
-    // Octant order: on each axis the ray enters a slab through the plane row that faces it - lo for inv > 0, hi for inv < 0 - and leaves
-    // through the other one, so the step fetches the rows as (entry, exit) pairs and needs no per-axis min / max.  Both slab forms below are
-    // monotone in the plane for a fixed inv (correctly rounded operations of a monotone function), so for lo <= hi the entry distance IS
-    // the minimum of the two and the exit distance the maximum, bit for bit; every non-empty slot has finite lo <= hi (the host and device
-    // builders pad finite boxes; pt_debug_quad_info checks it) and an empty slot {+inf, +inf} still misses (entry +inf or exit -inf).
-    // The sign bit picks the row: ray_inv never returns 0, NaN or an infinity, and d = -0 gives -PT_INV_MAX, whose sign matches.
-    const uint32_t ex = (uint32_t)(__float_as_int(inv.x) >> 31) & 48u; // 0 or 48: byte offset of the entry row from the lo row
-    const uint32_t ey = (uint32_t)(__float_as_int(inv.y) >> 31) & 48u;
-    const uint32_t ez = (uint32_t)(__float_as_int(inv.z) >> 31) & 48u;
-    const uint32_t rec = (uint32_t)cur * (uint32_t)sizeof(PtNode4);
-    const f32x4 nx4 = ldg4u(nodes4, rec + ex, 0), ny4 = ldg4u(nodes4, rec + ey, 16), nz4 = ldg4u(nodes4, rec + ez, 32);
-    const f32x4 fx4 = ldg4u(nodes4, rec + (ex ^ 48u), 0), fy4 = ldg4u(nodes4, rec + (ey ^ 48u), 16), fz4 = ldg4u(nodes4, rec + (ez ^ 48u), 32);
-    const f32x4 cf = ldg4u(nodes4, rec, 96);
-    // Slab distances (round 4): fma(plane, 1/d, -(o/d)) - one packed fma per pair of planes instead of a subtraction and a multiplication
-    // (24 of the step's ~150 VALU operations; C4 492 -> 484-486 ms, C3 149 -> 146).  Against (plane - o) * (1/d) the distance is off by
-    // |o/d| 2^-24, i.e. the plane seems displaced by |o| 2^-24 in space: rays start on surfaces or at the camera, the boxes are padded by
-    // 1e-5 x the scene extent, and the host launches the instances with the subtracting form (`exact`) for a camera farther than 42
-    // extents from the origin (pt_render.cpp) - the test stays conservative with respect to every hit the triangle test can report, and
-    // the triangle test decides the image.  The reciprocals are finite (ray_inv clamps them: a direction component of exactly 0 would
-    // otherwise give -inf or NaN here depending on the signs of plane and origin, and cull boxes the ray runs through).
-    // (Both forms behind a run-time switch in ONE instance cost 4 %: C4 486 -> 508 ms, profiles/r04_notes.md.)
-    const f32x2 ox = {o.x, o.x}, oy = {o.y, o.y}, oz = {o.z, o.z}, ix = {inv.x, inv.x}, iy = {inv.y, inv.y}, iz = {inv.z, inv.z};
-    const float nx = -(o.x * inv.x), ny = -(o.y * inv.y), nz = -(o.z * inv.z);
-    const f32x2 nox = {nx, nx}, noy = {ny, ny}, noz = {nz, nz};
-    const f32x2 pad = {1.0000004f, 1.0000004f};
-    // Keys of the nearest-child choice: the entry distance's bits for a hit slot (a positive float: the bits order as unsigned integers),
-    // all ones for a miss - integer min / max and compares instead of selects of booleans.
-    const uint32_t kMiss = 0xffffffffu;
-    uint32_t key[4];
-#pragma unroll
-    for (int p = 0; p < 2; ++p) { // slots {0, 1} and {2, 3}
-        const f32x2 enx = p ? (f32x2){nx4.z, nx4.w} : (f32x2){nx4.x, nx4.y}, eny = p ? (f32x2){ny4.z, ny4.w} : (f32x2){ny4.x, ny4.y};
-        const f32x2 enz = p ? (f32x2){nz4.z, nz4.w} : (f32x2){nz4.x, nz4.y}, exx = p ? (f32x2){fx4.z, fx4.w} : (f32x2){fx4.x, fx4.y};
-        const f32x2 exy = p ? (f32x2){fy4.z, fy4.w} : (f32x2){fy4.x, fy4.y}, exz = p ? (f32x2){fz4.z, fz4.w} : (f32x2){fz4.x, fz4.y};
-        f32x2 tnx, tfx, tny, tfy, tnz, tfz;
-        if (exact) { // a compile-time constant in the product instances (see pt_render_wave_kernel: EXACT)
-            tnx = (enx - ox) * ix; tfx = (exx - ox) * ix;
-            tny = (eny - oy) * iy; tfy = (exy - oy) * iy;
-            tnz = (enz - oz) * iz; tfz = (exz - oz) * iz;
-        } else {
-            tnx = __builtin_elementwise_fma(enx, ix, nox); tfx = __builtin_elementwise_fma(exx, ix, nox);
-            tny = __builtin_elementwise_fma(eny, iy, noy); tfy = __builtin_elementwise_fma(exy, iy, noy);
-            tnz = __builtin_elementwise_fma(enz, iz, noz); tfz = __builtin_elementwise_fma(exz, iz, noz);
-        }
-        const float ta = fmax_hw(fmax_hw(tnx.x, tny.x), fmax_hw(tnz.x, kTMin));
-        const float tb = fmax_hw(fmax_hw(tnx.y, tny.y), fmax_hw(tnz.y, kTMin));
-        f32x2 tf = {fmin_hw(fmin_hw(tfx.x, tfy.x), fmin_hw(tfz.x, tbest)), fmin_hw(fmin_hw(tfx.y, tfy.y), fmin_hw(tfz.y, tbest))};
-        tf = tf * pad;
-        key[2 * p] = ta <= tf.x ? __float_as_uint(ta) : kMiss;
-        key[2 * p + 1] = tb <= tf.y ? __float_as_uint(tb) : kMiss;
-        if (CENSUS) { // instrumented instance: would the slot be hit without the bound of the best hit so far?
-            const float fa = fmin_hw(fmin_hw(tfx.x, tfy.x), tfz.x) * 1.0000004f;
-            const float fb = fmin_hw(fmin_hw(tfx.y, tfy.y), tfz.y) * 1.0000004f;
-            crossed = crossed || ta <= fa || tb <= fb;
-        }
-    }
-    const int r0 = __float_as_int(cf.x), r1 = __float_as_int(cf.y), r2 = __float_as_int(cf.z), r3 = __float_as_int(cf.w);
-    const bool b01 = key[1] < key[0], b23 = key[3] < key[2]; // the pair's second slot is the nearer one
-    const uint32_t m01 = b01 ? key[1] : key[0], M01 = b01 ? key[0] : key[1], m23 = b23 ? key[3] : key[2], M23 = b23 ? key[2] : key[3];
-    const int n01 = b01 ? r1 : r0, f01 = b01 ? r0 : r1, n23 = b23 ? r3 : r2, f23 = b23 ? r2 : r3; // nearer / farther child of each pair
-    const bool in_b = m23 < m01; // the nearest hit is in slot pair {2, 3}
-    const int nearc = in_b ? n23 : n01;
-    const bool any = (in_b ? m23 : m01) != kMiss;
-    if (CENSUS) { // steps that enter nothing, and of those the ones where the ray does cross a box: the node lies beyond the best hit
-        *n_nohit += any ? 0u : 1u;
-        *n_beyond += (!any && crossed) ? 1u : 0u;
-    }
-    // push order: the two slots of the OTHER pair first, the farther one first, then the nearest's sibling (popped first): siblings share a
-    // parent box, so the sibling is usually the next nearest.  Three pushes at most; a pushed key is a hit.
-    const int x1 = in_b ? f01 : f23, x2 = in_b ? n01 : n23, x3 = in_b ? f23 : f01;
-    const bool h1 = (in_b ? M01 : M23) != kMiss, h2 = (in_b ? m01 : m23) != kMiss, h3 = (in_b ? M23 : M01) != kMiss;
-    // (strictly by entry distance - the partner inserted where its distance puts it - costs 12 more instructions per step and saves
-    // 0.1 % of the triangle tests: C4 497 -> 515 ms, C5 3 211 -> 3 353, profiles/r04_notes.md)
-    if (LDS_ENTRIES == 0x7fffffff) {
-        // common instance (the caller made sure sp + 3 stays inside the LDS part): store above the top whether or not the entry is
-        // pushed - the slot is free either way - and advance sp by the predicate; no branches
-        stack[sp * STRIDE] = (uint32_t)x1; sp += h1 ? 1 : 0;
-        stack[sp * STRIDE] = (uint32_t)x2; sp += h2 ? 1 : 0;
-        stack[sp * STRIDE] = (uint32_t)x3; sp += h3 ? 1 : 0;
-    } else {
-        if (h1) { stack_push<STRIDE, LDS_ENTRIES>(stack, ovf, sp, (uint32_t)x1); ++sp; }
-        if (h2) { stack_push<STRIDE, LDS_ENTRIES>(stack, ovf, sp, (uint32_t)x2); ++sp; }
-        if (h3) { stack_push<STRIDE, LDS_ENTRIES>(stack, ovf, sp, (uint32_t)x3); ++sp; }
-    }
-    if (any) {
-        cur = nearc;
-    } else if (sp > 0) {
-        --sp;
-        cur = (int)stack_pop<STRIDE, LDS_ENTRIES>(stack, ovf, sp);
-    } else {
-        cur = PT_DONE;
-    }
-}
 
 // ---- (pixel, spp-chunk) work items of the wavefront kernel ----------------------------------------------------------------
 // Ring schedule: the frame is cut into n_chunks chunks per pixel (chunk_spp samples each, shrinking at the end).  A slot renders
@@ -444,9 +312,6 @@ __device__ __forceinline__ void finish_chunk(const PtKernelParams& P, uint32_t c
 // all L2 misses, at 70 % of the chip's measured random-64-B-gather rate (profiles/r01_fetch_calibration.md); with a full-depth
 // LDS stack and lstate in LDS only 8 waves fit a CU.  The short stack pays for keeping the state on chip.
 
-#ifndef PT_LDS_STACK
-#define PT_LDS_STACK 12
-#endif
 enum { L_DIRX = 0, L_DIRY, L_DIRZ, L_AX, L_AY, L_AZ, L_NFIELDS };
 // S_RNG holds the ticket while the slot waits for its work item (S_PIX == PT_FRESH); S_QKC = chunk index (cost pre-pass: clock at the start of the pixel)
 enum { S_PIX = 0, S_RNG, S_PACK, S_COLX, S_COLY, S_COLZ, S_THRX, S_THRY, S_THRZ, S_QKC, S_NFIELDS };
@@ -1312,9 +1177,8 @@ __global__ void __launch_bounds__(PT_WAVE, WAVES) PT_RENDER_KERNEL(const PtKerne
 
 // ---- launchers (called from pt_render.cpp) --------------------------------------------------------------------
 
-#if !PT_AOV // (the guide builds take the device functions above and instantiate none of the render kernels)
 // d_params: device copy of *p (wavefront kernel reads its parameters from HBM; the caller keeps it stream-ordered)
-// (the batch build defines the same two functions for its own instances: pt_launch_render_batch / pt_batch_kernel_geometry, variants 2 and 3 only)
+// (the batch build spells the names of its two functions out: pt_launch_render_batch / pt_batch_kernel_geometry, variants 2 and 3 only)
 #if PT_BATCH
 extern "C" hipError_t pt_launch_render_batch(const PtKernelParams* p, const PtKernelParams* d_params, int variant, int grid, size_t lds_bytes,
                                              hipStream_t stream, int count)
@@ -1322,7 +1186,7 @@ extern "C" hipError_t pt_launch_render_batch(const PtKernelParams* p, const PtKe
     if (variant != 2 && variant != 3) return hipErrorInvalidValue; // the lane-per-pixel kernel has no batch form
     if (p->batch_frames < 1 || p->batch_cams == nullptr) return hipErrorInvalidValue;
 #else
-extern "C" hipError_t pt_launch_render(const PtKernelParams* p, const PtKernelParams* d_params, int variant, int grid, size_t lds_bytes,
+extern "C" hipError_t PT_RENDER_LAUNCH(const PtKernelParams* p, const PtKernelParams* d_params, int variant, int grid, size_t lds_bytes,
                                        hipStream_t stream, int count)
 {
 #if PT_WATERTIGHT
@@ -1351,7 +1215,7 @@ extern "C" hipError_t pt_batch_kernel_geometry(int variant, int count, int stack
 {
     if (variant != 2 && variant != 3) return hipErrorInvalidValue;
 #else
-extern "C" hipError_t pt_kernel_geometry(int variant, int count, int stack_entries, int group_entries, int want_ns, int exact, PtGeometry* g)
+extern "C" hipError_t PT_RENDER_GEOMETRY(int variant, int count, int stack_entries, int group_entries, int want_ns, int exact, PtGeometry* g)
 {
 #if PT_WATERTIGHT || PT_RAYGEN
     if (variant != 2 && variant != 3) return hipErrorInvalidValue;
@@ -1379,760 +1243,6 @@ extern "C" hipError_t pt_kernel_geometry(int variant, int count, int stack_entri
     return hipOccupancyMaxActiveBlocksPerMultiprocessor(&g->max_blocks_per_cu, fn, g->block, g->lds_bytes);
 }
 
-#endif // !PT_AOV
-
-#if !PT_BATCH && !PT_AOV && !PT_RAYGEN // (the probes belong to the single-frame build)
-// =====================================================================================================================
-// Ray probes (tests only: pt_debug_eval ops PT_PROBE_*, pt_launch.h; tests/test_gpu_ray_probes.py)
-// =====================================================================================================================
-// Caller-chosen rays through the walks of pt_render_wave_kernel: the kernels below own no traversal arithmetic, they call ray_inv,
-// node4_step, leaf_test and traverse_groups - the functions above and in pt_trace.h - the way the render kernel does, and write the
-// closest hit out per ray.  They live in this file because those functions do (anonymous namespace: one copy per translation unit);
-// they are separate kernels, so the product instances' code does not change with them.
-namespace {
-__device__ __forceinline__ void probe_store(float* y, bool hit, float t, float u, float v, int id, float aux)
-{
-    y[0] = hit ? 1.0f : 0.0f; y[1] = t; y[2] = u; y[3] = v; y[4] = __int_as_float(hit ? id : -1); y[5] = aux;
-}
-} // namespace
-
-// Quad walk, one ray per lane, one wave per workgroup (stack[level * 64 + lane] as in the render kernel).  LDS_ENTRIES = 0x7fffffff: the common
-// instance of the step (whole stack in LDS; `cap` levels are allocated: the stack bound + the three stores above the top);
-// LDS_ENTRIES = PT_LDS_STACK: the overflow-aware instance, levels >= PT_LDS_STACK in the wave's HBM columns.  EXACT as in the render kernel.
-template <int LDS_ENTRIES, bool EXACT>
-__global__ void __launch_bounds__(PT_WAVE) pt_probe_quad_kernel(const PtKernelParams P, const float* __restrict__ in, int in_stride, float* __restrict__ out, int out_stride,
-                                                                long long n, uint32_t* ovf_area, int cap)
-{
-    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
-    const int lane = threadIdx.x;
-    uint32_t* stack = lds + lane;
-    const int ovf_levels = cap > P.lds_levels ? cap - P.lds_levels : 0;
-    uint32_t PT_AS1* ovf = gp(ovf_area) + (size_t)blockIdx.x * ((size_t)ovf_levels * PT_WAVE) + lane;
-    const PtNode4* __restrict__ nodes4 = P.nodes4;
-    const PtTri* __restrict__ tris = P.tris;
-    for (long long i = (long long)blockIdx.x * PT_WAVE + lane; i < n; i += (long long)gridDim.x * PT_WAVE) {
-        const float* x = in + i * in_stride;
-        const v3 o = V(x[0], x[1], x[2]), d = V(x[3], x[4], x[5]);
-        const v3 inv = ray_inv(d);
-        Hit h;
-        h.t = kTMax; h.u = 0.0f; h.v = 0.0f; h.id = 0x7fffffff; h.slot = -1;
-        int cur = P.root, sp = 0, max_sp = 0, steps = 0;
-        while (cur != PT_DONE) {
-            // bounded whatever the tree holds: a ray needs a few thousand steps, and the stack bound comes from the host (3 * depth4 + 1)
-            if (++steps > (1 << 20) || sp + 3 > cap) {
-                gp(P.error_flag)[0] = 1u;
-                break;
-            }
-            if (cur >= 0) {
-                node4_step<PT_WAVE, LDS_ENTRIES>(nodes4, stack, ovf, o, inv, h.t, cur, sp, EXACT);
-                max_sp = sp > max_sp ? sp : max_sp;
-            } else {
-                const uint32_t code = ~(uint32_t)cur;
-                leaf_test(tris, (int)(code >> 3), (int)(code & 7u), o, d, h);
-                if (sp > 0) {
-                    --sp;
-                    cur = (int)stack_pop<PT_WAVE, LDS_ENTRIES>(stack, ovf, sp);
-                } else {
-                    cur = PT_DONE;
-                }
-            }
-        }
-        probe_store(out + i * out_stride, h.slot >= 0, h.t, h.u, h.v, h.id, (float)max_sp);
-    }
-}
-
-// Group walk: a minimal wave context around traverse_groups.  The wave owns rays [first, first + per_wave) and ns path slots; its
-// "shading pass" writes the queued hits and misses out and gives each of those slots the wave's next ray, exactly where shade_pass would
-// emit the continuation ray.  The batch thresholds are small (8 / 4 / 4), so pick_pass ends most group phases with groups still walking:
-// they are parked in HBM and resumed by the next phase.  lstate is one word per slot here: the ray the slot carries (PT_FRESH: none).
-__global__ void __launch_bounds__(PT_WAVE) pt_probe_group_kernel(const PtKernelParams P, const float* __restrict__ in, int in_stride, float* __restrict__ out,
-                                                                 int out_stride, long long n, int per_wave, uint32_t* park_area)
-{
-    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
-    const int lane = threadIdx.x;
-    const int ns = P.ns;
-    uint32_t* lray = lds + P.lds_levels * PT_WAVE;
-    uint32_t* lidx = lray + L_NFIELDS * ns;
-    uint32_t PT_AS1* park = gp(park_area) + (size_t)blockIdx.x * (K_NFIELDS * PT_WAVE) + lane;
-    WaveCtx w;
-    w.lray = lray;
-    w.lstate = lidx;
-    w.ns = ns;
-    w.rayq = reinterpret_cast<uint8_t*>(lidx + ns);
-    w.hitq = w.rayq + ns;
-    w.missq = w.hitq + ns;
-    w.tier.counter = nullptr; w.tier.q0 = w.tier.count = 0u; w.tier.express = false;
-    w.miss_blocked = false;
-    w.topup_min = 0; w.topup = false;
-    w.min_batch = 4; w.ray_low = 4; w.full_batch = 8;
-    w.adapt = 0;
-    w.n_run = 0;
-    for (int i = lane; i < ns; i += PT_WAVE) {
-        w.missq[i] = (uint8_t)i; // as in the render kernel: every slot starts fresh, in the miss queue
-        lidx[i] = PT_FRESH;
-    }
-    w.ray_head = 0; w.ray_count = 0; w.hit_head = 0; w.hit_count = 0; w.miss_head = 0; w.miss_count = ns; w.n_dead = 0;
-    const long long first = (long long)blockIdx.x * per_wave;
-    const long long end = first + per_wave < n ? first + per_wave : n;
-    long long next = first;
-    int n_parked = 0, n_park_phases = 0, rounds = 0;
-    Counters cn;
-#define LF(f, s) lray[(f) * ns + (s)]
-#define LFF(f, s) __uint_as_float(lray[(f) * ns + (s)])
-    while (w.n_dead < ns) {
-        if (++rounds > (1 << 20)) { // every round retires or walks at least one ray
-            if (lane == 0) gp(P.error_flag)[0] = 1u;
-            break;
-        }
-        // ---- "shading pass": all queued hits, then all queued misses (ns <= 64: one pass takes both queues whole) ----
-        const int n1 = w.hit_count, n2 = w.miss_count, np = n1 + n2;
-        if (np > 0) {
-            const bool mine = lane < np, is_hit = lane < n1;
-            const int slot = !mine ? 0 : (is_hit ? (int)w.hitq[w.wrap(w.hit_head + lane)] : (int)w.missq[w.wrap(w.miss_head + lane - n1)]);
-            w.hit_head = w.wrap(w.hit_head + n1); w.hit_count = 0;
-            w.miss_head = w.wrap(w.miss_head + n2); w.miss_count = 0;
-            const long long mine_next = next + rank_in(__ballot(mine));
-            bool to_ray = false, died = false;
-            if (mine) {
-                const uint32_t idx = lidx[slot];
-                if (idx != PT_FRESH) {
-                    const int tslot = is_hit ? (int)LF(L_AZ, slot) : -1;
-                    const int id = is_hit ? gp(P.tris)[tslot].id : -1;
-                    probe_store(out + (first + idx) * out_stride, is_hit, 0.0f, is_hit ? LFF(L_AX, slot) : 0.0f, is_hit ? LFF(L_AY, slot) : 0.0f, id, (float)n_park_phases);
-                }
-                if (mine_next < end) {
-                    const float* x = in + mine_next * in_stride;
-                    LF(L_AX, slot) = __float_as_uint(x[0]); LF(L_AY, slot) = __float_as_uint(x[1]); LF(L_AZ, slot) = __float_as_uint(x[2]);
-                    LF(L_DIRX, slot) = __float_as_uint(x[3]); LF(L_DIRY, slot) = __float_as_uint(x[4]); LF(L_DIRZ, slot) = __float_as_uint(x[5]);
-                    lidx[slot] = (uint32_t)(mine_next - first);
-                    to_ray = true;
-                } else {
-                    lidx[slot] = PT_FRESH;
-                    died = true;
-                }
-            }
-            const unsigned long long m_ray = __ballot(to_ray);
-            if (to_ray) w.rayq[w.wrap(w.wrap(w.ray_head + w.ray_count) + rank_in(m_ray))] = (uint8_t)slot;
-            w.ray_count += popc64(m_ray);
-            w.n_dead += popc64(__ballot(died));
-            next += np;
-            w.n_run = ns - w.n_dead;
-        }
-        // ---- group phase over the ray queue and the groups the last phase parked ----
-        if (w.ray_count > 0 || n_parked > 0) {
-            n_parked = traverse_groups<false>(P, w, lane, lds, park, n_parked, cn, P.box_exact != 0);
-            n_park_phases += n_parked > 0 ? 1 : 0;
-        }
-    }
-#undef LF
-#undef LFF
-}
-
-extern "C" int pt_probe_lds_stack(void) { return PT_LDS_STACK; }
-extern "C" size_t pt_probe_group_lds_bytes(int lds_levels, int ns)
-{
-    return ((size_t)lds_levels * PT_WAVE + (size_t)(L_NFIELDS + 1) * ns) * 4 + (((size_t)3 * ns + 15) & ~(size_t)15);
-}
-extern "C" size_t pt_probe_group_state_words(void) { return (size_t)K_NFIELDS * PT_WAVE; }
-
-extern "C" hipError_t pt_launch_probe(const PtKernelParams* p, int op, const float* in, int in_stride, float* out, int out_stride, long long n, int grid, size_t lds_bytes,
-                                      uint32_t* scratch, hipStream_t stream)
-{
-    if (grid < 1) grid = 1;
-    const int cap = p->stack_entries + 3;
-    switch (op) {
-    case PT_PROBE_QUAD: hipLaunchKernelGGL((pt_probe_quad_kernel<0x7fffffff, false>), dim3(grid), dim3(PT_WAVE), lds_bytes, stream, *p, in, in_stride, out, out_stride, n, scratch, cap); break;
-    case PT_PROBE_QUAD + 1: hipLaunchKernelGGL((pt_probe_quad_kernel<0x7fffffff, true>), dim3(grid), dim3(PT_WAVE), lds_bytes, stream, *p, in, in_stride, out, out_stride, n, scratch, cap); break;
-    case PT_PROBE_QUAD_OVF: hipLaunchKernelGGL((pt_probe_quad_kernel<PT_LDS_STACK, false>), dim3(grid), dim3(PT_WAVE), lds_bytes, stream, *p, in, in_stride, out, out_stride, n, scratch, cap); break;
-    case PT_PROBE_QUAD_OVF + 1: hipLaunchKernelGGL((pt_probe_quad_kernel<PT_LDS_STACK, true>), dim3(grid), dim3(PT_WAVE), lds_bytes, stream, *p, in, in_stride, out, out_stride, n, scratch, cap); break;
-    case PT_PROBE_GROUP:
-    case PT_PROBE_GROUP + 1: hipLaunchKernelGGL(pt_probe_group_kernel, dim3(grid), dim3(PT_WAVE), lds_bytes, stream, *p, in, in_stride, out, out_stride, n, PT_PROBE_GROUP_RAYS, scratch); break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-}
-#endif // !PT_BATCH && !PT_AOV && !PT_RAYGEN
-
-#if PT_AOV == 1 || PT_AOV == 2
-// =====================================================================================================================
-// Guide pass (pt_render_aov, include/mi355pt.h): first-hit albedo, shading normal, depth and coverage
-// =====================================================================================================================
-// Built as translation units of their own - pt_kernel_aov.hip and, with PT_WATERTIGHT = 1, pt_kernel_aov_wt.hip include this file with
-// PT_AOV = 1 - so that the translation units of the render instances hold the kernels they always held (tests/test_watertight_host.py
-// counts them) and `make asm`, `asm-batch`, `asm-wt` print what they printed.
-// A pass of its own beside the render kernel (whose instances sit at their register budgets: no room for seven more accumulators per
-// slot): one pixel per lane, one wave per workgroup, n_samples camera rays per pixel, each walked to its closest hit and no further.
-// Like the probes above the kernel owns no traversal or shading arithmetic: the ray is gen_camera_ray's, the walk is ray_inv -> node4_step<PT_WAVE,
-// PT_LDS_STACK> (short LDS stack, deeper levels in the wave's HBM columns) -> leaf_test with the probe's loop around them, and what a
-// sample contributes comes from the records, the material row and the texture that shade_hit reads, through the same functions.
-// The lanes of a wave take an 8 x 8 block of pixels (four per 16-pixel shard tile; pt_shard_pixels deals tiles whose side is a multiple
-// of 8, so a block has one owner and a wave that does not own its block has nothing to do): the primary rays of a wave stay together
-// through the upper node steps.  BINARY (no quad nodes: option quad = 0 or a tree too deep for them): closest_hit of pt_trace.h, whole
-// stack in LDS, Moeller-Trumbore only - the watertight build has no such instance.
-#ifndef PT_AOV_WAVES_PER_EU
-#define PT_AOV_WAVES_PER_EU 4 // 128 VGPRs, 16 waves per CU at 3 KB of LDS each
+#if !PT_BATCH && !PT_RAYGEN
+#include "pt_probes.h" // tests only; the single-frame and the watertight build carry them, after WaveCtx, shade_pass and traverse_groups
 #endif
-namespace {
-__device__ __forceinline__ bool finite_(float x) { return !(isinf_(x) || isnan_(x)); }
-// What one sample contributes: tslot < 0 = miss.  The miss branch and the attribute fetch are shade_hit's, expression for expression.
-__device__ __forceinline__ void aov_sample(const PtKernelParams& P, int tslot, float hu, float hv, float ht, v3 dir, v3& albedo, float& alpha, v3& normal, float& depth)
-{
-    if (tslot < 0) {
-        v3 radiance = vs(0.0f);
-        if (P.env_use_map && P.env_map.width > 0) {
-            float tu, tv;
-            uv_on_sphere(dir, tu, tv);
-            radiance = radiance + tex_nearest(gp(P.env_map.texels), P.env_map.width, P.env_map.height, tu, tv);
-        } else if (P.env_use_auto) {
-            radiance = radiance + lerp3(vs(1.0f), V(0.5f, 0.7f, 1.0f), 0.5f * (dir.y + 1.0f));
-        } else {
-            radiance = radiance + V(P.env_color[0], P.env_color[1], P.env_color[2]);
-        }
-        albedo = radiance * P.env_intensity;
-        alpha = 0.0f; normal = vs(0.0f); depth = 0.0f;
-        return;
-    }
-    const f32x4 c = ldg4(P.tris, (size_t)(uint32_t)tslot * sizeof(PtTri) + 32); // {p2.z, id, material, pad}
-    const size_t sb = (size_t)(uint32_t)tslot * sizeof(PtShade);
-    const f32x4 s0 = ldg4(P.shade, sb), s1 = ldg4(P.shade, sb + 16), s2 = ldg4(P.shade, sb + 32), s3 = ldg4(P.shade, sb + 48);
-    const int mi = __float_as_int(c.z);
-    Material mat = material_default();
-    int tex_slot = -1;
-    if (mi >= 0) {
-        const float PT_AS1* mp = gp(P.materials) + mi * PT_MAT_STRIDE;
-        mat = material_load(mp);
-        tex_slot = __float_as_int(mp[17]);
-    }
-    const float bx = hu, by = hv;
-    const float bw = 1.0f - bx - by;
-    const v3 v_n = normalize(interp3(bw, bx, by, V(s0.x, s0.y, s0.z), V(s0.w, s1.x, s1.y), V(s1.z, s1.w, s2.x)));
-    normal = (finite_(v_n.x) && finite_(v_n.y) && finite_(v_n.z)) ? v_n : vs(0.0f); // not flipped towards the viewer; emitters have one too
-    if (mat.emission > 0.0f) {
-        albedo = vs(mat.emission);
-    } else {
-        if (tex_slot >= 0) {
-            const float tu = fma_(by, s3.z, fma_(bx, s3.x, bw * s2.z));
-            const float tv = fma_(by, s3.w, fma_(bx, s3.y, bw * s2.w));
-            const PtTexDesc PT_AS1* tdp = gp(P.textures) + tex_slot;
-            mat.base_color = tex_nearest(gp(tdp->texels), tdp->width, tdp->height, tu, tv);
-        }
-        albedo = mat.base_color;
-    }
-    alpha = 1.0f;
-    depth = ht;
-}
-} // namespace
-
-#if PT_AOV == 1
-template <bool BINARY, bool EXACT>
-__global__ void __launch_bounds__(PT_WAVE, PT_AOV_WAVES_PER_EU) pt_aov_kernel(const PtKernelParams P, const PtAovArgs A)
-{
-    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
-    const int lane = threadIdx.x;
-    uint32_t* stack = lds + lane; // stack[level * 64 + lane]
-    const int ovf_levels = A.cap > PT_LDS_STACK ? A.cap - PT_LDS_STACK : 0;
-    uint32_t PT_AS1* ovf = gp(A.ovf) + (size_t)blockIdx.x * ((size_t)ovf_levels * PT_WAVE) + lane;
-    const PtNode4* __restrict__ nodes4 = P.nodes4;
-    const PtTri* __restrict__ tris = P.tris;
-    const int nbx = (P.width + 7) >> 3, nby = (P.height + 7) >> 3;
-    const float inv_n = 1.0f / (float)A.n_samples;
-    for (int b = blockIdx.x; b < nbx * nby; b += gridDim.x) {
-        const int bx = b % nbx, by = b / nbx;
-        if (((bx * 8) / A.tile + (by * 8) / A.tile) % A.world != A.rank) continue; // another rank's tile (wave-uniform)
-        const int px = bx * 8 + (lane & 7), py = by * 8 + (lane >> 3);
-        if (px >= P.width || py >= P.height) continue; // the block sticks out of the frame
-        PathState ps;
-        ps.rng = rng_init((uint32_t)px, (uint32_t)py); // the beauty frame's stream: sample 0 is its first camera ray of this pixel
-        v3 s_alb = vs(0.0f), s_nrm = vs(0.0f);
-        float s_alpha = 0.0f, s_depth = 0.0f;
-        for (int k = 0; k < A.n_samples; ++k) {
-            gen_camera_ray(P, px, py, ps); // two draws; nothing else of this pass draws from the stream
-            const v3 o = ps.org, d = ps.dir;
-            Hit h;
-            h.t = kTMax; h.u = 0.0f; h.v = 0.0f; h.id = 0x7fffffff; h.slot = -1;
-#if !PT_WATERTIGHT
-            if (BINARY) {
-                Counters cn;
-                closest_hit<false, PT_WAVE>(P, stack, o, d, h, cn);
-            } else
-#endif
-            {
-                const v3 inv = ray_inv(d);
-                int cur = P.root, sp = 0, steps = 0;
-                while (cur != PT_DONE) {
-                    // bounded as the probe's walk: a ray needs a few thousand steps, the stack bound comes from the host (3 * depth4 + 1, + 3)
-                    if (++steps > (1 << 20) || sp + 3 > A.cap) {
-                        gp(P.error_flag)[0] = 1u;
-                        break;
-                    }
-                    if (cur >= 0) {
-                        node4_step<PT_WAVE, PT_LDS_STACK>(nodes4, stack, ovf, o, inv, h.t, cur, sp, EXACT);
-                    } else {
-                        const uint32_t code = ~(uint32_t)cur;
-                        leaf_test(tris, (int)(code >> 3), (int)(code & 7u), o, d, h);
-                        if (sp > 0) {
-                            --sp;
-                            cur = (int)stack_pop<PT_WAVE, PT_LDS_STACK>(stack, ovf, sp);
-                        } else {
-                            cur = PT_DONE;
-                        }
-                    }
-                }
-            }
-            v3 alb, nrm;
-            float alpha, depth;
-            aov_sample(P, h.slot, h.u, h.v, h.t, d, alb, alpha, nrm, depth);
-            s_alb = s_alb + alb; s_alpha = s_alpha + alpha; // float32, in sample order
-            s_nrm = s_nrm + nrm; s_depth = s_depth + depth;
-        }
-        const size_t ofs = (size_t)px + (size_t)P.width * (size_t)(P.height - 1 - py); // as out_rgb
-        f32x4 PT_AS1* y = (f32x4 PT_AS1*)(gp(A.out) + 8 * ofs);                        // two 16-byte stores
-        y[0] = (f32x4){s_alb.x * inv_n, s_alb.y * inv_n, s_alb.z * inv_n, s_alpha * inv_n};
-        y[1] = (f32x4){s_nrm.x * inv_n, s_nrm.y * inv_n, s_nrm.z * inv_n, s_depth * inv_n};
-    }
-}
-
-extern "C" hipError_t pt_aov_geometry(int binary, int exact, int stack_entries, PtGeometry* g)
-{
-#if PT_WATERTIGHT
-    if (binary) return hipErrorInvalidValue; // the binary walk has no watertight test
-    const void* fn = exact ? (const void*)pt_aov_kernel<false, true> : (const void*)pt_aov_kernel<false, false>;
-#else
-    const void* fn = binary ? (const void*)pt_aov_kernel<true, false> : (exact ? (const void*)pt_aov_kernel<false, true> : (const void*)pt_aov_kernel<false, false>);
-#endif
-    g->block = PT_WAVE;
-    g->ns = PT_WAVE;
-    g->lds_levels = binary ? stack_entries : PT_LDS_STACK;
-    g->lds_bytes = (size_t)g->lds_levels * PT_WAVE * 4;
-    g->state_words = 0;
-    hipFuncAttributes fa;
-    hipError_t e = hipFuncGetAttributes(&fa, fn);
-    if (e != hipSuccess) return e;
-    if (fa.localSizeBytes != 0) return hipErrorInvalidConfiguration; // as the render instances: a build that spills is refused
-    g->vgprs = fa.numRegs;
-    g->max_blocks_per_cu = 0;
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(&g->max_blocks_per_cu, fn, g->block, g->lds_bytes);
-}
-
-extern "C" hipError_t pt_launch_aov(const PtKernelParams* p, const PtAovArgs* a, int binary, int grid, size_t lds_bytes, hipStream_t stream)
-{
-    if (grid < 1) grid = 1;
-#if PT_WATERTIGHT
-    if (binary) return hipErrorInvalidValue;
-#else
-    if (binary) hipLaunchKernelGGL((pt_aov_kernel<true, false>), dim3(grid), dim3(PT_WAVE), lds_bytes, stream, *p, *a);
-    else
-#endif
-    if (p->box_exact) hipLaunchKernelGGL((pt_aov_kernel<false, true>), dim3(grid), dim3(PT_WAVE), lds_bytes, stream, *p, *a);
-    else hipLaunchKernelGGL((pt_aov_kernel<false, false>), dim3(grid), dim3(PT_WAVE), lds_bytes, stream, *p, *a);
-    return hipGetLastError();
-}
-#else // PT_AOV == 2
-// =====================================================================================================================
-// Guide pass, follow mode (pt_render_aov_follow, include/mi355pt.h): the guide ray passes mirrors and glass
-// =====================================================================================================================
-// Translation units of their own again - pt_kernel_aov_follow.hip and pt_kernel_aov_follow_wt.hip include this file with PT_AOV = 2 - so
-// that `make asm-aov` goes on listing the five first-hit kernels and nothing else.  The frame loop, the pixel blocks, the walk and every
-// fetch are the first-hit kernel's; what is new is the loop around the walk: a hit on a surface that classifies MIRROR or GLASS
-// (aov_classify) sends the ray on from shade_hit's hit point with reflect / refract of pt_device.h, and the tint and the path length
-// travel with it.  The loop draws nothing from the stream.
-// Registers.  The first-hit instances sit at 119..128 of the 128 VGPRs of four waves per SIMD, and the follow loop adds state that
-// lives across the walk: tint (3), path length, and an origin that now differs per lane (3).  The eight per-pixel sums are needed only
-// BETWEEN samples, so they live in LDS across the walks - acc[field * 64 + lane] behind the wave's stack, conflict-free like the stack -
-// and so do the tint and the path length, which are needed only between two walks of a sample, and the RNG state and the pixel, needed
-// only between samples, and the lane's place in its 8 x 8 block: 15 words per lane, 3.75 KB per wave (16 waves per CU: 108 KB of 160 KB together with the stacks).  The accesses
-// are volatile: the compiler must not promote the parked words back into registers across the walk (it did, and spilled them to scratch).
-// No scratch, 128 VGPRs at the most (`make asm-aov-follow`).
-// BATCH BUILD (pt_kernel_aov_follow_batch.hip: PT_AOV = 2 and PT_BATCH = 1; pt_render_aov_batch).  The same kernel as pt_aov_follow_batch_kernel
-// over the 8 x 8 blocks of K frames, frame by frame: a wave's block lies in one frame, so the frame's camera (P.batch_cams) and material
-// table (P.materials + frame * n_materials * PT_MAT_STRIDE) are wave-uniform - scalar loads, no per-lane gather as in the render batch -
-// and frame f is stored W * H pixels behind frame f - 1.  With PT_BATCH = 0 the preprocessor removes all of it (`make asm-aov-follow-batch`).
-#define PT_AS3 __attribute__((address_space(3)))
-#define PT_AOV_PARK 15 // LDS words per lane behind the stack: 8 sums, tint r g b, path length, RNG state, px | py << 16, the lane's place in its block
-enum { AOV_NONE = 0, AOV_MIRROR = 1, AOV_GLASS = 2 };
-namespace {
-// Which lobe a guide ray follows: the lobe weights are sample_disney's own expressions (pt_device.h); a NaN field fails every comparison
-__device__ __forceinline__ int aov_classify(const Material& m, float roughness_max)
-{
-    const float dw = (1.0f - m.specular_transmission) * (1.0f - m.metallic);
-    const float mw = m.metallic;
-    const float cw = 0.25f * m.clearcoat;
-    const float gw = (1.0f - m.metallic) * m.specular_transmission;
-    if (mw > gw && mw > dw && mw > cw && m.roughness <= roughness_max) return AOV_MIRROR;
-    if (gw > mw && gw > dw && gw > cw && m.specular_transmission_roughness <= roughness_max) return AOV_GLASS;
-    return AOV_NONE;
-}
-
-// One surface of a guide ray (o, d) whose walk ended in h.  Returns true if the ray goes on: o, d, tint updated, dist advanced.  Otherwise
-// the sample's contribution is complete: albedo, normal, depth set.  The miss branch is aov_sample's; the fetches are its expressions.
-#if PT_BATCH
-// (batch instances: mats = the material table of the block's frame, wave-uniform; everything else as below)
-__device__ __forceinline__ bool aov_follow_surface(const PtKernelParams& P, const float* mats, const PtAovFollowArgs& F, const Hit& h, int step, v3& o, v3& d, v3& tint,
-                                                   float& dist, v3& albedo, v3& normal, float& depth)
-#else
-__device__ __forceinline__ bool aov_follow_surface(const PtKernelParams& P, const PtAovFollowArgs& F, const Hit& h, int step, v3& o, v3& d, v3& tint, float& dist,
-                                                   v3& albedo, v3& normal, float& depth)
-#endif
-{
-    if (h.slot < 0) { // aov_sample's miss branch, expression for expression
-        v3 radiance = vs(0.0f);
-        if (P.env_use_map && P.env_map.width > 0) {
-            float tu, tv;
-            uv_on_sphere(d, tu, tv);
-            radiance = radiance + tex_nearest(gp(P.env_map.texels), P.env_map.width, P.env_map.height, tu, tv);
-        } else if (P.env_use_auto) {
-            radiance = radiance + lerp3(vs(1.0f), V(0.5f, 0.7f, 1.0f), 0.5f * (d.y + 1.0f));
-        } else {
-            // the colour passes an empty asm so that 0 + colour is formed here: hoisted out of the frame loop the three wave-uniform sums
-            // sit in VGPRs across every walk, which is what tips the tightest instance into scratch
-            float cr = P.env_color[0], cg = P.env_color[1], cb = P.env_color[2];
-            asm volatile("" : "+s"(cr), "+s"(cg), "+s"(cb));
-            radiance = radiance + V(cr, cg, cb);
-        }
-        albedo = tint * (radiance * P.env_intensity);
-        normal = vs(0.0f);
-        depth = dist;
-        return false;
-    }
-    dist = dist + h.t; // float32, in step order
-    const size_t tb = (size_t)(uint32_t)h.slot * sizeof(PtTri);
-    const f32x4 c = ldg4(P.tris, tb + 32); // {p2.z, id, material, pad}
-    const size_t sb = (size_t)(uint32_t)h.slot * sizeof(PtShade);
-    const f32x4 s0 = ldg4(P.shade, sb), s1 = ldg4(P.shade, sb + 16), s2 = ldg4(P.shade, sb + 32), s3 = ldg4(P.shade, sb + 48);
-    const int mi = __float_as_int(c.z);
-    Material mat = material_default();
-    int tex_slot = -1;
-    if (mi >= 0) {
-#if PT_BATCH
-        const float PT_AS1* mp = gp(mats) + mi * PT_MAT_STRIDE;
-#else
-        const float PT_AS1* mp = gp(P.materials) + mi * PT_MAT_STRIDE;
-#endif
-        mat = material_load(mp);
-        tex_slot = __float_as_int(mp[17]);
-    }
-    const float bx = h.u, by = h.v;
-    const float bw = 1.0f - bx - by;
-    const v3 v_n = normalize(interp3(bw, bx, by, V(s0.x, s0.y, s0.z), V(s0.w, s1.x, s1.y), V(s1.z, s1.w, s2.x)));
-    const bool n_ok = finite_(v_n.x) && finite_(v_n.y) && finite_(v_n.z);
-    const bool emits = mat.emission > 0.0f;
-    if (!emits && tex_slot >= 0) {
-        const float tu = fma_(by, s3.z, fma_(bx, s3.x, bw * s2.z));
-        const float tv = fma_(by, s3.w, fma_(bx, s3.y, bw * s2.w));
-        const PtTexDesc PT_AS1* tdp = gp(P.textures) + tex_slot;
-        mat.base_color = tex_nearest(gp(tdp->texels), tdp->width, tdp->height, tu, tv);
-    }
-    const int kind = (emits || step == F.max_follow || !n_ok) ? (int)AOV_NONE : aov_classify(mat, F.roughness_max);
-    if (kind != AOV_NONE) {
-        const v3 wo = -d;
-        v3 wi, t2 = tint * mat.base_color;
-        bool through = false;
-        if (kind == AOV_GLASS) {
-            const float ct = dot(wo, v_n);
-            through = ct > 0.0f ? refract(wo, v_n, 1.0f / mat.ior, wi) : refract(wo, -v_n, mat.ior, wi);
-        }
-        if (through) t2 = tint * V(sqrt_(mat.base_color.x), sqrt_(mat.base_color.y), sqrt_(mat.base_color.z));
-        else wi = reflect(wo, v_n); // a mirror, or total internal reflection
-        const v3 dn = normalize(wi);
-        if (finite_(dn.x) && finite_(dn.y) && finite_(dn.z)) {
-            const f32x4 a = ldg4(P.tris, tb), b = ldg4(P.tris, tb + 16);
-            o = interp3(bw, bx, by, V(a.x, a.y, a.z), V(a.w, b.x, b.y), V(b.z, b.w, c.x)); // shade_hit's v_p: no normal offset
-            d = dn;
-            tint = t2;
-            return true;
-        }
-    }
-    albedo = tint * (emits ? vs(mat.emission) : mat.base_color);
-    normal = n_ok ? v_n : vs(0.0f);
-    depth = dist;
-    return false;
-}
-} // namespace
-
-template <bool BINARY, bool EXACT>
-__global__ void __launch_bounds__(PT_WAVE, PT_AOV_WAVES_PER_EU) pt_aov_follow_kernel(const PtKernelParams P, const PtAovFollowArgs F)
-{
-    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
-    const PtAovArgs& A = F.a;
-    const int lane = threadIdx.x;
-    uint32_t* stack = lds + lane; // stack[level * 64 + lane]
-    // park[field * 64 + lane]: 0..7 the sums, 8..10 tint, 11 path length; 12 RNG state, 13 pixel, 14 place in the block (LDS address space spelled out: ds_read / ds_write)
-    volatile float PT_AS3* park = (volatile float PT_AS3*)(lds + P.lds_levels * PT_WAVE + lane);
-    volatile uint32_t PT_AS3* parku = (volatile uint32_t PT_AS3*)park;
-    const int ovf_levels = A.cap > PT_LDS_STACK ? A.cap - PT_LDS_STACK : 0;
-    uint32_t PT_AS1* ovf = gp(A.ovf) + (size_t)blockIdx.x * ((size_t)ovf_levels * PT_WAVE) + lane;
-    const PtNode4* __restrict__ nodes4 = P.nodes4;
-    const PtTri* __restrict__ tris = P.tris;
-    const int nbx = (P.width + 7) >> 3, nby = (P.height + 7) >> 3;
-    parku[14 * PT_WAVE] = (uint32_t)(lane & 7) | ((uint32_t)(lane >> 3) << 16);
-#if PT_BATCH
-    // K * nbx * nby blocks, frame by frame: a block belongs to ONE frame whatever the height, so the frame, its camera and its material
-    // table are wave-uniform.  bf: the block inside its frame - shard, pixels and RNG stream are the single frame's.
-    const int nb = nbx * nby;
-    for (int bb = blockIdx.x; bb < P.batch_frames * nb; bb += gridDim.x) {
-        const int frame = bb / nb, b = bb - frame * nb;
-        const int bx = b % nbx, by = b / nbx;
-#else
-    for (int b = blockIdx.x; b < nbx * nby; b += gridDim.x) {
-        const int bx = b % nbx, by = b / nbx;
-#endif
-        if (((bx * 8) / A.tile + (by * 8) / A.tile) % A.world != A.rank) continue; // another rank's tile (wave-uniform)
-        const uint32_t in_block = parku[14 * PT_WAVE];
-        const int px = bx * 8 + (int)(in_block & 0xffffu), py = by * 8 + (int)(in_block >> 16);
-        if (px >= P.width || py >= P.height) continue; // the block sticks out of the frame
-#pragma unroll
-        for (int i = 0; i < 8; ++i) park[i * PT_WAVE] = 0.0f;
-        parku[12 * PT_WAVE] = rng_init((uint32_t)px, (uint32_t)py);
-        parku[13 * PT_WAVE] = (uint32_t)px | ((uint32_t)py << 16); // both below 65536
-        for (int k = 0; k < A.n_samples; ++k) {
-            PathState ps;
-            ps.rng = parku[12 * PT_WAVE];
-            const uint32_t pxy = parku[13 * PT_WAVE];
-#if PT_BATCH
-            gen_camera_ray_from(P, gp(P.batch_cams) + 12 * frame, (int)(pxy & 0xffffu), (int)(pxy >> 16), ps);
-#else
-            gen_camera_ray(P, (int)(pxy & 0xffffu), (int)(pxy >> 16), ps); // two draws; the follow loop draws nothing
-#endif
-            parku[12 * PT_WAVE] = ps.rng;
-            v3 o = ps.org, d = ps.dir;
-            park[8 * PT_WAVE] = 1.0f; park[9 * PT_WAVE] = 1.0f; park[10 * PT_WAVE] = 1.0f; park[11 * PT_WAVE] = 0.0f;
-            v3 alb, nrm;
-            float depth;
-            for (int step = 0;; ++step) {
-                Hit h;
-                h.t = kTMax; h.u = 0.0f; h.v = 0.0f; h.id = 0x7fffffff; h.slot = -1;
-#if !PT_WATERTIGHT
-                if (BINARY) {
-                    Counters cn;
-                    closest_hit<false, PT_WAVE>(P, stack, o, d, h, cn);
-                } else
-#endif
-                {
-                    const v3 inv = ray_inv(d);
-                    int cur = P.root, sp = 0, steps = 0;
-                    while (cur != PT_DONE) {
-                        // the first-hit kernel's walk and bounds (pt_aov_kernel)
-                        if (++steps > (1 << 20) || sp + 3 > A.cap) {
-                            gp(P.error_flag)[0] = 1u;
-                            break;
-                        }
-                        if (cur >= 0) {
-                            node4_step<PT_WAVE, PT_LDS_STACK>(nodes4, stack, ovf, o, inv, h.t, cur, sp, EXACT);
-                        } else {
-                            const uint32_t code = ~(uint32_t)cur;
-                            leaf_test(tris, (int)(code >> 3), (int)(code & 7u), o, d, h);
-                            if (sp > 0) {
-                                --sp;
-                                cur = (int)stack_pop<PT_WAVE, PT_LDS_STACK>(stack, ovf, sp);
-                            } else {
-                                cur = PT_DONE;
-                            }
-                        }
-                    }
-                }
-                if (step == 0 && h.slot >= 0) park[3 * PT_WAVE] = park[3 * PT_WAVE] + 1.0f; // coverage stays first-hit
-                v3 tint = V(park[8 * PT_WAVE], park[9 * PT_WAVE], park[10 * PT_WAVE]);
-                float dist = park[11 * PT_WAVE];
-#if PT_BATCH
-                if (!aov_follow_surface(P, P.materials + (size_t)frame * (size_t)(P.n_materials * PT_MAT_STRIDE), F, h, step, o, d, tint, dist, alb, nrm, depth)) break;
-#else
-                if (!aov_follow_surface(P, F, h, step, o, d, tint, dist, alb, nrm, depth)) break;
-#endif
-                park[8 * PT_WAVE] = tint.x; park[9 * PT_WAVE] = tint.y; park[10 * PT_WAVE] = tint.z; park[11 * PT_WAVE] = dist;
-            }
-            // float32, in sample order
-            park[0 * PT_WAVE] = park[0 * PT_WAVE] + alb.x; park[1 * PT_WAVE] = park[1 * PT_WAVE] + alb.y; park[2 * PT_WAVE] = park[2 * PT_WAVE] + alb.z;
-            park[4 * PT_WAVE] = park[4 * PT_WAVE] + nrm.x; park[5 * PT_WAVE] = park[5 * PT_WAVE] + nrm.y; park[6 * PT_WAVE] = park[6 * PT_WAVE] + nrm.z;
-            park[7 * PT_WAVE] = park[7 * PT_WAVE] + depth;
-        }
-        const uint32_t pxy = parku[13 * PT_WAVE];
-#if PT_BATCH
-        const size_t ofs = (size_t)frame * ((size_t)P.width * (size_t)P.height) + (size_t)(pxy & 0xffffu) + (size_t)P.width * (size_t)(P.height - 1 - (int)(pxy >> 16));
-#else
-        const size_t ofs = (size_t)(pxy & 0xffffu) + (size_t)P.width * (size_t)(P.height - 1 - (int)(pxy >> 16)); // as out_rgb
-#endif
-        f32x4 PT_AS1* y = (f32x4 PT_AS1*)(gp(A.out) + 8 * ofs);                        // two 16-byte stores
-        y[0] = (f32x4){park[0 * PT_WAVE] * F.inv_n, park[1 * PT_WAVE] * F.inv_n, park[2 * PT_WAVE] * F.inv_n, park[3 * PT_WAVE] * F.inv_n};
-        y[1] = (f32x4){park[4 * PT_WAVE] * F.inv_n, park[5 * PT_WAVE] * F.inv_n, park[6 * PT_WAVE] * F.inv_n, park[7 * PT_WAVE] * F.inv_n};
-    }
-}
-
-extern "C" hipError_t pt_aov_follow_geometry(int binary, int exact, int stack_entries, PtGeometry* g)
-{
-#if PT_WATERTIGHT
-    if (binary) return hipErrorInvalidValue; // the binary walk has no watertight test
-    const void* fn = exact ? (const void*)pt_aov_follow_kernel<false, true> : (const void*)pt_aov_follow_kernel<false, false>;
-#else
-    const void* fn = binary ? (const void*)pt_aov_follow_kernel<true, false>
-                            : (exact ? (const void*)pt_aov_follow_kernel<false, true> : (const void*)pt_aov_follow_kernel<false, false>);
-#endif
-    g->block = PT_WAVE;
-    g->ns = PT_WAVE;
-    g->lds_levels = binary ? stack_entries : PT_LDS_STACK;
-    g->lds_bytes = (size_t)(g->lds_levels + PT_AOV_PARK) * PT_WAVE * 4; // the stack, then the parked state
-    g->state_words = 0;
-    hipFuncAttributes fa;
-    hipError_t e = hipFuncGetAttributes(&fa, fn);
-    if (e != hipSuccess) return e;
-    if (fa.localSizeBytes != 0) return hipErrorInvalidConfiguration; // a build that spills is refused
-    g->vgprs = fa.numRegs;
-    g->max_blocks_per_cu = 0;
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(&g->max_blocks_per_cu, fn, g->block, g->lds_bytes);
-}
-
-extern "C" hipError_t pt_launch_aov_follow(const PtKernelParams* p, const PtAovFollowArgs* a, int binary, int grid, size_t lds_bytes, hipStream_t stream)
-{
-    if (grid < 1) grid = 1;
-#if PT_BATCH
-    if (p->batch_frames < 1 || p->batch_cams == nullptr) return hipErrorInvalidValue; // (pt_launch_aov_follow_batch: frames, cameras and tables as pt_launch_render_batch)
-#endif
-#if PT_WATERTIGHT
-    if (binary) return hipErrorInvalidValue;
-#else
-    if (binary) hipLaunchKernelGGL((pt_aov_follow_kernel<true, false>), dim3(grid), dim3(PT_WAVE), lds_bytes, stream, *p, *a);
-    else
-#endif
-    if (p->box_exact) hipLaunchKernelGGL((pt_aov_follow_kernel<false, true>), dim3(grid), dim3(PT_WAVE), lds_bytes, stream, *p, *a);
-    else hipLaunchKernelGGL((pt_aov_follow_kernel<false, false>), dim3(grid), dim3(PT_WAVE), lds_bytes, stream, *p, *a);
-    return hipGetLastError();
-}
-#endif // PT_AOV == 1 / 2
-#endif // PT_AOV == 1 || PT_AOV == 2
-
-#if PT_AOV == 3
-// =====================================================================================================================
-// Ray queries (pt_trace_closest, pt_trace_occluded, include/mi355pt.h): closest hit and occlusion for the caller's rays
-// =====================================================================================================================
-// Translation units of their own once more - pt_kernel_rays.hip and, with PT_WATERTIGHT = 1, pt_kernel_rays_wt.hip include this file with
-// PT_AOV = 3 - so that every other `make asm-*` target goes on listing the kernels it listed.  Like the probes and the guide kernels the
-// kernel owns no traversal arithmetic: ray_inv -> node4_step<PT_WAVE, PT_LDS_STACK> (short LDS stack, deeper levels in the wave's HBM
-// columns) -> leaf_test -> stack_pop, with the probe's bounds around them.  The ray's own bound enters only as the initial h.t.
-// What is new:
-//   * ray I/O: a ray is two 16-byte loads, a closest hit one 16-byte store, an occlusion flag a byte store;
-//   * any-hit exit (OCCLUDED): a lane whose leaf_test accepted a triangle (h.slot >= 0) is done at once.  tbest never shrinks below the
-//     ray's bound in such a walk, so ordering the children buys nothing - node4_step is left as it is;
-//   * lane refill (the persistent "while-while" loop of Aila and Laine 2009, without its atomics): a wave owns the contiguous range
-//     [blockIdx.x * per_wave, + per_wave) of the rays - a multiple of 64, so what coherence the caller's order has stays inside a wave -
-//     and `next`, the first ray not handed out yet, is wave-uniform.  Every round: idle = ballot(the lane holds no ray); when at most
-//     A.refill lanes are still walking, every idle lane takes ray next + (its rank among the idle lanes), loads and initialises it, and
-//     next += popcount(idle).  Nothing crosses waves.  Then every lane that holds a ray takes ONE step of its walk, and a lane whose walk
-//     ended stores its result at once and is idle from the next round on.
-// TERMINATION, read off the code: a lane that holds a ray takes a step every round, and a walk is over after at most 2^20 + 1 steps
-// (`steps`; the stack bound `cap` comes from the host: 3 * depth4 + 1, + 3 - a walk that runs out of either sets error_flag and its ray
-// is reported as a miss); a round in which no lane holds a ray either hands out at least one (next < end: no lane is walking, which is
-// <= any A.refill) or leaves the loop; `next` only grows.
-#ifndef PT_RAYS_WAVES_PER_EU
-#define PT_RAYS_WAVES_PER_EU 4 // 128 VGPRs, 16 waves per CU at 3 KB of LDS each
-#endif
-template <bool OCCLUDED, bool EXACT>
-__global__ void __launch_bounds__(PT_WAVE, PT_RAYS_WAVES_PER_EU) pt_rays_kernel(const PtKernelParams P, const PtRaysArgs A)
-{
-    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
-    const int lane = threadIdx.x;
-    uint32_t* stack = lds + lane; // stack[level * 64 + lane]
-    const int ovf_levels = A.cap > PT_LDS_STACK ? A.cap - PT_LDS_STACK : 0;
-    uint32_t PT_AS1* ovf = gp(A.ovf) + (size_t)blockIdx.x * ((size_t)ovf_levels * PT_WAVE) + lane;
-    const PtNode4* __restrict__ nodes4 = P.nodes4;
-    const PtTri* __restrict__ tris = P.tris;
-    const long long first = (long long)blockIdx.x * A.per_wave; // < n: the launcher refuses a grid with an empty range
-    const int end = (int)(first + A.per_wave < (long long)A.n ? first + A.per_wave : (long long)A.n);
-    int next = (int)first;
-    int ray = -1, cur = PT_DONE, sp = 0, steps = 0; // ray < 0: the lane is idle
-    v3 o = vs(0.0f), d = vs(0.0f), inv = vs(0.0f);
-    Hit h;
-    h.t = 0.0f; h.u = 0.0f; h.v = 0.0f; h.id = 0x7fffffff; h.slot = -1;
-    for (;;) {
-        const unsigned long long m_idle = __ballot(ray < 0);
-        const int n_idle = popc64(m_idle);
-        if (next < end) {
-            if (PT_WAVE - n_idle <= A.refill) {
-                const long long i = (long long)next + rank_in(m_idle); // (64-bit: next may be within 63 of 2^31 - 1)
-                if (ray < 0 && i < (long long)end) {
-                    const f32x4 r0 = ldg4(A.rays, (size_t)(uint32_t)i * 32), r1 = ldg4(A.rays, (size_t)(uint32_t)i * 32 + 16); // {org, tmax}, {dir, not read}
-                    o = V(r0.x, r0.y, r0.z);
-                    d = V(r1.x, r1.y, r1.z);
-                    inv = ray_inv(d);
-                    h.t = r0.w < kTMax ? r0.w : kTMax; // NaN and +inf: the library's own bound; a hit at exactly this t is taken (id below)
-                    h.u = 0.0f; h.v = 0.0f; h.id = 0x7fffffff; h.slot = -1;
-                    cur = P.root; sp = 0; steps = 0;
-                    ray = (int)i;
-                }
-                next = (end - next > n_idle) ? next + n_idle : end;
-            }
-        } else if (n_idle == PT_WAVE) {
-            break;
-        }
-        if (ray >= 0) {
-            if (cur != PT_DONE) {
-                // bounded as the probe's walk: a ray needs a few thousand steps, the stack bound comes from the host (3 * depth4 + 1, + 3)
-                if (++steps > (1 << 20) || sp + 3 > A.cap) {
-                    gp(P.error_flag)[0] = 1u;
-                    h.slot = -1; // retired as a miss
-                    cur = PT_DONE;
-                } else if (cur >= 0) {
-                    node4_step<PT_WAVE, PT_LDS_STACK>(nodes4, stack, ovf, o, inv, h.t, cur, sp, EXACT);
-                } else {
-                    const uint32_t code = ~(uint32_t)cur;
-                    leaf_test(tris, (int)(code >> 3), (int)(code & 7u), o, d, h);
-                    if ((OCCLUDED && h.slot >= 0) || sp == 0) {
-                        cur = PT_DONE;
-                    } else {
-                        --sp;
-                        cur = (int)stack_pop<PT_WAVE, PT_LDS_STACK>(stack, ovf, sp);
-                    }
-                }
-            }
-            if (cur == PT_DONE) { // the walk has ended: the result is stored now, the lane is idle from the next round on
-                const bool hit = h.slot >= 0;
-                if (OCCLUDED) {
-                    ((uint8_t PT_AS1*)A.out)[(size_t)(uint32_t)ray] = hit ? (uint8_t)1 : (uint8_t)0;
-                } else {
-                    f32x4 PT_AS1* y = (f32x4 PT_AS1*)((char PT_AS1*)A.out + (size_t)(uint32_t)ray * 16);
-                    *y = hit ? (f32x4){h.t, h.u, h.v, __int_as_float(h.id)} : (f32x4){0.0f, 0.0f, 0.0f, __int_as_float(-1)};
-                }
-                ray = -1;
-            }
-        }
-    }
-}
-
-namespace {
-const void* rays_instance(int occluded, int exact)
-{
-    if (occluded) return exact ? (const void*)pt_rays_kernel<true, true> : (const void*)pt_rays_kernel<true, false>;
-    return exact ? (const void*)pt_rays_kernel<false, true> : (const void*)pt_rays_kernel<false, false>;
-}
-} // namespace
-
-extern "C" hipError_t pt_rays_geometry(int occluded, int exact, PtGeometry* g)
-{
-    const void* fn = rays_instance(occluded, exact);
-    g->block = PT_WAVE;
-    g->ns = PT_WAVE;
-    g->lds_levels = PT_LDS_STACK;
-    g->lds_bytes = (size_t)g->lds_levels * PT_WAVE * 4;
-    g->state_words = 0;
-    hipFuncAttributes fa;
-    hipError_t e = hipFuncGetAttributes(&fa, fn);
-    if (e != hipSuccess) return e;
-    if (fa.localSizeBytes != 0) return hipErrorInvalidConfiguration; // as the guide instances: a build that spills is refused
-    g->vgprs = fa.numRegs;
-    g->max_blocks_per_cu = 0;
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(&g->max_blocks_per_cu, fn, g->block, g->lds_bytes);
-}
-
-extern "C" hipError_t pt_launch_rays(const PtKernelParams* p, const PtRaysArgs* a, int occluded, int grid, size_t lds_bytes, hipStream_t stream)
-{
-    if (grid < 1 || a->n < 1 || a->per_wave < PT_WAVE || (a->per_wave % PT_WAVE) != 0 || a->refill < 0 || a->refill >= PT_WAVE) return hipErrorInvalidValue;
-    if ((long long)grid * a->per_wave < (long long)a->n) return hipErrorInvalidValue; // the ranges cover every ray ...
-    if ((long long)(grid - 1) * a->per_wave >= (long long)a->n) return hipErrorInvalidValue; // ... and none is empty: the kernel relies on it
-    if (occluded) {
-        if (p->box_exact) hipLaunchKernelGGL((pt_rays_kernel<true, true>), dim3(grid), dim3(PT_WAVE), lds_bytes, stream, *p, *a);
-        else hipLaunchKernelGGL((pt_rays_kernel<true, false>), dim3(grid), dim3(PT_WAVE), lds_bytes, stream, *p, *a);
-    } else {
-        if (p->box_exact) hipLaunchKernelGGL((pt_rays_kernel<false, true>), dim3(grid), dim3(PT_WAVE), lds_bytes, stream, *p, *a);
-        else hipLaunchKernelGGL((pt_rays_kernel<false, false>), dim3(grid), dim3(PT_WAVE), lds_bytes, stream, *p, *a);
-    }
-    return hipGetLastError();
-}
-#endif // PT_AOV == 3

@@ -1,4 +1,4 @@
-// pt_launch.h -- prototypes of the kernel launchers (defined in pt_kernel.hip / pt_lbvh.hip, stubbed in pt_nogpu_stubs.cpp for the
+// pt_launch.h -- prototypes of the kernel launchers (defined in the .hip units: pt_kernel.hip, the family headers it names, pt_lbvh.hip, ...; stubbed in pt_nogpu_stubs.cpp for the
 // host-side sanitizer build) as pt_scene.cpp / pt_render.cpp / pt_guides.cpp / pt_debug.cpp / pt_comm.cpp call them.  ONE declaration for definition, stub and caller: the functions
 // have C linkage, so a mismatched parameter list would link and then misbehave (round-3 advisor finding).
 #pragma once
@@ -19,7 +19,7 @@ struct PtGeometry {
     int max_blocks_per_cu;  // occupancy at lds_bytes
 };
 
-// Ray probes of pt_debug_eval (pt_kernel.hip, "ray probes"): op = PT_PROBE_QUAD / PT_PROBE_QUAD_OVF / PT_PROBE_GROUP + slab form (0: fma, 1: subtracting).
+// Ray probes of pt_debug_eval (pt_probes.h): op = PT_PROBE_QUAD / PT_PROBE_QUAD_OVF / PT_PROBE_GROUP + slab form (0: fma, 1: subtracting).
 // in: o[3], d[3] per ray; out: PT_PROBE_OUT floats per ray (layout in include/mi355pt.h).
 enum { PT_PROBE_FIRST = 30, PT_PROBE_QUAD = 30, PT_PROBE_QUAD_OVF = 32, PT_PROBE_GROUP = 34, PT_PROBE_LAST = 35 };
 #define PT_PROBE_OUT 6
@@ -46,7 +46,7 @@ struct PtRefitArgs {
     int32_t n_slots, n_levels, n_slots4, n_slots8;
 };
 
-// Guide pass (pt_render_aov; pt_kernel.hip "guide pass"): what the guide kernels take beside the scene and the camera in PtKernelParams.
+// Guide pass (pt_render_aov; pt_aov_first.h): what the guide kernels take beside the scene and the camera in PtKernelParams.
 struct PtAovArgs {
     float* out;        // W*H*8 floats, cleared by the caller: {albedo r, g, b, alpha, normal x, y, z, depth} per pixel, framebuffer order
     uint32_t* ovf;     // quad walk: the waves' HBM stack columns, (cap - PT_LDS_STACK) * 64 words per workgroup (none when cap <= PT_LDS_STACK)
@@ -55,7 +55,7 @@ struct PtAovArgs {
     int32_t rank, world, tile; // pixel shard (pt_shard_pixels: tile a multiple of 8, tile (tx, ty) belongs to rank (tx + ty) % world)
     int32_t pad;
 };
-// Follow mode of the guide pass (pt_render_aov_follow; pt_kernel.hip "guide pass, follow mode"): the first-hit pass's arguments and pt_aov_params
+// Follow mode of the guide pass (pt_render_aov_follow; pt_aov_follow.h): the first-hit pass's arguments and pt_aov_params
 struct PtAovFollowArgs {
     PtAovArgs a;
     int32_t max_follow;  // 0..8 specular surfaces a guide ray may pass
@@ -64,7 +64,7 @@ struct PtAovFollowArgs {
     int32_t pad;
 };
 
-// Ray queries (pt_trace_closest, pt_trace_occluded; pt_kernel.hip "ray queries"): what the ray kernels take beside the scene in PtKernelParams.
+// Ray queries (pt_trace_closest, pt_trace_occluded; pt_rays_kernels.h): what the ray kernels take beside the scene in PtKernelParams.
 struct PtRaysArgs {
     const void* rays;  // n pt_ray records (include/mi355pt.h: org, tmax, dir, one float that is not read), 16-byte aligned
     void* out;         // closest: n pt_ray_hit {t, u, v, prim}, 16-byte aligned; occluded: n bytes
@@ -228,7 +228,7 @@ hipError_t pt_launch_accum_variance(const PtAccumVarArgs* a, hipStream_t stream)
 size_t pt_denoise_batch_workspace_bytes(int W, int H, int K);
 hipError_t pt_denoise_batch_geometry(int W, int H, int K, PtGeometry* g, int* grid);
 hipError_t pt_launch_denoise_batch(const PtDenoiseArgs* a, int K, hipStream_t stream);
-// pt_kernel.hip / pt_kernel_wt.hip: the guide kernels.  binary = 1: the one-level walk over PtNode[] (closest_hit of pt_trace.h; Moeller-
+// pt_kernel_aov.hip / pt_kernel_aov_wt.hip: the guide kernels.  binary = 1: the one-level walk over PtNode[] (closest_hit of pt_trace.h; Moeller-
 // Trumbore only: the watertight build has no such instance and answers hipErrorInvalidValue).  Geometry: block, lds_bytes, lds_levels and
 // vgprs of the instance; hipErrorInvalidConfiguration if it needs scratch.
 hipError_t pt_launch_aov(const PtKernelParams* p, const PtAovArgs* a, int binary, int grid, size_t lds_bytes, hipStream_t stream);

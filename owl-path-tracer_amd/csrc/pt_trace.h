@@ -1,6 +1,7 @@
-// pt_trace.h -- device code shared by the render kernels (pt_kernel.hip: the wavefront-scheduled product kernel; pt_kernel_aux.hip: the
-// lane-per-pixel variant and the validation kernel): closest-hit building blocks (slab test, Moeller-Trumbore, binary node step), the
-// reference's path loop body after owl::traceRay (shade_hit: device.cu:136-214), camera rays (device.cu:231-241) and the work counters.
+// pt_trace.h -- device code shared by every kernel family that walks the tree (pt_kernel.hip: the wavefront-scheduled product kernel;
+// pt_kernel_aux.hip: the lane-per-pixel variant and the validation kernel; pt_probes.h, pt_aov_first.h, pt_aov_follow.h,
+// pt_rays_kernels.h): closest-hit building blocks (slab test, Moeller-Trumbore, binary node step, quad-node step), the reference's
+// path loop body after owl::traceRay (shade_hit: device.cu:136-214), camera rays (device.cu:231-241) and the work counters.
 // Everything is in an anonymous namespace: each translation unit gets its own inlined copy.
 #pragma once
 #include <cstdlib>
@@ -71,7 +72,7 @@ __device__ __forceinline__ bool box_test(float bminx, float bminy, float bminz, 
     return tn <= tf * 1.0000004f;
 }
 
-// The same test with the slab distances as fma(bound, inv, -(o * inv)): see node4_step (pt_kernel.hip) for the error bound and when the
+// The same test with the slab distances as fma(bound, inv, -(o * inv)): see node4_step (below) for the error bound and when the
 // host asks for the subtracting form instead.
 __device__ __forceinline__ bool box_test_fma(float bminx, float bminy, float bminz, float bmaxx, float bmaxy, float bmaxz, v3 o, v3 inv, float tbest, float& tnear)
 {
@@ -172,7 +173,7 @@ __device__ __forceinline__ void tri_eval2(const f32x4 a0, const f32x4 b0, const 
     if (take1) tri_take(t.y, u.y, v.y, uv.y, __float_as_int(c1.y), slot0 + 1, h);
 }
 #if PT_WATERTIGHT
-// WATERTIGHT BUILD (pt_kernel_wt.hip includes pt_kernel.hip with PT_WATERTIGHT = 1; option "watertight").  The triangle test of Woop,
+// WATERTIGHT BUILD (the *_wt.hip units include their family's code with PT_WATERTIGHT = 1; option "watertight").  The triangle test of Woop,
 // Benthin and Wald ("Watertight Ray/Triangle Intersection", JCGT 2013) in the fixed float32 sequence of DESIGN.md 2.1: the ray's dominant
 // axis becomes z, the vertices are sheared into the ray's frame and the three 2-D edge functions U, V, W decide the hit.  An edge
 // function is a difference of two products of the SAME four float32 values for the two triangles that share the edge, with the roles
@@ -344,6 +345,9 @@ __device__ __forceinline__ void leaf_test(const PtTri* __restrict__ tris, int fi
 // Stack entry i lives in LDS (stack[i * STRIDE]) for i < LDS_ENTRIES, else in the lane's HBM overflow column
 // (ovf[(i - LDS_ENTRIES) * STRIDE]): on C4 0.006 % of the binary walk's pushes go deeper than 12 (census of the instrumented build: profiles/r01_summary.md), so a 12-entry LDS
 // stack halves the LDS a wave needs for BVHs of any depth.  LDS_ENTRIES = 0x7fffffff: everything in LDS.
+#ifndef PT_LDS_STACK
+#define PT_LDS_STACK 12 // levels of a lane's stack that the one-wave kernels keep in LDS (wavefront kernel, probes, guide kernels, ray queries)
+#endif
 template <int STRIDE, int LDS_ENTRIES>
 __device__ __forceinline__ void stack_push(uint32_t* stack, uint32_t PT_AS1* ovf, int sp, uint32_t v)
 {
@@ -397,7 +401,112 @@ __device__ __forceinline__ void node_step(const PtNode* __restrict__ nodes, uint
     }
 }
 
-// STRIDE: words between two levels of a lane's stack = threads of the workgroup (the guide kernel of pt_kernel.hip runs it with one wave)
+// Quad-node step (PtNode4, pt_types.h): the four grandchild boxes of a binary node in one 128-byte record - one cache line and
+// one memory round trip per TWO levels of the binary tree.  Slab test as in node_step, two packed pairs; the lane continues with
+// the nearest hit child and pushes the other hit children (in slot order; any visiting order gives the same closest hit).
+// The lane reads its own record with 7 x global_load_dwordx4 = 7 vL1D accesses per lane and step, at 32-bit offsets from the wave-uniform
+// base (the host keeps the quad nodes below 4 GiB: pt_render.cpp).  (Two validated experiments that did not pay - whole-line cooperative
+// fetches through an LDS staging area, 64-byte records with 8-bit planes - live in variants/.)
+template <int STRIDE, int LDS_ENTRIES, bool CENSUS = false>
+__device__ __forceinline__ void node4_step(const PtNode4* __restrict__ nodes4, uint32_t* stack, uint32_t PT_AS1* ovf, v3 o, v3 inv, float tbest, int& cur, int& sp,
+                                           const bool exact, uint32_t* n_nohit = nullptr, uint32_t* n_beyond = nullptr)
+{
+    bool crossed = false; // CENSUS: the ray crosses some slot's box when the bound of the best hit is ignored
+    // Octant order: on each axis the ray enters a slab through the plane row that faces it - lo for inv > 0, hi for inv < 0 - and leaves
+    // through the other one, so the step fetches the rows as (entry, exit) pairs and needs no per-axis min / max.  Both slab forms below are
+    // monotone in the plane for a fixed inv (correctly rounded operations of a monotone function), so for lo <= hi the entry distance IS
+    // the minimum of the two and the exit distance the maximum, bit for bit; every non-empty slot has finite lo <= hi (the host and device
+    // builders pad finite boxes; pt_debug_quad_info checks it) and an empty slot {+inf, +inf} still misses (entry +inf or exit -inf).
+    // The sign bit picks the row: ray_inv never returns 0, NaN or an infinity, and d = -0 gives -PT_INV_MAX, whose sign matches.
+    const uint32_t ex = (uint32_t)(__float_as_int(inv.x) >> 31) & 48u; // 0 or 48: byte offset of the entry row from the lo row
+    const uint32_t ey = (uint32_t)(__float_as_int(inv.y) >> 31) & 48u;
+    const uint32_t ez = (uint32_t)(__float_as_int(inv.z) >> 31) & 48u;
+    const uint32_t rec = (uint32_t)cur * (uint32_t)sizeof(PtNode4);
+    const f32x4 nx4 = ldg4u(nodes4, rec + ex, 0), ny4 = ldg4u(nodes4, rec + ey, 16), nz4 = ldg4u(nodes4, rec + ez, 32);
+    const f32x4 fx4 = ldg4u(nodes4, rec + (ex ^ 48u), 0), fy4 = ldg4u(nodes4, rec + (ey ^ 48u), 16), fz4 = ldg4u(nodes4, rec + (ez ^ 48u), 32);
+    const f32x4 cf = ldg4u(nodes4, rec, 96);
+    // Slab distances (round 4): fma(plane, 1/d, -(o/d)) - one packed fma per pair of planes instead of a subtraction and a multiplication
+    // (24 of the step's ~150 VALU operations; C4 492 -> 484-486 ms, C3 149 -> 146).  Against (plane - o) * (1/d) the distance is off by
+    // |o/d| 2^-24, i.e. the plane seems displaced by |o| 2^-24 in space: rays start on surfaces or at the camera, the boxes are padded by
+    // 1e-5 x the scene extent, and the host launches the instances with the subtracting form (`exact`) for a camera farther than 42
+    // extents from the origin (pt_render.cpp) - the test stays conservative with respect to every hit the triangle test can report, and
+    // the triangle test decides the image.  The reciprocals are finite (ray_inv clamps them: a direction component of exactly 0 would
+    // otherwise give -inf or NaN here depending on the signs of plane and origin, and cull boxes the ray runs through).
+    // (Both forms behind a run-time switch in ONE instance cost 4 %: C4 486 -> 508 ms, profiles/r04_notes.md.)
+    const f32x2 ox = {o.x, o.x}, oy = {o.y, o.y}, oz = {o.z, o.z}, ix = {inv.x, inv.x}, iy = {inv.y, inv.y}, iz = {inv.z, inv.z};
+    const float nx = -(o.x * inv.x), ny = -(o.y * inv.y), nz = -(o.z * inv.z);
+    const f32x2 nox = {nx, nx}, noy = {ny, ny}, noz = {nz, nz};
+    const f32x2 pad = {1.0000004f, 1.0000004f};
+    // Keys of the nearest-child choice: the entry distance's bits for a hit slot (a positive float: the bits order as unsigned integers),
+    // all ones for a miss - integer min / max and compares instead of selects of booleans.
+    const uint32_t kMiss = 0xffffffffu;
+    uint32_t key[4];
+#pragma unroll
+    for (int p = 0; p < 2; ++p) { // slots {0, 1} and {2, 3}
+        const f32x2 enx = p ? (f32x2){nx4.z, nx4.w} : (f32x2){nx4.x, nx4.y}, eny = p ? (f32x2){ny4.z, ny4.w} : (f32x2){ny4.x, ny4.y};
+        const f32x2 enz = p ? (f32x2){nz4.z, nz4.w} : (f32x2){nz4.x, nz4.y}, exx = p ? (f32x2){fx4.z, fx4.w} : (f32x2){fx4.x, fx4.y};
+        const f32x2 exy = p ? (f32x2){fy4.z, fy4.w} : (f32x2){fy4.x, fy4.y}, exz = p ? (f32x2){fz4.z, fz4.w} : (f32x2){fz4.x, fz4.y};
+        f32x2 tnx, tfx, tny, tfy, tnz, tfz;
+        if (exact) { // a compile-time constant in the product instances (see pt_render_wave_kernel: EXACT)
+            tnx = (enx - ox) * ix; tfx = (exx - ox) * ix;
+            tny = (eny - oy) * iy; tfy = (exy - oy) * iy;
+            tnz = (enz - oz) * iz; tfz = (exz - oz) * iz;
+        } else {
+            tnx = __builtin_elementwise_fma(enx, ix, nox); tfx = __builtin_elementwise_fma(exx, ix, nox);
+            tny = __builtin_elementwise_fma(eny, iy, noy); tfy = __builtin_elementwise_fma(exy, iy, noy);
+            tnz = __builtin_elementwise_fma(enz, iz, noz); tfz = __builtin_elementwise_fma(exz, iz, noz);
+        }
+        const float ta = fmax_hw(fmax_hw(tnx.x, tny.x), fmax_hw(tnz.x, kTMin));
+        const float tb = fmax_hw(fmax_hw(tnx.y, tny.y), fmax_hw(tnz.y, kTMin));
+        f32x2 tf = {fmin_hw(fmin_hw(tfx.x, tfy.x), fmin_hw(tfz.x, tbest)), fmin_hw(fmin_hw(tfx.y, tfy.y), fmin_hw(tfz.y, tbest))};
+        tf = tf * pad;
+        key[2 * p] = ta <= tf.x ? __float_as_uint(ta) : kMiss;
+        key[2 * p + 1] = tb <= tf.y ? __float_as_uint(tb) : kMiss;
+        if (CENSUS) { // instrumented instance: would the slot be hit without the bound of the best hit so far?
+            const float fa = fmin_hw(fmin_hw(tfx.x, tfy.x), tfz.x) * 1.0000004f;
+            const float fb = fmin_hw(fmin_hw(tfx.y, tfy.y), tfz.y) * 1.0000004f;
+            crossed = crossed || ta <= fa || tb <= fb;
+        }
+    }
+    const int r0 = __float_as_int(cf.x), r1 = __float_as_int(cf.y), r2 = __float_as_int(cf.z), r3 = __float_as_int(cf.w);
+    const bool b01 = key[1] < key[0], b23 = key[3] < key[2]; // the pair's second slot is the nearer one
+    const uint32_t m01 = b01 ? key[1] : key[0], M01 = b01 ? key[0] : key[1], m23 = b23 ? key[3] : key[2], M23 = b23 ? key[2] : key[3];
+    const int n01 = b01 ? r1 : r0, f01 = b01 ? r0 : r1, n23 = b23 ? r3 : r2, f23 = b23 ? r2 : r3; // nearer / farther child of each pair
+    const bool in_b = m23 < m01; // the nearest hit is in slot pair {2, 3}
+    const int nearc = in_b ? n23 : n01;
+    const bool any = (in_b ? m23 : m01) != kMiss;
+    if (CENSUS) { // steps that enter nothing, and of those the ones where the ray does cross a box: the node lies beyond the best hit
+        *n_nohit += any ? 0u : 1u;
+        *n_beyond += (!any && crossed) ? 1u : 0u;
+    }
+    // push order: the two slots of the OTHER pair first, the farther one first, then the nearest's sibling (popped first): siblings share a
+    // parent box, so the sibling is usually the next nearest.  Three pushes at most; a pushed key is a hit.
+    const int x1 = in_b ? f01 : f23, x2 = in_b ? n01 : n23, x3 = in_b ? f23 : f01;
+    const bool h1 = (in_b ? M01 : M23) != kMiss, h2 = (in_b ? m01 : m23) != kMiss, h3 = (in_b ? M23 : M01) != kMiss;
+    // (strictly by entry distance - the partner inserted where its distance puts it - costs 12 more instructions per step and saves
+    // 0.1 % of the triangle tests: C4 497 -> 515 ms, C5 3 211 -> 3 353, profiles/r04_notes.md)
+    if (LDS_ENTRIES == 0x7fffffff) {
+        // common instance (the caller made sure sp + 3 stays inside the LDS part): store above the top whether or not the entry is
+        // pushed - the slot is free either way - and advance sp by the predicate; no branches
+        stack[sp * STRIDE] = (uint32_t)x1; sp += h1 ? 1 : 0;
+        stack[sp * STRIDE] = (uint32_t)x2; sp += h2 ? 1 : 0;
+        stack[sp * STRIDE] = (uint32_t)x3; sp += h3 ? 1 : 0;
+    } else {
+        if (h1) { stack_push<STRIDE, LDS_ENTRIES>(stack, ovf, sp, (uint32_t)x1); ++sp; }
+        if (h2) { stack_push<STRIDE, LDS_ENTRIES>(stack, ovf, sp, (uint32_t)x2); ++sp; }
+        if (h3) { stack_push<STRIDE, LDS_ENTRIES>(stack, ovf, sp, (uint32_t)x3); ++sp; }
+    }
+    if (any) {
+        cur = nearc;
+    } else if (sp > 0) {
+        --sp;
+        cur = (int)stack_pop<STRIDE, LDS_ENTRIES>(stack, ovf, sp);
+    } else {
+        cur = PT_DONE;
+    }
+}
+
+// STRIDE: words between two levels of a lane's stack = threads of the workgroup (the guide kernels of pt_aov_first.h / pt_aov_follow.h run it with one wave)
 template <bool COUNT, int STRIDE = PT_BLOCK>
 __device__ __forceinline__ void closest_hit(const PtKernelParams& P, uint32_t* stack, v3 o, v3 d, Hit& h, Counters& cn)
 {

@@ -19,7 +19,7 @@ OPS = {"sin": 0, "cos": 1, "tan": 2, "atan": 3, "atan2": 4, "asin": 5, "log": 6,
        # column, group walk; "_exact" = the subtracting slab form.  6 floats out: hit, t, u, v, id bits, aux
        "quad": 30, "quad_exact": 31, "quad_ovf": 32, "quad_ovf_exact": 33, "group": 34, "group_exact": 35}
 PROBE_OPS = ("quad", "quad_exact", "quad_ovf", "quad_ovf_exact", "group", "group_exact")
-PT_LDS_STACK = 12  # csrc/pt_kernel.hip: stack levels of the quad walk kept in LDS
+PT_LDS_STACK = 12  # csrc/pt_trace.h: stack levels of the quad walk kept in LDS
 
 # csrc/pt_types.h, for Context.export_trees
 NODE_DTYPE = np.dtype([("lo", "<f4", (3, 2)), ("hi", "<f4", (3, 2)), ("left", "<i4"), ("right", "<i4"), ("pad", "<u4", (2,))])

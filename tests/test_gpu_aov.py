@@ -1,4 +1,4 @@
-"""The guide pass on the GPU (pt_render_aov; kernel: csrc/pt_kernel.hip "guide pass").  Every comparison is bit for bit on all 8 channels
+"""The guide pass on the GPU (pt_render_aov; kernel: csrc/pt_aov_first.h).  Every comparison is bit for bit on all 8 channels
 of every pixel.
 
 * GPU == tests/aov_ref.py (numpy, from the oracle's building blocks) == the CPU twin pt_debug_aov_host on the cases of aov_common.py

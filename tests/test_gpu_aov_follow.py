@@ -1,5 +1,5 @@
-"""The follow mode of the guide pass on the GPU (pt_render_aov_follow; kernels: csrc/pt_kernel_aov_follow.hip = pt_kernel.hip "guide pass,
-follow mode").  Every comparison is bit for bit on all 8 channels of every pixel.
+"""The follow mode of the guide pass on the GPU (pt_render_aov_follow; kernels: csrc/pt_kernel_aov_follow.hip =
+csrc/pt_aov_follow.h).  Every comparison is bit for bit on all 8 channels of every pixel.
 
 * GPU == tests/aov_follow_ref.py (numpy) == the CPU twin pt_debug_aov_follow_host over the cases of aov_follow_common.py (four scenes, two
   sizes, n = 1 and 3, max_follow 0 1 2 4, roughness_max 0.3 and 0.2), each with watertight 0 and 1; pt_get_stats: one launch, <= 128 VGPRs.

@@ -1,4 +1,4 @@
-"""The box invariant of the octant-ordered slab test (pt_kernel.hip, node4_step) for trees built by the device builders (bvh_builder 1:
+"""The box invariant of the octant-ordered slab test (pt_trace.h, node4_step) for trees built by the device builders (bvh_builder 1:
 LBVH, 2: PLOC): every non-empty quad slot has a finite box with lo <= hi (pt_debug_quad_info fails otherwise).  The host builder is
 covered by tests/test_quad_boxes.py."""
 import numpy as np

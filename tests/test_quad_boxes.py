@@ -1,4 +1,4 @@
-"""The box invariant of the octant-ordered slab test (pt_kernel.hip, node4_step): the quad-node step takes the lo row of an axis as the
+"""The box invariant of the octant-ordered slab test (pt_trace.h, node4_step): the quad-node step takes the lo row of an axis as the
 entry plane for a positive reciprocal direction and the hi row for a negative one, which equals the per-axis min / max only when every
 non-empty slot has a finite box with lo <= hi.  pt_debug_quad_info checks every slot of the host-built quad nodes (and that empty slots
 carry {+inf, +inf}); these scenes push the builder at slivers, degenerate and NaN / infinite vertices."""
