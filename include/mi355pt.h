@@ -170,7 +170,7 @@ int pt_render(pt_ctx* ctx, const pt_camera* cam, int32_t width, int32_t height, 
  * every call that touches what a frame in flight uses is ordered after the context's LAST ASYNCHRONOUS CALL, whichever stream that
  * call was given.  So any call of this header may follow a pt_*_device call at once, with no pt_synchronize between them.
  *   - The asynchronous calls (pt_render_device, pt_render_batch_device, pt_render_aov_device, pt_render_aov_follow_device, pt_render_aov_batch_device, pt_denoise_device,
- *     pt_denoise_batch_device, pt_denoise_var_device, pt_accum_add_device, pt_accum_denoise_device, pt_accum_reproject_device, pt_upsample_device, pt_trace_closest_device, pt_trace_occluded_device, pt_render_rays_device, pt_reduce_framebuffer) wait ON THE
+ *     pt_denoise_batch_device, pt_denoise_var_device, pt_accum_add_device, pt_accum_denoise_device, pt_accum_reproject_device, pt_upsample_device, pt_trace_closest_device, pt_trace_occluded_device, pt_render_rays_device, pt_render_aov_rays_device, pt_reduce_framebuffer) wait ON THE
  *     DEVICE: the stream they are given waits for an event recorded at the end of the previous asynchronous call - only if that call
  *     used another stream; on the same stream the stream's own order suffices and nothing is added.  The host returns at once, with
  *     two exceptions that existed before: a frame of another size, shard or batch length rewrites the pixel queue and a frame that
@@ -178,7 +178,7 @@ int pt_render(pt_ctx* ctx, const pt_camera* cam, int32_t width, int32_t height, 
  *     before) - both first wait on the host for the frame in flight; pt_render_batch_device and pt_render_aov_batch_device
  *     return when their per-frame tables have reached HBM, i.e. after whatever precedes them on `stream`; and a pt_accum_add_device that
  *     selects its pixels returns when the count of its active set has reached the host (see there).
- *   - The blocking renders (pt_render, pt_render_batch, pt_render_aov, pt_render_aov_follow, pt_render_aov_batch, pt_accum_add), pt_denoise, pt_denoise_batch, pt_denoise_var, pt_accum_denoise, pt_accum_reproject, pt_upsample, pt_trace_closest, pt_trace_occluded and pt_render_rays run on the context's stream behind the same device-side wait
+ *   - The blocking renders (pt_render, pt_render_batch, pt_render_aov, pt_render_aov_follow, pt_render_aov_batch, pt_accum_add), pt_denoise, pt_denoise_batch, pt_denoise_var, pt_accum_denoise, pt_accum_reproject, pt_upsample, pt_trace_closest, pt_trace_occluded, pt_render_rays and pt_render_aov_rays run on the context's stream behind the same device-side wait
  *     and return with the context idle.  After a blocking call, or on the context's own stream, they add no wait at all.
  *   - The calls that change or read what a frame uses WAIT ON THE HOST for the last asynchronous call's stream (if it is not the
  *     context's) and then for the context's: pt_set_materials, pt_set_environment, pt_update_vertices, pt_upload_scene,
@@ -193,7 +193,7 @@ int pt_render(pt_ctx* ctx, const pt_camera* cam, int32_t width, int32_t height, 
 int pt_render_device(pt_ctx* ctx, const pt_camera* cam, int32_t width, int32_t height, int32_t max_samples, int32_t max_path_depth,
                      void* d_out_rgb, void* d_out_rgba8, void* stream);
 /* Waits on the host for the context's last asynchronous call - pt_render_device, pt_render_batch_device, pt_render_aov_device,
- * pt_render_aov_follow_device, pt_render_aov_batch_device, pt_denoise_device, pt_denoise_batch_device, pt_denoise_var_device, pt_accum_add_device, pt_accum_denoise_device, pt_accum_reproject_device, pt_upsample_device, pt_trace_closest_device, pt_trace_occluded_device, pt_render_rays_device or pt_reduce_framebuffer, on the stream it was given - and for the context's own stream.  Every earlier asynchronous call of the context
+ * pt_render_aov_follow_device, pt_render_aov_batch_device, pt_denoise_device, pt_denoise_batch_device, pt_denoise_var_device, pt_accum_add_device, pt_accum_denoise_device, pt_accum_reproject_device, pt_upsample_device, pt_trace_closest_device, pt_trace_occluded_device, pt_render_rays_device, pt_render_aov_rays_device or pt_reduce_framebuffer, on the stream it was given - and for the context's own stream.  Every earlier asynchronous call of the context
  * is complete then as well, whatever stream it used: each was ordered before the next (see pt_render_device).  Returns PT_E_HIP if a
  * wave's watchdog fired during the last frame (the image is then incomplete); pt_get_stats reports the same.  PT_OK at once on an idle
  * or host-only context.  A caller's stream may be destroyed once this has returned. */
@@ -761,7 +761,7 @@ int pt_prim_to_mesh(pt_ctx* ctx, int32_t prim, int32_t* mesh, int32_t* triangle)
  * blocking form stages the table in a buffer of the context's, runs on the context's stream behind the same device-side wait, and reads
  * back; the context is idle on return.
  * NOT BUILT: no pt_main flag, no pt_group_* form, no batch form, no watertight instances, no communicator, no accumulation over a ray
- * image, no guide pass for ray images (a denoised panorama needs one). */
+ * image.  The guide pass over a ray image is pt_render_aov_rays below. */
 typedef struct pt_ray_gen {      /* 64 bytes, read as four 16-byte loads */
     float org[3]; float reserved0;   /* reserved floats are NOT READ */
     float dir[3]; float reserved1;
@@ -772,6 +772,49 @@ int pt_render_rays(pt_ctx* ctx, const pt_ray_gen* rays, int32_t width, int32_t h
                    float* out_rgb, uint32_t* out_rgba8);
 int pt_render_rays_device(pt_ctx* ctx, const void* d_rays, int32_t width, int32_t height, int32_t max_samples, int32_t max_path_depth,
                           void* d_out_rgb, void* d_out_rgba8, void* stream);
+/* The guide pass over a ray image: the 8-float guide record of pt_render_aov / pt_render_aov_follow - what pt_denoise, pt_denoise_batch,
+ * pt_denoise_var and pt_upsample filter under - for a frame rendered with pt_render_rays.  The instances of csrc/pt_kernel_aov_rays.hip
+ * and csrc/pt_kernel_aov_rays_wt.hip are the follow kernels (csrc/pt_aov_follow.h) compiled with the ray generator of the ray image
+ * (gen_ray_from, csrc/pt_trace.h): quad walk only, both slab forms, both triangle tests.
+ * DEFINITION: that of pt_render_aov_follow, word for word, with ONE substitution - the camera ray.  The camera ray of sample k of pixel
+ * (px, py) is the ray of pt_render_rays: the stream is rng_init(px, py); each sample draws rx = rng_next, then ry = rng_next (both draws
+ * are made even when du = dv = 0); the record is read at launch index px + W*py; the ray starts at org and has the direction
+ *     dir_s = normalize((dir + du * rx) + dv * ry)
+ * in the arithmetic contract of csrc/pt_device.h; the four reserved floats are NOT READ.  Everything after the camera ray is
+ * pt_render_aov_follow's, unchanged: the closest-hit rule (option "watertight" selects the triangle test), the follow loop with o = org,
+ * classify, the tint and the path length, coverage from step 0, the float32 sum in sample order times 1.0f / n_samples, the 8-float
+ * layout at x + W*(H-1-y), +0 for pixels the context does not own.  max_follow = 0 gives first-hit guides (the CONSEQUENCES at
+ * pt_render_aov_follow): there is no separate first-hit entry point.
+ * CONSEQUENCES:
+ *   (a) with du = dv = 0, pixel (x, y) is bit for bit pixel (x, y) of pt_render_aov_follow at the same W, H and params under the camera
+ *       {origin = org, llc = L, horizontal = 0, vertical = 0}, whenever fl(L - org) == dir;
+ *   (b) at W = H = 1 with org = 0 the pixel is bit for bit pt_render_aov_follow's under the camera {0, dir, du, dv}: su = (0 + rx) / 1 = rx,
+ *       and x - 0 = x;
+ *   (c) sample 0 of a pixel is the first camera ray of that pixel in pt_render_rays of the same table: where the pixel's coverage at
+ *       n_samples = 1 says hit, its first surface is that path's first hit.
+ * The call honours the material table, the environment, pt_update_vertices, a pixel shard set with pt_set_pixel_shard and "watertight".
+ * "box_exact" as pt_render_rays: the default -1 judges the blocking form's origins and gives the device form the subtracting form - the
+ * buffer is the same under both.  It keeps no render state: a pt_render, an accumulation or a pt_render_rays around it is unchanged.
+ * pt_get_stats afterwards reads as after pt_render_aov: launches = 1, the guide kernel's geometry fields, kernel_ms.  pt_synchronize
+ * returns PT_E_HIP if a walk ran out of its step or stack bound.
+ * REFUSED with PT_E_INVALID, by name, before anything is touched: NULL rays / d_rays or out_aov / d_out_aov; a d_rays or d_out_aov that
+ * is not 16-byte aligned; the sizes pt_render_aov refuses; what pt_render_aov_follow refuses in p; in the blocking form and the twin
+ * (the host reads the table) a record whose org, dir, du or dv is not finite or whose dir is 0; a scene without quad nodes - option
+ * "quad" = 0 or a tree too deep for them (as pt_trace_*: there are no binary-walk instances); a context with a communicator (as
+ * pt_render_rays).  PT_E_NO_SCENE without a scene.  On a host-only context valid arguments give PT_E_NO_DEVICE and invalid ones
+ * PT_E_INVALID.  The device form cannot check the records: a record that the blocking form would refuse gives an undefined pixel, inside
+ * the walk's usual bounds.
+ * ORDERING: pt_render_aov_rays_device (W*H*8 floats left in HBM at d_out_aov) joins the asynchronous calls of the streams contract at
+ * pt_render_device and the list at pt_synchronize; d_rays stays the caller's buffer and must stay valid and unchanged until the work
+ * has completed on `stream`.  The blocking form stages the table in the buffer pt_render_rays stages it in, runs on the context's stream
+ * behind the same device-side wait, and reads back; the context is idle on return.
+ * LIMITS: those of pt_render_aov_follow.  pt_denoise does not wrap around the seam of an equirectangular panorama: its taps outside
+ * the frame are skipped, so the two columns at the seam are filtered as frame edges.
+ * NOT BUILT: no pt_main flag, no pt_group_* form, no batch form. */
+int pt_render_aov_rays(pt_ctx* ctx, const pt_ray_gen* rays, int32_t width, int32_t height, const pt_aov_params* p /* NULL = defaults */,
+                       float* out_aov);
+int pt_render_aov_rays_device(pt_ctx* ctx, const void* d_rays, int32_t width, int32_t height, const pt_aov_params* p, void* d_out_aov,
+                              void* stream);
 
 /* ---- N GPUs: pixel tiles sharded over ranks + ONE RCCL sum-reduce of the float3 framebuffer onto rank 0 (pt_comm.cpp) ----
  * No reference counterpart (the reference is single-GPU: create_context(nullptr, 1), application.cpp:62); for N > 1 these
@@ -888,6 +931,11 @@ int64_t pt_debug_aov_host(pt_ctx* ctx, const pt_camera* cam, int32_t width, int3
 /* The CPU twin of the follow mode (pt_render_aov_follow), the same way; p NULL = the defaults; PT_E_INVALID also for what that call refuses in p. */
 int64_t pt_debug_aov_follow_host(pt_ctx* ctx, const pt_camera* cam, int32_t width, int32_t height, const pt_aov_params* p, const uint32_t* pixel_ids,
                                  int64_t n_pixels, float* out);
+/* The CPU twin of the guide pass over a ray image (pt_render_aov_rays), the same way: the follow twin with the camera ray replaced by the
+ * pixel's record of `rays` (width x height records).  PT_E_INVALID also for what the blocking form refuses in the table and in p; it
+ * walks the host's binary tree, so it works whatever "quad" says, and on a host-only context. */
+int64_t pt_debug_aov_rays_host(pt_ctx* ctx, const pt_ray_gen* rays, int32_t width, int32_t height, const pt_aov_params* p,
+                               const uint32_t* pixel_ids, int64_t n_pixels, float* out);
 /* Batched device-side evaluation of the kernel's building blocks on the GPU (op codes in pt_kernel_aux.hip):
  * lets the parity tests compare them bit-for-bit with the oracle.  in/out are host arrays.
  * Ops 30..35 are RAY PROBES: in = o[3], d[3] per ray, out = {hit, t, u, v, id bits, aux} (6 floats), through the device functions of

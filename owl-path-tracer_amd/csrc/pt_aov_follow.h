@@ -16,15 +16,35 @@
 // over the 8 x 8 blocks of K frames, frame by frame: a wave's block lies in one frame, so the frame's camera (P.batch_cams) and material
 // table (P.materials + frame * n_materials * PT_MAT_STRIDE) are wave-uniform - scalar loads, no per-lane gather as in the render batch -
 // and frame f is stored W * H pixels behind frame f - 1.  With PT_BATCH = 0 the preprocessor removes all of it (`make asm-aov-follow-batch`).
+// RAY IMAGE BUILD (pt_kernel_aov_rays.hip, pt_kernel_aov_rays_wt.hip: PT_RAYGEN = 1; pt_render_aov_rays).  The same kernel as
+// pt_aov_rays_kernel / pt_aov_rays_wt_kernel, quad walk only: a sample starts on the pixel's ray record of the caller's table
+// (gen_ray_from, pt_trace.h: a 64-bit per-lane address and four 16-byte loads; the table pointer travels in P.batch_cams, batch_frames
+// stays 0) instead of the camera's ray, which is the whole difference.  The gather sits in the sample prologue, between two walks, where
+// sums, tint, RNG state and pixel are parked: 118 / 124 / 127 / 128 VGPRs, no scratch (`make asm-aov-rays`).  With PT_RAYGEN = 0 the
+// preprocessor removes all of it.
 #pragma once
 #include "pt_aov.h"
 #ifndef PT_BATCH
 #define PT_BATCH 0
 #endif
+#ifndef PT_RAYGEN
+#define PT_RAYGEN 0 // 1: pt_kernel_aov_rays.hip / pt_kernel_aov_rays_wt.hip - the camera replaced by a per-pixel ray record (pt_render_aov_rays, "RAY IMAGE BUILD" above)
+#endif
 #if PT_WATERTIGHT && PT_BATCH
 #error "batches have no watertight instances"
 #endif
-#if PT_WATERTIGHT
+#if PT_RAYGEN && PT_BATCH
+#error "batches have no ray-image instances"
+#endif
+#if PT_RAYGEN && PT_WATERTIGHT
+#define PT_AOV_FOLLOW_KERNEL pt_aov_rays_wt_kernel
+#define PT_AOV_FOLLOW_LAUNCH pt_launch_aov_rays_wt
+#define PT_AOV_FOLLOW_GEOMETRY pt_aov_rays_geometry_wt
+#elif PT_RAYGEN
+#define PT_AOV_FOLLOW_KERNEL pt_aov_rays_kernel
+#define PT_AOV_FOLLOW_LAUNCH pt_launch_aov_rays
+#define PT_AOV_FOLLOW_GEOMETRY pt_aov_rays_geometry
+#elif PT_WATERTIGHT
 #define PT_AOV_FOLLOW_KERNEL pt_aov_follow_wt_kernel
 #define PT_AOV_FOLLOW_LAUNCH pt_launch_aov_follow_wt
 #define PT_AOV_FOLLOW_GEOMETRY pt_aov_follow_geometry_wt
@@ -180,6 +200,8 @@ __global__ void __launch_bounds__(PT_WAVE, PT_AOV_WAVES_PER_EU) PT_AOV_FOLLOW_KE
             const uint32_t pxy = parku[13 * PT_WAVE];
 #if PT_BATCH
             gen_camera_ray_from(P, gp(P.batch_cams) + 12 * frame, (int)(pxy & 0xffffu), (int)(pxy >> 16), ps);
+#elif PT_RAYGEN
+            gen_ray_from(P, gp(P.batch_cams), (int)(pxy & 0xffffu), (int)(pxy >> 16), ps); // the pixel's own ray record: a per-lane gather from the table in HBM
 #else
             gen_camera_ray(P, (int)(pxy & 0xffffu), (int)(pxy >> 16), ps); // two draws; the follow loop draws nothing
 #endif
@@ -191,7 +213,7 @@ __global__ void __launch_bounds__(PT_WAVE, PT_AOV_WAVES_PER_EU) PT_AOV_FOLLOW_KE
             for (int step = 0;; ++step) {
                 Hit h;
                 h.t = kTMax; h.u = 0.0f; h.v = 0.0f; h.id = 0x7fffffff; h.slot = -1;
-#if !PT_WATERTIGHT
+#if !PT_WATERTIGHT && !PT_RAYGEN
                 if (BINARY) {
                     Counters cn;
                     closest_hit<false, PT_WAVE>(P, stack, o, d, h, cn);
@@ -249,8 +271,8 @@ __global__ void __launch_bounds__(PT_WAVE, PT_AOV_WAVES_PER_EU) PT_AOV_FOLLOW_KE
 
 extern "C" hipError_t PT_AOV_FOLLOW_GEOMETRY(int binary, int exact, int stack_entries, PtGeometry* g)
 {
-#if PT_WATERTIGHT
-    if (binary) return hipErrorInvalidValue; // the binary walk has no watertight test
+#if PT_WATERTIGHT || PT_RAYGEN
+    if (binary) return hipErrorInvalidValue; // the binary walk has no watertight test, and no ray-image instance
     const void* fn = exact ? (const void*)PT_AOV_FOLLOW_KERNEL<false, true> : (const void*)PT_AOV_FOLLOW_KERNEL<false, false>;
 #else
     const void* fn = binary ? (const void*)PT_AOV_FOLLOW_KERNEL<true, false>
@@ -276,7 +298,10 @@ extern "C" hipError_t PT_AOV_FOLLOW_LAUNCH(const PtKernelParams* p, const PtAovF
 #if PT_BATCH
     if (p->batch_frames < 1 || p->batch_cams == nullptr) return hipErrorInvalidValue; // (pt_launch_aov_follow_batch: frames, cameras and tables as pt_launch_render_batch)
 #endif
-#if PT_WATERTIGHT
+#if PT_RAYGEN
+    if (p->batch_frames != 0 || p->batch_cams == nullptr) return hipErrorInvalidValue; // (pt_launch_aov_rays*: the table in the batch cameras' place, as pt_launch_render_rayimage)
+#endif
+#if PT_WATERTIGHT || PT_RAYGEN
     if (binary) return hipErrorInvalidValue;
 #else
     if (binary) hipLaunchKernelGGL((PT_AOV_FOLLOW_KERNEL<true, false>), dim3(grid), dim3(PT_WAVE), lds_bytes, stream, *p, *a);

@@ -6,6 +6,8 @@
 // compiles, run by the CPU under the same contract (binary32, -ffp-contract=off, fma only where spelled, correctly rounded division
 // and sqrt).  What is restated here is what the kernel takes from pt_trace.h, which is device code throughout: the camera ray
 // (gen_camera_ray), interp3 and the miss branch / attribute fetch of shade_hit - each a few lines, once for both twin pixels, cited below.
+// pt_debug_aov_rays_host, the twin of the guide pass over a ray image (pt_render_aov_rays), is the follow twin with the camera ray
+// replaced by the pixel's ray record (gen_ray_from): ONE follow loop serves both.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -38,6 +40,7 @@ struct AovScene {
     const HostScene* s;
     std::vector<int32_t> slot_of; // global triangle id -> leaf-order slot (the host walk reports the id, the records are in leaf order)
     v3 origin, llc, hor, ver;     // the camera
+    const pt_ray_gen* rays;       // a ray image's table of W * H records instead (pt_debug_aov_rays_host); null: the camera
     int W, H, n;
     bool wt;
 };
@@ -50,6 +53,16 @@ v3 camera_dir(const AovScene& A, int px, int py, uint32_t& rng)
     const float su = ((float)px + rx) / (float)A.W;
     const float sv = ((float)py + ry) / (float)A.H;
     return normalize(((A.llc + A.hor * su) + A.ver * sv) - A.origin);
+}
+
+// gen_ray_from: the next sample's ray of pixel (px, py) from its record of the ray image - the same two draws, then the record's ray
+void table_ray(const AovScene& A, int px, int py, uint32_t& rng, v3& o, v3& d)
+{
+    const float rx = rng_next(rng);
+    const float ry = rng_next(rng);
+    const pt_ray_gen& r = A.rays[(size_t)px + (size_t)A.W * (size_t)py];
+    o = V(r.org[0], r.org[1], r.org[2]);
+    d = normalize((V(r.dir[0], r.dir[1], r.dir[2]) + V(r.du[0], r.du[1], r.du[2]) * rx) + V(r.dv[0], r.dv[1], r.dv[2]) * ry);
 }
 
 // shade_hit's miss branch: what a ray along dir sees of the environment
@@ -159,7 +172,9 @@ void aov_follow_pixel(const AovScene& A, const pt_aov_params& prm, int px, int p
     v3 s_alb = vs(0.0f), s_nrm = vs(0.0f);
     float s_alpha = 0.0f, s_depth = 0.0f;
     for (int k = 0; k < A.n; ++k) {
-        v3 o = A.origin, d = camera_dir(A, px, py, rng);
+        v3 o = A.origin, d;
+        if (A.rays) table_ray(A, px, py, rng, o, d); // (pt_aov_rays_kernel: the one difference)
+        else d = camera_dir(A, px, py, rng);
         v3 tint = vs(1.0f), alb = vs(0.0f), nrm = vs(0.0f);
         float dist = 0.0f, alpha = 0.0f, depth = 0.0f;
         for (int step = 0;; ++step) {
@@ -212,8 +227,8 @@ void aov_follow_pixel(const AovScene& A, const pt_aov_params& prm, int px, int p
 }
 
 // What both twins take: the argument checks of pt_debug_aov_host, the scene's host copies, the slot table
-int64_t aov_host(pt_ctx* c, const pt_camera* cam, int32_t W, int32_t H, int32_t n_samples, const uint32_t* pixel_ids, int64_t n_pixels, float* out, const pt_aov_params* follow,
-                 const char* who);
+int64_t aov_host(pt_ctx* c, const pt_camera* cam, const pt_ray_gen* rays, int32_t W, int32_t H, int32_t n_samples, const uint32_t* pixel_ids, int64_t n_pixels, float* out,
+                 const pt_aov_params* follow, const char* who);
 
 } // namespace
 
@@ -247,29 +262,47 @@ extern "C" int64_t pt_debug_aov_follow_host(pt_ctx* c, const pt_camera* cam, int
     pt_aov_params prm;
     const int rc = check_aov_params(c, p, "pt_debug_aov_follow_host", &prm);
     if (rc) return rc;
-    return aov_host(c, cam, W, H, prm.n_samples, pixel_ids, n_pixels, out, &prm, "pt_debug_aov_follow_host");
+    return aov_host(c, cam, nullptr, W, H, prm.n_samples, pixel_ids, n_pixels, out, &prm, "pt_debug_aov_follow_host");
+}
+
+extern "C" int64_t pt_debug_aov_rays_host(pt_ctx* c, const pt_ray_gen* rays, int32_t W, int32_t H, const pt_aov_params* p, const uint32_t* pixel_ids, int64_t n_pixels, float* out)
+{
+    if (!c) return PT_E_INVALID;
+    if (n_pixels < 0 || (n_pixels > 0 && !pixel_ids)) return fail(c, PT_E_INVALID, "pt_debug_aov_rays_host: %lld pixels%s", (long long)n_pixels, pixel_ids ? "" : ", pixel_ids NULL");
+    int rc;
+    if ((rc = check_ray_ptrs(c, "pt_debug_aov_rays_host", rays, out, "out", false))) return rc;
+    pt_aov_params prm;
+    if ((rc = check_aov_params(c, p, "pt_debug_aov_rays_host", &prm))) return rc;
+    if (!c->have_scene) return fail(c, PT_E_NO_SCENE, "pt_debug_aov_rays_host: no geometries (pt_upload_scene not called)");
+    return aov_host(c, nullptr, rays, W, H, prm.n_samples, pixel_ids, n_pixels, out, &prm, "pt_debug_aov_rays_host");
 }
 
 extern "C" int64_t pt_debug_aov_host(pt_ctx* c, const pt_camera* cam, int32_t W, int32_t H, int32_t n_samples, const uint32_t* pixel_ids, int64_t n_pixels, float* out)
 {
     if (!c || !cam || !out || n_pixels < 0 || (n_pixels > 0 && !pixel_ids)) return PT_E_INVALID;
     if (!c->have_scene) return fail(c, PT_E_NO_SCENE, "no geometries (pt_upload_scene not called)");
-    return aov_host(c, cam, W, H, n_samples, pixel_ids, n_pixels, out, nullptr, "pt_debug_aov_host");
+    return aov_host(c, cam, nullptr, W, H, n_samples, pixel_ids, n_pixels, out, nullptr, "pt_debug_aov_host");
 }
 
 namespace {
-int64_t aov_host(pt_ctx* c, const pt_camera* cam, int32_t W, int32_t H, int32_t n_samples, const uint32_t* pixel_ids, int64_t n_pixels, float* out, const pt_aov_params* follow,
-                 const char* who)
+int64_t aov_host(pt_ctx* c, const pt_camera* cam, const pt_ray_gen* rays, int32_t W, int32_t H, int32_t n_samples, const uint32_t* pixel_ids, int64_t n_pixels, float* out,
+                 const pt_aov_params* follow, const char* who)
 {
     if (W <= 0 || H <= 0 || W > 65535 || H > 65535 || n_samples <= 0 || (int64_t)W * H > (int64_t)0x7fffffff)
         return fail(c, PT_E_INVALID, "bad guide pass size %dx%d, %d samples", W, H, n_samples);
     for (int64_t i = 0; i < n_pixels; ++i)
         if (pixel_ids[i] >= (uint32_t)W * (uint32_t)H) return fail(c, PT_E_INVALID, "%s: pixel id %u outside the %dx%d frame", who, pixel_ids[i], W, H);
+    int rc;
+    if (rays && (rc = check_ray_table(c, who, rays, W, H, false, false))) return rc; // the records, as the blocking form
     sync_host_scene(c);
     AovScene A;
     A.s = &c->scene;
-    A.origin = V(cam->origin[0], cam->origin[1], cam->origin[2]); A.llc = V(cam->llc[0], cam->llc[1], cam->llc[2]);
-    A.hor = V(cam->horizontal[0], cam->horizontal[1], cam->horizontal[2]); A.ver = V(cam->vertical[0], cam->vertical[1], cam->vertical[2]);
+    A.rays = rays;
+    A.origin = A.llc = A.hor = A.ver = vs(0.0f);
+    if (cam) {
+        A.origin = V(cam->origin[0], cam->origin[1], cam->origin[2]); A.llc = V(cam->llc[0], cam->llc[1], cam->llc[2]);
+        A.hor = V(cam->horizontal[0], cam->horizontal[1], cam->horizontal[2]); A.ver = V(cam->vertical[0], cam->vertical[1], cam->vertical[2]);
+    }
     A.W = W; A.H = H; A.n = n_samples;
     A.wt = c->opt.watertight != 0; // the walk follows the option as the render does
     A.slot_of.assign((size_t)c->scene.n_triangles, -1);

@@ -4,6 +4,7 @@
 // blocking entry points.
 // None reads the render's pixel queue or touches its buffers and state (d_laps, slots): their own are d_aov_ws, d_dn_ws, d_dn_var and d_up_ws.
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 
 #include "pt_internal.h"
@@ -52,8 +53,12 @@ const struct AovInstance { AovGeometry geometry; AovLaunch launch; } kAovInstanc
     {{{pt_aov_follow_geometry, pt_launch_aov_follow}, {pt_aov_follow_batch_geometry, pt_launch_aov_follow_batch}}, {{pt_aov_follow_geometry_wt, pt_launch_aov_follow_wt}, {}}},
 };
 
+// The ray-image instances of the follow kernel (pt_render_aov_rays), by [watertight]: quad walk only, single frames only.
+const AovInstance kAovRaysInstance[2] = {{pt_aov_rays_geometry, pt_launch_aov_rays}, {pt_aov_rays_geometry_wt, pt_launch_aov_rays_wt}};
+
 // What a guide pass renders: ONE frame from `cam` on the single-frame kernels, or frames [0, n_frames) of a batch (frames != null) on
-// the batch instances, their buffers back to back in d_out (W*H*8 floats per frame).
+// the batch instances, their buffers back to back in d_out (W*H*8 floats per frame), or ONE frame over a ray image (cam and frames null)
+// on the ray-image instances.
 struct AovJob {
     const pt_camera* cam;
     const pt_frame* frames;
@@ -62,6 +67,12 @@ struct AovJob {
     void* d_out;
     hipStream_t stream;
     bool reduce;                 // with a communicator: ONE sum-reduce onto rank 0 per launch sequence, over all of its frames
+    // a ray image (pt_render_aov_rays; follow != null): the table of W * H pt_ray_gen records in HBM; far_o: its largest |org| component, which
+    // decides the slab form as the camera's origin does in walk_params (+infinity: unknown, rays_image_device of pt_render.cpp); host_rays:
+    // the blocking form's table, staged in d_ray_image first
+    const void* d_rays = nullptr;
+    float far_o = 0.0f;
+    const pt_ray_gen* host_rays = nullptr;
 };
 
 // One launch of the guide kernel per launch sequence over the 8 x 8 pixel blocks of its frames - a single frame is one sequence, a batch
@@ -74,18 +85,22 @@ int aov_device(pt_ctx* c, const AovJob& j)
     // quad: the quad instances walk the scene - its quad nodes, or a root that is itself a leaf (a scene of a few triangles has no nodes at
     // all: root4 is the leaf reference, the walk is one leaf step and touches no node).  Only a tree too deep for quad nodes (nodes4
     // cleared, root4 >= 0) and option quad = 0 leave the binary walk.
-    const bool batch = j.frames != nullptr, quad = c->opt.quad && (!c->scene.nodes4.empty() || c->scene.root4 < 0), wt = c->opt.watertight != 0;
+    const bool batch = j.frames != nullptr, rays = j.d_rays != nullptr, quad = c->opt.quad && (!c->scene.nodes4.empty() || c->scene.root4 < 0), wt = c->opt.watertight != 0;
     const int W = j.W, H = j.H, n_frames = batch ? j.n_frames : 1, binary = quad ? 0 : 1;
     hipStream_t stream = j.stream;
+    if (rays && !quad) return fail(c, PT_E_INVALID, "pt_render_aov_rays: the guide pass over a ray image needs quad nodes"); // (check_aov_rays_args, by name)
     if (!quad && wt)
         return fail(c, PT_E_INVALID, "%s: without quad nodes (option quad = 0, or a tree too deep for them) the guide pass runs the binary walk, which has no watertight test (option watertight = 1)", j.follow ? "pt_render_aov_follow" : "pt_render_aov");
     if (quad && (c->scene.bvh.tris.size() * sizeof(PtTri) > 0xffffffffull || c->scene.nodes4.size() * sizeof(PtNode4) > 0xffffffffull))
         return fail(c, PT_E_LIMIT, "the guide kernel needs triangle records and quad nodes below 4 GiB each (%zu triangle slots, %zu quad nodes)", c->scene.bvh.tris.size(), c->scene.nodes4.size());
     const int64_t kmax = batch ? batch_max_frames(W, H, c->opt.batch_frames) : 1;
     if (kmax < 1) return fail(c, PT_E_LIMIT, "pt_render_aov_batch: one %dx%d frame already exceeds a launch sequence (< 2^24 pixels)", W, H);
-    const pt_camera* cam0 = batch ? &j.frames[0].camera : j.cam;
+    pt_camera ray_cam{}; // a ray image has no camera: walk_params reads the origin alone, the kernel nothing of P.cam
+    ray_cam.origin[0] = j.far_o;
+    const pt_camera* cam0 = rays ? &ray_cam : (batch ? &j.frames[0].camera : j.cam);
     PtKernelParams P;
     walk_params(c, cam0, P); // the scene, the slab form ("box_exact" as the render; of a batch: chosen per launch sequence below)
+    ray_cam.origin[0] = 0.0f;
     P.nodes8 = nullptr;
     P.groups = 0;
     if (quad) {
@@ -97,7 +112,8 @@ int aov_device(pt_ctx* c, const AovJob& j)
         P.root = c->scene.bvh.root;
         P.stack_entries = c->scene.bvh.depth < 1 ? 1 : c->scene.bvh.depth;
     }
-    const AovInstance& inst = kAovInstance[j.follow != nullptr][wt][batch];
+    const AovInstance& inst = rays ? kAovRaysInstance[wt] : kAovInstance[j.follow != nullptr][wt][batch];
+    if (rays) P.batch_cams = (const float*)j.d_rays; // (batch_frames stays 0: pt_launch_aov_rays checks both)
     // both slab forms may run in one batch: neither may spill, and they share the launch geometry (block, LDS)
     PtGeometry g{}, gx{};
     hipError_t ge = inst.geometry(binary, batch ? 0 : P.box_exact, P.stack_entries, &g);
@@ -186,6 +202,12 @@ int aov_blocking(pt_ctx* c, AovJob j, float* out_aov)
         j.d_out = c->d_aov.p;
         j.stream = c->stream;
         j.reduce = true;
+        if (j.host_rays) { // a ray image: the table staged where pt_render_rays stages it
+            const size_t bytes = (size_t)j.W * (size_t)j.H * sizeof(pt_ray_gen);
+            if ((rc = ensure(c, c->d_ray_image, bytes))) return rc;
+            HIP_TRY(c, hipMemcpyAsync(c->d_ray_image.p, j.host_rays, bytes, hipMemcpyHostToDevice, c->stream));
+            j.d_rays = c->d_ray_image.p;
+        }
         if ((rc = aov_device(c, j))) return rc;
         return drain(c, {{root ? out_aov : nullptr, c->d_aov.p, n_floats * 4}});
     });
@@ -205,6 +227,24 @@ int check_aov_batch_args(pt_ctx* c, const char* who, const pt_frame* frames, int
     int tile = c->tile < 8 ? 8 : c->tile; // as pt_shard_pixels rounds it
     tile = (tile + 7) & ~7;
     if (pt_shard_pixels(W, H, tile, c->rank, c->world, nullptr, 0) < 0) return fail(c, PT_E_INVALID, "%s: invalid pixel shard (%d of %d)", who, c->rank, c->world);
+    return need_device(c);
+}
+
+// What the two forms of the guide pass over a ray image refuse alike before anything is touched, a host-only context last (device: rays
+// and out are device pointers, and the host cannot look at the records).  The table's checks are pt_render_rays' (pt_render.cpp), the
+// parameters' and the sizes' pt_render_aov_follow's.
+int check_aov_rays_args(pt_ctx* c, const char* who, const void* rays, int W, int H, const pt_aov_params* p, const void* out_aov, bool device, pt_aov_params* eff)
+{
+    int rc;
+    if ((rc = check_ray_ptrs(c, who, rays, out_aov, device ? "d_out_aov" : "out_aov", device))) return rc;
+    if (device && ((uintptr_t)out_aov & 15u)) return fail(c, PT_E_INVALID, "%s: d_out_aov is not 16-byte aligned (a guide record is two 16-byte stores)", who);
+    if ((rc = check_aov_params(c, p, who, eff))) return rc;
+    if (!c->have_scene) return fail(c, PT_E_NO_SCENE, "%s: no geometries (pt_upload_scene not called)", who);
+    if (W <= 0 || H <= 0 || W > 65535 || H > 65535 || (int64_t)W * H > (int64_t)0x7fffffff) return fail(c, PT_E_INVALID, "%s: bad guide pass size %dx%d", who, W, H);
+    // the ray-image instances walk the quad nodes - or a root that is itself a leaf - and nothing else (as the ray queries, pt_rays_host.cpp)
+    if (!c->opt.quad || (c->scene.nodes4.empty() && c->scene.root4 >= 0))
+        return fail(c, PT_E_INVALID, "%s: the guide pass over a ray image needs quad nodes (%s); there are no binary-walk instances", who, !c->opt.quad ? "option quad = 0" : "the tree is too deep for them");
+    if ((rc = check_ray_table(c, who, rays, W, H, device, true))) return rc;
     return need_device(c);
 }
 
@@ -517,6 +557,31 @@ int pt_render_aov_batch(pt_ctx* c, const pt_frame* frames, int32_t n_frames, int
     int rc;
     if ((rc = check_aov_batch_args(c, "pt_render_aov_batch", frames, n_frames, n_materials, W, H, p, &prm))) return rc;
     return aov_blocking(c, AovJob{nullptr, frames, n_frames, W, H, prm.n_samples, &prm}, out_aov);
+}
+
+int pt_render_aov_rays_device(pt_ctx* c, const void* d_rays, int32_t W, int32_t H, const pt_aov_params* p, void* d_out_aov, void* stream_v)
+{
+    if (!c) return PT_E_INVALID;
+    pt_aov_params prm;
+    int rc;
+    if ((rc = check_aov_rays_args(c, "pt_render_aov_rays_device", d_rays, W, H, p, d_out_aov, true, &prm))) return rc;
+    AovJob j{nullptr, nullptr, 1, W, H, prm.n_samples, &prm};
+    j.d_rays = d_rays;
+    j.far_o = INFINITY; // the records are the caller's and unknown here: the slab form that holds at any distance, unless the option chooses
+    return aov_async(c, j, d_out_aov, stream_v);
+}
+
+int pt_render_aov_rays(pt_ctx* c, const pt_ray_gen* rays, int32_t W, int32_t H, const pt_aov_params* p, float* out_aov)
+{
+    if (!c) return PT_E_INVALID;
+    pt_aov_params prm;
+    int rc;
+    if ((rc = check_aov_rays_args(c, "pt_render_aov_rays", rays, W, H, p, out_aov, false, &prm))) return rc;
+    AovJob j{nullptr, nullptr, 1, W, H, prm.n_samples, &prm};
+    j.host_rays = rays;
+    j.d_rays = rays; // (a ray image; aov_blocking puts the staged table here)
+    j.far_o = ray_table_far_o(rays, (size_t)W * (size_t)H);
+    return aov_blocking(c, j, out_aov);
 }
 
 int pt_denoise_device(pt_ctx* c, const void* d_rgb, const void* d_aov, int32_t W, int32_t H, const pt_denoise_params* p, void* d_out_rgb, void* d_out_rgba8, void* stream_v)

@@ -185,6 +185,10 @@ int check_watchdog(pt_ctx* c);
 PT_LOCAL void fill_params(pt_ctx* c, PtKernelParams& P);
 PT_LOCAL void walk_params(pt_ctx* c, const pt_camera* cam, PtKernelParams& P);
 PT_LOCAL int check_render_args(pt_ctx* c, int W, int H, int max_samples, int max_depth, const int32_t* n_materials = nullptr);
+// a ray image's table (pt_render_rays*, pt_render_aov_rays* and the guide twin): pointers; then communicator (comm) and, of a host table, the records
+PT_LOCAL int check_ray_ptrs(pt_ctx* c, const char* who, const void* rays, const void* out, const char* out_name, bool device);
+PT_LOCAL int check_ray_table(pt_ctx* c, const char* who, const void* rays, int W, int H, bool device, bool comm);
+PT_LOCAL float ray_table_far_o(const pt_ray_gen* rays, size_t n); // the largest |org| component: decides the slab form as a camera's origin does
 PT_LOCAL int64_t batch_max_frames(int W, int H, int max_frames);
 PT_LOCAL int stage_batch_tables(pt_ctx* c, const pt_frame* frames, int n_frames, hipStream_t stream);
 struct D2H { void* dst; const void* src; size_t bytes; }; // a copy to a host buffer of the caller; dst null: none

@@ -250,6 +250,12 @@ hipError_t pt_aov_follow_geometry_wt(int binary, int exact, int stack_entries, P
 // the first frame's table, a->out = the first frame's buffers; PtKernelParams::batch_*), same conventions
 hipError_t pt_launch_aov_follow_batch(const PtKernelParams* p, const PtAovFollowArgs* a, int binary, int grid, size_t lds_bytes, hipStream_t stream);
 hipError_t pt_aov_follow_batch_geometry(int binary, int exact, int stack_entries, PtGeometry* g);
+// pt_kernel_aov_rays.hip / pt_kernel_aov_rays_wt.hip: the ray-image instances of the follow kernels (p->batch_cams = the table of W * H pt_ray_gen
+// records, p->batch_frames = 0; PtKernelParams::batch_cams), same conventions; quad walk only: binary = 1 answers hipErrorInvalidValue
+hipError_t pt_launch_aov_rays(const PtKernelParams* p, const PtAovFollowArgs* a, int binary, int grid, size_t lds_bytes, hipStream_t stream);
+hipError_t pt_aov_rays_geometry(int binary, int exact, int stack_entries, PtGeometry* g);
+hipError_t pt_launch_aov_rays_wt(const PtKernelParams* p, const PtAovFollowArgs* a, int binary, int grid, size_t lds_bytes, hipStream_t stream);
+hipError_t pt_aov_rays_geometry_wt(int binary, int exact, int stack_entries, PtGeometry* g);
 size_t pt_refit_workspace_bytes(void);
 // gather, extent, one refit launch per level, propagate - all on `stream`, `first` recorded before the first kernel, `last` after the last
 hipError_t pt_launch_refit(const PtRefitArgs* a, hipEvent_t first, hipEvent_t last, hipStream_t stream);

@@ -32,6 +32,10 @@ hipError_t pt_launch_aov_follow_wt(const PtKernelParams*, const PtAovFollowArgs*
 hipError_t pt_aov_follow_geometry_wt(int, int, int, PtGeometry*) { return hipErrorNotSupported; }
 hipError_t pt_launch_aov_follow_batch(const PtKernelParams*, const PtAovFollowArgs*, int, int, size_t, hipStream_t) { return hipErrorNotSupported; }
 hipError_t pt_aov_follow_batch_geometry(int, int, int, PtGeometry*) { return hipErrorNotSupported; }
+hipError_t pt_launch_aov_rays(const PtKernelParams*, const PtAovFollowArgs*, int, int, size_t, hipStream_t) { return hipErrorNotSupported; }
+hipError_t pt_aov_rays_geometry(int, int, int, PtGeometry*) { return hipErrorNotSupported; }
+hipError_t pt_launch_aov_rays_wt(const PtKernelParams*, const PtAovFollowArgs*, int, int, size_t, hipStream_t) { return hipErrorNotSupported; }
+hipError_t pt_aov_rays_geometry_wt(int, int, int, PtGeometry*) { return hipErrorNotSupported; }
 hipError_t pt_launch_rays(const PtKernelParams*, const PtRaysArgs*, int, int, size_t, hipStream_t) { return hipErrorNotSupported; }
 hipError_t pt_rays_geometry(int, int, PtGeometry*) { return hipErrorNotSupported; }
 hipError_t pt_launch_rays_wt(const PtKernelParams*, const PtRaysArgs*, int, int, size_t, hipStream_t) { return hipErrorNotSupported; }

@@ -93,6 +93,44 @@ int check_render_args(pt_ctx* c, int W, int H, int max_samples, int max_depth, c
     return PT_OK;
 }
 
+// A ray image's pointers (pt_render_rays*, pt_render_aov_rays*): NULL table or output, a device table that is not 16-byte aligned.
+int check_ray_ptrs(pt_ctx* c, const char* who, const void* rays, const void* out, const char* out_name, bool device)
+{
+    if (!rays || !out) return fail(c, PT_E_INVALID, "%s: NULL %s", who, !rays ? (device ? "d_rays" : "rays") : out_name);
+    if (device && ((uintptr_t)rays & 15u)) return fail(c, PT_E_INVALID, "%s: d_rays is not 16-byte aligned (a record is four 16-byte loads)", who);
+    return PT_OK;
+}
+
+// A ray image's table, after the sizes: a communicator (comm: the entry points; the twin renders none), and - where the host can read
+// the W * H records - a record that is not finite or has no direction to normalize.
+int check_ray_table(pt_ctx* c, const char* who, const void* rays, int W, int H, bool device, bool comm)
+{
+    if (comm && c->comm) return fail(c, PT_E_INVALID, "%s: a context with a communicator renders no ray images yet (render the ranks' shards with pt_set_pixel_shard and reduce them yourself)", who);
+    if (!device) { // the records themselves: finite, and a direction to normalize
+        const pt_ray_gen* r = (const pt_ray_gen*)rays;
+        const int64_t n = (int64_t)W * H;
+        for (int64_t i = 0; i < n; ++i) {
+            const float* v[4] = {r[i].org, r[i].dir, r[i].du, r[i].dv};
+            static const char* const name[4] = {"org", "dir", "du", "dv"};
+            for (int k = 0; k < 4; ++k)
+                if (!std::isfinite(v[k][0]) || !std::isfinite(v[k][1]) || !std::isfinite(v[k][2]))
+                    return fail(c, PT_E_INVALID, "%s: record %lld (pixel %lld, %lld): %s is not finite", who, (long long)i, (long long)(i % W), (long long)(i / W), name[k]);
+            if (r[i].dir[0] == 0.0f && r[i].dir[1] == 0.0f && r[i].dir[2] == 0.0f)
+                return fail(c, PT_E_INVALID, "%s: record %lld (pixel %lld, %lld): dir is 0", who, (long long)i, (long long)(i % W), (long long)(i / W));
+        }
+    }
+    return PT_OK;
+}
+
+// The largest |org| component of a host table: what decides the slab form of a ray image as the camera's origin does in walk_params.
+float ray_table_far_o(const pt_ray_gen* rays, size_t n)
+{
+    float far_o = 0.0f;
+    for (size_t i = 0; i < n; ++i)
+        for (int a = 0; a < 3; ++a) far_o = std::max(far_o, std::fabs(rays[i].org[a]));
+    return far_o;
+}
+
 // ---- batches (pt_render_batch) ------------------------------------------------------------------------------------------
 // K frames of the uploaded scene are stacked into a virtual image of W x (K * H) and rendered by ONE launch sequence over the queue of
 // that image (pt_kernel_batch.hip).  What bounds K, from the code that sets each limit:
@@ -669,32 +707,19 @@ int render_device(pt_ctx* c, const pt_camera* cam, int W, int H, int max_samples
 
 // ---- ray images (pt_render_rays) ----------------------------------------------------------------------------------------
 // What both forms refuse before anything is touched, a host-only context last (who: the entry point; device: rays is a device pointer,
-// whose records the host cannot look at).
+// whose records the host cannot look at).  The table's own checks are check_ray_ptrs / check_ray_table above, which the guide pass over a
+// ray image shares (pt_render_aov_rays, pt_guides.cpp).
 int check_ray_image_args(pt_ctx* c, const char* who, const void* rays, int W, int H, int max_samples, int max_depth, const void* out_rgb, bool device)
 {
-    if (!rays || !out_rgb) return fail(c, PT_E_INVALID, "%s: NULL %s", who, !rays ? (device ? "d_rays" : "rays") : (device ? "d_out_rgb" : "out_rgb"));
-    if (device && ((uintptr_t)rays & 15u)) return fail(c, PT_E_INVALID, "%s: d_rays is not 16-byte aligned (a record is four 16-byte loads)", who);
-    int rc = check_render_args(c, W, H, max_samples, max_depth);
-    if (rc) return rc;
+    int rc;
+    if ((rc = check_ray_ptrs(c, who, rays, out_rgb, device ? "d_out_rgb" : "out_rgb", device))) return rc;
+    if ((rc = check_render_args(c, W, H, max_samples, max_depth))) return rc;
     // what only exists for a camera's frame is refused by name, never rendered some other way
     if (c->opt.kernel != 2) return fail(c, PT_E_INVALID, "%s: the lane-per-pixel kernel (option kernel = 1) has no ray-image form", who);
     if (c->opt.watertight) return fail(c, PT_E_INVALID, "%s: ray images have no watertight instances (option watertight = 1); set watertight = 0", who);
     if (c->opt.latency) return fail(c, PT_E_INVALID, "%s: the per-pixel latency diagnostics (option latency) belong to pt_render; switch them off for a ray image", who);
     if (c->opt.timeline) return fail(c, PT_E_INVALID, "%s: the chunk timeline (option timeline) belongs to pt_render; switch it off for a ray image", who);
-    if (c->comm) return fail(c, PT_E_INVALID, "%s: a context with a communicator renders no ray images yet (render the ranks' shards with pt_set_pixel_shard and reduce them yourself)", who);
-    if (!device) { // the records themselves: finite, and a direction to normalize
-        const pt_ray_gen* r = (const pt_ray_gen*)rays;
-        const int64_t n = (int64_t)W * H;
-        for (int64_t i = 0; i < n; ++i) {
-            const float* v[4] = {r[i].org, r[i].dir, r[i].du, r[i].dv};
-            static const char* const name[4] = {"org", "dir", "du", "dv"};
-            for (int k = 0; k < 4; ++k)
-                if (!std::isfinite(v[k][0]) || !std::isfinite(v[k][1]) || !std::isfinite(v[k][2]))
-                    return fail(c, PT_E_INVALID, "%s: record %lld (pixel %lld, %lld): %s is not finite", who, (long long)i, (long long)(i % W), (long long)(i / W), name[k]);
-            if (r[i].dir[0] == 0.0f && r[i].dir[1] == 0.0f && r[i].dir[2] == 0.0f)
-                return fail(c, PT_E_INVALID, "%s: record %lld (pixel %lld, %lld): dir is 0", who, (long long)i, (long long)(i % W), (long long)(i / W));
-        }
-    }
+    if ((rc = check_ray_table(c, who, rays, W, H, device, true))) return rc;
     return need_device(c);
 }
 
@@ -830,9 +855,7 @@ int pt_render_rays(pt_ctx* c, const pt_ray_gen* rays, int32_t W, int32_t H, int3
     if ((rc = check_ray_image_args(c, "pt_render_rays", rays, W, H, max_samples, max_depth, out_rgb, false))) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t npx = (size_t)W * H;
-    float far_o = 0.0f;
-    for (size_t i = 0; i < npx; ++i)
-        for (int a = 0; a < 3; ++a) far_o = std::max(far_o, std::fabs(rays[i].org[a]));
+    const float far_o = ray_table_far_o(rays, npx);
     return blocking_call(c, [&]() -> int {
         int rc;
         if ((rc = ensure(c, c->d_out, npx * 12)) || (rc = ensure(c, c->d_ray_image, npx * sizeof(pt_ray_gen)))) return rc;

@@ -133,7 +133,7 @@ EXPORTS = ["pt_create", "pt_destroy", "pt_last_error", "pt_abi_version", "pt_upl
            "pt_accum_reproject_default_params", "pt_accum_reproject", "pt_accum_reproject_device", "pt_debug_accum_reproject_host",
            "pt_upsample_default_params", "pt_upsample", "pt_upsample_device", "pt_debug_upsample_host",
            "pt_trace_closest", "pt_trace_closest_device", "pt_trace_occluded", "pt_trace_occluded_device", "pt_debug_trace_rays_host", "pt_prim_to_mesh",
-           "pt_render_rays", "pt_render_rays_device"]
+           "pt_render_rays", "pt_render_rays_device", "pt_render_aov_rays", "pt_render_aov_rays_device", "pt_debug_aov_rays_host"]
 # pt_ray / pt_ray_hit (include/mi355pt.h "ray queries"): 32 and 16 bytes
 RAY_DTYPE = np.dtype([("org", "<f4", (3,)), ("tmax", "<f4"), ("dir", "<f4", (3,)), ("unused", "<f4")])
 HIT_DTYPE = np.dtype([("t", "<f4"), ("u", "<f4"), ("v", "<f4"), ("prim", "<i4")])
@@ -298,6 +298,10 @@ def lib():
     L.pt_prim_to_mesh.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.pt_render_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, fp, C.POINTER(C.c_uint32)]
     L.pt_render_rays_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.pt_render_aov_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(AovParams), fp]
+    L.pt_render_aov_rays_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(AovParams), C.c_void_p, C.c_void_p]
+    L.pt_debug_aov_rays_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(AovParams), C.POINTER(C.c_uint32), C.c_int64, fp]
+    L.pt_debug_aov_rays_host.restype = C.c_int64
     _lib = L
     return L
 
@@ -1079,6 +1083,38 @@ class Context:
         self._check(lib().pt_render_rays_device(self._h, C.c_void_p(d_rays), W, H, spp, max_depth, C.c_void_p(d_out_rgb),
                                                 C.c_void_p(d_out_rgba8) if d_out_rgba8 else None, C.c_void_p(stream) if stream else None),
                     "pt_render_rays_device")
+
+    def render_aov_rays(self, rays, W, H, params=None):
+        """pt_render_aov_rays: the guide buffers (H, W, 8) of render_aov_follow over a ray image - the table of render_rays (pyhost/ray_image.py
+        builds them), so that a frame of render_rays can be denoised or upsampled; params: AovParams, None = the defaults (max_follow = 0
+        gives first-hit guides).  Framebuffer order (row H - 1 - y), as render_aov_follow."""
+        r = np.ascontiguousarray(rays, RAY_GEN_DTYPE).reshape(-1)
+        if r.shape[0] != W * H:
+            raise PtError("render_aov_rays: %d records for a %dx%d ray image" % (r.shape[0], W, H))
+        out = np.empty((H, W, 8), np.float32)
+        self._check(lib().pt_render_aov_rays(self._h, r.ctypes.data_as(C.c_void_p), W, H, C.byref(params) if params is not None else None,
+                                             out.ctypes.data_as(C.POINTER(C.c_float))), "pt_render_aov_rays")
+        return out
+
+    def render_aov_rays_device(self, d_rays, W, H, d_out_aov, params=None, stream=None):
+        """pt_render_aov_rays_device: asynchronous, W * H pt_ray_gen records at the device pointer d_rays (16-byte aligned; the caller's, valid
+        and unchanged until the work has completed), W*H*8 floats left in HBM at d_out_aov (16-byte aligned); conventions of render_aov_device."""
+        self._check(lib().pt_render_aov_rays_device(self._h, C.c_void_p(d_rays), W, H, C.byref(params) if params is not None else None, C.c_void_p(d_out_aov),
+                                                    C.c_void_p(stream) if stream else None), "pt_render_aov_rays_device")
+
+    def aov_rays_host(self, rays, W, H, params=None, pixel_ids=None):
+        """pt_debug_aov_rays_host, the CPU twin of render_aov_rays (works on a host-only context); pixel_ids and result as aov_host."""
+        r = np.ascontiguousarray(rays, RAY_GEN_DTYPE).reshape(-1)
+        if r.shape[0] != W * H:
+            raise PtError("aov_rays_host: %d records for a %dx%d ray image" % (r.shape[0], W, H))
+        whole = pixel_ids is None
+        ids = np.arange(W * H, dtype=np.uint32) if whole else np.ascontiguousarray(pixel_ids, np.uint32).reshape(-1)
+        out = np.zeros((ids.size, 8), np.float32)
+        n = lib().pt_debug_aov_rays_host(self._h, r.ctypes.data_as(C.c_void_p), W, H, C.byref(params) if params is not None else None,
+                                         ids.ctypes.data_as(C.POINTER(C.c_uint32)), ids.size, out.ctypes.data_as(C.POINTER(C.c_float)))
+        if n < 0:
+            self._check(int(n), "pt_debug_aov_rays_host")
+        return out.reshape(H, W, 8)[::-1].copy() if whole else out
 
     def synchronize(self):
         self._check(lib().pt_synchronize(self._h), "pt_synchronize")
