@@ -14,7 +14,7 @@
 
 #include "../../include/mi355pt.h"
 #include "pt_accum_math.h"
-#include "pt_launch.h"
+#include "pt_instance.h"
 
 using namespace ptd;
 
@@ -86,21 +86,14 @@ __global__ __launch_bounds__(ACC_BLOCK) void pt_accum_select_kernel(PtAccumSelec
 
 extern "C" hipError_t pt_accum_geometry(PtGeometry* g)
 {
-    const void* fns[2] = {(const void*)pt_accum_select_kernel, (const void*)pt_accum_resolve_kernel};
-    hipFuncAttributes fa;
-    for (int k = 0; k < 2; ++k) { // (ends on the resolve kernel)
-        hipError_t e = hipFuncGetAttributes(&fa, fns[k]);
-        if (e != hipSuccess) return e;
-        if (fa.localSizeBytes != 0) return hipErrorInvalidConfiguration;
-    }
+    const hipError_t e = pt_refuse_scratch({(const void*)pt_accum_select_kernel});
+    if (e != hipSuccess) return e;
     g->block = ACC_BLOCK;
     g->ns = ACC_BLOCK;
     g->lds_bytes = 0;
     g->lds_levels = 0;
     g->state_words = 0;
-    g->vgprs = fa.numRegs;
-    g->max_blocks_per_cu = 0;
-    return hipSuccess;
+    return pt_complete_geometry(g, (const void*)pt_accum_resolve_kernel);
 }
 
 extern "C" hipError_t pt_launch_accum_resolve(const PtAccumArgs* a, hipStream_t stream)

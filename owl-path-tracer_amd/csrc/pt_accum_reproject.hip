@@ -13,7 +13,7 @@
 
 #include "../../include/mi355pt.h"
 #include "pt_accum_math.h"
-#include "pt_launch.h"
+#include "pt_instance.h"
 
 using namespace ptd;
 
@@ -64,19 +64,13 @@ __global__ __launch_bounds__(REPROJECT_BLOCK) void pt_accum_reproject_kernel(PtA
 
 extern "C" hipError_t pt_accum_reproject_geometry(int W, int H, PtGeometry* g, int* grid)
 {
-    hipFuncAttributes fa;
-    hipError_t e = hipFuncGetAttributes(&fa, (const void*)pt_accum_reproject_kernel);
-    if (e != hipSuccess) return e;
-    if (fa.localSizeBytes != 0) return hipErrorInvalidConfiguration;
     g->block = REPROJECT_BLOCK;
     g->ns = REPROJECT_BLOCK;
     g->lds_bytes = 0;
     g->lds_levels = 0;
     g->state_words = 0;
-    g->vgprs = fa.numRegs;
-    g->max_blocks_per_cu = 0;
     *grid = (int)(((size_t)W * (size_t)H + REPROJECT_BLOCK - 1) / REPROJECT_BLOCK);
-    return hipSuccess;
+    return pt_complete_geometry(g, (const void*)pt_accum_reproject_kernel);
 }
 
 extern "C" hipError_t pt_launch_accum_reproject(const PtAccumReprojectArgs* a, hipStream_t stream)

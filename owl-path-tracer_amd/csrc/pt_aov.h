@@ -3,7 +3,7 @@
 // instances sit at their register budgets: no room for seven more accumulators per slot), so that the render units hold the kernels
 // they always held (tests/test_watertight_host.py counts them); they take the device code of pt_trace.h and nothing of pt_kernel.hip.
 #pragma once
-#include "pt_launch.h"
+#include "pt_instance.h"
 #include "pt_trace.h"
 #ifndef PT_AOV_WAVES_PER_EU
 #define PT_AOV_WAVES_PER_EU 4 // 128 VGPRs, 16 waves per CU at 3 KB of LDS each

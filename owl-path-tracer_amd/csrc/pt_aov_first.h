@@ -90,38 +90,35 @@ __global__ void __launch_bounds__(PT_WAVE, PT_AOV_WAVES_PER_EU) PT_AOV_KERNEL(co
     }
 }
 
-extern "C" hipError_t PT_AOV_GEOMETRY(int binary, int exact, int stack_entries, PtGeometry* g)
+// The instance that serves (binary, exact), for the geometry function and the launcher alike; nullptr: no such instance.
+static const void* aov_instance(int binary, int exact)
 {
 #if PT_WATERTIGHT
-    if (binary) return hipErrorInvalidValue; // the binary walk has no watertight test
-    const void* fn = exact ? (const void*)PT_AOV_KERNEL<false, true> : (const void*)PT_AOV_KERNEL<false, false>;
+    if (binary) return nullptr; // the binary walk has no watertight test
 #else
-    const void* fn = binary ? (const void*)PT_AOV_KERNEL<true, false> : (exact ? (const void*)PT_AOV_KERNEL<false, true> : (const void*)PT_AOV_KERNEL<false, false>);
+    if (binary) return (const void*)PT_AOV_KERNEL<true, false>;
 #endif
+    return exact ? (const void*)PT_AOV_KERNEL<false, true> : (const void*)PT_AOV_KERNEL<false, false>;
+}
+
+extern "C" hipError_t PT_AOV_GEOMETRY(int binary, int exact, int stack_entries, PtGeometry* g)
+{
+    const void* fn = aov_instance(binary, exact);
+    if (!fn) return hipErrorInvalidValue;
     g->block = PT_WAVE;
     g->ns = PT_WAVE;
     g->lds_levels = binary ? stack_entries : PT_LDS_STACK;
     g->lds_bytes = (size_t)g->lds_levels * PT_WAVE * 4;
     g->state_words = 0;
-    hipFuncAttributes fa;
-    hipError_t e = hipFuncGetAttributes(&fa, fn);
-    if (e != hipSuccess) return e;
-    if (fa.localSizeBytes != 0) return hipErrorInvalidConfiguration; // as the render instances: a build that spills is refused
-    g->vgprs = fa.numRegs;
-    g->max_blocks_per_cu = 0;
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(&g->max_blocks_per_cu, fn, g->block, g->lds_bytes);
+    return pt_complete_geometry(g, fn);
 }
 
 extern "C" hipError_t PT_AOV_LAUNCH(const PtKernelParams* p, const PtAovArgs* a, int binary, int grid, size_t lds_bytes, hipStream_t stream)
 {
     if (grid < 1) grid = 1;
-#if PT_WATERTIGHT
-    if (binary) return hipErrorInvalidValue;
-#else
-    if (binary) hipLaunchKernelGGL((PT_AOV_KERNEL<true, false>), dim3(grid), dim3(PT_WAVE), lds_bytes, stream, *p, *a);
-    else
-#endif
-    if (p->box_exact) hipLaunchKernelGGL((PT_AOV_KERNEL<false, true>), dim3(grid), dim3(PT_WAVE), lds_bytes, stream, *p, *a);
-    else hipLaunchKernelGGL((PT_AOV_KERNEL<false, false>), dim3(grid), dim3(PT_WAVE), lds_bytes, stream, *p, *a);
+    const void* fn = aov_instance(binary, p->box_exact);
+    if (!fn) return hipErrorInvalidValue;
+    void* args[] = {(void*)p, (void*)a};
+    (void)hipLaunchKernel(fn, dim3(grid), dim3(PT_WAVE), args, lds_bytes, stream);
     return hipGetLastError();
 }

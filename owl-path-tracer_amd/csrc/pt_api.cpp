@@ -252,8 +252,7 @@ int pt_set_pixel_shard(pt_ctx* c, int32_t rank, int32_t world_size, int32_t tile
 int64_t pt_shard_pixels(int32_t W, int32_t H, int32_t tile, int32_t rank, int32_t world, uint32_t* ids, int64_t cap)
 {
     if (W <= 0 || H <= 0 || world < 1 || rank < 0 || rank >= world) return -1;
-    if (tile < 8) tile = 8;
-    tile = (tile + 7) & ~7;
+    tile = shard_tile(tile);
     int ntx = (W + tile - 1) / tile, nty = (H + tile - 1) / tile;
     int64_t n = 0;
     for (int ty = 0; ty < nty; ++ty)

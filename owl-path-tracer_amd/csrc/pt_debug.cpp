@@ -26,9 +26,7 @@ int probe_eval(pt_ctx* c, PtKernelParams& P, int op, int in_stride, float* out, 
     size_t lds = 0, scratch_words = 0;
     if (!group) {
         if (c->scene.nodes4.empty() && c->scene.root4 >= 0) return fail(c, PT_E_LIMIT, "ray probe: the scene has no quad nodes (tree too deep for the quad walk)");
-        P.nodes4 = (const PtNode4*)c->d_nodes4.p;
-        P.root = c->scene.root4;
-        P.stack_entries = 3 * c->scene.depth4 + 1;
+        quad_walk_params(c, P);
         const bool overflow = op >= PT_PROBE_QUAD_OVF;
         const int levels = P.stack_entries + 3; // the LDS-only step stores three entries above the top whether or not it pushes them
         grid = (int)std::min<int64_t>((n + 63) / 64, 2048);

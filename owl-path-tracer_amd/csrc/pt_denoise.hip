@@ -21,7 +21,7 @@
 
 #include "../../include/mi355pt.h"
 #include "pt_device.h"
-#include "pt_launch.h"
+#include "pt_instance.h"
 
 using namespace ptd;
 
@@ -177,25 +177,18 @@ extern "C" hipError_t pt_denoise_geometry(int W, int H, int K, PtGeometry* g, in
 extern "C" hipError_t pt_denoise_geometry(int W, int H, PtGeometry* g, int* grid)
 #endif
 {
-    const void* fns[3] = {(const void*)pt_denoise_iter_kernel, (const void*)pt_denoise_prepare_kernel, (const void*)pt_denoise_finish_kernel};
-    hipFuncAttributes fa;
-    for (int k = 2; k >= 0; --k) {
-        hipError_t e = hipFuncGetAttributes(&fa, fns[k]);
-        if (e != hipSuccess) return e;
-        if (fa.localSizeBytes != 0) return hipErrorInvalidConfiguration;
-    }
+    const hipError_t e = pt_refuse_scratch({(const void*)pt_denoise_finish_kernel, (const void*)pt_denoise_prepare_kernel});
+    if (e != hipSuccess) return e;
     g->block = DN_TILE_W * DN_TILE_H;
     g->ns = DN_TILE_W * DN_TILE_H;
     g->lds_bytes = 0;
     g->lds_levels = 0;
     g->state_words = 0;
-    g->vgprs = fa.numRegs; // (the loop ends on the iteration kernel)
-    g->max_blocks_per_cu = 0;
     *grid = ((W + DN_TILE_W - 1) / DN_TILE_W) * ((H + DN_TILE_H - 1) / DN_TILE_H);
 #if PT_DENOISE_BATCH
     *grid *= K;
 #endif
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(&g->max_blocks_per_cu, fns[0], g->block, 0);
+    return pt_complete_geometry(g, (const void*)pt_denoise_iter_kernel);
 }
 
 // prepare, a->iterations iteration launches, finish - all on `stream`.  a->ws: pt_denoise_workspace_bytes(), 16-byte aligned.

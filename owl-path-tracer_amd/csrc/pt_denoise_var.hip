@@ -18,7 +18,7 @@
 
 #include "../../include/mi355pt.h"
 #include "pt_accum_math.h"
-#include "pt_launch.h"
+#include "pt_instance.h"
 
 using namespace ptd;
 
@@ -174,23 +174,15 @@ extern "C" size_t pt_denoise_var_workspace_bytes(int W, int H) { return (size_t)
 // one of the four kernels needs scratch in this build.
 extern "C" hipError_t pt_denoise_var_geometry(int W, int H, PtGeometry* g, int* grid)
 {
-    const void* fns[4] = {(const void*)pt_denoise_var_iter_kernel, (const void*)pt_denoise_var_prepare_kernel, (const void*)pt_denoise_var_finish_kernel,
-                          (const void*)pt_accum_variance_kernel};
-    hipFuncAttributes fa;
-    for (int k = 3; k >= 0; --k) {
-        hipError_t e = hipFuncGetAttributes(&fa, fns[k]);
-        if (e != hipSuccess) return e;
-        if (fa.localSizeBytes != 0) return hipErrorInvalidConfiguration;
-    }
+    const hipError_t e = pt_refuse_scratch({(const void*)pt_accum_variance_kernel, (const void*)pt_denoise_var_finish_kernel, (const void*)pt_denoise_var_prepare_kernel});
+    if (e != hipSuccess) return e;
     g->block = DV_TILE_W * DV_TILE_H;
     g->ns = DV_TILE_W * DV_TILE_H;
     g->lds_bytes = 0;
     g->lds_levels = 0;
     g->state_words = 0;
-    g->vgprs = fa.numRegs; // (the loop ends on the iteration kernel)
-    g->max_blocks_per_cu = 0;
     *grid = ((W + DV_TILE_W - 1) / DV_TILE_W) * ((H + DV_TILE_H - 1) / DV_TILE_H);
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(&g->max_blocks_per_cu, fns[0], g->block, 0);
+    return pt_complete_geometry(g, (const void*)pt_denoise_var_iter_kernel);
 }
 
 // prepare, a->iterations iteration launches, finish - all on `stream`.  a->ws: pt_denoise_var_workspace_bytes(), 16-byte aligned.

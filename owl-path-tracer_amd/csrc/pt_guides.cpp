@@ -78,21 +78,18 @@ struct AovJob {
 // One launch of the guide kernel per launch sequence over the 8 x 8 pixel blocks of its frames - a single frame is one sequence, a batch
 // is cut as pt_render_batch cuts it (batch_max_frames), the blocks of a sequence being those of its frames one after the other.  The
 // kernel itself skips the blocks of other ranks' tiles, so the pass needs no pixel queue.
-#define PT_AOV_FLAG_WORDS 64 // d_aov_ws: the bound flag on a line of its own, then the overflow columns
 int aov_device(pt_ctx* c, const AovJob& j)
 {
     // refusals first: nothing is enqueued or allocated before them
-    // quad: the quad instances walk the scene - its quad nodes, or a root that is itself a leaf (a scene of a few triangles has no nodes at
-    // all: root4 is the leaf reference, the walk is one leaf step and touches no node).  Only a tree too deep for quad nodes (nodes4
-    // cleared, root4 >= 0) and option quad = 0 leave the binary walk.
-    const bool batch = j.frames != nullptr, rays = j.d_rays != nullptr, quad = c->opt.quad && (!c->scene.nodes4.empty() || c->scene.root4 < 0), wt = c->opt.watertight != 0;
+    // quad: without the quad walk (quad_walk_available) the guide pass runs the binary walk
+    const bool batch = j.frames != nullptr, rays = j.d_rays != nullptr, quad = quad_walk_available(c), wt = c->opt.watertight != 0;
     const int W = j.W, H = j.H, n_frames = batch ? j.n_frames : 1, binary = quad ? 0 : 1;
     hipStream_t stream = j.stream;
+    int rc;
     if (rays && !quad) return fail(c, PT_E_INVALID, "pt_render_aov_rays: the guide pass over a ray image needs quad nodes"); // (check_aov_rays_args, by name)
     if (!quad && wt)
         return fail(c, PT_E_INVALID, "%s: without quad nodes (option quad = 0, or a tree too deep for them) the guide pass runs the binary walk, which has no watertight test (option watertight = 1)", j.follow ? "pt_render_aov_follow" : "pt_render_aov");
-    if (quad && (c->scene.bvh.tris.size() * sizeof(PtTri) > 0xffffffffull || c->scene.nodes4.size() * sizeof(PtNode4) > 0xffffffffull))
-        return fail(c, PT_E_LIMIT, "the guide kernel needs triangle records and quad nodes below 4 GiB each (%zu triangle slots, %zu quad nodes)", c->scene.bvh.tris.size(), c->scene.nodes4.size());
+    if (quad && (rc = check_quad_walk_size(c, "guide"))) return rc;
     const int64_t kmax = batch ? batch_max_frames(W, H, c->opt.batch_frames) : 1;
     if (kmax < 1) return fail(c, PT_E_LIMIT, "pt_render_aov_batch: one %dx%d frame already exceeds a launch sequence (< 2^24 pixels)", W, H);
     pt_camera ray_cam{}; // a ray image has no camera: walk_params reads the origin alone, the kernel nothing of P.cam
@@ -104,9 +101,7 @@ int aov_device(pt_ctx* c, const AovJob& j)
     P.nodes8 = nullptr;
     P.groups = 0;
     if (quad) {
-        P.nodes4 = (const PtNode4*)c->d_nodes4.p;
-        P.root = c->scene.root4;
-        P.stack_entries = 3 * c->scene.depth4 + 1;
+        quad_walk_params(c, P);
     } else {
         P.nodes4 = nullptr;
         P.root = c->scene.bvh.root;
@@ -121,8 +116,7 @@ int aov_device(pt_ctx* c, const AovJob& j)
     if (ge == hipErrorInvalidConfiguration) return fail(c, PT_E_LIMIT, "this build of the %sguide kernel spills registers to scratch; such builds are refused (pt_kernel.hip)", batch ? "batch " : "");
     HIP_TRY(c, ge);
     if (g.max_blocks_per_cu < 1) return fail(c, PT_E_LIMIT, "guide kernel does not fit a CU (LDS %zu bytes, BVH depth %d)", g.lds_bytes, c->scene.bvh.depth);
-    int tile = c->tile < 8 ? 8 : c->tile; // as pt_shard_pixels rounds it
-    tile = (tile + 7) & ~7;
+    const int tile = shard_tile(c->tile);
     // (a batch's shard: check_aov_batch_args, before the device is asked for)
     if (!batch && pt_shard_pixels(W, H, tile, c->rank, c->world, nullptr, 0) < 0) return fail(c, PT_E_INVALID, "invalid pixel shard (%d of %d)", c->rank, c->world);
     const long n_blocks = (long)((W + 7) / 8) * (long)((H + 7) / 8); // of one frame
@@ -131,19 +125,14 @@ int aov_device(pt_ctx* c, const AovJob& j)
     PtAovArgs& A = F.a;
     A.cap = quad ? P.stack_entries + 3 : 0;
     const int k_first = (int)std::min<int64_t>(kmax, n_frames); // the longest sequence has the most workgroups
-    const size_t ovf_words = quad ? (size_t)std::max(0, A.cap - g.lds_levels) * 64 * (size_t)grid_of(k_first) : 0;
-    int rc;
-    if ((rc = ensure(c, c->d_aov_ws, (PT_AOV_FLAG_WORDS + ovf_words) * 4))) return rc;
+    if ((rc = walk_workspace(c, A.cap, g.lds_levels, grid_of(k_first), stream, P, &A.ovf))) return rc; // one bound flag for every sequence (the binary walk: cap 0, no columns)
     if (batch && (rc = stage_batch_tables(c, j.frames, n_frames, stream))) return rc;
     const size_t npx = (size_t)W * H;
-    HIP_TRY(c, hipMemsetAsync(c->d_aov_ws.p, 0, PT_AOV_FLAG_WORDS * 4, stream)); // one bound flag for every sequence
     HIP_TRY(c, hipMemsetAsync(j.d_out, 0, (size_t)n_frames * npx * 8 * sizeof(float), stream)); // pixels of other ranks stay 0
-    P.error_flag = (uint32_t*)c->d_aov_ws.p;
     P.lds_levels = g.lds_levels;
     std::memcpy(P.cam, cam0, sizeof(float) * 12); // (a batch does not read it: every frame's camera comes from batch_cams)
     P.width = W;
     P.height = H;
-    A.ovf = (uint32_t*)c->d_aov_ws.p + PT_AOV_FLAG_WORDS;
     A.n_samples = j.n_samples;
     A.rank = c->rank; A.world = c->world; A.tile = tile;
     if (j.follow) {
@@ -224,9 +213,7 @@ int check_aov_batch_args(pt_ctx* c, const char* who, const pt_frame* frames, int
     if (n_materials != c->scene.n_materials) return fail(c, PT_E_INVALID, "%s: %d materials per frame, the scene has %d", who, n_materials, c->scene.n_materials);
     if (W <= 0 || H <= 0 || W > 65535 || H > 65535 || (int64_t)W * H > (int64_t)0x7fffffff) return fail(c, PT_E_INVALID, "%s: bad guide pass size %dx%d", who, W, H);
     if (c->opt.watertight) return fail(c, PT_E_INVALID, "%s: batches have no watertight instances (option watertight = 1); render the guides frame by frame or set watertight = 0", who);
-    int tile = c->tile < 8 ? 8 : c->tile; // as pt_shard_pixels rounds it
-    tile = (tile + 7) & ~7;
-    if (pt_shard_pixels(W, H, tile, c->rank, c->world, nullptr, 0) < 0) return fail(c, PT_E_INVALID, "%s: invalid pixel shard (%d of %d)", who, c->rank, c->world);
+    if (pt_shard_pixels(W, H, shard_tile(c->tile), c->rank, c->world, nullptr, 0) < 0) return fail(c, PT_E_INVALID, "%s: invalid pixel shard (%d of %d)", who, c->rank, c->world);
     return need_device(c);
 }
 
@@ -242,7 +229,7 @@ int check_aov_rays_args(pt_ctx* c, const char* who, const void* rays, int W, int
     if (!c->have_scene) return fail(c, PT_E_NO_SCENE, "%s: no geometries (pt_upload_scene not called)", who);
     if (W <= 0 || H <= 0 || W > 65535 || H > 65535 || (int64_t)W * H > (int64_t)0x7fffffff) return fail(c, PT_E_INVALID, "%s: bad guide pass size %dx%d", who, W, H);
     // the ray-image instances walk the quad nodes - or a root that is itself a leaf - and nothing else (as the ray queries, pt_rays_host.cpp)
-    if (!c->opt.quad || (c->scene.nodes4.empty() && c->scene.root4 >= 0))
+    if (!quad_walk_available(c))
         return fail(c, PT_E_INVALID, "%s: the guide pass over a ray image needs quad nodes (%s); there are no binary-walk instances", who, !c->opt.quad ? "option quad = 0" : "the tree is too deep for them");
     if ((rc = check_ray_table(c, who, rays, W, H, device, true))) return rc;
     return need_device(c);

@@ -184,6 +184,16 @@ PT_LOCAL void material_row(const pt_ctx* c, float* dst, const float* src, int i)
 int check_watchdog(pt_ctx* c);
 PT_LOCAL void fill_params(pt_ctx* c, PtKernelParams& P);
 PT_LOCAL void walk_params(pt_ctx* c, const pt_camera* cam, PtKernelParams& P);
+// What a one-wave quad walk (guide pass, ray queries; pt_aov_first.h, pt_aov_follow.h, pt_rays_kernels.h) needs from the host.  Its workspace
+// is d_aov_ws: kWalkFlagWords words whose first is the walks' bound flag, on a line of its own, then the waves' stack overflow columns.
+constexpr size_t kWalkFlagWords = 64;
+PT_LOCAL bool quad_walk_available(const pt_ctx* c);            // quad nodes, or a root that is itself a leaf (walk_params asks for nodes: the wavefront kernel takes a leaf root another way)
+PT_LOCAL void quad_walk_params(pt_ctx* c, PtKernelParams& P);  // P.nodes4, P.root, P.stack_entries
+PT_LOCAL int check_quad_walk_size(pt_ctx* c, const char* kernel); // PT_E_LIMIT: the quad-node and leaf steps address their records with 32-bit byte offsets
+PT_LOCAL int shard_tile(int tile);                             // as pt_shard_pixels rounds it: a multiple of 8, at least 8
+// d_aov_ws for `grid` workgroups whose lanes may use `cap` stack levels, lds_levels of them in LDS: sized, the flag words cleared on
+// `stream`, P.error_flag on the flag, *ovf on the columns ((cap - lds_levels) * 64 words per workgroup)
+PT_LOCAL int walk_workspace(pt_ctx* c, int cap, int lds_levels, int grid, hipStream_t stream, PtKernelParams& P, uint32_t** ovf);
 PT_LOCAL int check_render_args(pt_ctx* c, int W, int H, int max_samples, int max_depth, const int32_t* n_materials = nullptr);
 // a ray image's table (pt_render_rays*, pt_render_aov_rays* and the guide twin): pointers; then communicator (comm) and, of a host table, the records
 PT_LOCAL int check_ray_ptrs(pt_ctx* c, const char* who, const void* rays, const void* out, const char* out_name, bool device);

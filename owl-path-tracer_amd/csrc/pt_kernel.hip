@@ -47,7 +47,7 @@
 // from the table in HBM (gen_ray_from, pt_trace.h; the table pointer travels in P.batch_cams, which nothing else reads when batch_frames == 0).
 // The record is gathered per sample, not kept: the 4-wave instance has no 16 registers to spare, and a pixel's chunks may run on different
 // waves.  With PT_RAYGEN = 0 the preprocessor removes all of it ("Ray images").
-#include "pt_launch.h"
+#include "pt_instance.h"
 #include "pt_tiers.h"
 #include "pt_trace.h"
 #ifndef PT_BATCH
@@ -1177,33 +1177,39 @@ __global__ void __launch_bounds__(PT_WAVE, WAVES) PT_RENDER_KERNEL(const PtKerne
 
 // ---- launchers (called from pt_render.cpp) --------------------------------------------------------------------
 
+// The instance that serves (variant, count, exact): 2 the product instance, 3 its 168-VGPR fallback, count the instrumented one.  The
+// geometry function and the launcher both ask here, so the host sizes LDS and reports registers for the instance the GPU runs.
+// nullptr: no such instance - the lane-per-pixel kernel (variant 1, pt_kernel_aux.hip) has no batch, watertight or ray-image form.
+static const void* render_instance(int variant, int count, int exact)
+{
+    if (variant != 2 && variant != 3) return nullptr;
+    if (count) return (const void*)PT_RENDER_KERNEL<true, PT_COUNT_WAVES_PER_EU, false>;
+    if (variant == 3) return exact ? (const void*)PT_RENDER_KERNEL<false, PT_FALLBACK_WAVES, true> : (const void*)PT_RENDER_KERNEL<false, PT_FALLBACK_WAVES, false>;
+    return exact ? (const void*)PT_RENDER_KERNEL<false, PT_WAVES_PER_EU, true> : (const void*)PT_RENDER_KERNEL<false, PT_WAVES_PER_EU, false>;
+}
+
 // d_params: device copy of *p (wavefront kernel reads its parameters from HBM; the caller keeps it stream-ordered)
-// (the batch build spells the names of its two functions out: pt_launch_render_batch / pt_batch_kernel_geometry, variants 2 and 3 only)
+// (the batch build spells the names of its two functions out: pt_launch_render_batch / pt_batch_kernel_geometry)
 #if PT_BATCH
 extern "C" hipError_t pt_launch_render_batch(const PtKernelParams* p, const PtKernelParams* d_params, int variant, int grid, size_t lds_bytes,
                                              hipStream_t stream, int count)
-{
-    if (variant != 2 && variant != 3) return hipErrorInvalidValue; // the lane-per-pixel kernel has no batch form
-    if (p->batch_frames < 1 || p->batch_cams == nullptr) return hipErrorInvalidValue;
 #else
 extern "C" hipError_t PT_RENDER_LAUNCH(const PtKernelParams* p, const PtKernelParams* d_params, int variant, int grid, size_t lds_bytes,
                                        hipStream_t stream, int count)
+#endif
 {
-#if PT_WATERTIGHT
-    if (variant != 2 && variant != 3) return hipErrorInvalidValue; // the lane-per-pixel kernel has no watertight form
-#elif PT_RAYGEN
-    if (variant != 2 && variant != 3) return hipErrorInvalidValue; // the lane-per-pixel kernel has no ray-image form
-    if (p->batch_cams == nullptr || p->batch_frames != 0) return hipErrorInvalidValue; // (the ray table, in the batch cameras' place)
-#else
+#if !PT_BATCH && !PT_WATERTIGHT && !PT_RAYGEN
     if (variant == 1) return pt_launch_render_lane(p, grid, lds_bytes, stream, count); // pt_kernel_aux.hip
 #endif
+    const void* fn = render_instance(variant, count, p->box_exact != 0);
+    if (!fn) return hipErrorInvalidValue;
+#if PT_BATCH
+    if (p->batch_frames < 1 || p->batch_cams == nullptr) return hipErrorInvalidValue;
+#elif PT_RAYGEN
+    if (p->batch_cams == nullptr || p->batch_frames != 0) return hipErrorInvalidValue; // (the ray table, in the batch cameras' place)
 #endif
-    const bool exact = p->box_exact != 0;
-    if (count) hipLaunchKernelGGL((PT_RENDER_KERNEL<true, PT_COUNT_WAVES_PER_EU, false>), dim3(grid), dim3(PT_WAVE), lds_bytes, stream, d_params);
-    else if (variant == 3 && exact) hipLaunchKernelGGL((PT_RENDER_KERNEL<false, PT_FALLBACK_WAVES, true>), dim3(grid), dim3(PT_WAVE), lds_bytes, stream, d_params);
-    else if (variant == 3) hipLaunchKernelGGL((PT_RENDER_KERNEL<false, PT_FALLBACK_WAVES, false>), dim3(grid), dim3(PT_WAVE), lds_bytes, stream, d_params);
-    else if (exact) hipLaunchKernelGGL((PT_RENDER_KERNEL<false, PT_WAVES_PER_EU, true>), dim3(grid), dim3(PT_WAVE), lds_bytes, stream, d_params);
-    else hipLaunchKernelGGL((PT_RENDER_KERNEL<false, PT_WAVES_PER_EU, false>), dim3(grid), dim3(PT_WAVE), lds_bytes, stream, d_params);
+    void* args[] = {(void*)&d_params};
+    (void)hipLaunchKernel(fn, dim3(grid), dim3(PT_WAVE), args, lds_bytes, stream);
     return hipGetLastError();
 }
 
@@ -1212,35 +1218,24 @@ extern "C" hipError_t PT_RENDER_LAUNCH(const PtKernelParams* p, const PtKernelPa
 // global state words, registers, occupancy.  hipErrorInvalidConfiguration: the instance needs scratch (see below).
 #if PT_BATCH
 extern "C" hipError_t pt_batch_kernel_geometry(int variant, int count, int stack_entries, int group_entries, int want_ns, int exact, PtGeometry* g)
-{
-    if (variant != 2 && variant != 3) return hipErrorInvalidValue;
 #else
 extern "C" hipError_t PT_RENDER_GEOMETRY(int variant, int count, int stack_entries, int group_entries, int want_ns, int exact, PtGeometry* g)
+#endif
 {
-#if PT_WATERTIGHT || PT_RAYGEN
-    if (variant != 2 && variant != 3) return hipErrorInvalidValue;
-#else
+#if !PT_BATCH && !PT_WATERTIGHT && !PT_RAYGEN
     if (variant == 1) return pt_lane_kernel_geometry(count, stack_entries, g); // pt_kernel_aux.hip
 #endif
-#endif
-    const void* fn = count ? (const void*)PT_RENDER_KERNEL<true, PT_COUNT_WAVES_PER_EU, false>
-                     : variant == 3 ? (exact ? (const void*)PT_RENDER_KERNEL<false, PT_FALLBACK_WAVES, true> : (const void*)PT_RENDER_KERNEL<false, PT_FALLBACK_WAVES, false>)
-                                    : (exact ? (const void*)PT_RENDER_KERNEL<false, PT_WAVES_PER_EU, true> : (const void*)PT_RENDER_KERNEL<false, PT_WAVES_PER_EU, false>);
+    const void* fn = render_instance(variant, count, exact);
+    if (!fn) return hipErrorInvalidValue;
     const int n = want_ns < 16 ? 16 : (want_ns > 252 ? 252 : want_ns);
     g->block = PT_WAVE;
     g->ns = n;
     g->lds_bytes = pt_wave_lds_bytes(stack_entries, group_entries, n);
     g->lds_levels = pt_wave_lds_stack(stack_entries, group_entries);
     g->state_words = pt_wave_state_words(stack_entries);
-    hipFuncAttributes fa;
-    hipError_t e = hipFuncGetAttributes(&fa, fn);
-    if (e != hipSuccess) return e;
     // register spills: see pt_render_wave_kernel.  A build with -DPT_ALLOW_SCRATCH=1 (make variant) lifts the refusal for the experiment
     // that investigates it (profiles/r02_spill_investigation.md); never in production
-    if (fa.localSizeBytes != 0 && !PT_ALLOW_SCRATCH) return hipErrorInvalidConfiguration;
-    g->vgprs = fa.numRegs;
-    g->max_blocks_per_cu = 0;
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(&g->max_blocks_per_cu, fn, g->block, g->lds_bytes);
+    return pt_complete_geometry(g, fn, PT_ALLOW_SCRATCH);
 }
 
 #if !PT_BATCH && !PT_RAYGEN

@@ -2,7 +2,7 @@
 //   pt_render_kernel   the simple persistent lane-per-pixel megakernel (option kernel=1): kept for A/B measurements and as an independent
 //                      implementation in the parity suite (tests/test_gpu_parity.py::test_lane_per_pixel_variant_bitwise);
 //   pt_debug_kernel    batched evaluation of the kernels' building blocks for the bit-exact comparisons with the oracle (pt_debug_eval).
-#include "pt_launch.h"
+#include "pt_instance.h"
 #include "pt_trace.h"
 
 namespace {
@@ -202,12 +202,7 @@ extern "C" hipError_t pt_lane_kernel_geometry(int count, int stack_entries, PtGe
     g->lds_bytes = (size_t)stack_entries * PT_BLOCK * 4;
     g->lds_levels = stack_entries;
     g->state_words = 0;
-    hipFuncAttributes fa;
-    hipError_t e = hipFuncGetAttributes(&fa, fn);
-    if (e != hipSuccess) return e;
-    g->vgprs = fa.numRegs;
-    g->max_blocks_per_cu = 0;
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(&g->max_blocks_per_cu, fn, g->block, g->lds_bytes);
+    return pt_complete_geometry(g, fn, true); // (never held to the no-scratch rule of the wavefront kernel)
 }
 
 extern "C" int pt_debug_block(void) { return PT_BLOCK; }

@@ -1,6 +1,10 @@
 // pt_launch.h -- prototypes of the kernel launchers (defined in the .hip units: pt_kernel.hip, the family headers it names, pt_lbvh.hip, ...; stubbed in pt_nogpu_stubs.cpp for the
 // host-side sanitizer build) as pt_scene.cpp / pt_render.cpp / pt_guides.cpp / pt_debug.cpp / pt_comm.cpp call them.  ONE declaration for definition, stub and caller: the functions
 // have C linkage, so a mismatched parameter list would link and then misbehave (round-3 advisor finding).
+// The same holds inside a family: its *_geometry function (what the host sizes LDS and overflow columns from, and reports in pt_stats)
+// and its launcher (what the GPU runs) must mean the same kernel instance, and nothing at link time says so.  Each walking family
+// therefore has ONE function that maps the selector arguments to the instance, and both ask it; what every *_geometry function asks the
+// runtime about that instance - registers, occupancy, and the refusal of one that spills - is pt_instance.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>

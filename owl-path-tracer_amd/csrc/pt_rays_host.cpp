@@ -2,7 +2,7 @@
 // and blocking entry points, the CPU twin pt_debug_trace_rays_host and pt_prim_to_mesh.
 // The pass reads the scene and nothing of a frame: no pixel queue, no shard, no materials, no environment, no collective.  Its own
 // buffers are d_rays_in / d_rays_out (the blocking forms' staging); the waves' stack overflow columns and the bound flag are the guide
-// pass's d_aov_ws, laid out as there (pt_guides.cpp) - the two passes are ordered like any two calls of a context, and check_watchdog
+// pass's d_aov_ws (walk_workspace, pt_internal.h) - the two passes are ordered like any two calls of a context, and check_watchdog
 // looks at one flag.
 #include <algorithm>
 #include <cstring>
@@ -14,7 +14,6 @@ using namespace pti;
 
 namespace {
 
-#define PT_RAYS_FLAG_WORDS 64 // d_aov_ws: the bound flag on a line of its own, then the overflow columns (PT_AOV_FLAG_WORDS of pt_guides.cpp)
 constexpr float kRayTMin = 1e-3f, kRayTMax = 1e10f; // kTMin, kTMax of pt_device.h
 
 static_assert(sizeof(pt_ray) == 32 && sizeof(pt_ray_hit) == 16, "the ray kernels read a ray as two 16-byte loads and store a hit as one");
@@ -32,8 +31,8 @@ int check_rays_args(pt_ctx* c, const char* who, const void* rays, int64_t n, con
     if (device && n > 0 && ((uintptr_t)rays & 15u)) return fail(c, PT_E_INVALID, "%s: d_rays is not 16-byte aligned (a ray is two 16-byte loads)", who);
     if (device && closest && n > 0 && ((uintptr_t)out & 15u)) return fail(c, PT_E_INVALID, "%s: d_out is not 16-byte aligned (a hit is one 16-byte store)", who);
     if (!c->have_scene) return fail(c, PT_E_NO_SCENE, "%s: no geometries (pt_upload_scene not called)", who);
-    // the ray kernels walk the quad nodes - or a root that is itself a leaf (a scene of a few triangles has no nodes at all) - and nothing else
-    if (!c->opt.quad || (c->scene.nodes4.empty() && c->scene.root4 >= 0))
+    // the ray kernels walk the quad nodes - or a root that is itself a leaf - and nothing else
+    if (!quad_walk_available(c))
         return fail(c, PT_E_INVALID, "%s: the ray queries need quad nodes (%s)", who, !c->opt.quad ? "option quad = 0" : "the tree is too deep for them");
     return need_device(c);
 }
@@ -42,16 +41,13 @@ int check_rays_args(pt_ctx* c, const char* who, const void* rays, int64_t n, con
 // occupancy query says is resident, or fewer when there are fewer blocks.
 int rays_device(pt_ctx* c, bool occluded, const void* d_rays, int64_t n, void* d_out, hipStream_t stream)
 {
-    const bool wt = c->opt.watertight != 0;
-    if (c->scene.bvh.tris.size() * sizeof(PtTri) > 0xffffffffull || c->scene.nodes4.size() * sizeof(PtNode4) > 0xffffffffull)
-        return fail(c, PT_E_LIMIT, "the ray kernel needs triangle records and quad nodes below 4 GiB each (%zu triangle slots, %zu quad nodes)", c->scene.bvh.tris.size(), c->scene.nodes4.size());
+    int rc;
+    if ((rc = check_quad_walk_size(c, "ray"))) return rc;
     PtKernelParams P;
     fill_params(c, P); // the scene; no camera, so no distance to judge the slab form by: the subtracting form only on request
     P.box_exact = c->opt.box_exact > 0 ? 1 : 0;
-    P.nodes4 = (const PtNode4*)c->d_nodes4.p;
-    P.root = c->scene.root4;
-    P.stack_entries = 3 * c->scene.depth4 + 1;
-    const RaysInstance& inst = kRaysInstance[wt];
+    quad_walk_params(c, P);
+    const RaysInstance& inst = kRaysInstance[c->opt.watertight != 0];
     PtGeometry g{};
     const hipError_t ge = inst.geometry(occluded, P.box_exact, &g);
     if (ge == hipErrorInvalidConfiguration) return fail(c, PT_E_LIMIT, "this build of the ray kernel spills registers to scratch; such builds are refused (pt_kernel.hip)");
@@ -65,15 +61,10 @@ int rays_device(pt_ctx* c, bool occluded, const void* d_rays, int64_t n, void* d
     if (blocks_per_wave * 64 > 0x7fffffc0ll) return fail(c, PT_E_LIMIT, "ray kernel: %lld rays per wave", (long long)blocks_per_wave * 64);
     PtRaysArgs A{};
     A.cap = P.stack_entries + 3;
-    const size_t ovf_words = (size_t)std::max(0, A.cap - g.lds_levels) * 64 * (size_t)grid;
-    int rc;
-    if ((rc = ensure(c, c->d_aov_ws, (PT_RAYS_FLAG_WORDS + ovf_words) * 4))) return rc; // (growing it first waits on the host for what is in flight)
-    HIP_TRY(c, hipMemsetAsync(c->d_aov_ws.p, 0, PT_RAYS_FLAG_WORDS * 4, stream));
-    P.error_flag = (uint32_t*)c->d_aov_ws.p;
+    if ((rc = walk_workspace(c, A.cap, g.lds_levels, grid, stream, P, &A.ovf))) return rc;
     P.lds_levels = g.lds_levels;
     A.rays = d_rays;
     A.out = d_out;
-    A.ovf = (uint32_t*)c->d_aov_ws.p + PT_RAYS_FLAG_WORDS;
     A.n = (int32_t)n;
     A.per_wave = (int32_t)(blocks_per_wave * 64);
     A.refill = c->opt.rays_refill;

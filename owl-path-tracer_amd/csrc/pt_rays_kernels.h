@@ -19,7 +19,7 @@
 // is reported as a miss); a round in which no lane holds a ray either hands out at least one (next < end: no lane is walking, which is
 // <= any A.refill) or leaves the loop; `next` only grows.
 #pragma once
-#include "pt_launch.h"
+#include "pt_instance.h"
 #include "pt_trace.h"
 #if PT_WATERTIGHT
 #define PT_RAYS_KERNEL pt_rays_wt_kernel
@@ -105,29 +105,21 @@ __global__ void __launch_bounds__(PT_WAVE, PT_RAYS_WAVES_PER_EU) PT_RAYS_KERNEL(
     }
 }
 
-namespace {
-const void* rays_instance(int occluded, int exact)
+// The instance that serves (occluded, exact), for the geometry function and the launcher alike.
+static const void* rays_instance(int occluded, int exact)
 {
     if (occluded) return exact ? (const void*)PT_RAYS_KERNEL<true, true> : (const void*)PT_RAYS_KERNEL<true, false>;
     return exact ? (const void*)PT_RAYS_KERNEL<false, true> : (const void*)PT_RAYS_KERNEL<false, false>;
 }
-} // namespace
 
 extern "C" hipError_t PT_RAYS_GEOMETRY(int occluded, int exact, PtGeometry* g)
 {
-    const void* fn = rays_instance(occluded, exact);
     g->block = PT_WAVE;
     g->ns = PT_WAVE;
     g->lds_levels = PT_LDS_STACK;
     g->lds_bytes = (size_t)g->lds_levels * PT_WAVE * 4;
     g->state_words = 0;
-    hipFuncAttributes fa;
-    hipError_t e = hipFuncGetAttributes(&fa, fn);
-    if (e != hipSuccess) return e;
-    if (fa.localSizeBytes != 0) return hipErrorInvalidConfiguration; // as the guide instances: a build that spills is refused
-    g->vgprs = fa.numRegs;
-    g->max_blocks_per_cu = 0;
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(&g->max_blocks_per_cu, fn, g->block, g->lds_bytes);
+    return pt_complete_geometry(g, rays_instance(occluded, exact));
 }
 
 extern "C" hipError_t PT_RAYS_LAUNCH(const PtKernelParams* p, const PtRaysArgs* a, int occluded, int grid, size_t lds_bytes, hipStream_t stream)
@@ -135,12 +127,7 @@ extern "C" hipError_t PT_RAYS_LAUNCH(const PtKernelParams* p, const PtRaysArgs* 
     if (grid < 1 || a->n < 1 || a->per_wave < PT_WAVE || (a->per_wave % PT_WAVE) != 0 || a->refill < 0 || a->refill >= PT_WAVE) return hipErrorInvalidValue;
     if ((long long)grid * a->per_wave < (long long)a->n) return hipErrorInvalidValue; // the ranges cover every ray ...
     if ((long long)(grid - 1) * a->per_wave >= (long long)a->n) return hipErrorInvalidValue; // ... and none is empty: the kernel relies on it
-    if (occluded) {
-        if (p->box_exact) hipLaunchKernelGGL((PT_RAYS_KERNEL<true, true>), dim3(grid), dim3(PT_WAVE), lds_bytes, stream, *p, *a);
-        else hipLaunchKernelGGL((PT_RAYS_KERNEL<true, false>), dim3(grid), dim3(PT_WAVE), lds_bytes, stream, *p, *a);
-    } else {
-        if (p->box_exact) hipLaunchKernelGGL((PT_RAYS_KERNEL<false, true>), dim3(grid), dim3(PT_WAVE), lds_bytes, stream, *p, *a);
-        else hipLaunchKernelGGL((PT_RAYS_KERNEL<false, false>), dim3(grid), dim3(PT_WAVE), lds_bytes, stream, *p, *a);
-    }
+    void* args[] = {(void*)p, (void*)a};
+    (void)hipLaunchKernel(rays_instance(occluded, p->box_exact), dim3(grid), dim3(PT_WAVE), args, lds_bytes, stream);
     return hipGetLastError();
 }

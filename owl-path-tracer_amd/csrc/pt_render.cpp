@@ -70,16 +70,46 @@ void walk_params(pt_ctx* c, const pt_camera* cam, PtKernelParams& P)
         for (int a = 0; a < 3; ++a) far_o = std::max(far_o, std::fabs(cam->origin[a]));
         P.box_exact = (c->opt.box_exact > 0 || (c->opt.box_exact < 0 && !(far_o <= reach))) ? 1 : 0;
     }
-    if (c->opt.kernel == 2 && c->opt.quad && !c->scene.nodes4.empty()) { // the wavefront kernel walks the quad nodes: own root and stack bound
-        P.nodes4 = (const PtNode4*)c->d_nodes4.p;
-        P.root = c->scene.root4;
-        P.stack_entries = 3 * c->scene.depth4 + 1;
-    }
+    if (c->opt.kernel == 2 && c->opt.quad && !c->scene.nodes4.empty()) quad_walk_params(c, P); // the wavefront kernel walks the quad nodes
     if (c->opt.kernel == 2 && c->opt.groups && !c->scene.nodes8.empty()) { // group walk of sparse waves (oct nodes)
         P.nodes8 = (const PtNode8*)c->d_nodes8.p;
         P.root8 = c->scene.root8;
         P.groups = c->opt.groups;
     }
+}
+
+// ---- one-wave quad walks (pt_internal.h) --------------------------------------------------------------------------------
+// The quad instances walk the scene's quad nodes, or a root that is itself a leaf (a scene of a few triangles has no nodes at all: root4
+// is the leaf reference, the walk is one leaf step and touches no node).  Only a tree too deep for quad nodes (nodes4 cleared,
+// root4 >= 0) and option quad = 0 leave them without a walk.
+bool quad_walk_available(const pt_ctx* c) { return c->opt.quad && (!c->scene.nodes4.empty() || c->scene.root4 < 0); }
+
+// The quad walk's own root and stack bound: up to three pushes per step.
+void quad_walk_params(pt_ctx* c, PtKernelParams& P)
+{
+    P.nodes4 = (const PtNode4*)c->d_nodes4.p;
+    P.root = c->scene.root4;
+    P.stack_entries = 3 * c->scene.depth4 + 1;
+}
+
+int check_quad_walk_size(pt_ctx* c, const char* kernel)
+{
+    if (c->scene.bvh.tris.size() * sizeof(PtTri) > 0xffffffffull || c->scene.nodes4.size() * sizeof(PtNode4) > 0xffffffffull)
+        return fail(c, PT_E_LIMIT, "the %s kernel needs triangle records and quad nodes below 4 GiB each (%zu triangle slots, %zu quad nodes)", kernel, c->scene.bvh.tris.size(), c->scene.nodes4.size());
+    return PT_OK;
+}
+
+int shard_tile(int tile) { return ((tile < 8 ? 8 : tile) + 7) & ~7; }
+
+int walk_workspace(pt_ctx* c, int cap, int lds_levels, int grid, hipStream_t stream, PtKernelParams& P, uint32_t** ovf)
+{
+    const size_t ovf_words = (size_t)std::max(0, cap - lds_levels) * 64 * (size_t)grid;
+    int rc;
+    if ((rc = ensure(c, c->d_aov_ws, (kWalkFlagWords + ovf_words) * 4))) return rc; // (growing it first waits on the host for what is in flight)
+    HIP_TRY(c, hipMemsetAsync(c->d_aov_ws.p, 0, kWalkFlagWords * 4, stream));
+    P.error_flag = (uint32_t*)c->d_aov_ws.p;
+    *ovf = (uint32_t*)c->d_aov_ws.p + kWalkFlagWords;
+    return PT_OK;
 }
 
 // What pt_render_device and a batch refuse alike, before anything is enqueued.  n_materials: rows of a batch's per-frame tables, compared
@@ -260,11 +290,18 @@ Schedule make_schedule(int total, int chunk, int rem_min, int tail_min)
 // through the per-chunk rings, so that the frame ends on ~n_pixels short work items.
 // schedule 0 (or spp_per_launch, which the resumability tests use): one launch, chunk_spp chunks + halving tail.
 // All schedules give the same image bit for bit (a pixel's stream does not depend on who renders it, or when).
+// The families of the render kernel (pt_launch.h), one build of pt_kernel.hip each.  A frame runs ONE: the caller asks for kBatch or
+// kRayImage before plan_frame, which turns kFrame into kWatertight with option "watertight" and refuses the combinations that have no build.
+enum RenderFamily { kFrame, kWatertight, kBatch, kRayImage };
+const struct RenderInstance {
+    hipError_t (*geometry)(int variant, int count, int stack_entries, int group_entries, int want_ns, int exact, PtGeometry* g);
+    hipError_t (*launch)(const PtKernelParams* p, const PtKernelParams* d_params, int variant, int grid, size_t lds_bytes, hipStream_t stream, int count);
+} kRenderInstance[4] = {{pt_kernel_geometry, pt_launch_render}, {pt_wt_kernel_geometry, pt_launch_render_wt}, {pt_batch_kernel_geometry, pt_launch_render_batch},
+                        {pt_rayimage_kernel_geometry, pt_launch_render_rayimage}};
+
 struct FramePlan {
-    int variant = 0, use_count = 0; // instance of the render kernel (pt_launch_render) and whether it is the instrumented one
-    bool batch = false;             // the batch instances (pt_launch_render_batch): set by the caller before plan_frame
-    bool wt = false;                // the watertight instances (pt_launch_render_wt): option "watertight", set by plan_frame
-    bool rays = false;              // the ray-image instances (pt_launch_render_rayimage): set by the caller before plan_frame (rays_image_device)
+    RenderFamily family = kFrame;   // whose geometry sized the frame and whose launcher runs it
+    int variant = 0, use_count = 0; // instance of that family and whether it is the instrumented one
     PtGeometry geo{};               // its launch geometry
     int bpc = 0, grid = 0;          // workgroups per CU, of the (main) launch
     int ring_grid = 0;              // with a tier plan: the workgroups of the ring schedule (the plan's fallback; the pre-pass launches these)
@@ -352,26 +389,22 @@ int plan_frame(pt_ctx* c, const PtKernelParams& P, int max_samples, FramePlan& f
     // instrumented instance only: the product instance is kept small for the instruction cache)
     // option "watertight": the same three instances from pt_kernel_wt.hip, chosen and refused by the same rules (a 128-VGPR watertight
     // instance that needs scratch falls back to the 168-VGPR one, a fallback that needs it too is PT_E_LIMIT below)
-    f.wt = c->opt.watertight != 0;
-    if (f.wt && c->opt.kernel != 2) return fail(c, PT_E_INVALID, "watertight = 1: the lane-per-pixel kernel (option kernel = 1) has no watertight form");
-    if (f.wt && f.rays) return fail(c, PT_E_INVALID, "pt_render_rays: ray images have no watertight instances (option watertight = 1); set watertight = 0");
-    if (f.wt && f.batch) return fail(c, PT_E_INVALID, "pt_render_batch: batches have no watertight instances (option watertight = 1); render the frames one by one or set watertight = 0");
+    const bool wt = c->opt.watertight != 0;
+    if (wt && c->opt.kernel != 2) return fail(c, PT_E_INVALID, "watertight = 1: the lane-per-pixel kernel (option kernel = 1) has no watertight form");
+    if (wt && f.family == kRayImage) return fail(c, PT_E_INVALID, "pt_render_rays: ray images have no watertight instances (option watertight = 1); set watertight = 0");
+    if (wt && f.family == kBatch) return fail(c, PT_E_INVALID, "pt_render_batch: batches have no watertight instances (option watertight = 1); render the frames one by one or set watertight = 0");
+    if (wt) f.family = kWatertight;
     f.use_count = (c->opt.count || (c->opt.kernel == 2 && !P.nodes4)) ? 1 : 0;
     f.variant = c->opt.kernel == 2 && c->opt.fallback && !f.use_count ? 3 : c->opt.kernel;
     // the wavefront kernel's quad-node and leaf steps address their records with 32-bit byte offsets from the buffer base (node4_step, leaf_test)
-    if (c->opt.kernel == 2 && (c->scene.bvh.tris.size() * sizeof(PtTri) > 0xffffffffull || c->scene.nodes4.size() * sizeof(PtNode4) > 0xffffffffull))
-        return fail(c, PT_E_LIMIT, "the wavefront kernel needs triangle records and quad nodes below 4 GiB each (%zu triangle slots, %zu quad nodes)", c->scene.bvh.tris.size(), c->scene.nodes4.size());
+    int rc;
+    if (c->opt.kernel == 2 && (rc = check_quad_walk_size(c, "wavefront"))) return rc;
     // The wavefront kernel keeps `ns` pixels in flight per wave; shrink ns when the image is too small to give every resident wave a
     // full set (e.g. 512x512 over 4096 waves), otherwise use the default.
     const int group_entries = P.nodes8 ? 7 * c->scene.depth8 + 1 : 0;
     int want_ns = c->opt.slots_per_wave > 0 ? c->opt.slots_per_wave : PT_DEFAULT_NS;
     const PtGeometry& g = f.geo;
-    auto geometry = [&] {
-        return f.batch ? pt_batch_kernel_geometry(f.variant, f.use_count, P.stack_entries, group_entries, want_ns, P.box_exact, &f.geo)
-               : f.rays ? pt_rayimage_kernel_geometry(f.variant, f.use_count, P.stack_entries, group_entries, want_ns, P.box_exact, &f.geo)
-               : f.wt  ? pt_wt_kernel_geometry(f.variant, f.use_count, P.stack_entries, group_entries, want_ns, P.box_exact, &f.geo)
-                       : pt_kernel_geometry(f.variant, f.use_count, P.stack_entries, group_entries, want_ns, P.box_exact, &f.geo);
-    };
+    auto geometry = [&] { return kRenderInstance[f.family].geometry(f.variant, f.use_count, P.stack_entries, group_entries, want_ns, P.box_exact, &f.geo); };
     hipError_t ge = geometry();
     if (ge == hipErrorInvalidConfiguration && f.variant == 2 && !f.use_count) {
         f.variant = 3;
@@ -597,10 +630,7 @@ int run_launches(pt_ctx* c, const FramePlan& f, PtKernelParams& P, int W, int H,
         // (with a tier plan prepared only the main launch has every resident workgroup; the pre-pass measures the pixels' costs in waves
         // as dense as the ring schedule's - C2 74.3 -> 71 ms, 1/8 shard 198 -> 194)
         const int grid = (f.tiers && l == 0) ? f.ring_grid : f.grid;
-        HIP_TRY(c, f.batch ? pt_launch_render_batch(&P, dP, f.variant, grid, f.geo.lds_bytes, stream, f.use_count)
-                   : f.rays ? pt_launch_render_rayimage(&P, dP, f.variant, grid, f.geo.lds_bytes, stream, f.use_count)
-                   : f.wt  ? pt_launch_render_wt(&P, dP, f.variant, grid, f.geo.lds_bytes, stream, f.use_count)
-                           : pt_launch_render(&P, dP, f.variant, grid, f.geo.lds_bytes, stream, f.use_count));
+        HIP_TRY(c, kRenderInstance[f.family].launch(&P, dP, f.variant, grid, f.geo.lds_bytes, stream, f.use_count));
     }
     return PT_OK;
 }
@@ -627,7 +657,7 @@ int batch_sequence(pt_ctx* c, const BatchArgs& a, int f0, int K, bool first, voi
         P.box_exact = Q.box_exact;
     }
     FramePlan f;
-    f.batch = true;
+    f.family = kBatch;
     if ((rc = plan_frame(c, P, a.max_samples, f))) return rc;
     if ((rc = frame_buffers(c, f, W, Hv, d_out_rgb, d_out_rgba8, stream, first))) return rc;
     frame_params(c, f, &a.frames[f0].camera, W, H, a.max_samples, a.max_depth, d_out_rgb, d_out_rgba8, P);
@@ -724,7 +754,7 @@ int check_ray_image_args(pt_ctx* c, const char* who, const void* rays, int W, in
 }
 
 // One frame over the ray image at d_rays on `stream`, which the caller has ordered after the context's last asynchronous call: render_device
-// with the ray-image instances (FramePlan::rays) and the table in the batch cameras' place.  far_o: the largest |org| component of the
+// with the ray-image instances (kRayImage) and the table in the batch cameras' place.  far_o: the largest |org| component of the
 // table, which decides the slab form as the camera's origin does in walk_params (+infinity: unknown, the subtracting form unless
 // option "box_exact" = 0 asks for the other).
 int rays_image_device(pt_ctx* c, const void* d_rays, float far_o, int W, int H, int max_samples, int max_depth, void* d_out_rgb, void* d_out_rgba8, hipStream_t stream)
@@ -741,7 +771,7 @@ int rays_image_device(pt_ctx* c, const void* d_rays, float far_o, int W, int H, 
     PtKernelParams P;
     walk_params(c, &cam, P);
     FramePlan f;
-    f.rays = true;
+    f.family = kRayImage;
     if ((rc = plan_frame(c, P, max_samples, f))) return rc;
     if ((rc = frame_buffers(c, f, W, H, d_out_rgb, d_out_rgba8, stream))) return rc;
     cam.origin[0] = 0.0f;

@@ -18,7 +18,7 @@
 
 #include "../../include/mi355pt.h"
 #include "pt_device.h"
-#include "pt_launch.h"
+#include "pt_instance.h"
 
 using namespace ptd;
 
@@ -112,22 +112,15 @@ extern "C" size_t pt_upsample_workspace_bytes(int w, int h) { return (size_t)w *
 // one of the two kernels needs scratch in this build.
 extern "C" hipError_t pt_upsample_geometry(int W, int H, PtGeometry* g, int* grid)
 {
-    const void* fns[2] = {(const void*)pt_upsample_kernel, (const void*)pt_upsample_prepare_kernel};
-    hipFuncAttributes fa;
-    for (int k = 1; k >= 0; --k) {
-        hipError_t e = hipFuncGetAttributes(&fa, fns[k]);
-        if (e != hipSuccess) return e;
-        if (fa.localSizeBytes != 0) return hipErrorInvalidConfiguration;
-    }
+    const hipError_t e = pt_refuse_scratch({(const void*)pt_upsample_prepare_kernel});
+    if (e != hipSuccess) return e;
     g->block = UP_TILE_W * UP_TILE_H;
     g->ns = UP_TILE_W * UP_TILE_H;
     g->lds_bytes = 0;
     g->lds_levels = 0;
     g->state_words = 0;
-    g->vgprs = fa.numRegs; // (the loop ends on the upsample kernel)
-    g->max_blocks_per_cu = 0;
     *grid = ((W + UP_TILE_W - 1) / UP_TILE_W) * ((H + UP_TILE_H - 1) / UP_TILE_H);
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(&g->max_blocks_per_cu, fns[0], g->block, 0);
+    return pt_complete_geometry(g, (const void*)pt_upsample_kernel);
 }
 
 // prepare over the low frame, upsample over the high frame - both on `stream`.  a->ws: pt_upsample_workspace_bytes(), 16-byte aligned.

@@ -142,7 +142,7 @@ def test_batch_kernel_instances_need_no_scratch():
     report = _hipcc_resource_report("pt_kernel_batch.hip")
     blocks = re.findall(r"Function Name: (\S*pt_render_batch_kernel\S*).*?VGPRs: (\d+).*?ScratchSize \[bytes/lane\]: (\d+)", report, flags=re.S)
     names = sorted(n for n, _, _ in blocks)
-    # <COUNT, WAVES, EXACT> of the five launches in pt_launch_render_batch (PT_WAVES_PER_EU 4, PT_FALLBACK_WAVES 3, PT_COUNT_WAVES_PER_EU 2)
+    # <COUNT, WAVES, EXACT> of the five instances pt_launch_render_batch launches (PT_WAVES_PER_EU 4, PT_FALLBACK_WAVES 3, PT_COUNT_WAVES_PER_EU 2)
     want = sorted("_Z22pt_render_batch_kernelILb%dELi%dELb%dEEvPK14PtKernelParams" % t for t in ((0, 4, 0), (0, 4, 1), (0, 3, 0), (0, 3, 1), (1, 2, 0)))
     assert names == want, names
     assert all(int(sz) == 0 for _, _, sz in blocks), blocks
@@ -151,8 +151,10 @@ def test_batch_kernel_instances_need_no_scratch():
         assert int(vg) <= budget[re.search(r"Li\dE", n).group(0)], (n, vg)
     assert "pt_render_wave_kernel" not in report
     src = open(os.path.join(CSRC, "pt_kernel.hip")).read()
-    launcher = src[src.index('extern "C" hipError_t pt_launch_render_batch'):src.index('// Launch geometry of a render variant')]
-    assert len(re.findall(r"hipLaunchKernelGGL\(\(PT_RENDER_KERNEL<", launcher)) == len(blocks) == 5
+    # (the launcher and the geometry function take the instance from render_instance: the one place that names them)
+    pick = src[src.index('static const void* render_instance'):src.index('extern "C" hipError_t pt_launch_render_batch')]
+    assert len(re.findall(r"\(const void\*\)PT_RENDER_KERNEL<", pick)) == len(blocks) == 5
+    assert "PT_RENDER_KERNEL<" not in src[src.index('extern "C" hipError_t pt_launch_render_batch'):]
 
 
 def test_batch_host_paths_under_asan():
