@@ -1,5 +1,5 @@
 // pt_nogpu_stubs.cpp -- the kernel launchers of pt_kernel.hip / pt_lbvh.hip as stubs that fail: ONLY for the host-side sanitizer build
-// (make -C csrc asan: libmi355pt_asan.so).  That build compiles the host sources (pt_api.cpp, pt_scene.cpp, pt_render.cpp, pt_guides.cpp, pt_debug.cpp, pt_comm.cpp, pt_bvh.cpp, pt_aov_host.cpp, pt_denoise_host.cpp) with g++ -fsanitize=address,
+// (make -C csrc asan: libmi355pt_asan.so).  That build compiles the host sources (HOST_SRCS of the Makefile) with g++ -fsanitize=address,
 // undefined so that the CPU tests and the garbled-input tests run the host paths of the library (scene flattening, BVH build and
 // collapse, sharding, validation hooks) under ASan/UBSan; device code cannot be sanitized on this pool and a host-only context never
 // reaches these functions (every render path refuses first: "no CPU fallback").  Not part of libmi355pt.so.

@@ -340,24 +340,9 @@ def test_render_kernel_instances_need_no_scratch():
     on the GPU box only.  hipcc reports the resource usage without a GPU: all five instances must show ScratchSize 0 (found the hard way
     in round 4: a dynamic index into the counter block sent all of it to scratch).  The flags are the Makefile's CXXFLAGS - the code
     generation that ships (the machine scheduler strategy among them decides the registers)."""
-    import shlex, shutil, subprocess, tempfile
+    import resource_report
 
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    csrc = os.path.join(ROOT, "owl-path-tracer_amd", "csrc")
-    with open(os.path.join(csrc, "Makefile")) as f:
-        flags = shlex.split(re.search(r"^CXXFLAGS\s*\?=(.*)$", f.read(), flags=re.M).group(1))
-    # what make itself passes to hipcc for the same file (a CXXFLAGS of the caller's environment would override the Makefile's)
-    env = {k: v for k, v in os.environ.items() if k not in ("CXXFLAGS", "MAKEFLAGS")}
-    dry = subprocess.run(["make", "-n", "-s", "-C", csrc, "asm"], env=env, capture_output=True, text=True, timeout=60)
-    assert dry.returncode == 0, dry.stderr
-    made = shlex.split(dry.stdout.strip().splitlines()[-1])
-    assert made[:2] == [made[0], "--offload-arch=gfx950"] and made[2:2 + len(flags)] == flags and made[2 + len(flags)] == "-S", (flags, made)
-    with tempfile.TemporaryDirectory() as td:
-        r = subprocess.run([hipcc, "--offload-arch=gfx950"] + flags + ["-S", "--cuda-device-only", "-o", os.path.join(td, "k.s"), os.path.join(csrc, "pt_kernel.hip"),
-                            "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-2000:]
-    blocks = re.findall(r"Function Name: (\S*pt_render_wave_kernel\S*).*?ScratchSize \[bytes/lane\]: (\d+)", r.stderr, flags=re.S)
+    resource_report.assert_ships_with_makefile_flags("pt_kernel")
+    blocks = re.findall(r"Function Name: (\S*pt_render_wave_kernel\S*).*?ScratchSize \[bytes/lane\]: (\d+)", resource_report.report("asm")[0], flags=re.S)
     assert len(blocks) == 5, blocks  # product / fallback, each with the fma and the subtracting slab form, + the instrumented instance
     assert all(int(sz) == 0 for _, sz in blocks), blocks

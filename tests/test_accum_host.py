@@ -13,7 +13,6 @@ import ctypes as C
 import json
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
@@ -21,6 +20,7 @@ import pytest
 
 import accum_ref
 import aov_common as AC
+import resource_report
 from owl_path_tracer_amd.pyhost import binding as B
 
 ROOT = AC.ROOT
@@ -247,21 +247,9 @@ def test_pt_main_refuses_more_adds_than_samples():
         assert r.returncode == 1 and "--adds" in r.stderr and word in r.stderr, r.stderr[-1000:]
 
 
-def _report(target):
-    if not (shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc")):
-        pytest.skip("hipcc not available")
-    csrc = os.path.join(ROOT, "owl-path-tracer_amd", "csrc")
-    env = {k: v for k, v in os.environ.items() if k not in ("CXXFLAGS", "MAKEFLAGS")}
-    r = subprocess.run(["make", "-s", "-C", csrc, target], env=env, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, (r.stdout + r.stderr)[-2000:]
-    blocks = re.findall(r"Function Name: (\S+).*?TotalSGPRs: (\d+).*?VGPRs: (\d+).*?AGPRs: (\d+).*?ScratchSize \[bytes/lane\]: (\d+).*?Occupancy \[waves/SIMD\]: (\d+)"
-                        r".*?LDS Size \[bytes/block\]: (\d+)", r.stdout + r.stderr, flags=re.S)
-    return {b[0]: dict(sgprs=int(b[1]), vgprs=int(b[2]), agprs=int(b[3]), scratch=int(b[4]), occupancy=int(b[5]), lds=int(b[6])) for b in blocks}
-
-
 def test_accum_kernels_need_no_scratch():
     """From the Makefile's own target (the flags that ship): two kernels, ScratchSize 0, no LDS."""
-    rep = _report("asm-accum")
+    rep = resource_report.resources("asm-accum")
     assert len(rep) == 2, sorted(rep)
     for stage in ("resolve", "select"):
         assert sum(("pt_accum_%s_kernel" % stage) in nm for nm in rep) == 1, sorted(rep)
@@ -273,7 +261,7 @@ def test_render_kernels_are_the_parents(target):
     """The render kernel has no VGPR to spare (128 of 128): every instance of its three translation units reports what it reported before
     the accumulation existed."""
     want = json.load(open(os.path.join(ROOT, "tests", "golden", "render_kernel_resources.json")))["targets"][target]
-    got = _report(target)
+    got = resource_report.resources(target)
     assert sorted(got) == sorted(want)
     assert sum("pt_render_" in nm for nm in want) == 5, "the product, fallback and instrumented instances"
     if target == "asm":

@@ -27,8 +27,6 @@
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -37,6 +35,7 @@ import accum_reproject_common as RC
 import accum_reproject_ref as RR
 import aov_common as AC
 import denoise_common as DC
+import resource_report
 from owl_path_tracer_amd.pyhost import binding as B
 
 ROOT = AC.ROOT
@@ -325,13 +324,7 @@ def test_refusals(host):
 # ---- build --------------------------------------------------------------------------------------------------------------------
 def test_reproject_kernel_needs_no_scratch():
     """From the Makefile's own target (the flags that ship): exactly one kernel, ScratchSize 0."""
-    if not (shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc")):
-        pytest.skip("hipcc not available")
-    csrc = os.path.join(ROOT, "owl-path-tracer_amd", "csrc")
-    env = {k: v for k, v in os.environ.items() if k not in ("CXXFLAGS", "MAKEFLAGS")}
-    r = subprocess.run(["make", "-s", "-C", csrc, "asm-accum-reproject"], env=env, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, (r.stdout + r.stderr)[-2000:]
-    blocks = re.findall(r"Function Name: (\S+).*?VGPRs: (\d+).*?ScratchSize \[bytes/lane\]: (\d+)", r.stdout + r.stderr, flags=re.S)
+    blocks = resource_report.report("asm-accum-reproject")[1]
     assert len(blocks) == 1 and "pt_accum_reproject_kernel" in blocks[0][0], blocks
     assert int(blocks[0][2]) == 0, blocks
     print("pt_accum_reproject_kernel: %s VGPRs" % blocks[0][1])

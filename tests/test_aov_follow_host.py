@@ -18,10 +18,7 @@
   first hit is the mirror or the pane: follow < first-hit.  (When the test was written: 773 pixels, 0.190 noisy, 0.552 with first-hit
   guides, 0.160 with follow guides; the test prints its own figures.)"""
 import ctypes as C
-import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -29,6 +26,7 @@ import pytest
 import aov_follow_common as FC
 import aov_follow_ref as FR
 import refit_common as RC
+import resource_report
 from owl_path_tracer_amd.pyhost import binding as B, scene_io
 
 ROOT = FC.ROOT
@@ -272,20 +270,10 @@ def test_host_only_context_after_update_vertices():
         dyn.close()
 
 
-def _asm_report(target):
-    if not (shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc")):
-        pytest.skip("hipcc not available")
-    csrc = os.path.join(ROOT, "owl-path-tracer_amd", "csrc")
-    env = {k: v for k, v in os.environ.items() if k not in ("CXXFLAGS", "MAKEFLAGS")}
-    r = subprocess.run(["make", "-s", "-C", csrc, target], env=env, capture_output=True, text=True, timeout=1500)
-    assert r.returncode == 0, (r.stdout + r.stderr)[-2000:]
-    return re.findall(r"Function Name: (\S+).*?VGPRs: (\d+).*?ScratchSize \[bytes/lane\]: (\d+)", r.stdout + r.stderr, flags=re.S)
-
-
 def test_follow_kernels_need_no_scratch_and_fit_128_vgprs():
     """From the Makefile's own target (the flags that ship): the five follow kernels and no other, ScratchSize 0, at most 128 VGPRs - the
     four waves per SIMD the kernel is launched with."""
-    blocks = _asm_report("asm-aov-follow")
+    blocks = resource_report.report("asm-aov-follow")[1]
     names = [b[0] for b in blocks]
     assert all("pt_aov_follow_" in nm for nm in names), names  # told from pt_aov_kernel / pt_aov_wt_kernel by name
     assert len(blocks) == 5 and len(set(names)) == 5, names  # binary walk + two slab forms of the quad walk; the watertight build: the two quad forms
@@ -295,7 +283,7 @@ def test_follow_kernels_need_no_scratch_and_fit_128_vgprs():
 
 
 def test_first_hit_translation_units_keep_their_five_kernels():
-    blocks = _asm_report("asm-aov")
+    blocks = resource_report.report("asm-aov")[1]
     names = [b[0] for b in blocks]
     assert len(blocks) == 5 and len(set(names)) == 5 and not any("follow" in nm for nm in names), names
     assert sum("pt_aov_wt_kernel" in nm for nm in names) == 2 and sum("pt_aov_kernel" in nm for nm in names) == 3, names

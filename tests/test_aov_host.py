@@ -12,10 +12,7 @@
 * A host-only context after pt_update_vertices equals a fresh upload of the moved meshes.
 * The guide kernels need no scratch: the resource report of `make asm-aov`."""
 import ctypes as C
-import os
 import re
-import shutil
-import subprocess
 from fractions import Fraction
 
 import numpy as np
@@ -24,6 +21,7 @@ import pytest
 import aov_common as AC
 import aov_ref
 import refit_common as RC
+import resource_report
 from owl_path_tracer_amd.pyhost import binding as B
 
 ROOT = AC.ROOT
@@ -207,13 +205,7 @@ def test_host_only_context_after_update_vertices(scene_name, frm, at):
 
 def test_guide_kernels_need_no_scratch():
     """From the Makefile's own target (the flags that ship): every instance of the guide kernel, both builds, reports ScratchSize 0."""
-    if not (shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc")):
-        pytest.skip("hipcc not available")
-    csrc = os.path.join(ROOT, "owl-path-tracer_amd", "csrc")
-    env = {k: v for k, v in os.environ.items() if k not in ("CXXFLAGS", "MAKEFLAGS")}
-    r = subprocess.run(["make", "-s", "-C", csrc, "asm-aov"], env=env, capture_output=True, text=True, timeout=1500)
-    assert r.returncode == 0, (r.stdout + r.stderr)[-2000:]
-    blocks = re.findall(r"Function Name: (\S+).*?VGPRs: (\d+).*?ScratchSize \[bytes/lane\]: (\d+)", r.stdout + r.stderr, flags=re.S)
+    blocks = resource_report.report("asm-aov")[1]
     names = [b[0] for b in blocks]
     assert all("pt_aov_" in nm for nm in names), "the guide translation units hold the guide kernels and no other: %r" % (names,)
     assert len(blocks) == 5 and len(set(names)) == 5, names  # binary walk + two slab forms of the quad walk; the watertight build: the two quad forms

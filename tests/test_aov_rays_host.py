@@ -17,8 +17,6 @@ import ctypes as C
 import json
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -26,6 +24,7 @@ import pytest
 import aov_rays_common as RC
 import aov_rays_ref
 import ray_image_ref as RR
+import resource_report
 from owl_path_tracer_amd.pyhost import binding as B
 from owl_path_tracer_amd.pyhost import ray_image as RI
 from owl_path_tracer_amd.pyhost import scene_io
@@ -277,24 +276,11 @@ def test_consequence_c_sample_0_is_the_first_camera_ray(orc, name):
 
 
 # ---- resource reports ---------------------------------------------------------------------------------------------------
-def _report(target):
-    if not (shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc")):
-        pytest.skip("hipcc not available")
-    csrc = os.path.join(ROOT, "owl-path-tracer_amd", "csrc")
-    env = {k: v for k, v in os.environ.items() if k not in ("CXXFLAGS", "MAKEFLAGS")}
-    r = subprocess.run(["make", "-s", "-C", csrc, target], env=env, capture_output=True, text=True, timeout=1500)
-    assert r.returncode == 0, (r.stdout + r.stderr)[-2000:]
-    blocks = re.findall(r"Function Name: (\S+).*?TotalSGPRs: (\d+).*?VGPRs: (\d+).*?AGPRs: (\d+).*?ScratchSize \[bytes/lane\]: (\d+).*?Occupancy \[waves/SIMD\]: (\d+)"
-                        r".*?LDS Size \[bytes/block\]: (\d+)", r.stdout + r.stderr, flags=re.S)
-    assert len({b[0] for b in blocks}) == len(blocks)
-    return {b[0]: dict(sgprs=int(b[1]), vgprs=int(b[2]), agprs=int(b[3]), scratch=int(b[4]), occupancy=int(b[5]), lds=int(b[6])) for b in blocks}
-
-
 def test_ray_image_guide_kernels_need_no_scratch_and_fit_128_vgprs():
     """From the Makefile's own target (the flags that ship): the four ray-image instances and no other - both slab forms of the quad walk
     under both triangle tests - ScratchSize 0, at most 128 VGPRs (the four waves per SIMD the kernel is launched with), no static LDS:
     what the kernel uses is the launch's dynamic allocation, (PT_LDS_STACK + PT_AOV_PARK) * 64 * 4 bytes of a CU's 160 KB."""
-    rep = _report("asm-aov-rays")
+    rep = resource_report.resources("asm-aov-rays")
     names = sorted(rep)
     assert len(rep) == 4, names
     assert sum("pt_aov_rays_wt_kernel" in nm for nm in names) == 2 and sum("pt_aov_rays_kernel" in nm for nm in names) == 2, names
@@ -307,7 +293,7 @@ def test_ray_image_guide_kernels_need_no_scratch_and_fit_128_vgprs():
 
 def test_the_other_guide_targets_list_their_kernels():
     for target, count, word, wt in (("asm-aov-follow", 5, "pt_aov_follow_", 2), ("asm-aov", 5, "pt_aov_", 2), ("asm-aov-follow-batch", 3, "pt_aov_follow_batch_kernel", 0)):
-        rep = _report(target)
+        rep = resource_report.resources(target)
         names = sorted(rep)
         assert len(rep) == count and all(word in nm for nm in names) and not any("rays" in nm for nm in names), (target, names)
         assert sum("_wt_kernel" in nm for nm in names) == wt, (target, names)
@@ -319,7 +305,7 @@ def test_the_other_guide_targets_list_their_kernels():
 @pytest.mark.parametrize("target", ["asm", "asm-wt", "asm-batch"])
 def test_render_kernels_are_the_parents(target):
     want = json.load(open(os.path.join(ROOT, "tests", "golden", "render_kernel_resources.json")))["targets"][target]
-    got = _report(target)
+    got = resource_report.resources(target)
     assert sorted(got) == sorted(want)
     for nm in want:
         assert got[nm] == want[nm], (nm, got[nm], want[nm])

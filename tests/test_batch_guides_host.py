@@ -8,14 +8,13 @@
 * The references tests/test_gpu_batch_guides.py uses are sound on the CPU: for every frame of batch_guides_common.py - the moved cameras,
   the changed tables - pt_debug_aov_follow_host equals tests/aov_follow_ref.py over a `flat` built with the frame's table."""
 import ctypes as C
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import batch_guides_common as BG
+import resource_report
 from owl_path_tracer_amd.pyhost import binding as B
 
 F32 = np.float32
@@ -130,17 +129,8 @@ def test_denoise_batch_refusals_on_a_host_only_context():
         ctx.close()
 
 
-def _asm_report(target):
-    """(function name, VGPRs, scratch bytes per lane) of every kernel `make <target>` reports, with the flags that ship."""
-    csrc = os.path.join(BG.FC.ROOT, "owl-path-tracer_amd", "csrc")
-    env = {k: v for k, v in os.environ.items() if k not in ("CXXFLAGS", "MAKEFLAGS")}
-    r = subprocess.run(["make", "-s", "-C", csrc, target], env=env, capture_output=True, text=True, timeout=1500)
-    assert r.returncode == 0, (r.stdout + r.stderr)[-2000:]
-    return re.findall(r"Function Name: (\S+).*?VGPRs: (\d+).*?ScratchSize \[bytes/lane\]: (\d+)", r.stdout + r.stderr, flags=re.S)
-
-
 def test_batch_guide_kernels_need_no_scratch_and_fit_128_vgprs():
-    blocks = _asm_report("asm-aov-follow-batch")
+    blocks = resource_report.report("asm-aov-follow-batch")[1]
     names = [b[0] for b in blocks]
     assert len(blocks) == 3 and len(set(names)) == 3, names  # the binary walk and the two slab forms of the quad walk
     assert all("pt_aov_follow_batch" in nm for nm in names), names
@@ -149,7 +139,7 @@ def test_batch_guide_kernels_need_no_scratch_and_fit_128_vgprs():
 
 
 def test_batch_denoise_kernels_need_no_scratch():
-    blocks = _asm_report("asm-denoise-batch")
+    blocks = resource_report.report("asm-denoise-batch")[1]
     names = [b[0] for b in blocks]
     assert len(blocks) == 3 and len(set(names)) == 3, names
     for stage in ("prepare", "iter", "finish"):

@@ -10,6 +10,7 @@ import sys
 import numpy as np
 import pytest
 
+import resource_report
 from owl_path_tracer_amd.pyhost import binding as B
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -112,34 +113,13 @@ def test_batch_argument_errors_on_a_host_only_context(cube):
     ctx.close()
 
 
-def _hipcc_resource_report(source):
-    """hipcc's -Rpass-analysis=kernel-resource-usage for one file with the Makefile's CXXFLAGS (the method of
-    tests/test_abi_host.py::test_render_kernel_instances_need_no_scratch)."""
-    import shlex, shutil, tempfile
-
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    with open(os.path.join(CSRC, "Makefile")) as f:
-        flags = shlex.split(re.search(r"^CXXFLAGS\s*\?=(.*)$", f.read(), flags=re.M).group(1))
-    env = {k: v for k, v in os.environ.items() if k not in ("CXXFLAGS", "MAKEFLAGS")}
-    dry = subprocess.run(["make", "-n", "-s", "-C", CSRC, "asm-batch"], env=env, capture_output=True, text=True, timeout=60)
-    assert dry.returncode == 0, dry.stderr
-    made = shlex.split(dry.stdout.strip().splitlines()[-1])
-    assert made[:2] == [made[0], "--offload-arch=gfx950"] and made[2:2 + len(flags)] == flags and made[2 + len(flags)] == "-S", (flags, made)
-    with tempfile.TemporaryDirectory() as td:
-        r = subprocess.run([hipcc, "--offload-arch=gfx950"] + flags + ["-S", "--cuda-device-only", "-o", os.path.join(td, "k.s"), os.path.join(CSRC, source),
-                            "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-2000:]
-    return r.stderr
-
-
 def test_batch_kernel_instances_need_no_scratch():
     """pt_render_batch refuses a batch instance that spills, as pt_render does for the single-frame ones (plan_frame): every batch
     instance must report ScratchSize 0, there must be exactly the five the launcher selects from (pt_launch_render_batch: product and
     fallback budget, each with the fma and the subtracting slab form, and the instrumented instance), and the batch translation unit
     must not define a second copy of the single-frame kernel."""
-    report = _hipcc_resource_report("pt_kernel_batch.hip")
+    resource_report.assert_ships_with_makefile_flags("pt_kernel_batch")
+    report = resource_report.report("asm-batch")[0]
     blocks = re.findall(r"Function Name: (\S*pt_render_batch_kernel\S*).*?VGPRs: (\d+).*?ScratchSize \[bytes/lane\]: (\d+)", report, flags=re.S)
     names = sorted(n for n, _, _ in blocks)
     # <COUNT, WAVES, EXACT> of the five instances pt_launch_render_batch launches (PT_WAVES_PER_EU 4, PT_FALLBACK_WAVES 3, PT_COUNT_WAVES_PER_EU 2)

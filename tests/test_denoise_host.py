@@ -19,7 +19,6 @@
 import ctypes as C
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
@@ -28,6 +27,7 @@ import pytest
 import aov_common as AC
 import denoise_common as DC
 import denoise_ref
+import resource_report
 from owl_path_tracer_amd.pyhost import binding as B
 
 ROOT = AC.ROOT
@@ -126,13 +126,7 @@ def test_refusals(host):
 
 def test_denoise_kernels_need_no_scratch():
     """From the Makefile's own target (the flags that ship): the three kernels report ScratchSize 0."""
-    if not (shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc")):
-        pytest.skip("hipcc not available")
-    csrc = os.path.join(ROOT, "owl-path-tracer_amd", "csrc")
-    env = {k: v for k, v in os.environ.items() if k not in ("CXXFLAGS", "MAKEFLAGS")}
-    r = subprocess.run(["make", "-s", "-C", csrc, "asm-denoise"], env=env, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, (r.stdout + r.stderr)[-2000:]
-    blocks = re.findall(r"Function Name: (\S+).*?VGPRs: (\d+).*?ScratchSize \[bytes/lane\]: (\d+)", r.stdout + r.stderr, flags=re.S)
+    blocks = resource_report.report("asm-denoise")[1]
     names = [b[0] for b in blocks]
     assert len(blocks) == 3 and all("pt_denoise_" in nm for nm in names), names
     for stage in ("prepare", "iter", "finish"):

@@ -26,7 +26,6 @@
 import ctypes as C
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
@@ -36,6 +35,7 @@ import aov_common as AC
 import denoise_common as DC
 import denoise_var_common as VC
 import denoise_var_ref as VR
+import resource_report
 from owl_path_tracer_amd.pyhost import binding as B
 
 ROOT = AC.ROOT
@@ -367,13 +367,7 @@ def test_quality_icospheres(orc, host):
 # ---- build and tool -----------------------------------------------------------------------------------------------------------
 def test_denoise_var_kernels_need_no_scratch():
     """From the Makefile's own target (the flags that ship): exactly four kernels, each with ScratchSize 0."""
-    if not (shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc")):
-        pytest.skip("hipcc not available")
-    csrc = os.path.join(ROOT, "owl-path-tracer_amd", "csrc")
-    env = {k: v for k, v in os.environ.items() if k not in ("CXXFLAGS", "MAKEFLAGS")}
-    r = subprocess.run(["make", "-s", "-C", csrc, "asm-denoise-var"], env=env, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, (r.stdout + r.stderr)[-2000:]
-    blocks = re.findall(r"Function Name: (\S+).*?VGPRs: (\d+).*?ScratchSize \[bytes/lane\]: (\d+)", r.stdout + r.stderr, flags=re.S)
+    blocks = resource_report.report("asm-denoise-var")[1]
     names = [b[0] for b in blocks]
     assert len(blocks) == 4, names
     for kernel in ("pt_accum_variance_kernel", "pt_denoise_var_prepare_kernel", "pt_denoise_var_iter_kernel", "pt_denoise_var_finish_kernel"):

@@ -9,16 +9,14 @@
   sky, and the 1 x 1 form is the camera it names.
 * `make asm-rayimage`: exactly the five instances, no scratch, the 4-wave instances within 128 VGPRs."""
 import ctypes as C
-import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import aov_common as AC
 import ray_image_ref as RR
+import resource_report
 from owl_path_tracer_amd.pyhost import binding as B
 from owl_path_tracer_amd.pyhost import ray_image as RI
 
@@ -256,13 +254,7 @@ def test_ray_image_kernel_resources():
     """From the Makefile's own target (the flags that ship): the five instances of the translation unit and nothing else - the instrumented
     one, both slab forms of the 4-wave product instance and of its 3-wave fallback - no scratch anywhere, the 4-wave instances within 128
     VGPRs."""
-    if not (shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc")):
-        pytest.skip("hipcc not available")
-    csrc = os.path.join(AC.ROOT, "owl-path-tracer_amd", "csrc")
-    env = {k: v for k, v in os.environ.items() if k not in ("CXXFLAGS", "MAKEFLAGS")}
-    r = subprocess.run(["make", "-s", "-C", csrc, "asm-rayimage"], env=env, capture_output=True, text=True, timeout=1500)
-    assert r.returncode == 0, (r.stdout + r.stderr)[-2000:]
-    blocks = re.findall(r"Function Name: (\S+).*?VGPRs: (\d+).*?ScratchSize \[bytes/lane\]: (\d+)", r.stdout + r.stderr, flags=re.S)
+    blocks = resource_report.report("asm-rayimage")[1]
     names = [b[0] for b in blocks]
     assert len(blocks) == 5 and len(set(names)) == 5, names
     assert all("pt_render_rayimage_kernel" in nm for nm in names), "the ray-image translation unit holds the ray-image kernels and no other: %r" % (names,)

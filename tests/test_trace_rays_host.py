@@ -12,15 +12,13 @@
 * After pt_update_vertices on a "dynamic" upload the twin equals a fresh upload; pt_prim_to_mesh on a two-mesh scene; every refusal and
   error code of the header on a host-only context; n = 0; `make asm-rays`: exactly the eight instances, 0 scratch, at most 128 VGPRs."""
 import ctypes as C
-import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import ray_battery as rb
+import resource_report
 import trace_rays_common as TC
 from owl_path_tracer_amd.pyhost import binding as B
 from owl_path_tracer_amd.pyhost import scene_io
@@ -238,13 +236,7 @@ def test_n_zero(orc):
 def test_ray_kernels_resources():
     """From the Makefile's own target (the flags that ship): the four <OCCLUDED, EXACT> instances of each translation unit and nothing
     else, no scratch, at most 128 VGPRs (four waves per SIMD)."""
-    if not (shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc")):
-        pytest.skip("hipcc not available")
-    csrc = os.path.join(ROOT, "owl-path-tracer_amd", "csrc")
-    env = {k: v for k, v in os.environ.items() if k not in ("CXXFLAGS", "MAKEFLAGS")}
-    r = subprocess.run(["make", "-s", "-C", csrc, "asm-rays"], env=env, capture_output=True, text=True, timeout=1500)
-    assert r.returncode == 0, (r.stdout + r.stderr)[-2000:]
-    blocks = re.findall(r"Function Name: (\S+).*?VGPRs: (\d+).*?ScratchSize \[bytes/lane\]: (\d+)", r.stdout + r.stderr, flags=re.S)
+    blocks = resource_report.report("asm-rays")[1]
     names = [b[0] for b in blocks]
     assert len(blocks) == 8 and len(set(names)) == 8, names
     assert all("pt_rays_" in nm for nm in names), "the ray translation units hold the ray kernels and no other: %r" % (names,)

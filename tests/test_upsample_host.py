@@ -23,7 +23,6 @@
 import ctypes as C
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
@@ -31,6 +30,7 @@ import pytest
 
 import aov_common as AC
 import denoise_common as DC
+import resource_report
 import upsample_common as UC
 import upsample_ref
 from owl_path_tracer_amd.pyhost import binding as B
@@ -152,13 +152,7 @@ def test_refusals(host):
 
 def test_upsample_kernels_need_no_scratch():
     """From the Makefile's own target (the flags that ship): the two kernels report ScratchSize 0."""
-    if not (shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc")):
-        pytest.skip("hipcc not available")
-    csrc = os.path.join(ROOT, "owl-path-tracer_amd", "csrc")
-    env = {k: v for k, v in os.environ.items() if k not in ("CXXFLAGS", "MAKEFLAGS")}
-    r = subprocess.run(["make", "-s", "-C", csrc, "asm-upsample"], env=env, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, (r.stdout + r.stderr)[-2000:]
-    blocks = re.findall(r"Function Name: (\S+).*?VGPRs: (\d+).*?ScratchSize \[bytes/lane\]: (\d+)", r.stdout + r.stderr, flags=re.S)
+    blocks = resource_report.report("asm-upsample")[1]
     names = [b[0] for b in blocks]
     assert len(blocks) == 2, names
     assert sum("pt_upsample_prepare_kernel" in nm for nm in names) == 1 and sum("pt_upsample_kernel" in nm for nm in names) == 1, names

@@ -211,24 +211,10 @@ def test_watertight_instances_need_no_scratch():
     """hipcc's resource report for pt_kernel_wt.hip with the flags `make asm-wt` passes (the Makefile's CXXFLAGS): the five render
     instances the library can launch (product / fallback, fma and subtracting slab form each, + the instrumented one) and the five
     probe kernels all show ScratchSize 0.  (plan_frame refuses an instance with scratch; this finds it without a GPU.)"""
-    import shlex, shutil, subprocess, tempfile
+    import resource_report
 
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    csrc = os.path.join(ROOT, "owl-path-tracer_amd", "csrc")
-    with open(os.path.join(csrc, "Makefile")) as f:
-        flags = shlex.split(re.search(r"^CXXFLAGS\s*\?=(.*)$", f.read(), flags=re.M).group(1))
-    env = {k: v for k, v in os.environ.items() if k not in ("CXXFLAGS", "MAKEFLAGS")}
-    dry = subprocess.run(["make", "-n", "-s", "-C", csrc, "asm-wt"], env=env, capture_output=True, text=True, timeout=60)
-    assert dry.returncode == 0, dry.stderr
-    made = shlex.split(dry.stdout.strip().splitlines()[-1])
-    assert made[:2] == [made[0], "--offload-arch=gfx950"] and made[2:2 + len(flags)] == flags and made[2 + len(flags)] == "-S" and "pt_kernel_wt.hip" in made, (flags, made)
-    with tempfile.TemporaryDirectory() as td:
-        r = subprocess.run([hipcc, "--offload-arch=gfx950"] + flags + ["-S", "--cuda-device-only", "-o", os.path.join(td, "k.s"), os.path.join(csrc, "pt_kernel_wt.hip"),
-                            "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-2000:]
-    blocks = re.findall(r"Function Name: (\S+).*?VGPRs: (\d+).*?ScratchSize \[bytes/lane\]: (\d+)", r.stderr, flags=re.S)
+    resource_report.assert_ships_with_makefile_flags("pt_kernel_wt")
+    blocks = resource_report.report("asm-wt")[1]
     render = [b for b in blocks if "pt_render_wt_kernel" in b[0]]
     probes = [b for b in blocks if "pt_probe_quad_wt_kernel" in b[0] or "pt_probe_group_wt_kernel" in b[0]]
     assert len(render) == 5 and len(probes) == 5, blocks
