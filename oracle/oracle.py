@@ -94,6 +94,10 @@ def lib():
     L.orc_intersect_n.argtypes = [C.c_void_p, fp, C.c_int64, C.c_float, C.c_float, C.c_int, C.c_int, fp]
     L.orc_render.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(Env), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                              C.POINTER(C.c_uint32), C.c_int64, fp, C.POINTER(C.c_uint32), C.POINTER(Counters)]
+    L.orc_render_rays.argtypes = [C.c_void_p, fp, C.POINTER(Env), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                  C.POINTER(C.c_uint32), C.c_int64, fp, C.POINTER(C.c_uint32), C.POINTER(Counters)]
+    L.orc_trace_sample_rays.argtypes = [C.c_void_p, fp, C.POINTER(Env), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, fp, C.c_int]
+    L.orc_trace_pixel_rays.argtypes = [C.c_void_p, fp, C.POINTER(Env), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, fp, C.POINTER(C.c_uint32)]
     L.orc_accumulate.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(Env), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                  C.POINTER(C.c_uint32), C.c_int64, C.c_int, C.POINTER(C.c_uint32), fp, C.POINTER(Counters)]
     L.orc_trace_pixel.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(Env), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
@@ -299,6 +303,19 @@ def make_env(use_map=False, use_auto=False, color=(0, 0, 0), intensity=0.0, env_
     return e
 
 
+def _table_floats(table, W, H):
+    """A ray image as the W * H * 16 contiguous float32 the library reads: the bytes of the records, whatever the reserved floats hold."""
+    t = np.ascontiguousarray(table)
+    if t.dtype != np.float32:
+        if t.dtype.itemsize != 64:
+            raise ValueError("ray image: records of %d bytes, not 64" % t.dtype.itemsize)
+        t = t.reshape(-1).view(np.float32)
+    t = t.reshape(-1)
+    if t.size != W * H * 16:
+        raise ValueError("ray image: %d floats for a %dx%d image, not %d" % (t.size, W, H, W * H * 16))
+    return t
+
+
 class Scene:
     """Oracle scene built from a flattened triangle soup (see pyhost.scene_io.flatten_scene)."""
 
@@ -401,6 +418,54 @@ class Scene:
         if rc != 0:
             raise RuntimeError("orc_render failed: %d" % rc)
         return rgb, rgba, (cnt.as_dict() if cnt is not None else None)
+
+    def render_rays(self, table, env, W, H, spp, max_depth, use_bvh=True, threads=None, pixel_list=None, want_rgba8=False,
+                    want_counters=False, out=None):
+        """render() of a ray image: `table` is W * H records of 64 bytes laid out as pt_ray_gen (a structured array, or W*H*16 float32),
+        the record of pixel (x, y) at x + W * y; a sample's path starts at org along normalize((dir + du * rx) + dv * ry).  Returns what
+        render() returns."""
+        tab = _table_floats(table, W, H)
+        if threads is None:
+            threads = os.cpu_count() or 1
+        rgb = out if out is not None else np.zeros((H, W, 3), np.float32)
+        rgba = np.zeros((H, W), np.uint32) if want_rgba8 else None
+        cnt = Counters() if want_counters else None
+        pl = None
+        npx = 0
+        if pixel_list is not None:
+            pl = np.ascontiguousarray(pixel_list, np.uint32)
+            npx = pl.size
+            if npx and int(pl.max()) >= W * H:
+                raise ValueError("render_rays: pixel_list names a pixel outside the image")
+        rc = lib().orc_render_rays(self.h, tab.ctypes.data_as(C.POINTER(C.c_float)), C.byref(env), W, H, spp, max_depth, int(use_bvh),
+                                   int(threads), pl.ctypes.data_as(C.POINTER(C.c_uint32)) if pl is not None else None, npx,
+                                   rgb.ctypes.data_as(C.POINTER(C.c_float)),
+                                   rgba.ctypes.data_as(C.POINTER(C.c_uint32)) if rgba is not None else None,
+                                   C.byref(cnt) if cnt is not None else None)
+        if rc != 0:
+            raise RuntimeError("orc_render_rays failed: %d" % rc)
+        return rgb, rgba, (cnt.as_dict() if cnt is not None else None)
+
+    def trace_sample_rays(self, table, env, W, H, px, py, sample, max_depth, use_bvh=True, max_rows=256):
+        """trace_sample() of one sample of pixel (px, py) of a ray image: row 0 holds the ray the sample starts on."""
+        tab = _table_floats(table, W, H)
+        log = np.zeros((max_rows, 32), np.float32)
+        n = lib().orc_trace_sample_rays(self.h, tab.ctypes.data_as(C.POINTER(C.c_float)), C.byref(env), W, H, int(px), int(py), int(sample),
+                                        int(max_depth), int(use_bvh), log.ctypes.data_as(C.POINTER(C.c_float)), max_rows)
+        if n < 0:
+            raise RuntimeError("orc_trace_sample_rays failed: %d" % n)
+        return log[:n]
+
+    def trace_pixel_rays(self, table, env, W, H, px, py, spp, max_depth, use_bvh=True):
+        """trace_pixel() of pixel (px, py) of a ray image: (per-sample radiance (spp, 3), the stream's state after each sample (spp,))."""
+        tab = _table_floats(table, W, H)
+        rgb = np.zeros((spp, 3), np.float32)
+        st = np.zeros(spp, np.uint32)
+        rc = lib().orc_trace_pixel_rays(self.h, tab.ctypes.data_as(C.POINTER(C.c_float)), C.byref(env), W, H, int(px), int(py), int(spp), int(max_depth),
+                                        int(use_bvh), rgb.ctypes.data_as(C.POINTER(C.c_float)), st.ctypes.data_as(C.POINTER(C.c_uint32)))
+        if rc != 0:
+            raise RuntimeError("orc_trace_pixel_rays failed: %d" % rc)
+        return rgb, st
 
     def accumulate(self, cam, env, W, H, n_samples, max_depth, rng, sum, pixel_list=None, first=False, threads=None, use_bvh=True):
         """n_samples more samples for the launch ids x + W*y of pixel_list (None: every pixel), continuing from rng[id] (uint32, W*H) and

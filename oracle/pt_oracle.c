@@ -1381,22 +1381,44 @@ static v3 trace_path(const render_ctx* rc, v3 org, v3 dir, uint32_t* rng, orc_co
     return vmul(radiance, throughput); /* device.cu:217 */
 }
 
+/* Where a sample's first ray comes from: a camera (ray_gen, device.cu:239-240), or a ray image - W * H records of 16 floats laid out as
+   pt_ray_gen (include/mi355pt.h), the record of pixel (px, py) at 16 * (px + W * py): org at floats 0-2, dir, du, dv from floats 4, 8
+   and 12; floats 3, 7, 11 and 15 are never read.  Exactly one of the two is set. */
+typedef struct ray_source {
+    const orc_camera* cam;
+    const float* table;
+} ray_source;
+
+/* The first ray of a sample of pixel (px, py) whose two draws were rx, then ry. */
+static inline void first_ray(const ray_source* src, int W, int H, int px, int py, float rx, float ry, v3* org, v3* dir)
+{
+    if (src->table) {
+        const float* r = src->table + 16 * ((size_t)px + (size_t)W * (size_t)py);
+        *org = ld3(r);
+        *dir = vnormalize(vadd(vadd(ld3(r + 4), vscale(ld3(r + 8), rx)), vscale(ld3(r + 12), ry)));
+        return;
+    }
+    const orc_camera* cam = src->cam;
+    v3 origin = ld3(cam->origin), llc = ld3(cam->llc), hor = ld3(cam->horizontal), ver = ld3(cam->vertical);
+    float su = ((float)px + rx) / (float)W;
+    float sv = ((float)py + ry) / (float)H;
+    /* llc + u*horizontal + v*vertical - origin, left to right (device.cu:239-240) */
+    *org = origin;
+    *dir = vnormalize(vsub(vadd(vadd(llc, vscale(hor, su)), vscale(ver, sv)), origin));
+}
+
 /* `n` more iterations of ray_gen's sample loop (device.cu:232-245) for one pixel, continuing from *rng and *color: THE one copy of the
-   loop.  per_sample_*: optional, n entries. */
-static void accumulate_pixel(const render_ctx* rc, const orc_camera* cam, int W, int H, int px, int py, int n, uint32_t* rng_io, v3* color_io,
+   loop, for a camera's frame and for a ray image.  per_sample_*: optional, n entries. */
+static void accumulate_pixel(const render_ctx* rc, const ray_source* src, int W, int H, int px, int py, int n, uint32_t* rng_io, v3* color_io,
                              orc_counters* cnt, float* per_sample_rgb, uint32_t* per_sample_state)
 {
     uint32_t rng = *rng_io;
     v3 color = *color_io;
-    v3 origin = ld3(cam->origin), llc = ld3(cam->llc), hor = ld3(cam->horizontal), ver = ld3(cam->vertical);
     for (int s = 0; s < n; ++s) {
         float rx = rng_next(&rng);
         float ry = rng_next(&rng);
-        float su = ((float)px + rx) / (float)W;
-        float sv = ((float)py + ry) / (float)H;
-        /* llc + u*horizontal + v*vertical - origin, left to right (device.cu:239-240) */
-        v3 d = vsub(vadd(vadd(llc, vscale(hor, su)), vscale(ver, sv)), origin);
-        d = vnormalize(d);
+        v3 origin, d;
+        first_ray(src, W, H, px, py, rx, ry, &origin, &d);
         v3 r = trace_path(rc, origin, d, &rng, cnt);
         color = vadd(color, r);
         if (cnt) cnt->samples++;
@@ -1408,19 +1430,19 @@ static void accumulate_pixel(const render_ctx* rc, const orc_camera* cam, int W,
 }
 
 /* one pixel of ray_gen, device.cu:220-254: accumulate from the seed, then scale */
-static v3 render_pixel(const render_ctx* rc, const orc_camera* cam, int W, int H, int px, int py, int max_samples, orc_counters* cnt,
+static v3 render_pixel(const render_ctx* rc, const ray_source* src, int W, int H, int px, int py, int max_samples, orc_counters* cnt,
                        float* per_sample_rgb, uint32_t* per_sample_state)
 {
     uint32_t rng = orc_rng_init((uint32_t)px, (uint32_t)py);
     v3 color = vs(0.0f);
-    accumulate_pixel(rc, cam, W, H, px, py, max_samples, &rng, &color, cnt, per_sample_rgb, per_sample_state);
+    accumulate_pixel(rc, src, W, H, px, py, max_samples, &rng, &color, cnt, per_sample_rgb, per_sample_state);
     color = vscale(color, 1.0f / (float)max_samples); /* device.cu:247 */
     return color;
 }
 
 typedef struct job {
     render_ctx rc;
-    const orc_camera* cam;
+    ray_source src;
     int W, H, max_samples;
     const uint32_t* pixel_list;
     int64_t n_pixels;
@@ -1451,12 +1473,12 @@ static void* worker(void* arg)
             if (j->acc_rng) {
                 uint32_t rng = j->acc_first ? orc_rng_init((uint32_t)px, (uint32_t)py) : j->acc_rng[id];
                 v3 c = j->acc_first ? vs(0.0f) : ld3(j->acc_sum + (size_t)id * 3);
-                accumulate_pixel(&j->rc, j->cam, j->W, j->H, px, py, j->max_samples, &rng, &c, j->want_counters ? &local : NULL, NULL, NULL);
+                accumulate_pixel(&j->rc, &j->src, j->W, j->H, px, py, j->max_samples, &rng, &c, j->want_counters ? &local : NULL, NULL, NULL);
                 j->acc_rng[id] = rng;
                 st3(j->acc_sum + (size_t)id * 3, c);
                 continue;
             }
-            v3 c = render_pixel(&j->rc, j->cam, j->W, j->H, px, py, j->max_samples, j->want_counters ? &local : NULL, NULL, NULL);
+            v3 c = render_pixel(&j->rc, &j->src, j->W, j->H, px, py, j->max_samples, j->want_counters ? &local : NULL, NULL, NULL);
             size_t ofs = (size_t)px + (size_t)j->W * (size_t)(j->H - 1 - py); /* device.cu:251 */
             if (j->out_rgb) st3(j->out_rgb + ofs * 3, c);
             if (j->out_rgba8) j->out_rgba8[ofs] = make_rgba(c);
@@ -1493,7 +1515,22 @@ int orc_render(const orc_scene* s, const orc_camera* cam, const orc_env* env, in
     job j;
     memset(&j, 0, sizeof(j));
     j.rc.s = s; j.rc.env = env; j.rc.max_depth = max_depth; j.rc.use_bvh = use_bvh;
-    j.cam = cam; j.W = W; j.H = H; j.max_samples = max_samples;
+    j.src.cam = cam; j.W = W; j.H = H; j.max_samples = max_samples;
+    j.pixel_list = pixel_list;
+    j.n_pixels = pixel_list ? n_pixels : (int64_t)W * H;
+    j.out_rgb = out_rgb; j.out_rgba8 = out_rgba8;
+    run_job(&j, n_threads, counters);
+    return 0;
+}
+
+int orc_render_rays(const orc_scene* s, const float* table, const orc_env* env, int W, int H, int max_samples, int max_depth, int use_bvh,
+                    int n_threads, const uint32_t* pixel_list, int64_t n_pixels, float* out_rgb, uint32_t* out_rgba8, orc_counters* counters)
+{
+    if (!s || !table || !env || W <= 0 || H <= 0 || max_samples <= 0) return -1;
+    job j;
+    memset(&j, 0, sizeof(j));
+    j.rc.s = s; j.rc.env = env; j.rc.max_depth = max_depth; j.rc.use_bvh = use_bvh;
+    j.src.table = table; j.W = W; j.H = H; j.max_samples = max_samples;
     j.pixel_list = pixel_list;
     j.n_pixels = pixel_list ? n_pixels : (int64_t)W * H;
     j.out_rgb = out_rgb; j.out_rgba8 = out_rgba8;
@@ -1511,7 +1548,7 @@ int orc_accumulate(const orc_scene* s, const orc_camera* cam, const orc_env* env
     job j;
     memset(&j, 0, sizeof(j));
     j.rc.s = s; j.rc.env = env; j.rc.max_depth = max_depth; j.rc.use_bvh = use_bvh;
-    j.cam = cam; j.W = W; j.H = H; j.max_samples = n_samples;
+    j.src.cam = cam; j.W = W; j.H = H; j.max_samples = n_samples;
     j.pixel_list = pixel_list;
     j.n_pixels = pixel_list ? n_pixels : (int64_t)W * H;
     j.acc_rng = rng; j.acc_sum = sum; j.acc_first = first != 0;
@@ -1521,20 +1558,18 @@ int orc_accumulate(const orc_scene* s, const orc_camera* cam, const orc_env* env
 
 /* Test infrastructure for bisecting a parity failure: the per-bounce log (see ORC_LOG_FLOATS) of sample `sample` of pixel (px, py).
    Returns the number of rows written. */
-int orc_trace_sample(const orc_scene* s, const orc_camera* cam, const orc_env* env, int W, int H, int px, int py, int sample, int max_depth,
-                     int use_bvh, float* log, int max_rows)
+static int trace_sample(const orc_scene* s, const ray_source* src, const orc_env* env, int W, int H, int px, int py, int sample, int max_depth,
+                        int use_bvh, float* log, int max_rows)
 {
     render_ctx rc;
     rc.s = s; rc.env = env; rc.max_depth = max_depth; rc.use_bvh = use_bvh;
     uint32_t rng = orc_rng_init((uint32_t)px, (uint32_t)py);
-    v3 origin = ld3(cam->origin), llc = ld3(cam->llc), hor = ld3(cam->horizontal), ver = ld3(cam->vertical);
     int rows = 0;
     for (int k = 0; k <= sample; ++k) {
         float rx = rng_next(&rng);
         float ry = rng_next(&rng);
-        float su = ((float)px + rx) / (float)W;
-        float sv = ((float)py + ry) / (float)H;
-        v3 d = vnormalize(vsub(vadd(vadd(llc, vscale(hor, su)), vscale(ver, sv)), origin));
+        v3 origin, d;
+        first_ray(src, W, H, px, py, rx, ry, &origin, &d);
         if (k == sample) { g_log = log; g_log_rows = 0; g_log_cap = max_rows; }
         trace_path(&rc, origin, d, &rng, NULL);
         if (k == sample) { rows = g_log_rows; g_log = NULL; g_log_cap = 0; }
@@ -1542,11 +1577,38 @@ int orc_trace_sample(const orc_scene* s, const orc_camera* cam, const orc_env* e
     return rows;
 }
 
+int orc_trace_sample(const orc_scene* s, const orc_camera* cam, const orc_env* env, int W, int H, int px, int py, int sample, int max_depth,
+                     int use_bvh, float* log, int max_rows)
+{
+    ray_source src = { cam, NULL };
+    return trace_sample(s, &src, env, W, H, px, py, sample, max_depth, use_bvh, log, max_rows);
+}
+
+int orc_trace_sample_rays(const orc_scene* s, const float* table, const orc_env* env, int W, int H, int px, int py, int sample, int max_depth,
+                          int use_bvh, float* log, int max_rows)
+{
+    ray_source src = { NULL, table };
+    if (!s || !table || !env || px < 0 || py < 0 || px >= W || py >= H) return -1;
+    return trace_sample(s, &src, env, W, H, px, py, sample, max_depth, use_bvh, log, max_rows);
+}
+
 int orc_trace_pixel(const orc_scene* s, const orc_camera* cam, const orc_env* env, int W, int H, int px, int py, int max_samples,
                     int max_depth, int use_bvh, float* per_sample_rgb, uint32_t* per_sample_state)
 {
     render_ctx rc;
     rc.s = s; rc.env = env; rc.max_depth = max_depth; rc.use_bvh = use_bvh;
-    render_pixel(&rc, cam, W, H, px, py, max_samples, NULL, per_sample_rgb, per_sample_state);
+    ray_source src = { cam, NULL };
+    render_pixel(&rc, &src, W, H, px, py, max_samples, NULL, per_sample_rgb, per_sample_state);
+    return 0;
+}
+
+int orc_trace_pixel_rays(const orc_scene* s, const float* table, const orc_env* env, int W, int H, int px, int py, int max_samples,
+                         int max_depth, int use_bvh, float* per_sample_rgb, uint32_t* per_sample_state)
+{
+    if (!s || !table || !env || px < 0 || py < 0 || px >= W || py >= H) return -1;
+    render_ctx rc;
+    rc.s = s; rc.env = env; rc.max_depth = max_depth; rc.use_bvh = use_bvh;
+    ray_source src = { NULL, table };
+    render_pixel(&rc, &src, W, H, px, py, max_samples, NULL, per_sample_rgb, per_sample_state);
     return 0;
 }

@@ -105,6 +105,18 @@ int orc_render(const orc_scene* s, const orc_camera* cam, const orc_env* env, in
                float* out_rgb, uint32_t* out_rgba8, orc_counters* counters);
 
 /*
+ * Render a ray image: orc_render with another ray generator, everything else - seed, sum, the 1.0f / max_samples scale, the row flip,
+ * make_rgba, the pixel list, threading, counters - unchanged.  table: W*H*16 floats laid out as pt_ray_gen (include/mi355pt.h), the
+ * record of pixel (x, y) at 16*(x + W*y): org at floats 0-2, dir, du, dv from floats 4, 8 and 12; floats 3, 7, 11, 15 are never read.
+ * Per sample rx = rng_next, then ry = rng_next (both always drawn), and the path starts at org along
+ * normalize((dir + du*rx) + dv*ry).
+ */
+int orc_render_rays(const orc_scene* s, const float* table, const orc_env* env, int W, int H,
+                    int max_samples, int max_depth, int use_bvh, int n_threads,
+                    const uint32_t* pixel_list, int64_t n_pixels,
+                    float* out_rgb, uint32_t* out_rgba8, orc_counters* counters);
+
+/*
  * Continue pixels: for every listed launch id x + W*y (all W*H when pixel_list is NULL; ids are distinct) n_samples more iterations of
  * ray_gen's sample loop, from rng[id] and sum[3*id ..] - or from orc_rng_init(x, y) and 0 when `first` is set - under the scene's
  * present materials and triangle test.  rng (W*H u32) and sum (W*H*3 floats), both in launch order, are updated in place; pixels that
@@ -119,6 +131,9 @@ int orc_accumulate(const orc_scene* s, const orc_camera* cam, const orc_env* env
 /* Per-pixel trace for debugging parity: per-sample radiance (max_samples*3) and rng state after each sample. */
 int orc_trace_pixel(const orc_scene* s, const orc_camera* cam, const orc_env* env, int W, int H, int px, int py,
                     int max_samples, int max_depth, int use_bvh, float* per_sample_rgb, uint32_t* per_sample_state);
+/* The same for pixel (px, py) of a ray image (table as orc_render_rays'); -1 for a pixel outside the image. */
+int orc_trace_pixel_rays(const orc_scene* s, const float* table, const orc_env* env, int W, int H, int px, int py,
+                         int max_samples, int max_depth, int use_bvh, float* per_sample_rgb, uint32_t* per_sample_state);
 
 /* Per-bounce log of ONE sample of one pixel (32 floats per bounce: origin, direction, hit flag, t u v, triangle, material, rng state before
    sample_disney, local wo, f, pdf, local wi, lobe, throughput, rng state after, radiance, depth - layout at ORC_LOG_FLOATS in pt_oracle.c).
@@ -126,6 +141,9 @@ int orc_trace_pixel(const orc_scene* s, const orc_camera* cam, const orc_env* en
    parts ways.  Returns the number of rows written (<= max_rows). */
 int orc_trace_sample(const orc_scene* s, const orc_camera* cam, const orc_env* env, int W, int H, int px, int py, int sample, int max_depth,
                      int use_bvh, float* log, int max_rows);
+/* The same for a sample of pixel (px, py) of a ray image (table as orc_render_rays'); -1 for a pixel outside the image. */
+int orc_trace_sample_rays(const orc_scene* s, const float* table, const orc_env* env, int W, int H, int px, int py, int sample,
+                          int max_depth, int use_bvh, float* log, int max_rows);
 
 /* ---- unit hooks (vector tests) ---- */
 uint32_t orc_rng_init(uint32_t seed_u, uint32_t seed_v);        /* random.hpp:46-56 */

@@ -2,14 +2,24 @@
 ray image (pt_render_aov_rays).
 
 The scenes are those of tests/aov_common.py and tests/aov_follow_common.py: Cornell, the textured cube, mirror_wall (a mirror and a
-window pane in front of a textured wall) and tir (the camera inside a glass sphere).  Two kinds of table, both with zero jitter and
-both built the way tests/test_gpu_ray_image.py builds them - the tests choose org and a target L, never dir, which is fl(L - org):
+window pane in front of a textured wall) and tir (the camera inside a glass sphere).  Two kinds of table with zero jitter, both built
+the way tests/test_gpu_ray_image.py builds them - the tests choose org and a target L, never dir, which is fl(L - org):
 
   centres  the pixel-centre rays of the scene's camera at W x H (ray_image_ref.pixel_centre_targets);
   probes   24 x 16 unrelated rays: origins anywhere in the scene's box, a seeded twelve up to 5 extents outside (half of those look back
            at the scene), directions uniform on the sphere.
 
-A CASE is (scene, kind, W, H, n_samples, max_follow); roughness_max is the default 0.3."""
+and the two kinds of tests/ray_tables.py whose jitter differs from record to record, so that a pixel that took another record's du / dv,
+a stale record, the other draw or the terms in another order shows:
+
+  scrambled  org, dir, du and dv all per pixel, an eighth of the records without du, without dv and without both, NaN in the reserved floats;
+  equirect   a panorama from inside the scene, the jitter shrinking towards the poles.
+
+A CASE is (scene, kind, W, H, n_samples, max_follow); roughness_max is the default 0.3.  CASES are the zero-jitter ones.  JITTER_CASES
+are on mirror_wall and tir, where followed rays start from jittered ones (and one frame each on Cornell and the cube): the shapes 1 x 1,
+7 x 9 (under one wave, partial 8 x 8 blocks), 20 x 13, 130 x 3 (more blocks than rows), 3 x 130 and 64 x 48 (many waves); n_samples 1, 3
+and 16; max_follow 0 and 4 - not the full cross product, each value with each shape class (NK).  A 1 x 1 panorama has no jitter to
+speak of (du = 0, dv parallel to dir): no equirect case there."""
 import os
 import re
 
@@ -18,6 +28,7 @@ import numpy as np
 import aov_follow_common as FC
 import aov_rays_ref
 import ray_image_ref as RR
+import ray_tables as RT
 
 F32 = np.float32
 ROOT = FC.ROOT
@@ -26,6 +37,13 @@ PROBE_SIZE = (24, 16)
 ROUGHNESS_MAX = 0.3
 CASES = [(name, "centres", W, H, n, k) for name in SCENES for (W, H) in ((20, 13), (64, 48)) for n in (1, 3) for k in (0, 4)]
 CASES += [(name, "probes") + PROBE_SIZE + (n, k) for name in SCENES for n in (1, 3) for k in (0, 4)]
+JITTER_KINDS = ("scrambled", "equirect")
+JITTER_SHAPES = ((1, 1), (7, 9), (20, 13), (130, 3), (3, 130), (64, 48))
+NK = {(64, 48): ((1, 4), (3, 0)), (20, 13): ((1, 0), (3, 4), (16, 0), (16, 4))}
+NK_SMALL = ((1, 0), (3, 4), (16, 4))
+JITTER_CASES = [(name, kind, W, H, n, k) for name in ("mirror_wall", "tir") for kind in JITTER_KINDS for (W, H) in JITTER_SHAPES
+                if not (kind == "equirect" and W * H == 1) for (n, k) in NK.get((W, H), NK_SMALL)]
+JITTER_CASES += [(name, "scrambled", 20, 13, 3, 4) for name in ("cornell", "cube")]
 
 scene, upload, camera, bits, assert_same, params = FC.scene, FC.upload, FC.camera, FC.bits, FC.assert_same, FC.params
 _tables = {}
@@ -83,6 +101,8 @@ def rays_of(name, kind, W, H, make):
 
 
 def table(name, kind, W, H, make):
+    if kind in JITTER_KINDS:
+        return RT.table(kind, name, W, H)
     return fixed_table(*rays_of(name, kind, W, H, make))
 
 
@@ -96,6 +116,30 @@ def reference(orc, name, kind, W, H, n, max_follow, wt, want_samples=False):
         a.setflags(write=False)
         _ref[key] = (a, r)
     return _ref[key] if want_samples else _ref[key][0]
+
+
+def precondition(orc, name, kind, W, H, n, max_follow):
+    """The precondition of tests/ray_tables.py for a jittered case, in guide buffers: aov_rays_ref's buffers of the case's table differ, in
+    at least half (RT.CAP) of all pixels, from its buffers of the table with du / dv rolled by one record, with the jitter zeroed and
+    with du and dv exchanged - asserted, computed once per session; returns {variant: share}.  (A 1 x 1 table has no neighbour.)"""
+    key = ("pre", name, kind, W, H, n, max_follow)
+    if key not in _ref:
+        sc = scene(name)
+        S = orc.Scene(sc["flat"])
+        want = reference(orc, name, kind, W, H, n, max_follow, 0)
+        t = table(name, kind, W, H, orc.to_camera_data)
+        out = {}
+        for what, f in RT.VARIANTS:
+            if what == "neighbour" and W * H == 1:
+                continue
+            other = aov_rays_ref.aov(S, sc["flat"], sc["env"], f(t), W, H, n, max_follow, ROUGHNESS_MAX)
+            out[what] = float((bits(other) != bits(want)).any(-1).mean())
+        _ref[key] = out
+    out = _ref[key]
+    for what, share in out.items():
+        assert share >= RT.CAP, "%s %s %dx%d n=%d max_follow=%d: the guide buffers differ from the '%s' table's in %.1f %% of the pixels only (%r)" % (
+            name, kind, W, H, n, max_follow, what, 100 * share, out)
+    return out
 
 
 def camera_of(B, c12):

@@ -7,9 +7,14 @@
 * pt_debug_aov_rays_host == tests/aov_rays_ref.py, all 8 channels of every pixel, over the cases of tests/aov_rays_common.py: Cornell,
   the textured cube, mirror_wall and tir; the pixel-centre rays at 20 x 13 and 64 x 48 and 24 x 16 probe rays from inside and up to 5
   extents outside the scene; n_samples 1 and 3; max_follow 0 and 4.  And on the closed icosphere (tir) under Scene(..., watertight=True).
+  The same over JITTER_CASES: the scrambled and equirect tables of tests/ray_tables.py, whose jitter differs from record to record, at
+  1 x 1 to 64 x 48, n_samples 1, 3 and 16, under both triangle tests, each case first shown to meet the precondition of
+  tests/ray_tables.py in guide buffers (RC.precondition); a restatement with the neighbouring record's jitter, the draws swapped or dv added first is
+  told apart from the twin on them.
 * Consequence (a): a zero-jitter record is pt_debug_aov_follow_host's pixel under its degenerate camera, one call per listed ray.
 * Consequence (b): eight jittered 1 x 1 images at n_samples = 16 from the origin are pt_debug_aov_follow_host's under {0, dir, du, dv}.
-* Consequence (c): where a pixel's coverage at n = 1 says hit, its depth at max_follow = 0 is t of pt_debug_trace_rays_host on sample 0's ray.
+* Consequence (c): where a pixel's coverage at n = 1 says hit, its depth at max_follow = 0 is t of pt_debug_trace_rays_host on sample 0's
+  ray - on a pinhole table and on a scrambled one.
 * `make asm-aov-rays`: exactly the four instances, no scratch, at most 128 VGPRs, no static LDS - the stack and the parked words are
   the launch's dynamic (PT_LDS_STACK + PT_AOV_PARK) * 64 * 4 bytes, which tests/test_gpu_aov_rays.py reads back from pt_get_stats - and
   the other guide and render targets report what they reported before."""
@@ -24,6 +29,7 @@ import pytest
 import aov_rays_common as RC
 import aov_rays_ref
 import ray_image_ref as RR
+import ray_tables as RT
 import resource_report
 from owl_path_tracer_amd.pyhost import binding as B
 from owl_path_tracer_amd.pyhost import ray_image as RI
@@ -186,6 +192,54 @@ def test_host_twin_equals_the_restatement(orc, name, kind, W, H, n, k):
         assert (RC.bits(want) != RC.bits(first)).any(), what + ": the case must follow something"
 
 
+@pytest.mark.parametrize("name,kind,W,H,n,k", RC.JITTER_CASES, ids=lambda v: str(v))
+def test_host_twin_equals_the_restatement_on_jittered_tables(orc, name, kind, W, H, n, k):
+    what = "%s %s %dx%d n=%d max_follow=%d" % (name, kind, W, H, n, k)
+    want, smp = RC.reference(orc, name, kind, W, H, n, k, 0, want_samples=True)
+    assert np.isfinite(want).all()
+    table = RC.table(name, kind, W, H, B.to_camera_data)
+    assert table.dtype == B.RAY_GEN_DTYPE
+    shares = RC.precondition(orc, name, kind, W, H, n, k)  # the case can tell records apart, or it is no case
+    print(what + ": pixels that differ: " + ", ".join("%s %.1f %%" % (v, 100 * x) for v, x in shares.items()))
+    ctx = _host(name)
+    try:
+        got = ctx.aov_rays_host(table, W, H, RC.params(B, n, k, RC.ROUGHNESS_MAX))
+        RC.assert_same(got, want, what + ": host twin vs aov_rays_ref")
+        ctx.set_option("watertight", 1)
+        RC.assert_same(ctx.aov_rays_host(table, W, H, RC.params(B, n, k, RC.ROUGHNESS_MAX)), RC.reference(orc, name, kind, W, H, n, k, 1), what + ", watertight")
+    finally:
+        ctx.close()
+    if W * H > 1:
+        assert smp["hit0"].any(), what
+
+
+@pytest.mark.parametrize("name", ["mirror_wall", "tir"])
+def test_a_wrong_generator_differs_from_the_twin(name):
+    """At n_samples = 1 the guide buffers of a table under a generator of some form (RR.FORMS) are those of the zero-jitter table that holds
+    that form's sum of sample 0 (RR.one_sample_table): the right form gives the twin's buffers of the jittered table bit for bit, every
+    wrong form gives others - a kernel with that mistake would fail tests/test_gpu_aov_rays.py, which compares every pixel."""
+    import oracle as orc
+
+    W, H = 20, 13
+    t = RT.scrambled(name, W, H)
+    rx, ry = RR.draws(orc, W, H, 1)
+    prm = RC.params(B, 1, 4, RC.ROUGHNESS_MAX)
+    ctx = _host(name)
+    try:
+        want = ctx.aov_rays_host(t, W, H, prm)
+        shares = {}
+        for form in RR.FORMS:
+            got = ctx.aov_rays_host(RR.one_sample_table(t, rx[:, 0], ry[:, 0], form), W, H, prm)
+            shares[form] = float((RC.bits(got) != RC.bits(want)).any(-1).mean())
+    finally:
+        ctx.close()
+    print(name, shares)
+    assert shares["right"] == 0.0
+    for form in RR.FORMS:
+        if form != "right":
+            assert shares[form] > 0.0, "the form '%s' (%s) gives the twin's buffers" % (form, RR.FORMS[form])
+
+
 @pytest.mark.parametrize("kind,W,H", [("centres", 20, 13), ("probes",) + RC.PROBE_SIZE])
 def test_watertight_on_the_closed_icosphere(orc, kind, W, H):
     name, n, k = "tir", 3, 4
@@ -255,12 +309,7 @@ def test_consequence_b_one_pixel_images_are_the_camera_they_name(orc):
         ctx.close()
 
 
-@pytest.mark.parametrize("name", ["cornell", "mirror_wall"])
-def test_consequence_c_sample_0_is_the_first_camera_ray(orc, name):
-    """A jittered table (pinhole of the scene's camera): sample 0's ray is aov_rays_ref.table_rays' - the ray pt_render_rays starts the
-    pixel's first path on - and where coverage says hit, the first-hit depth is the ray query's t on it."""
-    W, H = 20, 13
-    table = RI.pinhole(RC.camera(RC.scene(name), W, H, B.to_camera_data), W, H)
+def _consequence_c(name, table, W, H):
     rays0 = aov_rays_ref.table_rays(table, W, H, 1, np.arange(W * H))[:, 0]
     ctx = _host(name)
     try:
@@ -273,6 +322,20 @@ def test_consequence_c_sample_0_is_the_first_camera_ray(orc, name):
     assert (covered == (hits["prim"] >= 0)).all()
     assert (got[covered, 7].view(U32) == hits["t"][covered].view(U32)).all()
     assert (got[~covered, 7] == 0).all()
+
+
+@pytest.mark.parametrize("name", ["cornell", "mirror_wall"])
+def test_consequence_c_sample_0_is_the_first_camera_ray(orc, name):
+    """A jittered table (pinhole of the scene's camera): sample 0's ray is aov_rays_ref.table_rays' - the ray pt_render_rays starts the
+    pixel's first path on - and where coverage says hit, the first-hit depth is the ray query's t on it."""
+    W, H = 20, 13
+    _consequence_c(name, RI.pinhole(RC.camera(RC.scene(name), W, H, B.to_camera_data), W, H), W, H)
+
+
+@pytest.mark.parametrize("name", ["cornell", "mirror_wall", "tir"])
+def test_consequence_c_on_a_scrambled_table(orc, name):
+    """The same where every record has its own origin, direction and jitter."""
+    _consequence_c(name, RT.scrambled(name, 20, 13), 20, 13)
 
 
 # ---- resource reports ---------------------------------------------------------------------------------------------------

@@ -2,9 +2,17 @@
 csrc/pt_aov_follow.h with PT_RAYGEN = 1).  Every comparison is bit for bit on all 8 channels of every pixel.
 
 The reference is the CPU twin pt_debug_aov_rays_host, which tests/test_aov_rays_host.py holds to the numpy restatement on these cases.
+The zero-jitter tables (centres, probes) cannot tell one record's jitter from another's; the jittered cases can, and there the GPU is
+held to the twin and to the restatement (tests/aov_rays_ref.py) itself.
 
 * GPU == twin over the cases of tests/aov_rays_common.py (four scenes, pixel-centre rays at 20 x 13 and 64 x 48 and 24 x 16 probe rays,
   n = 1 and 3, max_follow 0 and 4), blocking and device forms, "watertight" 0 and 1; pt_get_stats reads as after pt_render_aov.
+* GPU == twin == aov_rays_ref over JITTER_CASES: the scrambled and equirect tables of tests/ray_tables.py (every record its own origin,
+  direction and jitter, NaN in the reserved floats) on mirror_wall and tir, where followed rays start from jittered ones, at 1 x 1, 7 x 9,
+  20 x 13, 130 x 3, 3 x 130 and 64 x 48, n_samples 1, 3 and 16, max_follow 0 and 4, "watertight" 0 and 1 (the restatement under both),
+  blocking and device forms, each case first shown to meet the precondition of tests/ray_tables.py in guide buffers;
+  both slab forms on a scrambled table; consequence (c) on the device: where coverage at n_samples = 1 says hit, the depth is
+  pt_trace_closest's t on table_rays' sample-0 ray.
 * The device form on a caller's stream directly behind a pt_render_rays_device of the same table with no synchronize.
 * Both slab forms; a shard of world 3 with tile 8 at 20 x 13 (one rank gets a partial block column; pixels not owned are +0); the frame
   after pt_set_materials, pt_set_environment and pt_update_vertices; a 130 x 3 frame (more blocks than rows); 1 x 1 jittered images.
@@ -19,6 +27,7 @@ import numpy as np
 import pytest
 
 import aov_rays_common as RC
+import aov_rays_ref
 import async_common as AS
 import ray_image_ref as RR
 import refit_common as RF
@@ -107,6 +116,76 @@ def test_gpu_equals_the_twin(name, kind, W, H, n, k):
         ctx.synchronize()
         table.free()
         out.free()
+
+
+@pytest.mark.parametrize("name,kind,W,H,n,k", RC.JITTER_CASES, ids=lambda v: str(v))
+def test_gpu_equals_the_twin_and_the_restatement_on_jittered_tables(orc, name, kind, W, H, n, k):
+    ctx = gpu(name)
+    rays = RC.table(name, kind, W, H, B.to_camera_data)
+    prm = RC.params(B, n, k, RC.ROUGHNESS_MAX)
+    RC.precondition(orc, name, kind, W, H, n, k)  # asserted: the case can tell records apart
+    table, out = device_table(rays, W, H), AS.DeviceFrame(W, H, floats=8)
+    try:
+        for wt in (0, 1):
+            what = "%s %s %dx%d n=%d max_follow=%d wt=%d" % (name, kind, W, H, n, k, wt)
+            want = twin(name, kind, W, H, n, k, wt)
+            ctx.set_option("watertight", wt)
+            try:
+                got = ctx.render_aov_rays(rays, W, H, prm)
+                check_stats(ctx.stats(), W, H)
+                ctx.render_aov_rays_device(table.rgb, W, H, out.rgb, prm)
+                ctx.synchronize()
+                check_stats(ctx.stats(), W, H)
+            finally:
+                ctx.set_option("watertight", 0)
+            dev = out.read()[0]
+            RC.assert_same(got, want, what + ": blocking form vs twin")
+            RC.assert_same(dev, want, what + ": device form vs twin")
+            RC.assert_same(got, RC.reference(orc, name, kind, W, H, n, k, wt), what + ": blocking form vs aov_rays_ref")
+    finally:
+        ctx.synchronize()
+        table.free()
+        out.free()
+
+
+def test_both_slab_forms_on_a_scrambled_table():
+    name, kind, W, H, n, k = "mirror_wall", "scrambled", 20, 13, 3, 4
+    ctx = gpu(name)
+    rays = RC.table(name, kind, W, H, B.to_camera_data)
+    prm = RC.params(B, n, k, RC.ROUGHNESS_MAX)
+    table, out = device_table(rays, W, H), AS.DeviceFrame(W, H, floats=8)
+    try:
+        for be in (0, 1):
+            for wt in (0, 1):
+                ctx.set_option("box_exact", be)
+                ctx.set_option("watertight", wt)
+                RC.assert_same(ctx.render_aov_rays(rays, W, H, prm), twin(name, kind, W, H, n, k, wt), "box_exact = %d, watertight = %d, blocking" % (be, wt))
+                ctx.render_aov_rays_device(table.rgb, W, H, out.rgb, prm)
+                ctx.synchronize()
+                RC.assert_same(out.read()[0], twin(name, kind, W, H, n, k, wt), "box_exact = %d, watertight = %d, device" % (be, wt))
+    finally:
+        for key, v in (("watertight", 0), ("box_exact", -1)):
+            ctx.set_option(key, v)
+        table.free()
+        out.free()
+
+
+@pytest.mark.parametrize("name", ["cornell", "mirror_wall", "tir"])
+def test_consequence_c_on_a_scrambled_table(name):
+    """Where coverage at n_samples = 1 says hit, the first-hit depth is pt_trace_closest's t on the ray aov_rays_ref.table_rays gives
+    sample 0 of the pixel - the ray query knows nothing of tables, so a pixel that read another record or the other draw shows here
+    without any twin."""
+    W, H = 20, 13
+    ctx = gpu(name)
+    t = RC.table(name, "scrambled", W, H, B.to_camera_data)
+    rays0 = aov_rays_ref.table_rays(t, W, H, 1, np.arange(W * H))[:, 0]
+    got = RI.to_list(ctx.render_aov_rays(t, W, H, B.aov_default_params(n_samples=1, max_follow=0)), W, H)
+    hits = ctx.trace_closest(rays0)
+    covered = got[:, 3] == 1
+    assert covered.sum() > W * H // 4 and ((got[:, 3] == 0) | covered).all()
+    assert (covered == (hits["prim"] >= 0)).all()
+    assert (got[covered, 7].view(U32) == hits["t"][covered].view(U32)).all()
+    assert (got[~covered, 7] == 0).all()
 
 
 def test_device_form_right_behind_a_render_rays_device():

@@ -1,7 +1,10 @@
 """pt_render_rays on the GPU (include/mi355pt.h "ray images"): the ray-image instances of the wavefront kernel against the oracle.
 
-Every comparison is bit for bit on out_rgb and out_rgba8 except leg D.  The oracle side is tests/ray_image_ref.py: a ray with zero jitter
-is the degenerate camera {org, L, 0, 0} with dir = fl(L - org), one Scene.render per ray; the tests choose org and L, never dir.
+Every comparison is bit for bit on out_rgb and out_rgba8 except leg D.  The oracle side is tests/ray_image_ref.py.  Legs A, B, C, E and F
+go through the degenerate camera: a ray with zero jitter is the camera {org, L, 0, 0} with dir = fl(L - org), one Scene.render per ray;
+the tests choose org and L, never dir.  Legs D2, G, H and I go through the oracle's own ray-image generator, Scene.render_rays, which
+tests/test_ray_image_host.py anchors to that camera and to a numpy restatement of the first ray: a jittered frame of any size has an
+exact reference.
 
 A. Pinhole through fixed rays: the pixel-centre rays of the scene's camera on Cornell, the textured cube under the automatic environment
    and the glass and metal icospheres under an environment map; 20 x 13 (partial 8 x 8 blocks, more than one wave) and 64 x 48, 4 and
@@ -13,10 +16,22 @@ C. Jitter: eight 1 x 1 images at 64 spp from inside a translated Cornell box, or
 D. Jitter over a frame (NOT exact): pinhole(cam, 64, 48) at 256 spp against pt_render(cam) under the metrics and the stated bars of
    tools/tolerance_calibration.py.  The record's three vectors are rounded once each, so a sample's direction differs from the camera's
    by an ulp or so before normalize: same streams, ulp-level arithmetic differences - what the bars were calibrated for.
+D2. Its exact twin: pinhole(cam, 64, 48) at 64 spp against Scene.render_rays of that same table.
 E. Paths through the host code: blocking and device forms, a caller's stream, right behind a pt_render_device, with and without a cost
    pre-pass, ring and tier schedules, the group walk forced on and off, both slab forms, "count", a shard of world 3, and the frame
    after pt_set_materials and after pt_update_vertices.
 F. Nothing else moves: pt_render around a pt_render_rays, an accumulation around one, and the spill-test build (kernel_variant 3).
+G. Tables that tell records apart (tests/ray_tables.py): the scrambled table - org, dir, du, dv all per pixel, NaN in the reserved
+   floats - and an equirectangular panorama from inside the scene, on Cornell, the cube and ico_map, at 1 x 1, 7 x 9 (under one wave,
+   partial blocks), 20 x 13, 64 x 48 (many waves), 130 x 3 (more blocks than rows) and 3 x 130, at 4 spp (no cost pre-pass) and 64 spp
+   (pre-pass, sort, tiers), depth 8.  Each case first asserts the precondition on the oracle's frames: the frame differs in at least half
+   of its pixels from the frame with the neighbouring record's du / dv, with the jitter zeroed, and with du and dv exchanged - a kernel
+   that read another record, a stale one, or swapped the draws cannot pass.
+H. Hand-offs: one scrambled 20 x 13 frame at 64 spp under every schedule and walk option that moves samples between slots, chunks and
+   launches; the blocking and the device form on the context's and a caller's stream and right behind a pt_render_device; a shard of
+   world 3 (owned pixels exact, the others +0, the union the frame); "count" = 1, whose counters are the oracle's.
+I. Random scenes: the generator of tests/test_gpu_fuzz.py, each scene under a scrambled table with origins inside its box, frames up to
+   40 x 30, 4 to 32 spp, depth 1 to 8; every seed compared, until 32 of the compared frames meet the precondition of leg G.
 And the one refusal that needs a device: a context with a communicator."""
 import ctypes as C
 import os
@@ -29,6 +44,7 @@ import pytest
 import aov_common as AC
 import async_common as AS
 import ray_image_ref as RR
+import ray_tables as RT
 import refit_common as RC
 from owl_path_tracer_amd.pyhost import binding as B
 from owl_path_tracer_amd.pyhost import ray_image as RI
@@ -194,6 +210,19 @@ def test_d_jitter_over_a_frame_within_the_stated_bars():
     assert m["l2_p99"] <= 1e-4
     assert m["l2_p999"] <= 0.04
     assert m["rel_rmse"] <= 1e-2
+
+
+def test_d2_jitter_over_a_frame_exactly(orc):
+    """Leg D's table at 64 spp, every pixel bit for bit against the oracle's frame of that same table."""
+    W, H, spp = 64, 48, 64
+    ctx = gpu("cornell")
+    t = RI.pinhole(AC.camera(AC.scene("cornell"), W, H, B.to_camera_data), W, H)
+    S, env = oracle_scene(orc, "cornell")
+    want = S.render_rays(t, env, W, H, spp, DEPTH, want_rgba8=True)[:2]
+    assert np.isfinite(want[0]).all() and want[0].std() > 0.01
+    got = ctx.render_rays(t, W, H, spp, DEPTH, want_rgba8=True)
+    assert ctx.stats()["prepass_spp"] > 0
+    assert_frame(got, want, "pinhole table, cornell %dx%d %d spp" % (W, H, spp))
 
 
 # ---- E ------------------------------------------------------------------------------------------------------------------
@@ -399,6 +428,197 @@ print("RAY_IMAGE_FALLBACK_OK", st["vgprs"])
 """ % dict(root=AC.ROOT, tmp=str(tmp_path), W=W, H=H, spp=spp, depth=DEPTH)
     r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, PT_LIB_PATH=lib), capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and "RAY_IMAGE_FALLBACK_OK" in r.stdout, r.stdout + r.stderr
+
+# ---- G ------------------------------------------------------------------------------------------------------------------
+G_SIZES = ((1, 1), (7, 9), (20, 13), (64, 48), (130, 3), (3, 130))
+
+
+def jitter_case(orc, kind, name, W, H, spp, depth=DEPTH, counters=False):
+    """(table, the oracle's frame (rgb, rgba8[, counters])) of a table of tests/ray_tables.py, computed once, the precondition asserted on
+    the frame that is handed out, read-only."""
+    key = ("jit", kind, name, W, H, spp, depth)
+    if key not in _ref:
+        S, env = oracle_scene(orc, name)
+        t = RT.table(kind, name, W, H)
+        want = S.render_rays(t, env, W, H, spp, depth, want_rgba8=True, want_counters=True)
+        assert np.isfinite(want[0]).all()
+        shares = RT.precondition(S, env, t, W, H, spp, depth, want=want[0])
+        print("%s %s %dx%d %d spp: differing pixels %s" % (kind, name, W, H, spp, ", ".join("%s %.1f %%" % (k, 100 * v) for k, v in shares.items())))
+        for a in want[:2]:
+            a.setflags(write=False)
+        _ref[key] = (t, want)
+    t, want = _ref[key]
+    return t, (want if counters else want[:2])
+
+
+# (a 1 x 1 panorama has du = 0 and dv parallel to dir - no jitter to speak of, tests/ray_tables.py: no equirect case there)
+G_CASES = [(name, kind, W, H, spp) for name in SCENES for kind in ("scrambled", "equirect") for (W, H) in G_SIZES if not (kind == "equirect" and W * H == 1)
+           for spp in (4, 64)]
+
+
+@pytest.mark.parametrize("name,kind,W,H,spp", G_CASES, ids=["%s-%s-%dx%d-%d" % c for c in G_CASES])
+def test_g_tables_that_tell_records_apart(orc, name, kind, W, H, spp):
+    t, want = jitter_case(orc, kind, name, W, H, spp)
+    ctx = gpu(name)
+    got = ctx.render_rays(t, W, H, spp, DEPTH, want_rgba8=True)
+    assert (ctx.stats()["prepass_spp"] > 0) == (spp == 64)
+    assert_frame(got, want, "%s table, %s %dx%d %d spp" % (kind, name, W, H, spp))
+
+
+# ---- H ------------------------------------------------------------------------------------------------------------------
+HW, HH, HSPP = 20, 13, 64
+HANDOFFS = [("spp_per_launch", 8, 0), ("spp_per_launch", 16, 0), ("chunk_spp", 8, 64), ("whole", 0, -1), ("whole", 1, -1), ("groups", 0, 1), ("groups", 2, 1),
+            ("box_exact", 0, -1), ("box_exact", 1, -1), ("fallback", 1, 0), ("slots_per_wave", 64, 0)]
+
+
+@pytest.mark.parametrize("key,value,default", HANDOFFS, ids=["%s=%d" % o[:2] for o in HANDOFFS])
+def test_h_handoffs_on_a_scrambled_table(orc, key, value, default):
+    t, want = jitter_case(orc, "scrambled", "cornell", HW, HH, HSPP)
+    ctx = gpu("cornell")
+    ctx.set_option(key, value)
+    try:
+        got = ctx.render_rays(t, HW, HH, HSPP, DEPTH, want_rgba8=True)
+        st = ctx.stats()
+    finally:
+        ctx.set_option(key, default)
+    assert_frame(got, want, "scrambled table, %s = %d" % (key, value))
+    if key == "spp_per_launch":
+        assert st["prepass_spp"] == 0  # (the unsorted schedule: chunks of `value` samples)
+    if key == "whole":
+        assert (st["whole_pixels"] == HW * HH) == (value == 1)
+    if key == "fallback":
+        assert st["kernel_variant"] == 3
+    assert_frame(ctx.render_rays(t, HW, HH, HSPP, DEPTH, want_rgba8=True), want, "the default again after %s = %d" % (key, value))
+
+
+def test_h_blocking_and_device_forms_and_streams(orc):
+    t, want = jitter_case(orc, "scrambled", "cornell", HW, HH, HSPP)
+    _, want4 = jitter_case(orc, "scrambled", "cornell", HW, HH, 4)
+    ctx = gpu("cornell")
+    assert_frame(ctx.render_rays(t, HW, HH, HSPP, DEPTH, want_rgba8=True), want, "blocking form")
+    W2, H2 = 29, 31
+    cam2 = AC.camera(AC.scene("cornell"), W2, H2, B.to_camera_data)
+    front = ctx.render(cam2, W2, H2, 8, 7, want_rgba8=True)
+    table = AS.DeviceFrame(HW, HH, floats=16)
+    AS.to_device(table.rgb, t)
+    out, out2 = AS.DeviceFrame(HW, HH), AS.DeviceFrame(W2, H2)
+    try:
+        ctx.render_rays_device(table.rgb, HW, HH, HSPP, DEPTH, out.rgb, out.rgba8)
+        ctx.synchronize()
+        assert_frame(out.read(), want, "device form, the context's stream")
+        s0, s1 = AS.stream(0), AS.stream(1)
+        ctx.render_rays_device(table.rgb, HW, HH, 4, DEPTH, out.rgb, out.rgba8, stream=s0)
+        ctx.synchronize()
+        assert_frame(out.read(), want4, "device form, a caller's stream, 4 spp")
+        ctx.render_rays_device(table.rgb, HW, HH, HSPP, DEPTH, out.rgb, out.rgba8, stream=s0)
+        ctx.synchronize()
+        assert_frame(out.read(), want, "device form, a caller's stream")
+        ctx.render_device(cam2, W2, H2, 8, 7, out2.rgb, out2.rgba8, stream=s1)
+        ctx.render_rays_device(table.rgb, HW, HH, HSPP, DEPTH, out.rgb, out.rgba8, stream=s0)  # no synchronize between the two
+        ctx.synchronize()
+        assert_frame(out2.read(), front, "pt_render_device in front of a pt_render_rays_device")
+        assert_frame(out.read(), want, "pt_render_rays_device right behind a pt_render_device")
+    finally:
+        ctx.synchronize()
+        for b in (table, out, out2):
+            b.free()
+
+
+def test_h_shard_of_world_3(orc):
+    t, want = jitter_case(orc, "scrambled", "cornell", HW, HH, HSPP)
+    ctx = gpu("cornell")
+    covered = np.zeros((HH, HW), bool)
+    union = np.zeros((HH, HW, 3), F32)
+    union8 = np.zeros((HH, HW), U32)
+    try:
+        for rank in (0, 1, 2):
+            own = np.zeros(HW * HH, bool)
+            own[B.shard_pixels(HW, HH, 8, rank, 3)] = True
+            own = own.reshape(HH, HW)[::-1]  # launch order -> framebuffer order
+            assert own.any() and not (own & covered).any()
+            covered |= own
+            ctx.set_pixel_shard(rank, 3, 8)
+            rgb, rgba = ctx.render_rays(t, HW, HH, HSPP, DEPTH, want_rgba8=True)
+            assert (rgb[own].view(U32) == want[0][own].view(U32)).all() and (rgba[own] == want[1][own]).all(), "rank %d: its pixels" % rank
+            assert (np.ascontiguousarray(rgb[~own]).view(U32) == 0).all() and (rgba[~own] == 0).all(), "rank %d: +0 outside the shard" % rank
+            union[own], union8[own] = rgb[own], rgba[own]
+    finally:
+        ctx.set_pixel_shard(0, 1, 16)
+    assert covered.all()
+    assert_frame((union, union8), want, "the union over the ranks")
+    assert_frame(ctx.render_rays(t, HW, HH, HSPP, DEPTH, want_rgba8=True), want, "the unsharded frame afterwards")
+
+
+@pytest.mark.parametrize("spp", (4, HSPP))
+def test_h_counters_are_the_oracles(orc, spp):
+    t, want = jitter_case(orc, "scrambled", "cornell", HW, HH, spp, counters=True)
+    ctx = gpu("cornell")
+    ctx.set_option("count", 1)
+    try:
+        got = ctx.render_rays(t, HW, HH, spp, DEPTH, want_rgba8=True)
+        st = ctx.stats()
+    finally:
+        ctx.set_option("count", 0)
+    assert_frame(got, want[:2], "the instrumented instance, %d spp" % spp)
+    for k in ("samples", "rays", "scatters", "env_misses", "nan_retries"):
+        assert st[k] == want[2][k], (k, st[k], want[2][k])
+    assert st["samples"] == HW * HH * spp and st["rays"] > st["samples"]
+
+
+# ---- I ------------------------------------------------------------------------------------------------------------------
+I_TELLING = 32  # cases whose frame tells the records apart (RT.CAP under all three wrong tables) the leg runs until it has compared
+I_MOST = 96  # seeds at the most
+I_SEED0 = 20261020
+
+
+def random_case(seed):
+    """A scene of tests/test_gpu_fuzz.py's generator (its own seed sequence, untouched) with a frame size, sample count, depth and a
+    scrambled table of this test's: origins inside the scene's box, so every ray starts within one extent of the scene, inside the
+    closest-hit domain of 10 extents."""
+    import test_gpu_fuzz as FZ
+
+    c = FZ.draw_case(seed)
+    rng = np.random.default_rng([seed, 1])
+    W, H = int(rng.integers(1, 41)), int(rng.integers(1, 31))
+    spp = int(rng.choice([4, 7, 16, 32]))
+    depth = int(rng.choice([1, 2, 4, 8]))
+    P = np.concatenate([m["vertices"] for m, _ in c["ents"]]).astype(np.float64)
+    t = RT.scrambled_in_box(P.min(0), P.max(0), W, H, [seed, 2])
+    return c, t, W, H, spp, depth
+
+
+def test_i_random_scenes(orc, scene_io):
+    """Every seed from I_SEED0 on is compared bit for bit, none is left out.  A random scene may hide the jitter - a constant environment
+    seen directly, a dark scene, one pixel - so the leg goes on until I_TELLING of the frames it compared meet the precondition of
+    tests/ray_tables.py on the oracle's frames (at least half of the pixels differ under the neighbouring record's, the zeroed and the
+    exchanged jitter): that many frames a kernel reading the wrong record could not have passed.  About every second seed is one."""
+    ctx = B.Context(0)
+    telling, used, pixels, differing = 0, 0, 0, {k: 0 for k, _ in RT.VARIANTS}
+    try:
+        while telling < I_TELLING:
+            assert used < I_MOST, "only %d of %d random frames tell records apart" % (telling, used)
+            seed = I_SEED0 + used
+            used += 1
+            c, t, W, H, spp, depth = random_case(seed)
+            ctx.upload_scene(c["ents"], c["mats"], textures=c["texs"], mesh_textures=c["mesh_tex"], env=B.make_env(**c["env"]))
+            got, got8 = ctx.render_rays(t, W, H, spp, depth, want_rgba8=True)
+            S = orc.Scene(scene_io.flatten_scene(c["ents"], [("m%d" % i, m, "") for i, m in enumerate(c["mats"])], c["tex_by_mat"]))
+            env = orc.make_env(**c["env"])
+            want, want8, _ = S.render_rays(t, env, W, H, spp, depth, want_rgba8=True)
+            what = "random scene seed=%d (%dx%d, %d spp, depth %d, %d triangles)" % (seed, W, H, spp, depth, sum(len(m["indices"]) for m, _ in c["ents"]))
+            same = (got.view(U32) == want.view(U32)) | (np.isnan(got) & np.isnan(want))
+            assert same.all(), "%s: %d of %d pixels differ; first (row, column) %s: got %r, want %r" % (
+                what, int((~same).any(-1).sum()), W * H, tuple(np.argwhere(~same.all(-1))[0]), got[tuple(np.argwhere(~same.all(-1))[0])], want[tuple(np.argwhere(~same.all(-1))[0])])
+            assert (got8 == want8).all(), what + ": RGBA8 differs"
+            shares = {k: RT.differing_share(want, S.render_rays(f(t), env, W, H, spp, depth)[0]) for k, f in RT.VARIANTS if not (k == "neighbour" and W * H == 1)}
+            telling += int(min(shares.values()) >= RT.CAP)
+            pixels += W * H
+            for k, v in shares.items():
+                differing[k] += v * W * H
+    finally:
+        ctx.close()
+    print("random scenes: %d compared, %d of them tell records apart; of all %d pixels %s differ" % (
+        used, telling, pixels, ", ".join("%.1f %% under '%s'" % (100 * v / pixels, k) for k, v in differing.items())))
 
 
 def test_communicator_is_refused_by_name(orc):

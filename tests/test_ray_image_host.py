@@ -7,6 +7,12 @@
 * pyhost/ray_image.py: pinhole against gen_camera_ray's formula in float64, equirect against its formula, fixed and to_list.
 * tests/ray_image_ref.py itself: through a degenerate camera the oracle's pixel depends on the pixel's stream on a diffuse wall and not on
   sky, and the 1 x 1 form is the camera it names.
+* The oracle's ray-image generator (Scene.render_rays), anchored before the GPU tests hold anything to it: with zero jitter it is the
+  degenerate camera bit for bit (frame, RGBA8, counters; 1 and many threads; a pixel list); eight jittered 1 x 1 records are the camera
+  they name; on a table with per-pixel jitter the first ray of samples 0 to 7 of every pixel is the numpy restatement's; the
+  reserved floats are not read; a restatement that takes the neighbouring record's du / dv, swaps rx and ry or adds dv before du is told
+  apart, ray by ray and as a 1 spp frame; and the tables of tests/ray_tables.py meet their precondition at every size and sample count
+  the GPU tests use.
 * `make asm-rayimage`: exactly the five instances, no scratch, the 4-wave instances within 128 VGPRs."""
 import ctypes as C
 import re
@@ -15,7 +21,9 @@ import numpy as np
 import pytest
 
 import aov_common as AC
+import aov_rays_ref
 import ray_image_ref as RR
+import ray_tables as RT
 import resource_report
 from owl_path_tracer_amd.pyhost import binding as B
 from owl_path_tracer_amd.pyhost import ray_image as RI
@@ -265,3 +273,237 @@ def test_ray_image_kernel_resources():
         assert int(scratch) == 0 and int(vgprs) > 0, (nm, vgprs, scratch)
         if "Li4E" in nm:
             assert int(vgprs) <= 128, (nm, vgprs)
+
+
+# ---- the oracle's ray-image generator -----------------------------------------------------------------------------------------
+ANCHOR_SCENES = ("cornell", "cube", "ico_map")
+AW, AH, ASPP, ADEPTH = 20, 13, 4, 8
+_oracle = {}
+
+
+def _oracle_scene(orc, name):
+    if name not in _oracle:
+        sc = AC.scene(name)
+        _oracle[name] = (orc.Scene(sc["flat"]), orc.make_env(**sc["env"]))
+    return _oracle[name]
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, F32).view(np.uint32)
+
+
+@pytest.mark.parametrize("name", ANCHOR_SCENES)
+def test_zero_jitter_is_the_degenerate_camera(orc, name):
+    """Origins and directions of the scrambled table (every pixel its own), the jitter zero: dir = fl(L - org) with L = fl(org + dir)."""
+    S, env = _oracle_scene(orc, name)
+    t = RT.scrambled(name, AW, AH)
+    orgs = t["org"].copy()
+    targets = (orgs.astype(np.float64) + t["dir"].astype(np.float64)).astype(F32)
+    _, dirs = RR.rays_through(orgs, targets)
+    table = RI.fixed(orgs, dirs, AW, AH)
+    assert (table["dir"] == dirs).all() and (table["org"] == orgs).all()
+    cnt = {}
+    want, want8 = RR.oracle_pixels(orc, S, env, orgs, targets, AW, AH, ASPP, ADEPTH, counters=cnt)
+    assert len({p.tobytes() for p in want.reshape(-1, 3)}) > AW * AH // 3 and cnt["samples"] == AW * AH * ASPP
+    for threads in (1, 7):
+        rgb, rgba, c = S.render_rays(table, env, AW, AH, ASPP, ADEPTH, threads=threads, want_rgba8=True, want_counters=True)
+        assert (_bits(rgb) == _bits(want)).all() and (rgba == want8).all(), threads
+        assert c == cnt, (threads, c, cnt)
+    # the same records as W * H * 16 plain floats
+    flat = np.ascontiguousarray(table).view(F32).copy()
+    assert (_bits(S.render_rays(flat, env, AW, AH, ASPP, ADEPTH)[0]) == _bits(want)).all()
+    ids = [0, 3, AW + 2, AW * AH - 1, 7 * AW + 19]
+    part, part8, c = S.render_rays(table, env, AW, AH, ASPP, ADEPTH, pixel_list=ids, want_rgba8=True, want_counters=True)
+    wp, wp8 = RR.oracle_pixels(orc, S, env, orgs, targets, AW, AH, ASPP, ADEPTH, ids=ids)
+    assert (_bits(part) == _bits(wp)).all() and (part8 == wp8).all() and c["samples"] == len(ids) * ASPP
+    assert (part.reshape(-1, 3).max(1) != 0).sum() <= len(ids)
+    with pytest.raises(ValueError):
+        S.render_rays(table, env, AW, AH, ASPP, ADEPTH, pixel_list=[AW * AH])
+    with pytest.raises(ValueError):
+        S.render_rays(table[:-1], env, AW, AH, ASPP, ADEPTH)
+
+
+@pytest.mark.parametrize("name", ("cornell", "cube"))
+def test_jittered_one_pixel_records_are_the_camera_they_name(orc, name):
+    import aov_rays_common as ARC
+
+    S, env = _oracle_scene(orc, name)
+    seen = set()
+    for t in ARC.jitter_records(RT.DTYPE):
+        rgb, rgba, c = S.render_rays(t, env, 1, 1, 64, ADEPTH, want_rgba8=True, want_counters=True)
+        want, want8 = RR.oracle_jitter_1x1(orc, S, env, t["dir"][0], t["du"][0], t["dv"][0], 64, ADEPTH)
+        assert (_bits(rgb[0, 0]) == _bits(want)).all() and rgba[0, 0] == want8 and c["samples"] == 64
+        seen.add(want.tobytes())
+    assert len(seen) >= 2  # (from the origin some of the eight see the environment alone)
+
+
+FIRST_RAY_SAMPLES = 8
+
+
+def _far_scene(orc):
+    """One triangle far outside every table: every sample of every pixel misses, so no path draws from the stream."""
+    far = dict(positions=F32([[[1e6, 1e6, 1e6], [1e6 + 1, 1e6, 1e6], [1e6, 1e6 + 1, 1e6]]]), normals=F32([[[0, 0, 1]] * 3]), texcoords=None,
+               material_index=np.zeros(1, np.int32), texture_index=np.full(1, -1, np.int32), materials=orc.MAT_DEFAULT[None, :], textures=[])
+    return orc.Scene(far), orc.make_env(color=(1, 1, 1), intensity=1.0), RT.scrambled_in_box((-1, -2, -3), (3, 2, 1), AW, AH, 77)
+
+
+def _first_rays(orc, S, env, t, W, H, ns, depth):
+    """What the oracle says of the first ns samples of every pixel at `depth`: rays (W * H, ns, 6) = row 0 of each sample's per-bounce log,
+    hit (W * H, ns) = its hit flag, rx, ry (W * H, ns) = the two draws from the state the stream was in when the sample began -
+    rng_init(x, y) for sample 0, the state trace_pixel_rays reports after sample k - 1 for sample k."""
+    n = W * H
+    rays, hit = np.zeros((n, ns, 6), F32), np.zeros((n, ns), bool)
+    rx, ry = np.zeros((n, ns), F32), np.zeros((n, ns), F32)
+    for i in range(n):
+        x, y = i % W, i // W
+        rgb, after = S.trace_pixel_rays(t, env, W, H, x, y, ns, depth)
+        begin = [orc.rng_init(x, y)] + [int(v) for v in after[:-1]]
+        for k in range(ns):
+            log = S.trace_sample_rays(t, env, W, H, x, y, k, depth)
+            assert 1 <= log.shape[0] and log[0, 31] == 0
+            rays[i, k], hit[i, k] = log[0, :6], log[0, 6] != 0
+            rx[i, k], st = orc.rng_next(begin[k])
+            ry[i, k], st = orc.rng_next(st)
+    return rays, hit, rx, ry
+
+
+@pytest.mark.parametrize("what", ("far", "ico_map", "cornell"))
+def test_first_ray_is_the_numpy_restatement_and_no_wrong_form_is(orc, what):
+    """Row 0 of the per-bounce log (the ray a sample starts on) of EVERY pixel of a scrambled 20 x 13 table, samples 0 to 7 (the issue's
+    0, 1 and 7 among them), depth 8, against the numpy restatement: the two draws from the state the stream is in when the sample
+    begins, RR.first_sums in float32 and aov_rays_ref.normalize3 - bit for bit.  A path draws from the pixel's stream at every hit, so
+    sample k > 0 begins where sample k - 1 ended (Scene.trace_pixel_rays, behind the one trace_path that tests/test_oracle_vs_reference.py
+    holds to the reference), not at draw 2k.  aov_rays_ref.table_rays, the restatement the guide pass is held to, does put sample k at
+    draws 2k and 2k + 1: it is compared on sample 0 of every pixel, on the later samples of the pixels whose earlier samples all missed,
+    and on everything in the scene where every sample misses ("far").  Then the mistakes a generator could make (RR.FORMS): each differs
+    from the oracle."""
+    n, ns = AW * AH, FIRST_RAY_SAMPLES
+    S, env, t = _far_scene(orc) if what == "far" else _oracle_scene(orc, what) + (RT.scrambled(what, AW, AH),)
+    rays, hit, rx, ry = _first_rays(orc, S, env, t, AW, AH, ns, ADEPTH)
+    assert (_bits(rays[..., :3]) == _bits(t["org"])[:, None, :]).all()
+    jittered = t["du"].any(1) | t["dv"].any(1)
+    both = t["du"].any(1) & t["dv"].any(1)
+    assert len({r.tobytes() for r in t["du"][both]}) == both.sum() > n // 2 and (rx != ry).all()
+    for form in RR.FORMS:
+        differ = np.zeros((n, ns), bool)
+        for k in range(ns):
+            with np.errstate(invalid="ignore", divide="ignore"):
+                d = aov_rays_ref.normalize3(RR.first_sums(t, rx[:, k], ry[:, k], form))
+            differ[:, k] = (_bits(d) != _bits(rays[:, k, 3:])).any(1)
+        print("%s, form %-9s: %4d of %d directions differ from the oracle's" % (what, form, differ.sum(), differ.size))
+        if form == "right":
+            assert not differ.any()
+        elif form == "dv_first":  # the same terms in another order: a rounding apart where both are there, and nothing otherwise
+            assert not differ[~both].any() and differ[both].any()
+        else:  # another record's jitter, or the other draw: every jittered record shows it
+            assert differ[jittered].all()
+    # table_rays: where the stream is at draw 2k
+    want = aov_rays_ref.table_rays(t, AW, AH, ns, np.arange(n))
+    clean = np.concatenate([np.ones((n, 1), bool), np.cumsum(hit, 1)[:, :-1] == 0], 1)  # no sample in front drew from the stream
+    print("%s: samples at draw 2k per position 0..7: %s" % (what, clean.sum(0).tolist()))
+    if what == "far":
+        assert not hit.any() and clean.all()
+        d_rx, d_ry = RR.draws(orc, AW, AH, ns)
+        assert (d_rx == rx).all() and (d_ry == ry).all()
+    else:
+        assert clean[:, 0].all() and not clean[:, 1].all()
+    same = (_bits(rays) == _bits(want)).all(-1)
+    assert same[clean].all(), "%s: %d first rays differ from table_rays" % (what, int((~same[clean]).sum()))
+    with pytest.raises(RuntimeError):
+        S.trace_sample_rays(t, env, AW, AH, AW, 0, 0, 1)
+    with pytest.raises(RuntimeError):
+        S.trace_pixel_rays(t, env, AW, AH, 0, AH, 1, 1)
+
+
+@pytest.mark.parametrize("name", ANCHOR_SCENES)
+def test_a_wrong_generator_differs_from_the_oracle_as_a_frame(orc, name):
+    """At 1 spp the frame of a table under a generator of some form is the frame of the zero-jitter table that holds that form's sum of
+    sample 0 (RR.one_sample_table).  The right form gives Scene.render_rays of the jittered table bit for bit - the generator anchored
+    once more, at W, H > 1 with jitter, through the zero-jitter identity above - and every wrong form gives another frame: a kernel
+    with that mistake would fail the GPU legs, which compare every pixel."""
+    S, env = _oracle_scene(orc, name)
+    t = RT.scrambled(name, AW, AH)
+    rx, ry = RR.draws(orc, AW, AH, 1)
+    want = S.render_rays(t, env, AW, AH, 1, ADEPTH)[0]
+    shares = {}
+    for form in RR.FORMS:
+        got = S.render_rays(RR.one_sample_table(t, rx[:, 0], ry[:, 0], form), env, AW, AH, 1, ADEPTH)[0]
+        shares[form] = RT.differing_share(got, want)
+    print(name, shares)
+    assert shares["right"] == 0.0
+    for form in RR.FORMS:
+        if form != "right":
+            assert shares[form] > 0.0, "the form '%s' (%s) gives the oracle's frame" % (form, RR.FORMS[form])
+
+
+def test_reserved_floats_are_not_read(orc):
+    S, env = _oracle_scene(orc, "cornell")
+    t = RT.scrambled("cornell", AW, AH)
+    assert all(np.isnan(t["reserved%d" % k]).all() for k in range(4))
+    z = t.copy()
+    other = t.copy()
+    for k in range(4):
+        z["reserved%d" % k] = 0.0
+        other["reserved%d" % k] = F32(k + 1) * F32(1e30)
+    a = S.render_rays(t, env, AW, AH, ASPP, ADEPTH, want_rgba8=True, want_counters=True)
+    for b in (S.render_rays(z, env, AW, AH, ASPP, ADEPTH, want_rgba8=True, want_counters=True), S.render_rays(other, env, AW, AH, ASPP, ADEPTH, want_rgba8=True, want_counters=True)):
+        assert (_bits(a[0]) == _bits(b[0])).all() and (a[1] == b[1]).all() and a[2] == b[2]
+    assert np.isfinite(a[0]).all()
+    la, lz = S.trace_sample_rays(t, env, AW, AH, 5, 4, 2, ADEPTH), S.trace_sample_rays(z, env, AW, AH, 5, 4, 2, ADEPTH)
+    assert la.shape == lz.shape and (_bits(la) == _bits(lz)).all()
+
+
+def test_scrambled_table_is_what_it_says():
+    for name, W, H in (("cornell", 64, 48), ("ico_map", 64, 48), ("cube", 20, 13)):
+        t = RT.scrambled(name, W, H)
+        assert t.dtype == RT.DTYPE == B.RAY_GEN_DTYPE and t.shape == (W * H,) and not t.flags.writeable
+        assert RT.scrambled(name, W, H) is t and RT.scrambled_in_box((0, 0, 0), (1, 1, 1), 3, 2, 5).tobytes() == RT.scrambled_in_box((0, 0, 0), (1, 1, 1), 3, 2, 5).tobytes()
+        lo, hi = RT.box_of(AC.scene(name)["flat"])
+        u = (t["org"].astype(np.float64) - lo) / (hi - lo)
+        assert u.min() >= 0.1 - 1e-6 and u.max() <= 0.9 + 1e-6 and u.std(0).min() > 0.15
+        for c, r in RT.DARK.get(name, ()):
+            assert (np.linalg.norm(t["org"] - F32(c), axis=1) >= r - 1e-5).all()
+        ln = np.linalg.norm(t["dir"].astype(np.float64), axis=1)
+        assert ln.min() >= 0.5 - 1e-6 and ln.max() <= 2.0 + 1e-6
+        for f in ("du", "dv"):
+            r = np.linalg.norm(t[f].astype(np.float64), axis=1) / ln
+            zero = r == 0
+            assert 0.15 < zero.mean() < 0.35  # an eighth alone and an eighth with the other
+            assert r[~zero].min() >= 0.05 - 1e-6 and r[~zero].max() <= 0.5 + 1e-6
+        both = ~t["du"].any(1) & ~t["dv"].any(1)
+        assert 0.06 < both.mean() < 0.2
+        assert all(np.isnan(t["reserved%d" % k]).all() for k in range(4))
+        for f in ("org", "dir", "du", "dv"):
+            assert np.isfinite(t[f]).all()
+    for name, (c, r) in RT.ONLY.items():
+        t = RT.scrambled(name, 20, 13)
+        assert (np.linalg.norm(t["org"].astype(np.float64) - c, axis=1) < r).all() and t["org"].std(0).min() > 0.2 * r
+    one = RT.scrambled("cornell", 1, 1)
+    assert one["du"].any() and one["dv"].any()
+    # the three wrong tables
+    t = RT.scrambled("cube", 20, 13)
+    nb, z, ex = RT.neighbour(t), RT.zeroed(t), RT.exchanged(t)
+    assert (nb["du"][1:] == t["du"][:-1]).all() and (nb["dv"][0] == t["dv"][-1]).all() and (nb["dir"] == t["dir"]).all() and (nb["org"] == t["org"]).all()
+    assert not z["du"].any() and not z["dv"].any() and (z["dir"] == t["dir"]).all()
+    assert (ex["du"] == t["dv"]).all() and (ex["dv"] == t["du"]).all()
+    p = RI.pinhole(AC.camera(AC.scene("cornell"), 8, 6, B.to_camera_data), 8, 6)
+    assert RT.neighbour(p).tobytes() == p.tobytes(), "a pinhole table rolled is the same table: why it cannot tell records apart"
+    e = RT.equirect("cornell", 16, 8)
+    assert (np.linalg.norm(e["du"][:16], axis=1) < 0.5 * np.linalg.norm(e["du"][4 * 16:5 * 16], axis=1)).all(), "the jitter shrinks towards the poles"
+
+
+RAY_SIZES = ((1, 1), (7, 9), (20, 13), (64, 48), (130, 3), (3, 130))
+
+
+@pytest.mark.parametrize("kind", ("scrambled", "equirect"))
+@pytest.mark.parametrize("name", ANCHOR_SCENES)
+def test_tables_meet_their_precondition(orc, name, kind):
+    """With the oracle alone, at every (scene, table, size, spp) the GPU legs of tests/test_gpu_ray_image.py use (they assert it again on
+    the frames they compare): the figures in the docstring of tests/ray_tables.py."""
+    S, env = _oracle_scene(orc, name)
+    for W, H in RAY_SIZES:
+        if kind == "equirect" and W * H == 1:
+            continue
+        for spp in (4, 64):
+            out = RT.precondition(S, env, RT.table(kind, name, W, H), W, H, spp, ADEPTH)
+            print("%-9s %-7s %3d x %-3d %2d spp: %s" % (kind, name, W, H, spp, "  ".join("%s %.1f %%" % (k, 100 * v) for k, v in out.items())))
