@@ -170,7 +170,7 @@ int pt_render(pt_ctx* ctx, const pt_camera* cam, int32_t width, int32_t height, 
  * every call that touches what a frame in flight uses is ordered after the context's LAST ASYNCHRONOUS CALL, whichever stream that
  * call was given.  So any call of this header may follow a pt_*_device call at once, with no pt_synchronize between them.
  *   - The asynchronous calls (pt_render_device, pt_render_batch_device, pt_render_aov_device, pt_render_aov_follow_device, pt_render_aov_batch_device, pt_denoise_device,
- *     pt_denoise_batch_device, pt_denoise_var_device, pt_accum_add_device, pt_accum_denoise_device, pt_accum_reproject_device, pt_upsample_device, pt_trace_closest_device, pt_trace_occluded_device, pt_render_rays_device, pt_render_aov_rays_device, pt_reduce_framebuffer) wait ON THE
+ *     pt_denoise_batch_device, pt_denoise_var_device, pt_accum_add_device, pt_accum_denoise_device, pt_accum_reproject_device, pt_upsample_device, pt_trace_closest_device, pt_trace_occluded_device, pt_trace_surface_device, pt_render_rays_device, pt_render_aov_rays_device, pt_reduce_framebuffer) wait ON THE
  *     DEVICE: the stream they are given waits for an event recorded at the end of the previous asynchronous call - only if that call
  *     used another stream; on the same stream the stream's own order suffices and nothing is added.  The host returns at once, with
  *     two exceptions that existed before: a frame of another size, shard or batch length rewrites the pixel queue and a frame that
@@ -178,7 +178,7 @@ int pt_render(pt_ctx* ctx, const pt_camera* cam, int32_t width, int32_t height, 
  *     before) - both first wait on the host for the frame in flight; pt_render_batch_device and pt_render_aov_batch_device
  *     return when their per-frame tables have reached HBM, i.e. after whatever precedes them on `stream`; and a pt_accum_add_device that
  *     selects its pixels returns when the count of its active set has reached the host (see there).
- *   - The blocking renders (pt_render, pt_render_batch, pt_render_aov, pt_render_aov_follow, pt_render_aov_batch, pt_accum_add), pt_denoise, pt_denoise_batch, pt_denoise_var, pt_accum_denoise, pt_accum_reproject, pt_upsample, pt_trace_closest, pt_trace_occluded, pt_render_rays and pt_render_aov_rays run on the context's stream behind the same device-side wait
+ *   - The blocking renders (pt_render, pt_render_batch, pt_render_aov, pt_render_aov_follow, pt_render_aov_batch, pt_accum_add), pt_denoise, pt_denoise_batch, pt_denoise_var, pt_accum_denoise, pt_accum_reproject, pt_upsample, pt_trace_closest, pt_trace_occluded, pt_trace_surface, pt_render_rays and pt_render_aov_rays run on the context's stream behind the same device-side wait
  *     and return with the context idle.  After a blocking call, or on the context's own stream, they add no wait at all.
  *   - The calls that change or read what a frame uses WAIT ON THE HOST for the last asynchronous call's stream (if it is not the
  *     context's) and then for the context's: pt_set_materials, pt_set_environment, pt_update_vertices, pt_upload_scene,
@@ -193,7 +193,7 @@ int pt_render(pt_ctx* ctx, const pt_camera* cam, int32_t width, int32_t height, 
 int pt_render_device(pt_ctx* ctx, const pt_camera* cam, int32_t width, int32_t height, int32_t max_samples, int32_t max_path_depth,
                      void* d_out_rgb, void* d_out_rgba8, void* stream);
 /* Waits on the host for the context's last asynchronous call - pt_render_device, pt_render_batch_device, pt_render_aov_device,
- * pt_render_aov_follow_device, pt_render_aov_batch_device, pt_denoise_device, pt_denoise_batch_device, pt_denoise_var_device, pt_accum_add_device, pt_accum_denoise_device, pt_accum_reproject_device, pt_upsample_device, pt_trace_closest_device, pt_trace_occluded_device, pt_render_rays_device, pt_render_aov_rays_device or pt_reduce_framebuffer, on the stream it was given - and for the context's own stream.  Every earlier asynchronous call of the context
+ * pt_render_aov_follow_device, pt_render_aov_batch_device, pt_denoise_device, pt_denoise_batch_device, pt_denoise_var_device, pt_accum_add_device, pt_accum_denoise_device, pt_accum_reproject_device, pt_upsample_device, pt_trace_closest_device, pt_trace_occluded_device, pt_trace_surface_device, pt_render_rays_device, pt_render_aov_rays_device or pt_reduce_framebuffer, on the stream it was given - and for the context's own stream.  Every earlier asynchronous call of the context
  * is complete then as well, whatever stream it used: each was ordered before the next (see pt_render_device).  Returns PT_E_HIP if a
  * wave's watchdog fired during the last frame (the image is then incomplete); pt_get_stats reports the same.  PT_OK at once on an idle
  * or host-only context.  A caller's stream may be destroyed once this has returned. */
@@ -725,6 +725,59 @@ int64_t pt_debug_trace_rays_host(pt_ctx* ctx, const pt_ray* rays, int64_t n, int
 /* Host only: the mesh (entity of the upload) and the triangle inside it of a global triangle id, through the prefix sums of n_triangles
  * of the upload.  PT_E_INVALID outside 0 .. n_triangles-1, PT_E_NO_SCENE without a scene. */
 int pt_prim_to_mesh(pt_ctx* ctx, int32_t prim, int32_t* mesh, int32_t* triangle);
+
+/* ---- ray queries: the surface at the hit (no reference counterpart) ----
+ * pt_trace_surface is pt_trace_closest with WHAT IS THERE stored beside the hit: the hit point, the geometric and the shading normal,
+ * the texcoord, the material index, the base colour after the texture lookup and the emission - what picking, ambient occlusion and
+ * baking need next, from the records the library keeps in HBM in leaf order beside the triangle the walk just tested.  A caller takes
+ * p and ng / ns from this call, makes hemisphere rays of their own and sends them to pt_trace_occluded_device on the same stream.
+ * Kernels of their own (csrc/pt_kernel_rays_surface.hip, csrc/pt_kernel_rays_surface_wt.hip: the closest-hit walk of the ray kernels,
+ * whose lanes retire through csrc/pt_surface.h); the CPU twin is pt_debug_trace_surface_host.
+ * DEFINITION, per ray (a pt_ray as above; out: a pt_surface, 80 bytes, stored as five 16-byte stores).  Arithmetic under the contract
+ * of csrc/pt_device.h: binary32, no contraction, fma only where written (fma_).
+ *   The first 16 bytes {t, u, v, prim} are bit for bit what pt_trace_closest stores for that ray: thi, the tie-break, slivers never,
+ *   option "watertight".
+ *   A MISS is {+0, +0, +0, -1}, then p = +0, material = -1, and every remaining word +0.  All 80 bytes are written for every ray.
+ *   A HIT, with bx = u, by = v, bw = 1.0f - bx - by, (p0, p1, p2) the triangle's vertices, (n0, n1, n2) its vertex normals and
+ *   (tc0, tc1, tc2) its texcoords as the render's shade_hit reads them (csrc/pt_trace.h), and
+ *   interp3(bw, bx, by, a, b, c) = fma_(by, c, fma_(bx, b, bw * a)) per component:
+ *     p        = interp3(bw, bx, by, p0, p1, p2) - the render's hit point, with no normal offset; NOT org + t * dir.
+ *     ns       = normalize(interp3(bw, bx, by, n0, n1, n2)), or (0, 0, 0) if a component of that is not finite; NOT flipped towards
+ *                the ray (the normal of the guide pass).
+ *     ng       = normalize(cross(p1 - p0, p2 - p0)) with cross(a, b).x = fma_(a.y, b.z, -(a.z * b.y)) (cyclic) and
+ *                normalize(a) = a * (1.0f / sqrt(dot(a, a))); (0, 0, 0) by the same rule; NOT flipped: its orientation is that of the
+ *                mesh's index order.
+ *     tu, tv   = fma_(by, tc2.x, fma_(bx, tc1.x, bw * tc0.x)) and likewise in y; always computed (a mesh without texcoords: zeros).
+ *     material = the mesh's material_index as uploaded (may be < 0).
+ *     The ROW is the default material for material < 0 (base colour 0.8, emission 0), else row `material` of the current table
+ *     (pt_set_materials) with its texture slot.
+ *     base     = the row's base colour, or the nearest texel at (tu, tv) of the row's texture if it has one (the render's lookup:
+ *                RGBA8, clamp, normalised coordinates) - taken whether or not the material emits (the render and the guide pass
+ *                skip the lookup on an emitter).
+ *     emission = the row's emission.
+ * The call honours "watertight", "box_exact" (as pt_trace_*: only 1 selects the subtracting form), "rays_refill", "rays_grid",
+ * pt_set_materials and pt_update_vertices (the records are the leaf-order ones a refit rewrites).  It ignores the pixel shard and the
+ * environment, issues no collective and keeps no render state: a pt_render after it is bit for bit the one before.  It needs quad nodes.
+ * REFUSALS, ORDERING, n == 0, pt_get_stats, the bound flag behind pt_synchronize (a walk that ran out of its step or stack bound
+ * retires as a miss) and HOST-ONLY CONTEXTS are those of pt_trace_closest / pt_trace_closest_device, word for word, with pt_surface in
+ * place of pt_ray_hit: in particular d_out must be 16-byte aligned (a record is five 16-byte stores), and pt_trace_surface_device joins
+ * the asynchronous calls at pt_render_device and the list at pt_synchronize.
+ * NOT BUILT: a lookup from a caller's (prim, u, v) without a ray - the records are in leaf order and the scene keeps no table from a
+ * triangle id to its slot on the device; a mesh index in the record (pt_prim_to_mesh stays the way); no pt_main flag, no pt_group_*
+ * form, no batch form. */
+typedef struct pt_surface {          /* 80 bytes */
+    float t, u, v; int32_t prim;     /* bit for bit pt_trace_closest's record of this ray */
+    float p[3];    int32_t material; /* hit point; the mesh's material_index (may be < 0) */
+    float ng[3];   float tu;         /* geometric normal; interpolated texcoord u */
+    float ns[3];   float tv;         /* shading normal;   interpolated texcoord v */
+    float base[3]; float emission;   /* base colour after the texture lookup; material emission */
+} pt_surface;
+int pt_trace_surface       (pt_ctx* ctx, const pt_ray* rays, int64_t n, pt_surface* out);
+int pt_trace_surface_device(pt_ctx* ctx, const void* d_rays, int64_t n, void* d_out /* n pt_surface, 16-byte aligned */, void* stream);
+/* The CPU twin: pt_debug_trace_rays_host's walk, then the record above from the host copies of the scene (triangles, shading
+ * records, material table, textures); works on a host-only context, follows "watertight", pt_set_materials and pt_update_vertices.
+ * Returns n. */
+int64_t pt_debug_trace_surface_host(pt_ctx* ctx, const pt_ray* rays, int64_t n, pt_surface* out);
 
 /* ---- ray images: path-traced radiance along the CALLER'S rays (no reference counterpart: the reference starts every path at its one
  * pinhole camera, device.cu:231-241) ----

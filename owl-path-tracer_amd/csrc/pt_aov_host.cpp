@@ -8,6 +8,8 @@
 // (gen_camera_ray), interp3 and the miss branch / attribute fetch of shade_hit - each a few lines, once for both twin pixels, cited below.
 // pt_debug_aov_rays_host, the twin of the guide pass over a ray image (pt_render_aov_rays), is the follow twin with the camera ray
 // replaced by the pixel's ray record (gen_ray_from): ONE follow loop serves both.
+// pti::surface_record_host, the record of pt_debug_trace_surface_host (the twin of pt_trace_surface, pt_rays_host.cpp), sits here for
+// the same reason: it is pt_surface.h's function with these host forms of the device arithmetic.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -118,6 +120,12 @@ AovHit fetch_hit(const AovScene& A, int32_t prim, float hu, float hv)
         h.mat.base_color = tex_nearest(tx.px.data(), tx.w, tx.h, tu, tv);
     }
     return h;
+}
+
+v3 surface_unit(v3 a) // pt_surface.h
+{
+    const v3 n = normalize(a);
+    return (finite_(n.x) && finite_(n.y) && finite_(n.z)) ? n : vs(0.0f);
 }
 
 // One pixel: include/mi355pt.h, "guide pass"; the kernel's loop body (pt_aov_kernel) line for line.
@@ -282,6 +290,42 @@ extern "C" int64_t pt_debug_aov_host(pt_ctx* c, const pt_camera* cam, int32_t W,
     if (!c || !cam || !out || n_pixels < 0 || (n_pixels > 0 && !pixel_ids)) return PT_E_INVALID;
     if (!c->have_scene) return fail(c, PT_E_NO_SCENE, "no geometries (pt_upload_scene not called)");
     return aov_host(c, cam, nullptr, W, H, n_samples, pixel_ids, n_pixels, out, nullptr, "pt_debug_aov_host");
+}
+
+// surface_record of pt_surface.h over the host copies (pt_debug_trace_surface_host, pt_rays_host.cpp), line for line.
+void pti::surface_record_host(const HostScene& S, int32_t slot, float t, float u, float v, int32_t prim, pt_surface* out)
+{
+    std::memset(out, 0, sizeof *out); // a miss: {+0, +0, +0, -1}, p = +0, material = -1, every remaining word +0
+    out->prim = -1;
+    out->material = -1;
+    if (slot < 0) return;
+    const PtTri& tr = S.bvh.tris[(size_t)slot];
+    const PtShade& sh = S.shade[(size_t)slot];
+    const int mi = tr.material;
+    Material mat = material_default();
+    int32_t tex_slot = -1;
+    if (mi >= 0) {
+        const float* mp = &S.materials[(size_t)mi * PT_MAT_STRIDE];
+        mat = material_load(mp);
+        std::memcpy(&tex_slot, mp + 17, 4);
+    }
+    const float bx = u, by = v;
+    const float bw = 1.0f - bx - by;
+    const v3 p0 = V(tr.p0[0], tr.p0[1], tr.p0[2]), p1 = V(tr.p1[0], tr.p1[1], tr.p1[2]), p2 = V(tr.p2[0], tr.p2[1], tr.p2[2]);
+    const v3 v_p = interp3(bw, bx, by, p0, p1, p2);
+    const v3 v_ns = surface_unit(interp3(bw, bx, by, V(sh.n0[0], sh.n0[1], sh.n0[2]), V(sh.n1[0], sh.n1[1], sh.n1[2]), V(sh.n2[0], sh.n2[1], sh.n2[2])));
+    const v3 v_ng = surface_unit(cross(p1 - p0, p2 - p0));
+    const float tu = fma_(by, sh.tc[4], fma_(bx, sh.tc[2], bw * sh.tc[0]));
+    const float tv = fma_(by, sh.tc[5], fma_(bx, sh.tc[3], bw * sh.tc[1]));
+    if (tex_slot >= 0) {
+        const HostTexture& tx = S.textures[(size_t)tex_slot];
+        mat.base_color = tex_nearest(tx.px.data(), tx.w, tx.h, tu, tv);
+    }
+    out->t = t; out->u = u; out->v = v; out->prim = prim;
+    out->p[0] = v_p.x; out->p[1] = v_p.y; out->p[2] = v_p.z; out->material = mi;
+    out->ng[0] = v_ng.x; out->ng[1] = v_ng.y; out->ng[2] = v_ng.z; out->tu = tu;
+    out->ns[0] = v_ns.x; out->ns[1] = v_ns.y; out->ns[2] = v_ns.z; out->tv = tv;
+    out->base[0] = mat.base_color.x; out->base[1] = mat.base_color.y; out->base[2] = mat.base_color.z; out->emission = mat.emission;
 }
 
 namespace {

@@ -225,6 +225,9 @@ PT_LOCAL int need_accum(pt_ctx* c, const char* who);  // PT_E_INVALID by name wi
 PT_LOCAL int refuse_comm(pt_ctx* c, const char* who); // PT_E_INVALID by name with a communicator
 // pt_aov_host.cpp
 PT_LOCAL int check_aov_params(pt_ctx* c, const pt_aov_params* p, const char* who, pt_aov_params* eff); // the refusals of pt_render_aov_follow* and the twin; *eff = the parameters in effect
+// the surface record of pt_trace_surface at the hit (t, u, v, prim) on the triangle in leaf-order slot `slot` (< 0: the miss record), from the host
+// copies of the scene with the arithmetic of pt_device.h: csrc/pt_surface.h expression for expression (pt_debug_trace_surface_host)
+PT_LOCAL void surface_record_host(const HostScene& S, int32_t slot, float t, float u, float v, int32_t prim, pt_surface* out);
 // pt_comm.cpp
 PT_LOCAL int reduce_framebuffer(pt_ctx* c, void* d_rgb, void* d_rgba8, int64_t n_pixels, hipStream_t stream); // pt_reduce_framebuffer inside a call that is ordered already
 PT_LOCAL int reduce_sum(pt_ctx* c, void* d_buf, size_t n_floats, hipStream_t stream); // in-place sum-reduce onto rank 0; nothing without a communicator

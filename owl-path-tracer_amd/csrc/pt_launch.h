@@ -71,7 +71,7 @@ struct PtAovFollowArgs {
 // Ray queries (pt_trace_closest, pt_trace_occluded; pt_rays_kernels.h): what the ray kernels take beside the scene in PtKernelParams.
 struct PtRaysArgs {
     const void* rays;  // n pt_ray records (include/mi355pt.h: org, tmax, dir, one float that is not read), 16-byte aligned
-    void* out;         // closest: n pt_ray_hit {t, u, v, prim}, 16-byte aligned; occluded: n bytes
+    void* out;         // closest: n pt_ray_hit {t, u, v, prim}, 16-byte aligned; occluded: n bytes; surface: n pt_surface (80 bytes), 16-byte aligned
     uint32_t* ovf;     // the waves' HBM stack columns, (cap - PT_LDS_STACK) * 64 words per workgroup (none when cap <= PT_LDS_STACK)
     int32_t n;         // rays (< 2^31)
     int32_t per_wave;  // rays of a workgroup's range, a multiple of 64: workgroup b owns [b * per_wave, min(n, (b + 1) * per_wave))
@@ -245,6 +245,12 @@ hipError_t pt_launch_rays(const PtKernelParams* p, const PtRaysArgs* a, int occl
 hipError_t pt_rays_geometry(int occluded, int exact, PtGeometry* g);
 hipError_t pt_launch_rays_wt(const PtKernelParams* p, const PtRaysArgs* a, int occluded, int grid, size_t lds_bytes, hipStream_t stream);
 hipError_t pt_rays_geometry_wt(int occluded, int exact, PtGeometry* g);
+// pt_kernel_rays_surface.hip / pt_kernel_rays_surface_wt.hip: the surface instances of the ray kernels (pt_trace_surface; a->out: n pt_surface
+// records of 80 bytes, 16-byte aligned), same conventions; closest hit only: occluded = 1 answers hipErrorInvalidValue
+hipError_t pt_launch_rays_surface(const PtKernelParams* p, const PtRaysArgs* a, int occluded, int grid, size_t lds_bytes, hipStream_t stream);
+hipError_t pt_rays_surface_geometry(int occluded, int exact, PtGeometry* g);
+hipError_t pt_launch_rays_surface_wt(const PtKernelParams* p, const PtRaysArgs* a, int occluded, int grid, size_t lds_bytes, hipStream_t stream);
+hipError_t pt_rays_surface_geometry_wt(int occluded, int exact, PtGeometry* g);
 // pt_kernel_aov_follow.hip / pt_kernel_aov_follow_wt.hip: the follow kernels, same conventions; lds_bytes covers the stack and the state a lane parks behind it
 hipError_t pt_launch_aov_follow(const PtKernelParams* p, const PtAovFollowArgs* a, int binary, int grid, size_t lds_bytes, hipStream_t stream);
 hipError_t pt_aov_follow_geometry(int binary, int exact, int stack_entries, PtGeometry* g);

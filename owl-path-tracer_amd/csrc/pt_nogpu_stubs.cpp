@@ -40,6 +40,10 @@ hipError_t pt_launch_rays(const PtKernelParams*, const PtRaysArgs*, int, int, si
 hipError_t pt_rays_geometry(int, int, PtGeometry*) { return hipErrorNotSupported; }
 hipError_t pt_launch_rays_wt(const PtKernelParams*, const PtRaysArgs*, int, int, size_t, hipStream_t) { return hipErrorNotSupported; }
 hipError_t pt_rays_geometry_wt(int, int, PtGeometry*) { return hipErrorNotSupported; }
+hipError_t pt_launch_rays_surface(const PtKernelParams*, const PtRaysArgs*, int, int, size_t, hipStream_t) { return hipErrorNotSupported; }
+hipError_t pt_rays_surface_geometry(int, int, PtGeometry*) { return hipErrorNotSupported; }
+hipError_t pt_launch_rays_surface_wt(const PtKernelParams*, const PtRaysArgs*, int, int, size_t, hipStream_t) { return hipErrorNotSupported; }
+hipError_t pt_rays_surface_geometry_wt(int, int, PtGeometry*) { return hipErrorNotSupported; }
 size_t pt_denoise_workspace_bytes(int, int) { return 16; }
 hipError_t pt_denoise_geometry(int, int, PtGeometry*, int*) { return hipErrorNotSupported; }
 hipError_t pt_launch_denoise(const PtDenoiseArgs*, hipStream_t) { return hipErrorNotSupported; }

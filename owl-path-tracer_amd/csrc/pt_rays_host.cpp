@@ -1,6 +1,7 @@
-// pt_rays_host.cpp -- ray queries on the caller's rays (pt_trace_closest*, pt_trace_occluded*): ONE device path behind the asynchronous
-// and blocking entry points, the CPU twin pt_debug_trace_rays_host and pt_prim_to_mesh.
-// The pass reads the scene and nothing of a frame: no pixel queue, no shard, no materials, no environment, no collective.  Its own
+// pt_rays_host.cpp -- ray queries on the caller's rays (pt_trace_closest*, pt_trace_occluded*, pt_trace_surface*): ONE device path behind
+// the asynchronous and blocking entry points, the CPU twins pt_debug_trace_rays_host and pt_debug_trace_surface_host, and pt_prim_to_mesh.
+// The pass reads the scene and nothing of a frame: no pixel queue, no shard, no environment, no collective - and no materials or
+// textures either, except in surface mode, which reads the hit's material row and texel (fill_params: the current table).  Its own
 // buffers are d_rays_in / d_rays_out (the blocking forms' staging); the waves' stack overflow columns and the bound flag are the guide
 // pass's d_aov_ws (walk_workspace, pt_internal.h) - the two passes are ordered like any two calls of a context, and check_watchdog
 // looks at one flag.
@@ -17,19 +18,26 @@ namespace {
 constexpr float kRayTMin = 1e-3f, kRayTMax = 1e10f; // kTMin, kTMax of pt_device.h
 
 static_assert(sizeof(pt_ray) == 32 && sizeof(pt_ray_hit) == 16, "the ray kernels read a ray as two 16-byte loads and store a hit as one");
+static_assert(sizeof(pt_surface) == 80, "the surface instances store a record as five 16-byte stores");
+
+// What a call stores per ray: a pt_ray_hit, a byte, or a pt_surface.
+enum RaysMode { kClosest = 0, kOccluded = 1, kSurface = 2 };
+constexpr size_t kRecordBytes[3] = {sizeof(pt_ray_hit), 1, sizeof(pt_surface)};
 
 const struct RaysInstance {
     hipError_t (*geometry)(int occluded, int exact, PtGeometry* g);
     hipError_t (*launch)(const PtKernelParams* p, const PtRaysArgs* a, int occluded, int grid, size_t lds_bytes, hipStream_t stream);
-} kRaysInstance[2] = {{pt_rays_geometry, pt_launch_rays}, {pt_rays_geometry_wt, pt_launch_rays_wt}}; // by [watertight]
+} kRaysInstance[2][2] = {{{pt_rays_geometry, pt_launch_rays}, {pt_rays_geometry_wt, pt_launch_rays_wt}},
+                         {{pt_rays_surface_geometry, pt_launch_rays_surface}, {pt_rays_surface_geometry_wt, pt_launch_rays_surface_wt}}}; // by [surface][watertight]
 
 // What every form refuses before anything is touched, a host-only context last (who: the entry point).
-int check_rays_args(pt_ctx* c, const char* who, const void* rays, int64_t n, const void* out, bool device, bool closest)
+int check_rays_args(pt_ctx* c, const char* who, const void* rays, int64_t n, const void* out, bool device, RaysMode mode)
 {
     if (n < 0 || n >= ((int64_t)1 << 31)) return fail(c, PT_E_INVALID, "%s: n = %lld rays (0 .. 2^31 - 1)", who, (long long)n);
     if (n > 0 && (!rays || !out)) return fail(c, PT_E_INVALID, "%s: NULL %s", who, !rays ? (device ? "d_rays" : "rays") : (device ? "d_out" : "out"));
     if (device && n > 0 && ((uintptr_t)rays & 15u)) return fail(c, PT_E_INVALID, "%s: d_rays is not 16-byte aligned (a ray is two 16-byte loads)", who);
-    if (device && closest && n > 0 && ((uintptr_t)out & 15u)) return fail(c, PT_E_INVALID, "%s: d_out is not 16-byte aligned (a hit is one 16-byte store)", who);
+    if (device && mode != kOccluded && n > 0 && ((uintptr_t)out & 15u))
+        return fail(c, PT_E_INVALID, "%s: d_out is not 16-byte aligned (a %s)", who, mode == kSurface ? "surface record is five 16-byte stores of its 80 bytes" : "hit is one 16-byte store");
     if (!c->have_scene) return fail(c, PT_E_NO_SCENE, "%s: no geometries (pt_upload_scene not called)", who);
     // the ray kernels walk the quad nodes - or a root that is itself a leaf - and nothing else
     if (!quad_walk_available(c))
@@ -39,7 +47,7 @@ int check_rays_args(pt_ctx* c, const char* who, const void* rays, int64_t n, con
 
 // One launch of the ray kernel over n >= 1 rays in HBM.  A wave owns a contiguous range of whole 64-ray blocks; the grid is what the
 // occupancy query says is resident, or fewer when there are fewer blocks.
-int rays_device(pt_ctx* c, bool occluded, const void* d_rays, int64_t n, void* d_out, hipStream_t stream)
+int rays_device(pt_ctx* c, RaysMode mode, const void* d_rays, int64_t n, void* d_out, hipStream_t stream)
 {
     int rc;
     if ((rc = check_quad_walk_size(c, "ray"))) return rc;
@@ -47,7 +55,8 @@ int rays_device(pt_ctx* c, bool occluded, const void* d_rays, int64_t n, void* d
     fill_params(c, P); // the scene; no camera, so no distance to judge the slab form by: the subtracting form only on request
     P.box_exact = c->opt.box_exact > 0 ? 1 : 0;
     quad_walk_params(c, P);
-    const RaysInstance& inst = kRaysInstance[c->opt.watertight != 0];
+    const RaysInstance& inst = kRaysInstance[mode == kSurface][c->opt.watertight != 0];
+    const int occluded = mode == kOccluded;
     PtGeometry g{};
     const hipError_t ge = inst.geometry(occluded, P.box_exact, &g);
     if (ge == hipErrorInvalidConfiguration) return fail(c, PT_E_LIMIT, "this build of the ray kernel spills registers to scratch; such builds are refused (pt_kernel.hip)");
@@ -75,31 +84,31 @@ int rays_device(pt_ctx* c, bool occluded, const void* d_rays, int64_t n, void* d
     return PT_OK;
 }
 
-int rays_async(pt_ctx* c, const char* who, bool occluded, const void* d_rays, int64_t n, void* d_out, void* stream_v)
+int rays_async(pt_ctx* c, const char* who, RaysMode mode, const void* d_rays, int64_t n, void* d_out, void* stream_v)
 {
     if (!c) return PT_E_INVALID;
     int rc;
-    if ((rc = check_rays_args(c, who, d_rays, n, d_out, true, !occluded))) return rc;
+    if ((rc = check_rays_args(c, who, d_rays, n, d_out, true, mode))) return rc;
     if (n == 0) return PT_OK;
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t stream = stream_v ? (hipStream_t)stream_v : c->stream;
-    return async_call(c, stream, [&] { return rays_device(c, occluded, d_rays, n, d_out, stream); });
+    return async_call(c, stream, [&] { return rays_device(c, mode, d_rays, n, d_out, stream); });
 }
 
 // Host buffers: the rays staged in d_rays_in, the results in d_rays_out, and back.
-int rays_blocking(pt_ctx* c, const char* who, bool occluded, const pt_ray* rays, int64_t n, void* out)
+int rays_blocking(pt_ctx* c, const char* who, RaysMode mode, const pt_ray* rays, int64_t n, void* out)
 {
     if (!c) return PT_E_INVALID;
     int rc;
-    if ((rc = check_rays_args(c, who, rays, n, out, false, !occluded))) return rc;
+    if ((rc = check_rays_args(c, who, rays, n, out, false, mode))) return rc;
     if (n == 0) return PT_OK;
     HIP_TRY(c, hipSetDevice(c->device));
-    const size_t out_bytes = (size_t)n * (occluded ? 1 : sizeof(pt_ray_hit));
+    const size_t out_bytes = (size_t)n * kRecordBytes[mode];
     return blocking_call(c, [&]() -> int {
         int rc2;
         if ((rc2 = ensure(c, c->d_rays_in, (size_t)n * sizeof(pt_ray))) || (rc2 = ensure(c, c->d_rays_out, out_bytes))) return rc2;
         HIP_TRY(c, hipMemcpyAsync(c->d_rays_in.p, rays, (size_t)n * sizeof(pt_ray), hipMemcpyHostToDevice, c->stream));
-        if ((rc2 = rays_device(c, occluded, c->d_rays_in.p, n, c->d_rays_out.p, c->stream))) return rc2;
+        if ((rc2 = rays_device(c, mode, c->d_rays_in.p, n, c->d_rays_out.p, c->stream))) return rc2;
         return drain(c, {{out, c->d_rays_out.p, out_bytes}});
     });
 }
@@ -108,10 +117,12 @@ int rays_blocking(pt_ctx* c, const char* who, bool occluded, const pt_ray* rays,
 
 extern "C" {
 
-int pt_trace_closest(pt_ctx* c, const pt_ray* rays, int64_t n, pt_ray_hit* out) { return rays_blocking(c, "pt_trace_closest", false, rays, n, out); }
-int pt_trace_occluded(pt_ctx* c, const pt_ray* rays, int64_t n, uint8_t* out) { return rays_blocking(c, "pt_trace_occluded", true, rays, n, out); }
-int pt_trace_closest_device(pt_ctx* c, const void* d_rays, int64_t n, void* d_out, void* stream) { return rays_async(c, "pt_trace_closest_device", false, d_rays, n, d_out, stream); }
-int pt_trace_occluded_device(pt_ctx* c, const void* d_rays, int64_t n, void* d_out, void* stream) { return rays_async(c, "pt_trace_occluded_device", true, d_rays, n, d_out, stream); }
+int pt_trace_closest(pt_ctx* c, const pt_ray* rays, int64_t n, pt_ray_hit* out) { return rays_blocking(c, "pt_trace_closest", kClosest, rays, n, out); }
+int pt_trace_occluded(pt_ctx* c, const pt_ray* rays, int64_t n, uint8_t* out) { return rays_blocking(c, "pt_trace_occluded", kOccluded, rays, n, out); }
+int pt_trace_closest_device(pt_ctx* c, const void* d_rays, int64_t n, void* d_out, void* stream) { return rays_async(c, "pt_trace_closest_device", kClosest, d_rays, n, d_out, stream); }
+int pt_trace_occluded_device(pt_ctx* c, const void* d_rays, int64_t n, void* d_out, void* stream) { return rays_async(c, "pt_trace_occluded_device", kOccluded, d_rays, n, d_out, stream); }
+int pt_trace_surface(pt_ctx* c, const pt_ray* rays, int64_t n, pt_surface* out) { return rays_blocking(c, "pt_trace_surface", kSurface, rays, n, out); }
+int pt_trace_surface_device(pt_ctx* c, const void* d_rays, int64_t n, void* d_out, void* stream) { return rays_async(c, "pt_trace_surface_device", kSurface, d_rays, n, d_out, stream); }
 
 int64_t pt_debug_trace_rays_host(pt_ctx* c, const pt_ray* rays, int64_t n, int32_t occluded, void* out)
 {
@@ -130,6 +141,33 @@ int64_t pt_debug_trace_rays_host(pt_ctx* c, const pt_ray* rays, int64_t n, int32
             const bool hit = pt_bvh_closest_hit_host(c->scene.bvh, r.org, r.dir, kRayTMin, thi, &t, &u, &v, &prim, wt);
             if (occluded) ((uint8_t*)out)[i] = hit ? 1 : 0;
             else ((pt_ray_hit*)out)[i] = hit ? pt_ray_hit{t, u, v, prim} : pt_ray_hit{0.0f, 0.0f, 0.0f, -1};
+        }
+    });
+    return n;
+}
+
+int64_t pt_debug_trace_surface_host(pt_ctx* c, const pt_ray* rays, int64_t n, pt_surface* out)
+{
+    if (!c) return PT_E_INVALID;
+    if (n < 0 || n >= ((int64_t)1 << 31)) return fail(c, PT_E_INVALID, "pt_debug_trace_surface_host: n = %lld rays (0 .. 2^31 - 1)", (long long)n);
+    if (n > 0 && (!rays || !out)) return fail(c, PT_E_INVALID, "pt_debug_trace_surface_host: NULL %s", !rays ? "rays" : "out");
+    if (!c->have_scene) return fail(c, PT_E_NO_SCENE, "pt_debug_trace_surface_host: no geometries (pt_upload_scene not called)");
+    sync_host_scene(c);
+    const bool wt = c->opt.watertight != 0;
+    // global triangle id -> leaf-order slot: the host walk reports the id, the records are in leaf order (padding slots carry id 0x7fffffff)
+    std::vector<int32_t> slot_of((size_t)c->scene.n_triangles, -1);
+    for (size_t s = 0; s < c->scene.bvh.tris.size(); ++s) {
+        const int32_t id = c->scene.bvh.tris[s].id;
+        if (id >= 0 && (size_t)id < slot_of.size()) slot_of[(size_t)id] = (int32_t)s;
+    }
+    pt_parallel_ranges((size_t)n, [&](size_t lo, size_t hi) {
+        for (size_t i = lo; i < hi; ++i) {
+            const pt_ray& r = rays[i];
+            const float thi = r.tmax < kRayTMax ? r.tmax : kRayTMax; // NaN and +inf: the library's own bound
+            float t = 0.0f, u = 0.0f, v = 0.0f;
+            int32_t prim = -1;
+            const bool hit = pt_bvh_closest_hit_host(c->scene.bvh, r.org, r.dir, kRayTMin, thi, &t, &u, &v, &prim, wt);
+            surface_record_host(c->scene, hit ? slot_of[(size_t)prim] : -1, t, u, v, prim, &out[i]);
         }
     });
     return n;

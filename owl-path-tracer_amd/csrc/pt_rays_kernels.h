@@ -1,11 +1,9 @@
 // pt_rays_kernels.h -- ray queries (pt_trace_closest, pt_trace_occluded, include/mi355pt.h): closest hit and occlusion for the caller's rays
-//
 // Translation units of their own once more - pt_kernel_rays.hip and, with PT_WATERTIGHT = 1, pt_kernel_rays_wt.hip include this header -
 // so that every other `make asm-*` target goes on listing the kernels it listed.  No batch form.  Like the probes and the guide kernels the
 // kernel owns no traversal arithmetic: ray_inv -> node4_step<PT_WAVE, PT_LDS_STACK> (short LDS stack, deeper levels in the wave's HBM
 // columns) -> leaf_test -> stack_pop, with the probe's bounds around them.  The ray's own bound enters only as the initial h.t.
-// What is new:
-//   * ray I/O: a ray is two 16-byte loads, a closest hit one 16-byte store, an occlusion flag a byte store;
+// What is new:  * ray I/O: a ray is two 16-byte loads, a closest hit one 16-byte store, an occlusion flag a byte store;
 //   * any-hit exit (OCCLUDED): a lane whose leaf_test accepted a triangle (h.slot >= 0) is done at once.  tbest never shrinks below the
 //     ray's bound in such a walk, so ordering the children buys nothing - node4_step is left as it is;
 //   * lane refill (the persistent "while-while" loop of Aila and Laine 2009, without its atomics): a wave owns the contiguous range
@@ -21,7 +19,9 @@
 #pragma once
 #include "pt_instance.h"
 #include "pt_trace.h"
-#if PT_WATERTIGHT
+#if PT_RAYS_SURFACE
+#include "pt_surface.h" // surface mode (pt_trace_surface): the record a lane retires with, and PT_RAYS_KERNEL / _LAUNCH / _GEOMETRY
+#elif PT_WATERTIGHT
 #define PT_RAYS_KERNEL pt_rays_wt_kernel
 #define PT_RAYS_LAUNCH pt_launch_rays_wt
 #define PT_RAYS_GEOMETRY pt_rays_geometry_wt
@@ -95,6 +95,12 @@ __global__ void __launch_bounds__(PT_WAVE, PT_RAYS_WAVES_PER_EU) PT_RAYS_KERNEL(
                 const bool hit = h.slot >= 0;
                 if (OCCLUDED) {
                     ((uint8_t PT_AS1*)A.out)[(size_t)(uint32_t)ray] = hit ? (uint8_t)1 : (uint8_t)0;
+#if PT_RAYS_SURFACE
+                } else if (PT_RAYS_SURFACE) { // surface mode: the 80-byte record of the hit; h.slot < 0 (a miss, a walk out of its bounds): the miss record
+                    const SurfaceRecord r = surface_record(P, h.slot, h.u, h.v, h.t, h.id);
+                    f32x4 PT_AS1* y = (f32x4 PT_AS1*)((char PT_AS1*)A.out + (size_t)(uint32_t)ray * 80);
+                    y[0] = r.hit; y[1] = r.p; y[2] = r.ng; y[3] = r.ns; y[4] = r.base;
+#endif
                 } else {
                     f32x4 PT_AS1* y = (f32x4 PT_AS1*)((char PT_AS1*)A.out + (size_t)(uint32_t)ray * 16);
                     *y = hit ? (f32x4){h.t, h.u, h.v, __int_as_float(h.id)} : (f32x4){0.0f, 0.0f, 0.0f, __int_as_float(-1)};
@@ -108,8 +114,13 @@ __global__ void __launch_bounds__(PT_WAVE, PT_RAYS_WAVES_PER_EU) PT_RAYS_KERNEL(
 // The instance that serves (occluded, exact), for the geometry function and the launcher alike.
 static const void* rays_instance(int occluded, int exact)
 {
+#if PT_RAYS_SURFACE
+    if (occluded) return nullptr; // no such instance: the geometry function and the launcher answer hipErrorInvalidValue
+    return exact ? (const void*)PT_RAYS_KERNEL<false, true> : (const void*)PT_RAYS_KERNEL<false, false>;
+#else
     if (occluded) return exact ? (const void*)PT_RAYS_KERNEL<true, true> : (const void*)PT_RAYS_KERNEL<true, false>;
     return exact ? (const void*)PT_RAYS_KERNEL<false, true> : (const void*)PT_RAYS_KERNEL<false, false>;
+#endif
 }
 
 extern "C" hipError_t PT_RAYS_GEOMETRY(int occluded, int exact, PtGeometry* g)
@@ -119,6 +130,9 @@ extern "C" hipError_t PT_RAYS_GEOMETRY(int occluded, int exact, PtGeometry* g)
     g->lds_levels = PT_LDS_STACK;
     g->lds_bytes = (size_t)g->lds_levels * PT_WAVE * 4;
     g->state_words = 0;
+#if PT_RAYS_SURFACE
+    if (occluded) return hipErrorInvalidValue;
+#endif
     return pt_complete_geometry(g, rays_instance(occluded, exact));
 }
 
@@ -127,6 +141,9 @@ extern "C" hipError_t PT_RAYS_LAUNCH(const PtKernelParams* p, const PtRaysArgs* 
     if (grid < 1 || a->n < 1 || a->per_wave < PT_WAVE || (a->per_wave % PT_WAVE) != 0 || a->refill < 0 || a->refill >= PT_WAVE) return hipErrorInvalidValue;
     if ((long long)grid * a->per_wave < (long long)a->n) return hipErrorInvalidValue; // the ranges cover every ray ...
     if ((long long)(grid - 1) * a->per_wave >= (long long)a->n) return hipErrorInvalidValue; // ... and none is empty: the kernel relies on it
+#if PT_RAYS_SURFACE
+    if (occluded) return hipErrorInvalidValue;
+#endif
     void* args[] = {(void*)p, (void*)a};
     (void)hipLaunchKernel(rays_instance(occluded, p->box_exact), dim3(grid), dim3(PT_WAVE), args, lds_bytes, stream);
     return hipGetLastError();

@@ -132,12 +132,16 @@ EXPORTS = ["pt_create", "pt_destroy", "pt_last_error", "pt_abi_version", "pt_upl
            "pt_accum_variance", "pt_debug_accum_variance_host", "pt_accum_denoise", "pt_accum_denoise_device",
            "pt_accum_reproject_default_params", "pt_accum_reproject", "pt_accum_reproject_device", "pt_debug_accum_reproject_host",
            "pt_upsample_default_params", "pt_upsample", "pt_upsample_device", "pt_debug_upsample_host",
-           "pt_trace_closest", "pt_trace_closest_device", "pt_trace_occluded", "pt_trace_occluded_device", "pt_debug_trace_rays_host", "pt_prim_to_mesh",
+           "pt_trace_closest", "pt_trace_closest_device", "pt_trace_occluded", "pt_trace_occluded_device", "pt_debug_trace_rays_host", "pt_prim_to_mesh", "pt_trace_surface", "pt_trace_surface_device", "pt_debug_trace_surface_host",
            "pt_render_rays", "pt_render_rays_device", "pt_render_aov_rays", "pt_render_aov_rays_device", "pt_debug_aov_rays_host"]
 # pt_ray / pt_ray_hit (include/mi355pt.h "ray queries"): 32 and 16 bytes
 RAY_DTYPE = np.dtype([("org", "<f4", (3,)), ("tmax", "<f4"), ("dir", "<f4", (3,)), ("unused", "<f4")])
 HIT_DTYPE = np.dtype([("t", "<f4"), ("u", "<f4"), ("v", "<f4"), ("prim", "<i4")])
 assert RAY_DTYPE.itemsize == 32 and HIT_DTYPE.itemsize == 16
+# pt_surface (include/mi355pt.h "ray queries: the surface at the hit"): pt_trace_closest's record, then what lies at the hit
+SURFACE_DTYPE = np.dtype([("t", "<f4"), ("u", "<f4"), ("v", "<f4"), ("prim", "<i4"), ("p", "<f4", (3,)), ("material", "<i4"), ("ng", "<f4", (3,)), ("tu", "<f4"),
+                          ("ns", "<f4", (3,)), ("tv", "<f4"), ("base", "<f4", (3,)), ("emission", "<f4")])
+assert SURFACE_DTYPE.itemsize == 80
 # pt_ray_gen (include/mi355pt.h "ray images"): 64 bytes; pyhost/ray_image.py builds tables of these
 RAY_GEN_DTYPE = np.dtype([("org", "<f4", (3,)), ("reserved0", "<f4"), ("dir", "<f4", (3,)), ("reserved1", "<f4"),
                           ("du", "<f4", (3,)), ("reserved2", "<f4"), ("dv", "<f4", (3,)), ("reserved3", "<f4")])
@@ -296,6 +300,10 @@ def lib():
     L.pt_debug_trace_rays_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
     L.pt_debug_trace_rays_host.restype = C.c_int64
     L.pt_prim_to_mesh.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    L.pt_trace_surface.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    L.pt_trace_surface_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    L.pt_debug_trace_surface_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    L.pt_debug_trace_surface_host.restype = C.c_int64
     L.pt_render_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, fp, C.POINTER(C.c_uint32)]
     L.pt_render_rays_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     L.pt_render_aov_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(AovParams), fp]
@@ -1008,9 +1016,9 @@ class Context:
         self._check(int(rc), "pt_debug_accum_reproject_host")
         return o
 
-    def _trace(self, fn, what, rays, occluded, extra=()):
+    def _trace(self, fn, what, rays, occluded, extra=(), dtype=None):
         r = _rays(rays)
-        out = np.empty(r.shape[0], np.uint8 if occluded else HIT_DTYPE)
+        out = np.empty(r.shape[0], dtype if dtype is not None else np.uint8 if occluded else HIT_DTYPE)
         rc = fn(self._h, r.ctypes.data_as(C.c_void_p), r.shape[0], *extra, out.ctypes.data_as(C.c_void_p))
         self._check(int(rc), what)
         return out
@@ -1036,6 +1044,19 @@ class Context:
     def trace_occluded_device(self, d_rays, n, d_out, stream=None):
         """pt_trace_occluded_device: the same for the occlusion flags, n bytes left at d_out."""
         self._check(lib().pt_trace_occluded_device(self._h, C.c_void_p(d_rays), int(n), C.c_void_p(d_out), C.c_void_p(stream) if stream else None), "pt_trace_occluded_device")
+
+    def trace_surface(self, rays):
+        """pt_trace_surface: trace_closest with the surface at the hit, as a SURFACE_DTYPE array (80 bytes per ray: the hit record, hit
+        point, material index, geometric and shading normal, texcoord, base colour, emission; include/mi355pt.h)."""
+        return self._trace(lib().pt_trace_surface, "pt_trace_surface", rays, False, dtype=SURFACE_DTYPE)
+
+    def trace_surface_host(self, rays):
+        """pt_debug_trace_surface_host, the CPU twin of trace_surface (works on a host-only context)."""
+        return self._trace(lib().pt_debug_trace_surface_host, "pt_debug_trace_surface_host", rays, False, dtype=SURFACE_DTYPE)
+
+    def trace_surface_device(self, d_rays, n, d_out, stream=None):
+        """pt_trace_surface_device: asynchronous as trace_closest_device, n pt_surface records (80 bytes each) left at d_out (16-byte aligned)."""
+        self._check(lib().pt_trace_surface_device(self._h, C.c_void_p(d_rays), int(n), C.c_void_p(d_out), C.c_void_p(stream) if stream else None), "pt_trace_surface_device")
 
     def prim_to_mesh(self, prim):
         """pt_prim_to_mesh: (entity of the upload, triangle inside it) of a global triangle id."""
