@@ -170,7 +170,7 @@ int pt_render(pt_ctx* ctx, const pt_camera* cam, int32_t width, int32_t height, 
  * every call that touches what a frame in flight uses is ordered after the context's LAST ASYNCHRONOUS CALL, whichever stream that
  * call was given.  So any call of this header may follow a pt_*_device call at once, with no pt_synchronize between them.
  *   - The asynchronous calls (pt_render_device, pt_render_batch_device, pt_render_aov_device, pt_render_aov_follow_device, pt_render_aov_batch_device, pt_denoise_device,
- *     pt_denoise_batch_device, pt_denoise_var_device, pt_accum_add_device, pt_accum_denoise_device, pt_accum_reproject_device, pt_upsample_device, pt_trace_closest_device, pt_trace_occluded_device, pt_trace_surface_device, pt_render_rays_device, pt_render_aov_rays_device, pt_reduce_framebuffer) wait ON THE
+ *     pt_denoise_batch_device, pt_denoise_var_device, pt_accum_add_device, pt_accum_denoise_device, pt_accum_reproject_device, pt_upsample_device, pt_trace_closest_device, pt_trace_occluded_device, pt_trace_surface_device, pt_trace_ao_device, pt_render_rays_device, pt_render_aov_rays_device, pt_reduce_framebuffer) wait ON THE
  *     DEVICE: the stream they are given waits for an event recorded at the end of the previous asynchronous call - only if that call
  *     used another stream; on the same stream the stream's own order suffices and nothing is added.  The host returns at once, with
  *     two exceptions that existed before: a frame of another size, shard or batch length rewrites the pixel queue and a frame that
@@ -178,7 +178,7 @@ int pt_render(pt_ctx* ctx, const pt_camera* cam, int32_t width, int32_t height, 
  *     before) - both first wait on the host for the frame in flight; pt_render_batch_device and pt_render_aov_batch_device
  *     return when their per-frame tables have reached HBM, i.e. after whatever precedes them on `stream`; and a pt_accum_add_device that
  *     selects its pixels returns when the count of its active set has reached the host (see there).
- *   - The blocking renders (pt_render, pt_render_batch, pt_render_aov, pt_render_aov_follow, pt_render_aov_batch, pt_accum_add), pt_denoise, pt_denoise_batch, pt_denoise_var, pt_accum_denoise, pt_accum_reproject, pt_upsample, pt_trace_closest, pt_trace_occluded, pt_trace_surface, pt_render_rays and pt_render_aov_rays run on the context's stream behind the same device-side wait
+ *   - The blocking renders (pt_render, pt_render_batch, pt_render_aov, pt_render_aov_follow, pt_render_aov_batch, pt_accum_add), pt_denoise, pt_denoise_batch, pt_denoise_var, pt_accum_denoise, pt_accum_reproject, pt_upsample, pt_trace_closest, pt_trace_occluded, pt_trace_surface, pt_trace_ao, pt_render_rays and pt_render_aov_rays run on the context's stream behind the same device-side wait
  *     and return with the context idle.  After a blocking call, or on the context's own stream, they add no wait at all.
  *   - The calls that change or read what a frame uses WAIT ON THE HOST for the last asynchronous call's stream (if it is not the
  *     context's) and then for the context's: pt_set_materials, pt_set_environment, pt_update_vertices, pt_upload_scene,
@@ -193,7 +193,7 @@ int pt_render(pt_ctx* ctx, const pt_camera* cam, int32_t width, int32_t height, 
 int pt_render_device(pt_ctx* ctx, const pt_camera* cam, int32_t width, int32_t height, int32_t max_samples, int32_t max_path_depth,
                      void* d_out_rgb, void* d_out_rgba8, void* stream);
 /* Waits on the host for the context's last asynchronous call - pt_render_device, pt_render_batch_device, pt_render_aov_device,
- * pt_render_aov_follow_device, pt_render_aov_batch_device, pt_denoise_device, pt_denoise_batch_device, pt_denoise_var_device, pt_accum_add_device, pt_accum_denoise_device, pt_accum_reproject_device, pt_upsample_device, pt_trace_closest_device, pt_trace_occluded_device, pt_trace_surface_device, pt_render_rays_device, pt_render_aov_rays_device or pt_reduce_framebuffer, on the stream it was given - and for the context's own stream.  Every earlier asynchronous call of the context
+ * pt_render_aov_follow_device, pt_render_aov_batch_device, pt_denoise_device, pt_denoise_batch_device, pt_denoise_var_device, pt_accum_add_device, pt_accum_denoise_device, pt_accum_reproject_device, pt_upsample_device, pt_trace_closest_device, pt_trace_occluded_device, pt_trace_surface_device, pt_trace_ao_device, pt_render_rays_device, pt_render_aov_rays_device or pt_reduce_framebuffer, on the stream it was given - and for the context's own stream.  Every earlier asynchronous call of the context
  * is complete then as well, whatever stream it used: each was ordered before the next (see pt_render_device).  Returns PT_E_HIP if a
  * wave's watchdog fired during the last frame (the image is then incomplete); pt_get_stats reports the same.  PT_OK at once on an idle
  * or host-only context.  A caller's stream may be destroyed once this has returned. */
@@ -730,7 +730,8 @@ int pt_prim_to_mesh(pt_ctx* ctx, int32_t prim, int32_t* mesh, int32_t* triangle)
  * pt_trace_surface is pt_trace_closest with WHAT IS THERE stored beside the hit: the hit point, the geometric and the shading normal,
  * the texcoord, the material index, the base colour after the texture lookup and the emission - what picking, ambient occlusion and
  * baking need next, from the records the library keeps in HBM in leaf order beside the triangle the walk just tested.  A caller takes
- * p and ng / ns from this call, makes hemisphere rays of their own and sends them to pt_trace_occluded_device on the same stream.
+ * p and ng / ns from this call, makes rays of their own and sends them to pt_trace_occluded_device on the same stream; for cosine-weighted
+ * ambient occlusion that composition is built in as ONE kernel: pt_trace_ao, below.
  * Kernels of their own (csrc/pt_kernel_rays_surface.hip, csrc/pt_kernel_rays_surface_wt.hip: the closest-hit walk of the ray kernels,
  * whose lanes retire through csrc/pt_surface.h); the CPU twin is pt_debug_trace_surface_host.
  * DEFINITION, per ray (a pt_ray as above; out: a pt_surface, 80 bytes, stored as five 16-byte stores).  Arithmetic under the contract
@@ -778,6 +779,65 @@ int pt_trace_surface_device(pt_ctx* ctx, const void* d_rays, int64_t n, void* d_
  * records, material table, textures); works on a host-only context, follows "watertight", pt_set_materials and pt_update_vertices.
  * Returns n. */
 int64_t pt_debug_trace_surface_host(pt_ctx* ctx, const pt_ray* rays, int64_t n, pt_surface* out);
+
+/* ---- ray queries: ambient occlusion (no reference counterpart: the reference shoots no shadow rays) ----
+ * pt_trace_ao is pt_trace_closest with the AMBIENT OCCLUSION at the hit stored beside it: the fraction of K cosine-distributed rays
+ * from the hit point that reach `radius` unoccluded.  It is the composition pt_trace_surface -> K hemisphere rays per hit ->
+ * pt_trace_occluded in ONE kernel (csrc/pt_kernel_rays_ao.hip, csrc/pt_kernel_rays_ao_wt.hip; csrc/pt_ao.h): a lane walks its primary
+ * ray and then its own K occlusion rays without leaving the wave, and no occlusion ray is ever stored to HBM.  The CPU twin is
+ * pt_debug_trace_ao_host; kernel and twin compile the arithmetic between the walks from one header, csrc/pt_ao_math.h.
+ * DEFINITION, per ray i - its index in the caller's array (a pt_ray as above; out: a pt_ao_hit, 32 bytes, stored as two 16-byte
+ * stores).  Arithmetic under the contract of csrc/pt_device.h: binary32, no contraction, fma only where written.
+ *   1. CLOSEST HIT: exactly pt_trace_closest's - thi, the tie-break, slivers never, option "watertight".  A miss stores
+ *      {+0, +0, +0, -1}, then {+0, +0, +0, 1.0f}.
+ *   2. SURFACE: p, ng and ns are exactly pt_trace_surface's expressions.  nrm = ns under PT_AO_SHADING_NORMAL, else ng.  If nrm is
+ *      (0, 0, 0) the second half is {+0, +0, +0, 1.0f} and nothing is traced.  No material row and no texel is read.
+ *   3. FACING: nf = dot(nrm, dir) > 0.0f ? -nrm : nrm, with dir the caller's direction as given (not normalised) and dot of
+ *      pt_device.h: dot(a, b) = fma_(a.z, b.z, fma_(a.y, b.y, a.x * b.x)).
+ *   4. OCCLUSION RAYS: rng = rng_init((uint32_t)i, seed) and onb(nf, T, B), once per ray.  For k = 0 .. K-1: r1 = rng_next(rng), then
+ *      r2 = rng_next(rng); w = sample_cosine_hemisphere(r1, r2); d_k = to_world(T, B, nf, w) (all of pt_device.h).  Ray k starts at p
+ *      with NO offset - the library's fixed 1e-3 lower bound does that work, as in the render - has direction d_k and the bound
+ *      thi = radius < 1e10f ? radius : 1e10f.  It is occluded iff pt_trace_occluded of {p, thi, d_k} would store 1: a property of the
+ *      scene, not of the walk.  clear = the number of rays that are not occluded.
+ *   5. RESULT: ao = (float)clear * (1.0f / (float)K), and n = nf.
+ * CONSEQUENCES.  The first 16 bytes are pt_trace_closest's record of the ray.  With out_ao_rays from the twin, clear of ray i equals
+ * the number of zeros pt_trace_occluded returns for records i*K .. i*K+K-1 (a ray that traces nothing - a miss, a zero normal - gets K
+ * records with the empty interval tmax = +0, which nothing occludes: K zeros, ao = 1).  The stream depends on (i, seed) only, so the
+ * result does not depend on "rays_refill", "rays_grid", the grid or the slab form.  The occlusion rays of a surface point leave the
+ * hit domain stated at "validation hooks" now and then (a direction that grazes an edge below 1e-2 rad); there kernel and twin are
+ * both valid walks and may disagree on a ray, as everywhere.
+ * The call honours "watertight", "box_exact" (as pt_trace_*: only 1 selects the subtracting form), "rays_refill", "rays_grid" and
+ * pt_update_vertices.  It ignores the pixel shard, the materials and the environment, issues no collective and keeps no render state.
+ * It needs quad nodes.  The step and stack bounds of the walk apply PER WALK; a ray one of whose walks runs out is reported as a miss
+ * with ao = 1, and pt_synchronize returns PT_E_HIP.
+ * THE WALK is that of pt_trace_closest with one difference in the launch: a ray is 1 + K walks where it hits and one where it misses,
+ * so the call cuts eight times as many, shorter ranges as the other ray queries (never shorter than 64 rays; "rays_grid" caps their
+ * number as it does there) and lets the hardware balance them; the stack-overflow workspace of the context grows with the ranges.
+ * REFUSALS, ORDERING, n == 0, pt_get_stats, the bound flag behind pt_synchronize and HOST-ONLY CONTEXTS are those of pt_trace_closest /
+ * pt_trace_closest_device, word for word, with pt_ao_hit in place of pt_ray_hit (d_out 16-byte aligned).  ADDITIONALLY REFUSED with
+ * PT_E_INVALID, by name, before anything else: n_rays outside 1..4096, a flag bit other than PT_AO_SHADING_NORMAL, a radius that is not
+ * > 0 (NaN included).  pt_trace_ao_device joins the asynchronous calls at pt_render_device and the list at pt_synchronize; pt_trace_ao
+ * joins the blocking calls.
+ * NOT BUILT: a camera or ray-image form; pt_group_*, batch and communicator forms; a pt_main flag; a per-ray lower bound (the origin
+ * offset stays the library's 1e-3); stratified or low-discrepancy sampling (K independent draws of the per-ray stream). */
+#define PT_AO_SHADING_NORMAL 1
+typedef struct pt_ao_params {   /* 16 bytes */
+    int32_t  n_rays;   /* K, 1..4096 occlusion rays per hit */
+    int32_t  flags;    /* bit 0 PT_AO_SHADING_NORMAL: hemisphere about ns; 0: about ng.  Other bits must be 0 */
+    float    radius;   /* > 0: tmax of the occlusion rays in world units; +inf = the library's bound.  NaN, <= 0 refused */
+    uint32_t seed;     /* second word of the per-ray stream */
+} pt_ao_params;
+void pt_ao_default_params(pt_ao_params* p);      /* 16, 0, +inf, 0 */
+typedef struct pt_ao_hit {      /* 32 bytes, two 16-byte stores */
+    float t, u, v; int32_t prim;   /* bit for bit pt_trace_closest's record of this ray */
+    float n[3];    float ao;       /* the facing normal used; fraction of occlusion rays that were NOT occluded */
+} pt_ao_hit;
+int pt_trace_ao        (pt_ctx* ctx, const pt_ray* rays, int64_t n, const pt_ao_params* p /* NULL = defaults */, pt_ao_hit* out);
+int pt_trace_ao_device (pt_ctx* ctx, const void* d_rays, int64_t n, const pt_ao_params* p, void* d_out /* n pt_ao_hit, 16-byte aligned */, void* stream);
+/* The CPU twin: the definition above through the host walk on all host threads and csrc/pt_ao_math.h; works on a host-only context,
+ * follows "watertight" and pt_update_vertices.  out_ao_rays: NULL, or n * K pt_ray records - the occlusion rays of ray i at
+ * i*K .. i*K+K-1, as pt_trace_occluded takes them.  Returns n. */
+int64_t pt_debug_trace_ao_host(pt_ctx* ctx, const pt_ray* rays, int64_t n, const pt_ao_params* p, pt_ao_hit* out, pt_ray* out_ao_rays);
 
 /* ---- ray images: path-traced radiance along the CALLER'S rays (no reference counterpart: the reference starts every path at its one
  * pinhole camera, device.cu:231-241) ----

@@ -5,11 +5,12 @@
 // normalize, lerp3, uv_on_sphere (the polynomial atan2 / asin), tex_nearest and the material row are the functions the kernel
 // compiles, run by the CPU under the same contract (binary32, -ffp-contract=off, fma only where spelled, correctly rounded division
 // and sqrt).  What is restated here is what the kernel takes from pt_trace.h, which is device code throughout: the camera ray
-// (gen_camera_ray), interp3 and the miss branch / attribute fetch of shade_hit - each a few lines, once for both twin pixels, cited below.
+// (gen_camera_ray) and the miss branch / attribute fetch of shade_hit - each a few lines, once for both twin pixels, cited below.
 // pt_debug_aov_rays_host, the twin of the guide pass over a ray image (pt_render_aov_rays), is the follow twin with the camera ray
 // replaced by the pixel's ray record (gen_ray_from): ONE follow loop serves both.
 // pti::surface_record_host, the record of pt_debug_trace_surface_host (the twin of pt_trace_surface, pt_rays_host.cpp), sits here for
-// the same reason: it is pt_surface.h's function with these host forms of the device arithmetic.
+// the same reason: it is pt_surface.h's function with these host forms of the device arithmetic.  So does pti::ao_ray_host, one ray
+// of pt_debug_trace_ao_host (the twin of pt_trace_ao): the host walk around pt_ao_math.h, the header the kernel compiles.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -22,6 +23,7 @@ static inline float pt_host_uint_as_float(uint32_t u) { float x; std::memcpy(&x,
 #define __uint_as_float pt_host_uint_as_float
 #define PTD static inline
 #include "pt_device.h"
+#include "pt_ao_math.h"
 #undef __float_as_uint
 #undef __uint_as_float
 
@@ -32,10 +34,6 @@ using namespace ptd;
 
 namespace {
 
-v3 interp3(float bw, float bx, float by, v3 a, v3 b, v3 c) // pt_trace.h
-{
-    return V(fma_(by, c.x, fma_(bx, b.x, bw * a.x)), fma_(by, c.y, fma_(bx, b.y, bw * a.y)), fma_(by, c.z, fma_(bx, b.z, bw * a.z)));
-}
 bool finite_(float x) { return !(isinf_(x) || isnan_(x)); }
 
 struct AovScene {
@@ -120,12 +118,6 @@ AovHit fetch_hit(const AovScene& A, int32_t prim, float hu, float hv)
         h.mat.base_color = tex_nearest(tx.px.data(), tx.w, tx.h, tu, tv);
     }
     return h;
-}
-
-v3 surface_unit(v3 a) // pt_surface.h
-{
-    const v3 n = normalize(a);
-    return (finite_(n.x) && finite_(n.y) && finite_(n.z)) ? n : vs(0.0f);
 }
 
 // One pixel: include/mi355pt.h, "guide pass"; the kernel's loop body (pt_aov_kernel) line for line.
@@ -326,6 +318,41 @@ void pti::surface_record_host(const HostScene& S, int32_t slot, float t, float u
     out->ng[0] = v_ng.x; out->ng[1] = v_ng.y; out->ng[2] = v_ng.z; out->tu = tu;
     out->ns[0] = v_ns.x; out->ns[1] = v_ns.y; out->ns[2] = v_ns.z; out->tv = tv;
     out->base[0] = mat.base_color.x; out->base[1] = mat.base_color.y; out->base[2] = mat.base_color.z; out->emission = mat.emission;
+}
+
+// One ray of pt_debug_trace_ao_host (pt_rays_host.cpp): include/mi355pt.h, "ray queries: ambient occlusion", steps 1 to 5, with every
+// expression between the walks taken from pt_ao_math.h as the kernel takes it (pt_ao.h).
+void pti::ao_ray_host(const HostScene& S, const std::vector<int32_t>& slot_of, bool wt, const pt_ray& r, uint32_t index, const pt_ao_params& prm, pt_ao_hit* out,
+                      pt_ray* out_rays)
+{
+    *out = pt_ao_hit{0.0f, 0.0f, 0.0f, -1, {0.0f, 0.0f, 0.0f}, 1.0f};
+    // a ray without occlusion rays: K records that nothing occludes (an empty interval), so that the count of clear records is ao * K
+    for (int k = 0; out_rays && k < prm.n_rays; ++k) out_rays[k] = pt_ray{{0.0f, 0.0f, 0.0f}, 0.0f, {0.0f, 0.0f, 1.0f}, 0.0f};
+    const float thi0 = r.tmax < kTMax ? r.tmax : kTMax; // NaN and +inf: the library's own bound
+    float t = 0.0f, u = 0.0f, v = 0.0f;
+    int32_t prim = -1;
+    if (!pt_bvh_closest_hit_host(S.bvh, r.org, r.dir, kTMin, thi0, &t, &u, &v, &prim, wt)) return;
+    const size_t slot = (size_t)slot_of[(size_t)prim];
+    const PtTri& tr = S.bvh.tris[slot];
+    const PtShade& sh = S.shade[slot];
+    const AoSurface s = ao_surface(u, v, V(tr.p0[0], tr.p0[1], tr.p0[2]), V(tr.p1[0], tr.p1[1], tr.p1[2]), V(tr.p2[0], tr.p2[1], tr.p2[2]), V(sh.n0[0], sh.n0[1], sh.n0[2]),
+                                   V(sh.n1[0], sh.n1[1], sh.n1[2]), V(sh.n2[0], sh.n2[1], sh.n2[2]), V(r.dir[0], r.dir[1], r.dir[2]), prm.flags);
+    out->t = t; out->u = u; out->v = v; out->prim = prim;
+    out->n[0] = s.nf.x; out->n[1] = s.nf.y; out->n[2] = s.nf.z;
+    if (!s.traced) return;
+    uint32_t rng = rng_init(index, prm.seed);
+    const float thi = ao_thi(prm.radius);
+    const float org[3] = {s.p.x, s.p.y, s.p.z};
+    int clear = 0;
+    for (int k = 0; k < prm.n_rays; ++k) {
+        const v3 d = ao_direction(s.nf, rng);
+        const float dir[3] = {d.x, d.y, d.z};
+        float t2 = 0.0f, u2 = 0.0f, v2 = 0.0f;
+        int32_t prim2 = -1;
+        clear += pt_bvh_closest_hit_host(S.bvh, org, dir, kTMin, thi, &t2, &u2, &v2, &prim2, wt) ? 0 : 1;
+        if (out_rays) out_rays[k] = pt_ray{{org[0], org[1], org[2]}, thi, {dir[0], dir[1], dir[2]}, 0.0f};
+    }
+    out->ao = ao_value(clear, prm.n_rays);
 }
 
 namespace {

@@ -608,4 +608,19 @@ PTD void uv_on_sphere(v3 n, float& u, float& v) // device.cu:23-28
     v = 0.5f + asin_(n.y) / kPi;
 }
 
+// ---- the surface at a hit -----------------------------------------------------------------------
+// ONE copy for shade_hit and the guide kernels (pt_trace.h, pt_aov*.h), the surface record (pt_surface.h), ambient occlusion
+// (pt_ao_math.h) and the CPU twins.
+
+PTD v3 interp3(float bw, float bx, float by, v3 a, v3 b, v3 c)
+{
+    // (1-u-v)*a + u*b + v*c  (device.cu:59,72,86-89), evaluated as an fma chain
+    return V(fma_(by, c.x, fma_(bx, b.x, bw * a.x)), fma_(by, c.y, fma_(bx, b.y, bw * a.y)), fma_(by, c.z, fma_(bx, b.z, bw * a.z)));
+}
+PTD v3 surface_unit(v3 a) // normalize, or (0, 0, 0) where that has a component that is not finite (aov_sample's rule)
+{
+    const v3 n = normalize(a);
+    return (isinf_(n.x) || isnan_(n.x) || isinf_(n.y) || isnan_(n.y) || isinf_(n.z) || isnan_(n.z)) ? vs(0.0f) : n;
+}
+
 } // namespace ptd

@@ -228,6 +228,10 @@ PT_LOCAL int check_aov_params(pt_ctx* c, const pt_aov_params* p, const char* who
 // the surface record of pt_trace_surface at the hit (t, u, v, prim) on the triangle in leaf-order slot `slot` (< 0: the miss record), from the host
 // copies of the scene with the arithmetic of pt_device.h: csrc/pt_surface.h expression for expression (pt_debug_trace_surface_host)
 PT_LOCAL void surface_record_host(const HostScene& S, int32_t slot, float t, float u, float v, int32_t prim, pt_surface* out);
+// one ray of pt_debug_trace_ao_host: the definition of pt_trace_ao for ray `index` through the host walk and csrc/pt_ao_math.h, the
+// header the kernel compiles.  slot_of: global triangle id -> leaf-order slot; out_rays: null, or the n_rays records of this ray
+PT_LOCAL void ao_ray_host(const HostScene& S, const std::vector<int32_t>& slot_of, bool wt, const pt_ray& r, uint32_t index, const pt_ao_params& prm, pt_ao_hit* out,
+                          pt_ray* out_rays);
 // pt_comm.cpp
 PT_LOCAL int reduce_framebuffer(pt_ctx* c, void* d_rgb, void* d_rgba8, int64_t n_pixels, hipStream_t stream); // pt_reduce_framebuffer inside a call that is ordered already
 PT_LOCAL int reduce_sum(pt_ctx* c, void* d_buf, size_t n_floats, hipStream_t stream); // in-place sum-reduce onto rank 0; nothing without a communicator

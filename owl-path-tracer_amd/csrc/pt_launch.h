@@ -78,6 +78,14 @@ struct PtRaysArgs {
     int32_t cap;       // stack levels a lane may use (stack bound + the three pushes of a step)
     int32_t refill;    // option "rays_refill", 0..63: idle lanes take new rays when at most this many lanes are still walking
 };
+// Ambient occlusion (pt_trace_ao; pt_ao.h): the ray kernels' arguments (r.out: n pt_ao_hit of 32 bytes, 16-byte aligned) and pt_ao_params
+struct PtAoArgs {
+    PtRaysArgs r;
+    int32_t n_rays;    // K, 1..4096 occlusion rays per hit
+    int32_t flags;     // PT_AO_SHADING_NORMAL
+    float thi;         // the occlusion rays' bound: radius < 1e10f ? radius : 1e10f, formed on the host
+    uint32_t seed;     // second word of rng_init(ray index, seed)
+};
 
 // Denoiser (pt_denoise; pt_denoise.hip): what its three kernels take.  The host fills everything but the record pointers, which
 // pt_launch_denoise carves out of ws; the constants are include/mi355pt.h's "host constants" (pti::denoise_constants).
@@ -251,6 +259,11 @@ hipError_t pt_launch_rays_surface(const PtKernelParams* p, const PtRaysArgs* a, 
 hipError_t pt_rays_surface_geometry(int occluded, int exact, PtGeometry* g);
 hipError_t pt_launch_rays_surface_wt(const PtKernelParams* p, const PtRaysArgs* a, int occluded, int grid, size_t lds_bytes, hipStream_t stream);
 hipError_t pt_rays_surface_geometry_wt(int occluded, int exact, PtGeometry* g);
+// pt_kernel_rays_ao.hip / pt_kernel_rays_ao_wt.hip: the fused ambient-occlusion kernels (pt_trace_ao; pt_ao.h), same conventions
+hipError_t pt_launch_rays_ao(const PtKernelParams* p, const PtAoArgs* a, int grid, size_t lds_bytes, hipStream_t stream);
+hipError_t pt_rays_ao_geometry(int exact, PtGeometry* g);
+hipError_t pt_launch_rays_ao_wt(const PtKernelParams* p, const PtAoArgs* a, int grid, size_t lds_bytes, hipStream_t stream);
+hipError_t pt_rays_ao_geometry_wt(int exact, PtGeometry* g);
 // pt_kernel_aov_follow.hip / pt_kernel_aov_follow_wt.hip: the follow kernels, same conventions; lds_bytes covers the stack and the state a lane parks behind it
 hipError_t pt_launch_aov_follow(const PtKernelParams* p, const PtAovFollowArgs* a, int binary, int grid, size_t lds_bytes, hipStream_t stream);
 hipError_t pt_aov_follow_geometry(int binary, int exact, int stack_entries, PtGeometry* g);

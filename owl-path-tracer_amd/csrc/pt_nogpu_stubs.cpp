@@ -44,6 +44,10 @@ hipError_t pt_launch_rays_surface(const PtKernelParams*, const PtRaysArgs*, int,
 hipError_t pt_rays_surface_geometry(int, int, PtGeometry*) { return hipErrorNotSupported; }
 hipError_t pt_launch_rays_surface_wt(const PtKernelParams*, const PtRaysArgs*, int, int, size_t, hipStream_t) { return hipErrorNotSupported; }
 hipError_t pt_rays_surface_geometry_wt(int, int, PtGeometry*) { return hipErrorNotSupported; }
+hipError_t pt_launch_rays_ao(const PtKernelParams*, const PtAoArgs*, int, size_t, hipStream_t) { return hipErrorNotSupported; }
+hipError_t pt_rays_ao_geometry(int, PtGeometry*) { return hipErrorNotSupported; }
+hipError_t pt_launch_rays_ao_wt(const PtKernelParams*, const PtAoArgs*, int, size_t, hipStream_t) { return hipErrorNotSupported; }
+hipError_t pt_rays_ao_geometry_wt(int, PtGeometry*) { return hipErrorNotSupported; }
 size_t pt_denoise_workspace_bytes(int, int) { return 16; }
 hipError_t pt_denoise_geometry(int, int, PtGeometry*, int*) { return hipErrorNotSupported; }
 hipError_t pt_launch_denoise(const PtDenoiseArgs*, hipStream_t) { return hipErrorNotSupported; }

@@ -1,5 +1,6 @@
-// pt_rays_host.cpp -- ray queries on the caller's rays (pt_trace_closest*, pt_trace_occluded*, pt_trace_surface*): ONE device path behind
-// the asynchronous and blocking entry points, the CPU twins pt_debug_trace_rays_host and pt_debug_trace_surface_host, and pt_prim_to_mesh.
+// pt_rays_host.cpp -- ray queries on the caller's rays (pt_trace_closest*, pt_trace_occluded*, pt_trace_surface*, pt_trace_ao*): ONE device
+// path behind the asynchronous and blocking entry points, the CPU twins pt_debug_trace_rays_host, pt_debug_trace_surface_host and
+// pt_debug_trace_ao_host, and pt_prim_to_mesh.
 // The pass reads the scene and nothing of a frame: no pixel queue, no shard, no environment, no collective - and no materials or
 // textures either, except in surface mode, which reads the hit's material row and texel (fill_params: the current table).  Its own
 // buffers are d_rays_in / d_rays_out (the blocking forms' staging); the waves' stack overflow columns and the bound flag are the guide
@@ -15,20 +16,39 @@ using namespace pti;
 
 namespace {
 
+#ifndef PT_AO_RANGES
+#define PT_AO_RANGES 8 // ranges per resident wave of the ambient-occlusion launch (rays_device); 1 / 2 / 4 / 8 / 16 measured (README.md)
+#endif
 constexpr float kRayTMin = 1e-3f, kRayTMax = 1e10f; // kTMin, kTMax of pt_device.h
 
 static_assert(sizeof(pt_ray) == 32 && sizeof(pt_ray_hit) == 16, "the ray kernels read a ray as two 16-byte loads and store a hit as one");
 static_assert(sizeof(pt_surface) == 80, "the surface instances store a record as five 16-byte stores");
+static_assert(sizeof(pt_ao_hit) == 32 && sizeof(pt_ao_params) == 16, "the ambient-occlusion kernel stores a record as two 16-byte stores");
 
-// What a call stores per ray: a pt_ray_hit, a byte, or a pt_surface.
-enum RaysMode { kClosest = 0, kOccluded = 1, kSurface = 2 };
-constexpr size_t kRecordBytes[3] = {sizeof(pt_ray_hit), 1, sizeof(pt_surface)};
+// What a call stores per ray: a pt_ray_hit, a byte, a pt_surface, or a pt_ao_hit.
+enum RaysMode { kClosest = 0, kOccluded = 1, kSurface = 2, kAo = 3 };
+constexpr size_t kRecordBytes[4] = {sizeof(pt_ray_hit), 1, sizeof(pt_surface), sizeof(pt_ao_hit)};
 
 const struct RaysInstance {
     hipError_t (*geometry)(int occluded, int exact, PtGeometry* g);
     hipError_t (*launch)(const PtKernelParams* p, const PtRaysArgs* a, int occluded, int grid, size_t lds_bytes, hipStream_t stream);
 } kRaysInstance[2][2] = {{{pt_rays_geometry, pt_launch_rays}, {pt_rays_geometry_wt, pt_launch_rays_wt}},
                          {{pt_rays_surface_geometry, pt_launch_rays_surface}, {pt_rays_surface_geometry_wt, pt_launch_rays_surface_wt}}}; // by [surface][watertight]
+const struct AoInstance {
+    hipError_t (*geometry)(int exact, PtGeometry* g);
+    hipError_t (*launch)(const PtKernelParams* p, const PtAoArgs* a, int grid, size_t lds_bytes, hipStream_t stream);
+} kAoInstance[2] = {{pt_rays_ao_geometry, pt_launch_rays_ao}, {pt_rays_ao_geometry_wt, pt_launch_rays_ao_wt}}; // by [watertight]
+
+// What pt_trace_ao, its device form and the twin refuse beside the ray queries' refusals; *eff = the parameters in effect.
+int check_ao_params(pt_ctx* c, const char* who, const pt_ao_params* p, pt_ao_params* eff)
+{
+    if (p) *eff = *p;
+    else pt_ao_default_params(eff);
+    if (eff->n_rays < 1 || eff->n_rays > 4096) return fail(c, PT_E_INVALID, "%s: n_rays %d outside 1..4096", who, eff->n_rays);
+    if (eff->flags & ~PT_AO_SHADING_NORMAL) return fail(c, PT_E_INVALID, "%s: unknown flags 0x%x (PT_AO_SHADING_NORMAL is the only one)", who, (unsigned)eff->flags);
+    if (!(eff->radius > 0.0f)) return fail(c, PT_E_INVALID, "%s: radius %g must be > 0 (+inf: the library's bound)", who, (double)eff->radius);
+    return PT_OK;
+}
 
 // What every form refuses before anything is touched, a host-only context last (who: the entry point).
 int check_rays_args(pt_ctx* c, const char* who, const void* rays, int64_t n, const void* out, bool device, RaysMode mode)
@@ -37,7 +57,7 @@ int check_rays_args(pt_ctx* c, const char* who, const void* rays, int64_t n, con
     if (n > 0 && (!rays || !out)) return fail(c, PT_E_INVALID, "%s: NULL %s", who, !rays ? (device ? "d_rays" : "rays") : (device ? "d_out" : "out"));
     if (device && n > 0 && ((uintptr_t)rays & 15u)) return fail(c, PT_E_INVALID, "%s: d_rays is not 16-byte aligned (a ray is two 16-byte loads)", who);
     if (device && mode != kOccluded && n > 0 && ((uintptr_t)out & 15u))
-        return fail(c, PT_E_INVALID, "%s: d_out is not 16-byte aligned (a %s)", who, mode == kSurface ? "surface record is five 16-byte stores of its 80 bytes" : "hit is one 16-byte store");
+        return fail(c, PT_E_INVALID, "%s: d_out is not 16-byte aligned (a %s)", who, mode == kSurface ? "surface record is five 16-byte stores of its 80 bytes" : mode == kAo ? "record is two 16-byte stores" : "hit is one 16-byte store");
     if (!c->have_scene) return fail(c, PT_E_NO_SCENE, "%s: no geometries (pt_upload_scene not called)", who);
     // the ray kernels walk the quad nodes - or a root that is itself a leaf - and nothing else
     if (!quad_walk_available(c))
@@ -47,7 +67,8 @@ int check_rays_args(pt_ctx* c, const char* who, const void* rays, int64_t n, con
 
 // One launch of the ray kernel over n >= 1 rays in HBM.  A wave owns a contiguous range of whole 64-ray blocks; the grid is what the
 // occupancy query says is resident, or fewer when there are fewer blocks.
-int rays_device(pt_ctx* c, RaysMode mode, const void* d_rays, int64_t n, void* d_out, hipStream_t stream)
+// ao: the parameters in effect of an ambient-occlusion call (mode kAo), else null.
+int rays_device(pt_ctx* c, RaysMode mode, const void* d_rays, int64_t n, void* d_out, hipStream_t stream, const pt_ao_params* ao = nullptr)
 {
     int rc;
     if ((rc = check_quad_walk_size(c, "ray"))) return rc;
@@ -56,19 +77,26 @@ int rays_device(pt_ctx* c, RaysMode mode, const void* d_rays, int64_t n, void* d
     P.box_exact = c->opt.box_exact > 0 ? 1 : 0;
     quad_walk_params(c, P);
     const RaysInstance& inst = kRaysInstance[mode == kSurface][c->opt.watertight != 0];
+    const AoInstance& ao_inst = kAoInstance[c->opt.watertight != 0];
     const int occluded = mode == kOccluded;
     PtGeometry g{};
-    const hipError_t ge = inst.geometry(occluded, P.box_exact, &g);
+    const hipError_t ge = mode == kAo ? ao_inst.geometry(P.box_exact, &g) : inst.geometry(occluded, P.box_exact, &g);
     if (ge == hipErrorInvalidConfiguration) return fail(c, PT_E_LIMIT, "this build of the ray kernel spills registers to scratch; such builds are refused (pt_kernel.hip)");
     HIP_TRY(c, ge);
     if (g.max_blocks_per_cu < 1) return fail(c, PT_E_LIMIT, "ray kernel does not fit a CU (LDS %zu bytes)", g.lds_bytes);
     const int64_t n_blocks = (n + 63) / 64;
     int64_t resident = (int64_t)c->num_cus * g.max_blocks_per_cu;
+    // Ambient occlusion: a ray is 1 + K walks where it hits and one where it misses, so ranges of equal length are not equal work, and
+    // with one range per resident wave the launch lasts as long as its all-hit ranges (2 M primary rays of the C4 stand-in, K = 16: 2.5
+    // Grays/s).  PT_AO_RANGES times as many, shorter ranges: the hardware hands the later ones to the waves that finish early (8: 6.3
+    // Grays/s, one 64-ray block per wave there; 16 is the same launch).  The price is the workspace: an overflow column per range.
+    if (mode == kAo) resident *= PT_AO_RANGES;
     if (c->opt.rays_grid > 0) resident = std::min<int64_t>(resident, c->opt.rays_grid); // option "rays_grid": fewer, longer ranges (tests, tuning)
     const int64_t blocks_per_wave = (n_blocks + resident - 1) / resident;
     const int grid = (int)((n_blocks + blocks_per_wave - 1) / blocks_per_wave);
     if (blocks_per_wave * 64 > 0x7fffffc0ll) return fail(c, PT_E_LIMIT, "ray kernel: %lld rays per wave", (long long)blocks_per_wave * 64);
-    PtRaysArgs A{};
+    PtAoArgs AA{};
+    PtRaysArgs& A = AA.r;
     A.cap = P.stack_entries + 3;
     if ((rc = walk_workspace(c, A.cap, g.lds_levels, grid, stream, P, &A.ovf))) return rc;
     P.lds_levels = g.lds_levels;
@@ -78,28 +106,40 @@ int rays_device(pt_ctx* c, RaysMode mode, const void* d_rays, int64_t n, void* d
     A.per_wave = (int32_t)(blocks_per_wave * 64);
     A.refill = c->opt.rays_refill;
     HIP_TRY(c, hipEventRecord(c->ev0, stream));
-    HIP_TRY(c, inst.launch(&P, &A, occluded, grid, g.lds_bytes, stream));
+    if (mode == kAo) {
+        AA.n_rays = ao->n_rays;
+        AA.flags = ao->flags;
+        AA.thi = ao->radius < kRayTMax ? ao->radius : kRayTMax; // ao_thi of pt_ao_math.h: +inf gives the library's bound
+        AA.seed = ao->seed;
+        HIP_TRY(c, ao_inst.launch(&P, &AA, grid, g.lds_bytes, stream));
+    } else {
+        HIP_TRY(c, inst.launch(&P, &A, occluded, grid, g.lds_bytes, stream));
+    }
     HIP_TRY(c, hipEventRecord(c->ev1, stream));
     note_pass(c, (int)std::min<int64_t>(n, 0x7fffffff), 1, 1, grid, g, P.stack_entries, true);
     return PT_OK;
 }
 
-int rays_async(pt_ctx* c, const char* who, RaysMode mode, const void* d_rays, int64_t n, void* d_out, void* stream_v)
+int rays_async(pt_ctx* c, const char* who, RaysMode mode, const void* d_rays, int64_t n, void* d_out, void* stream_v, const pt_ao_params* ao = nullptr)
 {
     if (!c) return PT_E_INVALID;
     int rc;
+    pt_ao_params prm{};
+    if (mode == kAo && (rc = check_ao_params(c, who, ao, &prm))) return rc;
     if ((rc = check_rays_args(c, who, d_rays, n, d_out, true, mode))) return rc;
     if (n == 0) return PT_OK;
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t stream = stream_v ? (hipStream_t)stream_v : c->stream;
-    return async_call(c, stream, [&] { return rays_device(c, mode, d_rays, n, d_out, stream); });
+    return async_call(c, stream, [&] { return rays_device(c, mode, d_rays, n, d_out, stream, &prm); });
 }
 
 // Host buffers: the rays staged in d_rays_in, the results in d_rays_out, and back.
-int rays_blocking(pt_ctx* c, const char* who, RaysMode mode, const pt_ray* rays, int64_t n, void* out)
+int rays_blocking(pt_ctx* c, const char* who, RaysMode mode, const pt_ray* rays, int64_t n, void* out, const pt_ao_params* ao = nullptr)
 {
     if (!c) return PT_E_INVALID;
     int rc;
+    pt_ao_params prm{};
+    if (mode == kAo && (rc = check_ao_params(c, who, ao, &prm))) return rc;
     if ((rc = check_rays_args(c, who, rays, n, out, false, mode))) return rc;
     if (n == 0) return PT_OK;
     HIP_TRY(c, hipSetDevice(c->device));
@@ -108,7 +148,7 @@ int rays_blocking(pt_ctx* c, const char* who, RaysMode mode, const pt_ray* rays,
         int rc2;
         if ((rc2 = ensure(c, c->d_rays_in, (size_t)n * sizeof(pt_ray))) || (rc2 = ensure(c, c->d_rays_out, out_bytes))) return rc2;
         HIP_TRY(c, hipMemcpyAsync(c->d_rays_in.p, rays, (size_t)n * sizeof(pt_ray), hipMemcpyHostToDevice, c->stream));
-        if ((rc2 = rays_device(c, mode, c->d_rays_in.p, n, c->d_rays_out.p, c->stream))) return rc2;
+        if ((rc2 = rays_device(c, mode, c->d_rays_in.p, n, c->d_rays_out.p, c->stream, &prm))) return rc2;
         return drain(c, {{out, c->d_rays_out.p, out_bytes}});
     });
 }
@@ -123,6 +163,17 @@ int pt_trace_closest_device(pt_ctx* c, const void* d_rays, int64_t n, void* d_ou
 int pt_trace_occluded_device(pt_ctx* c, const void* d_rays, int64_t n, void* d_out, void* stream) { return rays_async(c, "pt_trace_occluded_device", kOccluded, d_rays, n, d_out, stream); }
 int pt_trace_surface(pt_ctx* c, const pt_ray* rays, int64_t n, pt_surface* out) { return rays_blocking(c, "pt_trace_surface", kSurface, rays, n, out); }
 int pt_trace_surface_device(pt_ctx* c, const void* d_rays, int64_t n, void* d_out, void* stream) { return rays_async(c, "pt_trace_surface_device", kSurface, d_rays, n, d_out, stream); }
+int pt_trace_ao(pt_ctx* c, const pt_ray* rays, int64_t n, const pt_ao_params* p, pt_ao_hit* out) { return rays_blocking(c, "pt_trace_ao", kAo, rays, n, out, p); }
+int pt_trace_ao_device(pt_ctx* c, const void* d_rays, int64_t n, const pt_ao_params* p, void* d_out, void* stream) { return rays_async(c, "pt_trace_ao_device", kAo, d_rays, n, d_out, stream, p); }
+
+void pt_ao_default_params(pt_ao_params* p)
+{
+    if (!p) return;
+    p->n_rays = 16;
+    p->flags = 0;
+    p->radius = __builtin_inff();
+    p->seed = 0u;
+}
 
 int64_t pt_debug_trace_rays_host(pt_ctx* c, const pt_ray* rays, int64_t n, int32_t occluded, void* out)
 {
@@ -169,6 +220,28 @@ int64_t pt_debug_trace_surface_host(pt_ctx* c, const pt_ray* rays, int64_t n, pt
             const bool hit = pt_bvh_closest_hit_host(c->scene.bvh, r.org, r.dir, kRayTMin, thi, &t, &u, &v, &prim, wt);
             surface_record_host(c->scene, hit ? slot_of[(size_t)prim] : -1, t, u, v, prim, &out[i]);
         }
+    });
+    return n;
+}
+
+int64_t pt_debug_trace_ao_host(pt_ctx* c, const pt_ray* rays, int64_t n, const pt_ao_params* p, pt_ao_hit* out, pt_ray* out_ao_rays)
+{
+    if (!c) return PT_E_INVALID;
+    int rc;
+    pt_ao_params prm{};
+    if ((rc = check_ao_params(c, "pt_debug_trace_ao_host", p, &prm))) return rc;
+    if (n < 0 || n >= ((int64_t)1 << 31)) return fail(c, PT_E_INVALID, "pt_debug_trace_ao_host: n = %lld rays (0 .. 2^31 - 1)", (long long)n);
+    if (n > 0 && (!rays || !out)) return fail(c, PT_E_INVALID, "pt_debug_trace_ao_host: NULL %s", !rays ? "rays" : "out");
+    if (!c->have_scene) return fail(c, PT_E_NO_SCENE, "pt_debug_trace_ao_host: no geometries (pt_upload_scene not called)");
+    sync_host_scene(c);
+    const bool wt = c->opt.watertight != 0;
+    std::vector<int32_t> slot_of((size_t)c->scene.n_triangles, -1); // global triangle id -> leaf-order slot, as pt_debug_trace_surface_host
+    for (size_t s = 0; s < c->scene.bvh.tris.size(); ++s) {
+        const int32_t id = c->scene.bvh.tris[s].id;
+        if (id >= 0 && (size_t)id < slot_of.size()) slot_of[(size_t)id] = (int32_t)s;
+    }
+    pt_parallel_ranges((size_t)n, [&](size_t lo, size_t hi) {
+        for (size_t i = lo; i < hi; ++i) ao_ray_host(c->scene, slot_of, wt, rays[i], (uint32_t)i, prm, &out[i], out_ao_rays ? out_ao_rays + i * (size_t)prm.n_rays : nullptr);
     });
     return n;
 }

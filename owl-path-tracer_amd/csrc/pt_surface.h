@@ -31,11 +31,11 @@ struct SurfaceRecord {
     f32x4 ns;   // {shading normal, texcoord v}
     f32x4 base; // {base colour after the texture lookup, emission}
 };
-__device__ __forceinline__ v3 surface_unit(v3 a) // normalize, or (0, 0, 0) where that has a component that is not finite (aov_sample's rule)
-{
-    const v3 n = normalize(a);
-    return (isinf_(n.x) || isnan_(n.x) || isinf_(n.y) || isnan_(n.y) || isinf_(n.z) || isnan_(n.z)) ? vs(0.0f) : n;
-}
+// surface_unit(a):
+//     normalize, or (0, 0, 0) where that has a component that is not finite (aov_sample's rule),
+// is pt_device.h's ("the surface at a hit"), shared with ambient occlusion (pt_ao_math.h) and the
+// CPU twins.  (This note takes the lines the function took: pt_rays_kernels.h, which includes
+// this header in surface mode, keeps its kernel on its source line.)
 // slot < 0: a miss.  (u, v, t, id) are the walk's Hit; slot is its leaf-order index, which serves PtTri and PtShade alike.
 __device__ __forceinline__ SurfaceRecord surface_record(const PtKernelParams& P, int slot, float u, float v, float t, int id)
 {

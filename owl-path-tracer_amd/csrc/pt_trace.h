@@ -534,11 +534,11 @@ __device__ __forceinline__ void closest_hit(const PtKernelParams& P, uint32_t* s
     }
 }
 
-__device__ __forceinline__ v3 interp3(float bw, float bx, float by, v3 a, v3 b, v3 c)
-{
-    // (1-u-v)*a + u*b + v*c  (device.cu:59,72,86-89), evaluated as an fma chain
-    return V(fma_(by, c.x, fma_(bx, b.x, bw * a.x)), fma_(by, c.y, fma_(bx, b.y, bw * a.y)), fma_(by, c.z, fma_(bx, b.z, bw * a.z)));
-}
+// interp3(bw, bx, by, a, b, c), the interpolation of a vertex attribute at a hit:
+//     (1-u-v)*a + u*b + v*c  (device.cu:59,72,86-89), evaluated as an fma chain,
+// is pt_device.h's ("the surface at a hit"), so that the CPU twins run the copy the kernels compile.
+// (This note takes the lines the function took: the resource reports name kernels by
+// source line, and the headers that hold kernels include this one.)
 
 struct PathState {
     uint32_t rng;

@@ -74,6 +74,11 @@ class AovParams(C.Structure):
     _fields_ = [("n_samples", C.c_int32), ("max_follow", C.c_int32), ("roughness_max", C.c_float), ("reserved", C.c_int32)]
 
 
+class AoParams(C.Structure):
+    """pt_ao_params: n_rays (K, 1..4096 occlusion rays per hit), flags (PT_AO_SHADING_NORMAL), radius (> 0; +inf: the library's bound), seed."""
+    _fields_ = [("n_rays", C.c_int32), ("flags", C.c_int32), ("radius", C.c_float), ("seed", C.c_uint32)]
+
+
 class AccumParams(C.Structure):
     """pt_accum_params: n_samples (1..65535) for every active pixel, max_pixel_samples (0: no cap), noise_threshold (0: uniform add), reserved (0)."""
     _fields_ = [("n_samples", C.c_int32), ("max_pixel_samples", C.c_int32), ("noise_threshold", C.c_float), ("reserved", C.c_int32)]
@@ -133,6 +138,7 @@ EXPORTS = ["pt_create", "pt_destroy", "pt_last_error", "pt_abi_version", "pt_upl
            "pt_accum_reproject_default_params", "pt_accum_reproject", "pt_accum_reproject_device", "pt_debug_accum_reproject_host",
            "pt_upsample_default_params", "pt_upsample", "pt_upsample_device", "pt_debug_upsample_host",
            "pt_trace_closest", "pt_trace_closest_device", "pt_trace_occluded", "pt_trace_occluded_device", "pt_debug_trace_rays_host", "pt_prim_to_mesh", "pt_trace_surface", "pt_trace_surface_device", "pt_debug_trace_surface_host",
+           "pt_ao_default_params", "pt_trace_ao", "pt_trace_ao_device", "pt_debug_trace_ao_host",
            "pt_render_rays", "pt_render_rays_device", "pt_render_aov_rays", "pt_render_aov_rays_device", "pt_debug_aov_rays_host"]
 # pt_ray / pt_ray_hit (include/mi355pt.h "ray queries"): 32 and 16 bytes
 RAY_DTYPE = np.dtype([("org", "<f4", (3,)), ("tmax", "<f4"), ("dir", "<f4", (3,)), ("unused", "<f4")])
@@ -142,6 +148,10 @@ assert RAY_DTYPE.itemsize == 32 and HIT_DTYPE.itemsize == 16
 SURFACE_DTYPE = np.dtype([("t", "<f4"), ("u", "<f4"), ("v", "<f4"), ("prim", "<i4"), ("p", "<f4", (3,)), ("material", "<i4"), ("ng", "<f4", (3,)), ("tu", "<f4"),
                           ("ns", "<f4", (3,)), ("tv", "<f4"), ("base", "<f4", (3,)), ("emission", "<f4")])
 assert SURFACE_DTYPE.itemsize == 80
+# pt_ao_hit (include/mi355pt.h "ray queries: ambient occlusion"): pt_trace_closest's record, then the facing normal and the occlusion
+AO_DTYPE = np.dtype([("t", "<f4"), ("u", "<f4"), ("v", "<f4"), ("prim", "<i4"), ("n", "<f4", (3,)), ("ao", "<f4")])
+assert AO_DTYPE.itemsize == 32 and C.sizeof(AoParams) == 16
+PT_AO_SHADING_NORMAL = 1
 # pt_ray_gen (include/mi355pt.h "ray images"): 64 bytes; pyhost/ray_image.py builds tables of these
 RAY_GEN_DTYPE = np.dtype([("org", "<f4", (3,)), ("reserved0", "<f4"), ("dir", "<f4", (3,)), ("reserved1", "<f4"),
                           ("du", "<f4", (3,)), ("reserved2", "<f4"), ("dv", "<f4", (3,)), ("reserved3", "<f4")])
@@ -304,6 +314,12 @@ def lib():
     L.pt_trace_surface_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     L.pt_debug_trace_surface_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     L.pt_debug_trace_surface_host.restype = C.c_int64
+    L.pt_ao_default_params.argtypes = [C.POINTER(AoParams)]
+    L.pt_ao_default_params.restype = None
+    L.pt_trace_ao.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(AoParams), C.c_void_p]
+    L.pt_trace_ao_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(AoParams), C.c_void_p, C.c_void_p]
+    L.pt_debug_trace_ao_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(AoParams), C.c_void_p, C.c_void_p]
+    L.pt_debug_trace_ao_host.restype = C.c_int64
     L.pt_render_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, fp, C.POINTER(C.c_uint32)]
     L.pt_render_rays_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     L.pt_render_aov_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(AovParams), fp]
@@ -443,6 +459,17 @@ def aov_default_params(**changes):
     lib().pt_aov_default_params(C.byref(p))
     for k, v in changes.items():
         if k not in dict(AovParams._fields_):
+            raise KeyError(k)
+        setattr(p, k, v)
+    return p
+
+
+def ao_default_params(**changes):
+    """pt_ao_default_params (16 rays, hemisphere about the geometric normal, radius +inf, seed 0), with the given fields changed."""
+    p = AoParams()
+    lib().pt_ao_default_params(C.byref(p))
+    for k, v in changes.items():
+        if k not in dict(AoParams._fields_):
             raise KeyError(k)
         setattr(p, k, v)
     return p
@@ -1057,6 +1084,30 @@ class Context:
     def trace_surface_device(self, d_rays, n, d_out, stream=None):
         """pt_trace_surface_device: asynchronous as trace_closest_device, n pt_surface records (80 bytes each) left at d_out (16-byte aligned)."""
         self._check(lib().pt_trace_surface_device(self._h, C.c_void_p(d_rays), int(n), C.c_void_p(d_out), C.c_void_p(stream) if stream else None), "pt_trace_surface_device")
+
+    def trace_ao(self, rays, params=None):
+        """pt_trace_ao: trace_closest with the ambient occlusion at the hit, as an AO_DTYPE array (32 bytes per ray: the hit record, the
+        facing normal, the fraction of the K occlusion rays that were not occluded).  params: an AoParams, None = the defaults."""
+        return self._trace(lib().pt_trace_ao, "pt_trace_ao", rays, False, (C.byref(params) if params is not None else None,), dtype=AO_DTYPE)
+
+    def trace_ao_host(self, rays, params=None, return_rays=False):
+        """pt_debug_trace_ao_host, the CPU twin of trace_ao (works on a host-only context).  return_rays: also the occlusion rays, an
+        (n, K) RAY_DTYPE array as trace_occluded takes them (a ray that traced none: K records that nothing occludes)."""
+        r = _rays(rays)
+        out = np.empty(r.shape[0], AO_DTYPE)
+        ao_rays = None
+        if return_rays:
+            dflt = ao_default_params()
+            ao_rays = np.empty((r.shape[0], int(params.n_rays if params is not None else dflt.n_rays)), RAY_DTYPE)
+        rc = lib().pt_debug_trace_ao_host(self._h, r.ctypes.data_as(C.c_void_p), r.shape[0], C.byref(params) if params is not None else None,
+                                          out.ctypes.data_as(C.c_void_p), ao_rays.ctypes.data_as(C.c_void_p) if ao_rays is not None and ao_rays.size else None)
+        self._check(int(rc), "pt_debug_trace_ao_host")
+        return (out, ao_rays) if return_rays else out
+
+    def trace_ao_device(self, d_rays, n, d_out, params=None, stream=None):
+        """pt_trace_ao_device: asynchronous as trace_closest_device, n pt_ao_hit records (32 bytes each) left at d_out (16-byte aligned)."""
+        self._check(lib().pt_trace_ao_device(self._h, C.c_void_p(d_rays), int(n), C.byref(params) if params is not None else None, C.c_void_p(d_out),
+                                             C.c_void_p(stream) if stream else None), "pt_trace_ao_device")
 
     def prim_to_mesh(self, prim):
         """pt_prim_to_mesh: (entity of the upload, triangle inside it) of a global triangle id."""
