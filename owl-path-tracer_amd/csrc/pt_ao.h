@@ -1,8 +1,8 @@
 // pt_ao.h -- the fused ambient-occlusion kernel of pt_trace_ao (include/mi355pt.h, "ray queries: ambient occlusion").  Translation units
 // of their own - pt_kernel_rays_ao.hip and, with PT_WATERTIGHT = 1, pt_kernel_rays_ao_wt.hip include this header - so that every other
 // `make asm-*` target goes on listing the kernels it listed; pt_rays_kernels.h is not touched.  Two instances per unit (EXACT 0 / 1).
-// The kernel is the persistent loop of pt_rays_kernels.h - ray_inv -> node4_step<PT_WAVE, PT_LDS_STACK> -> leaf_test -> stack_pop, a
-// wave owning a contiguous range of rays and refilling its idle lanes from it - with ONE more piece of per-lane state, the phase `k`:
+// The kernel is the persistent loop of pt_ray_range.h around quad_walk_step (pt_trace.h), as the ray kernels of pt_rays_kernels.h are -
+// a wave owning a contiguous range of rays and refilling its idle lanes from it - with ONE more piece of per-lane state, the phase `k`:
 //   k == AO_PRIMARY  the lane walks the caller's ray to its closest hit (the closest-hit instance's walk, step for step);
 //   k >= 0           the lane walks its k-th occlusion ray: origin p, direction ao_direction(nf, rng), bound A.thi; the any-hit exit
 //                    applies (a run-time test of k, not a template parameter: both kinds of lane sit in one wave);
@@ -14,12 +14,12 @@
 // occlusion phase holds a ray (ray >= 0) and so counts as walking for the refill ballot.
 // The frame (T, B) of the hemisphere is recomputed from nf per occlusion ray (ao_direction): six registers fewer in the walk than
 // keeping it, a normalize and a cross more per K-th of a walk, and the same bits.
-// TERMINATION: as pt_rays_kernels.h's, with `steps` and the stack bound applying PER WALK (both are reset when a walk starts); a lane
-// that holds a ray either takes a step of a walk or ends one, a ray has 1 + K <= 4097 walks, and an overrun retires it at once.
+// TERMINATION: pt_ray_range.h's argument, with `steps` and the stack bound applying PER WALK (both are reset when a walk starts); a
+// lane that holds a ray either takes a step of a walk or ends one, a ray has 1 + K <= 4097 walks, and an overrun retires it at once.
 #pragma once
 #include "pt_ao_math.h"
 #include "pt_instance.h"
-#include "pt_trace.h"
+#include "pt_ray_range.h"
 #if PT_WATERTIGHT
 #define PT_AO_KERNEL pt_rays_ao_wt_kernel
 #define PT_AO_LAUNCH pt_launch_rays_ao_wt
@@ -44,58 +44,25 @@ __global__ void __launch_bounds__(PT_WAVE, PT_AO_WAVES_PER_EU) PT_AO_KERNEL(cons
     uint32_t PT_AS1* ovf = gp(A.r.ovf) + (size_t)blockIdx.x * ((size_t)ovf_levels * PT_WAVE) + lane;
     const PtNode4* __restrict__ nodes4 = P.nodes4;
     const PtTri* __restrict__ tris = P.tris;
-    const long long first = (long long)blockIdx.x * A.r.per_wave; // < n: the launcher refuses a grid with an empty range
-    const int end = (int)(first + A.r.per_wave < (long long)A.r.n ? first + A.r.per_wave : (long long)A.r.n);
-    int next = (int)first;
+    RayRange R = ray_range(A.r);
     int ray = -1, cur = PT_DONE, sp = 0, steps = 0; // ray < 0: the lane is idle
     int k = AO_PRIMARY, clear = 0;
     uint32_t rng = 0u;
     v3 o = vs(0.0f), d = vs(0.0f), inv = vs(0.0f), nf = vs(0.0f);
     f32x4 first_hit = {0.0f, 0.0f, 0.0f, 0.0f}; // the closest hit's record, kept through the occlusion phase
     Hit h;
-    h.t = 0.0f; h.u = 0.0f; h.v = 0.0f; h.id = 0x7fffffff; h.slot = -1;
-    for (;;) {
-        const unsigned long long m_idle = __ballot(ray < 0);
-        const int n_idle = popc64(m_idle);
-        if (next < end) {
-            if (PT_WAVE - n_idle <= A.r.refill) {
-                const long long i = (long long)next + rank_in(m_idle); // (64-bit: next may be within 63 of 2^31 - 1)
-                if (ray < 0 && i < (long long)end) {
-                    const f32x4 r0 = ldg4(A.r.rays, (size_t)(uint32_t)i * 32), r1 = ldg4(A.r.rays, (size_t)(uint32_t)i * 32 + 16); // {org, tmax}, {dir, not read}
-                    o = V(r0.x, r0.y, r0.z);
-                    d = V(r1.x, r1.y, r1.z);
-                    inv = ray_inv(d);
-                    h.t = r0.w < kTMax ? r0.w : kTMax; // NaN and +inf: the library's own bound; a hit at exactly this t is taken (id below)
-                    h.u = 0.0f; h.v = 0.0f; h.id = 0x7fffffff; h.slot = -1;
-                    cur = P.root; sp = 0; steps = 0;
-                    k = AO_PRIMARY;
-                    ray = (int)i;
-                }
-                next = (end - next > n_idle) ? next + n_idle : end;
-            }
-        } else if (n_idle == PT_WAVE) {
-            break;
-        }
+    hit_reset(h, 0.0f);
+    const auto start = [&](int i) {
+        hit_reset(h, ray_load(A.r.rays, i, o, d, inv));
+        cur = P.root; sp = 0; steps = 0;
+        k = AO_PRIMARY;
+        ray = i;
+    };
+    while (ray_range_refill(R, A.r.refill, ray < 0, start)) {
         if (ray >= 0) {
-            if (cur != PT_DONE) {
-                // bounded as the probe's walk, per walk: the stack bound comes from the host (3 * depth4 + 1, + 3)
-                if (++steps > (1 << 20) || sp + 3 > A.r.cap) {
-                    gp(P.error_flag)[0] = 1u;
-                    k = AO_OVERRUN;
-                    cur = PT_DONE;
-                } else if (cur >= 0) {
-                    node4_step<PT_WAVE, PT_LDS_STACK>(nodes4, stack, ovf, o, inv, h.t, cur, sp, EXACT);
-                } else {
-                    const uint32_t code = ~(uint32_t)cur;
-                    leaf_test(tris, (int)(code >> 3), (int)(code & 7u), o, d, h);
-                    if ((k >= 0 && h.slot >= 0) || sp == 0) { // any-hit exit of an occlusion ray
-                        cur = PT_DONE;
-                    } else {
-                        --sp;
-                        cur = (int)stack_pop<PT_WAVE, PT_LDS_STACK>(stack, ovf, sp);
-                    }
-                }
-            }
+            // the bounds apply per walk; the any-hit exit is an occlusion ray's
+            if (cur != PT_DONE && !quad_walk_step<PT_LDS_STACK>(P, nodes4, tris, stack, ovf, A.r.cap, o, d, inv, h, cur, sp, steps, EXACT, k >= 0))
+                k = AO_OVERRUN;
             if (cur == PT_DONE) { // a walk has ended: the next one starts now, or the ray retires and the lane is idle from the next round on
                 bool retire = true;
                 float ao = 1.0f;
@@ -136,8 +103,7 @@ __global__ void __launch_bounds__(PT_WAVE, PT_AO_WAVES_PER_EU) PT_AO_KERNEL(cons
                 } else { // occlusion ray k
                     d = ao_direction(nf, rng);
                     inv = ray_inv(d);
-                    h.t = A.thi;
-                    h.u = 0.0f; h.v = 0.0f; h.id = 0x7fffffff; h.slot = -1;
+                    hit_reset(h, A.thi);
                     cur = P.root; sp = 0; steps = 0;
                 }
             }
@@ -149,20 +115,12 @@ static const void* ao_instance(int exact) { return exact ? (const void*)PT_AO_KE
 
 extern "C" hipError_t PT_AO_GEOMETRY(int exact, PtGeometry* g)
 {
-    g->block = PT_WAVE;
-    g->ns = PT_WAVE;
-    g->lds_levels = PT_LDS_STACK;
-    g->lds_bytes = (size_t)g->lds_levels * PT_WAVE * 4;
-    g->state_words = 0;
-    return pt_complete_geometry(g, ao_instance(exact));
+    return pt_wave_geometry(g, PT_LDS_STACK, 0, ao_instance(exact));
 }
 
 extern "C" hipError_t PT_AO_LAUNCH(const PtKernelParams* p, const PtAoArgs* a, int grid, size_t lds_bytes, hipStream_t stream)
 {
-    const PtRaysArgs& r = a->r;
-    if (grid < 1 || r.n < 1 || r.per_wave < PT_WAVE || (r.per_wave % PT_WAVE) != 0 || r.refill < 0 || r.refill >= PT_WAVE) return hipErrorInvalidValue;
-    if ((long long)grid * r.per_wave < (long long)r.n) return hipErrorInvalidValue; // the ranges cover every ray ...
-    if ((long long)(grid - 1) * r.per_wave >= (long long)r.n) return hipErrorInvalidValue; // ... and none is empty: the kernel relies on it
+    if (!pt_ray_ranges_ok(grid, a->r)) return hipErrorInvalidValue;
     if (a->n_rays < 1 || a->n_rays > 4096 || (a->flags & ~kAoShadingNormal) != 0 || !(a->thi > 0.0f && a->thi <= kTMax)) return hipErrorInvalidValue;
     void* args[] = {(void*)p, (void*)a};
     (void)hipLaunchKernel(ao_instance(p->box_exact), dim3(grid), dim3(PT_WAVE), args, lds_bytes, stream);

@@ -3,7 +3,7 @@
 // pt_kernel_aov.hip and, with PT_WATERTIGHT = 1, pt_kernel_aov_wt.hip include this header (`make asm-aov` prints both reports).
 // One pixel per lane, one wave per workgroup, n_samples camera rays per pixel, each walked to its closest hit and no further.
 // Like the probes the kernel owns no traversal or shading arithmetic: the ray is gen_camera_ray's, the walk is ray_inv -> node4_step<PT_WAVE,
-// PT_LDS_STACK> (short LDS stack, deeper levels in the wave's HBM columns) -> leaf_test with the probe's loop around them, and what a
+// PT_LDS_STACK> (short LDS stack, deeper levels in the wave's HBM columns) -> leaf_test, stepped by quad_walk_step (pt_trace.h), and what a
 // sample contributes comes from the records, the material row and the texture that shade_hit reads, through the same functions.
 // The lanes of a wave take an 8 x 8 block of pixels (four per 16-pixel shard tile; pt_shard_pixels deals tiles whose side is a multiple
 // of 8, so a block has one owner and a wave that does not own its block has nothing to do): the primary rays of a wave stay together
@@ -47,7 +47,7 @@ __global__ void __launch_bounds__(PT_WAVE, PT_AOV_WAVES_PER_EU) PT_AOV_KERNEL(co
             gen_camera_ray(P, px, py, ps); // two draws; nothing else of this pass draws from the stream
             const v3 o = ps.org, d = ps.dir;
             Hit h;
-            h.t = kTMax; h.u = 0.0f; h.v = 0.0f; h.id = 0x7fffffff; h.slot = -1;
+            hit_reset(h, kTMax);
 #if !PT_WATERTIGHT
             if (BINARY) {
                 Counters cn;
@@ -57,25 +57,8 @@ __global__ void __launch_bounds__(PT_WAVE, PT_AOV_WAVES_PER_EU) PT_AOV_KERNEL(co
             {
                 const v3 inv = ray_inv(d);
                 int cur = P.root, sp = 0, steps = 0;
-                while (cur != PT_DONE) {
-                    // bounded as the probe's walk: a ray needs a few thousand steps, the stack bound comes from the host (3 * depth4 + 1, + 3)
-                    if (++steps > (1 << 20) || sp + 3 > A.cap) {
-                        gp(P.error_flag)[0] = 1u;
-                        break;
-                    }
-                    if (cur >= 0) {
-                        node4_step<PT_WAVE, PT_LDS_STACK>(nodes4, stack, ovf, o, inv, h.t, cur, sp, EXACT);
-                    } else {
-                        const uint32_t code = ~(uint32_t)cur;
-                        leaf_test(tris, (int)(code >> 3), (int)(code & 7u), o, d, h);
-                        if (sp > 0) {
-                            --sp;
-                            cur = (int)stack_pop<PT_WAVE, PT_LDS_STACK>(stack, ovf, sp);
-                        } else {
-                            cur = PT_DONE;
-                        }
-                    }
-                }
+                // (a walk out of its bounds ends here too, with the best hit so far: quad_walk_step)
+                while (cur != PT_DONE) quad_walk_step<PT_LDS_STACK>(P, nodes4, tris, stack, ovf, A.cap, o, d, inv, h, cur, sp, steps, EXACT, false);
             }
             v3 alb, nrm;
             float alpha, depth;
@@ -105,12 +88,7 @@ extern "C" hipError_t PT_AOV_GEOMETRY(int binary, int exact, int stack_entries, 
 {
     const void* fn = aov_instance(binary, exact);
     if (!fn) return hipErrorInvalidValue;
-    g->block = PT_WAVE;
-    g->ns = PT_WAVE;
-    g->lds_levels = binary ? stack_entries : PT_LDS_STACK;
-    g->lds_bytes = (size_t)g->lds_levels * PT_WAVE * 4;
-    g->state_words = 0;
-    return pt_complete_geometry(g, fn);
+    return pt_wave_geometry(g, binary ? stack_entries : PT_LDS_STACK, 0, fn);
 }
 
 extern "C" hipError_t PT_AOV_LAUNCH(const PtKernelParams* p, const PtAovArgs* a, int binary, int grid, size_t lds_bytes, hipStream_t stream)

@@ -1,8 +1,8 @@
 // pt_aov_follow.h -- guide pass, follow mode (pt_render_aov_follow, include/mi355pt.h): the guide ray passes mirrors and glass
 //
 // Translation units of their own again - pt_kernel_aov_follow.hip and pt_kernel_aov_follow_wt.hip include this header - so
-// that `make asm-aov` goes on listing the five first-hit kernels and nothing else.  The frame loop, the pixel blocks, the walk and every
-// fetch are the first-hit kernel's; what is new is the loop around the walk: a hit on a surface that classifies MIRROR or GLASS
+// that `make asm-aov` goes on listing the five first-hit kernels and nothing else.  The frame loop, the pixel blocks, the walk (quad_walk_step, pt_trace.h) and
+// every fetch are the first-hit kernel's; what is new is the loop around the walk: a hit on a surface that classifies MIRROR or GLASS
 // (aov_classify) sends the ray on from shade_hit's hit point with reflect / refract of pt_device.h, and the tint and the path length
 // travel with it.  The loop draws nothing from the stream.
 // Registers.  The first-hit instances sit at 119..128 of the 128 VGPRs of four waves per SIMD, and the follow loop adds state that
@@ -212,7 +212,7 @@ __global__ void __launch_bounds__(PT_WAVE, PT_AOV_WAVES_PER_EU) PT_AOV_FOLLOW_KE
             float depth;
             for (int step = 0;; ++step) {
                 Hit h;
-                h.t = kTMax; h.u = 0.0f; h.v = 0.0f; h.id = 0x7fffffff; h.slot = -1;
+                hit_reset(h, kTMax);
 #if !PT_WATERTIGHT && !PT_RAYGEN
                 if (BINARY) {
                     Counters cn;
@@ -222,25 +222,8 @@ __global__ void __launch_bounds__(PT_WAVE, PT_AOV_WAVES_PER_EU) PT_AOV_FOLLOW_KE
                 {
                     const v3 inv = ray_inv(d);
                     int cur = P.root, sp = 0, steps = 0;
-                    while (cur != PT_DONE) {
-                        // the first-hit kernel's walk and bounds (pt_aov_kernel)
-                        if (++steps > (1 << 20) || sp + 3 > A.cap) {
-                            gp(P.error_flag)[0] = 1u;
-                            break;
-                        }
-                        if (cur >= 0) {
-                            node4_step<PT_WAVE, PT_LDS_STACK>(nodes4, stack, ovf, o, inv, h.t, cur, sp, EXACT);
-                        } else {
-                            const uint32_t code = ~(uint32_t)cur;
-                            leaf_test(tris, (int)(code >> 3), (int)(code & 7u), o, d, h);
-                            if (sp > 0) {
-                                --sp;
-                                cur = (int)stack_pop<PT_WAVE, PT_LDS_STACK>(stack, ovf, sp);
-                            } else {
-                                cur = PT_DONE;
-                            }
-                        }
-                    }
+                    // the first-hit kernel's walk (a walk out of its bounds ends here too, with the best hit so far: quad_walk_step)
+                    while (cur != PT_DONE) quad_walk_step<PT_LDS_STACK>(P, nodes4, tris, stack, ovf, A.cap, o, d, inv, h, cur, sp, steps, EXACT, false);
                 }
                 if (step == 0 && h.slot >= 0) park[3 * PT_WAVE] = park[3 * PT_WAVE] + 1.0f; // coverage stays first-hit
                 v3 tint = V(park[8 * PT_WAVE], park[9 * PT_WAVE], park[10 * PT_WAVE]);
@@ -284,12 +267,7 @@ extern "C" hipError_t PT_AOV_FOLLOW_GEOMETRY(int binary, int exact, int stack_en
 {
     const void* fn = aov_follow_instance(binary, exact);
     if (!fn) return hipErrorInvalidValue;
-    g->block = PT_WAVE;
-    g->ns = PT_WAVE;
-    g->lds_levels = binary ? stack_entries : PT_LDS_STACK;
-    g->lds_bytes = (size_t)(g->lds_levels + PT_AOV_PARK) * PT_WAVE * 4; // the stack, then the parked state
-    g->state_words = 0;
-    return pt_complete_geometry(g, fn);
+    return pt_wave_geometry(g, binary ? stack_entries : PT_LDS_STACK, PT_AOV_PARK, fn); // the stack, then the parked state
 }
 
 extern "C" hipError_t PT_AOV_FOLLOW_LAUNCH(const PtKernelParams* p, const PtAovFollowArgs* a, int binary, int grid, size_t lds_bytes, hipStream_t stream)

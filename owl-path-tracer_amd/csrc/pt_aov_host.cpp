@@ -284,6 +284,16 @@ extern "C" int64_t pt_debug_aov_host(pt_ctx* c, const pt_camera* cam, int32_t W,
     return aov_host(c, cam, nullptr, W, H, n_samples, pixel_ids, n_pixels, out, nullptr, "pt_debug_aov_host");
 }
 
+std::vector<int32_t> pti::slot_of_prim(const HostScene& S)
+{
+    std::vector<int32_t> slot_of((size_t)S.n_triangles, -1);
+    for (size_t s = 0; s < S.bvh.tris.size(); ++s) {
+        const int32_t id = S.bvh.tris[s].id;
+        if (id >= 0 && (size_t)id < slot_of.size()) slot_of[(size_t)id] = (int32_t)s; // (padding slots carry id 0x7fffffff)
+    }
+    return slot_of;
+}
+
 // surface_record of pt_surface.h over the host copies (pt_debug_trace_surface_host, pt_rays_host.cpp), line for line.
 void pti::surface_record_host(const HostScene& S, int32_t slot, float t, float u, float v, int32_t prim, pt_surface* out)
 {
@@ -376,11 +386,7 @@ int64_t aov_host(pt_ctx* c, const pt_camera* cam, const pt_ray_gen* rays, int32_
     }
     A.W = W; A.H = H; A.n = n_samples;
     A.wt = c->opt.watertight != 0; // the walk follows the option as the render does
-    A.slot_of.assign((size_t)c->scene.n_triangles, -1);
-    for (size_t s = 0; s < c->scene.bvh.tris.size(); ++s) {
-        const int32_t id = c->scene.bvh.tris[s].id;
-        if (id >= 0 && (size_t)id < A.slot_of.size()) A.slot_of[(size_t)id] = (int32_t)s; // (padding slots carry id 0x7fffffff)
-    }
+    A.slot_of = slot_of_prim(c->scene);
     pt_parallel_ranges((size_t)n_pixels, [&](size_t lo, size_t hi) {
         for (size_t i = lo; i < hi; ++i) {
             const int px = (int)(pixel_ids[i] % (uint32_t)W), py = (int)(pixel_ids[i] / (uint32_t)W);

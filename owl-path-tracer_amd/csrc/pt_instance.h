@@ -34,3 +34,23 @@ inline hipError_t pt_complete_geometry(PtGeometry* g, const void* fn, bool allow
     g->max_blocks_per_cu = 0;
     return hipOccupancyMaxActiveBlocksPerMultiprocessor(&g->max_blocks_per_cu, fn, g->block, g->lds_bytes);
 }
+
+// The geometry of the one-wave-per-workgroup kernels (guide kernels, ray queries, ambient occlusion): 64 threads, a pixel or ray per lane,
+// and in LDS the lds_levels lowest levels of the lanes' stacks, then park_words words per lane of parked state (the follow kernels').
+inline hipError_t pt_wave_geometry(PtGeometry* g, int lds_levels, int park_words, const void* fn)
+{
+    g->block = 64;
+    g->ns = 64;
+    g->lds_levels = lds_levels;
+    g->lds_bytes = (size_t)(lds_levels + park_words) * 64 * 4;
+    g->state_words = 0;
+    return pt_complete_geometry(g, fn);
+}
+
+// What the kernels that walk ray ranges (pt_ray_range.h) rely on: workgroup b of `grid` owns rays [b * per_wave, + per_wave) of a.n.
+inline bool pt_ray_ranges_ok(int grid, const PtRaysArgs& a)
+{
+    if (grid < 1 || a.n < 1 || a.per_wave < 64 || (a.per_wave % 64) != 0 || a.refill < 0 || a.refill >= 64) return false;
+    if ((long long)grid * a.per_wave < (long long)a.n) return false;    // the ranges cover every ray ...
+    return (long long)(grid - 1) * a.per_wave < (long long)a.n;         // ... and none is empty
+}

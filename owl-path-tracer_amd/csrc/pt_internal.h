@@ -225,6 +225,9 @@ PT_LOCAL int need_accum(pt_ctx* c, const char* who);  // PT_E_INVALID by name wi
 PT_LOCAL int refuse_comm(pt_ctx* c, const char* who); // PT_E_INVALID by name with a communicator
 // pt_aov_host.cpp
 PT_LOCAL int check_aov_params(pt_ctx* c, const pt_aov_params* p, const char* who, pt_aov_params* eff); // the refusals of pt_render_aov_follow* and the twin; *eff = the parameters in effect
+// global triangle id -> leaf-order slot of the host scene as it stands (after sync_host_scene): the host walk reports the id, the triangle
+// and shading records are in leaf order.  Built per call: nothing to invalidate where bvh.tris is rebuilt or reordered.
+PT_LOCAL std::vector<int32_t> slot_of_prim(const HostScene& S);
 // the surface record of pt_trace_surface at the hit (t, u, v, prim) on the triangle in leaf-order slot `slot` (< 0: the miss record), from the host
 // copies of the scene with the arithmetic of pt_device.h: csrc/pt_surface.h expression for expression (pt_debug_trace_surface_host)
 PT_LOCAL void surface_record_host(const HostScene& S, int32_t slot, float t, float u, float v, int32_t prim, pt_surface* out);

@@ -1,7 +1,7 @@
 // pt_probes.h -- ray probes (tests only: pt_debug_eval ops PT_PROBE_*, pt_launch.h; tests/test_gpu_ray_probes.py)
 //
 // Caller-chosen rays through the walks of pt_render_wave_kernel: the kernels below own no traversal arithmetic, they call ray_inv,
-// node4_step, leaf_test (pt_trace.h) and traverse_groups (pt_kernel.hip) the way the render kernel does, and write the closest hit out
+// node4_step and leaf_test (through quad_walk_step, pt_trace.h) and traverse_groups (pt_kernel.hip) the way the render kernel does, and write the closest hit out
 // per ray.  The group probe runs the render kernel's own WaveCtx, pick_pass and traverse_groups, which sit in the anonymous namespace
 // of pt_kernel.hip: that file includes this header at its end, in the single-frame and the watertight build, and nothing else does.
 // They are separate kernels, so the product instances' code does not change with them.
@@ -48,27 +48,11 @@ __global__ void __launch_bounds__(PT_WAVE) PT_PROBE_QUAD_KERNEL(const PtKernelPa
         const v3 o = V(x[0], x[1], x[2]), d = V(x[3], x[4], x[5]);
         const v3 inv = ray_inv(d);
         Hit h;
-        h.t = kTMax; h.u = 0.0f; h.v = 0.0f; h.id = 0x7fffffff; h.slot = -1;
+        hit_reset(h, kTMax);
         int cur = P.root, sp = 0, max_sp = 0, steps = 0;
-        while (cur != PT_DONE) {
-            // bounded whatever the tree holds: a ray needs a few thousand steps, and the stack bound comes from the host (3 * depth4 + 1)
-            if (++steps > (1 << 20) || sp + 3 > cap) {
-                gp(P.error_flag)[0] = 1u;
-                break;
-            }
-            if (cur >= 0) {
-                node4_step<PT_WAVE, LDS_ENTRIES>(nodes4, stack, ovf, o, inv, h.t, cur, sp, EXACT);
-                max_sp = sp > max_sp ? sp : max_sp;
-            } else {
-                const uint32_t code = ~(uint32_t)cur;
-                leaf_test(tris, (int)(code >> 3), (int)(code & 7u), o, d, h);
-                if (sp > 0) {
-                    --sp;
-                    cur = (int)stack_pop<PT_WAVE, LDS_ENTRIES>(stack, ovf, sp);
-                } else {
-                    cur = PT_DONE;
-                }
-            }
+        while (cur != PT_DONE) { // (a walk out of its bounds ends here too, with the best hit so far: quad_walk_step)
+            quad_walk_step<LDS_ENTRIES>(P, nodes4, tris, stack, ovf, cap, o, d, inv, h, cur, sp, steps, EXACT, false);
+            max_sp = sp > max_sp ? sp : max_sp; // sp falls only on a pop: the maximum is the one over the node steps
         }
         probe_store(out + i * out_stride, h.slot >= 0, h.t, h.u, h.v, h.id, (float)max_sp);
     }

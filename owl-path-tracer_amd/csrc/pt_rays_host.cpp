@@ -28,16 +28,22 @@ static_assert(sizeof(pt_ao_hit) == 32 && sizeof(pt_ao_params) == 16, "the ambien
 // What a call stores per ray: a pt_ray_hit, a byte, a pt_surface, or a pt_ao_hit.
 enum RaysMode { kClosest = 0, kOccluded = 1, kSurface = 2, kAo = 3 };
 constexpr size_t kRecordBytes[4] = {sizeof(pt_ray_hit), 1, sizeof(pt_surface), sizeof(pt_ao_hit)};
+constexpr int kKernelOf[4] = {0, 0, 1, 2}; // the kernel family that serves a mode: ray kernels (closest and occluded), their surface instances, ambient occlusion
 
+// The instances of the ray kernels (pt_launch.h), by [family][watertight], behind one signature: the ray and surface kernels take the
+// PtRaysArgs a PtAoArgs begins with, and the ambient-occlusion kernel has no occlusion form to select.
+template <auto launch> hipError_t rays_only(const PtKernelParams* p, const PtAoArgs* a, int occluded, int grid, size_t lds_bytes, hipStream_t stream)
+{
+    return launch(p, &a->r, occluded, grid, lds_bytes, stream);
+}
+template <auto launch> hipError_t ao_launch(const PtKernelParams* p, const PtAoArgs* a, int, int grid, size_t lds_bytes, hipStream_t stream) { return launch(p, a, grid, lds_bytes, stream); }
+template <auto geometry> hipError_t ao_geometry(int, int exact, PtGeometry* g) { return geometry(exact, g); }
 const struct RaysInstance {
     hipError_t (*geometry)(int occluded, int exact, PtGeometry* g);
-    hipError_t (*launch)(const PtKernelParams* p, const PtRaysArgs* a, int occluded, int grid, size_t lds_bytes, hipStream_t stream);
-} kRaysInstance[2][2] = {{{pt_rays_geometry, pt_launch_rays}, {pt_rays_geometry_wt, pt_launch_rays_wt}},
-                         {{pt_rays_surface_geometry, pt_launch_rays_surface}, {pt_rays_surface_geometry_wt, pt_launch_rays_surface_wt}}}; // by [surface][watertight]
-const struct AoInstance {
-    hipError_t (*geometry)(int exact, PtGeometry* g);
-    hipError_t (*launch)(const PtKernelParams* p, const PtAoArgs* a, int grid, size_t lds_bytes, hipStream_t stream);
-} kAoInstance[2] = {{pt_rays_ao_geometry, pt_launch_rays_ao}, {pt_rays_ao_geometry_wt, pt_launch_rays_ao_wt}}; // by [watertight]
+    hipError_t (*launch)(const PtKernelParams* p, const PtAoArgs* a, int occluded, int grid, size_t lds_bytes, hipStream_t stream);
+} kRaysInstance[3][2] = {{{pt_rays_geometry, rays_only<pt_launch_rays>}, {pt_rays_geometry_wt, rays_only<pt_launch_rays_wt>}},
+                         {{pt_rays_surface_geometry, rays_only<pt_launch_rays_surface>}, {pt_rays_surface_geometry_wt, rays_only<pt_launch_rays_surface_wt>}},
+                         {{ao_geometry<pt_rays_ao_geometry>, ao_launch<pt_launch_rays_ao>}, {ao_geometry<pt_rays_ao_geometry_wt>, ao_launch<pt_launch_rays_ao_wt>}}};
 
 // What pt_trace_ao, its device form and the twin refuse beside the ray queries' refusals; *eff = the parameters in effect.
 int check_ao_params(pt_ctx* c, const char* who, const pt_ao_params* p, pt_ao_params* eff)
@@ -76,11 +82,10 @@ int rays_device(pt_ctx* c, RaysMode mode, const void* d_rays, int64_t n, void* d
     fill_params(c, P); // the scene; no camera, so no distance to judge the slab form by: the subtracting form only on request
     P.box_exact = c->opt.box_exact > 0 ? 1 : 0;
     quad_walk_params(c, P);
-    const RaysInstance& inst = kRaysInstance[mode == kSurface][c->opt.watertight != 0];
-    const AoInstance& ao_inst = kAoInstance[c->opt.watertight != 0];
+    const RaysInstance& inst = kRaysInstance[kKernelOf[mode]][c->opt.watertight != 0];
     const int occluded = mode == kOccluded;
     PtGeometry g{};
-    const hipError_t ge = mode == kAo ? ao_inst.geometry(P.box_exact, &g) : inst.geometry(occluded, P.box_exact, &g);
+    const hipError_t ge = inst.geometry(occluded, P.box_exact, &g);
     if (ge == hipErrorInvalidConfiguration) return fail(c, PT_E_LIMIT, "this build of the ray kernel spills registers to scratch; such builds are refused (pt_kernel.hip)");
     HIP_TRY(c, ge);
     if (g.max_blocks_per_cu < 1) return fail(c, PT_E_LIMIT, "ray kernel does not fit a CU (LDS %zu bytes)", g.lds_bytes);
@@ -105,16 +110,14 @@ int rays_device(pt_ctx* c, RaysMode mode, const void* d_rays, int64_t n, void* d
     A.n = (int32_t)n;
     A.per_wave = (int32_t)(blocks_per_wave * 64);
     A.refill = c->opt.rays_refill;
-    HIP_TRY(c, hipEventRecord(c->ev0, stream));
     if (mode == kAo) {
         AA.n_rays = ao->n_rays;
         AA.flags = ao->flags;
         AA.thi = ao->radius < kRayTMax ? ao->radius : kRayTMax; // ao_thi of pt_ao_math.h: +inf gives the library's bound
         AA.seed = ao->seed;
-        HIP_TRY(c, ao_inst.launch(&P, &AA, grid, g.lds_bytes, stream));
-    } else {
-        HIP_TRY(c, inst.launch(&P, &A, occluded, grid, g.lds_bytes, stream));
     }
+    HIP_TRY(c, hipEventRecord(c->ev0, stream));
+    HIP_TRY(c, inst.launch(&P, &AA, occluded, grid, g.lds_bytes, stream));
     HIP_TRY(c, hipEventRecord(c->ev1, stream));
     note_pass(c, (int)std::min<int64_t>(n, 0x7fffffff), 1, 1, grid, g, P.stack_entries, true);
     return PT_OK;
@@ -153,6 +156,17 @@ int rays_blocking(pt_ctx* c, const char* who, RaysMode mode, const pt_ray* rays,
     });
 }
 
+// What every CPU twin refuses, in this order, `who` by name; then the host scene is brought up to date.  *wt: the watertight option.
+int twin_prologue(pt_ctx* c, const char* who, const pt_ray* rays, int64_t n, const void* out, bool* wt)
+{
+    if (n < 0 || n >= ((int64_t)1 << 31)) return fail(c, PT_E_INVALID, "%s: n = %lld rays (0 .. 2^31 - 1)", who, (long long)n);
+    if (n > 0 && (!rays || !out)) return fail(c, PT_E_INVALID, "%s: NULL %s", who, !rays ? "rays" : "out");
+    if (!c->have_scene) return fail(c, PT_E_NO_SCENE, "%s: no geometries (pt_upload_scene not called)", who);
+    sync_host_scene(c);
+    *wt = c->opt.watertight != 0;
+    return PT_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -178,11 +192,9 @@ void pt_ao_default_params(pt_ao_params* p)
 int64_t pt_debug_trace_rays_host(pt_ctx* c, const pt_ray* rays, int64_t n, int32_t occluded, void* out)
 {
     if (!c) return PT_E_INVALID;
-    if (n < 0 || n >= ((int64_t)1 << 31)) return fail(c, PT_E_INVALID, "pt_debug_trace_rays_host: n = %lld rays (0 .. 2^31 - 1)", (long long)n);
-    if (n > 0 && (!rays || !out)) return fail(c, PT_E_INVALID, "pt_debug_trace_rays_host: NULL %s", !rays ? "rays" : "out");
-    if (!c->have_scene) return fail(c, PT_E_NO_SCENE, "pt_debug_trace_rays_host: no geometries (pt_upload_scene not called)");
-    sync_host_scene(c);
-    const bool wt = c->opt.watertight != 0;
+    int rc;
+    bool wt;
+    if ((rc = twin_prologue(c, "pt_debug_trace_rays_host", rays, n, out, &wt))) return rc;
     pt_parallel_ranges((size_t)n, [&](size_t lo, size_t hi) {
         for (size_t i = lo; i < hi; ++i) {
             const pt_ray& r = rays[i];
@@ -200,17 +212,10 @@ int64_t pt_debug_trace_rays_host(pt_ctx* c, const pt_ray* rays, int64_t n, int32
 int64_t pt_debug_trace_surface_host(pt_ctx* c, const pt_ray* rays, int64_t n, pt_surface* out)
 {
     if (!c) return PT_E_INVALID;
-    if (n < 0 || n >= ((int64_t)1 << 31)) return fail(c, PT_E_INVALID, "pt_debug_trace_surface_host: n = %lld rays (0 .. 2^31 - 1)", (long long)n);
-    if (n > 0 && (!rays || !out)) return fail(c, PT_E_INVALID, "pt_debug_trace_surface_host: NULL %s", !rays ? "rays" : "out");
-    if (!c->have_scene) return fail(c, PT_E_NO_SCENE, "pt_debug_trace_surface_host: no geometries (pt_upload_scene not called)");
-    sync_host_scene(c);
-    const bool wt = c->opt.watertight != 0;
-    // global triangle id -> leaf-order slot: the host walk reports the id, the records are in leaf order (padding slots carry id 0x7fffffff)
-    std::vector<int32_t> slot_of((size_t)c->scene.n_triangles, -1);
-    for (size_t s = 0; s < c->scene.bvh.tris.size(); ++s) {
-        const int32_t id = c->scene.bvh.tris[s].id;
-        if (id >= 0 && (size_t)id < slot_of.size()) slot_of[(size_t)id] = (int32_t)s;
-    }
+    int rc;
+    bool wt;
+    if ((rc = twin_prologue(c, "pt_debug_trace_surface_host", rays, n, out, &wt))) return rc;
+    const std::vector<int32_t> slot_of = slot_of_prim(c->scene);
     pt_parallel_ranges((size_t)n, [&](size_t lo, size_t hi) {
         for (size_t i = lo; i < hi; ++i) {
             const pt_ray& r = rays[i];
@@ -230,16 +235,9 @@ int64_t pt_debug_trace_ao_host(pt_ctx* c, const pt_ray* rays, int64_t n, const p
     int rc;
     pt_ao_params prm{};
     if ((rc = check_ao_params(c, "pt_debug_trace_ao_host", p, &prm))) return rc;
-    if (n < 0 || n >= ((int64_t)1 << 31)) return fail(c, PT_E_INVALID, "pt_debug_trace_ao_host: n = %lld rays (0 .. 2^31 - 1)", (long long)n);
-    if (n > 0 && (!rays || !out)) return fail(c, PT_E_INVALID, "pt_debug_trace_ao_host: NULL %s", !rays ? "rays" : "out");
-    if (!c->have_scene) return fail(c, PT_E_NO_SCENE, "pt_debug_trace_ao_host: no geometries (pt_upload_scene not called)");
-    sync_host_scene(c);
-    const bool wt = c->opt.watertight != 0;
-    std::vector<int32_t> slot_of((size_t)c->scene.n_triangles, -1); // global triangle id -> leaf-order slot, as pt_debug_trace_surface_host
-    for (size_t s = 0; s < c->scene.bvh.tris.size(); ++s) {
-        const int32_t id = c->scene.bvh.tris[s].id;
-        if (id >= 0 && (size_t)id < slot_of.size()) slot_of[(size_t)id] = (int32_t)s;
-    }
+    bool wt;
+    if ((rc = twin_prologue(c, "pt_debug_trace_ao_host", rays, n, out, &wt))) return rc;
+    const std::vector<int32_t> slot_of = slot_of_prim(c->scene);
     pt_parallel_ranges((size_t)n, [&](size_t lo, size_t hi) {
         for (size_t i = lo; i < hi; ++i) ao_ray_host(c->scene, slot_of, wt, rays[i], (uint32_t)i, prm, &out[i], out_ao_rays ? out_ao_rays + i * (size_t)prm.n_rays : nullptr);
     });

@@ -1,6 +1,7 @@
 // pt_trace.h -- device code shared by every kernel family that walks the tree (pt_kernel.hip: the wavefront-scheduled product kernel;
 // pt_kernel_aux.hip: the lane-per-pixel variant and the validation kernel; pt_probes.h, pt_aov_first.h, pt_aov_follow.h,
-// pt_rays_kernels.h): closest-hit building blocks (slab test, Moeller-Trumbore, binary node step, quad-node step), the reference's
+// pt_rays_kernels.h, pt_ao.h): closest-hit building blocks (slab test, Moeller-Trumbore, binary node step, quad-node step, and
+// quad_walk_step: the one bounded step of the quad walk that every family outside the wavefront kernel calls), the reference's
 // path loop body after owl::traceRay (shade_hit: device.cu:136-214), camera rays (device.cu:231-241) and the work counters.
 // Everything is in an anonymous namespace: each translation unit gets its own inlined copy.
 #pragma once
@@ -26,6 +27,8 @@ struct Hit {
     int slot; // leaf-order index of the triangle
     int id;   // global triangle id (tie-break + shading record)
 };
+// No hit yet, and none accepted at or beyond t (a hit at exactly t is taken: every real id is below this one).
+__device__ __forceinline__ void hit_reset(Hit& h, float t) { h.t = t; h.u = 0.0f; h.v = 0.0f; h.id = 0x7fffffff; h.slot = -1; }
 
 struct Counters {
     uint32_t rays = 0, nodes = 0, tris = 0, scat = 0, env = 0, samples = 0, retry = 0;
@@ -504,6 +507,42 @@ __device__ __forceinline__ void node4_step(const PtNode4* __restrict__ nodes4, u
     } else {
         cur = PT_DONE;
     }
+}
+
+// ONE BOUNDED STEP of a lane's quad walk, for every one-wave kernel outside the wavefront kernel (quad probe, guide kernels, ray
+// queries, ambient occlusion): the node step at a node, the leaf test at a leaf, and after a leaf the next entry of the stack - or
+// PT_DONE where the stack is empty, or at once where any_hit is set and the lane holds a hit (an occlusion walk: tbest never shrinks
+// below the ray's bound there, so ordering the children buys nothing and node4_step is left as it is).  The caller starts a walk with
+// cur = P.root, sp = 0, steps = 0, hit_reset(h, bound) and steps while cur != PT_DONE.
+// BOUNDS AND TERMINATION: a walk is over after at most 2^20 + 1 calls (`steps`: a ray needs a few thousand), and the three pushes of a
+// node step stay below `cap`, which the host derives from the tree (3 * depth4 + 1, + 3 for the stores above the top).  A walk that runs
+// out of either is an OVERRUN: error_flag is set, cur = PT_DONE, and the function returns false; it returns true after every step it took.
+// What an overrun does to the result is the caller's:
+//     quad probe, first-hit and follow guide kernels    leave the walk with the best hit so far
+//     ray kernels (closest, occluded, surface)          retire the ray as a miss (h.slot = -1)
+//     ambient occlusion                                 k = AO_OVERRUN: the ray retires as a miss with ao = 1
+template <int LDS_ENTRIES>
+__device__ __forceinline__ bool quad_walk_step(const PtKernelParams& P, const PtNode4* __restrict__ nodes4, const PtTri* __restrict__ tris, uint32_t* stack, uint32_t PT_AS1* ovf,
+                                               const int cap, v3 o, v3 d, v3 inv, Hit& h, int& cur, int& sp, int& steps, const bool exact, const bool any_hit)
+{
+    if (++steps > (1 << 20) || sp + 3 > cap) {
+        gp(P.error_flag)[0] = 1u;
+        cur = PT_DONE;
+        return false;
+    }
+    if (cur >= 0) {
+        node4_step<PT_WAVE, LDS_ENTRIES>(nodes4, stack, ovf, o, inv, h.t, cur, sp, exact);
+    } else {
+        const uint32_t code = ~(uint32_t)cur;
+        leaf_test(tris, (int)(code >> 3), (int)(code & 7u), o, d, h);
+        if ((any_hit && h.slot >= 0) || sp == 0) {
+            cur = PT_DONE;
+        } else {
+            --sp;
+            cur = (int)stack_pop<PT_WAVE, LDS_ENTRIES>(stack, ovf, sp);
+        }
+    }
+    return true;
 }
 
 // STRIDE: words between two levels of a lane's stack = threads of the workgroup (the guide kernels of pt_aov_first.h / pt_aov_follow.h run it with one wave)
