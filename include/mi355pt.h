@@ -1098,6 +1098,17 @@ int pt_debug_oct_info(pt_ctx* ctx, int64_t out[8]);
  * render did not sort), or a negative error. */
 int64_t pt_debug_read_queue(pt_ctx* ctx, uint32_t* queue_ids, uint32_t* input_ids, uint8_t* cost, int64_t cap);
 
+/* For tests of the queue sort and the tier plan: a cost image of the caller's in place of the measured one.  img: width * height
+ * cost classes, index x + width * y; the context keeps a device copy (uploaded here, after waiting for the context's last call like
+ * the readers above; freed by pt_destroy).  While an image is set, every launch sequence with the cost-ordered schedule whose launch image
+ * is exactly width x height - for pt_render_batch the virtual image W x (K * H) of a sequence of K frames - runs its cost pre-pass as
+ * always and then copies the image over the measured costs (device to device, on the launch's stream, before the counting sort): the
+ * queue, the tier plan and what pt_debug_read_queue returns as cost are those of the image, the frame is the same bit for bit.  A launch
+ * sequence of another size ignores the image.  The bytes are taken as given: the sort reads 0 as "not this rank's pixel", so a caller who
+ * wants the semantics of a shard writes 0 at the pixels the rank does not own.  img NULL: back to the measured costs (width and height
+ * are not looked at).  PT_E_NO_DEVICE on a host-only context, PT_E_INVALID for a size pt_render refuses. */
+int pt_debug_set_cost_image(pt_ctx* ctx, const uint8_t* img, int32_t width, int32_t height);
+
 /* Timeline of the last wavefront launch, three arrays of n_chunks + 1 values: ticks[0] = constant 100 MHz clock (s_memrealtime)
  * at kernel entry, ticks[1 + c] = when the last pixel finished chunk c; then [0] unused, [1 + c] = when the last work item of
  * chunk c started; then [0] unused, [1 + c] = queue entry that finished chunk c last.  Returns the number of values written. */

@@ -1,5 +1,5 @@
 // pt_debug.cpp -- what looks into the device for the tests: pt_debug_eval with the ray probes, and the readers of the diagnostics a
-// frame leaves behind (queue, chunk timeline, tier plan, finish ticks).
+// frame leaves behind (queue, chunk timeline, tier plan, finish ticks), and the cost image a test sets in place of the measured one.
 #include <algorithm>
 #include <cstring>
 #include <vector>
@@ -86,6 +86,22 @@ int64_t pt_debug_read_queue(pt_ctx* c, uint32_t* queue_ids, uint32_t* input_ids,
         for (int64_t i = 0; i < n; ++i) cost[i] = ids[(size_t)i] < img.size() ? img[ids[(size_t)i]] : 0;
     }
     return n;
+}
+
+int pt_debug_set_cost_image(pt_ctx* c, const uint8_t* img, int32_t W, int32_t H)
+{
+    if (!c) return PT_E_INVALID;
+    if (c->host_only) return fail(c, PT_E_NO_DEVICE, "host-only context: pt_debug_set_cost_image needs the GPU");
+    if (img && (W <= 0 || H <= 0 || W > 65535 || H > 65535 || (int64_t)W * H > (int64_t)0x7fffffff)) // the sizes of check_render_args
+        return fail(c, PT_E_INVALID, "pt_debug_set_cost_image: bad image size %dx%d", W, H);
+    if (int rc = drain(c)) return rc; // a frame in flight may still copy the image that is replaced here
+    c->cost_image_w = c->cost_image_h = 0;
+    if (!img) return PT_OK; // back to the measured costs (the buffer stays the context's until pt_destroy)
+    if (int rc = upload(c, c->d_cost_image, img, (size_t)W * H)) return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->stream)); // img is the caller's
+    c->cost_image_w = W;
+    c->cost_image_h = H;
+    return PT_OK;
 }
 
 int64_t pt_debug_read_laps(pt_ctx* c, uint64_t* ticks, int64_t cap)

@@ -143,6 +143,8 @@ struct pt_ctx {
     DevBuf d_ray_image; // ray images: the blocking form's staging of the caller's table (pt_render_rays, pt_render.cpp)
     DevBuf d_up_ws, d_up_rgb, d_up_aov; // upsampling: the low frame's records (pt_upsample_workspace_bytes); pt_upsample's staging of the low frame and its guides (the high guides and both outputs stage in d_dn_aov, d_dn_rgb, d_dn_out8)
     std::vector<DevBuf> d_textures;
+    DevBuf d_cost_image; // pt_debug_set_cost_image: the caller's cost image, which run_launches copies over d_cost in launch sequences of its size
+    int cost_image_w = 0, cost_image_h = 0; // 0 x 0: none set, the measured costs stand
 
     // pixel queue
     QueueKey queue;

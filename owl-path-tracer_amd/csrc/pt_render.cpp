@@ -620,6 +620,9 @@ int run_launches(pt_ctx* c, const FramePlan& f, PtKernelParams& P, int W, int H,
     for (int l = 0; l < f.n_launch; ++l) {
         launch_params(c, f, l, max_samples, P);
         if (f.sorted && l == 1) { // the queue in cost order (and the tier plan) from the pre-pass's cost image
+            // ... or from the image a test has set for launch sequences of this size (pt_debug_set_cost_image): the pre-pass ran, its costs are replaced
+            if (c->cost_image_w == W && c->cost_image_h == H)
+                HIP_TRY(c, hipMemcpyAsync(c->d_cost.p, c->d_cost_image.p, (size_t)W * H, hipMemcpyDeviceToDevice, stream));
             HIP_TRY(c, pt_launch_sort_pixels((const uint8_t*)c->d_cost.p, W, H, c->opt.cost_radius, (const uint32_t*)c->d_pixels.p, (uint32_t*)c->d_sorted.p,
                                              c->n_pixels, (uint32_t)f.pre, (uint32_t*)c->d_sort_scratch.p, (uint8_t*)c->d_bucket.p, stream));
             if (f.tiers) HIP_TRY(c, pt_launch_plan_tiers((const uint32_t*)c->d_sort_scratch.p, c->n_pixels, f.grid, f.geo.ns, c->opt.whole > 0, (uint32_t*)c->d_tiers.p, stream));

@@ -122,7 +122,7 @@ class Stats(C.Structure):
 
 EXPORTS = ["pt_create", "pt_destroy", "pt_last_error", "pt_abi_version", "pt_upload_scene", "pt_set_materials", "pt_set_environment",
            "pt_set_pixel_shard", "pt_shard_pixels", "pt_render", "pt_render_device", "pt_synchronize", "pt_set_option", "pt_get_stats",
-           "pt_to_camera_data", "pt_debug_closest_hit_host", "pt_debug_closest_hit_host_n", "pt_debug_export_tree", "pt_debug_eval", "pt_debug_read_queue", "pt_debug_read_laps", "pt_debug_read_finish", "pt_debug_read_tiers", "pt_debug_plan_tiers",
+           "pt_to_camera_data", "pt_debug_closest_hit_host", "pt_debug_closest_hit_host_n", "pt_debug_export_tree", "pt_debug_eval", "pt_debug_read_queue", "pt_debug_read_laps", "pt_debug_read_finish", "pt_debug_read_tiers", "pt_debug_plan_tiers", "pt_debug_set_cost_image",
            "pt_comm_get_unique_id", "pt_comm_init_rank", "pt_comm_destroy", "pt_reduce_framebuffer", "pt_host_alloc", "pt_host_free",
            "pt_group_create", "pt_group_destroy", "pt_group_size", "pt_group_ctx", "pt_group_last_error", "pt_group_upload_scene",
            "pt_group_set_materials", "pt_group_set_option", "pt_group_render", "pt_debug_quad_info", "pt_debug_oct_info", "pt_debug_clone_scene",
@@ -209,6 +209,7 @@ def lib():
     L.pt_debug_read_tiers.restype = C.c_int64
     L.pt_debug_plan_tiers.argtypes = [C.POINTER(C.c_uint32), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_uint32), C.c_int64]
     L.pt_debug_plan_tiers.restype = C.c_int64
+    L.pt_debug_set_cost_image.argtypes = [C.c_void_p, C.POINTER(C.c_uint8), C.c_int32, C.c_int32]
     u8p = C.POINTER(C.c_uint8)
     L.pt_comm_get_unique_id.argtypes = [u8p]
     L.pt_comm_init_rank.argtypes = [C.c_void_p, u8p, C.c_int32, C.c_int32]
@@ -1252,6 +1253,16 @@ class Context:
         if n < 0:
             self._check(int(n), "pt_debug_read_queue")
         return q[:n], i[:n], c[:n]
+
+    def set_cost_image(self, img):
+        """pt_debug_set_cost_image: img (H, W) uint8 replaces the measured costs of every cost-ordered launch sequence whose launch image
+        is W x H (a batch: W x K*H) from here on; None: back to the measured costs."""
+        if img is None:
+            self._check(lib().pt_debug_set_cost_image(self._h, None, 0, 0), "pt_debug_set_cost_image")
+            return
+        a = np.ascontiguousarray(img, np.uint8)
+        assert a.ndim == 2
+        self._check(lib().pt_debug_set_cost_image(self._h, a.ctypes.data_as(C.POINTER(C.c_uint8)), a.shape[1], a.shape[0]), "pt_debug_set_cost_image")
 
     def read_finish(self, n_pixels):
         """Per pixel (x + W * y): (ms from the entry of the main launch to the pixel's last sample, rays traced - with count = 1); option latency = 1."""

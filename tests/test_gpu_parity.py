@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from owl_path_tracer_amd.pyhost import binding as B
+from queue_ref import _queue_classes  # cost_bucket(pixel_cost()) of csrc/pt_schedule.hip in numpy
 
 pytestmark = pytest.mark.gpu
 
@@ -324,20 +325,6 @@ def test_cornell_image_bitwise_and_golden(gpu, orc, cornell):
     for k in ("samples", "rays", "scatters", "nan_retries"):
         assert st[k] == cnt[k], k
     assert st["kernel_ms"] > 0 and st["launches"] == 2  # cost pre-pass + main launch over the cost-ordered pixel queue
-
-
-def _queue_classes(ids, cost, q, W, H, R=2):
-    """cost_bucket(pixel_cost()) of pt_kernel.hip for the queue entries q: the pre-pass class of a pixel (16 per doubling of the time its
-    pre-pass samples took), replaced by the mean over the neighbours within +-10 classes if that is larger, in buckets of 4 from 230 down."""
-    img = np.zeros((H, W), np.int32)
-    img.reshape(-1)[ids] = cost
-    pad = np.pad(img, R)
-    sh = np.stack([pad[dy:dy + H, dx:dx + W] for dy in range(2 * R + 1) for dx in range(2 * R + 1)])
-    ok = (sh != 0) & (np.abs(sh - img[None]) <= 10)
-    cnt = ok.sum(0)
-    mean = np.where(cnt > 0, (np.where(ok, sh, 0).sum(0) + cnt - 1) // np.maximum(cnt, 1), img)
-    est = np.maximum(img, mean).reshape(-1)
-    return np.clip((230 - est[q]) // 4, 0, 31)
 
 
 def test_cost_ordered_queue_properties(gpu, cornell):
