@@ -170,7 +170,7 @@ int pt_render(pt_ctx* ctx, const pt_camera* cam, int32_t width, int32_t height, 
  * every call that touches what a frame in flight uses is ordered after the context's LAST ASYNCHRONOUS CALL, whichever stream that
  * call was given.  So any call of this header may follow a pt_*_device call at once, with no pt_synchronize between them.
  *   - The asynchronous calls (pt_render_device, pt_render_batch_device, pt_render_aov_device, pt_render_aov_follow_device, pt_render_aov_batch_device, pt_denoise_device,
- *     pt_denoise_batch_device, pt_denoise_var_device, pt_accum_add_device, pt_accum_denoise_device, pt_accum_reproject_device, pt_upsample_device, pt_trace_closest_device, pt_trace_occluded_device, pt_trace_surface_device, pt_trace_ao_device, pt_render_rays_device, pt_render_aov_rays_device, pt_reduce_framebuffer) wait ON THE
+ *     pt_denoise_batch_device, pt_denoise_var_device, pt_accum_add_device, pt_accum_denoise_device, pt_accum_reproject_device, pt_upsample_device, pt_trace_closest_device, pt_trace_occluded_device, pt_trace_surface_device, pt_trace_ao_device, pt_closest_point_device, pt_render_rays_device, pt_render_aov_rays_device, pt_reduce_framebuffer) wait ON THE
  *     DEVICE: the stream they are given waits for an event recorded at the end of the previous asynchronous call - only if that call
  *     used another stream; on the same stream the stream's own order suffices and nothing is added.  The host returns at once, with
  *     two exceptions that existed before: a frame of another size, shard or batch length rewrites the pixel queue and a frame that
@@ -178,7 +178,7 @@ int pt_render(pt_ctx* ctx, const pt_camera* cam, int32_t width, int32_t height, 
  *     before) - both first wait on the host for the frame in flight; pt_render_batch_device and pt_render_aov_batch_device
  *     return when their per-frame tables have reached HBM, i.e. after whatever precedes them on `stream`; and a pt_accum_add_device that
  *     selects its pixels returns when the count of its active set has reached the host (see there).
- *   - The blocking renders (pt_render, pt_render_batch, pt_render_aov, pt_render_aov_follow, pt_render_aov_batch, pt_accum_add), pt_denoise, pt_denoise_batch, pt_denoise_var, pt_accum_denoise, pt_accum_reproject, pt_upsample, pt_trace_closest, pt_trace_occluded, pt_trace_surface, pt_trace_ao, pt_render_rays and pt_render_aov_rays run on the context's stream behind the same device-side wait
+ *   - The blocking renders (pt_render, pt_render_batch, pt_render_aov, pt_render_aov_follow, pt_render_aov_batch, pt_accum_add), pt_denoise, pt_denoise_batch, pt_denoise_var, pt_accum_denoise, pt_accum_reproject, pt_upsample, pt_trace_closest, pt_trace_occluded, pt_closest_point, pt_trace_surface, pt_trace_ao, pt_render_rays and pt_render_aov_rays run on the context's stream behind the same device-side wait
  *     and return with the context idle.  After a blocking call, or on the context's own stream, they add no wait at all.
  *   - The calls that change or read what a frame uses WAIT ON THE HOST for the last asynchronous call's stream (if it is not the
  *     context's) and then for the context's: pt_set_materials, pt_set_environment, pt_update_vertices, pt_upload_scene,
@@ -193,7 +193,7 @@ int pt_render(pt_ctx* ctx, const pt_camera* cam, int32_t width, int32_t height, 
 int pt_render_device(pt_ctx* ctx, const pt_camera* cam, int32_t width, int32_t height, int32_t max_samples, int32_t max_path_depth,
                      void* d_out_rgb, void* d_out_rgba8, void* stream);
 /* Waits on the host for the context's last asynchronous call - pt_render_device, pt_render_batch_device, pt_render_aov_device,
- * pt_render_aov_follow_device, pt_render_aov_batch_device, pt_denoise_device, pt_denoise_batch_device, pt_denoise_var_device, pt_accum_add_device, pt_accum_denoise_device, pt_accum_reproject_device, pt_upsample_device, pt_trace_closest_device, pt_trace_occluded_device, pt_trace_surface_device, pt_trace_ao_device, pt_render_rays_device, pt_render_aov_rays_device or pt_reduce_framebuffer, on the stream it was given - and for the context's own stream.  Every earlier asynchronous call of the context
+ * pt_render_aov_follow_device, pt_render_aov_batch_device, pt_denoise_device, pt_denoise_batch_device, pt_denoise_var_device, pt_accum_add_device, pt_accum_denoise_device, pt_accum_reproject_device, pt_upsample_device, pt_trace_closest_device, pt_trace_occluded_device, pt_trace_surface_device, pt_trace_ao_device, pt_closest_point_device, pt_render_rays_device, pt_render_aov_rays_device or pt_reduce_framebuffer, on the stream it was given - and for the context's own stream.  Every earlier asynchronous call of the context
  * is complete then as well, whatever stream it used: each was ordered before the next (see pt_render_device).  Returns PT_E_HIP if a
  * wave's watchdog fired during the last frame (the image is then incomplete); pt_get_stats reports the same.  PT_OK at once on an idle
  * or host-only context.  A caller's stream may be destroyed once this has returned. */
@@ -838,6 +838,81 @@ int pt_trace_ao_device (pt_ctx* ctx, const void* d_rays, int64_t n, const pt_ao_
  * follows "watertight" and pt_update_vertices.  out_ao_rays: NULL, or n * K pt_ray records - the occlusion rays of ray i at
  * i*K .. i*K+K-1, as pt_trace_occluded takes them.  Returns n. */
 int64_t pt_debug_trace_ao_host(pt_ctx* ctx, const pt_ray* rays, int64_t n, const pt_ao_params* p, pt_ao_hit* out, pt_ray* out_ao_rays);
+
+/* ---- point queries: the nearest surface to the CALLER'S points (no reference counterpart: the reference answers questions about its
+ * own rays only) ----
+ * pt_closest_point answers "how far is this point from the scene, and where is the nearest surface" - distance fields for collision
+ * and contact, proximity shading, snapping bake samples and particles to a surface, distance supervision for implicit models - on the
+ * hierarchy that is in HBM already and that pt_update_vertices refits.  A kernel of its own (csrc/pt_kernel_points.hip): NOT a variant
+ * of the ray walk but a nearest-first, distance-pruned descent of the quad tree, with point-to-box distances where the rays have slab
+ * tests and a point-to-triangle kernel where they have a ray-triangle test.  The CPU twin is pt_debug_closest_point_host; kernel and
+ * twin compile the per-triangle code and the box distance from one header, csrc/pt_points_math.h.
+ * DEFINITION, per point (a pt_point: 16 bytes, one 16-byte load; out: a pt_point_hit, 32 bytes, two 16-byte stores).  Arithmetic under
+ * the contract of csrc/pt_device.h: binary32, no contraction, correctly rounded / and sqrt, and its dot(a, b) = fma_(a.z, b.z,
+ * fma_(a.y, b.y, a.x * b.x)), sqrt_ and max_.  v3 * scalar and v3 +- v3 are per component.
+ *   SEARCH BOUND.  rmax = radius < 1e10f ? radius : 1e10f: NaN and +infinity give the library's own bound.  r2 = rmax * rmax.  A
+ *   negative radius (rmax < 0) finds nothing, whatever r2 is.
+ *   PER TRIANGLE (p0, p1, p2) with global id `id`, and x = p.  A triangle that the sliver rule collapsed (p0 == p1 == p2) is never a
+ *   candidate.  Otherwise, in exactly this order (Ericson, "Real-Time Collision Detection", 5.1.5):
+ *     1. ab = p1 - p0, ac = p2 - p0, ap = x - p0, d1 = dot(ab, ap), d2 = dot(ac, ap).
+ *        If d1 <= 0 && d2 <= 0: q = p0, (u, v) = (0, 0), feature 1.
+ *     2. bp = x - p1, d3 = dot(ab, bp), d4 = dot(ac, bp).  If d3 >= 0 && d4 <= d3: q = p1, (1, 0), feature 2.
+ *     3. vc = d1*d4 - d3*d2.  If vc <= 0 && d1 >= 0 && d3 <= 0: s = d1 / (d1 - d3), q = p0 + ab*s, (s, 0), feature 4.
+ *     4. cp = x - p2, d5 = dot(ab, cp), d6 = dot(ac, cp).  If d6 >= 0 && d5 <= d6: q = p2, (0, 1), feature 3.
+ *     5. vb = d5*d2 - d1*d6.  If vb <= 0 && d2 >= 0 && d6 <= 0: s = d2 / (d2 - d6), q = p0 + ac*s, (0, s), feature 6.
+ *     6. va = d3*d6 - d5*d4, e = d4 - d3, f = d5 - d6.  If va <= 0 && e >= 0 && f >= 0: s = e / (e + f), q = p1 + (p2 - p1)*s,
+ *        (1 - s, s), feature 5.
+ *     7. Else: k = 1.0f / ((va + vb) + vc), v = vb*k, w = vc*k, q = (p0 + ab*v) + ac*w, (v, w), feature 0.
+ *   Then e = x - q per component and dd = dot(e, e).  u weighs p1 and v weighs p2: the convention of pt_ray_hit.  feature: 0 the face,
+ *   1 / 2 / 3 the vertex p0 / p1 / p2, 4 / 5 / 6 the edge p0p1 / p1p2 / p0p2.
+ *   WINNER.  The search starts at best = r2, best_id = 0x7fffffff; a triangle replaces the best iff dd < best || (dd == best && id <
+ *   best_id).  So a NaN dd never wins, a point at exactly dd == r2 is found, and ties - a point nearest to a shared vertex or edge, a
+ *   mesh uploaded twice - go to the lower global triangle id.
+ *   RECORD.  out = {sqrt_(dd), u, v, prim, q, feature}, prim the global triangle id (pt_prim_to_mesh inverts it); nothing found is
+ *   prim = -1 and every other word +0.  All 32 bytes are written for every point.
+ * The result is a property of the scene and the point: it does not depend on the hierarchy, the visiting order, the grid or the refill
+ * setting.  WHY: the walk skips a box only when dbox > best (strictly), with dbox = dot(a, a), a = max_(max_(lo - x, x - hi), 0) per
+ * axis.  dbox and dd are built from the same monotone, correctly rounded operations, so if the computed q of a triangle lies inside a
+ * box, lo <= q <= hi per axis, then |fl(x - q)| >= a per axis and dd >= dbox bit for bit; every ancestor's box contains the leaf's box
+ * with the builders' pad.  THE PREMISE is therefore that the computed q of the winning triangle lies inside that triangle's padded leaf
+ * box.  The pad is 1e-5 of E = max(scene extent, largest |coordinate| of the scene), 2^-16.6 E.  A vertex q is exact.  An edge q =
+ * p + e*s has 0 <= s <= 1 - s is a non-negative number over its sum with another - and two roundings, under 2^-22 E.  Step 7 is reached
+ * with va, vb, vc > 0 wherever the conditions of the earlier steps agree with each other, and then v, w and 1 - v - w lie in (0, 1)
+ * WHATEVER cancellation did to their values: q is a convex combination of the vertices up to four roundings.  So the distance of the
+ * point decides how well q is PLACED on the triangle (v and w are differences of products that cancel: their relative error grows
+ * with the square of distance over edge length), not whether q lies on it, and the premise asks only the latter.  What remains is
+ * step 7 reached with a weight <= 0, where rounding made steps 3, 5 and 6 contradict one another; q then leaves the triangle by
+ * |weight| times an edge.
+ *   DOMAIN: finite points whose largest |coordinate| is within 10 E - the ray queries' "within 10 extents" - on scenes of finite
+ *   triangles.  tests/test_closest_point_host.py asserts the premise on every case it uses, for the winner of every point and for
+ *   every triangle on a subsample, out to 10 E.  Outside the domain every form is still a valid evaluation of the steps above on the
+ *   triangles it visits, and two forms may then report different triangles.
+ * The call honours pt_update_vertices, "rays_refill" and "rays_grid" (the lane refill and the ranges of pt_trace_closest).  It ignores
+ * the pixel shard, materials, environment, "watertight" and "box_exact".  With a communicator it issues no collective.  It needs quad
+ * nodes: a scene loaded with option "quad" = 0, or one whose tree is too deep for them, is refused with PT_E_INVALID by name.  It keeps
+ * no render state: a pt_render after it is bit for bit the one before.  n == 0 is PT_OK with no launch.
+ * REFUSED with PT_E_INVALID, by name, before anything is touched: NULL pts or out with n > 0; n < 0 or n >= 2^31; a d_pts or a d_out
+ * that is not 16-byte aligned.  PT_E_NO_SCENE without a scene.  On a host-only context valid arguments give PT_E_NO_DEVICE and invalid
+ * ones PT_E_INVALID; the twin works there.
+ * ORDERING: pt_closest_point_device (device pointers, `stream` NULL = the context's) joins the asynchronous calls of the streams
+ * contract at pt_render_device and the list at pt_synchronize.  The blocking form stages the points, runs on the context's stream
+ * behind the same device-side wait, and reads back; the context is idle on return.
+ * THE WALK: a wave owns a contiguous range of points (a multiple of 64) and refills its idle lanes from it when no more than
+ * "rays_refill" lanes are still walking; the call cuts four times as many, shorter ranges as pt_trace_closest (never shorter than 64
+ * points; "rays_grid" caps their number as it does there), because points far from every surface cost many times the steps of points
+ * next to one.  A lane's stack is in LDS with the deeper levels in the wave's HBM column; an entry is the child's reference alone, and
+ * one that the best distance has overtaken costs a step that enters nothing (the form that keeps the box distance beside the reference
+ * measured slower).  Every walk is bounded in steps and stack; pt_synchronize returns PT_E_HIP if one ran out of a bound (that point is
+ * reported as not found), as for the ray queries.  pt_get_stats afterwards: kernel_ms and launches (1) are the point launch's, and so
+ * are block, grid, vgprs, lds_bytes, stack_entries.
+ * NOT BUILT: a sign (inside or outside); the k nearest triangles; pt_group_*, batch and pt_main forms. */
+typedef struct pt_point     { float p[3]; float radius; } pt_point;                                          /* 16 bytes, one 16-byte load */
+typedef struct pt_point_hit { float dist, u, v; int32_t prim; float q[3]; int32_t feature; } pt_point_hit;   /* 32 bytes, two 16-byte stores */
+int pt_closest_point        (pt_ctx* ctx, const pt_point* pts, int64_t n, pt_point_hit* out);
+int pt_closest_point_device (pt_ctx* ctx, const void* d_pts, int64_t n, void* d_out /* n pt_point_hit, 16-byte aligned */, void* stream);
+/* The CPU twin: the definition above by brute force over the host copy of the triangles in leaf order, on all host threads - the
+ * definition, not a walk; works on a host-only context, follows pt_update_vertices.  Returns n. */
+int64_t pt_debug_closest_point_host(pt_ctx* ctx, const pt_point* pts, int64_t n, pt_point_hit* out);
 
 /* ---- ray images: path-traced radiance along the CALLER'S rays (no reference counterpart: the reference starts every path at its one
  * pinhole camera, device.cu:231-241) ----

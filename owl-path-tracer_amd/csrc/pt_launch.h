@@ -264,6 +264,12 @@ hipError_t pt_launch_rays_ao(const PtKernelParams* p, const PtAoArgs* a, int gri
 hipError_t pt_rays_ao_geometry(int exact, PtGeometry* g);
 hipError_t pt_launch_rays_ao_wt(const PtKernelParams* p, const PtAoArgs* a, int grid, size_t lds_bytes, hipStream_t stream);
 hipError_t pt_rays_ao_geometry_wt(int exact, PtGeometry* g);
+// pt_kernel_points.hip: the point kernel (pt_closest_point), one instance.  a: the ray kernels' arguments with a->rays = n pt_point records
+// (16 bytes), a->out = n pt_point_hit (32 bytes), both 16-byte aligned, and a->cap in stack ENTRIES of pt_points_entry_words() words each:
+// a->ovf holds (cap * words - g->lds_levels) * 64 words per workgroup, g->lds_levels being the words of a lane's stack kept in LDS
+hipError_t pt_launch_points(const PtKernelParams* p, const PtRaysArgs* a, int grid, size_t lds_bytes, hipStream_t stream);
+hipError_t pt_points_geometry(PtGeometry* g);
+int pt_points_entry_words(void);
 // pt_kernel_aov_follow.hip / pt_kernel_aov_follow_wt.hip: the follow kernels, same conventions; lds_bytes covers the stack and the state a lane parks behind it
 hipError_t pt_launch_aov_follow(const PtKernelParams* p, const PtAovFollowArgs* a, int binary, int grid, size_t lds_bytes, hipStream_t stream);
 hipError_t pt_aov_follow_geometry(int binary, int exact, int stack_entries, PtGeometry* g);

@@ -48,6 +48,9 @@ hipError_t pt_launch_rays_ao(const PtKernelParams*, const PtAoArgs*, int, size_t
 hipError_t pt_rays_ao_geometry(int, PtGeometry*) { return hipErrorNotSupported; }
 hipError_t pt_launch_rays_ao_wt(const PtKernelParams*, const PtAoArgs*, int, size_t, hipStream_t) { return hipErrorNotSupported; }
 hipError_t pt_rays_ao_geometry_wt(int, PtGeometry*) { return hipErrorNotSupported; }
+hipError_t pt_launch_points(const PtKernelParams*, const PtRaysArgs*, int, size_t, hipStream_t) { return hipErrorNotSupported; }
+hipError_t pt_points_geometry(PtGeometry*) { return hipErrorNotSupported; }
+int pt_points_entry_words(void) { return 1; }
 size_t pt_denoise_workspace_bytes(int, int) { return 16; }
 hipError_t pt_denoise_geometry(int, int, PtGeometry*, int*) { return hipErrorNotSupported; }
 hipError_t pt_launch_denoise(const PtDenoiseArgs*, hipStream_t) { return hipErrorNotSupported; }

@@ -139,6 +139,7 @@ EXPORTS = ["pt_create", "pt_destroy", "pt_last_error", "pt_abi_version", "pt_upl
            "pt_upsample_default_params", "pt_upsample", "pt_upsample_device", "pt_debug_upsample_host",
            "pt_trace_closest", "pt_trace_closest_device", "pt_trace_occluded", "pt_trace_occluded_device", "pt_debug_trace_rays_host", "pt_prim_to_mesh", "pt_trace_surface", "pt_trace_surface_device", "pt_debug_trace_surface_host",
            "pt_ao_default_params", "pt_trace_ao", "pt_trace_ao_device", "pt_debug_trace_ao_host",
+           "pt_closest_point", "pt_closest_point_device", "pt_debug_closest_point_host",
            "pt_render_rays", "pt_render_rays_device", "pt_render_aov_rays", "pt_render_aov_rays_device", "pt_debug_aov_rays_host"]
 # pt_ray / pt_ray_hit (include/mi355pt.h "ray queries"): 32 and 16 bytes
 RAY_DTYPE = np.dtype([("org", "<f4", (3,)), ("tmax", "<f4"), ("dir", "<f4", (3,)), ("unused", "<f4")])
@@ -152,6 +153,10 @@ assert SURFACE_DTYPE.itemsize == 80
 AO_DTYPE = np.dtype([("t", "<f4"), ("u", "<f4"), ("v", "<f4"), ("prim", "<i4"), ("n", "<f4", (3,)), ("ao", "<f4")])
 assert AO_DTYPE.itemsize == 32 and C.sizeof(AoParams) == 16
 PT_AO_SHADING_NORMAL = 1
+# pt_point / pt_point_hit (include/mi355pt.h "point queries: the nearest surface"): 16 and 32 bytes
+POINT_DTYPE = np.dtype([("p", "<f4", (3,)), ("radius", "<f4")])
+POINT_HIT_DTYPE = np.dtype([("dist", "<f4"), ("u", "<f4"), ("v", "<f4"), ("prim", "<i4"), ("q", "<f4", (3,)), ("feature", "<i4")])
+assert POINT_DTYPE.itemsize == 16 and POINT_HIT_DTYPE.itemsize == 32
 # pt_ray_gen (include/mi355pt.h "ray images"): 64 bytes; pyhost/ray_image.py builds tables of these
 RAY_GEN_DTYPE = np.dtype([("org", "<f4", (3,)), ("reserved0", "<f4"), ("dir", "<f4", (3,)), ("reserved1", "<f4"),
                           ("du", "<f4", (3,)), ("reserved2", "<f4"), ("dv", "<f4", (3,)), ("reserved3", "<f4")])
@@ -321,6 +326,10 @@ def lib():
     L.pt_trace_ao_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(AoParams), C.c_void_p, C.c_void_p]
     L.pt_debug_trace_ao_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(AoParams), C.c_void_p, C.c_void_p]
     L.pt_debug_trace_ao_host.restype = C.c_int64
+    L.pt_closest_point.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    L.pt_closest_point_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    L.pt_debug_closest_point_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    L.pt_debug_closest_point_host.restype = C.c_int64
     L.pt_render_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, fp, C.POINTER(C.c_uint32)]
     L.pt_render_rays_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     L.pt_render_aov_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(AovParams), fp]
@@ -419,6 +428,21 @@ def _rays(rays):
     """pt_ray records as a contiguous RAY_DTYPE array (an (n, 6) float array gets tmax = +inf)."""
     a = np.asarray(rays)
     return np.ascontiguousarray(a) if a.dtype == RAY_DTYPE else make_rays(a)
+
+
+def make_points(points, radius=np.inf):
+    """(n, 3) float32 positions -> n pt_point records (POINT_DTYPE) with the given radius or radii: a scalar or n values."""
+    p = np.asarray(points, np.float32).reshape(-1, 3)
+    out = np.zeros(p.shape[0], POINT_DTYPE)
+    out["p"] = p
+    out["radius"] = np.asarray(radius, np.float32)
+    return out
+
+
+def _points(points):
+    """pt_point records as a contiguous POINT_DTYPE array (an (n, 3) float array gets radius = +inf)."""
+    a = np.asarray(points)
+    return np.ascontiguousarray(a) if a.dtype == POINT_DTYPE else make_points(a)
 
 
 def denoise_default_params(**changes):
@@ -1109,6 +1133,28 @@ class Context:
         """pt_trace_ao_device: asynchronous as trace_closest_device, n pt_ao_hit records (32 bytes each) left at d_out (16-byte aligned)."""
         self._check(lib().pt_trace_ao_device(self._h, C.c_void_p(d_rays), int(n), C.byref(params) if params is not None else None, C.c_void_p(d_out),
                                              C.c_void_p(stream) if stream else None), "pt_trace_ao_device")
+
+    def _points(self, fn, what, points):
+        p = _points(points)
+        out = np.empty(p.shape[0], POINT_HIT_DTYPE)
+        rc = fn(self._h, p.ctypes.data_as(C.c_void_p), p.shape[0], out.ctypes.data_as(C.c_void_p))
+        self._check(int(rc), what)
+        return out
+
+    def closest_point(self, points):
+        """pt_closest_point: the nearest triangle to every point (POINT_DTYPE records, or (n, 3) positions with radius = +inf) as a
+        POINT_HIT_DTYPE array {dist, u, v, prim, q, feature}; nothing within the radius is prim = -1 and zeros (include/mi355pt.h
+        "point queries")."""
+        return self._points(lib().pt_closest_point, "pt_closest_point", points)
+
+    def closest_point_host(self, points):
+        """pt_debug_closest_point_host, the CPU twin of closest_point: brute force over every triangle (works on a host-only context)."""
+        return self._points(lib().pt_debug_closest_point_host, "pt_debug_closest_point_host", points)
+
+    def closest_point_device(self, d_pts, n, d_out, stream=None):
+        """pt_closest_point_device: asynchronous as trace_closest_device, n pt_point records (16 bytes each) at d_pts, n pt_point_hit
+        records (32 bytes each) left at d_out, both 16-byte aligned."""
+        self._check(lib().pt_closest_point_device(self._h, C.c_void_p(d_pts), int(n), C.c_void_p(d_out), C.c_void_p(stream) if stream else None), "pt_closest_point_device")
 
     def prim_to_mesh(self, prim):
         """pt_prim_to_mesh: (entity of the upload, triangle inside it) of a global triangle id."""
