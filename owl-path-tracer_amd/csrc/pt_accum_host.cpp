@@ -1,7 +1,7 @@
 // pt_accum_host.cpp -- the progressive accumulation (pt_accum_*; include/mi355pt.h, "progressive accumulation"): a frame that grows by
 // adds.  This file owns the accumulation's state across calls (Accum, pt_internal.h), runs an add - select, the frame path of
 // pt_render.cpp over the active set (pti::accum_frame), resolve - and holds the CPU twins of the two kernels of pt_accum.hip, which
-// compile the very definition the kernels compile (pt_accum_math.h with PTD = static inline, as pt_denoise_host.cpp does).
+// compile the very definition the kernels compile (pt_accum_math.h with PTD = static inline: pt_device_host.h).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -10,14 +10,8 @@
 #include <limits>
 #include <vector>
 
-static inline uint32_t pt_host_float_as_uint(float x) { uint32_t u; std::memcpy(&u, &x, 4); return u; }
-static inline float pt_host_uint_as_float(uint32_t u) { float x; std::memcpy(&x, &u, 4); return x; }
-#define __float_as_uint pt_host_float_as_uint
-#define __uint_as_float pt_host_uint_as_float
-#define PTD static inline
+#include "pt_device_host.h"
 #include "pt_accum_math.h"
-#undef __float_as_uint
-#undef __uint_as_float
 
 #include "pt_internal.h"
 #include "pt_launch.h"
@@ -372,9 +366,7 @@ int pt_accum_add_device(pt_ctx* c, const pt_accum_params* p, void* d_out_rgb, vo
     pt_accum_params prm;
     int rc;
     if ((rc = check_add(c, "pt_accum_add_device", p, &prm)) || (rc = need_device(c))) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t stream = stream_v ? (hipStream_t)stream_v : c->stream;
-    return async_call(c, stream, [&] { return add_device(c, prm, d_out_rgb, d_out_rgba8, stream); });
+    return async_call_on(c, stream_v, [&](hipStream_t stream) { return add_device(c, prm, d_out_rgb, d_out_rgba8, stream); });
 }
 
 int pt_accum_add(pt_ctx* c, const pt_accum_params* p, float* out_rgb, uint32_t* out_rgba8)
@@ -537,9 +529,7 @@ int pt_accum_reproject_device(pt_ctx* c, const pt_camera* new_cam, const void* d
     pt_reproject_params prm;
     int rc;
     if ((rc = check_reproject(c, "pt_accum_reproject_device", new_cam, d_aov_prev, d_aov_cur, p, &prm))) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t stream = stream_v ? (hipStream_t)stream_v : c->stream;
-    return async_call(c, stream, [&] { return reproject_device(c, *new_cam, prm, d_aov_prev, d_aov_cur, stream); });
+    return async_call_on(c, stream_v, [&](hipStream_t stream) { return reproject_device(c, *new_cam, prm, d_aov_prev, d_aov_cur, stream); });
 }
 
 int pt_accum_reproject(pt_ctx* c, const pt_camera* new_cam, const float* aov_prev, const float* aov_cur, const pt_reproject_params* p)

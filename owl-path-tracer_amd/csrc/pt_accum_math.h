@@ -1,7 +1,7 @@
 // pt_accum_math.h -- the per-pixel definition of the progressive accumulation (include/mi355pt.h, "progressive accumulation"): resolve
 // and select, the variance of a pixel and its reprojection to a new camera, ONE copy for the kernels of pt_accum.hip, pt_denoise_var.hip
-// and pt_accum_reproject.hip and their CPU twins in pt_accum_host.cpp (which include pt_device.h with
-// PTD = static inline first, as pt_denoise_host.cpp does).  Arithmetic: the contract of pt_device.h - binary32, no contraction, correctly
+// and pt_accum_reproject.hip and their CPU twins in pt_accum_host.cpp (which include pt_device_host.h
+// first: PTD = static inline).  Arithmetic: the contract of pt_device.h - binary32, no contraction, correctly
 // rounded division, its sqrt_, abs_, max_ and make_rgba.
 #pragma once
 #include "pt_device.h"

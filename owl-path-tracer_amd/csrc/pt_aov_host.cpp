@@ -1,7 +1,7 @@
 // pt_aov_host.cpp -- pt_debug_aov_host: the CPU twin of the guide pass (pt_render_aov; kernel: pt_kernel.hip "guide pass"), and
 // pt_debug_aov_follow_host, the twin of its follow mode (pt_render_aov_follow; "guide pass, follow mode"), with that mode's parameter checks.
 // The twin runs the definition of include/mi355pt.h with the host walk of pt_debug_closest_hit_host_n over the host copies of the
-// scene, and with the arithmetic of pt_device.h itself: the header is included here with PTD = static inline, so rng_init, rng_next,
+// scene, and with the arithmetic of pt_device.h itself: the header is included here with PTD = static inline (pt_device_host.h), so rng_init, rng_next,
 // normalize, lerp3, uv_on_sphere (the polynomial atan2 / asin), tex_nearest and the material row are the functions the kernel
 // compiles, run by the CPU under the same contract (binary32, -ffp-contract=off, fma only where spelled, correctly rounded division
 // and sqrt).  What is restated here is what the kernel takes from pt_trace.h, which is device code throughout: the camera ray
@@ -16,16 +16,8 @@
 #include <cstring>
 #include <vector>
 
-// the four bit casts pt_device.h uses are device functions of the HIP headers: host forms under the same names
-static inline uint32_t pt_host_float_as_uint(float x) { uint32_t u; std::memcpy(&u, &x, 4); return u; }
-static inline float pt_host_uint_as_float(uint32_t u) { float x; std::memcpy(&x, &u, 4); return x; }
-#define __float_as_uint pt_host_float_as_uint
-#define __uint_as_float pt_host_uint_as_float
-#define PTD static inline
-#include "pt_device.h"
+#include "pt_device_host.h"
 #include "pt_ao_math.h"
-#undef __float_as_uint
-#undef __uint_as_float
 
 #include "pt_internal.h"
 

@@ -12,7 +12,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#ifndef PTD // (pt_aov_host.cpp defines it empty-handed - static inline - and so runs these very functions on the CPU: the guide pass's twin)
+#ifndef PTD // (a host source gets static inline from pt_device_host.h and so runs these very functions on the CPU: the CPU twins)
 #define PTD __device__ __forceinline__
 #endif
 

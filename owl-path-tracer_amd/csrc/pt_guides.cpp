@@ -171,11 +171,12 @@ int aov_device(pt_ctx* c, const AovJob& j)
 // The asynchronous entry points, after their checks: on the caller's stream (null: the context's), no reduce.
 int aov_async(pt_ctx* c, AovJob j, void* d_out_aov, void* stream_v)
 {
-    HIP_TRY(c, hipSetDevice(c->device));
     j.d_out = d_out_aov;
-    j.stream = stream_v ? (hipStream_t)stream_v : c->stream;
     j.reduce = false;
-    return async_call(c, j.stream, [&] { return aov_device(c, j); });
+    return async_call_on(c, stream_v, [&](hipStream_t stream) {
+        j.stream = stream;
+        return aov_device(c, j);
+    });
 }
 
 // The blocking entry points, after their checks: into d_aov, reduced, and from there to the host buffer of the root (with a
@@ -286,9 +287,7 @@ int denoise_device(pt_ctx* c, const DenoiseJob& j, const void* d_rgb, const void
 
 int denoise_async(pt_ctx* c, const DenoiseJob& j, const void* d_rgb, const void* d_aov, void* d_out_rgb, void* d_out_rgba8, void* stream_v)
 {
-    HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t stream = stream_v ? (hipStream_t)stream_v : c->stream;
-    return async_call(c, stream, [&] { return denoise_device(c, j, d_rgb, d_aov, d_out_rgb, d_out_rgba8, stream); });
+    return async_call_on(c, stream_v, [&](hipStream_t stream) { return denoise_device(c, j, d_rgb, d_aov, d_out_rgb, d_out_rgba8, stream); });
 }
 
 // Host buffers: staged in d_dn_rgb / d_dn_aov, filtered in place on the staging copy, and back.
@@ -345,9 +344,7 @@ int upsample_device(pt_ctx* c, const UpsampleJob& j, const void* d_rgb_lo, const
 
 int upsample_async(pt_ctx* c, const UpsampleJob& j, const void* d_rgb_lo, const void* d_aov_lo, const void* d_aov_hi, void* d_out_rgb, void* d_out_rgba8, void* stream_v)
 {
-    HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t stream = stream_v ? (hipStream_t)stream_v : c->stream;
-    return async_call(c, stream, [&] { return upsample_device(c, j, d_rgb_lo, d_aov_lo, d_aov_hi, d_out_rgb, d_out_rgba8, stream); });
+    return async_call_on(c, stream_v, [&](hipStream_t stream) { return upsample_device(c, j, d_rgb_lo, d_aov_lo, d_aov_hi, d_out_rgb, d_out_rgba8, stream); });
 }
 
 // Host buffers: the low frame and its guides staged in d_up_rgb / d_up_aov, the high guides in d_dn_aov, the result in d_dn_rgb (and
@@ -433,9 +430,7 @@ int denoise_var_device(pt_ctx* c, const DenoiseVarJob& j, const void* d_rgb, con
 
 int denoise_var_async(pt_ctx* c, const DenoiseVarJob& j, const void* d_rgb, const void* d_var, const void* d_aov, void* d_out_rgb, void* d_out_rgba8, void* stream_v)
 {
-    HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t stream = stream_v ? (hipStream_t)stream_v : c->stream;
-    return async_call(c, stream, [&] { return denoise_var_device(c, j, d_rgb, d_var, d_aov, d_out_rgb, d_out_rgba8, stream); });
+    return async_call_on(c, stream_v, [&](hipStream_t stream) { return denoise_var_device(c, j, d_rgb, d_var, d_aov, d_out_rgb, d_out_rgba8, stream); });
 }
 
 // Host buffers: staged in d_dn_rgb / d_dn_var / d_dn_aov, filtered into d_dn_rgb, and back.  accum: only the guides are staged.

@@ -1,6 +1,9 @@
 // pt_internal.h -- private to the library: the context behind the opaque pt_ctx of include/mi355pt.h and the helpers its host sources
 // share: pt_api.cpp (context, options, stats), pt_scene.cpp (scene upload and clone), pt_render.cpp (frames and batches), pt_guides.cpp
-// (guide pass and denoiser), pt_accum_host.cpp (progressive accumulation and its reprojection), pt_rays_host.cpp (ray queries), pt_debug.cpp (probes and readers) and pt_comm.cpp (RCCL reduce, multi-GPU group).
+// (guide pass and the device paths of the filters), pt_aov_host.cpp, pt_denoise_host.cpp and pt_upsample_host.cpp (refusals, constants
+// and CPU twins of the guide pass, the two denoisers and the upsampler), pt_accum_host.cpp (progressive accumulation and its
+// reprojection), pt_rays_host.cpp (ray queries), pt_points_host.cpp (point queries), pt_debug.cpp (probes and readers) and pt_comm.cpp
+// (RCCL reduce, multi-GPU group). A source that runs device arithmetic on the CPU includes pt_device_host.h before its *_math.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -241,6 +244,12 @@ PT_LOCAL void ao_ray_host(const HostScene& S, const std::vector<int32_t>& slot_o
 PT_LOCAL int reduce_framebuffer(pt_ctx* c, void* d_rgb, void* d_rgba8, int64_t n_pixels, hipStream_t stream); // pt_reduce_framebuffer inside a call that is ordered already
 PT_LOCAL int reduce_sum(pt_ctx* c, void* d_buf, size_t n_floats, hipStream_t stream); // in-place sum-reduce onto rank 0; nothing without a communicator
 
+#define HIP_TRY(c, call)                                                                                   \
+    do {                                                                                                   \
+        hipError_t e__ = (call);                                                                           \
+        if (e__ != hipSuccess) return pti::fail(c, PT_E_HIP, "%s failed: %s", #call, hipGetErrorString(e__)); \
+    } while (0)
+
 // An asynchronous entry point around `enqueue`: ordered after the context's last asynchronous call on the device, and itself the last
 // one from here on - also when it failed half-way, for what it did enqueue.
 template <class F> int async_call(pt_ctx* c, hipStream_t stream, F enqueue)
@@ -250,6 +259,15 @@ template <class F> int async_call(pt_ctx* c, hipStream_t stream, F enqueue)
     rc = enqueue();
     const int rm = mark_last(c, stream);
     return rc ? rc : rm;
+}
+
+// async_call for an entry point that takes the caller's stream as void*: on the context's device and on that stream (null: the context's
+// own), which `enqueue` receives.
+template <class F> int async_call_on(pt_ctx* c, void* stream_v, F enqueue)
+{
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t stream = stream_v ? (hipStream_t)stream_v : c->stream;
+    return async_call(c, stream, [&] { return enqueue(stream); });
 }
 
 // A blocking render around `run`, which enqueues on the context's stream and drains it: ordered after the last asynchronous call like
@@ -263,9 +281,3 @@ template <class F> int blocking_call(pt_ctx* c, F run)
     return rc;
 }
 } // namespace pti
-
-#define HIP_TRY(c, call)                                                                                   \
-    do {                                                                                                   \
-        hipError_t e__ = (call);                                                                           \
-        if (e__ != hipSuccess) return pti::fail(c, PT_E_HIP, "%s failed: %s", #call, hipGetErrorString(e__)); \
-    } while (0)

@@ -11,15 +11,8 @@
 #include <algorithm>
 #include <cstring>
 
-// the bit casts pt_device.h uses are device functions of the HIP headers: host forms under the same names, as in pt_aov_host.cpp
-static inline uint32_t pt_host_float_as_uint(float x) { uint32_t u; std::memcpy(&u, &x, 4); return u; }
-static inline float pt_host_uint_as_float(uint32_t u) { float x; std::memcpy(&x, &u, 4); return x; }
-#define __float_as_uint pt_host_float_as_uint
-#define __uint_as_float pt_host_uint_as_float
-#define PTD static inline
+#include "pt_device_host.h"
 #include "pt_points_math.h"
-#undef __float_as_uint
-#undef __uint_as_float
 
 #include "pt_internal.h"
 #include "pt_launch.h"
@@ -98,9 +91,7 @@ int pt_closest_point_device(pt_ctx* c, const void* d_pts, int64_t n, void* d_out
     int rc;
     if ((rc = check_points_args(c, "pt_closest_point_device", d_pts, n, d_out, true))) return rc;
     if (n == 0) return PT_OK;
-    HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t stream = stream_v ? (hipStream_t)stream_v : c->stream;
-    return async_call(c, stream, [&] { return points_device(c, d_pts, n, d_out, stream); });
+    return async_call_on(c, stream_v, [&](hipStream_t stream) { return points_device(c, d_pts, n, d_out, stream); });
 }
 
 // Host buffers: the points staged in d_rays_in, the records in d_rays_out, and back.

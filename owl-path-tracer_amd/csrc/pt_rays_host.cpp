@@ -131,9 +131,7 @@ int rays_async(pt_ctx* c, const char* who, RaysMode mode, const void* d_rays, in
     if (mode == kAo && (rc = check_ao_params(c, who, ao, &prm))) return rc;
     if ((rc = check_rays_args(c, who, d_rays, n, d_out, true, mode))) return rc;
     if (n == 0) return PT_OK;
-    HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t stream = stream_v ? (hipStream_t)stream_v : c->stream;
-    return async_call(c, stream, [&] { return rays_device(c, mode, d_rays, n, d_out, stream, &prm); });
+    return async_call_on(c, stream_v, [&](hipStream_t stream) { return rays_device(c, mode, d_rays, n, d_out, stream, &prm); });
 }
 
 // Host buffers: the rays staged in d_rays_in, the results in d_rays_out, and back.

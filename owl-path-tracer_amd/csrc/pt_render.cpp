@@ -830,9 +830,7 @@ int pt_render_device(pt_ctx* c, const pt_camera* cam, int32_t W, int32_t H, int3
     if (!c || !cam || !d_out_rgb) return PT_E_INVALID;
     int rc;
     if ((rc = need_device(c)) || (rc = check_render_args(c, W, H, max_samples, max_depth))) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t stream = stream_v ? (hipStream_t)stream_v : c->stream;
-    return async_call(c, stream, [&] { return render_device(c, cam, W, H, max_samples, max_depth, d_out_rgb, d_out_rgba8, stream); });
+    return async_call_on(c, stream_v, [&](hipStream_t stream) { return render_device(c, cam, W, H, max_samples, max_depth, d_out_rgb, d_out_rgba8, stream); });
 }
 
 int pt_synchronize(pt_ctx* c)
@@ -875,10 +873,8 @@ int pt_render_rays_device(pt_ctx* c, const void* d_rays, int32_t W, int32_t H, i
     if (!c) return PT_E_INVALID;
     int rc;
     if ((rc = check_ray_image_args(c, "pt_render_rays_device", d_rays, W, H, max_samples, max_depth, d_out_rgb, true))) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t stream = stream_v ? (hipStream_t)stream_v : c->stream;
     // the records are the caller's and unknown here: the slab form that holds at any distance, unless the option chooses
-    return async_call(c, stream, [&] { return rays_image_device(c, d_rays, INFINITY, W, H, max_samples, max_depth, d_out_rgb, d_out_rgba8, stream); });
+    return async_call_on(c, stream_v, [&](hipStream_t stream) { return rays_image_device(c, d_rays, INFINITY, W, H, max_samples, max_depth, d_out_rgb, d_out_rgba8, stream); });
 }
 
 int pt_render_rays(pt_ctx* c, const pt_ray_gen* rays, int32_t W, int32_t H, int32_t max_samples, int32_t max_depth, float* out_rgb, uint32_t* out_rgba8)
@@ -904,9 +900,7 @@ int pt_render_batch_device(pt_ctx* c, const pt_frame* frames, int32_t n_frames, 
 {
     if (!c || !d_out_rgb) return PT_E_INVALID;
     if (c->host_only) return batch_device(c, frames, n_frames, n_materials, W, H, max_samples, max_depth, d_out_rgb, d_out_rgba8, nullptr, nullptr, false); // (refused there, with its message)
-    HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t stream = stream_v ? (hipStream_t)stream_v : c->stream;
-    return async_call(c, stream, [&] { return batch_device(c, frames, n_frames, n_materials, W, H, max_samples, max_depth, d_out_rgb, d_out_rgba8, nullptr, stream, false); });
+    return async_call_on(c, stream_v, [&](hipStream_t stream) { return batch_device(c, frames, n_frames, n_materials, W, H, max_samples, max_depth, d_out_rgb, d_out_rgba8, nullptr, stream, false); });
 }
 
 int pt_render_batch(pt_ctx* c, const pt_frame* frames, int32_t n_frames, int32_t n_materials, int32_t W, int32_t H, int32_t max_samples, int32_t max_depth,

@@ -1,22 +1,11 @@
 // pt_upsample_host.cpp -- pt_debug_upsample_host: the CPU twin of the upsampling (pt_upsample; kernels: pt_upsample.hip), and what the
 // twin and the device path share on the host: the default parameters, the refusals and the host constants.
-// The twin runs the definition of include/mi355pt.h ("upsampling") with the arithmetic of pt_device.h itself: the header is included here
-// with PTD = static inline, so exp_, dot, max_, abs_ and make_rgba are the functions the kernels compile, run by the CPU under the same
-// contract (binary32, -ffp-contract=off, fma only where spelled, correctly rounded division).  Rows are spread over all host threads.
-#include <hip/hip_runtime.h>
+// The twin compiles the per-pixel definition the kernels compile, pt_filter_math.h with PTD = static inline (pt_device_host.h), and keeps
+// the loops around it: prepare over the low pixels, upsample over the high rows.  Rows are spread over all host threads.
+#include "pt_device_host.h"
+#include "pt_filter_math.h"
 
-#include <cstring>
 #include <vector>
-
-// the bit casts pt_device.h uses are device functions of the HIP headers: host forms under the same names (as pt_aov_host.cpp)
-static inline uint32_t pt_host_float_as_uint(float x) { uint32_t u; std::memcpy(&u, &x, 4); return u; }
-static inline float pt_host_uint_as_float(uint32_t u) { float x; std::memcpy(&x, &u, 4); return x; }
-#define __float_as_uint pt_host_float_as_uint
-#define __uint_as_float pt_host_uint_as_float
-#define PTD static inline
-#include "pt_device.h"
-#undef __float_as_uint
-#undef __uint_as_float
 
 #include "pt_internal.h"
 
@@ -56,68 +45,6 @@ void upsample_constants(const pt_upsample_params& p, int w, int h, int W, int H,
 
 } // namespace pti
 
-namespace {
-
-struct Rec { float x, y, z, w; };
-
-float finite_or_0(float v) { return (isinf_(v) || isnan_(v)) ? 0.0f : v; }
-float up_div(float a) { return max_(a, 1e-3f); }
-
-struct Consts { int w, h, W, taps, flags; float sigma_depth, rx, ry, kn, ka, ir; };
-
-// One high pixel: include/mi355pt.h, "upsampling"; the kernel's body (pt_upsample_kernel) line for line.
-v3 upsample_pixel(const Rec* col, const Rec* nzb, const Rec* alb, const float* aov_hi, const Consts& A, int x, int row)
-{
-    const int w = A.w, h = A.h;
-    const size_t p = (size_t)row * (size_t)A.W + (size_t)x;
-    const float* g = aov_hi + 8 * p;
-    const v3 a_p = V(g[0], g[1], g[2]), n_p = V(g[4], g[5], g[6]);
-    const float z_p = g[7], kn = A.kn, ka = A.ka, ir = A.ir;
-    const float sd = A.sigma_depth * max_(z_p, 1e-6f);
-    const float kz = 1.0f / (sd * sd);
-    const float fx = ((float)x + 0.5f) * A.rx - 0.5f, fy = ((float)row + 0.5f) * A.ry - 0.5f;
-    const int x0 = (int)__builtin_floorf(fx), y0 = (int)__builtin_floorf(fy);
-    const float tx = fx - (float)x0, ty = fy - (float)y0;
-    const bool ring = A.taps == 4;
-    float sx = 0.0f, sy = 0.0f, sz = 0.0f, px = 0.0f, py = 0.0f, pz = 0.0f, wsum = 0.0f, pw = 0.0f;
-    for (int j = -1; j <= 2; ++j) {
-        if (!ring && (j < 0 || j > 1)) continue;
-        const int qy = y0 + j;
-        if (qy < 0 || qy >= h) continue;
-        const float by = 1.0f - abs_((float)j - ty) * ir;
-        for (int i = -1; i <= 2; ++i) {
-            if (!ring && (i < 0 || i > 1)) continue;
-            const int qx = x0 + i;
-            if (qx < 0 || qx >= w) continue;
-            const float bx = 1.0f - abs_((float)i - tx) * ir;
-            if (!(bx > 0.0f && by > 0.0f)) continue;
-            const size_t q = (size_t)qy * (size_t)w + (size_t)qx;
-            const Rec cq = col[q], nq = nzb[q], aq = alb[q];
-            const float b = bx * by;
-            px = fma_(b, cq.x, px);
-            py = fma_(b, cq.y, py);
-            pz = fma_(b, cq.z, pz);
-            pw = pw + b;
-            const v3 dn = V(nq.x, nq.y, nq.z) - n_p, da = V(aq.x, aq.y, aq.z) - a_p;
-            const float en = dot(dn, dn), ea = dot(da, da);
-            const float dz = nq.w - z_p;
-            const float ez = dz * dz;
-            const float e = fma_(ea, ka, fma_(ez, kz, en * kn));
-            const float wt = b * exp_(-e);
-            if (!(wt > 0.0f)) continue;
-            sx = fma_(wt, cq.x, sx);
-            sy = fma_(wt, cq.y, sy);
-            sz = fma_(wt, cq.z, sz);
-            wsum = wsum + wt;
-        }
-    }
-    v3 o = (wsum >= 1e-4f * pw) ? V(sx / wsum, sy / wsum, sz / wsum) : V(px / pw, py / pw, pz / pw);
-    if (A.flags & PT_UPSAMPLE_DEMODULATE) o = V(o.x * up_div(a_p.x), o.y * up_div(a_p.y), o.z * up_div(a_p.z));
-    return o;
-}
-
-} // namespace
-
 extern "C" void pt_upsample_default_params(pt_upsample_params* p)
 {
     if (!p) return;
@@ -138,25 +65,26 @@ extern "C" int64_t pt_debug_upsample_host(pt_ctx* c, const float* rgb_lo, const 
     pt_upsample_params prm;
     int rc = check_upsample_args(c, "pt_debug_upsample_host", w, h, W, H, p, &prm);
     if (rc) return rc;
-    Consts A{w, h, W, prm.taps, prm.flags, prm.sigma_depth};
-    upsample_constants(prm, w, h, W, H, &A.rx, &A.ry, &A.kn, &A.ka, &A.ir);
-    const bool dm = (prm.flags & PT_UPSAMPLE_DEMODULATE) != 0;
     const size_t npx = (size_t)w * (size_t)h;
-    std::vector<Rec> col(npx), nzb(npx), alb(npx);
+    std::vector<float4> col(npx), nzb(npx), alb(npx);
+    PtUpsampleArgs A{}; // the kernels' arguments, the records on the host
+    A.col = col.data();
+    A.nz = nzb.data();
+    A.alb = alb.data();
+    A.w = w; A.h = h; A.W = W; A.H = H;
+    A.taps = prm.taps;
+    A.flags = prm.flags;
+    A.sigma_depth = prm.sigma_depth;
+    upsample_constants(prm, w, h, W, H, &A.rx, &A.ry, &A.kn, &A.ka, &A.ir);
     pt_parallel_ranges(npx, [&](size_t lo, size_t hi) { // prepare
-        for (size_t i = lo; i < hi; ++i) {
-            const float* g = aov_lo + 8 * i;
-            const float r[3] = {finite_or_0(rgb_lo[3 * i]), finite_or_0(rgb_lo[3 * i + 1]), finite_or_0(rgb_lo[3 * i + 2])};
-            col[i] = dm ? Rec{r[0] / up_div(g[0]), r[1] / up_div(g[1]), r[2] / up_div(g[2]), 0.0f} : Rec{r[0], r[1], r[2], 0.0f};
-            nzb[i] = Rec{g[4], g[5], g[6], g[7]};
-            alb[i] = Rec{g[0], g[1], g[2], 0.0f};
-        }
+        for (size_t i = lo; i < hi; ++i)
+            filter_prepare_pixel<kFilterUpsample>(rgb_lo + 3 * i, nullptr, filter_guide_word(aov_lo + 8 * i), filter_guide_word(aov_lo + 8 * i + 4), prm.flags, prm.sigma_depth, col[i], nzb[i], alb[i]);
     });
     pt_parallel_ranges((size_t)H, [&](size_t lo, size_t hi) {
         for (size_t row = lo; row < hi; ++row)
             for (int x = 0; x < W; ++x) {
-                const v3 o = upsample_pixel(col.data(), nzb.data(), alb.data(), aov_hi, A, x, (int)row);
                 const size_t i = row * (size_t)W + (size_t)x;
+                const v3 o = upsample_pixel(A, filter_guide_word(aov_hi + 8 * i), filter_guide_word(aov_hi + 8 * i + 4), x, (int)row);
                 out_rgb[3 * i] = o.x; out_rgb[3 * i + 1] = o.y; out_rgb[3 * i + 2] = o.z;
                 if (out_rgba8) out_rgba8[i] = make_rgba(o);
             }
