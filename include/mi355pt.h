@@ -170,7 +170,7 @@ int pt_render(pt_ctx* ctx, const pt_camera* cam, int32_t width, int32_t height, 
  * every call that touches what a frame in flight uses is ordered after the context's LAST ASYNCHRONOUS CALL, whichever stream that
  * call was given.  So any call of this header may follow a pt_*_device call at once, with no pt_synchronize between them.
  *   - The asynchronous calls (pt_render_device, pt_render_batch_device, pt_render_aov_device, pt_render_aov_follow_device, pt_render_aov_batch_device, pt_denoise_device,
- *     pt_denoise_batch_device, pt_denoise_var_device, pt_accum_add_device, pt_accum_denoise_device, pt_accum_reproject_device, pt_upsample_device, pt_trace_closest_device, pt_trace_occluded_device, pt_trace_surface_device, pt_trace_ao_device, pt_closest_point_device, pt_render_rays_device, pt_render_aov_rays_device, pt_reduce_framebuffer) wait ON THE
+ *     pt_denoise_batch_device, pt_denoise_var_device, pt_accum_add_device, pt_accum_denoise_device, pt_accum_reproject_device, pt_upsample_device, pt_trace_closest_device, pt_trace_occluded_device, pt_trace_surface_device, pt_trace_ao_device, pt_trace_hits_device, pt_closest_point_device, pt_render_rays_device, pt_render_aov_rays_device, pt_reduce_framebuffer) wait ON THE
  *     DEVICE: the stream they are given waits for an event recorded at the end of the previous asynchronous call - only if that call
  *     used another stream; on the same stream the stream's own order suffices and nothing is added.  The host returns at once, with
  *     two exceptions that existed before: a frame of another size, shard or batch length rewrites the pixel queue and a frame that
@@ -178,7 +178,7 @@ int pt_render(pt_ctx* ctx, const pt_camera* cam, int32_t width, int32_t height, 
  *     before) - both first wait on the host for the frame in flight; pt_render_batch_device and pt_render_aov_batch_device
  *     return when their per-frame tables have reached HBM, i.e. after whatever precedes them on `stream`; and a pt_accum_add_device that
  *     selects its pixels returns when the count of its active set has reached the host (see there).
- *   - The blocking renders (pt_render, pt_render_batch, pt_render_aov, pt_render_aov_follow, pt_render_aov_batch, pt_accum_add), pt_denoise, pt_denoise_batch, pt_denoise_var, pt_accum_denoise, pt_accum_reproject, pt_upsample, pt_trace_closest, pt_trace_occluded, pt_closest_point, pt_trace_surface, pt_trace_ao, pt_render_rays and pt_render_aov_rays run on the context's stream behind the same device-side wait
+ *   - The blocking renders (pt_render, pt_render_batch, pt_render_aov, pt_render_aov_follow, pt_render_aov_batch, pt_accum_add), pt_denoise, pt_denoise_batch, pt_denoise_var, pt_accum_denoise, pt_accum_reproject, pt_upsample, pt_trace_closest, pt_trace_occluded, pt_trace_hits, pt_closest_point, pt_trace_surface, pt_trace_ao, pt_render_rays and pt_render_aov_rays run on the context's stream behind the same device-side wait
  *     and return with the context idle.  After a blocking call, or on the context's own stream, they add no wait at all.
  *   - The calls that change or read what a frame uses WAIT ON THE HOST for the last asynchronous call's stream (if it is not the
  *     context's) and then for the context's: pt_set_materials, pt_set_environment, pt_update_vertices, pt_upload_scene,
@@ -193,7 +193,7 @@ int pt_render(pt_ctx* ctx, const pt_camera* cam, int32_t width, int32_t height, 
 int pt_render_device(pt_ctx* ctx, const pt_camera* cam, int32_t width, int32_t height, int32_t max_samples, int32_t max_path_depth,
                      void* d_out_rgb, void* d_out_rgba8, void* stream);
 /* Waits on the host for the context's last asynchronous call - pt_render_device, pt_render_batch_device, pt_render_aov_device,
- * pt_render_aov_follow_device, pt_render_aov_batch_device, pt_denoise_device, pt_denoise_batch_device, pt_denoise_var_device, pt_accum_add_device, pt_accum_denoise_device, pt_accum_reproject_device, pt_upsample_device, pt_trace_closest_device, pt_trace_occluded_device, pt_trace_surface_device, pt_trace_ao_device, pt_closest_point_device, pt_render_rays_device, pt_render_aov_rays_device or pt_reduce_framebuffer, on the stream it was given - and for the context's own stream.  Every earlier asynchronous call of the context
+ * pt_render_aov_follow_device, pt_render_aov_batch_device, pt_denoise_device, pt_denoise_batch_device, pt_denoise_var_device, pt_accum_add_device, pt_accum_denoise_device, pt_accum_reproject_device, pt_upsample_device, pt_trace_closest_device, pt_trace_occluded_device, pt_trace_surface_device, pt_trace_ao_device, pt_trace_hits_device, pt_closest_point_device, pt_render_rays_device, pt_render_aov_rays_device or pt_reduce_framebuffer, on the stream it was given - and for the context's own stream.  Every earlier asynchronous call of the context
  * is complete then as well, whatever stream it used: each was ordered before the next (see pt_render_device).  Returns PT_E_HIP if a
  * wave's watchdog fired during the last frame (the image is then incomplete); pt_get_stats reports the same.  PT_OK at once on an idle
  * or host-only context.  A caller's stream may be destroyed once this has returned. */
@@ -838,6 +838,57 @@ int pt_trace_ao_device (pt_ctx* ctx, const void* d_rays, int64_t n, const pt_ao_
  * follows "watertight" and pt_update_vertices.  out_ao_rays: NULL, or n * K pt_ray records - the occlusion rays of ray i at
  * i*K .. i*K+K-1, as pt_trace_occluded takes them.  Returns n. */
 int64_t pt_debug_trace_ao_host(pt_ctx* ctx, const pt_ray* rays, int64_t n, const pt_ao_params* p, pt_ao_hit* out, pt_ray* out_ao_rays);
+
+/* ---- ray queries: the first K hits (no reference counterpart: the reference stops every ray at its first surface) ----
+ * pt_trace_hits answers "what lies along this ray, in order": the first K triangles it crosses, not only the first - layered
+ * transparency and X-ray views, wall thickness (second hit minus first), peeling away a cover, counting the surfaces between two
+ * points, picking through a window.  Re-shooting from each hit with an epsilon loses coplanar surfaces, accumulates error and costs a
+ * launch per layer; this is ONE walk per ray.  Kernels of their own (csrc/pt_kernel_rays_hits.hip, csrc/pt_kernel_rays_hits_wt.hip;
+ * csrc/pt_hits.h): the walk of the ray kernels, whose leaf step offers every triangle it accepts to a per-lane sorted list in LDS
+ * instead of keeping the best one.  The CPU twin is pt_debug_trace_hits_host.
+ * DEFINITION, per ray i (a pt_ray as above; out: K = max_hits records of pt_ray_hit at out[i*K .. i*K+K-1], K 16-byte stores).
+ *   thi, the fixed lower bound 1e-3, the ray domain and the unread float 7 are exactly those of pt_trace_closest.
+ *   S = the set of triangles the active test accepts with 1e-3 < t <= thi; the active test is Moeller-Trumbore, or the watertight
+ *   test under option "watertight" = 1.  Slivers are never in S.
+ *   S is ordered by (t as a float32 value, global triangle id), ascending.
+ *   out[i*K + j] for j < min(K, |S|) is {t, u, v, prim} of the j-th element; the bits of t, u and v are what the triangle test computes
+ *   for that triangle - what pt_trace_closest would store if that triangle were the closest.
+ *   Every entry j >= |S| is the miss record {+0, +0, +0, -1}.
+ *   All K * 16 bytes of every ray are written; nothing behind n * K * 16 is touched.
+ * CONSEQUENCES.  K = 1 is bit for bit pt_trace_closest.  Entry 0 for any K is pt_trace_closest's record of the ray.  The list for K is
+ * the prefix of the list for any K' > K.  The result is a property of the scene, not of the walk: it does not depend on the hierarchy,
+ * "rays_grid", "rays_refill", the slab form or a refit against a fresh upload.  Two triangles with bit-equal t (a surface stored
+ * twice) both appear, the lower id first.
+ * A walk that runs out of its step or stack bound retires its ray with K miss records and raises the flag behind pt_synchronize
+ * (PT_E_HIP), like the other ray kernels.
+ * The call honours "watertight", "box_exact" (as pt_trace_*: only 1 selects the subtracting form), "rays_refill", "rays_grid" and
+ * pt_update_vertices.  It ignores the pixel shard, the materials and the environment, issues no collective, keeps no render state (a
+ * pt_render after it is bit for bit the one before) and needs quad nodes.  n == 0 is PT_OK with no launch.
+ * THE WALK is that of pt_trace_closest - a wave owns a contiguous range of rays and refills its idle lanes from it, one range per
+ * resident wave - with the node step culling against thi until a lane's list is full and against its K-th entry from then on; boxes
+ * whose entry distance ties with that entry are still visited.  The list is in LDS behind the lane's stack, (12 + 4 K) * 256 bytes per
+ * wave, so the waves resident on a CU shrink as K grows (pt_get_stats: lds_bytes).
+ * REFUSALS, ORDERING, pt_get_stats (the hits kernel's launch: launches 1, block, grid, vgprs, lds_bytes, stack_entries) and HOST-ONLY
+ * CONTEXTS are those of pt_trace_closest / pt_trace_closest_device, word for word, by name, before anything is touched (d_out 16-byte
+ * aligned); on a host-only context valid arguments give PT_E_NO_DEVICE, invalid ones PT_E_INVALID, and the twin works there.
+ * ADDITIONALLY REFUSED with PT_E_INVALID, by name, before anything else: max_hits outside 1..PT_HITS_MAX, a reserved word that is not 0.
+ * pt_trace_hits_device joins the asynchronous calls at pt_render_device and the list at pt_synchronize; pt_trace_hits joins the
+ * blocking calls.
+ * NOT BUILT: a per-ray lower bound or (t, id) floor to continue past the K-th hit (float 7 of pt_ray stays unread); a count of all
+ * hits; surface records per entry; a pt_group_* form; a batch form; a pt_main flag. */
+#define PT_HITS_MAX 16
+typedef struct pt_hits_params {   /* 16 bytes */
+    int32_t max_hits;      /* K, 1..PT_HITS_MAX records per ray */
+    int32_t reserved[3];   /* must be 0 */
+} pt_hits_params;
+void pt_hits_default_params(pt_hits_params* p);   /* 4, 0, 0, 0 */
+int pt_trace_hits        (pt_ctx* ctx, const pt_ray* rays, int64_t n, const pt_hits_params* p /* NULL = defaults */, pt_ray_hit* out /* n * K */);
+int pt_trace_hits_device (pt_ctx* ctx, const void* d_rays, int64_t n, const pt_hits_params* p, void* d_out /* n * K pt_ray_hit, 16-byte aligned */, void* stream);
+/* The CPU twin: the definition above by the HOST WALK of pt_debug_trace_rays_host (not a brute force) with a sorted K-list in place of
+ * the best hit, on all host threads.  Its slab tests cull against thi alone, never against the list, so the triangles it offers to the
+ * list do not depend on K and its lists are prefixes of each other on every ray.  Works on a host-only context, follows "watertight"
+ * and pt_update_vertices.  Returns n. */
+int64_t pt_debug_trace_hits_host(pt_ctx* ctx, const pt_ray* rays, int64_t n, const pt_hits_params* p, pt_ray_hit* out);
 
 /* ---- point queries: the nearest surface to the CALLER'S points (no reference counterpart: the reference answers questions about its
  * own rays only) ----

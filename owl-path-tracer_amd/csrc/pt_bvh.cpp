@@ -1235,6 +1235,22 @@ inline bool host_wt_tri(const PtTri& tr, const float o[3], const HostWtRay& r, f
     *t = T * inv; *u = V * inv; *v = W * inv;
     return true;
 }
+// Moeller-Trumbore, two-sided, as tri_eval of pt_trace.h; false: rejected before t is looked at
+inline bool host_mt_tri(const PtTri& tr, hv3 o, hv3 d, float* t_out, float* u_out, float* v_out)
+{
+    hv3 p0{tr.p0[0], tr.p0[1], tr.p0[2]}, p1{tr.p1[0], tr.p1[1], tr.p1[2]}, p2{tr.p2[0], tr.p2[1], tr.p2[2]};
+    hv3 e1 = hsub(p1, p0), e2 = hsub(p2, p0);
+    hv3 pv = hcross(d, e2);
+    float det = hdot(e1, pv);
+    float idet = 1.0f / det;
+    hv3 tv = hsub(o, p0);
+    float u = hdot(tv, pv) * idet;
+    hv3 qv = hcross(tv, e1);
+    float v = hdot(d, qv) * idet;
+    float t = hdot(e2, qv) * idet;
+    *t_out = t; *u_out = u; *v_out = v;
+    return u >= 0.0f && v >= 0.0f && u + v <= 1.0f;
+}
 } // namespace
 
 bool pt_bvh_closest_hit_host(const PtBvh& bvh, const float org[3], const float dir[3], float tmin, float tmax, float* t_out, float* u_out,
@@ -1275,17 +1291,8 @@ bool pt_bvh_closest_hit_host(const PtBvh& bvh, const float org[3], const float d
                     }
                     continue;
                 }
-                hv3 p0{tr.p0[0], tr.p0[1], tr.p0[2]}, p1{tr.p1[0], tr.p1[1], tr.p1[2]}, p2{tr.p2[0], tr.p2[1], tr.p2[2]};
-                hv3 e1 = hsub(p1, p0), e2 = hsub(p2, p0);
-                hv3 pv = hcross(d, e2);
-                float det = hdot(e1, pv);
-                float idet = 1.0f / det;
-                hv3 tv = hsub(o, p0);
-                float u = hdot(tv, pv) * idet;
-                hv3 qv = hcross(tv, e1);
-                float v = hdot(d, qv) * idet;
-                float t = hdot(e2, qv) * idet;
-                if (u >= 0.0f && v >= 0.0f && u + v <= 1.0f && t > tmin && (t < bt || (t == bt && tr.id < bid))) {
+                float t, u, v;
+                if (host_mt_tri(tr, o, d, &t, &u, &v) && t > tmin && (t < bt || (t == bt && tr.id < bid))) {
                     bt = t; bu = u; bv = v; bid = tr.id;
                 }
             }
@@ -1296,4 +1303,52 @@ bool pt_bvh_closest_hit_host(const PtBvh& bvh, const float org[3], const float d
     *t_out = bt; *u_out = bu; *v_out = bv;
     *prim = bid == 0x7fffffff ? -1 : bid;
     return bid != 0x7fffffff;
+}
+
+// The first k triangles along a ray in (t, id) order (pt_trace_hits, include/mi355pt.h): the walk above with a sorted list of k entries
+// in place of the best hit.  The slab tests cull against tmax ALONE, never against the list: the leaves visited - and so the triangles
+// offered to the list - do not depend on k, which makes the list for k the prefix of the list for any larger k on every ray, inside
+// the hit domain or not.  The order of the visits does not matter to a sorted list, so the children are not ordered.
+int pt_bvh_first_hits_host(const PtBvh& bvh, const float org[3], const float dir[3], float tmin, float tmax, int k, float* t_out, float* u_out, float* v_out,
+                           int32_t* prim, bool watertight)
+{
+    const hv3 o{org[0], org[1], org[2]}, d{dir[0], dir[1], dir[2]};
+    const HostWtRay wr = watertight ? host_wt_ray(dir) : HostWtRay{};
+    const hv3 inv{1.0f / d.x, 1.0f / d.y, 1.0f / d.z};
+    float bt = tmax; // the bound of the acceptance: {tmax, 0x7fffffff} until the list is full, then its last entry
+    int32_t bid = 0x7fffffff;
+    int n = 0;
+    int32_t stack[PT_MAX_STACK + 8];
+    int sp = 0;
+    int32_t cur = bvh.root;
+    for (;;) {
+        if (cur >= 0) {
+            const PtNode& nd = bvh.nodes[cur];
+            float tl, tr;
+            const float lmin[3] = {nd.lo[0][0], nd.lo[1][0], nd.lo[2][0]}, lmax[3] = {nd.hi[0][0], nd.hi[1][0], nd.hi[2][0]};
+            const float rmin[3] = {nd.lo[0][1], nd.lo[1][1], nd.lo[2][1]}, rmax[3] = {nd.hi[0][1], nd.hi[1][1], nd.hi[2][1]};
+            const bool hl = hbox(lmin, lmax, o, inv, tmin, tmax, &tl), hr = hbox(rmin, rmax, o, inv, tmin, tmax, &tr);
+            if (hl && hr) stack[sp++] = nd.right;
+            if (hl || hr) { cur = hl ? nd.left : nd.right; continue; }
+        } else if (cur != -1) {
+            const uint32_t code = ~(uint32_t)cur;
+            const int first = (int)(code >> 3), count = (int)(code & 7u);
+            for (int i = 0; i < count; ++i) {
+                const PtTri& tr = bvh.tris[first + i];
+                float t, u, v;
+                const bool in = watertight ? host_wt_tri(tr, org, wr, &t, &u, &v) : host_mt_tri(tr, o, d, &t, &u, &v);
+                if (!(in && t > tmin && (t < bt || (t == bt && tr.id < bid)))) continue;
+                int j = n < k ? n : k - 1; // the place that opens: behind the tail, or the tail of a full list
+                for (; j > 0 && !(t_out[j - 1] < t || (t_out[j - 1] == t && prim[j - 1] < tr.id)); --j) {
+                    t_out[j] = t_out[j - 1]; u_out[j] = u_out[j - 1]; v_out[j] = v_out[j - 1]; prim[j] = prim[j - 1];
+                }
+                t_out[j] = t; u_out[j] = u; v_out[j] = v; prim[j] = tr.id;
+                if (n < k) ++n;
+                if (n == k) { bt = t_out[k - 1]; bid = prim[k - 1]; }
+            }
+        }
+        if (sp == 0) break;
+        cur = stack[--sp];
+    }
+    return n;
 }

@@ -40,6 +40,10 @@ void pt_bvh_quad_cost(const std::vector<PtNode4>& nodes4, int32_t root4, double*
 // watertight: the triangle test of option "watertight" = 1 (csrc/pt_trace.h, "WATERTIGHT BUILD") instead of Moeller-Trumbore
 bool pt_bvh_closest_hit_host(const PtBvh& bvh, const float org[3], const float dir[3], float tmin, float tmax, float* t, float* u,
                              float* v, int32_t* prim, bool watertight = false);
+// The same walk keeping the first k >= 1 triangles in (t, id) order, its slab tests culling against tmax alone
+// (pt_debug_trace_hits_host): returns how many of t[], u[], v[], prim[] (k entries each) it filled.
+int pt_bvh_first_hits_host(const PtBvh& bvh, const float org[3], const float dir[3], float tmin, float tmax, int k, float* t, float* u, float* v, int32_t* prim,
+                           bool watertight = false);
 
 // Three-level collapse into oct nodes (PtNode8, pt_types.h): starting from the two children of a binary node, the internal slot with
 // the largest surface area is replaced by its two children until eight slots are used (or none is internal).  root8 = 0 when the

@@ -86,6 +86,13 @@ struct PtAoArgs {
     float thi;         // the occlusion rays' bound: radius < 1e10f ? radius : 1e10f, formed on the host
     uint32_t seed;     // second word of rng_init(ray index, seed)
 };
+// The first K hits (pt_trace_hits; pt_hits.h): the ray kernels' arguments (r.out: n * k pt_ray_hit, 16-byte aligned) and K
+#define PT_HITS_K_MAX 16 // PT_HITS_MAX of include/mi355pt.h
+struct PtHitsArgs {
+    PtRaysArgs r;
+    int32_t k;         // K, 1..PT_HITS_K_MAX records per ray
+    int32_t pad[3];
+};
 
 // Denoiser (pt_denoise; pt_denoise.hip): what its three kernels take.  The host fills everything but the record pointers, which
 // pt_launch_denoise carves out of ws; the constants are include/mi355pt.h's "host constants" (pti::denoise_constants).
@@ -264,6 +271,12 @@ hipError_t pt_launch_rays_ao(const PtKernelParams* p, const PtAoArgs* a, int gri
 hipError_t pt_rays_ao_geometry(int exact, PtGeometry* g);
 hipError_t pt_launch_rays_ao_wt(const PtKernelParams* p, const PtAoArgs* a, int grid, size_t lds_bytes, hipStream_t stream);
 hipError_t pt_rays_ao_geometry_wt(int exact, PtGeometry* g);
+// pt_kernel_rays_hits.hip / pt_kernel_rays_hits_wt.hip: the first-K-hits kernels (pt_trace_hits; pt_hits.h), same conventions; the geometry is that
+// of a launch with k records per ray (lds_bytes grows with k: four words per record and lane behind the stack)
+hipError_t pt_launch_rays_hits(const PtKernelParams* p, const PtHitsArgs* a, int grid, size_t lds_bytes, hipStream_t stream);
+hipError_t pt_rays_hits_geometry(int exact, int k, PtGeometry* g);
+hipError_t pt_launch_rays_hits_wt(const PtKernelParams* p, const PtHitsArgs* a, int grid, size_t lds_bytes, hipStream_t stream);
+hipError_t pt_rays_hits_geometry_wt(int exact, int k, PtGeometry* g);
 // pt_kernel_points.hip: the point kernel (pt_closest_point), one instance.  a: the ray kernels' arguments with a->rays = n pt_point records
 // (16 bytes), a->out = n pt_point_hit (32 bytes), both 16-byte aligned, and a->cap in stack ENTRIES of pt_points_entry_words() words each:
 // a->ovf holds (cap * words - g->lds_levels) * 64 words per workgroup, g->lds_levels being the words of a lane's stack kept in LDS

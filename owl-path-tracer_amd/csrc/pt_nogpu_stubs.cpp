@@ -48,6 +48,10 @@ hipError_t pt_launch_rays_ao(const PtKernelParams*, const PtAoArgs*, int, size_t
 hipError_t pt_rays_ao_geometry(int, PtGeometry*) { return hipErrorNotSupported; }
 hipError_t pt_launch_rays_ao_wt(const PtKernelParams*, const PtAoArgs*, int, size_t, hipStream_t) { return hipErrorNotSupported; }
 hipError_t pt_rays_ao_geometry_wt(int, PtGeometry*) { return hipErrorNotSupported; }
+hipError_t pt_launch_rays_hits(const PtKernelParams*, const PtHitsArgs*, int, size_t, hipStream_t) { return hipErrorNotSupported; }
+hipError_t pt_rays_hits_geometry(int, int, PtGeometry*) { return hipErrorNotSupported; }
+hipError_t pt_launch_rays_hits_wt(const PtKernelParams*, const PtHitsArgs*, int, size_t, hipStream_t) { return hipErrorNotSupported; }
+hipError_t pt_rays_hits_geometry_wt(int, int, PtGeometry*) { return hipErrorNotSupported; }
 hipError_t pt_launch_points(const PtKernelParams*, const PtRaysArgs*, int, size_t, hipStream_t) { return hipErrorNotSupported; }
 hipError_t pt_points_geometry(PtGeometry*) { return hipErrorNotSupported; }
 int pt_points_entry_words(void) { return 1; }

@@ -29,6 +29,11 @@ struct Hit {
 };
 // No hit yet, and none accepted at or beyond t (a hit at exactly t is taken: every real id is below this one).
 __device__ __forceinline__ void hit_reset(Hit& h, float t) { h.t = t; h.u = 0.0f; h.v = 0.0f; h.id = 0x7fffffff; h.slot = -1; }
+// What the leaf code and quad_walk_step ask of the sink H that takes accepted triangles - a Hit here, the best one so far; a HitList in
+// pt_hits.h - beside its member t, the cull bound: is (t, id) in front of what it holds, take this triangle, does it hold one.
+__device__ __forceinline__ bool hit_admits(const Hit& h, float t, int id) { return t < h.t || (t == h.t && id < h.id); }
+__device__ __forceinline__ void hit_take(Hit& h, float t, float u, float v, int id, int slot) { h.t = t; h.u = u; h.v = v; h.id = id; h.slot = slot; }
+__device__ __forceinline__ bool hit_found(const Hit& h) { return h.slot >= 0; }
 
 struct Counters {
     uint32_t rays = 0, nodes = 0, tris = 0, scat = 0, env = 0, samples = 0, retry = 0;
@@ -120,7 +125,7 @@ __device__ __forceinline__ v3 ray_inv(v3 d)
 // Moeller-Trumbore, two-sided, kTMin < t; ties in t go to the lower global id (order independent result).
 // tri_eval works on a record that is already in registers, so that a leaf step can issue the loads of all its triangles
 // before the first test (one memory round trip per leaf instead of one per triangle).
-__device__ __forceinline__ void tri_eval(const f32x4 a, const f32x4 b, const f32x4 c, int slot, v3 o, v3 d, Hit& h)
+template <class H> __device__ __forceinline__ void tri_eval(const f32x4 a, const f32x4 b, const f32x4 c, int slot, v3 o, v3 d, H& h)
 {
     v3 p0 = V(a.x, a.y, a.z), p1 = V(a.w, b.x, b.y), p2 = V(b.z, b.w, c.x);
     int id = __float_as_int(c.y);
@@ -133,30 +138,26 @@ __device__ __forceinline__ void tri_eval(const f32x4 a, const f32x4 b, const f32
     v3 qv = cross(tv, e1);
     float v = dot(d, qv) * inv;
     float t = dot(e2, qv) * inv;
-    if (u >= 0.0f && v >= 0.0f && u + v <= 1.0f && t > kTMin && (t < h.t || (t == h.t && id < h.id))) {
-        h.t = t; h.u = u; h.v = v; h.id = id; h.slot = slot;
-    }
+    if (u >= 0.0f && v >= 0.0f && u + v <= 1.0f && t > kTMin && hit_admits(h, t, id)) hit_take(h, t, u, v, id, slot);
 }
-__device__ __forceinline__ void tri_test(const PtTri* __restrict__ tris, int slot, v3 o, v3 d, Hit& h)
+template <class H> __device__ __forceinline__ void tri_test(const PtTri* __restrict__ tris, int slot, v3 o, v3 d, H& h)
 {
     const size_t tb = (size_t)(uint32_t)slot * sizeof(PtTri);
     const f32x4 a = ldg4(tris, tb), b = ldg4(tris, tb + 16), c = ldg4(tris, tb + 32);
     tri_eval(a, b, c, slot, o, d, h);
 }
 // tri_eval's acceptance of one triangle, with u + v already formed
-__device__ __forceinline__ void tri_take(float t, float u, float v, float uv, int id, int slot, Hit& h)
+template <class H> __device__ __forceinline__ void tri_take(float t, float u, float v, float uv, int id, int slot, H& h)
 {
-    if (u >= 0.0f && v >= 0.0f && uv <= 1.0f && t > kTMin && (t < h.t || (t == h.t && id < h.id))) {
-        h.t = t; h.u = u; h.v = v; h.id = id; h.slot = slot;
-    }
+    if (u >= 0.0f && v >= 0.0f && uv <= 1.0f && t > kTMin && hit_admits(h, t, id)) hit_take(h, t, u, v, id, slot);
 }
 __device__ __forceinline__ f32x2 fma2(f32x2 a, f32x2 b, f32x2 c) { return __builtin_elementwise_fma(a, b, c); }
 // Two triangles at once, {first, second} in the two halves of packed-f32 registers (v_pk_mul / v_pk_add / v_pk_fma_f32): each half does
 // exactly tri_eval's operations in tri_eval's order - dot and cross as in pt_device.h, an fma only where they have one, the correctly
 // rounded 1/det per triangle - so t, u and v are tri_eval's bit for bit.  The hits are merged in (t, id) order, first then second (take1:
 // the second is a triangle of the leaf).
-__device__ __forceinline__ void tri_eval2(const f32x4 a0, const f32x4 b0, const f32x2 c0, const f32x4 a1, const f32x4 b1, const f32x2 c1, int slot0, bool take1,
-                                          const f32x2 ox, const f32x2 oy, const f32x2 oz, const f32x2 dx, const f32x2 dy, const f32x2 dz, Hit& h)
+template <class H> __device__ __forceinline__ void tri_eval2(const f32x4 a0, const f32x4 b0, const f32x2 c0, const f32x4 a1, const f32x4 b1, const f32x2 c1, int slot0, bool take1,
+                                          const f32x2 ox, const f32x2 oy, const f32x2 oz, const f32x2 dx, const f32x2 dy, const f32x2 dz, H& h)
 {
     const f32x2 p0x = {a0.x, a1.x}, p0y = {a0.y, a1.y}, p0z = {a0.z, a1.z};
     const f32x2 p1x = {a0.w, a1.w}, p1y = {b0.x, b1.x}, p1z = {b0.y, b1.y};
@@ -226,16 +227,14 @@ __device__ __forceinline__ float wt_edge64(float a, float b, float c, float d)
 }
 // acceptance: the edge functions do not disagree in sign, det != 0, then tri_take's rule for t and the tie-break (u, v are not tested
 // again: V / det may round to 1 + 2^-23 on an edge, and rejecting that would open the seam the test exists to close)
-__device__ __forceinline__ void wt_take(float U, float V, float W, float det, float t, float u, float v, int id, int slot, Hit& h)
+template <class H> __device__ __forceinline__ void wt_take(float U, float V, float W, float det, float t, float u, float v, int id, int slot, H& h)
 {
     const bool neg = U < 0.0f || V < 0.0f || W < 0.0f, pos = U > 0.0f || V > 0.0f || W > 0.0f;
-    if (!(neg && pos) && det != 0.0f && t > kTMin && (t < h.t || (t == h.t && id < h.id))) {
-        h.t = t; h.u = u; h.v = v; h.id = id; h.slot = slot;
-    }
+    if (!(neg && pos) && det != 0.0f && t > kTMin && hit_admits(h, t, id)) hit_take(h, t, u, v, id, slot);
 }
 // One triangle (the group walk's lane-per-triangle leaf, triangles beyond the fourth of a leaf).  n64: instrumented instance, counts the
 // pairs that took the float64 branch.
-__device__ __forceinline__ void tri_eval_wt(const f32x4 a, const f32x4 b, const f32x4 c, int slot, v3 o, PT_WT_PARAMS, Hit& h, uint32_t* n64 = nullptr)
+template <class H> __device__ __forceinline__ void tri_eval_wt(const f32x4 a, const f32x4 b, const f32x4 c, int slot, v3 o, PT_WT_PARAMS, H& h, uint32_t* n64 = nullptr)
 {
 #pragma clang fp contract(off)
     const WtRay r = PT_WT_FROM_PARAMS;
@@ -260,8 +259,8 @@ __device__ __forceinline__ void tri_eval_wt(const f32x4 a, const f32x4 b, const 
 }
 // Two triangles at once in packed-f32 registers, as tri_eval2: each half does exactly tri_eval_wt's operations in its order
 // (v_pk_mul_f32 / v_pk_add_f32 round like their scalar forms), the reciprocal of det per triangle.
-__device__ __forceinline__ void tri_eval_wt2(const f32x4 a0, const f32x4 b0, const f32x2 c0, const f32x4 a1, const f32x4 b1, const f32x2 c1, int slot0, bool take1, const f32x2 ox,
-                                             const f32x2 oy, const f32x2 oz, PT_WT_PARAMS, Hit& h, uint32_t* n64 = nullptr)
+template <class H> __device__ __forceinline__ void tri_eval_wt2(const f32x4 a0, const f32x4 b0, const f32x2 c0, const f32x4 a1, const f32x4 b1, const f32x2 c1, int slot0, bool take1, const f32x2 ox,
+                                             const f32x2 oy, const f32x2 oz, PT_WT_PARAMS, H& h, uint32_t* n64 = nullptr)
 {
 #pragma clang fp contract(off)
     const WtRay r = PT_WT_FROM_PARAMS;
@@ -299,7 +298,7 @@ __device__ __forceinline__ void tri_eval_wt2(const f32x4 a0, const f32x4 b0, con
 #if PT_WATERTIGHT
 // The watertight leaf step: the same loads and the same pairing; the ray's axes and shear are formed here, once per leaf step, from d
 // alone (carrying them with the ray would cost five registers in the walk and a wider park area; the arithmetic gives the same bits).
-__device__ __forceinline__ void leaf_test(const PtTri* __restrict__ tris, int first, int count, v3 o, v3 d, Hit& h, uint32_t* n64 = nullptr)
+template <class H> __device__ __forceinline__ void leaf_test(const PtTri* __restrict__ tris, int first, int count, v3 o, v3 d, H& h, uint32_t* n64 = nullptr)
 {
     static_assert(PT_LEAF_PREFETCH == 4, "the leaf step tests the triangles of a leaf in two pairs");
     f32x4 ra[4], rb[4];
@@ -320,7 +319,7 @@ __device__ __forceinline__ void leaf_test(const PtTri* __restrict__ tris, int fi
     }
 }
 #else
-__device__ __forceinline__ void leaf_test(const PtTri* __restrict__ tris, int first, int count, v3 o, v3 d, Hit& h)
+template <class H> __device__ __forceinline__ void leaf_test(const PtTri* __restrict__ tris, int first, int count, v3 o, v3 d, H& h)
 {
 #if PT_LEAF_PREFETCH == 0
     for (int k = 0; k < count; ++k) tri_test(tris, first + k, o, d, h);
@@ -519,11 +518,11 @@ __device__ __forceinline__ void node4_step(const PtNode4* __restrict__ nodes4, u
 // out of either is an OVERRUN: error_flag is set, cur = PT_DONE, and the function returns false; it returns true after every step it took.
 // What an overrun does to the result is the caller's:
 //     quad probe, first-hit and follow guide kernels    leave the walk with the best hit so far
-//     ray kernels (closest, occluded, surface)          retire the ray as a miss (h.slot = -1)
+//     ray kernels (closest, occluded, surface)          retire the ray as a miss (h.slot = -1); first-K hits (pt_hits.h): as K misses
 //     ambient occlusion                                 k = AO_OVERRUN: the ray retires as a miss with ao = 1
-template <int LDS_ENTRIES>
+template <int LDS_ENTRIES, class H>
 __device__ __forceinline__ bool quad_walk_step(const PtKernelParams& P, const PtNode4* __restrict__ nodes4, const PtTri* __restrict__ tris, uint32_t* stack, uint32_t PT_AS1* ovf,
-                                               const int cap, v3 o, v3 d, v3 inv, Hit& h, int& cur, int& sp, int& steps, const bool exact, const bool any_hit)
+                                               const int cap, v3 o, v3 d, v3 inv, H& h, int& cur, int& sp, int& steps, const bool exact, const bool any_hit)
 {
     if (++steps > (1 << 20) || sp + 3 > cap) {
         gp(P.error_flag)[0] = 1u;
@@ -535,7 +534,7 @@ __device__ __forceinline__ bool quad_walk_step(const PtKernelParams& P, const Pt
     } else {
         const uint32_t code = ~(uint32_t)cur;
         leaf_test(tris, (int)(code >> 3), (int)(code & 7u), o, d, h);
-        if ((any_hit && h.slot >= 0) || sp == 0) {
+        if ((any_hit && hit_found(h)) || sp == 0) {
             cur = PT_DONE;
         } else {
             --sp;
@@ -576,8 +575,7 @@ __device__ __forceinline__ void closest_hit(const PtKernelParams& P, uint32_t* s
 // interp3(bw, bx, by, a, b, c), the interpolation of a vertex attribute at a hit:
 //     (1-u-v)*a + u*b + v*c  (device.cu:59,72,86-89), evaluated as an fma chain,
 // is pt_device.h's ("the surface at a hit"), so that the CPU twins run the copy the kernels compile.
-// (This note takes the lines the function took: the resource reports name kernels by
-// source line, and the headers that hold kernels include this one.)
+// (This note takes the lines the function took: the resource reports name kernels by source line, and the headers that hold kernels include this one.)
 
 struct PathState {
     uint32_t rng;

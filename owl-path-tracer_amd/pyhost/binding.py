@@ -79,6 +79,11 @@ class AoParams(C.Structure):
     _fields_ = [("n_rays", C.c_int32), ("flags", C.c_int32), ("radius", C.c_float), ("seed", C.c_uint32)]
 
 
+class HitsParams(C.Structure):
+    """pt_hits_params: max_hits (K, 1..PT_HITS_MAX records per ray), three reserved words (0)."""
+    _fields_ = [("max_hits", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
 class AccumParams(C.Structure):
     """pt_accum_params: n_samples (1..65535) for every active pixel, max_pixel_samples (0: no cap), noise_threshold (0: uniform add), reserved (0)."""
     _fields_ = [("n_samples", C.c_int32), ("max_pixel_samples", C.c_int32), ("noise_threshold", C.c_float), ("reserved", C.c_int32)]
@@ -139,6 +144,7 @@ EXPORTS = ["pt_create", "pt_destroy", "pt_last_error", "pt_abi_version", "pt_upl
            "pt_upsample_default_params", "pt_upsample", "pt_upsample_device", "pt_debug_upsample_host",
            "pt_trace_closest", "pt_trace_closest_device", "pt_trace_occluded", "pt_trace_occluded_device", "pt_debug_trace_rays_host", "pt_prim_to_mesh", "pt_trace_surface", "pt_trace_surface_device", "pt_debug_trace_surface_host",
            "pt_ao_default_params", "pt_trace_ao", "pt_trace_ao_device", "pt_debug_trace_ao_host",
+           "pt_hits_default_params", "pt_trace_hits", "pt_trace_hits_device", "pt_debug_trace_hits_host",
            "pt_closest_point", "pt_closest_point_device", "pt_debug_closest_point_host",
            "pt_render_rays", "pt_render_rays_device", "pt_render_aov_rays", "pt_render_aov_rays_device", "pt_debug_aov_rays_host"]
 # pt_ray / pt_ray_hit (include/mi355pt.h "ray queries"): 32 and 16 bytes
@@ -153,6 +159,8 @@ assert SURFACE_DTYPE.itemsize == 80
 AO_DTYPE = np.dtype([("t", "<f4"), ("u", "<f4"), ("v", "<f4"), ("prim", "<i4"), ("n", "<f4", (3,)), ("ao", "<f4")])
 assert AO_DTYPE.itemsize == 32 and C.sizeof(AoParams) == 16
 PT_AO_SHADING_NORMAL = 1
+PT_HITS_MAX = 16  # pt_trace_hits: the largest K
+assert C.sizeof(HitsParams) == 16
 # pt_point / pt_point_hit (include/mi355pt.h "point queries: the nearest surface"): 16 and 32 bytes
 POINT_DTYPE = np.dtype([("p", "<f4", (3,)), ("radius", "<f4")])
 POINT_HIT_DTYPE = np.dtype([("dist", "<f4"), ("u", "<f4"), ("v", "<f4"), ("prim", "<i4"), ("q", "<f4", (3,)), ("feature", "<i4")])
@@ -326,6 +334,12 @@ def lib():
     L.pt_trace_ao_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(AoParams), C.c_void_p, C.c_void_p]
     L.pt_debug_trace_ao_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(AoParams), C.c_void_p, C.c_void_p]
     L.pt_debug_trace_ao_host.restype = C.c_int64
+    L.pt_hits_default_params.argtypes = [C.POINTER(HitsParams)]
+    L.pt_hits_default_params.restype = None
+    L.pt_trace_hits.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(HitsParams), C.c_void_p]
+    L.pt_trace_hits_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(HitsParams), C.c_void_p, C.c_void_p]
+    L.pt_debug_trace_hits_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(HitsParams), C.c_void_p]
+    L.pt_debug_trace_hits_host.restype = C.c_int64
     L.pt_closest_point.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     L.pt_closest_point_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     L.pt_debug_closest_point_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
@@ -486,6 +500,17 @@ def aov_default_params(**changes):
         if k not in dict(AovParams._fields_):
             raise KeyError(k)
         setattr(p, k, v)
+    return p
+
+
+def hits_params(k=None):
+    """The pt_hits_params of a call: k None = pt_hits_default_params (K = 4), an int = that K, a HitsParams = itself."""
+    if isinstance(k, HitsParams):
+        return k
+    p = HitsParams()
+    lib().pt_hits_default_params(C.byref(p))
+    if k is not None:
+        p.max_hits = int(k)
     return p
 
 
@@ -1133,6 +1158,28 @@ class Context:
         """pt_trace_ao_device: asynchronous as trace_closest_device, n pt_ao_hit records (32 bytes each) left at d_out (16-byte aligned)."""
         self._check(lib().pt_trace_ao_device(self._h, C.c_void_p(d_rays), int(n), C.byref(params) if params is not None else None, C.c_void_p(d_out),
                                              C.c_void_p(stream) if stream else None), "pt_trace_ao_device")
+
+    def _trace_hits(self, fn, what, rays, k):
+        r = _rays(rays)
+        p = hits_params(k)
+        out = np.empty((r.shape[0], min(max(int(p.max_hits), 0), PT_HITS_MAX)), HIT_DTYPE)  # (a K the call refuses: no room is needed)
+        rc = fn(self._h, r.ctypes.data_as(C.c_void_p), r.shape[0], C.byref(p), out.ctypes.data_as(C.c_void_p))
+        self._check(int(rc), what)
+        return out
+
+    def trace_hits(self, rays, k=None):
+        """pt_trace_hits: the first K triangles along every ray in (t, id) order as an (n, K) HIT_DTYPE array; entries behind the last
+        hit are misses {0, 0, 0, -1}.  k: the K (1..PT_HITS_MAX), None = the default 4, or a HitsParams (include/mi355pt.h "the first K hits")."""
+        return self._trace_hits(lib().pt_trace_hits, "pt_trace_hits", rays, k)
+
+    def trace_hits_host(self, rays, k=None):
+        """pt_debug_trace_hits_host, the CPU twin of trace_hits (works on a host-only context)."""
+        return self._trace_hits(lib().pt_debug_trace_hits_host, "pt_debug_trace_hits_host", rays, k)
+
+    def trace_hits_device(self, d_rays, n, d_out, k=None, stream=None):
+        """pt_trace_hits_device: asynchronous as trace_closest_device, n * K pt_ray_hit records left at d_out (16-byte aligned)."""
+        self._check(lib().pt_trace_hits_device(self._h, C.c_void_p(d_rays), int(n), C.byref(hits_params(k)), C.c_void_p(d_out),
+                                               C.c_void_p(stream) if stream else None), "pt_trace_hits_device")
 
     def _points(self, fn, what, points):
         p = _points(points)
